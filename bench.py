@@ -18,8 +18,11 @@ per-frame re-layout).
 
 N > 1: the north-star partition -- ONE volume split into Z-slabs over the ranks (strong scaling: `value` = frames of the one
 volume per second), halo tile layers recomputed locally (default) or RCCL all-gathered, nearest-hit gather of one 32-byte record
-per hit ray to rank 0 (rgbd-recon_amd/multigpu.py).  Before anything is timed rank 0 checks the composite of both frames
-against an unpartitioned context, bit for bit, and the run fails if they differ.
+per hit ray to rank 0 (rgbd-recon_amd/multigpu.py).  With --full, before anything is timed rank 0 checks the composite of both
+frames against an unpartitioned context, bit for bit, and the run fails if they differ.
+
+A plain run sets up, warms up, times --steps frames and prints the line; --full adds every other measurement and check (see
+--help).  --dump-outputs DIR writes what the last timed frame computed, for output-for-output comparison of two builds.
 
 Prints ONE JSON line on rank 0.
 """
@@ -50,6 +53,7 @@ LUT = 128
 LIMIT = 0.01
 HBM_PEAK_GBS = 8000.0        # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 TRAFFIC_JSON = os.path.join(ROOT, "profiles", "traffic.json")   # per-kernel HBM bytes from separate rocprofv3 --pmc passes
+WARMUP_S = 1.0                # least wall time of frames before anything is timed, on top of the warm-up steps
 MOVED = dict(sphere_c=(0.4, 0.7, -0.3), box_c=(-0.5, 1.5, 0.2))  # frame B: both objects somewhere else (every tile churns)
 
 
@@ -136,6 +140,32 @@ def same(np, a, b):
     return bool(((a == b) | (np.isnan(a) & np.isnan(b))).all())
 
 
+DUMP_VOXELS = 1 << 21          # voxels in the --dump-outputs sample of the volume (8 MB)
+
+
+def dump_outputs(np, dirname, ctx, volume):
+    """--dump-outputs: what a caller of the frame receives after the last timed step -- the hole-filled framebuffer (colour RGBA,
+    depth) -- and, where the whole volume fits one download (<= 2^28 voxels), DUMP_VOXELS voxels of the TSDF at indices drawn with a
+    fixed seed (the same voxels for the same --config).
+
+    The path's results may hold non-finite values on purpose: the hole filling divides by the weight of the neighbours that pass its
+    colour and depth tests, which can be zero (0 / 0 = NaN, as in the reference's inpaint shader).  Every array is written as two
+    finite float32 .npy files: <name> with its non-finite entries set to 0, and <name>_nonfinite of the same shape, 0 where the
+    value is finite, 1 = NaN, 2 = +inf, 3 = -inf.  About 54 MB at the bench view."""
+    os.makedirs(dirname, exist_ok=True)
+    col, dep = ctx.framebuffer()
+    arrays = {"framebuffer_color": col, "framebuffer_depth": dep}
+    n_vox = ctx.res[0] * ctx.res[1] * ctx.res[2]
+    if volume and n_vox <= (1 << 28):
+        idx = np.unique(np.random.default_rng(20240607).integers(0, n_vox, min(n_vox, DUMP_VOXELS), dtype=np.int64))
+        arrays["tsdf_sample"] = ctx.tsdf().reshape(-1)[idx]
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, np.float32)
+        code = np.select([np.isnan(a), a == np.inf, a == -np.inf], [1.0, 2.0, 3.0], 0.0).astype(np.float32)
+        np.save(os.path.join(dirname, name + ".npy"), np.where(code == 0, a, np.float32(0)))
+        np.save(os.path.join(dirname, name + "_nonfinite.npy"), code)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -174,6 +204,15 @@ def main():
     ap.add_argument("--no-timers", action="store_true", help="leave the per-kernel HIP event timers off")
     ap.add_argument("--no-c1", action="store_true", help="skip the dense configs[1] kernel timings (`roofline_c1`)")
     ap.add_argument("--long-steps", type=int, default=1000, help="steps of the extra long pass reported as `long_run` (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the bit-for-bit checks before timing (lanes vs one stream, N > 1: slabs "
+                         "vs the whole volume), stage and kernel timers, rooflines, the spread windows, static / resident / three-lane / long / "
+                         "pre-processing / PCIe / replica rates, frame latency, c1 kernels and the CPU baseline.  Off: set up, warm up, time "
+                         "--steps frames, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed frame computed as DIR/<name>.npy (float32): the hole-filled "
+                         "framebuffer (colour, depth) and, single GPU with at most 2^28 voxels, a fixed seeded sample of the TSDF volume; "
+                         "non-finite entries are written as 0 and marked in DIR/<name>_nonfinite.npy (1 NaN, 2 +inf, 3 -inf)")
     args = ap.parse_args()
     if args.ingest:
         args.preprocess = True
@@ -354,7 +393,7 @@ def main():
     slab_check = None
     if alone_slab:
         slab_check = f"skipped: one slab ({alone_slab}, voxel planes {list(slab)}) alone is not the frame"
-    elif slabs_mode:
+    elif slabs_mode and args.full:
         ok = True
         got = []
         for k in range(nsc):
@@ -394,7 +433,7 @@ def main():
     # (tsdf_set_stage_overlap(0)) -- are fed the same 8 moving frames from the start; the lanes' frames are queued back to back with no read; after
     # frame 6 and after frame 7 volume, raymarch images and the hole-filled framebuffer must be equal bit for bit, or nothing is timed.
     lane_check = None
-    if world == 1 and not alone and args.frames_in_flight == 1 and (repack or raw_repack) and os.environ.get("RR_OVERLAP_FILL", "1") != "0":
+    if args.full and world == 1 and not alone and args.frames_in_flight == 1 and (repack or raw_repack) and os.environ.get("RR_OVERLAP_FILL", "1") != "0":
         def frame_on(b, i):
             if repack:
                 b.frame_dev(mv, pr, raw[i % nsc][1])
@@ -426,11 +465,13 @@ def main():
     hip.sync()
     if not repack and not raw_repack:
         hip.select_frame_slot(0)    # scene A's slot (the slab check above leaves the LAST slot current: uploading A there would overwrite frame B)
-    tu0 = time.perf_counter()
-    for _ in range(5):
-        hip.upload_frame(scene)
-    hip.sync()
-    upload_ms = (time.perf_counter() - tu0) / 5 * 1e3
+    upload_ms = None
+    if args.full:
+        tu0 = time.perf_counter()
+        for _ in range(5):
+            hip.upload_frame(scene)
+        hip.sync()
+        upload_ms = (time.perf_counter() - tu0) / 5 * 1e3
     warmup_effective = max(800, args.warmup)
     for i in range(args.warmup):
         step(drv, i)
@@ -440,6 +481,15 @@ def main():
     for i in range(max(0, 800 - args.warmup)):
         step(drv, i)
     barrier()
+    # ... then keep the device busy for another WARMUP_S seconds: a --full run spends longer than that on its checks and timer passes
+    # before its timed region, and a plain run must meet the device in the same steady state (one rank only: with N > 1 every rank
+    # would have to stop after the same number of frames, their steps hold collectives)
+    tw0 = time.perf_counter()
+    while world == 1 and time.perf_counter() - tw0 < WARMUP_S:
+        for i in range(100):
+            step(drv, i)
+        barrier()
+        warmup_effective += 100
 
     # Stage breakdown, OUTSIDE the timed region: every recorded HIP event costs a few microseconds of stream time, so the full set
     # of timers runs on its own short pass ...
@@ -452,7 +502,7 @@ def main():
     dom = None
     serial = None
     dom_ms_serial = None
-    if not args.no_timers:
+    if args.full and not args.no_timers:
         for d in every:
             d.b.set_stage_overlap(False)
         hip.set_timer_filter(None)
@@ -502,8 +552,11 @@ def main():
     t_issued = time.perf_counter() - t0                   # (the host's share: every call of the loop has returned; the device may still be working)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        last = slots[(args.steps - 1) % len(slots)].b    # the context that computed the last timed frame (rank 0: the composite when N > 1)
+        dump_outputs(np, args.dump_outputs, last, volume=world == 1 and not alone)
     dom_ms_insitu = None
-    if not args.no_timers:                                # the dominant kernel in situ (beside the other lanes' kernels), a pass of its own
+    if args.full and not args.no_timers:                  # the dominant kernel in situ (beside the other lanes' kernels), a pass of its own
         if dom:                                           # (every rank runs the loop -- its steps hold collectives --, whether it times a kernel or not)
             hip.timer_stats(dom)                          # (drops the serial pass's samples)
         stride = max(1, args.steps // 200)
@@ -537,13 +590,15 @@ def main():
         return max_over_ranks(time.perf_counter() - t)
 
     # the spread of `value`: four more windows of --steps frames of the same loop (a 20-step window is a 2.5 ms sample)
-    spread = [args.steps / dt] + [args.steps / timed(args.steps, lambda i: step(slots[i % len(slots)], i // len(slots) if len(slots) > 1 else i)) for _ in range(4)]
-    value_spread = {"windows": 5, "min": min(spread), "median": sorted(spread)[2], "max": max(spread),
-                    "note": "frames/s of the timed region and of four more windows of --steps frames right after it"}
+    value_spread = None
+    if args.full:
+        spread = [args.steps / dt] + [args.steps / timed(args.steps, lambda i: step(slots[i % len(slots)], i // len(slots) if len(slots) > 1 else i)) for _ in range(4)]
+        value_spread = {"windows": 5, "min": min(spread), "median": sorted(spread)[2], "max": max(spread),
+                        "note": "frames/s of the timed region and of four more windows of --steps frames right after it"}
     # the static scene (best case of the incremental bookkeeping: nothing churns), same number of steps
     static = None
     resident = None
-    if nsc > 1:
+    if args.full and nsc > 1:
         def st(i):
             drv.frame(mv, pr, new_frame=raw[0][1] if repack else (raw_dev[0][1] if raw_repack else None))
         if not repack and not raw_repack:
@@ -552,7 +607,7 @@ def main():
         ds = timed(args.steps, st)
         static = {"value": args.steps / ds, "ms_per_step": ds / args.steps * 1e3,
                   "note": "frame A arrives every step (re-laid out every time): no tile goes stale, the dirty-tile history is a no-op"}
-    if nsc > 1 and repack and not slabs_mode:
+    if args.full and nsc > 1 and repack and not slabs_mode:
         # rounds 1 / 2 defined `value` without the per-frame re-layout: two already re-laid-out frames in the two frame slots alternate
         # (a context of its own: explicit frame-slot calls switch a context's lane ahead off)
         rh = rr.ReconIntegrationHip(scene, res=cfg["res"], brick_size=brick, limit=LIMIT, view=VIEW, device=local, sparse_pool_tiles=args.sparse_pool)
@@ -577,7 +632,7 @@ def main():
                     "note": "two frames already in the kernels' layout alternate (tsdf_select_frame_slot; brick passes on the context's stream): the definition of `value` in rounds 1 and 2"}
     # the same loop without the integrate lane (RR_DEEP=0 at creation: integrate() on the context's stream, one volume -- three lanes)
     three_lanes = None
-    if nsc > 1 and repack and not slabs_mode and overlap and os.environ.get("RR_DEEP", "1") != "0":
+    if args.full and nsc > 1 and repack and not slabs_mode and overlap and os.environ.get("RR_DEEP", "1") != "0":
         th = make_ctx(sparse=args.sparse_pool, lane_flags=rr.LANES_NO_INTEGRATE_LANE)
         for i in range(300):
             th.frame_dev(mv, pr, raw[i % nsc][1])
@@ -591,13 +646,13 @@ def main():
         three_lanes = {"value": args.steps / dtl, "ms_per_step": dtl / args.steps * 1e3,
                        "note": "a context created with tsdf_config::lane_flags = TSDF_LANES_NO_INTEGRATE_LANE: lane ahead + the context's stream (integrate, march, shade) + fill lane, one volume"}
     long_run = None
-    if args.long_steps and args.frames_in_flight == 1:
+    if args.full and args.long_steps and args.frames_in_flight == 1:
         dl = timed(args.long_steps, lambda i: step(drv, i))
         long_run = {"steps": args.long_steps, "value": args.long_steps / dl, "ms_per_step": dl / args.long_steps * 1e3,
                     "note": "a second, longer pass of the same loop (the contract's timed region above is exactly --steps)"}
     # ---- the same loop from the RAW frames (f1, SURVEY.md section 8f: NetKinectArray::processTextures() in front of the path), an extra key, never `value`
     with_pre = None
-    if world == 1 and not alone and repack and args.frames_in_flight == 1 and not args.sparse_pool:
+    if args.full and world == 1 and not alone and repack and args.frames_in_flight == 1 and not args.sparse_pool:
         ph = make_ctx()
         ph.set_preprocess_calibration(scene)
         rd = []
@@ -673,7 +728,7 @@ def main():
     device_mem_bytes = int(mem_free_before - torch.cuda.mem_get_info(local)[0])
     # per-frame device time distribution (SURVEY.md section 8d asks for median and p95): one event pair per frame, own short pass
     frame_ms = None
-    if not args.no_timers:
+    if args.full and not args.no_timers:
         hip.timer_reserve("frame", 100)
         hip.set_timer_filter(["frame"])
         hip.enable_timers(True)
@@ -738,7 +793,7 @@ def main():
                          "exceeds ms_per_step a little): 0repack + bricks + 2integrate + 3recon = the frame; k_pair_masks / k_integrate_tiles lie inside 2integrate, "
                          "brickdraw / draw / k_march / holefill inside 3recon",
         "upload_ms_per_frame": upload_ms,
-        "pcie_inclusive_frames_per_s": 1e3 / (upload_ms + dt / args.steps * 1e3),
+        "pcie_inclusive_frames_per_s": 1e3 / (upload_ms + dt / args.steps * 1e3) if upload_ms is not None else None,
     }
     if slabs_mode:
         out["slab_check"] = slab_check
@@ -746,7 +801,7 @@ def main():
         out["overflowed_frames"] = drv.overflowed_frames   # frames composited from truncated record lists and not repaired: must be 0 (exit code below)
     # N > 1, an extra key, never `value`: what the same N GPUs deliver as N independent single-GPU frame streams (every frame rebuilds
     # the volume from scratch, so frames are independent units: no exchange at all, weak scaling by construction)
-    if world > 1:
+    if args.full and world > 1:
         rep = make_ctx()
         rdrv = mg.SlabDriver(rep, 0, 1, f"cuda:{local}", view=VIEW)
         for i in range(50):
@@ -818,7 +873,7 @@ def main():
                                              "traffic = FETCH_SIZE + WRITE_SIZE summed over the frame's kernels (separate --pmc passes on one stream, profiles/traffic.json; "
                                              "FETCH_SIZE counts half of a coalesced stream: traffic_if_streaming doubles it) -- below the algorithmic figure because the hole "
                                              "filling keeps to the dirty screen tiles while the formula counts every pixel of every level"}
-    if world > 1:
+    if args.full and world > 1:
         # N > 1: the same object for the slowest slab launch (every rank that owns a slab measures its own; counters -- `traffic` -- were
         # only collected on one GPU).  Only culled integrate launches: the units are the slab's active tiles (halo layers it recomputes included)
         mine = None
@@ -835,7 +890,7 @@ def main():
                                        f"{r['tiles']} active tiles in the timed frames (the halo layers it recomputes included); bytes as at N = 1 with the frame's valid depth pixels "
                                        "counted in full for every slab (an upper figure); other ranks: " + ", ".join(f"rank {q['rank']} {q['ms'] * 1e3:.1f} us / {q['alg'] / 1e6:.1f} MB" for q in allr if q is not r))
     # ---- the dense configuration (configs[1]): both kernels against the dense byte counts, in the same line
-    if world == 1 and not alone and not args.no_c1 and not args.no_timers and args.config != "c1" and args.frames_in_flight == 1:
+    if args.full and world == 1 and not alone and not args.no_c1 and not args.no_timers and args.config != "c1" and args.frames_in_flight == 1:
         c1 = CONFIGS["c1"]
         sc1 = scene if n_streams == c1["streams"] else rr.scene.make_scene(n_streams=c1["streams"], width=640, height=480, lut_res=LUT, inv_res=LUT)
         ext1 = sc1["bbox_max"] - sc1["bbox_min"]
@@ -897,7 +952,7 @@ def main():
                                  "one frame in flight; `value` above stays the HBM-resident rate"}
     # ---- PCIe-inclusive rate with the upload of frame f + 1 overlapping the compute of frame f (double-buffered frame slots,
     # pinned staging filled in place as the reference's reader thread fills the mapped PBO): never `value`
-    if world == 1 and not alone and not args.preprocess and args.frames_in_flight == 1:
+    if args.full and world == 1 and not alone and not args.preprocess and args.frames_in_flight == 1:
         with torch.cuda.stream(stream):
             for k in range(2):                            # both staging buffers hold a frame (the producer's job)
                 st_d, st_q, st_s, st_c = hip.frame_staging()
@@ -917,7 +972,7 @@ def main():
                 dto = (time.perf_counter() - t0) / ko
         out["pcie_overlapped"] = {"frames_per_s": 1.0 / dto, "ms_per_frame": dto * 1e3, "bytes_per_frame": int(scene["depth"].nbytes + scene["quality"].nbytes + scene["silhouette"].nbytes + scene["color"].nbytes),
                                   "note": "tsdf_upload_frame_async of the next frame (pinned staging -> copy stream -> other frame slot) overlapped with the compute of the current one"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(scene, cfg, LIMIT, brick)
     if rank == 0:
         sys.stdout.flush()

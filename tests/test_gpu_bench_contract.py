@@ -1,10 +1,12 @@
 """-m gpu: bench.py's output contract -- exactly one JSON line on stdout with the keys and types the driver reads, the
-`roofline` and `cpu_baseline` objects, and the library (not the oracle) as the thing that was measured."""
+`roofline` and `cpu_baseline` objects (--full), the library (not the oracle) as the thing that was measured, and the plain run's
+--dump-outputs arrays."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -18,7 +20,7 @@ def c_one(d):
 
 @pytest.mark.timeout(900)
 def test_bench_prints_one_json_line_with_the_contract_keys():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "3"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "3", "--full"],
                        cwd=ROOT, capture_output=True, text=True, timeout=800)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -59,6 +61,40 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     assert d["value"] > 100 * c["value"]                                        # the GPU line is not the oracle's
 
 
+@pytest.mark.timeout(600)
+def test_plain_bench_times_exactly_steps_and_dumps_the_last_frame(tmp_path):
+    """Without --full: the contract keys of the headline figure and nothing measured beside it; --dump-outputs writes the last
+    timed frame's framebuffer and a fixed sample of its volume as finite float32 arrays -- non-finite entries as 0 beside a code array
+    -- at most 64 MB, the same for the same arguments.  18 steps: the last timed frame is frame B, whose hole filling leaves NaN colours."""
+    outs = []
+    for k in range(2):
+        dump = tmp_path / f"run{k}"
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "18", "--warmup", "3", "--dump-outputs", str(dump)],
+                           cwd=ROOT, capture_output=True, text=True, timeout=500)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, p.stdout[:500]
+        d = json.loads(lines[0])
+        for k_, t in dict(metric=str, value=float, unit=str, ms_per_step=float, higher_is_better=bool, dtype=str).items():
+            assert isinstance(d[k_], t), (k_, d[k_])
+        assert d["steps"] == 18 and d["unit"] == "frames/s" and d["dtype"] == "f32" and d["higher_is_better"] is True
+        assert abs(d["value"] - 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"] and d["value"] > 30.0
+        assert "cpu_baseline" not in d and "roofline" not in d and d["long_run"] is None and d["static"] is None and d["stage_ms"] == {}
+        files = sorted(os.listdir(dump))
+        names = ["framebuffer_color", "framebuffer_depth", "tsdf_sample"]
+        assert files == sorted(f"{n}{s}.npy" for n in names for s in ("", "_nonfinite")), files
+        arrs = {f: np.load(dump / f) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values()) and sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        for n in names:
+            v, c = arrs[f"{n}.npy"], arrs[f"{n}_nonfinite.npy"]
+            assert v.shape == c.shape and np.isin(c, (0, 1, 2, 3)).all() and (v[c != 0] == 0).all(), n
+        assert arrs["framebuffer_color.npy"].shape == (720, 1280, 4) and int((arrs["framebuffer_depth.npy"] < 1).sum()) > 1000
+        assert arrs["tsdf_sample.npy"].size > 1000000 and (arrs["tsdf_sample_nonfinite.npy"] == 0).any()
+        outs.append(arrs)
+    for f in outs[0]:                                                            # same arguments, same inputs: the same frame, bit for bit
+        assert np.array_equal(outs[0][f], outs[1][f]), f
+
+
 @pytest.mark.timeout(1500)
 @pytest.mark.parametrize("world,extra,what", [(2, [], "1 Z-slab(s) on ranks 1..1 + rank 0 as dedicated compositor"),
                                               (3, [], "2 Z-slab(s) on ranks 1..2 + rank 0 as dedicated compositor"),
@@ -70,7 +106,7 @@ def test_bench_with_more_ranks_runs_the_slab_partition_by_default(world, extra, 
     device): everything else is the driver's command."""
     env = dict(os.environ, RR_BENCH_BACKEND="gloo", RR_BENCH_DEVICE="0")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1", "--master-port", str(29571 + world + len(extra)),
-                        os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "10", "--warmup", "2", "--long-steps", "0"] + extra,
+                        os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "10", "--warmup", "2", "--long-steps", "0", "--full"] + extra,
                        cwd=ROOT, capture_output=True, text=True, timeout=1400, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip().startswith("{")]

@@ -1,19 +1,19 @@
 """The host matrix block of ReconIntegration::draw() (recon_integration.cpp:66-72,182-205) against the REFERENCE's own
 matrix libraries: oracle/_ref/ref_view_math is compiled from external/gloost/{Matrix,Vector3,Point3,Ray}.cpp and the vendored
-glm where they lie under /root/reference (oracle/ref/Makefile; built by __graft_entry__.build(), travels to the GPU box).
+glm where they lie in the reference tree (oracle/ref/Makefile, run by __graft_entry__.build() where that tree exists; elsewhere the
+tool's recorded answers, tests/ref_tools.py).
 
 The reference forms these matrices in fp32 (gloost Gauss-Jordan inverse, glm cofactor inverse); the library and the oracle form
 them in double and round once, so agreement is to fp32 rounding of the reference's own arithmetic -- the tolerance below is
 relative to the largest element of each matrix; the library and the oracle agree to the last fp32 bit or two."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
+import ref_tools
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOOL = os.path.join(ROOT, "oracle", "_ref", "ref_view_math")
-needs_ref = pytest.mark.skipif(not os.path.exists(TOOL), reason="oracle/_ref not built (needs /root/reference: __graft_entry__.build())")
 
 BBOX = (np.array([-1.0, 0.0, -1.0], np.float32), np.array([1.0, 2.2, 1.0], np.float32))      # kinect_client.cpp:206-207
 
@@ -34,7 +34,7 @@ def views(rr):
 
 def reference(mv, pr, view, bbox):
     args = [TOOL] + ["%.9g" % v for v in np.concatenate([mv, pr])] + [str(view[0]), str(view[1])] + ["%.9g" % v for v in np.concatenate(bbox)]
-    v = np.array(subprocess.run(args, check=True, capture_output=True, text=True).stdout.split(), np.float64)
+    v = np.array(ref_tools.check_output(args).decode().split(), np.float64)
     assert v.size == 51
     return {"vol_to_world": v[:16], "image_to_eye": v[16:32], "normal_matrix": v[32:48], "camera_pos": v[48:]}
 
@@ -44,7 +44,6 @@ def close(a, b, rel):
     return np.max(np.abs(a - b)) <= rel * max(np.max(np.abs(b)), 1e-30)
 
 
-@needs_ref
 def test_library_matrices_match_the_reference_libraries(rr):
     for name, view, mv, pr in views(rr):
         ref = reference(mv, pr, view, BBOX)
@@ -55,7 +54,6 @@ def test_library_matrices_match_the_reference_libraries(rr):
         assert close(got["camera_pos"], ref["camera_pos"], 1e-6), name
 
 
-@needs_ref
 def test_oracle_matrices_match_the_reference_libraries(rr):
     from oracle.oracle import OracleRecon
     sc = rr.scene.make_scene(n_streams=1, width=32, height=24, lut_res=8, inv_res=8)

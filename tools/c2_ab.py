@@ -5,7 +5,7 @@ for lib in sys.argv[1:]:
     env = dict(os.environ)
     if lib != "default":
         env["RGBDR_LIB"] = os.path.abspath(lib)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-c1", "--long-steps", "0", "--steps", "300"], env=env, capture_output=True, text=True)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-c1", "--long-steps", "0", "--steps", "300"], env=env, capture_output=True, text=True)
     try:
         d = json.loads(p.stdout.strip().splitlines()[-1])
         print(lib, "moving", round(d["value"], 1), "static", round(d["static"]["value"], 1), {k: round(v * 1e3, 1) for k, v in d["stage_ms"].items()}, flush=True)

@@ -1,9 +1,9 @@
 #!/bin/bash
-# tools/collect_profiles.sh TAG NAME : copy what tools/profile_round.sh TAG left under gpurun_out/TAG into profiles/NAME_* and regenerate profiles/traffic.json
+# tools/collect_profiles.sh TAG NAME : copy what tools/profile_round.sh TAG left under bench_out/TAG (or $OUT/TAG) into profiles/NAME_* and regenerate profiles/traffic.json
 set -e
 TAG=$1; NAME=$2
 R=$(cd "$(dirname "$0")/.." && pwd)
-G=$R/gpurun_out/$TAG
+G=${OUT:-$R/bench_out}/$TAG
 find_stats() { find $G/$1 -name '*kernel_stats.csv' | head -n 1; }
 # the kernel stats the roofline figures agree with: one stream (RR_OVERLAP_FILL=0); the run with all lanes (as shipped) beside them
 cp $(find_stats c2_serial) $R/profiles/${NAME}_c2_kernel_stats.csv

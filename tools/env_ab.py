@@ -9,7 +9,7 @@ for var in sys.argv[2:]:
     for kv in var.split():
         k, v = kv.split("=", 1)
         env[k] = v
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", config, "--no-cpu-baseline", "--no-c1", "--long-steps", "0", "--steps", steps] + os.environ.get("AB_ARGS", "").split(),
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", config, "--no-cpu-baseline", "--no-c1", "--long-steps", "0", "--steps", steps] + os.environ.get("AB_ARGS", "").split(),
                        env=env, capture_output=True, text=True)
     try:
         d = json.loads(p.stdout.strip().splitlines()[-1])
