@@ -177,6 +177,19 @@ int32_t tsdf_draw_points(tsdf_ctx* ctx, const float modelview[16], const float p
  * (default 0.0125, KinectCalibrationFile.cpp:96).  Result: tsdf_download_framebuffer. */
 int32_t tsdf_set_min_length(tsdf_ctx* ctx, float min_length);
 int32_t tsdf_draw_trigrid(tsdf_ctx* ctx, const float modelview[16], const float projection[16]);
+/* kinect::ReconMVT::draw(), framework/reconstruction/recon_mvt.cpp:84-150 + glsl/mvt_accum.{vs,gs,fs}, trigrid_normalize.fs: the
+ * client's "Trigrid orig" mode (source/kinect_client.cpp:249-253).  Trigrid's passes, but every grid vertex reads the RAW depth of the
+ * last raw upload (tsdf_upload_raw_frame / _dev / tsdf_upload_wire_frame; metres, NetKinectArray.cpp:173,191 -- the 8-bit compressed raw
+ * array of :170 is not reproduced) through a 13 x 13 bilateral filter (mvt_accum.vs:43-115, depth limits the constants 0.5 / 4.5 m of
+ * recon_mvt.cpp:35-36), validSurface rejects depths < 0.5 m and edges >= min_length * avg_depth + 0.005 (mvt_accum.gs:29-41), fragment
+ * quality = lateral_quality / depth (mvt_accum.fs:53).  tsdf_process_textures is not needed and tsdf_set_preprocess does not matter.
+ * View size, viewport offset, colour mask, min_length (tsdf_set_min_length) and timers ("mvt") as for tsdf_draw_trigrid.
+ * Result: tsdf_download_framebuffer.  TSDF_ERR_STATE without a raw frame. */
+int32_t tsdf_draw_mvt(tsdf_ctx* ctx, const float modelview[16], const float projection[16]);
+/* The last tsdf_draw_mvt's vertex stage (inspection, like tsdf_download_preprocessed): out [N][W+1][H+1][2] = (filtered depth in metres,
+ * lateral quality) of grid vertex (gx, gy), gx in [0, H], gy in [0, W] at u = (gx + 0.5) / W, v = (gy + 0.5) / H (the swapped loop bounds
+ * of recon_mvt.cpp:53-54).  TSDF_ERR_STATE before the first MVT draw. */
+int32_t tsdf_download_mvt_vertices(tsdf_ctx* ctx, float* out);
 
 /* ---- draw() host matrices.  Host only, no context, no GPU: the matrix block ReconIntegration::draw()
  * builds before the raymarch -- vol_to_world = translate(bbox_min) * scale(bbox extent) (recon_integration.cpp:66-72),

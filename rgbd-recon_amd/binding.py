@@ -386,6 +386,17 @@ class ReconIntegrationHip:
     def drawTrigrid(self, mv, proj):
         self._ck(self._L.tsdf_draw_trigrid(self._c, _fp(_f32(mv)), _fp(_f32(proj))))
 
+    # kinect::ReconMVT (recon_mvt.cpp): the triangle grid from the raw depth, bilateral-filtered per grid vertex
+    def drawMVT(self, mv, proj):
+        self._ck(self._L.tsdf_draw_mvt(self._c, _fp(_f32(mv)), _fp(_f32(proj))))
+
+    def mvt_vertices(self):
+        """the last drawMVT's vertex stage: [N][W+1][H+1][2] (filtered depth in metres, lateral quality) of grid vertex (gx, gy) at [l][gy][gx]"""
+        h, w, _, _ = self._dims
+        out = np.zeros((self.n, w + 1, h + 1, 2), np.float32)
+        self._ck(self._L.tsdf_download_mvt_vertices(self._c, _fp(out)))
+        return out
+
     def fillColors(self): self._ck(self._L.tsdf_fill_colors(self._c))
     def drawF(self, mv, proj): self._ck(self._L.tsdf_draw_f(self._c, _fp(_f32(mv)), _fp(_f32(proj))))
 

@@ -816,6 +816,8 @@ int32_t tsdf_destroy(tsdf_ctx* c) {
   if (c->pre_gate_b) hipEventDestroy(c->pre_gate_b);
   if (c->src_ready) hipEventDestroy(c->src_ready);
   if (c->normals_read) hipEventDestroy(c->normals_read);
+  if (c->raw_read) hipEventDestroy(c->raw_read);
+  hipFree(c->d_mvt_vtx);
   if (c->fill_worker) {
     c->fill_worker->stop.store(true);
     { std::lock_guard<std::mutex> lk(c->fill_worker->m); }
@@ -1115,6 +1117,13 @@ static int32_t ensure_pre_buffers(tsdf_ctx* c) {
   }
   return TSDF_OK;
 }
+// an MVT draw still queued on the context's stream reads d_raw: a raw upload that rewrites it on the lane ahead waits for that draw
+static int32_t wait_raw_read(tsdf_ctx* c, hipStream_t lane) {
+  if (!c->raw_read_pending) return TSDF_OK;
+  if (lane != c->stream) HIP_TRY(c, hipStreamWaitEvent(lane, c->raw_read, 0));
+  c->raw_read_pending = false;
+  return TSDF_OK;
+}
 // The raw frame (NetKinectArray::update(): depth + colour of every sensor) goes through the lane ahead like a pre-processed one does (round 4): its
 // colour is re-laid out into the frame slot the lane writes, its depth is what tsdf_process_textures() -- on the same lane -- starts from.
 int32_t tsdf_upload_raw_frame(tsdf_ctx* c, const float* depth_raw, const uint8_t* colour) {
@@ -1124,6 +1133,7 @@ int32_t tsdf_upload_raw_frame(tsdf_ctx* c, const float* depth_raw, const uint8_t
   if (int32_t rc = ensure_pre_buffers(c)) return rc;
   const hipStream_t lane = pre_enter(c);
   if (int32_t rc = begin_slot_write(c, lane, false)) return rc;
+  if (int32_t rc = wait_raw_read(c, lane)) return rc;
   const FrameImages& F = c->frame;
   const size_t np = (size_t)c->cfg.num_streams * F.w * F.h, nc = (size_t)c->cfg.num_streams * F.cw * F.ch;
   HIP_TRY(c, hipMemcpyAsync(c->d_raw, depth_raw, np * sizeof(float), hipMemcpyHostToDevice, lane));
@@ -1228,6 +1238,7 @@ int32_t tsdf_upload_wire_frame(tsdf_ctx* c, const void* message, uint64_t bytes,
   if (timestamp) memcpy(timestamp, c->h_wire[k], sizeof(double));        // the first 8 bytes of the message, :510
   const hipStream_t lane = pre_enter(c);                                 // (round 4) the lane ahead: copy, unpack / DXT decode and the passes that follow
   if (int32_t rc = begin_slot_write(c, lane, false)) return rc;
+  if (int32_t rc = wait_raw_read(c, lane)) return rc;
   HIP_TRY(c, hipMemcpyAsync(c->d_wire, c->h_wire[k], want, hipMemcpyHostToDevice, lane));
   HIP_TRY(c, hipEventRecord(c->wire_done[k], lane));
   c->wire_pending[k] = true;
@@ -1738,6 +1749,51 @@ int32_t tsdf_draw_trigrid(tsdf_ctx* c, const float* mv, const float* pr) {
   launch_draw_trigrid(c->stream, P, Q, c->luts, c->frame, c->min_length, c->d_tri_z, c->d_tri_acc, c->d_fb_c, c->d_fb_d);
   timer_end(c, "trigrid");
   HIP_TRY(c, hipGetLastError());
+  return TSDF_OK;
+}
+// kinect::ReconMVT (recon_mvt.cpp): Trigrid's draw() from the raw depth, bilateral-filtered per grid vertex
+int32_t tsdf_draw_mvt(tsdf_ctx* c, const float* mv, const float* pr) {
+  CHECK_CTX(c);
+  if (!mv || !pr) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "null matrix");
+  if (!c->have_raw) FAIL(c, TSDF_ERR_STATE, "no raw frame uploaded (tsdf_upload_raw_frame / tsdf_upload_raw_frame_dev / tsdf_upload_wire_frame)");
+  for (uint32_t i = 0; i < c->cfg.num_streams; ++i) {
+    if (!c->have_calib[i] || !c->luts.s[i].xyz || !c->luts.s[i].uv) FAIL(c, TSDF_ERR_STATE, "stream %u needs cv_xyz and cv_uv (tsdf_set_calibration)", i);
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  ViewParams P;
+  if (!make_view_params(c, mv, pr, &P)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "singular modelview / projection matrix");
+  PointParams Q{};
+  double mvd[16], prd[16], pm[16];
+  for (int i = 0; i < 16; ++i) { mvd[i] = mv[i]; prd[i] = pr[i]; }
+  mat_mul_d(prd, mvd, pm);
+  for (int i = 0; i < 16; ++i) Q.pmv.m[i] = (float)pm[i];
+  for (int a = 0; a < 3; ++a) { Q.bbox_min[a] = c->cfg.bbox_min[a]; Q.bbox_max[a] = c->cfg.bbox_max[a]; }
+  const size_t nv = (size_t)c->vw * c->vh;
+  if (!c->d_tri_z) { HIP_TRY(c, hipMalloc(&c->d_tri_z, nv * sizeof(uint32_t))); HIP_TRY(c, hipMalloc(&c->d_tri_acc, nv * sizeof(float4))); }
+  if (!c->d_mvt_vtx) HIP_TRY(c, hipMalloc(&c->d_mvt_vtx, (size_t)c->cfg.num_streams * (c->frame.w + 1) * (c->frame.h + 1) * sizeof(float2)));
+  if (int32_t rc = flush_pending_colour(c)) return rc;                   // the slot colour of a raw frame nobody has processed yet
+  HIP_TRY(c, join_pre(c));
+  timer_begin(c, "mvt");
+  HIP_TRY(c, join_fill(c));
+  c->fb_consistent = false;
+  launch_draw_mvt(c->stream, P, Q, c->luts, c->frame, c->raw_src, c->min_length, c->d_mvt_vtx, c->d_tri_z, c->d_tri_acc, c->d_fb_c, c->d_fb_d);
+  timer_end(c, "mvt");
+  HIP_TRY(c, hipGetLastError());
+  c->have_mvt = true;
+  if (pipelined(c)) {                                                    // the next raw upload on the lane ahead rewrites d_raw
+    if (!c->raw_read) HIP_TRY(c, hipEventCreateWithFlags(&c->raw_read, hipEventDisableTiming));
+    HIP_TRY(c, hipEventRecord(c->raw_read, c->stream));
+    c->raw_read_pending = true;
+  }
+  return TSDF_OK;
+}
+int32_t tsdf_download_mvt_vertices(tsdf_ctx* c, float* out) {
+  CHECK_CTX(c);
+  if (!out) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "null output");
+  if (!c->have_mvt) FAIL(c, TSDF_ERR_STATE, "no MVT draw yet (tsdf_draw_mvt)");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, sync_ctx(c));
+  HIP_TRY(c, hipMemcpy(out, c->d_mvt_vtx, (size_t)c->cfg.num_streams * (c->frame.w + 1) * (c->frame.h + 1) * sizeof(float2), hipMemcpyDeviceToHost));
   return TSDF_OK;
 }
 int32_t tsdf_raymarch(tsdf_ctx* c, const float* mv, const float* pr) {

@@ -110,6 +110,8 @@ struct tsdf_ctx {
   // whether the masks of the latest draw may be trusted / the framebuffer holds the background outside them
   uint8_t* d_fill_mask[2]{}; uint8_t* d_lvl_mask[2]{}; bool draw_masks_valid = false, fb_consistent = false, fill_tiles = true; uint64_t n_fills = 0, n_fills_by_tiles = 0;
   uint32_t* d_tri_z = nullptr; float4* d_tri_acc = nullptr; float min_length = 0.0125f;   // triangle-grid back-end; KinectCalibrationFile.cpp:96 default
+  float2* d_mvt_vtx = nullptr; bool have_mvt = false;   // MVT back-end: the last draw's vertex stage, [N][W+1][H+1] (filtered depth m, lateral quality)
+  hipEvent_t raw_read = nullptr; bool raw_read_pending = false;   // recorded behind an MVT draw: the next raw upload on the lane ahead rewrites d_raw
   bool use_tile_history = true;   // RR_IMAGE_TILES=0 turns it off (A/B)
   bool peels_cleared = false;     // integrate() already reset the peel tiles the coming draw would reset (part C of k_classify_lists)
   uint32_t* d_pair_masks = nullptr;   // per work item of the integrate launch: this frame's (tile, stream) pair classes (k_pair_masks)

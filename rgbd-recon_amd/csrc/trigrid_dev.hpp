@@ -1,0 +1,140 @@
+// Device helpers of the two triangle-grid back-ends: kinect::ReconTrigrid (k_trigrid.hip, glsl/trigrid_accum.{vs,gs,fs}) and
+// kinect::ReconMVT (k_mvt.hip, glsl/mvt_accum.{vs,gs,fs}).  The two share the host code (recon_trigrid.cpp / recon_mvt.cpp differ in
+// their uniforms only), the rasteriser and the fragment tests; they differ in where a vertex's depth comes from, in validSurface and in
+// the fragment's quality (kMvt below).  Coverage, interpolation and every test are the oracle's expressions in the oracle's order.
+#ifndef RR_TRIGRID_DEV_HPP
+#define RR_TRIGRID_DEV_HPP
+#include "shading_dev.hpp"
+
+namespace rr {
+
+struct TriVert { float3 pos_cs, pos_es; float tcx, tcy, depth, quality, xw, yw, zw, iw; bool front; };
+struct TriSetup { TriVert v[3]; float3 normal; float area; bool ok; };
+struct TriFragment { float z, tcx, tcy, quality, depth; float3 pos_es, pos_cs; };
+
+__device__ __forceinline__ float len3(float3 a) { return sqrtf(a.x * a.x + a.y * a.y + a.z * a.z); }
+__device__ __forceinline__ float3 sub3(float3 a, float3 b) { return make_float3(a.x - b.x, a.y - b.y, a.z - b.z); }
+
+// vertex (gx, gy) of the grid (recon_trigrid.cpp:51-62 = recon_mvt.cpp:51-62): texel-centre position (u, v) in the depth image
+__device__ __forceinline__ float grid_u(int gx, int w) { const float step = 1.0f / (float)w; return (float)(((double)gx + 0.5) * (double)step); }
+
+// the vertex stage after the depth fetch: calibration-volume lookups at (u, v, lut_w), eye / clip / window position
+__device__ __forceinline__ TriVert tri_vertex_at(const ViewParams& P, const PointParams& Q, const StreamTable& T, int l, float u, float v, float lut_w,
+                                                 float depth, float quality) {
+  TriVert t;
+  t.depth = depth; t.quality = quality;
+  const StreamLut& L = T.s[l];
+  t.pos_cs = tex3d_rgba_xyz(L.xyz, L.xyz_res, u, v, lut_w);
+  const float2 tc = tex3d_rg(L.uv, L.uv_res, u, v, lut_w);
+  t.tcx = tc.x; t.tcy = tc.y;
+  const float4 pe = mat_mul(P.mv, t.pos_cs.x, t.pos_cs.y, t.pos_cs.z, 1.0f);
+  t.pos_es = make_float3(pe.x, pe.y, pe.z);
+  const float4 clip = mat_mul(Q.pmv, t.pos_cs.x, t.pos_cs.y, t.pos_cs.z, 1.0f);
+  t.front = clip.w > 0.0f;
+  t.iw = 1.0f / clip.w;
+  t.xw = (clip.x / clip.w * 0.5f + 0.5f) * (float)P.w;
+  t.yw = (clip.y / clip.w * 0.5f + 0.5f) * (float)P.h;
+  t.zw = clip.z / clip.w * 0.5f + 0.5f;
+  return t;
+}
+
+// validSurface + triangle set-up of the geometry stage.  Trigrid (trigrid_accum.gs:31-42): depth < 0 rejects, edges < min_length * avg * 4
+// (depth normalised to [0, 1]).  MVT (mvt_accum.gs:29-41): depth < 0.5 m rejects, edges < min_length * avg + 0.005 (depth in metres).
+template <bool kMvt>
+__device__ __forceinline__ TriSetup tri_setup(float min_length, const TriVert& a, const TriVert& b, const TriVert& d) {
+  TriSetup S; S.v[0] = a; S.v[1] = b; S.v[2] = d; S.ok = false;
+  const float dmin = kMvt ? 0.5f : 0.0f;
+  if (a.depth < dmin || b.depth < dmin || d.depth < dmin) return S;
+  const float avg = (a.depth + b.depth + d.depth) / 3.0f;
+  const float l = kMvt ? min_length * avg + 0.005f : min_length * avg * 4.0f;
+  if (!(len3(sub3(b.pos_cs, a.pos_cs)) < l && len3(sub3(d.pos_cs, a.pos_cs)) < l && len3(sub3(d.pos_cs, b.pos_cs)) < l)) return S;
+  if (!(a.front && b.front && d.front)) return S;
+  const float3 ea = sub3(b.pos_es, a.pos_es), eb = sub3(d.pos_es, a.pos_es);
+  S.normal = normalize3(make_float3(ea.y * eb.z - eb.y * ea.z, ea.z * eb.x - eb.z * ea.x, ea.x * eb.y - eb.x * ea.y));   // :59
+  S.area = (b.xw - a.xw) * (d.yw - a.yw) - (d.xw - a.xw) * (b.yw - a.yw);
+  if (!(S.area != 0.0f)) return S;
+  S.ok = true;
+  return S;
+}
+
+__device__ __forceinline__ bool tri_fragment(const TriSetup& S, int px, int py, TriFragment& f) {
+  const float x = (float)px + 0.5f, y = (float)py + 0.5f;
+  const TriVert &a = S.v[0], &b = S.v[1], &d = S.v[2];
+  const float e0 = (d.xw - b.xw) * (y - b.yw) - (d.yw - b.yw) * (x - b.xw);
+  const float e1 = (a.xw - d.xw) * (y - d.yw) - (a.yw - d.yw) * (x - d.xw);
+  const float e2 = (b.xw - a.xw) * (y - a.yw) - (b.yw - a.yw) * (x - a.xw);
+  const float sgn = S.area > 0.0f ? 1.0f : -1.0f;
+  const float ex[3] = {(d.xw - b.xw) * sgn, (a.xw - d.xw) * sgn, (b.xw - a.xw) * sgn}, ey[3] = {(d.yw - b.yw) * sgn, (a.yw - d.yw) * sgn, (b.yw - a.yw) * sgn};
+  const float ee[3] = {e0 * sgn, e1 * sgn, e2 * sgn};
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    if (ee[i] < 0.0f) return false;
+    if (ee[i] == 0.0f && !(ey[i] > 0.0f || (ey[i] == 0.0f && ex[i] < 0.0f))) return false;
+    if (!(ee[i] >= 0.0f)) return false;
+  }
+  const float l0 = e0 / S.area, l1 = e1 / S.area, l2 = e2 / S.area;
+  f.z = l0 * a.zw + l1 * b.zw + l2 * d.zw;
+  if (!(f.z >= 0.0f && f.z <= 1.0f)) return false;
+  const float w0 = l0 * a.iw, w1 = l1 * b.iw, w2 = l2 * d.iw, iw = w0 + w1 + w2;
+#define RR_IP(p, q, r) ((w0 * (p) + w1 * (q) + w2 * (r)) / iw)
+  f.tcx = RR_IP(a.tcx, b.tcx, d.tcx); f.tcy = RR_IP(a.tcy, b.tcy, d.tcy); f.quality = RR_IP(a.quality, b.quality, d.quality);
+  f.depth = RR_IP(a.depth, b.depth, d.depth);                            // (read by MVT only)
+  f.pos_es = make_float3(RR_IP(a.pos_es.x, b.pos_es.x, d.pos_es.x), RR_IP(a.pos_es.y, b.pos_es.y, d.pos_es.y), RR_IP(a.pos_es.z, b.pos_es.z, d.pos_es.z));
+  f.pos_cs = make_float3(RR_IP(a.pos_cs.x, b.pos_cs.x, d.pos_cs.x), RR_IP(a.pos_cs.y, b.pos_cs.y, d.pos_cs.y), RR_IP(a.pos_cs.z, b.pos_cs.z, d.pos_cs.z));
+#undef RR_IP
+  return true;
+}
+
+__device__ __forceinline__ bool tri_fragment_kept(const PointParams& Q, const TriSetup& S, const TriFragment& f, float3& n) {   // trigrid_accum.fs:44-62 = mvt_accum.fs:35-50
+  const bool in_box = f.pos_cs.x >= Q.bbox_min[0] && f.pos_cs.y >= Q.bbox_min[1] && f.pos_cs.z >= Q.bbox_min[2] &&
+                      f.pos_cs.x <= Q.bbox_max[0] && f.pos_cs.y <= Q.bbox_max[1] && f.pos_cs.z <= Q.bbox_max[2];
+  if (!in_box) return false;
+  if (f.tcx > 0.99f || f.tcx < 0.01f || f.tcy > 0.99f || f.tcy < 0.01f) return false;
+  const float3 nn = normalize3(S.normal);
+  n = make_float3(-nn.x, -nn.y, -nn.z);
+  const float3 pe = normalize3(f.pos_es);
+  if (n.x * pe.x + n.y * pe.y + n.z * pe.z > 0.0f) return false;
+  return true;
+}
+
+// The two triangles of one cell (recon_trigrid.cpp:55-61), rasterised into the z pre-pass (kStage 0) or the blend (kStage 1).
+// Fragment quality: Trigrid the interpolated quality; MVT lateral_quality / depth, both interpolated (mvt_accum.fs:53).
+template <int kStage, bool kMvt>
+__device__ __forceinline__ void tri_cell(const ViewParams& P, const PointParams& Q, const FrameImages& F, float min_length, int l, const TriVert& v00,
+                                         const TriVert& v10, const TriVert& v01, const TriVert& v11, uint32_t* __restrict__ zbuf, float* __restrict__ acc) {
+#pragma unroll 1
+  for (int t = 0; t < 2; ++t) {
+    const TriSetup S = t == 0 ? tri_setup<kMvt>(min_length, v00, v10, v01) : tri_setup<kMvt>(min_length, v10, v11, v01);
+    if (!S.ok) continue;
+    const float minx = fminf(fminf(S.v[0].xw, S.v[1].xw), S.v[2].xw), maxx = fmaxf(fmaxf(S.v[0].xw, S.v[1].xw), S.v[2].xw);
+    const float miny = fminf(fminf(S.v[0].yw, S.v[1].yw), S.v[2].yw), maxy = fmaxf(fmaxf(S.v[0].yw, S.v[1].yw), S.v[2].yw);
+    if (!(maxx >= 0.0f && maxy >= 0.0f && minx <= (float)P.w && miny <= (float)P.h)) continue;
+    const int x0 = (int)fmaxf(floorf(minx - 0.5f), 0.0f), x1 = (int)fminf(ceilf(maxx - 0.5f), (float)(P.w - 1));
+    const int y0 = (int)fmaxf(floorf(miny - 0.5f), 0.0f), y1 = (int)fminf(ceilf(maxy - 0.5f), (float)(P.h - 1));
+    for (int py = y0; py <= y1; ++py)
+      for (int px = x0; px <= x1; ++px) {
+        TriFragment f;
+        if (!tri_fragment(S, px, py, f)) continue;
+        float3 n;
+        if (!tri_fragment_kept(Q, S, f, n)) continue;
+        const size_t o = (size_t)py * P.w + px;
+        if (kStage == 0) {
+          atomicMin(&zbuf[o], __float_as_uint(f.z));                     // GL_LESS
+        } else {
+          const float depth_curr = __uint_as_float(zbuf[o]);
+          const float4 pc = mat_mul(P.img_to_eye, ((float)px + 0.5f) + 0.5f, ((float)py + 0.5f) + 0.5f, depth_curr, 1.0f);   // sic, trigrid_accum.fs:69
+          const float3 es = make_float3(pc.x / pc.w, pc.y / pc.w, pc.z / pc.w);
+          if (0.075f < len3(sub3(es, f.pos_es))) continue;               // epsilon, recon_trigrid.cpp:35
+          const float q = kMvt ? f.quality / f.depth : f.quality;
+          float3 col;
+          if (P.shade_mode == 3) col = make_float3(c_camera_colors[l & 7][0], c_camera_colors[l & 7][1], c_camera_colors[l & 7][2]);
+          else col = shade(P, f.pos_es, n, color_bilinear(F, l, f.tcx, f.tcy));
+          atomicAdd(&acc[4 * o], col.x * q); atomicAdd(&acc[4 * o + 1], col.y * q);
+          atomicAdd(&acc[4 * o + 2], col.z * q); atomicAdd(&acc[4 * o + 3], q);
+        }
+      }
+  }
+}
+
+}  // namespace rr
+#endif

@@ -184,6 +184,11 @@ void launch_draw_points(hipStream_t st, const ViewParams& P, const PointParams& 
 
 void launch_draw_trigrid(hipStream_t st, const ViewParams& P, const PointParams& Q, const StreamTable& T, const FrameImages& F, float min_length, uint32_t* zbuf,
                          float4* acc, float4* fb_c, float* fb_d);
+void launch_tri_clear(hipStream_t st, uint32_t* zbuf, float4* acc, int n);                                       // (k_trigrid.hip, shared with MVT)
+void launch_tri_normalize(hipStream_t st, const uint32_t* zbuf, const float4* acc, int n, float4* fb_c, float* fb_d);
+// MVT back-end (k_mvt.hip): raw depth [N][H][W] metres -> per-vertex (filtered depth, lateral quality) vtx [N][W+1][H+1] -> framebuffer
+void launch_draw_mvt(hipStream_t st, const ViewParams& P, const PointParams& Q, const StreamTable& T, const FrameImages& F, const float* raw, float min_length,
+                     float2* vtx, uint32_t* zbuf, float4* acc, float4* fb_c, float* fb_d);
 
 // inverse calibration volume builder (k_inverter.hip)
 struct InverterGrid {

@@ -145,6 +145,8 @@ class ReconIntegrationHip {
   // ---- kinect::ReconTrigrid::draw() (recon_trigrid.cpp:85-148)
   void setMinLength(float v) { check(tsdf_set_min_length(m_ctx, v)); }
   void drawTrigrid() { check(tsdf_draw_trigrid(m_ctx, m_mv, m_proj)); }
+  // ---- kinect::ReconMVT::draw() (recon_mvt.cpp:84-150): reads the raw frame of the last raw / wire upload
+  void drawMVT() { check(tsdf_draw_mvt(m_ctx, m_mv, m_proj)); }
   tsdf_ctx* handle() const { return m_ctx; }
 
  private:
