@@ -191,6 +191,52 @@ int32_t tsdf_draw_mvt(tsdf_ctx* ctx, const float modelview[16], const float proj
  * of recon_mvt.cpp:53-54).  TSDF_ERR_STATE before the first MVT draw. */
 int32_t tsdf_download_mvt_vertices(tsdf_ctx* ctx, float* out);
 
+/* ---- the overlays the client draws after drawF() in mono mode (source/kinect_client.cpp:672-683), each into the framebuffer as the
+ * previous draw left it (tsdf_download_framebuffer reads the result; tsdf_upload_framebuffer puts a known one under an overlay), depth
+ * func GL_LESS (:983-984), colour and depth written, no blending.  Pixels no fragment passes keep their colour and depth.
+ * TSDF_ERR_INVALID_ARGUMENT for a null or singular modelview / projection; TSDF_ERR_STATE with a colour-mask mode != 0 or a viewport
+ * origin / offset != 0 (the stereo modes draw no overlay).
+ *
+ * tsdf_draw_calibvis: "Draw TSDF" (g_draw_calibvis, :420, key V :791) = kinect::ReconCalibs::draw(), recon_calibs.cpp:54-61 with
+ *   glsl/calib_vis.{vs,fs}.  One point per cell of a grid of stream 0's inverse LUT resolution (CalibVolumes::getVolumeRes,
+ *   CalibVolumes.cpp:90-92, whatever the active sensor), point (x, y, z) at p = ((x + 0.5f) * (1.0f / res.x), ...) in fp32, drawn x fastest,
+ *   then y, then z (volume_sampler.cpp:33-45).  d = the TSDF of the latest integrate() at p (trilinear, CLAMP_TO_EDGE; calib_vis.vs:37);
+ *   gl_Position = P * (MV * (vol_to_world * (p, 1))), the products in that order (:29-38), vol_to_world = translate(bbox_min) *
+ *   scale(bbox_max - bbox_min) in fp32 (recon_calibs.cpp:38-45).  Colour (calib_vis.fs:17-30) with the static limit 0.01
+ *   (recon_calibs.cpp:20; not tsdf_set_tsdf_limit's value): inv = |d| / 0.01 (an IEEE division); d > 0 -> (1 - inv, 0, 0, 1), else
+ *   (0, 1 - inv, 0, 1); then d >= 0.01 -> (0, 0, 1, 1); d <= -0.01 -> discarded before the depth test.  Timer "calibvis".
+ *   TSDF_ERR_STATE without stream 0's cv_xyz_inv and on a Z-slab context (the overlay needs the whole volume).
+ * tsdf_set_active_kinect: ReconCalibs::setActiveKinect.  Validates the stream (TSDF_ERR_INVALID_ARGUMENT out of range) and changes no
+ *   output: the layer only selects the cv_xyz_inv / cv_xyz lookups of calib_vis.vs:26-27 / .fs:25, which feed nothing the output uses.
+ * tsdf_draw_frustums: "Draw frustums" (g_draw_frustums, key F :742) = CalibVolumes::drawFrustums() (CalibVolumes.cpp:214-218) ->
+ *   Frustum::draw() (frustum.cpp:45-95), stream after stream: 12 GL_LINES between the 8 corner samples of the stream's forward LUT
+ *   (getCornerPoints, CalibVolumes.cpp:98-113,122; captured by tsdf_set_calibration) in the order 0-4 1-5 2-6 3-7 0-1 1-2 2-3 3-0 4-5 5-6
+ *   6-7 7-4, colour (0, 1, 0, 1), width 1, aliased; then one point of size 3 at Frustum::getCameraPos() (the value of
+ *   tsdf_frustum_from_volume), colour (1, 0, 0, 1).  Positions are world coordinates through P * (MV * p).  Timer "frustums".
+ *   TSDF_ERR_STATE when a stream has no cv_xyz.
+ * tsdf_calibvis_stats: out[0] = grid points of the last tsdf_draw_calibvis, out[1] = of them removed whole by its empty-space test (blocks
+ *   whose trilinear taps lie in tiles that hold only the clear value -limit, when -limit <= -0.01: every such sample is discarded).
+ *
+ * What GL leaves open, defined here and restated by tests/overlay_reference.py (the kernels match it bit for bit; fp32 throughout, matrix
+ * products as sum_k m[k][row] * v[k] left to right, no contraction):
+ *   Points.  Whole-point clip: dropped unless clip.w > 0 and |x|, |y|, |z| <= clip.w; window x = (clip.x / clip.w * 0.5 + 0.5) * W (y alike),
+ *     z = clip.z / clip.w * 0.5 + 0.5, dropped unless z < 1.  A point of size s covers the pixels px in [ceil((x - s/2) - 0.5),
+ *     ceil((x + s/2) - 0.5) - 1] (rows alike) inside the view: s = 1 for the TSDF overlay (calib_vis.vs never writes gl_PointSize), 3 for the
+ *     camera point.
+ *   Lines (GL 4.4 section 14.5.1, diamond exit, width 1).  The segment is clipped in clip space against the near plane (z + w >= 0), then
+ *     the far plane (w - z >= 0): an end point e outside moves towards the other one o, to e + (o - e) * t with t = d_e / (d_e - d_o)
+ *     (d: the plane distances above); a line wholly outside either plane is dropped, as is one with an end point at w <= 0 after clipping.  With the window coordinates of start a and end b: if
+ *     |b.x - a.x| >= |b.y - a.y| (x-major) every pixel column i whose centre c = i + 0.5 lies in [a.x, b.x) along the direction of travel
+ *     (a.x <= c < b.x, or b.x < c <= a.x) makes one fragment in row floor(a.y + (b.y - a.y) * t), t = (c - a.x) / (b.x - a.x), with depth
+ *     a.z + (b.z - a.z) * t clamped to [0, 1]; y-major lines the same with rows.  Fragments outside the view are dropped.
+ *   Depth test.  A fragment passes only if z < the framebuffer's depth before the overlay (strict); among passing fragments of one pixel the
+ *     smallest (z bits, primitive index) wins -- GL_LESS with primitives drawn in order.  Primitive index: the grid's linear index
+ *     (x + res.x * (y + res.y * z)) for the TSDF overlay, stream * 13 + k for the frustums (k < 12 the lines in the order above, 12 the point). */
+int32_t tsdf_draw_calibvis(tsdf_ctx* ctx, const float modelview[16], const float projection[16]);
+int32_t tsdf_set_active_kinect(tsdf_ctx* ctx, uint32_t stream);
+int32_t tsdf_draw_frustums(tsdf_ctx* ctx, const float modelview[16], const float projection[16]);
+int32_t tsdf_calibvis_stats(tsdf_ctx* ctx, uint64_t out[2]);
+
 /* ---- draw() host matrices.  Host only, no context, no GPU: the matrix block ReconIntegration::draw()
  * builds before the raymarch -- vol_to_world = translate(bbox_min) * scale(bbox extent) (recon_integration.cpp:66-72),
  * image_to_eye = inverse(scale(w/2, h/2, 1/2) * translate(1,1,1) * projection) (:182-193), NormalMatrix =
@@ -337,6 +383,7 @@ int32_t tsdf_download_active_tiles(tsdf_ctx* ctx, uint32_t* ids, uint32_t capaci
 int32_t tsdf_download_image(tsdf_ctx* ctx, float* rgba, float* depth, float* nsamples, float* peels);
 int32_t tsdf_upload_image(tsdf_ctx* ctx, const float* rgba, const float* depth);
 int32_t tsdf_download_framebuffer(tsdf_ctx* ctx, float* rgba, float* depth);    /* output of fillColors */
+int32_t tsdf_upload_framebuffer(tsdf_ctx* ctx, const float* rgba, const float* depth);    /* its twin: a known framebuffer under an overlay (tests) */
 int32_t tsdf_download_atlas(tsdf_ctx* ctx, float* rgba, float* depth);          /* [h][1.5w] pyramid atlas */
 
 /* ---- multi-GPU hooks (one context per rank; the collective itself is the caller's: RCCL) ---------- */

@@ -397,6 +397,21 @@ class ReconIntegrationHip:
         self._ck(self._L.tsdf_download_mvt_vertices(self._c, _fp(out)))
         return out
 
+    # the client's overlays after drawF() in mono mode (kinect_client.cpp:672-683): "Draw TSDF" (kinect::ReconCalibs) and "Draw frustums"
+    def drawCalibVis(self, mv, proj):
+        self._ck(self._L.tsdf_draw_calibvis(self._c, _fp(_f32(mv)), _fp(_f32(proj))))
+
+    def setActiveKinect(self, i): self._ck(self._L.tsdf_set_active_kinect(self._c, C.c_uint32(int(i))))
+
+    def drawFrustums(self, mv, proj):
+        self._ck(self._L.tsdf_draw_frustums(self._c, _fp(_f32(mv)), _fp(_f32(proj))))
+
+    def calibvis_stats(self):
+        """(grid points of the last drawCalibVis, of them removed by its empty-space test)"""
+        out = (C.c_uint64 * 2)()
+        self._ck(self._L.tsdf_calibvis_stats(self._c, out))
+        return int(out[0]), int(out[1])
+
     def fillColors(self): self._ck(self._L.tsdf_fill_colors(self._c))
     def drawF(self, mv, proj): self._ck(self._L.tsdf_draw_f(self._c, _fp(_f32(mv)), _fp(_f32(proj))))
 
@@ -508,6 +523,12 @@ class ReconIntegrationHip:
         rgba, d = np.empty((h, w, 4), np.float32), np.empty((h, w), np.float32)
         self._ck(self._L.tsdf_download_framebuffer(self._c, _fp(rgba), _fp(d)))
         return rgba, d
+
+    def set_framebuffer(self, rgba, depth):
+        w, h = self.view
+        rgba, depth = _f32(rgba), _f32(depth)
+        assert rgba.shape == (h, w, 4) and depth.shape == (h, w)
+        self._ck(self._L.tsdf_upload_framebuffer(self._c, _fp(rgba), _fp(depth)))
 
     def atlas(self):
         w, h = self.view

@@ -817,7 +817,7 @@ int32_t tsdf_destroy(tsdf_ctx* c) {
   if (c->src_ready) hipEventDestroy(c->src_ready);
   if (c->normals_read) hipEventDestroy(c->normals_read);
   if (c->raw_read) hipEventDestroy(c->raw_read);
-  hipFree(c->d_mvt_vtx);
+  hipFree(c->d_mvt_vtx); hipFree(c->d_calibvis_skipped);
   if (c->fill_worker) {
     c->fill_worker->stop.store(true);
     { std::lock_guard<std::mutex> lk(c->fill_worker->m); }
@@ -940,9 +940,15 @@ int32_t tsdf_set_calibration(tsdf_ctx* c, uint32_t i, const float* inv, const ui
     // CalibVolumes::addVolume builds the sensor's frustum from this volume (CalibVolumes.cpp:122) and getCameraPositions()
     // (:224-230) feeds the quality pass: default camera position, until tsdf_set_camera_position overrides it
     float cam[3];
-    if (tsdf_frustum_from_volume(xyz, rx, nullptr, cam) == TSDF_OK && std::isfinite(cam[0]) && std::isfinite(cam[1]) && std::isfinite(cam[2])) {
-      for (int a = 0; a < 3; ++a) c->pre.cam[i][a] = cam[a];
-      c->have_cam[i] = true;
+    if (tsdf_frustum_from_volume(xyz, rx, nullptr, cam) == TSDF_OK) {
+      if (std::isfinite(cam[0]) && std::isfinite(cam[1]) && std::isfinite(cam[2])) {
+        for (int a = 0; a < 3; ++a) c->pre.cam[i][a] = cam[a];
+        c->have_cam[i] = true;
+      }
+      // ... and draws it (CalibVolumes::drawFrustums, :214-218): the corner samples and the camera position of the frustum overlay
+      frustum_corners(xyz, rx, c->frustum_corner[i]);
+      for (int a = 0; a < 3; ++a) c->frustum_cam[i][a] = cam[a];
+      c->have_frustum[i] = true;
     }
   }
   c->have_calib[i] = true;
@@ -1912,6 +1918,97 @@ int32_t tsdf_set_stage_overlap(tsdf_ctx* c, int32_t on) {
   return TSDF_OK;
 }
 
+// ---- the overlays of the client's draw3d() in mono mode (kinect_client.cpp:672-683): "Draw TSDF" and "Draw frustums"
+static int32_t overlay_checks(tsdf_ctx* c, const float* mv, const float* pr, ViewParams* P) {
+  if (!mv || !pr) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "null matrix");
+  if (!make_view_params(c, mv, pr, P)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "singular modelview / projection matrix");
+  if (c->color_mask_mode != 0 || c->vp_org[0] != 0 || c->vp_org[1] != 0 || c->vp_off[0] != 0.0f || c->vp_off[1] != 0.0f)
+    FAIL(c, TSDF_ERR_STATE, "the overlays are drawn in mono mode only (colour mask 0, no viewport origin / offset)");
+  return TSDF_OK;
+}
+int32_t tsdf_draw_calibvis(tsdf_ctx* c, const float* mv, const float* pr) {
+  CHECK_CTX(c);
+  ViewParams P;
+  if (int32_t rc = overlay_checks(c, mv, pr, &P)) return rc;
+  if (!c->have_calib[0] || !c->luts.s[0].inv) FAIL(c, TSDF_ERR_STATE, "stream 0 needs cv_xyz_inv (tsdf_set_calibration): its resolution is the point grid");
+  if (!(c->vol.own_tz0 == 0 && c->vol.own_tz1 == (c->res[2] + 7) / 8)) FAIL(c, TSDF_ERR_STATE, "the TSDF overlay needs the whole volume (a Z-slab context holds part of it)");
+  HIP_TRY(c, hipSetDevice(c->device));
+  CalibVisParams Q{};
+  for (int a = 0; a < 3; ++a) {                                          // vol_to_world = translate(bbox_min) * scale(extent), fp32 (recon_calibs.cpp:38-45)
+    Q.v2w.m[a * 5] = c->cfg.bbox_max[a] - c->cfg.bbox_min[a];
+    Q.v2w.m[12 + a] = c->cfg.bbox_min[a];
+    Q.gres[a] = c->luts.s[0].inv_res[a];
+    Q.step[a] = 1.0f / (float)Q.gres[a];
+  }
+  Q.v2w.m[15] = 1.0f;
+  memcpy(Q.mv.m, mv, 64); memcpy(Q.proj.m, pr, 64);
+  Q.w = c->vw; Q.h = c->vh;
+  // empty-space skip: a tile of class kTileMinus holds -limit (every change of the limit marks every class of both volume sets mixed,
+  // tsdf_set_tsdf_limit, so the classes were computed under the current one); such samples are discarded iff -limit <= -0.01
+  Q.skip = -c->vol.limit <= -kCalibVisLimit ? 1 : 0;
+  if (!c->d_comp_key) HIP_TRY(c, hipMalloc(&c->d_comp_key, (size_t)c->vw * c->vh * sizeof(unsigned long long)));
+  if (!c->d_calibvis_skipped) HIP_TRY(c, hipMalloc(&c->d_calibvis_skipped, sizeof(unsigned long long)));
+  Q.skipped = c->d_calibvis_skipped;
+  // a draw: the volume of the latest integrate() (the set a raymarch issued now would read), the framebuffer after the hole filling
+  HIP_TRY(c, join_pre(c));
+  HIP_TRY(c, join_integ(c));
+  HIP_TRY(c, join_fill(c));
+  timer_begin(c, "calibvis");
+  HIP_TRY(c, hipMemsetAsync(c->d_calibvis_skipped, 0, sizeof(unsigned long long), c->stream));
+  c->fb_consistent = false;
+  launch_draw_calibvis(c->stream, Q, c->vol, c->d_comp_key, c->d_fb_c, c->d_fb_d);
+  timer_end(c, "calibvis");
+  c->calibvis_points = (uint64_t)Q.gres[0] * Q.gres[1] * Q.gres[2];
+  // fillColors() recorded draw_done[set] BEFORE this draw, and the integrate() two frames later that overwrites the set waits for that
+  // event only: record it again behind the overlay (after the hole-filling job that waits for its previous record has issued that wait)
+  if (c->integ_stream && c->draw_done[c->vol_set]) {
+    if (c->fill_worker) c->fill_worker->wait_issued(c->draw_wait_job[c->vol_set]);
+    HIP_TRY(c, hipEventRecord(c->draw_done[c->vol_set], c->stream));
+    c->draw_pending[c->vol_set] = true;
+  }
+  HIP_TRY(c, hipGetLastError());
+  return TSDF_OK;
+}
+int32_t tsdf_set_active_kinect(tsdf_ctx* c, uint32_t stream) {
+  CHECK_CTX(c);
+  if (stream >= c->cfg.num_streams) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "stream %u out of range", stream);
+  return TSDF_OK;                                                        // (the layer selects LUT lookups whose results calib_vis.{vs,fs} never use)
+}
+int32_t tsdf_draw_frustums(tsdf_ctx* c, const float* mv, const float* pr) {
+  CHECK_CTX(c);
+  ViewParams P;
+  if (int32_t rc = overlay_checks(c, mv, pr, &P)) return rc;
+  FrustumParams Q{};
+  for (uint32_t i = 0; i < c->cfg.num_streams; ++i) {
+    if (!c->have_frustum[i]) FAIL(c, TSDF_ERR_STATE, "stream %u needs cv_xyz (tsdf_set_calibration): its corner samples are the frustum", i);
+    memcpy(Q.corner[i], c->frustum_corner[i], sizeof(Q.corner[i]));
+    memcpy(Q.cam[i], c->frustum_cam[i], sizeof(Q.cam[i]));
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  memcpy(Q.mv.m, mv, 64); memcpy(Q.proj.m, pr, 64);
+  Q.n = (int)c->cfg.num_streams; Q.w = c->vw; Q.h = c->vh;
+  if (!c->d_comp_key) HIP_TRY(c, hipMalloc(&c->d_comp_key, (size_t)c->vw * c->vh * sizeof(unsigned long long)));
+  HIP_TRY(c, join_fill(c));                                              // the hole filling writes the framebuffer from its own lane
+  timer_begin(c, "frustums");
+  c->fb_consistent = false;
+  launch_draw_frustums(c->stream, Q, c->d_comp_key, c->d_fb_c, c->d_fb_d);
+  timer_end(c, "frustums");
+  HIP_TRY(c, hipGetLastError());
+  return TSDF_OK;
+}
+int32_t tsdf_calibvis_stats(tsdf_ctx* c, uint64_t out[2]) {
+  CHECK_CTX(c);
+  if (!out) return TSDF_ERR_INVALID_ARGUMENT;
+  out[0] = c->calibvis_points; out[1] = 0;
+  if (!c->d_calibvis_skipped) return TSDF_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, sync_ctx(c));
+  unsigned long long n = 0;
+  HIP_TRY(c, hipMemcpy(&n, c->d_calibvis_skipped, sizeof(n), hipMemcpyDeviceToHost));
+  out[1] = n;
+  return TSDF_OK;
+}
+
 // ---- setters
 int32_t tsdf_set_tsdf_limit(tsdf_ctx* c, float limit) {
   CHECK_CTX(c);
@@ -2114,6 +2211,17 @@ int32_t tsdf_download_framebuffer(tsdf_ctx* c, float* rgba, float* depth) {
   const size_t n = (size_t)c->vw * c->vh;
   if (rgba) HIP_TRY(c, hipMemcpy(rgba, c->d_fb_c, n * 16, hipMemcpyDeviceToHost));
   if (depth) HIP_TRY(c, hipMemcpy(depth, c->d_fb_d, n * 4, hipMemcpyDeviceToHost));
+  return TSDF_OK;
+}
+int32_t tsdf_upload_framebuffer(tsdf_ctx* c, const float* rgba, const float* depth) {
+  CHECK_CTX(c);
+  if (!rgba || !depth) return TSDF_ERR_INVALID_ARGUMENT;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, sync_ctx(c));
+  const size_t n = (size_t)c->vw * c->vh;
+  HIP_TRY(c, hipMemcpy(c->d_fb_c, rgba, n * 16, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(c->d_fb_d, depth, n * 4, hipMemcpyHostToDevice));
+  c->fb_consistent = false;                                              // the hole filling may no longer keep to the dirty tiles
   return TSDF_OK;
 }
 int32_t tsdf_download_atlas(tsdf_ctx* c, float* rgba, float* depth) {

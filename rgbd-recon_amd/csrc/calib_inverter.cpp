@@ -61,6 +61,11 @@ int32_t fail_hip(hipError_t e, const char* what) { rr_set_io_error(std::string(w
 bool bad_res(const uint32_t r[3]) { return !r || r[0] < 1 || r[1] < 1 || r[2] < 1 || r[0] > 2048 || r[1] > 2048 || r[2] > 2048; }
 }  // namespace
 
+void rr::frustum_corners(const float* cv_xyz, const uint32_t res[3], float out[8][3]) {
+  const FrustumData f = frustum_of(cv_xyz, res);
+  for (int i = 0; i < 8; ++i) { out[i][0] = f.corner[i].x; out[i][1] = f.corner[i].y; out[i][2] = f.corner[i].z; }
+}
+
 extern "C" {
 
 int32_t tsdf_frustum_from_volume(const float* cv_xyz, const uint32_t res[3], float planes[24], float camera_pos[3]) {

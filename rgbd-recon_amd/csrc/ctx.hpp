@@ -85,6 +85,9 @@ struct tsdf_ctx {
   const float* raw_src = nullptr;   // the raw depth the passes read: d_raw (host upload, wire unpack) or the caller's device array (tsdf_upload_raw_frame_dev)
   hipEvent_t normals_read = nullptr; bool normals_read_pending = false;   // recorded behind a point / triangle-grid draw: the lane ahead rewrites d_normal
   bool have_limits[TSDF_MAX_STREAMS]{}, have_cam[TSDF_MAX_STREAMS]{};
+  // the frustum overlay (tsdf_draw_frustums): per stream the forward LUT's corner samples and Frustum::getCameraPos, captured by tsdf_set_calibration
+  float frustum_corner[TSDF_MAX_STREAMS][8][3]{}; float frustum_cam[TSDF_MAX_STREAMS][3]{}; bool have_frustum[TSDF_MAX_STREAMS]{};
+  unsigned long long* d_calibvis_skipped = nullptr; uint64_t calibvis_points = 0;   // the TSDF overlay: grid points of the last draw, device count of those the empty-space test removed
   // frame ingest (readLoop / update): wire formats, pinned double buffer (the reference's double_pbo), device copy of the message
   uint32_t color_format = TSDF_COLOR_RGB8, depth_format = TSDF_DEPTH_F32;
   uint8_t* h_wire[2]{}; hipEvent_t wire_done[2]{}; bool wire_pending[2]{}; int wire_slot = 0;

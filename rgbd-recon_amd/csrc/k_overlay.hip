@@ -1,0 +1,202 @@
+// The two overlays the client draws after drawF() in mono mode (source/kinect_client.cpp:672-683), depth-tested into the framebuffer:
+//   "Draw TSDF"      kinect::ReconCalibs::draw(), framework/reconstruction/recon_calibs.cpp:54-61 + glsl/calib_vis.{vs,fs}: one GL point per
+//                    cell of stream 0's inverse LUT grid, coloured by the TSDF sampled there
+//   "Draw frustums"  CalibVolumes::drawFrustums() -> Frustum::draw(), framework/calibration/frustum.cpp:45-95: per stream 12 lines between
+//                    the forward LUT's corner samples and a 3-pixel point at the camera position
+// GL_LESS with primitives drawn in order becomes the points back-end's scheme (k_points.hip): a 64-bit atomicMin per fragment on (window z
+// bits, primitive index) into a key buffer seeded with the framebuffer's depth, behind a strict z < fb_d test against the depth as it was
+// before the overlay; a resolve pass then writes the winners' colour and depth and leaves every other pixel as the previous draw left it.
+// The definitions GL leaves open (point size, line rasterisation, depth clamp) are listed in include/rgbd_recon_hip.h and restated in
+// tests/overlay_reference.py.
+#include "sampling.hpp"
+
+namespace rr {
+
+constexpr uint32_t kNoId = 0xffffffffu;
+
+__device__ __forceinline__ unsigned long long overlay_key(float z, uint32_t id) { return ((unsigned long long)__float_as_uint(z) << 32) | (unsigned long long)id; }
+
+// one fragment: strict GL_LESS against the framebuffer's depth, then the in-order tie rule through the key.  Keys only decrease: a plain load
+// that already holds a key <= k makes the atomic redundant.
+__device__ __forceinline__ void overlay_fragment(const float* __restrict__ fb_d, unsigned long long* __restrict__ key, int pix, float z, uint32_t id) {
+  if (!(z < fb_d[pix])) return;
+  const unsigned long long k = overlay_key(z, id);
+  if (k < key[pix]) atomicMin(&key[pix], k);
+}
+
+__global__ __launch_bounds__(256) void k_overlay_clear(const float* __restrict__ fb_d, unsigned long long* __restrict__ key, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) key[i] = overlay_key(fb_d[i], kNoId);
+}
+
+// ---- "Draw TSDF"
+template <bool kSparse>
+__device__ __forceinline__ float calib_sample(const CalibVisParams& Q, const Volume& V, int x, int y, int z, float* u) {
+  u[0] = ((float)x + 0.5f) * Q.step[0]; u[1] = ((float)y + 0.5f) * Q.step[1]; u[2] = ((float)z + 0.5f) * Q.step[2];   // volume_sampler.cpp:33-45
+  return tex3d_tsdf<kSparse, true>(V, u[0], u[1], u[2]);                                                               // calib_vis.vs:37
+}
+// calib_vis.fs:17-30; the division is IEEE (not a multiply by the reciprocal)
+__device__ __forceinline__ float4 calib_color(float d) {
+  const float inv = fabsf(d) / kCalibVisLimit;
+  float4 c = d > 0.0f ? make_float4(1.0f - inv, 0.0f, 0.0f, 1.0f) : make_float4(0.0f, 1.0f - inv, 0.0f, 1.0f);
+  if (d >= kCalibVisLimit) c = make_float4(0.0f, 0.0f, 1.0f, 1.0f);
+  return c;
+}
+
+template <bool kSparse>
+__global__ __launch_bounds__(256) void k_calibvis_scatter(CalibVisParams Q, Volume V, const float* __restrict__ fb_d, unsigned long long* __restrict__ key) {
+  const int t = threadIdx.x;
+  const int b0[3] = {(int)blockIdx.x * 8, (int)blockIdx.y * 8, (int)blockIdx.z * 4}, bn[3] = {8, 8, 4};
+  if (Q.skip) {
+    // Empty-space skip.  lerpf(a, a, t) == a, so a sample whose eight taps all hold the clear value -limit IS -limit, and -limit <= -0.01 is
+    // discarded (the host sets skip only then).  Taps are monotone in the grid coordinate: the block's first and last point bound them.
+    int lo[3], hi[3], cnt = 1;
+    for (int a = 0; a < 3; ++a) {
+      const int last = min(b0[a] + bn[a], Q.gres[a]) - 1;
+      lo[a] = axis_linear(((float)b0[a] + 0.5f) * Q.step[a], V.res[a]).i0 >> 3;
+      hi[a] = axis_linear(((float)last + 0.5f) * Q.step[a], V.res[a]).i1 >> 3;
+      cnt *= last - b0[a] + 1;
+    }
+    const int nx = hi[0] - lo[0] + 1, ny = hi[1] - lo[1] + 1, nt = nx * ny * (hi[2] - lo[2] + 1);
+    if (nt <= 1024) {                                                    // (a LUT far coarser than the volume: too many tiles to be worth a look)
+      int mixed = 0;
+      for (int k = t; k < nt; k += 256) {
+        const int tx = lo[0] + k % nx, ty = lo[1] + (k / nx) % ny, tz = lo[2] + k / (nx * ny);
+        mixed |= V.cls[(uint32_t)__mul24(__mul24(tz - V.tz0, V.nty) + ty, V.ntx) + (uint32_t)tx] != kTileMinus;
+      }
+      if (!__syncthreads_or(mixed)) {
+        if (t == 0) atomicAdd(Q.skipped, (unsigned long long)cnt);
+        return;
+      }
+    }
+  }
+  const int x = b0[0] + (t & 7), y = b0[1] + ((t >> 3) & 7), z = b0[2] + (t >> 6);
+  if (x >= Q.gres[0] || y >= Q.gres[1] || z >= Q.gres[2]) return;
+  float u[3];
+  const float d = calib_sample<kSparse>(Q, V, x, y, z, u);
+  if (d <= -kCalibVisLimit) return;                                      // calib_vis.fs:29: discard (before the depth test)
+  const float4 pw = mat_mul(Q.v2w, u[0], u[1], u[2], 1.0f);              // calib_vis.vs:29-38, in this order
+  const float4 pe = mat_mul(Q.mv, pw.x, pw.y, pw.z, 1.0f);
+  const float4 clip = mat_mul(Q.proj, pe.x, pe.y, pe.z, 1.0f);
+  if (!(clip.w > 0.0f) || fabsf(clip.x) > clip.w || fabsf(clip.y) > clip.w || fabsf(clip.z) > clip.w) return;   // whole-point clip (point_vertex)
+  const float xw = (clip.x / clip.w * 0.5f + 0.5f) * (float)Q.w;
+  const float yw = (clip.y / clip.w * 0.5f + 0.5f) * (float)Q.h;
+  const float zw = clip.z / clip.w * 0.5f + 0.5f;
+  if (!(zw < 1.0f)) return;
+  // a 1-pixel point, k_points_scatter's coverage rule
+  int x0 = (int)ceilf((xw - 0.5f) - 0.5f), x1 = (int)ceilf((xw + 0.5f) - 0.5f) - 1;
+  int y0 = (int)ceilf((yw - 0.5f) - 0.5f), y1 = (int)ceilf((yw + 0.5f) - 0.5f) - 1;
+  x0 = max(x0, 0); y0 = max(y0, 0); x1 = min(x1, Q.w - 1); y1 = min(y1, Q.h - 1);
+  const uint32_t id = (uint32_t)((z * Q.gres[1] + y) * Q.gres[0] + x);   // draw order: x fastest, then y, then z
+  for (int py = y0; py <= y1; ++py)
+    for (int px = x0; px <= x1; ++px) overlay_fragment(fb_d, key, py * Q.w + px, zw, id);
+}
+
+template <bool kSparse>
+__global__ __launch_bounds__(256) void k_calibvis_resolve(CalibVisParams Q, Volume V, const unsigned long long* __restrict__ key, float4* __restrict__ fb_c,
+                                                          float* __restrict__ fb_d) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Q.w * Q.h) return;
+  const unsigned long long k = key[i];
+  const uint32_t id = (uint32_t)k;
+  if (id == kNoId) return;                                               // no fragment passed: the previous draw's pixel stays
+  const int x = (int)(id % (uint32_t)Q.gres[0]), y = (int)((id / (uint32_t)Q.gres[0]) % (uint32_t)Q.gres[1]), z = (int)(id / (uint32_t)(Q.gres[0] * Q.gres[1]));
+  float u[3];
+  fb_c[i] = calib_color(calib_sample<kSparse>(Q, V, x, y, z, u));        // recomputed from the id: no per-point colour store
+  fb_d[i] = __uint_as_float((uint32_t)(k >> 32));
+}
+
+void launch_draw_calibvis(hipStream_t st, const CalibVisParams& Q, const Volume& V, unsigned long long* key, float4* fb_c, float* fb_d) {
+  const int n = Q.w * Q.h;
+  const dim3 grid((Q.gres[0] + 7) / 8, (Q.gres[1] + 7) / 8, (Q.gres[2] + 3) / 4);
+  hipLaunchKernelGGL(k_overlay_clear, dim3((n + 255) / 256), dim3(256), 0, st, fb_d, key, n);
+  if (V.slot) {
+    hipLaunchKernelGGL(k_calibvis_scatter<true>, grid, dim3(256), 0, st, Q, V, fb_d, key);
+    hipLaunchKernelGGL(k_calibvis_resolve<true>, dim3((n + 255) / 256), dim3(256), 0, st, Q, V, key, fb_c, fb_d);
+  } else {
+    hipLaunchKernelGGL(k_calibvis_scatter<false>, grid, dim3(256), 0, st, Q, V, fb_d, key);
+    hipLaunchKernelGGL(k_calibvis_resolve<false>, dim3((n + 255) / 256), dim3(256), 0, st, Q, V, key, fb_c, fb_d);
+  }
+}
+
+// ---- "Draw frustums": 13 primitives per stream (the 12 lines of frustum.cpp:48-84, then the camera point of :87-94), one wave each
+__constant__ int c_frustum_lines[12][2] = {{0, 4}, {1, 5}, {2, 6}, {3, 7}, {0, 1}, {1, 2}, {2, 3}, {3, 0}, {4, 5}, {5, 6}, {6, 7}, {7, 4}};
+
+__device__ __forceinline__ float4 frustum_clip(const FrustumParams& Q, const float* p) {   // P . (MV . p)
+  const float4 e = mat_mul(Q.mv, p[0], p[1], p[2], 1.0f);
+  return mat_mul(Q.proj, e.x, e.y, e.z, e.w);
+}
+// clip the segment a -> b against one plane (inside: dist >= 0); false = nothing left
+__device__ __forceinline__ bool clip_plane(float4& a, float4& b, float da, float db) {
+  if (!(da >= 0.0f) && !(db >= 0.0f)) return false;
+  if (!(da >= 0.0f)) {
+    const float t = da / (da - db);
+    a = make_float4(a.x + (b.x - a.x) * t, a.y + (b.y - a.y) * t, a.z + (b.z - a.z) * t, a.w + (b.w - a.w) * t);
+  } else if (!(db >= 0.0f)) {
+    const float t = db / (db - da);
+    b = make_float4(b.x + (a.x - b.x) * t, b.y + (a.y - b.y) * t, b.z + (a.z - b.z) * t, b.w + (a.w - b.w) * t);
+  }
+  return true;
+}
+
+__global__ __launch_bounds__(64) void k_frustum_lines(FrustumParams Q, const float* __restrict__ fb_d, unsigned long long* __restrict__ key) {
+  const int prim = blockIdx.x, s = prim / 13, k = prim % 13, lane = threadIdx.x;
+  const uint32_t id = (uint32_t)prim;                                    // stream * 13 + k: the draw order
+  const float W = (float)Q.w, H = (float)Q.h;
+  if (k == 12) {                                                         // glPointSize(3) at the camera position
+    const float4 clip = frustum_clip(Q, Q.cam[s]);
+    if (!(clip.w > 0.0f) || fabsf(clip.x) > clip.w || fabsf(clip.y) > clip.w || fabsf(clip.z) > clip.w) return;
+    const float xw = (clip.x / clip.w * 0.5f + 0.5f) * W, yw = (clip.y / clip.w * 0.5f + 0.5f) * H, zw = clip.z / clip.w * 0.5f + 0.5f;
+    if (!(zw < 1.0f)) return;
+    int x0 = (int)ceilf((xw - 1.5f) - 0.5f), x1 = (int)ceilf((xw + 1.5f) - 0.5f) - 1;
+    int y0 = (int)ceilf((yw - 1.5f) - 0.5f), y1 = (int)ceilf((yw + 1.5f) - 0.5f) - 1;
+    x0 = max(x0, 0); y0 = max(y0, 0); x1 = min(x1, Q.w - 1); y1 = min(y1, Q.h - 1);
+    const int nx = x1 - x0 + 1, ny = y1 - y0 + 1;
+    if (nx <= 0 || ny <= 0) return;
+    for (int q = lane; q < nx * ny; q += 64) overlay_fragment(fb_d, key, (y0 + q / nx) * Q.w + x0 + q % nx, zw, id);
+    return;
+  }
+  float4 a = frustum_clip(Q, Q.corner[s][c_frustum_lines[k][0]]), b = frustum_clip(Q, Q.corner[s][c_frustum_lines[k][1]]);
+  if (!clip_plane(a, b, a.z + a.w, b.z + b.w) || !clip_plane(a, b, a.w - a.z, b.w - b.z)) return;   // near, then far
+  if (!(a.w > 0.0f) || !(b.w > 0.0f)) return;
+  const float ax = (a.x / a.w * 0.5f + 0.5f) * W, ay = (a.y / a.w * 0.5f + 0.5f) * H, az = a.z / a.w * 0.5f + 0.5f;
+  const float bx = (b.x / b.w * 0.5f + 0.5f) * W, by = (b.y / b.w * 0.5f + 0.5f) * H, bz = b.z / b.w * 0.5f + 0.5f;
+  // diamond exit for width 1: an x-major line makes one fragment per pixel column whose centre c lies in [start, end) along the line's
+  // direction, in the row floor(y(c)); y-major the same with rows
+  const bool xmajor = fabsf(bx - ax) >= fabsf(by - ay);
+  const float s0 = xmajor ? ax : ay, s1 = xmajor ? bx : by, o0 = xmajor ? ay : ax, o1 = xmajor ? by : bx;
+  const int n_major = xmajor ? Q.w : Q.h, n_minor = xmajor ? Q.h : Q.w;
+  const float lo = fmaxf(floorf(fminf(s0, s1)) - 1.0f, 0.0f), hi = fminf(ceilf(fmaxf(s0, s1)) + 1.0f, (float)(n_major - 1));
+  if (!(lo <= hi)) return;
+  for (int i = (int)lo + lane; i <= (int)hi; i += 64) {
+    const float c = (float)i + 0.5f;
+    if (!(s1 > s0 ? (c >= s0 && c < s1) : (c <= s0 && c > s1))) continue;
+    const float t = (c - s0) / (s1 - s0);
+    const float m = floorf(o0 + (o1 - o0) * t);
+    if (!(m >= 0.0f && m < (float)n_minor)) continue;
+    float z = az + (bz - az) * t;
+    if (z != z) continue;
+    z = z > 0.0f ? (z < 1.0f ? z : 1.0f) : 0.0f;                          // the depth range [0, 1]
+    const int px = xmajor ? i : (int)m, py = xmajor ? (int)m : i;
+    overlay_fragment(fb_d, key, py * Q.w + px, z, id);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_frustum_resolve(int n, const unsigned long long* __restrict__ key, float4* __restrict__ fb_c, float* __restrict__ fb_d) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned long long k = key[i];
+  const uint32_t id = (uint32_t)k;
+  if (id == kNoId) return;
+  fb_c[i] = id % 13 == 12 ? make_float4(1.0f, 0.0f, 0.0f, 1.0f) : make_float4(0.0f, 1.0f, 0.0f, 1.0f);   // frustum.cpp:49 / :91
+  fb_d[i] = __uint_as_float((uint32_t)(k >> 32));
+}
+
+void launch_draw_frustums(hipStream_t st, const FrustumParams& Q, unsigned long long* key, float4* fb_c, float* fb_d) {
+  const int n = Q.w * Q.h;
+  hipLaunchKernelGGL(k_overlay_clear, dim3((n + 255) / 256), dim3(256), 0, st, fb_d, key, n);
+  hipLaunchKernelGGL(k_frustum_lines, dim3(Q.n * 13), dim3(64), 0, st, Q, fb_d, key);
+  hipLaunchKernelGGL(k_frustum_resolve, dim3((n + 255) / 256), dim3(256), 0, st, n, key, fb_c, fb_d);
+}
+
+}  // namespace rr

@@ -190,6 +190,27 @@ void launch_tri_normalize(hipStream_t st, const uint32_t* zbuf, const float4* ac
 void launch_draw_mvt(hipStream_t st, const ViewParams& P, const PointParams& Q, const StreamTable& T, const FrameImages& F, const float* raw, float min_length,
                      float2* vtx, uint32_t* zbuf, float4* acc, float4* fb_c, float* fb_d);
 
+// overlays of the client's draw3d() (k_overlay.hip): "Draw TSDF" (kinect::ReconCalibs::draw) and "Draw frustums" (Frustum::draw)
+struct CalibVisParams {
+  Mat4 v2w, mv, proj;           // vol_to_world as recon_calibs.cpp:38-45 builds it in fp32; the caller's matrices
+  int gres[3];                  // the point grid: stream 0's inverse LUT resolution (CalibVolumes::getVolumeRes)
+  float step[3];                // 1.0f / gres (volume_sampler.cpp:33-35)
+  int w, h;
+  int skip;                     // 1: a workgroup whose taps lie in kTileMinus tiles only is discarded whole (the clear value is <= -0.01)
+  unsigned long long* skipped;  // device counter: grid points removed by that test
+};
+struct FrustumParams {
+  Mat4 mv, proj;
+  float corner[TSDF_MAX_STREAMS][8][3];   // getCornerPoints of each stream's cv_xyz (CalibVolumes.cpp:98-113)
+  float cam[TSDF_MAX_STREAMS][3];         // Frustum::getCameraPos
+  int n, w, h;
+};
+constexpr float kCalibVisLimit = 0.01f;   // recon_calibs.cpp:20 (static; not the context's setTsdfLimit value)
+void launch_draw_calibvis(hipStream_t st, const CalibVisParams& Q, const Volume& V, unsigned long long* key, float4* fb_c, float* fb_d);
+void launch_draw_frustums(hipStream_t st, const FrustumParams& Q, unsigned long long* key, float4* fb_c, float* fb_d);
+// the 8 corner texels of a forward volume [rz][ry][rx][3] in getCornerPoints order (calib_inverter.cpp)
+void frustum_corners(const float* cv_xyz, const uint32_t res[3], float out[8][3]);
+
 // inverse calibration volume builder (k_inverter.hip)
 struct InverterGrid {
   uint32_t rx, ry, rz, n;     // forward volume resolution, sample count

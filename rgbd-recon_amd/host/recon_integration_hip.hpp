@@ -124,6 +124,8 @@ class ReconIntegrationHip {
   void clearOccupiedBricks() const { check(tsdf_clear_bricks(m_ctx)); }
   void updateOccupiedBricks() { check(tsdf_update_occupied(m_ctx, nullptr)); }
   void setMinVoxelsPerBrick(unsigned i) { check(tsdf_set_min_voxels_per_brick(m_ctx, i)); }
+  // drawOccupiedBricks() (recon_integration.cpp:447-454) draws with solid.vs, whose `transform` uniform is never set: GL's zero matrix puts every
+  // vertex at clip (0,0,0,0) and the reference draws nothing.  So does this.
   void drawOccupiedBricks() const {}
   void setShadeMode(int mode) { check(tsdf_set_shade_mode(m_ctx, mode)); }
 
@@ -148,6 +150,8 @@ class ReconIntegrationHip {
   // ---- kinect::ReconMVT::draw() (recon_mvt.cpp:84-150): reads the raw frame of the last raw / wire upload
   void drawMVT() { check(tsdf_draw_mvt(m_ctx, m_mv, m_proj)); }
   tsdf_ctx* handle() const { return m_ctx; }
+  const float* modelview() const { return m_mv; }
+  const float* projection() const { return m_proj; }
 
  private:
   void check(int32_t rc) const { if (rc != TSDF_OK) throw std::runtime_error(std::string("ReconIntegrationHip: ") + tsdf_last_error(m_ctx)); }
@@ -156,6 +160,29 @@ class ReconIntegrationHip {
   float m_mv[16], m_proj[16];
   float m_brick_size;
   bool m_draw_bricks = false;
+};
+
+// The client's overlays after drawF() in mono mode (source/kinect_client.cpp:672-683), over the SAME context and its matrices (setMatrices):
+// "Draw TSDF" is kinect::ReconCalibs (recon_calibs.hpp), "Draw frustums" CalibVolumes::drawFrustums() (CalibVolumes.cpp:214-218).
+class ReconCalibsHip {
+ public:
+  explicit ReconCalibsHip(ReconIntegrationHip& recon) : m_recon(recon) {}
+  void draw() { check(tsdf_draw_calibvis(m_recon.handle(), m_recon.modelview(), m_recon.projection())); }
+  void setActiveKinect(unsigned num_kinect) { check(tsdf_set_active_kinect(m_recon.handle(), num_kinect)); }   // validates only: changes no output
+
+ private:
+  void check(int32_t rc) const { if (rc != TSDF_OK) throw std::runtime_error(std::string("ReconCalibsHip: ") + tsdf_last_error(m_recon.handle())); }
+  ReconIntegrationHip& m_recon;
+};
+// the drawing side of CalibVolumes (its 3-D textures are ReconIntegrationHip::setCalibration)
+class CalibVolumesHip {
+ public:
+  explicit CalibVolumesHip(ReconIntegrationHip& recon) : m_recon(recon) {}
+  void drawFrustums() const { check(tsdf_draw_frustums(m_recon.handle(), m_recon.modelview(), m_recon.projection())); }
+
+ private:
+  void check(int32_t rc) const { if (rc != TSDF_OK) throw std::runtime_error(std::string("CalibVolumesHip: ") + tsdf_last_error(m_recon.handle())); }
+  ReconIntegrationHip& m_recon;
 };
 
 // The input side: kinect::NetKinectArray's public surface (framework/NetKinectArray.h:40-55) over the SAME context, for callers

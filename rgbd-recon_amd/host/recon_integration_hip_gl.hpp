@@ -67,7 +67,8 @@ class ReconIntegrationHipGL : public Reconstruction {
   float getBrickSize() const { return m_impl.getBrickSize(); }
   void clearOccupiedBricks() const { m_impl.clearOccupiedBricks(); }
   void updateOccupiedBricks() { m_impl.updateOccupiedBricks(); }
-  void drawOccupiedBricks() const {}                                      // wireframe debug overlay (solid.vs/fs): not part of the path
+  // (solid.vs's `transform` uniform is never set, recon_integration.cpp:447-454: GL's zero matrix puts every vertex at clip (0,0,0,0), the reference draws nothing)
+  void drawOccupiedBricks() const {}
   // the frame's explicit inputs and everything else of the C ABI
   ReconIntegrationHip& impl() { return m_impl; }
 
