@@ -216,6 +216,30 @@ int32_t tsdf_download_mvt_vertices(tsdf_ctx* ctx, float* out);
  *   TSDF_ERR_STATE when a stream has no cv_xyz.
  * tsdf_calibvis_stats: out[0] = grid points of the last tsdf_draw_calibvis, out[1] = of them removed whole by its empty-space test (blocks
  *   whose trilinear taps lie in tiles that hold only the clear value -limit, when -limit <= -0.01: every such sample is discarded).
+ * tsdf_draw_bbox: the bounding-box wireframe (g_draw_grid, on by default :70, .conf key draw_grid :299; :685-702) = gloost::BoundingBox::
+ *   draw() (external/gloost/BoundingBox.cpp:298-318) -> gloost::drawWiredBox (gloostRenderGoodies.h:251-304): six GL_LINE_LOOPs of four
+ *   corners of the box bbox_min..bbox_max as configured, in world coordinates through P * (MV * p): front (z = max), right (x = max), back
+ *   (z = min), left (x = min), top (y = max), bottom (y = min), corners in drawWiredBox's order, each loop closed by its v3 -> v0 segment
+ *   (24 segments; every box edge is drawn twice, once in each direction, and the first one drawn wins depth ties).  glLineWidth(2), aliased.
+ *   Colour (1, 1, 1, 0.75) with GL_COLOR_MATERIAL on and lighting off, written unmodulated, no blending.  Timer "bbox".  Runs after any
+ *   back-end (tsdf_draw_f, tsdf_draw_points, tsdf_draw_trigrid, tsdf_draw_mvt) and after the two overlays above (the client's order).
+ * tsdf_draw_textures: the texture view (g_draw_textures, key T :773, selector key Y :768; :704-707) = TextureBlitter::blit(15 + which,
+ *   resolution_full / 2) (texture_blitter.cpp, glsl/texture_passthrough.{vs,fs} mode 0), drawn last.  which = 0: unit 15, the atlas the
+ *   latest hole filling completed (the one fillColors() binds at recon_integration.cpp:315: the 1.5w x h RGBA32F ViewLod whose level 0 is
+ *   that draw's raymarch, levels 1.. its pyramid and every other texel the clear value (0, 1, 0, 0) of ViewLod::enable -- GL's T atlas of
+ *   the two-atlas sequence, which no transfer pass clears).  which = 1: unit 16, the w x h RGBA32F depth-limit image drawDepthLimits() left
+ *   (:171; clear (1, 0, 1, 0) :144, then per pixel MIN-blended (z, -z, back-facing ? z : 1, 1) of bricks.fs).  A drawF() without colour
+ *   filling or without space skipping leaves the respective texture as it was.  The blit covers the viewport (0, 0, vw, vh), (vw, vh) =
+ *   uvec2(fvec2(uvec2(1.5f * w, h)) / 2) (960 x 360 at 1280 x 720) whatever the source's size; framebuffer row y is GL window row y, as
+ *   tsdf_download_framebuffer returns it.  Output (rgb, 1); the depth test is off and depth is not written; pixels outside the viewport are
+ *   untouched.  Timer "textures".  TSDF_ERR_INVALID_ARGUMENT for which > 1; TSDF_ERR_STATE when the chosen texture has not been produced
+ *   since create / tsdf_resize (no draw with colour filling, no drawF with space skipping -- GL would show an undefined texture), after a
+ *   march into the pyramid that no hole filling has completed yet, and for unit 16 after an integrate() that already reset the image for
+ *   the coming draw.
+ *   Assumed, not defined by GL state alone: the client's glEnable(GL_TEXTURE_2D) on unit 0 (kinect_client.cpp:982) would modulate the
+ *   wireframe's colour by a complete 2-D texture bound on unit 0 under fixed-function texturing; this definition assumes none is, so the wire
+ *   colour is the current colour.  After tsdf_draw_trigrid / tsdf_draw_mvt GL's units 15 / 16 hold those back-ends' pass textures
+ *   (recon_trigrid.cpp:142-143); tsdf_draw_textures shows ReconIntegration's textures, which is what the client's texture view is for.
  *
  * What GL leaves open, defined here and restated by tests/overlay_reference.py (the kernels match it bit for bit; fp32 throughout, matrix
  * products as sum_k m[k][row] * v[k] left to right, no contraction):
@@ -229,13 +253,27 @@ int32_t tsdf_download_mvt_vertices(tsdf_ctx* ctx, float* out);
  *     |b.x - a.x| >= |b.y - a.y| (x-major) every pixel column i whose centre c = i + 0.5 lies in [a.x, b.x) along the direction of travel
  *     (a.x <= c < b.x, or b.x < c <= a.x) makes one fragment in row floor(a.y + (b.y - a.y) * t), t = (c - a.x) / (b.x - a.x), with depth
  *     a.z + (b.z - a.z) * t clamped to [0, 1]; y-major lines the same with rows.  Fragments outside the view are dropped.
+ *   Wide lines (GL 4.4 section 14.5.2.2, aliased; the bounding box's width 2).  After the near / far clip the width is rounded to w = 2 and
+ *     the window segment moves by -(w - 1) / 2 = -0.5 in its minor direction (a.y and b.y of an x-major line, where |dx| >= |dy|; a.x and b.x
+ *     of a y-major one; the major direction is that of the unmoved segment, which the shift does not change).  The moved segment is walked
+ *     by the width-1 rule above, and each of its fragments becomes a column (x-major) or row (y-major) of w fragments whose lowest
+ *     (leftmost) one is that fragment, all at its depth, each dropped on its own outside the view.
+ *   Texture view.  Pixel (x, y) of the viewport takes the texture coordinate (u, v) = ((x + 0.5f) / vw, (y + 0.5f) / vh) (IEEE divisions;
+ *     the full-screen triangle of screen_quad.cpp:11-15).  Sampling is fp32 bilinear on the source's own size (sw, sh), sampling.hpp's
+ *     axis_linear: f = u * sw - 0.5, taps clamp(floor(f)) and clamp(floor(f) + 1) to [0, sw - 1] (CLAMP_TO_EDGE; for u in [0, 1] the
+ *     atlas's MIRRORED_REPEAT picks the same taps), weight a = f - floor(f); rows alike.  Per channel lerp(lerp(t00, t10, ax), lerp(t01, t11,
+ *     ax), ay) with lerp(p, q, t) = p + (q - p) * t, t10 the tap right of t00 and t01 the one above it.  Unit 16's green channel is
+ *     min(0, -z) = 0 - max z, +0 where no brick fragment landed.
  *   Depth test.  A fragment passes only if z < the framebuffer's depth before the overlay (strict); among passing fragments of one pixel the
  *     smallest (z bits, primitive index) wins -- GL_LESS with primitives drawn in order.  Primitive index: the grid's linear index
- *     (x + res.x * (y + res.y * z)) for the TSDF overlay, stream * 13 + k for the frustums (k < 12 the lines in the order above, 12 the point). */
+ *     (x + res.x * (y + res.y * z)) for the TSDF overlay, stream * 13 + k for the frustums (k < 12 the lines in the order above, 12 the point),
+ *     4 * loop + k for the bounding box (loop in the order above, k the segment from its corner k to corner (k + 1) % 4). */
 int32_t tsdf_draw_calibvis(tsdf_ctx* ctx, const float modelview[16], const float projection[16]);
 int32_t tsdf_set_active_kinect(tsdf_ctx* ctx, uint32_t stream);
 int32_t tsdf_draw_frustums(tsdf_ctx* ctx, const float modelview[16], const float projection[16]);
 int32_t tsdf_calibvis_stats(tsdf_ctx* ctx, uint64_t out[2]);
+int32_t tsdf_draw_bbox(tsdf_ctx* ctx, const float modelview[16], const float projection[16]);
+int32_t tsdf_draw_textures(tsdf_ctx* ctx, uint32_t which);
 
 /* ---- draw() host matrices.  Host only, no context, no GPU: the matrix block ReconIntegration::draw()
  * builds before the raymarch -- vol_to_world = translate(bbox_min) * scale(bbox extent) (recon_integration.cpp:66-72),

@@ -406,6 +406,13 @@ class ReconIntegrationHip:
     def drawFrustums(self, mv, proj):
         self._ck(self._L.tsdf_draw_frustums(self._c, _fp(_f32(mv)), _fp(_f32(proj))))
 
+    # ... and the two after them (:685-707): the bounding-box wireframe (gloost::BoundingBox::draw) and the texture view
+    # (TextureBlitter::blit of unit 15 + which: 0 = the hole-filling atlas, 1 = the depth-limit image)
+    def drawBBox(self, mv, proj):
+        self._ck(self._L.tsdf_draw_bbox(self._c, _fp(_f32(mv)), _fp(_f32(proj))))
+
+    def drawTextures(self, which): self._ck(self._L.tsdf_draw_textures(self._c, C.c_uint32(int(which))))
+
     def calibvis_stats(self):
         """(grid points of the last drawCalibVis, of them removed by its empty-space test)"""
         out = (C.c_uint64 * 2)()

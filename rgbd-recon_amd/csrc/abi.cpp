@@ -80,7 +80,7 @@ void release_view(tsdf_ctx* c) {
   hipFree(c->d_tri_z); hipFree(c->d_tri_acc); c->d_tri_z = nullptr; c->d_tri_acc = nullptr;
   for (int k = 0; k < 3; ++k) { hipFree(c->d_touched[k]); c->d_touched[k] = nullptr; }
   for (int k = 0; k < 2; ++k) { hipFree(c->d_fill_mask[k]); hipFree(c->d_lvl_mask[k]); c->d_fill_mask[k] = nullptr; c->d_lvl_mask[k] = nullptr; }
-  c->draw_masks_valid = false; c->fb_consistent = false;
+  c->draw_masks_valid = false; c->fb_consistent = false; c->tex_atlas_ok = false; c->tex_limits_ok = false;
   c->tile_history = false; c->touched_idx = 0;
   hipFree(c->d_hits); hipFree(c->d_hit_counters); hipFree(c->d_comp_key); c->d_hits = nullptr; c->d_hit_counters = nullptr; c->d_comp_key = nullptr;
   c->atlas.color = nullptr; c->atlas.depth = nullptr; c->d_peels = nullptr; c->d_nsamples = nullptr; c->d_fb_c = nullptr; c->d_fb_d = nullptr;
@@ -1525,6 +1525,7 @@ int32_t tsdf_integrate(tsdf_ctx* c) {
     const bool whole = (c->vol.own_tz0 == 0 && c->vol.own_tz1 == (c->res[2] + 7) / 8);
     if (!deep && !pipelined(c) && c->use_bricks && !c->full_classify && c->skip_space && whole && c->use_tile_history && c->tile_history && !c->last_alt_peels && c->d_peels) {   // (with the lanes on the reset rides on the lane ahead: tsdf_mark_bricks)
       pc.peels = (uint4*)c->d_peels; pc.touched_prev = c->d_touched[(c->touched_idx + 2) % 3];     // the previous draw's tiles
+      c->tex_limits_ok = false;                                                                     // (unit 16's image: reset for the coming draw)
       pc.w = c->vw; pc.h = c->vh; pc.ntx = (c->vw + 7) / 8; pc.n_tiles = pc.ntx * ((c->vh + 7) / 8);
       c->peels_cleared = true;
     }
@@ -1624,6 +1625,7 @@ static int32_t raymarch_impl(tsdf_ctx* c, const float* mv, const float* pr, bool
     launch_depth_limits(c->stream, P, c->br, c->d_peels, use_tiles ? c->d_touched[c->touched_idx] : nullptr,
                         use_tiles && c->tile_history ? c->d_touched[(c->touched_idx + (alt_peels ? 1 : 2)) % 3] : nullptr, use_tiles && c->tile_history && c->peels_cleared ? 1 : 0);
     timer_end(c, "brickdraw");
+    c->tex_limits_ok = true;                                             // drawDepthLimits() rewrote m_view_depth (unit 16)
   }
   c->peels_cleared = false;                                              // consumed (or void: this draw did its own reset)
   // two pyramids alternate while the hole filling runs beside the next frame (stage overlap): this draw takes the other one and only has
@@ -1660,6 +1662,7 @@ static int32_t raymarch_impl(tsdf_ctx* c, const float* mv, const float* pr, bool
     c->tiled_draws = std::min(2, c->tiled_draws + 1);
   } else { c->tile_history = false; c->draw_masks_valid = false; }
   if (!c->fill_holes) c->fb_consistent = false;                          // the march (or the masked merge below) writes the framebuffer itself
+  if (c->fill_holes || masked_direct(c)) c->tex_atlas_ok = false;        // level 0 of c->atlas: this march's until its hole filling completes the pyramid
   HIP_TRY(c, join_integ(c));                                             // the volume: from here on (the depth limits above needed the bricks only)
   timer_begin(c, "draw");
   timer_begin(c, "k_march");
@@ -1827,6 +1830,7 @@ static int32_t fill_colors_impl(tsdf_ctx* c, hipStream_t* used) {
   ++c->n_fills; c->n_fills_by_tiles += by_tiles ? 1 : 0;
   c->fb_consistent = c->color_mask_mode == 0 && !c->keep_color;         // the framebuffer is this pass's now: background wherever no tile was dirty
   c->draw_masks_valid = false;                                           // (consumed: a second fillColors() of the same draw, e.g. after a composite, goes through every tile)
+  c->tex_atlas_ok = true;                                                // the texture bound on unit 15 at recon_integration.cpp:315
   if (c->overlap_fill && c->fill_thread && !c->timers_on) {              // the helper thread issues the lane's calls (tsdf_ctx::fill_worker)
     if (!c->fill_worker) {
       c->fill_worker = new tsdf_ctx::FillWorker();
@@ -1919,11 +1923,24 @@ int32_t tsdf_set_stage_overlap(tsdf_ctx* c, int32_t on) {
 }
 
 // ---- the overlays of the client's draw3d() in mono mode (kinect_client.cpp:672-683): "Draw TSDF" and "Draw frustums"
+static int32_t overlay_mono(tsdf_ctx* c) {
+  if (c->color_mask_mode != 0 || c->vp_org[0] != 0 || c->vp_org[1] != 0 || c->vp_off[0] != 0.0f || c->vp_off[1] != 0.0f)
+    FAIL(c, TSDF_ERR_STATE, "the overlays are drawn in mono mode only (colour mask 0, no viewport origin / offset)");
+  return TSDF_OK;
+}
 static int32_t overlay_checks(tsdf_ctx* c, const float* mv, const float* pr, ViewParams* P) {
   if (!mv || !pr) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "null matrix");
   if (!make_view_params(c, mv, pr, P)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "singular modelview / projection matrix");
-  if (c->color_mask_mode != 0 || c->vp_org[0] != 0 || c->vp_org[1] != 0 || c->vp_off[0] != 0.0f || c->vp_off[1] != 0.0f)
-    FAIL(c, TSDF_ERR_STATE, "the overlays are drawn in mono mode only (colour mask 0, no viewport origin / offset)");
+  return overlay_mono(c);
+}
+// fillColors() recorded draw_done[set] BEFORE an overlay, and the integrate() two frames later that overwrites the set waits for that event
+// only: record it again behind the overlay (after the hole-filling job that waits for its previous record has issued that wait)
+static int32_t overlay_rerecord_draw(tsdf_ctx* c) {
+  if (c->integ_stream && c->draw_done[c->vol_set]) {
+    if (c->fill_worker) c->fill_worker->wait_issued(c->draw_wait_job[c->vol_set]);
+    HIP_TRY(c, hipEventRecord(c->draw_done[c->vol_set], c->stream));
+    c->draw_pending[c->vol_set] = true;
+  }
   return TSDF_OK;
 }
 int32_t tsdf_draw_calibvis(tsdf_ctx* c, const float* mv, const float* pr) {
@@ -1959,13 +1976,7 @@ int32_t tsdf_draw_calibvis(tsdf_ctx* c, const float* mv, const float* pr) {
   launch_draw_calibvis(c->stream, Q, c->vol, c->d_comp_key, c->d_fb_c, c->d_fb_d);
   timer_end(c, "calibvis");
   c->calibvis_points = (uint64_t)Q.gres[0] * Q.gres[1] * Q.gres[2];
-  // fillColors() recorded draw_done[set] BEFORE this draw, and the integrate() two frames later that overwrites the set waits for that
-  // event only: record it again behind the overlay (after the hole-filling job that waits for its previous record has issued that wait)
-  if (c->integ_stream && c->draw_done[c->vol_set]) {
-    if (c->fill_worker) c->fill_worker->wait_issued(c->draw_wait_job[c->vol_set]);
-    HIP_TRY(c, hipEventRecord(c->draw_done[c->vol_set], c->stream));
-    c->draw_pending[c->vol_set] = true;
-  }
+  if (int32_t rc = overlay_rerecord_draw(c)) return rc;
   HIP_TRY(c, hipGetLastError());
   return TSDF_OK;
 }
@@ -1993,6 +2004,47 @@ int32_t tsdf_draw_frustums(tsdf_ctx* c, const float* mv, const float* pr) {
   c->fb_consistent = false;
   launch_draw_frustums(c->stream, Q, c->d_comp_key, c->d_fb_c, c->d_fb_d);
   timer_end(c, "frustums");
+  HIP_TRY(c, hipGetLastError());
+  return TSDF_OK;
+}
+int32_t tsdf_draw_bbox(tsdf_ctx* c, const float* mv, const float* pr) {
+  CHECK_CTX(c);
+  ViewParams P;
+  if (int32_t rc = overlay_checks(c, mv, pr, &P)) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  BBoxParams Q{};
+  memcpy(Q.mv.m, mv, 64); memcpy(Q.proj.m, pr, 64);
+  for (int a = 0; a < 3; ++a) { Q.lo[a] = c->cfg.bbox_min[a]; Q.hi[a] = c->cfg.bbox_max[a]; }
+  Q.w = c->vw; Q.h = c->vh;
+  if (!c->d_comp_key) HIP_TRY(c, hipMalloc(&c->d_comp_key, (size_t)c->vw * c->vh * sizeof(unsigned long long)));
+  HIP_TRY(c, join_fill(c));                                              // the hole filling writes the framebuffer from its own lane
+  timer_begin(c, "bbox");
+  c->fb_consistent = false;
+  launch_draw_bbox(c->stream, Q, c->d_comp_key, c->d_fb_c, c->d_fb_d);
+  timer_end(c, "bbox");
+  if (int32_t rc = overlay_rerecord_draw(c)) return rc;
+  HIP_TRY(c, hipGetLastError());
+  return TSDF_OK;
+}
+int32_t tsdf_draw_textures(tsdf_ctx* c, uint32_t which) {
+  CHECK_CTX(c);
+  if (which > 1) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "texture %u: 0 (unit 15, the hole-filling atlas) or 1 (unit 16, the depth-limit image)", which);
+  if (int32_t rc = overlay_mono(c)) return rc;
+  if (which == 0 && !c->tex_atlas_ok) FAIL(c, TSDF_ERR_STATE, "unit 15: no hole filling has completed the atlas since the context was created or resized (or a later march rewrote it)");
+  if (which == 1 && !c->tex_limits_ok) FAIL(c, TSDF_ERR_STATE, "unit 16: no draw with space skipping has produced the depth-limit image since the context was created or resized (or an integrate() reset it for the coming draw)");
+  HIP_TRY(c, hipSetDevice(c->device));
+  BlitParams Q{};
+  const float rf_x = (float)(uint32_t)(1.5f * (float)c->vw), rf_y = (float)c->vh;   // ViewLod::resolution_full, view_lod.cpp:29
+  Q.vw = (int)(uint32_t)(rf_x / 2.0f); Q.vh = (int)(uint32_t)(rf_y / 2.0f);          // uvec2(fvec2(resolution_full) / 2), kinect_client.cpp:706
+  Q.vw = std::min(Q.vw, c->vw); Q.vh = std::min(Q.vh, c->vh);            // (the viewport lies inside the framebuffer: 0.75 w x 0.5 h)
+  Q.fw = c->vw;
+  if (which == 0) { Q.src = c->atlas.color; Q.peels = 0; Q.sw = c->atlas.aw; Q.sh = c->atlas.h; }
+  else { Q.src = c->d_peels; Q.peels = 1; Q.sw = c->vw; Q.sh = c->vh; }
+  HIP_TRY(c, join_fill(c));                                              // the hole filling completes the atlas and writes the framebuffer on its own lane
+  timer_begin(c, "textures");
+  c->fb_consistent = false;
+  launch_blit_texture(c->stream, Q, c->d_fb_c);
+  timer_end(c, "textures");
   HIP_TRY(c, hipGetLastError());
   return TSDF_OK;
 }
@@ -2202,6 +2254,7 @@ int32_t tsdf_upload_image(tsdf_ctx* c, const float* rgba, const float* depth) {
   HIP_TRY(c, hipMemcpy2D(R.color, (size_t)R.stride * 16, rgba, w * 16, w * 16, h, hipMemcpyHostToDevice));
   HIP_TRY(c, hipMemcpy2D(R.depth, (size_t)R.stride * 4, depth, w * 4, w * 4, h, hipMemcpyHostToDevice));
   c->tile_history = false; c->draw_masks_valid = false;                  // the march target no longer holds what the last march left
+  if (c->fill_holes || masked_direct(c)) c->tex_atlas_ok = false;
   return TSDF_OK;
 }
 int32_t tsdf_download_framebuffer(tsdf_ctx* c, float* rgba, float* depth) {
@@ -2284,6 +2337,7 @@ int32_t tsdf_composite_dev(tsdf_ctx* c, const void* gathered, uint32_t n) {
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, join_fill(c));
   c->draw_masks_valid = false;                                           // the composite writes every pixel of the march target
+  if (c->fill_holes || masked_direct(c)) c->tex_atlas_ok = false;
   launch_composite(c->stream, gathered, (int)n, ray_target(c), c->vw, c->vh);
   HIP_TRY(c, hipGetLastError());
   return TSDF_OK;
@@ -2308,6 +2362,7 @@ int32_t tsdf_composite_hits_dev(tsdf_ctx* c, const void* gathered, uint32_t n, u
   // a compositing context that did not march this frame (dedicated compositor, multigpu.py) has no miss counts of its own: 0 then
   HIP_TRY(c, join_fill(c));
   c->draw_masks_valid = false;                                           // the composite writes every pixel of the march target
+  if (c->fill_holes || masked_direct(c)) c->tex_atlas_ok = false;
   launch_composite_hits(c->stream, gathered, (size_t)stride_bytes, (int)n, ray_target(c), c->vw, c->vh, c->d_comp_key, c->own_miss_counts ? 1 : 0);
   HIP_TRY(c, hipGetLastError());
   return TSDF_OK;

@@ -88,6 +88,9 @@ struct tsdf_ctx {
   // the frustum overlay (tsdf_draw_frustums): per stream the forward LUT's corner samples and Frustum::getCameraPos, captured by tsdf_set_calibration
   float frustum_corner[TSDF_MAX_STREAMS][8][3]{}; float frustum_cam[TSDF_MAX_STREAMS][3]{}; bool have_frustum[TSDF_MAX_STREAMS]{};
   unsigned long long* d_calibvis_skipped = nullptr; uint64_t calibvis_points = 0;   // the TSDF overlay: grid points of the last draw, device count of those the empty-space test removed
+  // the texture view (tsdf_draw_textures): c->atlas is the one the latest hole filling completed (GL's unit 15), d_peels the depth-limit image
+  // of the latest draw with space skipping (unit 16) -- each until something rewrites it
+  bool tex_atlas_ok = false, tex_limits_ok = false;
   // frame ingest (readLoop / update): wire formats, pinned double buffer (the reference's double_pbo), device copy of the message
   uint32_t color_format = TSDF_COLOR_RGB8, depth_format = TSDF_DEPTH_F32;
   uint8_t* h_wire[2]{}; hipEvent_t wire_done[2]{}; bool wire_pending[2]{}; int wire_slot = 0;

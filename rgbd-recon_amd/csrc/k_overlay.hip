@@ -1,4 +1,4 @@
-// The two overlays the client draws after drawF() in mono mode (source/kinect_client.cpp:672-683), depth-tested into the framebuffer:
+// The overlays the client draws after drawF() in mono mode (source/kinect_client.cpp:672-683), depth-tested into the framebuffer:
 //   "Draw TSDF"      kinect::ReconCalibs::draw(), framework/reconstruction/recon_calibs.cpp:54-61 + glsl/calib_vis.{vs,fs}: one GL point per
 //                    cell of stream 0's inverse LUT grid, coloured by the TSDF sampled there
 //   "Draw frustums"  CalibVolumes::drawFrustums() -> Frustum::draw(), framework/calibration/frustum.cpp:45-95: per stream 12 lines between
@@ -6,6 +6,8 @@
 // GL_LESS with primitives drawn in order becomes the points back-end's scheme (k_points.hip): a 64-bit atomicMin per fragment on (window z
 // bits, primitive index) into a key buffer seeded with the framebuffer's depth, behind a strict z < fb_d test against the depth as it was
 // before the overlay; a resolve pass then writes the winners' colour and depth and leaves every other pixel as the previous draw left it.
+// The client then draws the bounding-box wireframe (gloost::BoundingBox::draw, width-2 lines, same scheme) and the texture view
+// (TextureBlitter::blit, a bilinear blit of texture unit 15 or 16 into the lower-left of the frame, no depth test).
 // The definitions GL leaves open (point size, line rasterisation, depth clamp) are listed in include/rgbd_recon_hip.h and restated in
 // tests/overlay_reference.py.
 #include "sampling.hpp"
@@ -139,6 +141,44 @@ __device__ __forceinline__ bool clip_plane(float4& a, float4& b, float da, float
   return true;
 }
 
+// One segment between the clip-space points a -> b, walked by the 64 lanes of a wave: near, then far clip, then the diamond exit for
+// width 1 -- an x-major line makes one fragment per pixel column whose centre c lies in [start, end) along the line's direction, in the row
+// floor(y(c)); y-major the same with rows.  Wider lines (GL 4.4 section 14.5.2.2, aliased): the segment moves by -(width - 1) / 2 in its
+// minor direction, is walked by the same rule, and each of its fragments becomes `width` fragments upwards in the minor direction at that
+// fragment's depth, each dropped on its own outside the view.
+__device__ __forceinline__ void overlay_line(float4 a, float4 b, int w, int h, int width, uint32_t id, int lane, const float* __restrict__ fb_d,
+                                             unsigned long long* __restrict__ key) {
+  if (!clip_plane(a, b, a.z + a.w, b.z + b.w) || !clip_plane(a, b, a.w - a.z, b.w - b.z)) return;   // near, then far
+  if (!(a.w > 0.0f) || !(b.w > 0.0f)) return;
+  const float W = (float)w, H = (float)h;
+  const float ax = (a.x / a.w * 0.5f + 0.5f) * W, ay = (a.y / a.w * 0.5f + 0.5f) * H, az = a.z / a.w * 0.5f + 0.5f;
+  const float bx = (b.x / b.w * 0.5f + 0.5f) * W, by = (b.y / b.w * 0.5f + 0.5f) * H, bz = b.z / b.w * 0.5f + 0.5f;
+  const bool xmajor = fabsf(bx - ax) >= fabsf(by - ay);
+  float s0 = xmajor ? ax : ay, s1 = xmajor ? bx : by, o0 = xmajor ? ay : ax, o1 = xmajor ? by : bx;
+  if (width > 1) {
+    const float shift = 0.5f * (float)(width - 1);
+    o0 -= shift; o1 -= shift;
+  }
+  const int n_major = xmajor ? w : h, n_minor = xmajor ? h : w;
+  const float lo = fmaxf(floorf(fminf(s0, s1)) - 1.0f, 0.0f), hi = fminf(ceilf(fmaxf(s0, s1)) + 1.0f, (float)(n_major - 1));
+  if (!(lo <= hi)) return;
+  for (int i = (int)lo + lane; i <= (int)hi; i += 64) {
+    const float c = (float)i + 0.5f;
+    if (!(s1 > s0 ? (c >= s0 && c < s1) : (c <= s0 && c > s1))) continue;
+    const float t = (c - s0) / (s1 - s0);
+    const float m = floorf(o0 + (o1 - o0) * t);
+    float z = az + (bz - az) * t;
+    if (z != z) continue;
+    z = z > 0.0f ? (z < 1.0f ? z : 1.0f) : 0.0f;                          // the depth range [0, 1]
+    for (int r = 0; r < width; ++r) {
+      const float mr = m + (float)r;
+      if (!(mr >= 0.0f && mr < (float)n_minor)) continue;
+      const int px = xmajor ? i : (int)mr, py = xmajor ? (int)mr : i;
+      overlay_fragment(fb_d, key, py * w + px, z, id);
+    }
+  }
+}
+
 __global__ __launch_bounds__(64) void k_frustum_lines(FrustumParams Q, const float* __restrict__ fb_d, unsigned long long* __restrict__ key) {
   const int prim = blockIdx.x, s = prim / 13, k = prim % 13, lane = threadIdx.x;
   const uint32_t id = (uint32_t)prim;                                    // stream * 13 + k: the draw order
@@ -156,30 +196,7 @@ __global__ __launch_bounds__(64) void k_frustum_lines(FrustumParams Q, const flo
     for (int q = lane; q < nx * ny; q += 64) overlay_fragment(fb_d, key, (y0 + q / nx) * Q.w + x0 + q % nx, zw, id);
     return;
   }
-  float4 a = frustum_clip(Q, Q.corner[s][c_frustum_lines[k][0]]), b = frustum_clip(Q, Q.corner[s][c_frustum_lines[k][1]]);
-  if (!clip_plane(a, b, a.z + a.w, b.z + b.w) || !clip_plane(a, b, a.w - a.z, b.w - b.z)) return;   // near, then far
-  if (!(a.w > 0.0f) || !(b.w > 0.0f)) return;
-  const float ax = (a.x / a.w * 0.5f + 0.5f) * W, ay = (a.y / a.w * 0.5f + 0.5f) * H, az = a.z / a.w * 0.5f + 0.5f;
-  const float bx = (b.x / b.w * 0.5f + 0.5f) * W, by = (b.y / b.w * 0.5f + 0.5f) * H, bz = b.z / b.w * 0.5f + 0.5f;
-  // diamond exit for width 1: an x-major line makes one fragment per pixel column whose centre c lies in [start, end) along the line's
-  // direction, in the row floor(y(c)); y-major the same with rows
-  const bool xmajor = fabsf(bx - ax) >= fabsf(by - ay);
-  const float s0 = xmajor ? ax : ay, s1 = xmajor ? bx : by, o0 = xmajor ? ay : ax, o1 = xmajor ? by : bx;
-  const int n_major = xmajor ? Q.w : Q.h, n_minor = xmajor ? Q.h : Q.w;
-  const float lo = fmaxf(floorf(fminf(s0, s1)) - 1.0f, 0.0f), hi = fminf(ceilf(fmaxf(s0, s1)) + 1.0f, (float)(n_major - 1));
-  if (!(lo <= hi)) return;
-  for (int i = (int)lo + lane; i <= (int)hi; i += 64) {
-    const float c = (float)i + 0.5f;
-    if (!(s1 > s0 ? (c >= s0 && c < s1) : (c <= s0 && c > s1))) continue;
-    const float t = (c - s0) / (s1 - s0);
-    const float m = floorf(o0 + (o1 - o0) * t);
-    if (!(m >= 0.0f && m < (float)n_minor)) continue;
-    float z = az + (bz - az) * t;
-    if (z != z) continue;
-    z = z > 0.0f ? (z < 1.0f ? z : 1.0f) : 0.0f;                          // the depth range [0, 1]
-    const int px = xmajor ? i : (int)m, py = xmajor ? (int)m : i;
-    overlay_fragment(fb_d, key, py * Q.w + px, z, id);
-  }
+  overlay_line(frustum_clip(Q, Q.corner[s][c_frustum_lines[k][0]]), frustum_clip(Q, Q.corner[s][c_frustum_lines[k][1]]), Q.w, Q.h, 1, id, lane, fb_d, key);
 }
 
 __global__ __launch_bounds__(256) void k_frustum_resolve(int n, const unsigned long long* __restrict__ key, float4* __restrict__ fb_c, float* __restrict__ fb_d) {
@@ -197,6 +214,66 @@ void launch_draw_frustums(hipStream_t st, const FrustumParams& Q, unsigned long 
   hipLaunchKernelGGL(k_overlay_clear, dim3((n + 255) / 256), dim3(256), 0, st, fb_d, key, n);
   hipLaunchKernelGGL(k_frustum_lines, dim3(Q.n * 13), dim3(64), 0, st, Q, fb_d, key);
   hipLaunchKernelGGL(k_frustum_resolve, dim3((n + 255) / 256), dim3(256), 0, st, n, key, fb_c, fb_d);
+}
+
+// ---- the bounding-box wireframe: gloost::BoundingBox::draw() -> drawWiredBox (gloostRenderGoodies.h:251-304), glLineWidth(2).  Six
+// GL_LINE_LOOPs of four corners (front, right, back, left, top, bottom), each closed by its v3 -> v0 segment: 24 segments, one wave each,
+// primitive index 4 * loop + k.  A corner is x | y << 1 | z << 2 with 0 = bbox_min and 1 = bbox_max on that axis.
+__constant__ uint8_t c_bbox_loops[6][4] = {{4, 5, 7, 6}, {5, 1, 3, 7}, {1, 0, 2, 3}, {0, 4, 6, 2}, {6, 7, 3, 2}, {0, 1, 5, 4}};
+
+__device__ __forceinline__ float4 bbox_clip(const BBoxParams& Q, int corner) {   // P . (MV . p)
+  const float4 e = mat_mul(Q.mv, (corner & 1) ? Q.hi[0] : Q.lo[0], (corner & 2) ? Q.hi[1] : Q.lo[1], (corner & 4) ? Q.hi[2] : Q.lo[2], 1.0f);
+  return mat_mul(Q.proj, e.x, e.y, e.z, e.w);
+}
+
+__global__ __launch_bounds__(64) void k_bbox_lines(BBoxParams Q, const float* __restrict__ fb_d, unsigned long long* __restrict__ key) {
+  const int prim = blockIdx.x, loop = prim >> 2, k = prim & 3;
+  overlay_line(bbox_clip(Q, c_bbox_loops[loop][k]), bbox_clip(Q, c_bbox_loops[loop][(k + 1) & 3]), Q.w, Q.h, 2, (uint32_t)prim, threadIdx.x, fb_d, key);
+}
+
+__global__ __launch_bounds__(256) void k_bbox_resolve(int n, const unsigned long long* __restrict__ key, float4* __restrict__ fb_c, float* __restrict__ fb_d) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned long long k = key[i];
+  if ((uint32_t)k == kNoId) return;
+  fb_c[i] = make_float4(1.0f, 1.0f, 1.0f, 0.75f);                        // glColor4f(1, 1, 1, 0.75), BoundingBox.cpp:304-305
+  fb_d[i] = __uint_as_float((uint32_t)(k >> 32));
+}
+
+void launch_draw_bbox(hipStream_t st, const BBoxParams& Q, unsigned long long* key, float4* fb_c, float* fb_d) {
+  const int n = Q.w * Q.h;
+  hipLaunchKernelGGL(k_overlay_clear, dim3((n + 255) / 256), dim3(256), 0, st, fb_d, key, n);
+  hipLaunchKernelGGL(k_bbox_lines, dim3(24), dim3(64), 0, st, Q, fb_d, key);
+  hipLaunchKernelGGL(k_bbox_resolve, dim3((n + 255) / 256), dim3(256), 0, st, n, key, fb_c, fb_d);
+}
+
+// ---- the texture view: TextureBlitter::blit(unit, res) (texture_blitter.cpp, glsl/texture_passthrough.{vs,fs} mode 0) of texture unit 15
+// (the hole-filling atlas) or 16 (the brick depth-limit image) into the viewport (0, 0, vw, vh), one lane per output pixel.  No depth test,
+// no depth write: fb_d is not touched, nor is any pixel outside the viewport.
+__device__ __forceinline__ float4 blit_texel(const BlitParams& Q, int x, int y) {
+  const size_t o = (size_t)y * (size_t)Q.sw + (size_t)x;
+  if (!Q.peels) return Q.src[o];
+  // the depth-limit image as GL's MIN blend leaves it, clear (1, 0, 1, 0) (recon_integration.cpp:144): the peels hold (min z, MAX z, min
+  // back-face z, 0) as bits, GL's green channel is min(0, -z) = 0 - max z (+0 where no brick fragment landed)
+  const uint4 p = ((const uint4*)Q.src)[o];
+  return make_float4(__uint_as_float(p.x), 0.0f - __uint_as_float(p.y), __uint_as_float(p.z), __uint_as_float(p.w));
+}
+
+__global__ __launch_bounds__(256) void k_blit_texture(BlitParams Q, float4* __restrict__ fb_c) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Q.vw * Q.vh) return;
+  const int x = i % Q.vw, y = i / Q.vw;
+  const float u = ((float)x + 0.5f) / (float)Q.vw, v = ((float)y + 0.5f) / (float)Q.vh;   // the full-screen triangle's texcoord at the pixel centre
+  const Axis X = axis_linear(u, Q.sw), Y = axis_linear(v, Q.sh);          // LINEAR, CLAMP_TO_EDGE (= MIRRORED_REPEAT for u, v in [0, 1])
+  const float4 t00 = blit_texel(Q, X.i0, Y.i0), t10 = blit_texel(Q, X.i1, Y.i0), t01 = blit_texel(Q, X.i0, Y.i1), t11 = blit_texel(Q, X.i1, Y.i1);
+  fb_c[(size_t)y * Q.fw + x] = make_float4(lerpf(lerpf(t00.x, t10.x, X.a), lerpf(t01.x, t11.x, X.a), Y.a),
+                                           lerpf(lerpf(t00.y, t10.y, X.a), lerpf(t01.y, t11.y, X.a), Y.a),
+                                           lerpf(lerpf(t00.z, t10.z, X.a), lerpf(t01.z, t11.z, X.a), Y.a), 1.0f);   // vec4(texture(..).rgb, 1)
+}
+
+void launch_blit_texture(hipStream_t st, const BlitParams& Q, float4* fb_c) {
+  const int n = Q.vw * Q.vh;
+  hipLaunchKernelGGL(k_blit_texture, dim3((n + 255) / 256), dim3(256), 0, st, Q, fb_c);
 }
 
 }  // namespace rr

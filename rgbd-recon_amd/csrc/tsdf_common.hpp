@@ -208,6 +208,21 @@ struct FrustumParams {
 constexpr float kCalibVisLimit = 0.01f;   // recon_calibs.cpp:20 (static; not the context's setTsdfLimit value)
 void launch_draw_calibvis(hipStream_t st, const CalibVisParams& Q, const Volume& V, unsigned long long* key, float4* fb_c, float* fb_d);
 void launch_draw_frustums(hipStream_t st, const FrustumParams& Q, unsigned long long* key, float4* fb_c, float* fb_d);
+// ... and the two after them: the bounding-box wireframe (gloost::BoundingBox::draw) and the texture view (TextureBlitter::blit)
+struct BBoxParams {
+  Mat4 mv, proj;
+  float lo[3], hi[3];           // bbox_min / bbox_max as configured (g_bbox)
+  int w, h;
+};
+struct BlitParams {
+  const float4* src;            // unit 15: the hole-filling atlas (RGBA32F); unit 16: the depth-limit peels (bits, see k_blit_texture)
+  int peels;                    // 1: src is the peel image
+  int sw, sh;                   // the source's size
+  int vw, vh;                   // the blit viewport (0, 0, vw, vh)
+  int fw;                       // framebuffer row length
+};
+void launch_draw_bbox(hipStream_t st, const BBoxParams& Q, unsigned long long* key, float4* fb_c, float* fb_d);
+void launch_blit_texture(hipStream_t st, const BlitParams& Q, float4* fb_c);
 // the 8 corner texels of a forward volume [rz][ry][rx][3] in getCornerPoints order (calib_inverter.cpp)
 void frustum_corners(const float* cv_xyz, const uint32_t res[3], float out[8][3]);
 

@@ -185,6 +185,32 @@ class CalibVolumesHip {
   ReconIntegrationHip& m_recon;
 };
 
+// The last two draws of the client's mono frame (kinect_client.cpp:685-707), over the same context and its matrices: the bounding-box wireframe
+// g_bbox.draw() (gloost::BoundingBox::draw, BoundingBox.cpp:298-318; the box is the context's bbox_min / bbox_max) and the texture view
+// TextureBlitter::blit(15 + g_num_texture % 2, resolution_full / 2) (texture_blitter.cpp).
+class BoundingBoxHip {
+ public:
+  explicit BoundingBoxHip(ReconIntegrationHip& recon) : m_recon(recon) {}
+  void draw() const { check(tsdf_draw_bbox(m_recon.handle(), m_recon.modelview(), m_recon.projection())); }
+
+ private:
+  void check(int32_t rc) const { if (rc != TSDF_OK) throw std::runtime_error(std::string("BoundingBoxHip: ") + tsdf_last_error(m_recon.handle())); }
+  ReconIntegrationHip& m_recon;
+};
+class TextureBlitterHip {
+ public:
+  explicit TextureBlitterHip(ReconIntegrationHip& recon) : m_recon(recon) {}
+  // unit 15 (the hole-filling atlas) or 16 (the depth-limit image): the client's 15 + g_num_texture % 2; the viewport is resolution_full / 2
+  void blit(unsigned unit) const {
+    if (unit != 15 && unit != 16) throw std::invalid_argument("TextureBlitterHip: the client blits texture unit 15 or 16");
+    check(tsdf_draw_textures(m_recon.handle(), unit - 15));
+  }
+
+ private:
+  void check(int32_t rc) const { if (rc != TSDF_OK) throw std::runtime_error(std::string("TextureBlitterHip: ") + tsdf_last_error(m_recon.handle())); }
+  ReconIntegrationHip& m_recon;
+};
+
 // The input side: kinect::NetKinectArray's public surface (framework/NetKinectArray.h:40-55) over the SAME context, for callers
 // that also replace the GL upload / pre-process.  The ZMQ socket stays with the caller: where readLoop() memcpy's the received
 // message into the PBOs (NetKinectArray.cpp:513-523), hand it to submit().
