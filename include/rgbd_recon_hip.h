@@ -417,6 +417,17 @@ int32_t tsdf_upload_brick_counters(tsdf_ctx* ctx, const uint32_t* counters);
  * lists of the occupied bricks, recon_integration.cpp:254-258): x-fastest tile indices relative to tile layer grid[2];
  * grid = {tiles along x, tiles along y, first integrated tile layer, number of integrated tiles}.  ids may be NULL (count only) */
 int32_t tsdf_download_active_tiles(tsdf_ctx* ctx, uint32_t* ids, uint32_t capacity, uint32_t* count, uint32_t grid[4]);
+/* Which integrate kernel the last tsdf_integrate() launched (tests assert the path they are about; the choice follows the inverse LUTs' texel box per
+ * 8^3 tile against the LDS budget, the RR_K1_FORM cap and the projection-cache budget).  out[0] = TSDF_K1_*, out[1] = workgroups of that launch
+ * (TSDF_K1_CACHED: of the LDS kernel that takes the tiles the cache does not hold), out[2] = its work items (tiles: the active list of a culled launch,
+ * every integrated tile of a dense one), out[3] = 1 culled / 0 dense.  out[1] < out[2]: the workgroups stride over the items.  Read-only; a culled
+ * launch's item count is read from the device (synchronises like tsdf_download_active_tiles).  TSDF_ERR_STATE before the first integrate(). */
+#define TSDF_K1_GENERIC 0u        /* k_integrate_tiles: every LUT tap from global memory (a tile's texel box exceeds the LDS budget) */
+#define TSDF_K1_LDS_DIRECT 1u     /* k_integrate_tiles_lds, 8 taps per voxel out of the LDS box */
+#define TSDF_K1_LDS_SEPARABLE 2u  /* k_integrate_tiles_lds, separable x / y passes */
+#define TSDF_K1_RECORD 3u         /* k_integrate_tiles_rec: work records written by the pair-mask pass */
+#define TSDF_K1_CACHED 4u         /* k_integrate_cached + the separable LDS kernel for uncached tiles (projection cache) */
+int32_t tsdf_integrate_form(tsdf_ctx* ctx, uint32_t out[4]);
 /* raymarch target level 0: rgba [h][w][4], depth [h][w], nsamples [h][w], depth peels [h][w][4]; any may be NULL */
 int32_t tsdf_download_image(tsdf_ctx* ctx, float* rgba, float* depth, float* nsamples, float* peels);
 int32_t tsdf_upload_image(tsdf_ctx* ctx, const float* rgba, const float* depth);

@@ -175,6 +175,7 @@ def read_stream_record(path, record_bytes, frame):
 
 COLOR_RGB8, COLOR_DXT1, COLOR_DXT5 = 0, 1, 5
 DEPTH_F32, DEPTH_U8 = 0, 1
+K1_FORMS = ("generic", "lds_direct", "lds_separable", "record", "cached")   # TSDF_K1_* of rgbd_recon_hip.h
 
 
 class ReconIntegrationHip:
@@ -510,6 +511,12 @@ class ReconIntegrationHip:
         ids = ids[:n.value].astype(np.int64)
         ntx, nty, tz0 = int(grid[0]), int(grid[1]), int(grid[2])
         return np.stack([ids % ntx, (ids // ntx) % nty, tz0 + ids // (ntx * nty)], -1), int(grid[3])
+
+    def integrate_form(self):
+        """dict of the last integrate() launch (tsdf_integrate_form): form (one of K1_FORMS), grid (workgroups), items (tiles), culled"""
+        out = (C.c_uint32 * 4)()
+        self._ck(self._L.tsdf_integrate_form(self._c, out))
+        return dict(form=K1_FORMS[int(out[0])], grid=int(out[1]), items=int(out[2]), culled=bool(out[3]))
 
     def set_counters(self, a):
         a = np.ascontiguousarray(a, np.uint32)

@@ -571,6 +571,7 @@ void release_volume(tsdf_ctx* c) {
   hipFree(c->d_tile_list[0]); hipFree(c->d_tile_list[1]); hipFree(c->d_tile_counts); hipFree(c->d_linear); hipFree(c->d_tile_bounds); hipFree(c->d_pair_masks); c->d_pair_masks = nullptr; hipFree(c->d_work_recs); c->d_work_recs = nullptr;
   hipFree(c->proj.data); hipFree(c->proj.slot); hipFree(c->proj.items); hipFree(c->d_proj_words); hipFree(c->d_item_stats);
   c->proj = ProjCache{}; c->d_proj_words = nullptr; c->d_item_stats = nullptr; c->proj_failed = false; c->last_integrate_cached = false;
+  c->last_k1 = IntegrateLaunch{-1, 0};
   hipFree(c->alt.data); hipFree(c->alt.cls_all); hipFree(c->alt.stamp); hipFree(c->alt.list[0]); hipFree(c->alt.list[1]); hipFree(c->alt.counts);
   c->alt = tsdf_ctx::VolSet{}; c->deep_failed = false;
   c->vol.data = nullptr; c->vol.slot = nullptr; c->tiles.stamp = nullptr; c->d_cls_all = nullptr;
@@ -1584,7 +1585,8 @@ int32_t tsdf_integrate(tsdf_ctx* c) {
     timer_end_on(c, "k_pair_masks", lane);
   }
   timer_begin_on(c, "k_integrate_tiles", lane);                                // the kernel(s) alone (bench.py's roofline)
-  launch_integrate(lane, c->luts, c->frame, c->vol, c->br, c->tiles, c->use_bricks ? 1 : 0, lds, 0, c->frame_stamp, 4, nullptr, bounds, bounds ? c->d_pair_masks : nullptr, proj, bounds && c->use_recs ? c->d_work_recs : nullptr);
+  launch_integrate(lane, c->luts, c->frame, c->vol, c->br, c->tiles, c->use_bricks ? 1 : 0, lds, 0, c->frame_stamp, 4, nullptr, bounds, bounds ? c->d_pair_masks : nullptr, proj, bounds && c->use_recs ? c->d_work_recs : nullptr, &c->last_k1);
+  c->last_k1_culled = c->use_bricks;
   timer_end_on(c, "k_integrate_tiles", lane);
   if (c->use_bricks) { c->tile_parity ^= 1; c->full_classify = false; }
   else c->full_classify = true;                                       // a dense pass wrote every tile: the next culled frame must look at all of them
@@ -2211,6 +2213,21 @@ int32_t tsdf_download_active_tiles(tsdf_ctx* c, uint32_t* ids, uint32_t capacity
   *count = n;
   if (grid) { grid[0] = (uint32_t)c->vol.ntx; grid[1] = (uint32_t)c->vol.nty; grid[2] = (uint32_t)c->vol.int_tz0; grid[3] = (uint32_t)c->tiles.n; }
   if (ids && capacity) HIP_TRY(c, hipMemcpy(ids, c->d_tile_list[p], (size_t)std::min(n, capacity) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return TSDF_OK;
+}
+// which integrate kernel the last tsdf_integrate launched, its grid and its work items: host values of the launcher; the culled launch's
+// item count lives on the device (the compacted tile list's length), read like tsdf_download_active_tiles reads it
+int32_t tsdf_integrate_form(tsdf_ctx* c, uint32_t out[4]) {
+  CHECK_CTX(c);
+  if (!out) return TSDF_ERR_INVALID_ARGUMENT;
+  if (c->last_k1.form < 0) FAIL(c, TSDF_ERR_STATE, "no integrate() since the volume was set up");
+  uint32_t n = (uint32_t)c->tiles.n;
+  if (c->last_k1_culled) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, sync_ctx(c));
+    HIP_TRY(c, hipMemcpy(&n, c->d_tile_counts + (c->tile_parity ^ 1), sizeof(uint32_t), hipMemcpyDeviceToHost));   // integrate() flipped the parity after its launches
+  }
+  out[0] = (uint32_t)c->last_k1.form; out[1] = c->last_k1.grid; out[2] = n; out[3] = c->last_k1_culled ? 1u : 0u;
   return TSDF_OK;
 }
 int32_t tsdf_download_bricks(tsdf_ctx* c, uint32_t* counters, uint8_t* flags) {

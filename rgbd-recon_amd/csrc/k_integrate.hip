@@ -219,7 +219,9 @@ __global__ __launch_bounds__(256) void k_classify_lists(Volume V, Bricks B, Tile
 // means that such a tile needs no reset when it stops being active.  One __syncthreads_and per tile.
 __device__ __forceinline__ void store_tile_class(const TileState& S, int tile, bool mine_all_clear) {
   // one ballot per wave, one LDS flag per wave, ONE barrier (round 4; __syncthreads_and is a DPP reduction, an LDS atomic and three barriers).  The flags are
-  // read by thread 0 right behind the barrier and written again one whole tile later, behind that tile's own barriers.
+  // read by thread 0 right behind the barrier.  The CALLER keeps the next call's flag writes behind that read: a workgroup that calls this once per loop
+  // iteration needs a barrier of its own between two calls (the LDS and record kernels have their phase barriers there; k_integrate_tiles, whose loop body
+  // has no other barrier, ends every iteration with one).
   __shared__ int s_wave_clear[4];
   const bool wave_clear = __ballot(!mine_all_clear) == 0ull;
   if ((threadIdx.x & 63) == 0) s_wave_clear[threadIdx.x >> 6] = wave_clear ? 1 : 0;
@@ -264,6 +266,9 @@ __global__ __launch_bounds__(256) void k_integrate_tiles(StreamTable T, FrameIma
       out[l] = v[half];
     }
     store_tile_class(S, tile, v[0] == -limit && v[1] == -limit);
+    // the loop body has no other barrier: without this one waves 1..3 could finish the workgroup's NEXT tile and overwrite their class flags before
+    // thread 0 has read this tile's (a wrong kTileMinus: a missed reset when the tile goes stale, a tile the dense march leaps over)
+    __syncthreads();
   }
 }
 
@@ -1136,7 +1141,7 @@ void launch_item_stats(hipStream_t st, const StreamTable& T, const TileState& S,
 
 void launch_integrate(hipStream_t st, const StreamTable& T, const FrameImages& F, const Volume& V, const Bricks& B, const TileState& S, int use_bricks, int lds_ok,
                       int full_classify, uint32_t frame_stamp, int phase, const PeelClear* pc, const float4* tile_bounds, uint32_t* pair_masks, const ProjCache* proj,
-                      uint4* work_recs) {
+                      uint4* work_recs, IntegrateLaunch* info) {
   // phase 1: tile classification + stale-tile clear; 2: pair-mask pass + integrate kernel(s); 3: the pair-mask pass alone; 4: the integrate
   // kernel(s) alone; 0: everything (the split lets the caller time the kernels separately)
   const ProjCache none_pc{};
@@ -1168,32 +1173,39 @@ void launch_integrate(hipStream_t st, const StreamTable& T, const FrameImages& F
     static const int forced = [] { const char* e = getenv("RR_K1_GRID"); return e ? atoi(e) : 0; }();                  // A/B hook
     const int cap = forced > 0 ? forced : (S.n <= 262144 ? 2048 : 4096);
     const dim3 grid(S.n < cap ? S.n : cap);
+    int form;
     if (cached) {
+      form = kFormCached;
       hipLaunchKernelGGL((k_integrate_cached<true, RR_K1C_CHUNK>), dim3(RR_K1C_GRID), dim3(64), 0, st, T.n, F, V, B, S, pvc, S.count, S.list, pair_masks, PC.items, PC);
       hipLaunchKernelGGL((k_integrate_tiles_lds<true, true, true, true>), grid, dim3(256), 0, st, T, F, V, B, S, pvc, pair_masks, PC);
     }
-    else if (rec && pvc) hipLaunchKernelGGL((k_integrate_tiles_rec<true, true>), grid, dim3(256), 0, st, T, F, V, B, S, work_recs, (const unsigned long long*)(work_recs + S.n));
-    else if (rec) hipLaunchKernelGGL((k_integrate_tiles_rec<true, false>), grid, dim3(256), 0, st, T, F, V, B, S, work_recs, (const unsigned long long*)nullptr);
-    else if (ranges) hipLaunchKernelGGL((k_integrate_tiles_lds<true, true, true>), grid, dim3(256), 0, st, T, F, V, B, S, pvc, pair_masks, PC);
-    else if (lds_ok >= 2) hipLaunchKernelGGL((k_integrate_tiles_lds<true, true>), grid, dim3(256), 0, st, T, F, V, B, S, pvc, nullptr, PC);
-    else if (lds_ok) hipLaunchKernelGGL((k_integrate_tiles_lds<true, false>), grid, dim3(256), 0, st, T, F, V, B, S, pvc, nullptr, PC);
-    else hipLaunchKernelGGL(k_integrate_tiles<true>, grid, dim3(256), 0, st, T, F, V, B, S, pvc);
+    else if (rec && pvc) { form = kFormRecord; hipLaunchKernelGGL((k_integrate_tiles_rec<true, true>), grid, dim3(256), 0, st, T, F, V, B, S, work_recs, (const unsigned long long*)(work_recs + S.n)); }
+    else if (rec) { form = kFormRecord; hipLaunchKernelGGL((k_integrate_tiles_rec<true, false>), grid, dim3(256), 0, st, T, F, V, B, S, work_recs, (const unsigned long long*)nullptr); }
+    else if (ranges) { form = kFormLdsSeparable; hipLaunchKernelGGL((k_integrate_tiles_lds<true, true, true>), grid, dim3(256), 0, st, T, F, V, B, S, pvc, pair_masks, PC); }
+    else if (lds_ok >= 2) { form = kFormLdsSeparable; hipLaunchKernelGGL((k_integrate_tiles_lds<true, true>), grid, dim3(256), 0, st, T, F, V, B, S, pvc, nullptr, PC); }
+    else if (lds_ok) { form = kFormLdsDirect; hipLaunchKernelGGL((k_integrate_tiles_lds<true, false>), grid, dim3(256), 0, st, T, F, V, B, S, pvc, nullptr, PC); }
+    else { form = kFormGeneric; hipLaunchKernelGGL(k_integrate_tiles<true>, grid, dim3(256), 0, st, T, F, V, B, S, pvc); }
+    if (info) *info = IntegrateLaunch{form, grid.x};
   } else {
+    int form;
+    dim3 grid(S.n);
     if (cached) {
+      form = kFormCached;
       hipLaunchKernelGGL((k_integrate_cached<false, RR_K1C_CHUNK>), dim3((unsigned)(((S.n + 7) >> 3) << 6)), dim3(64), 0, st, T.n, F, V, B, S, 0, S.count, S.list, pair_masks, PC.items, PC);
-      hipLaunchKernelGGL((k_integrate_tiles_lds<false, true, true, true>), dim3(S.n), dim3(256), 0, st, T, F, V, B, S, 0, pair_masks, PC);
+      hipLaunchKernelGGL((k_integrate_tiles_lds<false, true, true, true>), grid, dim3(256), 0, st, T, F, V, B, S, 0, pair_masks, PC);
     }
     else if (ranges) {
       // at most 16 384 workgroups striding over the tiles instead of one per tile: the launch alone is as fast (119 us at c1), the frame beside the other
       // lanes 2.5 % faster (4 349 against 4 242 frames/s; 8 192: 4 380 but the launch alone 125 us, 2 048: 3 796); RR_K1_DENSE_GRID: A/B hook
       static const int dcap = [] { const char* e = getenv("RR_K1_DENSE_GRID"); return e ? atoi(e) : 16384; }();
-      const dim3 dgrid(dcap > 0 && dcap < S.n ? dcap : S.n);
-      if (rec) hipLaunchKernelGGL((k_integrate_tiles_rec<false, false>), dgrid, dim3(256), 0, st, T, F, V, B, S, work_recs, (const unsigned long long*)nullptr);
-      else hipLaunchKernelGGL((k_integrate_tiles_lds<false, true, true>), dgrid, dim3(256), 0, st, T, F, V, B, S, 0, pair_masks, PC);
+      grid = dim3(dcap > 0 && dcap < S.n ? dcap : S.n);
+      if (rec) { form = kFormRecord; hipLaunchKernelGGL((k_integrate_tiles_rec<false, false>), grid, dim3(256), 0, st, T, F, V, B, S, work_recs, (const unsigned long long*)nullptr); }
+      else { form = kFormLdsSeparable; hipLaunchKernelGGL((k_integrate_tiles_lds<false, true, true>), grid, dim3(256), 0, st, T, F, V, B, S, 0, pair_masks, PC); }
     }
-    else if (lds_ok >= 2) hipLaunchKernelGGL((k_integrate_tiles_lds<false, true>), dim3(S.n), dim3(256), 0, st, T, F, V, B, S, 0, nullptr, PC);
-    else if (lds_ok) hipLaunchKernelGGL((k_integrate_tiles_lds<false, false>), dim3(S.n), dim3(256), 0, st, T, F, V, B, S, 0, nullptr, PC);
-    else hipLaunchKernelGGL(k_integrate_tiles<false>, dim3(S.n), dim3(256), 0, st, T, F, V, B, S, 0);
+    else if (lds_ok >= 2) { form = kFormLdsSeparable; hipLaunchKernelGGL((k_integrate_tiles_lds<false, true>), grid, dim3(256), 0, st, T, F, V, B, S, 0, nullptr, PC); }
+    else if (lds_ok) { form = kFormLdsDirect; hipLaunchKernelGGL((k_integrate_tiles_lds<false, false>), grid, dim3(256), 0, st, T, F, V, B, S, 0, nullptr, PC); }
+    else { form = kFormGeneric; hipLaunchKernelGGL(k_integrate_tiles<false>, grid, dim3(256), 0, st, T, F, V, B, S, 0); }
+    if (info) *info = IntegrateLaunch{form, grid.x};
   }
 }
 int integrate_box_cap() { return kBoxCap; }

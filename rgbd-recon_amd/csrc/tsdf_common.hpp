@@ -271,12 +271,17 @@ void launch_update_occupied(hipStream_t st, const Bricks& B, uint32_t min_voxels
 // PeelClear: the peel-tile reset of the coming draw (k_raymarch.hip's k_clear_peel_tiles) rides along in the k_classify_lists launch
 // ... and so does the zeroing of the spare brick-counter buffer (`zero`, in 16-byte units of zero_words / 4)
 struct PeelClear { uint4* peels; const uint8_t* touched_prev; int w, h, ntx, n_tiles; uint32_t* zero; uint32_t zero_words; };   // null pointers: nothing to do
+// which kernel the integrate launch (phase 0 / 2 / 4) was and how many workgroups it got: host values, for tsdf_integrate_form.  The forms are the
+// TSDF_K1_* values of rgbd_recon_hip.h; kFormCached = k_integrate_cached + the separable LDS kernel for the tiles the cache does not hold (grid: the latter's)
+enum { kFormGeneric = 0, kFormLdsDirect = 1, kFormLdsSeparable = 2, kFormRecord = 3, kFormCached = 4 };
+struct IntegrateLaunch { int form; uint32_t grid; };
 void launch_integrate(hipStream_t st, const StreamTable& T, const FrameImages& F, const Volume& V, const Bricks& B, const TileState& S, int use_bricks, int lds_ok,
                       int full_classify, uint32_t frame_stamp, int phase = 0, const PeelClear* pc = nullptr,
                       const float4* tile_bounds = nullptr,   // per (stored tile, stream) 2 x float4 LUT-box bounds (launch_tile_bounds), or null
                       uint32_t* pair_masks = nullptr,         // per work item: the frame's pair classes (written by the launch itself), or null
                       const ProjCache* proj = nullptr,        // projection cache (needs tile_bounds / pair_masks: its work items are classified by the pair-mask pass), or null
-                      uint4* work_recs = nullptr);            // per work item: the 16-byte record of k_integrate_tiles_rec (written by the pair-mask pass), or null
+                      uint4* work_recs = nullptr,             // per work item: the 16-byte record of k_integrate_tiles_rec (written by the pair-mask pass), or null
+                      IntegrateLaunch* info = nullptr);       // out: what the integrate launch itself was (untouched by phases 1 and 3)
 // [work items, cached items, (tile, stream) pairs of cached items evaluated per voxel, items taken by the LDS kernel] of the last launch -> out[4] (device)
 void launch_item_stats(hipStream_t st, const StreamTable& T, const TileState& S, int use_bricks, const uint32_t* pair_masks, const ProjCache& PC, uint32_t* out);
 void launch_tile_bounds(hipStream_t st, const StreamTable& T, const Volume& V, float4* bounds);

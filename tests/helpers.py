@@ -73,3 +73,26 @@ def assert_frames_identical(hip, orc, what="", min_hits=1, colour_atol=0.0):
     n = int((fd < 1).sum())
     assert n >= min_hits, f"{what}: only {n} covered pixels"
     return n
+
+
+LDS_BOX_CAP, LDS_ROW_CAP = 384, 512     # LUT texels per stream / x-pass rows the LDS integrate kernels hold (kBoxCap, kRowCap of k_integrate.hip)
+
+
+def lut_box_class(res, inv_res):
+    """The integrate kernel's selection rule, restated: (largest LUT texel box per axis any 8^3-voxel tile of a `res` volume touches in an
+    `inv_res` LUT -- the GL linear filter's two taps per axis, fp32 as the kernels index --, class) with class 0 = the box does not fit the
+    LDS budget (generic kernel), 1 = the box fits (direct 8-tap LDS form), 2 = the separable passes' rows and planes fit too."""
+    worst = []
+    for r, n in zip(res, inv_res):
+        r, n = int(r), int(n)
+        step = np.float32(1.0) / np.float32(r)
+
+        def tap(v, up):
+            f = (np.float32(v) + np.float32(0.5)) * step * np.float32(n) - np.float32(0.5)
+            k = int(min(max(np.floor(f), np.float32(-1.0)), np.float32(n)))
+            return min(max(k + up, 0), n - 1)
+        worst.append(max(tap(min(t * 8 + 7, r - 1), 1) - tap(t * 8, 0) + 1 for t in range((r + 7) // 8)))
+    dx, dy, dz = worst
+    if dx * dy * dz > LDS_BOX_CAP:
+        return tuple(worst), 0
+    return tuple(worst), 2 if (dy * dz * 8 <= LDS_ROW_CAP and dz * 64 <= LDS_BOX_CAP) else 1

@@ -67,6 +67,8 @@ def test_config2_512cubed_cull_and_inpaint(rr):
         o.clearOccupiedBricks(); o.markBricks(); ratios.append(o.updateOccupiedBricks()); o.integrate(); o.draw(mv, pr)
     assert ratios[0] == ratios[1] and 0.002 < ratios[0] < 0.05
     np.testing.assert_array_equal(hip.bricks()[0], orc.counters())
+    form = hip.integrate_form()                                              # the measured hot path: the record kernel, 2048 workgroups striding over the active tiles
+    assert form["form"] == "record" and form["culled"] and form["grid"] == 2048 and form["items"] == len(hip.active_tiles()[0]) > 0
     assert same(hip.tsdf(), orc.tsdf()).all()
     (ha, hd, hn, hp), (oa, od, on, op) = hip.view_images(), orc.view_images()
     assert same(hp, op).all()                                                # depth peels (min-z of the occupied bricks' faces)

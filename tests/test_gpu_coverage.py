@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import assert_frames_identical, assert_same
+from helpers import assert_frames_identical, assert_same, lut_box_class
 from oracle.oracle import OracleRecon
 
 pytestmark = pytest.mark.gpu
@@ -44,13 +44,19 @@ def test_lut_finer_than_volume_takes_the_global_path(rr):
     for o in (hip, orc):
         o.setUseBricks(False)
         o.integrate()
+    assert lut_box_class((32, 32, 32), (64, 64, 64))[1] == 0
+    assert hip.integrate_form() == dict(form="generic", grid=64, items=64, culled=False)
     assert_same(hip.tsdf(), orc.tsdf(), "tsdf (global-memory integrate)")
 
 
-@pytest.mark.parametrize("res,inv_res", [((40, 40, 40), 28), ((40, 48, 56), 28), ((24, 24, 24), 20)])
-def test_lds_box_near_its_capacity(rr, res, inv_res):
-    """LUT nearly as fine as the volume: a tile's texel box is 6..7 texels per axis (up to 343 of the 384 the LDS path holds),
-    boxes of different shapes per axis, partial tiles at the volume border -- still the LDS kernel, dense and culled."""
+@pytest.mark.parametrize("res,inv_res,box,form", [((40, 40, 40), 28, (7, 7, 7), "lds_direct"), ((40, 48, 56), 28, (7, 6, 6), "record"),
+                                                  ((24, 24, 24), 20, (8, 8, 8), "generic")])
+def test_lds_box_near_its_capacity(rr, res, inv_res, box, form):
+    """LUT nearly as fine as the volume, partial tiles at the volume border, dense and culled.  A tile's texel box of 7 x 7 x 7 = 343 of the
+    384 texels the LDS path holds: the direct LDS form (7 planes are one too many for the separable passes); 7 x 6 x 6: the separable
+    form's budget holds, and with it the record kernel takes the launch; 8^3 = 512 (20 texels under 24 voxels -- this case was written as
+    an LDS case and never was one): just over the budget, the generic kernel.  tsdf_integrate_form says which kernel ran."""
+    assert lut_box_class(res, (inv_res,) * 3) == (box, {"generic": 0, "lds_direct": 1, "record": 2}[form])
     sc = rr.scene.make_scene(n_streams=3, width=96, height=72, lut_res=16, inv_res=inv_res)
     kw = dict(KW, res=res, brick_size=[2.0 / 5, 2.2 / 5, 2.0 / 5], limit=0.08)
     hip, orc = rr.ReconIntegrationHip(sc, **kw), OracleRecon(sc, **kw)
@@ -58,6 +64,8 @@ def test_lds_box_near_its_capacity(rr, res, inv_res):
         for o in (hip, orc):
             o.setUseBricks(use_bricks)
             o.clearOccupiedBricks(); o.markBricks(); o.updateOccupiedBricks(); o.integrate()
+        f = hip.integrate_form()
+        assert f["form"] == form and f["culled"] == use_bricks and 0 < f["items"] <= int(np.prod([(r + 7) // 8 for r in res]))
         a = hip.tsdf()
         assert_same(a, orc.tsdf(), f"tsdf (use_bricks={use_bricks})")
         assert (np.abs(a) < 0.08).sum() > 500
@@ -77,6 +85,8 @@ def test_all_three_integrate_kernels_give_the_same_volume(rr, small_scene, form,
         for o in (hip, orc):
             o.setUseBricks(use_bricks)
             o.clearOccupiedBricks(); o.markBricks(); o.updateOccupiedBricks(); o.integrate()
+        # (uncapped, the 32^3 LUT under 64^3 voxels -- a 6^3 box -- selects the separable budget, on which the record kernel runs by default)
+        assert hip.integrate_form()["form"] == {"3": "cached", "2": "record", "1": "lds_direct", "0": "generic"}[form]
         assert_same(hip.tsdf(), orc.tsdf(), f"tsdf (form {form}, use_bricks={use_bricks})")
 
 
@@ -108,6 +118,7 @@ def test_nan_and_out_of_range_lut_coordinates_sample_like_the_oracle(rr):
             o.integrate()
             o.integrate()
             o.drawF(mv, pr)
+        assert hip.integrate_form()["form"] == {"3": "cached", "2": "record", "1": "lds_direct", "0": "generic"}[form]
         assert_same(hip.tsdf(), orc.tsdf(), f"tsdf (form {form})")
         assert_frames_identical(hip, orc, f"frame (form {form})", min_hits=0)
 
