@@ -223,6 +223,32 @@ int32_t tsdf_download_mvt_vertices(tsdf_ctx* ctx, float* out);
  *   (24 segments; every box edge is drawn twice, once in each direction, and the first one drawn wins depth ties).  glLineWidth(2), aliased.
  *   Colour (1, 1, 1, 0.75) with GL_COLOR_MATERIAL on and lighting off, written unmodulated, no blending.  Timer "bbox".  Runs after any
  *   back-end (tsdf_draw_f, tsdf_draw_points, tsdf_draw_trigrid, tsdf_draw_mvt) and after the two overlays above (the client's order).
+ * tsdf_draw_bricks: "Draw occupied bricks" (g_draw_bricks, :83,275,409-410, key :764-765) = ReconIntegration::drawOccupiedBricks()
+ *   (recon_integration.cpp:447-454): the program linked from glsl/bricks.vs + glsl/solid.fs (:130-133), uniform Color = (1, 0, 0),
+ *   UnitCube::drawWireInstanced (unit_cube.cpp:20-29,74-83) with one instance per entry of m_bricks_occupied.  Per instance 12 GL_LINES
+ *   between the unit cube's vertices v0..v7 = (1,1,1) (0,1,1) (1,1,0) (0,1,0) (1,0,1) (0,0,1) (0,0,0) (1,0,0), start -> end in this order:
+ *   v0-v1 v0-v2 v0-v4 v5-v1 v5-v4 v5-v6 v3-v1 v3-v6 v3-v2 v7-v2 v7-v4 v7-v6.  A vertex p of brick id lies at world
+ *   float(index) * brick_size + bbox_min + p * brick_size per axis, in that operand order, index = index_3d(id) (bricks.vs:16-20,
+ *   inc_bricks.glsl:22-38), and goes through P * (MV * (world, 1)).  Every brick is drawn at the full brick size, the clipped last brick of
+ *   an axis too, so the wireframe can stick out of the bounding box.  Colour (1, 0, 0, 1) (solid.fs), width 1, aliased (the only
+ *   glLineWidth of the client is the bounding box's, inside glPushAttrib / glPopAttrib, external/gloost/BoundingBox.cpp:301-316).  The
+ *   instances are the bricks of the latest tsdf_update_occupied (:430-445: ascending brick id, threshold tsdf_set_min_voxels_per_brick),
+ *   whatever tsdf_set_use_bricks / tsdf_set_space_skip say; while there is no list (a new context, a new brick grid after
+ *   tsdf_set_voxel_size / tsdf_set_brick_size) nothing is drawn and the call returns TSDF_OK.  (As for every reader of the list: a
+ *   tsdf_mark_bricks issued since the latest update, with no draw, integrate or ratio read-back in between, may already have reset the
+ *   count for the coming update.)  Needs no volume: sparse-pool and Z-slab contexts draw the same lines (every rank marks the whole brick
+ *   grid).  This is the client's call while another back-end is showing (kinect_client.cpp:681-683), after "Draw TSDF" and "Draw
+ *   frustums" and before the bounding box.  Timer "brickwire" (the reference has none; "brickdraw" is the depth limits').
+ *   TSDF_ERR_STATE for a brick grid with 12 * bricks >= 2^32 - 1.
+ *   Assumed, not checkable without a GL implementation: that bricks.vs + solid.fs links although bricks.vs writes a non-flat uint output
+ *   that solid.fs never reads.  The depth-limit program (bricks.vs + bricks.gs + bricks.fs) uses the same vertex shader, and this project
+ *   treats it as working throughout.
+ * tsdf_set_draw_bricks: ReconIntegration::setDrawBricks, off by default (recon_integration.cpp:57).  While it is on, tsdf_draw_f -- and
+ *   through it tsdf_frame_dev / tsdf_frame_raw_dev -- ends with tsdf_draw_bricks under the draw's own matrices, after the hole filling and
+ *   before timer "3recon" ends (:160-173).  With it on and a stereo state set (colour-mask mode != 0, viewport origin / offset != 0)
+ *   tsdf_draw_f returns TSDF_ERR_STATE before it queues anything: the stereo form of this debug view is not provided.  The overlay
+ *   joins the hole-filling lane and the lane ahead, so with stage overlap the lanes run one after the other for that frame: accepted
+ *   for a debug view.  With the flag off every path is what it is without this entry.
  * tsdf_draw_textures: the texture view (g_draw_textures, key T :773, selector key Y :768; :704-707) = TextureBlitter::blit(15 + which,
  *   resolution_full / 2) (texture_blitter.cpp, glsl/texture_passthrough.{vs,fs} mode 0), drawn last.  which = 0: unit 15, the atlas the
  *   latest hole filling completed (the one fillColors() binds at recon_integration.cpp:315: the 1.5w x h RGBA32F ViewLod whose level 0 is
@@ -267,12 +293,16 @@ int32_t tsdf_download_mvt_vertices(tsdf_ctx* ctx, float* out);
  *   Depth test.  A fragment passes only if z < the framebuffer's depth before the overlay (strict); among passing fragments of one pixel the
  *     smallest (z bits, primitive index) wins -- GL_LESS with primitives drawn in order.  Primitive index: the grid's linear index
  *     (x + res.x * (y + res.y * z)) for the TSDF overlay, stream * 13 + k for the frustums (k < 12 the lines in the order above, 12 the point),
- *     4 * loop + k for the bounding box (loop in the order above, k the segment from its corner k to corner (k + 1) % 4). */
+ *     4 * loop + k for the bounding box (loop in the order above, k the segment from its corner k to corner (k + 1) % 4), 12 * brick id + k
+ *     for the occupied bricks (k the segment in the order above; GL draws instance after instance and the reference's list ascends in brick
+ *     id, so this is its draw order whatever the order of the device list). */
 int32_t tsdf_draw_calibvis(tsdf_ctx* ctx, const float modelview[16], const float projection[16]);
 int32_t tsdf_set_active_kinect(tsdf_ctx* ctx, uint32_t stream);
 int32_t tsdf_draw_frustums(tsdf_ctx* ctx, const float modelview[16], const float projection[16]);
 int32_t tsdf_calibvis_stats(tsdf_ctx* ctx, uint64_t out[2]);
 int32_t tsdf_draw_bbox(tsdf_ctx* ctx, const float modelview[16], const float projection[16]);
+int32_t tsdf_draw_bricks(tsdf_ctx* ctx, const float modelview[16], const float projection[16]);
+int32_t tsdf_set_draw_bricks(tsdf_ctx* ctx, int32_t active);
 int32_t tsdf_draw_textures(tsdf_ctx* ctx, uint32_t which);
 
 /* ---- draw() host matrices.  Host only, no context, no GPU: the matrix block ReconIntegration::draw()

@@ -414,6 +414,13 @@ class ReconIntegrationHip:
 
     def drawTextures(self, which): self._ck(self._L.tsdf_draw_textures(self._c, C.c_uint32(int(which))))
 
+    # "Draw occupied bricks" (ReconIntegration::drawOccupiedBricks): 12 red lines per brick of the latest updateOccupiedBricks(); the client
+    # calls it between the frustums and the bounding box while another back-end is showing.  setDrawBricks(True): drawF() ends with it.
+    def drawOccupiedBricks(self, mv, proj):
+        self._ck(self._L.tsdf_draw_bricks(self._c, _fp(_f32(mv)), _fp(_f32(proj))))
+
+    def setDrawBricks(self, a): self._ck(self._L.tsdf_set_draw_bricks(self._c, int(bool(a))))
+
     def calibvis_stats(self):
         """(grid points of the last drawCalibVis, of them removed by its empty-space test)"""
         out = (C.c_uint64 * 2)()

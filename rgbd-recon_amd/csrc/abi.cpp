@@ -1863,14 +1863,26 @@ int32_t tsdf_fill_colors(tsdf_ctx* c) {
   HIP_TRY(c, hipSetDevice(c->device));
   return fill_colors_impl(c, nullptr);
 }
-int32_t tsdf_draw_f(tsdf_ctx* c, const float* mv, const float* pr) {
-  CHECK_CTX(c);
-  int32_t rc = raymarch_impl(c, mv, pr, true);
-  if (rc) return rc;
+static int32_t brickwire_precheck(tsdf_ctx* c);
+static int32_t draw_bricks_impl(tsdf_ctx* c, const float* mv, const float* pr);
+// the tail of drawF() behind the raymarch (recon_integration.cpp:160-173): fillColors(), drawOccupiedBricks() when setDrawBricks is on, end of "3recon"
+static int32_t draw_f_tail(tsdf_ctx* c, const float* mv, const float* pr) {
+  int32_t rc;
   hipStream_t last = c->stream;
   if (c->fill_holes && (rc = fill_colors_impl(c, &last))) return rc;
+  if (c->draw_bricks) {
+    if ((rc = draw_bricks_impl(c, mv, pr))) return rc;
+    last = c->stream;                                                    // (the overlay joined the fill lane)
+  }
   timer_end_on(c, "3recon", last);
   return TSDF_OK;
+}
+int32_t tsdf_draw_f(tsdf_ctx* c, const float* mv, const float* pr) {
+  CHECK_CTX(c);
+  int32_t rc;
+  if (c->draw_bricks && (rc = brickwire_precheck(c))) return rc;         // (before anything is queued)
+  if ((rc = raymarch_impl(c, mv, pr, true))) return rc;
+  return draw_f_tail(c, mv, pr);
 }
 int32_t tsdf_frame_dev(tsdf_ctx* c, const float* depth_rg, const float* quality, const float* silhouette, const uint8_t* colour, uint32_t flags, const float* mv, const float* pr) {
   CHECK_CTX(c);
@@ -1890,11 +1902,10 @@ int32_t tsdf_frame_dev(tsdf_ctx* c, const float* depth_rg, const float* quality,
     lap(2);
     if ((rc = tsdf_integrate(c))) return rc;
     lap(3);
+    if (c->draw_bricks && (rc = brickwire_precheck(c))) return rc;
     if ((rc = raymarch_impl(c, mv, pr, true))) return rc;
     lap(4);
-    hipStream_t last = c->stream;
-    if (c->fill_holes && (rc = fill_colors_impl(c, &last))) return rc;
-    timer_end_on(c, "3recon", last);
+    if ((rc = draw_f_tail(c, mv, pr))) return rc;
     lap(5);
     if (++n % 1000 == 0) { fprintf(stderr, "host us per frame: upload %.1f clear+mark %.1f update %.1f integrate %.1f draw %.1f fill %.1f\n", acc[0] / 1000, acc[1] / 1000, acc[2] / 1000, acc[3] / 1000, acc[4] / 1000, acc[5] / 1000); for (double& a : acc) a = 0; }
     return TSDF_OK;
@@ -2026,6 +2037,44 @@ int32_t tsdf_draw_bbox(tsdf_ctx* c, const float* mv, const float* pr) {
   timer_end(c, "bbox");
   if (int32_t rc = overlay_rerecord_draw(c)) return rc;
   HIP_TRY(c, hipGetLastError());
+  return TSDF_OK;
+}
+// ---- "Draw occupied bricks" (ReconIntegration::drawOccupiedBricks, recon_integration.cpp:447-454)
+static int32_t brickwire_precheck(tsdf_ctx* c) {
+  if (int32_t rc = overlay_mono(c)) return rc;
+  if (12ull * (unsigned long long)c->br.n >= 0xffffffffull) FAIL(c, TSDF_ERR_STATE, "the brick grid is too large for the wireframe's primitive index (12 * bricks + segment in 32 bits)");
+  return TSDF_OK;
+}
+static int32_t draw_bricks_impl(tsdf_ctx* c, const float* mv, const float* pr) {
+  const bool plain = getenv("RR_BRICKWIRE_PLAIN") != nullptr;             // (measurement hook: the one-wave-per-segment form)
+  BrickWireParams Q{};
+  memcpy(Q.mv.m, mv, 64); memcpy(Q.proj.m, pr, 64);
+  Q.w = c->vw; Q.h = c->vh;
+  if (!c->d_comp_key) HIP_TRY(c, hipMalloc(&c->d_comp_key, (size_t)c->vw * c->vh * sizeof(unsigned long long)));
+  HIP_TRY(c, join_fill(c));                                              // the hole filling writes the framebuffer from its own lane
+  // the list of the latest update, from whatever lane ran it.  The join marks the occupancy set as in use by the context's stream, so the
+  // next update on the lane ahead takes the other set; the one after that returns to this set behind the lane's gate, which the
+  // context's stream records at the next frame's first lane call -- behind this draw, wherever in the frame it was queued.
+  HIP_TRY(c, join_pre(c));
+  timer_begin(c, "brickwire");
+  c->fb_consistent = false;
+  launch_draw_brickwire(c->stream, Q, c->br, c->d_comp_key, c->d_fb_c, c->d_fb_d, plain);
+  timer_end(c, "brickwire");
+  if (int32_t rc = overlay_rerecord_draw(c)) return rc;
+  HIP_TRY(c, hipGetLastError());
+  return TSDF_OK;
+}
+int32_t tsdf_draw_bricks(tsdf_ctx* c, const float* mv, const float* pr) {
+  CHECK_CTX(c);
+  ViewParams P;
+  if (int32_t rc = overlay_checks(c, mv, pr, &P)) return rc;
+  if (int32_t rc = brickwire_precheck(c)) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  return draw_bricks_impl(c, mv, pr);
+}
+int32_t tsdf_set_draw_bricks(tsdf_ctx* c, int32_t active) {
+  CHECK_CTX(c);
+  c->draw_bricks = active != 0;
   return TSDF_OK;
 }
 int32_t tsdf_draw_textures(tsdf_ctx* c, uint32_t which) {

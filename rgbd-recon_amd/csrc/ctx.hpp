@@ -135,6 +135,7 @@ struct tsdf_ctx {
   float* d_linear = nullptr;     // scratch for volume up/download
   // flags (recon_integration.cpp:54-57)
   bool fill_holes = true, use_bricks = true, skip_space = true;
+  bool draw_bricks = false;   // setDrawBricks (recon_integration.cpp:57,160-173): tsdf_draw_f ends with the occupied-brick wireframes
   int shade_mode = 0;
   // stereo modes of the client (source/kinect_client.cpp:616-669): viewport origin + viewport_offset uniform (side by side),
   // colour mask + "colour buffer not cleared before this draw" (anaglyph)

@@ -8,6 +8,8 @@
 // before the overlay; a resolve pass then writes the winners' colour and depth and leaves every other pixel as the previous draw left it.
 // The client then draws the bounding-box wireframe (gloost::BoundingBox::draw, width-2 lines, same scheme) and the texture view
 // (TextureBlitter::blit, a bilinear blit of texture unit 15 or 16 into the lower-left of the frame, no depth test).
+// Between the frustums and the bounding box (or inside drawF() itself, setDrawBricks) come the wireframes of the occupied bricks
+// (ReconIntegration::drawOccupiedBricks, recon_integration.cpp:447-454): width-1 lines, the same scheme, thousands of short segments.
 // The definitions GL leaves open (point size, line rasterisation, depth clamp) are listed in include/rgbd_recon_hip.h and restated in
 // tests/overlay_reference.py.
 #include "sampling.hpp"
@@ -141,15 +143,15 @@ __device__ __forceinline__ bool clip_plane(float4& a, float4& b, float da, float
   return true;
 }
 
-// One segment between the clip-space points a -> b, walked by the 64 lanes of a wave: near, then far clip, then the diamond exit for
-// width 1 -- an x-major line makes one fragment per pixel column whose centre c lies in [start, end) along the line's direction, in the row
-// floor(y(c)); y-major the same with rows.  Wider lines (GL 4.4 section 14.5.2.2, aliased): the segment moves by -(width - 1) / 2 in its
-// minor direction, is walked by the same rule, and each of its fragments becomes `width` fragments upwards in the minor direction at that
-// fragment's depth, each dropped on its own outside the view.
-__device__ __forceinline__ void overlay_line(float4 a, float4 b, int w, int h, int width, uint32_t id, int lane, const float* __restrict__ fb_d,
-                                             unsigned long long* __restrict__ key) {
-  if (!clip_plane(a, b, a.z + a.w, b.z + b.w) || !clip_plane(a, b, a.w - a.z, b.w - b.z)) return;   // near, then far
-  if (!(a.w > 0.0f) || !(b.w > 0.0f)) return;
+// The set-up of a clipped segment: window coordinates, major / minor axis, and the conservative range [lo, hi] of pixel columns (rows) whose
+// centres can lie on it.  false = nothing to walk.
+struct LineSetup {
+  float s0, s1, o0, o1, az, bz;                                          // major start / end, minor start / end, depth start / end
+  int lo, hi, xmajor;
+};
+__device__ __forceinline__ bool overlay_line_setup(float4 a, float4 b, int w, int h, int width, LineSetup& L) {
+  if (!clip_plane(a, b, a.z + a.w, b.z + b.w) || !clip_plane(a, b, a.w - a.z, b.w - b.z)) return false;   // near, then far
+  if (!(a.w > 0.0f) || !(b.w > 0.0f)) return false;
   const float W = (float)w, H = (float)h;
   const float ax = (a.x / a.w * 0.5f + 0.5f) * W, ay = (a.y / a.w * 0.5f + 0.5f) * H, az = a.z / a.w * 0.5f + 0.5f;
   const float bx = (b.x / b.w * 0.5f + 0.5f) * W, by = (b.y / b.w * 0.5f + 0.5f) * H, bz = b.z / b.w * 0.5f + 0.5f;
@@ -159,24 +161,41 @@ __device__ __forceinline__ void overlay_line(float4 a, float4 b, int w, int h, i
     const float shift = 0.5f * (float)(width - 1);
     o0 -= shift; o1 -= shift;
   }
-  const int n_major = xmajor ? w : h, n_minor = xmajor ? h : w;
+  const int n_major = xmajor ? w : h;
   const float lo = fmaxf(floorf(fminf(s0, s1)) - 1.0f, 0.0f), hi = fminf(ceilf(fmaxf(s0, s1)) + 1.0f, (float)(n_major - 1));
-  if (!(lo <= hi)) return;
-  for (int i = (int)lo + lane; i <= (int)hi; i += 64) {
-    const float c = (float)i + 0.5f;
-    if (!(s1 > s0 ? (c >= s0 && c < s1) : (c <= s0 && c > s1))) continue;
-    const float t = (c - s0) / (s1 - s0);
-    const float m = floorf(o0 + (o1 - o0) * t);
-    float z = az + (bz - az) * t;
-    if (z != z) continue;
-    z = z > 0.0f ? (z < 1.0f ? z : 1.0f) : 0.0f;                          // the depth range [0, 1]
-    for (int r = 0; r < width; ++r) {
-      const float mr = m + (float)r;
-      if (!(mr >= 0.0f && mr < (float)n_minor)) continue;
-      const int px = xmajor ? i : (int)mr, py = xmajor ? (int)mr : i;
-      overlay_fragment(fb_d, key, py * w + px, z, id);
-    }
+  if (!(lo <= hi)) return false;
+  L.s0 = s0; L.s1 = s1; L.o0 = o0; L.o1 = o1; L.az = az; L.bz = bz;
+  L.lo = (int)lo; L.hi = (int)hi; L.xmajor = xmajor ? 1 : 0;
+  return true;
+}
+// ... and the fragment(s) of pixel column (row) i of such a segment
+__device__ __forceinline__ void overlay_line_fragment(float s0, float s1, float o0, float o1, float az, float bz, bool xmajor, int i, int w, int h, int width,
+                                                      uint32_t id, const float* __restrict__ fb_d, unsigned long long* __restrict__ key) {
+  const float c = (float)i + 0.5f;
+  if (!(s1 > s0 ? (c >= s0 && c < s1) : (c <= s0 && c > s1))) return;
+  const float t = (c - s0) / (s1 - s0);
+  const float m = floorf(o0 + (o1 - o0) * t);
+  float z = az + (bz - az) * t;
+  if (z != z) return;
+  z = z > 0.0f ? (z < 1.0f ? z : 1.0f) : 0.0f;                            // the depth range [0, 1]
+  const int n_minor = xmajor ? h : w;
+  for (int r = 0; r < width; ++r) {
+    const float mr = m + (float)r;
+    if (!(mr >= 0.0f && mr < (float)n_minor)) continue;
+    const int px = xmajor ? i : (int)mr, py = xmajor ? (int)mr : i;
+    overlay_fragment(fb_d, key, py * w + px, z, id);
   }
+}
+// One segment between the clip-space points a -> b, walked by the 64 lanes of a wave: near, then far clip, then the diamond exit for
+// width 1 -- an x-major line makes one fragment per pixel column whose centre c lies in [start, end) along the line's direction, in the row
+// floor(y(c)); y-major the same with rows.  Wider lines (GL 4.4 section 14.5.2.2, aliased): the segment moves by -(width - 1) / 2 in its
+// minor direction, is walked by the same rule, and each of its fragments becomes `width` fragments upwards in the minor direction at that
+// fragment's depth, each dropped on its own outside the view.
+__device__ __forceinline__ void overlay_line(float4 a, float4 b, int w, int h, int width, uint32_t id, int lane, const float* __restrict__ fb_d,
+                                             unsigned long long* __restrict__ key) {
+  LineSetup L;
+  if (!overlay_line_setup(a, b, w, h, width, L)) return;
+  for (int i = L.lo + lane; i <= L.hi; i += 64) overlay_line_fragment(L.s0, L.s1, L.o0, L.o1, L.az, L.bz, L.xmajor != 0, i, w, h, width, id, fb_d, key);
 }
 
 __global__ __launch_bounds__(64) void k_frustum_lines(FrustumParams Q, const float* __restrict__ fb_d, unsigned long long* __restrict__ key) {
@@ -245,6 +264,113 @@ void launch_draw_bbox(hipStream_t st, const BBoxParams& Q, unsigned long long* k
   hipLaunchKernelGGL(k_overlay_clear, dim3((n + 255) / 256), dim3(256), 0, st, fb_d, key, n);
   hipLaunchKernelGGL(k_bbox_lines, dim3(24), dim3(64), 0, st, Q, fb_d, key);
   hipLaunchKernelGGL(k_bbox_resolve, dim3((n + 255) / 256), dim3(256), 0, st, n, key, fb_c, fb_d);
+}
+
+// ---- "Draw occupied bricks": ReconIntegration::drawOccupiedBricks() (recon_integration.cpp:447-454) = glsl/bricks.vs + glsl/solid.fs over
+// UnitCube::drawWireInstanced (unit_cube.cpp:20-29,74-83): 12 width-1 lines per brick of the latest updateOccupiedBricks(), colour (1, 0, 0, 1).
+// A cube corner is x | y << 1 | z << 2 (0 / 1 = the unit cube's coordinate); the cube's vertex v0..v7 and its 12 segments start -> end, in
+// draw order.  Primitive index 12 * brick id + segment: GL draws the instances in list order and the reference's list ascends in brick id,
+// so the key is independent of the order of the device list.
+__constant__ uint8_t c_cube_vertex[8] = {7, 6, 3, 2, 5, 4, 0, 1};
+__constant__ uint8_t c_cube_wire[12][2] = {{0, 1}, {0, 2}, {0, 4}, {5, 1}, {5, 4}, {5, 6}, {3, 1}, {3, 6}, {3, 2}, {7, 2}, {7, 4}, {7, 6}};
+
+// bricks.vs:16-20: P . (MV . to_world(position, index_3d(id))), to_world in the operand order of inc_bricks.glsl:22-24 (k_depth_limits)
+__device__ __forceinline__ float4 brick_corner_clip(const BrickWireParams& Q, const Bricks& B, uint32_t id, int corner) {
+  int idx[3];
+  idx[2] = (int)(id / (uint32_t)(B.res[0] * B.res[1]));                  // index_3d(), inc_bricks.glsl:30-38
+  const uint32_t rem = id % (uint32_t)(B.res[0] * B.res[1]);
+  idx[1] = (int)(rem / (uint32_t)B.res[0]);
+  idx[0] = (int)(rem % (uint32_t)B.res[0]);
+  float p[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) p[a] = (float)idx[a] * B.size[a] + B.bbox_min[a] + (((corner >> a) & 1) ? 1.0f : 0.0f) * B.size[a];
+  const float4 e = mat_mul(Q.mv, p[0], p[1], p[2], 1.0f);
+  return mat_mul(Q.proj, e.x, e.y, e.z, e.w);
+}
+
+// The plain form (kept for comparison, RR_BRICKWIRE_PLAIN=1): one wave per (brick, segment) pair, each projecting its two corners and
+// walking its segment with overlay_line -- for a brick of a few tens of pixels most of the 64 lanes have no pixel column.
+__global__ __launch_bounds__(64) void k_brickwire_plain(BrickWireParams Q, Bricks B, const float* __restrict__ fb_d, unsigned long long* __restrict__ key) {
+  const uint32_t n = *B.num_occupied * 12u;
+  for (uint32_t p = blockIdx.x; p < n; p += gridDim.x) {
+    const uint32_t id = B.occupied[p / 12u], s = p % 12u;
+    overlay_line(brick_corner_clip(Q, B, id, c_cube_vertex[c_cube_wire[s][0]]), brick_corner_clip(Q, B, id, c_cube_vertex[c_cube_wire[s][1]]), Q.w, Q.h, 1,
+                 id * 12u + s, threadIdx.x, fb_d, key);
+  }
+}
+
+// The balanced form: a persistent grid of single-wave workgroups, one brick at a time from the compacted list (k_depth_limits' shape).
+// Lanes 0..7 project the cube's eight vertices once; lanes 0..11 clip and set up one segment each (overlay_line_setup, the operations of
+// overlay_line); the candidate pixel columns / rows [lo, hi] of the 12 segments are concatenated and the 64 lanes walk that one list with
+// overlay_line_fragment, so that the lanes stay busy whatever the segments' lengths.  Vertices and set-ups go through LDS (one b128
+// write and two b128 reads per lane and phase; twelve ds_bpermute per phase would cost more LDS issue slots than that).
+__global__ __launch_bounds__(64) void k_brickwire_scatter(BrickWireParams Q, Bricks B, const float* __restrict__ fb_d, unsigned long long* __restrict__ key) {
+  __shared__ float4 s_clip[8];
+  __shared__ float4 s_seg[12][2];                                        // (s0, s1, o0, o1), (az, bz, bits of lo, bits of xmajor)
+  __shared__ int s_cnt[12];                                              // candidate pixel columns / rows per segment
+  const int lane = threadIdx.x;
+  const int n_occ = (int)*B.num_occupied;
+  for (int w = blockIdx.x; w < n_occ; w += gridDim.x) {
+    const uint32_t id = B.occupied[w];
+    float4 cl = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (lane < 8) { cl = brick_corner_clip(Q, B, id, c_cube_vertex[lane]); s_clip[lane] = cl; }
+    // Early out, exact: (a) every vertex fails the near test, or every vertex fails the far test -- clip_plane drops each of the 12
+    // segments; (b) no vertex fails either (no segment is clipped, so every end point is a vertex with w > 0: z + w >= 0 and w - z >= 0
+    // give w >= 0, and w = 0 would make z = 0 and the window depth NaN -- excluded with w > 0) and every vertex lies beyond the same side of
+    // the view: x > w > 0 makes x / w >= 1 and the window coordinate >= W, x < -w makes it <= 0 (y alike), and no pixel centre i + 0.5
+    // with 0 <= i < W lies in a half-open interval between two such coordinates.
+    const bool live = lane < 8;
+    const bool near_in = cl.z + cl.w >= 0.0f, far_in = cl.w - cl.z >= 0.0f;
+    const unsigned long long all8 = 0xffull;
+    const unsigned long long m_near = __ballot(live && near_in), m_far = __ballot(live && far_in);
+    if (m_near == 0 || m_far == 0) continue;
+    if (m_near == all8 && m_far == all8 && __ballot(live && cl.w > 0.0f) == all8) {
+      if (__ballot(live && cl.x > cl.w) == all8 || __ballot(live && cl.x < -cl.w) == all8 || __ballot(live && cl.y > cl.w) == all8 ||
+          __ballot(live && cl.y < -cl.w) == all8) continue;
+    }
+    __syncthreads();
+    int cnt = 0;
+    if (lane < 12) {
+      LineSetup L;
+      if (overlay_line_setup(s_clip[c_cube_wire[lane][0]], s_clip[c_cube_wire[lane][1]], Q.w, Q.h, 1, L)) {
+        cnt = L.hi - L.lo + 1;
+        s_seg[lane][0] = make_float4(L.s0, L.s1, L.o0, L.o1);
+        s_seg[lane][1] = make_float4(L.az, L.bz, __int_as_float(L.lo), __int_as_float(L.xmajor));
+      }
+    }
+    if (lane < 12) s_cnt[lane] = cnt;
+    __syncthreads();
+    int end[12];                                                          // inclusive prefix sum of the counts, in every lane (broadcast reads)
+    end[0] = s_cnt[0];
+#pragma unroll
+    for (int s = 1; s < 12; ++s) end[s] = end[s - 1] + s_cnt[s];
+    for (int k = lane; k < end[11]; k += 64) {
+      int s = 0, first = 0;
+#pragma unroll
+      for (int q = 0; q < 11; ++q) if (k >= end[q]) { s = q + 1; first = end[q]; }   // the segment whose range holds candidate k
+      const float4 g0 = s_seg[s][0], g1 = s_seg[s][1];
+      overlay_line_fragment(g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, __float_as_int(g1.w) != 0, __float_as_int(g1.z) + (k - first), Q.w, Q.h, 1,
+                            id * 12u + (uint32_t)s, fb_d, key);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_brickwire_resolve(int n, const unsigned long long* __restrict__ key, float4* __restrict__ fb_c, float* __restrict__ fb_d) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned long long k = key[i];
+  if ((uint32_t)k == kNoId) return;
+  fb_c[i] = make_float4(1.0f, 0.0f, 0.0f, 1.0f);                         // uniform Color (1, 0, 0), solid.fs: (Color, 1)
+  fb_d[i] = __uint_as_float((uint32_t)(k >> 32));
+}
+
+void launch_draw_brickwire(hipStream_t st, const BrickWireParams& Q, const Bricks& B, unsigned long long* key, float4* fb_c, float* fb_d, bool plain) {
+  const int n = Q.w * Q.h;
+  hipLaunchKernelGGL(k_overlay_clear, dim3((n + 255) / 256), dim3(256), 0, st, fb_d, key, n);
+  // the list's length is a device scalar: the grids are sized by the brick grid, never by a read-back
+  if (plain) hipLaunchKernelGGL(k_brickwire_plain, dim3(12ll * B.n < 65536 ? 12 * B.n : 65536), dim3(64), 0, st, Q, B, fb_d, key);
+  else hipLaunchKernelGGL(k_brickwire_scatter, dim3(B.n < 8192 ? B.n : 8192), dim3(64), 0, st, Q, B, fb_d, key);
+  hipLaunchKernelGGL(k_brickwire_resolve, dim3((n + 255) / 256), dim3(256), 0, st, n, key, fb_c, fb_d);
 }
 
 // ---- the texture view: TextureBlitter::blit(unit, res) (texture_blitter.cpp, glsl/texture_passthrough.{vs,fs} mode 0) of texture unit 15

@@ -222,6 +222,12 @@ struct BlitParams {
   int fw;                       // framebuffer row length
 };
 void launch_draw_bbox(hipStream_t st, const BBoxParams& Q, unsigned long long* key, float4* fb_c, float* fb_d);
+// the occupied-brick wireframes (ReconIntegration::drawOccupiedBricks): the list and count of B as the latest update left them
+struct BrickWireParams {
+  Mat4 mv, proj;
+  int w, h;
+};
+void launch_draw_brickwire(hipStream_t st, const BrickWireParams& Q, const Bricks& B, unsigned long long* key, float4* fb_c, float* fb_d, bool plain);
 void launch_blit_texture(hipStream_t st, const BlitParams& Q, float4* fb_c);
 // the 8 corner texels of a forward volume [rz][ry][rx][3] in getCornerPoints order (calib_inverter.cpp)
 void frustum_corners(const float* cv_xyz, const uint32_t res[3], float out[8][3]);

@@ -1,14 +1,18 @@
 // Headless harness: one frame in the reference's call order (source/kinect_client.cpp:569-599,614) through the C++
 // adapter, on a hand-made single-stream scene (constant inverse LUT, constant images).  Exit codes: 0 ok,
 // 3 no HIP device (the path has no CPU fallback), 1 any other failure.
+// Option --draw-bricks: setDrawBricks(true) before the draw, so that drawF() ends with the occupied-brick wireframes; the number of
+// pure red (1, 0, 0, 1) pixels is printed and must not be zero.
 //   g++ -std=c++17 frame_harness.cpp -o frame_harness -L.. -lrgbd_recon_hip -Wl,-rpath,'$ORIGIN/..'
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 #include "recon_integration_hip.hpp"
 
-int main() {
+int main(int argc, char** argv) {
+  const bool draw_bricks = argc > 1 && std::strcmp(argv[1], "--draw-bricks") == 0;
   kinect::ReconInputs in;
   in.num_kinects = 1;
   in.depth_width = in.color_width = 8;
@@ -40,6 +44,7 @@ int main() {
     const float f = 1.0f / std::tan(0.5f * 0.6f), n = 0.1f, fa = 50.0f;
     const float pr[16] = {f, 0, 0, 0, 0, f, 0, 0, 0, 0, (fa + n) / (n - fa), -1, 0, 0, 2 * fa * n / (n - fa), 0};
     recon.setMatrices(mv, pr);
+    recon.setDrawBricks(draw_bricks);
     recon.drawF();
     std::vector<float> tsdf, rgba, d;
     recon.downloadVolume(tsdf);
@@ -47,6 +52,12 @@ int main() {
     int band = 0;
     for (float v : tsdf) band += std::fabs(v - 0.02f) < 1e-6f;
     std::printf("occupied ratio %.4f, %u bricks, %d of %zu voxels at sdist 0.02\n", recon.occupiedRatio(), recon.numBricks(), band, tsdf.size());
+    if (draw_bricks) {
+      int wire = 0;
+      for (std::size_t i = 0; i < d.size(); ++i) wire += rgba[4 * i] == 1.0f && rgba[4 * i + 1] == 0.0f && rgba[4 * i + 2] == 0.0f && rgba[4 * i + 3] == 1.0f;
+      std::printf("%d wireframe pixels\n", wire);
+      if (wire == 0) return 1;
+    }
     return band > 0 ? 0 : 1;
   } catch (std::exception const& e) {
     std::fprintf(stderr, "%s\n", e.what());

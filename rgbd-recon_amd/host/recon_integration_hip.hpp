@@ -114,7 +114,7 @@ class ReconIntegrationHip {
   void setColorFilling(bool active) { check(tsdf_set_color_filling(m_ctx, active)); }
   void setUseBricks(bool active) { check(tsdf_set_use_bricks(m_ctx, active)); }
   void setSpaceSkip(bool active) { check(tsdf_set_space_skip(m_ctx, active)); }
-  void setDrawBricks(bool active) { m_draw_bricks = active; }    // wireframe debug overlay: not part of the HIP path
+  void setDrawBricks(bool active) { check(tsdf_set_draw_bricks(m_ctx, active)); }   // drawF() then ends with drawOccupiedBricks(), recon_integration.cpp:166-168
   void setVoxelSize(float size) { check(tsdf_set_voxel_size(m_ctx, size)); }      // recon_integration.cpp:340-353
   void setTsdfLimit(float limit) { check(tsdf_set_tsdf_limit(m_ctx, limit)); }
   void setBrickSize(float size) { const float s[3] = {size, size, size}; check(tsdf_set_brick_size(m_ctx, s)); m_brick_size = size; }
@@ -124,9 +124,9 @@ class ReconIntegrationHip {
   void clearOccupiedBricks() const { check(tsdf_clear_bricks(m_ctx)); }
   void updateOccupiedBricks() { check(tsdf_update_occupied(m_ctx, nullptr)); }
   void setMinVoxelsPerBrick(unsigned i) { check(tsdf_set_min_voxels_per_brick(m_ctx, i)); }
-  // drawOccupiedBricks() (recon_integration.cpp:447-454) draws with solid.vs, whose `transform` uniform is never set: GL's zero matrix puts every
-  // vertex at clip (0,0,0,0) and the reference draws nothing.  So does this.
-  void drawOccupiedBricks() const {}
+  // drawOccupiedBricks() (recon_integration.cpp:447-454; bricks.vs + solid.fs, :130-133): 12 red lines per brick of the latest
+  // updateOccupiedBricks(), under the matrices of setMatrices -- the client's call while another back-end is showing (kinect_client.cpp:681-683)
+  void drawOccupiedBricks() const { check(tsdf_draw_bricks(m_ctx, m_mv, m_proj)); }
   void setShadeMode(int mode) { check(tsdf_set_shade_mode(m_ctx, mode)); }
 
   // ---- results (the GL class leaves them in textures / the bound framebuffer)
@@ -159,7 +159,6 @@ class ReconIntegrationHip {
   tsdf_ctx* m_ctx = nullptr;
   float m_mv[16], m_proj[16];
   float m_brick_size;
-  bool m_draw_bricks = false;
 };
 
 // The client's overlays after drawF() in mono mode (source/kinect_client.cpp:672-683), over the SAME context and its matrices (setMatrices):

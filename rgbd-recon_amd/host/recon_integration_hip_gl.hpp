@@ -67,8 +67,9 @@ class ReconIntegrationHipGL : public Reconstruction {
   float getBrickSize() const { return m_impl.getBrickSize(); }
   void clearOccupiedBricks() const { m_impl.clearOccupiedBricks(); }
   void updateOccupiedBricks() { m_impl.updateOccupiedBricks(); }
-  // (solid.vs's `transform` uniform is never set, recon_integration.cpp:447-454: GL's zero matrix puts every vertex at clip (0,0,0,0), the reference draws nothing)
-  void drawOccupiedBricks() const {}
+  // the client's call while another back-end is showing (kinect_client.cpp:681-683): the wireframes over the framebuffer the library holds,
+  // under the matrices of the last draw() / drawF(); impl().downloadFramebuffer() reads the result
+  void drawOccupiedBricks() const { m_impl.drawOccupiedBricks(); }
   // the frame's explicit inputs and everything else of the C ABI
   ReconIntegrationHip& impl() { return m_impl; }
 
