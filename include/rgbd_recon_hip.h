@@ -305,6 +305,70 @@ int32_t tsdf_draw_bricks(tsdf_ctx* ctx, const float modelview[16], const float p
 int32_t tsdf_set_draw_bricks(tsdf_ctx* ctx, int32_t active);
 int32_t tsdf_draw_textures(tsdf_ctx* ctx, uint32_t which);
 
+/* ---- the GUI's "Show textures" windows (settings panel, source/kinect_client.cpp:336-338,483-515): each window is an ImGui::Image of ONE
+ * LAYER of one of NetKinectArray's seven texture arrays -- the view people open first when a reconstruction looks wrong.
+ * tsdf_draw_sensor_texture draws that image quad into the framebuffer as the previous draw left it (tsdf_upload_framebuffer puts a known one
+ * underneath, tsdf_download_framebuffer reads the result).  Out of scope, the host GUI's business: ImGui's window chrome, its list boxes and
+ * the one-pixel border rectangle around the image (imgui.cpp:5621-5625, anti-aliased through the font atlas).  `rect` is the image quad itself
+ * (bb.Min + 1 .. bb.Max - 1 when the border colour is set, as at kinect_client.cpp:509).
+ *   type   0 Color, 1 Depth, 2 Quality, 3 Normals, 4 Silhouette, 5 Orig Depth, 6 LAB colors (the list box of kinect_client.cpp:496)
+ *   stream the sensor = the array layer (TexInfo::layer = -stream - 1, :499; the back-end passes -(layer + 1), imgui_impl_glfw_glb.cpp:116)
+ *   rect   p_min.x, p_min.y, p_max.x, p_max.y in ImGui coordinates: origin at the top left of the w x h view, y down
+ *   clip   ImDrawCmd::ClipRect (x, y, z, w), or NULL = the whole view
+ * tsdf_sensor_view_size: the size the client gives the image, ImVec2(width, width / aspect) with aspect = float(res.y) / res.x of the DEPTH
+ *   resolution (:502-509: the image is shown turned by a quarter turn, so a 640 x 480 sensor makes a 480-wide image 640 high).  Host only.
+ *
+ * Sources.  The arrays are picked through texture units getStartTextureUnit() + type (NetKinectArray.cpp:428-462, bound at :451-462); every
+ * array is a globjects texture with its default LINEAR + CLAMP_TO_EDGE (TextureArray.cpp:27) unless NEAREST is set (NetKinectArray.cpp:
+ * 147-188).  A texel becomes the sample's vec4 as GL expands its format:
+ *   0  m_colorArray: RGB8 -> (rgb / 255, 1); the COMPRESSED_RGBA DXT1 / DXT5 formats -> rgba / 255 of the decoded RGBA8 this library holds
+ *      (tsdf_download_raw_frame's colour).  LINEAR, COLOUR resolution.  Bytes are converted (c / 255, an IEEE division) before the filter, and
+ *      all four channels are filtered, DXT alpha too.
+ *   1  the texture unit "depth" holds after processTextures(), m_textures_depth_b (:364,377): RG32F -> (r, g, 0, 1), NEAREST.
+ *   2  m_textures_quality: LUMINANCE32F -> (L, L, L, 1), LINEAR.
+ *   3  m_textures_normal: RGB32F -> (rgb, 1), LINEAR.
+ *   4  m_textures_silhouette: R32F -> (r, 0, 0, 1), LINEAR.
+ *   5  unit "morph_depth", m_textures_depth2.front (:283): the eroded-then-dilated raw depth, whatever useProcessedDepths says;
+ *      LUMINANCE32F -> (L, L, L, 1), NEAREST.
+ *   6  unit "color_lab", m_textures_color: the Lab image of pre_depth.fs, RGB32F -> (rgb, 1), LINEAR.
+ *   Types 1 - 6 have the depth resolution.  LINEAR is sampling.hpp's axis_linear on the source's own size (the "Texture view" paragraph
+ *   above: f = u * n - 0.5, taps clamp(floor(f)) and clamp(floor(f) + 1), weight f - floor(f)), lerp along x, then along y, per channel.
+ *   NEAREST is texel clamp(floor(u * n), 0, n - 1) per axis.
+ * Coverage and Frag_UV (GL leaves rasterisation and interpolation latitude; defined here).  Framebuffer pixel (i, j) is GL window row j, as
+ *   tsdf_download_framebuffer returns it; its centre in ImGui coordinates is cx = i + 0.5f, cy = float(h) - (j + 0.5f) -- the orthographic
+ *   projection of imgui_impl_glfw_glb.cpp:79-85 undone.  The pixel is covered iff p_min.x <= cx < p_max.x and p_min.y <= cy < p_max.y, and
+ *   it lies inside the view and inside the scissor box of :123: columns [sx, sx + sw), rows [sy, sy + sh) with sx = (int)clip.x,
+ *   sy = (int)(float(h) - clip.w), sw = (int)(clip.z - clip.x), sh = (int)(clip.w - clip.y) (fp32 differences; (int) truncates, values beyond
+ *   +-2^30 saturate there; a negative sw or sh -- which GL rejects -- covers nothing).  Frag_UV = ((cx - p_min.x) / (p_max.x - p_min.x),
+ *   (cy - p_min.y) / (p_max.y - p_min.y)), IEEE divisions: uv0 = (0, 0) and uv1 = (1, 1) as at kinect_client.cpp:509.
+ * The turn (fragment shader, imgui_impl_glfw_glb.cpp:275-281).  uv -= .5; uv = mat2(cos r, -sin r, sin r, cos r) * uv (column major), that is
+ *   (c * u + s * v, (-s) * u + c * v), products first, then the sum, no contraction; uv += .5; r = radians(90.0).  c and s are the fp32 values
+ *   cosf(1.5707964f) = -4.37113883e-08f (bits 0xb33bbd2e, NOT 0) and sinf(1.5707964f) = 1.  The sample is texture(array, (uv, stream)).
+ *   Assumed, not checkable without a GL implementation: a GLSL compiler may fold these constants at another precision (c = 0 exactly would
+ *   move uv by at most 2.2e-8, which can change a NEAREST pick or a LINEAR weight only at a texel border).
+ * Blend and writes (:68-74).  Depth test off, depth not written.  Frag_Color is white (ImColor(255,255,255,255), :509), so Out_Color is the
+ *   sample s.  GL_FUNC_ADD with (SRC_ALPHA, ONE_MINUS_SRC_ALPHA) on all four channels of the destination d, fp32: k = 1 - s.a, out =
+ *   (s * s.a) + (d * k) per channel, alpha included.  A sample with s.a == 1 REPLACES the pixel exactly (every type but DXT colour): a NaN or
+ *   inf a previous draw left underneath does not get through d * 0.  Values are not clamped: the client's RGBA8 window would clamp, this
+ *   project's float framebuffer does not (the convention of tsdf_draw_textures).  Pixels outside the quad, the scissor box or the view are
+ *   untouched.  Timer "sensortex".
+ * State.  The windows show NetKinectArray's arrays as of the latest tsdf_process_textures: all seven types after it, on every raw ingest path
+ *   (tsdf_upload_raw_frame, _dev, tsdf_upload_wire_frame with RGB8 / DXT1 / DXT5, tsdf_frame_raw_dev).  Type 6 produces the whole Lab image
+ *   on request exactly as tsdf_download_preprocessed does, and returns TSDF_ERR_STATE under the same condition.  A raw frame uploaded but not
+ *   yet processed: TSDF_ERR_STATE for every type, as before any frame.  For a frame handed over already processed (tsdf_upload_frame, _dev,
+ *   _async + tsdf_select_frame_slot, tsdf_frame_dev) types 0, 1, 2 and 4 read the current frame slot; type 1 then shows (r, 0, 0, 1), because
+ *   the slot keeps depth.r alone; type 3 shows the image of tsdf_upload_normals once that was called for this kind of frame, TSDF_ERR_STATE
+ *   before; types 5 and 6 return TSDF_ERR_STATE.
+ *   TSDF_ERR_INVALID_ARGUMENT: type > 6, stream >= num_streams, rect NULL, a non-finite rect or clip value, p_max <= p_min on either axis.
+ *   TSDF_ERR_STATE: a viewport origin / offset != 0 (side-by-side stereo renders no GUI, kinect_client.cpp:529-531).  A colour-mask mode != 0
+ *   is allowed and ignored: the reference restores the full mask at the end of every draw (recon_integration.cpp:235-236,332-333) and ImGui
+ *   renders over the anaglyph picture.  Needs no volume: sparse-pool and Z-slab contexts draw the same.
+ *   With stage overlap the draw joins the hole-filling lane and the lane ahead, and the next tsdf_process_textures waits for a window that read
+ *   a product it rewrites: the lanes run one after the other for that frame, accepted for a debug view.  Without a call to this entry every
+ *   path is what it is without it. */
+int32_t tsdf_draw_sensor_texture(tsdf_ctx* ctx, uint32_t type, uint32_t stream, const float rect[4], const float clip[4]);
+int32_t tsdf_sensor_view_size(const tsdf_ctx* ctx, float width, float size[2]);
+
 /* ---- draw() host matrices.  Host only, no context, no GPU: the matrix block ReconIntegration::draw()
  * builds before the raymarch -- vol_to_world = translate(bbox_min) * scale(bbox extent) (recon_integration.cpp:66-72),
  * image_to_eye = inverse(scale(w/2, h/2, 1/2) * translate(1,1,1) * projection) (:182-193), NormalMatrix =

@@ -414,6 +414,21 @@ class ReconIntegrationHip:
 
     def drawTextures(self, which): self._ck(self._L.tsdf_draw_textures(self._c, C.c_uint32(int(which))))
 
+    # the GUI's "Show textures" windows (kinect_client.cpp:483-515): layer `stream` of NetKinectArray's array `type` (0 Color, 1 Depth, 2 Quality,
+    # 3 Normals, 4 Silhouette, 5 Orig Depth, 6 LAB colors) as the ImGui image quad rect = (p_min.x, p_min.y, p_max.x, p_max.y), ImGui coordinates
+    # (origin top left, y down); clip = ImDrawCmd::ClipRect or None for the whole view
+    def drawSensorTexture(self, type, stream, rect, clip=None):
+        r = _f32(rect).reshape(-1)
+        cl = _f32(clip).reshape(-1) if clip is not None else None
+        assert r.size == 4 and (cl is None or cl.size == 4)
+        self._ck(self._L.tsdf_draw_sensor_texture(self._c, C.c_uint32(int(type)), C.c_uint32(int(stream)), _fp(r), _fp(cl)))
+
+    def sensorViewSize(self, width):
+        """ImVec2(width, width / aspect) of the client's image (kinect_client.cpp:502-509)"""
+        out = (C.c_float * 2)()
+        self._ck(self._L.tsdf_sensor_view_size(self._c, C.c_float(width), out))
+        return float(out[0]), float(out[1])
+
     # "Draw occupied bricks" (ReconIntegration::drawOccupiedBricks): 12 red lines per brick of the latest updateOccupiedBricks(); the client
     # calls it between the frustums and the bounding box while another back-end is showing.  setDrawBricks(True): drawF() ends with it.
     def drawOccupiedBricks(self, mv, proj):

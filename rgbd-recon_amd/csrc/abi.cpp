@@ -818,6 +818,7 @@ int32_t tsdf_destroy(tsdf_ctx* c) {
   if (c->src_ready) hipEventDestroy(c->src_ready);
   if (c->normals_read) hipEventDestroy(c->normals_read);
   if (c->raw_read) hipEventDestroy(c->raw_read);
+  if (c->products_read) hipEventDestroy(c->products_read);
   hipFree(c->d_mvt_vtx); hipFree(c->d_calibvis_skipped);
   if (c->fill_worker) {
     c->fill_worker->stop.store(true);
@@ -995,7 +996,7 @@ int32_t tsdf_upload_frame(tsdf_ctx* c, const float* depth_rg, const float* quali
   launch_pack_frame_fused(lane, c->d_stage_depth, c->d_stage_q, c->d_stage_s, (float4*)F.dqs, (float*)c->frame.depth, c->slots[c->cur_slot].ranges,
                           (int)c->cfg.num_streams, F.w, F.h, colour ? c->d_stage_col : nullptr, (uchar4*)F.color, nc, counters_for_upload(c, lane), (uint32_t)c->counter_words);
   HIP_TRY(c, hipGetLastError());
-  c->slots[c->cur_slot].have = true;
+  c->slots[c->cur_slot].have = true; c->slots[c->cur_slot].origin = tsdf_ctx::kFramePre;
   HIP_TRY(c, pre_leave(c, lane));
   return TSDF_OK;
 }
@@ -1025,7 +1026,7 @@ int32_t tsdf_upload_frame_dev(tsdf_ctx* c, const float* depth_rg, const float* q
                           (int)c->cfg.num_streams, F.w, F.h, colour, (uchar4*)F.color, nc, counters_for_upload(c, lane), (uint32_t)c->counter_words);
   timer_end_on(c, "0repack", lane);
   HIP_TRY(c, hipGetLastError());
-  c->slots[c->cur_slot].have = true;
+  c->slots[c->cur_slot].have = true; c->slots[c->cur_slot].origin = tsdf_ctx::kFramePre;
   HIP_TRY(c, pre_leave(c, lane));
   return TSDF_OK;
 }
@@ -1084,7 +1085,7 @@ int32_t tsdf_upload_frame_async(tsdf_ctx* c, const float* depth_rg, const float*
   launch_pack_frame_fused(c->copy_stream, (const float*)c->d_astage, (const float*)(c->d_astage + np * 8), (const float*)(c->d_astage + np * 12), S.dqs, S.depth, S.ranges,
                           (int)c->cfg.num_streams, c->frame.w, c->frame.h, with_colour ? c->d_astage + np * 16 : nullptr, S.color, nc);
   HIP_TRY(c, hipEventRecord(S.ready, c->copy_stream));
-  S.pending = true; S.have = true;
+  S.pending = true; S.have = true; S.origin = tsdf_ctx::kFramePre;
   HIP_TRY(c, hipGetLastError());
   return TSDF_OK;
 }
@@ -1146,7 +1147,7 @@ int32_t tsdf_upload_raw_frame(tsdf_ctx* c, const float* depth_raw, const uint8_t
   HIP_TRY(c, hipMemcpyAsync(c->d_raw, depth_raw, np * sizeof(float), hipMemcpyHostToDevice, lane));
   HIP_TRY(c, hipMemcpyAsync(c->d_stage_col, colour, nc * 3, hipMemcpyHostToDevice, lane));
   c->pending_rgb = c->d_stage_col;                                       // its RGBA8 re-layout rides along in tsdf_process_textures' first launch
-  c->raw_src = c->d_raw; c->have_raw = true; ++c->raw_generation;
+  c->raw_src = c->d_raw; c->have_raw = true; ++c->raw_generation; c->slots[c->cur_slot].origin = tsdf_ctx::kFrameRawPending;
   HIP_TRY(c, pre_leave(c, lane));
   return TSDF_OK;
 }
@@ -1166,7 +1167,7 @@ static int32_t upload_raw_frame_dev_impl(tsdf_ctx* c, const float* depth_raw, co
   }
   if (int32_t rc = begin_slot_write(c, lane, false)) return rc;
   c->pending_rgb = colour;                                               // its RGBA8 re-layout rides along in tsdf_process_textures' first launch
-  c->raw_src = depth_raw; c->have_raw = true; ++c->raw_generation;
+  c->raw_src = depth_raw; c->have_raw = true; ++c->raw_generation; c->slots[c->cur_slot].origin = tsdf_ctx::kFrameRawPending;
   HIP_TRY(c, pre_leave(c, lane));
   return TSDF_OK;
 }
@@ -1257,7 +1258,7 @@ int32_t tsdf_upload_wire_frame(tsdf_ctx* c, const void* message, uint64_t bytes,
   launch_wire_unpack(lane, L, (uchar4*)c->frame.color, c->d_raw);
   timer_end_on(c, "0ingest", lane);
   HIP_TRY(c, hipGetLastError());
-  c->raw_src = c->d_raw; c->have_raw = true; ++c->raw_generation;
+  c->raw_src = c->d_raw; c->have_raw = true; ++c->raw_generation; c->slots[c->cur_slot].origin = tsdf_ctx::kFrameRawPending;
   HIP_TRY(c, pre_leave(c, lane));
   return TSDF_OK;
 }
@@ -1315,6 +1316,10 @@ static int32_t process_textures_impl(tsdf_ctx* c, int phase) {
     if (lane != c->stream) HIP_TRY(c, hipStreamWaitEvent(lane, c->normals_read, 0));
     c->normals_read_pending = false;
   }
+  if (c->products_read_pending) {                                        // a sensor texture window read the products this call rewrites (phase 1: d_depth2 and the filter pass's images)
+    if (lane != c->stream) HIP_TRY(c, hipStreamWaitEvent(lane, c->products_read, 0));
+    c->products_read_pending = false;
+  }
   PreParams& P = c->pre;
   P.W = c->frame.w; P.H = c->frame.h; P.N = (int)c->cfg.num_streams;
   for (int a = 0; a < 3; ++a) { P.bbox_min[a] = c->cfg.bbox_min[a]; P.bbox_max[a] = c->cfg.bbox_max[a]; }
@@ -1341,12 +1346,21 @@ static int32_t process_textures_impl(tsdf_ctx* c, int phase) {
   if (phase != 1) {
     c->pending_rgb = nullptr;
     timer_end_on(c, "1preprocess", lane);
-    c->slots[c->cur_slot].have = true;
+    c->slots[c->cur_slot].have = true; c->slots[c->cur_slot].origin = tsdf_ctx::kFrameRawDone; c->normals_uploaded = false;
   }
   HIP_TRY(c, pre_leave(c, lane));
   return TSDF_OK;
 }
 int32_t tsdf_process_textures(tsdf_ctx* c) { return process_textures_impl(c, 0); }
+// the Lab image of the filter pass: the passes evaluate it only where the boundary pass reads it (k_pre_boundary); the whole image is produced on request, on the
+// context's stream, from the inputs of the frame that was processed -- which must still be the resident ones
+static int32_t produce_lab(tsdf_ctx* c) {
+  if (c->pre_generation != c->raw_generation || c->pre_processed_depth != c->use_processed_depth)
+    FAIL(c, TSDF_ERR_STATE, "the Lab image is produced on request from the processed frame's inputs, and a newer raw frame has replaced them (download before the next upload)");
+  launch_pre_lab(c->stream, c->pre, pre_buffers(c), c->luts, c->frame);
+  HIP_TRY(c, hipGetLastError());
+  return TSDF_OK;
+}
 int32_t tsdf_download_preprocessed(tsdf_ctx* c, float* depth2, float* depth_rg, float* lab, float* depth_b, float* sil, float* normals, float* quality) {
   CHECK_CTX(c);
   if (!c->have_raw) FAIL(c, TSDF_ERR_STATE, "nothing was pre-processed yet");
@@ -1360,12 +1374,7 @@ int32_t tsdf_download_preprocessed(tsdf_ctx* c, float* depth2, float* depth_rg, 
   auto fetch4 = [&](const void* src) -> int32_t { tmp.resize(np); HIP_TRY(c, hipMemcpy(tmp.data(), src, np * 16, hipMemcpyDeviceToHost)); return TSDF_OK; };
   int32_t rc;
   if (lab) {
-    // the Lab image of the filter pass: the passes evaluate it only where the boundary pass reads it (k_pre_boundary); the whole image is produced here, from the
-    // inputs of the frame that was processed -- which must still be the resident ones
-    if (c->pre_generation != c->raw_generation || c->pre_processed_depth != c->use_processed_depth)
-      FAIL(c, TSDF_ERR_STATE, "the Lab image is produced on request from the processed frame's inputs, and a newer raw frame has replaced them (download before the next upload)");
-    launch_pre_lab(c->stream, c->pre, pre_buffers(c), c->luts, c->frame);
-    HIP_TRY(c, hipGetLastError());
+    if ((rc = produce_lab(c))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   if (lab) { if ((rc = fetch4(c->d_lab))) return rc; for (size_t i = 0; i < np; ++i) { lab[3 * i] = tmp[i].x; lab[3 * i + 1] = tmp[i].y; lab[3 * i + 2] = tmp[i].z; } }
@@ -1691,6 +1700,7 @@ int32_t tsdf_upload_normals(tsdf_ctx* c, const float* normals_rgb) {
   for (size_t i = 0; i < np; ++i) padded[i] = make_float4(normals_rgb[3 * i], normals_rgb[3 * i + 1], normals_rgb[3 * i + 2], 0.0f);
   HIP_TRY(c, sync_ctx(c));
   HIP_TRY(c, hipMemcpy(c->d_normal, padded.data(), np * sizeof(float4), hipMemcpyHostToDevice));
+  c->normals_uploaded = true;
   return TSDF_OK;
 }
 int32_t tsdf_view_matrices(const float* mv, const float* pr, uint32_t vw, uint32_t vh, const float* bbox_min, const float* bbox_max, float* out) {
@@ -2096,6 +2106,90 @@ int32_t tsdf_draw_textures(tsdf_ctx* c, uint32_t which) {
   c->fb_consistent = false;
   launch_blit_texture(c->stream, Q, c->d_fb_c);
   timer_end(c, "textures");
+  HIP_TRY(c, hipGetLastError());
+  return TSDF_OK;
+}
+// ---- the GUI's "Show textures" windows (kinect_client.cpp:483-515): one layer of one of NetKinectArray's seven texture arrays as an ImGui::Image
+int32_t tsdf_sensor_view_size(const tsdf_ctx* c, float width, float size[2]) {
+  CHECK_CTX(c);
+  if (!size) return TSDF_ERR_INVALID_ARGUMENT;
+  const float aspect = float(c->frame.h) / (float)c->frame.w;             // float(res.y) / res.x of the depth resolution, :506
+  size[0] = width; size[1] = width / aspect;                              // ImVec2(width, width / aspect), :509
+  return TSDF_OK;
+}
+int32_t tsdf_draw_sensor_texture(tsdf_ctx* c, uint32_t type, uint32_t stream, const float rect[4], const float clip[4]) {
+  CHECK_CTX(c);
+  if (type > 6) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "texture type %u: 0 Color, 1 Depth, 2 Quality, 3 Normals, 4 Silhouette, 5 Orig Depth, 6 LAB colors", type);
+  if (stream >= c->cfg.num_streams) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "stream %u out of range", stream);
+  if (!rect) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "null rect");
+  for (int k = 0; k < 4; ++k)
+    if (!std::isfinite(rect[k]) || (clip && !std::isfinite(clip[k]))) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "rect and clip must be finite");
+  if (!(rect[2] > rect[0]) || !(rect[3] > rect[1])) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "empty quad: p_max must be greater than p_min on both axes");
+  if (c->vp_org[0] != 0 || c->vp_org[1] != 0 || c->vp_off[0] != 0.0f || c->vp_off[1] != 0.0f)
+    FAIL(c, TSDF_ERR_STATE, "the GUI is not rendered side by side (viewport origin / offset must be 0)");
+  const tsdf_ctx::FrameSlot& S = c->slots[c->cur_slot];
+  const int origin = S.have ? S.origin : tsdf_ctx::kFrameNone;
+  if (origin == tsdf_ctx::kFrameNone) FAIL(c, TSDF_ERR_STATE, "no frame uploaded");
+  if (origin == tsdf_ctx::kFrameRawPending) FAIL(c, TSDF_ERR_STATE, "the raw frame uploaded last has not been processed yet (tsdf_process_textures)");
+  const bool raw = origin == tsdf_ctx::kFrameRawDone;
+  if (!raw && type >= 5) FAIL(c, TSDF_ERR_STATE, "a frame handed over already processed has no %s image", type == 5 ? "morphed raw depth" : "Lab");
+  if (!raw && type == 3 && !c->normals_uploaded) FAIL(c, TSDF_ERR_STATE, "a frame handed over already processed has normals only after tsdf_upload_normals");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const FrameImages& F = c->frame;
+  const size_t np = (size_t)F.w * F.h, layer = stream;
+  SensorTexParams Q{};
+  Q.layer = (int)stream; Q.sw = F.w; Q.sh = F.h;
+  switch (type) {
+    case 0: Q.mode = kSensorRgba8; Q.src = F.color + layer * (size_t)F.cw * F.ch; Q.sw = F.cw; Q.sh = F.ch; break;
+    case 1: if (raw) { Q.mode = kSensorRgNearest; Q.src = c->d_depth_b + layer * np; } else Q.mode = kSensorSlotDepth; break;   // (the slot keeps depth.r alone)
+    case 2: Q.mode = kSensorSlotQuality; break;
+    case 3: Q.mode = kSensorRgb32f; Q.src = c->d_normal + layer * np; break;
+    case 4: Q.mode = kSensorSlotSilhouette; break;
+    case 5: Q.mode = kSensorLumNearest; Q.src = c->d_depth2 + layer * np; break;
+    default: Q.mode = kSensorRgb32f; Q.src = c->d_lab + layer * np; break;
+  }
+  // the scissor box of imgui_impl_glfw_glb.cpp:123 cut to the view; NULL: the whole view.  (int) truncates; +-2^30 bounds what a float can ask for
+  const int w = c->vw, h = c->vh;
+  auto trunc = [](float v) { return (int)std::min(std::max(v, -1073741824.0f), 1073741824.0f); };
+  long long bx = 0, by = 0, bw = w, bh = h;
+  if (clip) { bx = trunc(clip[0]); by = trunc((float)h - clip[3]); bw = trunc(clip[2] - clip[0]); bh = trunc(clip[3] - clip[1]); }
+  if (bw < 0) bw = 0;
+  if (bh < 0) bh = 0;
+  Q.sx0 = (int)std::max<long long>(bx, 0); Q.sx1 = (int)std::min<long long>(bx + bw, w);
+  Q.sy0 = (int)std::max<long long>(by, 0); Q.sy1 = (int)std::min<long long>(by + bh, h);
+  for (int a = 0; a < 2; ++a) { Q.pmin[a] = rect[a]; Q.pmax[a] = rect[2 + a]; }
+  Q.fw = w; Q.fh = h;
+  // the launch rectangle: the quad's pixels, one to spare on every side (the kernel decides each pixel with the definition's own fp32 tests), cut to the box
+  const double ylo = (double)h - (double)rect[3], yhi = (double)h - (double)rect[1];
+  auto within = [](double v, int n) { return (int)std::min(std::max(v, -1.0), (double)n); };   // (a finite float can be far outside an int)
+  const int qx0 = within(std::floor((double)rect[0]) - 1.0, w), qx1 = within(std::ceil((double)rect[2]) + 1.0, w);
+  const int qy0 = within(std::floor(ylo) - 1.0, h), qy1 = within(std::ceil(yhi) + 1.0, h);
+  Q.x0 = std::max(qx0, Q.sx0); Q.y0 = std::max(qy0, Q.sy0);
+  Q.nx = std::min(qx1, Q.sx1) - Q.x0; Q.ny = std::min(qy1, Q.sy1) - Q.y0;
+  if (raw && type == 6) {                                                // (before anything is queued: the Lab image's own state rule)
+    if (c->pre_generation != c->raw_generation || c->pre_processed_depth != c->use_processed_depth)
+      FAIL(c, TSDF_ERR_STATE, "the Lab image is produced on request from the processed frame's inputs, and a newer raw frame has replaced them");
+  }
+  if (type == 0) { if (int32_t rc = flush_pending_colour(c)) return rc; }
+  HIP_TRY(c, join_fill(c));                                              // the hole filling writes the framebuffer from its own lane
+  HIP_TRY(c, join_pre(c));                                               // the lane ahead wrote the products and the frame slot
+  if (raw && type == 6) { if (int32_t rc = produce_lab(c)) return rc; }
+  timer_begin(c, "sensortex");
+  c->fb_consistent = false;
+  launch_sensor_texture(c->stream, Q, F, c->d_fb_c);
+  timer_end(c, "sensortex");
+  // d_depth_b, d_normal, d_depth2, d_lab exist once: the next tsdf_process_textures on the lane ahead waits for this draw (the frame slots alternate behind
+  // the lane's gate, which the context's stream records after this call).  The Lab pass also read the raw depth: a raw upload that rewrites d_raw waits too
+  if ((type == 3 || (raw && (type == 1 || type >= 5))) && pipelined(c)) {
+    if (!c->products_read) HIP_TRY(c, hipEventCreateWithFlags(&c->products_read, hipEventDisableTiming));
+    HIP_TRY(c, hipEventRecord(c->products_read, c->stream));
+    c->products_read_pending = true;
+    if (type == 6) {
+      if (!c->raw_read) HIP_TRY(c, hipEventCreateWithFlags(&c->raw_read, hipEventDisableTiming));
+      HIP_TRY(c, hipEventRecord(c->raw_read, c->stream));
+      c->raw_read_pending = true;
+    }
+  }
   HIP_TRY(c, hipGetLastError());
   return TSDF_OK;
 }

@@ -69,7 +69,8 @@ struct tsdf_ctx {
   // `cur_slot`, tsdf_upload_frame_async fills the other one on a copy stream; tsdf_select_frame_slot makes it current.
   struct FrameSlot { float4* dqs = nullptr; float* depth = nullptr; uchar4* color = nullptr; float4* ranges = nullptr; bool have = false;
                      hipEvent_t ready = nullptr; bool pending = false;      // recorded on the copy stream after the slot's upload + pack
-                     hipEvent_t released = nullptr; bool in_use = false; }; // recorded on the compute stream when the slot stopped being current
+                     hipEvent_t released = nullptr; bool in_use = false;    // recorded on the compute stream when the slot stopped being current
+                     int origin = 0; };                                     // where its frame came from (kFrame*, below): what the sensor texture windows may show
   FrameSlot slots[2];
   int cur_slot = 0;
   hipStream_t copy_stream = nullptr;
@@ -92,6 +93,13 @@ struct tsdf_ctx {
   // the texture view (tsdf_draw_textures): c->atlas is the one the latest hole filling completed (GL's unit 15), d_peels the depth-limit image
   // of the latest draw with space skipping (unit 16) -- each until something rewrites it
   bool tex_atlas_ok = false, tex_limits_ok = false;
+  // the sensor texture windows (tsdf_draw_sensor_texture) show NetKinectArray's arrays: FrameSlot::origin says whether the current slot's frame was handed
+  // over processed, is a raw frame still to be processed, or one tsdf_process_textures has gone through; normals_uploaded: d_normal is tsdf_upload_normals'.
+  // products_read is recorded behind a window that read one of the single-buffered products (d_depth2, d_depth_b, d_normal, d_lab): the next
+  // tsdf_process_textures on the lane ahead rewrites them, its first two passes in front of the lane's gate
+  static constexpr int kFrameNone = 0, kFramePre = 1, kFrameRawPending = 2, kFrameRawDone = 3;
+  bool normals_uploaded = false;
+  hipEvent_t products_read = nullptr; bool products_read_pending = false;
   // frame ingest (readLoop / update): wire formats, pinned double buffer (the reference's double_pbo), device copy of the message
   uint32_t color_format = TSDF_COLOR_RGB8, depth_format = TSDF_DEPTH_F32;
   uint8_t* h_wire[2]{}; hipEvent_t wire_done[2]{}; bool wire_pending[2]{}; int wire_slot = 0;

@@ -10,6 +10,7 @@
 // (TextureBlitter::blit, a bilinear blit of texture unit 15 or 16 into the lower-left of the frame, no depth test).
 // Between the frustums and the bounding box (or inside drawF() itself, setDrawBricks) come the wireframes of the occupied bricks
 // (ReconIntegration::drawOccupiedBricks, recon_integration.cpp:447-454): width-1 lines, the same scheme, thousands of short segments.
+// Last in this file: the GUI's per-sensor "Show textures" windows (tsdf_draw_sensor_texture), one lane per pixel, blended, no depth.
 // The definitions GL leaves open (point size, line rasterisation, depth clamp) are listed in include/rgbd_recon_hip.h and restated in
 // tests/overlay_reference.py.
 #include "sampling.hpp"
@@ -400,6 +401,76 @@ __global__ __launch_bounds__(256) void k_blit_texture(BlitParams Q, float4* __re
 void launch_blit_texture(hipStream_t st, const BlitParams& Q, float4* fb_c) {
   const int n = Q.vw * Q.vh;
   hipLaunchKernelGGL(k_blit_texture, dim3((n + 255) / 256), dim3(256), 0, st, Q, fb_c);
+}
+
+// ---- the GUI's "Show textures" windows (kinect_client.cpp:483-515): ImGui::Image of one layer of one of NetKinectArray's texture arrays,
+// drawn by the ImGui back-end's array mode (imgui_impl_glfw_glb.cpp:68-74,111-124,260-285): an alpha-blended quad whose fragment shader turns
+// the texture coordinate by radians(90.0) about (.5, .5).  One lane per destination pixel; no depth test, no depth write.  The definition
+// (coverage, Frag_UV, the turn, the blend) is in include/rgbd_recon_hip.h and restated by tests/sensor_view_reference.py.
+// cosf / sinf of the fp32 value of radians(90.0) = 1.5707964f
+constexpr float kSensorRotC = -4.37113883e-08f, kSensorRotS = 1.0f;
+
+template <int kMode>
+__device__ __forceinline__ float4 sensor_sample(const SensorTexParams& Q, const FrameImages& F, float u, float v) {
+  if (kMode == kSensorSlotDepth || kMode == kSensorSlotQuality || kMode == kSensorSlotSilhouette) {
+    const Dqs d = dqs_fetch(F, Q.layer, u, v);
+    if (kMode == kSensorSlotDepth) return make_float4(dqs_depth(d), 0.0f, 0.0f, 1.0f);
+    if (kMode == kSensorSlotSilhouette) return make_float4(dqs_silhouette(d), 0.0f, 0.0f, 1.0f);
+    const float q = dqs_quality(d);
+    return make_float4(q, q, q, 1.0f);
+  }
+  if (kMode == kSensorRgNearest || kMode == kSensorLumNearest) {
+    const uint32_t o = (uint32_t)__mul24(axis_nearest(v, Q.sh), Q.sw) + (uint32_t)axis_nearest(u, Q.sw);
+    if (kMode == kSensorRgNearest) { const float2 t = ((const float2*)Q.src)[o]; return make_float4(t.x, t.y, 0.0f, 1.0f); }
+    const float t = ((const float*)Q.src)[o];
+    return make_float4(t, t, t, 1.0f);
+  }
+  const Axis X = axis_linear(u, Q.sw), Y = axis_linear(v, Q.sh);
+  const uint32_t r0 = (uint32_t)__mul24(Y.i0, Q.sw), r1 = (uint32_t)__mul24(Y.i1, Q.sw);
+  if (kMode == kSensorRgb32f) {
+    const float4* __restrict__ t = (const float4*)Q.src;
+    const float3 c = lerp3(lerp3(t[r0 + X.i0], t[r0 + X.i1], X.a), lerp3(t[r1 + X.i0], t[r1 + X.i1], X.a), Y.a);
+    return make_float4(c.x, c.y, c.z, 1.0f);
+  }
+  // RGBA8, unsigned normalised: c / 255 (an IEEE division) before the filter, all four channels
+  const uchar4* __restrict__ t = (const uchar4*)Q.src;
+  const uchar4 t00 = t[r0 + X.i0], t10 = t[r0 + X.i1], t01 = t[r1 + X.i0], t11 = t[r1 + X.i1];
+  return make_float4(lerpf(lerpf(t00.x / 255.0f, t10.x / 255.0f, X.a), lerpf(t01.x / 255.0f, t11.x / 255.0f, X.a), Y.a),
+                     lerpf(lerpf(t00.y / 255.0f, t10.y / 255.0f, X.a), lerpf(t01.y / 255.0f, t11.y / 255.0f, X.a), Y.a),
+                     lerpf(lerpf(t00.z / 255.0f, t10.z / 255.0f, X.a), lerpf(t01.z / 255.0f, t11.z / 255.0f, X.a), Y.a),
+                     lerpf(lerpf(t00.w / 255.0f, t10.w / 255.0f, X.a), lerpf(t01.w / 255.0f, t11.w / 255.0f, X.a), Y.a));
+}
+
+// A workgroup is four waves, a wave an 8 x 8 tile of destination pixels: the quarter turn makes destination rows walk source columns, so a
+// wave laid out as a 64-pixel row would read 64 texels a full source row apart.  As a square its loads and its stores fall into 8 runs each.
+template <int kMode>
+__global__ __launch_bounds__(256) void k_sensor_texture(SensorTexParams Q, FrameImages F, float4* __restrict__ fb_c) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int i = Q.x0 + (int)blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
+  const int j = Q.y0 + (int)blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+  if (i < Q.sx0 || i >= Q.sx1 || j < Q.sy0 || j >= Q.sy1) return;         // scissor box and view (and with them the launch rectangle's overhang)
+  const float cx = (float)i + 0.5f, cy = (float)Q.fh - ((float)j + 0.5f); // the pixel centre in ImGui coordinates
+  if (!(Q.pmin[0] <= cx && cx < Q.pmax[0] && Q.pmin[1] <= cy && cy < Q.pmax[1])) return;
+  float u = (cx - Q.pmin[0]) / (Q.pmax[0] - Q.pmin[0]), v = (cy - Q.pmin[1]) / (Q.pmax[1] - Q.pmin[1]);   // Frag_UV
+  u -= 0.5f; v -= 0.5f;
+  const float ru = kSensorRotC * u + kSensorRotS * v, rv = (-kSensorRotS) * u + kSensorRotC * v;   // mat2(c, -s, s, c) * uv, column major
+  const float4 s = sensor_sample<kMode>(Q, F, ru + 0.5f, rv + 0.5f);
+  float4* const px = fb_c + (size_t)j * Q.fw + i;
+  if (s.w == 1.0f) { *px = s; return; }                                   // (every source but DXT colour; nothing from underneath gets through d * 0)
+  const float4 d = *px;
+  const float k = 1.0f - s.w;                                             // SRC_ALPHA, ONE_MINUS_SRC_ALPHA on all four channels
+  *px = make_float4(s.x * s.w + d.x * k, s.y * s.w + d.y * k, s.z * s.w + d.z * k, s.w * s.w + d.w * k);
+}
+
+void launch_sensor_texture(hipStream_t st, const SensorTexParams& Q, const FrameImages& F, float4* fb_c) {
+  if (Q.nx <= 0 || Q.ny <= 0) return;
+  const dim3 grid((Q.nx + 15) / 16, (Q.ny + 15) / 16), block(256);
+  switch (Q.mode) {
+#define RR_SENSOR_CASE(m) case m: hipLaunchKernelGGL(k_sensor_texture<m>, grid, block, 0, st, Q, F, fb_c); break
+    RR_SENSOR_CASE(kSensorRgba8); RR_SENSOR_CASE(kSensorRgNearest); RR_SENSOR_CASE(kSensorSlotDepth); RR_SENSOR_CASE(kSensorSlotQuality);
+    RR_SENSOR_CASE(kSensorSlotSilhouette); RR_SENSOR_CASE(kSensorRgb32f); RR_SENSOR_CASE(kSensorLumNearest);
+#undef RR_SENSOR_CASE
+  }
 }
 
 }  // namespace rr

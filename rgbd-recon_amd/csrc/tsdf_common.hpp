@@ -229,6 +229,26 @@ struct BrickWireParams {
 };
 void launch_draw_brickwire(hipStream_t st, const BrickWireParams& Q, const Bricks& B, unsigned long long* key, float4* fb_c, float* fb_d, bool plain);
 void launch_blit_texture(hipStream_t st, const BlitParams& Q, float4* fb_c);
+// the GUI's "Show textures" windows (tsdf_draw_sensor_texture): what the layer's texel is and how it becomes the sample's vec4
+enum SensorTexMode {
+  kSensorRgba8 = 0,       // uchar4, LINEAR, rgba / 255
+  kSensorRgNearest,       // float2, NEAREST, (r, g, 0, 1)
+  kSensorSlotDepth,       // the frame slot's packed texel, NEAREST, (depth.r, 0, 0, 1)
+  kSensorSlotQuality,     // the frame slot's packed texel, LINEAR, (q, q, q, 1)
+  kSensorSlotSilhouette,  // the frame slot's packed texel, LINEAR, (s, 0, 0, 1)
+  kSensorRgb32f,          // float4 (rgb padded to 16 B), LINEAR, (rgb, 1)
+  kSensorLumNearest       // float, NEAREST, (L, L, L, 1)
+};
+struct SensorTexParams {
+  const void* src;              // first texel of the LAYER (the plain arrays); the packed-texel modes read F / layer instead
+  int mode, layer;
+  int sw, sh;                   // the source's size
+  int x0, y0, nx, ny;           // the launch's pixel rectangle: a superset of quad, scissor box and view (every lane tests its own pixel)
+  int sx0, sy0, sx1, sy1;       // scissor box cut to the view: columns [sx0, sx1), GL window rows [sy0, sy1)
+  float pmin[2], pmax[2];       // the image quad in ImGui coordinates
+  int fw, fh;                   // the framebuffer
+};
+void launch_sensor_texture(hipStream_t st, const SensorTexParams& Q, const FrameImages& F, float4* fb_c);
 // the 8 corner texels of a forward volume [rz][ry][rx][3] in getCornerPoints order (calib_inverter.cpp)
 void frustum_corners(const float* cv_xyz, const uint32_t res[3], float out[8][3]);
 

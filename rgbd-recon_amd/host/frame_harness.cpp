@@ -3,16 +3,27 @@
 // 3 no HIP device (the path has no CPU fallback), 1 any other failure.
 // Option --draw-bricks: setDrawBricks(true) before the draw, so that drawF() ends with the occupied-brick wireframes; the number of
 // pure red (1, 0, 0, 1) pixels is printed and must not be zero.
+// Option --sensor-view TYPE WIDTH: after the frame, one "Show textures" window per sensor (SensorTextureViewHip; TYPE 0 Color, 1 Depth,
+// 2 Quality, 4 Silhouette for this pre-processed frame), WIDTH wide, side by side from the top left; the number of pixels it changed is
+// printed and must not be zero.
 //   g++ -std=c++17 frame_harness.cpp -o frame_harness -L.. -lrgbd_recon_hip -Wl,-rpath,'$ORIGIN/..'
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "recon_integration_hip.hpp"
 
 int main(int argc, char** argv) {
-  const bool draw_bricks = argc > 1 && std::strcmp(argv[1], "--draw-bricks") == 0;
+  bool draw_bricks = false;
+  int view_type = -1;
+  float view_width = 0.0f;
+  for (int a = 1; a < argc; ++a) {
+    if (std::strcmp(argv[a], "--draw-bricks") == 0) draw_bricks = true;
+    else if (std::strcmp(argv[a], "--sensor-view") == 0 && a + 2 < argc) { view_type = std::atoi(argv[a + 1]); view_width = (float)std::atof(argv[a + 2]); a += 2; }
+    else { std::fprintf(stderr, "usage: frame_harness [--draw-bricks] [--sensor-view TYPE WIDTH]\n"); return 1; }
+  }
   kinect::ReconInputs in;
   in.num_kinects = 1;
   in.depth_width = in.color_width = 8;
@@ -57,6 +68,24 @@ int main(int argc, char** argv) {
       for (std::size_t i = 0; i < d.size(); ++i) wire += rgba[4 * i] == 1.0f && rgba[4 * i + 1] == 0.0f && rgba[4 * i + 2] == 0.0f && rgba[4 * i + 3] == 1.0f;
       std::printf("%d wireframe pixels\n", wire);
       if (wire == 0) return 1;
+    }
+    if (view_type >= 0) {
+      kinect::NetKinectArrayHip nka(recon, TSDF_COLOR_RGB8, false);
+      nka.setStartTextureUnit(1);                                         // (any: the view subtracts it again)
+      kinect::SensorTextureViewHip view(nka);
+      struct { std::uint16_t unit; std::int16_t layer; } info;            // the reference's TexInfo
+      const std::array<float, 2> size = view.imageSize(view_width);
+      for (unsigned i = 0; i < in.num_kinects; ++i) {
+        info.unit = (std::uint16_t)(nka.getStartTextureUnit() + (unsigned)view_type); info.layer = (std::int16_t)(-(int)i - 1);
+        const float p_min[2] = {1.0f + (float)i * (size[0] + 2.0f), 1.0f}, p_max[2] = {p_min[0] + size[0], p_min[1] + size[1]};
+        view.draw(info, p_min, p_max);
+      }
+      std::vector<float> rgba2, d2;
+      recon.downloadFramebuffer(rgba2, d2, 32, 32);
+      int changed = 0;
+      for (std::size_t i = 0; i < d.size(); ++i) changed += std::memcmp(&rgba[4 * i], &rgba2[4 * i], 16) != 0;
+      std::printf("%d pixels changed by the sensor windows (%g x %g)\n", changed, size[0], size[1]);
+      if (changed == 0 || d2 != d) return 1;
     }
     return band > 0 ? 0 : 1;
   } catch (std::exception const& e) {

@@ -232,6 +232,11 @@ class NetKinectArrayHip {
   void useProcessedDepths(bool f) { m_processed = f; apply(); }
   void refineBoundary(bool f) { m_refine = f; apply(); }
   double frameTime() const { return m_frametime; }
+  // NetKinectArray.cpp:428-437,464-466: the first of the seven texture units (color, depth, quality, normal, silhouette, morph_depth, color_lab).
+  // Nothing is bound here; the GUI encodes the array it wants to see as unit = start + type (SensorTextureViewHip)
+  void setStartTextureUnit(unsigned start_texture_unit) { m_start_texture_unit = start_texture_unit; }
+  unsigned getStartTextureUnit() const { return m_start_texture_unit; }
+  tsdf_ctx* handle() const { return m_ctx; }
 
  private:
   void apply() { check(tsdf_set_preprocess(m_ctx, m_filter, m_processed, m_refine)); }
@@ -239,6 +244,34 @@ class NetKinectArrayHip {
   tsdf_ctx* m_ctx;
   bool m_dirty = false, m_filter = true, m_processed = true, m_refine = true;
   double m_frametime = 0.0;
+  unsigned m_start_texture_unit = 0;                                                 // NetKinectArray.cpp:69
+};
+
+// The GUI's "Show textures" windows (kinect_client.cpp:483-515): ImGui::Image of one layer of one of NetKinectArray's texture arrays, drawn by
+// the ImGui back-end's array mode (imgui_impl_glfw_glb.cpp:111-124).  `info` is the reference's TexInfo (imgui_impl_glfw_glb.h:28-40) -- any
+// struct with its two members: unit = getStartTextureUnit() + type, layer = -stream - 1 -- so a caller that holds an ImDrawCmd forwards
+// what it memcpy's out of TextureId, the image quad of the command's vertices and its ClipRect unchanged.
+class SensorTextureViewHip {
+ public:
+  explicit SensorTextureViewHip(NetKinectArrayHip const& nka) : m_nka(nka) {}
+  // ImVec2(width, width / aspect) of kinect_client.cpp:502-509
+  std::array<float, 2> imageSize(float width) const {
+    std::array<float, 2> s{{0.0f, 0.0f}};
+    check(tsdf_sensor_view_size(m_nka.handle(), width, s.data()));
+    return s;
+  }
+  template <class TexInfoT>
+  void draw(TexInfoT const& info, const float p_min[2], const float p_max[2], const float clip_rect[4] = nullptr) const {
+    const long unit = (long)info.unit, start = (long)m_nka.getStartTextureUnit(), layer = (long)info.layer;
+    if (unit < start || unit > start + 6) throw std::invalid_argument("SensorTextureViewHip: texture unit outside NetKinectArray's start .. start + 6");
+    if (layer >= 0) throw std::invalid_argument("SensorTextureViewHip: layer >= 0 is a plain 2-D texture id, not a texture array layer");
+    const float rect[4] = {p_min[0], p_min[1], p_max[0], p_max[1]};
+    check(tsdf_draw_sensor_texture(m_nka.handle(), (uint32_t)(unit - start), (uint32_t)(-(layer + 1)), rect, clip_rect));
+  }
+
+ private:
+  void check(int32_t rc) const { if (rc != TSDF_OK) throw std::runtime_error(std::string("SensorTextureViewHip: ") + tsdf_last_error(m_nka.handle())); }
+  NetKinectArrayHip const& m_nka;
 };
 
 }  // namespace kinect
