@@ -529,6 +529,54 @@ int32_t tsdf_download_framebuffer(tsdf_ctx* ctx, float* rgba, float* depth);    
 int32_t tsdf_upload_framebuffer(tsdf_ctx* ctx, const float* rgba, const float* depth);    /* its twin: a known framebuffer under an overlay (tests) */
 int32_t tsdf_download_atlas(tsdf_ctx* ctx, float* rgba, float* depth);          /* [h][1.5w] pyramid atlas */
 
+/* ---- frame read-out: the swap ------------------------------------------------------------------------
+ * The client ends a frame with glfwSwapBuffers (source/kinect_client.cpp:533): an RGBA8 window goes to a display (GLFW's default framebuffer has 8
+ * bits per channel and the client sets no window hint that changes it, :942-951).  This device has no display; tsdf_present is the swap for a host
+ * that wants to SEE the frame: it converts the finished framebuffer to what the window would hold -- or to the DXT1 blocks of the system's wire format
+ * (TSDF_COLOR_DXT1), 1/8 of that --, copies it into a ring of pinned host buffers on the context's copy stream, and hands finished frames out in
+ * order while the lanes work on the next ones.  (tsdf_download_framebuffer stays what it was: synchronous, fp32, 20 bytes per pixel, for tests.)
+ * tests/present_reference.py restates the definition in numpy; device and numpy agree byte for byte.
+ *
+ * RGBA8.  Per channel u = (uint8) rint(min(max(v, 0), 1) * 255.0f): the product in fp32, rint = round to nearest, half-way cases to even; NaN maps to
+ *   0, -inf to 0, +inf to 255.  This is the float -> unsigned-normalised conversion of GL 4.4 section 2.3.5.2; GL only RECOMMENDS round-to-nearest
+ *   there, an implementation may do otherwise, this library always rounds so.  Alpha is converted like the colour channels: the framebuffer's
+ *   alpha = -1 "fallback" pixels become 0.  Four bytes r, g, b, a per pixel, w * h * 4 bytes.
+ * Row order.  Bottom row first (row j = GL window row j, the library's convention); with TSDF_PRESENT_TOP_DOWN output row j is window row h - 1 - j.
+ *   DXT1 blocks are cut from the image in its OUTPUT orientation.
+ * DXT1.  Opaque four-colour mode only.  ceil(w / 4) x ceil(h / 4) blocks, row-major over blocks, 8 bytes each: c0 (u16, little endian), c1 (u16 LE),
+ *   index word (u32 LE) with texel i = 4 y + x at bits 2i .. 2i + 1.  Texels outside the image replicate the last column / row (clamped coordinates).
+ * DXT1 encoder.  On the converted 8-bit r, g, b (alpha is dropped), in integer arithmetic only:
+ *   1. lo[c], hi[c] = per-channel min / max over the block's 16 texels;
+ *   2. inset[c] = (hi[c] - lo[c]) >> 4, lo' = lo + inset, hi' = hi - inset;
+ *   3. endpoint A = hi', endpoint B = lo' -- except that for c in {r, b} with cov = 16 * sum(c * g) - sum(c) * sum(g) < 0 (sums over the 16
+ *      texels; fits 32 bits) A takes lo'[c] and B takes hi'[c]: the block's diagonal (a channel that falls where green rises);
+ *   4. each endpoint is quantised r >> 3, g >> 2, b >> 3 and packed 565 (r in the high bits);
+ *   5. c0 = the larger of A565 and B565, c1 = the smaller;
+ *   6. c0 == c1: the index word is 0;
+ *   7. otherwise both are expanded by bit replication ((r5 << 3) | (r5 >> 2), (g6 << 2) | (g6 >> 4)), p2 = (2 p0 + p1) / 3 and p3 = (p0 + 2 p1) / 3 in
+ *      integer division -- the palette this library's own DXT1 decoder (tsdf_upload_wire_frame) produces --, and a texel's index is the k = 0..3 with
+ *      the smallest summed squared r, g, b difference, the lowest k among equals.
+ *
+ * The ring.  tsdf_present_config sets format, flags and the number of slots (2..8; a context starts with RGBA8, no flags, 3 slots); each slot is a
+ *   device buffer, a pinned host buffer and a ready event, allocated by the first tsdf_present.  tsdf_present(tag) takes the next free slot --
+ *   TSDF_ERR_STATE and nothing queued when every slot is queued or held --, queues the conversion on the context's stream behind everything queued so
+ *   far (the hole filling and any overlay since: the finished frame) and the copy on the copy stream behind it.  It never blocks the host, and the
+ *   framebuffer is free for the next frame as soon as the conversion has run (the copy reads the slot's device buffer).
+ *   tsdf_present_acquire hands out the oldest presented frame not yet released, in the order of the tsdf_present calls: *data points at the slot's
+ *   pinned buffer (valid until tsdf_present_release), *bytes its size, *tag the tag, size = {w, h}; bytes, tag and size may be NULL.  wait != 0: the call
+ *   waits for that frame's copy.  wait == 0: while the copy has not finished the call returns TSDF_OK with *data = NULL (never a partial frame).
+ *   TSDF_ERR_STATE with nothing queued, or with a frame already held.  tsdf_present_release frees the held slot (TSDF_ERR_STATE when none is held).
+ *   While frames are queued or held, tsdf_present_config and tsdf_resize return TSDF_ERR_STATE.  tsdf_destroy drains the ring.
+ *   Timer "present" brackets the conversion kernel.  A context that never calls these runs exactly what it ran before they existed. */
+#define TSDF_PRESENT_RGBA8 0u
+#define TSDF_PRESENT_DXT1  1u
+#define TSDF_PRESENT_TOP_DOWN 1u
+int32_t tsdf_present_config(tsdf_ctx* ctx, uint32_t format, uint32_t flags, uint32_t slots);
+int32_t tsdf_present_size(tsdf_ctx* ctx, uint64_t* bytes);     /* of one frame at the current view size and format */
+int32_t tsdf_present(tsdf_ctx* ctx, uint64_t tag);
+int32_t tsdf_present_acquire(tsdf_ctx* ctx, int32_t wait, const void** data, uint64_t* bytes, uint64_t* tag, uint32_t size[2]);
+int32_t tsdf_present_release(tsdf_ctx* ctx);
+
 /* ---- multi-GPU hooks (one context per rank; the collective itself is the caller's: RCCL) ---------- */
 /* Halo = whole storage tile layers (8 voxel planes) next to the slab faces; sizes in bytes per face. */
 int32_t tsdf_halo_info(const tsdf_ctx* ctx, uint32_t* layers, uint64_t* bytes_per_face);

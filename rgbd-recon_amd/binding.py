@@ -175,6 +175,8 @@ def read_stream_record(path, record_bytes, frame):
 
 COLOR_RGB8, COLOR_DXT1, COLOR_DXT5 = 0, 1, 5
 DEPTH_F32, DEPTH_U8 = 0, 1
+PRESENT_RGBA8, PRESENT_DXT1 = 0, 1    # tsdf_present_config: format
+PRESENT_TOP_DOWN = 1                  # ... flags
 K1_FORMS = ("generic", "lds_direct", "lds_separable", "record", "cached")   # TSDF_K1_* of rgbd_recon_hip.h
 
 
@@ -565,6 +567,36 @@ class ReconIntegrationHip:
         rgba, depth = _f32(rgba), _f32(depth)
         assert rgba.shape == (h, w, 4) and depth.shape == (h, w)
         self._ck(self._L.tsdf_upload_framebuffer(self._c, _fp(rgba), _fp(depth)))
+
+    # ------------------------------------------------------------------ frame read-out: the swap (glfwSwapBuffers, source/kinect_client.cpp:533)
+    def present_config(self, format=PRESENT_RGBA8, flags=0, slots=3):
+        self._ck(self._L.tsdf_present_config(self._c, C.c_uint32(int(format)), C.c_uint32(int(flags)), C.c_uint32(int(slots))))
+        self._present_format = int(format)
+
+    def present_size(self):
+        n = C.c_uint64()
+        self._ck(self._L.tsdf_present_size(self._c, C.byref(n)))
+        return n.value
+
+    def present(self, tag=0):
+        """queue conversion + copy of the finished framebuffer into the next ring slot; never blocks (TsdfError, code -4, when every slot is taken)"""
+        self._ck(self._L.tsdf_present(self._c, C.c_uint64(int(tag))))
+
+    def present_acquire(self, wait=True):
+        """the oldest presented frame not yet released as (a numpy COPY of its bytes, tag, (w, h)) -- uint8 [h][w][4] for RGBA8, the flat block
+        bytes for DXT1 -- and still held until present_release(); None while its copy is still under way (wait=False)"""
+        data, n, tag, size = C.c_void_p(), C.c_uint64(), C.c_uint64(), (C.c_uint32 * 2)()
+        self._ck(self._L.tsdf_present_acquire(self._c, C.c_int32(1 if wait else 0), C.byref(data), C.byref(n), C.byref(tag), size))
+        if not data.value:
+            return None
+        a = np.ctypeslib.as_array(C.cast(data, C.POINTER(C.c_uint8)), shape=(n.value,)).copy()
+        w, h = int(size[0]), int(size[1])
+        if getattr(self, "_present_format", PRESENT_RGBA8) == PRESENT_RGBA8:
+            a = a.reshape(h, w, 4)
+        return a, tag.value, (w, h)
+
+    def present_release(self):
+        self._ck(self._L.tsdf_present_release(self._c))
 
     def atlas(self):
         w, h = self.view

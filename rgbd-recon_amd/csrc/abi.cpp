@@ -85,6 +85,16 @@ void release_view(tsdf_ctx* c) {
   hipFree(c->d_hits); hipFree(c->d_hit_counters); hipFree(c->d_comp_key); c->d_hits = nullptr; c->d_hit_counters = nullptr; c->d_comp_key = nullptr;
   c->atlas.color = nullptr; c->atlas.depth = nullptr; c->d_peels = nullptr; c->d_nsamples = nullptr; c->d_fb_c = nullptr; c->d_fb_d = nullptr;
 }
+// the read-out ring's buffers and events (nothing may be in flight: an idle ring, or behind a synchronisation of both streams)
+void release_present(tsdf_ctx* c) {
+  for (auto& S : c->present_ring) {
+    hipFree(S.dev); if (S.host) hipHostFree(S.host);
+    if (S.converted) hipEventDestroy(S.converted);
+    if (S.ready) hipEventDestroy(S.ready);
+    S = tsdf_ctx::PresentSlot{};
+  }
+  c->present_bytes = 0; c->present_head = 0; c->present_count = 0; c->present_held = false;
+}
 void release_bricks(tsdf_ctx* c) {
   for (int k = 0; k < 2; ++k) { hipFree(c->d_counters[k]); hipFree(c->d_flags[k]); hipFree(c->d_occupied[k]); c->d_counters[k] = nullptr; c->d_flags[k] = nullptr; c->d_occupied[k] = nullptr; }
   c->br.counters = nullptr; c->br.flags = nullptr; c->br.num_occupied = nullptr; c->br.occupied = nullptr;
@@ -795,7 +805,8 @@ int32_t tsdf_destroy(tsdf_ctx* c) {
   CHECK_CTX(c);
   hipSetDevice(c->device);
   sync_ctx(c);          // (a null handle is the NULL stream: tsdf_adopt_null_stream)
-  if (c->copy_stream) hipStreamSynchronize(c->copy_stream);   // an asynchronous upload may still be writing a frame slot
+  if (c->copy_stream) hipStreamSynchronize(c->copy_stream);   // an asynchronous upload may still be writing a frame slot, a presented frame still travelling to its host buffer
+  release_present(c);
   tsdf_comm_destroy(c);
   release_view(c); release_bricks(c);
   release_volume(c);
@@ -1035,7 +1046,7 @@ int32_t tsdf_upload_frame_dev(tsdf_ctx* c, const float* depth_rg, const float* q
 // mapped back buffer NetKinectArray.cpp:516-520; update() = swap + PBO -> texture DMA, :225-236) as two device frame slots, a pinned
 // host staging ring and a copy stream.  While the path computes on the current slot the next frame travels into the other one.
 static int32_t ensure_async_upload(tsdf_ctx* c) {
-  if (c->copy_stream) return TSDF_OK;
+  if (c->async_upload_ready) return TSDF_OK;
   const size_t np = (size_t)c->cfg.num_streams * c->frame.w * c->frame.h, nc = (size_t)c->cfg.num_streams * c->frame.cw * c->frame.ch;
   const size_t bytes = np * 16 + nc * 3;
   for (int k = 0; k < 2; ++k) {                                            // (re-entered after a failed first attempt: keep what exists)
@@ -1046,7 +1057,8 @@ static int32_t ensure_async_upload(tsdf_ctx* c) {
   if (int32_t rc = alloc_frame_slot(c, 0)) return rc;
   if (int32_t rc = alloc_frame_slot(c, 1)) return rc;
   HIP_TRY(c, sync_ctx(c));                             // the new slot's colour memset
-  HIP_TRY(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+  if (!c->copy_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));   // (the frame read-out may have made it already)
+  c->async_upload_ready = true;
   return TSDF_OK;
 }
 int32_t tsdf_frame_staging(tsdf_ctx* c, float** depth_rg, float** quality, float** silhouette, uint8_t** colour) {
@@ -2294,6 +2306,7 @@ int32_t tsdf_set_brick_size(tsdf_ctx* c, const float size[3]) {
 }
 int32_t tsdf_resize(tsdf_ctx* c, uint32_t w, uint32_t h) {
   CHECK_CTX(c);
+  if (c->present_count) FAIL(c, TSDF_ERR_STATE, "%u presented frame(s) are queued or held: acquire and release them before the view changes size", c->present_count);
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, sync_ctx(c));
   int32_t rc = setup_view(c, w, h);
@@ -2444,6 +2457,92 @@ int32_t tsdf_download_atlas(tsdf_ctx* c, float* rgba, float* depth) {
   const size_t n = (size_t)c->atlas.aw * c->atlas.h;
   if (rgba) HIP_TRY(c, hipMemcpy(rgba, c->atlas.color, n * 16, hipMemcpyDeviceToHost));
   if (depth) HIP_TRY(c, hipMemcpy(depth, c->atlas.depth, n * 4, hipMemcpyDeviceToHost));
+  return TSDF_OK;
+}
+
+// ---- frame read-out: what the client's window holds after glfwSwapBuffers (source/kinect_client.cpp:533), converted on the device and copied to a pinned
+// host ring (include/rgbd_recon_hip.h, "frame read-out").  The mirror image of the asynchronous upload: a ring, the copy stream, the wire's DXT1.
+static size_t present_frame_bytes(const tsdf_ctx* c) {
+  return c->present_format == TSDF_PRESENT_DXT1 ? (size_t)((c->vw + 3) / 4) * ((c->vh + 3) / 4) * 8 : (size_t)c->vw * c->vh * 4;
+}
+int32_t tsdf_present_config(tsdf_ctx* c, uint32_t format, uint32_t flags, uint32_t slots) {
+  CHECK_CTX(c);
+  if (format > TSDF_PRESENT_DXT1 || (flags & ~TSDF_PRESENT_TOP_DOWN) || slots < 2 || slots > tsdf_ctx::kMaxPresentSlots)
+    FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "present format %u / flags %u / slots %u (formats 0 RGBA8, 1 DXT1; flag 1 top-down; 2..%u slots)", format, flags, slots, tsdf_ctx::kMaxPresentSlots);
+  if (c->present_count) FAIL(c, TSDF_ERR_STATE, "%u presented frame(s) are queued or held: acquire and release them first", c->present_count);
+  HIP_TRY(c, hipSetDevice(c->device));
+  release_present(c);                                                    // (the ring is idle: every copy was waited for before its frame was released)
+  c->present_format = format; c->present_flags = flags; c->present_slots = slots;
+  return TSDF_OK;
+}
+int32_t tsdf_present_size(tsdf_ctx* c, uint64_t* bytes) {
+  CHECK_CTX(c);
+  if (!bytes) return TSDF_ERR_INVALID_ARGUMENT;
+  *bytes = (uint64_t)present_frame_bytes(c);
+  return TSDF_OK;
+}
+int32_t tsdf_present(tsdf_ctx* c, uint64_t tag) {
+  CHECK_CTX(c);
+  if (c->present_count >= c->present_slots) FAIL(c, TSDF_ERR_STATE, "all %u present slots are queued or held (tsdf_present_acquire / tsdf_present_release)", c->present_slots);
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t bytes = present_frame_bytes(c);
+  if (c->present_bytes != bytes) {                                       // first use at this view size and format (tsdf_resize and tsdf_present_config drop the ring)
+    release_present(c);
+    for (uint32_t k = 0; k < c->present_slots; ++k) {
+      tsdf_ctx::PresentSlot& S = c->present_ring[k];
+      HIP_TRY(c, hipMalloc(&S.dev, bytes));
+      HIP_TRY(c, hipHostMalloc(&S.host, bytes, hipHostMallocDefault));
+      HIP_TRY(c, hipEventCreateWithFlags(&S.converted, hipEventDisableTiming));
+      HIP_TRY(c, hipEventCreateWithFlags(&S.ready, hipEventDisableTiming));
+    }
+    c->present_bytes = bytes;
+  }
+  if (!c->copy_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));   // (as ensure_async_upload makes it)
+  tsdf_ctx::PresentSlot& S = c->present_ring[(c->present_head + c->present_count) % c->present_slots];
+  // The finished frame: the hole filling writes the framebuffer from its own lane, overlays from the context's stream.  The kernel's output is the slot's
+  // device buffer, so the framebuffer is free again when the KERNEL has run, and nobody has to wait for the copy: every later writer of the framebuffer
+  // is ordered behind the context's stream already -- the next hole filling waits for draw_done, which fill_colors_impl records on this stream behind the
+  // next march (and so behind this kernel); a direct march (colour filling off) and the overlays run on this stream themselves.
+  HIP_TRY(c, join_fill(c));
+  timer_begin(c, "present");
+  launch_present(c->stream, c->d_fb_c, S.dev, c->vw, c->vh, c->present_format, (c->present_flags & TSDF_PRESENT_TOP_DOWN) ? 1 : 0);
+  timer_end(c, "present");
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipEventRecord(S.converted, c->stream));
+  HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, S.converted, 0));
+  HIP_TRY(c, hipMemcpyAsync(S.host, S.dev, bytes, hipMemcpyDeviceToHost, c->copy_stream));
+  HIP_TRY(c, hipEventRecord(S.ready, c->copy_stream));
+  S.tag = tag;
+  ++c->present_count;
+  return TSDF_OK;
+}
+int32_t tsdf_present_acquire(tsdf_ctx* c, int32_t wait, const void** data, uint64_t* bytes, uint64_t* tag, uint32_t size[2]) {
+  CHECK_CTX(c);
+  if (!data) return TSDF_ERR_INVALID_ARGUMENT;
+  *data = nullptr;
+  if (!c->present_count) FAIL(c, TSDF_ERR_STATE, "no presented frame is queued");
+  if (c->present_held) FAIL(c, TSDF_ERR_STATE, "a presented frame is held already: tsdf_present_release first");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const tsdf_ctx::PresentSlot& S = c->present_ring[c->present_head];
+  if (wait) HIP_TRY(c, hipEventSynchronize(S.ready));
+  else {
+    const hipError_t e = hipEventQuery(S.ready);
+    if (e == hipErrorNotReady) { (void)hipGetLastError(); return TSDF_OK; }   // still travelling: *data stays NULL ("not ready" is no error: it must not stay behind as the thread's last one)
+    HIP_TRY(c, e);
+  }
+  c->present_held = true;
+  *data = S.host;
+  if (bytes) *bytes = (uint64_t)c->present_bytes;
+  if (tag) *tag = S.tag;
+  if (size) { size[0] = (uint32_t)c->vw; size[1] = (uint32_t)c->vh; }
+  return TSDF_OK;
+}
+int32_t tsdf_present_release(tsdf_ctx* c) {
+  CHECK_CTX(c);
+  if (!c->present_held) FAIL(c, TSDF_ERR_STATE, "no presented frame is held");
+  c->present_held = false;
+  c->present_head = (c->present_head + 1) % c->present_slots;
+  --c->present_count;
   return TSDF_OK;
 }
 

@@ -141,6 +141,16 @@ struct tsdf_ctx {
   unsigned long long* d_comp_key = nullptr;   // per-pixel bid of the compact composite (rank 0, allocated on first use)   // raymarch hit list (k_march -> k_shade)
   float4* d_fb_c = nullptr; float* d_fb_d = nullptr;
   float* d_linear = nullptr;     // scratch for volume up/download
+  // frame read-out (tsdf_present): the window after the swap (kinect_client.cpp:533) as RGBA8 or DXT1, through a ring of slots -- device buffer (the
+  // conversion kernel's output, on the context's stream), pinned host buffer (the copy stream's, behind `converted`), `ready` behind the copy.  Slots
+  // are taken and handed out in order: present_head is the oldest frame not yet released, present_count the frames queued or held, present_held
+  // whether the head is in the caller's hands.  Allocated by the first tsdf_present at a view size / format; nothing exists before that.
+  struct PresentSlot { void* dev = nullptr; void* host = nullptr; hipEvent_t converted = nullptr, ready = nullptr; uint64_t tag = 0; };
+  static constexpr uint32_t kMaxPresentSlots = 8;
+  PresentSlot present_ring[kMaxPresentSlots];
+  uint32_t present_format = 0, present_flags = 0, present_slots = 3, present_head = 0, present_count = 0; bool present_held = false;
+  size_t present_bytes = 0;      // what the ring's buffers were allocated for (0: none)
+  bool async_upload_ready = false;   // ensure_async_upload ran through (copy_stream alone may be the read-out's)
   // flags (recon_integration.cpp:54-57)
   bool fill_holes = true, use_bricks = true, skip_space = true;
   bool draw_bricks = false;   // setDrawBricks (recon_integration.cpp:57,160-173): tsdf_draw_f ends with the occupied-brick wireframes

@@ -341,6 +341,8 @@ void launch_inpaint_pyramid(hipStream_t st, const Atlas& A, const uint8_t* tile_
 void launch_colorfill(hipStream_t st, const Atlas& A, int w, int h, float4* fb_color, float* fb_depth, int mask = 0, int keep_color = 0, const uint8_t* tile_mask = nullptr);
 // fill_holes off with a colour mask / an uncleared colour buffer: the march renders into the atlas' level-0 region and this merges it
 void launch_resolve_masked(hipStream_t st, const Atlas& A, int w, int h, float4* fb_color, float* fb_depth, int mask, int keep_color);
+// frame read-out (k_present.hip): the framebuffer colour as RGBA8 (format 0: w * h * 4 bytes) or DXT1 blocks (1: ceil(w/4) * ceil(h/4) * 8 bytes) into out
+void launch_present(hipStream_t st, const float4* fb_c, void* out, int w, int h, uint32_t format, int top_down);
 void launch_clear_image(hipStream_t st, float4* color, float* depth, size_t n, float4 c, float d);
 void launch_export_partial(hipStream_t st, const RayTarget& R, int w, int h, void* dst);
 void launch_composite(hipStream_t st, const void* gathered, int n, const RayTarget& R, int w, int h);

@@ -6,6 +6,9 @@
 // Option --sensor-view TYPE WIDTH: after the frame, one "Show textures" window per sensor (SensorTextureViewHip; TYPE 0 Color, 1 Depth,
 // 2 Quality, 4 Silhouette for this pre-processed frame), WIDTH wide, side by side from the top left; the number of pixels it changed is
 // printed and must not be zero.
+// Option --present rgba8|dxt1: five more draws of the frame, each followed by the swap (present, source/kinect_client.cpp:533), the presented frames
+// picked up two frames late and the last two after the loop; tags must come back in order, every frame must have the format's size, and the RGBA8
+// frames must equal the framebuffer download converted on the host (the frame is the same each time).
 //   g++ -std=c++17 frame_harness.cpp -o frame_harness -L.. -lrgbd_recon_hip -Wl,-rpath,'$ORIGIN/..'
 #include <cmath>
 #include <cstdio>
@@ -19,10 +22,14 @@ int main(int argc, char** argv) {
   bool draw_bricks = false;
   int view_type = -1;
   float view_width = 0.0f;
+  int present_format = -1;
   for (int a = 1; a < argc; ++a) {
     if (std::strcmp(argv[a], "--draw-bricks") == 0) draw_bricks = true;
     else if (std::strcmp(argv[a], "--sensor-view") == 0 && a + 2 < argc) { view_type = std::atoi(argv[a + 1]); view_width = (float)std::atof(argv[a + 2]); a += 2; }
-    else { std::fprintf(stderr, "usage: frame_harness [--draw-bricks] [--sensor-view TYPE WIDTH]\n"); return 1; }
+    else if (std::strcmp(argv[a], "--present") == 0 && a + 1 < argc && (std::strcmp(argv[a + 1], "rgba8") == 0 || std::strcmp(argv[a + 1], "dxt1") == 0)) {
+      present_format = std::strcmp(argv[a + 1], "dxt1") == 0 ? (int)TSDF_PRESENT_DXT1 : (int)TSDF_PRESENT_RGBA8; a += 1;
+    }
+    else { std::fprintf(stderr, "usage: frame_harness [--draw-bricks] [--sensor-view TYPE WIDTH] [--present rgba8|dxt1]\n"); return 1; }
   }
   kinect::ReconInputs in;
   in.num_kinects = 1;
@@ -86,6 +93,35 @@ int main(int argc, char** argv) {
       for (std::size_t i = 0; i < d.size(); ++i) changed += std::memcmp(&rgba[4 * i], &rgba2[4 * i], 16) != 0;
       std::printf("%d pixels changed by the sensor windows (%g x %g)\n", changed, size[0], size[1]);
       if (changed == 0 || d2 != d) return 1;
+    }
+    if (present_format >= 0) {
+      recon.configurePresent((unsigned)present_format, TSDF_PRESENT_TOP_DOWN, 3);
+      recon.downloadFramebuffer(rgba, d, 32, 32);
+      const std::uint64_t want_bytes = present_format == (int)TSDF_PRESENT_DXT1 ? 8u * 8u * 8u : 32u * 32u * 4u;
+      const int frames = 5, lag = 2;
+      int got = 0, wrong = 0;
+      auto take = [&](std::uint64_t want_tag) {
+        kinect::ReconIntegrationHip::PresentedFrame fr;
+        if (!recon.acquirePresented(fr) || fr.tag != want_tag || fr.bytes != want_bytes || fr.width != 32 || fr.height != 32) { ++wrong; return; }
+        if (present_format == (int)TSDF_PRESENT_RGBA8) {
+          const std::uint8_t* px = (const std::uint8_t*)fr.data;
+          for (int j = 0; j < 32; ++j) for (int i = 0; i < 32 * 4; ++i) {
+            const float v = rgba[(std::size_t)(31 - j) * 128 + i];                                     // top-down: output row j is window row h - 1 - j
+            const float cl = std::isnan(v) ? 0.0f : std::fmin(std::fmax(v, 0.0f), 1.0f);
+            wrong += px[j * 128 + i] != (std::uint8_t)std::nearbyint(cl * 255.0f);
+          }
+        }
+        recon.releasePresented();
+        ++got;
+      };
+      for (int f = 0; f < frames; ++f) {
+        recon.drawF();
+        if (!recon.present((std::uint64_t)(100 + f))) ++wrong;
+        if (f >= lag) take((std::uint64_t)(100 + f - lag));
+      }
+      for (int f = frames - lag; f < frames; ++f) take((std::uint64_t)(100 + f));
+      std::printf("%d frames presented as %s, %d picked up in order, %d mismatches\n", frames, present_format ? "dxt1" : "rgba8", got, wrong);
+      if (got != frames || wrong != 0) return 1;
     }
     return band > 0 ? 0 : 1;
   } catch (std::exception const& e) {

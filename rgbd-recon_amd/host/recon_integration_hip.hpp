@@ -135,6 +135,31 @@ class ReconIntegrationHip {
     depth.resize((std::size_t)width * height);
     check(tsdf_download_framebuffer(m_ctx, rgba.data(), depth.data()));
   }
+  // ---- the swap: glfwSwapBuffers(window) at the end of the client's frame (source/kinect_client.cpp:533) puts an RGBA8 window on a display; here the
+  // finished framebuffer travels to a ring of pinned host buffers as RGBA8 or as the wire's DXT1 blocks, and the host picks frames up in order while
+  // the next ones are computed.  configurePresent before the first frame (TSDF_PRESENT_RGBA8 / _DXT1, TSDF_PRESENT_TOP_DOWN, 2..8 slots)
+  struct PresentedFrame { const void* data = nullptr; std::uint64_t bytes = 0, tag = 0; unsigned width = 0, height = 0; };
+  void configurePresent(unsigned format, unsigned flags = 0, unsigned slots = 3) { check(tsdf_present_config(m_ctx, format, flags, slots)); }
+  // where the client calls glfwSwapBuffers (kinect_client.cpp:533): never blocks; false = every slot is queued or held, nothing was queued
+  bool present(std::uint64_t tag) {
+    const int32_t rc = tsdf_present(m_ctx, tag);
+    if (rc == TSDF_ERR_STATE) return false;
+    check(rc);
+    return true;
+  }
+  // the oldest frame presented (kinect_client.cpp:533) and not yet released: false while its copy is still under way (wait = false) or nothing is queued;
+  // out.data stays valid until releasePresented()
+  bool acquirePresented(PresentedFrame& out, bool wait = true) {
+    uint32_t size[2] = {0, 0};
+    out = PresentedFrame{};
+    const int32_t rc = tsdf_present_acquire(m_ctx, wait ? 1 : 0, &out.data, &out.bytes, &out.tag, size);
+    if (rc == TSDF_ERR_STATE) return false;
+    check(rc);
+    out.width = size[0]; out.height = size[1];
+    return out.data != nullptr;
+  }
+  // hands the slot of the acquired frame back to present() (the window's back buffer after the swap of kinect_client.cpp:533)
+  void releasePresented() { check(tsdf_present_release(m_ctx)); }
   void downloadVolume(std::vector<float>& tsdf) {
     uint32_t r[3];
     check(tsdf_get_resolution(m_ctx, r, nullptr, nullptr));
