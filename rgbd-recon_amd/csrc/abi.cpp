@@ -1725,6 +1725,10 @@ int32_t tsdf_view_matrices(const float* mv, const float* pr, uint32_t vw, uint32
   return TSDF_OK;
 }
 
+// the per-pixel 64-bit keys of the depth-keyed draws (raster_dev.hpp) and of the compact composite, allocated on first use
+static hipError_t comp_key(tsdf_ctx* c) {
+  return c->d_comp_key ? hipSuccess : hipMalloc(&c->d_comp_key, (size_t)c->vw * c->vh * sizeof(unsigned long long));
+}
 int32_t tsdf_draw_points(tsdf_ctx* c, const float* mv, const float* pr) {
   CHECK_CTX(c);
   if (!mv || !pr) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "null matrix");
@@ -1740,7 +1744,7 @@ int32_t tsdf_draw_points(tsdf_ctx* c, const float* mv, const float* pr) {
   for (int i = 0; i < 16; ++i) Q.pmv.m[i] = (float)pm[i];
   for (int a = 0; a < 3; ++a) { Q.bbox_min[a] = c->cfg.bbox_min[a]; Q.bbox_max[a] = c->cfg.bbox_max[a]; }
   Q.normals = c->d_normal;
-  if (!c->d_comp_key) HIP_TRY(c, hipMalloc(&c->d_comp_key, (size_t)c->vw * c->vh * sizeof(unsigned long long)));
+  HIP_TRY(c, comp_key(c));
   FrameImages F = c->frame;
   F.depth = (float*)c->frame.depth;
   HIP_TRY(c, join_pre(c));
@@ -1958,6 +1962,12 @@ int32_t tsdf_set_stage_overlap(tsdf_ctx* c, int32_t on) {
 }
 
 // ---- the overlays of the client's draw3d() in mono mode (kinect_client.cpp:672-683): "Draw TSDF" and "Draw frustums"
+static OverlayView overlay_view(const tsdf_ctx* c, const float* mv, const float* pr) {
+  OverlayView v;
+  memcpy(v.mv.m, mv, 64); memcpy(v.proj.m, pr, 64);
+  v.w = c->vw; v.h = c->vh;
+  return v;
+}
 static int32_t overlay_mono(tsdf_ctx* c) {
   if (c->color_mask_mode != 0 || c->vp_org[0] != 0 || c->vp_org[1] != 0 || c->vp_off[0] != 0.0f || c->vp_off[1] != 0.0f)
     FAIL(c, TSDF_ERR_STATE, "the overlays are drawn in mono mode only (colour mask 0, no viewport origin / offset)");
@@ -1993,12 +2003,11 @@ int32_t tsdf_draw_calibvis(tsdf_ctx* c, const float* mv, const float* pr) {
     Q.step[a] = 1.0f / (float)Q.gres[a];
   }
   Q.v2w.m[15] = 1.0f;
-  memcpy(Q.mv.m, mv, 64); memcpy(Q.proj.m, pr, 64);
-  Q.w = c->vw; Q.h = c->vh;
+  Q.view = overlay_view(c, mv, pr);
   // empty-space skip: a tile of class kTileMinus holds -limit (every change of the limit marks every class of both volume sets mixed,
   // tsdf_set_tsdf_limit, so the classes were computed under the current one); such samples are discarded iff -limit <= -0.01
   Q.skip = -c->vol.limit <= -kCalibVisLimit ? 1 : 0;
-  if (!c->d_comp_key) HIP_TRY(c, hipMalloc(&c->d_comp_key, (size_t)c->vw * c->vh * sizeof(unsigned long long)));
+  HIP_TRY(c, comp_key(c));
   if (!c->d_calibvis_skipped) HIP_TRY(c, hipMalloc(&c->d_calibvis_skipped, sizeof(unsigned long long)));
   Q.skipped = c->d_calibvis_skipped;
   // a draw: the volume of the latest integrate() (the set a raymarch issued now would read), the framebuffer after the hole filling
@@ -2031,9 +2040,9 @@ int32_t tsdf_draw_frustums(tsdf_ctx* c, const float* mv, const float* pr) {
     memcpy(Q.cam[i], c->frustum_cam[i], sizeof(Q.cam[i]));
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  memcpy(Q.mv.m, mv, 64); memcpy(Q.proj.m, pr, 64);
-  Q.n = (int)c->cfg.num_streams; Q.w = c->vw; Q.h = c->vh;
-  if (!c->d_comp_key) HIP_TRY(c, hipMalloc(&c->d_comp_key, (size_t)c->vw * c->vh * sizeof(unsigned long long)));
+  Q.view = overlay_view(c, mv, pr);
+  Q.n = (int)c->cfg.num_streams;
+  HIP_TRY(c, comp_key(c));
   HIP_TRY(c, join_fill(c));                                              // the hole filling writes the framebuffer from its own lane
   timer_begin(c, "frustums");
   c->fb_consistent = false;
@@ -2048,10 +2057,9 @@ int32_t tsdf_draw_bbox(tsdf_ctx* c, const float* mv, const float* pr) {
   if (int32_t rc = overlay_checks(c, mv, pr, &P)) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   BBoxParams Q{};
-  memcpy(Q.mv.m, mv, 64); memcpy(Q.proj.m, pr, 64);
+  Q.view = overlay_view(c, mv, pr);
   for (int a = 0; a < 3; ++a) { Q.lo[a] = c->cfg.bbox_min[a]; Q.hi[a] = c->cfg.bbox_max[a]; }
-  Q.w = c->vw; Q.h = c->vh;
-  if (!c->d_comp_key) HIP_TRY(c, hipMalloc(&c->d_comp_key, (size_t)c->vw * c->vh * sizeof(unsigned long long)));
+  HIP_TRY(c, comp_key(c));
   HIP_TRY(c, join_fill(c));                                              // the hole filling writes the framebuffer from its own lane
   timer_begin(c, "bbox");
   c->fb_consistent = false;
@@ -2070,9 +2078,8 @@ static int32_t brickwire_precheck(tsdf_ctx* c) {
 static int32_t draw_bricks_impl(tsdf_ctx* c, const float* mv, const float* pr) {
   const bool plain = getenv("RR_BRICKWIRE_PLAIN") != nullptr;             // (measurement hook: the one-wave-per-segment form)
   BrickWireParams Q{};
-  memcpy(Q.mv.m, mv, 64); memcpy(Q.proj.m, pr, 64);
-  Q.w = c->vw; Q.h = c->vh;
-  if (!c->d_comp_key) HIP_TRY(c, hipMalloc(&c->d_comp_key, (size_t)c->vw * c->vh * sizeof(unsigned long long)));
+  Q.view = overlay_view(c, mv, pr);
+  HIP_TRY(c, comp_key(c));
   HIP_TRY(c, join_fill(c));                                              // the hole filling writes the framebuffer from its own lane
   // the list of the latest update, from whatever lane ran it.  The join marks the occupancy set as in use by the context's stream, so the
   // next update on the lane ahead takes the other set; the one after that returns to this set behind the lane's gate, which the
@@ -2617,7 +2624,7 @@ int32_t tsdf_composite_hits_dev(tsdf_ctx* c, const void* gathered, uint32_t n, u
   CHECK_CTX(c);
   if (!gathered || n < 1 || n > 32 || stride_bytes < 32) return TSDF_ERR_INVALID_ARGUMENT;
   HIP_TRY(c, hipSetDevice(c->device));
-  if (!c->d_comp_key) HIP_TRY(c, hipMalloc(&c->d_comp_key, (size_t)c->vw * c->vh * sizeof(unsigned long long)));
+  HIP_TRY(c, comp_key(c));
   // a compositing context that did not march this frame (dedicated compositor, multigpu.py) has no miss counts of its own: 0 then
   HIP_TRY(c, join_fill(c));
   c->draw_masks_valid = false;                                           // the composite writes every pixel of the march target

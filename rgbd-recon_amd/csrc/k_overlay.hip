@@ -3,9 +3,8 @@
 //                    cell of stream 0's inverse LUT grid, coloured by the TSDF sampled there
 //   "Draw frustums"  CalibVolumes::drawFrustums() -> Frustum::draw(), framework/calibration/frustum.cpp:45-95: per stream 12 lines between
 //                    the forward LUT's corner samples and a 3-pixel point at the camera position
-// GL_LESS with primitives drawn in order becomes the points back-end's scheme (k_points.hip): a 64-bit atomicMin per fragment on (window z
-// bits, primitive index) into a key buffer seeded with the framebuffer's depth, behind a strict z < fb_d test against the depth as it was
-// before the overlay; a resolve pass then writes the winners' colour and depth and leaves every other pixel as the previous draw left it.
+// GL_LESS with primitives drawn in order is the depth-key rasteriser of raster_dev.hpp, the single statement of the scheme; here the keys are
+// seeded with the framebuffer's depth as it was before the overlay, and the resolve leaves a pixel without a winner as the previous draw left it.
 // The client then draws the bounding-box wireframe (gloost::BoundingBox::draw, width-2 lines, same scheme) and the texture view
 // (TextureBlitter::blit, a bilinear blit of texture unit 15 or 16 into the lower-left of the frame, no depth test).
 // Between the frustums and the bounding box (or inside drawF() itself, setDrawBricks) come the wireframes of the occupied bricks
@@ -13,25 +12,35 @@
 // Last in this file: the GUI's per-sensor "Show textures" windows (tsdf_draw_sensor_texture), one lane per pixel, blended, no depth.
 // The definitions GL leaves open (point size, line rasterisation, depth clamp) are listed in include/rgbd_recon_hip.h and restated in
 // tests/overlay_reference.py.
-#include "sampling.hpp"
+#include "raster_dev.hpp"
 
 namespace rr {
 
-constexpr uint32_t kNoId = 0xffffffffu;
-
-__device__ __forceinline__ unsigned long long overlay_key(float z, uint32_t id) { return ((unsigned long long)__float_as_uint(z) << 32) | (unsigned long long)id; }
-
-// one fragment: strict GL_LESS against the framebuffer's depth, then the in-order tie rule through the key.  Keys only decrease: a plain load
-// that already holds a key <= k makes the atomic redundant.
-__device__ __forceinline__ void overlay_fragment(const float* __restrict__ fb_d, unsigned long long* __restrict__ key, int pix, float z, uint32_t id) {
-  if (!(z < fb_d[pix])) return;
-  const unsigned long long k = overlay_key(z, id);
-  if (k < key[pix]) atomicMin(&key[pix], k);
-}
-
 __global__ __launch_bounds__(256) void k_overlay_clear(const float* __restrict__ fb_d, unsigned long long* __restrict__ key, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) key[i] = overlay_key(fb_d[i], kNoId);
+  if (i < n) key[i] = depth_key(fb_d[i], kNoId);
+}
+
+// the winner's colour from its primitive index (a functor), and its depth; a pixel no fragment passed at stays as the previous draw left it
+template <class Color>
+__global__ __launch_bounds__(256) void k_overlay_resolve(Color color, int n, const unsigned long long* __restrict__ key, float4* __restrict__ fb_c,
+                                                         float* __restrict__ fb_d) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned long long k = key[i];
+  if (key_id(k) == kNoId) return;
+  fb_c[i] = color(key_id(k));
+  fb_d[i] = key_depth(k);
+}
+struct SolidColor { float4 c; __device__ float4 operator()(uint32_t) const { return c; } };
+
+// one overlay draw: clear, the caller's scatter launch, resolve
+template <class Scatter, class Color>
+static void overlay_draw(hipStream_t st, const OverlayView& view, unsigned long long* key, float4* fb_c, float* fb_d, Scatter scatter, Color color) {
+  const int n = view.w * view.h;
+  hipLaunchKernelGGL(k_overlay_clear, dim3((n + 255) / 256), dim3(256), 0, st, fb_d, key, n);
+  scatter();
+  hipLaunchKernelGGL(k_overlay_resolve<Color>, dim3((n + 255) / 256), dim3(256), 0, st, color, n, key, fb_c, fb_d);
 }
 
 // ---- "Draw TSDF"
@@ -81,159 +90,60 @@ __global__ __launch_bounds__(256) void k_calibvis_scatter(CalibVisParams Q, Volu
   const float d = calib_sample<kSparse>(Q, V, x, y, z, u);
   if (d <= -kCalibVisLimit) return;                                      // calib_vis.fs:29: discard (before the depth test)
   const float4 pw = mat_mul(Q.v2w, u[0], u[1], u[2], 1.0f);              // calib_vis.vs:29-38, in this order
-  const float4 pe = mat_mul(Q.mv, pw.x, pw.y, pw.z, 1.0f);
-  const float4 clip = mat_mul(Q.proj, pe.x, pe.y, pe.z, 1.0f);
-  if (!(clip.w > 0.0f) || fabsf(clip.x) > clip.w || fabsf(clip.y) > clip.w || fabsf(clip.z) > clip.w) return;   // whole-point clip (point_vertex)
-  const float xw = (clip.x / clip.w * 0.5f + 0.5f) * (float)Q.w;
-  const float yw = (clip.y / clip.w * 0.5f + 0.5f) * (float)Q.h;
-  const float zw = clip.z / clip.w * 0.5f + 0.5f;
-  if (!(zw < 1.0f)) return;
-  // a 1-pixel point, k_points_scatter's coverage rule
-  int x0 = (int)ceilf((xw - 0.5f) - 0.5f), x1 = (int)ceilf((xw + 0.5f) - 0.5f) - 1;
-  int y0 = (int)ceilf((yw - 0.5f) - 0.5f), y1 = (int)ceilf((yw + 0.5f) - 0.5f) - 1;
-  x0 = max(x0, 0); y0 = max(y0, 0); x1 = min(x1, Q.w - 1); y1 = min(y1, Q.h - 1);
+  const float4 pe = mat_mul(Q.view.mv, pw.x, pw.y, pw.z, 1.0f);
+  const float4 clip = mat_mul(Q.view.proj, pe.x, pe.y, pe.z, 1.0f);      // (w = 1 here, not pe.w: the shader's own expression)
+  const WindowPoint win = point_to_window(clip, Q.view.w, Q.view.h);
+  if (!win.ok) return;
+  const PixelBox b = square_coverage(win.pos.x, win.pos.y, 0.5f, Q.view.w, Q.view.h);   // a 1-pixel point
   const uint32_t id = (uint32_t)((z * Q.gres[1] + y) * Q.gres[0] + x);   // draw order: x fastest, then y, then z
-  for (int py = y0; py <= y1; ++py)
-    for (int px = x0; px <= x1; ++px) overlay_fragment(fb_d, key, py * Q.w + px, zw, id);
+  for (int py = b.y0; py <= b.y1; ++py)
+    for (int px = b.x0; px <= b.x1; ++px) overlay_fragment(fb_d, key, py * Q.view.w + px, win.pos.z, id);
 }
 
 template <bool kSparse>
-__global__ __launch_bounds__(256) void k_calibvis_resolve(CalibVisParams Q, Volume V, const unsigned long long* __restrict__ key, float4* __restrict__ fb_c,
-                                                          float* __restrict__ fb_d) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= Q.w * Q.h) return;
-  const unsigned long long k = key[i];
-  const uint32_t id = (uint32_t)k;
-  if (id == kNoId) return;                                               // no fragment passed: the previous draw's pixel stays
-  const int x = (int)(id % (uint32_t)Q.gres[0]), y = (int)((id / (uint32_t)Q.gres[0]) % (uint32_t)Q.gres[1]), z = (int)(id / (uint32_t)(Q.gres[0] * Q.gres[1]));
-  float u[3];
-  fb_c[i] = calib_color(calib_sample<kSparse>(Q, V, x, y, z, u));        // recomputed from the id: no per-point colour store
-  fb_d[i] = __uint_as_float((uint32_t)(k >> 32));
-}
-
-void launch_draw_calibvis(hipStream_t st, const CalibVisParams& Q, const Volume& V, unsigned long long* key, float4* fb_c, float* fb_d) {
-  const int n = Q.w * Q.h;
-  const dim3 grid((Q.gres[0] + 7) / 8, (Q.gres[1] + 7) / 8, (Q.gres[2] + 3) / 4);
-  hipLaunchKernelGGL(k_overlay_clear, dim3((n + 255) / 256), dim3(256), 0, st, fb_d, key, n);
-  if (V.slot) {
-    hipLaunchKernelGGL(k_calibvis_scatter<true>, grid, dim3(256), 0, st, Q, V, fb_d, key);
-    hipLaunchKernelGGL(k_calibvis_resolve<true>, dim3((n + 255) / 256), dim3(256), 0, st, Q, V, key, fb_c, fb_d);
-  } else {
-    hipLaunchKernelGGL(k_calibvis_scatter<false>, grid, dim3(256), 0, st, Q, V, fb_d, key);
-    hipLaunchKernelGGL(k_calibvis_resolve<false>, dim3((n + 255) / 256), dim3(256), 0, st, Q, V, key, fb_c, fb_d);
+struct CalibVisColor {                                                   // recomputed from the id: no per-point colour store
+  CalibVisParams Q; Volume V;
+  __device__ float4 operator()(uint32_t id) const {
+    const int x = (int)(id % (uint32_t)Q.gres[0]), y = (int)((id / (uint32_t)Q.gres[0]) % (uint32_t)Q.gres[1]), z = (int)(id / (uint32_t)(Q.gres[0] * Q.gres[1]));
+    float u[3];
+    return calib_color(calib_sample<kSparse>(Q, V, x, y, z, u));
   }
+};
+template <bool kSparse>
+static void draw_calibvis(hipStream_t st, const CalibVisParams& Q, const Volume& V, unsigned long long* key, float4* fb_c, float* fb_d) {
+  const dim3 grid((Q.gres[0] + 7) / 8, (Q.gres[1] + 7) / 8, (Q.gres[2] + 3) / 4);
+  overlay_draw(st, Q.view, key, fb_c, fb_d, [&] { hipLaunchKernelGGL(k_calibvis_scatter<kSparse>, grid, dim3(256), 0, st, Q, V, fb_d, key); },
+               CalibVisColor<kSparse>{Q, V});
+}
+void launch_draw_calibvis(hipStream_t st, const CalibVisParams& Q, const Volume& V, unsigned long long* key, float4* fb_c, float* fb_d) {
+  if (V.slot) draw_calibvis<true>(st, Q, V, key, fb_c, fb_d); else draw_calibvis<false>(st, Q, V, key, fb_c, fb_d);
 }
 
 // ---- "Draw frustums": 13 primitives per stream (the 12 lines of frustum.cpp:48-84, then the camera point of :87-94), one wave each
 __constant__ int c_frustum_lines[12][2] = {{0, 4}, {1, 5}, {2, 6}, {3, 7}, {0, 1}, {1, 2}, {2, 3}, {3, 0}, {4, 5}, {5, 6}, {6, 7}, {7, 4}};
 
-__device__ __forceinline__ float4 frustum_clip(const FrustumParams& Q, const float* p) {   // P . (MV . p)
-  const float4 e = mat_mul(Q.mv, p[0], p[1], p[2], 1.0f);
-  return mat_mul(Q.proj, e.x, e.y, e.z, e.w);
-}
-// clip the segment a -> b against one plane (inside: dist >= 0); false = nothing left
-__device__ __forceinline__ bool clip_plane(float4& a, float4& b, float da, float db) {
-  if (!(da >= 0.0f) && !(db >= 0.0f)) return false;
-  if (!(da >= 0.0f)) {
-    const float t = da / (da - db);
-    a = make_float4(a.x + (b.x - a.x) * t, a.y + (b.y - a.y) * t, a.z + (b.z - a.z) * t, a.w + (b.w - a.w) * t);
-  } else if (!(db >= 0.0f)) {
-    const float t = db / (db - da);
-    b = make_float4(b.x + (a.x - b.x) * t, b.y + (a.y - b.y) * t, b.z + (a.z - b.z) * t, b.w + (a.w - b.w) * t);
-  }
-  return true;
-}
-
-// The set-up of a clipped segment: window coordinates, major / minor axis, and the conservative range [lo, hi] of pixel columns (rows) whose
-// centres can lie on it.  false = nothing to walk.
-struct LineSetup {
-  float s0, s1, o0, o1, az, bz;                                          // major start / end, minor start / end, depth start / end
-  int lo, hi, xmajor;
-};
-__device__ __forceinline__ bool overlay_line_setup(float4 a, float4 b, int w, int h, int width, LineSetup& L) {
-  if (!clip_plane(a, b, a.z + a.w, b.z + b.w) || !clip_plane(a, b, a.w - a.z, b.w - b.z)) return false;   // near, then far
-  if (!(a.w > 0.0f) || !(b.w > 0.0f)) return false;
-  const float W = (float)w, H = (float)h;
-  const float ax = (a.x / a.w * 0.5f + 0.5f) * W, ay = (a.y / a.w * 0.5f + 0.5f) * H, az = a.z / a.w * 0.5f + 0.5f;
-  const float bx = (b.x / b.w * 0.5f + 0.5f) * W, by = (b.y / b.w * 0.5f + 0.5f) * H, bz = b.z / b.w * 0.5f + 0.5f;
-  const bool xmajor = fabsf(bx - ax) >= fabsf(by - ay);
-  float s0 = xmajor ? ax : ay, s1 = xmajor ? bx : by, o0 = xmajor ? ay : ax, o1 = xmajor ? by : bx;
-  if (width > 1) {
-    const float shift = 0.5f * (float)(width - 1);
-    o0 -= shift; o1 -= shift;
-  }
-  const int n_major = xmajor ? w : h;
-  const float lo = fmaxf(floorf(fminf(s0, s1)) - 1.0f, 0.0f), hi = fminf(ceilf(fmaxf(s0, s1)) + 1.0f, (float)(n_major - 1));
-  if (!(lo <= hi)) return false;
-  L.s0 = s0; L.s1 = s1; L.o0 = o0; L.o1 = o1; L.az = az; L.bz = bz;
-  L.lo = (int)lo; L.hi = (int)hi; L.xmajor = xmajor ? 1 : 0;
-  return true;
-}
-// ... and the fragment(s) of pixel column (row) i of such a segment
-__device__ __forceinline__ void overlay_line_fragment(float s0, float s1, float o0, float o1, float az, float bz, bool xmajor, int i, int w, int h, int width,
-                                                      uint32_t id, const float* __restrict__ fb_d, unsigned long long* __restrict__ key) {
-  const float c = (float)i + 0.5f;
-  if (!(s1 > s0 ? (c >= s0 && c < s1) : (c <= s0 && c > s1))) return;
-  const float t = (c - s0) / (s1 - s0);
-  const float m = floorf(o0 + (o1 - o0) * t);
-  float z = az + (bz - az) * t;
-  if (z != z) return;
-  z = z > 0.0f ? (z < 1.0f ? z : 1.0f) : 0.0f;                            // the depth range [0, 1]
-  const int n_minor = xmajor ? h : w;
-  for (int r = 0; r < width; ++r) {
-    const float mr = m + (float)r;
-    if (!(mr >= 0.0f && mr < (float)n_minor)) continue;
-    const int px = xmajor ? i : (int)mr, py = xmajor ? (int)mr : i;
-    overlay_fragment(fb_d, key, py * w + px, z, id);
-  }
-}
-// One segment between the clip-space points a -> b, walked by the 64 lanes of a wave: near, then far clip, then the diamond exit for
-// width 1 -- an x-major line makes one fragment per pixel column whose centre c lies in [start, end) along the line's direction, in the row
-// floor(y(c)); y-major the same with rows.  Wider lines (GL 4.4 section 14.5.2.2, aliased): the segment moves by -(width - 1) / 2 in its
-// minor direction, is walked by the same rule, and each of its fragments becomes `width` fragments upwards in the minor direction at that
-// fragment's depth, each dropped on its own outside the view.
-__device__ __forceinline__ void overlay_line(float4 a, float4 b, int w, int h, int width, uint32_t id, int lane, const float* __restrict__ fb_d,
-                                             unsigned long long* __restrict__ key) {
-  LineSetup L;
-  if (!overlay_line_setup(a, b, w, h, width, L)) return;
-  for (int i = L.lo + lane; i <= L.hi; i += 64) overlay_line_fragment(L.s0, L.s1, L.o0, L.o1, L.az, L.bz, L.xmajor != 0, i, w, h, width, id, fb_d, key);
-}
-
+__device__ __forceinline__ float4 frustum_clip(const FrustumParams& Q, const float* p) { return clip_pos(Q.view.mv, Q.view.proj, p[0], p[1], p[2]); }
 __global__ __launch_bounds__(64) void k_frustum_lines(FrustumParams Q, const float* __restrict__ fb_d, unsigned long long* __restrict__ key) {
   const int prim = blockIdx.x, s = prim / 13, k = prim % 13, lane = threadIdx.x;
   const uint32_t id = (uint32_t)prim;                                    // stream * 13 + k: the draw order
-  const float W = (float)Q.w, H = (float)Q.h;
+  const int w = Q.view.w, h = Q.view.h;
   if (k == 12) {                                                         // glPointSize(3) at the camera position
-    const float4 clip = frustum_clip(Q, Q.cam[s]);
-    if (!(clip.w > 0.0f) || fabsf(clip.x) > clip.w || fabsf(clip.y) > clip.w || fabsf(clip.z) > clip.w) return;
-    const float xw = (clip.x / clip.w * 0.5f + 0.5f) * W, yw = (clip.y / clip.w * 0.5f + 0.5f) * H, zw = clip.z / clip.w * 0.5f + 0.5f;
-    if (!(zw < 1.0f)) return;
-    int x0 = (int)ceilf((xw - 1.5f) - 0.5f), x1 = (int)ceilf((xw + 1.5f) - 0.5f) - 1;
-    int y0 = (int)ceilf((yw - 1.5f) - 0.5f), y1 = (int)ceilf((yw + 1.5f) - 0.5f) - 1;
-    x0 = max(x0, 0); y0 = max(y0, 0); x1 = min(x1, Q.w - 1); y1 = min(y1, Q.h - 1);
-    const int nx = x1 - x0 + 1, ny = y1 - y0 + 1;
+    const WindowPoint win = point_to_window(frustum_clip(Q, Q.cam[s]), w, h);
+    if (!win.ok) return;
+    const PixelBox b = square_coverage(win.pos.x, win.pos.y, 1.5f, w, h);
+    const int nx = b.x1 - b.x0 + 1, ny = b.y1 - b.y0 + 1;
     if (nx <= 0 || ny <= 0) return;
-    for (int q = lane; q < nx * ny; q += 64) overlay_fragment(fb_d, key, (y0 + q / nx) * Q.w + x0 + q % nx, zw, id);
+    for (int q = lane; q < nx * ny; q += 64) overlay_fragment(fb_d, key, (b.y0 + q / nx) * w + b.x0 + q % nx, win.pos.z, id);
     return;
   }
-  overlay_line(frustum_clip(Q, Q.corner[s][c_frustum_lines[k][0]]), frustum_clip(Q, Q.corner[s][c_frustum_lines[k][1]]), Q.w, Q.h, 1, id, lane, fb_d, key);
+  overlay_line(frustum_clip(Q, Q.corner[s][c_frustum_lines[k][0]]), frustum_clip(Q, Q.corner[s][c_frustum_lines[k][1]]), w, h, 1, id, lane, fb_d, key);
 }
 
-__global__ __launch_bounds__(256) void k_frustum_resolve(int n, const unsigned long long* __restrict__ key, float4* __restrict__ fb_c, float* __restrict__ fb_d) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const unsigned long long k = key[i];
-  const uint32_t id = (uint32_t)k;
-  if (id == kNoId) return;
-  fb_c[i] = id % 13 == 12 ? make_float4(1.0f, 0.0f, 0.0f, 1.0f) : make_float4(0.0f, 1.0f, 0.0f, 1.0f);   // frustum.cpp:49 / :91
-  fb_d[i] = __uint_as_float((uint32_t)(k >> 32));
-}
-
+struct FrustumColor {                                                    // frustum.cpp:49 (the lines) / :91 (the point)
+  __device__ float4 operator()(uint32_t id) const { return id % 13 == 12 ? make_float4(1.0f, 0.0f, 0.0f, 1.0f) : make_float4(0.0f, 1.0f, 0.0f, 1.0f); }
+};
 void launch_draw_frustums(hipStream_t st, const FrustumParams& Q, unsigned long long* key, float4* fb_c, float* fb_d) {
-  const int n = Q.w * Q.h;
-  hipLaunchKernelGGL(k_overlay_clear, dim3((n + 255) / 256), dim3(256), 0, st, fb_d, key, n);
-  hipLaunchKernelGGL(k_frustum_lines, dim3(Q.n * 13), dim3(64), 0, st, Q, fb_d, key);
-  hipLaunchKernelGGL(k_frustum_resolve, dim3((n + 255) / 256), dim3(256), 0, st, n, key, fb_c, fb_d);
+  overlay_draw(st, Q.view, key, fb_c, fb_d, [&] { hipLaunchKernelGGL(k_frustum_lines, dim3(Q.n * 13), dim3(64), 0, st, Q, fb_d, key); }, FrustumColor{});
 }
 
 // ---- the bounding-box wireframe: gloost::BoundingBox::draw() -> drawWiredBox (gloostRenderGoodies.h:251-304), glLineWidth(2).  Six
@@ -241,30 +151,19 @@ void launch_draw_frustums(hipStream_t st, const FrustumParams& Q, unsigned long 
 // primitive index 4 * loop + k.  A corner is x | y << 1 | z << 2 with 0 = bbox_min and 1 = bbox_max on that axis.
 __constant__ uint8_t c_bbox_loops[6][4] = {{4, 5, 7, 6}, {5, 1, 3, 7}, {1, 0, 2, 3}, {0, 4, 6, 2}, {6, 7, 3, 2}, {0, 1, 5, 4}};
 
-__device__ __forceinline__ float4 bbox_clip(const BBoxParams& Q, int corner) {   // P . (MV . p)
-  const float4 e = mat_mul(Q.mv, (corner & 1) ? Q.hi[0] : Q.lo[0], (corner & 2) ? Q.hi[1] : Q.lo[1], (corner & 4) ? Q.hi[2] : Q.lo[2], 1.0f);
-  return mat_mul(Q.proj, e.x, e.y, e.z, e.w);
+__device__ __forceinline__ float4 bbox_clip(const BBoxParams& Q, int corner) {
+  return clip_pos(Q.view.mv, Q.view.proj, (corner & 1) ? Q.hi[0] : Q.lo[0], (corner & 2) ? Q.hi[1] : Q.lo[1], (corner & 4) ? Q.hi[2] : Q.lo[2]);
 }
 
 __global__ __launch_bounds__(64) void k_bbox_lines(BBoxParams Q, const float* __restrict__ fb_d, unsigned long long* __restrict__ key) {
   const int prim = blockIdx.x, loop = prim >> 2, k = prim & 3;
-  overlay_line(bbox_clip(Q, c_bbox_loops[loop][k]), bbox_clip(Q, c_bbox_loops[loop][(k + 1) & 3]), Q.w, Q.h, 2, (uint32_t)prim, threadIdx.x, fb_d, key);
-}
-
-__global__ __launch_bounds__(256) void k_bbox_resolve(int n, const unsigned long long* __restrict__ key, float4* __restrict__ fb_c, float* __restrict__ fb_d) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const unsigned long long k = key[i];
-  if ((uint32_t)k == kNoId) return;
-  fb_c[i] = make_float4(1.0f, 1.0f, 1.0f, 0.75f);                        // glColor4f(1, 1, 1, 0.75), BoundingBox.cpp:304-305
-  fb_d[i] = __uint_as_float((uint32_t)(k >> 32));
+  overlay_line(bbox_clip(Q, c_bbox_loops[loop][k]), bbox_clip(Q, c_bbox_loops[loop][(k + 1) & 3]), Q.view.w, Q.view.h, 2, (uint32_t)prim, threadIdx.x, fb_d,
+               key);
 }
 
 void launch_draw_bbox(hipStream_t st, const BBoxParams& Q, unsigned long long* key, float4* fb_c, float* fb_d) {
-  const int n = Q.w * Q.h;
-  hipLaunchKernelGGL(k_overlay_clear, dim3((n + 255) / 256), dim3(256), 0, st, fb_d, key, n);
-  hipLaunchKernelGGL(k_bbox_lines, dim3(24), dim3(64), 0, st, Q, fb_d, key);
-  hipLaunchKernelGGL(k_bbox_resolve, dim3((n + 255) / 256), dim3(256), 0, st, n, key, fb_c, fb_d);
+  overlay_draw(st, Q.view, key, fb_c, fb_d, [&] { hipLaunchKernelGGL(k_bbox_lines, dim3(24), dim3(64), 0, st, Q, fb_d, key); },
+               SolidColor{make_float4(1.0f, 1.0f, 1.0f, 0.75f)});        // glColor4f(1, 1, 1, 0.75), BoundingBox.cpp:304-305
 }
 
 // ---- "Draw occupied bricks": ReconIntegration::drawOccupiedBricks() (recon_integration.cpp:447-454) = glsl/bricks.vs + glsl/solid.fs over
@@ -285,8 +184,7 @@ __device__ __forceinline__ float4 brick_corner_clip(const BrickWireParams& Q, co
   float p[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) p[a] = (float)idx[a] * B.size[a] + B.bbox_min[a] + (((corner >> a) & 1) ? 1.0f : 0.0f) * B.size[a];
-  const float4 e = mat_mul(Q.mv, p[0], p[1], p[2], 1.0f);
-  return mat_mul(Q.proj, e.x, e.y, e.z, e.w);
+  return clip_pos(Q.view.mv, Q.view.proj, p[0], p[1], p[2]);
 }
 
 // The plain form (kept for comparison, RR_BRICKWIRE_PLAIN=1): one wave per (brick, segment) pair, each projecting its two corners and
@@ -295,8 +193,8 @@ __global__ __launch_bounds__(64) void k_brickwire_plain(BrickWireParams Q, Brick
   const uint32_t n = *B.num_occupied * 12u;
   for (uint32_t p = blockIdx.x; p < n; p += gridDim.x) {
     const uint32_t id = B.occupied[p / 12u], s = p % 12u;
-    overlay_line(brick_corner_clip(Q, B, id, c_cube_vertex[c_cube_wire[s][0]]), brick_corner_clip(Q, B, id, c_cube_vertex[c_cube_wire[s][1]]), Q.w, Q.h, 1,
-                 id * 12u + s, threadIdx.x, fb_d, key);
+    overlay_line(brick_corner_clip(Q, B, id, c_cube_vertex[c_cube_wire[s][0]]), brick_corner_clip(Q, B, id, c_cube_vertex[c_cube_wire[s][1]]), Q.view.w,
+                 Q.view.h, 1, id * 12u + s, threadIdx.x, fb_d, key);
   }
 }
 
@@ -333,7 +231,7 @@ __global__ __launch_bounds__(64) void k_brickwire_scatter(BrickWireParams Q, Bri
     int cnt = 0;
     if (lane < 12) {
       LineSetup L;
-      if (overlay_line_setup(s_clip[c_cube_wire[lane][0]], s_clip[c_cube_wire[lane][1]], Q.w, Q.h, 1, L)) {
+      if (overlay_line_setup(s_clip[c_cube_wire[lane][0]], s_clip[c_cube_wire[lane][1]], Q.view.w, Q.view.h, 1, L)) {
         cnt = L.hi - L.lo + 1;
         s_seg[lane][0] = make_float4(L.s0, L.s1, L.o0, L.o1);
         s_seg[lane][1] = make_float4(L.az, L.bz, __int_as_float(L.lo), __int_as_float(L.xmajor));
@@ -350,28 +248,18 @@ __global__ __launch_bounds__(64) void k_brickwire_scatter(BrickWireParams Q, Bri
 #pragma unroll
       for (int q = 0; q < 11; ++q) if (k >= end[q]) { s = q + 1; first = end[q]; }   // the segment whose range holds candidate k
       const float4 g0 = s_seg[s][0], g1 = s_seg[s][1];
-      overlay_line_fragment(g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, __float_as_int(g1.w) != 0, __float_as_int(g1.z) + (k - first), Q.w, Q.h, 1,
-                            id * 12u + (uint32_t)s, fb_d, key);
+      overlay_line_fragment(g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, __float_as_int(g1.w) != 0, __float_as_int(g1.z) + (k - first), Q.view.w,
+                            Q.view.h, 1, id * 12u + (uint32_t)s, fb_d, key);
     }
   }
 }
 
-__global__ __launch_bounds__(256) void k_brickwire_resolve(int n, const unsigned long long* __restrict__ key, float4* __restrict__ fb_c, float* __restrict__ fb_d) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const unsigned long long k = key[i];
-  if ((uint32_t)k == kNoId) return;
-  fb_c[i] = make_float4(1.0f, 0.0f, 0.0f, 1.0f);                         // uniform Color (1, 0, 0), solid.fs: (Color, 1)
-  fb_d[i] = __uint_as_float((uint32_t)(k >> 32));
-}
-
 void launch_draw_brickwire(hipStream_t st, const BrickWireParams& Q, const Bricks& B, unsigned long long* key, float4* fb_c, float* fb_d, bool plain) {
-  const int n = Q.w * Q.h;
-  hipLaunchKernelGGL(k_overlay_clear, dim3((n + 255) / 256), dim3(256), 0, st, fb_d, key, n);
   // the list's length is a device scalar: the grids are sized by the brick grid, never by a read-back
-  if (plain) hipLaunchKernelGGL(k_brickwire_plain, dim3(12ll * B.n < 65536 ? 12 * B.n : 65536), dim3(64), 0, st, Q, B, fb_d, key);
-  else hipLaunchKernelGGL(k_brickwire_scatter, dim3(B.n < 8192 ? B.n : 8192), dim3(64), 0, st, Q, B, fb_d, key);
-  hipLaunchKernelGGL(k_brickwire_resolve, dim3((n + 255) / 256), dim3(256), 0, st, n, key, fb_c, fb_d);
+  overlay_draw(st, Q.view, key, fb_c, fb_d, [&] {
+    if (plain) hipLaunchKernelGGL(k_brickwire_plain, dim3(12ll * B.n < 65536 ? 12 * B.n : 65536), dim3(64), 0, st, Q, B, fb_d, key);
+    else hipLaunchKernelGGL(k_brickwire_scatter, dim3(B.n < 8192 ? B.n : 8192), dim3(64), 0, st, Q, B, fb_d, key);
+  }, SolidColor{make_float4(1.0f, 0.0f, 0.0f, 1.0f)});                   // uniform Color (1, 0, 0), solid.fs: (Color, 1)
 }
 
 // ---- the texture view: TextureBlitter::blit(unit, res) (texture_blitter.cpp, glsl/texture_passthrough.{vs,fs} mode 0) of texture unit 15

@@ -9,7 +9,7 @@
 // SURVEY.md Appendix C.3).
 #include <cstdlib>
 
-#include "sampling.hpp"
+#include "raster_dev.hpp"
 #include "shading_dev.hpp"
 
 namespace rr {
@@ -101,8 +101,8 @@ __global__ __launch_bounds__(64) void k_depth_limits(ViewParams P, Bricks B, uin
       const float4 e = mat_mul(P.mv, (c & 1) ? hi[0] : lo[0], (c & 2) ? hi[1] : lo[1], (c & 4) ? hi[2] : lo[2], 1.0f);
       const float4 cl = mat_mul(P.proj, e.x, e.y, e.z, e.w);
       behind |= !(cl.w > 1.0e-6f);
-      const float wx = (cl.x / cl.w * 0.5f + 0.5f) * (float)P.w, wy = (cl.y / cl.w * 0.5f + 0.5f) * (float)P.h;
-      bx0 = fminf(bx0, wx); bx1 = fmaxf(bx1, wx); by0 = fminf(by0, wy); by1 = fmaxf(by1, wy);
+      const float3 win = clip_to_window(cl, P.w, P.h);
+      bx0 = fminf(bx0, win.x); bx1 = fmaxf(bx1, win.x); by0 = fminf(by0, win.y); by1 = fmaxf(by1, win.y);
     }
     int x0 = 0, x1 = P.w - 1, y0 = 0, y1 = P.h - 1;
     if (!behind) {

@@ -4,6 +4,7 @@
 // the fragment's quality (kMvt below).  Coverage, interpolation and every test are the oracle's expressions in the oracle's order.
 #ifndef RR_TRIGRID_DEV_HPP
 #define RR_TRIGRID_DEV_HPP
+#include "raster_dev.hpp"
 #include "shading_dev.hpp"
 
 namespace rr {
@@ -32,9 +33,8 @@ __device__ __forceinline__ TriVert tri_vertex_at(const ViewParams& P, const Poin
   const float4 clip = mat_mul(Q.pmv, t.pos_cs.x, t.pos_cs.y, t.pos_cs.z, 1.0f);
   t.front = clip.w > 0.0f;
   t.iw = 1.0f / clip.w;
-  t.xw = (clip.x / clip.w * 0.5f + 0.5f) * (float)P.w;
-  t.yw = (clip.y / clip.w * 0.5f + 0.5f) * (float)P.h;
-  t.zw = clip.z / clip.w * 0.5f + 0.5f;
+  const float3 win = clip_to_window(clip, P.w, P.h);                     // (no clip here: tri_setup drops a triangle with a vertex behind the eye)
+  t.xw = win.x; t.yw = win.y; t.zw = win.z;
   return t;
 }
 

@@ -191,28 +191,28 @@ void launch_draw_mvt(hipStream_t st, const ViewParams& P, const PointParams& Q, 
                      float2* vtx, uint32_t* zbuf, float4* acc, float4* fb_c, float* fb_d);
 
 // overlays of the client's draw3d() (k_overlay.hip): "Draw TSDF" (kinect::ReconCalibs::draw) and "Draw frustums" (Frustum::draw)
+struct OverlayView { Mat4 mv, proj; int w, h; };   // the head of every overlay's parameters: the caller's matrices and the view's size
 struct CalibVisParams {
-  Mat4 v2w, mv, proj;           // vol_to_world as recon_calibs.cpp:38-45 builds it in fp32; the caller's matrices
+  Mat4 v2w;                     // vol_to_world as recon_calibs.cpp:38-45 builds it in fp32
+  OverlayView view;
   int gres[3];                  // the point grid: stream 0's inverse LUT resolution (CalibVolumes::getVolumeRes)
   float step[3];                // 1.0f / gres (volume_sampler.cpp:33-35)
-  int w, h;
   int skip;                     // 1: a workgroup whose taps lie in kTileMinus tiles only is discarded whole (the clear value is <= -0.01)
   unsigned long long* skipped;  // device counter: grid points removed by that test
 };
 struct FrustumParams {
-  Mat4 mv, proj;
+  OverlayView view;
   float corner[TSDF_MAX_STREAMS][8][3];   // getCornerPoints of each stream's cv_xyz (CalibVolumes.cpp:98-113)
   float cam[TSDF_MAX_STREAMS][3];         // Frustum::getCameraPos
-  int n, w, h;
+  int n;
 };
 constexpr float kCalibVisLimit = 0.01f;   // recon_calibs.cpp:20 (static; not the context's setTsdfLimit value)
 void launch_draw_calibvis(hipStream_t st, const CalibVisParams& Q, const Volume& V, unsigned long long* key, float4* fb_c, float* fb_d);
 void launch_draw_frustums(hipStream_t st, const FrustumParams& Q, unsigned long long* key, float4* fb_c, float* fb_d);
 // ... and the two after them: the bounding-box wireframe (gloost::BoundingBox::draw) and the texture view (TextureBlitter::blit)
 struct BBoxParams {
-  Mat4 mv, proj;
+  OverlayView view;
   float lo[3], hi[3];           // bbox_min / bbox_max as configured (g_bbox)
-  int w, h;
 };
 struct BlitParams {
   const float4* src;            // unit 15: the hole-filling atlas (RGBA32F); unit 16: the depth-limit peels (bits, see k_blit_texture)
@@ -223,10 +223,7 @@ struct BlitParams {
 };
 void launch_draw_bbox(hipStream_t st, const BBoxParams& Q, unsigned long long* key, float4* fb_c, float* fb_d);
 // the occupied-brick wireframes (ReconIntegration::drawOccupiedBricks): the list and count of B as the latest update left them
-struct BrickWireParams {
-  Mat4 mv, proj;
-  int w, h;
-};
+struct BrickWireParams { OverlayView view; };
 void launch_draw_brickwire(hipStream_t st, const BrickWireParams& Q, const Bricks& B, unsigned long long* key, float4* fb_c, float* fb_d, bool plain);
 void launch_blit_texture(hipStream_t st, const BlitParams& Q, float4* fb_c);
 // the GUI's "Show textures" windows (tsdf_draw_sensor_texture): what the layer's texel is and how it becomes the sample's vec4
