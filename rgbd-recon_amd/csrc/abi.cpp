@@ -434,10 +434,11 @@ hipError_t join_integ(tsdf_ctx* c) {
   const hipError_t e = hipEventRecord(c->integ_done, c->integ_stream);
   return e != hipSuccess ? e : hipStreamWaitEvent(c->stream, c->integ_done, 0);
 }
+// the context holds every tile layer of the volume (false: a Z-slab)
+static bool whole_volume(const tsdf_ctx* c) { return c->vol.own_tz0 == 0 && c->vol.own_tz1 == (c->res[2] + 7) / 8; }
 bool deep_ok(const tsdf_ctx* c) {
   // (a Z-slab context too, when it recomputes its halo layers itself: an EXCHANGED halo is written into the volume from outside between integrate() and the draw)
-  const bool whole = (c->vol.own_tz0 == 0 && c->vol.own_tz1 == (c->res[2] + 7) / 8);
-  return c->deep && !c->deep_failed && pipelined(c) && c->integ_stream && (whole || c->cfg.slab_recompute_halo != 0) && !c->vol.slot && c->proj_budget == 0;
+  return c->deep && !c->deep_failed && pipelined(c) && c->integ_stream && (whole_volume(c) || c->cfg.slab_recompute_halo != 0) && !c->vol.slot && c->proj_budget == 0;
 }
 // exchange the set in use with the other one (host pointers only: kernels already queued keep the pointers they were launched with)
 void swap_volume_set(tsdf_ctx* c) {
@@ -471,6 +472,36 @@ bool ensure_alt_set(tsdf_ctx* c, hipStream_t lane) {
   hipMemsetAsync(a.stamp, 0, n * sizeof(uint32_t), lane);
   a.parity = 0; a.full = true; a.stampno = 0;
   return true;
+}
+// projection cache: the pool and its tables, on the first integrate() that can use them, and this frame's turn of its slow-item counters.  Capacity = the
+// budget, at most one slot per stored tile; a failed allocation (another context holds the memory) just leaves this context on the LUT path (*proj stays null)
+static int32_t ensure_proj_cache(tsdf_ctx* c, const ProjCache** proj) {
+  if (!c->proj.data) {
+    int dz_max = 1;
+    for (uint32_t i = 0; i < c->cfg.num_streams; ++i) dz_max = std::max(dz_max, c->lut_dz[i]);
+    const size_t slot_bytes = (size_t)c->cfg.num_streams * dz_max * 64 * 3 * sizeof(float);
+    const size_t cap = std::min<size_t>((size_t)c->vol.n_stored_tiles, c->proj_budget / slot_bytes);
+    bool ok = cap > 0;
+    ok = ok && hipMalloc((void**)&c->proj.slot, (size_t)c->vol.n_stored_tiles * sizeof(uint32_t)) == hipSuccess;
+    ok = ok && hipMalloc((void**)&c->proj.items, (size_t)c->tiles.n * sizeof(uint32_t)) == hipSuccess;
+    ok = ok && hipMalloc((void**)&c->d_proj_words, 4 * sizeof(uint32_t)) == hipSuccess;
+    ok = ok && hipMalloc((void**)&c->proj.data, cap * slot_bytes) == hipSuccess;
+    if (!ok) {
+      (void)hipGetLastError();
+      hipFree(c->proj.slot); hipFree(c->proj.items); hipFree(c->d_proj_words); hipFree(c->proj.data);
+      c->proj = ProjCache{}; c->d_proj_words = nullptr; c->proj_failed = true;
+      return TSDF_OK;
+    }
+    HIP_TRY(c, hipMemsetAsync(c->proj.slot, 0xff, (size_t)c->vol.n_stored_tiles * sizeof(uint32_t), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_proj_words, 0, 4 * sizeof(uint32_t), c->stream));
+    c->proj.cap = (uint32_t)cap; c->proj.slot_floats = (uint32_t)(slot_bytes / sizeof(float)); c->proj.alloc = c->d_proj_words; c->proj.dz_max = (uint32_t)dz_max;
+    c->proj_parity = 0;
+  }
+  for (uint32_t i = 0; i < c->cfg.num_streams; ++i) c->proj.inv_rz[i] = c->luts.s[i].inv_res[2];
+  c->proj.n_slow = c->d_proj_words + 1 + c->proj_parity; c->proj.n_slow_next = c->d_proj_words + 1 + (c->proj_parity ^ 1);
+  c->proj_parity ^= 1;
+  *proj = &c->proj;
+  return TSDF_OK;
 }
 hipError_t sync_ctx(tsdf_ctx* c) {
   hipError_t e = hipStreamSynchronize(c->stream);
@@ -581,7 +612,7 @@ void release_volume(tsdf_ctx* c) {
   hipFree(c->d_tile_list[0]); hipFree(c->d_tile_list[1]); hipFree(c->d_tile_counts); hipFree(c->d_linear); hipFree(c->d_tile_bounds); hipFree(c->d_pair_masks); c->d_pair_masks = nullptr; hipFree(c->d_work_recs); c->d_work_recs = nullptr;
   hipFree(c->proj.data); hipFree(c->proj.slot); hipFree(c->proj.items); hipFree(c->d_proj_words); hipFree(c->d_item_stats);
   c->proj = ProjCache{}; c->d_proj_words = nullptr; c->d_item_stats = nullptr; c->proj_failed = false; c->last_integrate_cached = false;
-  c->last_k1 = IntegrateLaunch{-1, 0};
+  c->last_k1 = IntegratePlan{};
   hipFree(c->alt.data); hipFree(c->alt.cls_all); hipFree(c->alt.stamp); hipFree(c->alt.list[0]); hipFree(c->alt.list[1]); hipFree(c->alt.counts);
   c->alt = tsdf_ctx::VolSet{}; c->deep_failed = false;
   c->vol.data = nullptr; c->vol.slot = nullptr; c->tiles.stamp = nullptr; c->d_cls_all = nullptr;
@@ -1340,20 +1371,19 @@ static int32_t process_textures_impl(tsdf_ctx* c, int phase) {
   if (phase != 2) timer_begin_on(c, "1preprocess", lane);
   const size_t ncol = (size_t)c->cfg.num_streams * c->frame.cw * c->frame.ch;
   float4* const ranges = c->slots[c->cur_slot].ranges;
-  if (phase == 1) {
-    launch_preprocess(lane, P, B, c->luts, c->frame, c->br, ranges, nullptr, nullptr, 0, nullptr, 0, 1);
-    launch_preprocess(lane, P, B, c->luts, c->frame, c->br, ranges, nullptr, nullptr, 0, nullptr, 0, 2);
-  } else if (phase == 2) {
-    if (c->pending_rgb) launch_preprocess(lane, P, B, c->luts, c->frame, c->br, ranges, c->pending_rgb, (uchar4*)c->frame.color, ncol, nullptr, 0, 6);
-    for (int k = 3; k <= 5; ++k) launch_preprocess(lane, P, B, c->luts, c->frame, c->br, ranges, nullptr, nullptr, 0, nullptr, 0, k);
-  } else if (c->timers_on && c->timer_filter.find(",k_pre_") != std::string::npos) {   // each pass between its own pair of events, when the timer filter NAMES them (a pair costs the lane ~7 us)
-    static const char* const names[5] = {"k_pre_morph", "k_pre_filter", "k_pre_boundary", "k_pre_normal", "k_pre_quality"};
-    for (int k = 1; k <= 5; ++k) {
-      timer_begin_on(c, names[k - 1], lane);
-      launch_preprocess(lane, P, B, c->luts, c->frame, c->br, ranges, c->pending_rgb, (uchar4*)c->frame.color, ncol, nullptr, 0, k);
-      timer_end_on(c, names[k - 1], lane);
+  uchar4* const rgba = (uchar4*)c->frame.color;
+  auto launch = [&](unsigned passes, const uint8_t* rgb) { launch_preprocess(lane, P, B, c->luts, c->frame, c->br, ranges, passes, rgb, rgba, ncol); };
+  if (phase == 1) launch(kPreMorph | kPreFilter, nullptr);
+  else if (phase == 2) launch(kPreRelayout | kPreBoundary | kPreNormal | kPreQuality, c->pending_rgb);
+  else if (c->timers_on && c->timer_filter.find(",k_pre_") != std::string::npos) {   // each pass between its own pair of events, when the timer filter NAMES them (a pair costs the lane ~7 us)
+    static const struct { unsigned pass; const char* name; } each[5] = {
+        {kPreMorph, "k_pre_morph"}, {kPreFilter, "k_pre_filter"}, {kPreBoundary, "k_pre_boundary"}, {kPreNormal, "k_pre_normal"}, {kPreQuality, "k_pre_quality"}};
+    for (const auto& e : each) {
+      timer_begin_on(c, e.name, lane);
+      launch(e.pass, c->pending_rgb);
+      timer_end_on(c, e.name, lane);
     }
-  } else launch_preprocess(lane, P, B, c->luts, c->frame, c->br, ranges, c->pending_rgb, (uchar4*)c->frame.color, ncol);
+  } else launch(kPreAll, c->pending_rgb);
   HIP_TRY(c, hipGetLastError());
   if (phase != 1) {
     c->pending_rgb = nullptr;
@@ -1544,7 +1574,7 @@ int32_t tsdf_integrate(tsdf_ctx* c) {
   // the draw that follows would first reset the peel tiles its predecessor touched: let the classify launch do it
   PeelClear pc{};
   {
-    const bool whole = (c->vol.own_tz0 == 0 && c->vol.own_tz1 == (c->res[2] + 7) / 8);
+    const bool whole = whole_volume(c);
     if (!deep && !pipelined(c) && c->use_bricks && !c->full_classify && c->skip_space && whole && c->use_tile_history && c->tile_history && !c->last_alt_peels && c->d_peels) {   // (with the lanes on the reset rides on the lane ahead: tsdf_mark_bricks)
       pc.peels = (uint4*)c->d_peels; pc.touched_prev = c->d_touched[(c->touched_idx + 2) % 3];     // the previous draw's tiles
       c->tex_limits_ok = false;                                                                     // (unit 16's image: reset for the coming draw)
@@ -1556,7 +1586,7 @@ int32_t tsdf_integrate(tsdf_ctx* c) {
     pc.zero = c->d_counters[alt_of(c->counters_cur)]; pc.zero_words = (uint32_t)c->counter_words;
     c->spare_clean = true;
   }
-  launch_integrate(lane, c->luts, c->frame, c->vol, c->br, c->tiles, c->use_bricks ? 1 : 0, lds, c->full_classify ? 1 : 0, c->frame_stamp, 1, &pc);
+  if (c->use_bricks) launch_classify_tiles(lane, c->vol, c->br, c->tiles, c->full_classify, c->frame_stamp, pc);
   // dense launches: the static half of the uniform-pair shortcut (k_integrate.hip), built once per calibration
   const float4* bounds = nullptr;
   const bool culled_ranges = c->use_bricks && c->culled_ranges && !c->vol.slot && (size_t)c->vol.n_stored_tiles * c->cfg.num_streams * 32 <= ((size_t)512 << 20);
@@ -1567,47 +1597,22 @@ int32_t tsdf_integrate(tsdf_ctx* c) {
     if (!c->tile_bounds_valid) { launch_tile_bounds(lane, c->luts, c->vol, c->d_tile_bounds); c->tile_bounds_valid = true; }
     bounds = c->d_tile_bounds;
   }
-  // projection cache: the pool and its tables, on the first integrate() that can use them.  Capacity = the budget, at most one slot per
-  // stored tile; a failed allocation (another context holds the memory) just leaves this context on the LUT path
   const ProjCache* proj = nullptr;
-  if (bounds && want_cache) {
-    if (!c->proj.data) {
-      int dz_max = 1;
-      for (uint32_t i = 0; i < c->cfg.num_streams; ++i) dz_max = std::max(dz_max, c->lut_dz[i]);
-      const size_t slot_bytes = (size_t)c->cfg.num_streams * dz_max * 64 * 3 * sizeof(float);
-      const size_t cap = std::min<size_t>((size_t)c->vol.n_stored_tiles, c->proj_budget / slot_bytes);
-      bool ok = cap > 0;
-      ok = ok && hipMalloc((void**)&c->proj.slot, (size_t)c->vol.n_stored_tiles * sizeof(uint32_t)) == hipSuccess;
-      ok = ok && hipMalloc((void**)&c->proj.items, (size_t)c->tiles.n * sizeof(uint32_t)) == hipSuccess;
-      ok = ok && hipMalloc((void**)&c->d_proj_words, 4 * sizeof(uint32_t)) == hipSuccess;
-      ok = ok && hipMalloc((void**)&c->proj.data, cap * slot_bytes) == hipSuccess;
-      if (!ok) {
-        (void)hipGetLastError();
-        hipFree(c->proj.slot); hipFree(c->proj.items); hipFree(c->d_proj_words); hipFree(c->proj.data);
-        c->proj = ProjCache{}; c->d_proj_words = nullptr; c->proj_failed = true;
-      } else {
-        HIP_TRY(c, hipMemsetAsync(c->proj.slot, 0xff, (size_t)c->vol.n_stored_tiles * sizeof(uint32_t), c->stream));
-        HIP_TRY(c, hipMemsetAsync(c->d_proj_words, 0, 4 * sizeof(uint32_t), c->stream));
-        c->proj.cap = (uint32_t)cap; c->proj.slot_floats = (uint32_t)(slot_bytes / sizeof(float)); c->proj.alloc = c->d_proj_words; c->proj.dz_max = (uint32_t)dz_max;
-        c->proj_parity = 0;
-      }
-    }
-    if (c->proj.data) {
-      for (uint32_t i = 0; i < c->cfg.num_streams; ++i) c->proj.inv_rz[i] = c->luts.s[i].inv_res[2];
-      c->proj.n_slow = c->d_proj_words + 1 + c->proj_parity; c->proj.n_slow_next = c->d_proj_words + 1 + (c->proj_parity ^ 1);
-      c->proj_parity ^= 1;
-      proj = &c->proj;
-    }
-  }
+  if (bounds && want_cache) { if ((rc = ensure_proj_cache(c, &proj))) return rc; }
   c->last_integrate_cached = proj != nullptr;
-  if (bounds) {                                                        // this frame's (tile, stream) pair classes (+ which work items are cached)
+  // which kernels, with what grids: decided here, once (launch_plan.hpp); the two A/B hooks are read once per process
+  static const int forced_grid = [] { const char* e = getenv("RR_K1_GRID"); return e ? atoi(e) : 0; }();
+  static const int dense_cap = [] { const char* e = getenv("RR_K1_DENSE_GRID"); return e ? atoi(e) : 16384; }();
+  const IntegratePlan plan = plan_integrate(c->use_bricks, lds, c->frame.ranges != nullptr, bounds != nullptr, c->use_recs, proj != nullptr, c->vol.slot != nullptr,
+                                            c->tiles.uniform != 0, c->tiles.n, forced_grid, dense_cap);
+  c->last_k1 = plan;
+  if (plan.pair_pass) {                                                // this frame's (tile, stream) pair classes (+ which work items are cached)
     timer_begin_on(c, "k_pair_masks", lane);
-    launch_integrate(lane, c->luts, c->frame, c->vol, c->br, c->tiles, c->use_bricks ? 1 : 0, lds, 0, c->frame_stamp, 3, nullptr, bounds, c->d_pair_masks, proj, c->use_recs ? c->d_work_recs : nullptr);
+    launch_pair_masks(lane, c->luts, c->frame, c->vol, c->br, c->tiles, plan, bounds, c->d_pair_masks, proj, c->d_work_recs);
     timer_end_on(c, "k_pair_masks", lane);
   }
   timer_begin_on(c, "k_integrate_tiles", lane);                                // the kernel(s) alone (bench.py's roofline)
-  launch_integrate(lane, c->luts, c->frame, c->vol, c->br, c->tiles, c->use_bricks ? 1 : 0, lds, 0, c->frame_stamp, 4, nullptr, bounds, bounds ? c->d_pair_masks : nullptr, proj, bounds && c->use_recs ? c->d_work_recs : nullptr, &c->last_k1);
-  c->last_k1_culled = c->use_bricks;
+  launch_integrate_tiles(lane, c->luts, c->frame, c->vol, c->br, c->tiles, plan, c->d_pair_masks, proj, c->d_work_recs);
   timer_end_on(c, "k_integrate_tiles", lane);
   if (c->use_bricks) { c->tile_parity ^= 1; c->full_classify = false; }
   else c->full_classify = true;                                       // a dense pass wrote every tile: the next culled frame must look at all of them
@@ -1625,7 +1630,7 @@ static int32_t raymarch_impl(tsdf_ctx* c, const float* mv, const float* pr, bool
   if (!make_view_params(c, mv, pr, &P)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "singular modelview / projection matrix");
   HIP_TRY(c, join_pre(c));
   if (outer_timer) timer_begin(c, "3recon");
-  const bool partial = !(c->vol.own_tz0 == 0 && c->vol.own_tz1 == (c->res[2] + 7) / 8);
+  const bool partial = !whole_volume(c);
   const bool shifted = P.vp_org[0] != 0 || P.vp_org[1] != 0 || P.vp_off[0] != 0.0f || P.vp_off[1] != 0.0f;
   if (shifted && partial) FAIL(c, TSDF_ERR_STATE, "a viewport origin / offset is not available on a slab context (the composite indexes pixels)");
   if (shifted) HIP_TRY(c, hipMemsetAsync(c->d_nsamples, 0, (size_t)c->vw * c->vh * sizeof(float), c->stream));   // clearImage of tex_num_samples, :207-208: the stores land at origin + pixel
@@ -1687,13 +1692,14 @@ static int32_t raymarch_impl(tsdf_ctx* c, const float* mv, const float* pr, bool
   if (!c->fill_holes) c->fb_consistent = false;                          // the march (or the masked merge below) writes the framebuffer itself
   if (c->fill_holes || masked_direct(c)) c->tex_atlas_ok = false;        // level 0 of c->atlas: this march's until its hole filling completes the pyramid
   HIP_TRY(c, join_integ(c));                                             // the volume: from here on (the depth limits above needed the bricks only)
+  const MarchPlan plan = plan_march(partial, P.skip != 0, c->vol.slot != nullptr, c->d_long != nullptr, c->march_cap ? c->march_cap : 0xffffffffu, c->march_box);
   timer_begin(c, "draw");
   timer_begin(c, "k_march");
-  launch_raymarch(c->stream, P, c->luts, c->frame, c->vol, RT, partial ? 1 : 0, c->d_hits, c->d_hit_counters, c->hit_parity, 2, c->d_long, c->march_cap ? c->march_cap : 0xffffffffu, c->march_box);
+  launch_march(c->stream, P, c->vol, RT, plan, c->d_hits, c->d_hit_counters, c->hit_parity, c->d_long);
   timer_end(c, "k_march");
-  launch_raymarch(c->stream, P, c->luts, c->frame, c->vol, RT, partial ? 1 : 0, c->d_hits, c->d_hit_counters, c->hit_parity, 3, c->d_long, c->march_cap ? c->march_cap : 0xffffffffu, c->march_box);
+  launch_shade(c->stream, P, c->luts, c->frame, c->vol, RT, plan, c->d_hits, c->d_hit_counters, c->hit_parity, c->d_long);
   c->hit_parity ^= 1;
-  c->last_two_pass = !partial && P.skip && c->d_long && c->march_cap != 0;          // launch_raymarch's own condition
+  c->last_two_pass = plan.two_pass;
   c->own_miss_counts = true;
   if (masked_direct(c)) launch_resolve_masked(c->stream, c->atlas, c->vw, c->vh, c->d_fb_c, c->d_fb_d, (int)c->color_mask_mode, c->keep_color ? 1 : 0);
   timer_end(c, "draw");
@@ -1993,7 +1999,7 @@ int32_t tsdf_draw_calibvis(tsdf_ctx* c, const float* mv, const float* pr) {
   ViewParams P;
   if (int32_t rc = overlay_checks(c, mv, pr, &P)) return rc;
   if (!c->have_calib[0] || !c->luts.s[0].inv) FAIL(c, TSDF_ERR_STATE, "stream 0 needs cv_xyz_inv (tsdf_set_calibration): its resolution is the point grid");
-  if (!(c->vol.own_tz0 == 0 && c->vol.own_tz1 == (c->res[2] + 7) / 8)) FAIL(c, TSDF_ERR_STATE, "the TSDF overlay needs the whole volume (a Z-slab context holds part of it)");
+  if (!whole_volume(c)) FAIL(c, TSDF_ERR_STATE, "the TSDF overlay needs the whole volume (a Z-slab context holds part of it)");
   HIP_TRY(c, hipSetDevice(c->device));
   CalibVisParams Q{};
   for (int a = 0; a < 3; ++a) {                                          // vol_to_world = translate(bbox_min) * scale(extent), fp32 (recon_calibs.cpp:38-45)
@@ -2229,7 +2235,7 @@ int32_t tsdf_calibvis_stats(tsdf_ctx* c, uint64_t out[2]) {
 int32_t tsdf_set_tsdf_limit(tsdf_ctx* c, float limit) {
   CHECK_CTX(c);
   if (!(limit > 0.0f)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "limit must be > 0");
-  const bool whole = (c->vol.own_tz0 == 0 && c->vol.own_tz1 == (c->res[2] + 7) / 8);
+  const bool whole = whole_volume(c);
   if (!whole && halo_layers_for(limit, c->res[2]) > c->halo_layers) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "limit needs a wider slab halo than this context allocated");
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, sync_ctx(c));
@@ -2385,12 +2391,12 @@ int32_t tsdf_integrate_form(tsdf_ctx* c, uint32_t out[4]) {
   if (!out) return TSDF_ERR_INVALID_ARGUMENT;
   if (c->last_k1.form < 0) FAIL(c, TSDF_ERR_STATE, "no integrate() since the volume was set up");
   uint32_t n = (uint32_t)c->tiles.n;
-  if (c->last_k1_culled) {
+  if (c->last_k1.culled) {
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, sync_ctx(c));
     HIP_TRY(c, hipMemcpy(&n, c->d_tile_counts + (c->tile_parity ^ 1), sizeof(uint32_t), hipMemcpyDeviceToHost));   // integrate() flipped the parity after its launches
   }
-  out[0] = (uint32_t)c->last_k1.form; out[1] = c->last_k1.grid; out[2] = n; out[3] = c->last_k1_culled ? 1u : 0u;
+  out[0] = (uint32_t)c->last_k1.form; out[1] = c->last_k1.grid; out[2] = n; out[3] = c->last_k1.culled ? 1u : 0u;
   return TSDF_OK;
 }
 int32_t tsdf_download_bricks(tsdf_ctx* c, uint32_t* counters, uint8_t* flags) {

@@ -63,7 +63,7 @@ struct tsdf_ctx {
   // the volume, invalidated by tsdf_set_calibration
   ProjCache proj{}; uint32_t* d_proj_words = nullptr; int proj_parity = 0; size_t proj_budget = 0; bool proj_failed = false; uint32_t* d_item_stats = nullptr;
   bool last_integrate_cached = false;
-  IntegrateLaunch last_k1{-1, 0}; bool last_k1_culled = false;   // tsdf_integrate_form: what the last integrate() launched (form -1: none since the volume was set up)
+  IntegratePlan last_k1{};       // tsdf_integrate_form: the plan the last integrate() launched by (form -1: none since the volume was set up)
   FrameImages frame{};           // the CURRENT frame slot's images (what mark / integrate / draw read)
   // Two frame slots (the reference's double PBO + texture arrays, NetKinectArray.cpp:225-236): while the path computes on slot
   // `cur_slot`, tsdf_upload_frame_async fills the other one on a copy stream; tsdf_select_frame_slot makes it current.

@@ -1139,74 +1139,57 @@ void launch_item_stats(hipStream_t st, const StreamTable& T, const TileState& S,
   else hipLaunchKernelGGL(k_item_stats<false>, dim3(64), dim3(256), 0, st, T, S, pair_masks, PC, out);
 }
 
-void launch_integrate(hipStream_t st, const StreamTable& T, const FrameImages& F, const Volume& V, const Bricks& B, const TileState& S, int use_bricks, int lds_ok,
-                      int full_classify, uint32_t frame_stamp, int phase, const PeelClear* pc, const float4* tile_bounds, uint32_t* pair_masks, const ProjCache* proj,
-                      uint4* work_recs, IntegrateLaunch* info) {
-  // phase 1: tile classification + stale-tile clear; 2: pair-mask pass + integrate kernel(s); 3: the pair-mask pass alone; 4: the integrate
-  // kernel(s) alone; 0: everything (the split lets the caller time the kernels separately)
+// tile classification + stale-tile clear of a culled volume: every tile, or the incremental lists (the coming draw's peel reset and the spare counters' clear ride along)
+void launch_classify_tiles(hipStream_t st, const Volume& V, const Bricks& B, const TileState& S, bool full_classify, uint32_t frame_stamp, const PeelClear& pc) {
+  if (full_classify) hipLaunchKernelGGL(k_classify_clear_tiles, dim3((S.n + 255) / 256), dim3(256), 0, st, V, B, S);
+  else {
+    const int extra = pc.peels ? (pc.n_tiles + 3) / 4 : 0;
+    hipLaunchKernelGGL(k_classify_lists, dim3(kScatterBlocks + kStaleBlocks + kZeroBlocks + extra), dim3(256), 0, st, V, B, S, frame_stamp, pc);
+  }
+}
+void launch_pair_masks(hipStream_t st, const StreamTable& T, const FrameImages& F, const Volume& V, const Bricks& B, const TileState& S, const IntegratePlan& plan,
+                       const float4* tile_bounds, uint32_t* pair_masks, const ProjCache* proj, uint4* work_recs) {
   const ProjCache none_pc{};
-  const bool ranges = F.ranges && tile_bounds && pair_masks && lds_ok >= 2;
-  const bool cached = ranges && proj && proj->data;
-  const bool rec = ranges && !cached && !V.slot && work_recs;           // k_integrate_tiles_rec
-  const ProjCache& PC = cached ? *proj : none_pc;
-  const int pvc = use_bricks ? (S.uniform ? 0 : 1) : 0;
-  if (use_bricks && phase < 2) {
-    if (full_classify) hipLaunchKernelGGL(k_classify_clear_tiles, dim3((S.n + 255) / 256), dim3(256), 0, st, V, B, S);
-    else {
-      PeelClear none{};
-      const PeelClear& P = pc ? *pc : none;
-      const int extra = P.peels ? (P.n_tiles + 3) / 4 : 0;
-      hipLaunchKernelGGL(k_classify_lists, dim3(kScatterBlocks + kStaleBlocks + kZeroBlocks + extra), dim3(256), 0, st, V, B, S, frame_stamp, P);
-    }
+  const ProjCache& PC = plan.cached ? *proj : none_pc;
+  const int pvc = plan.per_voxel_check ? 1 : 0;
+  uint4* const recs = plan.rec ? work_recs : nullptr;
+  unsigned long long* const vmasks = (plan.rec && pvc) ? (unsigned long long*)(work_recs + S.n) : nullptr;   // (the record buffer holds 16 + 64 bytes per tile: abi.cpp)
+  if (plan.culled) hipLaunchKernelGGL(k_pair_masks<true>, dim3(2048), dim3(256), 0, st, T, F, V, B, S, pvc, tile_bounds, pair_masks, recs, PC, vmasks);
+  else hipLaunchKernelGGL(k_pair_masks<false>, dim3((S.n + 3) / 4 < 4096 ? (S.n + 3) / 4 : 4096), dim3(256), 0, st, T, F, V, B, S, pvc, tile_bounds, pair_masks, recs, PC, vmasks);
+}
+// the plan's form over the work list (kList: culled) or over every tile
+template <bool kList>
+static void launch_form(hipStream_t st, const StreamTable& T, const FrameImages& F, const Volume& V, const Bricks& B, const TileState& S, const IntegratePlan& plan,
+                        const uint32_t* pair_masks, const ProjCache& PC, const uint4* work_recs) {
+  const int pvc = plan.per_voxel_check ? 1 : 0;
+  const uint32_t* const masks = plan.ranges ? pair_masks : nullptr;
+  const dim3 grid(plan.grid), wg(256);
+  switch (plan.form) {
+    case kFormCached:
+      hipLaunchKernelGGL((k_integrate_cached<kList, RR_K1C_CHUNK>), dim3(kList ? (unsigned)RR_K1C_GRID : (unsigned)(((S.n + 7) >> 3) << 6)), dim3(64), 0, st, T.n, F, V, B, S, pvc, S.count, S.list,
+                         masks, PC.items, PC);
+      hipLaunchKernelGGL((k_integrate_tiles_lds<kList, true, true, true>), grid, wg, 0, st, T, F, V, B, S, pvc, masks, PC);
+      break;
+    case kFormRecord:
+      if constexpr (kList) {                                               // (per_voxel_check: culled launches only)
+        if (pvc) { hipLaunchKernelGGL((k_integrate_tiles_rec<true, true>), grid, wg, 0, st, T, F, V, B, S, work_recs, (const unsigned long long*)(work_recs + S.n)); break; }
+      }
+      hipLaunchKernelGGL((k_integrate_tiles_rec<kList, false>), grid, wg, 0, st, T, F, V, B, S, work_recs, (const unsigned long long*)nullptr);
+      break;
+    case kFormLdsSeparable:
+      if (plan.ranges) hipLaunchKernelGGL((k_integrate_tiles_lds<kList, true, true>), grid, wg, 0, st, T, F, V, B, S, pvc, masks, PC);
+      else hipLaunchKernelGGL((k_integrate_tiles_lds<kList, true>), grid, wg, 0, st, T, F, V, B, S, pvc, masks, PC);
+      break;
+    case kFormLdsDirect: hipLaunchKernelGGL((k_integrate_tiles_lds<kList, false>), grid, wg, 0, st, T, F, V, B, S, pvc, masks, PC); break;
+    default: hipLaunchKernelGGL(k_integrate_tiles<kList>, grid, wg, 0, st, T, F, V, B, S, pvc); break;
   }
-  if (phase == 1) return;
-  if (ranges && phase != 4) {
-    unsigned long long* const vmasks = (rec && pvc) ? (unsigned long long*)(work_recs + S.n) : nullptr;   // (the record buffer holds 16 + 64 bytes per tile: abi.cpp)
-    if (use_bricks) hipLaunchKernelGGL(k_pair_masks<true>, dim3(2048), dim3(256), 0, st, T, F, V, B, S, pvc, tile_bounds, pair_masks, rec ? work_recs : nullptr, PC, vmasks);
-    else hipLaunchKernelGGL(k_pair_masks<false>, dim3((S.n + 3) / 4 < 4096 ? (S.n + 3) / 4 : 4096), dim3(256), 0, st, T, F, V, B, S, 0, tile_bounds, pair_masks, rec ? work_recs : nullptr, PC, (unsigned long long*)nullptr);
-  }
-  if (phase == 3) return;
-  if (use_bricks) {
-    // Workgroups of the culled launch (they stride over the work list).  2048 = the 8 x 256 a MI355X holds at once: beside the other lanes' kernels (stage overlap)
-    // a c2 frame takes 112 - 113 us with it against 119 with 4096 (the launch alone 43.9 against 42.9 us: queued workgroups of this kernel no longer take the slots
-    // a co-runner's workgroups wait for), c3 the same either way; the 25 000-tile launch of a 1024^3 volume wants the larger grid (c4: 2 834 against 2 551 frames/s).
-    static const int forced = [] { const char* e = getenv("RR_K1_GRID"); return e ? atoi(e) : 0; }();                  // A/B hook
-    const int cap = forced > 0 ? forced : (S.n <= 262144 ? 2048 : 4096);
-    const dim3 grid(S.n < cap ? S.n : cap);
-    int form;
-    if (cached) {
-      form = kFormCached;
-      hipLaunchKernelGGL((k_integrate_cached<true, RR_K1C_CHUNK>), dim3(RR_K1C_GRID), dim3(64), 0, st, T.n, F, V, B, S, pvc, S.count, S.list, pair_masks, PC.items, PC);
-      hipLaunchKernelGGL((k_integrate_tiles_lds<true, true, true, true>), grid, dim3(256), 0, st, T, F, V, B, S, pvc, pair_masks, PC);
-    }
-    else if (rec && pvc) { form = kFormRecord; hipLaunchKernelGGL((k_integrate_tiles_rec<true, true>), grid, dim3(256), 0, st, T, F, V, B, S, work_recs, (const unsigned long long*)(work_recs + S.n)); }
-    else if (rec) { form = kFormRecord; hipLaunchKernelGGL((k_integrate_tiles_rec<true, false>), grid, dim3(256), 0, st, T, F, V, B, S, work_recs, (const unsigned long long*)nullptr); }
-    else if (ranges) { form = kFormLdsSeparable; hipLaunchKernelGGL((k_integrate_tiles_lds<true, true, true>), grid, dim3(256), 0, st, T, F, V, B, S, pvc, pair_masks, PC); }
-    else if (lds_ok >= 2) { form = kFormLdsSeparable; hipLaunchKernelGGL((k_integrate_tiles_lds<true, true>), grid, dim3(256), 0, st, T, F, V, B, S, pvc, nullptr, PC); }
-    else if (lds_ok) { form = kFormLdsDirect; hipLaunchKernelGGL((k_integrate_tiles_lds<true, false>), grid, dim3(256), 0, st, T, F, V, B, S, pvc, nullptr, PC); }
-    else { form = kFormGeneric; hipLaunchKernelGGL(k_integrate_tiles<true>, grid, dim3(256), 0, st, T, F, V, B, S, pvc); }
-    if (info) *info = IntegrateLaunch{form, grid.x};
-  } else {
-    int form;
-    dim3 grid(S.n);
-    if (cached) {
-      form = kFormCached;
-      hipLaunchKernelGGL((k_integrate_cached<false, RR_K1C_CHUNK>), dim3((unsigned)(((S.n + 7) >> 3) << 6)), dim3(64), 0, st, T.n, F, V, B, S, 0, S.count, S.list, pair_masks, PC.items, PC);
-      hipLaunchKernelGGL((k_integrate_tiles_lds<false, true, true, true>), grid, dim3(256), 0, st, T, F, V, B, S, 0, pair_masks, PC);
-    }
-    else if (ranges) {
-      // at most 16 384 workgroups striding over the tiles instead of one per tile: the launch alone is as fast (119 us at c1), the frame beside the other
-      // lanes 2.5 % faster (4 349 against 4 242 frames/s; 8 192: 4 380 but the launch alone 125 us, 2 048: 3 796); RR_K1_DENSE_GRID: A/B hook
-      static const int dcap = [] { const char* e = getenv("RR_K1_DENSE_GRID"); return e ? atoi(e) : 16384; }();
-      grid = dim3(dcap > 0 && dcap < S.n ? dcap : S.n);
-      if (rec) { form = kFormRecord; hipLaunchKernelGGL((k_integrate_tiles_rec<false, false>), grid, dim3(256), 0, st, T, F, V, B, S, work_recs, (const unsigned long long*)nullptr); }
-      else { form = kFormLdsSeparable; hipLaunchKernelGGL((k_integrate_tiles_lds<false, true, true>), grid, dim3(256), 0, st, T, F, V, B, S, 0, pair_masks, PC); }
-    }
-    else if (lds_ok >= 2) { form = kFormLdsSeparable; hipLaunchKernelGGL((k_integrate_tiles_lds<false, true>), grid, dim3(256), 0, st, T, F, V, B, S, 0, nullptr, PC); }
-    else if (lds_ok) { form = kFormLdsDirect; hipLaunchKernelGGL((k_integrate_tiles_lds<false, false>), grid, dim3(256), 0, st, T, F, V, B, S, 0, nullptr, PC); }
-    else { form = kFormGeneric; hipLaunchKernelGGL(k_integrate_tiles<false>, grid, dim3(256), 0, st, T, F, V, B, S, 0); }
-    if (info) *info = IntegrateLaunch{form, grid.x};
-  }
+}
+void launch_integrate_tiles(hipStream_t st, const StreamTable& T, const FrameImages& F, const Volume& V, const Bricks& B, const TileState& S, const IntegratePlan& plan,
+                            const uint32_t* pair_masks, const ProjCache* proj, const uint4* work_recs) {
+  const ProjCache none_pc{};
+  const ProjCache& PC = plan.cached ? *proj : none_pc;
+  if (plan.culled) launch_form<true>(st, T, F, V, B, S, plan, pair_masks, PC, work_recs);
+  else launch_form<false>(st, T, F, V, B, S, plan, pair_masks, PC, work_recs);
 }
 int integrate_box_cap() { return kBoxCap; }
 int integrate_row_cap() { return kRowCap; }

@@ -394,18 +394,18 @@ __global__ __launch_bounds__(256) void k_pre_quality(PreParams P, PreBuffers B, 
 }
 
 void launch_preprocess(hipStream_t st, const PreParams& P, const PreBuffers& B, const StreamTable& T, const FrameImages& F, const Bricks& BR, float4* ranges,
-                       const uint8_t* rgb, uchar4* rgba, size_t n_color_px, uint32_t* zero, uint32_t zero_words, int only) {
+                       unsigned passes, const uint8_t* rgb, uchar4* rgba, size_t n_color_px) {
   const dim3 rows((P.W + 63) / 64, (P.H + 3) / 4, P.N), tiles((P.W + 15) / 16, (P.H + 15) / 16, P.N);
-  const PreExtra E{rgb, rgba, (uint32_t)n_color_px, (uint4*)zero, zero_words >> 2};
-  if (!only || only == 1) hipLaunchKernelGGL(k_pre_morph, dim3(rows.x, rows.y, P.N + ((rgb || zero) ? 2 : 0)), dim3(256), 0, st, P, B, E);
-  if (only == 6 && (rgb || zero)) {                                      // the two extra layers alone (tsdf_frame_raw_dev: behind the lane's gate, the morph pass in front of it)
+  const PreExtra E{rgb, rgba, (uint32_t)n_color_px, nullptr, 0};          // (no word buffer to clear)
+  if (passes & kPreMorph) hipLaunchKernelGGL(k_pre_morph, dim3(rows.x, rows.y, P.N + (rgb ? 2 : 0)), dim3(256), 0, st, P, B, E);
+  if ((passes & kPreRelayout) && rgb) {                                  // the two extra layers alone (tsdf_frame_raw_dev: behind the lane's gate, the morph pass in front of it)
     PreParams P0 = P; P0.N = 0;
     hipLaunchKernelGGL(k_pre_morph, dim3(rows.x, rows.y, 2), dim3(256), 0, st, P0, B, E);
   }
-  if (!only || only == 2) hipLaunchKernelGGL(k_pre_filter, tiles, dim3(256), 0, st, P, B, T);
-  if (!only || only == 3) hipLaunchKernelGGL(k_pre_boundary, dim3(tiles.x * tiles.y * tiles.z + (B.blk_flag ? B.cand_cap : 0u)), dim3(256), 0, st, P, B, T, F, (int)tiles.x, (int)tiles.y);
-  if (!only || only == 4) hipLaunchKernelGGL(k_pre_normal, tiles, dim3(256), 0, st, P, B, T, BR);
-  if (!only || only == 5) hipLaunchKernelGGL(k_pre_quality, tiles, dim3(256), 0, st, P, B, T, ranges, (P.W + 7) / 8, (P.H + 7) / 8);
+  if (passes & kPreFilter) hipLaunchKernelGGL(k_pre_filter, tiles, dim3(256), 0, st, P, B, T);
+  if (passes & kPreBoundary) hipLaunchKernelGGL(k_pre_boundary, dim3(tiles.x * tiles.y * tiles.z + (B.blk_flag ? B.cand_cap : 0u)), dim3(256), 0, st, P, B, T, F, (int)tiles.x, (int)tiles.y);
+  if (passes & kPreNormal) hipLaunchKernelGGL(k_pre_normal, tiles, dim3(256), 0, st, P, B, T, BR);
+  if (passes & kPreQuality) hipLaunchKernelGGL(k_pre_quality, tiles, dim3(256), 0, st, P, B, T, ranges, (P.W + 7) / 8, (P.H + 7) / 8);
 }
 
 // the Lab image of the filter pass (PreBuffers::lab), for callers that read it back: the passes themselves no longer write it (lab_of_pixel)

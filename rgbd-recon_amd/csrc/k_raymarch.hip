@@ -1008,34 +1008,34 @@ __global__ __launch_bounds__(256, RR_SHADE_BOUNDS) void k_shade_and_long(ViewPar
   if (blockIdx.x < kLongBlocks) march_long<kSparse>(P, V, R, longs, long_count, kLongBlocks, &T, &F);
   else shade_list<kSparse>(P, T, F, V, R, hits, hit_count, next_count, kLongBlocks);
 }
-void launch_raymarch(hipStream_t st, const ViewParams& P, const StreamTable& T, const FrameImages& F, const Volume& V, const RayTarget& R, int partial,
-                     void* hit_list, uint32_t* hit_counters, int parity, int phase, void* long_list, uint32_t cap, int box_march) {
-  // phase 2: k_march alone; phase 3: k_shade alone; 0: everything (the split lets the caller time the march kernel alone)
-  dim3 grid((P.w + 15) / 16, (P.h + 15) / 16);
-  // counters: [hit parity 0, hit parity 1, long parity 0, long parity 1]
-  const bool two_pass = !partial && P.skip && long_list && cap != 0xffffffffu;
-  const bool sparse = V.slot != nullptr;
-  if (phase != 3) {
-    const uint32_t cap1 = two_pass ? cap : 0xffffffffu;
-    LongRay* const ll = partial ? nullptr : (LongRay*)long_list;
-#define RR_LAUNCH_MARCH(PART, SP, B) hipLaunchKernelGGL((k_march<PART, SP, B>), grid, dim3(256), 0, st, P, V, R, (Hit*)hit_list, hit_counters + parity, ll, hit_counters + 2 + parity, cap1)
-    if (partial) { if (sparse) RR_LAUNCH_MARCH(true, true, kBatchDense); else RR_LAUNCH_MARCH(true, false, kBatchDense); }
-    else if (two_pass) { if (sparse) RR_LAUNCH_MARCH(false, true, kBatchSkip); else RR_LAUNCH_MARCH(false, false, kBatchSkip); }
-    else if (!sparse && !P.skip && box_march == 2) hipLaunchKernelGGL(k_march_box<true>, dim3(grid.x, (P.h + 7) / 8), dim3(128), 0, st, P, V, R, (Hit*)hit_list, hit_counters + parity);
-    else if (!sparse && !P.skip && box_march) hipLaunchKernelGGL(k_march_box<false>, grid, dim3(256), 0, st, P, V, R, (Hit*)hit_list, hit_counters + parity);
-    else { if (sparse) RR_LAUNCH_MARCH(false, true, kBatchDense); else RR_LAUNCH_MARCH(false, false, kBatchDense); }
+// counters: [hit parity 0, hit parity 1, long parity 0, long parity 1]
+void launch_march(hipStream_t st, const ViewParams& P, const Volume& V, const RayTarget& R, const MarchPlan& plan, void* hit_list, uint32_t* hit_counters, int parity,
+                  void* long_list) {
+  const dim3 grid((P.w + 15) / 16, (P.h + 15) / 16);
+  LongRay* const ll = plan.kernel == kMarchPartial ? nullptr : (LongRay*)long_list;
+#define RR_LAUNCH_MARCH(PART, SP, B) hipLaunchKernelGGL((k_march<PART, SP, B>), grid, dim3(256), 0, st, P, V, R, (Hit*)hit_list, hit_counters + parity, ll, hit_counters + 2 + parity, plan.cap)
+  switch (plan.kernel) {
+    case kMarchPartial: if (plan.sparse) RR_LAUNCH_MARCH(true, true, kBatchDense); else RR_LAUNCH_MARCH(true, false, kBatchDense); break;
+    case kMarchTwoPass: if (plan.sparse) RR_LAUNCH_MARCH(false, true, kBatchSkip); else RR_LAUNCH_MARCH(false, false, kBatchSkip); break;
+    case kMarchBoxPair: hipLaunchKernelGGL(k_march_box<true>, dim3(grid.x, (P.h + 7) / 8), dim3(128), 0, st, P, V, R, (Hit*)hit_list, hit_counters + parity); break;
+    case kMarchBox: hipLaunchKernelGGL(k_march_box<false>, grid, dim3(256), 0, st, P, V, R, (Hit*)hit_list, hit_counters + parity); break;
+    default: if (plan.sparse) RR_LAUNCH_MARCH(false, true, kBatchDense); else RR_LAUNCH_MARCH(false, false, kBatchDense); break;
+  }
 #undef RR_LAUNCH_MARCH
+}
+void launch_shade(hipStream_t st, const ViewParams& P, const StreamTable& T, const FrameImages& F, const Volume& V, const RayTarget& R, const MarchPlan& plan,
+                  const void* hit_list, uint32_t* hit_counters, int parity, const void* long_list) {
+  const Hit* const hits = (const Hit*)hit_list;
+  const uint32_t* const n_hits = hit_counters + parity;
+  uint32_t* const next = hit_counters + (parity ^ 1);
+  if (plan.two_pass) {
+    const LongRay* const longs = (const LongRay*)long_list;
+    const uint32_t* const n_long = hit_counters + 2 + parity;
+    if (plan.sparse) hipLaunchKernelGGL(k_shade_and_long<true>, dim3(kLongBlocks + kShadeBlocks), dim3(256), 0, st, P, T, F, V, R, hits, n_hits, next, longs, n_long);
+    else hipLaunchKernelGGL(k_shade_and_long<false>, dim3(kLongBlocks + kShadeBlocks), dim3(256), 0, st, P, T, F, V, R, hits, n_hits, next, longs, n_long);
   }
-  if (phase == 2) return;
-  if (two_pass) {
-    if (sparse) hipLaunchKernelGGL(k_shade_and_long<true>, dim3(kLongBlocks + kShadeBlocks), dim3(256), 0, st, P, T, F, V, R, (const Hit*)hit_list, hit_counters + parity, hit_counters + (parity ^ 1),
-                                   (const LongRay*)long_list, hit_counters + 2 + parity);
-    else hipLaunchKernelGGL(k_shade_and_long<false>, dim3(kLongBlocks + kShadeBlocks), dim3(256), 0, st, P, T, F, V, R, (const Hit*)hit_list, hit_counters + parity, hit_counters + (parity ^ 1),
-                            (const LongRay*)long_list, hit_counters + 2 + parity);
-    return;
-  }
-  if (sparse) hipLaunchKernelGGL(k_shade<true>, dim3(1024), dim3(256), 0, st, P, T, F, V, R, (const Hit*)hit_list, hit_counters + parity, hit_counters + (parity ^ 1));
-  else hipLaunchKernelGGL(k_shade<false>, dim3(1024), dim3(256), 0, st, P, T, F, V, R, (const Hit*)hit_list, hit_counters + parity, hit_counters + (parity ^ 1));
+  else if (plan.sparse) hipLaunchKernelGGL(k_shade<true>, dim3(1024), dim3(256), 0, st, P, T, F, V, R, hits, n_hits, next);
+  else hipLaunchKernelGGL(k_shade<false>, dim3(1024), dim3(256), 0, st, P, T, F, V, R, hits, n_hits, next);
 }
 
 // ------------------------------------------------------------------------------------------- multi-GPU image exchange

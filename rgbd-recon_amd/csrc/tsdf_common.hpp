@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/rgbd_recon_hip.h"
+#include "launch_plan.hpp"
 
 namespace rr {
 
@@ -271,11 +272,12 @@ struct WireLayout {
   int cfmt, dfmt;         // TSDF_COLOR_* / TSDF_DEPTH_*
 };
 void launch_wire_unpack(hipStream_t st, const WireLayout& L, uchar4* rgba, float* raw);
-// ranges: the frame slot's 8x8-pixel range cells (written by the last pass), or null; rgb -> rgba (n_color_px pixels) and zero (zero_words words, a multiple of
-// 4): the frame's colour re-layout and the brick counters' clear riding along in the first launch, or null
+// the passes of processTextures() as a set of bits; kPreRelayout: the colour re-layout layers of the morph kernel alone (no depth layer)
+enum : unsigned { kPreMorph = 1, kPreFilter = 2, kPreBoundary = 4, kPreNormal = 8, kPreQuality = 16, kPreRelayout = 32, kPreAll = 31 };
+// launches the passes of `passes` in the order above.  ranges: the frame slot's 8x8-pixel range cells (written by the last pass), or null;
+// rgb -> rgba (n_color_px pixels): the frame's colour re-layout, riding along in the morph launch (or launched alone: kPreRelayout), or null
 void launch_preprocess(hipStream_t st, const PreParams& P, const PreBuffers& B, const StreamTable& T, const FrameImages& F, const Bricks& BR, float4* ranges,
-                       const uint8_t* rgb = nullptr, uchar4* rgba = nullptr, size_t n_color_px = 0, uint32_t* zero = nullptr, uint32_t zero_words = 0,
-                       int only = 0);   // only: 0 = the five passes, 1 .. 5 = that pass alone (morph, filter, boundary, normal, quality: per-kernel timers)
+                       unsigned passes, const uint8_t* rgb = nullptr, uchar4* rgba = nullptr, size_t n_color_px = 0);
 void launch_pre_lab(hipStream_t st, const PreParams& P, const PreBuffers& B, const StreamTable& T, const FrameImages& F);   // PreBuffers::lab, on request
 
 // launchers (one per kernel family, defined in the .hip files)
@@ -294,17 +296,15 @@ void launch_update_occupied(hipStream_t st, const Bricks& B, uint32_t min_voxels
 // PeelClear: the peel-tile reset of the coming draw (k_raymarch.hip's k_clear_peel_tiles) rides along in the k_classify_lists launch
 // ... and so does the zeroing of the spare brick-counter buffer (`zero`, in 16-byte units of zero_words / 4)
 struct PeelClear { uint4* peels; const uint8_t* touched_prev; int w, h, ntx, n_tiles; uint32_t* zero; uint32_t zero_words; };   // null pointers: nothing to do
-// which kernel the integrate launch (phase 0 / 2 / 4) was and how many workgroups it got: host values, for tsdf_integrate_form.  The forms are the
-// TSDF_K1_* values of rgbd_recon_hip.h; kFormCached = k_integrate_cached + the separable LDS kernel for the tiles the cache does not hold (grid: the latter's)
-enum { kFormGeneric = 0, kFormLdsDirect = 1, kFormLdsSeparable = 2, kFormRecord = 3, kFormCached = 4 };
-struct IntegrateLaunch { int form; uint32_t grid; };
-void launch_integrate(hipStream_t st, const StreamTable& T, const FrameImages& F, const Volume& V, const Bricks& B, const TileState& S, int use_bricks, int lds_ok,
-                      int full_classify, uint32_t frame_stamp, int phase = 0, const PeelClear* pc = nullptr,
-                      const float4* tile_bounds = nullptr,   // per (stored tile, stream) 2 x float4 LUT-box bounds (launch_tile_bounds), or null
-                      uint32_t* pair_masks = nullptr,         // per work item: the frame's pair classes (written by the launch itself), or null
-                      const ProjCache* proj = nullptr,        // projection cache (needs tile_bounds / pair_masks: its work items are classified by the pair-mask pass), or null
-                      uint4* work_recs = nullptr,             // per work item: the 16-byte record of k_integrate_tiles_rec (written by the pair-mask pass), or null
-                      IntegrateLaunch* info = nullptr);       // out: what the integrate launch itself was (untouched by phases 1 and 3)
+// one integrate(): the tile classification (culled volumes only), the pair-mask pass (plan.pair_pass only) and the integrate kernel(s), one launcher
+// each; `plan` (launch_plan.hpp) says which kernel and which grid.  tile_bounds: per (stored tile, stream) 2 x float4 LUT-box bounds (launch_tile_bounds);
+// pair_masks: per work item the frame's pair classes; work_recs: per work item the 16-byte record of k_integrate_tiles_rec, then (after all records)
+// the tiles' per-voxel bits; proj: the projection cache -- each read only where the plan uses it
+void launch_classify_tiles(hipStream_t st, const Volume& V, const Bricks& B, const TileState& S, bool full_classify, uint32_t frame_stamp, const PeelClear& pc);
+void launch_pair_masks(hipStream_t st, const StreamTable& T, const FrameImages& F, const Volume& V, const Bricks& B, const TileState& S, const IntegratePlan& plan,
+                       const float4* tile_bounds, uint32_t* pair_masks, const ProjCache* proj, uint4* work_recs);
+void launch_integrate_tiles(hipStream_t st, const StreamTable& T, const FrameImages& F, const Volume& V, const Bricks& B, const TileState& S, const IntegratePlan& plan,
+                            const uint32_t* pair_masks, const ProjCache* proj, const uint4* work_recs);
 // [work items, cached items, (tile, stream) pairs of cached items evaluated per voxel, items taken by the LDS kernel] of the last launch -> out[4] (device)
 void launch_item_stats(hipStream_t st, const StreamTable& T, const TileState& S, int use_bricks, const uint32_t* pair_masks, const ProjCache& PC, uint32_t* out);
 void launch_tile_bounds(hipStream_t st, const StreamTable& T, const Volume& V, float4* bounds);
@@ -325,9 +325,11 @@ struct RayTarget {
   const uint8_t* touched_cur; const uint8_t* touched_prev; const uint8_t* touched_prev_target; uint8_t* touched_recycle; int rewrite_all, rewrite_target;
   uint8_t* fill_mask;   // (nullable) per tile: touched by this draw or one of the two before -- what the hole filling of this draw has to look at
 };
-void launch_raymarch(hipStream_t st, const ViewParams& P, const StreamTable& T, const FrameImages& F, const Volume& V, const RayTarget& R, int partial,
-                     void* hit_list, uint32_t* hit_counters, int parity, int phase = 0, void* long_list = nullptr, uint32_t cap = 0xffffffffu,
-                     int box_march = 1);   // dense whole-volume march without depth limits: 1 = through LDS voxel boxes with tile-class leaps (k_march_box), 0 = gather march
+// one draw's march and shading, as `plan` (launch_plan.hpp) names them
+void launch_march(hipStream_t st, const ViewParams& P, const Volume& V, const RayTarget& R, const MarchPlan& plan, void* hit_list, uint32_t* hit_counters, int parity,
+                  void* long_list);
+void launch_shade(hipStream_t st, const ViewParams& P, const StreamTable& T, const FrameImages& F, const Volume& V, const RayTarget& R, const MarchPlan& plan,
+                  const void* hit_list, uint32_t* hit_counters, int parity, const void* long_list);
 // hit_list: 16 B per view pixel; long_list: 32 B per view pixel (rays handed to the wave-per-ray pass after `cap` samples);
 // hit_counters: 4 words [hit, hit', long, long'], the primed ones re-armed for the next frame by k_shade
 void launch_inpaint_level(hipStream_t st, const Atlas& A, int lod);

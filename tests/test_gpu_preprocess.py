@@ -66,3 +66,27 @@ def test_process_textures_needs_its_inputs(rr, small_scene):
     with pytest.raises(rr.TsdfError) as e:
         hip.processTextures()
     assert e.value.code == -4
+
+
+def test_each_pass_alone_under_its_timer(rr, small_scene):
+    """timers on and the filter naming the five k_pre_* timers: processTextures() launches each pass alone between its own pair of events.
+    Every product is bit-equal to a context that ran the five passes in one piece with timers off, and each timer holds one sample."""
+    names = ["k_pre_morph", "k_pre_filter", "k_pre_boundary", "k_pre_normal", "k_pre_quality"]
+    timed, plain = rr.ReconIntegrationHip(small_scene, **KW), rr.ReconIntegrationHip(small_scene, **KW)
+    timed.enable_timers(True)
+    timed.set_timer_filter(names)
+    for o in (timed, plain):
+        o.upload_raw_frame(small_scene)
+        o.clearOccupiedBricks()
+        o.processTextures()
+    a, b = timed.preprocessed(), plain.preprocessed()
+    assert set(a) == set(b) == {"depth2", "depth_rg", "lab", "depth_b", "silhouette", "normals", "quality"}
+    for k in a:
+        assert same(a[k], b[k]).all(), f"{k}: {(~same(a[k], b[k])).sum()} of {a[k].size} differ"
+    for x, y in zip(timed.raw_frame() + timed.bricks()[:1], plain.raw_frame() + plain.bricks()[:1]):   # raw depth, the re-laid-out colour, the brick counters
+        np.testing.assert_array_equal(x, y)
+    assert plain.bricks()[0].sum() > 0 and plain.raw_frame()[1].any()
+    assert (b["silhouette"] > 0).sum() > 500 and np.isfinite(b["quality"]).sum() > 500
+    for n in names:
+        assert len(timed.timer_samples(n)) == 1, n
+    timed.close(); plain.close()
