@@ -529,6 +529,53 @@ int32_t tsdf_download_framebuffer(tsdf_ctx* ctx, float* rgba, float* depth);    
 int32_t tsdf_upload_framebuffer(tsdf_ctx* ctx, const float* rgba, const float* depth);    /* its twin: a known framebuffer under an overlay (tests) */
 int32_t tsdf_download_atlas(tsdf_ctx* ctx, float* rgba, float* depth);          /* [h][1.5w] pyramid atlas */
 
+/* ---- mesh extraction: the fused surface as an indexed, coloured triangle mesh ---------------------------
+ * The reference never exports what it fused (tsdf_download_volume is 4 bytes per voxel and leaves the iso-surfacing to the caller); these entries have
+ * no counterpart in it.  They are built on what the raymarch restates: the hit test f > 0 (tsdf_raymarch.fs:96), get_gradient (:140-149),
+ * blendColors (:295-330) and vol_to_world / NormalMatrix (recon_integration.cpp:66-72,199).  tests/mesh_reference.py restates the definition in numpy;
+ * device and numpy agree bit for bit in counts, positions and indices.
+ *
+ * Marching tetrahedra on the voxel-centre lattice.
+ * Samples.  Voxel (i, j, k) holds f at unit-cube position u = ((i + .5) / rx, (j + .5) / ry, (k + .5) / rz), each component in fp32 as
+ *   ((float)i + 0.5f) / (float)rx.  A NaN or infinite value reads as -limit.  A lattice point is INSIDE iff f > 0 (zero and -0 are outside).
+ * Cells.  Cell (i, j, k), 0 <= i < rx - 1 (likewise y, z), has corners c_b = (i + bx, j + by, k + bz), b = bx + 2 by + 4 bz.
+ * Tetrahedra.  Kuhn's six along the diagonal c0 - c7, in this order: (0,1,3,7), (0,1,5,7), (0,2,3,7), (0,2,6,7), (0,4,5,7), (0,4,6,7).  The split is
+ *   translation invariant and face compatible: the mesh is closed wherever the surface does not leave the volume.
+ * Vertices.  Every tetrahedron edge runs from a lattice point p to p + d, d = 1..7 as a bit offset, and is owned by p.  It carries a vertex iff exactly
+ *   one end is inside: with a = f(p), b = f(p + d), t = a / (a - b), per axis u = u_p + t * (u_q - u_p), world = bbox_min + u * (bbox_max - bbox_min);
+ *   fp32, in this operation order.  A vertex exists once, however many triangles use it.
+ * Triangles, per tetrahedron (v0, v1, v2, v3).  All or none inside: none.  One inside, or one outside (A): one triangle over the three edges at A, in
+ *   vertex order.  Two inside (A before B), two outside (C before D): the quad AC, AD, BD, BC as (AC, AD, BD) and (AC, BD, BC).  The winding makes the
+ *   geometric normal point from the inside corners to the outside ones (empty space, f <= 0) for positive bounding-box extents; it is a constant of
+ *   (tetrahedron, case), never decided in floating point.  Degenerate triangles (t = 0) are kept.
+ * Order.  Vertices by (8^3 storage tile of the owner, x fastest as in tsdf_download_active_tiles; owner inside the tile, x fastest, 0..511; d).
+ *   Triangles by (tile of the cell, cell inside the tile, tetrahedron 0..5, triangle 0..1).  Indices are uint32.  No position depends on an atomic: two
+ *   extracts of the same volume give identical arrays.
+ * Normal (TSDF_MESH_NORMALS).  g = central differences of the trilinear TSDF at u +- limit / 2 per axis, gn = normalize(g) exactly as the raymarch shades a
+ *   hit; the world normal is normalize(-gn / (bbox_max - bbox_min)): inverseTranspose(vol_to_world) of the shader's -gn.
+ * Colour (TSDF_MESH_COLOURS).  blendColors of the CURRENT frame slot at u, four floats; alpha +1 = valid, -1 = fallback; independent of the shade mode;
+ *   NaN stays NaN, as in the frame.
+ *
+ * tsdf_mesh_extract reads the volume tsdf_download_volume would return at that moment (it waits for an integrate() in flight on its lane), runs on the
+ *   context's stream, synchronises and returns the counts (either pointer may be NULL).  The mesh stays in device memory of the context, sized exactly
+ *   from the counts, until the next extract, tsdf_set_voxel_size or tsdf_destroy.  It writes no volume set, frame slot, pyramid or lane state.  A tile
+ *   whose own class and whose seven +x/+y/+z neighbours' classes say "every voxel is -limit" (sparse pool: no slot) is skipped without reading a voxel.
+ *   Timers "mesh_count", "mesh_scan", "mesh_emit".
+ *   TSDF_ERR_STATE before the first tsdf_integrate / tsdf_upload_volume; for TSDF_MESH_COLOURS without calibration (cv_xyz_inv, cv_uv) and a frame; on a
+ *   Z-slab context (welding slab meshes is deliberately out of scope: extract from a whole-volume context).  TSDF_ERR_INVALID_ARGUMENT for an unknown flag.
+ *   TSDF_ERR_OUT_OF_MEMORY when the vertices do not fit uint32 or the allocation fails (no mesh is kept then).
+ * tsdf_mesh_download copies the last extract's arrays: position [V][3], normal [V][3], colour [V][4], triangles [T][3]; any may be NULL.
+ *   TSDF_ERR_STATE without an extract, and for an attribute the last extract did not produce.
+ * tsdf_mesh_write_ply writes the last extract as a binary little-endian PLY: vertex x y z, then nx ny nz and red green blue alpha (float) where
+ *   extracted, then faces as uchar 3 + three int indices.  TSDF_ERR_INVALID_ARGUMENT when the file cannot be written.
+ * tsdf_mesh_stats: out = {tiles, tiles skipped by class, tiles with surface, bytes of mesh storage} of the last extract. */
+#define TSDF_MESH_NORMALS 1u
+#define TSDF_MESH_COLOURS 2u
+int32_t tsdf_mesh_extract(tsdf_ctx* ctx, uint32_t flags, uint64_t* n_vertices, uint64_t* n_triangles);
+int32_t tsdf_mesh_download(tsdf_ctx* ctx, float* position_xyz, float* normal_xyz, float* colour_rgba, uint32_t* triangles);
+int32_t tsdf_mesh_write_ply(tsdf_ctx* ctx, const char* path);
+int32_t tsdf_mesh_stats(tsdf_ctx* ctx, uint64_t out[4]);
+
 /* ---- frame read-out: the swap ------------------------------------------------------------------------
  * The client ends a frame with glfwSwapBuffers (source/kinect_client.cpp:533): an RGBA8 window goes to a display (GLFW's default framebuffer has 8
  * bits per channel and the client sets no window hint that changes it, :942-951).  This device has no display; tsdf_present is the swap for a host

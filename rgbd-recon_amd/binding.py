@@ -177,6 +177,7 @@ COLOR_RGB8, COLOR_DXT1, COLOR_DXT5 = 0, 1, 5
 DEPTH_F32, DEPTH_U8 = 0, 1
 PRESENT_RGBA8, PRESENT_DXT1 = 0, 1    # tsdf_present_config: format
 PRESENT_TOP_DOWN = 1                  # ... flags
+MESH_NORMALS, MESH_COLOURS = 1, 2     # tsdf_mesh_extract: flags
 K1_FORMS = ("generic", "lds_direct", "lds_separable", "record", "cached")   # TSDF_K1_* of rgbd_recon_hip.h
 
 
@@ -468,6 +469,7 @@ class ReconIntegrationHip:
 
     def setVoxelSize(self, size):
         self._ck(self._L.tsdf_set_voxel_size(self._c, C.c_float(size)))
+        self._mesh_counts = None                                       # (the mesh went with the old grid)
         r3, b3, s3 = (C.c_uint32 * 3)(), (C.c_uint32 * 3)(), (C.c_float * 3)()
         self._ck(self._L.tsdf_get_resolution(self._c, r3, b3, s3))
         self.res, self.res_bricks, self.brick_size = tuple(r3), tuple(b3), tuple(s3)
@@ -604,6 +606,41 @@ class ReconIntegrationHip:
         rgba, d = np.empty((h, aw, 4), np.float32), np.empty((h, aw), np.float32)
         self._ck(self._L.tsdf_download_atlas(self._c, _fp(rgba), _fp(d)))
         return rgba, d
+
+    # ------------------------------------------------------------------ mesh extraction (no counterpart in the reference)
+    def extract_mesh(self, normals=True, colours=True):
+        """The fused surface as an indexed triangle mesh (tsdf_mesh_extract): dict(position [V][3] f32, triangles [T][3] uint32, and where asked
+        for normal [V][3] f32, colour [V][4] f32 with alpha +1 valid / -1 fallback), in the defined order."""
+        nv, nt = C.c_uint64(), C.c_uint64()
+        flags = (MESH_NORMALS if normals else 0) | (MESH_COLOURS if colours else 0)
+        self._mesh_counts = None
+        self._ck(self._L.tsdf_mesh_extract(self._c, C.c_uint32(flags), C.byref(nv), C.byref(nt)))
+        self._mesh_counts = (nv.value, nt.value)
+        return self.download_mesh(normals, colours)
+
+    def download_mesh(self, normals=True, colours=True):
+        """the arrays of the last extract_mesh (TsdfError, code -4, for an attribute it did not produce)"""
+        if getattr(self, "_mesh_counts", None) is None:
+            raise TsdfError(-4, "no mesh (extract_mesh)")
+        nv, nt = self._mesh_counts
+        out = dict(position=np.zeros((nv, 3), np.float32), triangles=np.zeros((nt, 3), np.uint32))
+        if normals:
+            out["normal"] = np.zeros((nv, 3), np.float32)
+        if colours:
+            out["colour"] = np.zeros((nv, 4), np.float32)
+        self._ck(self._L.tsdf_mesh_download(self._c, _fp(out["position"]), _fp(out.get("normal")), _fp(out.get("colour")),
+                                            out["triangles"].ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def write_ply(self, path):
+        """binary little-endian PLY of the last extract_mesh"""
+        self._ck(self._L.tsdf_mesh_write_ply(self._c, os.fspath(path).encode()))
+
+    def mesh_stats(self):
+        """dict of the last extract_mesh: tiles, tiles_skipped (by class, no voxel read), tiles_with_surface, bytes (of mesh storage)"""
+        out = (C.c_uint64 * 4)()
+        self._ck(self._L.tsdf_mesh_stats(self._c, out))
+        return dict(tiles=int(out[0]), tiles_skipped=int(out[1]), tiles_with_surface=int(out[2]), bytes=int(out[3]))
 
     # ------------------------------------------------------------------ timers / multi-GPU hooks
     def enable_timers(self, on=True): self._ck(self._L.tsdf_enable_timers(self._c, int(on)))

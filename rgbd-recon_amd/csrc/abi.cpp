@@ -606,7 +606,12 @@ RayTarget ray_target(tsdf_ctx* c) {
 
 // setVoxelSize()'s device side, recon_integration.cpp:340-348: the volume for the current c->res (tile-major storage, slot table of a
 // sparse pool, per-tile state and work lists).  Called by tsdf_create and tsdf_set_voxel_size; everything it allocates is released first.
+void release_mesh(tsdf_ctx* c) {
+  hipFree(c->mesh.pos); hipFree(c->mesh.nrm); hipFree(c->mesh.col); hipFree(c->mesh.tri);
+  c->mesh = tsdf_ctx::Mesh{};
+}
 void release_volume(tsdf_ctx* c) {
+  release_mesh(c); c->have_volume = false;                             // (a mesh belongs to the grid it was extracted from)
   hipFree(c->vol.data); hipFree(c->vol.slot);                          // (both callers have synchronised the stream)
   hipFree(c->tiles.stamp); hipFree(c->d_cls_all);
   hipFree(c->d_tile_list[0]); hipFree(c->d_tile_list[1]); hipFree(c->d_tile_counts); hipFree(c->d_linear); hipFree(c->d_tile_bounds); hipFree(c->d_pair_masks); c->d_pair_masks = nullptr; hipFree(c->d_work_recs); c->d_work_recs = nullptr;
@@ -1617,6 +1622,7 @@ int32_t tsdf_integrate(tsdf_ctx* c) {
   if (c->use_bricks) { c->tile_parity ^= 1; c->full_classify = false; }
   else c->full_classify = true;                                       // a dense pass wrote every tile: the next culled frame must look at all of them
   timer_end_on(c, "2integrate", lane);
+  c->have_volume = true;
   HIP_TRY(c, hipGetLastError());
   return TSDF_OK;
 }
@@ -2366,6 +2372,7 @@ int32_t tsdf_upload_volume(tsdf_ctx* c, const float* in) {
   launch_volume_from_linear(c->stream, c->vol, c->d_linear);
   launch_mark_all_mixed(c->stream, c->tiles);
   c->full_classify = true;
+  c->have_volume = true;
   HIP_TRY(c, sync_ctx(c));
   return TSDF_OK;
 }
@@ -2472,6 +2479,118 @@ int32_t tsdf_download_atlas(tsdf_ctx* c, float* rgba, float* depth) {
   if (depth) HIP_TRY(c, hipMemcpy(depth, c->atlas.depth, n * 4, hipMemcpyDeviceToHost));
   return TSDF_OK;
 }
+
+// ---- mesh extraction (k_mesh.hip; the definition is in the header).  The reference has no counterpart: it is built on the raymarch's hit test
+// (tsdf_raymarch.fs:96), get_gradient (:140-149), blendColors (:295-330) and vol_to_world / NormalMatrix (recon_integration.cpp:66-72,199).
+namespace {
+struct MeshTemp {                                                         // what one extract allocates besides the mesh: freed when it returns
+  MeshScratch s{}; uint32_t* records = nullptr;
+  ~MeshTemp() { hipFree(s.tile_cnt); hipFree(s.tile_skip); hipFree(s.tile_vbase); hipFree(s.tile_tbase); hipFree(s.tile_rec); hipFree(s.sums); hipFree(records); }
+};
+}  // namespace
+int32_t tsdf_mesh_extract(tsdf_ctx* c, uint32_t flags, uint64_t* n_vertices, uint64_t* n_triangles) {
+  CHECK_CTX(c);
+  if (flags & ~(TSDF_MESH_NORMALS | TSDF_MESH_COLOURS)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "unknown mesh flag");
+  if (!whole_volume(c)) FAIL(c, TSDF_ERR_STATE, "tsdf_mesh_extract on a Z-slab context: welding slab meshes is not provided");
+  if (!c->have_volume) FAIL(c, TSDF_ERR_STATE, "no volume yet (tsdf_integrate or tsdf_upload_volume)");
+  int32_t rc;
+  if ((flags & TSDF_MESH_COLOURS) && (rc = require_inputs(c, false, true))) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  release_mesh(c);                                                       // (nothing queued reads it: extract and download synchronise)
+  tsdf_ctx::Mesh& M = c->mesh;
+  const Volume& V = c->vol;
+  const int n_tiles = V.n_stored_tiles, nb = mesh_scan_blocks(n_tiles);
+  M.flags = flags; M.stats[0] = (uint64_t)n_tiles;
+  uint64_t totals[4] = {0, 0, 0, 0};
+  MeshTemp tmp;
+  if (c->res[0] >= 2 && c->res[1] >= 2 && c->res[2] >= 2) {             // (a lattice one point thick has no cell)
+    MeshScratch& S = tmp.s;
+    S.n_tiles = n_tiles;
+    HIP_TRY(c, hipMalloc((void**)&S.tile_cnt, (size_t)n_tiles * sizeof(uint2)));
+    HIP_TRY(c, hipMalloc((void**)&S.tile_skip, (size_t)n_tiles));
+    HIP_TRY(c, hipMalloc((void**)&S.tile_vbase, (size_t)n_tiles * sizeof(uint32_t)));
+    HIP_TRY(c, hipMalloc((void**)&S.tile_tbase, (size_t)n_tiles * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMalloc((void**)&S.tile_rec, (size_t)n_tiles * sizeof(uint32_t)));
+    HIP_TRY(c, hipMalloc(&S.sums, (size_t)(nb + 1) * sizeof(totals)));
+    HIP_TRY(c, join_integ(c));                                           // the volume tsdf_download_volume would return now
+    if (flags & TSDF_MESH_COLOURS) HIP_TRY(c, join_pre(c));              // ... and the current frame slot's images
+    timer_begin(c, "mesh_count");
+    launch_mesh_count(c->stream, V, S);
+    timer_end(c, "mesh_count");
+    timer_begin(c, "mesh_scan");
+    launch_mesh_scan(c->stream, S);
+    timer_end(c, "mesh_scan");
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(totals, (const char*)S.sums + (size_t)nb * sizeof(totals), sizeof(totals), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, sync_ctx(c));
+    if (totals[0] > 0xffffffffull) FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "%llu vertices do not fit 32-bit indices", (unsigned long long)totals[0]);
+    if (totals[0]) {
+      const size_t nv = (size_t)totals[0], nt = (size_t)totals[1];
+      bool ok = hipMalloc((void**)&M.pos, nv * 3 * sizeof(float)) == hipSuccess && hipMalloc((void**)&M.tri, std::max<size_t>(nt, 1) * 3 * sizeof(uint32_t)) == hipSuccess &&
+                hipMalloc((void**)&tmp.records, (size_t)totals[2] * 512 * sizeof(uint32_t)) == hipSuccess;
+      if (ok && (flags & TSDF_MESH_NORMALS)) ok = hipMalloc((void**)&M.nrm, nv * 3 * sizeof(float)) == hipSuccess;
+      if (ok && (flags & TSDF_MESH_COLOURS)) ok = hipMalloc((void**)&M.col, nv * 4 * sizeof(float)) == hipSuccess;
+      if (!ok) { (void)hipGetLastError(); release_mesh(c); FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "no device memory for a mesh of %zu vertices and %zu triangles", nv, nt); }
+      const float* lo = c->cfg.bbox_min; const float* hi = c->cfg.bbox_max;
+      const MeshGeometry G{{lo[0], lo[1], lo[2]}, {hi[0], hi[1], hi[2]}};
+      timer_begin(c, "mesh_emit");
+      launch_mesh_emit(c->stream, V, c->luts, c->frame, G, S, tmp.records, M.pos, M.nrm, M.col, M.tri);
+      timer_end(c, "mesh_emit");
+      HIP_TRY(c, hipGetLastError());
+      HIP_TRY(c, sync_ctx(c));
+    }
+  }
+  M.nv = totals[0]; M.nt = totals[1]; M.valid = true;
+  M.stats[1] = totals[3]; M.stats[2] = totals[2];
+  M.stats[3] = M.nv * (3 + ((flags & TSDF_MESH_NORMALS) ? 3 : 0) + ((flags & TSDF_MESH_COLOURS) ? 4 : 0)) * sizeof(float) + M.nt * 3 * sizeof(uint32_t);
+  if (n_vertices) *n_vertices = M.nv;
+  if (n_triangles) *n_triangles = M.nt;
+  return TSDF_OK;
+}
+static int32_t mesh_attribute_check(tsdf_ctx* c, bool want_normals, bool want_colours) {
+  if (!c->mesh.valid) FAIL(c, TSDF_ERR_STATE, "no mesh (tsdf_mesh_extract)");
+  if (want_normals && !(c->mesh.flags & TSDF_MESH_NORMALS)) FAIL(c, TSDF_ERR_STATE, "the last tsdf_mesh_extract produced no normals");
+  if (want_colours && !(c->mesh.flags & TSDF_MESH_COLOURS)) FAIL(c, TSDF_ERR_STATE, "the last tsdf_mesh_extract produced no colours");
+  return TSDF_OK;
+}
+int32_t tsdf_mesh_download(tsdf_ctx* c, float* position_xyz, float* normal_xyz, float* colour_rgba, uint32_t* triangles) {
+  CHECK_CTX(c);
+  int32_t rc = mesh_attribute_check(c, normal_xyz != nullptr, colour_rgba != nullptr);
+  if (rc) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const tsdf_ctx::Mesh& M = c->mesh;
+  if (M.nv) {
+    if (position_xyz) HIP_TRY(c, hipMemcpy(position_xyz, M.pos, (size_t)M.nv * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (normal_xyz) HIP_TRY(c, hipMemcpy(normal_xyz, M.nrm, (size_t)M.nv * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (colour_rgba) HIP_TRY(c, hipMemcpy(colour_rgba, M.col, (size_t)M.nv * 4 * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  if (M.nt && triangles) HIP_TRY(c, hipMemcpy(triangles, M.tri, (size_t)M.nt * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return TSDF_OK;
+}
+int32_t tsdf_mesh_write_ply(tsdf_ctx* c, const char* path) {
+  CHECK_CTX(c);
+  if (!path) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "null path");
+  int32_t rc = mesh_attribute_check(c, false, false);
+  if (rc) return rc;
+  const tsdf_ctx::Mesh& M = c->mesh;
+  const bool nrm = (M.flags & TSDF_MESH_NORMALS) != 0, col = (M.flags & TSDF_MESH_COLOURS) != 0;
+  std::vector<float> p((size_t)M.nv * 3), n(nrm ? (size_t)M.nv * 3 : 0), k(col ? (size_t)M.nv * 4 : 0);
+  std::vector<uint32_t> t((size_t)M.nt * 3);
+  if ((rc = tsdf_mesh_download(c, p.data(), nrm ? n.data() : nullptr, col ? k.data() : nullptr, t.data()))) return rc;
+  std::string why;
+  rc = rr_write_mesh_ply(path, M.nv, M.nt, p.data(), nrm ? n.data() : nullptr, col ? k.data() : nullptr, t.data(), &why);
+  if (rc) c->err = why;
+  return rc;
+}
+int32_t tsdf_mesh_stats(tsdf_ctx* c, uint64_t out[4]) {
+  CHECK_CTX(c);
+  if (!out) return TSDF_ERR_INVALID_ARGUMENT;
+  int32_t rc = mesh_attribute_check(c, false, false);
+  if (rc) return rc;
+  for (int k = 0; k < 4; ++k) out[k] = c->mesh.stats[k];
+  return TSDF_OK;
+}
+
 
 // ---- frame read-out: what the client's window holds after glfwSwapBuffers (source/kinect_client.cpp:533), converted on the device and copied to a pinned
 // host ring (include/rgbd_recon_hip.h, "frame read-out").  The mirror image of the asynchronous upload: a ring, the copy stream, the wire's DXT1.

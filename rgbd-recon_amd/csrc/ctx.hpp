@@ -151,6 +151,12 @@ struct tsdf_ctx {
   uint32_t present_format = 0, present_flags = 0, present_slots = 3, present_head = 0, present_count = 0; bool present_held = false;
   size_t present_bytes = 0;      // what the ring's buffers were allocated for (0: none)
   bool async_upload_ready = false;   // ensure_async_upload ran through (copy_stream alone may be the read-out's)
+  // mesh extraction (tsdf_mesh_extract): the arrays of the last extract, sized exactly from its counts, kept until the next extract, tsdf_set_voxel_size or
+  // destroy; flags = the attributes it produced; stats = {tiles, tiles skipped by class, tiles with surface, bytes of mesh storage}.  Everything else an
+  // extract allocates (per-tile counts, the lattice-point records) is gone when it returns.
+  struct Mesh { float* pos = nullptr; float* nrm = nullptr; float* col = nullptr; uint32_t* tri = nullptr; uint64_t nv = 0, nt = 0; uint32_t flags = 0; bool valid = false;
+                uint64_t stats[4] = {0, 0, 0, 0}; } mesh;
+  bool have_volume = false;          // integrate() or tsdf_upload_volume has written the volume since it was set up (what the mesh extraction may read)
   // flags (recon_integration.cpp:54-57)
   bool fill_holes = true, use_bricks = true, skip_space = true;
   bool draw_bricks = false;   // setDrawBricks (recon_integration.cpp:57,160-173): tsdf_draw_f ends with the occupied-brick wireframes
@@ -242,3 +248,5 @@ hipError_t join_integ(tsdf_ctx* c);     // GPU side: the context's stream waits 
 hipError_t sync_ctx(tsdf_ctx* c);       // host side: both streams
 RayTarget ray_target(tsdf_ctx* c);
 }  // namespace rrhost
+// file_io.cpp: binary little-endian PLY of host arrays (nrm / col may be null); 0 or TSDF_ERR_INVALID_ARGUMENT with *err set
+int32_t rr_write_mesh_ply(const char* path, uint64_t nv, uint64_t nt, const float* pos, const float* nrm, const float* col, const uint32_t* tri, std::string* err);

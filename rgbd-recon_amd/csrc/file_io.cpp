@@ -5,10 +5,12 @@
 // kinect::CalibrationVolume<T>::read / write (framework/calibration/calibration_volume.hpp:30-38, :62-78):
 //   u32 res.x, res.y, res.z; f32 depth_min, depth_max; T volume[res.x * res.y * res.z]   (x fastest, :57-59)
 // Host-only; no GPU involved.  Pinned against the reference's own reader/writer by tests/test_calib_io.py.
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "../../include/rgbd_recon_hip.h"
 
@@ -34,6 +36,41 @@ int32_t read_header(FILE* f, const char* path, uint32_t texel_floats, Header* h)
   return TSDF_OK;
 }
 }  // namespace
+
+// ---- binary little-endian PLY of an indexed triangle mesh (tsdf_mesh_write_ply): per vertex x y z [nx ny nz] [red green blue alpha], all float;
+// per face a uchar 3 and three int indices.  This library's own output format: the reference writes no mesh.
+int32_t rr_write_mesh_ply(const char* path, uint64_t nv, uint64_t nt, const float* pos, const float* nrm, const float* col, const uint32_t* tri, std::string* err) {
+  auto bad = [&](const std::string& m) { if (err) *err = m; return (int32_t)TSDF_ERR_INVALID_ARGUMENT; };
+  if (nv > 0x7fffffffull) return bad("more than 2^31 - 1 vertices do not fit the PLY's int indices");
+  FILE* f = fopen(path, "wb");
+  if (!f) return bad(std::string(path) + ": cannot create");
+  std::string h = "ply\nformat binary_little_endian 1.0\ncomment fused TSDF surface, marching tetrahedra on the voxel-centre lattice\n";
+  h += "element vertex " + std::to_string(nv) + "\nproperty float x\nproperty float y\nproperty float z\n";
+  if (nrm) h += "property float nx\nproperty float ny\nproperty float nz\n";
+  if (col) h += "property float red\nproperty float green\nproperty float blue\nproperty float alpha\n";
+  h += "element face " + std::to_string(nt) + "\nproperty list uchar int vertex_indices\nend_header\n";
+  bool ok = fwrite(h.data(), 1, h.size(), f) == h.size();
+  const size_t vf = 3 + (nrm ? 3 : 0) + (col ? 4 : 0);
+  std::vector<float> row(vf * 4096);
+  for (uint64_t v0 = 0; ok && v0 < nv; v0 += 4096) {
+    const size_t n = (size_t)std::min<uint64_t>(4096, nv - v0);
+    for (size_t i = 0; i < n; ++i) {
+      float* r = row.data() + i * vf;
+      memcpy(r, pos + (v0 + i) * 3, 12); r += 3;
+      if (nrm) { memcpy(r, nrm + (v0 + i) * 3, 12); r += 3; }
+      if (col) memcpy(r, col + (v0 + i) * 4, 16);
+    }
+    ok = fwrite(row.data(), sizeof(float) * vf, n, f) == n;
+  }
+  std::vector<uint8_t> faces(13 * 4096);
+  for (uint64_t t0 = 0; ok && t0 < nt; t0 += 4096) {
+    const size_t n = (size_t)std::min<uint64_t>(4096, nt - t0);
+    for (size_t i = 0; i < n; ++i) { faces[i * 13] = 3; memcpy(&faces[i * 13 + 1], tri + (t0 + i) * 3, 12); }
+    ok = fwrite(faces.data(), 13, n, f) == n;
+  }
+  if (fclose(f) != 0 || !ok) return bad(std::string(path) + ": write failed");
+  return TSDF_OK;
+}
 
 extern "C" {
 

@@ -1,0 +1,364 @@
+// Mesh extraction: the fused surface as an indexed triangle mesh (tsdf_mesh_extract, include/rgbd_recon_hip.h has the definition).
+// The reference has no counterpart; the entry is built on what the raymarch already restates: the hit test f > 0
+// (tsdf_raymarch.fs:96), get_gradient (:140-149), blendColors (:295-330) and vol_to_world (recon_integration.cpp:66-72,199).
+//
+// Marching tetrahedra on the voxel-centre lattice, Kuhn's six tetrahedra per cell.  One workgroup per 8^3 storage tile, one lane per
+// lattice point: a lattice point p owns the seven edges p -> p + d (d = 1..7 as a bit offset) and, where it is the origin of a cell,
+// that cell's triangles.  Five launches, each a plain function of its inputs -- no atomic decides a position and no workgroup waits
+// for another, so the output order (tile, lattice point, d / tetrahedron, triangle) is the same on every run:
+//   k_mesh_count      per tile: vertices and triangles (a tile whose own class and whose +x/+y/+z neighbours' are kTileMinus reads nothing)
+//   k_mesh_block_sums / k_mesh_scan_sums / k_mesh_scan_apply   exclusive scan of the per-tile counts (64-bit totals) and a compact
+//                     record slot for every tile with surface
+//   k_mesh_vertices   per tile with surface: a record per lattice point {edge mask, inside bit, vertex offset in the tile} and the
+//                     vertices (position, optionally normal and colour), one lane per vertex
+//   k_mesh_triangles  per tile with triangles: reads the records only (never the volume); the index of an edge owned by lattice point
+//                     q is tile_vbase[tile of q] + record(q).offset + popcount(record(q).mask below d)
+#include <cfloat>
+
+#include "blend_dev.hpp"
+
+namespace rr {
+
+constexpr int kMeshThreads = 512;            // one lane per lattice point of a tile
+constexpr int kMeshWaves = kMeshThreads / 64;
+constexpr int kMeshCorners = 9 * 9 * 9;      // a tile's lattice points and their +x/+y/+z neighbours
+constexpr int kScanThreads = 256, kScanPerThread = 4, kScanPerBlock = kScanThreads * kScanPerThread;
+
+// Kuhn's six tetrahedra along the diagonal c0 - c7 (corner b = bx + 2 by + 4 bz).  Every vertex list is a chain of bit sets, so every
+// tetrahedron edge runs from a corner to one that contains it: the edge (x, y), x < y, is edge d = y - x of lattice point p + x.
+__constant__ uint8_t c_tet[6][4] = {{0, 1, 3, 7}, {0, 1, 5, 7}, {0, 2, 3, 7}, {0, 2, 6, 7}, {0, 4, 5, 7}, {0, 4, 6, 7}};
+// Winding: bit `case` of row `tetrahedron` set = emit the triangle(s) of that case reversed.  case = sum of 1 << k over the inside
+// vertices v_k.  Tetrahedra 0, 3, 4 are positively oriented, 1, 2, 5 negatively; generated from the rule "the geometric normal points
+// from the inside corners to the outside corners" (tests/mesh_reference.py: winding_table(), which the CPU tests compare with these words).
+__constant__ uint16_t c_mesh_flip[6] = {0x4d24, 0x32da, 0x32da, 0x4d24, 0x4d24, 0x32da};
+
+// a voxel as the mesh reads it: NaN and +-inf read as -limit (NaN voxels exist, tsdf_integration.vs:52)
+__device__ __forceinline__ float mesh_value(float f, float limit) { return fabsf(f) <= FLT_MAX ? f : -limit; }
+
+// inclusive prefix sum inside a wave: Hillis-Steele over each row of 16 lanes with DPP row shifts (a lane without a source adds 0), then
+// the two row broadcasts
+__device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t v) {
+#define RR_DPP_ADD(ctrl, rm) v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rm, 0xf, false)
+  RR_DPP_ADD(0x111, 0xf); RR_DPP_ADD(0x112, 0xf); RR_DPP_ADD(0x114, 0xf); RR_DPP_ADD(0x118, 0xf);   // row_shr 1, 2, 4, 8
+  RR_DPP_ADD(0x142, 0xa); RR_DPP_ADD(0x143, 0xc);                                                   // row_bcast 15 -> rows 1, 3; row_bcast 31 -> rows 2, 3
+#undef RR_DPP_ADD
+  return v;
+}
+// exclusive prefix sum over the workgroup (every lane calls it); *total = the workgroup's sum.  s_wave: kWaves words of LDS.
+template <int kWaves>
+__device__ __forceinline__ uint32_t block_exclusive_sum(uint32_t v, uint32_t* s_wave, uint32_t* total) {
+  const uint32_t inc = wave_inclusive_sum(v);
+  const int wave = threadIdx.x >> 6;
+  __syncthreads();                                                     // (s_wave may still be read from the previous call)
+  if ((threadIdx.x & 63) == 63) s_wave[wave] = inc;
+  __syncthreads();
+  uint32_t before = 0, all = 0;
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w) { const uint32_t s = s_wave[w]; all += s; if (w < wave) before += s; }
+  *total = all;
+  return before + inc - v;
+}
+
+struct MeshTile { int tx, ty, tz, id; };
+__device__ __forceinline__ MeshTile mesh_tile(const Volume& V) {
+  MeshTile t;
+  t.id = (int)blockIdx.x;
+  const int per_layer = V.ntx * V.nty, layer = t.id / per_layer, in_layer = t.id - layer * per_layer;
+  t.tz = layer; t.ty = in_layer / V.ntx; t.tx = in_layer - t.ty * V.ntx;
+  return t;
+}
+__device__ __forceinline__ int corner_index(int lx, int ly, int lz) { return (lz * 9 + ly) * 9 + lx; }
+
+// the tile's 9 x 9 x 9 corner values -> LDS; a corner outside the lattice reads -limit (no edge and no cell reaches it: see mesh_point)
+template <bool kSparse>
+__device__ __forceinline__ void mesh_stage(const Volume& V, const MeshTile& t, float* s_f) {
+  for (int i = threadIdx.x; i < kMeshCorners; i += kMeshThreads) {
+    const int lx = i % 9, ly = (i / 9) % 9, lz = i / 81;
+    const int x = t.tx * 8 + lx, y = t.ty * 8 + ly, z = t.tz * 8 + lz;
+    float f = -V.limit;
+    if (x < V.res[0] && y < V.res[1] && z < V.res[2]) f = mesh_value(kSparse ? tsdf_tap_sparse(V, x, y, z) : V.data[vol_index(V, x, y, z)], V.limit);
+    s_f[i] = f;
+  }
+}
+
+// What lattice point `lane` of the tile owns: its edge mask (bit d - 1: the edge p -> p + d lies inside the lattice and exactly one
+// of its ends is inside the surface), whether p itself is inside, and the triangles of the cell whose origin it is.
+struct MeshPoint { uint32_t mask, inside, ntri; };
+__device__ __forceinline__ uint32_t tet_triangles(uint32_t corners, int k) {   // corners: bit b = corner b is inside
+  const uint32_t n = ((corners >> c_tet[k][0]) & 1u) + ((corners >> c_tet[k][1]) & 1u) + ((corners >> c_tet[k][2]) & 1u) + ((corners >> c_tet[k][3]) & 1u);
+  return n == 2u ? 2u : ((n == 1u || n == 3u) ? 1u : 0u);
+}
+__device__ __forceinline__ uint32_t cell_triangles(uint32_t corners) {
+  uint32_t n = 0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) n += tet_triangles(corners, k);
+  return n;
+}
+__device__ __forceinline__ MeshPoint mesh_point(const Volume& V, const MeshTile& t, const float* s_f, int lane) {
+  const int lx = lane & 7, ly = (lane >> 3) & 7, lz = lane >> 6;
+  const int x = t.tx * 8 + lx, y = t.ty * 8 + ly, z = t.tz * 8 + lz;
+  MeshPoint p{0u, 0u, 0u};
+  if (x >= V.res[0] || y >= V.res[1] || z >= V.res[2]) return p;
+  p.inside = s_f[corner_index(lx, ly, lz)] > 0.0f ? 1u : 0u;          // the raymarch's hit test, tsdf_raymarch.fs:96: zero and -0 are outside
+  uint32_t corners = p.inside;
+#pragma unroll
+  for (int d = 1; d < 8; ++d) {
+    const int bx = d & 1, by = (d >> 1) & 1, bz = d >> 2;
+    if (x + bx < V.res[0] && y + by < V.res[1] && z + bz < V.res[2]) {
+      const uint32_t in = s_f[corner_index(lx + bx, ly + by, lz + bz)] > 0.0f ? 1u : 0u;
+      corners |= in << d;
+      if (in != p.inside) p.mask |= 1u << (d - 1);
+    }
+  }
+  if (x + 1 < V.res[0] && y + 1 < V.res[1] && z + 1 < V.res[2]) p.ntri = cell_triangles(corners);
+  return p;
+}
+
+// ---- 1. count
+template <bool kSparse>
+__global__ __launch_bounds__(kMeshThreads) void k_mesh_count(Volume V, uint2* __restrict__ tile_cnt, uint8_t* __restrict__ tile_skip) {
+  __shared__ float s_f[kMeshCorners];
+  __shared__ uint32_t s_wave[kMeshWaves];
+  const MeshTile t = mesh_tile(V);
+  // the tile and its seven +x/+y/+z neighbours hold the clear value only (-limit: outside): no edge of this tile can cross the surface
+  int mixed = 0;
+  if (threadIdx.x < 8) {
+    const int nx = t.tx + (threadIdx.x & 1), ny = t.ty + ((threadIdx.x >> 1) & 1), nz = t.tz + (threadIdx.x >> 2);
+    if (nx < V.ntx && ny < V.nty && nz < V.tz1) {
+      const uint32_t id = (uint32_t)((nz * V.nty + ny) * V.ntx + nx);
+      mixed = kSparse ? V.slot[id] != kNoSlot : V.cls[id] != kTileMinus;
+    }
+  }
+  if (!__syncthreads_or(mixed)) {
+    if (threadIdx.x == 0) { tile_cnt[t.id] = make_uint2(0u, 0u); tile_skip[t.id] = 1; }
+    return;
+  }
+  mesh_stage<kSparse>(V, t, s_f);
+  __syncthreads();
+  const MeshPoint p = mesh_point(V, t, s_f, threadIdx.x);
+  uint32_t total;
+  block_exclusive_sum<kMeshWaves>((uint32_t)__popc(p.mask) | (p.ntri << 16), s_wave, &total);   // both counts in one word: at most 3584 and 6144 per tile
+  if (threadIdx.x == 0) { tile_cnt[t.id] = make_uint2(total & 0xffffu, total >> 16); tile_skip[t.id] = 0; }
+}
+
+// ---- 2. scan of the per-tile counts: block sums, scan of the block sums, add.  Four quantities: vertices, triangles, tiles with
+// surface, tiles skipped by class.  A block covers kScanPerBlock tiles, so its own sums fit 32 bits; everything across blocks is 64-bit.
+struct MeshSums { unsigned long long nv, nt, surface, skipped; };
+__device__ __forceinline__ void scan_load(const uint2* __restrict__ tile_cnt, const uint8_t* __restrict__ tile_skip, int n, uint2 c[kScanPerThread], uint32_t sk[kScanPerThread]) {
+  const int first = ((int)blockIdx.x * kScanThreads + (int)threadIdx.x) * kScanPerThread;
+#pragma unroll
+  for (int k = 0; k < kScanPerThread; ++k) {
+    const bool in = first + k < n;
+    c[k] = in ? tile_cnt[first + k] : make_uint2(0u, 0u);
+    sk[k] = in ? (uint32_t)tile_skip[first + k] : 0u;
+  }
+}
+__global__ __launch_bounds__(kScanThreads) void k_mesh_block_sums(const uint2* __restrict__ tile_cnt, const uint8_t* __restrict__ tile_skip, int n, MeshSums* __restrict__ sums) {
+  __shared__ uint32_t s_wave[kScanThreads / 64];
+  uint2 c[kScanPerThread]; uint32_t sk[kScanPerThread];
+  scan_load(tile_cnt, tile_skip, n, c, sk);
+  uint32_t nv = 0, nt = 0, flags = 0;
+#pragma unroll
+  for (int k = 0; k < kScanPerThread; ++k) { nv += c[k].x; nt += c[k].y; flags += (c[k].x ? 1u : 0u) | (sk[k] << 16); }
+  uint32_t tv, tt, tf;
+  block_exclusive_sum<kScanThreads / 64>(nv, s_wave, &tv);
+  block_exclusive_sum<kScanThreads / 64>(nt, s_wave, &tt);
+  block_exclusive_sum<kScanThreads / 64>(flags, s_wave, &tf);
+  if (threadIdx.x == 0) sums[blockIdx.x] = MeshSums{tv, tt, tf & 0xffffu, tf >> 16};
+}
+// one workgroup: sums[0 .. nb) become exclusive prefixes, sums[nb] the totals.  Every lane takes a contiguous run of blocks.
+__global__ __launch_bounds__(kScanThreads) void k_mesh_scan_sums(MeshSums* __restrict__ sums, int nb) {
+  __shared__ MeshSums s_run[kScanThreads];
+  const int per = (nb + kScanThreads - 1) / kScanThreads, b0 = min((int)threadIdx.x * per, nb), b1 = min(b0 + per, nb);
+  MeshSums run{0, 0, 0, 0};
+  for (int b = b0; b < b1; ++b) { const MeshSums s = sums[b]; run.nv += s.nv; run.nt += s.nt; run.surface += s.surface; run.skipped += s.skipped; }
+  s_run[threadIdx.x] = run;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    MeshSums acc{0, 0, 0, 0};
+    for (int k = 0; k < kScanThreads; ++k) {
+      const MeshSums s = s_run[k];
+      s_run[k] = acc;
+      acc.nv += s.nv; acc.nt += s.nt; acc.surface += s.surface; acc.skipped += s.skipped;
+    }
+    sums[nb] = acc;
+  }
+  __syncthreads();
+  MeshSums acc = s_run[threadIdx.x];
+  for (int b = b0; b < b1; ++b) {
+    const MeshSums s = sums[b];
+    sums[b] = acc;
+    acc.nv += s.nv; acc.nt += s.nt; acc.surface += s.surface; acc.skipped += s.skipped;
+  }
+}
+__global__ __launch_bounds__(kScanThreads) void k_mesh_scan_apply(const uint2* __restrict__ tile_cnt, const uint8_t* __restrict__ tile_skip, int n, const MeshSums* __restrict__ sums,
+                                                                  uint32_t* __restrict__ tile_vbase, unsigned long long* __restrict__ tile_tbase, uint32_t* __restrict__ tile_rec) {
+  __shared__ uint32_t s_wave[kScanThreads / 64];
+  uint2 c[kScanPerThread]; uint32_t sk[kScanPerThread];
+  scan_load(tile_cnt, tile_skip, n, c, sk);
+  uint32_t nv = 0, nt = 0, ns = 0;
+#pragma unroll
+  for (int k = 0; k < kScanPerThread; ++k) { nv += c[k].x; nt += c[k].y; ns += c[k].x ? 1u : 0u; }
+  uint32_t total;
+  const MeshSums base = sums[blockIdx.x];
+  unsigned long long v = base.nv + block_exclusive_sum<kScanThreads / 64>(nv, s_wave, &total);
+  unsigned long long t = base.nt + block_exclusive_sum<kScanThreads / 64>(nt, s_wave, &total);
+  unsigned long long s = base.surface + block_exclusive_sum<kScanThreads / 64>(ns, s_wave, &total);
+  const int first = ((int)blockIdx.x * kScanThreads + (int)threadIdx.x) * kScanPerThread;
+#pragma unroll
+  for (int k = 0; k < kScanPerThread; ++k)
+    if (first + k < n) {
+      tile_vbase[first + k] = (uint32_t)v;                             // (the host refuses a mesh whose vertices do not fit 32 bits before anything reads this)
+      tile_tbase[first + k] = t;
+      tile_rec[first + k] = c[k].x ? (uint32_t)s : kNoSlot;
+      v += c[k].x; t += c[k].y; s += c[k].x ? 1u : 0u;
+    }
+}
+
+// ---- 3. records and vertices
+// record of a lattice point: bits 0..6 edge mask, bit 7 inside, bits 8.. the offset of its first vertex inside the tile
+template <bool kSparse>
+__global__ __launch_bounds__(kMeshThreads) void k_mesh_vertices(Volume V, StreamTable T, FrameImages F, MeshGeometry G, const uint2* __restrict__ tile_cnt,
+                                                                const uint32_t* __restrict__ tile_vbase, const uint32_t* __restrict__ tile_rec, uint32_t* __restrict__ records,
+                                                                float* __restrict__ out_pos, float* __restrict__ out_nrm, float4* __restrict__ out_col) {
+  __shared__ float s_f[kMeshCorners];
+  __shared__ uint32_t s_wave[kMeshWaves];
+  __shared__ uint16_t s_edge[kMeshThreads * 7];                        // per vertex of the tile: lattice point << 3 | d
+  const MeshTile t = mesh_tile(V);
+  const uint32_t nv = tile_cnt[t.id].x;
+  if (nv == 0) return;
+  mesh_stage<kSparse>(V, t, s_f);
+  __syncthreads();
+  const MeshPoint p = mesh_point(V, t, s_f, threadIdx.x);
+  uint32_t total;
+  const uint32_t off = block_exclusive_sum<kMeshWaves>((uint32_t)__popc(p.mask), s_wave, &total);
+  records[(size_t)tile_rec[t.id] * kMeshThreads + threadIdx.x] = p.mask | (p.inside << 7) | (off << 8);
+  {
+    uint32_t k = off;
+#pragma unroll
+    for (int d = 1; d < 8; ++d)
+      if (p.mask & (1u << (d - 1))) s_edge[k++] = (uint16_t)((threadIdx.x << 3) | d);
+  }
+  __syncthreads();
+  const float ex = G.bbox_max[0] - G.bbox_min[0], ey = G.bbox_max[1] - G.bbox_min[1], ez = G.bbox_max[2] - G.bbox_min[2];
+  const float limit = V.limit, sd = limit * 0.5f;
+  for (uint32_t v = threadIdx.x; v < nv; v += kMeshThreads) {
+    const int e = s_edge[v], lane = e >> 3, d = e & 7;
+    const int lx = lane & 7, ly = (lane >> 3) & 7, lz = lane >> 6;
+    const int bx = d & 1, by = (d >> 1) & 1, bz = d >> 2;
+    const float a = s_f[corner_index(lx, ly, lz)], b = s_f[corner_index(lx + bx, ly + by, lz + bz)];
+    const float w = a / (a - b);
+    const int x = t.tx * 8 + lx, y = t.ty * 8 + ly, z = t.tz * 8 + lz;
+    const float upx = ((float)x + 0.5f) / (float)V.res[0], uqx = ((float)(x + bx) + 0.5f) / (float)V.res[0];
+    const float upy = ((float)y + 0.5f) / (float)V.res[1], uqy = ((float)(y + by) + 0.5f) / (float)V.res[1];
+    const float upz = ((float)z + 0.5f) / (float)V.res[2], uqz = ((float)(z + bz) + 0.5f) / (float)V.res[2];
+    const float3 u = make_float3(upx + w * (uqx - upx), upy + w * (uqy - upy), upz + w * (uqz - upz));
+    const size_t o = (size_t)tile_vbase[t.id] + v;
+    out_pos[o * 3 + 0] = G.bbox_min[0] + u.x * ex;                     // vol_to_world, recon_integration.cpp:66-72
+    out_pos[o * 3 + 1] = G.bbox_min[1] + u.y * ey;
+    out_pos[o * 3 + 2] = G.bbox_min[2] + u.z * ez;
+    if (out_nrm) {
+      const float gx = tex3d_tsdf<kSparse>(V, u.x + sd, u.y, u.z) - tex3d_tsdf<kSparse>(V, u.x - sd, u.y, u.z);
+      const float gy = tex3d_tsdf<kSparse>(V, u.x, u.y + sd, u.z) - tex3d_tsdf<kSparse>(V, u.x, u.y - sd, u.z);
+      const float gz = tex3d_tsdf<kSparse>(V, u.x, u.y, u.z + sd) - tex3d_tsdf<kSparse>(V, u.x, u.y, u.z - sd);
+      const float3 gn = normalize3(make_float3(gx, gy, gz));          // get_gradient(), tsdf_raymarch.fs:140-149, as shade_hit does it
+      // inverseTranspose(vol_to_world) of the shader's -gn: the NormalMatrix of recon_integration.cpp:199 without the model-view
+      const float3 n = normalize3(make_float3(-gn.x / ex, -gn.y / ey, -gn.z / ez));
+      out_nrm[o * 3 + 0] = n.x; out_nrm[o * 3 + 1] = n.y; out_nrm[o * 3 + 2] = n.z;
+    }
+    if (out_col) out_col[o] = blend_colors(T, F, limit, u);           // all four components: alpha +1 valid, -1 fallback
+  }
+}
+
+// ---- 4. triangles, from the records alone
+__device__ __forceinline__ uint32_t edge_vertex(const uint32_t* s_first, const uint8_t* s_mask, int lx, int ly, int lz, int x, int y) {   // corners x < y of the cell at (lx, ly, lz)
+  const int i = corner_index(lx + (x & 1), ly + ((x >> 1) & 1), lz + (x >> 2)), d = y - x;
+  return s_first[i] + (uint32_t)__popc((uint32_t)s_mask[i] & ((1u << (d - 1)) - 1u));
+}
+__global__ __launch_bounds__(kMeshThreads) void k_mesh_triangles(Volume V, const uint2* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_vbase,
+                                                                 const unsigned long long* __restrict__ tile_tbase, const uint32_t* __restrict__ tile_rec,
+                                                                 const uint32_t* __restrict__ records, uint32_t* __restrict__ out_tri) {
+  __shared__ uint32_t s_first[kMeshCorners];                           // per corner: the mesh index of the first vertex it owns
+  __shared__ uint8_t s_mask[kMeshCorners];                             // ... and its record's low byte (edge mask, inside bit)
+  __shared__ uint32_t s_wave[kMeshWaves];
+  const MeshTile t = mesh_tile(V);
+  if (tile_cnt[t.id].y == 0) return;
+  for (int i = threadIdx.x; i < kMeshCorners; i += kMeshThreads) {
+    const int lx = i % 9, ly = (i / 9) % 9, lz = i / 81;
+    const int x = t.tx * 8 + lx, y = t.ty * 8 + ly, z = t.tz * 8 + lz;
+    uint32_t first = 0, mask = 0;
+    if (x < V.res[0] && y < V.res[1] && z < V.res[2]) {
+      const int tile = ((z >> 3) * V.nty + (y >> 3)) * V.ntx + (x >> 3);
+      const uint32_t slot = tile_rec[tile];
+      if (slot != kNoSlot) {                                           // (a tile without surface owns no crossed edge: nothing is looked up in it)
+        const uint32_t r = records[(size_t)slot * kMeshThreads + (((z & 7) << 6) | ((y & 7) << 3) | (x & 7))];
+        first = tile_vbase[tile] + (r >> 8); mask = r & 0xffu;
+      }
+    }
+    s_first[i] = first; s_mask[i] = (uint8_t)mask;
+  }
+  __syncthreads();
+  const int lx = threadIdx.x & 7, ly = (threadIdx.x >> 3) & 7, lz = threadIdx.x >> 6;
+  const int x = t.tx * 8 + lx, y = t.ty * 8 + ly, z = t.tz * 8 + lz;
+  // the cell's corner bits from its origin's record: corner b is inside iff the origin is, unless the edge origin -> b is crossed
+  uint32_t corners = 0, ntri = 0;
+  if (x + 1 < V.res[0] && y + 1 < V.res[1] && z + 1 < V.res[2]) {
+    const uint32_t m = s_mask[corner_index(lx, ly, lz)];
+    corners = ((m & 0x7fu) << 1) ^ ((m & 0x80u) ? 0xffu : 0u);
+    ntri = cell_triangles(corners);
+  }
+  uint32_t total;
+  const uint32_t off = block_exclusive_sum<kMeshWaves>(ntri, s_wave, &total);
+  if (ntri == 0) return;
+  uint32_t* __restrict__ o = out_tri + (size_t)(tile_tbase[t.id] + off) * 3;
+  for (int k = 0; k < 6; ++k) {
+    const int v[4] = {c_tet[k][0], c_tet[k][1], c_tet[k][2], c_tet[k][3]};
+    uint32_t cs = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) cs |= ((corners >> v[j]) & 1u) << j;
+    if (cs == 0u || cs == 15u) continue;
+    const bool flip = (c_mesh_flip[k] >> cs) & 1u;
+    const int n_in = __popc(cs);
+    if (n_in != 2) {                                                   // one vertex apart from the other three: one triangle over its three edges, in vertex order
+      const uint32_t lone = n_in == 1 ? cs : (cs ^ 15u);
+      const int a = __ffs((int)lone) - 1;
+      uint32_t e[3]; int n = 0;
+      for (int j = 0; j < 4; ++j)
+        if (j != a) { e[n++] = edge_vertex(s_first, s_mask, lx, ly, lz, min(v[a], v[j]), max(v[a], v[j])); }
+      o[0] = e[0]; o[1] = flip ? e[2] : e[1]; o[2] = flip ? e[1] : e[2];
+      o += 3;
+    } else {                                                           // inside A before B, outside C before D: the quad AC, AD, BD, BC as (AC, AD, BD), (AC, BD, BC)
+      int in[2], out[2], ni = 0, no = 0;
+      for (int j = 0; j < 4; ++j) { if ((cs >> j) & 1u) in[ni++] = v[j]; else out[no++] = v[j]; }
+      const uint32_t ac = edge_vertex(s_first, s_mask, lx, ly, lz, min(in[0], out[0]), max(in[0], out[0]));
+      const uint32_t ad = edge_vertex(s_first, s_mask, lx, ly, lz, min(in[0], out[1]), max(in[0], out[1]));
+      const uint32_t bd = edge_vertex(s_first, s_mask, lx, ly, lz, min(in[1], out[1]), max(in[1], out[1]));
+      const uint32_t bc = edge_vertex(s_first, s_mask, lx, ly, lz, min(in[1], out[0]), max(in[1], out[0]));
+      o[0] = ac; o[1] = flip ? bd : ad; o[2] = flip ? ad : bd;
+      o[3] = ac; o[4] = flip ? bc : bd; o[5] = flip ? bd : bc;
+      o += 6;
+    }
+  }
+}
+
+// ---- launchers
+int mesh_scan_blocks(int n_tiles) { return (n_tiles + kScanPerBlock - 1) / kScanPerBlock; }
+void launch_mesh_count(hipStream_t st, const Volume& V, const MeshScratch& S) {
+  if (V.slot) hipLaunchKernelGGL(k_mesh_count<true>, dim3(S.n_tiles), dim3(kMeshThreads), 0, st, V, S.tile_cnt, S.tile_skip);
+  else hipLaunchKernelGGL(k_mesh_count<false>, dim3(S.n_tiles), dim3(kMeshThreads), 0, st, V, S.tile_cnt, S.tile_skip);
+}
+void launch_mesh_scan(hipStream_t st, const MeshScratch& S) {
+  const int nb = mesh_scan_blocks(S.n_tiles);
+  MeshSums* sums = (MeshSums*)S.sums;
+  hipLaunchKernelGGL(k_mesh_block_sums, dim3(nb), dim3(kScanThreads), 0, st, S.tile_cnt, S.tile_skip, S.n_tiles, sums);
+  hipLaunchKernelGGL(k_mesh_scan_sums, dim3(1), dim3(kScanThreads), 0, st, sums, nb);
+  hipLaunchKernelGGL(k_mesh_scan_apply, dim3(nb), dim3(kScanThreads), 0, st, S.tile_cnt, S.tile_skip, S.n_tiles, sums, S.tile_vbase, S.tile_tbase, S.tile_rec);
+}
+void launch_mesh_emit(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S, uint32_t* records,
+                      float* pos, float* nrm, float* col, uint32_t* tri) {
+  if (V.slot) hipLaunchKernelGGL(k_mesh_vertices<true>, dim3(S.n_tiles), dim3(kMeshThreads), 0, st, V, T, F, G, S.tile_cnt, S.tile_vbase, S.tile_rec, records, pos, nrm, (float4*)col);
+  else hipLaunchKernelGGL(k_mesh_vertices<false>, dim3(S.n_tiles), dim3(kMeshThreads), 0, st, V, T, F, G, S.tile_cnt, S.tile_vbase, S.tile_rec, records, pos, nrm, (float4*)col);
+  hipLaunchKernelGGL(k_mesh_triangles, dim3(S.n_tiles), dim3(kMeshThreads), 0, st, V, S.tile_cnt, S.tile_vbase, S.tile_tbase, S.tile_rec, records, tri);
+}
+
+}  // namespace rr

@@ -342,6 +342,23 @@ void launch_colorfill(hipStream_t st, const Atlas& A, int w, int h, float4* fb_c
 void launch_resolve_masked(hipStream_t st, const Atlas& A, int w, int h, float4* fb_color, float* fb_depth, int mask, int keep_color);
 // frame read-out (k_present.hip): the framebuffer colour as RGBA8 (format 0: w * h * 4 bytes) or DXT1 blocks (1: ceil(w/4) * ceil(h/4) * 8 bytes) into out
 void launch_present(hipStream_t st, const float4* fb_c, void* out, int w, int h, uint32_t format, int top_down);
+// mesh extraction (k_mesh.hip): per-tile scratch of one extract, sized by the launchers' caller.  Whole-volume contexts only: tile id = stored tile index.
+struct MeshGeometry { float bbox_min[3], bbox_max[3]; };
+struct MeshScratch {
+  uint2* tile_cnt;                  // per tile {vertices, triangles}
+  uint8_t* tile_skip;               // per tile: 1 = skipped by its class (no voxel read)
+  uint32_t* tile_vbase;             // exclusive scan of the vertex counts
+  unsigned long long* tile_tbase;   // ... of the triangle counts
+  uint32_t* tile_rec;               // compact slot of a tile with surface in the record pool, or kNoSlot
+  void* sums;                       // mesh_scan_blocks(n_tiles) + 1 entries of 4 x uint64: per-block prefixes, then the totals {vertices, triangles, tiles with surface, tiles skipped}
+  int n_tiles;
+};
+int mesh_scan_blocks(int n_tiles);
+void launch_mesh_count(hipStream_t st, const Volume& V, const MeshScratch& S);
+void launch_mesh_scan(hipStream_t st, const MeshScratch& S);   // three launches: block sums, scan of the block sums, add
+// records: 512 words per tile with surface; nrm / col may be null (attribute not wanted; T and F are read for colours only)
+void launch_mesh_emit(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S, uint32_t* records,
+                      float* pos, float* nrm, float* col, uint32_t* tri);
 void launch_clear_image(hipStream_t st, float4* color, float* depth, size_t n, float4 c, float d);
 void launch_export_partial(hipStream_t st, const RayTarget& R, int w, int h, void* dst);
 void launch_composite(hipStream_t st, const void* gathered, int n, const RayTarget& R, int w, int h);

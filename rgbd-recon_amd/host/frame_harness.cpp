@@ -9,6 +9,9 @@
 // Option --present rgba8|dxt1: five more draws of the frame, each followed by the swap (present, source/kinect_client.cpp:533), the presented frames
 // picked up two frames late and the last two after the loop; tags must come back in order, every frame must have the format's size, and the RGBA8
 // frames must equal the framebuffer download converted on the host (the frame is the same each time).
+// Option --mesh FILE.ply: after the last frame, the fused surface is extracted as a triangle mesh with normals and colours (extractMesh) and written to
+// FILE.ply; the counts are printed and the downloaded arrays must have their sizes.  (This scene's TSDF is positive everywhere: the mesh is empty, the file
+// a header.)
 //   g++ -std=c++17 frame_harness.cpp -o frame_harness -L.. -lrgbd_recon_hip -Wl,-rpath,'$ORIGIN/..'
 #include <cmath>
 #include <cstdio>
@@ -23,13 +26,15 @@ int main(int argc, char** argv) {
   int view_type = -1;
   float view_width = 0.0f;
   int present_format = -1;
+  const char* mesh_path = nullptr;
   for (int a = 1; a < argc; ++a) {
     if (std::strcmp(argv[a], "--draw-bricks") == 0) draw_bricks = true;
     else if (std::strcmp(argv[a], "--sensor-view") == 0 && a + 2 < argc) { view_type = std::atoi(argv[a + 1]); view_width = (float)std::atof(argv[a + 2]); a += 2; }
     else if (std::strcmp(argv[a], "--present") == 0 && a + 1 < argc && (std::strcmp(argv[a + 1], "rgba8") == 0 || std::strcmp(argv[a + 1], "dxt1") == 0)) {
       present_format = std::strcmp(argv[a + 1], "dxt1") == 0 ? (int)TSDF_PRESENT_DXT1 : (int)TSDF_PRESENT_RGBA8; a += 1;
     }
-    else { std::fprintf(stderr, "usage: frame_harness [--draw-bricks] [--sensor-view TYPE WIDTH] [--present rgba8|dxt1]\n"); return 1; }
+    else if (std::strcmp(argv[a], "--mesh") == 0 && a + 1 < argc) { mesh_path = argv[a + 1]; a += 1; }
+    else { std::fprintf(stderr, "usage: frame_harness [--draw-bricks] [--sensor-view TYPE WIDTH] [--present rgba8|dxt1] [--mesh FILE.ply]\n"); return 1; }
   }
   kinect::ReconInputs in;
   in.num_kinects = 1;
@@ -122,6 +127,14 @@ int main(int argc, char** argv) {
       for (int f = frames - lag; f < frames; ++f) take((std::uint64_t)(100 + f));
       std::printf("%d frames presented as %s, %d picked up in order, %d mismatches\n", frames, present_format ? "dxt1" : "rgba8", got, wrong);
       if (got != frames || wrong != 0) return 1;
+    }
+    if (mesh_path) {
+      const kinect::ReconIntegrationHip::MeshCounts n = recon.extractMesh(true, true);
+      kinect::ReconIntegrationHip::Mesh mesh;
+      recon.downloadMesh(mesh);
+      recon.writeMeshPly(mesh_path);
+      std::printf("mesh: %llu vertices, %llu triangles -> %s\n", (unsigned long long)n.vertices, (unsigned long long)n.triangles, mesh_path);
+      if (mesh.position.size() != n.vertices * 3 || mesh.normal.size() != n.vertices * 3 || mesh.colour.size() != n.vertices * 4 || mesh.triangles.size() != n.triangles * 3) return 1;
     }
     return band > 0 ? 0 : 1;
   } catch (std::exception const& e) {

@@ -166,6 +166,26 @@ class ReconIntegrationHip {
     tsdf.resize((std::size_t)r[0] * r[1] * r[2]);
     check(tsdf_download_volume(m_ctx, tsdf.data()));
   }
+  // ---- the fused surface as an indexed triangle mesh (tsdf_mesh_extract).  The reference has no counterpart: it never exports what it fused.
+  // extractMesh runs the extraction on the volume as it is now and returns the counts; downloadMesh copies the arrays of the last extract
+  // (normals / colours stay empty unless that extract produced them); writeMeshPly writes it as a binary little-endian PLY.
+  struct Mesh { std::vector<float> position, normal, colour; std::vector<std::uint32_t> triangles; };   // [V][3], [V][3], [V][4] (alpha +1 valid, -1 fallback), [T][3]
+  struct MeshCounts { std::uint64_t vertices = 0, triangles = 0; };
+  MeshCounts extractMesh(bool normals = true, bool colours = true) {
+    m_mesh_flags = (normals ? TSDF_MESH_NORMALS : 0u) | (colours ? TSDF_MESH_COLOURS : 0u);
+    m_mesh = MeshCounts{};
+    check(tsdf_mesh_extract(m_ctx, m_mesh_flags, &m_mesh.vertices, &m_mesh.triangles));
+    return m_mesh;
+  }
+  void downloadMesh(Mesh& out) {
+    out.position.resize((std::size_t)m_mesh.vertices * 3);
+    out.normal.resize((m_mesh_flags & TSDF_MESH_NORMALS) ? (std::size_t)m_mesh.vertices * 3 : 0);
+    out.colour.resize((m_mesh_flags & TSDF_MESH_COLOURS) ? (std::size_t)m_mesh.vertices * 4 : 0);
+    out.triangles.resize((std::size_t)m_mesh.triangles * 3);
+    check(tsdf_mesh_download(m_ctx, out.position.data(), out.normal.empty() ? nullptr : out.normal.data(), out.colour.empty() ? nullptr : out.colour.data(),
+                             out.triangles.data()));
+  }
+  void writeMeshPly(const char* path) { check(tsdf_mesh_write_ply(m_ctx, path)); }
   // ---- kinect::ReconPoints::draw() (recon_points.cpp:71-111) on the same inputs: the point back-end for A/B comparison
   void uploadNormals(const float* normals_rgb) { check(tsdf_upload_normals(m_ctx, normals_rgb)); }
   void drawPoints() { check(tsdf_draw_points(m_ctx, m_mv, m_proj)); }
@@ -182,6 +202,7 @@ class ReconIntegrationHip {
   void check(int32_t rc) const { if (rc != TSDF_OK) throw std::runtime_error(std::string("ReconIntegrationHip: ") + tsdf_last_error(m_ctx)); }
   ReconInputs m_in;
   tsdf_ctx* m_ctx = nullptr;
+  MeshCounts m_mesh; std::uint32_t m_mesh_flags = 0;   // of the last extractMesh
   float m_mv[16], m_proj[16];
   float m_brick_size;
 };
