@@ -576,6 +576,76 @@ int32_t tsdf_mesh_download(tsdf_ctx* ctx, float* position_xyz, float* normal_xyz
 int32_t tsdf_mesh_write_ply(tsdf_ctx* ctx, const char* path);
 int32_t tsdf_mesh_stats(tsdf_ctx* ctx, uint64_t out[4]);
 
+/* ---- mesh streaming: the fused surface every frame, packed, through a pinned ring -------------------------
+ * tsdf_mesh_extract is a one-shot export: it allocates, waits for the host twice and leaves 12..40 bytes per vertex in fp32.  A telepresence client hands
+ * its geometry to a remote renderer, a recorder or a thin client EVERY frame; these entries deliver the mesh the way tsdf_present delivers the picture:
+ * queued behind the frame on the context's stream, compact, copied into a ring of pinned host buffers on the copy stream, picked up while the lanes
+ * compute the next frames.  No counterpart in the reference.  tests/mesh_pack_reference.py restates the packing in numpy on top of
+ * tests/mesh_reference.py; device and numpy agree byte for byte.
+ *
+ * What is meshed.  Exactly the mesh of tsdf_mesh_extract above: the same lattice, tetrahedra, one vertex per crossed edge, winding table, vertex and
+ *   triangle order, uint32 indices, and the same reading of 0, -0, NaN and infinite voxels.  The triangle array of a streamed frame is byte-identical to
+ *   the one tsdf_mesh_extract + tsdf_mesh_download give for the same volume.  The volume is the one tsdf_download_volume would return at the moment of the
+ *   tsdf_mesh_stream call, the colours those of the frame slot current then; both are taken as stream dependencies (the context's stream waits for the
+ *   integrate lane, and for the lane ahead when colours are asked for), never as a host wait.
+ * Packed vertex.  One aligned vector store per vertex; vertex_stride = 8 bytes with flags == 0, 16 bytes with TSDF_MESH_NORMALS and / or
+ *   TSDF_MESH_COLOURS (a field that was not asked for is 0).  Little endian.
+ *   bytes 0-7   position: four uint16 qx, qy, qz, 0 with q = (uint16) rint(min(max(u, 0), 1) * 65535.0f), u the vertex's UNIT-CUBE coordinate of the
+ *               definition above (u = u_p + t * (u_q - u_p), before vol_to_world); the product in fp32, rint = round to nearest, half-way cases to even.
+ *               The receiver reconstructs world = bbox_min + (q / 65535) * (bbox_max - bbox_min): at most half a step, 0.5 / 65535 of the extent per axis,
+ *               from the fp32 position.
+ *   bytes 8-11  normal, octahedral, two int16 ox, oy.  n = the world normal of the definition above; s = (|nx| + |ny|) + |nz|, px = nx / s, py = ny / s;
+ *               if nz < 0 (-0 is not): (px, py) = ((1 - |py|) * sg(px), (1 - |px|) * sg(py)), the old values on the right, sg(x) = x >= 0 ? 1 : -1;
+ *               o = (int16) rint(min(max(p, -1), 1) * 32767.0f).  If any component of n is NaN (a zero gradient) both codes are -32768, which no finite
+ *               normal produces.  Decoding: p = o / 32767, z = 1 - |px| - |py|, for z < 0 the same fold, normalize(px, py, z).
+ *   bytes 12-15 colour r, g, b, a: blendColors as above, each channel by tsdf_present's RGBA8 rule (NaN -> 0, clamp, rint(v * 255)): the fallback alpha -1
+ *               becomes 0, a valid alpha +1 becomes 255.
+ * The ring.  tsdf_mesh_stream_config fixes the flags, the three capacities (vertices, triangles, 8^3 tiles with surface) and the number of slots (2..8);
+ *   TSDF_ERR_INVALID_ARGUMENT for an unknown flag, a zero capacity, a slot count out of range, or a payload of more than 4 GiB.  A slot is a device buffer (a 64-byte header, then
+ *   max_vertices * stride + max_triangles * 12 bytes), a pinned host buffer of the same size and four events.  The slots and ONE persistent set of
+ *   scratch (per-tile counts and bases, the scan's sums, lattice-point records for max_surface_tiles tiles) are allocated by the first tsdf_mesh_stream
+ *   after a config (or after tsdf_set_voxel_size); from the second call on tsdf_mesh_stream allocates nothing, frees nothing and never blocks the host:
+ *   it waits for no GPU work.  (With the volume sets alternating and a hole-filling worker thread it does wait, as the overlays do, until that thread has
+ *   ISSUED the stream wait of the job it was handed this frame -- a few host instructions of another thread, bounded, no device time.)
+ * tsdf_mesh_stream(tag) takes the next free slot -- TSDF_ERR_STATE and nothing queued when every slot is queued or held -- and queues count, scan, a
+ *   one-lane launch that writes the slot's header, and the two emit launches on the context's stream behind everything queued so far.  The emit kernels
+ *   read the needs and the capacities from that header in device memory: when a need exceeds its capacity every workgroup returns at once and the
+ *   header says so (overflow bits: 1 vertices, 2 triangles, 4 surface tiles; needed_* always filled; n_vertices = n_triangles = 0).  A frame is never
+ *   partial.  The copy stream copies the header as soon as it is written; the payload -- exactly n_vertices * vertex_stride + n_triangles * 12 bytes in one
+ *   copy, never the capacity -- is queued behind the emit by whichever of tsdf_mesh_stream, tsdf_mesh_stream_acquire and tsdf_mesh_stream_release is called
+ *   first after the header has arrived on the host (each of them looks at every queued frame, oldest first); an acquire with wait != 0 waits for the
+ *   header itself.  With a ring of 3 slots and the acquire two frames late no call ever waits.
+ * tsdf_mesh_stream_acquire hands frames out in the order of the tsdf_mesh_stream calls.  *out is filled and *ready = 1 when the oldest frame is complete
+ *   on the host; the pointers are into the slot's pinned buffer and stay valid until tsdf_mesh_stream_release (triangles follow the vertices directly).
+ *   wait != 0 waits for that frame; wait == 0 sets *ready = 0 and returns TSDF_OK while it is not complete (never a partial frame).  ready may be NULL
+ *   with wait != 0.  TSDF_ERR_STATE with nothing queued, or with a frame already held.  tsdf_mesh_stream_release frees the held slot (TSDF_ERR_STATE
+ *   when none is held).
+ * tsdf_mesh_stream_stats: out = {frames queued since the config, of those overflowed (as far as their headers have been seen), payload bytes copied to
+ *   the host (headers not counted), device bytes held by slots and scratch}.
+ * While frames are queued or held, tsdf_mesh_stream_config and tsdf_set_voxel_size return TSDF_ERR_STATE.  tsdf_destroy drains the ring.  TSDF_ERR_STATE
+ *   on a Z-slab context, before the first tsdf_integrate / tsdf_upload_volume, and for TSDF_MESH_COLOURS without calibration and a frame -- as
+ *   tsdf_mesh_extract; before any tsdf_mesh_stream_config too.  A lattice thinner than 2 on an axis yields frames with zero counts.  The mesh ring and the
+ *   present ring share the copy stream and work side by side.  With the volume sets alternating (stage overlap), the integrate() two frames later that
+ *   overwrites the set a frame's mesh kernels read waits for them.  Timers "mesh_stream_count", "mesh_stream_scan", "mesh_stream_emit".
+ *   A context that never calls these runs exactly what it ran before they existed; tsdf_mesh_extract and its three companions are untouched. */
+typedef struct tsdf_mesh_frame {
+  const void*     vertices;      /* packed, n_vertices * vertex_stride bytes, in the slot's pinned buffer */
+  const uint32_t* triangles;     /* [n_triangles][3] */
+  uint64_t n_vertices, n_triangles;                           /* 0 when overflow != 0 */
+  uint64_t needed_vertices, needed_triangles, needed_tiles;   /* what this frame's surface needs, always filled */
+  uint64_t tag;
+  uint32_t flags, vertex_stride, overflow;                    /* overflow bits: 1 vertices, 2 triangles, 4 surface tiles */
+  uint32_t res[3]; float bbox_min[3], bbox_max[3];            /* what the receiver needs to dequantise */
+} tsdf_mesh_frame;
+#define TSDF_MESH_OVERFLOW_VERTICES  1u
+#define TSDF_MESH_OVERFLOW_TRIANGLES 2u
+#define TSDF_MESH_OVERFLOW_TILES     4u
+int32_t tsdf_mesh_stream_config(tsdf_ctx* ctx, uint32_t flags, uint32_t max_vertices, uint32_t max_triangles, uint32_t max_surface_tiles, uint32_t slots);
+int32_t tsdf_mesh_stream(tsdf_ctx* ctx, uint64_t tag);
+int32_t tsdf_mesh_stream_acquire(tsdf_ctx* ctx, int32_t wait, tsdf_mesh_frame* out, int32_t* ready);
+int32_t tsdf_mesh_stream_release(tsdf_ctx* ctx);
+int32_t tsdf_mesh_stream_stats(tsdf_ctx* ctx, uint64_t out[4]);
+
 /* ---- frame read-out: the swap ------------------------------------------------------------------------
  * The client ends a frame with glfwSwapBuffers (source/kinect_client.cpp:533): an RGBA8 window goes to a display (GLFW's default framebuffer has 8
  * bits per channel and the client sets no window hint that changes it, :942-951).  This device has no display; tsdf_present is the swap for a host

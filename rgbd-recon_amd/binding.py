@@ -178,6 +178,25 @@ DEPTH_F32, DEPTH_U8 = 0, 1
 PRESENT_RGBA8, PRESENT_DXT1 = 0, 1    # tsdf_present_config: format
 PRESENT_TOP_DOWN = 1                  # ... flags
 MESH_NORMALS, MESH_COLOURS = 1, 2     # tsdf_mesh_extract: flags
+MESH_OVERFLOW_VERTICES, MESH_OVERFLOW_TRIANGLES, MESH_OVERFLOW_TILES = 1, 2, 4   # tsdf_mesh_frame: overflow bits
+
+
+class MeshFrame(C.Structure):
+    """tsdf_mesh_frame of rgbd_recon_hip.h"""
+    _fields_ = [("vertices", C.c_void_p), ("triangles", C.POINTER(C.c_uint32)), ("n_vertices", C.c_uint64), ("n_triangles", C.c_uint64),
+                ("needed_vertices", C.c_uint64), ("needed_triangles", C.c_uint64), ("needed_tiles", C.c_uint64), ("tag", C.c_uint64),
+                ("flags", C.c_uint32), ("vertex_stride", C.c_uint32), ("overflow", C.c_uint32), ("res", C.c_uint32 * 3),
+                ("bbox_min", C.c_float * 3), ("bbox_max", C.c_float * 3)]
+
+
+def unpack_mesh_vertices(vertices):
+    """a streamed frame's vertex array -> dict(position uint16 [V][3], and for the 16-byte stride normal int16 [V][2], colour uint8 [V][4])"""
+    if vertices.dtype == np.uint16:
+        return dict(position=vertices[:, :3])
+    v = np.ascontiguousarray(vertices)
+    return dict(position=v[:, :8].view(np.uint16)[:, :3], normal=v[:, 8:12].view(np.int16), colour=v[:, 12:16])
+
+
 K1_FORMS = ("generic", "lds_direct", "lds_separable", "record", "cached")   # TSDF_K1_* of rgbd_recon_hip.h
 
 
@@ -641,6 +660,52 @@ class ReconIntegrationHip:
         out = (C.c_uint64 * 4)()
         self._ck(self._L.tsdf_mesh_stats(self._c, out))
         return dict(tiles=int(out[0]), tiles_skipped=int(out[1]), tiles_with_surface=int(out[2]), bytes=int(out[3]))
+
+    # ------------------------------------------------------------------ mesh streaming (no counterpart in the reference)
+    def mesh_stream_config(self, normals=False, colours=False, max_vertices=1 << 20, max_triangles=1 << 21, max_surface_tiles=1 << 14, slots=3):
+        """flags, the three capacities and the slot count of the mesh ring (tsdf_mesh_stream_config); the first mesh_stream after it allocates"""
+        flags = (MESH_NORMALS if normals else 0) | (MESH_COLOURS if colours else 0)
+        self._ck(self._L.tsdf_mesh_stream_config(self._c, C.c_uint32(flags), C.c_uint32(int(max_vertices)), C.c_uint32(int(max_triangles)),
+                                                 C.c_uint32(int(max_surface_tiles)), C.c_uint32(int(slots))))
+
+    def mesh_stream(self, tag=0):
+        """queue count, scan, emit and the copy of the current surface into the next ring slot; never blocks (TsdfError, code -4, when every slot is taken)"""
+        self._ck(self._L.tsdf_mesh_stream(self._c, C.c_uint64(int(tag))))
+
+    def mesh_stream_acquire(self, wait=True):
+        """the oldest streamed frame not yet released as (vertices, triangles, info), still held until mesh_stream_release(); None while it is not
+        complete on the host (wait=False).  vertices: a VIEW of the slot's pinned buffer, uint16 [V][4] (qx, qy, qz, 0) with stride 8, uint8 [V][16] with
+        stride 16 (unpack_mesh_vertices splits it); triangles: a view, uint32 [T][3]; info: dict of the tsdf_mesh_frame fields."""
+        f, ready = MeshFrame(), C.c_int32()
+        self._ck(self._L.tsdf_mesh_stream_acquire(self._c, C.c_int32(1 if wait else 0), C.byref(f), C.byref(ready)))
+        if not ready.value:
+            return None
+        nv, nt, stride = int(f.n_vertices), int(f.n_triangles), int(f.vertex_stride)
+        raw = np.ctypeslib.as_array(C.cast(f.vertices, C.POINTER(C.c_uint8)), shape=(nv * stride,)) if nv else np.zeros(0, np.uint8)
+        vertices = raw.view(np.uint16).reshape(nv, 4) if stride == 8 else raw.reshape(nv, 16)
+        triangles = np.ctypeslib.as_array(f.triangles, shape=(nt, 3)) if nt else np.zeros((0, 3), np.uint32)
+        info = dict(n_vertices=nv, n_triangles=nt, needed_vertices=int(f.needed_vertices), needed_triangles=int(f.needed_triangles),
+                    needed_tiles=int(f.needed_tiles), tag=int(f.tag), flags=int(f.flags), vertex_stride=stride, overflow=int(f.overflow),
+                    res=tuple(int(x) for x in f.res), bbox_min=np.array(f.bbox_min[:], np.float32), bbox_max=np.array(f.bbox_max[:], np.float32))
+        return vertices, triangles, info
+
+    def mesh_stream_release(self):
+        self._ck(self._L.tsdf_mesh_stream_release(self._c))
+
+    def mesh_stream_take(self, wait=True):
+        """acquire, COPY, release: (vertices, triangles, info) as numpy arrays of the caller's own, or None (wait=False, frame not complete)"""
+        got = self.mesh_stream_acquire(wait)
+        if got is None:
+            return None
+        out = (got[0].copy(), got[1].copy(), got[2])
+        self.mesh_stream_release()
+        return out
+
+    def mesh_stream_stats(self):
+        """dict: frames (queued since the config), overflowed, payload_bytes (copied to the host, headers not counted), device_bytes (held)"""
+        out = (C.c_uint64 * 4)()
+        self._ck(self._L.tsdf_mesh_stream_stats(self._c, out))
+        return dict(frames=int(out[0]), overflowed=int(out[1]), payload_bytes=int(out[2]), device_bytes=int(out[3]))
 
     # ------------------------------------------------------------------ timers / multi-GPU hooks
     def enable_timers(self, on=True): self._ck(self._L.tsdf_enable_timers(self._c, int(on)))

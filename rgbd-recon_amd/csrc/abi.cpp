@@ -610,8 +610,22 @@ void release_mesh(tsdf_ctx* c) {
   hipFree(c->mesh.pos); hipFree(c->mesh.nrm); hipFree(c->mesh.col); hipFree(c->mesh.tri);
   c->mesh = tsdf_ctx::Mesh{};
 }
+// the mesh ring's slots and scratch (nothing may be in flight: an idle ring, or behind a synchronisation of the streams); the configuration stays
+void release_mesh_stream(tsdf_ctx* c) {
+  tsdf_ctx::MeshStream& R = c->mstream;
+  for (auto& S : R.ring) {
+    hipFree(S.dev); if (S.host) hipHostFree(S.host);
+    for (hipEvent_t e : {S.header_written, S.emitted, S.header_ready, S.ready}) if (e) hipEventDestroy(e);
+    S = tsdf_ctx::MeshStreamSlot{};
+  }
+  MeshScratch& T = R.scratch;
+  hipFree(T.tile_cnt); hipFree(T.tile_skip); hipFree(T.tile_vbase); hipFree(T.tile_tbase); hipFree(T.tile_rec); hipFree(T.sums); hipFree(R.records);
+  T = MeshScratch{}; R.records = nullptr;
+  R.allocated = false; R.head = 0; R.count = 0; R.held = false; R.device_bytes = 0;
+}
 void release_volume(tsdf_ctx* c) {
   release_mesh(c); c->have_volume = false;                             // (a mesh belongs to the grid it was extracted from)
+  release_mesh_stream(c);                                              // (... and the streaming scratch is sized by its tiles)
   hipFree(c->vol.data); hipFree(c->vol.slot);                          // (both callers have synchronised the stream)
   hipFree(c->tiles.stamp); hipFree(c->d_cls_all);
   hipFree(c->d_tile_list[0]); hipFree(c->d_tile_list[1]); hipFree(c->d_tile_counts); hipFree(c->d_linear); hipFree(c->d_tile_bounds); hipFree(c->d_pair_masks); c->d_pair_masks = nullptr; hipFree(c->d_work_recs); c->d_work_recs = nullptr;
@@ -841,7 +855,7 @@ int32_t tsdf_destroy(tsdf_ctx* c) {
   CHECK_CTX(c);
   hipSetDevice(c->device);
   sync_ctx(c);          // (a null handle is the NULL stream: tsdf_adopt_null_stream)
-  if (c->copy_stream) hipStreamSynchronize(c->copy_stream);   // an asynchronous upload may still be writing a frame slot, a presented frame still travelling to its host buffer
+  if (c->copy_stream) hipStreamSynchronize(c->copy_stream);   // an asynchronous upload may still be writing a frame slot, a presented frame or a streamed mesh still travelling to its host buffer
   release_present(c);
   tsdf_comm_destroy(c);
   release_view(c); release_bricks(c);
@@ -2268,6 +2282,7 @@ int32_t tsdf_set_voxel_size(tsdf_ctx* c, float size) {
     res[a] = (int)ceilf((c->cfg.bbox_max[a] - c->cfg.bbox_min[a]) / size);
     if (res[a] < 1 || res[a] > 4096) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "volume resolution out of range [1, 4096]");
   }
+  if (c->mstream.count) FAIL(c, TSDF_ERR_STATE, "%u streamed mesh frame(s) are queued or held: acquire and release them before the grid changes", c->mstream.count);
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, sync_ctx(c));
   const int old_res[3] = {c->res[0], c->res[1], c->res[2]};
@@ -2591,6 +2606,169 @@ int32_t tsdf_mesh_stats(tsdf_ctx* c, uint64_t out[4]) {
   return TSDF_OK;
 }
 
+// ---- mesh streaming (the definition is in the header): the same mesh every frame, packed, without a host wait or an allocation after the first call
+static size_t mesh_stream_payload_capacity(const tsdf_ctx::MeshStream& R) { return (size_t)R.max_vertices * (R.flags ? 16 : 8) + (size_t)R.max_triangles * 12; }
+int32_t tsdf_mesh_stream_config(tsdf_ctx* c, uint32_t flags, uint32_t max_vertices, uint32_t max_triangles, uint32_t max_surface_tiles, uint32_t slots) {
+  CHECK_CTX(c);
+  tsdf_ctx::MeshStream& R = c->mstream;
+  if ((flags & ~(TSDF_MESH_NORMALS | TSDF_MESH_COLOURS)) || !max_vertices || !max_triangles || !max_surface_tiles || slots < 2 || slots > tsdf_ctx::MeshStream::kMaxSlots)
+    FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "mesh stream flags %u / capacities %u vertices, %u triangles, %u tiles / slots %u (flags 1 normals, 2 colours; capacities > 0; 2..%u slots)",
+         flags, max_vertices, max_triangles, max_surface_tiles, slots, tsdf_ctx::MeshStream::kMaxSlots);
+  if ((uint64_t)max_vertices * (flags ? 16 : 8) + (uint64_t)max_triangles * 12 > (4ull << 30)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "a mesh stream slot of more than 4 GiB");
+  if (R.count) FAIL(c, TSDF_ERR_STATE, "%u streamed mesh frame(s) are queued or held: acquire and release them first", R.count);
+  HIP_TRY(c, hipSetDevice(c->device));
+  // The ring is idle for the copies only (each was waited for before its frame was released): a frame that overflowed or had no payload was handed out
+  // behind its header copy alone, and its emit launches, which read the slot's device header and the scratch, may still be queued on the context's stream.
+  if (R.allocated) HIP_TRY(c, hipStreamSynchronize(c->stream));
+  release_mesh_stream(c);
+  R.flags = flags; R.max_vertices = max_vertices; R.max_triangles = max_triangles; R.max_tiles = max_surface_tiles; R.slots = slots; R.configured = true;
+  R.frames = R.overflowed = R.bytes_copied = 0;
+  return TSDF_OK;
+}
+// slots and scratch, once per configuration and grid
+static int32_t mesh_stream_allocate(tsdf_ctx* c) {
+  tsdf_ctx::MeshStream& R = c->mstream;
+  const size_t n_tiles = (size_t)c->vol.n_stored_tiles, nb = (size_t)mesh_scan_blocks((int)n_tiles), slot_bytes = sizeof(MeshStreamHeader) + mesh_stream_payload_capacity(R);
+  MeshScratch& T = R.scratch;
+  T.n_tiles = (int)n_tiles;
+  bool ok = hipMalloc((void**)&T.tile_cnt, n_tiles * sizeof(uint2)) == hipSuccess && hipMalloc((void**)&T.tile_skip, n_tiles) == hipSuccess &&
+            hipMalloc((void**)&T.tile_vbase, n_tiles * sizeof(uint32_t)) == hipSuccess && hipMalloc((void**)&T.tile_tbase, n_tiles * sizeof(unsigned long long)) == hipSuccess &&
+            hipMalloc((void**)&T.tile_rec, n_tiles * sizeof(uint32_t)) == hipSuccess && hipMalloc(&T.sums, (nb + 1) * 4 * sizeof(uint64_t)) == hipSuccess &&
+            hipMalloc((void**)&R.records, (size_t)R.max_tiles * 512 * sizeof(uint32_t)) == hipSuccess;
+  for (uint32_t k = 0; ok && k < R.slots; ++k) {
+    tsdf_ctx::MeshStreamSlot& S = R.ring[k];
+    ok = hipMalloc((void**)&S.dev, slot_bytes) == hipSuccess && hipHostMalloc((void**)&S.host, slot_bytes, hipHostMallocDefault) == hipSuccess;
+    for (hipEvent_t* e : {&S.header_written, &S.emitted, &S.header_ready, &S.ready}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+  }
+  if (ok && !c->copy_stream) ok = hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) == hipSuccess;   // (as ensure_async_upload makes it)
+  if (!ok) { (void)hipGetLastError(); release_mesh_stream(c); FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "no memory for %u mesh stream slots of %zu bytes and the scratch of %zu tiles", R.slots, slot_bytes, n_tiles); }
+  R.device_bytes = (uint64_t)R.slots * slot_bytes + n_tiles * (sizeof(uint2) + 1 + 4 + 8 + 4) + (nb + 1) * 4 * sizeof(uint64_t) + (uint64_t)R.max_tiles * 512 * sizeof(uint32_t);
+  R.allocated = true;
+  return TSDF_OK;
+}
+// Queue the payload copy of every queued frame whose header has arrived on the host, oldest first (the copy stream is in order: behind a header still
+// travelling nothing has arrived either).  Host side this is event queries only.
+static int32_t mesh_stream_pump(tsdf_ctx* c) {
+  tsdf_ctx::MeshStream& R = c->mstream;
+  for (uint32_t k = 0; k < R.count; ++k) {
+    tsdf_ctx::MeshStreamSlot& S = R.ring[(R.head + k) % R.slots];
+    if (S.payload_issued) continue;
+    const hipError_t e = hipEventQuery(S.header_ready);
+    if (e == hipErrorNotReady) { (void)hipGetLastError(); break; }       // ("not ready" is no error: it must not stay behind as the thread's last one)
+    HIP_TRY(c, e);
+    const MeshStreamHeader* H = (const MeshStreamHeader*)S.host;
+    S.payload_bytes = (size_t)H->n_vertices * (R.flags ? 16 : 8) + (size_t)H->n_triangles * 12;
+    if (S.payload_bytes) {
+      HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, S.emitted, 0));
+      HIP_TRY(c, hipMemcpyAsync(S.host + sizeof(MeshStreamHeader), S.dev + sizeof(MeshStreamHeader), S.payload_bytes, hipMemcpyDeviceToHost, c->copy_stream));
+      HIP_TRY(c, hipEventRecord(S.ready, c->copy_stream));
+    }
+    S.payload_issued = true;                                             // (the counters move with it: a call that failed above repeats the slot without counting it twice)
+    if (H->overflow) ++R.overflowed;
+    R.bytes_copied += S.payload_bytes;
+  }
+  return TSDF_OK;
+}
+int32_t tsdf_mesh_stream(tsdf_ctx* c, uint64_t tag) {
+  CHECK_CTX(c);
+  tsdf_ctx::MeshStream& R = c->mstream;
+  if (!R.configured) FAIL(c, TSDF_ERR_STATE, "tsdf_mesh_stream before tsdf_mesh_stream_config");
+  if (!whole_volume(c)) FAIL(c, TSDF_ERR_STATE, "tsdf_mesh_stream on a Z-slab context: welding slab meshes is not provided");
+  if (!c->have_volume) FAIL(c, TSDF_ERR_STATE, "no volume yet (tsdf_integrate or tsdf_upload_volume)");
+  int32_t rc;
+  if ((R.flags & TSDF_MESH_COLOURS) && (rc = require_inputs(c, false, true))) return rc;
+  if (R.count >= R.slots) FAIL(c, TSDF_ERR_STATE, "all %u mesh stream slots are queued or held (tsdf_mesh_stream_acquire / tsdf_mesh_stream_release)", R.slots);
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (!R.allocated && (rc = mesh_stream_allocate(c))) return rc;
+  if ((rc = mesh_stream_pump(c))) return rc;
+  tsdf_ctx::MeshStreamSlot& S = R.ring[(R.head + R.count) % R.slots];
+  MeshStreamHeader* H = (MeshStreamHeader*)S.dev;
+  const Volume& V = c->vol;
+  const bool cells = c->res[0] >= 2 && c->res[1] >= 2 && c->res[2] >= 2;  // (a lattice one point thick has no cell)
+  if (cells) {
+    HIP_TRY(c, join_integ(c));                                           // the volume tsdf_download_volume would return now
+    if (R.flags & TSDF_MESH_COLOURS) HIP_TRY(c, join_pre(c));            // ... and the current frame slot's images
+    timer_begin(c, "mesh_stream_count");
+    launch_mesh_count(c->stream, V, R.scratch);
+    timer_end(c, "mesh_stream_count");
+    timer_begin(c, "mesh_stream_scan");
+    launch_mesh_scan(c->stream, R.scratch);
+    launch_mesh_stream_header(c->stream, R.scratch, H, R.max_vertices, R.max_triangles, R.max_tiles);
+    timer_end(c, "mesh_stream_scan");
+  } else HIP_TRY(c, hipMemsetAsync(H, 0, sizeof(MeshStreamHeader), c->stream));
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipEventRecord(S.header_written, c->stream));
+  HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, S.header_written, 0));
+  HIP_TRY(c, hipMemcpyAsync(S.host, S.dev, sizeof(MeshStreamHeader), hipMemcpyDeviceToHost, c->copy_stream));
+  HIP_TRY(c, hipEventRecord(S.header_ready, c->copy_stream));
+  if (cells) {
+    const float* lo = c->cfg.bbox_min; const float* hi = c->cfg.bbox_max;
+    const MeshGeometry G{{lo[0], lo[1], lo[2]}, {hi[0], hi[1], hi[2]}};
+    timer_begin(c, "mesh_stream_emit");
+    launch_mesh_stream_emit(c->stream, V, c->luts, c->frame, G, R.scratch, R.flags, H, R.records, S.dev + sizeof(MeshStreamHeader));
+    timer_end(c, "mesh_stream_emit");
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(S.emitted, c->stream));
+    // With the volume sets alternating, the integrate() two frames later overwrites the set these launches read, and it waits for draw_done[set] only:
+    // record that event again behind them (as an overlay does).
+    if ((rc = overlay_rerecord_draw(c))) return rc;
+  }
+  S.tag = tag; S.payload_issued = false; S.payload_bytes = 0;
+  for (int a = 0; a < 3; ++a) S.res[a] = c->res[a];
+  ++R.count; ++R.frames;
+  return TSDF_OK;
+}
+int32_t tsdf_mesh_stream_acquire(tsdf_ctx* c, int32_t wait, tsdf_mesh_frame* out, int32_t* ready) {
+  CHECK_CTX(c);
+  if (!out || (!ready && !wait)) return TSDF_ERR_INVALID_ARGUMENT;
+  if (ready) *ready = 0;
+  tsdf_ctx::MeshStream& R = c->mstream;
+  if (!R.count) FAIL(c, TSDF_ERR_STATE, "no streamed mesh frame is queued");
+  if (R.held) FAIL(c, TSDF_ERR_STATE, "a streamed mesh frame is held already: tsdf_mesh_stream_release first");
+  HIP_TRY(c, hipSetDevice(c->device));
+  tsdf_ctx::MeshStreamSlot& S = R.ring[R.head];
+  if (wait && !S.payload_issued) HIP_TRY(c, hipEventSynchronize(S.header_ready));
+  int32_t rc;
+  if ((rc = mesh_stream_pump(c))) return rc;
+  if (!S.payload_issued) return TSDF_OK;                                  // (wait == 0: the header is still travelling)
+  if (S.payload_bytes) {
+    if (wait) HIP_TRY(c, hipEventSynchronize(S.ready));
+    else {
+      const hipError_t e = hipEventQuery(S.ready);
+      if (e == hipErrorNotReady) { (void)hipGetLastError(); return TSDF_OK; }
+      HIP_TRY(c, e);
+    }
+  }
+  const MeshStreamHeader* H = (const MeshStreamHeader*)S.host;
+  const uint32_t stride = R.flags ? 16u : 8u;
+  *out = tsdf_mesh_frame{};
+  out->vertices = S.host + sizeof(MeshStreamHeader);
+  out->triangles = (const uint32_t*)(S.host + sizeof(MeshStreamHeader) + (size_t)H->n_vertices * stride);
+  out->n_vertices = H->n_vertices; out->n_triangles = H->n_triangles;
+  out->needed_vertices = H->needed_vertices; out->needed_triangles = H->needed_triangles; out->needed_tiles = H->needed_tiles;
+  out->tag = S.tag; out->flags = R.flags; out->vertex_stride = stride; out->overflow = H->overflow;
+  for (int a = 0; a < 3; ++a) { out->res[a] = (uint32_t)S.res[a]; out->bbox_min[a] = c->cfg.bbox_min[a]; out->bbox_max[a] = c->cfg.bbox_max[a]; }
+  R.held = true;
+  if (ready) *ready = 1;
+  return TSDF_OK;
+}
+int32_t tsdf_mesh_stream_release(tsdf_ctx* c) {
+  CHECK_CTX(c);
+  tsdf_ctx::MeshStream& R = c->mstream;
+  if (!R.held) FAIL(c, TSDF_ERR_STATE, "no streamed mesh frame is held");
+  R.held = false;
+  R.head = (R.head + 1) % R.slots;
+  --R.count;
+  HIP_TRY(c, hipSetDevice(c->device));
+  return mesh_stream_pump(c);
+}
+int32_t tsdf_mesh_stream_stats(tsdf_ctx* c, uint64_t out[4]) {
+  CHECK_CTX(c);
+  if (!out) return TSDF_ERR_INVALID_ARGUMENT;
+  const tsdf_ctx::MeshStream& R = c->mstream;
+  out[0] = R.frames; out[1] = R.overflowed; out[2] = R.bytes_copied; out[3] = R.device_bytes;
+  return TSDF_OK;
+}
 
 // ---- frame read-out: what the client's window holds after glfwSwapBuffers (source/kinect_client.cpp:533), converted on the device and copied to a pinned
 // host ring (include/rgbd_recon_hip.h, "frame read-out").  The mirror image of the asynchronous upload: a ring, the copy stream, the wire's DXT1.

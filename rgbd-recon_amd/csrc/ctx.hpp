@@ -156,6 +156,22 @@ struct tsdf_ctx {
   // extract allocates (per-tile counts, the lattice-point records) is gone when it returns.
   struct Mesh { float* pos = nullptr; float* nrm = nullptr; float* col = nullptr; uint32_t* tri = nullptr; uint64_t nv = 0, nt = 0; uint32_t flags = 0; bool valid = false;
                 uint64_t stats[4] = {0, 0, 0, 0}; } mesh;
+  // mesh streaming (tsdf_mesh_stream): the mesh of every frame, packed, through a ring like the read-out's.  A slot's buffers start with the frame's 64-byte
+  // MeshStreamHeader, the payload (packed vertices, then triangles) follows.  Events: header_written (context's stream, behind the header launch: the copy
+  // stream's header copy waits for it), emitted (context's stream, behind the emit: the payload copy waits for it), header_ready / ready (copy stream, behind
+  // the header / payload copy).  payload_issued: a later call has seen the header on the host and queued the payload copy (or found nothing to copy);
+  // payload_bytes what it queued.  One persistent set of scratch serves every frame: the mesh launches of consecutive frames follow each other on the
+  // context's stream.  head / count / held as in the present ring.  Allocated by the first tsdf_mesh_stream after a config or a new grid.
+  struct MeshStreamSlot { uint8_t* dev = nullptr; uint8_t* host = nullptr; hipEvent_t header_written = nullptr, emitted = nullptr, header_ready = nullptr, ready = nullptr;
+                          uint64_t tag = 0; size_t payload_bytes = 0; bool payload_issued = false; int res[3] = {0, 0, 0}; };
+  struct MeshStream {
+    static constexpr uint32_t kMaxSlots = 8;
+    MeshStreamSlot ring[kMaxSlots];
+    MeshScratch scratch{}; uint32_t* records = nullptr;
+    uint32_t flags = 0, max_vertices = 0, max_triangles = 0, max_tiles = 0, slots = 0, head = 0, count = 0;
+    bool configured = false, allocated = false, held = false;
+    uint64_t frames = 0, overflowed = 0, bytes_copied = 0, device_bytes = 0;
+  } mstream;
   bool have_volume = false;          // integrate() or tsdf_upload_volume has written the volume since it was set up (what the mesh extraction may read)
   // flags (recon_integration.cpp:54-57)
   bool fill_holes = true, use_bricks = true, skip_space = true;

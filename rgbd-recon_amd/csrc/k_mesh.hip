@@ -270,14 +270,91 @@ __global__ __launch_bounds__(kMeshThreads) void k_mesh_vertices(Volume V, Stream
   }
 }
 
+// ... and the streamed form (tsdf_mesh_stream): k_mesh_vertices' text up to the vertex's unit-cube position u, word for word (the extraction keeps its
+// kernel untouched, so the two are written out twice), then the same vertices, quantised in registers and written with ONE 8- or 16-byte store each -- no fp32
+// position, normal or colour exists in memory.  H is the frame's header in device memory (k_mesh_stream_header): when a need exceeds its capacity
+// every workgroup of both emit kernels returns before it reads anything else, so nothing is ever written past a capacity.
+__device__ __forceinline__ bool mesh_stream_overflow(const MeshStreamHeader* __restrict__ H) {
+  return H->needed_vertices > H->max_vertices || H->needed_triangles > H->max_triangles || H->needed_tiles > H->max_tiles;
+}
+__device__ __forceinline__ uint32_t unorm16(float u) { return (uint32_t)__float2int_rn(fminf(fmaxf(u, 0.0f), 1.0f) * 65535.0f); }
+__device__ __forceinline__ uint32_t snorm16(float p) { return (uint32_t)__float2int_rn(fminf(fmaxf(p, -1.0f), 1.0f) * 32767.0f) & 0xffffu; }
+// tsdf_present's RGBA8 rule (k_present.hip: unorm8): the clamp maps NaN to 0
+__device__ __forceinline__ uint32_t mesh_unorm8(float v) { return (uint32_t)__float2int_rn(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f); }
+// octahedral code of a unit normal, two int16; a NaN component: (-32768, -32768)
+__device__ __forceinline__ uint32_t mesh_oct_normal(float3 n) {
+  if (n.x != n.x || n.y != n.y || n.z != n.z) return 0x80008000u;
+  const float s = (fabsf(n.x) + fabsf(n.y)) + fabsf(n.z);
+  float px = n.x / s, py = n.y / s;
+  if (n.z < 0.0f) {
+    const float fx = (1.0f - fabsf(py)) * (px >= 0.0f ? 1.0f : -1.0f), fy = (1.0f - fabsf(px)) * (py >= 0.0f ? 1.0f : -1.0f);
+    px = fx; py = fy;
+  }
+  return snorm16(px) | (snorm16(py) << 16);
+}
+template <bool kSparse, uint32_t kFlags>
+__global__ __launch_bounds__(kMeshThreads, 4) void k_mesh_vertices_packed(Volume V, StreamTable T, FrameImages F, MeshGeometry G, const MeshStreamHeader* __restrict__ H,
+                                                                          const uint2* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_vbase,
+                                                                          const uint32_t* __restrict__ tile_rec, uint32_t* __restrict__ records, void* __restrict__ out) {
+  __shared__ float s_f[kMeshCorners];
+  __shared__ uint32_t s_wave[kMeshWaves];
+  __shared__ uint16_t s_edge[kMeshThreads * 7];                        // per vertex of the tile: lattice point << 3 | d
+  const MeshTile t = mesh_tile(V);
+  const uint32_t nv = tile_cnt[t.id].x;                                // (read beside the header, not behind it: one wait for both; tile_cnt is valid on overflow too)
+  if (mesh_stream_overflow(H) || nv == 0) return;
+  mesh_stage<kSparse>(V, t, s_f);
+  __syncthreads();
+  const MeshPoint p = mesh_point(V, t, s_f, threadIdx.x);
+  uint32_t total;
+  const uint32_t off = block_exclusive_sum<kMeshWaves>((uint32_t)__popc(p.mask), s_wave, &total);
+  records[(size_t)tile_rec[t.id] * kMeshThreads + threadIdx.x] = p.mask | (p.inside << 7) | (off << 8);   // (tile_rec < needed_tiles <= max_tiles)
+  {
+    uint32_t k = off;
+#pragma unroll
+    for (int d = 1; d < 8; ++d)
+      if (p.mask & (1u << (d - 1))) s_edge[k++] = (uint16_t)((threadIdx.x << 3) | d);
+  }
+  __syncthreads();
+  const float ex = G.bbox_max[0] - G.bbox_min[0], ey = G.bbox_max[1] - G.bbox_min[1], ez = G.bbox_max[2] - G.bbox_min[2];
+  const float limit = V.limit, sd = limit * 0.5f;
+  for (uint32_t v = threadIdx.x; v < nv; v += kMeshThreads) {
+    const int e = s_edge[v], lane = e >> 3, d = e & 7;
+    const int lx = lane & 7, ly = (lane >> 3) & 7, lz = lane >> 6;
+    const int bx = d & 1, by = (d >> 1) & 1, bz = d >> 2;
+    const float a = s_f[corner_index(lx, ly, lz)], b = s_f[corner_index(lx + bx, ly + by, lz + bz)];
+    const float w = a / (a - b);
+    const int x = t.tx * 8 + lx, y = t.ty * 8 + ly, z = t.tz * 8 + lz;
+    const float upx = ((float)x + 0.5f) / (float)V.res[0], uqx = ((float)(x + bx) + 0.5f) / (float)V.res[0];
+    const float upy = ((float)y + 0.5f) / (float)V.res[1], uqy = ((float)(y + by) + 0.5f) / (float)V.res[1];
+    const float upz = ((float)z + 0.5f) / (float)V.res[2], uqz = ((float)(z + bz) + 0.5f) / (float)V.res[2];
+    const float3 u = make_float3(upx + w * (uqx - upx), upy + w * (uqy - upy), upz + w * (uqz - upz));
+    const size_t o = (size_t)tile_vbase[t.id] + v;                     // (< needed_vertices <= max_vertices)
+    const uint2 pos = make_uint2(unorm16(u.x) | (unorm16(u.y) << 16), unorm16(u.z));
+    if (kFlags == 0u) { ((uint2*)out)[o] = pos; continue; }
+    uint32_t nrm = 0u, col = 0u;
+    if (kFlags & 1u) {
+      const float gx = tex3d_tsdf<kSparse>(V, u.x + sd, u.y, u.z) - tex3d_tsdf<kSparse>(V, u.x - sd, u.y, u.z);
+      const float gy = tex3d_tsdf<kSparse>(V, u.x, u.y + sd, u.z) - tex3d_tsdf<kSparse>(V, u.x, u.y - sd, u.z);
+      const float gz = tex3d_tsdf<kSparse>(V, u.x, u.y, u.z + sd) - tex3d_tsdf<kSparse>(V, u.x, u.y, u.z - sd);
+      const float3 gn = normalize3(make_float3(gx, gy, gz));
+      nrm = mesh_oct_normal(normalize3(make_float3(-gn.x / ex, -gn.y / ey, -gn.z / ez)));
+    }
+    if (kFlags & 2u) {
+      const float4 c = blend_colors(T, F, limit, u);
+      col = mesh_unorm8(c.x) | (mesh_unorm8(c.y) << 8) | (mesh_unorm8(c.z) << 16) | (mesh_unorm8(c.w) << 24);
+    }
+    ((uint4*)out)[o] = make_uint4(pos.x, pos.y, nrm, col);
+  }
+}
+
 // ---- 4. triangles, from the records alone
 __device__ __forceinline__ uint32_t edge_vertex(const uint32_t* s_first, const uint8_t* s_mask, int lx, int ly, int lz, int x, int y) {   // corners x < y of the cell at (lx, ly, lz)
   const int i = corner_index(lx + (x & 1), ly + ((x >> 1) & 1), lz + (x >> 2)), d = y - x;
   return s_first[i] + (uint32_t)__popc((uint32_t)s_mask[i] & ((1u << (d - 1)) - 1u));
 }
-__global__ __launch_bounds__(kMeshThreads) void k_mesh_triangles(Volume V, const uint2* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_vbase,
-                                                                 const unsigned long long* __restrict__ tile_tbase, const uint32_t* __restrict__ tile_rec,
-                                                                 const uint32_t* __restrict__ records, uint32_t* __restrict__ out_tri) {
+__device__ __forceinline__ void mesh_tile_triangles(const Volume& V, const uint2* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_vbase,
+                                                    const unsigned long long* __restrict__ tile_tbase, const uint32_t* __restrict__ tile_rec,
+                                                    const uint32_t* __restrict__ records, uint32_t* __restrict__ out_tri) {
   __shared__ uint32_t s_first[kMeshCorners];                           // per corner: the mesh index of the first vertex it owns
   __shared__ uint8_t s_mask[kMeshCorners];                             // ... and its record's low byte (edge mask, inside bit)
   __shared__ uint32_t s_wave[kMeshWaves];
@@ -340,6 +417,29 @@ __global__ __launch_bounds__(kMeshThreads) void k_mesh_triangles(Volume V, const
     }
   }
 }
+__global__ __launch_bounds__(kMeshThreads) void k_mesh_triangles(Volume V, const uint2* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_vbase,
+                                                                 const unsigned long long* __restrict__ tile_tbase, const uint32_t* __restrict__ tile_rec,
+                                                                 const uint32_t* __restrict__ records, uint32_t* __restrict__ out_tri) {
+  mesh_tile_triangles(V, tile_cnt, tile_vbase, tile_tbase, tile_rec, records, out_tri);
+}
+// the streamed form: the triangle array follows the frame's vertices directly (payload + needed_vertices * stride: one copy takes both)
+__global__ __launch_bounds__(kMeshThreads) void k_mesh_triangles_stream(Volume V, const MeshStreamHeader* __restrict__ H, const uint2* __restrict__ tile_cnt,
+                                                                        const uint32_t* __restrict__ tile_vbase, const unsigned long long* __restrict__ tile_tbase,
+                                                                        const uint32_t* __restrict__ tile_rec, const uint32_t* __restrict__ records,
+                                                                        uint8_t* __restrict__ payload, uint32_t stride) {
+  if (mesh_stream_overflow(H)) return;
+  mesh_tile_triangles(V, tile_cnt, tile_vbase, tile_tbase, tile_rec, records, (uint32_t*)(payload + (size_t)H->needed_vertices * stride));
+}
+// one lane: the frame's header from the scan's totals (sums[nb]) and the ring's capacities
+__global__ void k_mesh_stream_header(const MeshSums* __restrict__ totals, MeshStreamHeader* __restrict__ H, uint32_t max_vertices, uint32_t max_triangles, uint32_t max_tiles) {
+  const MeshSums s = *totals;
+  MeshStreamHeader h{};
+  h.needed_vertices = s.nv; h.needed_triangles = s.nt; h.needed_tiles = s.surface; h.tiles_skipped = s.skipped;
+  h.max_vertices = max_vertices; h.max_triangles = max_triangles; h.max_tiles = max_tiles;
+  h.overflow = (s.nv > max_vertices ? 1u : 0u) | (s.nt > max_triangles ? 2u : 0u) | (s.surface > max_tiles ? 4u : 0u);
+  h.n_vertices = h.overflow ? 0ull : s.nv; h.n_triangles = h.overflow ? 0ull : s.nt;
+  *H = h;
+}
 
 // ---- launchers
 int mesh_scan_blocks(int n_tiles) { return (n_tiles + kScanPerBlock - 1) / kScanPerBlock; }
@@ -359,6 +459,30 @@ void launch_mesh_emit(hipStream_t st, const Volume& V, const StreamTable& T, con
   if (V.slot) hipLaunchKernelGGL(k_mesh_vertices<true>, dim3(S.n_tiles), dim3(kMeshThreads), 0, st, V, T, F, G, S.tile_cnt, S.tile_vbase, S.tile_rec, records, pos, nrm, (float4*)col);
   else hipLaunchKernelGGL(k_mesh_vertices<false>, dim3(S.n_tiles), dim3(kMeshThreads), 0, st, V, T, F, G, S.tile_cnt, S.tile_vbase, S.tile_rec, records, pos, nrm, (float4*)col);
   hipLaunchKernelGGL(k_mesh_triangles, dim3(S.n_tiles), dim3(kMeshThreads), 0, st, V, S.tile_cnt, S.tile_vbase, S.tile_tbase, S.tile_rec, records, tri);
+}
+
+// the streamed form's emit: header, packed vertices, triangles.  payload: max_vertices * stride + max_triangles * 12 bytes; records: 512 words for each
+// of max_tiles tiles.  A lattice thinner than 2 on an axis has no cell: the caller launches nothing but the header then (S.n_tiles == 0 is not a case).
+void launch_mesh_stream_header(hipStream_t st, const MeshScratch& S, MeshStreamHeader* H, uint32_t max_vertices, uint32_t max_triangles, uint32_t max_tiles) {
+  hipLaunchKernelGGL(k_mesh_stream_header, dim3(1), dim3(1), 0, st, (const MeshSums*)S.sums + mesh_scan_blocks(S.n_tiles), H, max_vertices, max_triangles, max_tiles);
+}
+template <bool kSparse>
+static void launch_vertices_packed(hipStream_t st, uint32_t flags, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S,
+                                   const MeshStreamHeader* H, uint32_t* records, void* payload) {
+  const dim3 g(S.n_tiles), b(kMeshThreads);
+  switch (flags & 3u) {
+    case 0u: hipLaunchKernelGGL((k_mesh_vertices_packed<kSparse, 0u>), g, b, 0, st, V, T, F, G, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
+    case 1u: hipLaunchKernelGGL((k_mesh_vertices_packed<kSparse, 1u>), g, b, 0, st, V, T, F, G, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
+    case 2u: hipLaunchKernelGGL((k_mesh_vertices_packed<kSparse, 2u>), g, b, 0, st, V, T, F, G, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
+    default: hipLaunchKernelGGL((k_mesh_vertices_packed<kSparse, 3u>), g, b, 0, st, V, T, F, G, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
+  }
+}
+void launch_mesh_stream_emit(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S, uint32_t flags,
+                             const MeshStreamHeader* H, uint32_t* records, void* payload) {
+  if (V.slot) launch_vertices_packed<true>(st, flags, V, T, F, G, S, H, records, payload);
+  else launch_vertices_packed<false>(st, flags, V, T, F, G, S, H, records, payload);
+  hipLaunchKernelGGL(k_mesh_triangles_stream, dim3(S.n_tiles), dim3(kMeshThreads), 0, st, V, H, S.tile_cnt, S.tile_vbase, S.tile_tbase, S.tile_rec, records, (uint8_t*)payload,
+                     flags ? 16u : 8u);
 }
 
 }  // namespace rr

@@ -359,6 +359,17 @@ void launch_mesh_scan(hipStream_t st, const MeshScratch& S);   // three launches
 // records: 512 words per tile with surface; nrm / col may be null (attribute not wanted; T and F are read for colours only)
 void launch_mesh_emit(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S, uint32_t* records,
                       float* pos, float* nrm, float* col, uint32_t* tri);
+// mesh streaming (tsdf_mesh_stream): a frame's header as k_mesh_stream_header leaves it in the slot's device buffer, and as the copy stream brings it to
+// the host -- 64 bytes in front of the payload.  The emit kernels read the needs and the capacities from it and return at once when one is exceeded.
+struct MeshStreamHeader {
+  unsigned long long needed_vertices, needed_triangles, needed_tiles, n_vertices, n_triangles, tiles_skipped;
+  uint32_t max_vertices, max_triangles, max_tiles, overflow;
+};
+static_assert(sizeof(MeshStreamHeader) == 64, "the payload follows the header at a 64-byte offset");
+void launch_mesh_stream_header(hipStream_t st, const MeshScratch& S, MeshStreamHeader* H, uint32_t max_vertices, uint32_t max_triangles, uint32_t max_tiles);
+// flags: TSDF_MESH_NORMALS | TSDF_MESH_COLOURS; payload: packed vertices (8 bytes each, 16 with a flag), then the triangles
+void launch_mesh_stream_emit(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S, uint32_t flags,
+                             const MeshStreamHeader* H, uint32_t* records, void* payload);
 void launch_clear_image(hipStream_t st, float4* color, float* depth, size_t n, float4 c, float d);
 void launch_export_partial(hipStream_t st, const RayTarget& R, int w, int h, void* dst);
 void launch_composite(hipStream_t st, const void* gathered, int n, const RayTarget& R, int w, int h);

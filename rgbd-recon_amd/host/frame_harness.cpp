@@ -12,6 +12,9 @@
 // Option --mesh FILE.ply: after the last frame, the fused surface is extracted as a triangle mesh with normals and colours (extractMesh) and written to
 // FILE.ply; the counts are printed and the downloaded arrays must have their sizes.  (This scene's TSDF is positive everywhere: the mesh is empty, the file
 // a header.)
+// Option --mesh-stream: five more draws of the frame, each followed by streamMesh (packed vertices with normals and colours into a 3-slot ring), the
+// frames picked up two frames late and the last two after the loop; tags must come back in order, no frame may overflow, and every frame's counts
+// must equal those of extractMesh on the same volume (zero for this scene).
 //   g++ -std=c++17 frame_harness.cpp -o frame_harness -L.. -lrgbd_recon_hip -Wl,-rpath,'$ORIGIN/..'
 #include <cmath>
 #include <cstdio>
@@ -27,6 +30,7 @@ int main(int argc, char** argv) {
   float view_width = 0.0f;
   int present_format = -1;
   const char* mesh_path = nullptr;
+  bool mesh_stream = false;
   for (int a = 1; a < argc; ++a) {
     if (std::strcmp(argv[a], "--draw-bricks") == 0) draw_bricks = true;
     else if (std::strcmp(argv[a], "--sensor-view") == 0 && a + 2 < argc) { view_type = std::atoi(argv[a + 1]); view_width = (float)std::atof(argv[a + 2]); a += 2; }
@@ -34,7 +38,8 @@ int main(int argc, char** argv) {
       present_format = std::strcmp(argv[a + 1], "dxt1") == 0 ? (int)TSDF_PRESENT_DXT1 : (int)TSDF_PRESENT_RGBA8; a += 1;
     }
     else if (std::strcmp(argv[a], "--mesh") == 0 && a + 1 < argc) { mesh_path = argv[a + 1]; a += 1; }
-    else { std::fprintf(stderr, "usage: frame_harness [--draw-bricks] [--sensor-view TYPE WIDTH] [--present rgba8|dxt1] [--mesh FILE.ply]\n"); return 1; }
+    else if (std::strcmp(argv[a], "--mesh-stream") == 0) mesh_stream = true;
+    else { std::fprintf(stderr, "usage: frame_harness [--draw-bricks] [--sensor-view TYPE WIDTH] [--present rgba8|dxt1] [--mesh FILE.ply] [--mesh-stream]\n"); return 1; }
   }
   kinect::ReconInputs in;
   in.num_kinects = 1;
@@ -135,6 +140,29 @@ int main(int argc, char** argv) {
       recon.writeMeshPly(mesh_path);
       std::printf("mesh: %llu vertices, %llu triangles -> %s\n", (unsigned long long)n.vertices, (unsigned long long)n.triangles, mesh_path);
       if (mesh.position.size() != n.vertices * 3 || mesh.normal.size() != n.vertices * 3 || mesh.colour.size() != n.vertices * 4 || mesh.triangles.size() != n.triangles * 3) return 1;
+    }
+    if (mesh_stream) {
+      const kinect::ReconIntegrationHip::MeshCounts n = recon.extractMesh(false, false);
+      recon.configureMeshStream(true, true, 4096, 8192, 64, 3);
+      const int frames = 5, lag = 2;
+      int got = 0, wrong = 0;
+      auto take = [&](std::uint64_t want_tag) {
+        tsdf_mesh_frame fr;
+        if (!recon.acquireMeshFrame(fr)) { ++wrong; return; }
+        const bool ok = fr.tag == want_tag && fr.overflow == 0 && fr.vertex_stride == 16 && fr.n_vertices == n.vertices && fr.n_triangles == n.triangles &&
+                        fr.needed_vertices == n.vertices && fr.res[0] == 16;
+        recon.releaseMeshFrame();                                              // (before it is counted: a held frame would fail every later acquire too)
+        ++(ok ? got : wrong);
+      };
+      for (int f = 0; f < frames; ++f) {
+        recon.drawF();
+        if (!recon.streamMesh((std::uint64_t)(200 + f))) ++wrong;
+        if (f >= lag) take((std::uint64_t)(200 + f - lag));
+      }
+      for (int f = frames - lag; f < frames; ++f) take((std::uint64_t)(200 + f));
+      const kinect::ReconIntegrationHip::MeshStreamStats st = recon.meshStreamStats();
+      std::printf("%d mesh frames streamed, %d picked up in order, %d mismatches, %llu payload bytes\n", frames, got, wrong, (unsigned long long)st.payload_bytes);
+      if (got != frames || wrong != 0 || st.frames != (std::uint64_t)frames || st.payload_bytes != (std::uint64_t)frames * (n.vertices * 16 + n.triangles * 12)) return 1;
     }
     return band > 0 ? 0 : 1;
   } catch (std::exception const& e) {

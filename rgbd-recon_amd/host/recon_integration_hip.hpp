@@ -186,6 +186,36 @@ class ReconIntegrationHip {
                              out.triangles.data()));
   }
   void writeMeshPly(const char* path) { check(tsdf_mesh_write_ply(m_ctx, path)); }
+  // ---- the same surface EVERY frame (tsdf_mesh_stream): packed vertices and uint32 triangles through a ring of pinned buffers, queued behind the frame
+  // like present().  The reference has no counterpart.  configureMeshStream before the first frame: attributes, capacities (vertices, triangles, 8^3
+  // tiles with surface; a frame that needs more comes back with overflow set and no geometry) and 2..8 slots.
+  struct MeshStreamStats { std::uint64_t frames = 0, overflowed = 0, payload_bytes = 0, device_bytes = 0; };
+  void configureMeshStream(bool normals, bool colours, unsigned max_vertices, unsigned max_triangles, unsigned max_surface_tiles, unsigned slots = 3) {
+    check(tsdf_mesh_stream_config(m_ctx, (normals ? TSDF_MESH_NORMALS : 0u) | (colours ? TSDF_MESH_COLOURS : 0u), max_vertices, max_triangles, max_surface_tiles, slots));
+  }
+  // after drawF(): never blocks; false = every slot is queued or held (or there is no volume yet), nothing was queued
+  bool streamMesh(std::uint64_t tag) {
+    const int32_t rc = tsdf_mesh_stream(m_ctx, tag);
+    if (rc == TSDF_ERR_STATE) return false;
+    check(rc);
+    return true;
+  }
+  // the oldest streamed frame not yet released: false while it is not complete on the host (wait = false) or nothing is queued; out's pointers stay
+  // valid until releaseMeshFrame()
+  bool acquireMeshFrame(tsdf_mesh_frame& out, bool wait = true) {
+    out = tsdf_mesh_frame{};
+    int32_t ready = 0;
+    const int32_t rc = tsdf_mesh_stream_acquire(m_ctx, wait ? 1 : 0, &out, &ready);
+    if (rc == TSDF_ERR_STATE) return false;
+    check(rc);
+    return ready != 0;
+  }
+  void releaseMeshFrame() { check(tsdf_mesh_stream_release(m_ctx)); }
+  MeshStreamStats meshStreamStats() {
+    std::uint64_t s[4];
+    check(tsdf_mesh_stream_stats(m_ctx, s));
+    return MeshStreamStats{s[0], s[1], s[2], s[3]};
+  }
   // ---- kinect::ReconPoints::draw() (recon_points.cpp:71-111) on the same inputs: the point back-end for A/B comparison
   void uploadNormals(const float* normals_rgb) { check(tsdf_upload_normals(m_ctx, normals_rgb)); }
   void drawPoints() { check(tsdf_draw_points(m_ctx, m_mv, m_proj)); }
