@@ -75,13 +75,12 @@ Mat4 to_mat4(const double* d) { Mat4 r; for (int i = 0; i < 16; ++i) r.m[i] = (f
 void release_view(tsdf_ctx* c) {
   for (int k = 0; k < 2; ++k) { hipFree(c->atlas_color[k]); hipFree(c->atlas_depth[k]); c->atlas_color[k] = nullptr; c->atlas_depth[k] = nullptr; }
   c->atlas_parity = 0;
-  hipFree(c->d_peels); hipFree(c->d_peels_alt); c->d_peels_alt = nullptr; c->last_alt_peels = false; hipFree(c->d_nsamples); hipFree(c->d_fb_c); hipFree(c->d_fb_d);
+  hipFree(c->d_peels); hipFree(c->d_peels_alt); c->d_peels_alt = nullptr; hipFree(c->d_nsamples); hipFree(c->d_fb_c); hipFree(c->d_fb_d);
   hipFree(c->d_long); c->d_long = nullptr;
   hipFree(c->d_tri_z); hipFree(c->d_tri_acc); c->d_tri_z = nullptr; c->d_tri_acc = nullptr;
   for (int k = 0; k < 3; ++k) { hipFree(c->d_touched[k]); c->d_touched[k] = nullptr; }
   for (int k = 0; k < 2; ++k) { hipFree(c->d_fill_mask[k]); hipFree(c->d_lvl_mask[k]); c->d_fill_mask[k] = nullptr; c->d_lvl_mask[k] = nullptr; }
-  c->draw_masks_valid = false; c->fb_consistent = false; c->tex_atlas_ok = false; c->tex_limits_ok = false;
-  c->tile_history = false; c->touched_idx = 0;
+  c->tiles_img.reset();
   hipFree(c->d_hits); hipFree(c->d_hit_counters); hipFree(c->d_comp_key); c->d_hits = nullptr; c->d_hit_counters = nullptr; c->d_comp_key = nullptr;
   c->atlas.color = nullptr; c->atlas.depth = nullptr; c->d_peels = nullptr; c->d_nsamples = nullptr; c->d_fb_c = nullptr; c->d_fb_d = nullptr;
 }
@@ -137,15 +136,13 @@ int32_t setup_view(tsdf_ctx* c, uint32_t w, uint32_t h) {
   const size_t n_img_tiles = (size_t)((c->vw + 7) / 8) * ((c->vh + 7) / 8);
   for (int k = 0; k < 3; ++k) { HIP_TRY(c, hipMalloc(&c->d_touched[k], n_img_tiles)); HIP_TRY(c, hipMemsetAsync(c->d_touched[k], 0, n_img_tiles, c->stream)); }
   for (int k = 0; k < 2; ++k) { HIP_TRY(c, hipMalloc(&c->d_fill_mask[k], n_img_tiles)); HIP_TRY(c, hipMalloc(&c->d_lvl_mask[k], n_img_tiles)); }
-  c->draw_masks_valid = false; c->fb_consistent = false;
-  if (const char* e = getenv("RR_FILL_TILES")) c->fill_tiles = atoi(e) != 0;          // A/B and test hook
-  c->tile_history = false; c->touched_idx = 0;
+  if (const char* e = getenv("RR_FILL_TILES")) c->tiles_img.fill_tiles = atoi(e) != 0;          // A/B and test hook
   HIP_TRY(c, hipMalloc(&c->d_hit_counters, 4 * sizeof(uint32_t)));
   HIP_TRY(c, hipMemsetAsync(c->d_hit_counters, 0, 4 * sizeof(uint32_t), c->stream));
   if (const char* e = getenv("RR_MARCH_CAP")) c->march_cap = (uint32_t)atoi(e);
   if (const char* e = getenv("RR_MARCH_BOX")) c->march_box = atoi(e);
   if (const char* e = getenv("RR_K1_FORM")) c->k1_form_cap = atoi(e);     // A/B and test hook, read when the context is created
-  if (const char* e = getenv("RR_IMAGE_TILES")) c->use_tile_history = atoi(e) != 0;
+  if (const char* e = getenv("RR_IMAGE_TILES")) c->tiles_img.use_history = atoi(e) != 0;
   c->hit_parity = 0;
   c->own_miss_counts = false;
   // the atlas starts as ViewLod::enable() leaves it (colour (0,1,0,0), depth 1); regions no kernel writes keep that
@@ -360,6 +357,12 @@ hipError_t join_fill_of(tsdf_ctx* c, int pyramid) {
 hipError_t join_fill(tsdf_ctx* c) {
   const hipError_t a = join_fill_of(c, 0), b = join_fill_of(c, 1);
   return a != hipSuccess ? a : b;
+}
+// the one doorway of whoever writes the framebuffer beside the hole filling (the point / triangle draws, the overlays, the texture views): wait for
+// the hole filling in flight, and tell the tile history that the framebuffer is no longer the hole filling's alone (image_tiles.hpp)
+static hipError_t begin_framebuffer_write(tsdf_ctx* c) {
+  c->tiles_img.framebuffer_written();
+  return join_fill(c);
 }
 // ---- the lane ahead (see tsdf_ctx::pre_stream)
 bool pipelined(const tsdf_ctx* c) { return c->overlap_fill && !c->pipeline_blocked; }
@@ -1488,10 +1491,9 @@ int32_t tsdf_mark_bricks(tsdf_ctx* c) {
   // the peel tiles the coming draw would reset first -- those the draw before the previous one touched, in the peel image that draw used (two alternate
   // while the lanes are on) --: reset here, on the lane ahead, beside the previous frame's kernels
   PeelClear pc{};
-  if (lane != c->stream && c->use_bricks && c->skip_space && c->use_tile_history && c->tile_history && c->last_alt_peels && c->d_peels_alt) {
-    pc.peels = (uint4*)c->d_peels_alt; pc.touched_prev = c->d_touched[(c->touched_idx + 1) % 3];
+  if (const int m = c->tiles_img.peel_reset_ahead(lane != c->stream && c->use_bricks && c->skip_space && c->d_peels_alt); m >= 0) {
+    pc.peels = (uint4*)c->d_peels_alt; pc.touched_prev = c->d_touched[m];
     pc.w = c->vw; pc.h = c->vh; pc.ntx = (c->vw + 7) / 8; pc.n_tiles = pc.ntx * ((c->vh + 7) / 8);
-    c->peels_cleared = true;
   }
   launch_mark_bricks(lane, c->luts, c->frame, c->br, zero_word, pc.peels ? &pc : nullptr);
   HIP_TRY(c, hipGetLastError());
@@ -1594,11 +1596,10 @@ int32_t tsdf_integrate(tsdf_ctx* c) {
   PeelClear pc{};
   {
     const bool whole = whole_volume(c);
-    if (!deep && !pipelined(c) && c->use_bricks && !c->full_classify && c->skip_space && whole && c->use_tile_history && c->tile_history && !c->last_alt_peels && c->d_peels) {   // (with the lanes on the reset rides on the lane ahead: tsdf_mark_bricks)
-      pc.peels = (uint4*)c->d_peels; pc.touched_prev = c->d_touched[(c->touched_idx + 2) % 3];     // the previous draw's tiles
-      c->tex_limits_ok = false;                                                                     // (unit 16's image: reset for the coming draw)
+    // (with the lanes on the reset rides on the lane ahead: tsdf_mark_bricks)
+    if (const int m = c->tiles_img.peel_reset_classify(!deep && !pipelined(c) && c->use_bricks && !c->full_classify && c->skip_space && whole && c->d_peels); m >= 0) {
+      pc.peels = (uint4*)c->d_peels; pc.touched_prev = c->d_touched[m];                             // the previous draw's tiles
       pc.w = c->vw; pc.h = c->vh; pc.ntx = (c->vw + 7) / 8; pc.n_tiles = pc.ntx * ((c->vh + 7) / 8);
-      c->peels_cleared = true;
     }
   }
   if (c->use_bricks && !c->full_classify && !c->spare_clean && !pipelined(c)) {   // ... and zero the spare counter buffer for the next clearOccupiedBricks() (the lane ahead clears its own)
@@ -1654,31 +1655,26 @@ static int32_t raymarch_impl(tsdf_ctx* c, const float* mv, const float* pr, bool
   const bool shifted = P.vp_org[0] != 0 || P.vp_org[1] != 0 || P.vp_off[0] != 0.0f || P.vp_off[1] != 0.0f;
   if (shifted && partial) FAIL(c, TSDF_ERR_STATE, "a viewport origin / offset is not available on a slab context (the composite indexes pixels)");
   if (shifted) HIP_TRY(c, hipMemsetAsync(c->d_nsamples, 0, (size_t)c->vw * c->vh * sizeof(float), c->stream));   // clearImage of tex_num_samples, :207-208: the stores land at origin + pixel
+  // what the tile history (image_tiles.hpp) makes of this draw: first the depth limits, ...
   // (slab contexts too: a tile without a brick under it holds clear values after the march AND after a composite into this target --
   // the brick tables are replicated, so no rank can hit there)
-  const bool use_tiles = P.skip && c->use_tile_history && !shifted && !masked_direct(c);
+  ImageTiles& T = c->tiles_img;
+  const ImageTiles::Limits L = T.draw_limits(P.skip != 0, shifted, masked_direct(c), pipelined(c) && c->d_peels_alt);
   if (P.skip) {
     timer_begin(c, "brickdraw");
-    // two peel images alternate per tiled draw while the lanes are on (tsdf_ctx::d_peels_alt); a change of that mode starts a new tile history
-    const bool alt_peels = use_tiles && pipelined(c) && c->d_peels_alt;
-    if (alt_peels != c->last_alt_peels) c->tile_history = false;
-    if (use_tiles && !c->tile_history) {
+    if (L.start_history) {
       const size_t n_img_tiles = (size_t)((c->vw + 7) / 8) * ((c->vh + 7) / 8);
       for (int k = 0; k < 3; ++k) HIP_TRY(c, hipMemsetAsync(c->d_touched[k], 0, n_img_tiles, c->stream));
-      if (alt_peels) launch_clear_peels(c->stream, c->d_peels_alt, c->vw * c->vh);   // (the other image: all clear, like the one this draw resets in full)
-      c->peels_cleared = false;
+      if (L.alt_peels) launch_clear_peels(c->stream, c->d_peels_alt, c->vw * c->vh);   // (the other image: all clear, like the one this draw resets in full)
     }
-    if (alt_peels && c->tile_history) std::swap(c->d_peels, c->d_peels_alt);          // the image of the draw before the previous one: its tiles are in the oldest mask
-    c->last_alt_peels = alt_peels;
-    launch_depth_limits(c->stream, P, c->br, c->d_peels, use_tiles ? c->d_touched[c->touched_idx] : nullptr,
-                        use_tiles && c->tile_history ? c->d_touched[(c->touched_idx + (alt_peels ? 1 : 2)) % 3] : nullptr, use_tiles && c->tile_history && c->peels_cleared ? 1 : 0);
+    if (L.swap_peels) std::swap(c->d_peels, c->d_peels_alt);
+    launch_depth_limits(c->stream, P, c->br, c->d_peels, L.touched_cur >= 0 ? c->d_touched[L.touched_cur] : nullptr,
+                        L.touched_prev >= 0 ? c->d_touched[L.touched_prev] : nullptr, L.already_cleared);
     timer_end(c, "brickdraw");
-    c->tex_limits_ok = true;                                             // drawDepthLimits() rewrote m_view_depth (unit 16)
   }
-  c->peels_cleared = false;                                              // consumed (or void: this draw did its own reset)
   // two pyramids alternate while the hole filling runs beside the next frame (stage overlap): this draw takes the other one and only has
   // to wait for the hole filling of the draw BEFORE the previous one -- long finished -- instead of the previous draw's
-  const bool two_pyramids = c->fill_holes && c->overlap_fill && !masked_direct(c);
+  const bool two_pyramids = ImageTiles::two_pyramids(c->fill_holes, c->overlap_fill, masked_direct(c));
   if (two_pyramids) {
     const int p = c->atlas_parity ^ 1;
     if (!c->atlas_color[p]) {
@@ -1686,31 +1682,22 @@ static int32_t raymarch_impl(tsdf_ctx* c, const float* mv, const float* pr, bool
       HIP_TRY(c, hipMalloc(&c->atlas_color[p], na * sizeof(float4)));
       HIP_TRY(c, hipMalloc(&c->atlas_depth[p], na * sizeof(float)));
       launch_clear_image(c->stream, c->atlas_color[p], c->atlas_depth[p], na, make_float4(0.0f, 1.0f, 0.0f, 0.0f), 1.0f);   // ViewLod::enable's clear
-      c->tile_history = false;
+      T.second_pyramid_allocated();
     }
     c->atlas_parity = p;
     c->atlas.color = c->atlas_color[p]; c->atlas.depth = c->atlas_depth[p];
     HIP_TRY(c, join_fill_of(c, p));
   } else HIP_TRY(c, join_fill(c));                                       // the previous draw's hole filling still reads level 0 / writes the framebuffer
-  if (!c->tile_history) c->tiled_draws = 0;
+  // ... then the march
+  const ImageTiles::March M = T.draw_march(L.use_tiles, two_pyramids, c->fill_holes, masked_direct(c), partial);
   RayTarget RT = ray_target(c);
-  if (use_tiles) {
-    const int cur = c->touched_idx, prev = (cur + 2) % 3, oldest = (cur + 1) % 3;
-    RT.touched_cur = c->d_touched[cur]; RT.touched_prev = c->d_touched[prev];
-    RT.touched_prev_target = c->d_touched[two_pyramids ? oldest : prev];
-    RT.touched_recycle = c->d_touched[oldest];
-    RT.rewrite_all = c->tiled_draws >= 1 ? 0 : 1;
-    RT.rewrite_target = c->tiled_draws >= (two_pyramids ? 2 : 1) ? 0 : 1;
-    // the hole filling of this draw may keep to the tiles of this draw and the two before, once three tiled draws in a row have left
-    // nothing else in the pyramid it fills and in the framebuffer
-    RT.fill_mask = c->fill_holes ? c->d_fill_mask[c->atlas_parity] : nullptr;
-    c->draw_masks_valid = c->fill_holes && c->tiled_draws >= 2 && !partial;
-    c->touched_idx = (cur + 1) % 3;
-    c->tile_history = true;
-    c->tiled_draws = std::min(2, c->tiled_draws + 1);
-  } else { c->tile_history = false; c->draw_masks_valid = false; }
-  if (!c->fill_holes) c->fb_consistent = false;                          // the march (or the masked merge below) writes the framebuffer itself
-  if (c->fill_holes || masked_direct(c)) c->tex_atlas_ok = false;        // level 0 of c->atlas: this march's until its hole filling completes the pyramid
+  if (L.use_tiles) {
+    RT.touched_cur = c->d_touched[M.touched_cur]; RT.touched_prev = c->d_touched[M.touched_prev];
+    RT.touched_prev_target = c->d_touched[M.touched_prev_target];
+    RT.touched_recycle = c->d_touched[M.touched_recycle];
+    RT.rewrite_all = M.rewrite_all; RT.rewrite_target = M.rewrite_target;
+    RT.fill_mask = M.fill_mask ? c->d_fill_mask[c->atlas_parity] : nullptr;
+  }
   HIP_TRY(c, join_integ(c));                                             // the volume: from here on (the depth limits above needed the bricks only)
   const MarchPlan plan = plan_march(partial, P.skip != 0, c->vol.slot != nullptr, c->d_long != nullptr, c->march_cap ? c->march_cap : 0xffffffffu, c->march_box);
   timer_begin(c, "draw");
@@ -1775,8 +1762,7 @@ int32_t tsdf_draw_points(tsdf_ctx* c, const float* mv, const float* pr) {
   F.depth = (float*)c->frame.depth;
   HIP_TRY(c, join_pre(c));
   timer_begin(c, "points");
-  HIP_TRY(c, join_fill(c));
-  c->fb_consistent = false;
+  HIP_TRY(c, begin_framebuffer_write(c));
   launch_draw_points(c->stream, P, Q, c->luts, F, c->d_comp_key, c->d_fb_c, c->d_fb_d);
   timer_end(c, "points");
   if (c->d_normal && pipelined(c)) {                                     // the next tsdf_process_textures() on the lane ahead rewrites the normal image
@@ -1807,8 +1793,7 @@ int32_t tsdf_draw_trigrid(tsdf_ctx* c, const float* mv, const float* pr) {
   if (!c->d_tri_z) { HIP_TRY(c, hipMalloc(&c->d_tri_z, nv * sizeof(uint32_t))); HIP_TRY(c, hipMalloc(&c->d_tri_acc, nv * sizeof(float4))); }
   HIP_TRY(c, join_pre(c));
   timer_begin(c, "trigrid");
-  HIP_TRY(c, join_fill(c));
-  c->fb_consistent = false;
+  HIP_TRY(c, begin_framebuffer_write(c));
   launch_draw_trigrid(c->stream, P, Q, c->luts, c->frame, c->min_length, c->d_tri_z, c->d_tri_acc, c->d_fb_c, c->d_fb_d);
   timer_end(c, "trigrid");
   HIP_TRY(c, hipGetLastError());
@@ -1837,8 +1822,7 @@ int32_t tsdf_draw_mvt(tsdf_ctx* c, const float* mv, const float* pr) {
   if (int32_t rc = flush_pending_colour(c)) return rc;                   // the slot colour of a raw frame nobody has processed yet
   HIP_TRY(c, join_pre(c));
   timer_begin(c, "mvt");
-  HIP_TRY(c, join_fill(c));
-  c->fb_consistent = false;
+  HIP_TRY(c, begin_framebuffer_write(c));
   launch_draw_mvt(c->stream, P, Q, c->luts, c->frame, c->raw_src, c->min_length, c->d_mvt_vtx, c->d_tri_z, c->d_tri_acc, c->d_fb_c, c->d_fb_d);
   timer_end(c, "mvt");
   HIP_TRY(c, hipGetLastError());
@@ -1879,12 +1863,9 @@ static int32_t fill_colors_impl(tsdf_ctx* c, hipStream_t* used) {
     c->draw_pending[c->vol_set] = true; c->draw_unrecorded = false;
     fs = c->fill_stream;
   }
-  const bool by_tiles = c->fill_tiles && c->draw_masks_valid && c->fb_consistent && c->color_mask_mode == 0 && !c->keep_color;
+  const bool by_tiles = c->tiles_img.fill(c->color_mask_mode != 0, c->keep_color);
   const uint8_t* tile_mask = by_tiles ? c->d_fill_mask[c->atlas_parity] : nullptr;
   ++c->n_fills; c->n_fills_by_tiles += by_tiles ? 1 : 0;
-  c->fb_consistent = c->color_mask_mode == 0 && !c->keep_color;         // the framebuffer is this pass's now: background wherever no tile was dirty
-  c->draw_masks_valid = false;                                           // (consumed: a second fillColors() of the same draw, e.g. after a composite, goes through every tile)
-  c->tex_atlas_ok = true;                                                // the texture bound on unit 15 at recon_integration.cpp:315
   if (c->overlap_fill && c->fill_thread && !c->timers_on) {              // the helper thread issues the lane's calls (tsdf_ctx::fill_worker)
     if (!c->fill_worker) {
       c->fill_worker = new tsdf_ctx::FillWorker();
@@ -1983,7 +1964,7 @@ int32_t tsdf_set_stage_overlap(tsdf_ctx* c, int32_t on) {
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, sync_ctx(c));
   c->overlap_fill = on != 0;
-  c->tile_history = false;                                               // one pyramid or two alternating: what the march targets hold changes
+  c->tiles_img.drop_history();                                           // one pyramid or two alternating: what the march targets hold changes
   return TSDF_OK;
 }
 
@@ -2039,10 +2020,9 @@ int32_t tsdf_draw_calibvis(tsdf_ctx* c, const float* mv, const float* pr) {
   // a draw: the volume of the latest integrate() (the set a raymarch issued now would read), the framebuffer after the hole filling
   HIP_TRY(c, join_pre(c));
   HIP_TRY(c, join_integ(c));
-  HIP_TRY(c, join_fill(c));
+  HIP_TRY(c, begin_framebuffer_write(c));
   timer_begin(c, "calibvis");
   HIP_TRY(c, hipMemsetAsync(c->d_calibvis_skipped, 0, sizeof(unsigned long long), c->stream));
-  c->fb_consistent = false;
   launch_draw_calibvis(c->stream, Q, c->vol, c->d_comp_key, c->d_fb_c, c->d_fb_d);
   timer_end(c, "calibvis");
   c->calibvis_points = (uint64_t)Q.gres[0] * Q.gres[1] * Q.gres[2];
@@ -2069,9 +2049,8 @@ int32_t tsdf_draw_frustums(tsdf_ctx* c, const float* mv, const float* pr) {
   Q.view = overlay_view(c, mv, pr);
   Q.n = (int)c->cfg.num_streams;
   HIP_TRY(c, comp_key(c));
-  HIP_TRY(c, join_fill(c));                                              // the hole filling writes the framebuffer from its own lane
+  HIP_TRY(c, begin_framebuffer_write(c));                                // the hole filling writes the framebuffer from its own lane
   timer_begin(c, "frustums");
-  c->fb_consistent = false;
   launch_draw_frustums(c->stream, Q, c->d_comp_key, c->d_fb_c, c->d_fb_d);
   timer_end(c, "frustums");
   HIP_TRY(c, hipGetLastError());
@@ -2086,9 +2065,8 @@ int32_t tsdf_draw_bbox(tsdf_ctx* c, const float* mv, const float* pr) {
   Q.view = overlay_view(c, mv, pr);
   for (int a = 0; a < 3; ++a) { Q.lo[a] = c->cfg.bbox_min[a]; Q.hi[a] = c->cfg.bbox_max[a]; }
   HIP_TRY(c, comp_key(c));
-  HIP_TRY(c, join_fill(c));                                              // the hole filling writes the framebuffer from its own lane
+  HIP_TRY(c, begin_framebuffer_write(c));                                // the hole filling writes the framebuffer from its own lane
   timer_begin(c, "bbox");
-  c->fb_consistent = false;
   launch_draw_bbox(c->stream, Q, c->d_comp_key, c->d_fb_c, c->d_fb_d);
   timer_end(c, "bbox");
   if (int32_t rc = overlay_rerecord_draw(c)) return rc;
@@ -2106,13 +2084,12 @@ static int32_t draw_bricks_impl(tsdf_ctx* c, const float* mv, const float* pr) {
   BrickWireParams Q{};
   Q.view = overlay_view(c, mv, pr);
   HIP_TRY(c, comp_key(c));
-  HIP_TRY(c, join_fill(c));                                              // the hole filling writes the framebuffer from its own lane
+  HIP_TRY(c, begin_framebuffer_write(c));                                // the hole filling writes the framebuffer from its own lane
   // the list of the latest update, from whatever lane ran it.  The join marks the occupancy set as in use by the context's stream, so the
   // next update on the lane ahead takes the other set; the one after that returns to this set behind the lane's gate, which the
   // context's stream records at the next frame's first lane call -- behind this draw, wherever in the frame it was queued.
   HIP_TRY(c, join_pre(c));
   timer_begin(c, "brickwire");
-  c->fb_consistent = false;
   launch_draw_brickwire(c->stream, Q, c->br, c->d_comp_key, c->d_fb_c, c->d_fb_d, plain);
   timer_end(c, "brickwire");
   if (int32_t rc = overlay_rerecord_draw(c)) return rc;
@@ -2136,8 +2113,8 @@ int32_t tsdf_draw_textures(tsdf_ctx* c, uint32_t which) {
   CHECK_CTX(c);
   if (which > 1) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "texture %u: 0 (unit 15, the hole-filling atlas) or 1 (unit 16, the depth-limit image)", which);
   if (int32_t rc = overlay_mono(c)) return rc;
-  if (which == 0 && !c->tex_atlas_ok) FAIL(c, TSDF_ERR_STATE, "unit 15: no hole filling has completed the atlas since the context was created or resized (or a later march rewrote it)");
-  if (which == 1 && !c->tex_limits_ok) FAIL(c, TSDF_ERR_STATE, "unit 16: no draw with space skipping has produced the depth-limit image since the context was created or resized (or an integrate() reset it for the coming draw)");
+  if (which == 0 && !c->tiles_img.atlas_complete()) FAIL(c, TSDF_ERR_STATE, "unit 15: no hole filling has completed the atlas since the context was created or resized (or a later march rewrote it)");
+  if (which == 1 && !c->tiles_img.limits_complete()) FAIL(c, TSDF_ERR_STATE, "unit 16: no draw with space skipping has produced the depth-limit image since the context was created or resized (or an integrate() reset it for the coming draw)");
   HIP_TRY(c, hipSetDevice(c->device));
   BlitParams Q{};
   const float rf_x = (float)(uint32_t)(1.5f * (float)c->vw), rf_y = (float)c->vh;   // ViewLod::resolution_full, view_lod.cpp:29
@@ -2146,9 +2123,8 @@ int32_t tsdf_draw_textures(tsdf_ctx* c, uint32_t which) {
   Q.fw = c->vw;
   if (which == 0) { Q.src = c->atlas.color; Q.peels = 0; Q.sw = c->atlas.aw; Q.sh = c->atlas.h; }
   else { Q.src = c->d_peels; Q.peels = 1; Q.sw = c->vw; Q.sh = c->vh; }
-  HIP_TRY(c, join_fill(c));                                              // the hole filling completes the atlas and writes the framebuffer on its own lane
+  HIP_TRY(c, begin_framebuffer_write(c));                                // the hole filling completes the atlas and writes the framebuffer on its own lane
   timer_begin(c, "textures");
-  c->fb_consistent = false;
   launch_blit_texture(c->stream, Q, c->d_fb_c);
   timer_end(c, "textures");
   HIP_TRY(c, hipGetLastError());
@@ -2216,11 +2192,10 @@ int32_t tsdf_draw_sensor_texture(tsdf_ctx* c, uint32_t type, uint32_t stream, co
       FAIL(c, TSDF_ERR_STATE, "the Lab image is produced on request from the processed frame's inputs, and a newer raw frame has replaced them");
   }
   if (type == 0) { if (int32_t rc = flush_pending_colour(c)) return rc; }
-  HIP_TRY(c, join_fill(c));                                              // the hole filling writes the framebuffer from its own lane
+  HIP_TRY(c, begin_framebuffer_write(c));                                // the hole filling writes the framebuffer from its own lane
   HIP_TRY(c, join_pre(c));                                               // the lane ahead wrote the products and the frame slot
   if (raw && type == 6) { if (int32_t rc = produce_lab(c)) return rc; }
   timer_begin(c, "sensortex");
-  c->fb_consistent = false;
   launch_sensor_texture(c->stream, Q, F, c->d_fb_c);
   timer_end(c, "sensortex");
   // d_depth_b, d_normal, d_depth2, d_lab exist once: the next tsdf_process_textures on the lane ahead waits for this draw (the frame slots alternate behind
@@ -2304,7 +2279,7 @@ int32_t tsdf_set_voxel_size(tsdf_ctx* c, float size) {
 }
 int32_t tsdf_set_use_bricks(tsdf_ctx* c, int32_t a) { CHECK_CTX(c); c->use_bricks = a != 0; return TSDF_OK; }
 int32_t tsdf_set_space_skip(tsdf_ctx* c, int32_t a) { CHECK_CTX(c); c->skip_space = a != 0; return TSDF_OK; }
-int32_t tsdf_set_color_filling(tsdf_ctx* c, int32_t a) { CHECK_CTX(c); c->fill_holes = a != 0; c->tile_history = false; return TSDF_OK; }   // the march target changes
+int32_t tsdf_set_color_filling(tsdf_ctx* c, int32_t a) { CHECK_CTX(c); c->fill_holes = a != 0; c->tiles_img.drop_history(); return TSDF_OK; }   // the march target changes
 int32_t tsdf_set_min_voxels_per_brick(tsdf_ctx* c, uint32_t n) { CHECK_CTX(c); c->min_voxels = n; return TSDF_OK; }
 int32_t tsdf_set_shade_mode(tsdf_ctx* c, int32_t m) {
   CHECK_CTX(c);
@@ -2314,11 +2289,11 @@ int32_t tsdf_set_shade_mode(tsdf_ctx* c, int32_t m) {
 }
 // Reconstruction::setViewportOffset -> uniform viewport_offset (recon_integration.cpp:527); the GL viewport origin is GL state the
 // reference reads implicitly through gl_FragCoord (glViewport(x, y, ..), kinect_client.cpp:650,658)
-int32_t tsdf_set_viewport_offset(tsdf_ctx* c, float x, float y) { CHECK_CTX(c); c->vp_off[0] = x; c->vp_off[1] = y; c->tile_history = false; return TSDF_OK; }
+int32_t tsdf_set_viewport_offset(tsdf_ctx* c, float x, float y) { CHECK_CTX(c); c->vp_off[0] = x; c->vp_off[1] = y; c->tiles_img.drop_history(); return TSDF_OK; }
 int32_t tsdf_set_viewport_origin(tsdf_ctx* c, int32_t x, int32_t y) {
   CHECK_CTX(c);
   if (x < -(1 << 20) || x > (1 << 20) || y < -(1 << 20) || y > (1 << 20)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "viewport origin out of range");
-  c->vp_org[0] = x; c->vp_org[1] = y; c->tile_history = false;
+  c->vp_org[0] = x; c->vp_org[1] = y; c->tiles_img.drop_history();
   return TSDF_OK;
 }
 // Reconstruction::setColorMaskMode (reconstruction.cpp:51-53; used recon_integration.cpp:212-216,321-333) and whether the client
@@ -2327,10 +2302,10 @@ int32_t tsdf_set_viewport_origin(tsdf_ctx* c, int32_t x, int32_t y) {
 int32_t tsdf_set_color_mask_mode(tsdf_ctx* c, uint32_t mode) {
   CHECK_CTX(c);
   if (mode > 2) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "colour mask mode must be 0 (all), 1 (red) or 2 (green + blue)");
-  c->color_mask_mode = mode; c->tile_history = false;
+  c->color_mask_mode = mode; c->tiles_img.drop_history();
   return TSDF_OK;
 }
-int32_t tsdf_set_framebuffer_clear(tsdf_ctx* c, int32_t clear_color) { CHECK_CTX(c); c->keep_color = clear_color == 0; c->tile_history = false; return TSDF_OK; }
+int32_t tsdf_set_framebuffer_clear(tsdf_ctx* c, int32_t clear_color) { CHECK_CTX(c); c->keep_color = clear_color == 0; c->tiles_img.drop_history(); return TSDF_OK; }
 int32_t tsdf_set_brick_size(tsdf_ctx* c, const float size[3]) {
   CHECK_CTX(c);
   if (!size) return TSDF_ERR_INVALID_ARGUMENT;
@@ -2461,8 +2436,7 @@ int32_t tsdf_upload_image(tsdf_ctx* c, const float* rgba, const float* depth) {
   const size_t w = (size_t)c->vw, h = (size_t)c->vh;
   HIP_TRY(c, hipMemcpy2D(R.color, (size_t)R.stride * 16, rgba, w * 16, w * 16, h, hipMemcpyHostToDevice));
   HIP_TRY(c, hipMemcpy2D(R.depth, (size_t)R.stride * 4, depth, w * 4, w * 4, h, hipMemcpyHostToDevice));
-  c->tile_history = false; c->draw_masks_valid = false;                  // the march target no longer holds what the last march left
-  if (c->fill_holes || masked_direct(c)) c->tex_atlas_ok = false;
+  c->tiles_img.target_uploaded(c->fill_holes || masked_direct(c));      // the march target no longer holds what the last march left
   return TSDF_OK;
 }
 int32_t tsdf_download_framebuffer(tsdf_ctx* c, float* rgba, float* depth) {
@@ -2482,7 +2456,7 @@ int32_t tsdf_upload_framebuffer(tsdf_ctx* c, const float* rgba, const float* dep
   const size_t n = (size_t)c->vw * c->vh;
   HIP_TRY(c, hipMemcpy(c->d_fb_c, rgba, n * 16, hipMemcpyHostToDevice));
   HIP_TRY(c, hipMemcpy(c->d_fb_d, depth, n * 4, hipMemcpyHostToDevice));
-  c->fb_consistent = false;                                              // the hole filling may no longer keep to the dirty tiles
+  c->tiles_img.framebuffer_written();                                    // (behind the synchronisation above: nothing to join)
   return TSDF_OK;
 }
 int32_t tsdf_download_atlas(tsdf_ctx* c, float* rgba, float* depth) {
@@ -2905,8 +2879,7 @@ int32_t tsdf_composite_dev(tsdf_ctx* c, const void* gathered, uint32_t n) {
   if (!gathered || n < 1) return TSDF_ERR_INVALID_ARGUMENT;
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, join_fill(c));
-  c->draw_masks_valid = false;                                           // the composite writes every pixel of the march target
-  if (c->fill_holes || masked_direct(c)) c->tex_atlas_ok = false;
+  c->tiles_img.target_composited(c->fill_holes || masked_direct(c));    // the composite writes every pixel of the march target
   launch_composite(c->stream, gathered, (int)n, ray_target(c), c->vw, c->vh);
   HIP_TRY(c, hipGetLastError());
   return TSDF_OK;
@@ -2930,14 +2903,13 @@ int32_t tsdf_composite_hits_dev(tsdf_ctx* c, const void* gathered, uint32_t n, u
   HIP_TRY(c, comp_key(c));
   // a compositing context that did not march this frame (dedicated compositor, multigpu.py) has no miss counts of its own: 0 then
   HIP_TRY(c, join_fill(c));
-  c->draw_masks_valid = false;                                           // the composite writes every pixel of the march target
-  if (c->fill_holes || masked_direct(c)) c->tex_atlas_ok = false;
+  c->tiles_img.target_composited(c->fill_holes || masked_direct(c));    // the composite writes every pixel of the march target
   launch_composite_hits(c->stream, gathered, (size_t)stride_bytes, (int)n, ray_target(c), c->vw, c->vh, c->d_comp_key, c->own_miss_counts ? 1 : 0);
   HIP_TRY(c, hipGetLastError());
   return TSDF_OK;
 }
 
-int32_t tsdf_set_march_cap(tsdf_ctx* c, uint32_t samples) { CHECK_CTX(c); c->march_cap = samples; c->tile_history = false; return TSDF_OK; }
+int32_t tsdf_set_march_cap(tsdf_ctx* c, uint32_t samples) { CHECK_CTX(c); c->march_cap = samples; c->tiles_img.drop_history(); return TSDF_OK; }
 
 // ---- timers
 int32_t tsdf_enable_timers(tsdf_ctx* c, int32_t a) { CHECK_CTX(c); c->timers_on = a != 0; return TSDF_OK; }

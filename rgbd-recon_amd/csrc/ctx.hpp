@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "tsdf_common.hpp"
+#include "image_tiles.hpp"
 
 using namespace rr;
 
@@ -90,9 +91,6 @@ struct tsdf_ctx {
   // the frustum overlay (tsdf_draw_frustums): per stream the forward LUT's corner samples and Frustum::getCameraPos, captured by tsdf_set_calibration
   float frustum_corner[TSDF_MAX_STREAMS][8][3]{}; float frustum_cam[TSDF_MAX_STREAMS][3]{}; bool have_frustum[TSDF_MAX_STREAMS]{};
   unsigned long long* d_calibvis_skipped = nullptr; uint64_t calibvis_points = 0;   // the TSDF overlay: grid points of the last draw, device count of those the empty-space test removed
-  // the texture view (tsdf_draw_textures): c->atlas is the one the latest hole filling completed (GL's unit 15), d_peels the depth-limit image
-  // of the latest draw with space skipping (unit 16) -- each until something rewrites it
-  bool tex_atlas_ok = false, tex_limits_ok = false;
   // the sensor texture windows (tsdf_draw_sensor_texture) show NetKinectArray's arrays: FrameSlot::origin says whether the current slot's frame was handed
   // over processed, is a raw frame still to be processed, or one tsdf_process_textures has gone through; normals_uploaded: d_normal is tsdf_upload_normals'.
   // products_read is recorded behind a window that read one of the single-buffered products (d_depth2, d_depth_b, d_normal, d_lab): the next
@@ -108,27 +106,18 @@ struct tsdf_ctx {
   int vw = 0, vh = 0;
   Atlas atlas{};
   float4* d_peels = nullptr; float* d_nsamples = nullptr;
-  // While the lanes are on, TWO peel images alternate per (tiled) draw: the one the coming draw uses was last written two draws ago, so its touched tiles can
-  // be reset on the lane ahead (a block range of the brick marking launch, k_mark_bricks) instead of by a launch of its own on the context's stream --
-  // 12 + 6 us of the lane that bounds the frame.  d_peels is the latest draw's (what tsdf_download_image returns)
-  float4* d_peels_alt = nullptr; bool last_alt_peels = false;
+  float4* d_peels_alt = nullptr;   // the second peel image (image_tiles.hpp); d_peels is the latest draw's (what tsdf_download_image returns)
   void* d_hits = nullptr; uint32_t* d_hit_counters = nullptr; int hit_parity = 0;
-  // image-space dirty tiles (k_raymarch.hip): three masks in rotation -- d_touched[touched_idx] is the coming draw's, (idx + 2) % 3 the
-  // previous draw's (peels, sample counts), (idx + 1) % 3 the one before (the other pyramid when two alternate; recycled by the march).
-  // The history is dropped whenever something else writes the march target; tiled_draws = consecutive draws since then (saturates at 2).
-  uint8_t* d_touched[3]{}; int touched_idx = 0; bool tile_history = false; int tiled_draws = 0;
-  // two pyramids, alternating per draw while stage overlap is on (round 3): the march of frame f + 1 writes level 0 of the OTHER one while
-  // the hole filling of frame f still reads this one (the reference's m_view_inpaint / m_view_inpaint2, for another reason: it swaps them
-  // between its transfer passes, recon_integration.cpp:279-338).  c->atlas points at the one the latest draw used.
-  float4* atlas_color[2]{}; float* atlas_depth[2]{}; int atlas_parity = 0;
-  // hole filling by dirty tiles (k_inpaint.hip): per pyramid the tile byte mask the march leaves, scratch masks of levels 1 / 2, and
-  // whether the masks of the latest draw may be trusted / the framebuffer holds the background outside them
-  uint8_t* d_fill_mask[2]{}; uint8_t* d_lvl_mask[2]{}; bool draw_masks_valid = false, fb_consistent = false, fill_tiles = true; uint64_t n_fills = 0, n_fills_by_tiles = 0;
+  // image-space dirty tiles: the state and its protocol are image_tiles.hpp's -- three masks in rotation, two peel images, two pyramids, when
+  // the hole filling may keep to the dirty tiles, what the texture view may show.  Here: the buffers it indexes
+  ImageTiles tiles_img{};
+  uint8_t* d_touched[3]{};
+  float4* atlas_color[2]{}; float* atlas_depth[2]{}; int atlas_parity = 0;   // the two pyramids (round 3); c->atlas points at the one the latest draw used
+  // per pyramid the tile byte mask the march leaves for the hole filling (k_inpaint.hip), and scratch masks of levels 1 / 2
+  uint8_t* d_fill_mask[2]{}; uint8_t* d_lvl_mask[2]{}; uint64_t n_fills = 0, n_fills_by_tiles = 0;
   uint32_t* d_tri_z = nullptr; float4* d_tri_acc = nullptr; float min_length = 0.0125f;   // triangle-grid back-end; KinectCalibrationFile.cpp:96 default
   float2* d_mvt_vtx = nullptr; bool have_mvt = false;   // MVT back-end: the last draw's vertex stage, [N][W+1][H+1] (filtered depth m, lateral quality)
   hipEvent_t raw_read = nullptr; bool raw_read_pending = false;   // recorded behind an MVT draw: the next raw upload on the lane ahead rewrites d_raw
-  bool use_tile_history = true;   // RR_IMAGE_TILES=0 turns it off (A/B)
-  bool peels_cleared = false;     // integrate() already reset the peel tiles the coming draw would reset (part C of k_classify_lists)
   uint32_t* d_pair_masks = nullptr;   // per work item of the integrate launch: this frame's (tile, stream) pair classes (k_pair_masks)
   uint4* d_work_recs = nullptr; bool use_recs = true;   // per work item of the integrate launch: the 16-byte record k_pair_masks leaves for k_integrate_tiles_rec (RR_K1_REC=0: off, A/B)
   float4* d_tile_bounds = nullptr; bool tile_bounds_valid = false;   // static per (stored tile, stream) LUT-box bounds, built on the first dense integrate after a calibration

@@ -4,6 +4,7 @@
     toggled options through ONE context equals a fresh context per frame, bit for bit;
   * two-pass march (rays handed to k_march_long after RR_MARCH_CAP samples) equals the single-pass march bit for bit,
     on frames where rays really are handed over;
+  * every foreign write of the framebuffer forces exactly one full hole-filling pass, against a twin without the shortcuts;
   * at BASELINE.json's full size (512^3 x 4 streams, 1280x720) the same through size-independent properties:
     idempotence, culled == dense inside the occupied bricks, slab partition == whole volume, wire upload == raw upload.
 """
@@ -79,6 +80,68 @@ def test_image_tile_history_equals_fresh_contexts(rr):
         assert_same(a, b, f"step {i}")
         touched_any.append((b["depth"] < 1).sum())
     assert min(touched_any) > 100 and len(set(touched_any)) > 3            # the frames really differ
+
+
+FOREIGN_WRITERS = ["drawPoints", "drawTrigrid", "drawCalibVis", "drawFrustums", "drawBBox", "drawOccupiedBricks", "drawTextures0", "drawTextures1",
+                   "set_framebuffer"]
+
+
+@pytest.fixture(scope="module")
+def tile_scenes(rr):
+    kw = dict(n_streams=3, width=128, height=96, lut_res=24, inv_res=32)
+    return [rr.scene.make_scene(**kw), rr.scene.make_scene(sphere_c=(0.4, 0.7, -0.3), box_c=(-0.5, 1.5, 0.2), **kw)]
+
+
+@pytest.mark.parametrize("overlap", [True, False])
+@pytest.mark.parametrize("writer", FOREIGN_WRITERS)
+def test_foreign_framebuffer_write_forces_one_full_hole_filling(rr, tile_scenes, writer, overlap):
+    """Whoever else writes the framebuffer -- a point or triangle-grid draw, an overlay, the texture view, an uploaded framebuffer -- costs the
+    hole filling exactly one pass through every tile: the pass after it.  A twin without tile history and without hole filling by tiles
+    (RR_IMAGE_TILES=0, RR_FILL_TILES=0) goes through the same calls and must show the same pictures, bit for bit."""
+    w, h = KW["view"]
+    mv, pr = views(rr, w, h)[0]
+    one = rr.ReconIntegrationHip(tile_scenes[0], **KW)
+    with env(RR_IMAGE_TILES=0, RR_FILL_TILES=0):
+        twin = rr.ReconIntegrationHip(tile_scenes[0], **KW)
+    both = (one, twin)
+    for o in both:
+        o.set_stage_overlap(overlap)
+    touched = np.zeros((h, w), bool)
+    n = [0]
+
+    def step(what):
+        for o in both:
+            o.upload_frame(tile_scenes[n[0] % 2]); frame(o, mv, pr)
+        n[0] += 1
+        a, b = outputs(one), outputs(twin)
+        assert_same(a, b, what)
+        np.logical_or(touched, b["depth"] < 1, out=touched)
+
+    for k in range(3):
+        step(f"frame {k}")
+    assert one.fill_stats() == (3, 1)                                       # the third draw of a history is the first to fill by tiles
+    rng = np.random.default_rng(11)
+    image = rng.random((h, w, 4), dtype=np.float32), rng.random((h, w), dtype=np.float32)
+    for o in both:
+        if writer == "drawPoints":
+            o.upload_normals(tile_scenes[0]["normals"]); o.drawPoints(mv, pr)
+        elif writer == "drawTextures0":
+            o.drawTextures(0)
+        elif writer == "drawTextures1":
+            o.drawTextures(1)
+        elif writer == "set_framebuffer":
+            o.set_framebuffer(*image)
+        else:
+            getattr(o, writer)(mv, pr)
+    (ac, ad), (bc, bd) = one.framebuffer(), twin.framebuffer()
+    assert_same(dict(fb_color=ac, fb_depth=ad), dict(fb_color=bc, fb_depth=bd), writer)
+    step("first frame after the write")
+    assert one.fill_stats() == (4, 1)                                       # every tile: the framebuffer held someone else's pixels
+    step("second frame after the write")
+    assert one.fill_stats() == (5, 2)                                       # ... and only that once
+    assert twin.fill_stats() == (5, 0)
+    tiles = touched[:h // 8 * 8, :w // 8 * 8].reshape(h // 8, 8, w // 8, 8).any(axis=(1, 3))
+    assert not tiles.all() and tiles.any()                                  # a tile no draw touched: there a pass by tiles and a full pass can differ
 
 
 def test_two_pass_march_equals_single_pass(rr, small_scene):
