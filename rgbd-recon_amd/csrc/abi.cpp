@@ -250,18 +250,17 @@ int32_t setup_bricks(tsdf_ctx* c, const float req[3]) {
     HIP_TRY(c, hipMalloc(&c->d_counters[k], c->counter_words * sizeof(uint32_t)));
     HIP_TRY(c, hipMemset(c->d_counters[k], 0, c->counter_words * sizeof(uint32_t)));
   }
-  c->counters_cur = 0; c->spare_clean = true;
+  c->ahead.new_brick_grid();
   B.counters = c->d_counters[0];
   if (!c->d_occ_counts) HIP_TRY(c, hipMalloc(&c->d_occ_counts, 3 * sizeof(uint32_t)));
   HIP_TRY(c, hipMemset(c->d_occ_counts, 0, 3 * sizeof(uint32_t)));      // a new grid: no occupied list yet
-  c->occ_counts_stale = false;
-  B.num_occupied = c->d_occ_counts + c->occ_parity;
+  B.num_occupied = c->d_occ_counts + c->ahead.occ_set();
   for (int k = 0; k < 2; ++k) {
     HIP_TRY(c, hipMalloc(&c->d_flags[k], (size_t)B.n));
     HIP_TRY(c, hipMalloc(&c->d_occupied[k], (size_t)B.n * sizeof(uint32_t)));
     HIP_TRY(c, hipMemset(c->d_flags[k], 0, (size_t)B.n));
   }
-  B.flags = c->d_flags[c->occ_parity]; B.occupied = c->d_occupied[c->occ_parity];
+  B.flags = c->d_flags[c->ahead.occ_set()]; B.occupied = c->d_occupied[c->ahead.occ_set()];
   // the fills above run on the NULL stream, asynchronously with respect to the host, and the context's streams are non-blocking: finished
   // before any of them touches the new tables
   HIP_TRY(c, hipDeviceSynchronize());
@@ -364,70 +363,59 @@ static hipError_t begin_framebuffer_write(tsdf_ctx* c) {
   c->tiles_img.framebuffer_written();
   return join_fill(c);
 }
-// ---- the lane ahead (see tsdf_ctx::pre_stream)
-bool pipelined(const tsdf_ctx* c) { return c->overlap_fill && !c->pipeline_blocked; }
+// ---- the lane ahead: its state and protocol are lane_ahead.hpp's (tsdf_ctx::ahead); here the streams, the events and what is queued on them
+bool pipelined(const tsdf_ctx* c) { return c->overlap_fill && !c->ahead.blocked(); }
 inline int alt_of(int x) { return x ^ 1; }
 bool deep_ok(const tsdf_ctx* c);
-// the deferred wait of the gate, now (every lane call that does not defer it itself starts with this)
-static void gate_now(tsdf_ctx* c) {
-  if (!c->gate_wait_pending) return;
-  c->gate_wait_pending = false;
-  hipStreamWaitEvent(c->pre_lane, c->gate_wait_ev, 0);
-}
+static void wait_gate(tsdf_ctx* c, int gate) { if (gate >= 0) hipStreamWaitEvent(c->pre_lane, c->pre_gate[gate], 0); }
 hipStream_t pre_enter(tsdf_ctx* c, bool defer_gate) {
   if (!pipelined(c)) return c->stream;
   if (!c->pre_stream) {                                                   // (a context created with RR_OVERLAP_FILL=0 and switched on later)
     if (hipStreamCreateWithFlags(&c->pre_stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&c->pre_done, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->pre_gate, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->pre_gate_b, hipEventDisableTiming) != hipSuccess) { c->pipeline_blocked = true; return c->stream; }
+        hipEventCreateWithFlags(&c->pre_gate[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->pre_gate[1], hipEventDisableTiming) != hipSuccess) { c->ahead.lane_unavailable(); return c->stream; }
   }
-  if (c->main_since_gate) {                                               // the lane's first call of a new frame
+  if (c->ahead.at_frame_start()) {                                        // the lane's first call of a new frame
     // which stream: the lane ahead's own -- or, with the integrate lane in use, that one: a frame's preparation and its integrate() then
     // follow each other without a cross-stream hand-over (15-35 us each on this machine) at the price of not
     // overlapping the preparation of frame f + 2 with the integrate of frame f + 1
     c->pre_lane = (c->pre_on_integ && deep_ok(c)) ? c->integ_stream : c->pre_stream;
-    hipEvent_t const gate_old = c->gate_flip ? c->pre_gate_b : c->pre_gate, gate_new = c->gate_flip ? c->pre_gate : c->pre_gate_b;
-    if (c->gate_wait_pending) { c->gate_wait_pending = false; hipStreamWaitEvent(c->pre_lane, c->gate_wait_ev, 0); }   // (a deferred wait nobody asked for: never skipped)
-    if (c->pre_gate_recorded) {                                            // (recorded at the previous frame's first call: the consumers of the frame before that)
-      if (defer_gate) { c->gate_wait_pending = true; c->gate_wait_ev = gate_old; }
-      else hipStreamWaitEvent(c->pre_lane, gate_old, 0);
-    }
     // ... on the context's stream, which waits for an integrate() on the fourth lane only when a DRAW joins it.  Frames integrated back to back with no
     // draw in between leave that integrate out of every gate, while it may still read the frame slot / brick counters / occupancy set this frame is about to
     // overwrite (the copies alternate): the lane waits for the integrate lane itself then.  (In the per-frame order upload .. integrate, draw the flag is
     // clear here -- the draw has joined the lane -- and nothing is added.)
-    if (c->integ_pending && c->integ_stream && c->pre_lane != c->integ_stream) {
+    const LaneAhead::Open O = c->ahead.open_frame(defer_gate, c->integ_pending && c->integ_stream && c->pre_lane != c->integ_stream);
+    wait_gate(c, O.overdue);
+    wait_gate(c, O.wait);
+    if (O.wait_integ) {
       hipEventRecord(c->integ_done, c->integ_stream);
       hipStreamWaitEvent(c->pre_lane, c->integ_done, 0);
     }
-    hipEventRecord(gate_new, c->stream);
-    c->gate_flip = !c->gate_flip;
-    c->pre_gate_recorded = true; c->main_since_gate = false;
-    c->slot_flipped = c->counters_flipped = c->occ_flipped = false;
-    c->counters_zeroed = c->occ_count_zeroed = false;
-  } else if (!defer_gate) gate_now(c);
+    hipEventRecord(c->pre_gate[O.record], c->stream);
+  } else wait_gate(c, c->ahead.later_call(defer_gate));
   return c->pre_lane;
 }
-hipError_t pre_leave(tsdf_ctx* c, hipStream_t lane) {
-  if (lane != c->stream) c->pre_pending = true;                          // (the event is recorded once, when a consumer asks: every record costs the lane ~4 us)
-  return hipSuccess;
+void pre_leave(tsdf_ctx* c, hipStream_t lane) { c->ahead.call_queued(lane != c->stream); }
+// a consumer has been queued (LaneAhead::consume); the context's stream, and `also` if given, wait for what the lane holds.  false: it holds nothing
+static bool consume_pre(tsdf_ctx* c, hipStream_t also, hipError_t* e) {
+  *e = hipSuccess;
+  if (!c->ahead.consume()) return false;
+  *e = hipEventRecord(c->pre_done, c->pre_lane);
+  if (*e == hipSuccess && also && also != c->pre_lane) *e = hipStreamWaitEvent(also, c->pre_done, 0);
+  if (*e == hipSuccess) *e = hipStreamWaitEvent(c->stream, c->pre_done, 0);
+  return true;
 }
 hipError_t join_pre(tsdf_ctx* c) {
-  gate_now(c);
-  c->main_since_gate = true;
-  c->slot_in_use = c->counters_in_use = c->occ_in_use = true;
-  if (!c->pre_pending) return hipSuccess;
-  c->pre_pending = false;
-  const hipError_t e = hipEventRecord(c->pre_done, c->pre_lane);
-  return e != hipSuccess ? e : hipStreamWaitEvent(c->stream, c->pre_done, 0);
+  wait_gate(c, c->ahead.take_deferred_gate());
+  hipError_t e;
+  consume_pre(c, nullptr, &e);
+  return e;
 }
 // leave the pipelined mode for good (explicit frame-slot calls, the pre-processing path): drain the lanes, everything on the context's stream from now on
 hipError_t block_pipeline(tsdf_ctx* c) {
-  if (c->pipeline_blocked) return hipSuccess;
-  c->pipeline_blocked = true;
+  if (!c->ahead.block()) return hipSuccess;
   hipError_t e = hipStreamSynchronize(c->stream);
   if (c->pre_stream) { const hipError_t f = hipStreamSynchronize(c->pre_stream); if (e == hipSuccess) e = f; }
   if (c->integ_stream) { const hipError_t f = hipStreamSynchronize(c->integ_stream); if (e == hipSuccess) e = f; c->integ_pending = false; }
-  c->pre_pending = false;
   return e;
 }
 // ---- the fourth lane (see tsdf_ctx::integ_stream)
@@ -509,7 +497,7 @@ static int32_t ensure_proj_cache(tsdf_ctx* c, const ProjCache** proj) {
 hipError_t sync_ctx(tsdf_ctx* c) {
   hipError_t e = hipStreamSynchronize(c->stream);
   if (c->integ_stream) { const hipError_t f = hipStreamSynchronize(c->integ_stream); if (e == hipSuccess) e = f; c->integ_pending = false; c->draw_pending[0] = c->draw_pending[1] = false; }
-  if (c->pre_stream) { const hipError_t f = hipStreamSynchronize(c->pre_stream); if (e == hipSuccess) e = f; c->pre_pending = false; }
+  if (c->pre_stream) { const hipError_t f = hipStreamSynchronize(c->pre_stream); if (e == hipSuccess) e = f; c->ahead.lane_synchronised(); }
   if (c->fill_worker) { c->fill_worker->drain(); const hipError_t f = fill_worker_error(c); if (e == hipSuccess) e = f; }
   if (c->fill_stream) { const hipError_t f = hipStreamSynchronize(c->fill_stream); if (e == hipSuccess) e = f; }
   c->fill_pending[0] = c->fill_pending[1] = false;
@@ -794,8 +782,8 @@ int32_t tsdf_create(const tsdf_config* cfg, tsdf_ctx** out) {
     const bool two_lanes = getenv("RR_LANES") ? atoi(getenv("RR_LANES")) == 2 : (cfg->lane_flags & TSDF_LANES_SHARED_FILL_LANE) != 0;   // the lane ahead and the fill lane share one stream
     if (make_stream(&c->pre_stream, 0, ppre, true) != hipSuccess ||
         (two_lanes ? (c->fill_stream = c->pre_stream, hipSuccess) : make_stream(&c->fill_stream, 1, pfill, true)) != hipSuccess ||
-        hipEventCreateWithFlags(&c->pre_done, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->pre_gate, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->pre_gate_b, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->pre_done, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->pre_gate[0], hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->pre_gate[1], hipEventDisableTiming) != hipSuccess ||
         make_stream(&c->integ_stream, 2, pinteg, true) != hipSuccess ||
         hipEventCreateWithFlags(&c->draw_done[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->draw_done[1], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->integ_done, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->integ_gate, hipEventDisableTiming) != hipSuccess ||
@@ -877,8 +865,7 @@ int32_t tsdf_destroy(tsdf_ctx* c) {
   for (auto& kv : c->timers) for (auto& e : kv.second.ev) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
   if (c->pre_stream && c->pre_stream != c->fill_stream) hipStreamDestroy(c->pre_stream);
   if (c->pre_done) hipEventDestroy(c->pre_done);
-  if (c->pre_gate) hipEventDestroy(c->pre_gate);
-  if (c->pre_gate_b) hipEventDestroy(c->pre_gate_b);
+  for (hipEvent_t g : c->pre_gate) if (g) hipEventDestroy(g);
   if (c->src_ready) hipEventDestroy(c->src_ready);
   if (c->normals_read) hipEventDestroy(c->normals_read);
   if (c->raw_read) hipEventDestroy(c->raw_read);
@@ -1024,18 +1011,14 @@ int32_t tsdf_set_calibration(tsdf_ctx* c, uint32_t i, const float* inv, const ui
 // On the lane ahead the re-layout launch of a new frame also clears the brick counters the frame's clearOccupiedBricks() is going to use
 // (it flips to them here instead): one launch and one dependent step less on the lane.
 static uint32_t* counters_for_upload(tsdf_ctx* c, hipStream_t lane) {
-  if (lane == c->stream || c->counters_zeroed || !c->d_counters[0]) return nullptr;
-  if (!c->counters_flipped && c->counters_in_use) { c->counters_cur = alt_of(c->counters_cur); c->br.counters = c->d_counters[c->counters_cur]; }
-  c->counters_flipped = true; c->counters_in_use = false; c->counters_zeroed = true; c->spare_clean = false;
-  return c->br.counters;
+  const int k = c->ahead.counters_for_upload(lane != c->stream && c->d_counters[0]);
+  if (k < 0) return nullptr;
+  return c->br.counters = c->d_counters[k];
 }
 // The frame slot a new frame is written to.  On the lane ahead: the OTHER slot (the context's stream may still read the current one for
 // the previous frame), once per frame of the lane; c->frame then points at it, so everything queued from now on reads the new frame.
 static int32_t begin_slot_write(tsdf_ctx* c, hipStream_t lane, bool keep_colour) {
-  if (lane == c->stream || c->slot_flipped) return TSDF_OK;
-  c->slot_flipped = true;
-  if (!c->slot_in_use) return TSDF_OK;                                   // nothing queued reads the current slot (the first frame): in place
-  c->slot_in_use = false;
+  if (!c->ahead.slot_for_write(lane != c->stream)) return TSDF_OK;      // (nothing queued reads the current slot -- the first frame --: in place)
   const int old = c->cur_slot, t = alt_of(old);
   if (int32_t rc = alloc_frame_slot(c, t)) return rc;
   if (keep_colour) {                                                     // "colour may be NULL (keeps the previous one)": the previous one lives in the other slot
@@ -1061,7 +1044,7 @@ int32_t tsdf_upload_frame(tsdf_ctx* c, const float* depth_rg, const float* quali
                           (int)c->cfg.num_streams, F.w, F.h, colour ? c->d_stage_col : nullptr, (uchar4*)F.color, nc, counters_for_upload(c, lane), (uint32_t)c->counter_words);
   HIP_TRY(c, hipGetLastError());
   c->slots[c->cur_slot].have = true; c->slots[c->cur_slot].origin = tsdf_ctx::kFramePre;
-  HIP_TRY(c, pre_leave(c, lane));
+  pre_leave(c, lane);
   return TSDF_OK;
 }
 // The same with the four arrays already in device memory (a producer on the GPU: the pre-processing of another library, a decoder, a
@@ -1091,7 +1074,7 @@ int32_t tsdf_upload_frame_dev(tsdf_ctx* c, const float* depth_rg, const float* q
   timer_end_on(c, "0repack", lane);
   HIP_TRY(c, hipGetLastError());
   c->slots[c->cur_slot].have = true; c->slots[c->cur_slot].origin = tsdf_ctx::kFramePre;
-  HIP_TRY(c, pre_leave(c, lane));
+  pre_leave(c, lane);
   return TSDF_OK;
 }
 
@@ -1213,7 +1196,7 @@ int32_t tsdf_upload_raw_frame(tsdf_ctx* c, const float* depth_raw, const uint8_t
   HIP_TRY(c, hipMemcpyAsync(c->d_stage_col, colour, nc * 3, hipMemcpyHostToDevice, lane));
   c->pending_rgb = c->d_stage_col;                                       // its RGBA8 re-layout rides along in tsdf_process_textures' first launch
   c->raw_src = c->d_raw; c->have_raw = true; ++c->raw_generation; c->slots[c->cur_slot].origin = tsdf_ctx::kFrameRawPending;
-  HIP_TRY(c, pre_leave(c, lane));
+  pre_leave(c, lane);
   return TSDF_OK;
 }
 // ... and with both arrays in device memory already (a decoder, a camera SDK's buffer): no copy -- the passes read depth_raw where it lies.  flags as
@@ -1233,7 +1216,7 @@ static int32_t upload_raw_frame_dev_impl(tsdf_ctx* c, const float* depth_raw, co
   if (int32_t rc = begin_slot_write(c, lane, false)) return rc;
   c->pending_rgb = colour;                                               // its RGBA8 re-layout rides along in tsdf_process_textures' first launch
   c->raw_src = depth_raw; c->have_raw = true; ++c->raw_generation; c->slots[c->cur_slot].origin = tsdf_ctx::kFrameRawPending;
-  HIP_TRY(c, pre_leave(c, lane));
+  pre_leave(c, lane);
   return TSDF_OK;
 }
 int32_t tsdf_upload_raw_frame_dev(tsdf_ctx* c, const float* depth_raw, const uint8_t* colour, uint32_t flags) { return upload_raw_frame_dev_impl(c, depth_raw, colour, flags, false); }
@@ -1324,7 +1307,7 @@ int32_t tsdf_upload_wire_frame(tsdf_ctx* c, const void* message, uint64_t bytes,
   timer_end_on(c, "0ingest", lane);
   HIP_TRY(c, hipGetLastError());
   c->raw_src = c->d_raw; c->have_raw = true; ++c->raw_generation; c->slots[c->cur_slot].origin = tsdf_ctx::kFrameRawPending;
-  HIP_TRY(c, pre_leave(c, lane));
+  pre_leave(c, lane);
   return TSDF_OK;
 }
 // the raw frame's colour waits for tsdf_process_textures' first launch (tsdf_ctx::pending_rgb): whoever reads the frame slot's colour before that asks for it here
@@ -1334,7 +1317,7 @@ static int32_t flush_pending_colour(tsdf_ctx* c) {
   launch_pack_color(lane, c->pending_rgb, (uchar4*)c->frame.color, (size_t)c->cfg.num_streams * c->frame.cw * c->frame.ch);
   c->pending_rgb = nullptr;
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, pre_leave(c, lane));
+  pre_leave(c, lane);
   return TSDF_OK;
 }
 int32_t tsdf_download_raw_frame(tsdf_ctx* c, float* depth_raw, uint8_t* colour_rgba) {
@@ -1412,7 +1395,7 @@ static int32_t process_textures_impl(tsdf_ctx* c, int phase) {
     timer_end_on(c, "1preprocess", lane);
     c->slots[c->cur_slot].have = true; c->slots[c->cur_slot].origin = tsdf_ctx::kFrameRawDone; c->normals_uploaded = false;
   }
-  HIP_TRY(c, pre_leave(c, lane));
+  pre_leave(c, lane);
   return TSDF_OK;
 }
 int32_t tsdf_process_textures(tsdf_ctx* c) { return process_textures_impl(c, 0); }
@@ -1462,18 +1445,12 @@ int32_t tsdf_clear_bricks(tsdf_ctx* c) {
   HIP_TRY(c, hipSetDevice(c->device));
   const hipStream_t lane = pre_enter(c);
   timer_begin_on(c, "bricks", lane);
-  if (lane != c->stream) {                                               // the lane ahead: the other counter buffer (the previous frame's draw may still read this one)
-    if (!c->counters_flipped && c->counters_in_use) { c->counters_cur = alt_of(c->counters_cur); c->br.counters = c->d_counters[c->counters_cur]; }
-    c->counters_flipped = true; c->counters_in_use = false;
-    c->spare_clean = false;
-    if (c->counters_zeroed) c->counters_zeroed = false;                  // the frame's re-layout launch cleared them (a second clear of the frame fills again)
-    else HIP_TRY(c, hipMemsetAsync(c->br.counters, 0, c->counter_words * sizeof(uint32_t), lane));
-  } else if (c->spare_clean) {                                           // the other buffer was zeroed by the last integrate(): swap
-    c->counters_cur = alt_of(c->counters_cur);
-    c->br.counters = c->d_counters[c->counters_cur];
-    c->spare_clean = false;
-  } else HIP_TRY(c, hipMemsetAsync(c->br.counters, 0, c->counter_words * sizeof(uint32_t), c->stream));
-  HIP_TRY(c, pre_leave(c, lane));
+  // the lane ahead: the other counter buffer (the previous frame's draw may still read this one), cleared by the frame's re-layout launch already;
+  // the context's stream: the buffer the last integrate() zeroed, if it did
+  const LaneAhead::Clear C = c->ahead.clear_bricks(lane != c->stream);
+  c->br.counters = c->d_counters[C.buffer];
+  if (C.fill) HIP_TRY(c, hipMemsetAsync(c->br.counters, 0, c->counter_words * sizeof(uint32_t), lane));
+  pre_leave(c, lane);
   return TSDF_OK;
 }
 int32_t tsdf_mark_bricks(tsdf_ctx* c) {
@@ -1482,12 +1459,8 @@ int32_t tsdf_mark_bricks(tsdf_ctx* c) {
   if (rc) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   const hipStream_t lane = pre_enter(c);
-  uint32_t* zero_word = nullptr;
-  if (lane != c->stream) {                                               // the count of the occupancy set the coming update flips to (or stays on)
-    c->occ_zeroed_word = (!c->occ_flipped && c->occ_in_use) ? alt_of(c->occ_parity) : c->occ_parity;
-    zero_word = c->d_occ_counts + c->occ_zeroed_word;
-    c->occ_count_zeroed = true;
-  }
+  const int word = c->ahead.mark_bricks(lane != c->stream);              // the count of the occupancy set the coming update flips to (or stays on)
+  uint32_t* const zero_word = word >= 0 ? c->d_occ_counts + word : nullptr;
   // the peel tiles the coming draw would reset first -- those the draw before the previous one touched, in the peel image that draw used (two alternate
   // while the lanes are on) --: reset here, on the lane ahead, beside the previous frame's kernels
   PeelClear pc{};
@@ -1497,38 +1470,22 @@ int32_t tsdf_mark_bricks(tsdf_ctx* c) {
   }
   launch_mark_bricks(lane, c->luts, c->frame, c->br, zero_word, pc.peels ? &pc : nullptr);
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, pre_leave(c, lane));
+  pre_leave(c, lane);
   return TSDF_OK;
 }
 int32_t tsdf_update_occupied(tsdf_ctx* c, float* ratio) {
   CHECK_CTX(c);
   HIP_TRY(c, hipSetDevice(c->device));
   const hipStream_t lane = pre_enter(c);
-  if (lane != c->stream) {
-    // the lane ahead: the other occupancy set (flags, list, count) -- the previous frame's integrate / draw may still read this one --, its
-    // count zeroed here instead of by the previous update (which would zero the word the context's stream is reading)
-    if (!c->occ_flipped && c->occ_in_use) c->occ_parity = alt_of(c->occ_parity);
-    c->occ_flipped = true; c->occ_in_use = false; c->occ_counts_stale = true;
-    c->br.num_occupied = c->d_occ_counts + c->occ_parity; c->br.flags = c->d_flags[c->occ_parity]; c->br.occupied = c->d_occupied[c->occ_parity];
-    // the frame's marking launch cleared a count word -- THE one this update lands on, unless a call between the two (a draw, tsdf_occupied_ratio, an
-    // integrate on the context's stream) joined the lane and made this update flip after all: then, and for a second update of the frame, fill again
-    const bool cleared = c->occ_count_zeroed && c->occ_zeroed_word == c->occ_parity;
-    c->occ_count_zeroed = false;
-    if (!cleared) HIP_TRY(c, hipMemsetAsync(c->br.num_occupied, 0, sizeof(uint32_t), lane));
-    launch_update_occupied(lane, c->br, c->min_voxels, c->d_occ_counts + 2);          // (a third word takes the kernel's re-arming store)
-  } else {
-    c->occ_parity = alt_of(c->occ_parity);
-    c->br.num_occupied = c->d_occ_counts + c->occ_parity;            // zero since the previous update (or creation) re-armed it ...
-    if (c->occ_counts_stale) {                                           // ... unless the lane ahead has used the words in between (it zeroes its own and re-arms none)
-      HIP_TRY(c, hipMemsetAsync(c->br.num_occupied, 0, sizeof(uint32_t), c->stream));
-      c->occ_counts_stale = false;
-    }
-    c->br.flags = c->d_flags[c->occ_parity]; c->br.occupied = c->d_occupied[c->occ_parity];
-    launch_update_occupied(c->stream, c->br, c->min_voxels, c->d_occ_counts + alt_of(c->occ_parity));
-  }
+  // the lane ahead: the other occupancy set (flags, list, count) -- the previous frame's integrate / draw may still read this one --, its count
+  // zeroed by the marking launch instead of by the previous update (which would zero the word the context's stream is reading)
+  const LaneAhead::Update U = c->ahead.update_occupied(lane != c->stream);
+  c->br.num_occupied = c->d_occ_counts + U.set; c->br.flags = c->d_flags[U.set]; c->br.occupied = c->d_occupied[U.set];
+  if (U.fill) HIP_TRY(c, hipMemsetAsync(c->br.num_occupied, 0, sizeof(uint32_t), lane));
+  launch_update_occupied(lane, c->br, c->min_voxels, c->d_occ_counts + U.rearm);
   HIP_TRY(c, hipGetLastError());
   timer_end_on(c, "bricks", lane);
-  HIP_TRY(c, pre_leave(c, lane));
+  pre_leave(c, lane);
   if (ratio) return tsdf_occupied_ratio(c, ratio);                     // the reference reads the count back every frame (:432-440); here only on request
   return TSDF_OK;
 }
@@ -1562,14 +1519,10 @@ int32_t tsdf_integrate(tsdf_ctx* c) {
     swap_volume_set(c);
     if (c->draw_pending[c->vol_set]) { HIP_TRY(c, hipStreamWaitEvent(lane, c->draw_done[c->vol_set], 0)); c->draw_pending[c->vol_set] = false; }   // the draw two frames back read this set
     // the frame's images and brick state: from the lane ahead (both this lane and the context's stream wait for it), or from work on the context's stream
-    c->main_since_gate = true;
-    c->slot_in_use = c->counters_in_use = c->occ_in_use = true;
-    if (c->pre_pending) {
-      c->pre_pending = false;
-      HIP_TRY(c, hipEventRecord(c->pre_done, c->pre_lane));
-      if (c->pre_lane != lane) HIP_TRY(c, hipStreamWaitEvent(lane, c->pre_done, 0));
-      HIP_TRY(c, hipStreamWaitEvent(c->stream, c->pre_done, 0));
-    } else {
+    hipError_t e;
+    const bool from_lane = consume_pre(c, lane, &e);
+    HIP_TRY(c, e);
+    if (!from_lane) {
       HIP_TRY(c, hipEventRecord(c->integ_gate, c->stream));
       HIP_TRY(c, hipStreamWaitEvent(lane, c->integ_gate, 0));
     }
@@ -1602,9 +1555,8 @@ int32_t tsdf_integrate(tsdf_ctx* c) {
       pc.w = c->vw; pc.h = c->vh; pc.ntx = (c->vw + 7) / 8; pc.n_tiles = pc.ntx * ((c->vh + 7) / 8);
     }
   }
-  if (c->use_bricks && !c->full_classify && !c->spare_clean && !pipelined(c)) {   // ... and zero the spare counter buffer for the next clearOccupiedBricks() (the lane ahead clears its own)
-    pc.zero = c->d_counters[alt_of(c->counters_cur)]; pc.zero_words = (uint32_t)c->counter_words;
-    c->spare_clean = true;
+  if (const int k = c->ahead.counters_zero_spare(c->use_bricks && !c->full_classify && !pipelined(c)); k >= 0) {   // ... and zero the spare counter buffer for the next clearOccupiedBricks() (the lane ahead clears its own)
+    pc.zero = c->d_counters[k]; pc.zero_words = (uint32_t)c->counter_words;
   }
   if (c->use_bricks) launch_classify_tiles(lane, c->vol, c->br, c->tiles, c->full_classify, c->frame_stamp, pc);
   // dense launches: the static half of the uniform-pair shortcut (k_integrate.hip), built once per calibration

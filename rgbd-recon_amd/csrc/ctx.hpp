@@ -7,6 +7,7 @@
 
 #include "tsdf_common.hpp"
 #include "image_tiles.hpp"
+#include "lane_ahead.hpp"
 
 using namespace rr;
 
@@ -44,12 +45,12 @@ struct tsdf_ctx {
   // active-tile lists of this and the previous integrate() (k_classify_lists), their two device counts, and what decides
   // whether the next integrate() may trust the previous list
   uint32_t* d_tile_list[2]{}; uint32_t* d_tile_counts = nullptr; int tile_parity = 0; bool full_classify = true; uint32_t frame_stamp = 0;
-  uint32_t* d_occ_counts = nullptr; int occ_parity = 0;   // two occupied-brick counts used alternately (see Bricks::num_occupied)
+  uint32_t* d_occ_counts = nullptr;   // three occupied-brick count words: two used alternately (see Bricks::num_occupied), one spare (lane_ahead.hpp)
   uint32_t min_voxels = 10;      // recon_integration.cpp:59
   size_t counter_words = 0;
   // two counter buffers: while frame f uses one, integrate(f)'s classify launch zeroes the other (part D of k_classify_lists), and
-  // clearOccupiedBricks() of frame f + 1 is a pointer swap instead of a fill launch; spare_clean says whether that happened
-  uint32_t* d_counters[2]{}; int counters_cur = 0; bool spare_clean = false;
+  // clearOccupiedBricks() of frame f + 1 is a pointer swap instead of a fill launch (which one is in use: lane_ahead.hpp)
+  uint32_t* d_counters[2]{};
   uint32_t* h_num_occupied = nullptr;   // pinned
   // calibration + frame
   StreamTable luts{};
@@ -195,26 +196,12 @@ struct tsdf_ctx {
   int vol_set = 0;
   hipStream_t pre_lane = nullptr; bool pre_on_integ = false;   // the stream the current frame's preparation runs on (pre_stream, or integ_stream: RR_PRE_ON_INTEG)
   bool overlap_fill = true;      // RR_OVERLAP_FILL=0 / tsdf_set_stage_overlap(ctx, 0): everything on the one stream, as in rounds 1 and 2
-  // ... and a third lane AHEAD of the context's stream (round 3): what a new frame needs before integrate() can run -- its re-layout and the
-  // brick passes (clear / mark / update) -- reads only the new frame and writes state nobody else writes, so it runs on `pre_stream` while
-  // the context's stream still works on the previous frame.  Everything the lane writes exists twice and alternates: the frame slots (flip at
-  // the first upload of a frame), the brick counters (flip at clearOccupiedBricks), flags + occupied list + count (flip at
-  // updateOccupiedBricks).  Two events tie the lanes: pre_done (integrate / draw wait for the lane) and pre_gate (recorded on the context's
-  // stream at the lane's first call of a frame, waited for at its first call of the NEXT frame: what the lane overwrites then was last read
-  // two frames ago).  (A third copy of everything, letting the lane run two frames ahead, was built and measured: the lanes then crowd each
-  // other -- every stage stretches -- and the frame takes 140 instead of 121 us: DESIGN.md section 5.)  Off with stage overlap off, after an explicit frame-slot call (tsdf_select_frame_slot, tsdf_upload_frame_async) and for
-  // the pre-processing path.
-  hipStream_t pre_stream = nullptr; hipEvent_t pre_done = nullptr, pre_gate = nullptr, pre_gate_b = nullptr, src_ready = nullptr;
-  // (round 4) the gate's wait can be DEFERRED inside tsdf_frame_raw_dev: the first two pre-processing passes write nothing the previous draws read, so they run in front of it.
-  // Two gate events alternate so that a deferred wait still refers to the record of the previous frame after this frame's record has been made.
-  hipEvent_t gate_wait_ev = nullptr; bool gate_wait_pending = false, gate_flip = false;
-  bool pre_pending = false, pre_gate_recorded = false, main_since_gate = true, pipeline_blocked = false;
-  bool slot_flipped = false, counters_flipped = false, occ_flipped = false;     // once per frame of the lane ...
-  bool slot_in_use = false, counters_in_use = false, occ_in_use = false;        // ... and only when a consumer has been queued since the buffer was last written
-  int occ_zeroed_word = 0;                                                      // which of the two count words the marking launch cleared
-  bool counters_zeroed = false, occ_count_zeroed = false;                       // the re-layout launch / the marking launch has cleared them already (no fill launch of its own)
+  // ... and a third lane AHEAD of the context's stream (round 3), preparing frame f + 1 on `pre_stream` while the context's stream still works on frame f:
+  // the state and its protocol are lane_ahead.hpp's -- the gate between the lanes and its deferred wait, which of the two frame slots, counter buffers
+  // and occupancy sets the lane writes, what is zero already.  Here: the stream, the events (pre_gate[]: the two gate events it indexes) and the buffers
+  LaneAhead ahead{};
+  hipStream_t pre_stream = nullptr; hipEvent_t pre_done = nullptr, pre_gate[2] = {nullptr, nullptr}, src_ready = nullptr;
   uint8_t* d_flags[2]{}; uint32_t* d_occupied[2]{};                             // the two occupancy sets (Bricks::flags / occupied point at the latest update's)
-  bool occ_counts_stale = false;                                                // the lane ahead has used the count words: the context's stream zeroes its word itself once
   // native multi-GPU exchange (comm.cpp): one RCCL communicator per context, every collective on the context's stream
   struct Comm {
     void* comm = nullptr;                     // ncclComm_t
@@ -243,8 +230,8 @@ struct tsdf_ctx {
 
 // helpers defined in abi.cpp
 namespace rrhost {
-hipStream_t pre_enter(tsdf_ctx* c, bool defer_gate = false);     // (defer_gate: tsdf_frame_raw_dev's first calls; see gate_wait_pending) the lane a frame-preparing call queues its work on (the context's stream when the lane is off); opens the lane's frame
-hipError_t pre_leave(tsdf_ctx* c, hipStream_t lane);   // ... and after queuing it
+hipStream_t pre_enter(tsdf_ctx* c, bool defer_gate = false);     // (defer_gate: tsdf_frame_raw_dev's first calls; see lane_ahead.hpp) the lane a frame-preparing call queues its work on (the context's stream when the lane is off); opens the lane's frame
+void pre_leave(tsdf_ctx* c, hipStream_t lane);   // ... and after queuing it
 hipError_t join_pre(tsdf_ctx* c);       // GPU side: the context's stream waits for the lane; called by every consumer of a frame's images / brick state
 void timer_begin(tsdf_ctx* c, const char* name);
 void timer_end(tsdf_ctx* c, const char* name);

@@ -235,3 +235,129 @@ def test_full_size_wire_upload_equals_raw_upload(rr, full):
     pa, pb = a.preprocessed(), b.preprocessed()
     for k in pa:
         assert ((pa[k] == pb[k]) | (np.isnan(pa[k]) & np.isnan(pb[k]))).all(), k
+
+
+# ---------------------------------------------------------------------------------------------- the lane ahead (csrc/lane_ahead.hpp)
+@pytest.fixture(scope="module")
+def lane_scenes(rr):
+    """four frames of a moving two-stream scene, on the host and (pre-processed and raw) in device memory"""
+    import torch
+    kw = dict(n_streams=2, width=128, height=96, lut_res=24, inv_res=32)
+    moves = [dict(), dict(sphere_c=(0.4, 0.7, -0.3), box_c=(-0.5, 1.5, 0.2)), dict(sphere_c=(-0.3, 1.3, 0.2)), dict(sphere_c=(0.1, 0.9, 0.4), box_c=(0.4, 1.2, -0.4))]
+    scs = [rr.scene.make_scene(**kw, **m) for m in moves]
+    dev = [{k: torch.from_numpy(np.ascontiguousarray(sc[k])).cuda() for k in ("depth", "quality", "silhouette", "color", "depth_raw")} for sc in scs]
+    torch.cuda.synchronize()
+    return scs, dev
+
+
+def _bricks(o):
+    o.clearOccupiedBricks(); o.markBricks(); o.updateOccupiedBricks(False)
+
+
+def _plain(o, k, scs, dev, mv, pr):
+    o.upload_frame(scs[k]); _bricks(o); o.integrate(); o.drawF(mv, pr)
+
+
+def _two_clears(o, k, scs, dev, mv, pr):
+    o.upload_frame(scs[k]); o.clearOccupiedBricks(); o.clearOccupiedBricks(); o.markBricks(); o.updateOccupiedBricks(False); o.integrate(); o.drawF(mv, pr)
+
+
+def _two_updates(o, k, scs, dev, mv, pr):
+    o.upload_frame(scs[k]); _bricks(o); o.updateOccupiedBricks(False); o.integrate(); o.drawF(mv, pr)
+
+
+def _two_uploads(o, k, scs, dev, mv, pr):
+    o.upload_frame(scs[(k + 1) % 4]); o.upload_frame(scs[k]); _bricks(o); o.integrate(); o.drawF(mv, pr)
+
+
+def _upload_without_colour(o, k, scs, dev, mv, pr):
+    """the second upload of the frame brings new images and no colour: the slot has flipped, the first upload's colour stays"""
+    d = dev[(k + 1) % 4]
+    o.upload_frame(scs[k]); o.upload_frame_dev(d["depth"].data_ptr(), d["quality"].data_ptr(), d["silhouette"].data_ptr(), 0, complete=True)
+    _bricks(o); o.integrate(); o.drawF(mv, pr)
+
+
+def _draw_between_mark_and_update(o, k, scs, dev, mv, pr):
+    o.upload_frame(scs[k]); o.clearOccupiedBricks(); o.markBricks(); o.drawF(mv, pr); o.updateOccupiedBricks(False); o.integrate(); o.drawF(mv, pr)
+
+
+def _ratio_between_clear_and_mark(o, k, scs, dev, mv, pr):
+    o.upload_frame(scs[k]); o.clearOccupiedBricks(); o.occupiedRatio(); o.markBricks(); o.updateOccupiedBricks(False); o.integrate(); o.drawF(mv, pr)
+
+
+def _integrate_before_the_clear(o, k, scs, dev, mv, pr):
+    o.upload_frame(scs[k]); o.integrate(); _bricks(o); o.integrate(); o.drawF(mv, pr)
+
+
+def _new_brick_size(o, k, scs, dev, mv, pr):
+    if k in (0, 2):                                          # (frame 0: the size the context was created with, or back to it)
+        o.setBrickSize(KW["brick_size"] if k == 0 else [2.0 / 6, 2.2 / 6, 2.0 / 6])
+    _plain(o, k, scs, dev, mv, pr)
+
+
+def _stage_overlap_off_and_on(o, k, scs, dev, mv, pr):
+    """off and on again in front of frame 1; frame 2 runs with it off (the context's stream takes over what the lane left), frame 3 with it on again"""
+    if o.lanes_on:
+        if k == 1:
+            o.set_stage_overlap(False); o.set_stage_overlap(True)
+        elif k >= 2:
+            o.set_stage_overlap(k == 3)
+    _plain(o, k, scs, dev, mv, pr)
+
+
+def _select_frame_slot(o, k, scs, dev, mv, pr):
+    if k == 2:
+        o.select_frame_slot(o.current_frame_slot())          # an explicit slot call: the lanes are off from here on
+    _plain(o, k, scs, dev, mv, pr)
+
+
+def _raw_fused_and_separate(o, k, scs, dev, mv, pr):
+    """tsdf_frame_raw_dev defers the lane's gate wait behind its first two passes; the separate calls do not"""
+    d = dev[k]
+    if k % 2 == 0:
+        o.frame_raw_dev(mv, pr, new_frame=(d["depth_raw"].data_ptr(), d["color"].data_ptr()), complete=True)
+    else:
+        o.upload_raw_frame_dev(d["depth_raw"].data_ptr(), d["color"].data_ptr(), complete=True)
+        o.clearOccupiedBricks(); o.processTextures(); o.updateOccupiedBricks(False); o.integrate(); o.drawF(mv, pr)
+
+
+LANE_ORDERS = [_plain, _two_clears, _two_updates, _two_uploads, _upload_without_colour, _draw_between_mark_and_update, _ratio_between_clear_and_mark,
+               _integrate_before_the_clear, _new_brick_size, _stage_overlap_off_and_on, _select_frame_slot, _raw_fused_and_separate]
+
+
+@pytest.mark.parametrize("order", LANE_ORDERS, ids=lambda f: f.__name__.lstrip("_"))
+def test_lane_ahead_call_orders_equal_one_stream(rr, lane_scenes, order):
+    """The lane ahead prepares frame f + 1 while the context's stream works on frame f; frame slot, brick counters and occupancy set alternate
+    under it (csrc/lane_ahead.hpp).  Every per-frame call order that reaches another branch of that bookkeeping, over four frames that differ
+    from one another (a read of the wrong slot, counter buffer or occupancy set shows), against a twin created with every kernel on one stream:
+    volume, brick counters and flags, occupied ratio and framebuffer, bit for bit -- first the four frames queued back to back with nothing
+    read in between (the lanes really overlap), then the four frames again with everything read back behind each."""
+    scs, dev = lane_scenes
+    vs = views(rr, *KW["view"])
+    lanes, twin = rr.ReconIntegrationHip(scs[0], **KW), rr.ReconIntegrationHip(scs[0], lane_flags=rr.LANES_ONE_STREAM, **KW)
+    lanes.lanes_on, twin.lanes_on = True, False
+    for o in (lanes, twin):
+        o.set_preprocess_calibration(scs[0])
+
+    def compare(what):
+        assert_same(dict(tsdf=lanes.tsdf()), dict(tsdf=twin.tsdf()), what)
+        (lc, lf), (tc, tf) = lanes.bricks(), twin.bricks()
+        np.testing.assert_array_equal(lc, tc, err_msg=f"{what}: brick counters"); np.testing.assert_array_equal(lf, tf, err_msg=f"{what}: brick flags")
+        assert lanes.occupiedRatio() == twin.occupiedRatio(), what
+        a, b = outputs(lanes), outputs(twin)
+        assert_same(dict(fb_color=a["fb_color"], fb_depth=a["fb_depth"]), dict(fb_color=b["fb_color"], fb_depth=b["fb_depth"]), what)
+        return twin.tsdf(), b["fb_depth"]
+
+    for k in range(4):
+        for o in (lanes, twin):
+            order(o, k, scs, dev, *vs[k])
+    compare("four frames back to back")
+    seen = []
+    for k in range(4):
+        for o in (lanes, twin):
+            order(o, k, scs, dev, *vs[k])
+        seen.append(compare(f"frame {k}, read back"))
+    assert all((d < 1).sum() > 100 for _, d in seen)
+    for a in range(4):
+        for b in range(a + 1, 4):
+            assert (seen[a][0] != seen[b][0]).any(), f"frames {a} and {b} leave the same volume"
