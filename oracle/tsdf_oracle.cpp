@@ -703,6 +703,17 @@ void orc_draw(orc_ctx* c, const float* mv16, const float* proj16) {
       const float fx = (float)px + 0.5f, fy = (float)py + 0.5f;
       vec3 step = normalize(pixel_dir_vol(V, fx, fy)) * sd;              // :64
       uint32_t max_n = 0; vec3 pos = {0, 0, 0};
+      // The fragments are those of the unit cube's faces (UnitCube::draw, culling off, recon_integration.cpp:223-225): a pixel whose ray
+      // misses the cube has none, with or without skipSpace -- bricks of the last row / column reach past the bounding box, so their depth
+      // limits cover pixels the cube does not.  The ray-cube test is intersectBox :363-374.
+      const vec3 eye = V.cam_vol;
+      const vec3 inv = {1.0f / step.x, 1.0f / step.y, 1.0f / step.z};
+      const vec3 tbot = inv * (vec3{0, 0, 0} - eye), ttop = inv * (vec3{1, 1, 1} - eye);
+      const vec3 tmn = {fminf(ttop.x, tbot.x), fminf(ttop.y, tbot.y), fminf(ttop.z, tbot.z)};
+      const vec3 tmx = {fmaxf(ttop.x, tbot.x), fmaxf(ttop.y, tbot.y), fmaxf(ttop.z, tbot.z)};
+      const float t0 = fmaxf(fmaxf(tmn.x, tmn.y), fmaxf(tmn.x, tmn.z));
+      const float t1 = fminf(fminf(tmx.x, tmx.y), fminf(tmx.x, tmx.z));
+      if (!(t0 <= t1) || t1 < 0.0f) continue;                            // pixel not covered by the cube: no fragment
       if (skip) {                                                        // getStartPos(ivec2(gl_FragCoord.xy - viewport_offset)) :70, :384-393
         const float qx = ((float)((long)px + org[0]) + 0.5f) - c->vp_off[0], qy = ((float)(py + org[1]) + 0.5f) - c->vp_off[1];   // gl_FragCoord - viewport_offset
         const int cx = (int)qx, cy = (int)qy;                            // ivec2(): truncation
@@ -714,17 +725,9 @@ void orc_draw(orc_ctx* c, const float* mv16, const float* proj16) {
         if (r >= 1.0f) pb = pf;
         pos = pf;
         max_n = (uint32_t)ceilf(length(pf - pb) / sd);                   // :73
-      } else {                                                           // intersectBox :363-374
-        const vec3 o = V.cam_vol;
-        vec3 inv = {1.0f / step.x, 1.0f / step.y, 1.0f / step.z};
-        vec3 tbot = inv * (vec3{0, 0, 0} - o), ttop = inv * (vec3{1, 1, 1} - o);
-        vec3 tmn = {fminf(ttop.x, tbot.x), fminf(ttop.y, tbot.y), fminf(ttop.z, tbot.z)};
-        vec3 tmx = {fmaxf(ttop.x, tbot.x), fmaxf(ttop.y, tbot.y), fmaxf(ttop.z, tbot.z)};
-        float t0 = fmaxf(fmaxf(tmn.x, tmn.y), fmaxf(tmn.x, tmn.z));
-        float t1 = fminf(fminf(tmx.x, tmx.y), fminf(tmx.x, tmx.z));
-        if (!(t0 <= t1) || t1 < 0.0f) continue;                          // pixel not covered by the cube: no fragment
+      } else {                                                           // :75-86
         float t_near = t0 < 0.0f ? 0.0f : t0;
-        pos = o + step * t_near;
+        pos = eye + step * t_near;
         max_n = (uint32_t)ceilf(fabsf(t1 - t_near));
       }
       float prev = -limit;

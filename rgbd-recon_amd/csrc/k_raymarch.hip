@@ -256,7 +256,19 @@ __global__ __launch_bounds__(256, RR_MARCH_BOUNDS) void k_march(ViewParams P, Vo
   float3 pos = make_float3(0, 0, 0);
   bool covered = inside;
   if (inside) {
-    if (P.skip) {                                                       // getStartPos(ivec2(gl_FragCoord.xy - viewport_offset)), :70, :384-393
+    // The fragments are those of the unit cube's faces (UnitCube::draw, culling off, recon_integration.cpp:223-225): a pixel whose ray misses
+    // the cube has none, with or without skipSpace -- bricks of the last row / column reach past the bounding box, so depth limits alone
+    // would let rays march beside the volume.  The ray-cube test is intersectBox(), :363-374.
+    const float3 o = make_float3(P.cam_vol[0], P.cam_vol[1], P.cam_vol[2]);
+    const float3 inv = make_float3(1.0f / step.x, 1.0f / step.y, 1.0f / step.z);
+    const float3 tbot = make_float3(inv.x * (0.0f - o.x), inv.y * (0.0f - o.y), inv.z * (0.0f - o.z));
+    const float3 ttop = make_float3(inv.x * (1.0f - o.x), inv.y * (1.0f - o.y), inv.z * (1.0f - o.z));
+    const float3 tmn = make_float3(fminf(ttop.x, tbot.x), fminf(ttop.y, tbot.y), fminf(ttop.z, tbot.z));
+    const float3 tmx = make_float3(fmaxf(ttop.x, tbot.x), fmaxf(ttop.y, tbot.y), fmaxf(ttop.z, tbot.z));
+    const float t0 = fmaxf(fmaxf(tmn.x, tmn.y), fmaxf(tmn.x, tmn.z));
+    const float t1 = fminf(fminf(tmx.x, tmx.y), fminf(tmx.x, tmx.z));
+    if (!(t0 <= t1) || t1 < 0.0f) covered = false;                      // no fragment: pixel not under the cube
+    else if (P.skip) {                                                  // getStartPos(ivec2(gl_FragCoord.xy - viewport_offset)), :70, :384-393
       // gl_FragCoord = viewport origin + pixel + 0.5 (window coordinates); the shader subtracts its viewport_offset uniform again.
       // origin == offset (what the client sets, kinect_client.cpp:650-662) gives back the pixel centre exactly; anything else
       // shifts the peel lookup and the unprojection the way the reference's arithmetic does (out-of-range texelFetch -> 0).
@@ -273,21 +285,10 @@ __global__ __launch_bounds__(256, RR_MARCH_BOUNDS) void k_march(ViewParams P, Vo
       pos = pf;
       const float3 dd = make_float3(pf.x - pb.x, pf.y - pb.y, pf.z - pb.z);
       max_n = (uint32_t)ceilf(sqrtf(dd.x * dd.x + dd.y * dd.y + dd.z * dd.z) / sd);   // :73
-    } else {                                                            // intersectBox(), :363-374
-      const float3 o = make_float3(P.cam_vol[0], P.cam_vol[1], P.cam_vol[2]);
-      const float3 inv = make_float3(1.0f / step.x, 1.0f / step.y, 1.0f / step.z);
-      const float3 tbot = make_float3(inv.x * (0.0f - o.x), inv.y * (0.0f - o.y), inv.z * (0.0f - o.z));
-      const float3 ttop = make_float3(inv.x * (1.0f - o.x), inv.y * (1.0f - o.y), inv.z * (1.0f - o.z));
-      const float3 tmn = make_float3(fminf(ttop.x, tbot.x), fminf(ttop.y, tbot.y), fminf(ttop.z, tbot.z));
-      const float3 tmx = make_float3(fmaxf(ttop.x, tbot.x), fmaxf(ttop.y, tbot.y), fmaxf(ttop.z, tbot.z));
-      const float t0 = fmaxf(fmaxf(tmn.x, tmn.y), fmaxf(tmn.x, tmn.z));
-      const float t1 = fminf(fminf(tmx.x, tmx.y), fminf(tmx.x, tmx.z));
-      if (!(t0 <= t1) || t1 < 0.0f) covered = false;                    // no fragment: pixel not under the cube
-      else {
-        const float t_near = t0 < 0.0f ? 0.0f : t0;
-        pos = make_float3(o.x + step.x * t_near, o.y + step.y * t_near, o.z + step.z * t_near);
-        max_n = (uint32_t)ceilf(fabsf(t1 - t_near));
-      }
+    } else {                                                            // :75-86
+      const float t_near = t0 < 0.0f ? 0.0f : t0;
+      pos = make_float3(o.x + step.x * t_near, o.y + step.y * t_near, o.z + step.z * t_near);
+      max_n = (uint32_t)ceilf(fabsf(t1 - t_near));
     }
   }
   // The march, :89-110.  Sample positions never depend on the densities, so (a) while the ray is in space known to hold

@@ -87,3 +87,32 @@ def test_view_matrices_match_their_definitions():
     np.testing.assert_allclose(img_to_eye.reshape(4, 4).T, np.linalg.inv(S @ T @ pr), rtol=2e-6, atol=1e-6)
     np.testing.assert_allclose(cam, [0.5, 0.5, 2.5], atol=1e-6)        # unit bbox: volume space == world
     np.testing.assert_allclose(normal.reshape(4, 4).T, np.linalg.inv(mv).T, rtol=2e-6, atol=1e-6)
+
+
+def test_skip_space_takes_no_sample_beside_the_volume():
+    """The fragments of the march are those of the unit cube (UnitCube::draw, recon_integration.cpp:223-225).  A brick size that does not
+    divide the bounding box leaves a last column of bricks that reaches past it (to_world of bricks.vs draws every brick whole), so the
+    depth limits cover pixels beside the cube: no fragment there, no sample, whatever the depth limits say."""
+    import main_path_reference as R
+    sc = tiny_scene([(0.5, 0.5, 0.5)], [0.5], [1.0], [1.0])
+    view = (192, 128)                                                   # the overhang is 1 / 48 of the box: a good two pixels wide here
+    o = OracleRecon(sc, res=(RES,) * 3, brick_size=[0.145] * 3, limit=LIMIT, view=view)      # snaps to 7 voxels: 7 bricks span 49 / 48 of the box
+    assert o.res_bricks == (7, 7, 7) and o.brick_size[0] * 7 > 1.0
+    o.set_tsdf(np.full((RES,) * 3, 0.01, np.float32))                   # positive everywhere: any sample is a hit
+    cnt = np.zeros(o.numBricks(), np.uint32)
+    cnt[6::7] = 50                                                     # the whole last column in x
+    o.set_counters(cnt)
+    o.updateOccupiedBricks()
+    o.setSpaceSkip(True)
+    o.setColorFilling(False)
+    mvf = rr.scene.gl_flat(rr.scene.look_at((0.5, 0.5, 2.5), (0.5, 0.5, 0.5)))
+    prf = rr.scene.gl_flat(rr.scene.perspective(40.0, view[0] / view[1], 0.1, 50.0))
+    o.draw(mvf, prf)
+    _, depth, ns, peels = o.view_images()
+    V = R.View(mvf, prf, view, (0, 0, 0), (1, 1, 1))
+    covered, _, _, margin = R.box_interval(V, V.ray_directions() * (LIMIT * 0.5))
+    beside = (peels[..., 0] < 1) & ~covered & (margin > 1e-3)          # under the overhanging bricks, clearly off the cube
+    under = (peels[..., 0] < -peels[..., 1]) & covered & (margin > 1e-3)     # a non-empty interval between the nearest and the farthest face
+    assert beside.sum() >= 10 and under.sum() >= 10
+    assert (ns[beside] == 0).all() and (depth[beside] == 1).all()
+    assert (ns[under] > 0).all() and (depth[under] < 1).all()
