@@ -74,7 +74,7 @@ Mat4 to_mat4(const double* d) { Mat4 r; for (int i = 0; i < 16; ++i) r.m[i] = (f
 
 void release_view(tsdf_ctx* c) {
   for (int k = 0; k < 2; ++k) { hipFree(c->atlas_color[k]); hipFree(c->atlas_depth[k]); c->atlas_color[k] = nullptr; c->atlas_depth[k] = nullptr; }
-  c->atlas_parity = 0;
+  c->lanes.view_released();
   hipFree(c->d_peels); hipFree(c->d_peels_alt); c->d_peels_alt = nullptr; hipFree(c->d_nsamples); hipFree(c->d_fb_c); hipFree(c->d_fb_d);
   hipFree(c->d_long); c->d_long = nullptr;
   hipFree(c->d_tri_z); hipFree(c->d_tri_acc); c->d_tri_z = nullptr; c->d_tri_acc = nullptr;
@@ -125,7 +125,7 @@ int32_t setup_view(tsdf_ctx* c, uint32_t w, uint32_t h) {
   const size_t na = (size_t)A.aw * A.h, nv = (size_t)w * h;
   HIP_TRY(c, hipMalloc(&A.color, na * sizeof(float4)));
   HIP_TRY(c, hipMalloc(&A.depth, na * sizeof(float)));
-  c->atlas_color[0] = A.color; c->atlas_depth[0] = A.depth; c->atlas_parity = 0;    // (the second pyramid: on the first overlapped draw)
+  c->atlas_color[0] = A.color; c->atlas_depth[0] = A.depth;                         // (pyramid 0 since release_view; the second one: on the first overlapped draw)
   HIP_TRY(c, hipMalloc(&c->d_peels, nv * sizeof(float4)));
   HIP_TRY(c, hipMalloc(&c->d_peels_alt, nv * sizeof(float4)));
   HIP_TRY(c, hipMalloc(&c->d_nsamples, nv * sizeof(float)));
@@ -291,7 +291,7 @@ void timer_end(tsdf_ctx* c, const char* name) {
 void timer_begin_on(tsdf_ctx* c, const char* name, hipStream_t st) { hipStream_t keep = c->stream; c->stream = st; timer_begin(c, name); c->stream = keep; }
 void timer_end_on(tsdf_ctx* c, const char* name, hipStream_t st) { hipStream_t keep = c->stream; c->stream = st; timer_end(c, name); c->stream = keep; }
 
-// ---- the helper thread that issues the fill lane's calls (see tsdf_ctx::fill_worker)
+// ---- the helper thread that issues the fill lane's calls (why: draw_lanes.hpp)
 }  // namespace rrhost
 struct tsdf_ctx::FillWorker {
   struct Job { Atlas atlas; const uint8_t* tile_mask; uint8_t* lvl_mask[2]; int vw, vh; float4* fb_c; float* fb_d; int mask_mode, keep; hipEvent_t wait_ev, done_ev; };
@@ -347,15 +347,19 @@ static hipError_t fill_worker_error(tsdf_ctx* c) {
   return (hipError_t)e;
 }
 // stage overlap: GPU-side join (the context's stream waits for the hole filling that is still in flight) and host-side sync of both streams
-hipError_t join_fill_of(tsdf_ctx* c, int pyramid) {
-  if (!c->fill_pending[pyramid]) return hipSuccess;
-  c->fill_pending[pyramid] = false;
-  if (c->fill_worker) { c->fill_worker->wait_issued(c->fill_job_no[pyramid]); const hipError_t e = fill_worker_error(c); if (e != hipSuccess) return e; }   // (its record must have been issued before this wait is)
+static hipError_t wait_fill(tsdf_ctx* c, int pyramid, DrawLanes::FillJoin J) {
+  if (!J.wait) return hipSuccess;
+  if (c->fill_worker) { c->fill_worker->wait_issued(J.job); const hipError_t e = fill_worker_error(c); if (e != hipSuccess) return e; }   // (its record must have been issued before this wait is)
   return hipStreamWaitEvent(c->stream, c->fill_done[pyramid], 0);
 }
 hipError_t join_fill(tsdf_ctx* c) {
-  const hipError_t a = join_fill_of(c, 0), b = join_fill_of(c, 1);
+  const hipError_t a = wait_fill(c, 0, c->lanes.join_fill(0)), b = wait_fill(c, 1, c->lanes.join_fill(1));
   return a != hipSuccess ? a : b;
+}
+// record draw_done[set] on the context's stream, behind whatever last read the set (DrawLanes::draw_end)
+static hipError_t record_draw_end(tsdf_ctx* c, DrawLanes::DrawEnd D) {
+  if (c->fill_worker) c->fill_worker->wait_issued(D.wait_job);           // (a job that waits for the event's PREVIOUS record must have issued that wait)
+  return hipEventRecord(c->draw_done[D.set], c->stream);
 }
 // the one doorway of whoever writes the framebuffer beside the hole filling (the point / triangle draws, the overlays, the texture views): wait for
 // the hole filling in flight, and tell the tile history that the framebuffer is no longer the hole filling's alone (image_tiles.hpp)
@@ -383,7 +387,7 @@ hipStream_t pre_enter(tsdf_ctx* c, bool defer_gate) {
     // draw in between leave that integrate out of every gate, while it may still read the frame slot / brick counters / occupancy set this frame is about to
     // overwrite (the copies alternate): the lane waits for the integrate lane itself then.  (In the per-frame order upload .. integrate, draw the flag is
     // clear here -- the draw has joined the lane -- and nothing is added.)
-    const LaneAhead::Open O = c->ahead.open_frame(defer_gate, c->integ_pending && c->integ_stream && c->pre_lane != c->integ_stream);
+    const LaneAhead::Open O = c->ahead.open_frame(defer_gate, c->lanes.integ_in_flight() && c->integ_stream && c->pre_lane != c->integ_stream);
     wait_gate(c, O.overdue);
     wait_gate(c, O.wait);
     if (O.wait_integ) {
@@ -415,23 +419,22 @@ hipError_t block_pipeline(tsdf_ctx* c) {
   if (!c->ahead.block()) return hipSuccess;
   hipError_t e = hipStreamSynchronize(c->stream);
   if (c->pre_stream) { const hipError_t f = hipStreamSynchronize(c->pre_stream); if (e == hipSuccess) e = f; }
-  if (c->integ_stream) { const hipError_t f = hipStreamSynchronize(c->integ_stream); if (e == hipSuccess) e = f; c->integ_pending = false; }
+  if (c->integ_stream) { const hipError_t f = hipStreamSynchronize(c->integ_stream); if (e == hipSuccess) e = f; c->lanes.integ_lane_drained(); }
   return e;
 }
-// ---- the fourth lane (see tsdf_ctx::integ_stream)
-hipError_t join_integ(tsdf_ctx* c) {
-  if (!c->integ_pending) return hipSuccess;
-  c->integ_pending = false;
+// ---- the fourth lane: its state and protocol are draw_lanes.hpp's (tsdf_ctx::lanes)
+static hipError_t wait_integ(tsdf_ctx* c) {
   const hipError_t e = hipEventRecord(c->integ_done, c->integ_stream);
   return e != hipSuccess ? e : hipStreamWaitEvent(c->stream, c->integ_done, 0);
 }
+hipError_t join_integ(tsdf_ctx* c) { return c->lanes.join_integ() ? wait_integ(c) : hipSuccess; }
 // the context holds every tile layer of the volume (false: a Z-slab)
 static bool whole_volume(const tsdf_ctx* c) { return c->vol.own_tz0 == 0 && c->vol.own_tz1 == (c->res[2] + 7) / 8; }
 bool deep_ok(const tsdf_ctx* c) {
   // (a Z-slab context too, when it recomputes its halo layers itself: an EXCHANGED halo is written into the volume from outside between integrate() and the draw)
-  return c->deep && !c->deep_failed && pipelined(c) && c->integ_stream && (whole_volume(c) || c->cfg.slab_recompute_halo != 0) && !c->vol.slot && c->proj_budget == 0;
+  return c->deep && !c->lanes.second_set_failed() && pipelined(c) && c->integ_stream && (whole_volume(c) || c->cfg.slab_recompute_halo != 0) && !c->vol.slot && c->proj_budget == 0;
 }
-// exchange the set in use with the other one (host pointers only: kernels already queued keep the pointers they were launched with)
+// exchange the set in use with the other one (host pointers only: kernels already queued keep the pointers they were launched with; which set: DrawLanes::integrate)
 void swap_volume_set(tsdf_ctx* c) {
   tsdf_ctx::VolSet& a = c->alt;
   std::swap(c->vol.data, a.data); std::swap(c->d_cls_all, a.cls_all); std::swap(c->tiles.stamp, a.stamp);
@@ -440,7 +443,6 @@ void swap_volume_set(tsdf_ctx* c) {
   c->vol.cls = c->d_cls_all;
   c->tiles.cls = c->d_cls_all + (size_t)(c->vol.int_tz0 - c->vol.tz0) * c->vol.nty * c->vol.ntx;
   c->tiles.list = c->d_tile_list[0]; c->tiles.count = c->d_tile_counts;
-  c->vol_set ^= 1;
 }
 // the second set, initialised on `lane` like setup_volume initialises the first; false = no memory for it (the context stays on one volume)
 bool ensure_alt_set(tsdf_ctx* c, hipStream_t lane) {
@@ -454,7 +456,7 @@ bool ensure_alt_set(tsdf_ctx* c, hipStream_t lane) {
   if (!ok) {
     (void)hipGetLastError();
     hipFree(a.data); hipFree(a.stamp); hipFree(a.cls_all); hipFree(a.list[0]); hipFree(a.list[1]); hipFree(a.counts);
-    a = tsdf_ctx::VolSet{}; c->deep_failed = true;
+    a = tsdf_ctx::VolSet{}; c->lanes.second_set_unavailable();
     return false;
   }
   launch_fill_u32(lane, (uint32_t*)a.data, 0u, nvox);
@@ -496,11 +498,11 @@ static int32_t ensure_proj_cache(tsdf_ctx* c, const ProjCache** proj) {
 }
 hipError_t sync_ctx(tsdf_ctx* c) {
   hipError_t e = hipStreamSynchronize(c->stream);
-  if (c->integ_stream) { const hipError_t f = hipStreamSynchronize(c->integ_stream); if (e == hipSuccess) e = f; c->integ_pending = false; c->draw_pending[0] = c->draw_pending[1] = false; }
+  if (c->integ_stream) { const hipError_t f = hipStreamSynchronize(c->integ_stream); if (e == hipSuccess) e = f; }
   if (c->pre_stream) { const hipError_t f = hipStreamSynchronize(c->pre_stream); if (e == hipSuccess) e = f; c->ahead.lane_synchronised(); }
   if (c->fill_worker) { c->fill_worker->drain(); const hipError_t f = fill_worker_error(c); if (e == hipSuccess) e = f; }
   if (c->fill_stream) { const hipError_t f = hipStreamSynchronize(c->fill_stream); if (e == hipSuccess) e = f; }
-  c->fill_pending[0] = c->fill_pending[1] = false;
+  c->lanes.host_synchronised(c->integ_stream != nullptr);
   return e;
 }
 
@@ -624,7 +626,7 @@ void release_volume(tsdf_ctx* c) {
   c->proj = ProjCache{}; c->d_proj_words = nullptr; c->d_item_stats = nullptr; c->proj_failed = false; c->last_integrate_cached = false;
   c->last_k1 = IntegratePlan{};
   hipFree(c->alt.data); hipFree(c->alt.cls_all); hipFree(c->alt.stamp); hipFree(c->alt.list[0]); hipFree(c->alt.list[1]); hipFree(c->alt.counts);
-  c->alt = tsdf_ctx::VolSet{}; c->deep_failed = false;
+  c->alt = tsdf_ctx::VolSet{}; c->lanes.volume_released();
   c->vol.data = nullptr; c->vol.slot = nullptr; c->tiles.stamp = nullptr; c->d_cls_all = nullptr;
   c->d_tile_list[0] = c->d_tile_list[1] = nullptr; c->d_tile_counts = nullptr; c->d_linear = nullptr; c->d_tile_bounds = nullptr;
   c->tile_bounds_valid = false; c->tile_parity = 0; c->full_classify = true; c->frame_stamp = 0;
@@ -1510,14 +1512,11 @@ int32_t tsdf_integrate(tsdf_ctx* c) {
   hipStream_t lane = c->stream;
   if (deep_ok(c) && ensure_alt_set(c, c->integ_stream)) {
     lane = c->integ_stream;
-    if (c->draw_unrecorded) {                                            // a draw without hole filling behind it: mark its end now
-      if (c->fill_worker) c->fill_worker->wait_issued(c->draw_wait_job[c->vol_set]);
-      HIP_TRY(c, hipEventRecord(c->draw_done[c->vol_set], c->stream));
-      c->draw_pending[c->vol_set] = true; c->draw_unrecorded = false;
-    }
-    HIP_TRY(c, join_integ(c));                                           // (bookkeeping only: the lane is in order, and a draw has normally consumed it)
+    const DrawLanes::Integrate I = c->lanes.integrate();
+    if (I.record_end) HIP_TRY(c, record_draw_end(c, I.end));             // a draw without hole filling behind it: mark its end now
+    if (I.join) HIP_TRY(c, wait_integ(c));                               // (bookkeeping only: the lane is in order, and a draw has normally consumed it)
     swap_volume_set(c);
-    if (c->draw_pending[c->vol_set]) { HIP_TRY(c, hipStreamWaitEvent(lane, c->draw_done[c->vol_set], 0)); c->draw_pending[c->vol_set] = false; }   // the draw two frames back read this set
+    if (I.wait_draw >= 0) HIP_TRY(c, hipStreamWaitEvent(lane, c->draw_done[I.wait_draw], 0));   // the draw two frames back read this set
     // the frame's images and brick state: from the lane ahead (both this lane and the context's stream wait for it), or from work on the context's stream
     hipError_t e;
     const bool from_lane = consume_pre(c, lane, &e);
@@ -1526,7 +1525,6 @@ int32_t tsdf_integrate(tsdf_ctx* c) {
       HIP_TRY(c, hipEventRecord(c->integ_gate, c->stream));
       HIP_TRY(c, hipStreamWaitEvent(lane, c->integ_gate, 0));
     }
-    c->integ_pending = true;
   } else {
     HIP_TRY(c, join_integ(c));
     HIP_TRY(c, join_pre(c));
@@ -1627,8 +1625,9 @@ static int32_t raymarch_impl(tsdf_ctx* c, const float* mv, const float* pr, bool
   // two pyramids alternate while the hole filling runs beside the next frame (stage overlap): this draw takes the other one and only has
   // to wait for the hole filling of the draw BEFORE the previous one -- long finished -- instead of the previous draw's
   const bool two_pyramids = ImageTiles::two_pyramids(c->fill_holes, c->overlap_fill, masked_direct(c));
+  const DrawLanes::Pyramid Y = c->lanes.take_pyramid(two_pyramids);
   if (two_pyramids) {
-    const int p = c->atlas_parity ^ 1;
+    const int p = Y.index;
     if (!c->atlas_color[p]) {
       const size_t na = (size_t)c->atlas.aw * c->atlas.h;
       HIP_TRY(c, hipMalloc(&c->atlas_color[p], na * sizeof(float4)));
@@ -1636,10 +1635,9 @@ static int32_t raymarch_impl(tsdf_ctx* c, const float* mv, const float* pr, bool
       launch_clear_image(c->stream, c->atlas_color[p], c->atlas_depth[p], na, make_float4(0.0f, 1.0f, 0.0f, 0.0f), 1.0f);   // ViewLod::enable's clear
       T.second_pyramid_allocated();
     }
-    c->atlas_parity = p;
     c->atlas.color = c->atlas_color[p]; c->atlas.depth = c->atlas_depth[p];
-    HIP_TRY(c, join_fill_of(c, p));
-  } else HIP_TRY(c, join_fill(c));                                       // the previous draw's hole filling still reads level 0 / writes the framebuffer
+  }
+  for (int p = 0; p < 2; ++p) HIP_TRY(c, wait_fill(c, p, Y.join[p]));    // (one pyramid: the previous draw's hole filling still reads level 0 / writes the framebuffer)
   // ... then the march
   const ImageTiles::March M = T.draw_march(L.use_tiles, two_pyramids, c->fill_holes, masked_direct(c), partial);
   RayTarget RT = ray_target(c);
@@ -1648,7 +1646,7 @@ static int32_t raymarch_impl(tsdf_ctx* c, const float* mv, const float* pr, bool
     RT.touched_prev_target = c->d_touched[M.touched_prev_target];
     RT.touched_recycle = c->d_touched[M.touched_recycle];
     RT.rewrite_all = M.rewrite_all; RT.rewrite_target = M.rewrite_target;
-    RT.fill_mask = M.fill_mask ? c->d_fill_mask[c->atlas_parity] : nullptr;
+    RT.fill_mask = M.fill_mask ? c->d_fill_mask[Y.index] : nullptr;
   }
   HIP_TRY(c, join_integ(c));                                             // the volume: from here on (the depth limits above needed the bricks only)
   const MarchPlan plan = plan_march(partial, P.skip != 0, c->vol.slot != nullptr, c->d_long != nullptr, c->march_cap ? c->march_cap : 0xffffffffu, c->march_box);
@@ -1662,7 +1660,7 @@ static int32_t raymarch_impl(tsdf_ctx* c, const float* mv, const float* pr, bool
   c->own_miss_counts = true;
   if (masked_direct(c)) launch_resolve_masked(c->stream, c->atlas, c->vw, c->vh, c->d_fb_c, c->d_fb_d, (int)c->color_mask_mode, c->keep_color ? 1 : 0);
   timer_end(c, "draw");
-  c->draw_unrecorded = c->integ_stream != nullptr;                       // (draw_done[set]: recorded by fillColors(), or by the next integrate())
+  c->lanes.draw_marched(c->integ_stream != nullptr);
   HIP_TRY(c, hipGetLastError());
   return TSDF_OK;
 }
@@ -1804,40 +1802,38 @@ int32_t tsdf_raymarch(tsdf_ctx* c, const float* mv, const float* pr) {
 // fillColors(): with stage overlap on its own stream behind an event of the context's stream; *used = the stream it was queued on
 static int32_t fill_colors_impl(tsdf_ctx* c, hipStream_t* used) {
   hipStream_t fs = c->stream;
+  const int set = c->lanes.set(), pyramid = c->lanes.pyramid();
   if (c->overlap_fill) {
     if (!c->fill_stream) {                                                // (a context created with RR_OVERLAP_FILL=0 and switched on later)
       HIP_TRY(c, hipStreamCreateWithFlags(&c->fill_stream, hipStreamNonBlocking));
       for (hipEvent_t& e : c->fill_done) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
     for (hipEvent_t& e : c->draw_done) if (!e) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (c->fill_worker) c->fill_worker->wait_issued(c->draw_wait_job[c->vol_set]);   // (a job that waits for the event's PREVIOUS record must have issued that wait)
-    HIP_TRY(c, hipEventRecord(c->draw_done[c->vol_set], c->stream));      // everything the caller queued so far: the march / composite into level 0
-    c->draw_pending[c->vol_set] = true; c->draw_unrecorded = false;
+    HIP_TRY(c, record_draw_end(c, c->lanes.draw_end()));                  // everything the caller queued so far: the march / composite into level 0
     fs = c->fill_stream;
   }
   const bool by_tiles = c->tiles_img.fill(c->color_mask_mode != 0, c->keep_color);
-  const uint8_t* tile_mask = by_tiles ? c->d_fill_mask[c->atlas_parity] : nullptr;
+  const uint8_t* tile_mask = by_tiles ? c->d_fill_mask[pyramid] : nullptr;
   ++c->n_fills; c->n_fills_by_tiles += by_tiles ? 1 : 0;
-  if (c->overlap_fill && c->fill_thread && !c->timers_on) {              // the helper thread issues the lane's calls (tsdf_ctx::fill_worker)
+  if (c->overlap_fill && c->fill_thread && !c->timers_on) {              // the helper thread issues the lane's calls (draw_lanes.hpp)
     if (!c->fill_worker) {
       c->fill_worker = new tsdf_ctx::FillWorker();
       c->fill_worker->device = c->device; c->fill_worker->stream = c->fill_stream;
       c->fill_worker->th = std::thread([w = c->fill_worker] { w->run(); });
     }
     tsdf_ctx::FillWorker::Job j{c->atlas, tile_mask, {c->d_lvl_mask[0], c->d_lvl_mask[1]}, c->vw, c->vh, c->d_fb_c, c->d_fb_d, (int)c->color_mask_mode, c->keep_color ? 1 : 0,
-                                c->draw_done[c->vol_set], c->fill_done[c->atlas_parity]};
-    c->fill_job_no[c->atlas_parity] = c->draw_wait_job[c->vol_set] = c->fill_worker->submit(j);
-    c->fill_pending[c->atlas_parity] = true;
+                                c->draw_done[set], c->fill_done[pyramid]};
+    c->lanes.fill_queued(c->fill_worker->submit(j));
     if (used) *used = c->fill_stream;
     return TSDF_OK;
   }
   if (c->fill_worker) { c->fill_worker->drain(); HIP_TRY(c, fill_worker_error(c)); }   // (earlier jobs first: the lane is in order)
-  if (c->overlap_fill) HIP_TRY(c, hipStreamWaitEvent(c->fill_stream, c->draw_done[c->vol_set], 0));
+  if (c->overlap_fill) HIP_TRY(c, hipStreamWaitEvent(c->fill_stream, c->draw_done[set], 0));
   timer_begin_on(c, "holefill", fs);
   launch_inpaint_pyramid(fs, c->atlas, tile_mask, c->d_lvl_mask);
   launch_colorfill(fs, c->atlas, c->vw, c->vh, c->d_fb_c, c->d_fb_d, (int)c->color_mask_mode, c->keep_color ? 1 : 0, tile_mask);
   timer_end_on(c, "holefill", fs);
-  if (c->overlap_fill) { HIP_TRY(c, hipEventRecord(c->fill_done[c->atlas_parity], fs)); c->fill_pending[c->atlas_parity] = true; }
+  if (c->overlap_fill) { HIP_TRY(c, hipEventRecord(c->fill_done[pyramid], fs)); c->lanes.fill_queued(); }
   HIP_TRY(c, hipGetLastError());
   if (used) *used = fs;
   return TSDF_OK;
@@ -1938,13 +1934,9 @@ static int32_t overlay_checks(tsdf_ctx* c, const float* mv, const float* pr, Vie
   return overlay_mono(c);
 }
 // fillColors() recorded draw_done[set] BEFORE an overlay, and the integrate() two frames later that overwrites the set waits for that event
-// only: record it again behind the overlay (after the hole-filling job that waits for its previous record has issued that wait)
+// only: record it again behind the overlay
 static int32_t overlay_rerecord_draw(tsdf_ctx* c) {
-  if (c->integ_stream && c->draw_done[c->vol_set]) {
-    if (c->fill_worker) c->fill_worker->wait_issued(c->draw_wait_job[c->vol_set]);
-    HIP_TRY(c, hipEventRecord(c->draw_done[c->vol_set], c->stream));
-    c->draw_pending[c->vol_set] = true;
-  }
+  if (c->integ_stream && c->draw_done[c->lanes.set()]) HIP_TRY(c, record_draw_end(c, c->lanes.draw_end(true)));
   return TSDF_OK;
 }
 int32_t tsdf_draw_calibvis(tsdf_ctx* c, const float* mv, const float* pr) {
@@ -2902,7 +2894,7 @@ int32_t tsdf_timer_end_after_fill(tsdf_ctx* c, const char* name) {
   CHECK_CTX(c);
   if (!name) return TSDF_ERR_INVALID_ARGUMENT;
   if (c->fill_worker) c->fill_worker->drain();
-  timer_end_on(c, name, (c->fill_pending[0] || c->fill_pending[1]) ? c->fill_stream : c->stream);
+  timer_end_on(c, name, c->lanes.any_fill_pending() ? c->fill_stream : c->stream);
   return TSDF_OK;
 }
 // the individual samples recorded since the last tsdf_timer_stats / tsdf_timer_samples of this timer (and resets it)

@@ -8,6 +8,7 @@
 #include "tsdf_common.hpp"
 #include "image_tiles.hpp"
 #include "lane_ahead.hpp"
+#include "draw_lanes.hpp"
 
 using namespace rr;
 
@@ -113,7 +114,7 @@ struct tsdf_ctx {
   // the hole filling may keep to the dirty tiles, what the texture view may show.  Here: the buffers it indexes
   ImageTiles tiles_img{};
   uint8_t* d_touched[3]{};
-  float4* atlas_color[2]{}; float* atlas_depth[2]{}; int atlas_parity = 0;   // the two pyramids (round 3); c->atlas points at the one the latest draw used
+  float4* atlas_color[2]{}; float* atlas_depth[2]{};   // the two pyramids (round 3; which one a draw takes: draw_lanes.hpp); c->atlas points at the one the latest draw used
   // per pyramid the tile byte mask the march leaves for the hole filling (k_inpaint.hip), and scratch masks of levels 1 / 2
   uint8_t* d_fill_mask[2]{}; uint8_t* d_lvl_mask[2]{}; uint64_t n_fills = 0, n_fills_by_tiles = 0;
   uint32_t* d_tri_z = nullptr; float4* d_tri_acc = nullptr; float min_length = 0.0125f;   // triangle-grid back-end; KinectCalibrationFile.cpp:96 default
@@ -171,29 +172,20 @@ struct tsdf_ctx {
   // colour mask + "colour buffer not cleared before this draw" (anaglyph)
   int vp_org[2]{}; float vp_off[2]{};
   uint32_t color_mask_mode = 0; bool keep_color = false;
-  // Stage overlap (round 3): the hole filling of draw f runs on a stream of its own beside whatever the caller queues next -- the brick
-  // passes and the integrate of frame f + 1 do not touch the pyramid or the framebuffer --, tied to the context's stream by two events:
-  // draw_done (below: the fill waits for the march) and fill_done (the next writer / reader of the pyramid or the framebuffer waits for it).
-  hipStream_t fill_stream = nullptr; hipEvent_t fill_done[2] = {nullptr, nullptr}; bool fill_pending[2] = {false, false};   // (per pyramid)
-  // The fill lane's calls are ISSUED by a helper thread (abi.cpp: FillWorker): issuing a c2 frame costs the calling thread ~100 us of HIP runtime
-  // calls -- as long as the device needs for the frame --, 28 of them for the hole filling's 6 launches and 2 event operations, and nothing the caller
-  // does next depends on them having been issued.  fillColors() records draw_done on the context's stream itself and hands the rest over as a job;
-  // whoever needs fill_done[p] first waits (host side, spinning) until the helper has issued that job's record.  Off while timers are on (their
-  // bookkeeping is the caller's thread's) and with RR_FILL_THREAD=0.
-  struct FillWorker; FillWorker* fill_worker = nullptr; uint64_t fill_job_no[2] = {0, 0}, draw_wait_job[2] = {0, 0}; bool fill_thread = true;
-  // ... and a fourth lane (round 3): integrate() of frame f + 1 on `integ_stream` beside the draw of frame f on the context's stream.  Everything
-  // integrate() writes and the draw reads -- the volume, its tile classes, the lists / stamps / counts of the incremental classification --
-  // exists twice and alternates per integrate(): `alt` holds the set not in use (allocated on the first such integrate), and each set evolves
-  // exactly like the single volume of rounds 1 / 2, seeing every other frame (the reference rebuilds the TSDF from scratch every frame,
-  // recon_integration.cpp:249-250: no state is carried from frame to frame).  Events: integ_done (the draw waits for its integrate),
-  // draw_done[set] (recorded behind the draw that read the set: the hole filling waits for it, and so does the integrate two frames later
-  // that overwrites the set), integ_gate (work queued on the context's stream that the lane must not overtake).  Whole-volume contexts with
-  // dense storage only; off with stage overlap off, with the projection cache, and with RR_DEEP=0.
+  // Stage overlap (round 3): the hole filling of draw f on `fill_stream` beside whatever the caller queues next, its calls issued by a helper thread
+  // (abi.cpp: FillWorker), and a fourth lane, integrate() of frame f + 1 on `integ_stream` beside the draw of frame f.  The state and its protocol are
+  // draw_lanes.hpp's -- which volume set and which pyramid are in use, what is in flight on the two lanes, which job of the helper a wait has to see
+  // issued first.  Here: the streams, the events it indexes (fill_done[pyramid], draw_done[set]; integ_done; integ_gate: work queued on the context's
+  // stream that the integrate lane must not overtake), the helper and the second volume set
+  DrawLanes lanes{};
+  hipStream_t fill_stream = nullptr; hipEvent_t fill_done[2] = {nullptr, nullptr};
+  struct FillWorker; FillWorker* fill_worker = nullptr; bool fill_thread = true;
+  // `alt` holds the set not in use (allocated on the first integrate() on the lane): the volume, its tile classes, the lists / stamps / counts of the
+  // incremental classification.  Whole-volume contexts with dense storage only; off with stage overlap off, with the projection cache, and with RR_DEEP=0.
   struct VolSet { float* data = nullptr; uint8_t* cls_all = nullptr; uint32_t* stamp = nullptr; uint32_t* list[2] = {nullptr, nullptr}; uint32_t* counts = nullptr;
                   int parity = 0; bool full = true; uint32_t stampno = 0; } alt;
   hipStream_t integ_stream = nullptr; hipEvent_t integ_done = nullptr, integ_gate = nullptr, draw_done[2] = {nullptr, nullptr};
-  bool integ_pending = false, draw_pending[2] = {false, false}, draw_unrecorded = false, deep = true, deep_failed = false;
-  int vol_set = 0;
+  bool deep = true;
   hipStream_t pre_lane = nullptr; bool pre_on_integ = false;   // the stream the current frame's preparation runs on (pre_stream, or integ_stream: RR_PRE_ON_INTEG)
   bool overlap_fill = true;      // RR_OVERLAP_FILL=0 / tsdf_set_stage_overlap(ctx, 0): everything on the one stream, as in rounds 1 and 2
   // ... and a third lane AHEAD of the context's stream (round 3), preparing frame f + 1 on `pre_stream` while the context's stream still works on frame f:

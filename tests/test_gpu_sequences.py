@@ -361,3 +361,115 @@ def test_lane_ahead_call_orders_equal_one_stream(rr, lane_scenes, order):
     for a in range(4):
         for b in range(a + 1, 4):
             assert (seen[a][0] != seen[b][0]).any(), f"frames {a} and {b} leave the same volume"
+
+
+# ---------------------------------------------------------------------------------------------- the integrate and fill lanes (csrc/draw_lanes.hpp)
+def _march_then_integrate(o, k, scs, dev, mv, pr):
+    """frames 0 and 2: a march with no fillColors() behind it -- the next integrate() marks the draw's end itself; frames 1 and 3: the two calls apart"""
+    o.upload_frame(scs[k]); _bricks(o); o.integrate(); o.draw(mv, pr)
+    if k % 2:
+        o.fillColors()
+
+
+def _two_integrates(o, k, scs, dev, mv, pr):
+    """another frame integrated first: two integrates with no draw in between, each into the other volume set"""
+    o.upload_frame(scs[(k + 1) % 4]); _bricks(o); o.integrate()
+    _plain(o, k, scs, dev, mv, pr)
+
+
+def _two_draws(o, k, scs, dev, mv, pr):
+    o.upload_frame(scs[k]); _bricks(o); o.integrate(); o.drawF(*o.vs[(k + 1) % 4]); o.drawF(mv, pr)
+
+
+def _hole_filling_off(o, k, scs, dev, mv, pr):
+    """off for frames 1 and 2: one pyramid, no fill lane, the march writes the framebuffer"""
+    o.setColorFilling(k in (0, 3))
+    _plain(o, k, scs, dev, mv, pr)
+
+
+def _bbox_after_draw(o, k, scs, dev, mv, pr):
+    _plain(o, k, scs, dev, mv, pr); o.drawBBox(mv, pr)
+
+
+def _mesh_stream_after_draw(o, k, scs, dev, mv, pr):
+    """the frame's mesh behind its draw; every slot is taken and released two frames late"""
+    if not hasattr(o, "meshes"):
+        o.mesh_stream_config(normals=True, colours=True, max_vertices=1 << 18, max_triangles=1 << 19, max_surface_tiles=1 << 12, slots=4)
+        o.meshes, o.meshed = [], 0
+    _plain(o, k, scs, dev, mv, pr)
+    o.mesh_stream(tag=o.meshed)
+    o.meshed += 1
+    if o.meshed > 2:
+        v, t, info = o.mesh_stream_take(wait=True)
+        assert info["overflow"] == 0 and info["tag"] == o.meshed - 3 and info["n_triangles"] > 100
+        o.meshes.append((v.tobytes(), t.tobytes()))
+
+
+def _present_after_draw(o, k, scs, dev, mv, pr):
+    """the frame's read-out behind its draw; acquired and released one frame late"""
+    if not hasattr(o, "presented"):
+        o.present_config(slots=3)
+        o.presented, o.n_presented = [], 0
+    _plain(o, k, scs, dev, mv, pr)
+    o.present(tag=o.n_presented)
+    o.n_presented += 1
+    if o.n_presented > 1:
+        a, tag, _ = o.present_acquire(wait=True)
+        assert tag == o.n_presented - 2
+        o.presented.append(a.tobytes())
+        o.present_release()
+
+
+def _timers_for_one_frame(o, k, scs, dev, mv, pr):
+    """timers on: the hole filling is queued by the caller's thread, behind whatever the helper thread still holds"""
+    o.enable_timers(k == 1)
+    _plain(o, k, scs, dev, mv, pr)
+    o.enable_timers(False)
+
+
+DRAW_LANE_ORDERS = [_plain, _march_then_integrate, _two_integrates, _two_draws, _hole_filling_off, _bbox_after_draw, _mesh_stream_after_draw, _present_after_draw,
+                    _stage_overlap_off_and_on, _timers_for_one_frame]
+DRAW_LANE_CASES = [(f, None) for f in DRAW_LANE_ORDERS] + [(f, flag) for flag in ("LANES_NO_FILL_THREAD", "LANES_NO_INTEGRATE_LANE") for f in (_plain, _bbox_after_draw)]
+
+
+@pytest.mark.parametrize("order,flag", DRAW_LANE_CASES, ids=[f.__name__.lstrip("_") + ("-" + flag[6:].lower() if flag else "") for f, flag in DRAW_LANE_CASES])
+def test_draw_lane_call_orders_equal_one_stream(rr, lane_scenes, order, flag):
+    """integrate() of frame f + 1 runs on a lane of its own beside the draw of frame f, the hole filling of draw f on another (issued by a helper
+    thread) beside whatever follows; two volume sets and two pyramids alternate under them (csrc/draw_lanes.hpp).  Every call order that reaches
+    another branch of that bookkeeping, over four frames that differ from one another (a read of the wrong set or pyramid, an integrate that
+    overtakes the draw of its set, a fill that overtakes its march shows), against a twin created with every kernel on one stream: volume,
+    brick state and framebuffer, bit for bit, and what the mesh stream and the read-out delivered -- first the four frames back to back with
+    nothing read in between, then again with everything read back behind each.  plain and the overlay order also without the helper thread
+    and without the integrate lane."""
+    scs, dev = lane_scenes
+    vs = views(rr, *KW["view"])
+    lanes = rr.ReconIntegrationHip(scs[0], lane_flags=getattr(rr, flag) if flag else 0, **KW)
+    twin = rr.ReconIntegrationHip(scs[0], lane_flags=rr.LANES_ONE_STREAM, **KW)
+    lanes.lanes_on, twin.lanes_on = True, False
+    lanes.vs = twin.vs = vs
+
+    def compare(what):
+        assert_same(dict(tsdf=lanes.tsdf()), dict(tsdf=twin.tsdf()), what)
+        (lc, lf), (tc, tf) = lanes.bricks(), twin.bricks()
+        np.testing.assert_array_equal(lc, tc, err_msg=f"{what}: brick counters"); np.testing.assert_array_equal(lf, tf, err_msg=f"{what}: brick flags")
+        a, b = outputs(lanes), outputs(twin)
+        assert_same(dict(fb_color=a["fb_color"], fb_depth=a["fb_depth"]), dict(fb_color=b["fb_color"], fb_depth=b["fb_depth"]), what)
+        return twin.tsdf(), b["fb_depth"]
+
+    for k in range(4):
+        for o in (lanes, twin):
+            order(o, k, scs, dev, *vs[k])
+    compare("four frames back to back")
+    seen = []
+    for k in range(4):
+        for o in (lanes, twin):
+            order(o, k, scs, dev, *vs[k])
+        seen.append(compare(f"frame {k}, read back"))
+    assert all((d < 1).sum() > 100 for _, d in seen)
+    for a in range(4):
+        for b in range(a + 1, 4):
+            assert (seen[a][0] != seen[b][0]).any(), f"frames {a} and {b} leave the same volume"
+    for what in ("meshes", "presented"):
+        got, want = getattr(lanes, what, []), getattr(twin, what, [])
+        assert len(got) == len(want) and all(g == w for g, w in zip(got, want)), f"{what}: the lanes delivered something else"
+        assert not hasattr(lanes, what) or (len(got) >= 6 and len(set(got)) >= 4)
