@@ -576,7 +576,7 @@ int32_t alloc_frame_slot(tsdf_ctx* c, int k) {
   return TSDF_OK;
 }
 void use_frame_slot(tsdf_ctx* c, int k) {
-  c->cur_slot = k;
+  c->intake.slots.made_current(k);
   c->frame.dqs = c->slots[k].dqs; c->frame.depth = c->slots[k].depth; c->frame.color = c->slots[k].color;
   c->frame.ranges = c->use_ranges ? c->slots[k].ranges : nullptr; c->frame.rcw = ((int)c->cfg.depth_w + 7) / 8; c->frame.rch = ((int)c->cfg.depth_h + 7) / 8;
 }
@@ -869,9 +869,7 @@ int32_t tsdf_destroy(tsdf_ctx* c) {
   if (c->pre_done) hipEventDestroy(c->pre_done);
   for (hipEvent_t g : c->pre_gate) if (g) hipEventDestroy(g);
   if (c->src_ready) hipEventDestroy(c->src_ready);
-  if (c->normals_read) hipEventDestroy(c->normals_read);
-  if (c->raw_read) hipEventDestroy(c->raw_read);
-  if (c->products_read) hipEventDestroy(c->products_read);
+  for (hipEvent_t e : c->read_fence) if (e) hipEventDestroy(e);
   hipFree(c->d_mvt_vtx); hipFree(c->d_calibvis_skipped);
   if (c->fill_worker) {
     c->fill_worker->stop.store(true);
@@ -1010,6 +1008,28 @@ int32_t tsdf_set_calibration(tsdf_ctx* c, uint32_t i, const float* inv, const ui
   return TSDF_OK;
 }
 
+// ---- the frame intake (frame_intake.hpp)
+static tsdf_ctx::FrameSlot& current_slot(tsdf_ctx* c) { return c->slots[c->intake.slots.current()]; }
+static const float* raw_depth(const tsdf_ctx* c) { return c->intake.raw.read_from() == kRawOwn ? c->d_raw : c->raw_src; }
+// a reader of a single-buffered image was queued on the context's stream: record fence f behind it
+static int32_t record_read_fence(tsdf_ctx* c, int f) {
+  c->intake.fences.reader_queued(f);
+  if (!c->read_fence[f]) HIP_TRY(c, hipEventCreateWithFlags(&c->read_fence[f], hipEventDisableTiming));
+  HIP_TRY(c, hipEventRecord(c->read_fence[f], c->stream));
+  return TSDF_OK;
+}
+// ... and the lane that rewrites the image waits for it
+static int32_t wait_read_fence(tsdf_ctx* c, int f, hipStream_t lane) {
+  if (c->intake.fences.writer_takes(f, lane != c->stream)) HIP_TRY(c, hipStreamWaitEvent(lane, c->read_fence[f], 0));
+  return TSDF_OK;
+}
+// the producer of a frame's device arrays may be work on the context's stream: the lane goes behind all of it
+static int32_t wait_for_producer(tsdf_ctx* c, hipStream_t lane) {
+  if (!c->src_ready) HIP_TRY(c, hipEventCreateWithFlags(&c->src_ready, hipEventDisableTiming));
+  HIP_TRY(c, hipEventRecord(c->src_ready, c->stream));
+  HIP_TRY(c, hipStreamWaitEvent(lane, c->src_ready, 0));
+  return TSDF_OK;
+}
 // On the lane ahead the re-layout launch of a new frame also clears the brick counters the frame's clearOccupiedBricks() is going to use
 // (it flips to them here instead): one launch and one dependent step less on the lane.
 static uint32_t* counters_for_upload(tsdf_ctx* c, hipStream_t lane) {
@@ -1021,7 +1041,7 @@ static uint32_t* counters_for_upload(tsdf_ctx* c, hipStream_t lane) {
 // the previous frame), once per frame of the lane; c->frame then points at it, so everything queued from now on reads the new frame.
 static int32_t begin_slot_write(tsdf_ctx* c, hipStream_t lane, bool keep_colour) {
   if (!c->ahead.slot_for_write(lane != c->stream)) return TSDF_OK;      // (nothing queued reads the current slot -- the first frame --: in place)
-  const int old = c->cur_slot, t = alt_of(old);
+  const int old = c->intake.slots.current(), t = alt_of(old);
   if (int32_t rc = alloc_frame_slot(c, t)) return rc;
   if (keep_colour) {                                                     // "colour may be NULL (keeps the previous one)": the previous one lives in the other slot
     const size_t nc = (size_t)c->cfg.num_streams * c->frame.cw * c->frame.ch;
@@ -1042,10 +1062,10 @@ int32_t tsdf_upload_frame(tsdf_ctx* c, const float* depth_rg, const float* quali
   HIP_TRY(c, hipMemcpyAsync(c->d_stage_q, quality, np * 4, hipMemcpyHostToDevice, lane));
   HIP_TRY(c, hipMemcpyAsync(c->d_stage_s, silhouette, np * 4, hipMemcpyHostToDevice, lane));
   if (colour) HIP_TRY(c, hipMemcpyAsync(c->d_stage_col, colour, nc * 3, hipMemcpyHostToDevice, lane));
-  launch_pack_frame_fused(lane, c->d_stage_depth, c->d_stage_q, c->d_stage_s, (float4*)F.dqs, (float*)c->frame.depth, c->slots[c->cur_slot].ranges,
+  launch_pack_frame_fused(lane, c->d_stage_depth, c->d_stage_q, c->d_stage_s, (float4*)F.dqs, (float*)c->frame.depth, current_slot(c).ranges,
                           (int)c->cfg.num_streams, F.w, F.h, colour ? c->d_stage_col : nullptr, (uchar4*)F.color, nc, counters_for_upload(c, lane), (uint32_t)c->counter_words);
   HIP_TRY(c, hipGetLastError());
-  c->slots[c->cur_slot].have = true; c->slots[c->cur_slot].origin = tsdf_ctx::kFramePre;
+  c->intake.slots.preprocessed_written();
   pre_leave(c, lane);
   return TSDF_OK;
 }
@@ -1062,20 +1082,16 @@ int32_t tsdf_upload_frame_dev(tsdf_ctx* c, const float* depth_rg, const float* q
     FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "device arrays must be aligned to their element size (depth 8 bytes, the others 4)");
   HIP_TRY(c, hipSetDevice(c->device));
   const hipStream_t lane = pre_enter(c);
-  if (lane != c->stream && !(flags & TSDF_FRAME_ARRAYS_COMPLETE)) {      // the producer may be work on the context's stream: behind all of it
-    if (!c->src_ready) HIP_TRY(c, hipEventCreateWithFlags(&c->src_ready, hipEventDisableTiming));
-    HIP_TRY(c, hipEventRecord(c->src_ready, c->stream));
-    HIP_TRY(c, hipStreamWaitEvent(lane, c->src_ready, 0));
-  }
+  if (lane != c->stream && !(flags & TSDF_FRAME_ARRAYS_COMPLETE)) { if (int32_t rc = wait_for_producer(c, lane)) return rc; }
   if (int32_t rc = begin_slot_write(c, lane, colour == nullptr)) return rc;
   const FrameImages& F = c->frame;
   const size_t nc = (size_t)c->cfg.num_streams * F.cw * F.ch;
   timer_begin_on(c, "0repack", lane);
-  launch_pack_frame_fused(lane, depth_rg, quality, silhouette, (float4*)F.dqs, (float*)c->frame.depth, c->slots[c->cur_slot].ranges,
+  launch_pack_frame_fused(lane, depth_rg, quality, silhouette, (float4*)F.dqs, (float*)c->frame.depth, current_slot(c).ranges,
                           (int)c->cfg.num_streams, F.w, F.h, colour, (uchar4*)F.color, nc, counters_for_upload(c, lane), (uint32_t)c->counter_words);
   timer_end_on(c, "0repack", lane);
   HIP_TRY(c, hipGetLastError());
-  c->slots[c->cur_slot].have = true; c->slots[c->cur_slot].origin = tsdf_ctx::kFramePre;
+  c->intake.slots.preprocessed_written();
   pre_leave(c, lane);
   return TSDF_OK;
 }
@@ -1104,10 +1120,10 @@ int32_t tsdf_frame_staging(tsdf_ctx* c, float** depth_rg, float** quality, float
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, block_pipeline(c));                                          // the caller manages the two frame slots himself from here on
   if (int32_t rc = ensure_async_upload(c)) return rc;
-  const int k = c->stage_k;
-  if (c->stage_busy[k]) { HIP_TRY(c, hipEventSynchronize(c->stage_done[k])); c->stage_busy[k] = false; }   // its last upload has left the buffer
+  const FrameSlots::Staging G = c->intake.slots.staging();
+  if (G.wait) HIP_TRY(c, hipEventSynchronize(c->stage_done[G.index]));   // its last upload has left the buffer
   const size_t np = (size_t)c->cfg.num_streams * c->frame.w * c->frame.h;
-  uint8_t* b = c->h_stage[k];
+  uint8_t* b = c->h_stage[G.index];
   if (depth_rg) *depth_rg = (float*)b;
   if (quality) *quality = (float*)(b + np * 8);
   if (silhouette) *silhouette = (float*)(b + np * 12);
@@ -1125,17 +1141,16 @@ int32_t tsdf_upload_frame_async(tsdf_ctx* c, const float* depth_rg, const float*
   if (quality && quality != sq) memcpy(sq, quality, np * 4);
   if (silhouette && silhouette != ss) memcpy(ss, silhouette, np * 4);
   if (colour && colour != sc) { memcpy(sc, colour, nc * 3); with_colour = 1; }
-  const int k = c->stage_k, t = alt_of(c->cur_slot);
-  tsdf_ctx::FrameSlot& S = c->slots[t];
-  if (S.in_use) HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, S.released, 0));   // the path's reads of slot t were all queued before `released`
+  const FrameSlots::Async A = c->intake.slots.async_queued();
+  const int k = A.staging;
+  tsdf_ctx::FrameSlot& S = c->slots[A.slot];
+  if (A.wait_released) HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, S.released, 0));   // the path's reads of the slot were all queued before `released`
   const size_t bytes = np * 16 + (with_colour ? nc * 3 : 0);
   HIP_TRY(c, hipMemcpyAsync(c->d_astage, c->h_stage[k], bytes, hipMemcpyHostToDevice, c->copy_stream));
   HIP_TRY(c, hipEventRecord(c->stage_done[k], c->copy_stream));
-  c->stage_busy[k] = true; c->stage_k ^= 1;
   launch_pack_frame_fused(c->copy_stream, (const float*)c->d_astage, (const float*)(c->d_astage + np * 8), (const float*)(c->d_astage + np * 12), S.dqs, S.depth, S.ranges,
                           (int)c->cfg.num_streams, c->frame.w, c->frame.h, with_colour ? c->d_astage + np * 16 : nullptr, S.color, nc);
   HIP_TRY(c, hipEventRecord(S.ready, c->copy_stream));
-  S.pending = true; S.have = true; S.origin = tsdf_ctx::kFramePre;
   HIP_TRY(c, hipGetLastError());
   return TSDF_OK;
 }
@@ -1145,16 +1160,14 @@ int32_t tsdf_select_frame_slot(tsdf_ctx* c, uint32_t slot) {
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, block_pipeline(c));                                          // the caller manages the two frame slots himself from here on
   if (int32_t rc = alloc_frame_slot(c, (int)slot)) return rc;
-  tsdf_ctx::FrameSlot& N = c->slots[slot];
-  if ((int)slot != c->cur_slot) {
-    tsdf_ctx::FrameSlot& O = c->slots[c->cur_slot];
-    if (O.released) { HIP_TRY(c, hipEventRecord(O.released, c->stream)); O.in_use = true; }
-  }
-  if (N.pending) { HIP_TRY(c, hipStreamWaitEvent(c->stream, N.ready, 0)); N.pending = false; }   // the path waits on the GPU, not on the host
+  tsdf_ctx::FrameSlot& O = current_slot(c);
+  const FrameSlots::Select T = c->intake.slots.select((int)slot, O.released != nullptr);
+  if (T.record_released) HIP_TRY(c, hipEventRecord(O.released, c->stream));
+  if (T.wait_ready) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->slots[slot].ready, 0));   // the path waits on the GPU, not on the host
   use_frame_slot(c, (int)slot);
   return TSDF_OK;
 }
-int32_t tsdf_current_frame_slot(const tsdf_ctx* c, uint32_t* slot) { CHECK_CTX(c); if (!slot) return TSDF_ERR_INVALID_ARGUMENT; *slot = (uint32_t)c->cur_slot; return TSDF_OK; }
+int32_t tsdf_current_frame_slot(const tsdf_ctx* c, uint32_t* slot) { CHECK_CTX(c); if (!slot) return TSDF_ERR_INVALID_ARGUMENT; *slot = (uint32_t)c->intake.slots.current(); return TSDF_OK; }
 
 // ---- image pre-processing (NetKinectArray::processTextures)
 static int32_t ensure_pre_buffers(tsdf_ctx* c) {
@@ -1175,13 +1188,6 @@ static int32_t ensure_pre_buffers(tsdf_ctx* c) {
   }
   return TSDF_OK;
 }
-// an MVT draw still queued on the context's stream reads d_raw: a raw upload that rewrites it on the lane ahead waits for that draw
-static int32_t wait_raw_read(tsdf_ctx* c, hipStream_t lane) {
-  if (!c->raw_read_pending) return TSDF_OK;
-  if (lane != c->stream) HIP_TRY(c, hipStreamWaitEvent(lane, c->raw_read, 0));
-  c->raw_read_pending = false;
-  return TSDF_OK;
-}
 // The raw frame (NetKinectArray::update(): depth + colour of every sensor) goes through the lane ahead like a pre-processed one does (round 4): its
 // colour is re-laid out into the frame slot the lane writes, its depth is what tsdf_process_textures() -- on the same lane -- starts from.
 int32_t tsdf_upload_raw_frame(tsdf_ctx* c, const float* depth_raw, const uint8_t* colour) {
@@ -1191,13 +1197,13 @@ int32_t tsdf_upload_raw_frame(tsdf_ctx* c, const float* depth_raw, const uint8_t
   if (int32_t rc = ensure_pre_buffers(c)) return rc;
   const hipStream_t lane = pre_enter(c);
   if (int32_t rc = begin_slot_write(c, lane, false)) return rc;
-  if (int32_t rc = wait_raw_read(c, lane)) return rc;
+  if (int32_t rc = wait_read_fence(c, kRawRead, lane)) return rc;   // an MVT draw (or a Lab window) still queued on the context's stream reads d_raw
   const FrameImages& F = c->frame;
   const size_t np = (size_t)c->cfg.num_streams * F.w * F.h, nc = (size_t)c->cfg.num_streams * F.cw * F.ch;
   HIP_TRY(c, hipMemcpyAsync(c->d_raw, depth_raw, np * sizeof(float), hipMemcpyHostToDevice, lane));
   HIP_TRY(c, hipMemcpyAsync(c->d_stage_col, colour, nc * 3, hipMemcpyHostToDevice, lane));
   c->pending_rgb = c->d_stage_col;                                       // its RGBA8 re-layout rides along in tsdf_process_textures' first launch
-  c->raw_src = c->d_raw; c->have_raw = true; ++c->raw_generation; c->slots[c->cur_slot].origin = tsdf_ctx::kFrameRawPending;
+  c->intake.raw.uploaded(kRawOwn, true); c->intake.slots.raw_arrived();
   pre_leave(c, lane);
   return TSDF_OK;
 }
@@ -1210,14 +1216,10 @@ static int32_t upload_raw_frame_dev_impl(tsdf_ctx* c, const float* depth_raw, co
   HIP_TRY(c, hipSetDevice(c->device));
   if (int32_t rc = ensure_pre_buffers(c)) return rc;
   const hipStream_t lane = pre_enter(c, defer_gate);                      // (nothing below writes what the previous frames' draws read: flips of host pointers, a wait for the producer)
-  if (lane != c->stream && !(flags & TSDF_FRAME_ARRAYS_COMPLETE)) {      // the producer may be work on the context's stream: behind all of it
-    if (!c->src_ready) HIP_TRY(c, hipEventCreateWithFlags(&c->src_ready, hipEventDisableTiming));
-    HIP_TRY(c, hipEventRecord(c->src_ready, c->stream));
-    HIP_TRY(c, hipStreamWaitEvent(lane, c->src_ready, 0));
-  }
+  if (lane != c->stream && !(flags & TSDF_FRAME_ARRAYS_COMPLETE)) { if (int32_t rc = wait_for_producer(c, lane)) return rc; }
   if (int32_t rc = begin_slot_write(c, lane, false)) return rc;
   c->pending_rgb = colour;                                               // its RGBA8 re-layout rides along in tsdf_process_textures' first launch
-  c->raw_src = depth_raw; c->have_raw = true; ++c->raw_generation; c->slots[c->cur_slot].origin = tsdf_ctx::kFrameRawPending;
+  c->raw_src = depth_raw; c->intake.raw.uploaded(kRawCaller, true); c->intake.slots.raw_arrived();
   pre_leave(c, lane);
   return TSDF_OK;
 }
@@ -1279,9 +1281,10 @@ int32_t tsdf_upload_wire_frame(tsdf_ctx* c, const void* message, uint64_t bytes,
   if (int32_t rc = ensure_pre_buffers(c)) return rc;
   if (c->wire_capacity < want) {
     HIP_TRY(c, sync_ctx(c));
+    c->intake.raw.wire_reallocated();
     for (int k = 0; k < 2; ++k) {
       if (c->h_wire[k]) HIP_TRY(c, hipHostFree(c->h_wire[k]));
-      c->h_wire[k] = nullptr; c->wire_pending[k] = false;
+      c->h_wire[k] = nullptr;
       HIP_TRY(c, hipHostMalloc((void**)&c->h_wire[k], want, hipHostMallocDefault));
       if (!c->wire_done[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->wire_done[k], hipEventDisableTiming));
     }
@@ -1290,16 +1293,16 @@ int32_t tsdf_upload_wire_frame(tsdf_ctx* c, const void* message, uint64_t bytes,
     c->wire_capacity = want;
   }
   // double buffer: the copy out of slot k may still be in flight from two frames ago
-  const int k = c->wire_slot; c->wire_slot ^= 1;
-  if (c->wire_pending[k]) HIP_TRY(c, hipEventSynchronize(c->wire_done[k]));
+  const RawFrame::Wire W = c->intake.raw.wire_taken();
+  const int k = W.index;
+  if (W.wait) HIP_TRY(c, hipEventSynchronize(c->wire_done[k]));
   memcpy(c->h_wire[k], message, want);                                   // readLoop's memcpy into the mapped PBO, :516-520
   if (timestamp) memcpy(timestamp, c->h_wire[k], sizeof(double));        // the first 8 bytes of the message, :510
   const hipStream_t lane = pre_enter(c);                                 // (round 4) the lane ahead: copy, unpack / DXT decode and the passes that follow
   if (int32_t rc = begin_slot_write(c, lane, false)) return rc;
-  if (int32_t rc = wait_raw_read(c, lane)) return rc;
+  if (int32_t rc = wait_read_fence(c, kRawRead, lane)) return rc;   // an MVT draw (or a Lab window) still queued on the context's stream reads d_raw
   HIP_TRY(c, hipMemcpyAsync(c->d_wire, c->h_wire[k], want, hipMemcpyHostToDevice, lane));
   HIP_TRY(c, hipEventRecord(c->wire_done[k], lane));
-  c->wire_pending[k] = true;
   WireLayout L{};
   L.msg = c->d_wire; L.rec = (uint32_t)(cs + ds); L.cs = (uint32_t)cs; L.n = (int)c->cfg.num_streams;
   L.cw = c->frame.cw; L.ch = c->frame.ch; L.w = c->frame.w; L.h = c->frame.h;
@@ -1308,39 +1311,38 @@ int32_t tsdf_upload_wire_frame(tsdf_ctx* c, const void* message, uint64_t bytes,
   launch_wire_unpack(lane, L, (uchar4*)c->frame.color, c->d_raw);
   timer_end_on(c, "0ingest", lane);
   HIP_TRY(c, hipGetLastError());
-  c->raw_src = c->d_raw; c->have_raw = true; ++c->raw_generation; c->slots[c->cur_slot].origin = tsdf_ctx::kFrameRawPending;
+  c->intake.raw.uploaded(kRawOwn, false); c->intake.slots.raw_arrived();   // (the unpack wrote the colour into the slot)
   pre_leave(c, lane);
   return TSDF_OK;
 }
-// the raw frame's colour waits for tsdf_process_textures' first launch (tsdf_ctx::pending_rgb): whoever reads the frame slot's colour before that asks for it here
+// the raw frame's colour waits for tsdf_process_textures' first launch: whoever reads the frame slot's colour before that asks for it here
 static int32_t flush_pending_colour(tsdf_ctx* c) {
-  if (!c->pending_rgb) return TSDF_OK;
+  if (!c->intake.raw.take_colour()) return TSDF_OK;
   const hipStream_t lane = pre_enter(c);
   launch_pack_color(lane, c->pending_rgb, (uchar4*)c->frame.color, (size_t)c->cfg.num_streams * c->frame.cw * c->frame.ch);
-  c->pending_rgb = nullptr;
   HIP_TRY(c, hipGetLastError());
   pre_leave(c, lane);
   return TSDF_OK;
 }
 int32_t tsdf_download_raw_frame(tsdf_ctx* c, float* depth_raw, uint8_t* colour_rgba) {
   CHECK_CTX(c);
-  if (!c->have_raw) FAIL(c, TSDF_ERR_STATE, "no raw frame uploaded");
+  if (!c->intake.raw.resident()) FAIL(c, TSDF_ERR_STATE, "no raw frame uploaded");
   HIP_TRY(c, hipSetDevice(c->device));
   if (int32_t rc = flush_pending_colour(c)) return rc;
   HIP_TRY(c, sync_ctx(c));
   const size_t np = (size_t)c->cfg.num_streams * c->frame.w * c->frame.h, nc = (size_t)c->cfg.num_streams * c->frame.cw * c->frame.ch;
-  if (depth_raw) HIP_TRY(c, hipMemcpy(depth_raw, c->raw_src, np * 4, hipMemcpyDeviceToHost));
+  if (depth_raw) HIP_TRY(c, hipMemcpy(depth_raw, raw_depth(c), np * 4, hipMemcpyDeviceToHost));
   if (colour_rgba) HIP_TRY(c, hipMemcpy(colour_rgba, c->frame.color, nc * 4, hipMemcpyDeviceToHost));
   return TSDF_OK;
 }
 int32_t tsdf_set_preprocess(tsdf_ctx* c, int32_t filter_textures, int32_t processed_depth, int32_t refine) {
   CHECK_CTX(c);
-  c->pre.filter_textures = filter_textures != 0; c->use_processed_depth = processed_depth != 0; c->pre.refine = refine != 0;
+  c->pre.filter_textures = filter_textures != 0; c->intake.raw.set_processed_depth(processed_depth != 0); c->pre.refine = refine != 0;
   return TSDF_OK;
 }
 static PreBuffers pre_buffers(tsdf_ctx* c) {
   PreBuffers B{};
-  B.raw = c->raw_src; B.depth2 = c->d_depth2; B.fdepth = c->use_processed_depth ? c->d_depth2 : c->raw_src;
+  B.raw = raw_depth(c); B.depth2 = c->d_depth2; B.fdepth = c->intake.raw.processed_depth() ? c->d_depth2 : B.raw;
   B.depth_rg = c->d_depth_rg; B.lab = c->d_lab; B.depth_b = c->d_depth_b; B.normal = c->d_normal;
   B.dqs = (float4*)c->frame.dqs; B.depth_plane = (float*)c->frame.depth;
   B.cand_count = c->d_pre_blocks; B.cand_list = c->d_pre_blocks + 1; B.cand_cap = c->pre_cand_cap; B.blk_flag = c->d_pre_blocks + 1 + c->pre_cand_cap;
@@ -1352,7 +1354,7 @@ static PreBuffers pre_buffers(tsdf_ctx* c) {
 // into the frame slot and runs the three passes that write what draws read (depth plane, packed texel, range cells, brick counters).
 static int32_t process_textures_impl(tsdf_ctx* c, int phase) {
   CHECK_CTX(c);
-  if (!c->have_raw) FAIL(c, TSDF_ERR_STATE, "no raw frame uploaded (tsdf_upload_raw_frame)");
+  if (!c->intake.raw.resident()) FAIL(c, TSDF_ERR_STATE, "no raw frame uploaded (tsdf_upload_raw_frame)");
   for (uint32_t i = 0; i < c->cfg.num_streams; ++i) {
     if (!c->have_calib[i] || !c->luts.s[i].xyz || !c->luts.s[i].uv) FAIL(c, TSDF_ERR_STATE, "stream %u needs cv_xyz and cv_uv (tsdf_set_calibration)", i);
     if (!c->have_limits[i] || !c->have_cam[i]) FAIL(c, TSDF_ERR_STATE, "stream %u needs tsdf_set_depth_limits and tsdf_set_camera_position", i);
@@ -1362,40 +1364,34 @@ static int32_t process_textures_impl(tsdf_ctx* c, int phase) {
   // the brick counters clearOccupiedBricks() flipped to, its own intermediate images), so they run beside the previous frames' integrate and draw.
   const hipStream_t lane = pre_enter(c, phase == 1);
   if (int32_t rc = begin_slot_write(c, lane, true)) return rc;          // (already done by the raw upload of this frame; a re-run of an old raw frame takes the colour along)
-  if (phase != 1 && c->normals_read_pending) {                           // the point / triangle-grid back-ends read the normal image this call rewrites
-    if (lane != c->stream) HIP_TRY(c, hipStreamWaitEvent(lane, c->normals_read, 0));
-    c->normals_read_pending = false;
-  }
-  if (c->products_read_pending) {                                        // a sensor texture window read the products this call rewrites (phase 1: d_depth2 and the filter pass's images)
-    if (lane != c->stream) HIP_TRY(c, hipStreamWaitEvent(lane, c->products_read, 0));
-    c->products_read_pending = false;
-  }
+  if (phase != 1) { if (int32_t rc = wait_read_fence(c, kNormalsRead, lane)) return rc; }   // the point back-end reads the normal image this call rewrites
+  if (int32_t rc = wait_read_fence(c, kProductsRead, lane)) return rc;   // a sensor texture window read the products this call rewrites (phase 1: d_depth2 and the filter pass's images)
   PreParams& P = c->pre;
   P.W = c->frame.w; P.H = c->frame.h; P.N = (int)c->cfg.num_streams;
   for (int a = 0; a < 3; ++a) { P.bbox_min[a] = c->cfg.bbox_min[a]; P.bbox_max[a] = c->cfg.bbox_max[a]; }
   const PreBuffers B = pre_buffers(c);
-  c->pre_generation = c->raw_generation; c->pre_processed_depth = c->use_processed_depth;
+  c->intake.raw.passes_started();
+  const uint8_t* const rgb = phase != 1 && c->intake.raw.take_colour() ? c->pending_rgb : nullptr;   // the colour rides along in the first launch behind the gate
   if (phase != 2) timer_begin_on(c, "1preprocess", lane);
   const size_t ncol = (size_t)c->cfg.num_streams * c->frame.cw * c->frame.ch;
-  float4* const ranges = c->slots[c->cur_slot].ranges;
+  float4* const ranges = current_slot(c).ranges;
   uchar4* const rgba = (uchar4*)c->frame.color;
   auto launch = [&](unsigned passes, const uint8_t* rgb) { launch_preprocess(lane, P, B, c->luts, c->frame, c->br, ranges, passes, rgb, rgba, ncol); };
   if (phase == 1) launch(kPreMorph | kPreFilter, nullptr);
-  else if (phase == 2) launch(kPreRelayout | kPreBoundary | kPreNormal | kPreQuality, c->pending_rgb);
+  else if (phase == 2) launch(kPreRelayout | kPreBoundary | kPreNormal | kPreQuality, rgb);
   else if (c->timers_on && c->timer_filter.find(",k_pre_") != std::string::npos) {   // each pass between its own pair of events, when the timer filter NAMES them (a pair costs the lane ~7 us)
     static const struct { unsigned pass; const char* name; } each[5] = {
         {kPreMorph, "k_pre_morph"}, {kPreFilter, "k_pre_filter"}, {kPreBoundary, "k_pre_boundary"}, {kPreNormal, "k_pre_normal"}, {kPreQuality, "k_pre_quality"}};
     for (const auto& e : each) {
       timer_begin_on(c, e.name, lane);
-      launch(e.pass, c->pending_rgb);
+      launch(e.pass, rgb);
       timer_end_on(c, e.name, lane);
     }
-  } else launch(kPreAll, c->pending_rgb);
+  } else launch(kPreAll, rgb);
   HIP_TRY(c, hipGetLastError());
   if (phase != 1) {
-    c->pending_rgb = nullptr;
     timer_end_on(c, "1preprocess", lane);
-    c->slots[c->cur_slot].have = true; c->slots[c->cur_slot].origin = tsdf_ctx::kFrameRawDone; c->normals_uploaded = false;
+    c->intake.raw.passes_completed(); c->intake.slots.passes_completed();
   }
   pre_leave(c, lane);
   return TSDF_OK;
@@ -1404,7 +1400,7 @@ int32_t tsdf_process_textures(tsdf_ctx* c) { return process_textures_impl(c, 0);
 // the Lab image of the filter pass: the passes evaluate it only where the boundary pass reads it (k_pre_boundary); the whole image is produced on request, on the
 // context's stream, from the inputs of the frame that was processed -- which must still be the resident ones
 static int32_t produce_lab(tsdf_ctx* c) {
-  if (c->pre_generation != c->raw_generation || c->pre_processed_depth != c->use_processed_depth)
+  if (!c->intake.raw.lab_current())
     FAIL(c, TSDF_ERR_STATE, "the Lab image is produced on request from the processed frame's inputs, and a newer raw frame has replaced them (download before the next upload)");
   launch_pre_lab(c->stream, c->pre, pre_buffers(c), c->luts, c->frame);
   HIP_TRY(c, hipGetLastError());
@@ -1412,7 +1408,7 @@ static int32_t produce_lab(tsdf_ctx* c) {
 }
 int32_t tsdf_download_preprocessed(tsdf_ctx* c, float* depth2, float* depth_rg, float* lab, float* depth_b, float* sil, float* normals, float* quality) {
   CHECK_CTX(c);
-  if (!c->have_raw) FAIL(c, TSDF_ERR_STATE, "nothing was pre-processed yet");
+  if (!c->intake.raw.resident()) FAIL(c, TSDF_ERR_STATE, "nothing was pre-processed yet");
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, sync_ctx(c));
   const size_t np = (size_t)c->cfg.num_streams * c->frame.w * c->frame.h;
@@ -1433,7 +1429,7 @@ int32_t tsdf_download_preprocessed(tsdf_ctx* c, float* depth2, float* depth_rg, 
 }
 
 static int32_t require_inputs(tsdf_ctx* c, bool need_xyz, bool need_uv) {
-  if (!c->slots[c->cur_slot].have) FAIL(c, TSDF_ERR_STATE, "no frame uploaded (tsdf_upload_frame)");
+  if (!c->intake.slots.have_frame()) FAIL(c, TSDF_ERR_STATE, "no frame uploaded (tsdf_upload_frame)");
   for (uint32_t i = 0; i < c->cfg.num_streams; ++i) {
     if (!c->have_calib[i]) FAIL(c, TSDF_ERR_STATE, "stream %u has no calibration (tsdf_set_calibration)", i);
     if (need_xyz && !c->luts.s[i].xyz) FAIL(c, TSDF_ERR_STATE, "stream %u has no cv_xyz volume", i);
@@ -1675,7 +1671,7 @@ int32_t tsdf_upload_normals(tsdf_ctx* c, const float* normals_rgb) {
   for (size_t i = 0; i < np; ++i) padded[i] = make_float4(normals_rgb[3 * i], normals_rgb[3 * i + 1], normals_rgb[3 * i + 2], 0.0f);
   HIP_TRY(c, sync_ctx(c));
   HIP_TRY(c, hipMemcpy(c->d_normal, padded.data(), np * sizeof(float4), hipMemcpyHostToDevice));
-  c->normals_uploaded = true;
+  c->intake.raw.normals_were_uploaded();
   return TSDF_OK;
 }
 int32_t tsdf_view_matrices(const float* mv, const float* pr, uint32_t vw, uint32_t vh, const float* bbox_min, const float* bbox_max, float* out) {
@@ -1715,11 +1711,7 @@ int32_t tsdf_draw_points(tsdf_ctx* c, const float* mv, const float* pr) {
   HIP_TRY(c, begin_framebuffer_write(c));
   launch_draw_points(c->stream, P, Q, c->luts, F, c->d_comp_key, c->d_fb_c, c->d_fb_d);
   timer_end(c, "points");
-  if (c->d_normal && pipelined(c)) {                                     // the next tsdf_process_textures() on the lane ahead rewrites the normal image
-    if (!c->normals_read) HIP_TRY(c, hipEventCreateWithFlags(&c->normals_read, hipEventDisableTiming));
-    HIP_TRY(c, hipEventRecord(c->normals_read, c->stream));
-    c->normals_read_pending = true;
-  }
+  if (c->d_normal && pipelined(c)) { if ((rc = record_read_fence(c, kNormalsRead))) return rc; }   // the next tsdf_process_textures() on the lane ahead rewrites the normal image
   HIP_TRY(c, hipGetLastError());
   return TSDF_OK;
 }
@@ -1753,7 +1745,7 @@ int32_t tsdf_draw_trigrid(tsdf_ctx* c, const float* mv, const float* pr) {
 int32_t tsdf_draw_mvt(tsdf_ctx* c, const float* mv, const float* pr) {
   CHECK_CTX(c);
   if (!mv || !pr) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "null matrix");
-  if (!c->have_raw) FAIL(c, TSDF_ERR_STATE, "no raw frame uploaded (tsdf_upload_raw_frame / tsdf_upload_raw_frame_dev / tsdf_upload_wire_frame)");
+  if (!c->intake.raw.resident()) FAIL(c, TSDF_ERR_STATE, "no raw frame uploaded (tsdf_upload_raw_frame / tsdf_upload_raw_frame_dev / tsdf_upload_wire_frame)");
   for (uint32_t i = 0; i < c->cfg.num_streams; ++i) {
     if (!c->have_calib[i] || !c->luts.s[i].xyz || !c->luts.s[i].uv) FAIL(c, TSDF_ERR_STATE, "stream %u needs cv_xyz and cv_uv (tsdf_set_calibration)", i);
   }
@@ -1773,15 +1765,11 @@ int32_t tsdf_draw_mvt(tsdf_ctx* c, const float* mv, const float* pr) {
   HIP_TRY(c, join_pre(c));
   timer_begin(c, "mvt");
   HIP_TRY(c, begin_framebuffer_write(c));
-  launch_draw_mvt(c->stream, P, Q, c->luts, c->frame, c->raw_src, c->min_length, c->d_mvt_vtx, c->d_tri_z, c->d_tri_acc, c->d_fb_c, c->d_fb_d);
+  launch_draw_mvt(c->stream, P, Q, c->luts, c->frame, raw_depth(c), c->min_length, c->d_mvt_vtx, c->d_tri_z, c->d_tri_acc, c->d_fb_c, c->d_fb_d);
   timer_end(c, "mvt");
   HIP_TRY(c, hipGetLastError());
   c->have_mvt = true;
-  if (pipelined(c)) {                                                    // the next raw upload on the lane ahead rewrites d_raw
-    if (!c->raw_read) HIP_TRY(c, hipEventCreateWithFlags(&c->raw_read, hipEventDisableTiming));
-    HIP_TRY(c, hipEventRecord(c->raw_read, c->stream));
-    c->raw_read_pending = true;
-  }
+  if (pipelined(c)) { if (int32_t rc = record_read_fence(c, kRawRead)) return rc; }   // the next raw upload on the lane ahead rewrites d_raw
   return TSDF_OK;
 }
 int32_t tsdf_download_mvt_vertices(tsdf_ctx* c, float* out) {
@@ -2092,13 +2080,16 @@ int32_t tsdf_draw_sensor_texture(tsdf_ctx* c, uint32_t type, uint32_t stream, co
   if (!(rect[2] > rect[0]) || !(rect[3] > rect[1])) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "empty quad: p_max must be greater than p_min on both axes");
   if (c->vp_org[0] != 0 || c->vp_org[1] != 0 || c->vp_off[0] != 0.0f || c->vp_off[1] != 0.0f)
     FAIL(c, TSDF_ERR_STATE, "the GUI is not rendered side by side (viewport origin / offset must be 0)");
-  const tsdf_ctx::FrameSlot& S = c->slots[c->cur_slot];
-  const int origin = S.have ? S.origin : tsdf_ctx::kFrameNone;
-  if (origin == tsdf_ctx::kFrameNone) FAIL(c, TSDF_ERR_STATE, "no frame uploaded");
-  if (origin == tsdf_ctx::kFrameRawPending) FAIL(c, TSDF_ERR_STATE, "the raw frame uploaded last has not been processed yet (tsdf_process_textures)");
-  const bool raw = origin == tsdf_ctx::kFrameRawDone;
-  if (!raw && type >= 5) FAIL(c, TSDF_ERR_STATE, "a frame handed over already processed has no %s image", type == 5 ? "morphed raw depth" : "Lab");
-  if (!raw && type == 3 && !c->normals_uploaded) FAIL(c, TSDF_ERR_STATE, "a frame handed over already processed has normals only after tsdf_upload_normals");
+  const WindowVerdict verdict = c->intake.raw.window(type, c->intake.slots.kind());
+  switch (verdict) {                                                     // (before anything is queued)
+    case kWindowNoFrame: FAIL(c, TSDF_ERR_STATE, "no frame uploaded");
+    case kWindowRawUnprocessed: FAIL(c, TSDF_ERR_STATE, "the raw frame uploaded last has not been processed yet (tsdf_process_textures)");
+    case kWindowNoSuchImage: FAIL(c, TSDF_ERR_STATE, "a frame handed over already processed has no %s image", type == 5 ? "morphed raw depth" : "Lab");
+    case kWindowNoNormals: FAIL(c, TSDF_ERR_STATE, "a frame handed over already processed has normals only after tsdf_upload_normals");
+    case kWindowLabStale: FAIL(c, TSDF_ERR_STATE, "the Lab image is produced on request from the processed frame's inputs, and a newer raw frame has replaced them");
+    default: break;
+  }
+  const bool raw = verdict == kWindowRaw;
   HIP_TRY(c, hipSetDevice(c->device));
   const FrameImages& F = c->frame;
   const size_t np = (size_t)F.w * F.h, layer = stream;
@@ -2131,10 +2122,6 @@ int32_t tsdf_draw_sensor_texture(tsdf_ctx* c, uint32_t type, uint32_t stream, co
   const int qy0 = within(std::floor(ylo) - 1.0, h), qy1 = within(std::ceil(yhi) + 1.0, h);
   Q.x0 = std::max(qx0, Q.sx0); Q.y0 = std::max(qy0, Q.sy0);
   Q.nx = std::min(qx1, Q.sx1) - Q.x0; Q.ny = std::min(qy1, Q.sy1) - Q.y0;
-  if (raw && type == 6) {                                                // (before anything is queued: the Lab image's own state rule)
-    if (c->pre_generation != c->raw_generation || c->pre_processed_depth != c->use_processed_depth)
-      FAIL(c, TSDF_ERR_STATE, "the Lab image is produced on request from the processed frame's inputs, and a newer raw frame has replaced them");
-  }
   if (type == 0) { if (int32_t rc = flush_pending_colour(c)) return rc; }
   HIP_TRY(c, begin_framebuffer_write(c));                                // the hole filling writes the framebuffer from its own lane
   HIP_TRY(c, join_pre(c));                                               // the lane ahead wrote the products and the frame slot
@@ -2145,14 +2132,8 @@ int32_t tsdf_draw_sensor_texture(tsdf_ctx* c, uint32_t type, uint32_t stream, co
   // d_depth_b, d_normal, d_depth2, d_lab exist once: the next tsdf_process_textures on the lane ahead waits for this draw (the frame slots alternate behind
   // the lane's gate, which the context's stream records after this call).  The Lab pass also read the raw depth: a raw upload that rewrites d_raw waits too
   if ((type == 3 || (raw && (type == 1 || type >= 5))) && pipelined(c)) {
-    if (!c->products_read) HIP_TRY(c, hipEventCreateWithFlags(&c->products_read, hipEventDisableTiming));
-    HIP_TRY(c, hipEventRecord(c->products_read, c->stream));
-    c->products_read_pending = true;
-    if (type == 6) {
-      if (!c->raw_read) HIP_TRY(c, hipEventCreateWithFlags(&c->raw_read, hipEventDisableTiming));
-      HIP_TRY(c, hipEventRecord(c->raw_read, c->stream));
-      c->raw_read_pending = true;
-    }
+    if (int32_t rc = record_read_fence(c, kProductsRead)) return rc;
+    if (type == 6) { if (int32_t rc = record_read_fence(c, kRawRead)) return rc; }
   }
   HIP_TRY(c, hipGetLastError());
   return TSDF_OK;

@@ -9,6 +9,7 @@
 #include "image_tiles.hpp"
 #include "lane_ahead.hpp"
 #include "draw_lanes.hpp"
+#include "frame_intake.hpp"
 
 using namespace rr;
 
@@ -68,41 +69,29 @@ struct tsdf_ctx {
   bool last_integrate_cached = false;
   IntegratePlan last_k1{};       // tsdf_integrate_form: the plan the last integrate() launched by (form -1: none since the volume was set up)
   FrameImages frame{};           // the CURRENT frame slot's images (what mark / integrate / draw read)
-  // Two frame slots (the reference's double PBO + texture arrays, NetKinectArray.cpp:225-236): while the path computes on slot
-  // `cur_slot`, tsdf_upload_frame_async fills the other one on a copy stream; tsdf_select_frame_slot makes it current.
-  struct FrameSlot { float4* dqs = nullptr; float* depth = nullptr; uchar4* color = nullptr; float4* ranges = nullptr; bool have = false;
-                     hipEvent_t ready = nullptr; bool pending = false;      // recorded on the copy stream after the slot's upload + pack
-                     hipEvent_t released = nullptr; bool in_use = false;    // recorded on the compute stream when the slot stopped being current
-                     int origin = 0; };                                     // where its frame came from (kFrame*, below): what the sensor texture windows may show
+  // The frame intake: the state and its protocol are frame_intake.hpp's -- which of the two frame slots is current and what each holds, the two
+  // pinned host rings, the raw frame and what the passes made of it, the read fences.  Here: the buffers and events it indexes
+  FrameIntake intake{};
+  struct FrameSlot { float4* dqs = nullptr; float* depth = nullptr; uchar4* color = nullptr; float4* ranges = nullptr; hipEvent_t ready = nullptr, released = nullptr; };
   FrameSlot slots[2];
-  int cur_slot = 0;
   hipStream_t copy_stream = nullptr;
-  uint8_t* h_stage[2]{}; hipEvent_t stage_done[2]{}; bool stage_busy[2]{}; int stage_k = 0;   // pinned host staging ring of the async upload
+  uint8_t* h_stage[2]{}; hipEvent_t stage_done[2]{};   // pinned host staging ring of the async upload
   float* d_stage_depth = nullptr; float* d_stage_q = nullptr; float* d_stage_s = nullptr; uint8_t* d_stage_col = nullptr;
   uint8_t* d_astage = nullptr;   // device staging of the async upload (its own: the copy stream runs beside the compute stream)
   // pre-processing state (NetKinectArray side)
   PreParams pre{};
   float* d_raw = nullptr; float* d_depth2 = nullptr; float2* d_depth_rg = nullptr; float4* d_lab = nullptr; float2* d_depth_b = nullptr; float4* d_normal = nullptr;
   uint32_t* d_pre_blocks = nullptr; uint32_t pre_cand_cap = 0;   // [count | cand_list[cap] | blk_flag[blocks]] (PreBuffers)
-  bool have_raw = false, use_processed_depth = true;
-  const uint8_t* pending_rgb = nullptr;   // RGB8 colour of the raw frame uploaded last, still to be re-laid out into the frame slot (rides along in processTextures' first launch)
-  uint64_t raw_generation = 0, pre_generation = 0; bool pre_processed_depth = true;   // which raw upload the products of processTextures() belong to (the Lab image is produced on request from its inputs)
-  const float* raw_src = nullptr;   // the raw depth the passes read: d_raw (host upload, wire unpack) or the caller's device array (tsdf_upload_raw_frame_dev)
-  hipEvent_t normals_read = nullptr; bool normals_read_pending = false;   // recorded behind a point / triangle-grid draw: the lane ahead rewrites d_normal
+  const uint8_t* pending_rgb = nullptr;   // RGB8 colour of the raw frame uploaded last (d_stage_col or the caller's array), while intake.raw says it is pending
+  const float* raw_src = nullptr;   // the caller's raw depth (tsdf_upload_raw_frame_dev), while intake.raw says the passes read from it
+  hipEvent_t read_fence[kReadFences]{};   // the read fences' events (frame_intake.hpp)
   bool have_limits[TSDF_MAX_STREAMS]{}, have_cam[TSDF_MAX_STREAMS]{};
   // the frustum overlay (tsdf_draw_frustums): per stream the forward LUT's corner samples and Frustum::getCameraPos, captured by tsdf_set_calibration
   float frustum_corner[TSDF_MAX_STREAMS][8][3]{}; float frustum_cam[TSDF_MAX_STREAMS][3]{}; bool have_frustum[TSDF_MAX_STREAMS]{};
   unsigned long long* d_calibvis_skipped = nullptr; uint64_t calibvis_points = 0;   // the TSDF overlay: grid points of the last draw, device count of those the empty-space test removed
-  // the sensor texture windows (tsdf_draw_sensor_texture) show NetKinectArray's arrays: FrameSlot::origin says whether the current slot's frame was handed
-  // over processed, is a raw frame still to be processed, or one tsdf_process_textures has gone through; normals_uploaded: d_normal is tsdf_upload_normals'.
-  // products_read is recorded behind a window that read one of the single-buffered products (d_depth2, d_depth_b, d_normal, d_lab): the next
-  // tsdf_process_textures on the lane ahead rewrites them, its first two passes in front of the lane's gate
-  static constexpr int kFrameNone = 0, kFramePre = 1, kFrameRawPending = 2, kFrameRawDone = 3;
-  bool normals_uploaded = false;
-  hipEvent_t products_read = nullptr; bool products_read_pending = false;
   // frame ingest (readLoop / update): wire formats, pinned double buffer (the reference's double_pbo), device copy of the message
   uint32_t color_format = TSDF_COLOR_RGB8, depth_format = TSDF_DEPTH_F32;
-  uint8_t* h_wire[2]{}; hipEvent_t wire_done[2]{}; bool wire_pending[2]{}; int wire_slot = 0;
+  uint8_t* h_wire[2]{}; hipEvent_t wire_done[2]{};
   uint8_t* d_wire = nullptr; size_t wire_capacity = 0;
   // view
   int vw = 0, vh = 0;
@@ -119,7 +108,6 @@ struct tsdf_ctx {
   uint8_t* d_fill_mask[2]{}; uint8_t* d_lvl_mask[2]{}; uint64_t n_fills = 0, n_fills_by_tiles = 0;
   uint32_t* d_tri_z = nullptr; float4* d_tri_acc = nullptr; float min_length = 0.0125f;   // triangle-grid back-end; KinectCalibrationFile.cpp:96 default
   float2* d_mvt_vtx = nullptr; bool have_mvt = false;   // MVT back-end: the last draw's vertex stage, [N][W+1][H+1] (filtered depth m, lateral quality)
-  hipEvent_t raw_read = nullptr; bool raw_read_pending = false;   // recorded behind an MVT draw: the next raw upload on the lane ahead rewrites d_raw
   uint32_t* d_pair_masks = nullptr;   // per work item of the integrate launch: this frame's (tile, stream) pair classes (k_pair_masks)
   uint4* d_work_recs = nullptr; bool use_recs = true;   // per work item of the integrate launch: the 16-byte record k_pair_masks leaves for k_integrate_tiles_rec (RR_K1_REC=0: off, A/B)
   float4* d_tile_bounds = nullptr; bool tile_bounds_valid = false;   // static per (stored tile, stream) LUT-box bounds, built on the first dense integrate after a calibration

@@ -473,3 +473,147 @@ def test_draw_lane_call_orders_equal_one_stream(rr, lane_scenes, order, flag):
         got, want = getattr(lanes, what, []), getattr(twin, what, [])
         assert len(got) == len(want) and all(g == w for g, w in zip(got, want)), f"{what}: the lanes delivered something else"
         assert not hasattr(lanes, what) or (len(got) >= 6 and len(set(got)) >= 4)
+
+
+# ---------------------------------------------------------------------------------------------- the frame intake (csrc/frame_intake.hpp)
+TSDF_ERR_STATE = -4
+WINDOW = (3.0, 2.0, 40.0, 50.0)
+
+
+def _process(o, mv, pr):
+    o.clearOccupiedBricks(); o.processTextures(); o.updateOccupiedBricks(False); o.integrate(); o.drawF(mv, pr)
+
+
+def _raw_dev(o, d):
+    o.upload_raw_frame_dev(d["depth_raw"].data_ptr(), d["color"].data_ptr(), complete=True)
+
+
+def _raw_host_then_process(o, k, scs, dev, mv, pr):
+    o.upload_raw_frame(scs[k]); _process(o, mv, pr)
+
+
+def _wire_both_buffers(o, k, scs, dev, mv, pr):
+    """every message takes the other pinned buffer; from the third on its previous copy has to have left it"""
+    o.upload_wire_frame(o.messages[k]); _process(o, mv, pr)
+
+
+def _raw_download_before_process(o, k, scs, dev, mv, pr):
+    """the read-back asks for the colour the first pass would have re-laid out"""
+    _raw_dev(o, dev[k])
+    o.delivered += [a.tobytes() for a in o.raw_frame()]
+    _process(o, mv, pr)
+
+
+def _process_twice(o, k, scs, dev, mv, pr):
+    """the second run finds the colour taken and the slot written"""
+    _raw_dev(o, dev[k]); o.clearOccupiedBricks(); o.processTextures(); o.processTextures(); o.updateOccupiedBricks(False); o.integrate(); o.drawF(mv, pr)
+
+
+def _points_then_process(o, k, scs, dev, mv, pr):
+    """the point draw reads the normal image the next frame's passes rewrite"""
+    _raw_dev(o, dev[k]); _process(o, mv, pr); o.drawPoints(mv, pr)
+
+
+def _mvt_then_raw_upload(o, k, scs, dev, mv, pr):
+    """the MVT draw reads the raw depth the next upload (host, then wire) rewrites"""
+    if k % 2:
+        o.upload_wire_frame(o.messages[k])
+    else:
+        o.upload_raw_frame(scs[k])
+    _process(o, mv, pr); o.drawMVT(mv, pr)
+
+
+def _windows_then_process(o, k, scs, dev, mv, pr):
+    """windows on the single-buffered products (type 6 also reads the raw depth) in front of the next frame's upload and passes"""
+    o.upload_raw_frame(scs[k]); _process(o, mv, pr)
+    for n, type in enumerate((1, 3, 5, 6)):
+        o.drawSensorTexture(type, (k + n) % 2, (WINDOW[0] + 30 * n, WINDOW[1], WINDOW[2] + 30 * n, WINDOW[3]))
+
+
+def _async_upload_and_select(o, k, scs, dev, mv, pr):
+    o.upload_frame_async(scs[k]); o.select_frame_slot(1 - o.current_frame_slot())
+    _bricks(o); o.integrate(); o.drawF(mv, pr)
+
+
+def _preprocessed_after_raw(o, k, scs, dev, mv, pr):
+    """a raw frame nobody processes, a pre-processed one over it"""
+    _raw_dev(o, dev[(k + 1) % 4]); o.upload_frame(scs[k]); _bricks(o); o.integrate(); o.drawF(mv, pr)
+
+
+INTAKE_ORDERS = [_raw_host_then_process, _wire_both_buffers, _raw_download_before_process, _process_twice, _points_then_process, _mvt_then_raw_upload,
+                 _windows_then_process, _async_upload_and_select, _preprocessed_after_raw]
+
+
+def _raises_state(rr, call):
+    with pytest.raises(rr.TsdfError) as e:
+        call()
+    assert e.value.code == TSDF_ERR_STATE
+
+
+def _state_verdicts(rr, o, scs):
+    """what the intake's state allows, absolutely: nothing of a raw frame before it is processed; of a frame handed over processed no morphed depth,
+    no Lab image and no normals until some are uploaded; no Lab image once a newer raw frame has replaced the processed one's inputs"""
+    o.upload_raw_frame(scs[0])
+    for type in range(7):
+        _raises_state(rr, lambda: o.drawSensorTexture(type, 0, WINDOW))
+    o.clearOccupiedBricks(); o.processTextures()
+    for type in range(7):
+        o.drawSensorTexture(type, 1, WINDOW)
+    assert set(o.preprocessed()) >= {"lab", "normals"}
+    o.upload_raw_frame(scs[1])
+    _raises_state(rr, o.preprocessed)
+    assert "lab" not in o.preprocessed(lab=False)
+    o.upload_frame(scs[2])
+    for type in (3, 5, 6):
+        _raises_state(rr, lambda: o.drawSensorTexture(type, 0, WINDOW))
+    for type in (0, 1, 2, 4):
+        o.drawSensorTexture(type, 0, WINDOW)
+    o.upload_normals(scs[2]["normals"])
+    o.drawSensorTexture(3, 0, WINDOW)
+    for type in (5, 6):
+        _raises_state(rr, lambda: o.drawSensorTexture(type, 0, WINDOW))
+
+
+@pytest.mark.parametrize("order", INTAKE_ORDERS, ids=lambda f: f.__name__.lstrip("_"))
+def test_frame_intake_call_orders_equal_one_stream(rr, lane_scenes, order):
+    """Which frame slot is current and what it holds, the two pinned rings, the raw frame and what was made of it, the three read fences behind
+    draws that read single-buffered images (csrc/frame_intake.hpp): every per-frame call order that reaches a branch of that bookkeeping the
+    orders above do not, over the same four frames against the same one-stream twin -- volume, brick counters and flags, framebuffer (with
+    whatever the order drew over it), bit for bit, back to back and then read back behind each frame; and what a read-back in the middle of a
+    frame delivered.  Then the state verdicts on both contexts, absolutely."""
+    scs, dev = lane_scenes
+    vs = views(rr, *KW["view"])
+    lanes, twin = rr.ReconIntegrationHip(scs[0], **KW), rr.ReconIntegrationHip(scs[0], lane_flags=rr.LANES_ONE_STREAM, **KW)
+    messages = [rr.scene.make_wire_message(sc, 0, 0) for sc in scs]
+    for o in (lanes, twin):
+        o.set_preprocess_calibration(scs[0])
+        o.messages, o.delivered = messages, []
+
+    def compare(what):
+        assert_same(dict(tsdf=lanes.tsdf()), dict(tsdf=twin.tsdf()), what)
+        (lc, lf), (tc, tf) = lanes.bricks(), twin.bricks()
+        np.testing.assert_array_equal(lc, tc, err_msg=f"{what}: brick counters"); np.testing.assert_array_equal(lf, tf, err_msg=f"{what}: brick flags")
+        a, b = outputs(lanes), outputs(twin)
+        assert_same(dict(fb_color=a["fb_color"], fb_depth=a["fb_depth"]), dict(fb_color=b["fb_color"], fb_depth=b["fb_depth"]), what)
+        return twin.tsdf(), b["fb_depth"], b["depth"]
+
+    for k in range(4):
+        for o in (lanes, twin):
+            order(o, k, scs, dev, *vs[k])
+    compare("four frames back to back")
+    seen = []
+    for k in range(4):
+        for o in (lanes, twin):
+            order(o, k, scs, dev, *vs[k])
+        seen.append(compare(f"frame {k}, read back"))
+    # The pictures are not empty.  The bound of 100 pixels is the march's, as in the tests above; an MVT draw REPLACES the framebuffer by the mesh of
+    # the 128 x 96 raw depth images, whose cover is tests/test_gpu_mvt.py's matter: there the march's own depth image carries the bound, and the
+    # framebuffer has to show a mesh at all.
+    assert all((m < 1).sum() > 100 for _, _, m in seen)
+    assert all((d < 1).sum() > (0 if order is _mvt_then_raw_upload else 100) for _, d, _ in seen)
+    for a in range(4):
+        for b in range(a + 1, 4):
+            assert (seen[a][0] != seen[b][0]).any(), f"frames {a} and {b} leave the same volume"
+    assert lanes.delivered == twin.delivered and (order is not _raw_download_before_process or len(set(lanes.delivered[0::2])) == 4)   # (the four raw depth images)
+    for o in (lanes, twin):
+        _state_verdicts(rr, o, scs)
