@@ -1110,7 +1110,8 @@ void orc_process_textures(orc_ctx* c) {
       }
 
   // ---- "quality": pre_quality.fs bilateral_filter :65-119, normal_angle :43-48.  pow() of a negative base is undefined
-  // in GLSL; powf is used as is (angle < 0 only for back-facing noise).
+  // in GLSL; powf is used as is.  (Not a corner case: under scene.make_scene's calibration, whose image rows run bottom-up, pre_normal.fs:55
+  // points every normal away from the camera and the angle is negative at every pixel -- tests/preprocess_reference_cases.py, mirrored().)
 #pragma omp parallel for collapse(2)
   for (int l = 0; l < N; ++l)
     for (int y = 0; y < H; ++y)
