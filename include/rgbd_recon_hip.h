@@ -576,6 +576,34 @@ int32_t tsdf_mesh_download(tsdf_ctx* ctx, float* position_xyz, float* normal_xyz
 int32_t tsdf_mesh_write_ply(tsdf_ctx* ctx, const char* path);
 int32_t tsdf_mesh_stats(tsdf_ctx* ctx, uint64_t out[4]);
 
+/* ---- mesh level of detail: the same surface on the lattice of every 2nd / 4th voxel -----------------------
+ * A level L has stride s = 1 << L: L = 0, 1, 2 give s = 1, 2, 4; any other level is TSDF_ERR_INVALID_ARGUMENT.  tests/mesh_lod_reference.py restates
+ * this in numpy on top of tests/mesh_reference.py; device and numpy agree bit for bit in counts, positions and indices.
+ * Lattice.  Level-L lattice point (i, j, k) IS voxel (s i, s j, s k): a point sample, not a filter.  The lattice has cr = ceil(r / s) points per axis.
+ *   Voxels beyond the last lattice point belong to no cell: the mesh ends at the last lattice point.  A lattice thinner than 2 on an axis yields zero
+ *   counts.
+ * Topology.  Everything of the level-0 definition above, applied to the lattice: the reading of NaN / +-inf as -limit, inside iff f > 0, Kuhn's six
+ *   tetrahedra, one vertex per crossed edge owned by its lower end p, the winding table, and the order by (8^3 LATTICE tile, x fastest; owner in the
+ *   tile; d) and (tile of the cell, cell, tetrahedron, triangle).  The triangle array of level L is, byte for byte, the level-0 triangle array of the
+ *   volume vol[::s, ::s, ::s].  "Tile" in the counts, in tsdf_mesh_stats, in max_surface_tiles and in needed_tiles means a lattice tile: 8^3 lattice
+ *   points, (8 s)^3 voxels.
+ * Vertex position: descent to a voxel edge.  A crossed lattice edge runs from voxel P = s p to P + s d, d its 0/1 offset vector.  For h = s/2, s/4, .., 1:
+ *   read the voxel M = P + h d (an exact voxel read, sanitised like every sample); if (f(M) > 0) == (f(P) > 0), set P = M.  After L steps P and P + d
+ *   are neighbouring voxels and exactly one of them is inside (the invariant holds at every step).  The vertex is the level-0 vertex of that voxel edge:
+ *   a = f(P), b = f(P + d), t = a / (a - b), u = u_P + t * (u_Q - u_P) with the FULL resolution in ((float)x + 0.5f) / (float)rx, then vol_to_world;
+ *   fp32 and the operation order of level 0.  So every level-L vertex is bit-identical to a vertex of the level-0 mesh, the position does not depend on
+ *   how the truncation limit compares with the stride (the TSDF saturates at +-limit: interpolating along a 4-voxel edge would not give that), and no
+ *   trilinear tap is involved.
+ * Normal and colour.  Unchanged: the full-resolution gradient and blendColors at the vertex's u.
+ * Class skip.  A lattice tile reads voxels in storage tiles [ct s, ct s + s] per axis, (s + 1)^3 of them, clipped to the grid.  When all of them say
+ *   "every voxel is -limit" (sparse pool: no slot) the tile is skipped without a voxel read; that is exact.  A surface that lies wholly between lattice
+ *   points is not part of a level-L mesh, skipped or not: a coarse level drops what its lattice does not sample, and a surface that leaves the lattice
+ *   (between the last lattice point and the volume's face) leaves the mesh open there.
+ * tsdf_mesh_extract_lod is tsdf_mesh_extract at a level; level 0 runs what tsdf_mesh_extract runs.  tsdf_mesh_download / _write_ply / _stats serve
+ *   whichever extract was last; the stats count lattice tiles.  Error codes as tsdf_mesh_extract (Z-slab context, no volume yet, colours without
+ *   calibration and a frame), and TSDF_ERR_INVALID_ARGUMENT for a level above 2. */
+int32_t tsdf_mesh_extract_lod(tsdf_ctx* ctx, uint32_t flags, uint32_t level, uint64_t* n_vertices, uint64_t* n_triangles);
+
 /* ---- mesh streaming: the fused surface every frame, packed, through a pinned ring -------------------------
  * tsdf_mesh_extract is a one-shot export: it allocates, waits for the host twice and leaves 12..40 bytes per vertex in fp32.  A telepresence client hands
  * its geometry to a remote renderer, a recorder or a thin client EVERY frame; these entries deliver the mesh the way tsdf_present delivers the picture:
@@ -645,6 +673,14 @@ int32_t tsdf_mesh_stream(tsdf_ctx* ctx, uint64_t tag);
 int32_t tsdf_mesh_stream_acquire(tsdf_ctx* ctx, int32_t wait, tsdf_mesh_frame* out, int32_t* ready);
 int32_t tsdf_mesh_stream_release(tsdf_ctx* ctx);
 int32_t tsdf_mesh_stream_stats(tsdf_ctx* ctx, uint64_t out[4]);
+/* The ring at a level of detail ("mesh level of detail" above): tsdf_mesh_stream_config_lod is tsdf_mesh_stream_config with a level (0, 1, 2;
+ * TSDF_ERR_INVALID_ARGUMENT otherwise), tsdf_mesh_stream_config is it with level 0.  Every frame streamed after it is the level's mesh: the packing of what
+ * tsdf_mesh_extract_lod gives for the same volume, triangles byte-identical.  max_surface_tiles and needed_tiles count lattice tiles of that level, and
+ * the scratch is sized by its lattice-tile count.  tsdf_mesh_frame keeps its layout (res is the volume's resolution: positions are coded in the unit
+ * cube at every level).  tsdf_mesh_stream / _acquire / _release / _stats are unchanged.  tsdf_mesh_stream_level reports the configured level
+ * (TSDF_ERR_STATE before any config). */
+int32_t tsdf_mesh_stream_config_lod(tsdf_ctx* ctx, uint32_t flags, uint32_t level, uint32_t max_vertices, uint32_t max_triangles, uint32_t max_surface_tiles, uint32_t slots);
+int32_t tsdf_mesh_stream_level(tsdf_ctx* ctx, uint32_t* level);
 
 /* ---- frame read-out: the swap ------------------------------------------------------------------------
  * The client ends a frame with glfwSwapBuffers (source/kinect_client.cpp:533): an RGBA8 window goes to a display (GLFW's default framebuffer has 8

@@ -627,13 +627,17 @@ class ReconIntegrationHip:
         return rgba, d
 
     # ------------------------------------------------------------------ mesh extraction (no counterpart in the reference)
-    def extract_mesh(self, normals=True, colours=True):
+    def extract_mesh(self, normals=True, colours=True, level=0):
         """The fused surface as an indexed triangle mesh (tsdf_mesh_extract): dict(position [V][3] f32, triangles [T][3] uint32, and where asked
-        for normal [V][3] f32, colour [V][4] f32 with alpha +1 valid / -1 fallback), in the defined order."""
+        for normal [V][3] f32, colour [V][4] f32 with alpha +1 valid / -1 fallback), in the defined order.  level 1 / 2: the same surface on the
+        lattice of every 2nd / 4th voxel (tsdf_mesh_extract_lod); level 0 calls tsdf_mesh_extract itself."""
         nv, nt = C.c_uint64(), C.c_uint64()
         flags = (MESH_NORMALS if normals else 0) | (MESH_COLOURS if colours else 0)
         self._mesh_counts = None
-        self._ck(self._L.tsdf_mesh_extract(self._c, C.c_uint32(flags), C.byref(nv), C.byref(nt)))
+        if level:
+            self._ck(self._L.tsdf_mesh_extract_lod(self._c, C.c_uint32(flags), C.c_uint32(int(level)), C.byref(nv), C.byref(nt)))
+        else:
+            self._ck(self._L.tsdf_mesh_extract(self._c, C.c_uint32(flags), C.byref(nv), C.byref(nt)))
         self._mesh_counts = (nv.value, nt.value)
         return self.download_mesh(normals, colours)
 
@@ -662,11 +666,21 @@ class ReconIntegrationHip:
         return dict(tiles=int(out[0]), tiles_skipped=int(out[1]), tiles_with_surface=int(out[2]), bytes=int(out[3]))
 
     # ------------------------------------------------------------------ mesh streaming (no counterpart in the reference)
-    def mesh_stream_config(self, normals=False, colours=False, max_vertices=1 << 20, max_triangles=1 << 21, max_surface_tiles=1 << 14, slots=3):
-        """flags, the three capacities and the slot count of the mesh ring (tsdf_mesh_stream_config); the first mesh_stream after it allocates"""
+    def mesh_stream_config(self, normals=False, colours=False, max_vertices=1 << 20, max_triangles=1 << 21, max_surface_tiles=1 << 14, slots=3, level=0):
+        """flags, the three capacities and the slot count of the mesh ring (tsdf_mesh_stream_config); the first mesh_stream after it allocates.
+        level 1 / 2 (tsdf_mesh_stream_config_lod): every frame is that level's mesh, max_surface_tiles counts its 8^3 lattice tiles."""
         flags = (MESH_NORMALS if normals else 0) | (MESH_COLOURS if colours else 0)
-        self._ck(self._L.tsdf_mesh_stream_config(self._c, C.c_uint32(flags), C.c_uint32(int(max_vertices)), C.c_uint32(int(max_triangles)),
-                                                 C.c_uint32(int(max_surface_tiles)), C.c_uint32(int(slots))))
+        caps = (C.c_uint32(int(max_vertices)), C.c_uint32(int(max_triangles)), C.c_uint32(int(max_surface_tiles)), C.c_uint32(int(slots)))
+        if level:
+            self._ck(self._L.tsdf_mesh_stream_config_lod(self._c, C.c_uint32(flags), C.c_uint32(int(level)), *caps))
+        else:
+            self._ck(self._L.tsdf_mesh_stream_config(self._c, C.c_uint32(flags), *caps))
+
+    def mesh_stream_level(self):
+        """the level of the last mesh_stream_config (tsdf_mesh_stream_level)"""
+        level = C.c_uint32()
+        self._ck(self._L.tsdf_mesh_stream_level(self._c, C.byref(level)))
+        return int(level.value)
 
     def mesh_stream(self, tag=0):
         """queue count, scan, emit and the copy of the current surface into the next ring slot; never blocks (TsdfError, code -4, when every slot is taken)"""

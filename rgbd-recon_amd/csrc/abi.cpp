@@ -2402,9 +2402,13 @@ struct MeshTemp {                                                         // wha
   ~MeshTemp() { hipFree(s.tile_cnt); hipFree(s.tile_skip); hipFree(s.tile_vbase); hipFree(s.tile_tbase); hipFree(s.tile_rec); hipFree(s.sums); hipFree(records); }
 };
 }  // namespace
-int32_t tsdf_mesh_extract(tsdf_ctx* c, uint32_t flags, uint64_t* n_vertices, uint64_t* n_triangles) {
+int32_t tsdf_mesh_extract(tsdf_ctx* c, uint32_t flags, uint64_t* n_vertices, uint64_t* n_triangles) { return tsdf_mesh_extract_lod(c, flags, 0u, n_vertices, n_triangles); }
+// one extract at a level of detail: level 0 is the voxel lattice (what tsdf_mesh_extract runs), level L the lattice of every (1 << L)-th voxel.  Everything
+// per tile -- scratch, scan, records, stats -- is per LATTICE tile of that level.
+int32_t tsdf_mesh_extract_lod(tsdf_ctx* c, uint32_t flags, uint32_t level, uint64_t* n_vertices, uint64_t* n_triangles) {
   CHECK_CTX(c);
   if (flags & ~(TSDF_MESH_NORMALS | TSDF_MESH_COLOURS)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "unknown mesh flag");
+  if (level > (uint32_t)kMeshMaxLevel) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "mesh level %u (0 .. %d: every voxel, every 2nd, every 4th)", level, kMeshMaxLevel);
   if (!whole_volume(c)) FAIL(c, TSDF_ERR_STATE, "tsdf_mesh_extract on a Z-slab context: welding slab meshes is not provided");
   if (!c->have_volume) FAIL(c, TSDF_ERR_STATE, "no volume yet (tsdf_integrate or tsdf_upload_volume)");
   int32_t rc;
@@ -2413,13 +2417,14 @@ int32_t tsdf_mesh_extract(tsdf_ctx* c, uint32_t flags, uint64_t* n_vertices, uin
   release_mesh(c);                                                       // (nothing queued reads it: extract and download synchronise)
   tsdf_ctx::Mesh& M = c->mesh;
   const Volume& V = c->vol;
-  const int n_tiles = V.n_stored_tiles, nb = mesh_scan_blocks(n_tiles);
+  const MeshLattice L = mesh_lattice(V.res, (int)level);                 // (level 0 on a whole-volume context: the storage tiles, n_tiles = V.n_stored_tiles)
+  const int n_tiles = L.ntx * L.nty * L.ntz, nb = mesh_scan_blocks(n_tiles);
   M.flags = flags; M.stats[0] = (uint64_t)n_tiles;
   uint64_t totals[4] = {0, 0, 0, 0};
   MeshTemp tmp;
-  if (c->res[0] >= 2 && c->res[1] >= 2 && c->res[2] >= 2) {             // (a lattice one point thick has no cell)
+  if (L.cr[0] >= 2 && L.cr[1] >= 2 && L.cr[2] >= 2) {                   // (a lattice one point thick has no cell)
     MeshScratch& S = tmp.s;
-    S.n_tiles = n_tiles;
+    S.n_tiles = n_tiles; S.level = (int)level;
     HIP_TRY(c, hipMalloc((void**)&S.tile_cnt, (size_t)n_tiles * sizeof(uint2)));
     HIP_TRY(c, hipMalloc((void**)&S.tile_skip, (size_t)n_tiles));
     HIP_TRY(c, hipMalloc((void**)&S.tile_vbase, (size_t)n_tiles * sizeof(uint32_t)));
@@ -2508,8 +2513,12 @@ int32_t tsdf_mesh_stats(tsdf_ctx* c, uint64_t out[4]) {
 // ---- mesh streaming (the definition is in the header): the same mesh every frame, packed, without a host wait or an allocation after the first call
 static size_t mesh_stream_payload_capacity(const tsdf_ctx::MeshStream& R) { return (size_t)R.max_vertices * (R.flags ? 16 : 8) + (size_t)R.max_triangles * 12; }
 int32_t tsdf_mesh_stream_config(tsdf_ctx* c, uint32_t flags, uint32_t max_vertices, uint32_t max_triangles, uint32_t max_surface_tiles, uint32_t slots) {
+  return tsdf_mesh_stream_config_lod(c, flags, 0u, max_vertices, max_triangles, max_surface_tiles, slots);
+}
+int32_t tsdf_mesh_stream_config_lod(tsdf_ctx* c, uint32_t flags, uint32_t level, uint32_t max_vertices, uint32_t max_triangles, uint32_t max_surface_tiles, uint32_t slots) {
   CHECK_CTX(c);
   tsdf_ctx::MeshStream& R = c->mstream;
+  if (level > (uint32_t)kMeshMaxLevel) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "mesh level %u (0 .. %d: every voxel, every 2nd, every 4th)", level, kMeshMaxLevel);
   if ((flags & ~(TSDF_MESH_NORMALS | TSDF_MESH_COLOURS)) || !max_vertices || !max_triangles || !max_surface_tiles || slots < 2 || slots > tsdf_ctx::MeshStream::kMaxSlots)
     FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "mesh stream flags %u / capacities %u vertices, %u triangles, %u tiles / slots %u (flags 1 normals, 2 colours; capacities > 0; 2..%u slots)",
          flags, max_vertices, max_triangles, max_surface_tiles, slots, tsdf_ctx::MeshStream::kMaxSlots);
@@ -2520,16 +2529,24 @@ int32_t tsdf_mesh_stream_config(tsdf_ctx* c, uint32_t flags, uint32_t max_vertic
   // behind its header copy alone, and its emit launches, which read the slot's device header and the scratch, may still be queued on the context's stream.
   if (R.allocated) HIP_TRY(c, hipStreamSynchronize(c->stream));
   release_mesh_stream(c);
-  R.flags = flags; R.max_vertices = max_vertices; R.max_triangles = max_triangles; R.max_tiles = max_surface_tiles; R.slots = slots; R.configured = true;
+  R.flags = flags; R.level = level; R.max_vertices = max_vertices; R.max_triangles = max_triangles; R.max_tiles = max_surface_tiles; R.slots = slots; R.configured = true;
   R.frames = R.overflowed = R.bytes_copied = 0;
+  return TSDF_OK;
+}
+int32_t tsdf_mesh_stream_level(tsdf_ctx* c, uint32_t* level) {
+  CHECK_CTX(c);
+  if (!level) return TSDF_ERR_INVALID_ARGUMENT;
+  if (!c->mstream.configured) FAIL(c, TSDF_ERR_STATE, "tsdf_mesh_stream_level before tsdf_mesh_stream_config");
+  *level = c->mstream.level;
   return TSDF_OK;
 }
 // slots and scratch, once per configuration and grid
 static int32_t mesh_stream_allocate(tsdf_ctx* c) {
   tsdf_ctx::MeshStream& R = c->mstream;
-  const size_t n_tiles = (size_t)c->vol.n_stored_tiles, nb = (size_t)mesh_scan_blocks((int)n_tiles), slot_bytes = sizeof(MeshStreamHeader) + mesh_stream_payload_capacity(R);
+  const MeshLattice L = mesh_lattice(c->vol.res, (int)R.level);
+  const size_t n_tiles = (size_t)L.ntx * L.nty * L.ntz, nb = (size_t)mesh_scan_blocks((int)n_tiles), slot_bytes = sizeof(MeshStreamHeader) + mesh_stream_payload_capacity(R);
   MeshScratch& T = R.scratch;
-  T.n_tiles = (int)n_tiles;
+  T.n_tiles = (int)n_tiles; T.level = (int)R.level;
   bool ok = hipMalloc((void**)&T.tile_cnt, n_tiles * sizeof(uint2)) == hipSuccess && hipMalloc((void**)&T.tile_skip, n_tiles) == hipSuccess &&
             hipMalloc((void**)&T.tile_vbase, n_tiles * sizeof(uint32_t)) == hipSuccess && hipMalloc((void**)&T.tile_tbase, n_tiles * sizeof(unsigned long long)) == hipSuccess &&
             hipMalloc((void**)&T.tile_rec, n_tiles * sizeof(uint32_t)) == hipSuccess && hipMalloc(&T.sums, (nb + 1) * 4 * sizeof(uint64_t)) == hipSuccess &&
@@ -2583,7 +2600,8 @@ int32_t tsdf_mesh_stream(tsdf_ctx* c, uint64_t tag) {
   tsdf_ctx::MeshStreamSlot& S = R.ring[(R.head + R.count) % R.slots];
   MeshStreamHeader* H = (MeshStreamHeader*)S.dev;
   const Volume& V = c->vol;
-  const bool cells = c->res[0] >= 2 && c->res[1] >= 2 && c->res[2] >= 2;  // (a lattice one point thick has no cell)
+  const MeshLattice L = mesh_lattice(V.res, (int)R.level);
+  const bool cells = L.cr[0] >= 2 && L.cr[1] >= 2 && L.cr[2] >= 2;       // (a lattice one point thick has no cell)
   if (cells) {
     HIP_TRY(c, join_integ(c));                                           // the volume tsdf_download_volume would return now
     if (R.flags & TSDF_MESH_COLOURS) HIP_TRY(c, join_pre(c));            // ... and the current frame slot's images

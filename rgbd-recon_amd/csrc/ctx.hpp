@@ -147,7 +147,7 @@ struct tsdf_ctx {
     static constexpr uint32_t kMaxSlots = 8;
     MeshStreamSlot ring[kMaxSlots];
     MeshScratch scratch{}; uint32_t* records = nullptr;
-    uint32_t flags = 0, max_vertices = 0, max_triangles = 0, max_tiles = 0, slots = 0, head = 0, count = 0;
+    uint32_t flags = 0, level = 0, max_vertices = 0, max_triangles = 0, max_tiles = 0, slots = 0, head = 0, count = 0;   // level: tsdf_mesh_stream_config_lod (the scratch is sized by its lattice tiles)
     bool configured = false, allocated = false, held = false;
     uint64_t frames = 0, overflowed = 0, bytes_copied = 0, device_bytes = 0;
   } mstream;

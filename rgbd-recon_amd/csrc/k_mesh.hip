@@ -13,7 +13,12 @@
 //                     vertices (position, optionally normal and colour), one lane per vertex
 //   k_mesh_triangles  per tile with triangles: reads the records only (never the volume); the index of an edge owned by lattice point
 //                     q is tile_vbase[tile of q] + record(q).offset + popcount(record(q).mask below d)
+// Level of detail (tsdf_mesh_extract_lod, level 1 and 2): the same launches on the lattice of every 2nd / 4th voxel.  "Tile" and "lattice point" above
+// then mean a tile of 8^3 LATTICE points ((8 << level)^3 voxels) and its points; MeshLattice holds that geometry.  Every kernel that knows the lattice is
+// instantiated per level; level 0 is the text it was, the lattice being the voxel grid.  A vertex of a coarse edge is the level-0 vertex of the voxel edge a
+// bisection along the edge ends on (mesh_descend: `level` voxel reads), so no position is interpolated over more than one voxel.
 #include <cfloat>
+#include <type_traits>
 
 #include "blend_dev.hpp"
 
@@ -60,24 +65,63 @@ __device__ __forceinline__ uint32_t block_exclusive_sum(uint32_t v, uint32_t* s_
 }
 
 struct MeshTile { int tx, ty, tz, id; };
-__device__ __forceinline__ MeshTile mesh_tile(const Volume& V) {
+// The lattice inside a kernel.  A level holds the MeshLattice of the volume's resolution (tsdf_common.hpp: the one definition, the host sizes the launch
+// by it).  Level 0 is the voxel grid and its storage tiles and reads the volume's own fields where they are used: the kernels' text before there were
+// levels (a copy made at the kernel's head costs k_mesh_triangles a scalar register and another block layout).
+template <int kLevel>
+struct LatticeOf {
+  MeshLattice g;
+  __device__ __forceinline__ explicit LatticeOf(const Volume& V) : g(mesh_lattice(V.res, kLevel)) {}
+  __device__ __forceinline__ int cr(int a) const { return g.cr[a]; }
+  __device__ __forceinline__ int ntx() const { return g.ntx; }
+  __device__ __forceinline__ int nty() const { return g.nty; }
+};
+template <>
+struct LatticeOf<0> {
+  const Volume& V;
+  __device__ __forceinline__ explicit LatticeOf(const Volume& v) : V(v) {}
+  __device__ __forceinline__ int cr(int a) const { return V.res[a]; }
+  __device__ __forceinline__ int ntx() const { return V.ntx; }
+  __device__ __forceinline__ int nty() const { return V.nty; }
+};
+template <int kLevel>
+__device__ __forceinline__ MeshTile mesh_tile(const LatticeOf<kLevel>& L) {
   MeshTile t;
   t.id = (int)blockIdx.x;
-  const int per_layer = V.ntx * V.nty, layer = t.id / per_layer, in_layer = t.id - layer * per_layer;
-  t.tz = layer; t.ty = in_layer / V.ntx; t.tx = in_layer - t.ty * V.ntx;
+  const int per_layer = L.ntx() * L.nty(), layer = t.id / per_layer, in_layer = t.id - layer * per_layer;
+  t.tz = layer; t.ty = in_layer / L.ntx(); t.tx = in_layer - t.ty * L.ntx();
   return t;
 }
 __device__ __forceinline__ int corner_index(int lx, int ly, int lz) { return (lz * 9 + ly) * 9 + lx; }
 
-// the tile's 9 x 9 x 9 corner values -> LDS; a corner outside the lattice reads -limit (no edge and no cell reaches it: see mesh_point)
+// one voxel, sanitised; (x, y, z) inside the grid
 template <bool kSparse>
-__device__ __forceinline__ void mesh_stage(const Volume& V, const MeshTile& t, float* s_f) {
+__device__ __forceinline__ float mesh_voxel(const Volume& V, int x, int y, int z) {
+  return mesh_value(kSparse ? tsdf_tap_sparse(V, x, y, z) : V.data[vol_index(V, x, y, z)], V.limit);
+}
+// the tile's 9 x 9 x 9 corner values -> LDS; a corner outside the lattice reads -limit (no edge and no cell reaches it: see mesh_point).  Lattice point
+// (x, y, z) is voxel (x, y, z) << level: a point sample (the last lattice point times the stride is below the resolution, cr = ceil(res / stride))
+template <bool kSparse, int kLevel>
+__device__ __forceinline__ void mesh_stage(const Volume& V, const LatticeOf<kLevel>& L, const MeshTile& t, float* s_f) {
   for (int i = threadIdx.x; i < kMeshCorners; i += kMeshThreads) {
     const int lx = i % 9, ly = (i / 9) % 9, lz = i / 81;
     const int x = t.tx * 8 + lx, y = t.ty * 8 + ly, z = t.tz * 8 + lz;
     float f = -V.limit;
-    if (x < V.res[0] && y < V.res[1] && z < V.res[2]) f = mesh_value(kSparse ? tsdf_tap_sparse(V, x, y, z) : V.data[vol_index(V, x, y, z)], V.limit);
+    if (x < L.cr(0) && y < L.cr(1) && z < L.cr(2)) f = mesh_voxel<kSparse>(V, x << kLevel, y << kLevel, z << kLevel);
     s_f[i] = f;
+  }
+}
+// Descent of a crossed lattice edge P -> P + (d << level) to the voxel edge that carries its vertex: bisection, the end on the midpoint's side of the
+// surface moves to the midpoint (a midpoint is a voxel read, never the LDS stage: it is no lattice point).  In: (x, y, z) = P as a voxel, a = f(P),
+// b = f(other end).  Out: neighbouring voxels (x, y, z), (x, y, z) + d with their values, exactly one of them inside, as on entry.
+template <bool kSparse, int kLevel>
+__device__ __forceinline__ void mesh_descend(const Volume& V, int bx, int by, int bz, int& x, int& y, int& z, float& a, float& b) {
+  const bool inside = a > 0.0f;
+#pragma unroll
+  for (int h = (1 << kLevel) >> 1; h >= 1; h >>= 1) {
+    const int mx = x + h * bx, my = y + h * by, mz = z + h * bz;
+    const float m = mesh_voxel<kSparse>(V, mx, my, mz);
+    if ((m > 0.0f) == inside) { a = m; x = mx; y = my; z = mz; } else b = m;
   }
 }
 
@@ -94,36 +138,40 @@ __device__ __forceinline__ uint32_t cell_triangles(uint32_t corners) {
   for (int k = 0; k < 6; ++k) n += tet_triangles(corners, k);
   return n;
 }
-__device__ __forceinline__ MeshPoint mesh_point(const Volume& V, const MeshTile& t, const float* s_f, int lane) {
+template <int kLevel>
+__device__ __forceinline__ MeshPoint mesh_point(const LatticeOf<kLevel>& L, const MeshTile& t, const float* s_f, int lane) {
   const int lx = lane & 7, ly = (lane >> 3) & 7, lz = lane >> 6;
   const int x = t.tx * 8 + lx, y = t.ty * 8 + ly, z = t.tz * 8 + lz;
   MeshPoint p{0u, 0u, 0u};
-  if (x >= V.res[0] || y >= V.res[1] || z >= V.res[2]) return p;
+  if (x >= L.cr(0) || y >= L.cr(1) || z >= L.cr(2)) return p;
   p.inside = s_f[corner_index(lx, ly, lz)] > 0.0f ? 1u : 0u;          // the raymarch's hit test, tsdf_raymarch.fs:96: zero and -0 are outside
   uint32_t corners = p.inside;
 #pragma unroll
   for (int d = 1; d < 8; ++d) {
     const int bx = d & 1, by = (d >> 1) & 1, bz = d >> 2;
-    if (x + bx < V.res[0] && y + by < V.res[1] && z + bz < V.res[2]) {
+    if (x + bx < L.cr(0) && y + by < L.cr(1) && z + bz < L.cr(2)) {
       const uint32_t in = s_f[corner_index(lx + bx, ly + by, lz + bz)] > 0.0f ? 1u : 0u;
       corners |= in << d;
       if (in != p.inside) p.mask |= 1u << (d - 1);
     }
   }
-  if (x + 1 < V.res[0] && y + 1 < V.res[1] && z + 1 < V.res[2]) p.ntri = cell_triangles(corners);
+  if (x + 1 < L.cr(0) && y + 1 < L.cr(1) && z + 1 < L.cr(2)) p.ntri = cell_triangles(corners);
   return p;
 }
 
 // ---- 1. count
-template <bool kSparse>
+template <bool kSparse, int kLevel>
 __global__ __launch_bounds__(kMeshThreads) void k_mesh_count(Volume V, uint2* __restrict__ tile_cnt, uint8_t* __restrict__ tile_skip) {
   __shared__ float s_f[kMeshCorners];
   __shared__ uint32_t s_wave[kMeshWaves];
-  const MeshTile t = mesh_tile(V);
-  // the tile and its seven +x/+y/+z neighbours hold the clear value only (-limit: outside): no edge of this tile can cross the surface
+  const LatticeOf<kLevel> L(V);
+  const MeshTile t = mesh_tile(L);
+  // the tile and its seven +x/+y/+z neighbours hold the clear value only (-limit: outside): no edge of this tile can cross the surface.  At a level the
+  // lattice tile's corners and the midpoints of its edges lie in storage tiles [t << level, (t << level) + (1 << level)] per axis: 27 / 125 lanes
+  constexpr uint32_t kN = (1u << kLevel) + 1u;
   int mixed = 0;
-  if (threadIdx.x < 8) {
-    const int nx = t.tx + (threadIdx.x & 1), ny = t.ty + ((threadIdx.x >> 1) & 1), nz = t.tz + (threadIdx.x >> 2);
+  if (threadIdx.x < kN * kN * kN) {
+    const int nx = (t.tx << kLevel) + (int)(threadIdx.x % kN), ny = (t.ty << kLevel) + (int)((threadIdx.x / kN) % kN), nz = (t.tz << kLevel) + (int)(threadIdx.x / (kN * kN));
     if (nx < V.ntx && ny < V.nty && nz < V.tz1) {
       const uint32_t id = (uint32_t)((nz * V.nty + ny) * V.ntx + nx);
       mixed = kSparse ? V.slot[id] != kNoSlot : V.cls[id] != kTileMinus;
@@ -133,9 +181,9 @@ __global__ __launch_bounds__(kMeshThreads) void k_mesh_count(Volume V, uint2* __
     if (threadIdx.x == 0) { tile_cnt[t.id] = make_uint2(0u, 0u); tile_skip[t.id] = 1; }
     return;
   }
-  mesh_stage<kSparse>(V, t, s_f);
+  mesh_stage<kSparse, kLevel>(V, L, t, s_f);
   __syncthreads();
-  const MeshPoint p = mesh_point(V, t, s_f, threadIdx.x);
+  const MeshPoint p = mesh_point(L, t, s_f, threadIdx.x);
   uint32_t total;
   block_exclusive_sum<kMeshWaves>((uint32_t)__popc(p.mask) | (p.ntri << 16), s_wave, &total);   // both counts in one word: at most 3584 and 6144 per tile
   if (threadIdx.x == 0) { tile_cnt[t.id] = make_uint2(total & 0xffffu, total >> 16); tile_skip[t.id] = 0; }
@@ -217,19 +265,20 @@ __global__ __launch_bounds__(kScanThreads) void k_mesh_scan_apply(const uint2* _
 
 // ---- 3. records and vertices
 // record of a lattice point: bits 0..6 edge mask, bit 7 inside, bits 8.. the offset of its first vertex inside the tile
-template <bool kSparse>
+template <bool kSparse, int kLevel>
 __global__ __launch_bounds__(kMeshThreads) void k_mesh_vertices(Volume V, StreamTable T, FrameImages F, MeshGeometry G, const uint2* __restrict__ tile_cnt,
                                                                 const uint32_t* __restrict__ tile_vbase, const uint32_t* __restrict__ tile_rec, uint32_t* __restrict__ records,
                                                                 float* __restrict__ out_pos, float* __restrict__ out_nrm, float4* __restrict__ out_col) {
   __shared__ float s_f[kMeshCorners];
   __shared__ uint32_t s_wave[kMeshWaves];
   __shared__ uint16_t s_edge[kMeshThreads * 7];                        // per vertex of the tile: lattice point << 3 | d
-  const MeshTile t = mesh_tile(V);
+  const LatticeOf<kLevel> L(V);
+  const MeshTile t = mesh_tile(L);
   const uint32_t nv = tile_cnt[t.id].x;
   if (nv == 0) return;
-  mesh_stage<kSparse>(V, t, s_f);
+  mesh_stage<kSparse, kLevel>(V, L, t, s_f);
   __syncthreads();
-  const MeshPoint p = mesh_point(V, t, s_f, threadIdx.x);
+  const MeshPoint p = mesh_point(L, t, s_f, threadIdx.x);
   uint32_t total;
   const uint32_t off = block_exclusive_sum<kMeshWaves>((uint32_t)__popc(p.mask), s_wave, &total);
   records[(size_t)tile_rec[t.id] * kMeshThreads + threadIdx.x] = p.mask | (p.inside << 7) | (off << 8);
@@ -246,9 +295,17 @@ __global__ __launch_bounds__(kMeshThreads) void k_mesh_vertices(Volume V, Stream
     const int e = s_edge[v], lane = e >> 3, d = e & 7;
     const int lx = lane & 7, ly = (lane >> 3) & 7, lz = lane >> 6;
     const int bx = d & 1, by = (d >> 1) & 1, bz = d >> 2;
-    const float a = s_f[corner_index(lx, ly, lz)], b = s_f[corner_index(lx + bx, ly + by, lz + bz)];
-    const float w = a / (a - b);
-    const int x = t.tx * 8 + lx, y = t.ty * 8 + ly, z = t.tz * 8 + lz;
+    float a = s_f[corner_index(lx, ly, lz)], b = s_f[corner_index(lx + bx, ly + by, lz + bz)];
+    float w;
+    int x, y, z;
+    if constexpr (kLevel == 0) {
+      w = a / (a - b);
+      x = t.tx * 8 + lx; y = t.ty * 8 + ly; z = t.tz * 8 + lz;
+    } else {                                                           // the voxel edge of the vertex: every level's vertex is a level-0 vertex
+      x = (t.tx * 8 + lx) << kLevel; y = (t.ty * 8 + ly) << kLevel; z = (t.tz * 8 + lz) << kLevel;
+      mesh_descend<kSparse, kLevel>(V, bx, by, bz, x, y, z, a, b);
+      w = a / (a - b);
+    }
     const float upx = ((float)x + 0.5f) / (float)V.res[0], uqx = ((float)(x + bx) + 0.5f) / (float)V.res[0];
     const float upy = ((float)y + 0.5f) / (float)V.res[1], uqy = ((float)(y + by) + 0.5f) / (float)V.res[1];
     const float upz = ((float)z + 0.5f) / (float)V.res[2], uqz = ((float)(z + bz) + 0.5f) / (float)V.res[2];
@@ -292,19 +349,20 @@ __device__ __forceinline__ uint32_t mesh_oct_normal(float3 n) {
   }
   return snorm16(px) | (snorm16(py) << 16);
 }
-template <bool kSparse, uint32_t kFlags>
+template <bool kSparse, uint32_t kFlags, int kLevel>
 __global__ __launch_bounds__(kMeshThreads, 4) void k_mesh_vertices_packed(Volume V, StreamTable T, FrameImages F, MeshGeometry G, const MeshStreamHeader* __restrict__ H,
                                                                           const uint2* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_vbase,
                                                                           const uint32_t* __restrict__ tile_rec, uint32_t* __restrict__ records, void* __restrict__ out) {
   __shared__ float s_f[kMeshCorners];
   __shared__ uint32_t s_wave[kMeshWaves];
   __shared__ uint16_t s_edge[kMeshThreads * 7];                        // per vertex of the tile: lattice point << 3 | d
-  const MeshTile t = mesh_tile(V);
+  const LatticeOf<kLevel> L(V);
+  const MeshTile t = mesh_tile(L);
   const uint32_t nv = tile_cnt[t.id].x;                                // (read beside the header, not behind it: one wait for both; tile_cnt is valid on overflow too)
   if (mesh_stream_overflow(H) || nv == 0) return;
-  mesh_stage<kSparse>(V, t, s_f);
+  mesh_stage<kSparse, kLevel>(V, L, t, s_f);
   __syncthreads();
-  const MeshPoint p = mesh_point(V, t, s_f, threadIdx.x);
+  const MeshPoint p = mesh_point(L, t, s_f, threadIdx.x);
   uint32_t total;
   const uint32_t off = block_exclusive_sum<kMeshWaves>((uint32_t)__popc(p.mask), s_wave, &total);
   records[(size_t)tile_rec[t.id] * kMeshThreads + threadIdx.x] = p.mask | (p.inside << 7) | (off << 8);   // (tile_rec < needed_tiles <= max_tiles)
@@ -321,9 +379,17 @@ __global__ __launch_bounds__(kMeshThreads, 4) void k_mesh_vertices_packed(Volume
     const int e = s_edge[v], lane = e >> 3, d = e & 7;
     const int lx = lane & 7, ly = (lane >> 3) & 7, lz = lane >> 6;
     const int bx = d & 1, by = (d >> 1) & 1, bz = d >> 2;
-    const float a = s_f[corner_index(lx, ly, lz)], b = s_f[corner_index(lx + bx, ly + by, lz + bz)];
-    const float w = a / (a - b);
-    const int x = t.tx * 8 + lx, y = t.ty * 8 + ly, z = t.tz * 8 + lz;
+    float a = s_f[corner_index(lx, ly, lz)], b = s_f[corner_index(lx + bx, ly + by, lz + bz)];
+    float w;
+    int x, y, z;
+    if constexpr (kLevel == 0) {
+      w = a / (a - b);
+      x = t.tx * 8 + lx; y = t.ty * 8 + ly; z = t.tz * 8 + lz;
+    } else {                                                           // the voxel edge of the vertex: every level's vertex is a level-0 vertex
+      x = (t.tx * 8 + lx) << kLevel; y = (t.ty * 8 + ly) << kLevel; z = (t.tz * 8 + lz) << kLevel;
+      mesh_descend<kSparse, kLevel>(V, bx, by, bz, x, y, z, a, b);
+      w = a / (a - b);
+    }
     const float upx = ((float)x + 0.5f) / (float)V.res[0], uqx = ((float)(x + bx) + 0.5f) / (float)V.res[0];
     const float upy = ((float)y + 0.5f) / (float)V.res[1], uqy = ((float)(y + by) + 0.5f) / (float)V.res[1];
     const float upz = ((float)z + 0.5f) / (float)V.res[2], uqz = ((float)(z + bz) + 0.5f) / (float)V.res[2];
@@ -352,20 +418,22 @@ __device__ __forceinline__ uint32_t edge_vertex(const uint32_t* s_first, const u
   const int i = corner_index(lx + (x & 1), ly + ((x >> 1) & 1), lz + (x >> 2)), d = y - x;
   return s_first[i] + (uint32_t)__popc((uint32_t)s_mask[i] & ((1u << (d - 1)) - 1u));
 }
+template <int kLevel>
 __device__ __forceinline__ void mesh_tile_triangles(const Volume& V, const uint2* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_vbase,
                                                     const unsigned long long* __restrict__ tile_tbase, const uint32_t* __restrict__ tile_rec,
                                                     const uint32_t* __restrict__ records, uint32_t* __restrict__ out_tri) {
   __shared__ uint32_t s_first[kMeshCorners];                           // per corner: the mesh index of the first vertex it owns
   __shared__ uint8_t s_mask[kMeshCorners];                             // ... and its record's low byte (edge mask, inside bit)
   __shared__ uint32_t s_wave[kMeshWaves];
-  const MeshTile t = mesh_tile(V);
+  const LatticeOf<kLevel> L(V);
+  const MeshTile t = mesh_tile(L);
   if (tile_cnt[t.id].y == 0) return;
   for (int i = threadIdx.x; i < kMeshCorners; i += kMeshThreads) {
     const int lx = i % 9, ly = (i / 9) % 9, lz = i / 81;
     const int x = t.tx * 8 + lx, y = t.ty * 8 + ly, z = t.tz * 8 + lz;
     uint32_t first = 0, mask = 0;
-    if (x < V.res[0] && y < V.res[1] && z < V.res[2]) {
-      const int tile = ((z >> 3) * V.nty + (y >> 3)) * V.ntx + (x >> 3);
+    if (x < L.cr(0) && y < L.cr(1) && z < L.cr(2)) {
+      const int tile = ((z >> 3) * L.nty() + (y >> 3)) * L.ntx() + (x >> 3);
       const uint32_t slot = tile_rec[tile];
       if (slot != kNoSlot) {                                           // (a tile without surface owns no crossed edge: nothing is looked up in it)
         const uint32_t r = records[(size_t)slot * kMeshThreads + (((z & 7) << 6) | ((y & 7) << 3) | (x & 7))];
@@ -379,7 +447,7 @@ __device__ __forceinline__ void mesh_tile_triangles(const Volume& V, const uint2
   const int x = t.tx * 8 + lx, y = t.ty * 8 + ly, z = t.tz * 8 + lz;
   // the cell's corner bits from its origin's record: corner b is inside iff the origin is, unless the edge origin -> b is crossed
   uint32_t corners = 0, ntri = 0;
-  if (x + 1 < V.res[0] && y + 1 < V.res[1] && z + 1 < V.res[2]) {
+  if (x + 1 < L.cr(0) && y + 1 < L.cr(1) && z + 1 < L.cr(2)) {
     const uint32_t m = s_mask[corner_index(lx, ly, lz)];
     corners = ((m & 0x7fu) << 1) ^ ((m & 0x80u) ? 0xffu : 0u);
     ntri = cell_triangles(corners);
@@ -417,18 +485,20 @@ __device__ __forceinline__ void mesh_tile_triangles(const Volume& V, const uint2
     }
   }
 }
+template <int kLevel>
 __global__ __launch_bounds__(kMeshThreads) void k_mesh_triangles(Volume V, const uint2* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_vbase,
                                                                  const unsigned long long* __restrict__ tile_tbase, const uint32_t* __restrict__ tile_rec,
                                                                  const uint32_t* __restrict__ records, uint32_t* __restrict__ out_tri) {
-  mesh_tile_triangles(V, tile_cnt, tile_vbase, tile_tbase, tile_rec, records, out_tri);
+  mesh_tile_triangles<kLevel>(V, tile_cnt, tile_vbase, tile_tbase, tile_rec, records, out_tri);
 }
 // the streamed form: the triangle array follows the frame's vertices directly (payload + needed_vertices * stride: one copy takes both)
+template <int kLevel>
 __global__ __launch_bounds__(kMeshThreads) void k_mesh_triangles_stream(Volume V, const MeshStreamHeader* __restrict__ H, const uint2* __restrict__ tile_cnt,
                                                                         const uint32_t* __restrict__ tile_vbase, const unsigned long long* __restrict__ tile_tbase,
                                                                         const uint32_t* __restrict__ tile_rec, const uint32_t* __restrict__ records,
                                                                         uint8_t* __restrict__ payload, uint32_t stride) {
   if (mesh_stream_overflow(H)) return;
-  mesh_tile_triangles(V, tile_cnt, tile_vbase, tile_tbase, tile_rec, records, (uint32_t*)(payload + (size_t)H->needed_vertices * stride));
+  mesh_tile_triangles<kLevel>(V, tile_cnt, tile_vbase, tile_tbase, tile_rec, records, (uint32_t*)(payload + (size_t)H->needed_vertices * stride));
 }
 // one lane: the frame's header from the scan's totals (sums[nb]) and the ring's capacities
 __global__ void k_mesh_stream_header(const MeshSums* __restrict__ totals, MeshStreamHeader* __restrict__ H, uint32_t max_vertices, uint32_t max_triangles, uint32_t max_tiles) {
@@ -441,11 +511,24 @@ __global__ void k_mesh_stream_header(const MeshSums* __restrict__ totals, MeshSt
   *H = h;
 }
 
-// ---- launchers
+// ---- launchers.  S.level picks the instantiation; the caller has checked it (0 .. kMeshMaxLevel) and sized S by mesh_lattice(res, level).
 int mesh_scan_blocks(int n_tiles) { return (n_tiles + kScanPerBlock - 1) / kScanPerBlock; }
+// f(sparse, level), both as compile-time constants: the one place that turns the volume's storage and the scratch's level into template arguments
+template <typename F>
+static void mesh_instantiation(const Volume& V, const MeshScratch& S, F&& f) {
+  auto at = [&](auto sparse) {
+    switch (S.level) {
+      case 0: f(sparse, std::integral_constant<int, 0>{}); break;
+      case 1: f(sparse, std::integral_constant<int, 1>{}); break;
+      default: f(sparse, std::integral_constant<int, 2>{}); break;
+    }
+  };
+  if (V.slot) at(std::true_type{}); else at(std::false_type{});
+}
 void launch_mesh_count(hipStream_t st, const Volume& V, const MeshScratch& S) {
-  if (V.slot) hipLaunchKernelGGL(k_mesh_count<true>, dim3(S.n_tiles), dim3(kMeshThreads), 0, st, V, S.tile_cnt, S.tile_skip);
-  else hipLaunchKernelGGL(k_mesh_count<false>, dim3(S.n_tiles), dim3(kMeshThreads), 0, st, V, S.tile_cnt, S.tile_skip);
+  mesh_instantiation(V, S, [&](auto sparse, auto level) {
+    hipLaunchKernelGGL((k_mesh_count<decltype(sparse)::value, decltype(level)::value>), dim3(S.n_tiles), dim3(kMeshThreads), 0, st, V, S.tile_cnt, S.tile_skip);
+  });
 }
 void launch_mesh_scan(hipStream_t st, const MeshScratch& S) {
   const int nb = mesh_scan_blocks(S.n_tiles);
@@ -456,9 +539,12 @@ void launch_mesh_scan(hipStream_t st, const MeshScratch& S) {
 }
 void launch_mesh_emit(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S, uint32_t* records,
                       float* pos, float* nrm, float* col, uint32_t* tri) {
-  if (V.slot) hipLaunchKernelGGL(k_mesh_vertices<true>, dim3(S.n_tiles), dim3(kMeshThreads), 0, st, V, T, F, G, S.tile_cnt, S.tile_vbase, S.tile_rec, records, pos, nrm, (float4*)col);
-  else hipLaunchKernelGGL(k_mesh_vertices<false>, dim3(S.n_tiles), dim3(kMeshThreads), 0, st, V, T, F, G, S.tile_cnt, S.tile_vbase, S.tile_rec, records, pos, nrm, (float4*)col);
-  hipLaunchKernelGGL(k_mesh_triangles, dim3(S.n_tiles), dim3(kMeshThreads), 0, st, V, S.tile_cnt, S.tile_vbase, S.tile_tbase, S.tile_rec, records, tri);
+  mesh_instantiation(V, S, [&](auto sparse, auto level) {
+    constexpr bool kSparse = decltype(sparse)::value;
+    constexpr int kLevel = decltype(level)::value;
+    hipLaunchKernelGGL((k_mesh_vertices<kSparse, kLevel>), dim3(S.n_tiles), dim3(kMeshThreads), 0, st, V, T, F, G, S.tile_cnt, S.tile_vbase, S.tile_rec, records, pos, nrm, (float4*)col);
+    hipLaunchKernelGGL(k_mesh_triangles<kLevel>, dim3(S.n_tiles), dim3(kMeshThreads), 0, st, V, S.tile_cnt, S.tile_vbase, S.tile_tbase, S.tile_rec, records, tri);
+  });
 }
 
 // the streamed form's emit: header, packed vertices, triangles.  payload: max_vertices * stride + max_triangles * 12 bytes; records: 512 words for each
@@ -466,23 +552,20 @@ void launch_mesh_emit(hipStream_t st, const Volume& V, const StreamTable& T, con
 void launch_mesh_stream_header(hipStream_t st, const MeshScratch& S, MeshStreamHeader* H, uint32_t max_vertices, uint32_t max_triangles, uint32_t max_tiles) {
   hipLaunchKernelGGL(k_mesh_stream_header, dim3(1), dim3(1), 0, st, (const MeshSums*)S.sums + mesh_scan_blocks(S.n_tiles), H, max_vertices, max_triangles, max_tiles);
 }
-template <bool kSparse>
-static void launch_vertices_packed(hipStream_t st, uint32_t flags, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S,
-                                   const MeshStreamHeader* H, uint32_t* records, void* payload) {
-  const dim3 g(S.n_tiles), b(kMeshThreads);
-  switch (flags & 3u) {
-    case 0u: hipLaunchKernelGGL((k_mesh_vertices_packed<kSparse, 0u>), g, b, 0, st, V, T, F, G, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
-    case 1u: hipLaunchKernelGGL((k_mesh_vertices_packed<kSparse, 1u>), g, b, 0, st, V, T, F, G, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
-    case 2u: hipLaunchKernelGGL((k_mesh_vertices_packed<kSparse, 2u>), g, b, 0, st, V, T, F, G, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
-    default: hipLaunchKernelGGL((k_mesh_vertices_packed<kSparse, 3u>), g, b, 0, st, V, T, F, G, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
-  }
-}
 void launch_mesh_stream_emit(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S, uint32_t flags,
                              const MeshStreamHeader* H, uint32_t* records, void* payload) {
-  if (V.slot) launch_vertices_packed<true>(st, flags, V, T, F, G, S, H, records, payload);
-  else launch_vertices_packed<false>(st, flags, V, T, F, G, S, H, records, payload);
-  hipLaunchKernelGGL(k_mesh_triangles_stream, dim3(S.n_tiles), dim3(kMeshThreads), 0, st, V, H, S.tile_cnt, S.tile_vbase, S.tile_tbase, S.tile_rec, records, (uint8_t*)payload,
-                     flags ? 16u : 8u);
+  mesh_instantiation(V, S, [&](auto sparse, auto level) {
+    constexpr bool kSparse = decltype(sparse)::value;
+    constexpr int kLevel = decltype(level)::value;
+    const dim3 g(S.n_tiles), b(kMeshThreads);
+    switch (flags & 3u) {
+      case 0u: hipLaunchKernelGGL((k_mesh_vertices_packed<kSparse, 0u, kLevel>), g, b, 0, st, V, T, F, G, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
+      case 1u: hipLaunchKernelGGL((k_mesh_vertices_packed<kSparse, 1u, kLevel>), g, b, 0, st, V, T, F, G, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
+      case 2u: hipLaunchKernelGGL((k_mesh_vertices_packed<kSparse, 2u, kLevel>), g, b, 0, st, V, T, F, G, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
+      default: hipLaunchKernelGGL((k_mesh_vertices_packed<kSparse, 3u, kLevel>), g, b, 0, st, V, T, F, G, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
+    }
+    hipLaunchKernelGGL(k_mesh_triangles_stream<kLevel>, g, b, 0, st, V, H, S.tile_cnt, S.tile_vbase, S.tile_tbase, S.tile_rec, records, (uint8_t*)payload, flags ? 16u : 8u);
+  });
 }
 
 }  // namespace rr

@@ -344,6 +344,21 @@ void launch_resolve_masked(hipStream_t st, const Atlas& A, int w, int h, float4*
 void launch_present(hipStream_t st, const float4* fb_c, void* out, int w, int h, uint32_t format, int top_down);
 // mesh extraction (k_mesh.hip): per-tile scratch of one extract, sized by the launchers' caller.  Whole-volume contexts only: tile id = stored tile index.
 struct MeshGeometry { float bbox_min[3], bbox_max[3]; };
+// The lattice of a level of detail (tsdf_mesh_extract_lod): lattice point (i, j, k) of level L is voxel (i, j, k) << L, cr = ceil(res / (1 << L)) points
+// per axis, tiles of 8^3 lattice points.  Level 0 is the voxel grid and its storage tiles.  A lattice tile's id is (tz * nty + ty) * ntx + tx.
+constexpr int kMeshMaxLevel = 2;
+struct MeshLattice {
+  int level;
+  int cr[3];            // lattice points per axis
+  int ntx, nty, ntz;    // lattice tiles per axis
+};
+__host__ __device__ inline MeshLattice mesh_lattice(const int res[3], int level) {
+  MeshLattice L;
+  L.level = level;
+  for (int a = 0; a < 3; ++a) L.cr[a] = (res[a] + (1 << level) - 1) >> level;
+  L.ntx = (L.cr[0] + 7) >> 3; L.nty = (L.cr[1] + 7) >> 3; L.ntz = (L.cr[2] + 7) >> 3;
+  return L;
+}
 struct MeshScratch {
   uint2* tile_cnt;                  // per tile {vertices, triangles}
   uint8_t* tile_skip;               // per tile: 1 = skipped by its class (no voxel read)
@@ -351,7 +366,8 @@ struct MeshScratch {
   unsigned long long* tile_tbase;   // ... of the triangle counts
   uint32_t* tile_rec;               // compact slot of a tile with surface in the record pool, or kNoSlot
   void* sums;                       // mesh_scan_blocks(n_tiles) + 1 entries of 4 x uint64: per-block prefixes, then the totals {vertices, triangles, tiles with surface, tiles skipped}
-  int n_tiles;
+  int n_tiles;                      // lattice tiles of `level`: ntx * nty * ntz of mesh_lattice(res, level)
+  int level;                        // 0 .. kMeshMaxLevel: which instantiation the launchers take
 };
 int mesh_scan_blocks(int n_tiles);
 void launch_mesh_count(hipStream_t st, const Volume& V, const MeshScratch& S);

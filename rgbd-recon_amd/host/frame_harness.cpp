@@ -15,6 +15,8 @@
 // Option --mesh-stream: five more draws of the frame, each followed by streamMesh (packed vertices with normals and colours into a 3-slot ring), the
 // frames picked up two frames late and the last two after the loop; tags must come back in order, no frame may overflow, and every frame's counts
 // must equal those of extractMesh on the same volume (zero for this scene).
+// Option --mesh-level N (0, 1, 2), applied to --mesh and --mesh-stream: the mesh at that level of detail (the lattice of every 2^N-th voxel) through the
+// adapter's overloads with a level; the streamed frames' counts must equal those of the extract at the same level, and the ring must report the level.
 //   g++ -std=c++17 frame_harness.cpp -o frame_harness -L.. -lrgbd_recon_hip -Wl,-rpath,'$ORIGIN/..'
 #include <cmath>
 #include <cstdio>
@@ -31,6 +33,7 @@ int main(int argc, char** argv) {
   int present_format = -1;
   const char* mesh_path = nullptr;
   bool mesh_stream = false;
+  int mesh_level = -1;                                                    // -1: not given (the entries without a level)
   for (int a = 1; a < argc; ++a) {
     if (std::strcmp(argv[a], "--draw-bricks") == 0) draw_bricks = true;
     else if (std::strcmp(argv[a], "--sensor-view") == 0 && a + 2 < argc) { view_type = std::atoi(argv[a + 1]); view_width = (float)std::atof(argv[a + 2]); a += 2; }
@@ -39,7 +42,11 @@ int main(int argc, char** argv) {
     }
     else if (std::strcmp(argv[a], "--mesh") == 0 && a + 1 < argc) { mesh_path = argv[a + 1]; a += 1; }
     else if (std::strcmp(argv[a], "--mesh-stream") == 0) mesh_stream = true;
-    else { std::fprintf(stderr, "usage: frame_harness [--draw-bricks] [--sensor-view TYPE WIDTH] [--present rgba8|dxt1] [--mesh FILE.ply] [--mesh-stream]\n"); return 1; }
+    else if (std::strcmp(argv[a], "--mesh-level") == 0 && a + 1 < argc && std::strlen(argv[a + 1]) == 1 && argv[a + 1][0] >= '0' && argv[a + 1][0] <= '2') { mesh_level = argv[a + 1][0] - '0'; a += 1; }
+    else {
+      std::fprintf(stderr, "usage: frame_harness [--draw-bricks] [--sensor-view TYPE WIDTH] [--present rgba8|dxt1] [--mesh FILE.ply] [--mesh-stream] [--mesh-level 0|1|2]\n");
+      return 1;
+    }
   }
   kinect::ReconInputs in;
   in.num_kinects = 1;
@@ -134,7 +141,7 @@ int main(int argc, char** argv) {
       if (got != frames || wrong != 0) return 1;
     }
     if (mesh_path) {
-      const kinect::ReconIntegrationHip::MeshCounts n = recon.extractMesh(true, true);
+      const kinect::ReconIntegrationHip::MeshCounts n = mesh_level < 0 ? recon.extractMesh(true, true) : recon.extractMesh(true, true, (unsigned)mesh_level);
       kinect::ReconIntegrationHip::Mesh mesh;
       recon.downloadMesh(mesh);
       recon.writeMeshPly(mesh_path);
@@ -142,8 +149,10 @@ int main(int argc, char** argv) {
       if (mesh.position.size() != n.vertices * 3 || mesh.normal.size() != n.vertices * 3 || mesh.colour.size() != n.vertices * 4 || mesh.triangles.size() != n.triangles * 3) return 1;
     }
     if (mesh_stream) {
-      const kinect::ReconIntegrationHip::MeshCounts n = recon.extractMesh(false, false);
-      recon.configureMeshStream(true, true, 4096, 8192, 64, 3);
+      const kinect::ReconIntegrationHip::MeshCounts n = mesh_level < 0 ? recon.extractMesh(false, false) : recon.extractMesh(false, false, (unsigned)mesh_level);
+      if (mesh_level < 0) recon.configureMeshStream(true, true, 4096, 8192, 64, 3);
+      else recon.configureMeshStream(true, true, (unsigned)mesh_level, 4096, 8192, 64, 3);
+      if (recon.meshStreamLevel() != (unsigned)(mesh_level < 0 ? 0 : mesh_level)) return 1;
       const int frames = 5, lag = 2;
       int got = 0, wrong = 0;
       auto take = [&](std::uint64_t want_tag) {

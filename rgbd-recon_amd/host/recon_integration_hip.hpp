@@ -177,6 +177,14 @@ class ReconIntegrationHip {
     check(tsdf_mesh_extract(m_ctx, m_mesh_flags, &m_mesh.vertices, &m_mesh.triangles));
     return m_mesh;
   }
+  // ... at a level of detail (tsdf_mesh_extract_lod): level 1 / 2 = the same surface on the lattice of every 2nd / 4th voxel, every vertex one of the
+  // full mesh's; level 0 is extractMesh(normals, colours).  downloadMesh / writeMeshPly serve whichever extract was last.
+  MeshCounts extractMesh(bool normals, bool colours, unsigned level) {
+    m_mesh_flags = (normals ? TSDF_MESH_NORMALS : 0u) | (colours ? TSDF_MESH_COLOURS : 0u);
+    m_mesh = MeshCounts{};
+    check(tsdf_mesh_extract_lod(m_ctx, m_mesh_flags, level, &m_mesh.vertices, &m_mesh.triangles));
+    return m_mesh;
+  }
   void downloadMesh(Mesh& out) {
     out.position.resize((std::size_t)m_mesh.vertices * 3);
     out.normal.resize((m_mesh_flags & TSDF_MESH_NORMALS) ? (std::size_t)m_mesh.vertices * 3 : 0);
@@ -192,6 +200,17 @@ class ReconIntegrationHip {
   struct MeshStreamStats { std::uint64_t frames = 0, overflowed = 0, payload_bytes = 0, device_bytes = 0; };
   void configureMeshStream(bool normals, bool colours, unsigned max_vertices, unsigned max_triangles, unsigned max_surface_tiles, unsigned slots = 3) {
     check(tsdf_mesh_stream_config(m_ctx, (normals ? TSDF_MESH_NORMALS : 0u) | (colours ? TSDF_MESH_COLOURS : 0u), max_vertices, max_triangles, max_surface_tiles, slots));
+  }
+  // ... at a level of detail (tsdf_mesh_stream_config_lod; the level follows the attributes as in the C entry, every argument given): every frame is
+  // that level's mesh and max_surface_tiles counts its 8^3 lattice tiles.  meshStreamLevel: the level of the last configuration.
+  void configureMeshStream(bool normals, bool colours, unsigned level, unsigned max_vertices, unsigned max_triangles, unsigned max_surface_tiles, unsigned slots) {
+    check(tsdf_mesh_stream_config_lod(m_ctx, (normals ? TSDF_MESH_NORMALS : 0u) | (colours ? TSDF_MESH_COLOURS : 0u), level, max_vertices, max_triangles,
+                                      max_surface_tiles, slots));
+  }
+  unsigned meshStreamLevel() {
+    std::uint32_t level = 0;
+    check(tsdf_mesh_stream_level(m_ctx, &level));
+    return level;
   }
   // after drawF(): never blocks; false = every slot is queued or held (or there is no volume yet), nothing was queued
   bool streamMesh(std::uint64_t tag) {

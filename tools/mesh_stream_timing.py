@@ -5,7 +5,11 @@
 2. Frames per second of the tsdf_frame_dev loop (timers off, a host clock around FRAMES frames that ends in a synchronise) in three forms: plain; with
    mesh_stream every frame (3-slot ring, frames picked up two late and copied out of the pinned buffer); with a synchronous extract + download
    every frame.  Bytes per frame to the host for both forms.
-A record, not a threshold.  Prints one JSON line; with a file argument, also writes it to that file; --stages-only leaves part 2 out."""
+A record, not a threshold.  Prints one JSON line; with a file argument, also writes it to that file; --stages-only leaves part 2 out.
+--level L[,L..] (0, 1, 2; default 0): the levels of detail to time (tsdf_mesh_stream_config_lod / tsdf_mesh_extract_lod).  In part 1 the levels alternate
+call by call in this one process (the ring is configured anew for each call, outside the timers), in part 2 loop by loop; the record then has a "levels"
+entry with each level's counts, capacities, stages (and the spread of the streamed device time over the N calls) and bytes per frame, and the frame
+rates carry the level in their names.  The top-level entries stay those of the first level named."""
 import sys, os, json, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch  # noqa: F401  (torch first: the library binds to the HIP runtime torch loaded)
@@ -15,7 +19,9 @@ N = 10
 FRAMES = 300
 EXTRACT_FRAMES = 30
 STAGES_ONLY = "--stages-only" in sys.argv
-OUT = [a for a in sys.argv[1:] if not a.startswith("--")]
+ARGS = sys.argv[1:]
+LEVELS = [int(x) for x in ARGS[ARGS.index("--level") + 1].split(",")] if "--level" in ARGS else [0]
+OUT = [a for i, a in enumerate(ARGS) if not a.startswith("--") and (i == 0 or ARGS[i - 1] != "--level")]
 VARIANTS = (("positions", dict(normals=False, colours=False)), ("normals", dict(normals=True, colours=False)), ("colours", dict(normals=False, colours=True)),
             ("all_attributes", dict(normals=True, colours=True)))
 STREAM_STAGES = ("mesh_stream_count", "mesh_stream_scan", "mesh_stream_emit")
@@ -32,36 +38,55 @@ ptrs = [t.data_ptr() for t in dev]
 for _ in range(4):                                                       # both volume sets hold the frame
     hip.frame_dev(mv, pr, ptrs)
 hip.sync()
-mesh = hip.extract_mesh(normals=False, colours=False)
-st = hip.mesh_stats()
-nv, nt, ns = len(mesh["position"]), len(mesh["triangles"]), st["tiles_with_surface"]
-caps = dict(max_vertices=nv + nv // 4, max_triangles=nt + nt // 4, max_surface_tiles=ns + ns // 4)
-rec = dict(shape="c2", res=list(hip.res), streams=4, vertices=nv, triangles=nt, tiles=st["tiles"], tiles_skipped=st["tiles_skipped"], tiles_with_surface=ns,
-           capacities=caps)
+levels = {}
+for L in LEVELS:
+    mesh = hip.extract_mesh(normals=False, colours=False, level=L)
+    st = hip.mesh_stats()
+    nv, nt, ns = len(mesh["position"]), len(mesh["triangles"]), st["tiles_with_surface"]
+    levels[L] = dict(vertices=nv, triangles=nt, tiles=st["tiles"], tiles_skipped=st["tiles_skipped"], tiles_with_surface=ns,
+                     capacities=dict(max_vertices=nv + nv // 4, max_triangles=nt + nt // 4, max_surface_tiles=ns + ns // 4))
+rec = dict(shape="c2", res=list(hip.res), streams=4, level=LEVELS[0], **{k: v for k, v in levels[LEVELS[0]].items()})
 
 # 1. device time per stage
 hip.enable_timers(True)
 hip.set_timer_filter(list(STREAM_STAGES + EXTRACT_STAGES))
+def one_call(L, kw):
+    """one streamed frame and one extract of level L; with one level the ring keeps its configuration"""
+    if len(LEVELS) > 1 or not one_call.configured:
+        hip.mesh_stream_config(slots=3, level=L, **kw, **levels[L]["capacities"])
+        one_call.configured = True
+    hip.mesh_stream(0); got = hip.mesh_stream_take()
+    hip.extract_mesh(level=L, **kw)
+    return got
 for label, kw in VARIANTS:
-    hip.mesh_stream_config(slots=3, **kw, **caps)
+    one_call.configured = False
     for _ in range(2):
-        hip.mesh_stream(0); got = hip.mesh_stream_take()
-        hip.extract_mesh(**kw)
-    assert got[2]["overflow"] == 0 and got[2]["n_vertices"] == nv and got[2]["n_triangles"] == nt
+        for L in LEVELS:
+            got = one_call(L, kw)
+            assert got[2]["overflow"] == 0 and got[2]["n_vertices"] == levels[L]["vertices"] and got[2]["n_triangles"] == levels[L]["triangles"]
     for s in STREAM_STAGES + EXTRACT_STAGES:
         hip.timer_stats(s)                                               # (resets the timer's samples)
-    for _ in range(N):                                                   # alternating: both forms see the same machine
-        hip.mesh_stream(0); hip.mesh_stream_take()
-        hip.extract_mesh(**kw)
-    r = {}
-    for name, stages in (("stream", STREAM_STAGES), ("extract", EXTRACT_STAGES)):
-        t = {s + "_ms": (lambda ct: ct[1] / ct[0])(hip.timer_stats(s)) for s in stages}
-        t["device_ms"] = sum(t.values())
-        r[name] = t
+    samples = {L: {s: [] for s in STREAM_STAGES + EXTRACT_STAGES} for L in LEVELS}
+    for _ in range(N):                                                   # alternating: both forms, and every level, see the same machine
+        for L in LEVELS:
+            one_call(L, kw)
+            for s in STREAM_STAGES + EXTRACT_STAGES:
+                cnt, total = hip.timer_stats(s)
+                samples[L][s].append(total / cnt)
     stride = 16 if (kw["normals"] or kw["colours"]) else 8
-    r["stream_bytes_per_frame"] = nv * stride + nt * 12 + 64            # payload + header
-    r["extract_bytes_per_frame"] = nv * (12 + (12 if kw["normals"] else 0) + (16 if kw["colours"] else 0)) + nt * 12
-    rec[label] = r
+    for L in LEVELS:
+        r = {}
+        for name, stages in (("stream", STREAM_STAGES), ("extract", EXTRACT_STAGES)):
+            t = {s + "_ms": float(np.mean(samples[L][s])) for s in stages}
+            per_call = np.sum([samples[L][s] for s in stages], axis=0)
+            t["device_ms"] = sum(t.values())
+            t["device_ms_min"], t["device_ms_max"] = float(per_call.min()), float(per_call.max())
+            r[name] = t
+        nv, nt = levels[L]["vertices"], levels[L]["triangles"]
+        r["stream_bytes_per_frame"] = nv * stride + nt * 12 + 64        # payload + header
+        r["extract_bytes_per_frame"] = nv * (12 + (12 if kw["normals"] else 0) + (16 if kw["colours"] else 0)) + nt * 12
+        levels[L][label] = r
+    rec[label] = levels[LEVELS[0]][label]
 hip.enable_timers(False)
 
 # 2. the frame loop
@@ -85,17 +110,21 @@ def drain_stream():
 
 nothing = lambda: None
 fps = {}
+suffix = (lambda L: "_level%d" % L) if "--level" in ARGS else (lambda L: "")
 for rep in range(0 if STAGES_ONLY else 3):                              # the three forms in turn, three times: the spread is part of the record
-    for label, kw in (("positions", dict(normals=False, colours=False)), ("all_attributes", dict(normals=True, colours=True))):
-        hip.mesh_stream_config(slots=3, **kw, **caps)
-        streamed.taken = 0
-        before = hip.mesh_stream_stats()["payload_bytes"]
-        fps.setdefault("stream_" + label, []).append(loop(FRAMES, streamed, drain_stream))
-        rec[label]["stream_payload_bytes_measured"] = (hip.mesh_stream_stats()["payload_bytes"] - before) // (FRAMES + 10)
-        fps.setdefault("extract_" + label, []).append(loop(EXTRACT_FRAMES, lambda f: hip.extract_mesh(**kw), nothing))
+    for L in LEVELS:
+        for label, kw in (("positions", dict(normals=False, colours=False)), ("all_attributes", dict(normals=True, colours=True))):
+            hip.mesh_stream_config(slots=3, level=L, **kw, **levels[L]["capacities"])
+            streamed.taken = 0
+            before = hip.mesh_stream_stats()["payload_bytes"]
+            fps.setdefault("stream_" + label + suffix(L), []).append(loop(FRAMES, streamed, drain_stream))
+            levels[L][label]["stream_payload_bytes_measured"] = (hip.mesh_stream_stats()["payload_bytes"] - before) // (FRAMES + 10)
+            fps.setdefault("extract_" + label + suffix(L), []).append(loop(EXTRACT_FRAMES, lambda f: hip.extract_mesh(level=L, **kw), nothing))
     fps.setdefault("plain", []).append(loop(FRAMES, lambda f: None, nothing))
 if fps:
     rec["frames_per_s"] = {k: dict(runs=[round(x, 1) for x in v], median=round(float(np.median(v)), 1)) for k, v in fps.items()}
+if "--level" in ARGS:
+    rec["levels"] = {str(L): levels[L] for L in LEVELS}
 print(json.dumps(rec), flush=True)
 if OUT:
     with open(OUT[0], "w") as f:

@@ -2,7 +2,10 @@
 c2 (512^3 culled, 4 streams).  Device time per stage from the library's HIP-event timers: "mesh_count" (one launch), "mesh_scan" (three), "mesh_emit"
 (vertices + triangles), each for the position-only extract and for the one with normals and colours; the volume download is bracketed by a timer of
 this tool's own on the context's stream (tile-major -> linear launch + the 512 MiB copy to pageable host memory).  A record, not a threshold.  Prints
-one JSON line; with an argument, also writes it to that file."""
+one JSON line; with a file argument, also writes it to that file.
+--level L[,L..] (0, 1, 2; default 0): the levels of detail to time (tsdf_mesh_extract_lod), alternating call by call in this one process so that every
+level sees the same machine; the record then has a "levels" entry with each level's stages, the spread of its device time over the N calls, its counts
+and its mesh bytes.  The top-level entries stay those of the first level named."""
 import sys, os, json, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch  # noqa: F401  (torch first: the library binds to the HIP runtime torch loaded)
@@ -10,6 +13,9 @@ import rgbd_recon_amd as rr
 VIEW = (1280, 720)
 N = 10
 STAGES = ("mesh_count", "mesh_scan", "mesh_emit")
+ARGS = sys.argv[1:]
+LEVELS = [int(x) for x in ARGS[ARGS.index("--level") + 1].split(",")] if "--level" in ARGS else [0]
+OUT = [a for i, a in enumerate(ARGS) if not a.startswith("--") and (i == 0 or ARGS[i - 1] != "--level")]
 
 scene = rr.scene.make_scene(n_streams=4, width=640, height=480, lut_res=128, inv_res=128)
 ext = scene["bbox_max"] - scene["bbox_min"]
@@ -21,22 +27,41 @@ hip.sync()
 hip.enable_timers(True)
 hip.set_timer_filter(list(STAGES) + ["volume_download"])
 rec = dict(shape="c2", res=list(hip.res), streams=4)
+levels = {L: {} for L in LEVELS}
 for label, kw in (("positions", dict(normals=False, colours=False)), ("all_attributes", dict(normals=True, colours=True))):
     for _ in range(2):
-        mesh = hip.extract_mesh(**kw)
+        for L in LEVELS:
+            mesh = hip.extract_mesh(level=L, **kw)
+            st = hip.mesh_stats()
+            levels[L].update(vertices=len(mesh["position"]), triangles=len(mesh["triangles"]), tiles=st["tiles"], tiles_skipped=st["tiles_skipped"],
+                             tiles_with_surface=st["tiles_with_surface"])
+            levels[L]["mesh_bytes_" + label] = st["bytes"]
     for s in STAGES:
         hip.timer_stats(s)                                               # (resets the timer's samples)
-    t0 = time.perf_counter()
-    for _ in range(N):
-        hip.extract_mesh(**kw)
-    wall = (time.perf_counter() - t0) / N * 1e3
-    r = {s + "_ms": (lambda ct: ct[1] / ct[0])(hip.timer_stats(s)) for s in STAGES}
-    r["device_ms"] = sum(r.values())
-    r["call_and_download_wall_ms"] = wall                                # extract + tsdf_mesh_download into numpy arrays
-    rec[label] = r
-st = hip.mesh_stats()
-rec.update(vertices=len(mesh["position"]), triangles=len(mesh["triangles"]), mesh_bytes=st["bytes"], tiles=st["tiles"], tiles_skipped=st["tiles_skipped"],
-           tiles_with_surface=st["tiles_with_surface"])
+    samples = {L: {s: [] for s in STAGES} for L in LEVELS}
+    wall = {L: 0.0 for L in LEVELS}
+    for _ in range(N):                                                   # the levels in turn, N times: all of them see the same machine
+        for L in LEVELS:
+            t0 = time.perf_counter()
+            hip.extract_mesh(level=L, **kw)
+            wall[L] += time.perf_counter() - t0
+            for s in STAGES:
+                cnt, total = hip.timer_stats(s)
+                samples[L][s].append(total / cnt)
+    for L in LEVELS:
+        r = {s + "_ms": float(np.mean(samples[L][s])) for s in STAGES}
+        per_call = np.sum([samples[L][s] for s in STAGES], axis=0)
+        r["device_ms"] = sum(r.values())
+        r["device_ms_min"], r["device_ms_max"] = float(per_call.min()), float(per_call.max())
+        r["call_and_download_wall_ms"] = wall[L] / N * 1e3               # extract + tsdf_mesh_download into numpy arrays
+        levels[L][label] = r
+first = levels[LEVELS[0]]
+for label in ("positions", "all_attributes"):
+    rec[label] = first[label]
+rec.update(level=LEVELS[0], vertices=first["vertices"], triangles=first["triangles"], mesh_bytes=first["mesh_bytes_all_attributes"], tiles=first["tiles"],
+           tiles_skipped=first["tiles_skipped"], tiles_with_surface=first["tiles_with_surface"])
+if "--level" in ARGS:
+    rec["levels"] = {str(L): levels[L] for L in LEVELS}
 hip.tsdf()
 hip.timer_stats("volume_download")
 t0 = time.perf_counter()
@@ -47,7 +72,7 @@ cnt, total = hip.timer_stats("volume_download")
 rec["volume_download_ms"] = total / cnt
 rec["volume_bytes"] = int(vol.nbytes)
 print(json.dumps(rec), flush=True)
-if len(sys.argv) > 1:
-    with open(sys.argv[1], "w") as f:
+if OUT:
+    with open(OUT[0], "w") as f:
         json.dump(rec, f, indent=1)
 hip.close()
