@@ -682,6 +682,72 @@ int32_t tsdf_mesh_stream_stats(tsdf_ctx* ctx, uint64_t out[4]);
 int32_t tsdf_mesh_stream_config_lod(tsdf_ctx* ctx, uint32_t flags, uint32_t level, uint32_t max_vertices, uint32_t max_triangles, uint32_t max_surface_tiles, uint32_t slots);
 int32_t tsdf_mesh_stream_level(tsdf_ctx* ctx, uint32_t* level);
 
+/* ---- ray queries: cast caller-given rays into the fused volume --------------------------------------------
+ * "What does this ray hit?" -- picking and measuring in a GUI, line-of-sight and range queries, views that are no pinhole.  The reference has
+ * no counterpart (its GUI picks nothing); these entries are built on what the draw restates: intersectBox (tsdf_raymarch.fs:363-374), the march
+ * (:62-114 with skipSpace off), get_gradient (:140-149), blendColors (:295-330) and vol_to_world (recon_integration.cpp:66-72).
+ * tests/ray_reference.py restates the definition in numpy; device and numpy agree byte for byte in every field.  All arithmetic is fp32, every
+ * operation rounded where it is written, sums and products left to right.
+ *
+ * The ray.  tsdf_ray, 32 bytes: origin o, t_min, direction d, t_max.  World coordinates by default; with TSDF_RAYS_UNIT_CUBE the volume's unit-cube
+ *   coordinates, used as they come: o_u = o, d_u = d.  A world ray is mapped per axis a: e = bbox_max - bbox_min, o_u = (o - bbox_min) / e (the
+ *   difference, then the division), d_u = d / e.  d need not be normalised.
+ * Invalid rays.  len2 = d_u.x * d_u.x + d_u.y * d_u.y + d_u.z * d_u.z, len = sqrt(len2).  A ray is INVALID (status 4) when a component of o_u or d_u is
+ *   not finite (so whenever one of o or d is not), when len is 0 or not finite (the zero direction, and directions whose squares underflow to zero or
+ *   overflow), or when t_min is NaN.  It is never marched: n_samples = 0, t = -1, pos = 0.  A NaN t_max reads as +inf.
+ * The march.  dn = d_u * (1.0f / len) (normalize3), sd = limit / 2, step = dn * sd.  intersectBox against the unit cube: inv = 1.0f / step,
+ *   tbot = inv * (0.0f - o_u), ttop = inv * (1.0f - o_u), tmn = fmin(ttop, tbot), tmx = fmax(ttop, tbot) per axis (IEEE minNum / maxNum: a NaN operand
+ *   -- 0 * inf of an axis-parallel ray -- is ignored), t0 = fmax(fmax(tmn.x, tmn.y), fmax(tmn.x, tmn.z)), t1 = fmin(fmin(tmx.x, tmx.y),
+ *   fmin(tmx.x, tmx.z)).  !(t0 <= t1) or t1 < 0: the ray misses the box (status 2).  t_near = t0 < 0 ? 0 : t0: the entry point, or the origin when it is
+ *   inside.  The caller's interval is in units of d; one step is sd / len of them: per = len / sd, s_min = t_min * per, s_max = t_max * per;
+ *   if s_min > t_near, t_near = s_min; if s_max < t1, t1 = s_max; !(t_near <= t1): the interval misses the box (status 2).  With t_min = 0 and
+ *   t_max = +inf neither assignment happens: the draw's arithmetic, bit for bit.  pos = o_u + step * t_near; max_n = ceil(|t1 - t_near|), at most
+ *   4.0f / limit + 2.0f (converted to uint32 by truncation.  No ray of the unit cube is longer than sqrt(3) / sd < 4 / limit steps; the bound only cuts
+ *   rays whose origin is so far off that t0 and t1 have lost the box to rounding).  prev = -limit.  Up to max_n times: dens = the trilinear TSDF at pos
+ *   (LINEAR, CLAMP_TO_EDGE); the sample is counted; dens > 0 is a hit (a NaN density compares as no hit, as in the draw) at
+ *   p = (pos - step) - step * (prev / (dens - prev)) and the march ends; otherwise prev = dens, pos = pos + step: chained additions.
+ * Skipping.  Empty space is skipped by the exact per-tile classes integrate() leaves ("every voxel of this 8^3 tile is -limit"; sparse pool: the tile has
+ *   no slot).  It never changes a bit of the above: skipped samples are accounted for by performing the same additions, and n_samples counts the
+ *   definition's samples, skipped or fetched.
+ * The answer.  tsdf_ray_hit, 32 bytes.  status: TSDF_RAY_HIT 1, TSDF_RAY_OUTSIDE 2 (the ray's interval misses the volume's box, no sample is taken),
+ *   TSDF_RAY_INVALID 4; 0 = marched, nothing hit.  On a hit pos = p in unit-cube coordinates with TSDF_RAYS_UNIT_CUBE, else the mesh section's
+ *   vol_to_world, bbox_min + p * e; t = ((p.x - o_u.x) * d_u.x + (p.y - o_u.y) * d_u.y + (p.z - o_u.z) * d_u.z) / len2, so that origin + t * dir is pos
+ *   in the caller's units (up to rounding).  Without a hit t = -1 and pos = 0.  pad is 0.
+ * The surface.  On request (TSDF_RAY_NORMALS, TSDF_RAY_COLOURS): tsdf_ray_surface, 32 bytes, per ray.  Exactly the mesh section's normal and colour
+ *   evaluated at u = p: normal = normalize(-gn / e) with gn = normalize(central differences at u +- limit / 2); rgba = blendColors of the CURRENT frame
+ *   slot at u, alpha +1 valid / -1 fallback, independent of the shade mode.  Zeros for a ray without a hit and for an attribute not asked for.
+ *
+ * tsdf_cast_rays: host arrays, synchronous.  Rays go in and results come out through device staging of the context that grows on demand (to a power of
+ *   two of rays) and is then kept.  Timers "rays_march", "rays_surface".
+ * tsdf_cast_rays_dev: device arrays.  Queued on the context's stream behind everything queued so far; never waits for the host.  The context's FIRST cast
+ *   (either form) allocates the hit list (4 MiB) and its counters; no cast after it allocates anything.  The arrays must stay valid until a later tsdf_sync.
+ * Both read the volume tsdf_download_volume would return at that moment (they wait, on the GPU, for an integrate() in flight on its lane) and for
+ *   colours the frame slot current then; they write no volume set, frame slot, pyramid or lane state, and the integrate() that later overwrites the
+ *   volume set they read waits for them.  n == 0: TSDF_OK, nothing is launched.  surface is NULL exactly when neither attribute flag is set.
+ *   TSDF_ERR_INVALID_ARGUMENT: an unknown flag; with n > 0 a NULL ray or hit array, a surface array without an attribute flag or a flag without the
+ *   array.  TSDF_ERR_STATE: before the first tsdf_integrate / tsdf_upload_volume; TSDF_RAY_COLOURS without calibration (cv_xyz_inv, cv_uv) and a frame;
+ *   on a Z-slab context (a ray crosses slabs: cast on a whole-volume context).  -1 for a NULL context.
+ * tsdf_view_rays: the draw's own rays for the pixel rectangle (x0, y0, w, h) of the current view size, row-major, bottom row first: unit-cube rays,
+ *   origin = the camera in the unit cube, direction = the UN-normalised direction of the pixel centre (x + .5, y + .5) from the device function the
+ *   draw's march calls, t_min = 0, t_max = +inf.  Cast with TSDF_RAYS_UNIT_CUBE they reproduce tsdf_raymarch with space skipping off: sample counts,
+ *   hit set and positions.  Picking a pixel is tsdf_view_rays for one pixel, then tsdf_cast_rays.  Synchronous; needs no volume.
+ *   TSDF_ERR_INVALID_ARGUMENT for a NULL argument, a singular matrix, an empty rectangle or one outside the view.
+ * tsdf_ray_stats: out = {rays, of them hits, samples accounted for, samples whose voxels were fetched} of the last cast (waits for it).
+ *   TSDF_ERR_STATE before any cast. */
+#define TSDF_RAYS_UNIT_CUBE 1u
+#define TSDF_RAY_NORMALS    2u
+#define TSDF_RAY_COLOURS    4u
+#define TSDF_RAY_HIT     1u
+#define TSDF_RAY_OUTSIDE 2u
+#define TSDF_RAY_INVALID 4u
+typedef struct tsdf_ray { float origin[3]; float t_min; float dir[3]; float t_max; } tsdf_ray;
+typedef struct tsdf_ray_hit { float pos[3]; float t; uint32_t n_samples; uint32_t status; uint32_t pad[2]; } tsdf_ray_hit;
+typedef struct tsdf_ray_surface { float normal[3]; float pad; float rgba[4]; } tsdf_ray_surface;
+int32_t tsdf_cast_rays(tsdf_ctx* ctx, const tsdf_ray* rays, uint64_t n, uint32_t flags, tsdf_ray_hit* hits, tsdf_ray_surface* surface);
+int32_t tsdf_cast_rays_dev(tsdf_ctx* ctx, const tsdf_ray* rays_dev, uint64_t n, uint32_t flags, tsdf_ray_hit* hits_dev, tsdf_ray_surface* surface_dev);
+int32_t tsdf_view_rays(tsdf_ctx* ctx, const float mv[16], const float proj[16], int32_t x0, int32_t y0, int32_t w, int32_t h, tsdf_ray* rays);
+int32_t tsdf_ray_stats(tsdf_ctx* ctx, uint64_t out[4]);
+
 /* ---- frame read-out: the swap ------------------------------------------------------------------------
  * The client ends a frame with glfwSwapBuffers (source/kinect_client.cpp:533): an RGBA8 window goes to a display (GLFW's default framebuffer has 8
  * bits per channel and the client sets no window hint that changes it, :942-951).  This device has no display; tsdf_present is the swap for a host

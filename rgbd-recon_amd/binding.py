@@ -197,6 +197,48 @@ def unpack_mesh_vertices(vertices):
     return dict(position=v[:, :8].view(np.uint16)[:, :3], normal=v[:, 8:12].view(np.int16), colour=v[:, 12:16])
 
 
+RAYS_UNIT_CUBE, RAY_NORMALS, RAY_COLOURS = 1, 2, 4   # tsdf_cast_rays: flags
+RAY_HIT, RAY_OUTSIDE, RAY_INVALID = 1, 2, 4         # tsdf_ray_hit: status bits
+
+
+class Ray(C.Structure):
+    """tsdf_ray of rgbd_recon_hip.h"""
+    _fields_ = [("origin", C.c_float * 3), ("t_min", C.c_float), ("dir", C.c_float * 3), ("t_max", C.c_float)]
+
+
+class RayHit(C.Structure):
+    """tsdf_ray_hit of rgbd_recon_hip.h"""
+    _fields_ = [("pos", C.c_float * 3), ("t", C.c_float), ("n_samples", C.c_uint32), ("status", C.c_uint32), ("pad", C.c_uint32 * 2)]
+
+
+class RaySurface(C.Structure):
+    """tsdf_ray_surface of rgbd_recon_hip.h"""
+    _fields_ = [("normal", C.c_float * 3), ("pad", C.c_float), ("rgba", C.c_float * 4)]
+
+
+# the same three records as numpy dtypes: what cast_rays / view_rays take and return
+RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("t_min", np.float32), ("dir", np.float32, 3), ("t_max", np.float32)])
+RAY_HIT_DTYPE = np.dtype([("pos", np.float32, 3), ("t", np.float32), ("n_samples", np.uint32), ("status", np.uint32), ("pad", np.uint32, 2)])
+RAY_SURFACE_DTYPE = np.dtype([("normal", np.float32, 3), ("pad", np.float32), ("rgba", np.float32, 4)])
+
+
+def as_rays(rays):
+    """RAY_DTYPE records from records or from floats [n][8] = origin, t_min, dir, t_max"""
+    rays = np.asarray(rays)
+    if rays.dtype != RAY_DTYPE:
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8).view(RAY_DTYPE).reshape(-1)
+    return np.ascontiguousarray(rays)
+
+
+def make_rays(origin, direction, t_min=0.0, t_max=np.inf):
+    """RAY_DTYPE records from origins [n][3] and directions [n][3] (t_min / t_max scalars or [n])"""
+    origin = np.asarray(origin, np.float32).reshape(-1, 3)
+    rays = np.zeros(len(origin), RAY_DTYPE)
+    rays["origin"], rays["dir"] = origin, np.asarray(direction, np.float32).reshape(-1, 3)
+    rays["t_min"], rays["t_max"] = t_min, t_max
+    return rays
+
+
 K1_FORMS = ("generic", "lds_direct", "lds_separable", "record", "cached")   # TSDF_K1_* of rgbd_recon_hip.h
 
 
@@ -233,6 +275,7 @@ class ReconIntegrationHip:
             raise TsdfError(rc, self._L.tsdf_last_error(None).decode())
         self._c = ctx
         self.view = tuple(view)
+        self._bbox = (np.array([float(x) for x in scene["bbox_min"]], np.float32), np.array([float(x) for x in scene["bbox_max"]], np.float32))
         self.n = scene["n"]
         self._dims = (scene["height"], scene["width"], scene["color_height"], scene["color_width"])
         r3, b3, s3 = (C.c_uint32 * 3)(), (C.c_uint32 * 3)(), (C.c_float * 3)()
@@ -720,6 +763,53 @@ class ReconIntegrationHip:
         out = (C.c_uint64 * 4)()
         self._ck(self._L.tsdf_mesh_stream_stats(self._c, out))
         return dict(frames=int(out[0]), overflowed=int(out[1]), payload_bytes=int(out[2]), device_bytes=int(out[3]))
+
+    # ------------------------------------------------------------------ ray queries (no counterpart in the reference)
+    def cast_rays(self, rays, normals=False, colours=False, unit_cube=False):
+        """Cast rays into the fused volume (tsdf_cast_rays).  rays: RAY_DTYPE records, or floats [n][8] = origin, t_min, dir, t_max; world coordinates
+        unless unit_cube.  -> hits (RAY_HIT_DTYPE [n]), or (hits, surface (RAY_SURFACE_DTYPE [n])) when normals or colours are asked for."""
+        rays = as_rays(rays)
+        n = len(rays)
+        flags = (RAYS_UNIT_CUBE if unit_cube else 0) | (RAY_NORMALS if normals else 0) | (RAY_COLOURS if colours else 0)
+        hits = np.zeros(n, RAY_HIT_DTYPE)
+        surface = np.zeros(n, RAY_SURFACE_DTYPE) if (normals or colours) else None
+        self._ck(self._L.tsdf_cast_rays(self._c, rays.ctypes.data_as(C.c_void_p), C.c_uint64(n), C.c_uint32(flags), hits.ctypes.data_as(C.c_void_p),
+                                        surface.ctypes.data_as(C.c_void_p) if surface is not None else None))
+        return hits if surface is None else (hits, surface)
+
+    def cast_rays_dev(self, rays_ptr, n, hits_ptr, surface_ptr=0, normals=False, colours=False, unit_cube=False):
+        """tsdf_cast_rays_dev: raw device pointers (e.g. torch tensors' data_ptr()) to n 32-byte records each; queued on the context's stream, no host wait.
+        The arrays must stay alive until a later sync()."""
+        flags = (RAYS_UNIT_CUBE if unit_cube else 0) | (RAY_NORMALS if normals else 0) | (RAY_COLOURS if colours else 0)
+        self._ck(self._L.tsdf_cast_rays_dev(self._c, C.c_void_p(int(rays_ptr)), C.c_uint64(int(n)), C.c_uint32(flags), C.c_void_p(int(hits_ptr)),
+                                            C.c_void_p(int(surface_ptr)) if surface_ptr else None))
+
+    def view_rays(self, mv, proj, rect=None):
+        """The draw's own rays (tsdf_view_rays) of the pixel rectangle rect = (x0, y0, w, h), default the whole view: RAY_DTYPE [h * w], row-major,
+        unit-cube coordinates -- cast them with unit_cube=True."""
+        x0, y0, w, h = rect if rect is not None else (0, 0, self.view[0], self.view[1])
+        rays = np.zeros(max(int(w), 0) * max(int(h), 0), RAY_DTYPE)
+        self._ck(self._L.tsdf_view_rays(self._c, _fp(_f32(mv).reshape(-1)), _fp(_f32(proj).reshape(-1)), C.c_int32(int(x0)), C.c_int32(int(y0)),
+                                        C.c_int32(int(w)), C.c_int32(int(h)), rays.ctypes.data_as(C.c_void_p)))
+        return rays
+
+    def pick(self, mv, proj, x, y, colours=True):
+        """What is under pixel (x, y) of the view (tsdf_view_rays for the pixel, then tsdf_cast_rays): dict(hit, position (world, vol_to_world of the
+        hit's unit-cube position `unit`), t, n_samples, status, normal (world), rgba (zeros with colours=False)); hit=False: n_samples and status only."""
+        ray = self.view_rays(mv, proj, (int(x), int(y), 1, 1))
+        hits, surface = self.cast_rays(ray, normals=True, colours=colours, unit_cube=True)
+        h, s = hits[0], surface[0]
+        if not (int(h["status"]) & RAY_HIT):
+            return dict(hit=False, n_samples=int(h["n_samples"]), status=int(h["status"]))
+        lo, hi = self._bbox
+        return dict(hit=True, position=(lo + h["pos"] * (hi - lo)).astype(np.float32), unit=h["pos"].copy(), t=float(h["t"]), n_samples=int(h["n_samples"]),
+                    status=int(h["status"]), normal=s["normal"].copy(), rgba=s["rgba"].copy())
+
+    def ray_stats(self):
+        """dict of the last cast: rays, hits, samples (the definition's, skipped or fetched), fetched (samples whose voxels were read)"""
+        out = (C.c_uint64 * 4)()
+        self._ck(self._L.tsdf_ray_stats(self._c, out))
+        return dict(rays=int(out[0]), hits=int(out[1]), samples=int(out[2]), fetched=int(out[3]))
 
     # ------------------------------------------------------------------ timers / multi-GPU hooks
     def enable_timers(self, on=True): self._ck(self._L.tsdf_enable_timers(self._c, int(on)))

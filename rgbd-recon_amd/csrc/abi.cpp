@@ -871,6 +871,7 @@ int32_t tsdf_destroy(tsdf_ctx* c) {
   if (c->src_ready) hipEventDestroy(c->src_ready);
   for (hipEvent_t e : c->read_fence) if (e) hipEventDestroy(e);
   hipFree(c->d_mvt_vtx); hipFree(c->d_calibvis_skipped);
+  hipFree(c->rays.d_rays); hipFree(c->rays.d_hits); hipFree(c->rays.d_surf); hipFree(c->rays.d_list); hipFree(c->rays.d_words);
   if (c->fill_worker) {
     c->fill_worker->stop.store(true);
     { std::lock_guard<std::mutex> lk(c->fill_worker->m); }
@@ -2684,6 +2685,124 @@ int32_t tsdf_mesh_stream_stats(tsdf_ctx* c, uint64_t out[4]) {
   if (!out) return TSDF_ERR_INVALID_ARGUMENT;
   const tsdf_ctx::MeshStream& R = c->mstream;
   out[0] = R.frames; out[1] = R.overflowed; out[2] = R.bytes_copied; out[3] = R.device_bytes;
+  return TSDF_OK;
+}
+
+// ---- ray queries (k_rays.hip; the definition is in the header, the host bookkeeping in ray_staging.hpp).  The reference has no counterpart.
+static int32_t ray_cast_checks(tsdf_ctx* c, const void* rays, uint64_t n, uint32_t flags, const void* hits, const void* surface) {
+  switch (ray_cast_arguments(n, flags, rays != nullptr, hits != nullptr, surface != nullptr)) {
+    case 0: break;
+    case 1: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "unknown ray flag (1 unit cube, 2 normals, 4 colours)");
+    case 2: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "null ray / hit array");
+    case 3: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "the surface array goes with TSDF_RAY_NORMALS / TSDF_RAY_COLOURS: given exactly when one is set");
+    default: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "%llu rays in one cast (at most 2^40)", (unsigned long long)n);
+  }
+  if (!whole_volume(c)) FAIL(c, TSDF_ERR_STATE, "ray queries on a Z-slab context: a ray crosses slabs, compositing per-ray partial results is not provided");
+  if (!c->have_volume) FAIL(c, TSDF_ERR_STATE, "no volume yet (tsdf_integrate or tsdf_upload_volume)");
+  if (flags & TSDF_RAY_COLOURS) return require_inputs(c, false, true);
+  return TSDF_OK;
+}
+// the launches of one cast on the context's stream, device arrays in and out; no host wait
+static int32_t ray_cast_queue(tsdf_ctx* c, const tsdf_ray* rays, uint64_t n, uint32_t flags, tsdf_ray_hit* hits, tsdf_ray_surface* surface) {
+  tsdf_ctx::Rays& R = c->rays;
+  if (!R.d_list) {                                                       // the context's first cast
+    HIP_TRY(c, hipMalloc((void**)&R.d_list, (size_t)kRayChunk * sizeof(RayHitRec)));
+    HIP_TRY(c, hipMalloc((void**)&R.d_words, 64));
+  }
+  uint32_t* count = (uint32_t*)((char*)R.d_words + 32);
+  HIP_TRY(c, join_integ(c));                                             // the volume tsdf_download_volume would return now
+  if (flags & TSDF_RAY_COLOURS) HIP_TRY(c, join_pre(c));                 // ... and the current frame slot's images
+  HIP_TRY(c, hipMemsetAsync(R.d_words, 0, 64, c->stream));
+  const float* lo = c->cfg.bbox_min; const float* hi = c->cfg.bbox_max;
+  RayCast Q{};
+  for (int a = 0; a < 3; ++a) { Q.bbox_min[a] = lo[a]; Q.ext[a] = hi[a] - lo[a]; }
+  Q.flags = flags; Q.run = ray_run_length(c->vol.limit, c->vol.res); Q.n_cap = ray_sample_cap(c->vol.limit);
+  const RayChunks K{n, kRayChunk};
+  for (uint64_t k = 0; k < K.pairs(); ++k) {
+    const uint64_t first = K.first(k);
+    Q.n = K.count(k);
+    if (k && surface) HIP_TRY(c, hipMemsetAsync(count, 0, sizeof(uint32_t), c->stream));
+    timer_begin(c, "rays_march");
+    launch_rays_march(c->stream, c->vol, Q, rays + first, hits + first, surface ? surface + first : nullptr, R.d_list, count, R.d_words);
+    timer_end(c, "rays_march");
+    if (surface) {
+      timer_begin(c, "rays_surface");
+      launch_rays_surface(c->stream, c->vol, c->luts, c->frame, Q, R.d_list, count, surface + first);
+      timer_end(c, "rays_surface");
+    }
+  }
+  HIP_TRY(c, hipGetLastError());
+  R.last_n = n; R.cast = true;
+  // With the volume sets alternating, the integrate() two frames later overwrites the set these launches read, and it waits for draw_done[set] only:
+  // record that event again behind them (as tsdf_mesh_stream does).
+  return overlay_rerecord_draw(c);
+}
+static int32_t ray_staging_reserve(tsdf_ctx* c, uint64_t n, bool surface) {
+  tsdf_ctx::Rays& R = c->rays;                                           // (nothing queued reads the staging: every call that uses it synchronises)
+  if (const uint64_t cap = R.staging.grow(n)) {
+    hipFree(R.d_rays); hipFree(R.d_hits); R.d_rays = nullptr; R.d_hits = nullptr; R.staging.grown(0);
+    HIP_TRY(c, hipMalloc((void**)&R.d_rays, (size_t)(cap * kRayBytes)));
+    HIP_TRY(c, hipMalloc((void**)&R.d_hits, (size_t)(cap * kRayBytes)));
+    R.staging.grown(cap);
+  }
+  if (const uint64_t cap = R.staging.grow_surface(n, surface)) {
+    hipFree(R.d_surf); R.d_surf = nullptr; R.staging.surface_grown(0);
+    HIP_TRY(c, hipMalloc((void**)&R.d_surf, (size_t)(cap * kRayBytes)));
+    R.staging.surface_grown(cap);
+  }
+  return TSDF_OK;
+}
+int32_t tsdf_cast_rays(tsdf_ctx* c, const tsdf_ray* rays, uint64_t n, uint32_t flags, tsdf_ray_hit* hits, tsdf_ray_surface* surface) {
+  CHECK_CTX(c);
+  int32_t rc = ray_cast_checks(c, rays, n, flags, hits, surface);
+  if (rc) return rc;
+  if (n == 0) { c->rays.last_n = 0; c->rays.cast = true; return TSDF_OK; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  if ((rc = ray_staging_reserve(c, n, surface != nullptr))) return rc;
+  tsdf_ctx::Rays& R = c->rays;
+  HIP_TRY(c, hipMemcpyAsync(R.d_rays, rays, (size_t)(n * kRayBytes), hipMemcpyHostToDevice, c->stream));
+  if ((rc = ray_cast_queue(c, R.d_rays, n, flags, R.d_hits, surface ? R.d_surf : nullptr))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(hits, R.d_hits, (size_t)(n * kRayBytes), hipMemcpyDeviceToHost, c->stream));
+  if (surface) HIP_TRY(c, hipMemcpyAsync(surface, R.d_surf, (size_t)(n * kRayBytes), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, sync_ctx(c));
+  return TSDF_OK;
+}
+int32_t tsdf_cast_rays_dev(tsdf_ctx* c, const tsdf_ray* rays_dev, uint64_t n, uint32_t flags, tsdf_ray_hit* hits_dev, tsdf_ray_surface* surface_dev) {
+  CHECK_CTX(c);
+  int32_t rc = ray_cast_checks(c, rays_dev, n, flags, hits_dev, surface_dev);
+  if (rc) return rc;
+  if (n == 0) { c->rays.last_n = 0; c->rays.cast = true; return TSDF_OK; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  return ray_cast_queue(c, rays_dev, n, flags, hits_dev, surface_dev);
+}
+int32_t tsdf_view_rays(tsdf_ctx* c, const float* mv, const float* pr, int32_t x0, int32_t y0, int32_t w, int32_t h, tsdf_ray* rays) {
+  CHECK_CTX(c);
+  if (!mv || !pr || !rays) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "null matrix / ray array");
+  if (ray_view_rect(x0, y0, w, h, c->vw, c->vh)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "pixel rectangle (%d, %d) + %d x %d outside the %d x %d view", x0, y0, w, h, c->vw, c->vh);
+  ViewParams P;
+  if (!make_view_params(c, mv, pr, &P)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "singular modelview / projection matrix");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const uint64_t n = (uint64_t)w * (uint64_t)h;
+  int32_t rc = ray_staging_reserve(c, n, false);
+  if (rc) return rc;
+  launch_view_rays(c->stream, P, x0, y0, w, h, c->rays.d_rays);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(rays, c->rays.d_rays, (size_t)(n * kRayBytes), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return TSDF_OK;
+}
+int32_t tsdf_ray_stats(tsdf_ctx* c, uint64_t out[4]) {
+  CHECK_CTX(c);
+  if (!out) return TSDF_ERR_INVALID_ARGUMENT;
+  const tsdf_ctx::Rays& R = c->rays;
+  if (!R.cast) FAIL(c, TSDF_ERR_STATE, "no cast yet (tsdf_cast_rays / tsdf_cast_rays_dev)");
+  out[0] = R.last_n; out[1] = out[2] = out[3] = 0;
+  if (!R.last_n) return TSDF_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  unsigned long long w[3] = {0, 0, 0};
+  HIP_TRY(c, hipMemcpyAsync(w, R.d_words, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  out[1] = w[0]; out[2] = w[1]; out[3] = w[2];
   return TSDF_OK;
 }
 

@@ -10,6 +10,7 @@
 #include "lane_ahead.hpp"
 #include "draw_lanes.hpp"
 #include "frame_intake.hpp"
+#include "ray_staging.hpp"
 
 using namespace rr;
 
@@ -151,6 +152,11 @@ struct tsdf_ctx {
     bool configured = false, allocated = false, held = false;
     uint64_t frames = 0, overflowed = 0, bytes_copied = 0, device_bytes = 0;
   } mstream;
+  // ray queries (tsdf_cast_rays / _dev, tsdf_view_rays): the synchronous form's device staging (ray_staging.hpp: grown on demand, then kept), the hit
+  // list k_rays_march compacts for k_rays_surface (kRayChunk records, allocated with the counters by the context's first cast; no cast after it
+  // allocates), `words` = {hits, samples accounted for, samples fetched} as three 64-bit counters of the cast, then the list's 32-bit count at byte 32
+  struct Rays { tsdf_ray* d_rays = nullptr; tsdf_ray_hit* d_hits = nullptr; tsdf_ray_surface* d_surf = nullptr; RayStaging staging{};
+                RayHitRec* d_list = nullptr; unsigned long long* d_words = nullptr; uint64_t last_n = 0; bool cast = false; } rays;
   bool have_volume = false;          // integrate() or tsdf_upload_volume has written the volume since it was set up (what the mesh extraction may read)
   // flags (recon_integration.cpp:54-57)
   bool fill_holes = true, use_bricks = true, skip_space = true;

@@ -11,6 +11,7 @@
 
 #include "raster_dev.hpp"
 #include "blend_dev.hpp"
+#include "ray_dev.hpp"
 
 namespace rr {
 
@@ -20,12 +21,7 @@ __device__ __forceinline__ float3 pixel_dir_world(const ViewParams& P, float fx,
   const float4 wd = mat_mul(P.mv_inv, p.x / p.w, p.y / p.w, p.z / p.w, 0.0f);
   return make_float3(wd.x, wd.y, wd.z);
 }
-__device__ __forceinline__ float3 pixel_dir_vol(const ViewParams& P, float fx, float fy) {
-  const float4 p = mat_mul(P.img_to_eye, fx, fy, 1.0f, 1.0f);
-  const float4 wd = mat_mul(P.mv_inv, p.x / p.w, p.y / p.w, p.z / p.w, 0.0f);
-  const float4 vd = mat_mul(P.v2w_inv, wd.x, wd.y, wd.z, wd.w);
-  return make_float3(vd.x, vd.y, vd.z);
-}
+// pixel_dir_vol: ray_dev.hpp (tsdf_view_rays hands the same rays to the caller)
 // screenToVol(), tsdf_raymarch.fs:376-383
 __device__ __forceinline__ float3 screen_to_vol(const ViewParams& P, float fx, float fy, float fz) {
   const float4 p = mat_mul(P.img_to_eye, fx, fy, fz, 1.0f);

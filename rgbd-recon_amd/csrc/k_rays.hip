@@ -1,0 +1,228 @@
+// Ray queries (tsdf_cast_rays / tsdf_cast_rays_dev / tsdf_view_rays; include/rgbd_recon_hip.h has the definition): caller-given rays marched
+// through the fused volume by the draw's rule (tsdf_raymarch.fs:62-114 with skipSpace off), the hit's normal and colour on request.  The reference has no
+// counterpart (its GUI picks nothing); the entries are built on what the draw restates: intersectBox (:363-374), the march (:89-110), get_gradient
+// (:140-149), blendColors (:295-330) and vol_to_world (recon_integration.cpp:66-72).
+//
+// k_march / k_march_box (k_raymarch.hip) take their ray from the pixel grid and skip space either by a screen-space rasterisation of the bricks or by a
+// leap the 64 neighbouring rays of a wave take together.  Neither means anything for rays that are no neighbours, so here everything is per lane:
+//   k_rays_march    one lane per ray.  The ray comes in as two 16-byte loads and the answer leaves as two 16-byte stores.  Samples are fetched kRayBatch at a
+//                   time (positions never depend on densities) and examined in order.  Empty space: for the next `run` samples the lane performs the
+//                   reference's chain of additions FIRST, takes the tap indices of the run's first and last position with the filter's own arithmetic
+//                   (axis_linear: the taps of the samples between lie between them, because a chain of additions of one step is monotonic per axis), and
+//                   looks up the classes (sparse pool: slots) of the at most 2 x 2 x 2 tiles those taps touch.  All "every voxel is -limit": the samples
+//                   are -limit (lerp(a, a, t) = a in fp32), so the run is accounted for and prev = -limit.  Anything else -- a mixed tile, a run that
+//                   spans more than two tiles on an axis, a position beyond 1e6 or not finite -- and the lane fetches from the run's first position.  No estimate takes
+//                   part: the positions tested are the positions sampled.
+//   k_rays_surface  one lane per HIT, over the list k_rays_march compacted (one atomic per wave, as k_march -> k_shade): the 128-register blend_colors
+//                   runs in dense waves and for hits only.  Results are indexed by ray number, so the list's order shows nowhere.
+//   k_view_rays     the draw's own rays of a pixel rectangle, through pixel_dir_vol (ray_dev.hpp: the function k_march calls).
+#include <cfloat>
+
+#include "blend_dev.hpp"
+#include "ray_dev.hpp"
+
+namespace rr {
+
+#ifndef RR_RAY_BATCH
+#define RR_RAY_BATCH 4
+#endif
+constexpr int kRayBatch = RR_RAY_BATCH;      // samples in flight per lane
+constexpr int kRayThreads = 256;
+
+__device__ __forceinline__ bool ray_finite(float v) { return fabsf(v) <= FLT_MAX; }
+
+// A position whose trilinear weights are proper numbers: beyond this the product with the resolution could overflow and a weight be NaN (as k_march_box's
+// leap: such a position takes the fetching path, which restates the filter whatever it gives)
+__device__ __forceinline__ bool ray_tame(float3 p) { return fabsf(p.x) < 1.0e6f && fabsf(p.y) < 1.0e6f && fabsf(p.z) < 1.0e6f; }
+// every voxel a tap of the positions a .. b (the run's first and last sample; the chain between them is monotonic per axis) can read is -limit
+template <bool kSparse>
+__device__ __forceinline__ bool ray_run_clear(const Volume& V, float3 a, float3 b) {
+  if (!(ray_tame(a) && ray_tame(b))) return false;
+  const Axis ax = axis_linear(a.x, V.res[0]), ay = axis_linear(a.y, V.res[1]), az = axis_linear(a.z, V.res[2]);
+  const Axis bx = axis_linear(b.x, V.res[0]), by = axis_linear(b.y, V.res[1]), bz = axis_linear(b.z, V.res[2]);
+  const int lx = min(ax.i0, bx.i0) >> 3, ly = min(ay.i0, by.i0) >> 3, lz = min(az.i0, bz.i0) >> 3;
+  const int hx = max(ax.i1, bx.i1) >> 3, hy = max(ay.i1, by.i1) >> 3, hz = max(az.i1, bz.i1) >> 3;
+  if (hx - lx > 1 || hy - ly > 1 || hz - lz > 1) return false;       // more than two tiles on an axis: not looked up
+  bool clear = true;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int tx = (k & 1) ? hx : lx, ty = (k & 2) ? hy : ly, tz = (k & 4) ? hz : lz;   // (tap indices are clamped into the grid: so are these)
+    const uint32_t id = (uint32_t)__mul24(__mul24(tz - V.tz0, V.nty) + ty, V.ntx) + (uint32_t)tx;
+    clear &= kSparse ? (V.slot[id] == kNoSlot) : (V.cls[id] == kTileMinus);
+  }
+  return clear;
+}
+
+template <bool kSparse>
+__global__ __launch_bounds__(kRayThreads) void k_rays_march(Volume V, RayCast Q, const float4* __restrict__ rays, float4* __restrict__ hits, float4* __restrict__ surf,
+                                                            RayHitRec* __restrict__ list, uint32_t* __restrict__ list_count, unsigned long long* __restrict__ stats) {
+  const uint32_t i = blockIdx.x * kRayThreads + threadIdx.x;
+  const int ln = threadIdx.x & 63;
+  const bool in = i < Q.n;
+  float4 r0 = make_float4(0, 0, 0, 0), r1 = make_float4(0, 0, 0, 0);
+  if (in) { r0 = rays[2 * i]; r1 = rays[2 * i + 1]; }
+  const float limit = V.limit, sd = limit * 0.5f;                       // sampleDistance, tsdf_raymarch.fs:34
+  float3 o = make_float3(r0.x, r0.y, r0.z), d = make_float3(r1.x, r1.y, r1.z);
+  const float t_min = r0.w, t_max = r1.w;
+  if (!(Q.flags & TSDF_RAYS_UNIT_CUBE)) {
+    o = make_float3((o.x - Q.bbox_min[0]) / Q.ext[0], (o.y - Q.bbox_min[1]) / Q.ext[1], (o.z - Q.bbox_min[2]) / Q.ext[2]);
+    d = make_float3(d.x / Q.ext[0], d.y / Q.ext[1], d.z / Q.ext[2]);
+  }
+  const float len2 = d.x * d.x + d.y * d.y + d.z * d.z;                 // (normalize3's sum)
+  const float len = sqrtf(len2);
+  const bool valid = in && ray_finite(o.x) && ray_finite(o.y) && ray_finite(o.z) && ray_finite(d.x) && ray_finite(d.y) && ray_finite(d.z) &&
+                     len > 0.0f && ray_finite(len) && !(t_min != t_min);
+  const float3 dn = normalize3(d);
+  const float3 step = make_float3(dn.x * sd, dn.y * sd, dn.z * sd);     // :64
+  uint32_t max_n = 0, status = valid ? 0u : TSDF_RAY_INVALID;
+  float3 pos = make_float3(0, 0, 0);
+  if (valid) {                                                          // intersectBox(), :363-374, as k_march has it
+    const float3 inv = make_float3(1.0f / step.x, 1.0f / step.y, 1.0f / step.z);
+    const float3 tbot = make_float3(inv.x * (0.0f - o.x), inv.y * (0.0f - o.y), inv.z * (0.0f - o.z));
+    const float3 ttop = make_float3(inv.x * (1.0f - o.x), inv.y * (1.0f - o.y), inv.z * (1.0f - o.z));
+    const float3 tmn = make_float3(fminf(ttop.x, tbot.x), fminf(ttop.y, tbot.y), fminf(ttop.z, tbot.z));
+    const float3 tmx = make_float3(fmaxf(ttop.x, tbot.x), fmaxf(ttop.y, tbot.y), fmaxf(ttop.z, tbot.z));
+    const float t0 = fmaxf(fmaxf(tmn.x, tmn.y), fmaxf(tmn.x, tmn.z));
+    float t1 = fminf(fminf(tmx.x, tmx.y), fminf(tmx.x, tmx.z));
+    if (!(t0 <= t1) || t1 < 0.0f) status = TSDF_RAY_OUTSIDE;
+    else {
+      float t_near = t0 < 0.0f ? 0.0f : t0;                             // :75-86
+      // the caller's interval, from units of `dir` to steps: one step is sd / len of them
+      const float per = len / sd, s_min = t_min * per, s_max = t_max * per;
+      if (s_min > t_near) t_near = s_min;
+      if (s_max < t1) t1 = s_max;
+      if (!(t_near <= t1)) status = TSDF_RAY_OUTSIDE;
+      else {
+        pos = make_float3(o.x + step.x * t_near, o.y + step.y * t_near, o.z + step.z * t_near);
+        max_n = (uint32_t)fminf(ceilf(fabsf(t1 - t_near)), Q.n_cap);
+      }
+    }
+  }
+  // The march, :89-110: positions by chained additions, dens > 0 the hit test, prev starts at -limit
+  float prev = -limit;
+  uint32_t n = 0, fetched = 0;
+  bool hit = false, try_skip = true;
+  float3 hit_pos = pos;
+  float hit_d = 0.0f;
+  const float ml = -limit;
+  while (n < max_n && !hit) {
+    if (try_skip) {
+      const uint32_t m = min((uint32_t)Q.run, max_n - n);
+      float3 e = pos;
+      for (uint32_t k = 1; k < m; ++k) e = make_float3(e.x + step.x, e.y + step.y, e.z + step.z);
+      if (ray_run_clear<kSparse>(V, pos, e)) {
+        pos = make_float3(e.x + step.x, e.y + step.y, e.z + step.z);
+        n += m; prev = ml;
+        continue;
+      }
+      try_skip = false;
+    }
+    float3 p[kRayBatch];
+    float dv[kRayBatch];
+    p[0] = pos;
+#pragma unroll
+    for (int k = 1; k < kRayBatch; ++k) p[k] = make_float3(p[k - 1].x + step.x, p[k - 1].y + step.y, p[k - 1].z + step.z);
+#pragma unroll
+    for (int k = 0; k < kRayBatch; ++k) dv[k] = tex3d_tsdf<kSparse, true>(V, p[k].x, p[k].y, p[k].z);   // unconditional: taps are clamped into the allocation
+    bool all_clear = true;
+#pragma unroll
+    for (int k = 0; k < kRayBatch; ++k) {
+      if (!hit && n < max_n) {
+        n += 1; fetched += 1;
+        all_clear &= dv[k] == ml;
+        if (dv[k] > 0.0f) { hit = true; hit_pos = p[k]; hit_d = dv[k]; }   // (a NaN density compares as no hit, as in the draw)
+        else prev = dv[k];
+      }
+    }
+    if (!hit) pos = make_float3(p[kRayBatch - 1].x + step.x, p[kRayBatch - 1].y + step.y, p[kRayBatch - 1].z + step.z);
+    try_skip = all_clear;                                               // back in empty space: look at the classes again
+  }
+  float3 pu = make_float3(0, 0, 0), pw = make_float3(0, 0, 0);
+  float t = -1.0f;
+  if (hit) {                                                            // approximate ray-cell intersection, :99-101
+    const float kk = prev / (hit_d - prev);
+    pu = make_float3((hit_pos.x - step.x) - step.x * kk, (hit_pos.y - step.y) - step.y * kk, (hit_pos.z - step.z) - step.z * kk);
+    t = ((pu.x - o.x) * d.x + (pu.y - o.y) * d.y + (pu.z - o.z) * d.z) / len2;
+    pw = pu;
+    if (!(Q.flags & TSDF_RAYS_UNIT_CUBE))                               // vol_to_world, in the mesh section's order
+      pw = make_float3(Q.bbox_min[0] + pu.x * Q.ext[0], Q.bbox_min[1] + pu.y * Q.ext[1], Q.bbox_min[2] + pu.z * Q.ext[2]);
+    status |= TSDF_RAY_HIT;
+  }
+  if (in) {
+    hits[2 * i] = make_float4(pw.x, pw.y, pw.z, t);
+    hits[2 * i + 1] = make_float4(__uint_as_float(n), __uint_as_float(status), 0.0f, 0.0f);
+    if (surf && !hit) { surf[2 * i] = make_float4(0, 0, 0, 0); surf[2 * i + 1] = make_float4(0, 0, 0, 0); }
+  }
+  // compact the hits of this wave into the list (one atomic per wave): what k_rays_surface runs over
+  const unsigned long long hm = __ballot(hit);
+  if (surf && hm) {
+    const int leader = __ffsll((long long)hm) - 1;
+    uint32_t base = 0;
+    if (ln == leader) base = atomicAdd(list_count, (uint32_t)__popcll(hm));
+    base = __shfl(base, leader);
+    if (hit) {
+      RayHitRec h;
+      h.x = pu.x; h.y = pu.y; h.z = pu.z; h.ray = i;
+      list[base + (uint32_t)__popcll(hm & ((1ull << ln) - 1ull))] = h;   // (base + rank < hits of the launch <= Q.n <= the list's capacity)
+    }
+  }
+  // tsdf_ray_stats: hits, samples accounted for, samples fetched
+  uint32_t sa = n, sf = fetched;
+  for (int s = 32; s; s >>= 1) { sa += (uint32_t)__shfl_xor((int)sa, s); sf += (uint32_t)__shfl_xor((int)sf, s); }   // (a wave's sums: 64 x max_n, far below 2^32 at n_cap)
+  if (ln == 0) {
+    if (hm) atomicAdd(&stats[0], (unsigned long long)__popcll(hm));
+    if (sa) { atomicAdd(&stats[1], (unsigned long long)sa); atomicAdd(&stats[2], (unsigned long long)sf); }
+  }
+}
+
+// the surface at the hits: exactly the mesh section's normal and colour (k_mesh_vertices' text) at the hit's unit-cube position
+template <bool kSparse>
+__global__ __launch_bounds__(kRayThreads) void k_rays_surface(Volume V, StreamTable T, FrameImages F, RayCast Q, const RayHitRec* __restrict__ list,
+                                                              const uint32_t* __restrict__ list_count, float4* __restrict__ surf) {
+  const uint32_t j = blockIdx.x * kRayThreads + threadIdx.x;
+  if (j >= *list_count) return;
+  const RayHitRec h = list[j];
+  const float3 u = make_float3(h.x, h.y, h.z);
+  const float limit = V.limit, sd = limit * 0.5f;
+  float4 nrm = make_float4(0, 0, 0, 0), col = make_float4(0, 0, 0, 0);
+  if (Q.flags & TSDF_RAY_NORMALS) {
+    const float gx = tex3d_tsdf<kSparse>(V, u.x + sd, u.y, u.z) - tex3d_tsdf<kSparse>(V, u.x - sd, u.y, u.z);
+    const float gy = tex3d_tsdf<kSparse>(V, u.x, u.y + sd, u.z) - tex3d_tsdf<kSparse>(V, u.x, u.y - sd, u.z);
+    const float gz = tex3d_tsdf<kSparse>(V, u.x, u.y, u.z + sd) - tex3d_tsdf<kSparse>(V, u.x, u.y, u.z - sd);
+    const float3 gn = normalize3(make_float3(gx, gy, gz));            // get_gradient(), tsdf_raymarch.fs:140-149
+    const float3 nn = normalize3(make_float3(-gn.x / Q.ext[0], -gn.y / Q.ext[1], -gn.z / Q.ext[2]));
+    nrm = make_float4(nn.x, nn.y, nn.z, 0.0f);
+  }
+  if (Q.flags & TSDF_RAY_COLOURS) col = blend_colors(T, F, limit, u);
+  surf[2 * h.ray] = nrm;
+  surf[2 * h.ray + 1] = col;
+}
+
+// the draw's rays of the pixel rectangle (x0, y0, w, h), row-major: origin cam_vol, direction the un-normalised pixel_dir_vol of the pixel centre
+__global__ __launch_bounds__(kRayThreads) void k_view_rays(ViewParams P, int x0, int y0, int w, int n, float4* __restrict__ rays) {
+  const int i = blockIdx.x * kRayThreads + threadIdx.x;
+  if (i >= n) return;
+  const int px = x0 + i % w, py = y0 + i / w;
+  const float3 d = pixel_dir_vol(P, (float)px + 0.5f, (float)py + 0.5f);
+  rays[2 * i] = make_float4(P.cam_vol[0], P.cam_vol[1], P.cam_vol[2], 0.0f);
+  rays[2 * i + 1] = make_float4(d.x, d.y, d.z, __int_as_float(0x7f800000));
+}
+
+void launch_rays_march(hipStream_t st, const Volume& V, const RayCast& Q, const tsdf_ray* rays, tsdf_ray_hit* hits, tsdf_ray_surface* surf, RayHitRec* list,
+                       uint32_t* list_count, unsigned long long* stats) {
+  const dim3 g((Q.n + kRayThreads - 1) / kRayThreads), b(kRayThreads);
+  if (V.slot) hipLaunchKernelGGL(k_rays_march<true>, g, b, 0, st, V, Q, (const float4*)rays, (float4*)hits, (float4*)surf, list, list_count, stats);
+  else hipLaunchKernelGGL(k_rays_march<false>, g, b, 0, st, V, Q, (const float4*)rays, (float4*)hits, (float4*)surf, list, list_count, stats);
+}
+void launch_rays_surface(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const RayCast& Q, const RayHitRec* list,
+                         const uint32_t* list_count, tsdf_ray_surface* surf) {
+  const dim3 g((Q.n + kRayThreads - 1) / kRayThreads), b(kRayThreads);   // (the hit count stays on the device: lanes past it return at once)
+  if (V.slot) hipLaunchKernelGGL(k_rays_surface<true>, g, b, 0, st, V, T, F, Q, list, list_count, (float4*)surf);
+  else hipLaunchKernelGGL(k_rays_surface<false>, g, b, 0, st, V, T, F, Q, list, list_count, (float4*)surf);
+}
+void launch_view_rays(hipStream_t st, const ViewParams& P, int x0, int y0, int w, int h, tsdf_ray* rays) {
+  const int n = w * h;
+  hipLaunchKernelGGL(k_view_rays, dim3((n + kRayThreads - 1) / kRayThreads), dim3(kRayThreads), 0, st, P, x0, y0, w, n, (float4*)rays);
+}
+
+}  // namespace rr

@@ -1,0 +1,76 @@
+// Host bookkeeping of the ray queries (tsdf_cast_rays / tsdf_cast_rays_dev / tsdf_view_rays), free of HIP: which arguments a cast accepts, how the
+// staging of the synchronous form grows, how a cast is cut into launches, and the two numbers the march kernel is launched with.  abi.cpp holds the
+// buffers and issues the calls; a stand-alone program (tests/test_ray_staging.py) runs this text under the host sanitizers.
+#pragma once
+#include <stdint.h>
+
+namespace rr {
+
+constexpr uint32_t kRayFlagUnitCube = 1u, kRayFlagNormals = 2u, kRayFlagColours = 4u;   // TSDF_RAYS_UNIT_CUBE, TSDF_RAY_NORMALS, TSDF_RAY_COLOURS
+constexpr uint32_t kRayFlagsAll = kRayFlagUnitCube | kRayFlagNormals | kRayFlagColours;
+constexpr uint64_t kRayBytes = 32;               // sizeof(tsdf_ray) == sizeof(tsdf_ray_hit) == sizeof(tsdf_ray_surface)
+constexpr uint64_t kRayMaxCount = 1ull << 40;    // rays of one cast: keeps every byte count below 2^46
+
+// 0: the arguments of a cast are acceptable; 1: unknown flag; 2: a NULL ray / hit array with n > 0; 3: `surface` given without an attribute flag, or
+// missing with one; 4: more rays than a cast takes
+inline int ray_cast_arguments(uint64_t n, uint32_t flags, bool have_rays, bool have_hits, bool have_surface) {
+  if (flags & ~kRayFlagsAll) return 1;
+  const bool wants = (flags & (kRayFlagNormals | kRayFlagColours)) != 0;
+  if (n == 0) return 0;
+  if (!have_rays || !have_hits) return 2;
+  if (wants != have_surface) return 3;
+  if (n > kRayMaxCount) return 4;
+  return 0;
+}
+// 0, or what is wrong with the pixel rectangle of tsdf_view_rays in a view of vw x vh: 1 empty or negative, 2 outside the view
+inline int ray_view_rect(int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t vw, int32_t vh) {
+  if (w <= 0 || h <= 0 || x0 < 0 || y0 < 0) return 1;
+  if ((int64_t)x0 + w > vw || (int64_t)y0 + h > vh) return 2;
+  return 0;
+}
+
+// Staging of the synchronous form: one capacity (in rays) for the ray, hit and surface buffers; grown to the next power of two at or above the need (at
+// least 1024 rays), never shrunk.
+struct RayStaging {
+  uint64_t capacity = 0;           // rays the ray / hit buffers hold
+  uint64_t surface_capacity = 0;   // rays the surface buffer holds (allocated by the first cast that asks for an attribute)
+  static uint64_t round_up(uint64_t n) {
+    uint64_t c = 1024;
+    while (c < n) c <<= 1;         // (n <= kRayMaxCount: no overflow)
+    return c;
+  }
+  // the capacity to allocate before a cast of n rays, or 0 when the buffers do
+  uint64_t grow(uint64_t n) const { return n > capacity ? round_up(n) : 0; }
+  uint64_t grow_surface(uint64_t n, bool wanted) const { return wanted && n > surface_capacity ? round_up(n) : 0; }
+  void grown(uint64_t c) { capacity = c; }
+  void surface_grown(uint64_t c) { surface_capacity = c; }
+  void released() { capacity = 0; surface_capacity = 0; }
+};
+
+// A cast runs as launch pairs of at most `chunk` rays (the hit list's capacity): pair k covers rays [first, first + count)
+struct RayChunks {
+  uint64_t n; uint32_t chunk;
+  uint64_t pairs() const { return (n + chunk - 1) / chunk; }
+  uint64_t first(uint64_t k) const { return k * chunk; }
+  uint32_t count(uint64_t k) const { const uint64_t left = n - first(k); return left < chunk ? (uint32_t)left : chunk; }
+};
+
+// Samples per look at the tile classes: the most for which a run's taps span at most two 8-voxel tiles on every axis, whatever the direction.  A step
+// moves a ray by at most limit / 2 * res voxels on an axis; (run - 1) steps, one voxel of filter footprint and the fraction must stay within 8.  (The
+// kernel tests the span of every run itself and fetches when it is larger: this only sizes the attempt.)
+inline int ray_run_length(float limit, const int res[3]) {
+  int r = res[0] > res[1] ? res[0] : res[1];
+  if (res[2] > r) r = res[2];
+  const float per_step = limit * 0.5f * (float)r;
+  if (!(per_step > 0.0f)) return 1;
+  const float k = 6.0f / per_step;
+  return k >= 31.0f ? 32 : (k < 1.0f ? 1 : (int)k + 1);
+}
+// The bound on a ray's sample count.  Inside the unit cube a ray is at most sqrt(3) long and a step limit / 2: every ray of the definition stays below
+// 2 / (limit / 2) + 2 samples.  Only a ray whose origin is so far off that t0 and t1 have lost the box to rounding is cut by it.
+inline float ray_sample_cap(float limit) {
+  const float c = 4.0f / limit + 2.0f;
+  return c > 0.0f && c < 4.0e9f ? c : 4.0e9f;
+}
+
+}  // namespace rr

@@ -386,6 +386,22 @@ void launch_mesh_stream_header(hipStream_t st, const MeshScratch& S, MeshStreamH
 // flags: TSDF_MESH_NORMALS | TSDF_MESH_COLOURS; payload: packed vertices (8 bytes each, 16 with a flag), then the triangles
 void launch_mesh_stream_emit(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S, uint32_t flags,
                              const MeshStreamHeader* H, uint32_t* records, void* payload);
+// ray queries (k_rays.hip): one launch pair serves at most kRayChunk rays -- the capacity of the context's hit list
+constexpr uint32_t kRayChunk = 1u << 18;
+struct RayCast {
+  float bbox_min[3], ext[3];        // vol_to_world: world = bbox_min + u * ext, ext = bbox_max - bbox_min in fp32
+  uint32_t flags;                   // TSDF_RAYS_UNIT_CUBE | TSDF_RAY_NORMALS | TSDF_RAY_COLOURS
+  uint32_t n;                       // rays of this launch (<= kRayChunk)
+  int run;                          // samples per look at the tile classes (ray_run_length)
+  float n_cap;                      // the bound on a ray's sample count (ray_sample_cap)
+};
+struct RayHitRec { float x, y, z; uint32_t ray; };   // a hit's unit-cube position and its ray's number in the launch
+// stats: three device words {hits, samples accounted for, samples fetched}, added to; list_count: zero at the launch
+void launch_rays_march(hipStream_t st, const Volume& V, const RayCast& Q, const tsdf_ray* rays, tsdf_ray_hit* hits, tsdf_ray_surface* surf, RayHitRec* list,
+                       uint32_t* list_count, unsigned long long* stats);
+void launch_rays_surface(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const RayCast& Q, const RayHitRec* list,
+                         const uint32_t* list_count, tsdf_ray_surface* surf);
+void launch_view_rays(hipStream_t st, const ViewParams& P, int x0, int y0, int w, int h, tsdf_ray* rays);
 void launch_clear_image(hipStream_t st, float4* color, float* depth, size_t n, float4 c, float d);
 void launch_export_partial(hipStream_t st, const RayTarget& R, int w, int h, void* dst);
 void launch_composite(hipStream_t st, const void* gathered, int n, const RayTarget& R, int w, int h);

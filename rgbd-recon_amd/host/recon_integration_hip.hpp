@@ -235,6 +235,41 @@ class ReconIntegrationHip {
     check(tsdf_mesh_stream_stats(m_ctx, s));
     return MeshStreamStats{s[0], s[1], s[2], s[3]};
   }
+  // ---- ray queries (tsdf_cast_rays): what does this ray hit?  The reference has no counterpart: its GUI picks nothing.
+  // castRays marches caller-given rays (world coordinates, or the volume's unit cube) through the volume as it is now, by the draw's rule; viewRays writes
+  // the draw's own rays of a pixel rectangle for the matrices last set; pick is the two for one pixel: the world position, normal and colour under it.
+  struct RayResults { std::vector<tsdf_ray_hit> hits; std::vector<tsdf_ray_surface> surface; };   // surface: empty unless normals / colours were asked for
+  struct RayStats { std::uint64_t rays = 0, hits = 0, samples = 0, fetched = 0; };
+  struct Pick { bool hit = false; float position[3] = {0, 0, 0}, normal[3] = {0, 0, 0}, rgba[4] = {0, 0, 0, 0}; float t = -1.0f; std::uint32_t samples = 0; };
+  void castRays(const std::vector<tsdf_ray>& rays, RayResults& out, bool normals = false, bool colours = false, bool unit_cube = false) {
+    const std::uint32_t flags = (unit_cube ? TSDF_RAYS_UNIT_CUBE : 0u) | (normals ? TSDF_RAY_NORMALS : 0u) | (colours ? TSDF_RAY_COLOURS : 0u);
+    out.hits.assign(rays.size(), tsdf_ray_hit{});
+    out.surface.assign((normals || colours) ? rays.size() : 0, tsdf_ray_surface{});
+    check(tsdf_cast_rays(m_ctx, rays.data(), rays.size(), flags, out.hits.data(), out.surface.empty() ? nullptr : out.surface.data()));
+  }
+  std::vector<tsdf_ray> viewRays(int x0, int y0, int w, int h) {
+    std::vector<tsdf_ray> rays((w > 0 && h > 0) ? (std::size_t)w * (std::size_t)h : 0);
+    check(tsdf_view_rays(m_ctx, m_mv, m_proj, x0, y0, w, h, rays.data()));
+    return rays;
+  }
+  Pick pick(int x, int y, bool colours = true) {
+    const std::vector<tsdf_ray> ray = viewRays(x, y, 1, 1);
+    tsdf_ray_hit h{};
+    tsdf_ray_surface s{};
+    check(tsdf_cast_rays(m_ctx, ray.data(), 1, TSDF_RAYS_UNIT_CUBE | TSDF_RAY_NORMALS | (colours ? TSDF_RAY_COLOURS : 0u), &h, &s));
+    Pick p;
+    p.hit = (h.status & TSDF_RAY_HIT) != 0; p.t = h.t; p.samples = h.n_samples;
+    if (p.hit) {
+      for (int a = 0; a < 3; ++a) { p.position[a] = m_in.bbox_min[a] + h.pos[a] * (m_in.bbox_max[a] - m_in.bbox_min[a]); p.normal[a] = s.normal[a]; }   // vol_to_world, recon_integration.cpp:66-72
+      for (int a = 0; a < 4; ++a) p.rgba[a] = s.rgba[a];
+    }
+    return p;
+  }
+  RayStats rayStats() {
+    std::uint64_t s[4];
+    check(tsdf_ray_stats(m_ctx, s));
+    return RayStats{s[0], s[1], s[2], s[3]};
+  }
   // ---- kinect::ReconPoints::draw() (recon_points.cpp:71-111) on the same inputs: the point back-end for A/B comparison
   void uploadNormals(const float* normals_rgb) { check(tsdf_upload_normals(m_ctx, normals_rgb)); }
   void drawPoints() { check(tsdf_draw_points(m_ctx, m_mv, m_proj)); }
