@@ -748,6 +748,60 @@ int32_t tsdf_cast_rays_dev(tsdf_ctx* ctx, const tsdf_ray* rays_dev, uint64_t n, 
 int32_t tsdf_view_rays(tsdf_ctx* ctx, const float mv[16], const float proj[16], int32_t x0, int32_t y0, int32_t w, int32_t h, tsdf_ray* rays);
 int32_t tsdf_ray_stats(tsdf_ctx* ctx, uint64_t out[4]);
 
+/* ---- texture taps: per-stream colour coordinates and blend weights at caller-given points -----------------
+ * A mesh carries one blendColors colour per vertex: voxel resolution, where the colour cameras deliver far more.  A receiver that already has the
+ * colour images (the wire's DXT frames, a recording) needs, per vertex and stream, only WHERE that stream's colour image is read and the two numbers
+ * blendColors weights the read with; with those it reproduces blendColors per fragment by plain projective texturing.  These are the values
+ * blendColors (tsdf_raymarch.fs:295-330) forms per stream before it accumulates; vol_to_world is recon_integration.cpp:66-72.  The reference has
+ * no counterpart: its client runs blendColors per pixel against the full colour images and the LUT volumes.  tests/texture_tap_reference.py restates the
+ * definition in numpy on the oracle's filters; device and numpy agree byte for byte.  All arithmetic is fp32, every operation rounded where it is written.
+ *
+ * The point.  float xyz[3], 12 bytes.  World coordinates by default: u = (p - bbox_min) / e per axis (the difference, then the division), e = bbox_max -
+ *   bbox_min: the ray section's mapping.  With TSDF_TAPS_UNIT_CUBE the volume's unit-cube coordinates, used as they come: u = p.
+ * Not evaluated.  A point whose u has a component that is not finite, or with |component| >= 1.0e6f, is not evaluated: every one of its taps is
+ *   {0, 0, 0, -1} and its sensor records are zero.  An evaluated dist is an absolute value and never negative, so dist == -1 marks the case.  Every other
+ *   point is evaluated, also far outside the cube: the filters clamp to the edge.
+ * Per stream i, in stream order, exactly the values blend_colors() forms: pc = texture(cv_xyz_inv[i], u).xyz; pcol = texture(cv_uv[i], pc).xy (both
+ *   LINEAR, CLAMP_TO_EDGE); depth = the NEAREST depth of the current frame slot at pc.xy; dist = |depth - pc.z|; quality = dist < limit ? the LINEAR
+ *   quality at pc.xy : 0.  A NaN stays a NaN (a NaN dist compares false: quality 0).
+ * tsdf_texture_tap, 16 bytes: {u, v, quality, dist} with (u, v) = pcol, unclamped: the coordinates the colour fetch receives, LINEAR, CLAMP_TO_EDGE.
+ * The receiver's rule.  With col_i the colour image of stream i read at (u, v) (RGB8 / 255, LINEAR, CLAMP_TO_EDGE):
+ *   tw = sum_i quality_i / (dist_i + 0.01f); if tw > 0 the colour is (sum_i col_i * quality_i / (dist_i + 0.01f)) / tw -- per channel, the product,
+ *   then the division --, otherwise it is (sum_i col_i / dist_i) / (sum_i 1.0f / dist_i).  The sums run left to right, in stream order, from 0.  This is
+ *   blendColors: fed the taps of a unit-cube point it gives the bits of tsdf_ray_surface.rgba / the mesh colour at that point (alpha +1 / -1 = which branch).
+ * tsdf_sensor_tap, 16 bytes, with TSDF_TAPS_SENSOR: {x, y, z, depth} = pc and the nearest depth: which sensor pixel looks at the point (x, y), the depth
+ *   the point has there (z), the depth the sensor measured (depth).
+ * Layout.  [n][N], point-major, N = num_streams: all taps of a point are contiguous, 16 * N bytes.
+ *
+ * tsdf_texture_taps: host arrays, synchronous, through device staging of the context that grows on demand (to a power of two of points) and is then kept.
+ * tsdf_texture_taps_dev: device arrays.  Queued on the context's stream behind everything queued so far; never waits for the host and allocates nothing.
+ *   The arrays must stay valid until a later tsdf_sync.
+ * Both read calibration and the frame slot current at the call (they wait, on the GPU, for the frame's preparation as a coloured ray cast does) and write
+ *   no volume set, frame slot, pyramid or lane state; the upload that later overwrites that slot waits for them.  They need no volume: they work
+ *   before the first tsdf_integrate and on a Z-slab context (which holds whole LUTs and frames).  Calls of more than 2^18 points run as several
+ *   launches.  Timer "texture_taps".
+ * tsdf_mesh_texture_taps: the device form over the position array of the last tsdf_mesh_extract / tsdf_mesh_extract_lod (any level) without a round trip
+ *   through the host.  Those are world coordinates -- the STORED fp32 positions: mapping them back does not give the emit kernel's u for every vertex (one
+ *   ulp apart for a few per cent), so no bit equality with the mesh's own vertex colours is claimed --, and TSDF_TAPS_UNIT_CUBE is TSDF_ERR_INVALID_ARGUMENT.
+ *   It uses the frame slot current at THIS call, not at the extract.  Results go into device arrays of the context sized exactly, kept until the next
+ *   extract, the next call of this entry, tsdf_set_voxel_size or tsdf_destroy.  It synchronises and returns the counts (either pointer may be NULL).
+ * tsdf_mesh_download_texture_taps: copies those results, [n_vertices][n_streams].  Either pointer may be NULL.  TSDF_ERR_STATE without taps for the
+ *   current extract, and for `sensor` when TSDF_TAPS_SENSOR was not asked for.
+ * tsdf_texture_tap_stats: out = {points, streams, (point, stream) pairs with quality > 0, pairs not evaluated} of the last call of any of the three forms
+ *   (waits for it).  TSDF_ERR_STATE before any call.
+ * Errors.  n == 0: TSDF_OK, nothing is launched.  TSDF_ERR_INVALID_ARGUMENT: an unknown flag (also with n == 0); with n > 0 a NULL point or tap array,
+ *   `sensor` given without TSDF_TAPS_SENSOR or the flag without the array; more than 2^40 points.  TSDF_ERR_STATE: without calibration (cv_xyz_inv, cv_uv)
+ *   of every stream or without a frame; the mesh form without an extract.  -1 for a NULL context. */
+#define TSDF_TAPS_UNIT_CUBE 1u
+#define TSDF_TAPS_SENSOR    2u
+typedef struct tsdf_texture_tap { float u, v, quality, dist; } tsdf_texture_tap;
+typedef struct tsdf_sensor_tap { float x, y, z, depth; } tsdf_sensor_tap;
+int32_t tsdf_texture_taps(tsdf_ctx* ctx, const float* xyz, uint64_t n, uint32_t flags, tsdf_texture_tap* taps, tsdf_sensor_tap* sensor);
+int32_t tsdf_texture_taps_dev(tsdf_ctx* ctx, const float* xyz_dev, uint64_t n, uint32_t flags, tsdf_texture_tap* taps_dev, tsdf_sensor_tap* sensor_dev);
+int32_t tsdf_mesh_texture_taps(tsdf_ctx* ctx, uint32_t flags, uint64_t* n_vertices, uint32_t* n_streams);
+int32_t tsdf_mesh_download_texture_taps(tsdf_ctx* ctx, tsdf_texture_tap* taps, tsdf_sensor_tap* sensor);
+int32_t tsdf_texture_tap_stats(tsdf_ctx* ctx, uint64_t out[4]);
+
 /* ---- frame read-out: the swap ------------------------------------------------------------------------
  * The client ends a frame with glfwSwapBuffers (source/kinect_client.cpp:533): an RGBA8 window goes to a display (GLFW's default framebuffer has 8
  * bits per channel and the client sets no window hint that changes it, :942-951).  This device has no display; tsdf_present is the swap for a host

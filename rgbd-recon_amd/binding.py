@@ -239,6 +239,70 @@ def make_rays(origin, direction, t_min=0.0, t_max=np.inf):
     return rays
 
 
+TAPS_UNIT_CUBE, TAPS_SENSOR = 1, 2   # tsdf_texture_taps: flags
+
+
+class TextureTap(C.Structure):
+    """tsdf_texture_tap of rgbd_recon_hip.h"""
+    _fields_ = [("u", C.c_float), ("v", C.c_float), ("quality", C.c_float), ("dist", C.c_float)]
+
+
+class SensorTap(C.Structure):
+    """tsdf_sensor_tap of rgbd_recon_hip.h"""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("depth", C.c_float)]
+
+
+# the same two records as numpy dtypes: what texture_taps / mesh_texture_taps return, [points][streams]
+TEXTURE_TAP_DTYPE = np.dtype([("u", np.float32), ("v", np.float32), ("quality", np.float32), ("dist", np.float32)])
+SENSOR_TAP_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("z", np.float32), ("depth", np.float32)])
+
+
+def _axis_linear(u, n):
+    """LINEAR + CLAMP_TO_EDGE along one axis in float32: f = u * n - 0.5, texels clamp(floor(f)), clamp(floor(f) + 1), weight f - floor(f)"""
+    f32 = np.float32
+    f = (u * f32(n) - f32(0.5)).astype(f32)
+    fl = np.floor(f)
+    a = (f - fl).astype(f32)
+    hi = f32(n - 1)
+    i0 = np.where(np.isnan(fl), f32(0), np.clip(fl, f32(0), hi)).astype(np.int64)
+    i1 = np.where(np.isnan(fl), f32(0), np.clip((fl + f32(1)).astype(f32), f32(0), hi)).astype(np.int64)
+    return i0, i1, a
+
+
+def blend_from_taps(taps, colour_rgb8):
+    """The receiver's rule of the header's texture tap section in float32 numpy: taps TEXTURE_TAP_DTYPE [n][N], colour_rgb8 uint8 [N][Hc][Wc][3] (the
+    frame's colour images) -> rgba float32 [n][4], alpha +1 (weighted by quality) / -1 (fallback).  Fed the taps of a unit-cube point it gives the bits of
+    blendColors there: the ray surface's rgba, the mesh colour."""
+    f32 = np.float32
+    taps = np.asarray(taps)
+    assert taps.dtype == TEXTURE_TAP_DTYPE and taps.ndim == 2
+    img = np.asarray(colour_rgb8, np.uint8)
+    n, N = taps.shape
+    assert img.ndim == 4 and img.shape[0] == N and img.shape[3] == 3
+    ch, cw = img.shape[1], img.shape[2]
+    lerp = lambda a, b, t: (a + ((b - a).astype(f32) * t).astype(f32)).astype(f32)
+    tc, tc2 = np.zeros((n, 3), f32), np.zeros((n, 3), f32)
+    tw, tw2 = np.zeros(n, f32), np.zeros(n, f32)
+    with np.errstate(all="ignore"):
+        for i in range(N):
+            x0, x1, ax = _axis_linear(taps["u"][:, i], cw)
+            y0, y1, ay = _axis_linear(taps["v"][:, i], ch)
+            tex = lambda y, x: (img[i][y, x].astype(f32) / f32(255.0)).astype(f32)
+            ax3, ay3 = ax[:, None], ay[:, None]
+            col = lerp(lerp(tex(y0, x0), tex(y0, x1), ax3), lerp(tex(y1, x0), tex(y1, x1), ax3), ay3)
+            q, dist = taps["quality"][:, i].astype(f32), taps["dist"][:, i].astype(f32)
+            de = (dist + f32(0.01)).astype(f32)
+            tc = (tc + ((col * q[:, None]).astype(f32) / de[:, None]).astype(f32)).astype(f32)
+            tw = (tw + (q / de).astype(f32)).astype(f32)
+            tc2 = (tc2 + (col / dist[:, None]).astype(f32)).astype(f32)
+            tw2 = (tw2 + (f32(1.0) / dist).astype(f32)).astype(f32)
+        valid = tw > 0
+        out = np.zeros((n, 4), f32)
+        out[:, :3] = np.where(valid[:, None], tc / tw[:, None], tc2 / tw2[:, None])
+        out[:, 3] = np.where(valid, f32(1.0), f32(-1.0))
+    return out
+
+
 K1_FORMS = ("generic", "lds_direct", "lds_separable", "record", "cached")   # TSDF_K1_* of rgbd_recon_hip.h
 
 
@@ -810,6 +874,50 @@ class ReconIntegrationHip:
         out = (C.c_uint64 * 4)()
         self._ck(self._L.tsdf_ray_stats(self._c, out))
         return dict(rays=int(out[0]), hits=int(out[1]), samples=int(out[2]), fetched=int(out[3]))
+
+    # ------------------------------------------------------------------ texture taps (no counterpart in the reference)
+    def texture_taps(self, points, unit_cube=False, sensor=False):
+        """Per point and stream where the stream's colour image is read and the two numbers blendColors weights the read with (tsdf_texture_taps).
+        points: floats [n][3], world coordinates unless unit_cube.  -> taps (TEXTURE_TAP_DTYPE [n][N]), or (taps, sensor records (SENSOR_TAP_DTYPE
+        [n][N])) with sensor=True.  blend_from_taps(taps, colour images) is the receiver's rule."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = len(pts)
+        flags = (TAPS_UNIT_CUBE if unit_cube else 0) | (TAPS_SENSOR if sensor else 0)
+        taps = np.zeros((n, self.n), TEXTURE_TAP_DTYPE)
+        sens = np.zeros((n, self.n), SENSOR_TAP_DTYPE) if sensor else None
+        self._ck(self._L.tsdf_texture_taps(self._c, pts.ctypes.data_as(C.c_void_p), C.c_uint64(n), C.c_uint32(flags), taps.ctypes.data_as(C.c_void_p),
+                                           sens.ctypes.data_as(C.c_void_p) if sens is not None else None))
+        return taps if sens is None else (taps, sens)
+
+    def texture_taps_dev(self, points_ptr, n, taps_ptr, sensor_ptr=0, unit_cube=False):
+        """tsdf_texture_taps_dev: raw device pointers (e.g. torch tensors' data_ptr()) to n points of 3 floats and n x N 16-byte records; sensor records
+        exactly when sensor_ptr is given.  Queued on the context's stream, no host wait; the arrays must stay alive until a later sync()."""
+        flags = (TAPS_UNIT_CUBE if unit_cube else 0) | (TAPS_SENSOR if sensor_ptr else 0)
+        self._ck(self._L.tsdf_texture_taps_dev(self._c, C.c_void_p(int(points_ptr)), C.c_uint64(int(n)), C.c_uint32(flags), C.c_void_p(int(taps_ptr)),
+                                               C.c_void_p(int(sensor_ptr)) if sensor_ptr else None))
+
+    def mesh_texture_taps(self, sensor=False, download=True):
+        """Texture taps at the vertices of the last extract_mesh (tsdf_mesh_texture_taps: on the device, over the mesh's stored world positions, with the
+        frame slot current NOW) -> taps (TEXTURE_TAP_DTYPE [n_vertices][N]), or (taps, sensor records) with sensor=True; download=False: the counts
+        (n_vertices, n_streams) only, the results stay on the device (mesh_download_texture_taps)."""
+        nv, ns = C.c_uint64(), C.c_uint32()
+        self._ck(self._L.tsdf_mesh_texture_taps(self._c, C.c_uint32(TAPS_SENSOR if sensor else 0), C.byref(nv), C.byref(ns)))
+        if not download:
+            return int(nv.value), int(ns.value)
+        return self.mesh_download_texture_taps(int(nv.value), sensor)
+
+    def mesh_download_texture_taps(self, n_vertices, sensor=False):
+        """tsdf_mesh_download_texture_taps for a mesh of n_vertices (what extract_mesh / mesh_texture_taps(download=False) returned)"""
+        taps = np.zeros((int(n_vertices), self.n), TEXTURE_TAP_DTYPE)
+        sens = np.zeros((int(n_vertices), self.n), SENSOR_TAP_DTYPE) if sensor else None
+        self._ck(self._L.tsdf_mesh_download_texture_taps(self._c, taps.ctypes.data_as(C.c_void_p), sens.ctypes.data_as(C.c_void_p) if sens is not None else None))
+        return taps if sens is None else (taps, sens)
+
+    def texture_tap_stats(self):
+        """dict of the last texture tap call: points, streams, with_quality ((point, stream) pairs with quality > 0), not_evaluated (pairs)"""
+        out = (C.c_uint64 * 4)()
+        self._ck(self._L.tsdf_texture_tap_stats(self._c, out))
+        return dict(points=int(out[0]), streams=int(out[1]), with_quality=int(out[2]), not_evaluated=int(out[3]))
 
     # ------------------------------------------------------------------ timers / multi-GPU hooks
     def enable_timers(self, on=True): self._ck(self._L.tsdf_enable_timers(self._c, int(on)))

@@ -599,9 +599,16 @@ RayTarget ray_target(tsdf_ctx* c) {
 
 // setVoxelSize()'s device side, recon_integration.cpp:340-348: the volume for the current c->res (tile-major storage, slot table of a
 // sparse pool, per-tile state and work lists).  Called by tsdf_create and tsdf_set_voxel_size; everything it allocates is released first.
+// the mesh form's texture taps belong to one extract (nothing queued reads them: tsdf_mesh_texture_taps synchronises)
+void release_mesh_texture_taps(tsdf_ctx* c) {
+  tsdf_ctx::TextureTaps& X = c->taps;
+  hipFree(X.mesh_taps); hipFree(X.mesh_sensor);
+  X.mesh_taps = nullptr; X.mesh_sensor = nullptr; X.mesh_nv = 0; X.mesh_valid = false; X.mesh_has_sensor = false;
+}
 void release_mesh(tsdf_ctx* c) {
   hipFree(c->mesh.pos); hipFree(c->mesh.nrm); hipFree(c->mesh.col); hipFree(c->mesh.tri);
   c->mesh = tsdf_ctx::Mesh{};
+  release_mesh_texture_taps(c);
 }
 // the mesh ring's slots and scratch (nothing may be in flight: an idle ring, or behind a synchronisation of the streams); the configuration stays
 void release_mesh_stream(tsdf_ctx* c) {
@@ -825,6 +832,7 @@ int32_t tsdf_create(const tsdf_config* cfg, tsdf_ctx** out) {
   };
   if ((rc = tryhip(hipHostMalloc((void**)&c->h_num_occupied, sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc"))) return fail(rc);
   *c->h_num_occupied = 0;
+  if ((rc = tryhip(hipMalloc((void**)&c->taps.d_words, (size_t)kTapStatBytes), "hipMalloc(texture tap counters)"))) return fail(rc);   // (so that tsdf_texture_taps_dev allocates nothing)
   if ((rc = setup_bricks(c, cfg->brick_size))) return fail(rc);
   // frame images
   FrameImages& F = c->frame;
@@ -872,6 +880,7 @@ int32_t tsdf_destroy(tsdf_ctx* c) {
   for (hipEvent_t e : c->read_fence) if (e) hipEventDestroy(e);
   hipFree(c->d_mvt_vtx); hipFree(c->d_calibvis_skipped);
   hipFree(c->rays.d_rays); hipFree(c->rays.d_hits); hipFree(c->rays.d_surf); hipFree(c->rays.d_list); hipFree(c->rays.d_words);
+  hipFree(c->taps.d_xyz); hipFree(c->taps.d_taps); hipFree(c->taps.d_sensor); hipFree(c->taps.mesh_taps); hipFree(c->taps.mesh_sensor); hipFree(c->taps.d_words);
   if (c->fill_worker) {
     c->fill_worker->stop.store(true);
     { std::lock_guard<std::mutex> lk(c->fill_worker->m); }
@@ -2803,6 +2812,130 @@ int32_t tsdf_ray_stats(tsdf_ctx* c, uint64_t out[4]) {
   HIP_TRY(c, hipMemcpyAsync(w, R.d_words, sizeof(w), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   out[1] = w[0]; out[2] = w[1]; out[3] = w[2];
+  return TSDF_OK;
+}
+
+// ---- texture taps (k_texture_taps.hip; the definition is in the header, the host bookkeeping in texture_taps.hpp).  The reference has no counterpart.
+static int32_t texture_taps_checks(tsdf_ctx* c, const void* xyz, uint64_t n, uint32_t flags, const void* taps, const void* sensor) {
+  switch (texture_taps_arguments(n, flags, xyz != nullptr, taps != nullptr, sensor != nullptr)) {
+    case 0: break;
+    case 1: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "unknown texture tap flag (1 unit cube, 2 sensor records)");
+    case 2: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "null point / tap array");
+    case 3: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "the sensor array goes with TSDF_TAPS_SENSOR: given exactly when it is set");
+    default: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "%llu points in one call (at most 2^40)", (unsigned long long)n);
+  }
+  return require_inputs(c, false, true);                                 // calibration (cv_xyz_inv, cv_uv) and a frame; no volume is read
+}
+// the launches of one call on the context's stream, device arrays in and out; no host wait, no allocation
+static int32_t texture_taps_queue(tsdf_ctx* c, const float* xyz, uint64_t n, uint32_t flags, tsdf_texture_tap* taps, tsdf_sensor_tap* sensor) {
+  tsdf_ctx::TextureTaps& X = c->taps;
+  const uint32_t N = c->cfg.num_streams;
+  X.last_n = n; X.called = true;
+  if (n == 0) return TSDF_OK;                                            // (tsdf_texture_tap_stats answers zeros without reading the counters)
+  HIP_TRY(c, hipMemsetAsync(X.d_words, 0, (size_t)kTapStatBytes, c->stream));
+  HIP_TRY(c, join_pre(c));                                              // the current frame slot's images, as the coloured ray cast takes them
+  const float* lo = c->cfg.bbox_min; const float* hi = c->cfg.bbox_max;
+  TapsLaunch Q{};
+  for (int a = 0; a < 3; ++a) { Q.bbox_min[a] = lo[a]; Q.ext[a] = hi[a] - lo[a]; }
+  Q.flags = flags;
+  const TapChunks K{n, kTapsChunk};
+  for (uint64_t k = 0; k < K.launches(); ++k) {
+    const uint64_t first = K.first(k);
+    Q.n_points = K.count(k);
+    timer_begin(c, "texture_taps");
+    launch_texture_taps(c->stream, c->luts, c->frame, c->vol.limit, Q, xyz + 3 * first, taps + first * N, sensor ? sensor + first * N : nullptr, X.d_words);
+    timer_end(c, "texture_taps");
+  }
+  HIP_TRY(c, hipGetLastError());
+  // the upload two frames later overwrites the slot these launches read: it waits for what the context's stream held when the frame between was opened
+  // (the lane ahead's gate), and with the volume sets alternating draw_done[set] is recorded again behind them, as the coloured cast and tsdf_mesh_stream do
+  return overlay_rerecord_draw(c);
+}
+int32_t tsdf_texture_taps(tsdf_ctx* c, const float* xyz, uint64_t n, uint32_t flags, tsdf_texture_tap* taps, tsdf_sensor_tap* sensor) {
+  CHECK_CTX(c);
+  int32_t rc = texture_taps_checks(c, xyz, n, flags, taps, sensor);
+  if (rc) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  tsdf_ctx::TextureTaps& X = c->taps;
+  const uint32_t N = c->cfg.num_streams;
+  if (n == 0) return texture_taps_queue(c, nullptr, 0, flags, nullptr, nullptr);
+  if (const uint64_t cap = X.staging.grow(n)) {                          // (nothing queued reads the staging: every call that uses it synchronises)
+    hipFree(X.d_xyz); hipFree(X.d_taps); X.d_xyz = nullptr; X.d_taps = nullptr; X.staging.grown(0);
+    HIP_TRY(c, hipMalloc((void**)&X.d_xyz, (size_t)tap_point_bytes(cap)));
+    HIP_TRY(c, hipMalloc((void**)&X.d_taps, (size_t)tap_record_bytes(cap, N)));
+    X.staging.grown(cap);
+  }
+  if (const uint64_t cap = X.staging.grow_sensor(n, sensor != nullptr)) {
+    hipFree(X.d_sensor); X.d_sensor = nullptr; X.staging.sensor_grown(0);
+    HIP_TRY(c, hipMalloc((void**)&X.d_sensor, (size_t)tap_record_bytes(cap, N)));
+    X.staging.sensor_grown(cap);
+  }
+  HIP_TRY(c, hipMemcpyAsync(X.d_xyz, xyz, (size_t)tap_point_bytes(n), hipMemcpyHostToDevice, c->stream));
+  if ((rc = texture_taps_queue(c, X.d_xyz, n, flags, X.d_taps, sensor ? X.d_sensor : nullptr))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(taps, X.d_taps, (size_t)tap_record_bytes(n, N), hipMemcpyDeviceToHost, c->stream));
+  if (sensor) HIP_TRY(c, hipMemcpyAsync(sensor, X.d_sensor, (size_t)tap_record_bytes(n, N), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, sync_ctx(c));
+  return TSDF_OK;
+}
+int32_t tsdf_texture_taps_dev(tsdf_ctx* c, const float* xyz_dev, uint64_t n, uint32_t flags, tsdf_texture_tap* taps_dev, tsdf_sensor_tap* sensor_dev) {
+  CHECK_CTX(c);
+  int32_t rc = texture_taps_checks(c, xyz_dev, n, flags, taps_dev, sensor_dev);
+  if (rc) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  return texture_taps_queue(c, xyz_dev, n, flags, taps_dev, sensor_dev);
+}
+int32_t tsdf_mesh_texture_taps(tsdf_ctx* c, uint32_t flags, uint64_t* n_vertices, uint32_t* n_streams) {
+  CHECK_CTX(c);
+  switch (mesh_texture_taps_arguments(flags)) {
+    case 0: break;
+    case 1: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "unknown texture tap flag (2 sensor records)");
+    default: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "TSDF_TAPS_UNIT_CUBE on the mesh form: a mesh's positions are world coordinates");
+  }
+  if (!c->mesh.valid) FAIL(c, TSDF_ERR_STATE, "no mesh (tsdf_mesh_extract / tsdf_mesh_extract_lod)");
+  int32_t rc = require_inputs(c, false, true);
+  if (rc) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  release_mesh_texture_taps(c);
+  tsdf_ctx::TextureTaps& X = c->taps;
+  const uint32_t N = c->cfg.num_streams;
+  const uint64_t nv = c->mesh.nv;
+  const bool want_sensor = (flags & TSDF_TAPS_SENSOR) != 0;
+  if (nv) {
+    bool ok = hipMalloc((void**)&X.mesh_taps, (size_t)tap_record_bytes(nv, N)) == hipSuccess;
+    if (ok && want_sensor) ok = hipMalloc((void**)&X.mesh_sensor, (size_t)tap_record_bytes(nv, N)) == hipSuccess;
+    if (!ok) { (void)hipGetLastError(); release_mesh_texture_taps(c); FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "no device memory for the texture taps of %llu vertices", (unsigned long long)nv); }
+  }
+  if ((rc = texture_taps_queue(c, c->mesh.pos, nv, flags, X.mesh_taps, X.mesh_sensor))) { release_mesh_texture_taps(c); return rc; }
+  HIP_TRY(c, sync_ctx(c));
+  X.mesh_nv = nv; X.mesh_valid = true; X.mesh_has_sensor = want_sensor;
+  if (n_vertices) *n_vertices = nv;
+  if (n_streams) *n_streams = N;
+  return TSDF_OK;
+}
+int32_t tsdf_mesh_download_texture_taps(tsdf_ctx* c, tsdf_texture_tap* taps, tsdf_sensor_tap* sensor) {
+  CHECK_CTX(c);
+  const tsdf_ctx::TextureTaps& X = c->taps;
+  if (!c->mesh.valid || !X.mesh_valid) FAIL(c, TSDF_ERR_STATE, "no texture taps for the current mesh (tsdf_mesh_texture_taps after the extract)");
+  if (sensor && !X.mesh_has_sensor) FAIL(c, TSDF_ERR_STATE, "the last tsdf_mesh_texture_taps produced no sensor records (TSDF_TAPS_SENSOR)");
+  if (!X.mesh_nv) return TSDF_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t bytes = (size_t)tap_record_bytes(X.mesh_nv, c->cfg.num_streams);
+  if (taps) HIP_TRY(c, hipMemcpy(taps, X.mesh_taps, bytes, hipMemcpyDeviceToHost));
+  if (sensor) HIP_TRY(c, hipMemcpy(sensor, X.mesh_sensor, bytes, hipMemcpyDeviceToHost));
+  return TSDF_OK;
+}
+int32_t tsdf_texture_tap_stats(tsdf_ctx* c, uint64_t out[4]) {
+  CHECK_CTX(c);
+  if (!out) return TSDF_ERR_INVALID_ARGUMENT;
+  const tsdf_ctx::TextureTaps& X = c->taps;
+  if (!X.called) FAIL(c, TSDF_ERR_STATE, "no texture tap call yet (tsdf_texture_taps / tsdf_texture_taps_dev / tsdf_mesh_texture_taps)");
+  out[0] = X.last_n; out[1] = c->cfg.num_streams; out[2] = out[3] = 0;
+  if (!X.last_n) return TSDF_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  unsigned long long w[kTapStatSlots * kTapStatStride] = {};             // the counters are kTapStatSlots pairs (texture_taps.hpp): summed here
+  HIP_TRY(c, hipMemcpyAsync(w, X.d_words, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  tap_stat_sum(w, out + 2);
   return TSDF_OK;
 }
 

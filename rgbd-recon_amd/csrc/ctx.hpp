@@ -11,6 +11,7 @@
 #include "draw_lanes.hpp"
 #include "frame_intake.hpp"
 #include "ray_staging.hpp"
+#include "texture_taps.hpp"
 
 using namespace rr;
 
@@ -157,6 +158,12 @@ struct tsdf_ctx {
   // allocates), `words` = {hits, samples accounted for, samples fetched} as three 64-bit counters of the cast, then the list's 32-bit count at byte 32
   struct Rays { tsdf_ray* d_rays = nullptr; tsdf_ray_hit* d_hits = nullptr; tsdf_ray_surface* d_surf = nullptr; RayStaging staging{};
                 RayHitRec* d_list = nullptr; unsigned long long* d_words = nullptr; uint64_t last_n = 0; bool cast = false; } rays;
+  // texture taps (tsdf_texture_taps / _dev, tsdf_mesh_texture_taps): the synchronous form's device staging (texture_taps.hpp: grown on demand, then kept),
+  // the mesh form's results for the current extract (sized exactly; released with the mesh), `words` = {pairs with quality > 0, pairs not evaluated} of the
+  // last call as kTapStatSlots pairs of 64-bit counters which the host sums (allocated with the context: no call allocates them), and the last call's point count
+  struct TextureTaps { float* d_xyz = nullptr; tsdf_texture_tap* d_taps = nullptr; tsdf_sensor_tap* d_sensor = nullptr; TapStaging staging{};
+                       tsdf_texture_tap* mesh_taps = nullptr; tsdf_sensor_tap* mesh_sensor = nullptr; uint64_t mesh_nv = 0; bool mesh_valid = false, mesh_has_sensor = false;
+                       unsigned long long* d_words = nullptr; uint64_t last_n = 0; bool called = false; } taps;
   bool have_volume = false;          // integrate() or tsdf_upload_volume has written the volume since it was set up (what the mesh extraction may read)
   // flags (recon_integration.cpp:54-57)
   bool fill_holes = true, use_bricks = true, skip_space = true;

@@ -402,6 +402,16 @@ void launch_rays_march(hipStream_t st, const Volume& V, const RayCast& Q, const 
 void launch_rays_surface(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const RayCast& Q, const RayHitRec* list,
                          const uint32_t* list_count, tsdf_ray_surface* surf);
 void launch_view_rays(hipStream_t st, const ViewParams& P, int x0, int y0, int w, int h, tsdf_ray* rays);
+// texture taps (k_texture_taps.hip): one launch serves at most kTapsChunk points (texture_taps.hpp), one lane per (point, stream) pair, blockIdx.y = stream
+struct TapsLaunch {
+  float bbox_min[3], ext[3];        // the ray section's mapping: u = (p - bbox_min) / ext, ext = bbox_max - bbox_min in fp32
+  uint32_t flags;                   // TSDF_TAPS_UNIT_CUBE | TSDF_TAPS_SENSOR
+  uint32_t n_points;                // points of this launch (<= kTapsChunk)
+};
+// xyz: the launch's points, 3 floats each; taps / sensor: [point][stream] records (sensor: nullptr without the flag); stats: the kTapStatSlots pairs
+// of device words {pairs with quality > 0, pairs not evaluated} (texture_taps.hpp), added to
+void launch_texture_taps(hipStream_t st, const StreamTable& T, const FrameImages& F, float limit, const TapsLaunch& Q, const float* xyz, tsdf_texture_tap* taps,
+                         tsdf_sensor_tap* sensor, unsigned long long* stats);
 void launch_clear_image(hipStream_t st, float4* color, float* depth, size_t n, float4 c, float d);
 void launch_export_partial(hipStream_t st, const RayTarget& R, int w, int h, void* dst);
 void launch_composite(hipStream_t st, const void* gathered, int n, const RayTarget& R, int w, int h);

@@ -270,6 +270,32 @@ class ReconIntegrationHip {
     check(tsdf_ray_stats(m_ctx, s));
     return RayStats{s[0], s[1], s[2], s[3]};
   }
+  // ---- texture taps (tsdf_texture_taps): camera-resolution colour for a receiver of the mesh.  The reference has no counterpart: its client runs
+  // blendColors per pixel against the colour images and the LUT volumes.  textureTaps gives, per point (world coordinates, or the volume's unit cube) and
+  // stream, where that stream's colour image is read and the two numbers blendColors weights the read with; meshTextureTaps the same at the vertices of the
+  // last meshExtract, evaluated on the device; a receiver blends per fragment by the rule in the header.  Records are [points][streams].
+  struct TextureTaps { std::vector<tsdf_texture_tap> taps; std::vector<tsdf_sensor_tap> sensor; std::uint64_t points = 0; std::uint32_t streams = 0; };   // sensor: empty unless asked for
+  struct TextureTapStats { std::uint64_t points = 0, streams = 0, with_quality = 0, not_evaluated = 0; };
+  void textureTaps(const std::vector<float>& xyz, TextureTaps& out, bool sensor = false, bool unit_cube = false) {
+    const std::uint32_t flags = (unit_cube ? TSDF_TAPS_UNIT_CUBE : 0u) | (sensor ? TSDF_TAPS_SENSOR : 0u);
+    out.points = xyz.size() / 3; out.streams = m_in.num_kinects;
+    const std::size_t records = (std::size_t)out.points * out.streams;
+    out.taps.assign(records, tsdf_texture_tap{});
+    out.sensor.assign(sensor ? records : 0, tsdf_sensor_tap{});
+    check(tsdf_texture_taps(m_ctx, xyz.data(), out.points, flags, out.taps.data(), sensor ? out.sensor.data() : nullptr));
+  }
+  void meshTextureTaps(TextureTaps& out, bool sensor = false) {
+    check(tsdf_mesh_texture_taps(m_ctx, sensor ? TSDF_TAPS_SENSOR : 0u, &out.points, &out.streams));
+    const std::size_t records = (std::size_t)out.points * out.streams;
+    out.taps.assign(records, tsdf_texture_tap{});
+    out.sensor.assign(sensor ? records : 0, tsdf_sensor_tap{});
+    check(tsdf_mesh_download_texture_taps(m_ctx, out.taps.data(), sensor ? out.sensor.data() : nullptr));
+  }
+  TextureTapStats textureTapStats() {
+    std::uint64_t s[4];
+    check(tsdf_texture_tap_stats(m_ctx, s));
+    return TextureTapStats{s[0], s[1], s[2], s[3]};
+  }
   // ---- kinect::ReconPoints::draw() (recon_points.cpp:71-111) on the same inputs: the point back-end for A/B comparison
   void uploadNormals(const float* normals_rgb) { check(tsdf_upload_normals(m_ctx, normals_rgb)); }
   void drawPoints() { check(tsdf_draw_points(m_ctx, m_mv, m_proj)); }
