@@ -802,6 +802,51 @@ int32_t tsdf_mesh_texture_taps(tsdf_ctx* ctx, uint32_t flags, uint64_t* n_vertic
 int32_t tsdf_mesh_download_texture_taps(tsdf_ctx* ctx, tsdf_texture_tap* taps, tsdf_sensor_tap* sensor);
 int32_t tsdf_texture_tap_stats(tsdf_ctx* ctx, uint64_t out[4]);
 
+/* ---- mesh components: label the mesh's islands, drop the small ones ---------------------------------------
+ * A TSDF fused from noisy depth does not fall as one surface: beside the subject and the floor there is a cloud of small closed blobs where a few voxels
+ * crossed zero.  These entries label the connected components of the mesh the last tsdf_mesh_extract / tsdf_mesh_extract_lod left in the context (any
+ * level; dense or sparse pool: only the mesh arrays are read) and rebuild the mesh without a set of them, on the device.  No counterpart in the
+ * reference.  tests/mesh_component_reference.py restates the definition in numpy; device and numpy agree byte for byte.
+ *
+ * Connectivity is by index, never by position.  Vertices i and j are adjacent iff some triangle contains both; a component is a class of the transitive
+ *   closure.  Coincident vertices with different indices (the mesh keeps degenerate triangles, so there are some) are connected only if triangles
+ *   connect them.
+ * Representative and numbering.  A component's representative is its smallest vertex index; components are numbered 0 .. C - 1 by increasing
+ *   representative, so component 0 contains vertex 0.
+ * Unused vertices.  A vertex used by no triangle is a component of its own with n_triangles = 0 (no extract produces one; the definition covers it).
+ * Triangles.  A triangle's component is that of its vertices: all three agree.
+ * Table.  tsdf_mesh_component, 16 bytes per component: first_vertex (the representative), n_vertices, n_triangles, reserved (0).
+ * Keeping a set.  keep[c] != 0: component c stays.  Kept vertices stay in their order, the new index of a vertex is the number of kept vertices before
+ *   it; position rows -- and normal and colour rows where extracted -- move bit for bit (NaN payloads included); kept triangles stay in their order,
+ *   their three indices remapped, the winding untouched.  The result is a mesh in the definition's order; zero kept components give the empty mesh.
+ * Defined despite atomics.  The device labels with a union-find whose links only ever point to a smaller index; whichever lane arrives first, the
+ *   roots at the end are the smallest indices, the numbering is a scan and the counts are integer sums: two runs give identical bytes.
+ *
+ * tsdf_mesh_components labels the current mesh on the context's stream, synchronises and returns C (the pointer may be NULL).  The labels and the table
+ *   stay in device memory beside the mesh until the next extract, tsdf_set_voxel_size, a keep / filter or tsdf_destroy; the mesh arrays are untouched.
+ *   It may be called again, also after a keep / filter: the components are then those of the filtered mesh.  Timer "mesh_components".
+ * tsdf_mesh_download_components copies vertex_component [V], triangle_component [T] and the table [C]; any may be NULL.
+ * tsdf_mesh_keep_components (keep: C bytes of host memory) and tsdf_mesh_filter_components (keep[c] = table[c].n_triangles >= min_triangles, decided on
+ *   the device) replace the context's mesh with the filtered one, its arrays sized exactly, and return its counts (either pointer may be NULL).
+ *   tsdf_mesh_download / _write_ply / _stats serve the filtered mesh afterwards: stats[3], the storage bytes, is updated, the three tile counts stay
+ *   those of the extract.  The labels are released (tsdf_mesh_components labels the new mesh), and so are the mesh's texture taps:
+ *   tsdf_mesh_download_texture_taps answers TSDF_ERR_STATE until tsdf_mesh_texture_taps runs again.  The new arrays are allocated before anything is
+ *   replaced: TSDF_ERR_OUT_OF_MEMORY leaves mesh and labels exactly as they were.  When every component is kept the arrays stay in place.
+ *   Timer "mesh_filter".
+ * tsdf_mesh_component_stats: out = {components, triangles of the largest component -- both of the last tsdf_mesh_components of the current mesh, 0
+ *   before it and after a keep / filter --, vertices removed, triangles removed by the last keep / filter of this extract (0 before one)}.
+ * Errors.  TSDF_ERR_STATE without an extract (a Z-slab context extracts no mesh, so always there); for download, keep and filter without components of
+ *   the current mesh.  TSDF_ERR_INVALID_ARGUMENT for a NULL keep or a NULL out.  -1 for a NULL context.
+ * Out of scope.  The streamed ring (tsdf_mesh_stream): a frame's header and payload size are fixed before its emit, a filtered frame needs a second
+ *   header stage.  Z-slab contexts.  Welding by position.  Geometric measures per component (area, volume, bounding box): the caller has the arrays.
+ *   A context that never calls these entries runs exactly what it ran before they existed. */
+typedef struct tsdf_mesh_component { uint32_t first_vertex, n_vertices, n_triangles, reserved /* 0 */; } tsdf_mesh_component;
+int32_t tsdf_mesh_components(tsdf_ctx* ctx, uint64_t* n_components);
+int32_t tsdf_mesh_download_components(tsdf_ctx* ctx, uint32_t* vertex_component, uint32_t* triangle_component, tsdf_mesh_component* table);
+int32_t tsdf_mesh_keep_components(tsdf_ctx* ctx, const uint8_t* keep, uint64_t* n_vertices, uint64_t* n_triangles);
+int32_t tsdf_mesh_filter_components(tsdf_ctx* ctx, uint32_t min_triangles, uint64_t* n_vertices, uint64_t* n_triangles);
+int32_t tsdf_mesh_component_stats(tsdf_ctx* ctx, uint64_t out[4]);
+
 /* ---- frame read-out: the swap ------------------------------------------------------------------------
  * The client ends a frame with glfwSwapBuffers (source/kinect_client.cpp:533): an RGBA8 window goes to a display (GLFW's default framebuffer has 8
  * bits per channel and the client sets no window hint that changes it, :942-951).  This device has no display; tsdf_present is the swap for a host

@@ -179,6 +179,8 @@ PRESENT_RGBA8, PRESENT_DXT1 = 0, 1    # tsdf_present_config: format
 PRESENT_TOP_DOWN = 1                  # ... flags
 MESH_NORMALS, MESH_COLOURS = 1, 2     # tsdf_mesh_extract: flags
 MESH_OVERFLOW_VERTICES, MESH_OVERFLOW_TRIANGLES, MESH_OVERFLOW_TILES = 1, 2, 4   # tsdf_mesh_frame: overflow bits
+# tsdf_mesh_component as a numpy dtype: what mesh_download_components returns as its table
+MESH_COMPONENT_DTYPE = np.dtype([("first_vertex", "<u4"), ("n_vertices", "<u4"), ("n_triangles", "<u4"), ("reserved", "<u4")])
 
 
 class MeshFrame(C.Structure):
@@ -771,6 +773,55 @@ class ReconIntegrationHip:
         out = (C.c_uint64 * 4)()
         self._ck(self._L.tsdf_mesh_stats(self._c, out))
         return dict(tiles=int(out[0]), tiles_skipped=int(out[1]), tiles_with_surface=int(out[2]), bytes=int(out[3]))
+
+    # ------------------------------------------------------------------ mesh components (no counterpart in the reference)
+    def mesh_components(self):
+        """Label the connected components of the current mesh (tsdf_mesh_components: connectivity by index, numbered by smallest vertex) -> their number"""
+        n = C.c_uint64()
+        self._ck(self._L.tsdf_mesh_components(self._c, C.byref(n)))
+        return int(n.value)
+
+    def mesh_download_components(self):
+        """dict of the last mesh_components: vertex_component [V] uint32, triangle_component [T] uint32, table [C] (MESH_COMPONENT_DTYPE)"""
+        self._ck(self._L.tsdf_mesh_download_components(self._c, None, None, None))      # (TsdfError, code -4, without components of the current mesh)
+        nv, nt = self._mesh_counts
+        out = dict(vertex_component=np.zeros(nv, np.uint32), triangle_component=np.zeros(nt, np.uint32),
+                   table=np.zeros(self.mesh_component_stats()["components"], MESH_COMPONENT_DTYPE))
+        self._ck(self._L.tsdf_mesh_download_components(self._c, *[out[k].ctypes.data_as(C.c_void_p) for k in ("vertex_component", "triangle_component", "table")]))
+        return out
+
+    def _mesh_kept(self, call):
+        nv, nt = C.c_uint64(), C.c_uint64()
+        self._ck(call(C.byref(nv), C.byref(nt)))
+        self._mesh_counts = (nv.value, nt.value)                         # download_mesh / write_ply / mesh_stats serve the filtered mesh from here on
+        return self._mesh_counts
+
+    def mesh_keep(self, keep):
+        """Drop every component c of the current mesh with keep[c] == 0 (tsdf_mesh_keep_components; keep: one flag per component) -> (vertices,
+        triangles) left.  The components and the mesh's texture taps are gone afterwards: mesh_components() labels the new mesh."""
+        self._ck(self._L.tsdf_mesh_download_components(self._c, None, None, None))
+        flags = np.ascontiguousarray(np.asarray(keep) != 0, np.uint8)
+        if flags.shape != (self.mesh_component_stats()["components"],):
+            raise ValueError(f"keep has shape {flags.shape}, the mesh has {self.mesh_component_stats()['components']} components")
+        return self._mesh_kept(lambda nv, nt: self._L.tsdf_mesh_keep_components(self._c, flags.ctypes.data_as(C.c_void_p), nv, nt))
+
+    def mesh_filter(self, min_triangles):
+        """mesh_keep of the components with at least min_triangles triangles, decided on the device (tsdf_mesh_filter_components)"""
+        return self._mesh_kept(lambda nv, nt: self._L.tsdf_mesh_filter_components(self._c, C.c_uint32(int(min_triangles)), nv, nt))
+
+    def mesh_keep_largest(self, k=1):
+        """mesh_keep of the k components with the most triangles (ties: the lower component index first)"""
+        n_triangles = self.mesh_download_components()["table"]["n_triangles"]
+        keep = np.zeros(len(n_triangles), np.uint8)
+        keep[np.argsort(-n_triangles.astype(np.int64), kind="stable")[:max(int(k), 0)]] = 1
+        return self.mesh_keep(keep)
+
+    def mesh_component_stats(self):
+        """dict: components and largest_triangles of the last mesh_components of the current mesh (0 before it and after a keep / filter),
+        vertices_removed and triangles_removed by the last keep / filter of this extract"""
+        out = (C.c_uint64 * 4)()
+        self._ck(self._L.tsdf_mesh_component_stats(self._c, out))
+        return dict(components=int(out[0]), largest_triangles=int(out[1]), vertices_removed=int(out[2]), triangles_removed=int(out[3]))
 
     # ------------------------------------------------------------------ mesh streaming (no counterpart in the reference)
     def mesh_stream_config(self, normals=False, colours=False, max_vertices=1 << 20, max_triangles=1 << 21, max_surface_tiles=1 << 14, slots=3, level=0):

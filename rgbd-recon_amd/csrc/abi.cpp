@@ -605,10 +605,18 @@ void release_mesh_texture_taps(tsdf_ctx* c) {
   hipFree(X.mesh_taps); hipFree(X.mesh_sensor);
   X.mesh_taps = nullptr; X.mesh_sensor = nullptr; X.mesh_nv = 0; X.mesh_valid = false; X.mesh_has_sensor = false;
 }
+// the labels and the table of a mesh (nothing queued reads them: tsdf_mesh_components, keep and filter synchronise); what a keep / filter removed stays on record
+void release_mesh_components(tsdf_ctx* c) {
+  tsdf_ctx::MeshComponents& K = c->mcomp;
+  hipFree(K.vertex); hipFree(K.triangle); hipFree(K.table);
+  K.vertex = nullptr; K.triangle = nullptr; K.table = nullptr; K.n = 0; K.largest = 0; K.valid = false;
+}
 void release_mesh(tsdf_ctx* c) {
   hipFree(c->mesh.pos); hipFree(c->mesh.nrm); hipFree(c->mesh.col); hipFree(c->mesh.tri);
   c->mesh = tsdf_ctx::Mesh{};
   release_mesh_texture_taps(c);
+  release_mesh_components(c);
+  c->mcomp = tsdf_ctx::MeshComponents{};
 }
 // the mesh ring's slots and scratch (nothing may be in flight: an idle ring, or behind a synchronisation of the streams); the configuration stays
 void release_mesh_stream(tsdf_ctx* c) {
@@ -2517,6 +2525,145 @@ int32_t tsdf_mesh_stats(tsdf_ctx* c, uint64_t out[4]) {
   int32_t rc = mesh_attribute_check(c, false, false);
   if (rc) return rc;
   for (int k = 0; k < 4; ++k) out[k] = c->mesh.stats[k];
+  return TSDF_OK;
+}
+
+// ---- mesh components (k_mesh_components.hip; the definition is in the header): labels and table of the current mesh, and the mesh without some of them
+namespace {
+struct ComponentTemp {                                                    // what one call allocates besides what it leaves in the context: freed when it returns
+  uint32_t* words = nullptr; unsigned long long* vsums = nullptr; unsigned long long* tsums = nullptr; uint32_t* largest = nullptr; uint8_t* keep = nullptr;
+  tsdf_ctx::MeshComponents made{}; tsdf_ctx::Mesh mesh{};                 // arrays not handed to the context yet
+  ~ComponentTemp() {
+    hipFree(words); hipFree(vsums); hipFree(tsums); hipFree(largest); hipFree(keep);
+    hipFree(made.vertex); hipFree(made.triangle); hipFree(made.table);
+    hipFree(mesh.pos); hipFree(mesh.nrm); hipFree(mesh.col); hipFree(mesh.tri);
+  }
+};
+bool device_alloc(void** p, size_t bytes) { return hipMalloc(p, std::max<size_t>(bytes, 4)) == hipSuccess; }
+}  // namespace
+int32_t tsdf_mesh_components(tsdf_ctx* c, uint64_t* n_components) {
+  CHECK_CTX(c);
+  if (!c->mesh.valid) FAIL(c, TSDF_ERR_STATE, "no mesh (tsdf_mesh_extract / tsdf_mesh_extract_lod)");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const tsdf_ctx::Mesh& M = c->mesh;
+  if (M.nt > 0xffffffffull) FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "%llu triangles do not fit a component's 32-bit count", (unsigned long long)M.nt);
+  const uint32_t nv = (uint32_t)M.nv;
+  const size_t nt = (size_t)M.nt;
+  const int nb = mesh_cc_scan_blocks(nv);
+  ComponentTemp tmp;
+  tsdf_ctx::MeshComponents& K = tmp.made;
+  bool ok = device_alloc((void**)&tmp.words, (size_t)nv * 4) && device_alloc((void**)&tmp.vsums, (size_t)(nb + 1) * 8) && device_alloc((void**)&tmp.largest, 4) &&
+            device_alloc((void**)&K.vertex, (size_t)nv * 4) && device_alloc((void**)&K.triangle, nt * 4);
+  if (!ok) { (void)hipGetLastError(); FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "no device memory for the components of %u vertices and %zu triangles", nv, nt); }
+  unsigned long long n = 0;
+  uint32_t largest = 0;
+  timer_begin(c, "mesh_components");
+  launch_mesh_cc_label(c->stream, M.tri, nv, nt, tmp.words, K.vertex, tmp.vsums);
+  timer_end(c, "mesh_components");
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(&n, tmp.vsums + nb, sizeof(n), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, sync_ctx(c));                                               // (the table is sized exactly: the host has to know C)
+  if (!device_alloc((void**)&K.table, (size_t)n * sizeof(tsdf_mesh_component))) {
+    (void)hipGetLastError();
+    FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "no device memory for a table of %llu components", n);
+  }
+  HIP_TRY(c, hipMemsetAsync(tmp.largest, 0, 4, c->stream));
+  timer_begin(c, "mesh_components");                                     // (a second sample of the same call: the host's allocation lies between the two)
+  launch_mesh_cc_number(c->stream, M.tri, nv, nt, tmp.vsums, (uint32_t)n, tmp.words, K.vertex, K.triangle, K.table, tmp.largest);
+  timer_end(c, "mesh_components");
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(&largest, tmp.largest, 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, sync_ctx(c));
+  release_mesh_components(c);                                            // (an earlier labelling of the same mesh: the same words)
+  tsdf_ctx::MeshComponents& X = c->mcomp;
+  X.vertex = K.vertex; X.triangle = K.triangle; X.table = K.table; X.n = n; X.largest = largest; X.valid = true;
+  K = tsdf_ctx::MeshComponents{};
+  if (n_components) *n_components = n;
+  return TSDF_OK;
+}
+static int32_t mesh_components_check(tsdf_ctx* c) {
+  if (!c->mesh.valid) FAIL(c, TSDF_ERR_STATE, "no mesh (tsdf_mesh_extract / tsdf_mesh_extract_lod)");
+  if (!c->mcomp.valid) FAIL(c, TSDF_ERR_STATE, "no components of the current mesh (tsdf_mesh_components after the extract, and again after a keep / filter)");
+  return TSDF_OK;
+}
+int32_t tsdf_mesh_download_components(tsdf_ctx* c, uint32_t* vertex_component, uint32_t* triangle_component, tsdf_mesh_component* table) {
+  CHECK_CTX(c);
+  int32_t rc = mesh_components_check(c);
+  if (rc) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const tsdf_ctx::MeshComponents& K = c->mcomp;
+  if (vertex_component && c->mesh.nv) HIP_TRY(c, hipMemcpy(vertex_component, K.vertex, (size_t)c->mesh.nv * 4, hipMemcpyDeviceToHost));
+  if (triangle_component && c->mesh.nt) HIP_TRY(c, hipMemcpy(triangle_component, K.triangle, (size_t)c->mesh.nt * 4, hipMemcpyDeviceToHost));
+  if (table && K.n) HIP_TRY(c, hipMemcpy(table, K.table, (size_t)K.n * sizeof(tsdf_mesh_component), hipMemcpyDeviceToHost));
+  return TSDF_OK;
+}
+// keep_host: C bytes, or null = derive the flags from the table (n_triangles >= min_triangles) on the device
+static int32_t mesh_keep(tsdf_ctx* c, const uint8_t* keep_host, uint32_t min_triangles, uint64_t* n_vertices, uint64_t* n_triangles) {
+  int32_t rc = mesh_components_check(c);
+  if (rc) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  tsdf_ctx::Mesh& M = c->mesh;
+  tsdf_ctx::MeshComponents& K = c->mcomp;
+  const uint32_t nv = (uint32_t)M.nv, nc = (uint32_t)K.n;
+  const size_t nt = (size_t)M.nt;
+  const int nbv = mesh_cc_scan_blocks(nv), nbt = mesh_cc_scan_blocks(nt);
+  ComponentTemp tmp;
+  bool ok = device_alloc((void**)&tmp.keep, nc) && device_alloc((void**)&tmp.vsums, (size_t)(nbv + 1) * 8) && device_alloc((void**)&tmp.tsums, (size_t)(nbt + 1) * 8) &&
+            device_alloc((void**)&tmp.words, (size_t)nv * 4);
+  if (!ok) { (void)hipGetLastError(); FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "no device memory to filter a mesh of %u vertices and %zu triangles", nv, nt); }
+  unsigned long long kept_v = 0, kept_t = 0;
+  if (keep_host && nc) HIP_TRY(c, hipMemcpyAsync(tmp.keep, keep_host, nc, hipMemcpyHostToDevice, c->stream));
+  timer_begin(c, "mesh_filter");
+  if (!keep_host) launch_mesh_cc_keep_from_table(c->stream, K.table, nc, min_triangles, tmp.keep);
+  launch_mesh_cc_keep_count(c->stream, tmp.keep, K.vertex, K.triangle, nv, nt, tmp.vsums, tmp.tsums);
+  timer_end(c, "mesh_filter");
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(&kept_v, tmp.vsums + nbv, 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&kept_t, tmp.tsums + nbt, 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, sync_ctx(c));                                               // (the new arrays are sized exactly; keep_host has been read)
+  if (kept_v != M.nv) {                                                  // (every vertex has a component: all vertices kept = every component kept = the mesh as it is)
+    tsdf_ctx::Mesh& N = tmp.mesh;                                        // everything new is allocated before anything is replaced
+    ok = true;
+    if (kept_v) {
+      ok = device_alloc((void**)&N.pos, (size_t)kept_v * 12) && device_alloc((void**)&N.tri, (size_t)kept_t * 12);
+      if (ok && M.nrm) ok = device_alloc((void**)&N.nrm, (size_t)kept_v * 12);
+      if (ok && M.col) ok = device_alloc((void**)&N.col, (size_t)kept_v * 16);
+    }
+    if (!ok) { (void)hipGetLastError(); FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "no device memory for a filtered mesh of %llu vertices and %llu triangles", kept_v, kept_t); }
+    if (kept_v) {
+      timer_begin(c, "mesh_filter");
+      launch_mesh_cc_keep_scatter(c->stream, tmp.keep, K.vertex, K.triangle, nv, nt, tmp.vsums, tmp.tsums, MeshArrays{M.pos, M.nrm, M.col, M.tri},
+                                  MeshArrays{N.pos, N.nrm, N.col, N.tri}, tmp.words);
+      timer_end(c, "mesh_filter");
+      HIP_TRY(c, hipGetLastError());
+      HIP_TRY(c, sync_ctx(c));
+    }
+    std::swap(M.pos, N.pos); std::swap(M.nrm, N.nrm); std::swap(M.col, N.col); std::swap(M.tri, N.tri);   // (tmp frees the old arrays)
+  }
+  K.removed_vertices = M.nv - kept_v; K.removed_triangles = M.nt - kept_t;
+  M.nv = kept_v; M.nt = kept_t;
+  M.stats[3] = M.nv * (3 + ((M.flags & TSDF_MESH_NORMALS) ? 3 : 0) + ((M.flags & TSDF_MESH_COLOURS) ? 4 : 0)) * sizeof(float) + M.nt * 3 * sizeof(uint32_t);
+  release_mesh_components(c);                                            // (they labelled the mesh that was)
+  release_mesh_texture_taps(c);
+  if (n_vertices) *n_vertices = M.nv;
+  if (n_triangles) *n_triangles = M.nt;
+  return TSDF_OK;
+}
+int32_t tsdf_mesh_keep_components(tsdf_ctx* c, const uint8_t* keep, uint64_t* n_vertices, uint64_t* n_triangles) {
+  CHECK_CTX(c);
+  if (!keep) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "null keep");
+  return mesh_keep(c, keep, 0u, n_vertices, n_triangles);
+}
+int32_t tsdf_mesh_filter_components(tsdf_ctx* c, uint32_t min_triangles, uint64_t* n_vertices, uint64_t* n_triangles) {
+  CHECK_CTX(c);
+  return mesh_keep(c, nullptr, min_triangles, n_vertices, n_triangles);
+}
+int32_t tsdf_mesh_component_stats(tsdf_ctx* c, uint64_t out[4]) {
+  CHECK_CTX(c);
+  if (!out) return TSDF_ERR_INVALID_ARGUMENT;
+  if (!c->mesh.valid) FAIL(c, TSDF_ERR_STATE, "no mesh (tsdf_mesh_extract / tsdf_mesh_extract_lod)");
+  const tsdf_ctx::MeshComponents& K = c->mcomp;
+  out[0] = K.n; out[1] = K.largest; out[2] = K.removed_vertices; out[3] = K.removed_triangles;
   return TSDF_OK;
 }
 

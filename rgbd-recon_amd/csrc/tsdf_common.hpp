@@ -386,6 +386,24 @@ void launch_mesh_stream_header(hipStream_t st, const MeshScratch& S, MeshStreamH
 // flags: TSDF_MESH_NORMALS | TSDF_MESH_COLOURS; payload: packed vertices (8 bytes each, 16 with a flag), then the triangles
 void launch_mesh_stream_emit(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S, uint32_t flags,
                              const MeshStreamHeader* H, uint32_t* records, void* payload);
+// mesh components (k_mesh_components.hip): the mesh arrays alone are read, so neither the volume nor a level appears.  Every scan works on `sums`:
+// mesh_cc_scan_blocks(n) + 1 64-bit words for n elements, the last of them the total once the launcher's work is done.
+struct MeshArrays { float* pos; float* nrm; float* col; uint32_t* tri; };   // nrm / col: null where the extract produced none
+int mesh_cc_scan_blocks(size_t n);
+// union-find over parent[nv] (scratch), label[v] = the smallest vertex index of v's component, sums (of nv) = the roots' scan: sums[blocks] = components
+void launch_mesh_cc_label(hipStream_t st, const uint32_t* tri, uint32_t nv, size_t nt, uint32_t* parent, uint32_t* label, unsigned long long* sums);
+// vertex_component: the labels on entry, the component indices on return; rank: nv words of scratch (parent may serve again); table: n_components
+// entries, written whole; largest: one word, zero on entry, the largest n_triangles on return
+void launch_mesh_cc_number(hipStream_t st, const uint32_t* tri, uint32_t nv, size_t nt, const unsigned long long* sums, uint32_t n_components, uint32_t* rank,
+                           uint32_t* vertex_component, uint32_t* triangle_component, tsdf_mesh_component* table, uint32_t* largest);
+void launch_mesh_cc_keep_from_table(hipStream_t st, const tsdf_mesh_component* table, uint32_t n_components, uint32_t min_triangles, uint8_t* keep);
+// the kept counts: vertex_sums[blocks(nv)] and triangle_sums[blocks(nt)] ...
+void launch_mesh_cc_keep_count(hipStream_t st, const uint8_t* keep, const uint32_t* vertex_component, const uint32_t* triangle_component, uint32_t nv, size_t nt,
+                               unsigned long long* vertex_sums, unsigned long long* triangle_sums);
+// ... and the scatter into arrays of exactly those sizes; new_index: nv words of scratch
+void launch_mesh_cc_keep_scatter(hipStream_t st, const uint8_t* keep, const uint32_t* vertex_component, const uint32_t* triangle_component, uint32_t nv, size_t nt,
+                                 const unsigned long long* vertex_sums, const unsigned long long* triangle_sums, const MeshArrays& src, const MeshArrays& dst,
+                                 uint32_t* new_index);
 // ray queries (k_rays.hip): one launch pair serves at most kRayChunk rays -- the capacity of the context's hit list
 constexpr uint32_t kRayChunk = 1u << 18;
 struct RayCast {

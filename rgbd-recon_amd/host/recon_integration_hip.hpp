@@ -194,6 +194,51 @@ class ReconIntegrationHip {
                              out.triangles.data()));
   }
   void writeMeshPly(const char* path) { check(tsdf_mesh_write_ply(m_ctx, path)); }
+  // ---- the mesh's islands (tsdf_mesh_components).  The reference has no counterpart.  meshComponents labels the connected components of the last
+  // extractMesh (by index; numbered by smallest vertex) and returns their number; downloadMeshComponents copies the labels and the 16-byte table;
+  // keepMeshComponents / filterMeshComponents / keepLargestMeshComponents replace the mesh with the kept part -- downloadMesh and writeMeshPly serve it
+  // from then on, the labels and the mesh's texture taps are gone until meshComponents / meshTextureTaps run again.
+  struct MeshComponents { std::vector<std::uint32_t> vertex_component, triangle_component; std::vector<tsdf_mesh_component> table; };
+  struct MeshComponentStats { std::uint64_t components = 0, largest_triangles = 0, vertices_removed = 0, triangles_removed = 0; };
+  std::uint64_t meshComponents() {
+    std::uint64_t n = 0;
+    check(tsdf_mesh_components(m_ctx, &n));
+    return n;
+  }
+  void downloadMeshComponents(MeshComponents& out) {
+    check(tsdf_mesh_download_components(m_ctx, nullptr, nullptr, nullptr));   // (throws without components of the current mesh)
+    out.vertex_component.resize((std::size_t)m_mesh.vertices);
+    out.triangle_component.resize((std::size_t)m_mesh.triangles);
+    out.table.resize((std::size_t)meshComponentStats().components);
+    check(tsdf_mesh_download_components(m_ctx, out.vertex_component.data(), out.triangle_component.data(), out.table.data()));
+  }
+  MeshCounts keepMeshComponents(const std::vector<std::uint8_t>& keep) {   // keep[c] != 0: component c stays; one entry per component
+    if (keep.size() != meshComponentStats().components) throw std::invalid_argument("ReconIntegrationHip: one keep flag per component");
+    const std::uint8_t none = 0;                                           // (no component: still a non-null pointer)
+    check(tsdf_mesh_keep_components(m_ctx, keep.empty() ? &none : keep.data(), &m_mesh.vertices, &m_mesh.triangles));
+    return m_mesh;
+  }
+  MeshCounts filterMeshComponents(std::uint32_t min_triangles) {           // keeps the components with at least min_triangles triangles
+    check(tsdf_mesh_filter_components(m_ctx, min_triangles, &m_mesh.vertices, &m_mesh.triangles));
+    return m_mesh;
+  }
+  MeshCounts keepLargestMeshComponents(std::size_t k = 1) {                // the k components with the most triangles; ties: the lower index first
+    MeshComponents comps;
+    downloadMeshComponents(comps);
+    std::vector<std::uint8_t> keep(comps.table.size(), 0);
+    for (std::size_t n = 0; n < k && n < keep.size(); ++n) {
+      std::size_t best = keep.size();
+      for (std::size_t c = 0; c < keep.size(); ++c)
+        if (!keep[c] && (best == keep.size() || comps.table[c].n_triangles > comps.table[best].n_triangles)) best = c;
+      keep[best] = 1;
+    }
+    return keepMeshComponents(keep);
+  }
+  MeshComponentStats meshComponentStats() {
+    std::uint64_t s[4] = {0, 0, 0, 0};
+    check(tsdf_mesh_component_stats(m_ctx, s));
+    return MeshComponentStats{s[0], s[1], s[2], s[3]};
+  }
   // ---- the same surface EVERY frame (tsdf_mesh_stream): packed vertices and uint32 triangles through a ring of pinned buffers, queued behind the frame
   // like present().  The reference has no counterpart.  configureMeshStream before the first frame: attributes, capacities (vertices, triangles, 8^3
   // tiles with surface; a frame that needs more comes back with overflow set and no geometry) and 2..8 slots.

@@ -5,7 +5,10 @@ this tool's own on the context's stream (tile-major -> linear launch + the 512 M
 one JSON line; with a file argument, also writes it to that file.
 --level L[,L..] (0, 1, 2; default 0): the levels of detail to time (tsdf_mesh_extract_lod), alternating call by call in this one process so that every
 level sees the same machine; the record then has a "levels" entry with each level's stages, the spread of its device time over the N calls, its counts
-and its mesh bytes.  The top-level entries stay those of the first level named."""
+and its mesh bytes.  The top-level entries stay those of the first level named.
+--components: after that, N times extract (every attribute, the first level named) + tsdf_mesh_components, and with --min-triangles M also
+tsdf_mesh_filter_components(M): the record gets a "components" entry with the timers "mesh_components" and "mesh_filter" (each the sum of its call's two
+samples: the host sizes an allocation between them) beside mesh_count / mesh_scan / mesh_emit of the same extracts, and the counts."""
 import sys, os, json, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch  # noqa: F401  (torch first: the library binds to the HIP runtime torch loaded)
@@ -15,7 +18,9 @@ N = 10
 STAGES = ("mesh_count", "mesh_scan", "mesh_emit")
 ARGS = sys.argv[1:]
 LEVELS = [int(x) for x in ARGS[ARGS.index("--level") + 1].split(",")] if "--level" in ARGS else [0]
-OUT = [a for i, a in enumerate(ARGS) if not a.startswith("--") and (i == 0 or ARGS[i - 1] != "--level")]
+COMPONENTS = "--components" in ARGS or "--min-triangles" in ARGS
+MIN_TRIANGLES = int(ARGS[ARGS.index("--min-triangles") + 1]) if "--min-triangles" in ARGS else None
+OUT = [a for i, a in enumerate(ARGS) if not a.startswith("--") and (i == 0 or ARGS[i - 1] not in ("--level", "--min-triangles"))]
 
 scene = rr.scene.make_scene(n_streams=4, width=640, height=480, lut_res=128, inv_res=128)
 ext = scene["bbox_max"] - scene["bbox_min"]
@@ -25,7 +30,7 @@ mv, pr = rr.scene.default_view(*VIEW)
 hip.clearOccupiedBricks(); hip.markBricks(); hip.updateOccupiedBricks(); hip.integrate(); hip.drawF(mv, pr)
 hip.sync()
 hip.enable_timers(True)
-hip.set_timer_filter(list(STAGES) + ["volume_download"])
+hip.set_timer_filter(list(STAGES) + ["volume_download", "mesh_components", "mesh_filter"])
 rec = dict(shape="c2", res=list(hip.res), streams=4)
 levels = {L: {} for L in LEVELS}
 for label, kw in (("positions", dict(normals=False, colours=False)), ("all_attributes", dict(normals=True, colours=True))):
@@ -62,6 +67,26 @@ rec.update(level=LEVELS[0], vertices=first["vertices"], triangles=first["triangl
            tiles_skipped=first["tiles_skipped"], tiles_with_surface=first["tiles_with_surface"])
 if "--level" in ARGS:
     rec["levels"] = {str(L): levels[L] for L in LEVELS}
+if COMPONENTS:
+    names = STAGES + ("mesh_components",) + (("mesh_filter",) if MIN_TRIANGLES is not None else ())
+    ms = {s: [] for s in names}
+    comp = dict(level=LEVELS[0])
+    for it in range(N + 1):                                              # (the first turn is a warm-up)
+        hip.extract_mesh(level=LEVELS[0], normals=True, colours=True)
+        comp["components"] = hip.mesh_components()
+        comp.update(largest_triangles=hip.mesh_component_stats()["largest_triangles"])
+        if MIN_TRIANGLES is not None:
+            comp["kept_vertices"], comp["kept_triangles"] = hip.mesh_filter(MIN_TRIANGLES)
+            st = hip.mesh_component_stats()
+            comp.update(min_triangles=MIN_TRIANGLES, vertices_removed=st["vertices_removed"], triangles_removed=st["triangles_removed"])
+        for s in names:
+            cnt, total = hip.timer_stats(s)                              # (the samples of this turn alone: timer_stats resets them)
+            if it:
+                ms[s].append(total)
+    for s in names:
+        comp[s + "_ms"], comp[s + "_ms_min"], comp[s + "_ms_max"] = float(np.mean(ms[s])), float(np.min(ms[s])), float(np.max(ms[s]))
+    comp["extract_ms"] = sum(comp[s + "_ms"] for s in STAGES)
+    rec["components"] = comp
 hip.tsdf()
 hip.timer_stats("volume_download")
 t0 = time.perf_counter()
