@@ -86,13 +86,42 @@ void release_view(tsdf_ctx* c) {
 }
 // the read-out ring's buffers and events (nothing may be in flight: an idle ring, or behind a synchronisation of both streams)
 void release_present(tsdf_ctx* c) {
-  for (auto& S : c->present_ring) {
+  for (auto& S : c->present.slot) {
     hipFree(S.dev); if (S.host) hipHostFree(S.host);
     if (S.converted) hipEventDestroy(S.converted);
     if (S.ready) hipEventDestroy(S.ready);
     S = tsdf_ctx::PresentSlot{};
   }
-  c->present_bytes = 0; c->present_head = 0; c->present_count = 0; c->present_held = false;
+  c->present.bytes = 0; c->present.ring.reset();
+}
+// the copy stream: made by whichever of the asynchronous upload, the frame read-out and the mesh stream needs it first
+int32_t ensure_copy_stream(tsdf_ctx* c) { if (!c->copy_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking)); return TSDF_OK; }
+// Has the copy stream reached `e`?  wait: the host waits for it; otherwise it asks, and *reached = false while the result is still travelling ("not
+// ready" is no error: it must not stay behind as the thread's last one)
+int32_t event_reached(tsdf_ctx* c, hipEvent_t e, bool wait, bool* reached) {
+  const hipError_t rc = wait ? hipEventSynchronize(e) : hipEventQuery(e);
+  *reached = rc == hipSuccess;
+  if (!wait && rc == hipErrorNotReady) { (void)hipGetLastError(); return TSDF_OK; }
+  HIP_TRY(c, rc);
+  return TSDF_OK;
+}
+// {bbox_min, extent} of the volume's box, as the ray queries and the texture taps map between world coordinates and the unit cube
+void box_origin_extent(const tsdf_ctx* c, float lo[3], float ext[3]) { for (int a = 0; a < 3; ++a) { lo[a] = c->cfg.bbox_min[a]; ext[a] = c->cfg.bbox_max[a] - lo[a]; } }
+// Grow the staging of a call's synchronous form to n elements (nothing queued reads it: every call that uses it synchronises): `in` and `out` by the one
+// capacity, `extra` by its own when the call wants it; *_bytes per element
+int32_t staging_reserve(tsdf_ctx* c, CallStaging& G, uint64_t n, bool want_extra, void** in, uint64_t in_bytes, void** out, uint64_t out_bytes, void** extra, uint64_t extra_bytes) {
+  if (const uint64_t cap = G.grow(n)) {
+    hipFree(*in); hipFree(*out); *in = nullptr; *out = nullptr; G.grown(0);
+    HIP_TRY(c, hipMalloc(in, (size_t)(cap * in_bytes)));
+    HIP_TRY(c, hipMalloc(out, (size_t)(cap * out_bytes)));
+    G.grown(cap);
+  }
+  if (const uint64_t cap = G.grow_extra(n, want_extra)) {
+    hipFree(*extra); *extra = nullptr; G.extra_grown(0);
+    HIP_TRY(c, hipMalloc(extra, (size_t)(cap * extra_bytes)));
+    G.extra_grown(cap);
+  }
+  return TSDF_OK;
 }
 void release_bricks(tsdf_ctx* c) {
   for (int k = 0; k < 2; ++k) { hipFree(c->d_counters[k]); hipFree(c->d_flags[k]); hipFree(c->d_occupied[k]); c->d_counters[k] = nullptr; c->d_flags[k] = nullptr; c->d_occupied[k] = nullptr; }
@@ -618,18 +647,31 @@ void release_mesh(tsdf_ctx* c) {
   release_mesh_components(c);
   c->mcomp = tsdf_ctx::MeshComponents{};
 }
+// What the mesh launches need besides their output, per lattice tile of `level`: six arrays (the lattice-point records are sized by each caller: from the
+// counts, or from the stream's capacity).  The first error, or hipSuccess with what the six take added to *bytes (may be null).
+hipError_t mesh_scratch_allocate(MeshScratch& S, int n_tiles, int level, uint64_t* bytes) {
+  const size_t n = (size_t)n_tiles;
+  S.n_tiles = n_tiles; S.level = level;
+  const struct { void** p; size_t bytes; } arrays[6] = {
+    {(void**)&S.tile_cnt, n * sizeof(uint2)}, {(void**)&S.tile_skip, n}, {(void**)&S.tile_vbase, n * sizeof(uint32_t)}, {(void**)&S.tile_tbase, n * sizeof(unsigned long long)},
+    {(void**)&S.tile_rec, n * sizeof(uint32_t)}, {(void**)&S.sums, (size_t)(mesh_scan_blocks(n_tiles) + 1) * 4 * sizeof(uint64_t)}};
+  for (const auto& A : arrays) { if (const hipError_t e = hipMalloc(A.p, A.bytes)) return e; if (bytes) *bytes += A.bytes; }
+  return hipSuccess;
+}
+void mesh_scratch_free(MeshScratch& S, uint32_t*& records) {            // ... and the records
+  hipFree(S.tile_cnt); hipFree(S.tile_skip); hipFree(S.tile_vbase); hipFree(S.tile_tbase); hipFree(S.tile_rec); hipFree(S.sums); hipFree(records);
+  S = MeshScratch{}; records = nullptr;
+}
 // the mesh ring's slots and scratch (nothing may be in flight: an idle ring, or behind a synchronisation of the streams); the configuration stays
 void release_mesh_stream(tsdf_ctx* c) {
   tsdf_ctx::MeshStream& R = c->mstream;
-  for (auto& S : R.ring) {
+  for (auto& S : R.slot) {
     hipFree(S.dev); if (S.host) hipHostFree(S.host);
     for (hipEvent_t e : {S.header_written, S.emitted, S.header_ready, S.ready}) if (e) hipEventDestroy(e);
     S = tsdf_ctx::MeshStreamSlot{};
   }
-  MeshScratch& T = R.scratch;
-  hipFree(T.tile_cnt); hipFree(T.tile_skip); hipFree(T.tile_vbase); hipFree(T.tile_tbase); hipFree(T.tile_rec); hipFree(T.sums); hipFree(R.records);
-  T = MeshScratch{}; R.records = nullptr;
-  R.allocated = false; R.head = 0; R.count = 0; R.held = false; R.device_bytes = 0;
+  mesh_scratch_free(R.scratch, R.records);
+  R.allocated = false; R.ring.reset(); R.device_bytes = 0;
 }
 void release_volume(tsdf_ctx* c) {
   release_mesh(c); c->have_volume = false;                             // (a mesh belongs to the grid it was extracted from)
@@ -1129,7 +1171,7 @@ static int32_t ensure_async_upload(tsdf_ctx* c) {
   if (int32_t rc = alloc_frame_slot(c, 0)) return rc;
   if (int32_t rc = alloc_frame_slot(c, 1)) return rc;
   HIP_TRY(c, sync_ctx(c));                             // the new slot's colour memset
-  if (!c->copy_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));   // (the frame read-out may have made it already)
+  if (int32_t rc = ensure_copy_stream(c)) return rc;   // (the frame read-out may have made it already)
   c->async_upload_ready = true;
   return TSDF_OK;
 }
@@ -2200,7 +2242,7 @@ int32_t tsdf_set_voxel_size(tsdf_ctx* c, float size) {
     res[a] = (int)ceilf((c->cfg.bbox_max[a] - c->cfg.bbox_min[a]) / size);
     if (res[a] < 1 || res[a] > 4096) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "volume resolution out of range [1, 4096]");
   }
-  if (c->mstream.count) FAIL(c, TSDF_ERR_STATE, "%u streamed mesh frame(s) are queued or held: acquire and release them before the grid changes", c->mstream.count);
+  if (!c->mstream.ring.idle()) FAIL(c, TSDF_ERR_STATE, "%u streamed mesh frame(s) are queued or held: acquire and release them before the grid changes", c->mstream.ring.count);
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, sync_ctx(c));
   const int old_res[3] = {c->res[0], c->res[1], c->res[2]};
@@ -2258,7 +2300,7 @@ int32_t tsdf_set_brick_size(tsdf_ctx* c, const float size[3]) {
 }
 int32_t tsdf_resize(tsdf_ctx* c, uint32_t w, uint32_t h) {
   CHECK_CTX(c);
-  if (c->present_count) FAIL(c, TSDF_ERR_STATE, "%u presented frame(s) are queued or held: acquire and release them before the view changes size", c->present_count);
+  if (!c->present.ring.idle()) FAIL(c, TSDF_ERR_STATE, "%u presented frame(s) are queued or held: acquire and release them before the view changes size", c->present.ring.count);
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, sync_ctx(c));
   int32_t rc = setup_view(c, w, h);
@@ -2414,12 +2456,23 @@ int32_t tsdf_download_atlas(tsdf_ctx* c, float* rgba, float* depth) {
 
 // ---- mesh extraction (k_mesh.hip; the definition is in the header).  The reference has no counterpart: it is built on the raymarch's hit test
 // (tsdf_raymarch.fs:96), get_gradient (:140-149), blendColors (:295-330) and vol_to_world / NormalMatrix (recon_integration.cpp:66-72,199).
-namespace {
-struct MeshTemp {                                                         // what one extract allocates besides the mesh: freed when it returns
-  MeshScratch s{}; uint32_t* records = nullptr;
-  ~MeshTemp() { hipFree(s.tile_cnt); hipFree(s.tile_skip); hipFree(s.tile_vbase); hipFree(s.tile_tbase); hipFree(s.tile_rec); hipFree(s.sums); hipFree(records); }
-};
+namespace {                                                               // what one extract allocates besides the mesh: freed when it returns
+struct MeshTemp { MeshScratch s{}; uint32_t* records = nullptr; ~MeshTemp() { mesh_scratch_free(s, records); } };
 }  // namespace
+static MeshGeometry mesh_geometry(const tsdf_ctx* c) {
+  const float* lo = c->cfg.bbox_min; const float* hi = c->cfg.bbox_max;
+  return MeshGeometry{{lo[0], lo[1], lo[2]}, {hi[0], hi[1], hi[2]}};
+}
+static uint64_t mesh_storage_bytes(const tsdf_ctx::Mesh& M) {
+  return M.nv * (3 + ((M.flags & TSDF_MESH_NORMALS) ? 3 : 0) + ((M.flags & TSDF_MESH_COLOURS) ? 4 : 0)) * sizeof(float) + M.nt * 3 * sizeof(uint32_t);
+}
+// May a call read the fused volume (the extract, the mesh stream, a cast)?  The whole volume on this context, written at least once; with colours also
+// calibration and a frame.  on_a_slab: what the call says on a Z-slab context
+static int32_t readable_volume_check(tsdf_ctx* c, const char* on_a_slab, bool wants_colour) {
+  if (!whole_volume(c)) FAIL(c, TSDF_ERR_STATE, "%s", on_a_slab);
+  if (!c->have_volume) FAIL(c, TSDF_ERR_STATE, "no volume yet (tsdf_integrate or tsdf_upload_volume)");
+  return wants_colour ? require_inputs(c, false, true) : TSDF_OK;
+}
 int32_t tsdf_mesh_extract(tsdf_ctx* c, uint32_t flags, uint64_t* n_vertices, uint64_t* n_triangles) { return tsdf_mesh_extract_lod(c, flags, 0u, n_vertices, n_triangles); }
 // one extract at a level of detail: level 0 is the voxel lattice (what tsdf_mesh_extract runs), level L the lattice of every (1 << L)-th voxel.  Everything
 // per tile -- scratch, scan, records, stats -- is per LATTICE tile of that level.
@@ -2427,10 +2480,7 @@ int32_t tsdf_mesh_extract_lod(tsdf_ctx* c, uint32_t flags, uint32_t level, uint6
   CHECK_CTX(c);
   if (flags & ~(TSDF_MESH_NORMALS | TSDF_MESH_COLOURS)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "unknown mesh flag");
   if (level > (uint32_t)kMeshMaxLevel) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "mesh level %u (0 .. %d: every voxel, every 2nd, every 4th)", level, kMeshMaxLevel);
-  if (!whole_volume(c)) FAIL(c, TSDF_ERR_STATE, "tsdf_mesh_extract on a Z-slab context: welding slab meshes is not provided");
-  if (!c->have_volume) FAIL(c, TSDF_ERR_STATE, "no volume yet (tsdf_integrate or tsdf_upload_volume)");
-  int32_t rc;
-  if ((flags & TSDF_MESH_COLOURS) && (rc = require_inputs(c, false, true))) return rc;
+  if (int32_t rc = readable_volume_check(c, "tsdf_mesh_extract on a Z-slab context: welding slab meshes is not provided", (flags & TSDF_MESH_COLOURS) != 0)) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   release_mesh(c);                                                       // (nothing queued reads it: extract and download synchronise)
   tsdf_ctx::Mesh& M = c->mesh;
@@ -2442,13 +2492,7 @@ int32_t tsdf_mesh_extract_lod(tsdf_ctx* c, uint32_t flags, uint32_t level, uint6
   MeshTemp tmp;
   if (L.cr[0] >= 2 && L.cr[1] >= 2 && L.cr[2] >= 2) {                   // (a lattice one point thick has no cell)
     MeshScratch& S = tmp.s;
-    S.n_tiles = n_tiles; S.level = (int)level;
-    HIP_TRY(c, hipMalloc((void**)&S.tile_cnt, (size_t)n_tiles * sizeof(uint2)));
-    HIP_TRY(c, hipMalloc((void**)&S.tile_skip, (size_t)n_tiles));
-    HIP_TRY(c, hipMalloc((void**)&S.tile_vbase, (size_t)n_tiles * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc((void**)&S.tile_tbase, (size_t)n_tiles * sizeof(unsigned long long)));
-    HIP_TRY(c, hipMalloc((void**)&S.tile_rec, (size_t)n_tiles * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc(&S.sums, (size_t)(nb + 1) * sizeof(totals)));
+    HIP_TRY(c, mesh_scratch_allocate(S, n_tiles, (int)level, nullptr));
     HIP_TRY(c, join_integ(c));                                           // the volume tsdf_download_volume would return now
     if (flags & TSDF_MESH_COLOURS) HIP_TRY(c, join_pre(c));              // ... and the current frame slot's images
     timer_begin(c, "mesh_count");
@@ -2468,10 +2512,8 @@ int32_t tsdf_mesh_extract_lod(tsdf_ctx* c, uint32_t flags, uint32_t level, uint6
       if (ok && (flags & TSDF_MESH_NORMALS)) ok = hipMalloc((void**)&M.nrm, nv * 3 * sizeof(float)) == hipSuccess;
       if (ok && (flags & TSDF_MESH_COLOURS)) ok = hipMalloc((void**)&M.col, nv * 4 * sizeof(float)) == hipSuccess;
       if (!ok) { (void)hipGetLastError(); release_mesh(c); FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "no device memory for a mesh of %zu vertices and %zu triangles", nv, nt); }
-      const float* lo = c->cfg.bbox_min; const float* hi = c->cfg.bbox_max;
-      const MeshGeometry G{{lo[0], lo[1], lo[2]}, {hi[0], hi[1], hi[2]}};
       timer_begin(c, "mesh_emit");
-      launch_mesh_emit(c->stream, V, c->luts, c->frame, G, S, tmp.records, M.pos, M.nrm, M.col, M.tri);
+      launch_mesh_emit(c->stream, V, c->luts, c->frame, mesh_geometry(c), S, tmp.records, M.pos, M.nrm, M.col, M.tri);
       timer_end(c, "mesh_emit");
       HIP_TRY(c, hipGetLastError());
       HIP_TRY(c, sync_ctx(c));
@@ -2479,7 +2521,7 @@ int32_t tsdf_mesh_extract_lod(tsdf_ctx* c, uint32_t flags, uint32_t level, uint6
   }
   M.nv = totals[0]; M.nt = totals[1]; M.valid = true;
   M.stats[1] = totals[3]; M.stats[2] = totals[2];
-  M.stats[3] = M.nv * (3 + ((flags & TSDF_MESH_NORMALS) ? 3 : 0) + ((flags & TSDF_MESH_COLOURS) ? 4 : 0)) * sizeof(float) + M.nt * 3 * sizeof(uint32_t);
+  M.stats[3] = mesh_storage_bytes(M);
   if (n_vertices) *n_vertices = M.nv;
   if (n_triangles) *n_triangles = M.nt;
   return TSDF_OK;
@@ -2642,7 +2684,7 @@ static int32_t mesh_keep(tsdf_ctx* c, const uint8_t* keep_host, uint32_t min_tri
   }
   K.removed_vertices = M.nv - kept_v; K.removed_triangles = M.nt - kept_t;
   M.nv = kept_v; M.nt = kept_t;
-  M.stats[3] = M.nv * (3 + ((M.flags & TSDF_MESH_NORMALS) ? 3 : 0) + ((M.flags & TSDF_MESH_COLOURS) ? 4 : 0)) * sizeof(float) + M.nt * 3 * sizeof(uint32_t);
+  M.stats[3] = mesh_storage_bytes(M);
   release_mesh_components(c);                                            // (they labelled the mesh that was)
   release_mesh_texture_taps(c);
   if (n_vertices) *n_vertices = M.nv;
@@ -2676,17 +2718,17 @@ int32_t tsdf_mesh_stream_config_lod(tsdf_ctx* c, uint32_t flags, uint32_t level,
   CHECK_CTX(c);
   tsdf_ctx::MeshStream& R = c->mstream;
   if (level > (uint32_t)kMeshMaxLevel) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "mesh level %u (0 .. %d: every voxel, every 2nd, every 4th)", level, kMeshMaxLevel);
-  if ((flags & ~(TSDF_MESH_NORMALS | TSDF_MESH_COLOURS)) || !max_vertices || !max_triangles || !max_surface_tiles || slots < 2 || slots > tsdf_ctx::MeshStream::kMaxSlots)
+  if ((flags & ~(TSDF_MESH_NORMALS | TSDF_MESH_COLOURS)) || !max_vertices || !max_triangles || !max_surface_tiles || slots < 2 || slots > kMaxResultSlots)
     FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "mesh stream flags %u / capacities %u vertices, %u triangles, %u tiles / slots %u (flags 1 normals, 2 colours; capacities > 0; 2..%u slots)",
-         flags, max_vertices, max_triangles, max_surface_tiles, slots, tsdf_ctx::MeshStream::kMaxSlots);
+         flags, max_vertices, max_triangles, max_surface_tiles, slots, kMaxResultSlots);
   if ((uint64_t)max_vertices * (flags ? 16 : 8) + (uint64_t)max_triangles * 12 > (4ull << 30)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "a mesh stream slot of more than 4 GiB");
-  if (R.count) FAIL(c, TSDF_ERR_STATE, "%u streamed mesh frame(s) are queued or held: acquire and release them first", R.count);
+  if (!R.ring.idle()) FAIL(c, TSDF_ERR_STATE, "%u streamed mesh frame(s) are queued or held: acquire and release them first", R.ring.count);
   HIP_TRY(c, hipSetDevice(c->device));
   // The ring is idle for the copies only (each was waited for before its frame was released): a frame that overflowed or had no payload was handed out
   // behind its header copy alone, and its emit launches, which read the slot's device header and the scratch, may still be queued on the context's stream.
   if (R.allocated) HIP_TRY(c, hipStreamSynchronize(c->stream));
   release_mesh_stream(c);
-  R.flags = flags; R.level = level; R.max_vertices = max_vertices; R.max_triangles = max_triangles; R.max_tiles = max_surface_tiles; R.slots = slots; R.configured = true;
+  R.flags = flags; R.level = level; R.max_vertices = max_vertices; R.max_triangles = max_triangles; R.max_tiles = max_surface_tiles; R.ring.configure(slots); R.configured = true;
   R.frames = R.overflowed = R.bytes_copied = 0;
   return TSDF_OK;
 }
@@ -2701,21 +2743,17 @@ int32_t tsdf_mesh_stream_level(tsdf_ctx* c, uint32_t* level) {
 static int32_t mesh_stream_allocate(tsdf_ctx* c) {
   tsdf_ctx::MeshStream& R = c->mstream;
   const MeshLattice L = mesh_lattice(c->vol.res, (int)R.level);
-  const size_t n_tiles = (size_t)L.ntx * L.nty * L.ntz, nb = (size_t)mesh_scan_blocks((int)n_tiles), slot_bytes = sizeof(MeshStreamHeader) + mesh_stream_payload_capacity(R);
-  MeshScratch& T = R.scratch;
-  T.n_tiles = (int)n_tiles; T.level = (int)R.level;
-  bool ok = hipMalloc((void**)&T.tile_cnt, n_tiles * sizeof(uint2)) == hipSuccess && hipMalloc((void**)&T.tile_skip, n_tiles) == hipSuccess &&
-            hipMalloc((void**)&T.tile_vbase, n_tiles * sizeof(uint32_t)) == hipSuccess && hipMalloc((void**)&T.tile_tbase, n_tiles * sizeof(unsigned long long)) == hipSuccess &&
-            hipMalloc((void**)&T.tile_rec, n_tiles * sizeof(uint32_t)) == hipSuccess && hipMalloc(&T.sums, (nb + 1) * 4 * sizeof(uint64_t)) == hipSuccess &&
-            hipMalloc((void**)&R.records, (size_t)R.max_tiles * 512 * sizeof(uint32_t)) == hipSuccess;
-  for (uint32_t k = 0; ok && k < R.slots; ++k) {
-    tsdf_ctx::MeshStreamSlot& S = R.ring[k];
+  const size_t n_tiles = (size_t)L.ntx * L.nty * L.ntz, slot_bytes = sizeof(MeshStreamHeader) + mesh_stream_payload_capacity(R), record_bytes = (size_t)R.max_tiles * 512 * sizeof(uint32_t);
+  uint64_t bytes = (uint64_t)R.ring.slots * slot_bytes + record_bytes;
+  bool ok = mesh_scratch_allocate(R.scratch, (int)n_tiles, (int)R.level, &bytes) == hipSuccess && hipMalloc((void**)&R.records, record_bytes) == hipSuccess;
+  for (uint32_t k = 0; ok && k < R.ring.slots; ++k) {
+    tsdf_ctx::MeshStreamSlot& S = R.slot[k];
     ok = hipMalloc((void**)&S.dev, slot_bytes) == hipSuccess && hipHostMalloc((void**)&S.host, slot_bytes, hipHostMallocDefault) == hipSuccess;
     for (hipEvent_t* e : {&S.header_written, &S.emitted, &S.header_ready, &S.ready}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
   }
-  if (ok && !c->copy_stream) ok = hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) == hipSuccess;   // (as ensure_async_upload makes it)
-  if (!ok) { (void)hipGetLastError(); release_mesh_stream(c); FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "no memory for %u mesh stream slots of %zu bytes and the scratch of %zu tiles", R.slots, slot_bytes, n_tiles); }
-  R.device_bytes = (uint64_t)R.slots * slot_bytes + n_tiles * (sizeof(uint2) + 1 + 4 + 8 + 4) + (nb + 1) * 4 * sizeof(uint64_t) + (uint64_t)R.max_tiles * 512 * sizeof(uint32_t);
+  if (ok) ok = ensure_copy_stream(c) == TSDF_OK;
+  if (!ok) { (void)hipGetLastError(); release_mesh_stream(c); FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "no memory for %u mesh stream slots of %zu bytes and the scratch of %zu tiles", R.ring.slots, slot_bytes, n_tiles); }
+  R.device_bytes = bytes;
   R.allocated = true;
   return TSDF_OK;
 }
@@ -2723,12 +2761,12 @@ static int32_t mesh_stream_allocate(tsdf_ctx* c) {
 // travelling nothing has arrived either).  Host side this is event queries only.
 static int32_t mesh_stream_pump(tsdf_ctx* c) {
   tsdf_ctx::MeshStream& R = c->mstream;
-  for (uint32_t k = 0; k < R.count; ++k) {
-    tsdf_ctx::MeshStreamSlot& S = R.ring[(R.head + k) % R.slots];
+  for (uint32_t k = 0; k < R.ring.count; ++k) {
+    tsdf_ctx::MeshStreamSlot& S = R.slot[R.ring.queued(k)];
     if (S.payload_issued) continue;
-    const hipError_t e = hipEventQuery(S.header_ready);
-    if (e == hipErrorNotReady) { (void)hipGetLastError(); break; }       // ("not ready" is no error: it must not stay behind as the thread's last one)
-    HIP_TRY(c, e);
+    bool arrived;
+    if (int32_t rc = event_reached(c, S.header_ready, false, &arrived)) return rc;
+    if (!arrived) break;                                                 // (behind a header still travelling nothing has arrived either)
     const MeshStreamHeader* H = (const MeshStreamHeader*)S.host;
     S.payload_bytes = (size_t)H->n_vertices * (R.flags ? 16 : 8) + (size_t)H->n_triangles * 12;
     if (S.payload_bytes) {
@@ -2746,15 +2784,15 @@ int32_t tsdf_mesh_stream(tsdf_ctx* c, uint64_t tag) {
   CHECK_CTX(c);
   tsdf_ctx::MeshStream& R = c->mstream;
   if (!R.configured) FAIL(c, TSDF_ERR_STATE, "tsdf_mesh_stream before tsdf_mesh_stream_config");
-  if (!whole_volume(c)) FAIL(c, TSDF_ERR_STATE, "tsdf_mesh_stream on a Z-slab context: welding slab meshes is not provided");
-  if (!c->have_volume) FAIL(c, TSDF_ERR_STATE, "no volume yet (tsdf_integrate or tsdf_upload_volume)");
   int32_t rc;
-  if ((R.flags & TSDF_MESH_COLOURS) && (rc = require_inputs(c, false, true))) return rc;
-  if (R.count >= R.slots) FAIL(c, TSDF_ERR_STATE, "all %u mesh stream slots are queued or held (tsdf_mesh_stream_acquire / tsdf_mesh_stream_release)", R.slots);
+  if ((rc = readable_volume_check(c, "tsdf_mesh_stream on a Z-slab context: welding slab meshes is not provided", (R.flags & TSDF_MESH_COLOURS) != 0))) return rc;
+  if (R.ring.full()) FAIL(c, TSDF_ERR_STATE, "all %u mesh stream slots are queued or held (tsdf_mesh_stream_acquire / tsdf_mesh_stream_release)", R.ring.slots);
   HIP_TRY(c, hipSetDevice(c->device));
   if (!R.allocated && (rc = mesh_stream_allocate(c))) return rc;
   if ((rc = mesh_stream_pump(c))) return rc;
-  tsdf_ctx::MeshStreamSlot& S = R.ring[(R.head + R.count) % R.slots];
+  tsdf_ctx::MeshStreamSlot& S = R.slot[R.ring.push()];                   // (queued before its calls are: result_paths.hpp's transitions precede what acts on them)
+  S.tag = tag; S.payload_issued = false; S.payload_bytes = 0;
+  for (int a = 0; a < 3; ++a) S.res[a] = c->res[a];
   MeshStreamHeader* H = (MeshStreamHeader*)S.dev;
   const Volume& V = c->vol;
   const MeshLattice L = mesh_lattice(V.res, (int)R.level);
@@ -2776,10 +2814,8 @@ int32_t tsdf_mesh_stream(tsdf_ctx* c, uint64_t tag) {
   HIP_TRY(c, hipMemcpyAsync(S.host, S.dev, sizeof(MeshStreamHeader), hipMemcpyDeviceToHost, c->copy_stream));
   HIP_TRY(c, hipEventRecord(S.header_ready, c->copy_stream));
   if (cells) {
-    const float* lo = c->cfg.bbox_min; const float* hi = c->cfg.bbox_max;
-    const MeshGeometry G{{lo[0], lo[1], lo[2]}, {hi[0], hi[1], hi[2]}};
     timer_begin(c, "mesh_stream_emit");
-    launch_mesh_stream_emit(c->stream, V, c->luts, c->frame, G, R.scratch, R.flags, H, R.records, S.dev + sizeof(MeshStreamHeader));
+    launch_mesh_stream_emit(c->stream, V, c->luts, c->frame, mesh_geometry(c), R.scratch, R.flags, H, R.records, S.dev + sizeof(MeshStreamHeader));
     timer_end(c, "mesh_stream_emit");
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(S.emitted, c->stream));
@@ -2787,9 +2823,7 @@ int32_t tsdf_mesh_stream(tsdf_ctx* c, uint64_t tag) {
     // record that event again behind them (as an overlay does).
     if ((rc = overlay_rerecord_draw(c))) return rc;
   }
-  S.tag = tag; S.payload_issued = false; S.payload_bytes = 0;
-  for (int a = 0; a < 3; ++a) S.res[a] = c->res[a];
-  ++R.count; ++R.frames;
+  ++R.frames;
   return TSDF_OK;
 }
 int32_t tsdf_mesh_stream_acquire(tsdf_ctx* c, int32_t wait, tsdf_mesh_frame* out, int32_t* ready) {
@@ -2797,21 +2831,18 @@ int32_t tsdf_mesh_stream_acquire(tsdf_ctx* c, int32_t wait, tsdf_mesh_frame* out
   if (!out || (!ready && !wait)) return TSDF_ERR_INVALID_ARGUMENT;
   if (ready) *ready = 0;
   tsdf_ctx::MeshStream& R = c->mstream;
-  if (!R.count) FAIL(c, TSDF_ERR_STATE, "no streamed mesh frame is queued");
-  if (R.held) FAIL(c, TSDF_ERR_STATE, "a streamed mesh frame is held already: tsdf_mesh_stream_release first");
+  if (R.ring.acquire() == kResultNoneQueued) FAIL(c, TSDF_ERR_STATE, "no streamed mesh frame is queued");
+  if (R.ring.acquire() == kResultAlreadyHeld) FAIL(c, TSDF_ERR_STATE, "a streamed mesh frame is held already: tsdf_mesh_stream_release first");
   HIP_TRY(c, hipSetDevice(c->device));
-  tsdf_ctx::MeshStreamSlot& S = R.ring[R.head];
+  tsdf_ctx::MeshStreamSlot& S = R.slot[R.ring.oldest()];
   if (wait && !S.payload_issued) HIP_TRY(c, hipEventSynchronize(S.header_ready));
   int32_t rc;
   if ((rc = mesh_stream_pump(c))) return rc;
   if (!S.payload_issued) return TSDF_OK;                                  // (wait == 0: the header is still travelling)
   if (S.payload_bytes) {
-    if (wait) HIP_TRY(c, hipEventSynchronize(S.ready));
-    else {
-      const hipError_t e = hipEventQuery(S.ready);
-      if (e == hipErrorNotReady) { (void)hipGetLastError(); return TSDF_OK; }
-      HIP_TRY(c, e);
-    }
+    bool arrived;
+    if ((rc = event_reached(c, S.ready, wait != 0, &arrived))) return rc;
+    if (!arrived) return TSDF_OK;
   }
   const MeshStreamHeader* H = (const MeshStreamHeader*)S.host;
   const uint32_t stride = R.flags ? 16u : 8u;
@@ -2822,17 +2853,14 @@ int32_t tsdf_mesh_stream_acquire(tsdf_ctx* c, int32_t wait, tsdf_mesh_frame* out
   out->needed_vertices = H->needed_vertices; out->needed_triangles = H->needed_triangles; out->needed_tiles = H->needed_tiles;
   out->tag = S.tag; out->flags = R.flags; out->vertex_stride = stride; out->overflow = H->overflow;
   for (int a = 0; a < 3; ++a) { out->res[a] = (uint32_t)S.res[a]; out->bbox_min[a] = c->cfg.bbox_min[a]; out->bbox_max[a] = c->cfg.bbox_max[a]; }
-  R.held = true;
+  R.ring.hold();
   if (ready) *ready = 1;
   return TSDF_OK;
 }
 int32_t tsdf_mesh_stream_release(tsdf_ctx* c) {
   CHECK_CTX(c);
   tsdf_ctx::MeshStream& R = c->mstream;
-  if (!R.held) FAIL(c, TSDF_ERR_STATE, "no streamed mesh frame is held");
-  R.held = false;
-  R.head = (R.head + 1) % R.slots;
-  --R.count;
+  if (!R.ring.release()) FAIL(c, TSDF_ERR_STATE, "no streamed mesh frame is held");
   HIP_TRY(c, hipSetDevice(c->device));
   return mesh_stream_pump(c);
 }
@@ -2853,10 +2881,7 @@ static int32_t ray_cast_checks(tsdf_ctx* c, const void* rays, uint64_t n, uint32
     case 3: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "the surface array goes with TSDF_RAY_NORMALS / TSDF_RAY_COLOURS: given exactly when one is set");
     default: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "%llu rays in one cast (at most 2^40)", (unsigned long long)n);
   }
-  if (!whole_volume(c)) FAIL(c, TSDF_ERR_STATE, "ray queries on a Z-slab context: a ray crosses slabs, compositing per-ray partial results is not provided");
-  if (!c->have_volume) FAIL(c, TSDF_ERR_STATE, "no volume yet (tsdf_integrate or tsdf_upload_volume)");
-  if (flags & TSDF_RAY_COLOURS) return require_inputs(c, false, true);
-  return TSDF_OK;
+  return readable_volume_check(c, "ray queries on a Z-slab context: a ray crosses slabs, compositing per-ray partial results is not provided", (flags & TSDF_RAY_COLOURS) != 0);
 }
 // the launches of one cast on the context's stream, device arrays in and out; no host wait
 static int32_t ray_cast_queue(tsdf_ctx* c, const tsdf_ray* rays, uint64_t n, uint32_t flags, tsdf_ray_hit* hits, tsdf_ray_surface* surface) {
@@ -2869,12 +2894,11 @@ static int32_t ray_cast_queue(tsdf_ctx* c, const tsdf_ray* rays, uint64_t n, uin
   HIP_TRY(c, join_integ(c));                                             // the volume tsdf_download_volume would return now
   if (flags & TSDF_RAY_COLOURS) HIP_TRY(c, join_pre(c));                 // ... and the current frame slot's images
   HIP_TRY(c, hipMemsetAsync(R.d_words, 0, 64, c->stream));
-  const float* lo = c->cfg.bbox_min; const float* hi = c->cfg.bbox_max;
   RayCast Q{};
-  for (int a = 0; a < 3; ++a) { Q.bbox_min[a] = lo[a]; Q.ext[a] = hi[a] - lo[a]; }
+  box_origin_extent(c, Q.bbox_min, Q.ext);
   Q.flags = flags; Q.run = ray_run_length(c->vol.limit, c->vol.res); Q.n_cap = ray_sample_cap(c->vol.limit);
-  const RayChunks K{n, kRayChunk};
-  for (uint64_t k = 0; k < K.pairs(); ++k) {
+  const CallChunks K{n, kRayChunk};
+  for (uint64_t k = 0; k < K.launches(); ++k) {
     const uint64_t first = K.first(k);
     Q.n = K.count(k);
     if (k && surface) HIP_TRY(c, hipMemsetAsync(count, 0, sizeof(uint32_t), c->stream));
@@ -2894,19 +2918,8 @@ static int32_t ray_cast_queue(tsdf_ctx* c, const tsdf_ray* rays, uint64_t n, uin
   return overlay_rerecord_draw(c);
 }
 static int32_t ray_staging_reserve(tsdf_ctx* c, uint64_t n, bool surface) {
-  tsdf_ctx::Rays& R = c->rays;                                           // (nothing queued reads the staging: every call that uses it synchronises)
-  if (const uint64_t cap = R.staging.grow(n)) {
-    hipFree(R.d_rays); hipFree(R.d_hits); R.d_rays = nullptr; R.d_hits = nullptr; R.staging.grown(0);
-    HIP_TRY(c, hipMalloc((void**)&R.d_rays, (size_t)(cap * kRayBytes)));
-    HIP_TRY(c, hipMalloc((void**)&R.d_hits, (size_t)(cap * kRayBytes)));
-    R.staging.grown(cap);
-  }
-  if (const uint64_t cap = R.staging.grow_surface(n, surface)) {
-    hipFree(R.d_surf); R.d_surf = nullptr; R.staging.surface_grown(0);
-    HIP_TRY(c, hipMalloc((void**)&R.d_surf, (size_t)(cap * kRayBytes)));
-    R.staging.surface_grown(cap);
-  }
-  return TSDF_OK;
+  tsdf_ctx::Rays& R = c->rays;
+  return staging_reserve(c, R.staging, n, surface, (void**)&R.d_rays, kRayBytes, (void**)&R.d_hits, kRayBytes, (void**)&R.d_surf, kRayBytes);
 }
 int32_t tsdf_cast_rays(tsdf_ctx* c, const tsdf_ray* rays, uint64_t n, uint32_t flags, tsdf_ray_hit* hits, tsdf_ray_surface* surface) {
   CHECK_CTX(c);
@@ -2981,11 +2994,10 @@ static int32_t texture_taps_queue(tsdf_ctx* c, const float* xyz, uint64_t n, uin
   if (n == 0) return TSDF_OK;                                            // (tsdf_texture_tap_stats answers zeros without reading the counters)
   HIP_TRY(c, hipMemsetAsync(X.d_words, 0, (size_t)kTapStatBytes, c->stream));
   HIP_TRY(c, join_pre(c));                                              // the current frame slot's images, as the coloured ray cast takes them
-  const float* lo = c->cfg.bbox_min; const float* hi = c->cfg.bbox_max;
   TapsLaunch Q{};
-  for (int a = 0; a < 3; ++a) { Q.bbox_min[a] = lo[a]; Q.ext[a] = hi[a] - lo[a]; }
+  box_origin_extent(c, Q.bbox_min, Q.ext);
   Q.flags = flags;
-  const TapChunks K{n, kTapsChunk};
+  const CallChunks K{n, kTapsChunk};
   for (uint64_t k = 0; k < K.launches(); ++k) {
     const uint64_t first = K.first(k);
     Q.n_points = K.count(k);
@@ -3006,17 +3018,7 @@ int32_t tsdf_texture_taps(tsdf_ctx* c, const float* xyz, uint64_t n, uint32_t fl
   tsdf_ctx::TextureTaps& X = c->taps;
   const uint32_t N = c->cfg.num_streams;
   if (n == 0) return texture_taps_queue(c, nullptr, 0, flags, nullptr, nullptr);
-  if (const uint64_t cap = X.staging.grow(n)) {                          // (nothing queued reads the staging: every call that uses it synchronises)
-    hipFree(X.d_xyz); hipFree(X.d_taps); X.d_xyz = nullptr; X.d_taps = nullptr; X.staging.grown(0);
-    HIP_TRY(c, hipMalloc((void**)&X.d_xyz, (size_t)tap_point_bytes(cap)));
-    HIP_TRY(c, hipMalloc((void**)&X.d_taps, (size_t)tap_record_bytes(cap, N)));
-    X.staging.grown(cap);
-  }
-  if (const uint64_t cap = X.staging.grow_sensor(n, sensor != nullptr)) {
-    hipFree(X.d_sensor); X.d_sensor = nullptr; X.staging.sensor_grown(0);
-    HIP_TRY(c, hipMalloc((void**)&X.d_sensor, (size_t)tap_record_bytes(cap, N)));
-    X.staging.sensor_grown(cap);
-  }
+  if ((rc = staging_reserve(c, X.staging, n, sensor != nullptr, (void**)&X.d_xyz, kTapPointBytes, (void**)&X.d_taps, N * kTapBytes, (void**)&X.d_sensor, N * kTapBytes))) return rc;
   HIP_TRY(c, hipMemcpyAsync(X.d_xyz, xyz, (size_t)tap_point_bytes(n), hipMemcpyHostToDevice, c->stream));
   if ((rc = texture_taps_queue(c, X.d_xyz, n, flags, X.d_taps, sensor ? X.d_sensor : nullptr))) return rc;
   HIP_TRY(c, hipMemcpyAsync(taps, X.d_taps, (size_t)tap_record_bytes(n, N), hipMemcpyDeviceToHost, c->stream));
@@ -3089,16 +3091,16 @@ int32_t tsdf_texture_tap_stats(tsdf_ctx* c, uint64_t out[4]) {
 // ---- frame read-out: what the client's window holds after glfwSwapBuffers (source/kinect_client.cpp:533), converted on the device and copied to a pinned
 // host ring (include/rgbd_recon_hip.h, "frame read-out").  The mirror image of the asynchronous upload: a ring, the copy stream, the wire's DXT1.
 static size_t present_frame_bytes(const tsdf_ctx* c) {
-  return c->present_format == TSDF_PRESENT_DXT1 ? (size_t)((c->vw + 3) / 4) * ((c->vh + 3) / 4) * 8 : (size_t)c->vw * c->vh * 4;
+  return c->present.format == TSDF_PRESENT_DXT1 ? (size_t)((c->vw + 3) / 4) * ((c->vh + 3) / 4) * 8 : (size_t)c->vw * c->vh * 4;
 }
 int32_t tsdf_present_config(tsdf_ctx* c, uint32_t format, uint32_t flags, uint32_t slots) {
   CHECK_CTX(c);
-  if (format > TSDF_PRESENT_DXT1 || (flags & ~TSDF_PRESENT_TOP_DOWN) || slots < 2 || slots > tsdf_ctx::kMaxPresentSlots)
-    FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "present format %u / flags %u / slots %u (formats 0 RGBA8, 1 DXT1; flag 1 top-down; 2..%u slots)", format, flags, slots, tsdf_ctx::kMaxPresentSlots);
-  if (c->present_count) FAIL(c, TSDF_ERR_STATE, "%u presented frame(s) are queued or held: acquire and release them first", c->present_count);
+  if (format > TSDF_PRESENT_DXT1 || (flags & ~TSDF_PRESENT_TOP_DOWN) || slots < 2 || slots > kMaxResultSlots)
+    FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "present format %u / flags %u / slots %u (formats 0 RGBA8, 1 DXT1; flag 1 top-down; 2..%u slots)", format, flags, slots, kMaxResultSlots);
+  if (!c->present.ring.idle()) FAIL(c, TSDF_ERR_STATE, "%u presented frame(s) are queued or held: acquire and release them first", c->present.ring.count);
   HIP_TRY(c, hipSetDevice(c->device));
   release_present(c);                                                    // (the ring is idle: every copy was waited for before its frame was released)
-  c->present_format = format; c->present_flags = flags; c->present_slots = slots;
+  c->present.format = format; c->present.flags = flags; c->present.ring.configure(slots);
   return TSDF_OK;
 }
 int32_t tsdf_present_size(tsdf_ctx* c, uint64_t* bytes) {
@@ -3109,66 +3111,61 @@ int32_t tsdf_present_size(tsdf_ctx* c, uint64_t* bytes) {
 }
 int32_t tsdf_present(tsdf_ctx* c, uint64_t tag) {
   CHECK_CTX(c);
-  if (c->present_count >= c->present_slots) FAIL(c, TSDF_ERR_STATE, "all %u present slots are queued or held (tsdf_present_acquire / tsdf_present_release)", c->present_slots);
+  tsdf_ctx::Present& R = c->present;
+  if (R.ring.full()) FAIL(c, TSDF_ERR_STATE, "all %u present slots are queued or held (tsdf_present_acquire / tsdf_present_release)", R.ring.slots);
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t bytes = present_frame_bytes(c);
-  if (c->present_bytes != bytes) {                                       // first use at this view size and format (tsdf_resize and tsdf_present_config drop the ring)
+  if (R.bytes != bytes) {                                                // first use at this view size and format (tsdf_resize and tsdf_present_config drop the ring)
     release_present(c);
-    for (uint32_t k = 0; k < c->present_slots; ++k) {
-      tsdf_ctx::PresentSlot& S = c->present_ring[k];
+    for (uint32_t k = 0; k < R.ring.slots; ++k) {
+      tsdf_ctx::PresentSlot& S = R.slot[k];
       HIP_TRY(c, hipMalloc(&S.dev, bytes));
       HIP_TRY(c, hipHostMalloc(&S.host, bytes, hipHostMallocDefault));
       HIP_TRY(c, hipEventCreateWithFlags(&S.converted, hipEventDisableTiming));
       HIP_TRY(c, hipEventCreateWithFlags(&S.ready, hipEventDisableTiming));
     }
-    c->present_bytes = bytes;
+    R.bytes = bytes;
   }
-  if (!c->copy_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));   // (as ensure_async_upload makes it)
-  tsdf_ctx::PresentSlot& S = c->present_ring[(c->present_head + c->present_count) % c->present_slots];
+  if (int32_t rc = ensure_copy_stream(c)) return rc;
+  tsdf_ctx::PresentSlot& S = R.slot[R.ring.push()];                      // (queued before its calls are: result_paths.hpp's transitions precede what acts on them)
+  S.tag = tag;
   // The finished frame: the hole filling writes the framebuffer from its own lane, overlays from the context's stream.  The kernel's output is the slot's
   // device buffer, so the framebuffer is free again when the KERNEL has run, and nobody has to wait for the copy: every later writer of the framebuffer
   // is ordered behind the context's stream already -- the next hole filling waits for draw_done, which fill_colors_impl records on this stream behind the
   // next march (and so behind this kernel); a direct march (colour filling off) and the overlays run on this stream themselves.
   HIP_TRY(c, join_fill(c));
   timer_begin(c, "present");
-  launch_present(c->stream, c->d_fb_c, S.dev, c->vw, c->vh, c->present_format, (c->present_flags & TSDF_PRESENT_TOP_DOWN) ? 1 : 0);
+  launch_present(c->stream, c->d_fb_c, S.dev, c->vw, c->vh, R.format, (R.flags & TSDF_PRESENT_TOP_DOWN) ? 1 : 0);
   timer_end(c, "present");
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipEventRecord(S.converted, c->stream));
   HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, S.converted, 0));
   HIP_TRY(c, hipMemcpyAsync(S.host, S.dev, bytes, hipMemcpyDeviceToHost, c->copy_stream));
   HIP_TRY(c, hipEventRecord(S.ready, c->copy_stream));
-  S.tag = tag;
-  ++c->present_count;
   return TSDF_OK;
 }
 int32_t tsdf_present_acquire(tsdf_ctx* c, int32_t wait, const void** data, uint64_t* bytes, uint64_t* tag, uint32_t size[2]) {
   CHECK_CTX(c);
   if (!data) return TSDF_ERR_INVALID_ARGUMENT;
   *data = nullptr;
-  if (!c->present_count) FAIL(c, TSDF_ERR_STATE, "no presented frame is queued");
-  if (c->present_held) FAIL(c, TSDF_ERR_STATE, "a presented frame is held already: tsdf_present_release first");
+  tsdf_ctx::Present& R = c->present;
+  if (R.ring.acquire() == kResultNoneQueued) FAIL(c, TSDF_ERR_STATE, "no presented frame is queued");
+  if (R.ring.acquire() == kResultAlreadyHeld) FAIL(c, TSDF_ERR_STATE, "a presented frame is held already: tsdf_present_release first");
   HIP_TRY(c, hipSetDevice(c->device));
-  const tsdf_ctx::PresentSlot& S = c->present_ring[c->present_head];
-  if (wait) HIP_TRY(c, hipEventSynchronize(S.ready));
-  else {
-    const hipError_t e = hipEventQuery(S.ready);
-    if (e == hipErrorNotReady) { (void)hipGetLastError(); return TSDF_OK; }   // still travelling: *data stays NULL ("not ready" is no error: it must not stay behind as the thread's last one)
-    HIP_TRY(c, e);
-  }
-  c->present_held = true;
+  const tsdf_ctx::PresentSlot& S = R.slot[R.ring.oldest()];
+  bool arrived;
+  if (int32_t rc = event_reached(c, S.ready, wait != 0, &arrived)) return rc;
+  if (!arrived) return TSDF_OK;                                          // still travelling: *data stays NULL
+  R.ring.hold();
   *data = S.host;
-  if (bytes) *bytes = (uint64_t)c->present_bytes;
+  if (bytes) *bytes = (uint64_t)R.bytes;
   if (tag) *tag = S.tag;
   if (size) { size[0] = (uint32_t)c->vw; size[1] = (uint32_t)c->vh; }
   return TSDF_OK;
 }
 int32_t tsdf_present_release(tsdf_ctx* c) {
   CHECK_CTX(c);
-  if (!c->present_held) FAIL(c, TSDF_ERR_STATE, "no presented frame is held");
-  c->present_held = false;
-  c->present_head = (c->present_head + 1) % c->present_slots;
-  --c->present_count;
+  if (!c->present.ring.release()) FAIL(c, TSDF_ERR_STATE, "no presented frame is held");
   return TSDF_OK;
 }
 

@@ -10,6 +10,7 @@
 #include "lane_ahead.hpp"
 #include "draw_lanes.hpp"
 #include "frame_intake.hpp"
+#include "result_paths.hpp"
 #include "ray_staging.hpp"
 #include "texture_taps.hpp"
 
@@ -124,13 +125,10 @@ struct tsdf_ctx {
   float* d_linear = nullptr;     // scratch for volume up/download
   // frame read-out (tsdf_present): the window after the swap (kinect_client.cpp:533) as RGBA8 or DXT1, through a ring of slots -- device buffer (the
   // conversion kernel's output, on the context's stream), pinned host buffer (the copy stream's, behind `converted`), `ready` behind the copy.  Slots
-  // are taken and handed out in order: present_head is the oldest frame not yet released, present_count the frames queued or held, present_held
-  // whether the head is in the caller's hands.  Allocated by the first tsdf_present at a view size / format; nothing exists before that.
+  // are taken and handed out in order: which is written, which handed out, what is queued or held is the ResultRing's (result_paths.hpp; three slots until
+  // tsdf_present_config).  Here: what it indexes, allocated by the first tsdf_present at a view size / format (`bytes`: for what; 0: nothing exists).
   struct PresentSlot { void* dev = nullptr; void* host = nullptr; hipEvent_t converted = nullptr, ready = nullptr; uint64_t tag = 0; };
-  static constexpr uint32_t kMaxPresentSlots = 8;
-  PresentSlot present_ring[kMaxPresentSlots];
-  uint32_t present_format = 0, present_flags = 0, present_slots = 3, present_head = 0, present_count = 0; bool present_held = false;
-  size_t present_bytes = 0;      // what the ring's buffers were allocated for (0: none)
+  struct Present { PresentSlot slot[kMaxResultSlots]; ResultRing ring{3, 0, 0, false}; uint32_t format = 0, flags = 0; size_t bytes = 0; } present;
   bool async_upload_ready = false;   // ensure_async_upload ran through (copy_stream alone may be the read-out's)
   // mesh extraction (tsdf_mesh_extract): the arrays of the last extract, sized exactly from its counts, kept until the next extract, tsdf_set_voxel_size or
   // destroy; flags = the attributes it produced; stats = {tiles, tiles skipped by class, tiles with surface, bytes of mesh storage}.  Everything else an
@@ -147,26 +145,26 @@ struct tsdf_ctx {
   // stream's header copy waits for it), emitted (context's stream, behind the emit: the payload copy waits for it), header_ready / ready (copy stream, behind
   // the header / payload copy).  payload_issued: a later call has seen the header on the host and queued the payload copy (or found nothing to copy);
   // payload_bytes what it queued.  One persistent set of scratch serves every frame: the mesh launches of consecutive frames follow each other on the
-  // context's stream.  head / count / held as in the present ring.  Allocated by the first tsdf_mesh_stream after a config or a new grid.
+  // context's stream.  The ring's protocol is the ResultRing's, as the read-out's.  Allocated by the first tsdf_mesh_stream after a config or a new grid.
   struct MeshStreamSlot { uint8_t* dev = nullptr; uint8_t* host = nullptr; hipEvent_t header_written = nullptr, emitted = nullptr, header_ready = nullptr, ready = nullptr;
                           uint64_t tag = 0; size_t payload_bytes = 0; bool payload_issued = false; int res[3] = {0, 0, 0}; };
   struct MeshStream {
-    static constexpr uint32_t kMaxSlots = 8;
-    MeshStreamSlot ring[kMaxSlots];
+    MeshStreamSlot slot[kMaxResultSlots];
+    ResultRing ring{};
     MeshScratch scratch{}; uint32_t* records = nullptr;
-    uint32_t flags = 0, level = 0, max_vertices = 0, max_triangles = 0, max_tiles = 0, slots = 0, head = 0, count = 0;   // level: tsdf_mesh_stream_config_lod (the scratch is sized by its lattice tiles)
-    bool configured = false, allocated = false, held = false;
+    uint32_t flags = 0, level = 0, max_vertices = 0, max_triangles = 0, max_tiles = 0;   // level: tsdf_mesh_stream_config_lod (the scratch is sized by its lattice tiles)
+    bool configured = false, allocated = false;
     uint64_t frames = 0, overflowed = 0, bytes_copied = 0, device_bytes = 0;
   } mstream;
-  // ray queries (tsdf_cast_rays / _dev, tsdf_view_rays): the synchronous form's device staging (ray_staging.hpp: grown on demand, then kept), the hit
+  // ray queries (tsdf_cast_rays / _dev, tsdf_view_rays): the synchronous form's device staging (result_paths.hpp: grown on demand, then kept), the hit
   // list k_rays_march compacts for k_rays_surface (kRayChunk records, allocated with the counters by the context's first cast; no cast after it
   // allocates), `words` = {hits, samples accounted for, samples fetched} as three 64-bit counters of the cast, then the list's 32-bit count at byte 32
-  struct Rays { tsdf_ray* d_rays = nullptr; tsdf_ray_hit* d_hits = nullptr; tsdf_ray_surface* d_surf = nullptr; RayStaging staging{};
+  struct Rays { tsdf_ray* d_rays = nullptr; tsdf_ray_hit* d_hits = nullptr; tsdf_ray_surface* d_surf = nullptr; CallStaging staging{};
                 RayHitRec* d_list = nullptr; unsigned long long* d_words = nullptr; uint64_t last_n = 0; bool cast = false; } rays;
-  // texture taps (tsdf_texture_taps / _dev, tsdf_mesh_texture_taps): the synchronous form's device staging (texture_taps.hpp: grown on demand, then kept),
+  // texture taps (tsdf_texture_taps / _dev, tsdf_mesh_texture_taps): the synchronous form's device staging (result_paths.hpp: grown on demand, then kept),
   // the mesh form's results for the current extract (sized exactly; released with the mesh), `words` = {pairs with quality > 0, pairs not evaluated} of the
   // last call as kTapStatSlots pairs of 64-bit counters which the host sums (allocated with the context: no call allocates them), and the last call's point count
-  struct TextureTaps { float* d_xyz = nullptr; tsdf_texture_tap* d_taps = nullptr; tsdf_sensor_tap* d_sensor = nullptr; TapStaging staging{};
+  struct TextureTaps { float* d_xyz = nullptr; tsdf_texture_tap* d_taps = nullptr; tsdf_sensor_tap* d_sensor = nullptr; CallStaging staging{};
                        tsdf_texture_tap* mesh_taps = nullptr; tsdf_sensor_tap* mesh_sensor = nullptr; uint64_t mesh_nv = 0; bool mesh_valid = false, mesh_has_sensor = false;
                        unsigned long long* d_words = nullptr; uint64_t last_n = 0; bool called = false; } taps;
   bool have_volume = false;          // integrate() or tsdf_upload_volume has written the volume since it was set up (what the mesh extraction may read)

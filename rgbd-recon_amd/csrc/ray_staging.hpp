@@ -1,6 +1,6 @@
-// Host bookkeeping of the ray queries (tsdf_cast_rays / tsdf_cast_rays_dev / tsdf_view_rays), free of HIP: which arguments a cast accepts, how the
-// staging of the synchronous form grows, how a cast is cut into launches, and the two numbers the march kernel is launched with.  abi.cpp holds the
-// buffers and issues the calls; a stand-alone program (tests/test_ray_staging.py) runs this text under the host sanitizers.
+// Host bookkeeping of the ray queries (tsdf_cast_rays / tsdf_cast_rays_dev / tsdf_view_rays), free of HIP: which arguments a cast accepts and the two
+// numbers the march kernel is launched with; how the staging grows and how a cast is cut into launches is result_paths.hpp's (CallStaging, CallChunks).
+// abi.cpp holds the buffers and issues the calls; a stand-alone program (tests/test_ray_staging.py) runs this text under the host sanitizers.
 #pragma once
 #include <stdint.h>
 
@@ -28,32 +28,6 @@ inline int ray_view_rect(int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t v
   if ((int64_t)x0 + w > vw || (int64_t)y0 + h > vh) return 2;
   return 0;
 }
-
-// Staging of the synchronous form: one capacity (in rays) for the ray, hit and surface buffers; grown to the next power of two at or above the need (at
-// least 1024 rays), never shrunk.
-struct RayStaging {
-  uint64_t capacity = 0;           // rays the ray / hit buffers hold
-  uint64_t surface_capacity = 0;   // rays the surface buffer holds (allocated by the first cast that asks for an attribute)
-  static uint64_t round_up(uint64_t n) {
-    uint64_t c = 1024;
-    while (c < n) c <<= 1;         // (n <= kRayMaxCount: no overflow)
-    return c;
-  }
-  // the capacity to allocate before a cast of n rays, or 0 when the buffers do
-  uint64_t grow(uint64_t n) const { return n > capacity ? round_up(n) : 0; }
-  uint64_t grow_surface(uint64_t n, bool wanted) const { return wanted && n > surface_capacity ? round_up(n) : 0; }
-  void grown(uint64_t c) { capacity = c; }
-  void surface_grown(uint64_t c) { surface_capacity = c; }
-  void released() { capacity = 0; surface_capacity = 0; }
-};
-
-// A cast runs as launch pairs of at most `chunk` rays (the hit list's capacity): pair k covers rays [first, first + count)
-struct RayChunks {
-  uint64_t n; uint32_t chunk;
-  uint64_t pairs() const { return (n + chunk - 1) / chunk; }
-  uint64_t first(uint64_t k) const { return k * chunk; }
-  uint32_t count(uint64_t k) const { const uint64_t left = n - first(k); return left < chunk ? (uint32_t)left : chunk; }
-};
 
 // Samples per look at the tile classes: the most for which a run's taps span at most two 8-voxel tiles on every axis, whatever the direction.  A step
 // moves a ray by at most limit / 2 * res voxels on an axis; (run - 1) steps, one voxel of filter footprint and the fraction must stay within 8.  (The

@@ -1,6 +1,6 @@
 // Host bookkeeping of the texture taps (tsdf_texture_taps / tsdf_texture_taps_dev / tsdf_mesh_texture_taps), free of HIP: which arguments a call accepts,
-// how the staging of the synchronous form grows, how a call is cut into launches, the pair count and grid size of a launch, and the byte counts.  abi.cpp
-// holds the buffers and issues the calls; a stand-alone program (tests/test_texture_taps_staging.py) runs this text under the host sanitizers.
+// the pair count and grid size of a launch, the statistics' counters, the byte counts; how the staging grows and how a call is cut into launches is
+// result_paths.hpp's (CallStaging, CallChunks).  abi.cpp issues the calls; tests/test_texture_taps_staging.py runs this text under the host sanitizers.
 #pragma once
 #include <stdint.h>
 
@@ -51,31 +51,5 @@ inline uint64_t tap_record_bytes(uint64_t n, uint32_t streams) { return n * (uin
 // grid is tap_grid(its points) workgroups per stream (blockIdx.y = stream): tap_grid(points) * streams in all
 inline uint64_t tap_pairs(uint64_t n, uint32_t streams) { return n * (uint64_t)streams; }
 inline uint64_t tap_grid(uint64_t lanes) { return (lanes + kTapsThreads - 1) / kTapsThreads; }
-
-// Staging of the synchronous form: one capacity (in points) for the point and tap buffers, one for the sensor buffer; grown to the next power of two at
-// or above the need (at least 1024 points), never shrunk.
-struct TapStaging {
-  uint64_t capacity = 0;          // points the point / tap buffers hold
-  uint64_t sensor_capacity = 0;   // points the sensor buffer holds (allocated by the first call that asks for sensor records)
-  static uint64_t round_up(uint64_t n) {
-    uint64_t c = 1024;
-    while (c < n) c <<= 1;        // (n <= kTapsMaxPoints: no overflow)
-    return c;
-  }
-  // the capacity to allocate before a call of n points, or 0 when the buffers do
-  uint64_t grow(uint64_t n) const { return n > capacity ? round_up(n) : 0; }
-  uint64_t grow_sensor(uint64_t n, bool wanted) const { return wanted && n > sensor_capacity ? round_up(n) : 0; }
-  void grown(uint64_t c) { capacity = c; }
-  void sensor_grown(uint64_t c) { sensor_capacity = c; }
-  void released() { capacity = 0; sensor_capacity = 0; }
-};
-
-// A call runs as launches of at most `chunk` points: launch k covers points [first, first + count)
-struct TapChunks {
-  uint64_t n; uint32_t chunk;
-  uint64_t launches() const { return (n + chunk - 1) / chunk; }
-  uint64_t first(uint64_t k) const { return k * chunk; }
-  uint32_t count(uint64_t k) const { const uint64_t left = n - first(k); return left < chunk ? (uint32_t)left : chunk; }
-};
 
 }  // namespace rr

@@ -164,6 +164,24 @@ def test_ring_order_states_and_empty_volume(rr, small_scene, scene2):
             hip.mesh_stream(13)                                          # the freed slot
     assert hip.mesh_stream_stats()["frames"] == 4
     assert code(rr, lambda: hip.mesh_stream_acquire()) == -4
+    # Drained with the head at slot 1 of three.  A ring of another size starts at its slot 0 whatever the old head was: exactly two frames are taken, they come
+    # out in order with the bytes as before, and the third frame is written where the first one was -- once round a ring of two.
+    hip.mesh_stream_config(slots=2, **BIG)
+    hip.mesh_stream(20)
+    hip.mesh_stream(21)
+    assert code(rr, lambda: hip.mesh_stream(22)) == -4                   # both slots are taken
+    where = []
+    for tag in (20, 21, 22):
+        v, t, info = hip.mesh_stream_acquire(wait=True)
+        assert info["tag"] == tag and info["overflow"] == 0
+        assert v.tobytes() == np.ascontiguousarray(want_v).tobytes() and t.tobytes() == want_t.tobytes()
+        where.append(v.ctypes.data)
+        hip.mesh_stream_release()
+        if tag == 20:
+            hip.mesh_stream(22)
+    assert where[2] == where[0] and where[1] != where[0]
+    assert hip.mesh_stream_stats()["frames"] == 3                        # (counted from the config)
+    assert code(rr, lambda: hip.mesh_stream_acquire()) == -4
     hip.close()
 
     hip = rr.ReconIntegrationHip(scene2, res=(20, 22, 19), **KW)         # every voxel -limit: no surface

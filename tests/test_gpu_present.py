@@ -130,6 +130,37 @@ def test_ring_of_three_slots(rr, ctx):
     ctx.present(tag=5)
     got, tag, size = take(ctx)
     assert tag == 5 and size == (20, 12) and got.shape == (12, 20, 4)
+    # the smallest ring and the largest: 2 * slots + 1 frames, at most `slots` of them in flight, so the head goes round the ring twice
+    ctx.resize(w, h)
+    for slots in (2, 8):
+        ctx.present_config(P.RGBA8, 0, slots)
+        n, queued, taken = 2 * slots + 1, 0, 0
+
+        def put():
+            nonlocal queued
+            ctx.set_framebuffer(*fbs[queued % 5])
+            ctx.present(tag=100 * slots + queued)
+            queued += 1
+
+        def get():
+            nonlocal taken
+            got, tag, _ = take(ctx)
+            assert tag == 100 * slots + taken, (slots, taken)
+            np.testing.assert_array_equal(got, expect(fbs[taken % 5][0], P.RGBA8, 0), f"{slots} slots, frame {taken}")
+            taken += 1
+
+        for _ in range(slots):
+            put()
+        with pytest.raises(rr.TsdfError) as e:
+            ctx.present(tag=99)                                                   # every slot is queued
+        assert e.value.code == -4
+        while queued < n:
+            get()
+            put()
+        while taken < n:
+            get()
+        with pytest.raises(rr.TsdfError):
+            ctx.present_acquire(wait=False)                                       # drained
 
 
 _plain_runs = {}

@@ -1,6 +1,6 @@
-"""CPU: the ray queries' host bookkeeping (rgbd-recon_amd/csrc/ray_staging.hpp, HIP-free) as a stand-alone program with its own main, built with the
-host address and undefined-behaviour sanitizers: argument checks, the staging's growth, the cut of a cast into launch pairs, the run length and the
-sample bound."""
+"""CPU: the ray queries' host bookkeeping (rgbd-recon_amd/csrc/ray_staging.hpp, with result_paths.hpp's CallStaging / CallChunks; HIP-free) as a stand-alone
+program with its own main, built with the host address and undefined-behaviour sanitizers: argument checks, the staging's growth, the cut of a cast into
+launch pairs, the run length and the sample bound."""
 import os
 import subprocess
 
@@ -12,6 +12,7 @@ MAIN = r'''
 #include <cstdlib>
 #include <vector>
 #include "ray_staging.hpp"
+#include "result_paths.hpp"
 using namespace rr;
 #define CHECK(x) do { if (!(x)) { std::fprintf(stderr, "line %d: %s\n", __LINE__, #x); std::exit(1); } } while (0)
 int main() {
@@ -27,20 +28,20 @@ int main() {
   CHECK(ray_view_rect(0, 0, 0, 1, 64, 36) == 1 && ray_view_rect(-1, 0, 1, 1, 64, 36) == 1 && ray_view_rect(0, 0, 1, -3, 64, 36) == 1);
   CHECK(ray_view_rect(63, 0, 2, 1, 64, 36) == 2 && ray_view_rect(0, 36, 1, 1, 64, 36) == 2 && ray_view_rect(2147483647, 0, 2147483647, 1, 64, 36) == 2);
   // staging: grows to a power of two, then keeps it
-  RayStaging s;
-  CHECK(s.grow(1) == 1024 && s.grow_surface(1, false) == 0 && s.grow_surface(1, true) == 1024);
+  CallStaging s;
+  CHECK(s.grow(1) == 1024 && s.grow_extra(1, false) == 0 && s.grow_extra(1, true) == 1024);
   s.grown(1024);
   CHECK(s.grow(1024) == 0 && s.grow(1025) == 2048 && s.grow(kRayMaxCount) == kRayMaxCount);
-  s.surface_grown(4096);
-  CHECK(s.grow_surface(4096, true) == 0 && s.grow_surface(4097, true) == 8192 && s.capacity == 1024);
+  s.extra_grown(4096);
+  CHECK(s.grow_extra(4096, true) == 0 && s.grow_extra(4097, true) == 8192 && s.capacity == 1024);
   s.released();
-  CHECK(s.capacity == 0 && s.surface_capacity == 0);
+  CHECK(s.capacity == 0 && s.extra_capacity == 0);
   // launch pairs: they tile [0, n) exactly, none longer than the list; what a pair indexes stays inside an array of n records
   for (unsigned long long n : {1ull, 63ull, 64ull, 65ull, 262143ull, 262144ull, 262145ull, 1000000ull}) {
     std::vector<unsigned char> covered((size_t)n, 0);
-    const RayChunks K{n, 1u << 18};
+    const CallChunks K{n, 1u << 18};
     unsigned long long next = 0;
-    for (unsigned long long k = 0; k < K.pairs(); ++k) {
+    for (unsigned long long k = 0; k < K.launches(); ++k) {
       CHECK(K.first(k) == next && K.count(k) >= 1 && K.count(k) <= (1u << 18));
       for (unsigned long long i = 0; i < K.count(k); ++i) covered[(size_t)(K.first(k) + i)] += 1;
       next += K.count(k);
@@ -48,7 +49,7 @@ int main() {
     CHECK(next == n);
     for (unsigned char c : covered) CHECK(c == 1);
   }
-  CHECK((RayChunks{0, 1u << 18}.pairs() == 0));
+  CHECK((CallChunks{0, 1u << 18}.launches() == 0));
   // the run: (run - 1) steps of limit / 2 * res voxels stay within 6 voxels, between 1 and 32 samples
   const int r512[3] = {512, 512, 512}, r32[3] = {32, 40, 24}, r4096[3] = {4096, 8, 8};
   CHECK(ray_run_length(0.01f, r512) == 3 && ray_run_length(0.04f, r32) == 8 && ray_run_length(0.04f, r4096) == 1 && ray_run_length(1.0e-6f, r32) == 32);

@@ -1,6 +1,6 @@
-"""CPU: the texture taps' host bookkeeping (rgbd-recon_amd/csrc/texture_taps.hpp, HIP-free) as a stand-alone program with its own main, built with
-the host address and undefined-behaviour sanitizers: the argument codes, the staging's growth, the cut of a call into launches, the pair and grid
-arithmetic in 64 bits and the byte counts."""
+"""CPU: the texture taps' host bookkeeping (rgbd-recon_amd/csrc/texture_taps.hpp, with result_paths.hpp's CallStaging / CallChunks; HIP-free) as a
+stand-alone program with its own main, built with the host address and undefined-behaviour sanitizers: the argument codes, the staging's growth, the cut
+of a call into launches, the pair and grid arithmetic in 64 bits and the byte counts."""
 import os
 import subprocess
 
@@ -12,6 +12,7 @@ MAIN = r'''
 #include <cstdlib>
 #include <vector>
 #include "texture_taps.hpp"
+#include "result_paths.hpp"
 using namespace rr;
 #define CHECK(x) do { if (!(x)) { std::fprintf(stderr, "line %d: %s\n", __LINE__, #x); std::exit(1); } } while (0)
 int main() {
@@ -26,19 +27,19 @@ int main() {
   CHECK(mesh_texture_taps_arguments(0) == 0 && mesh_texture_taps_arguments(kTapsFlagSensor) == 0);
   CHECK(mesh_texture_taps_arguments(kTapsFlagUnitCube) == 5 && mesh_texture_taps_arguments(kTapsFlagUnitCube | kTapsFlagSensor) == 5 && mesh_texture_taps_arguments(4) == 1);
   // staging: grows to a power of two of points, then keeps it
-  TapStaging s;
-  CHECK(s.grow(1) == 1024 && s.grow_sensor(1, false) == 0 && s.grow_sensor(1, true) == 1024);
+  CallStaging s;
+  CHECK(s.grow(1) == 1024 && s.grow_extra(1, false) == 0 && s.grow_extra(1, true) == 1024);
   s.grown(1024);
   CHECK(s.grow(1024) == 0 && s.grow(1025) == 2048 && s.grow(1000000) == (1u << 20) && s.grow(kTapsMaxPoints) == kTapsMaxPoints);
-  s.sensor_grown(4096);
-  CHECK(s.grow_sensor(4096, true) == 0 && s.grow_sensor(4097, true) == 8192 && s.grow_sensor(1u << 20, false) == 0 && s.capacity == 1024);
+  s.extra_grown(4096);
+  CHECK(s.grow_extra(4096, true) == 0 && s.grow_extra(4097, true) == 8192 && s.grow_extra(1u << 20, false) == 0 && s.capacity == 1024);
   s.released();
-  CHECK(s.capacity == 0 && s.sensor_capacity == 0);
+  CHECK(s.capacity == 0 && s.extra_capacity == 0);
   // launches: they tile [0, n) exactly, none longer than 2^18 points; a launch's pairs fit 32 bits with 16 streams
   CHECK(kTapsChunk == (1u << 18));
   for (unsigned long long n : {1ull, 262143ull, 262144ull, 262145ull, 1000000ull}) {
     std::vector<unsigned char> covered((size_t)n, 0);
-    const TapChunks K{n, kTapsChunk};
+    const CallChunks K{n, kTapsChunk};
     unsigned long long next = 0;
     for (unsigned long long k = 0; k < K.launches(); ++k) {
       CHECK(K.first(k) == next && K.count(k) >= 1 && K.count(k) <= kTapsChunk);
@@ -49,14 +50,14 @@ int main() {
     CHECK(next == n);
     for (unsigned char c : covered) CHECK(c == 1);
   }
-  CHECK((TapChunks{0, kTapsChunk}.launches() == 0));
-  CHECK((TapChunks{1000000, kTapsChunk}.launches() == 4) && (TapChunks{1000000, kTapsChunk}.count(3) == 1000000 - 3 * 262144));
+  CHECK((CallChunks{0, kTapsChunk}.launches() == 0));
+  CHECK((CallChunks{1000000, kTapsChunk}.launches() == 4) && (CallChunks{1000000, kTapsChunk}.count(3) == 1000000 - 3 * 262144));
   // pairs, grid and bytes in 64 bits: 2^40 points x 16 streams
   const uint64_t big = 1ull << 40;
   CHECK(tap_pairs(big, 16) == (1ull << 44) && tap_grid(tap_pairs(big, 16)) == (1ull << 36));
   CHECK(tap_pairs(3, 5) == 15 && tap_grid(15) == 1 && tap_grid(256) == 1 && tap_grid(257) == 2 && tap_grid(0) == 0);
   CHECK(tap_point_bytes(big) == 12 * big && tap_record_bytes(big, 16) == (1ull << 48) && tap_record_bytes(1000, 3) == 48000);
-  CHECK((TapChunks{big, kTapsChunk}.launches() == (1ull << 22)) && (TapChunks{big, kTapsChunk}.first((1ull << 22) - 1) == big - kTapsChunk));
+  CHECK((CallChunks{big, kTapsChunk}.launches() == (1ull << 22)) && (CallChunks{big, kTapsChunk}.first((1ull << 22) - 1) == big - kTapsChunk));
   // the statistics' counters: a pair per slot, each in a 128-byte line of its own, consecutive waves on different slots; the host's sum
   CHECK(kTapStatBytes == 8192 && (kTapStatSlots & (kTapStatSlots - 1)) == 0 && kTapStatStride * 8 == 128);
   std::vector<unsigned long long> words(kTapStatSlots * kTapStatStride, 0);
