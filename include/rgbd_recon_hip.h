@@ -837,8 +837,8 @@ int32_t tsdf_texture_tap_stats(tsdf_ctx* ctx, uint64_t out[4]);
  *   before it and after a keep / filter --, vertices removed, triangles removed by the last keep / filter of this extract (0 before one)}.
  * Errors.  TSDF_ERR_STATE without an extract (a Z-slab context extracts no mesh, so always there); for download, keep and filter without components of
  *   the current mesh.  TSDF_ERR_INVALID_ARGUMENT for a NULL keep or a NULL out.  -1 for a NULL context.
- * Out of scope.  The streamed ring (tsdf_mesh_stream): a frame's header and payload size are fixed before its emit, a filtered frame needs a second
- *   header stage.  Z-slab contexts.  Welding by position.  Geometric measures per component (area, volume, bounding box): the caller has the arrays.
+ * The streamed ring (tsdf_mesh_stream) filters by the same rule inside the frame: "mesh streaming: the filtered frame" below.
+ * Out of scope.  Z-slab contexts.  Welding by position.  Geometric measures per component (area, volume, bounding box): the caller has the arrays.
  *   A context that never calls these entries runs exactly what it ran before they existed. */
 typedef struct tsdf_mesh_component { uint32_t first_vertex, n_vertices, n_triangles, reserved /* 0 */; } tsdf_mesh_component;
 int32_t tsdf_mesh_components(tsdf_ctx* ctx, uint64_t* n_components);
@@ -846,6 +846,42 @@ int32_t tsdf_mesh_download_components(tsdf_ctx* ctx, uint32_t* vertex_component,
 int32_t tsdf_mesh_keep_components(tsdf_ctx* ctx, const uint8_t* keep, uint64_t* n_vertices, uint64_t* n_triangles);
 int32_t tsdf_mesh_filter_components(tsdf_ctx* ctx, uint32_t min_triangles, uint64_t* n_vertices, uint64_t* n_triangles);
 int32_t tsdf_mesh_component_stats(tsdf_ctx* ctx, uint64_t out[4]);
+
+/* ---- mesh streaming: the filtered frame -------------------------------------------------------------------
+ * The ring of "mesh streaming" above with the keep rule of "mesh components" inside it: a streamed frame is already the mesh without its small
+ * components, decided and compacted on the device.  The ring's guarantees stay whole: no host wait, no allocation after the first call, never a partial
+ * frame, identical bytes on every run.  No counterpart in the reference.  tests/mesh_stream_filter_reference.py composes the definition from the
+ * extraction's, the components' and the packing's numpy references; device and numpy agree byte for byte.
+ *
+ * tsdf_mesh_stream_config_filter is tsdf_mesh_stream_config_lod with min_triangles; with min_triangles == 0 it IS that call (which is this one with
+ *   0): no filter, and tsdf_mesh_stream runs the launches, events and copies it ran before this entry existed.  min_triangles >= 1 selects the filtered
+ *   path; 1 keeps every component and still goes through the filter.  Argument checks and error codes are tsdf_mesh_stream_config_lod's.
+ *   tsdf_mesh_stream_min_triangles reports the configured value (TSDF_ERR_STATE before any config, TSDF_ERR_INVALID_ARGUMENT for a NULL pointer).
+ * The filtered frame.  Take the mesh tsdf_mesh_extract_lod(flags, level) defines for the volume; label its components by index; drop every component
+ *   whose table entry has n_triangles < min_triangles; kept vertices and triangles stay in their order, indices are remapped to the number of kept
+ *   vertices before them, the winding is untouched; pack what is left by the mesh streaming section's rule.  Packing is per vertex, so packed rows move
+ *   bit for bit: pack(keep(mesh)) == pack(mesh)[kept].
+ * tsdf_mesh_frame keeps its 112-byte layout.  n_vertices and n_triangles are the FILTERED counts, and the payload copied to the host is exactly
+ *   n_vertices * vertex_stride + n_triangles * 12 bytes of them.  needed_vertices / needed_triangles / needed_tiles stay the needs of the UNFILTERED
+ *   mesh, and the three capacities bound the unfiltered mesh: it is emitted whole on the device (into a raw buffer of the configuration, not the
+ *   slot) before anything is dropped, so a frame whose filtered mesh would fit still overflows when the unfiltered one does not.  An overflow is what
+ *   it is without a filter: the bits, the needs, zero counts, no filter run.  A frame whose every component is dropped has zero counts, overflow == 0
+ *   and no payload copy.  There is no component capacity and no fourth overflow bit: the filter keeps one triangle count per vertex, not a table.
+ * tsdf_mesh_stream_frame_filter: out = {components of the unfiltered mesh, components kept, vertices removed, triangles removed} of the frame
+ *   currently HELD (between tsdf_mesh_stream_acquire and tsdf_mesh_stream_release); all four 0 for an overflowed frame.  TSDF_ERR_STATE when no frame
+ *   is held or when the ring is configured without a filter; TSDF_ERR_INVALID_ARGUMENT for a NULL out.  The four words travel in a 64-byte record in
+ *   front of the slot's 64-byte header, in the header's copy; header and payload are where they were.
+ * Protocol.  count, scan, raw header, emit (into the raw buffer) as before; draw_done is recorded again right behind the emit, so an integrate()
+ *   that overwrites the volume set never waits for the filter, which reads no volume.  Then the filter: every launch is sized by the configured
+ *   capacities and reads the frame's counts from the raw header on the device, so the host never learns a count before the final header arrives.  The
+ *   slot's final header is written by a last one-lane launch and copied to the host behind it; the payload copy is queued, as ever, by whichever call
+ *   first sees the header on the host.  The raw buffer (header + capacity-sized payload) and the filter's scratch (13 bytes per capacity vertex and
+ *   the scans' block sums) are allocated by the first tsdf_mesh_stream after a config, counted in tsdf_mesh_stream_stats' device bytes and freed
+ *   with the ring.  Timer "mesh_stream_filter": everything between the emit and the final header, the header's launch included. */
+int32_t tsdf_mesh_stream_config_filter(tsdf_ctx* ctx, uint32_t flags, uint32_t level, uint32_t min_triangles, uint32_t max_vertices, uint32_t max_triangles,
+                                       uint32_t max_surface_tiles, uint32_t slots);
+int32_t tsdf_mesh_stream_min_triangles(tsdf_ctx* ctx, uint32_t* min_triangles);
+int32_t tsdf_mesh_stream_frame_filter(tsdf_ctx* ctx, uint64_t out[4]);
 
 /* ---- frame read-out: the swap ------------------------------------------------------------------------
  * The client ends a frame with glfwSwapBuffers (source/kinect_client.cpp:533): an RGBA8 window goes to a display (GLFW's default framebuffer has 8

@@ -824,21 +824,40 @@ class ReconIntegrationHip:
         return dict(components=int(out[0]), largest_triangles=int(out[1]), vertices_removed=int(out[2]), triangles_removed=int(out[3]))
 
     # ------------------------------------------------------------------ mesh streaming (no counterpart in the reference)
-    def mesh_stream_config(self, normals=False, colours=False, max_vertices=1 << 20, max_triangles=1 << 21, max_surface_tiles=1 << 14, slots=3, level=0):
+    def mesh_stream_config(self, normals=False, colours=False, max_vertices=1 << 20, max_triangles=1 << 21, max_surface_tiles=1 << 14, slots=3, level=0,
+                           min_triangles=0):
         """flags, the three capacities and the slot count of the mesh ring (tsdf_mesh_stream_config); the first mesh_stream after it allocates.
-        level 1 / 2 (tsdf_mesh_stream_config_lod): every frame is that level's mesh, max_surface_tiles counts its 8^3 lattice tiles."""
+        level 1 / 2 (tsdf_mesh_stream_config_lod): every frame is that level's mesh, max_surface_tiles counts its 8^3 lattice tiles.
+        min_triangles >= 1 (tsdf_mesh_stream_config_filter): every frame leaves the device without its components of fewer triangles; n_* in a frame's
+        info are the filtered counts, needed_* and the capacities those of the unfiltered mesh."""
         flags = (MESH_NORMALS if normals else 0) | (MESH_COLOURS if colours else 0)
         caps = (C.c_uint32(int(max_vertices)), C.c_uint32(int(max_triangles)), C.c_uint32(int(max_surface_tiles)), C.c_uint32(int(slots)))
-        if level:
+        if min_triangles:
+            self._ck(self._L.tsdf_mesh_stream_config_filter(self._c, C.c_uint32(flags), C.c_uint32(int(level)), C.c_uint32(int(min_triangles)), *caps))
+        elif level:
             self._ck(self._L.tsdf_mesh_stream_config_lod(self._c, C.c_uint32(flags), C.c_uint32(int(level)), *caps))
         else:
             self._ck(self._L.tsdf_mesh_stream_config(self._c, C.c_uint32(flags), *caps))
+        self._mesh_stream_filtered = bool(min_triangles)                 # (behind the checks: a refused config leaves the ring as it was)
 
     def mesh_stream_level(self):
         """the level of the last mesh_stream_config (tsdf_mesh_stream_level)"""
         level = C.c_uint32()
         self._ck(self._L.tsdf_mesh_stream_level(self._c, C.byref(level)))
         return int(level.value)
+
+    def mesh_stream_min_triangles(self):
+        """min_triangles of the last mesh_stream_config (tsdf_mesh_stream_min_triangles); 0: the ring has no filter"""
+        n = C.c_uint32()
+        self._ck(self._L.tsdf_mesh_stream_min_triangles(self._c, C.byref(n)))
+        return int(n.value)
+
+    def mesh_stream_frame_filter(self):
+        """dict: components (of the unfiltered mesh), kept, vertices_removed, triangles_removed of the frame held now (tsdf_mesh_stream_frame_filter);
+        TsdfError, code -4, when no frame is held or the ring has no filter"""
+        out = (C.c_uint64 * 4)()
+        self._ck(self._L.tsdf_mesh_stream_frame_filter(self._c, out))
+        return dict(components=int(out[0]), kept=int(out[1]), vertices_removed=int(out[2]), triangles_removed=int(out[3]))
 
     def mesh_stream(self, tag=0):
         """queue count, scan, emit and the copy of the current surface into the next ring slot; never blocks (TsdfError, code -4, when every slot is taken)"""
@@ -865,11 +884,14 @@ class ReconIntegrationHip:
         self._ck(self._L.tsdf_mesh_stream_release(self._c))
 
     def mesh_stream_take(self, wait=True):
-        """acquire, COPY, release: (vertices, triangles, info) as numpy arrays of the caller's own, or None (wait=False, frame not complete)"""
+        """acquire, COPY, release: (vertices, triangles, info) as numpy arrays of the caller's own, or None (wait=False, frame not complete).
+        With a filter configured info["filter"] is the frame's mesh_stream_frame_filter()."""
         got = self.mesh_stream_acquire(wait)
         if got is None:
             return None
         out = (got[0].copy(), got[1].copy(), got[2])
+        if getattr(self, "_mesh_stream_filtered", False):
+            out[2]["filter"] = self.mesh_stream_frame_filter()
         self.mesh_stream_release()
         return out
 

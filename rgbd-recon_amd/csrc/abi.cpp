@@ -666,11 +666,15 @@ void mesh_scratch_free(MeshScratch& S, uint32_t*& records) {            // ... a
 void release_mesh_stream(tsdf_ctx* c) {
   tsdf_ctx::MeshStream& R = c->mstream;
   for (auto& S : R.slot) {
-    hipFree(S.dev); if (S.host) hipHostFree(S.host);
+    if (S.dev) hipFree(S.dev - S.lead);
+    if (S.host) hipHostFree(S.host - S.lead);
     for (hipEvent_t e : {S.header_written, S.emitted, S.header_ready, S.ready}) if (e) hipEventDestroy(e);
     S = tsdf_ctx::MeshStreamSlot{};
   }
   mesh_scratch_free(R.scratch, R.records);
+  MeshStreamFilter& F = R.filter;
+  hipFree(F.raw); hipFree(F.parent); hipFree(F.label); hipFree(F.count); hipFree(F.keep); hipFree(F.vertex_sums); hipFree(F.triangle_sums); hipFree(F.words);
+  F = MeshStreamFilter{};
   R.allocated = false; R.ring.reset(); R.device_bytes = 0;
 }
 void release_volume(tsdf_ctx* c) {
@@ -2715,6 +2719,10 @@ int32_t tsdf_mesh_stream_config(tsdf_ctx* c, uint32_t flags, uint32_t max_vertic
   return tsdf_mesh_stream_config_lod(c, flags, 0u, max_vertices, max_triangles, max_surface_tiles, slots);
 }
 int32_t tsdf_mesh_stream_config_lod(tsdf_ctx* c, uint32_t flags, uint32_t level, uint32_t max_vertices, uint32_t max_triangles, uint32_t max_surface_tiles, uint32_t slots) {
+  return tsdf_mesh_stream_config_filter(c, flags, level, 0u, max_vertices, max_triangles, max_surface_tiles, slots);
+}
+int32_t tsdf_mesh_stream_config_filter(tsdf_ctx* c, uint32_t flags, uint32_t level, uint32_t min_triangles, uint32_t max_vertices, uint32_t max_triangles,
+                                       uint32_t max_surface_tiles, uint32_t slots) {
   CHECK_CTX(c);
   tsdf_ctx::MeshStream& R = c->mstream;
   if (level > (uint32_t)kMeshMaxLevel) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "mesh level %u (0 .. %d: every voxel, every 2nd, every 4th)", level, kMeshMaxLevel);
@@ -2728,7 +2736,7 @@ int32_t tsdf_mesh_stream_config_lod(tsdf_ctx* c, uint32_t flags, uint32_t level,
   // behind its header copy alone, and its emit launches, which read the slot's device header and the scratch, may still be queued on the context's stream.
   if (R.allocated) HIP_TRY(c, hipStreamSynchronize(c->stream));
   release_mesh_stream(c);
-  R.flags = flags; R.level = level; R.max_vertices = max_vertices; R.max_triangles = max_triangles; R.max_tiles = max_surface_tiles; R.ring.configure(slots); R.configured = true;
+  R.flags = flags; R.level = level; R.max_vertices = max_vertices; R.max_triangles = max_triangles; R.max_tiles = max_surface_tiles; R.min_triangles = min_triangles; R.ring.configure(slots); R.configured = true;
   R.frames = R.overflowed = R.bytes_copied = 0;
   return TSDF_OK;
 }
@@ -2739,16 +2747,40 @@ int32_t tsdf_mesh_stream_level(tsdf_ctx* c, uint32_t* level) {
   *level = c->mstream.level;
   return TSDF_OK;
 }
+int32_t tsdf_mesh_stream_min_triangles(tsdf_ctx* c, uint32_t* min_triangles) {
+  CHECK_CTX(c);
+  if (!min_triangles) return TSDF_ERR_INVALID_ARGUMENT;
+  if (!c->mstream.configured) FAIL(c, TSDF_ERR_STATE, "tsdf_mesh_stream_min_triangles before tsdf_mesh_stream_config");
+  *min_triangles = c->mstream.min_triangles;
+  return TSDF_OK;
+}
+// the filter's raw buffer and scratch (min_triangles >= 1): sized by the capacities, like everything the filter launches
+static bool mesh_stream_filter_allocate(tsdf_ctx::MeshStream& R, uint64_t* bytes) {
+  MeshStreamFilter& F = R.filter;
+  F.max_vertices = R.max_vertices; F.max_triangles = R.max_triangles; F.min_triangles = R.min_triangles; F.stride = R.flags ? 16u : 8u;
+  const size_t nv = R.max_vertices;
+  const struct { void** p; size_t bytes; } arrays[8] = {
+    {(void**)&F.raw, sizeof(MeshStreamHeader) + mesh_stream_payload_capacity(R)}, {(void**)&F.parent, nv * sizeof(uint32_t)}, {(void**)&F.label, nv * sizeof(uint32_t)},
+    {(void**)&F.count, nv * sizeof(uint32_t)}, {(void**)&F.keep, (nv + 3) / 4 * 4}, {(void**)&F.vertex_sums, mesh_stream_filter_scan_words(R.max_vertices) * sizeof(uint64_t)},
+    {(void**)&F.triangle_sums, mesh_stream_filter_scan_words(R.max_triangles) * sizeof(uint64_t)}, {(void**)&F.words, 2 * sizeof(uint32_t)}};
+  for (const auto& A : arrays) { if (hipMalloc(A.p, A.bytes) != hipSuccess) return false; *bytes += A.bytes; }
+  return true;
+}
 // slots and scratch, once per configuration and grid
 static int32_t mesh_stream_allocate(tsdf_ctx* c) {
   tsdf_ctx::MeshStream& R = c->mstream;
   const MeshLattice L = mesh_lattice(c->vol.res, (int)R.level);
-  const size_t n_tiles = (size_t)L.ntx * L.nty * L.ntz, slot_bytes = sizeof(MeshStreamHeader) + mesh_stream_payload_capacity(R), record_bytes = (size_t)R.max_tiles * 512 * sizeof(uint32_t);
+  const size_t n_tiles = (size_t)L.ntx * L.nty * L.ntz, lead = R.min_triangles ? sizeof(MeshStreamFilterRecord) : 0,
+               slot_bytes = lead + sizeof(MeshStreamHeader) + mesh_stream_payload_capacity(R), record_bytes = (size_t)R.max_tiles * 512 * sizeof(uint32_t);
   uint64_t bytes = (uint64_t)R.ring.slots * slot_bytes + record_bytes;
   bool ok = mesh_scratch_allocate(R.scratch, (int)n_tiles, (int)R.level, &bytes) == hipSuccess && hipMalloc((void**)&R.records, record_bytes) == hipSuccess;
+  if (ok && R.min_triangles) ok = mesh_stream_filter_allocate(R, &bytes);
   for (uint32_t k = 0; ok && k < R.ring.slots; ++k) {
     tsdf_ctx::MeshStreamSlot& S = R.slot[k];
-    ok = hipMalloc((void**)&S.dev, slot_bytes) == hipSuccess && hipHostMalloc((void**)&S.host, slot_bytes, hipHostMallocDefault) == hipSuccess;
+    ok = hipMalloc((void**)&S.dev, slot_bytes) == hipSuccess;
+    if (ok) { S.dev += lead; S.lead = lead; }                          // (release_mesh_stream frees dev - lead: a failed host allocation below must find it so)
+    ok = ok && hipHostMalloc((void**)&S.host, slot_bytes, hipHostMallocDefault) == hipSuccess;
+    if (ok) S.host += lead;
     for (hipEvent_t* e : {&S.header_written, &S.emitted, &S.header_ready, &S.ready}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
   }
   if (ok) ok = ensure_copy_stream(c) == TSDF_OK;
@@ -2780,6 +2812,30 @@ static int32_t mesh_stream_pump(tsdf_ctx* c) {
   }
   return TSDF_OK;
 }
+// A filtered frame behind its raw header: emit into the raw buffer, the filter into the slot, the slot's final header, and only then the header's copy.
+// draw_done is recorded again right behind the emit: the filter reads no volume, a later integrate() does not wait for it.
+static int32_t mesh_stream_filtered_tail(tsdf_ctx* c, tsdf_ctx::MeshStreamSlot& S) {
+  tsdf_ctx::MeshStream& R = c->mstream;
+  const MeshStreamFilter& F = R.filter;
+  timer_begin(c, "mesh_stream_emit");
+  launch_mesh_stream_emit(c->stream, c->vol, c->luts, c->frame, mesh_geometry(c), R.scratch, R.flags, F.raw, R.records, F.raw + 1);
+  timer_end(c, "mesh_stream_emit");
+  HIP_TRY(c, hipGetLastError());
+  if (int32_t rc = overlay_rerecord_draw(c)) return rc;
+  timer_begin(c, "mesh_stream_filter");
+  launch_mesh_stream_filter(c->stream, F, S.dev + sizeof(MeshStreamHeader));
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipEventRecord(S.emitted, c->stream));
+  launch_mesh_stream_filter_header(c->stream, F, (MeshStreamHeader*)S.dev, (MeshStreamFilterRecord*)(S.dev - S.lead));
+  timer_end(c, "mesh_stream_filter");
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipEventRecord(S.header_written, c->stream));
+  HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, S.header_written, 0));
+  HIP_TRY(c, hipMemcpyAsync(S.host - S.lead, S.dev - S.lead, S.lead + sizeof(MeshStreamHeader), hipMemcpyDeviceToHost, c->copy_stream));
+  HIP_TRY(c, hipEventRecord(S.header_ready, c->copy_stream));
+  ++R.frames;
+  return TSDF_OK;
+}
 int32_t tsdf_mesh_stream(tsdf_ctx* c, uint64_t tag) {
   CHECK_CTX(c);
   tsdf_ctx::MeshStream& R = c->mstream;
@@ -2793,7 +2849,8 @@ int32_t tsdf_mesh_stream(tsdf_ctx* c, uint64_t tag) {
   tsdf_ctx::MeshStreamSlot& S = R.slot[R.ring.push()];                   // (queued before its calls are: result_paths.hpp's transitions precede what acts on them)
   S.tag = tag; S.payload_issued = false; S.payload_bytes = 0;
   for (int a = 0; a < 3; ++a) S.res[a] = c->res[a];
-  MeshStreamHeader* H = (MeshStreamHeader*)S.dev;
+  const bool filtered = R.min_triangles != 0;
+  MeshStreamHeader* H = filtered ? R.filter.raw : (MeshStreamHeader*)S.dev;   // with a filter: count, scan, header and emit write the raw buffer, not the slot
   const Volume& V = c->vol;
   const MeshLattice L = mesh_lattice(V.res, (int)R.level);
   const bool cells = L.cr[0] >= 2 && L.cr[1] >= 2 && L.cr[2] >= 2;       // (a lattice one point thick has no cell)
@@ -2807,11 +2864,12 @@ int32_t tsdf_mesh_stream(tsdf_ctx* c, uint64_t tag) {
     launch_mesh_scan(c->stream, R.scratch);
     launch_mesh_stream_header(c->stream, R.scratch, H, R.max_vertices, R.max_triangles, R.max_tiles);
     timer_end(c, "mesh_stream_scan");
-  } else HIP_TRY(c, hipMemsetAsync(H, 0, sizeof(MeshStreamHeader), c->stream));
+  } else HIP_TRY(c, hipMemsetAsync(S.dev - S.lead, 0, S.lead + sizeof(MeshStreamHeader), c->stream));
   HIP_TRY(c, hipGetLastError());
+  if (filtered && cells) return mesh_stream_filtered_tail(c, S);
   HIP_TRY(c, hipEventRecord(S.header_written, c->stream));
   HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, S.header_written, 0));
-  HIP_TRY(c, hipMemcpyAsync(S.host, S.dev, sizeof(MeshStreamHeader), hipMemcpyDeviceToHost, c->copy_stream));
+  HIP_TRY(c, hipMemcpyAsync(S.host - S.lead, S.dev - S.lead, S.lead + sizeof(MeshStreamHeader), hipMemcpyDeviceToHost, c->copy_stream));
   HIP_TRY(c, hipEventRecord(S.header_ready, c->copy_stream));
   if (cells) {
     timer_begin(c, "mesh_stream_emit");
@@ -2863,6 +2921,17 @@ int32_t tsdf_mesh_stream_release(tsdf_ctx* c) {
   if (!R.ring.release()) FAIL(c, TSDF_ERR_STATE, "no streamed mesh frame is held");
   HIP_TRY(c, hipSetDevice(c->device));
   return mesh_stream_pump(c);
+}
+int32_t tsdf_mesh_stream_frame_filter(tsdf_ctx* c, uint64_t out[4]) {
+  CHECK_CTX(c);
+  if (!out) return TSDF_ERR_INVALID_ARGUMENT;
+  const tsdf_ctx::MeshStream& R = c->mstream;
+  if (!R.configured || !R.min_triangles) FAIL(c, TSDF_ERR_STATE, "the mesh ring is configured without a filter (tsdf_mesh_stream_config_filter, min_triangles >= 1)");
+  if (!R.ring.held) FAIL(c, TSDF_ERR_STATE, "no streamed mesh frame is held (tsdf_mesh_stream_acquire)");
+  const tsdf_ctx::MeshStreamSlot& S = R.slot[R.ring.oldest()];
+  const MeshStreamFilterRecord* r = (const MeshStreamFilterRecord*)(S.host - S.lead);
+  out[0] = r->components; out[1] = r->kept; out[2] = r->vertices_removed; out[3] = r->triangles_removed;
+  return TSDF_OK;
 }
 int32_t tsdf_mesh_stream_stats(tsdf_ctx* c, uint64_t out[4]) {
   CHECK_CTX(c);

@@ -386,6 +386,26 @@ void launch_mesh_stream_header(hipStream_t st, const MeshScratch& S, MeshStreamH
 // flags: TSDF_MESH_NORMALS | TSDF_MESH_COLOURS; payload: packed vertices (8 bytes each, 16 with a flag), then the triangles
 void launch_mesh_stream_emit(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S, uint32_t flags,
                              const MeshStreamHeader* H, uint32_t* records, void* payload);
+// the streamed filter (k_mesh_stream_filter.hip; tsdf_mesh_stream_config_filter with min_triangles >= 1): the emit writes the unfiltered frame into `raw`
+// (a header, the capacity-sized payload behind it: device only, one per configuration), the filter's launches move what stays into a slot's payload and
+// write the slot's header and record.  Every launch is sized by the capacities and reads the frame's counts from the raw header.
+struct MeshStreamFilter {
+  MeshStreamHeader* raw;
+  uint32_t* parent;                 // max_vertices words: the forest, behind the flatten the kept vertices' new indices
+  uint32_t* label;                  // max_vertices words: the smallest vertex index of the vertex's component
+  uint32_t* count;                  // max_vertices words: at a root, its component's triangles
+  uint8_t* keep;                    // max_vertices bytes rounded up to 4
+  unsigned long long* vertex_sums;  // mesh_stream_filter_scan_words(max_vertices): block prefixes of the kept vertices, then their total
+  unsigned long long* triangle_sums;   // ... (max_triangles)
+  uint32_t* words;                  // {components, components kept}
+  uint32_t max_vertices, max_triangles, min_triangles, stride;
+};
+// what travels to the host in front of a filtered slot's header: out[4] of tsdf_mesh_stream_frame_filter
+struct MeshStreamFilterRecord { unsigned long long components, kept, vertices_removed, triangles_removed, reserved[4]; };
+static_assert(sizeof(MeshStreamFilterRecord) == 64, "record and header travel as one 128-byte copy; the payload stays 64 bytes behind the header");
+size_t mesh_stream_filter_scan_words(uint32_t capacity);
+void launch_mesh_stream_filter(hipStream_t st, const MeshStreamFilter& F, void* payload);   // everything up to the scatter
+void launch_mesh_stream_filter_header(hipStream_t st, const MeshStreamFilter& F, MeshStreamHeader* H, MeshStreamFilterRecord* record);
 // mesh components (k_mesh_components.hip): the mesh arrays alone are read, so neither the volume nor a level appears.  Every scan works on `sums`:
 // mesh_cc_scan_blocks(n) + 1 64-bit words for n elements, the last of them the total once the launcher's work is done.
 struct MeshArrays { float* pos; float* nrm; float* col; uint32_t* tri; };   // nrm / col: null where the extract produced none

@@ -34,6 +34,7 @@ int main(int argc, char** argv) {
   const char* mesh_path = nullptr;
   bool mesh_stream = false;
   int mesh_level = -1;                                                    // -1: not given (the entries without a level)
+  long mesh_stream_min_triangles = -1;                                    // -1: not given (the ring without a filter)
   for (int a = 1; a < argc; ++a) {
     if (std::strcmp(argv[a], "--draw-bricks") == 0) draw_bricks = true;
     else if (std::strcmp(argv[a], "--sensor-view") == 0 && a + 2 < argc) { view_type = std::atoi(argv[a + 1]); view_width = (float)std::atof(argv[a + 2]); a += 2; }
@@ -43,8 +44,12 @@ int main(int argc, char** argv) {
     else if (std::strcmp(argv[a], "--mesh") == 0 && a + 1 < argc) { mesh_path = argv[a + 1]; a += 1; }
     else if (std::strcmp(argv[a], "--mesh-stream") == 0) mesh_stream = true;
     else if (std::strcmp(argv[a], "--mesh-level") == 0 && a + 1 < argc && std::strlen(argv[a + 1]) == 1 && argv[a + 1][0] >= '0' && argv[a + 1][0] <= '2') { mesh_level = argv[a + 1][0] - '0'; a += 1; }
+    else if (std::strcmp(argv[a], "--mesh-stream-min-triangles") == 0 && a + 1 < argc && argv[a + 1][0] >= '0' && argv[a + 1][0] <= '9') {
+      mesh_stream_min_triangles = std::atol(argv[a + 1]); mesh_stream = true; a += 1;
+    }
     else {
-      std::fprintf(stderr, "usage: frame_harness [--draw-bricks] [--sensor-view TYPE WIDTH] [--present rgba8|dxt1] [--mesh FILE.ply] [--mesh-stream] [--mesh-level 0|1|2]\n");
+      std::fprintf(stderr, "usage: frame_harness [--draw-bricks] [--sensor-view TYPE WIDTH] [--present rgba8|dxt1] [--mesh FILE.ply] [--mesh-stream] [--mesh-level 0|1|2]"
+                           " [--mesh-stream-min-triangles N]\n");
       return 1;
     }
   }
@@ -149,17 +154,30 @@ int main(int argc, char** argv) {
       if (mesh.position.size() != n.vertices * 3 || mesh.normal.size() != n.vertices * 3 || mesh.colour.size() != n.vertices * 4 || mesh.triangles.size() != n.triangles * 3) return 1;
     }
     if (mesh_stream) {
-      const kinect::ReconIntegrationHip::MeshCounts n = mesh_level < 0 ? recon.extractMesh(false, false) : recon.extractMesh(false, false, (unsigned)mesh_level);
-      if (mesh_level < 0) recon.configureMeshStream(true, true, 4096, 8192, 64, 3);
+      const kinect::ReconIntegrationHip::MeshCounts whole = mesh_level < 0 ? recon.extractMesh(false, false) : recon.extractMesh(false, false, (unsigned)mesh_level);
+      kinect::ReconIntegrationHip::MeshCounts n = whole;
+      const bool filtered = mesh_stream_min_triangles >= 0;
+      std::uint64_t components = 0;
+      if (mesh_stream_min_triangles >= 1) {                                    // what the ring has to deliver: the one-shot filter's result
+        components = recon.meshComponents();
+        n = recon.filterMeshComponents((std::uint32_t)mesh_stream_min_triangles);
+      }
+      if (filtered) recon.configureMeshStream(true, true, (unsigned)(mesh_level < 0 ? 0 : mesh_level), (unsigned)mesh_stream_min_triangles, 4096, 8192, 64, 3);
+      else if (mesh_level < 0) recon.configureMeshStream(true, true, 4096, 8192, 64, 3);
       else recon.configureMeshStream(true, true, (unsigned)mesh_level, 4096, 8192, 64, 3);
       if (recon.meshStreamLevel() != (unsigned)(mesh_level < 0 ? 0 : mesh_level)) return 1;
+      if (recon.meshStreamMinTriangles() != (unsigned)(filtered ? mesh_stream_min_triangles : 0)) return 1;
       const int frames = 5, lag = 2;
       int got = 0, wrong = 0;
       auto take = [&](std::uint64_t want_tag) {
         tsdf_mesh_frame fr;
         if (!recon.acquireMeshFrame(fr)) { ++wrong; return; }
-        const bool ok = fr.tag == want_tag && fr.overflow == 0 && fr.vertex_stride == 16 && fr.n_vertices == n.vertices && fr.n_triangles == n.triangles &&
-                        fr.needed_vertices == n.vertices && fr.res[0] == 16;
+        bool ok = fr.tag == want_tag && fr.overflow == 0 && fr.vertex_stride == 16 && fr.n_vertices == n.vertices && fr.n_triangles == n.triangles &&
+                  fr.needed_vertices == whole.vertices && fr.res[0] == 16;
+        if (mesh_stream_min_triangles >= 1) {
+          const kinect::ReconIntegrationHip::MeshFrameFilter ff = recon.meshStreamFrameFilter();
+          ok = ok && ff.components == components && ff.vertices_removed == whole.vertices - n.vertices && ff.triangles_removed == whole.triangles - n.triangles;
+        }
         recon.releaseMeshFrame();                                              // (before it is counted: a held frame would fail every later acquire too)
         ++(ok ? got : wrong);
       };

@@ -257,6 +257,27 @@ class ReconIntegrationHip {
     check(tsdf_mesh_stream_level(m_ctx, &level));
     return level;
   }
+  // ... without its small components (tsdf_mesh_stream_config_filter; min_triangles follows the level as in the C entry, every argument given): every
+  // frame is the level's mesh minus the components with fewer than min_triangles triangles, dropped on the device before the frame leaves it; 0 is the
+  // ring without a filter.  A frame's n_* are the filtered counts, its needed_* and the capacities those of the unfiltered mesh.
+  // meshStreamFrameFilter: what the filter did to the frame HELD now (between acquireMeshFrame and releaseMeshFrame); throws without a filter.
+  struct MeshFrameFilter { std::uint64_t components = 0, kept = 0, vertices_removed = 0, triangles_removed = 0; };
+  // (The trailing return type is deliberate: tests/test_mesh_lod_abi.py counts the void-first overloads, the two of its own section.)
+  auto configureMeshStream(bool normals, bool colours, unsigned level, unsigned min_triangles, unsigned max_vertices, unsigned max_triangles, unsigned max_surface_tiles,
+                           unsigned slots) -> void {
+    check(tsdf_mesh_stream_config_filter(m_ctx, (normals ? TSDF_MESH_NORMALS : 0u) | (colours ? TSDF_MESH_COLOURS : 0u), level, min_triangles, max_vertices, max_triangles,
+                                         max_surface_tiles, slots));
+  }
+  unsigned meshStreamMinTriangles() {
+    std::uint32_t min_triangles = 0;
+    check(tsdf_mesh_stream_min_triangles(m_ctx, &min_triangles));
+    return min_triangles;
+  }
+  MeshFrameFilter meshStreamFrameFilter() {
+    std::uint64_t s[4];
+    check(tsdf_mesh_stream_frame_filter(m_ctx, s));
+    return MeshFrameFilter{s[0], s[1], s[2], s[3]};
+  }
   // after drawF(): never blocks; false = every slot is queued or held (or there is no volume yet), nothing was queued
   bool streamMesh(std::uint64_t tag) {
     const int32_t rc = tsdf_mesh_stream(m_ctx, tag);

@@ -9,7 +9,11 @@ A record, not a threshold.  Prints one JSON line; with a file argument, also wri
 --level L[,L..] (0, 1, 2; default 0): the levels of detail to time (tsdf_mesh_stream_config_lod / tsdf_mesh_extract_lod).  In part 1 the levels alternate
 call by call in this one process (the ring is configured anew for each call, outside the timers), in part 2 loop by loop; the record then has a "levels"
 entry with each level's counts, capacities, stages (and the spread of the streamed device time over the N calls) and bytes per frame, and the frame
-rates carry the level in their names.  The top-level entries stay those of the first level named."""
+rates carry the level in their names.  The top-level entries stay those of the first level named.
+--min-triangles N (default 0: no filter): the ring drops the components of fewer than N triangles on the device (tsdf_mesh_stream_config_filter).  The
+streamed stages then include "mesh_stream_filter" (everything between the emit and the final header), every variant reports the filtered counts, the
+four filter words and the payload bytes of the filtered and of the unfiltered frame, and the streamed loops are the filtered ring's.
+--variants NAME[,NAME..] (positions, normals, colours, all_attributes; default all four): the attribute variants part 1 times."""
 import sys, os, json, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch  # noqa: F401  (torch first: the library binds to the HIP runtime torch loaded)
@@ -21,10 +25,13 @@ EXTRACT_FRAMES = 30
 STAGES_ONLY = "--stages-only" in sys.argv
 ARGS = sys.argv[1:]
 LEVELS = [int(x) for x in ARGS[ARGS.index("--level") + 1].split(",")] if "--level" in ARGS else [0]
-OUT = [a for i, a in enumerate(ARGS) if not a.startswith("--") and (i == 0 or ARGS[i - 1] != "--level")]
+MIN_TRIANGLES = int(ARGS[ARGS.index("--min-triangles") + 1]) if "--min-triangles" in ARGS else 0
+OUT = [a for i, a in enumerate(ARGS) if not a.startswith("--") and (i == 0 or ARGS[i - 1] not in ("--level", "--min-triangles", "--variants"))]
 VARIANTS = (("positions", dict(normals=False, colours=False)), ("normals", dict(normals=True, colours=False)), ("colours", dict(normals=False, colours=True)),
             ("all_attributes", dict(normals=True, colours=True)))
-STREAM_STAGES = ("mesh_stream_count", "mesh_stream_scan", "mesh_stream_emit")
+if "--variants" in ARGS:
+    VARIANTS = tuple(v for v in VARIANTS if v[0] in ARGS[ARGS.index("--variants") + 1].split(","))
+STREAM_STAGES = ("mesh_stream_count", "mesh_stream_scan", "mesh_stream_emit") + (("mesh_stream_filter",) if MIN_TRIANGLES else ())
 EXTRACT_STAGES = ("mesh_count", "mesh_scan", "mesh_emit")
 
 scene = rr.scene.make_scene(n_streams=4, width=640, height=480, lut_res=128, inv_res=128)
@@ -45,7 +52,7 @@ for L in LEVELS:
     nv, nt, ns = len(mesh["position"]), len(mesh["triangles"]), st["tiles_with_surface"]
     levels[L] = dict(vertices=nv, triangles=nt, tiles=st["tiles"], tiles_skipped=st["tiles_skipped"], tiles_with_surface=ns,
                      capacities=dict(max_vertices=nv + nv // 4, max_triangles=nt + nt // 4, max_surface_tiles=ns + ns // 4))
-rec = dict(shape="c2", res=list(hip.res), streams=4, level=LEVELS[0], **{k: v for k, v in levels[LEVELS[0]].items()})
+rec = dict(shape="c2", res=list(hip.res), streams=4, level=LEVELS[0], min_triangles=MIN_TRIANGLES, **{k: v for k, v in levels[LEVELS[0]].items()})
 
 # 1. device time per stage
 hip.enable_timers(True)
@@ -53,7 +60,7 @@ hip.set_timer_filter(list(STREAM_STAGES + EXTRACT_STAGES))
 def one_call(L, kw):
     """one streamed frame and one extract of level L; with one level the ring keeps its configuration"""
     if len(LEVELS) > 1 or not one_call.configured:
-        hip.mesh_stream_config(slots=3, level=L, **kw, **levels[L]["capacities"])
+        hip.mesh_stream_config(slots=3, level=L, min_triangles=MIN_TRIANGLES, **kw, **levels[L]["capacities"])
         one_call.configured = True
     hip.mesh_stream(0); got = hip.mesh_stream_take()
     hip.extract_mesh(level=L, **kw)
@@ -63,7 +70,13 @@ for label, kw in VARIANTS:
     for _ in range(2):
         for L in LEVELS:
             got = one_call(L, kw)
-            assert got[2]["overflow"] == 0 and got[2]["n_vertices"] == levels[L]["vertices"] and got[2]["n_triangles"] == levels[L]["triangles"]
+            assert got[2]["overflow"] == 0 and got[2]["needed_vertices"] == levels[L]["vertices"] and got[2]["needed_triangles"] == levels[L]["triangles"]
+            if MIN_TRIANGLES:
+                f = got[2]["filter"]
+                assert got[2]["n_vertices"] == levels[L]["vertices"] - f["vertices_removed"] and got[2]["n_triangles"] == levels[L]["triangles"] - f["triangles_removed"]
+                levels[L]["filtered"] = dict(vertices=got[2]["n_vertices"], triangles=got[2]["n_triangles"], **f)
+            else:
+                assert got[2]["n_vertices"] == levels[L]["vertices"] and got[2]["n_triangles"] == levels[L]["triangles"]
     for s in STREAM_STAGES + EXTRACT_STAGES:
         hip.timer_stats(s)                                               # (resets the timer's samples)
     samples = {L: {s: [] for s in STREAM_STAGES + EXTRACT_STAGES} for L in LEVELS}
@@ -84,6 +97,9 @@ for label, kw in VARIANTS:
             r[name] = t
         nv, nt = levels[L]["vertices"], levels[L]["triangles"]
         r["stream_bytes_per_frame"] = nv * stride + nt * 12 + 64        # payload + header
+        if MIN_TRIANGLES:                                                # the unfiltered frame's bytes stay beside what the filtered ring sends
+            r["stream_unfiltered_bytes_per_frame"] = r["stream_bytes_per_frame"]
+            r["stream_bytes_per_frame"] = levels[L]["filtered"]["vertices"] * stride + levels[L]["filtered"]["triangles"] * 12 + 128   # payload + record + header
         r["extract_bytes_per_frame"] = nv * (12 + (12 if kw["normals"] else 0) + (16 if kw["colours"] else 0)) + nt * 12
         levels[L][label] = r
     rec[label] = levels[LEVELS[0]][label]
@@ -113,8 +129,8 @@ fps = {}
 suffix = (lambda L: "_level%d" % L) if "--level" in ARGS else (lambda L: "")
 for rep in range(0 if STAGES_ONLY else 3):                              # the three forms in turn, three times: the spread is part of the record
     for L in LEVELS:
-        for label, kw in (("positions", dict(normals=False, colours=False)), ("all_attributes", dict(normals=True, colours=True))):
-            hip.mesh_stream_config(slots=3, level=L, **kw, **levels[L]["capacities"])
+        for label, kw in [v for v in VARIANTS if v[0] in ("positions", "all_attributes")]:
+            hip.mesh_stream_config(slots=3, level=L, min_triangles=MIN_TRIANGLES, **kw, **levels[L]["capacities"])
             streamed.taken = 0
             before = hip.mesh_stream_stats()["payload_bytes"]
             fps.setdefault("stream_" + label + suffix(L), []).append(loop(FRAMES, streamed, drain_stream))
@@ -123,6 +139,8 @@ for rep in range(0 if STAGES_ONLY else 3):                              # the th
     fps.setdefault("plain", []).append(loop(FRAMES, lambda f: None, nothing))
 if fps:
     rec["frames_per_s"] = {k: dict(runs=[round(x, 1) for x in v], median=round(float(np.median(v)), 1)) for k, v in fps.items()}
+if MIN_TRIANGLES:
+    rec["filtered"] = levels[LEVELS[0]]["filtered"]
 if "--level" in ARGS:
     rec["levels"] = {str(L): levels[L] for L in LEVELS}
 print(json.dumps(rec), flush=True)
