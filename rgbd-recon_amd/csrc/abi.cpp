@@ -267,7 +267,7 @@ int32_t setup_bricks(tsdf_ctx* c, const float req[3]) {
     B.brick_t0[a] = c->d_brick_t0[a];
     B.brick_t1[a] = c->d_brick_t1[a];
   }
-  c->full_classify = true; c->alt.full = true;                           // a new brick grid: walk every tile once
+  for (tsdf_ctx::VolSet& s : c->vset) s.history.invalidate();            // a new brick grid: walk every tile once
   // tiles == bricks structurally?  (every voxel in exactly one brick per axis, and a tile never straddles two)
   bool uniform = true;
   for (int a = 0; a < 3 && uniform; ++a)
@@ -463,36 +463,42 @@ bool deep_ok(const tsdf_ctx* c) {
   // (a Z-slab context too, when it recomputes its halo layers itself: an EXCHANGED halo is written into the volume from outside between integrate() and the draw)
   return c->deep && !c->lanes.second_set_failed() && pipelined(c) && c->integ_stream && (whole_volume(c) || c->cfg.slab_recompute_halo != 0) && !c->vol.slot && c->proj_budget == 0;
 }
-// exchange the set in use with the other one (host pointers only: kernels already queued keep the pointers they were launched with; which set: DrawLanes::integrate)
-void swap_volume_set(tsdf_ctx* c) {
-  tsdf_ctx::VolSet& a = c->alt;
-  std::swap(c->vol.data, a.data); std::swap(c->d_cls_all, a.cls_all); std::swap(c->tiles.stamp, a.stamp);
-  std::swap(c->d_tile_list[0], a.list[0]); std::swap(c->d_tile_list[1], a.list[1]); std::swap(c->d_tile_counts, a.counts);
-  std::swap(c->tile_parity, a.parity); std::swap(c->full_classify, a.full); std::swap(c->frame_stamp, a.stampno);
-  c->vol.cls = c->d_cls_all;
-  c->tiles.cls = c->d_cls_all + (size_t)(c->vol.int_tz0 - c->vol.tz0) * c->vol.nty * c->vol.ntx;
-  c->tiles.list = c->d_tile_list[0]; c->tiles.count = c->d_tile_counts;
+// ---- the volume sets: tsdf_ctx::vset; what an integrate() may trust of a set is volume_sets.hpp's (VolSet::history)
+static tsdf_ctx::VolSet& set_in_use(tsdf_ctx* c) { return c->vset[c->lanes.set()]; }
+// Set s as the kernels get it: its volume and classes into V, its stamps and the classes of the integrated tiles into S, with list / count 0 (a culled
+// integrate() selects its own: TileHistory::begin).  Host pointers only: kernels already queued keep the pointers they were launched with
+static void bind_volume_set(const tsdf_ctx::VolSet& s, Volume& V, TileState& S) {
+  V.data = s.data; V.cls = s.cls;
+  S.cls = s.cls + class_offset(V.tz0, V.int_tz0, V.nty, V.ntx); S.stamp = s.stamp;
+  S.list = s.list[0]; S.count = s.counts;
 }
-// the second set, initialised on `lane` like setup_volume initialises the first; false = no memory for it (the context stays on one volume)
-bool ensure_alt_set(tsdf_ctx* c, hipStream_t lane) {
-  tsdf_ctx::VolSet& a = c->alt;
-  if (a.data) return true;
+static void free_volume_set(tsdf_ctx::VolSet& s) {
+  hipFree(s.data); hipFree(s.cls); hipFree(s.stamp); hipFree(s.list[0]); hipFree(s.list[1]); hipFree(s.counts);
+  s = tsdf_ctx::VolSet{};
+}
+// Allocate set s for the grid c->vol / c->tiles describe and initialise it on `lane`: the volume (the sparse pool where there is one) zeroed, every stored
+// tile kTileMixed (halo layers keep this value for good), no tile stamped, both lists empty.  On failure nothing of the set is left
+static hipError_t alloc_volume_set(tsdf_ctx* c, tsdf_ctx::VolSet& s, hipStream_t lane) {
   const Volume& V = c->vol;
-  const size_t nvox = (size_t)V.n_stored_tiles * TILE_VOX, n = (size_t)c->tiles.n;
-  bool ok = hipMalloc(&a.data, nvox * sizeof(float)) == hipSuccess && hipMalloc(&a.stamp, n * sizeof(uint32_t)) == hipSuccess &&
-            hipMalloc(&a.cls_all, (size_t)V.n_stored_tiles) == hipSuccess && hipMalloc(&a.list[0], n * sizeof(uint32_t)) == hipSuccess &&
-            hipMalloc(&a.list[1], n * sizeof(uint32_t)) == hipSuccess && hipMalloc(&a.counts, 2 * sizeof(uint32_t)) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
-    hipFree(a.data); hipFree(a.stamp); hipFree(a.cls_all); hipFree(a.list[0]); hipFree(a.list[1]); hipFree(a.counts);
-    a = tsdf_ctx::VolSet{}; c->lanes.second_set_unavailable();
-    return false;
-  }
-  launch_fill_u32(lane, (uint32_t*)a.data, 0u, nvox);
-  hipMemsetAsync(a.cls_all, kTileMixed, (size_t)V.n_stored_tiles, lane);
-  hipMemsetAsync(a.counts, 0, 2 * sizeof(uint32_t), lane);
-  hipMemsetAsync(a.stamp, 0, n * sizeof(uint32_t), lane);
-  a.parity = 0; a.full = true; a.stampno = 0;
+  const size_t nvox = (V.slot ? (size_t)V.pool_tiles : (size_t)V.n_stored_tiles) * TILE_VOX, n = (size_t)c->tiles.n;
+  hipError_t e = hipMalloc(&s.data, nvox * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&s.stamp, n * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc(&s.cls, (size_t)V.n_stored_tiles);
+  for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipMalloc(&s.list[k], n * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc(&s.counts, 2 * sizeof(uint32_t));
+  if (e != hipSuccess) { (void)hipGetLastError(); free_volume_set(s); return e; }
+  launch_fill_u32(lane, (uint32_t*)s.data, 0u, nvox);
+  hipMemsetAsync(s.cls, kTileMixed, (size_t)V.n_stored_tiles, lane);
+  hipMemsetAsync(s.counts, 0, 2 * sizeof(uint32_t), lane);
+  hipMemsetAsync(s.stamp, 0, n * sizeof(uint32_t), lane);
+  s.history.reset();
+  return hipSuccess;
+}
+// the other set, initialised on `lane` like setup_volume initialises the one in use; false = no memory for it (the context stays on one volume)
+bool ensure_other_set(tsdf_ctx* c, hipStream_t lane) {
+  tsdf_ctx::VolSet& s = c->vset[c->lanes.set() ^ 1];
+  if (s.data) return true;
+  if (alloc_volume_set(c, s, lane) != hipSuccess) { c->lanes.second_set_unavailable(); return false; }
   return true;
 }
 // projection cache: the pool and its tables, on the first integrate() that can use them, and this frame's turn of its slow-item counters.  Capacity = the
@@ -680,17 +686,15 @@ void release_mesh_stream(tsdf_ctx* c) {
 void release_volume(tsdf_ctx* c) {
   release_mesh(c); c->have_volume = false;                             // (a mesh belongs to the grid it was extracted from)
   release_mesh_stream(c);                                              // (... and the streaming scratch is sized by its tiles)
-  hipFree(c->vol.data); hipFree(c->vol.slot);                          // (both callers have synchronised the stream)
-  hipFree(c->tiles.stamp); hipFree(c->d_cls_all);
-  hipFree(c->d_tile_list[0]); hipFree(c->d_tile_list[1]); hipFree(c->d_tile_counts); hipFree(c->d_linear); hipFree(c->d_tile_bounds); hipFree(c->d_pair_masks); c->d_pair_masks = nullptr; hipFree(c->d_work_recs); c->d_work_recs = nullptr;
+  for (tsdf_ctx::VolSet& s : c->vset) free_volume_set(s);              // (both callers have synchronised the stream)
+  hipFree(c->vol.slot);
+  hipFree(c->d_linear); hipFree(c->d_tile_bounds); hipFree(c->d_pair_masks); c->d_pair_masks = nullptr; hipFree(c->d_work_recs); c->d_work_recs = nullptr;
   hipFree(c->proj.data); hipFree(c->proj.slot); hipFree(c->proj.items); hipFree(c->d_proj_words); hipFree(c->d_item_stats);
   c->proj = ProjCache{}; c->d_proj_words = nullptr; c->d_item_stats = nullptr; c->proj_failed = false; c->last_integrate_cached = false;
   c->last_k1 = IntegratePlan{};
-  hipFree(c->alt.data); hipFree(c->alt.cls_all); hipFree(c->alt.stamp); hipFree(c->alt.list[0]); hipFree(c->alt.list[1]); hipFree(c->alt.counts);
-  c->alt = tsdf_ctx::VolSet{}; c->lanes.volume_released();
-  c->vol.data = nullptr; c->vol.slot = nullptr; c->tiles.stamp = nullptr; c->d_cls_all = nullptr;
-  c->d_tile_list[0] = c->d_tile_list[1] = nullptr; c->d_tile_counts = nullptr; c->d_linear = nullptr; c->d_tile_bounds = nullptr;
-  c->tile_bounds_valid = false; c->tile_parity = 0; c->full_classify = true; c->frame_stamp = 0;
+  c->lanes.volume_released();                                          // (the index of the set in use stays: setup_volume allocates that one)
+  c->vol.data = nullptr; c->vol.slot = nullptr; c->tiles.stamp = nullptr; c->d_linear = nullptr; c->d_tile_bounds = nullptr;
+  c->tile_bounds_valid = false;
 }
 int32_t setup_volume(tsdf_ctx* c) {
   Volume& V = c->vol;
@@ -730,27 +734,17 @@ int32_t setup_volume(tsdf_ctx* c) {
     return e == hipErrorOutOfMemory ? TSDF_ERR_OUT_OF_MEMORY : TSDF_ERR_HIP;
   };
   release_volume(c);
-  if ((rc = tryhip(hipMalloc(&V.data, nvox * sizeof(float)), "hipMalloc(volume)"))) return rc;
-  launch_fill_u32(c->stream, (uint32_t*)V.data, 0u, nvox);
   V.slot = nullptr; V.pool_tiles = 0;
   if (sparse) {
     if ((rc = tryhip(hipMalloc(&V.slot, (size_t)V.n_stored_tiles * sizeof(uint32_t)), "hipMalloc(slot table)"))) return rc;
     if ((rc = tryhip(hipMemsetAsync(V.slot, 0xff, (size_t)V.n_stored_tiles * sizeof(uint32_t), c->stream), "hipMemset(slot table)"))) return rc;
     V.pool_tiles = c->cfg.sparse_pool_tiles;
   }
-  TileState& S = c->tiles;
-  S.n = (V.int_tz1 - V.int_tz0) * V.nty * V.ntx;
-  if ((rc = tryhip(hipMalloc(&S.stamp, (size_t)S.n * sizeof(uint32_t)), "hipMalloc(tiles)"))) return rc;
-  if ((rc = tryhip(hipMalloc(&c->d_cls_all, (size_t)V.n_stored_tiles), "hipMalloc(tiles)"))) return rc;
-  hipMemsetAsync(c->d_cls_all, kTileMixed, (size_t)V.n_stored_tiles, c->stream);   // halo layers keep this value for good
-  V.cls = c->d_cls_all;
-  S.cls = c->d_cls_all + (size_t)(V.int_tz0 - V.tz0) * V.nty * V.ntx;
-  for (int k = 0; k < 2; ++k)
-    if ((rc = tryhip(hipMalloc(&c->d_tile_list[k], (size_t)S.n * sizeof(uint32_t)), "hipMalloc(tiles)"))) return rc;
-  if ((rc = tryhip(hipMalloc(&c->d_tile_counts, 2 * sizeof(uint32_t)), "hipMalloc(tiles)"))) return rc;
-  hipMemsetAsync(c->d_tile_counts, 0, 2 * sizeof(uint32_t), c->stream);
-  hipMemsetAsync(S.stamp, 0, (size_t)S.n * sizeof(uint32_t), c->stream);
-  S.list = c->d_tile_list[0]; S.count = c->d_tile_counts;
+  c->tiles.n = (V.int_tz1 - V.int_tz0) * V.nty * V.ntx;
+  // the set in use -- either index: a released context keeps the one it was on --; the other one is the first integrate()'s on the lane (ensure_other_set)
+  tsdf_ctx::VolSet& s = set_in_use(c);
+  if ((rc = tryhip(alloc_volume_set(c, s, c->stream), "hipMalloc(volume set)"))) return rc;
+  bind_volume_set(s, V, c->tiles);
   return TSDF_OK;
 }
 // the largest LUT texel box any 8^3 tile of the current volume touches, with the kernel's own fp32 index arithmetic, against the LDS
@@ -975,9 +969,8 @@ int32_t tsdf_integrate_stats(tsdf_ctx* c, uint32_t out[6]) {
   if (!c->last_integrate_cached || !c->proj.data) return TSDF_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   if (!c->d_item_stats) HIP_TRY(c, hipMalloc((void**)&c->d_item_stats, 4 * sizeof(uint32_t)));
-  // (the tile list of the last integrate: tsdf_integrate has already flipped the parity)
   TileState S = c->tiles;
-  if (c->use_bricks) { const int p = c->tile_parity ^ 1; S.list = c->d_tile_list[p]; S.count = c->d_tile_counts + p; }
+  if (c->use_bricks) { const tsdf_ctx::VolSet& s = set_in_use(c); const int p = s.history.last(); S.list = s.list[p]; S.count = s.counts + p; }
   launch_item_stats(c->stream, c->luts, S, c->use_bricks ? 1 : 0, c->d_pair_masks, c->proj, c->d_item_stats);
   HIP_TRY(c, hipMemcpyAsync(out, c->d_item_stats, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(out + 4, c->proj.alloc, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -1570,12 +1563,12 @@ int32_t tsdf_integrate(tsdf_ctx* c) {
   HIP_TRY(c, hipSetDevice(c->device));
   // the lane: the fourth one and the volume set the previous draw is NOT reading (stage overlap), or the context's stream
   hipStream_t lane = c->stream;
-  if (deep_ok(c) && ensure_alt_set(c, c->integ_stream)) {
+  if (deep_ok(c) && ensure_other_set(c, c->integ_stream)) {
     lane = c->integ_stream;
     const DrawLanes::Integrate I = c->lanes.integrate();
     if (I.record_end) HIP_TRY(c, record_draw_end(c, I.end));             // a draw without hole filling behind it: mark its end now
     if (I.join) HIP_TRY(c, wait_integ(c));                               // (bookkeeping only: the lane is in order, and a draw has normally consumed it)
-    swap_volume_set(c);
+    bind_volume_set(set_in_use(c), c->vol, c->tiles);                    // (the other set a moment ago: DrawLanes::integrate)
     if (I.wait_draw >= 0) HIP_TRY(c, hipStreamWaitEvent(lane, c->draw_done[I.wait_draw], 0));   // the draw two frames back read this set
     // the frame's images and brick state: from the lane ahead (both this lane and the context's stream wait for it), or from work on the context's stream
     hipError_t e;
@@ -1595,28 +1588,30 @@ int32_t tsdf_integrate(tsdf_ctx* c) {
   for (uint32_t i = 0; i < c->cfg.num_streams; ++i) lds = std::min(lds, c->lds_ok[i]);
   const bool want_cache = lds >= 2 && c->k1_form_cap >= 3 && c->proj_budget > 0 && !c->vol.slot && !c->proj_failed;
   lds = std::min(lds, c->k1_form_cap);
+  tsdf_ctx::VolSet& set = set_in_use(c);
+  const TileHistory::Begin T = set.history.begin(c->use_bricks);
+  const bool full_walk = set.history.full_walk();
   if (c->use_bricks) {
     // this frame's list / count, the previous integrate()'s (trusted unless something else may have written the volume)
     TileState& S = c->tiles;
-    const int p = c->tile_parity;
-    S.list = c->d_tile_list[p]; S.count = c->d_tile_counts + p;
-    S.prev_list = c->d_tile_list[p ^ 1]; S.prev_count = c->d_tile_counts + (p ^ 1); S.next_count = c->d_tile_counts + (p ^ 1);
-    if (++c->frame_stamp == 0) { c->frame_stamp = 1; c->full_classify = true; HIP_TRY(c, hipMemsetAsync(S.stamp, 0, (size_t)S.n * sizeof(uint32_t), lane)); }
+    S.list = set.list[T.list]; S.count = set.counts + T.list;
+    S.prev_list = set.list[T.prev]; S.prev_count = S.next_count = set.counts + T.prev;
+    if (T.wipe) HIP_TRY(c, hipMemsetAsync(S.stamp, 0, (size_t)S.n * sizeof(uint32_t), lane));
   }
   // the draw that follows would first reset the peel tiles its predecessor touched: let the classify launch do it
   PeelClear pc{};
   {
     const bool whole = whole_volume(c);
     // (with the lanes on the reset rides on the lane ahead: tsdf_mark_bricks)
-    if (const int m = c->tiles_img.peel_reset_classify(!deep && !pipelined(c) && c->use_bricks && !c->full_classify && c->skip_space && whole && c->d_peels); m >= 0) {
+    if (const int m = c->tiles_img.peel_reset_classify(!deep && !pipelined(c) && c->use_bricks && !full_walk && c->skip_space && whole && c->d_peels); m >= 0) {
       pc.peels = (uint4*)c->d_peels; pc.touched_prev = c->d_touched[m];                             // the previous draw's tiles
       pc.w = c->vw; pc.h = c->vh; pc.ntx = (c->vw + 7) / 8; pc.n_tiles = pc.ntx * ((c->vh + 7) / 8);
     }
   }
-  if (const int k = c->ahead.counters_zero_spare(c->use_bricks && !c->full_classify && !pipelined(c)); k >= 0) {   // ... and zero the spare counter buffer for the next clearOccupiedBricks() (the lane ahead clears its own)
+  if (const int k = c->ahead.counters_zero_spare(c->use_bricks && !full_walk && !pipelined(c)); k >= 0) {   // ... and zero the spare counter buffer for the next clearOccupiedBricks() (the lane ahead clears its own)
     pc.zero = c->d_counters[k]; pc.zero_words = (uint32_t)c->counter_words;
   }
-  if (c->use_bricks) launch_classify_tiles(lane, c->vol, c->br, c->tiles, c->full_classify, c->frame_stamp, pc);
+  if (c->use_bricks) launch_classify_tiles(lane, c->vol, c->br, c->tiles, full_walk, T.stamp, pc);
   // dense launches: the static half of the uniform-pair shortcut (k_integrate.hip), built once per calibration
   const float4* bounds = nullptr;
   const bool culled_ranges = c->use_bricks && c->culled_ranges && !c->vol.slot && (size_t)c->vol.n_stored_tiles * c->cfg.num_streams * 32 <= ((size_t)512 << 20);
@@ -1644,8 +1639,7 @@ int32_t tsdf_integrate(tsdf_ctx* c) {
   timer_begin_on(c, "k_integrate_tiles", lane);                                // the kernel(s) alone (bench.py's roofline)
   launch_integrate_tiles(lane, c->luts, c->frame, c->vol, c->br, c->tiles, plan, c->d_pair_masks, proj, c->d_work_recs);
   timer_end_on(c, "k_integrate_tiles", lane);
-  if (c->use_bricks) { c->tile_parity ^= 1; c->full_classify = false; }
-  else c->full_classify = true;                                       // a dense pass wrote every tile: the next culled frame must look at all of them
+  set.history.end(c->use_bricks);
   timer_end_on(c, "2integrate", lane);
   c->have_volume = true;
   HIP_TRY(c, hipGetLastError());
@@ -2224,13 +2218,13 @@ int32_t tsdf_set_tsdf_limit(tsdf_ctx* c, float limit) {
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, sync_ctx(c));
   c->vol.limit = limit;
-  launch_mark_all_mixed(c->stream, c->tiles);    // the clear value changed: no tile is known to hold it
-  c->full_classify = true;
-  if (c->alt.data) {                                                     // ... in either volume set
-    TileState other = c->tiles;
-    other.cls = c->alt.cls_all + (size_t)(c->vol.int_tz0 - c->vol.tz0) * c->vol.nty * c->vol.ntx;
-    launch_mark_all_mixed(c->stream, other);
-    c->alt.full = true;
+  for (int k = 0; k < 2; ++k) {                  // the clear value changed: no tile is known to hold it, in either volume set (the one in use first)
+    tsdf_ctx::VolSet& s = c->vset[c->lanes.set() ^ k];
+    if (!s.data) continue;
+    Volume V = c->vol; TileState S = c->tiles;
+    bind_volume_set(s, V, S);
+    launch_mark_all_mixed(c->stream, S);
+    s.history.invalidate();
   }
   HIP_TRY(c, sync_ctx(c));
   return TSDF_OK;
@@ -2350,7 +2344,7 @@ int32_t tsdf_upload_volume(tsdf_ctx* c, const float* in) {
   HIP_TRY(c, hipMemcpyAsync(c->d_linear, in, (size_t)c->res[0] * c->res[1] * c->res[2] * sizeof(float), hipMemcpyHostToDevice, c->stream));
   launch_volume_from_linear(c->stream, c->vol, c->d_linear);
   launch_mark_all_mixed(c->stream, c->tiles);
-  c->full_classify = true;
+  set_in_use(c).history.invalidate();
   c->have_volume = true;
   HIP_TRY(c, sync_ctx(c));
   return TSDF_OK;
@@ -2362,12 +2356,13 @@ int32_t tsdf_download_active_tiles(tsdf_ctx* c, uint32_t* ids, uint32_t capacity
   if (!count) return TSDF_ERR_INVALID_ARGUMENT;
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, sync_ctx(c));
-  const int p = c->tile_parity ^ 1;                                       // integrate() flipped the parity after its launches
+  const tsdf_ctx::VolSet& s = set_in_use(c);
+  const int p = s.history.last();
   uint32_t n = 0;
-  HIP_TRY(c, hipMemcpy(&n, c->d_tile_counts + p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(&n, s.counts + p, sizeof(uint32_t), hipMemcpyDeviceToHost));
   *count = n;
   if (grid) { grid[0] = (uint32_t)c->vol.ntx; grid[1] = (uint32_t)c->vol.nty; grid[2] = (uint32_t)c->vol.int_tz0; grid[3] = (uint32_t)c->tiles.n; }
-  if (ids && capacity) HIP_TRY(c, hipMemcpy(ids, c->d_tile_list[p], (size_t)std::min(n, capacity) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (ids && capacity) HIP_TRY(c, hipMemcpy(ids, s.list[p], (size_t)std::min(n, capacity) * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return TSDF_OK;
 }
 // which integrate kernel the last tsdf_integrate launched, its grid and its work items: host values of the launcher; the culled launch's
@@ -2380,7 +2375,8 @@ int32_t tsdf_integrate_form(tsdf_ctx* c, uint32_t out[4]) {
   if (c->last_k1.culled) {
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, sync_ctx(c));
-    HIP_TRY(c, hipMemcpy(&n, c->d_tile_counts + (c->tile_parity ^ 1), sizeof(uint32_t), hipMemcpyDeviceToHost));   // integrate() flipped the parity after its launches
+    const tsdf_ctx::VolSet& s = set_in_use(c);
+    HIP_TRY(c, hipMemcpy(&n, s.counts + s.history.last(), sizeof(uint32_t), hipMemcpyDeviceToHost));
   }
   out[0] = (uint32_t)c->last_k1.form; out[1] = c->last_k1.grid; out[2] = n; out[3] = c->last_k1.culled ? 1u : 0u;
   return TSDF_OK;

@@ -11,6 +11,7 @@
 #include "draw_lanes.hpp"
 #include "frame_intake.hpp"
 #include "result_paths.hpp"
+#include "volume_sets.hpp"
 #include "ray_staging.hpp"
 #include "texture_taps.hpp"
 
@@ -34,7 +35,6 @@ struct tsdf_ctx {
   float vox[3]{};
   Volume vol{};
   TileState tiles{};
-  uint8_t* d_cls_all = nullptr;      // tile class of every stored tile (owned + halo)
   int halo_layers = 0;
   // bricks
   float brick_req[3]{};          // requested size (setBrickSize argument)
@@ -47,9 +47,6 @@ struct tsdf_ctx {
   uint8_t* d_tile_full[3]{};
   uint16_t* d_brick_t0[3]{};
   uint16_t* d_brick_t1[3]{};
-  // active-tile lists of this and the previous integrate() (k_classify_lists), their two device counts, and what decides
-  // whether the next integrate() may trust the previous list
-  uint32_t* d_tile_list[2]{}; uint32_t* d_tile_counts = nullptr; int tile_parity = 0; bool full_classify = true; uint32_t frame_stamp = 0;
   uint32_t* d_occ_counts = nullptr;   // three occupied-brick count words: two used alternately (see Bricks::num_occupied), one spare (lane_ahead.hpp)
   uint32_t min_voxels = 10;      // recon_integration.cpp:59
   size_t counter_words = 0;
@@ -185,14 +182,16 @@ struct tsdf_ctx {
   // (abi.cpp: FillWorker), and a fourth lane, integrate() of frame f + 1 on `integ_stream` beside the draw of frame f.  The state and its protocol are
   // draw_lanes.hpp's -- which volume set and which pyramid are in use, what is in flight on the two lanes, which job of the helper a wait has to see
   // issued first.  Here: the streams, the events it indexes (fill_done[pyramid], draw_done[set]; integ_done; integ_gate: work queued on the context's
-  // stream that the integrate lane must not overtake), the helper and the second volume set
+  // stream that the integrate lane must not overtake), the helper and the two volume sets
   DrawLanes lanes{};
   hipStream_t fill_stream = nullptr; hipEvent_t fill_done[2] = {nullptr, nullptr};
   struct FillWorker; FillWorker* fill_worker = nullptr; bool fill_thread = true;
-  // `alt` holds the set not in use (allocated on the first integrate() on the lane): the volume, its tile classes, the lists / stamps / counts of the
-  // incremental classification.  Whole-volume contexts with dense storage only; off with stage overlap off, with the projection cache, and with RR_DEEP=0.
-  struct VolSet { float* data = nullptr; uint8_t* cls_all = nullptr; uint32_t* stamp = nullptr; uint32_t* list[2] = {nullptr, nullptr}; uint32_t* counts = nullptr;
-                  int parity = 0; bool full = true; uint32_t stampno = 0; } alt;
+  // The volume sets: the state and its protocol are volume_sets.hpp's -- which tile list and count word an integrate() writes and which it trusts, the
+  // frame stamp, when it walks every tile.  Here: the buffers its indices select -- per set the volume, the class of every stored tile (owned + halo), the
+  // stamps, the two active-tile lists and their two device counts (k_classify_lists).  vset[lanes.set()] is the set in use, bound into `vol` and `tiles`
+  // (abi.cpp: bind_volume_set); setup_volume allocates it, the first integrate() on the lane the other one: contexts that integrate every stored layer,
+  // with dense storage only; off with stage overlap off, with the projection cache, and with RR_DEEP=0.
+  struct VolSet { float* data = nullptr; uint8_t* cls = nullptr; uint32_t* stamp = nullptr; uint32_t* list[2]{}; uint32_t* counts = nullptr; TileHistory history{}; } vset[2];
   hipStream_t integ_stream = nullptr; hipEvent_t integ_done = nullptr, integ_gate = nullptr, draw_done[2] = {nullptr, nullptr};
   bool deep = true;
   hipStream_t pre_lane = nullptr; bool pre_on_integ = false;   // the stream the current frame's preparation runs on (pre_stream, or integ_stream: RR_PRE_ON_INTEG)

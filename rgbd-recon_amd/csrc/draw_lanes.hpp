@@ -18,9 +18,10 @@
 // (DrawEnd::wait_job).  Off while timers are on (their bookkeeping is the caller's thread's) and with RR_FILL_THREAD=0: fill_queued().
 //
 // ... and a fourth lane (round 3): integrate() of frame f + 1 beside the draw of frame f on the context's stream.  Everything integrate() writes
-// and the draw reads exists twice and alternates per integrate() (abi.cpp: swap_volume_set; here the index of the set in use), and each set
-// evolves exactly like the single volume of rounds 1 / 2, seeing every other frame (the reference rebuilds the TSDF from scratch every frame,
-// recon_integration.cpp:249-250: no state is carried from frame to frame).  Events: integ_done (the draw waits for its integrate: join_integ),
+// and the draw reads exists twice and alternates per integrate() (here the index of the set in use, which abi.cpp binds: bind_volume_set; what a
+// set remembers from one integrate() to the next: volume_sets.hpp), and each set evolves exactly like the single volume of rounds 1 / 2, seeing
+// every other frame (the reference rebuilds the TSDF from scratch every frame, recon_integration.cpp:249-250: no state is carried from frame to
+// frame).  Events: integ_done (the draw waits for its integrate: join_integ),
 // draw_done[set] (recorded behind the draw that read the set -- by fillColors(), else by the next integrate(), and again behind an overlay or
 // the mesh stream, which read the set after fillColors() --: the hole filling waits for it, and so does the integrate two frames later that
 // overwrites the set).

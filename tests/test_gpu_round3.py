@@ -289,6 +289,48 @@ def test_two_volume_sets_alternate_without_a_trace(rr, monkeypatch):
         compare_images(hip, orc2, f"new brick grid, frame {k}")
 
 
+def oracle_active_tiles(orc):
+    """how many storage tiles a culled integrate() computes: those that hold a voxel of an occupied brick's voxel list [lo, hi)"""
+    active = np.zeros([(r + 7) // 8 for r in orc.res], bool)
+    for lo0, lo1, lo2, hi0, hi1, hi2 in orc.brick_ranges()[orc.occupied()].astype(np.int64):
+        if hi0 > lo0 and hi1 > lo1 and hi2 > lo2:
+            active[lo0 >> 3:((hi0 - 1) >> 3) + 1, lo1 >> 3:((hi1 - 1) >> 3) + 1, lo2 >> 3:((hi2 - 1) >> 3) + 1] = True
+    return int(active.sum())
+
+
+@pytest.mark.parametrize("frames_before", [3, 4])
+def test_a_new_grid_under_the_integrate_lane_on_either_volume_set(rr, monkeypatch, frames_before):
+    """setVoxelSize releases both volume sets and sets one up again -- the one in use, which after an odd number of integrate() calls on the lane is the
+    second of the pair, after an even number the first; the other one is the next integrate()'s to allocate.  From either, volume, framebuffer and the
+    culled launch's work items (read back through the list the last integrate() wrote) must be the oracle's after every frame, before and after."""
+    mk = dict(n_streams=3, width=160, height=120, lut_res=24, inv_res=32)
+    scs = [rr.scene.make_scene(**mk), rr.scene.make_scene(**mk, sphere_c=(0.4, 0.7, -0.3), box_c=(-0.5, 1.5, 0.2)), rr.scene.make_scene(**mk, sphere_c=(-0.3, 1.3, 0.2))]
+    kw = dict(res=(64, 64, 64), brick_size=[2.0 / 8, 2.2 / 8, 2.0 / 8], limit=0.04, view=(160, 90))
+    pr = rr.scene.gl_flat(rr.scene.perspective(50.0, 16.0 / 9.0, 0.1, 200.0))
+    mvs = [rr.scene.gl_flat(rr.scene.look_at(e, (0.0, 1.1, 0.0))) for e in [(0.0, 1.1, 3.0), (1.6, 1.4, 2.4), (-2.2, 0.6, 1.2)]]
+    hip, orc = make_pair(rr, scs[0], True, monkeypatch, **kw), OracleRecon(scs[0], **kw)
+    n = [0]
+
+    def run(frames, what):
+        for _ in range(frames):
+            k = n[0]; n[0] += 1
+            for o in (hip, orc):
+                o.upload_frame(scs[[0, 1, 1, 2, 0, 2][k % 6]])
+                frame(o, mvs[k % 3], pr)
+            assert_same(hip.tsdf(), orc.tsdf(), f"volume, {what}, frame {k}")
+            (hc, hd), (oc, od) = hip.framebuffer(), orc.framebuffer()
+            assert_same(hd, od, f"framebuffer depth, {what}, frame {k}"); assert_same(hc, oc, f"framebuffer colour, {what}, frame {k}")
+            assert (od < 1).sum() > 100
+            f = hip.integrate_form()
+            assert f["culled"] and f["items"] == oracle_active_tiles(orc) > 0, f"work items, {what}, frame {k}: {f}"
+
+    run(frames_before, "first grid")
+    for o in (hip, orc):
+        o.setVoxelSize(0.045)
+    assert tuple(hip.res) == tuple(orc.res) == (45, 49, 45)
+    run(4, "second grid")
+
+
 @pytest.mark.parametrize("use_bricks", [True, False])
 def test_fourth_lane_back_to_back_frames(rr, monkeypatch, use_bricks):
     """Frames queued back to back with no host read in between -- integrate(f + 1) really runs beside march / shade(f) -- leave what a
