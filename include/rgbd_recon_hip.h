@@ -562,7 +562,7 @@ int32_t tsdf_download_atlas(tsdf_ctx* ctx, float* rgba, float* depth);          
  *   whose own class and whose seven +x/+y/+z neighbours' classes say "every voxel is -limit" (sparse pool: no slot) is skipped without reading a voxel.
  *   Timers "mesh_count", "mesh_scan", "mesh_emit".
  *   TSDF_ERR_STATE before the first tsdf_integrate / tsdf_upload_volume; for TSDF_MESH_COLOURS without calibration (cv_xyz_inv, cv_uv) and a frame; on a
- *   Z-slab context (welding slab meshes is deliberately out of scope: extract from a whole-volume context).  TSDF_ERR_INVALID_ARGUMENT for an unknown flag.
+ *   Z-slab context (a slab extracts its part of the mesh with tsdf_mesh_slab_extract, below: the parts concatenate to this mesh).  TSDF_ERR_INVALID_ARGUMENT for an unknown flag.
  *   TSDF_ERR_OUT_OF_MEMORY when the vertices do not fit uint32 or the allocation fails (no mesh is kept then).
  * tsdf_mesh_download copies the last extract's arrays: position [V][3], normal [V][3], colour [V][4], triangles [T][3]; any may be NULL.
  *   TSDF_ERR_STATE without an extract, and for an attribute the last extract did not produce.
@@ -603,6 +603,62 @@ int32_t tsdf_mesh_stats(tsdf_ctx* ctx, uint64_t out[4]);
  *   whichever extract was last; the stats count lattice tiles.  Error codes as tsdf_mesh_extract (Z-slab context, no volume yet, colours without
  *   calibration and a frame), and TSDF_ERR_INVALID_ARGUMENT for a level above 2. */
 int32_t tsdf_mesh_extract_lod(tsdf_ctx* ctx, uint32_t flags, uint32_t level, uint64_t* n_vertices, uint64_t* n_triangles);
+
+/* ---- mesh extraction on Z-slab contexts: parts that join byte for byte ------------------------------------
+ * At the multi-GPU configurations no whole-volume context exists; these entries extract the mesh where the volume is.  The mesh above is ordered by
+ * 8^3 lattice tile with the tile layer (z) outermost, nothing in it depends on an atomic, and slabs are tile aligned: the whole mesh IS the
+ * concatenation of per-slab parts in slab order, and no vertex needs welding.  tests/mesh_slab_reference.py restates the split in numpy on top of
+ * tests/mesh_reference.py and tests/mesh_lod_reference.py; the concatenated parts equal tsdf_mesh_extract_lod + tsdf_mesh_download of a whole-volume
+ * context byte for byte.
+ * Part.  A context that owns lattice tile layers [L0, L1) at level L (stride s = 1 << L, a lattice tile is 8 s voxels per axis: L0 = slab_z0 / (8 s),
+ *   L1 = slab_z1 / (8 s), or the lattice's last layer + 1 when the slab reaches the volume's top) extracts
+ *   vertices:  those whose owning lattice point lies in these layers, in the order of the whole mesh;
+ *   triangles: those of the cells whose origin lies in these layers, in the order of the whole mesh;
+ *   indices:   uint32, GLOBAL: into the concatenated vertex array.
+ *   Positions (the descent at levels 1 and 2 included), normals and colours are exactly those of the definitions above; the class skip applies as it does
+ *   there (a slab's halo layers count as "not clear", so a slab may read a tile the whole volume skips: the result is the same, the statistics are not).
+ *   slab_z0 must be a multiple of 8 s, slab_z1 too unless it is the volume's top: TSDF_ERR_INVALID_ARGUMENT otherwise.  Level 0 always qualifies.  A
+ *   whole-volume context is the one-slab case: the entries work on it and reproduce tsdf_mesh_extract_lod.
+ * What a slab cannot know by itself is two sets of numbers: how many vertices the slabs below it hold (one uint64), and, for the triangles of its top cell
+ *   layer, whose corners with lz = 8 are lattice points of the slab above, the per-tile vertex bases of that slab's first tile layer (ntx * nty uint32).
+ *   Everything else about those lattice points -- edge mask, inside bit, offset inside their tile -- the slab computes itself: inside a tile, plane 0 comes
+ *   first in the vertex order, so the offsets of its 64 lattice points depend on lattice planes 0 and 1 of that layer alone: voxel planes z1 and z1 + s,
+ *   s <= 4, inside the halo.
+ * Halo.  Precondition: the halo is current -- exchanged or recomputed -- exactly as for a raymarch on the slab.  It covers every voxel a part reads.  With
+ *   x = limit / 2 * res_z (the gradient's offset in voxel planes) a context stores H = 8 * ceil((2 x + 2) / 8) >= 2 x + 2 >= 8 planes beyond either face.
+ *   Lattice points and the descent's midpoints: an owned edge runs from voxel plane z to z + s <= z1, its midpoints lie between; the seam records read
+ *   z1 and z1 + s <= z1 + 4.  Gradient taps: a vertex lies at voxel coordinate c in [z0, z1] (t = a / (a - b) is in [0, 1]); the tap at c + x has the
+ *   trilinear footprint floor(c + x), floor(c + x) + 1 <= z1 + x + 1 <= z1 + H - 1, the tap at c - x the footprint floor(c - x) >= z0 - x - 1 >= z0 - H.
+ *   So the clamp of Z taps into the stored planes never acts on a finite position, and normals equal the whole volume's bit for bit.  (A slab that stored
+ *   no layer above a face below the volume's top would be refused with TSDF_ERR_STATE, never clamped silently; tsdf_create admits no such slab.)
+ *
+ * tsdf_mesh_slab_extract runs count, scan and the vertex emit over the owned layers, and the records of plane 0 of the first lattice tile layer above
+ *   them (the seam layer: a records-only pass of its 64 plane-0 lanes per tile; seam tiles take record slots from the same scan and add nothing to the
+ *   counts).  It synchronises and returns the part's counts (either pointer may be NULL).  The part is kept in a state of its own -- tsdf_mesh_download,
+ *   _stats, _components, _texture_taps and the others do not see it and keep answering as before -- until the next tsdf_mesh_slab_extract,
+ *   tsdf_set_voxel_size or tsdf_destroy.  The call drops the part of an earlier extract BEFORE it looks at its arguments: after a refused extract no part
+ *   exists, and _seam, _link, _download and _stats answer TSDF_ERR_STATE (unlike tsdf_mesh_extract_lod, whose refused call leaves the old mesh: here the
+ *   table's and the arrays' sizes depend on the level, and a caller must never fill buffers sized for another extract).
+ *   Error codes as tsdf_mesh_extract_lod (without its refusal of slab contexts), plus the alignment rule above.
+ *   Timers "mesh_slab_count", "mesh_slab_scan", "mesh_slab_emit".
+ * tsdf_mesh_slab_seam: out[nty][ntx] (lattice tiles of the extract's level) = the slab-local vertex base of every lattice tile of the slab's FIRST owned
+ *   layer: the exclusive scan value, defined for tiles without surface too.  This is what the slab below needs.
+ * tsdf_mesh_slab_link writes the triangles.  The first vertex of an own tile is vertex_base + its local base; of a tile of the layer above,
+ *   vertex_base + n_vertices + above_seam[tile]: the slab above must follow directly in the concatenation -- slabs are contiguous in z, in slab order, and
+ *   above_seam is that slab's tsdf_mesh_slab_seam table of an extract at the same level.  above_seam may be NULL only when the slab reaches the volume's
+ *   top (it is not read then): TSDF_ERR_INVALID_ARGUMENT otherwise.  TSDF_ERR_OUT_OF_MEMORY when vertex_base + n_vertices exceeds uint32, or, below the
+ *   top, when above_seam[tile] plus that seam tile's plane-0 vertices does behind it (checked on the host before anything is written).  Linking again
+ *   with another base is allowed and rewrites the triangles.  TSDF_ERR_STATE before an extract.  Timer "mesh_slab_link".
+ * tsdf_mesh_slab_download: the shapes of tsdf_mesh_download; any pointer may be NULL.  TSDF_ERR_STATE before an extract, for an attribute the extract did
+ *   not produce, and for the triangles before a link.
+ * tsdf_mesh_slab_stats: out = {owned lattice tiles, of those skipped by class, of those with surface, bytes of the part's mesh storage}.
+ * Out of scope.  Gaps between slabs.  Mesh streaming, components and texture taps on parts (run them where the concatenated mesh is).  The native RCCL
+ *   exchange: the two numbers travel by whatever carries the caller's other collectives (rgbd-recon_amd/multigpu.py: SlabDriver.extract_mesh). */
+int32_t tsdf_mesh_slab_extract(tsdf_ctx* ctx, uint32_t flags, uint32_t level, uint64_t* n_vertices, uint64_t* n_triangles);
+int32_t tsdf_mesh_slab_seam(tsdf_ctx* ctx, uint32_t* out);
+int32_t tsdf_mesh_slab_link(tsdf_ctx* ctx, uint64_t vertex_base, const uint32_t* above_seam);
+int32_t tsdf_mesh_slab_download(tsdf_ctx* ctx, float* position_xyz, float* normal_xyz, float* colour_rgba, uint32_t* triangles);
+int32_t tsdf_mesh_slab_stats(tsdf_ctx* ctx, uint64_t out[4]);
 
 /* ---- mesh streaming: the fused surface every frame, packed, through a pinned ring -------------------------
  * tsdf_mesh_extract is a one-shot export: it allocates, waits for the host twice and leaves 12..40 bytes per vertex in fp32.  A telepresence client hands
@@ -838,7 +894,7 @@ int32_t tsdf_texture_tap_stats(tsdf_ctx* ctx, uint64_t out[4]);
  * Errors.  TSDF_ERR_STATE without an extract (a Z-slab context extracts no mesh, so always there); for download, keep and filter without components of
  *   the current mesh.  TSDF_ERR_INVALID_ARGUMENT for a NULL keep or a NULL out.  -1 for a NULL context.
  * The streamed ring (tsdf_mesh_stream) filters by the same rule inside the frame: "mesh streaming: the filtered frame" below.
- * Out of scope.  Z-slab contexts.  Welding by position.  Geometric measures per component (area, volume, bounding box): the caller has the arrays.
+ * Out of scope.  Z-slab contexts (tsdf_mesh_slab_extract's parts join into one mesh on the host: label that one).  Welding by position.  Geometric measures per component (area, volume, bounding box): the caller has the arrays.
  *   A context that never calls these entries runs exactly what it ran before they existed. */
 typedef struct tsdf_mesh_component { uint32_t first_vertex, n_vertices, n_triangles, reserved /* 0 */; } tsdf_mesh_component;
 int32_t tsdf_mesh_components(tsdf_ctx* ctx, uint64_t* n_components);

@@ -598,6 +598,7 @@ class ReconIntegrationHip:
     def setVoxelSize(self, size):
         self._ck(self._L.tsdf_set_voxel_size(self._c, C.c_float(size)))
         self._mesh_counts = None                                       # (the mesh went with the old grid)
+        self._mesh_slab = None
         r3, b3, s3 = (C.c_uint32 * 3)(), (C.c_uint32 * 3)(), (C.c_float * 3)()
         self._ck(self._L.tsdf_get_resolution(self._c, r3, b3, s3))
         self.res, self.res_bricks, self.brick_size = tuple(r3), tuple(b3), tuple(s3)
@@ -772,6 +773,54 @@ class ReconIntegrationHip:
         """dict of the last extract_mesh: tiles, tiles_skipped (by class, no voxel read), tiles_with_surface, bytes (of mesh storage)"""
         out = (C.c_uint64 * 4)()
         self._ck(self._L.tsdf_mesh_stats(self._c, out))
+        return dict(tiles=int(out[0]), tiles_skipped=int(out[1]), tiles_with_surface=int(out[2]), bytes=int(out[3]))
+
+    # ------------------------------------------------------------------ a Z-slab's part of the mesh (no counterpart in the reference)
+    def extract_mesh_slab(self, normals=True, colours=True, level=0):
+        """This context's part of the whole volume's mesh (tsdf_mesh_slab_extract): vertices of the owned lattice tile layers -> (n_vertices,
+        n_triangles).  The halo must be current, as for a draw.  The triangles exist after mesh_slab_link."""
+        nv, nt = C.c_uint64(), C.c_uint64()
+        flags = (MESH_NORMALS if normals else 0) | (MESH_COLOURS if colours else 0)
+        self._mesh_slab = None
+        self._ck(self._L.tsdf_mesh_slab_extract(self._c, C.c_uint32(flags), C.c_uint32(int(level)), C.byref(nv), C.byref(nt)))
+        s = 8 << int(level)
+        self._mesh_slab = (nv.value, nt.value, (-(-self.res[1] // s), -(-self.res[0] // s)))
+        return nv.value, nt.value
+
+    def mesh_slab_seam(self):
+        """[nty][ntx] uint32: the slab-local vertex base of every lattice tile of the first owned layer (tsdf_mesh_slab_seam): what the slab below links with"""
+        if getattr(self, "_mesh_slab", None) is None:                    # (no sizes: nothing may be copied into a buffer of this method's)
+            raise TsdfError(-4, "no slab mesh (extract_mesh_slab)")
+        out = np.zeros(self._mesh_slab[2], np.uint32)
+        self._ck(self._L.tsdf_mesh_slab_seam(self._c, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def mesh_slab_link(self, vertex_base, above_seam=None):
+        """Write the part's triangles with global indices (tsdf_mesh_slab_link): vertex_base = the vertices of the slabs below, above_seam = the
+        mesh_slab_seam() of the slab directly above (None at the volume's top)."""
+        above = None if above_seam is None else np.ascontiguousarray(above_seam, np.uint32)
+        self._ck(self._L.tsdf_mesh_slab_link(self._c, C.c_uint64(int(vertex_base)), above.ctypes.data_as(C.POINTER(C.c_uint32)) if above is not None else None))
+
+    def mesh_slab_download(self, normals=True, colours=True, triangles=True):
+        """dict of the part's arrays, shaped as download_mesh's (TsdfError, code -4, before an extract, and for the triangles before a link)"""
+        if getattr(self, "_mesh_slab", None) is None:
+            raise TsdfError(-4, "no slab mesh (extract_mesh_slab)")
+        nv, nt = self._mesh_slab[:2]
+        out = dict(position=np.zeros((nv, 3), np.float32))
+        if triangles:
+            out["triangles"] = np.zeros((nt, 3), np.uint32)
+        if normals:
+            out["normal"] = np.zeros((nv, 3), np.float32)
+        if colours:
+            out["colour"] = np.zeros((nv, 4), np.float32)
+        self._ck(self._L.tsdf_mesh_slab_download(self._c, _fp(out["position"]), _fp(out.get("normal")), _fp(out.get("colour")),
+                                                 out["triangles"].ctypes.data_as(C.POINTER(C.c_uint32)) if triangles else None))
+        return out
+
+    def mesh_slab_stats(self):
+        """dict of the last extract_mesh_slab: tiles (owned lattice tiles), tiles_skipped, tiles_with_surface, bytes"""
+        out = (C.c_uint64 * 4)()
+        self._ck(self._L.tsdf_mesh_slab_stats(self._c, out))
         return dict(tiles=int(out[0]), tiles_skipped=int(out[1]), tiles_with_surface=int(out[2]), bytes=int(out[3]))
 
     # ------------------------------------------------------------------ mesh components (no counterpart in the reference)

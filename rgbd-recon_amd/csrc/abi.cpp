@@ -683,8 +683,16 @@ void release_mesh_stream(tsdf_ctx* c) {
   F = MeshStreamFilter{};
   R.allocated = false; R.ring.reset(); R.device_bytes = 0;
 }
+// a slab's part of the mesh and what its link needs (nothing queued reads them: extract, link and download synchronise)
+void release_mesh_slab(tsdf_ctx* c) {
+  tsdf_ctx::MeshSlabPart& P = c->mslab;
+  hipFree(P.pos); hipFree(P.nrm); hipFree(P.col); hipFree(P.tri); hipFree(P.above);
+  mesh_scratch_free(P.scratch, P.records);
+  P = tsdf_ctx::MeshSlabPart{};
+}
 void release_volume(tsdf_ctx* c) {
   release_mesh(c); c->have_volume = false;                             // (a mesh belongs to the grid it was extracted from)
+  release_mesh_slab(c);
   release_mesh_stream(c);                                              // (... and the streaming scratch is sized by its tiles)
   for (tsdf_ctx::VolSet& s : c->vset) free_volume_set(s);              // (both callers have synchronised the stream)
   hipFree(c->vol.slot);
@@ -2480,7 +2488,7 @@ int32_t tsdf_mesh_extract_lod(tsdf_ctx* c, uint32_t flags, uint32_t level, uint6
   CHECK_CTX(c);
   if (flags & ~(TSDF_MESH_NORMALS | TSDF_MESH_COLOURS)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "unknown mesh flag");
   if (level > (uint32_t)kMeshMaxLevel) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "mesh level %u (0 .. %d: every voxel, every 2nd, every 4th)", level, kMeshMaxLevel);
-  if (int32_t rc = readable_volume_check(c, "tsdf_mesh_extract on a Z-slab context: welding slab meshes is not provided", (flags & TSDF_MESH_COLOURS) != 0)) return rc;
+  if (int32_t rc = readable_volume_check(c, "tsdf_mesh_extract on a Z-slab context: a slab extracts its part with tsdf_mesh_slab_extract", (flags & TSDF_MESH_COLOURS) != 0)) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   release_mesh(c);                                                       // (nothing queued reads it: extract and download synchronise)
   tsdf_ctx::Mesh& M = c->mesh;
@@ -2567,6 +2575,143 @@ int32_t tsdf_mesh_stats(tsdf_ctx* c, uint64_t out[4]) {
   int32_t rc = mesh_attribute_check(c, false, false);
   if (rc) return rc;
   for (int k = 0; k < 4; ++k) out[k] = c->mesh.stats[k];
+  return TSDF_OK;
+}
+
+// ---- a Z-slab's part of the mesh (k_mesh_slab.hip; the definition is in the header).  Extract: count, scan and vertices of the owned lattice tile layers
+// and the records of the seam layer's plane 0; link: the triangles, once the caller knows where the part starts and what the slab above begins with.
+static uint64_t mesh_slab_bytes(const tsdf_ctx::MeshSlabPart& P) {
+  return P.nv * (3 + ((P.flags & TSDF_MESH_NORMALS) ? 3 : 0) + ((P.flags & TSDF_MESH_COLOURS) ? 4 : 0)) * sizeof(float) + P.nt * 3 * sizeof(uint32_t);
+}
+int32_t tsdf_mesh_slab_extract(tsdf_ctx* c, uint32_t flags, uint32_t level, uint64_t* n_vertices, uint64_t* n_triangles) {
+  CHECK_CTX(c);
+  // The part of an earlier extract goes FIRST, before any argument is looked at: whatever this call answers, seam / link / download / stats never
+  // serve a part whose sizes the caller no longer holds (nothing queued reads it: extract, link and download synchronise).
+  HIP_TRY(c, hipSetDevice(c->device));
+  release_mesh_slab(c);
+  if (flags & ~(TSDF_MESH_NORMALS | TSDF_MESH_COLOURS)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "unknown mesh flag");
+  if (level > (uint32_t)kMeshMaxLevel) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "mesh level %u (0 .. %d: every voxel, every 2nd, every 4th)", level, kMeshMaxLevel);
+  if (!c->have_volume) FAIL(c, TSDF_ERR_STATE, "no volume yet (tsdf_integrate or tsdf_upload_volume)");
+  if (flags & TSDF_MESH_COLOURS) if (int32_t rc = require_inputs(c, false, true)) return rc;
+  const Volume& V = c->vol;
+  const MeshLattice L = mesh_lattice(V.res, (int)level);
+  const int stride = 1 << level;
+  const bool top = V.own_tz1 == (c->res[2] + 7) / 8;
+  if (V.own_tz0 % stride != 0 || (!top && V.own_tz1 % stride != 0))
+    FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "slab planes [%d, %d) do not lie on level %u's lattice tiles (%d planes each)", V.own_tz0 * 8, V.own_tz1 * 8, level, 8 * stride);
+  // The halo holds every plane a vertex of this slab reads (the header says why): voxel plane z1 + stride for the seam records, and the gradient taps'
+  // footprint x + 1 planes past either face, x = limit / 2 * res_z, against 8 * halo_layers >= 2 x + 2.  Checked all the same, never clamped silently.
+  if (!top && V.tz1 - V.own_tz1 < 1) FAIL(c, TSDF_ERR_STATE, "the slab stores no halo layer above its planes");
+  tsdf_ctx::MeshSlabPart& P = c->mslab;
+  const int layer0 = V.own_tz0 >> level, layer1 = top ? L.ntz : (V.own_tz1 >> level);
+  P.slab = MeshSlab{layer0, (layer1 - layer0) * L.ntx * L.nty, top ? 0 : L.ntx * L.nty};
+  P.ntx = L.ntx; P.nty = L.nty; P.flags = flags;
+  P.seam_cnt.assign((size_t)P.slab.n_seam, 0u);
+  P.stats[0] = (uint64_t)P.slab.n_own;
+  const int n_tiles = P.slab.n_own + P.slab.n_seam, nb = mesh_scan_blocks(n_tiles);
+  uint64_t totals[4] = {0, 0, 0, 0}, seam_vertices = 0, seam_surface = 0;
+  if (L.cr[0] >= 2 && L.cr[1] >= 2 && L.cr[2] >= 2 && P.slab.n_own > 0) {   // (a lattice one point thick has no cell)
+    MeshScratch& S = P.scratch;
+    auto fail = [&](hipError_t e) { (void)hipGetLastError(); release_mesh_slab(c); c->err = std::string("tsdf_mesh_slab_extract: ") + hipGetErrorString(e);
+                                    return e == hipErrorOutOfMemory ? TSDF_ERR_OUT_OF_MEMORY : TSDF_ERR_HIP; };
+    if (const hipError_t e = mesh_scratch_allocate(S, n_tiles, (int)level, nullptr)) return fail(e);
+    HIP_TRY(c, join_integ(c));                                           // the volume tsdf_download_volume would return now
+    if (flags & TSDF_MESH_COLOURS) HIP_TRY(c, join_pre(c));              // ... and the current frame slot's images
+    timer_begin(c, "mesh_slab_count");
+    launch_mesh_slab_count(c->stream, V, S, P.slab);
+    timer_end(c, "mesh_slab_count");
+    timer_begin(c, "mesh_slab_scan");
+    launch_mesh_scan(c->stream, S);
+    timer_end(c, "mesh_slab_scan");
+    if (const hipError_t e = hipGetLastError()) return fail(e);
+    std::vector<uint2> seam((size_t)P.slab.n_seam);
+    if (const hipError_t e = hipMemcpyAsync(totals, (const char*)S.sums + (size_t)nb * sizeof(totals), sizeof(totals), hipMemcpyDeviceToHost, c->stream)) return fail(e);
+    if (P.slab.n_seam)
+      if (const hipError_t e = hipMemcpyAsync(seam.data(), S.tile_cnt + P.slab.n_own, seam.size() * sizeof(uint2), hipMemcpyDeviceToHost, c->stream)) return fail(e);
+    if (const hipError_t e = sync_ctx(c)) return fail(e);
+    if (totals[0] > 0xffffffffull) { release_mesh_slab(c); FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "%llu vertices do not fit 32-bit indices", (unsigned long long)totals[0]); }
+    for (size_t k = 0; k < seam.size(); ++k) { P.seam_cnt[k] = seam[k].x; seam_vertices += seam[k].x; seam_surface += seam[k].x ? 1u : 0u; }
+    if (totals[2]) {                                                     // tiles with surface, seam tiles included: records for all of them
+      const size_t nv = (size_t)(totals[0] - seam_vertices), nt = (size_t)totals[1];
+      bool ok = hipMalloc((void**)&P.pos, std::max<size_t>(nv, 1) * 3 * sizeof(float)) == hipSuccess &&
+                hipMalloc((void**)&P.tri, std::max<size_t>(nt, 1) * 3 * sizeof(uint32_t)) == hipSuccess &&
+                hipMalloc((void**)&P.records, (size_t)totals[2] * 512 * sizeof(uint32_t)) == hipSuccess;
+      if (ok && (flags & TSDF_MESH_NORMALS)) ok = hipMalloc((void**)&P.nrm, std::max<size_t>(nv, 1) * 3 * sizeof(float)) == hipSuccess;
+      if (ok && (flags & TSDF_MESH_COLOURS)) ok = hipMalloc((void**)&P.col, std::max<size_t>(nv, 1) * 4 * sizeof(float)) == hipSuccess;
+      if (!ok) { (void)hipGetLastError(); release_mesh_slab(c); FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "no device memory for a slab mesh of %zu vertices and %zu triangles", nv, nt); }
+      timer_begin(c, "mesh_slab_emit");
+      launch_mesh_slab_vertices(c->stream, V, c->luts, c->frame, mesh_geometry(c), S, P.slab, P.records, P.pos, P.nrm, P.col);
+      timer_end(c, "mesh_slab_emit");
+      if (const hipError_t e = hipGetLastError()) return fail(e);
+      if (const hipError_t e = sync_ctx(c)) return fail(e);
+    }
+  }
+  P.nv = totals[0] - seam_vertices; P.nt = totals[1]; P.valid = true; P.linked = false;
+  P.stats[1] = totals[3]; P.stats[2] = totals[2] - seam_surface;
+  P.stats[3] = mesh_slab_bytes(P);
+  if (n_vertices) *n_vertices = P.nv;
+  if (n_triangles) *n_triangles = P.nt;
+  return TSDF_OK;
+}
+int32_t tsdf_mesh_slab_seam(tsdf_ctx* c, uint32_t* out) {
+  CHECK_CTX(c);
+  if (!out) return TSDF_ERR_INVALID_ARGUMENT;
+  const tsdf_ctx::MeshSlabPart& P = c->mslab;
+  if (!P.valid) FAIL(c, TSDF_ERR_STATE, "no slab mesh (tsdf_mesh_slab_extract)");
+  const size_t n = (size_t)P.ntx * P.nty;
+  if (!P.scratch.tile_vbase) { std::fill(out, out + n, 0u); return TSDF_OK; }   // (a lattice without a cell: nothing was counted)
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipMemcpy(out, P.scratch.tile_vbase, n * sizeof(uint32_t), hipMemcpyDeviceToHost));   // the first owned layer's tiles come first
+  return TSDF_OK;
+}
+int32_t tsdf_mesh_slab_link(tsdf_ctx* c, uint64_t vertex_base, const uint32_t* above_seam) {
+  CHECK_CTX(c);
+  tsdf_ctx::MeshSlabPart& P = c->mslab;
+  if (!P.valid) FAIL(c, TSDF_ERR_STATE, "no slab mesh (tsdf_mesh_slab_extract)");
+  const bool top = c->vol.own_tz1 == (c->res[2] + 7) / 8;
+  if (!above_seam && !top) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "a slab below the volume's top needs the seam table of the slab above");
+  // every index the triangles can hold, from what the host knows: the slab's own vertices, and per seam tile the plane-0 vertices behind its base
+  uint64_t end = vertex_base + P.nv;
+  if (above_seam)
+    for (size_t k = 0; k < P.seam_cnt.size(); ++k)
+      if (P.seam_cnt[k]) end = std::max(end, vertex_base + P.nv + above_seam[k] + P.seam_cnt[k]);
+  if (end > 0xffffffffull || vertex_base > 0xffffffffull) FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "indices up to %llu do not fit 32 bits", (unsigned long long)end);
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (P.nt) {
+    if (P.slab.n_seam) {
+      if (!P.above) HIP_TRY(c, hipMalloc((void**)&P.above, (size_t)P.slab.n_seam * sizeof(uint32_t)));
+      HIP_TRY(c, hipMemcpyAsync(P.above, above_seam, (size_t)P.slab.n_seam * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    }
+    timer_begin(c, "mesh_slab_link");
+    launch_mesh_slab_triangles(c->stream, c->vol, P.scratch, P.slab, P.records, (uint32_t)vertex_base, (uint32_t)P.nv, P.above, P.tri);
+    timer_end(c, "mesh_slab_link");
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, sync_ctx(c));                                             // (above_seam is the caller's again)
+  }
+  P.linked = true;
+  return TSDF_OK;
+}
+int32_t tsdf_mesh_slab_download(tsdf_ctx* c, float* position_xyz, float* normal_xyz, float* colour_rgba, uint32_t* triangles) {
+  CHECK_CTX(c);
+  const tsdf_ctx::MeshSlabPart& P = c->mslab;
+  if (!P.valid) FAIL(c, TSDF_ERR_STATE, "no slab mesh (tsdf_mesh_slab_extract)");
+  if (normal_xyz && !(P.flags & TSDF_MESH_NORMALS)) FAIL(c, TSDF_ERR_STATE, "the last tsdf_mesh_slab_extract produced no normals");
+  if (colour_rgba && !(P.flags & TSDF_MESH_COLOURS)) FAIL(c, TSDF_ERR_STATE, "the last tsdf_mesh_slab_extract produced no colours");
+  if (triangles && !P.linked) FAIL(c, TSDF_ERR_STATE, "the slab's triangles have no indices yet (tsdf_mesh_slab_link)");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (P.nv) {
+    if (position_xyz) HIP_TRY(c, hipMemcpy(position_xyz, P.pos, (size_t)P.nv * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (normal_xyz) HIP_TRY(c, hipMemcpy(normal_xyz, P.nrm, (size_t)P.nv * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (colour_rgba) HIP_TRY(c, hipMemcpy(colour_rgba, P.col, (size_t)P.nv * 4 * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  if (P.nt && triangles) HIP_TRY(c, hipMemcpy(triangles, P.tri, (size_t)P.nt * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return TSDF_OK;
+}
+int32_t tsdf_mesh_slab_stats(tsdf_ctx* c, uint64_t out[4]) {
+  CHECK_CTX(c);
+  if (!out) return TSDF_ERR_INVALID_ARGUMENT;
+  if (!c->mslab.valid) FAIL(c, TSDF_ERR_STATE, "no slab mesh (tsdf_mesh_slab_extract)");
+  for (int k = 0; k < 4; ++k) out[k] = c->mslab.stats[k];
   return TSDF_OK;
 }
 
@@ -2837,7 +2982,7 @@ int32_t tsdf_mesh_stream(tsdf_ctx* c, uint64_t tag) {
   tsdf_ctx::MeshStream& R = c->mstream;
   if (!R.configured) FAIL(c, TSDF_ERR_STATE, "tsdf_mesh_stream before tsdf_mesh_stream_config");
   int32_t rc;
-  if ((rc = readable_volume_check(c, "tsdf_mesh_stream on a Z-slab context: welding slab meshes is not provided", (R.flags & TSDF_MESH_COLOURS) != 0))) return rc;
+  if ((rc = readable_volume_check(c, "tsdf_mesh_stream on a Z-slab context: slab parts (tsdf_mesh_slab_extract) are not streamed", (R.flags & TSDF_MESH_COLOURS) != 0))) return rc;
   if (R.ring.full()) FAIL(c, TSDF_ERR_STATE, "all %u mesh stream slots are queued or held (tsdf_mesh_stream_acquire / tsdf_mesh_stream_release)", R.ring.slots);
   HIP_TRY(c, hipSetDevice(c->device));
   if (!R.allocated && (rc = mesh_stream_allocate(c))) return rc;

@@ -132,6 +132,13 @@ struct tsdf_ctx {
   // extract allocates (per-tile counts, the lattice-point records) is gone when it returns.
   struct Mesh { float* pos = nullptr; float* nrm = nullptr; float* col = nullptr; uint32_t* tri = nullptr; uint64_t nv = 0, nt = 0; uint32_t flags = 0; bool valid = false;
                 uint64_t stats[4] = {0, 0, 0, 0}; } mesh;
+  // a Z-slab's part of the mesh (tsdf_mesh_slab_extract): a state of its own, so that everything built on `mesh` keeps refusing on a slab context.  The
+  // vertex arrays and the triangle array (sized from the counts; the triangles are written by tsdf_mesh_slab_link, `linked` says whether they have been),
+  // and what a link needs again: the scratch over owned + seam tiles, the records, the device copy of the table it was handed.  seam_cnt: the seam
+  // tiles' plane-0 vertex counts on the host (the link's index check).  All of it lives until the next slab extract, tsdf_set_voxel_size or destroy.
+  struct MeshSlabPart { float* pos = nullptr; float* nrm = nullptr; float* col = nullptr; uint32_t* tri = nullptr; uint32_t* records = nullptr; uint32_t* above = nullptr;
+                        MeshScratch scratch{}; MeshSlab slab{}; int ntx = 0, nty = 0; std::vector<uint32_t> seam_cnt;
+                        uint64_t nv = 0, nt = 0; uint32_t flags = 0; bool valid = false, linked = false; uint64_t stats[4] = {0, 0, 0, 0}; } mslab;
   // mesh components (tsdf_mesh_components): the labels and the table of the current mesh, beside it in device memory; released with the mesh and by a
   // keep / filter (the mesh they labelled is gone then).  n / largest: components and the largest one's triangles of that labelling; removed_*: what the
   // last keep / filter of this extract took away.  Everything else a call allocates is gone when it returns.

@@ -17,19 +17,9 @@
 // then mean a tile of 8^3 LATTICE points ((8 << level)^3 voxels) and its points; MeshLattice holds that geometry.  Every kernel that knows the lattice is
 // instantiated per level; level 0 is the text it was, the lattice being the voxel grid.  A vertex of a coarse edge is the level-0 vertex of the voxel edge a
 // bisection along the edge ends on (mesh_descend: `level` voxel reads), so no position is interpolated over more than one voxel.
-#include <cfloat>
-#include <type_traits>
-
-#include "blend_dev.hpp"
-#include "scan_dev.hpp"
+#include "tsdf_common.hpp"
 
 namespace rr {
-
-constexpr int kMeshThreads = 512;            // one lane per lattice point of a tile
-constexpr int kMeshWaves = kMeshThreads / 64;
-constexpr int kMeshCorners = 9 * 9 * 9;      // a tile's lattice points and their +x/+y/+z neighbours
-constexpr int kScanThreads = 256, kScanPerThread = 4, kScanPerBlock = kScanThreads * kScanPerThread;
-
 // Kuhn's six tetrahedra along the diagonal c0 - c7 (corner b = bx + 2 by + 4 bz).  Every vertex list is a chain of bit sets, so every
 // tetrahedron edge runs from a corner to one that contains it: the edge (x, y), x < y, is edge d = y - x of lattice point p + x.
 __constant__ uint8_t c_tet[6][4] = {{0, 1, 3, 7}, {0, 1, 5, 7}, {0, 2, 3, 7}, {0, 2, 6, 7}, {0, 4, 5, 7}, {0, 4, 6, 7}};
@@ -37,30 +27,17 @@ __constant__ uint8_t c_tet[6][4] = {{0, 1, 3, 7}, {0, 1, 5, 7}, {0, 2, 3, 7}, {0
 // vertices v_k.  Tetrahedra 0, 3, 4 are positively oriented, 1, 2, 5 negatively; generated from the rule "the geometric normal points
 // from the inside corners to the outside corners" (tests/mesh_reference.py: winding_table(), which the CPU tests compare with these words).
 __constant__ uint16_t c_mesh_flip[6] = {0x4d24, 0x32da, 0x32da, 0x4d24, 0x4d24, 0x32da};
+}  // namespace rr
+#define RR_MESH_TABLES_DEFINED   // (mesh_dev.hpp asks for it: its functions read the two tables)
 
-// a voxel as the mesh reads it: NaN and +-inf read as -limit (NaN voxels exist, tsdf_integration.vs:52)
-__device__ __forceinline__ float mesh_value(float f, float limit) { return fabsf(f) <= FLT_MAX ? f : -limit; }
+#include "mesh_dev.hpp"
+#include "scan_dev.hpp"
 
-struct MeshTile { int tx, ty, tz, id; };
-// The lattice inside a kernel.  A level holds the MeshLattice of the volume's resolution (tsdf_common.hpp: the one definition, the host sizes the launch
-// by it).  Level 0 is the voxel grid and its storage tiles and reads the volume's own fields where they are used: the kernels' text before there were
-// levels (a copy made at the kernel's head costs k_mesh_triangles a scalar register and another block layout).
-template <int kLevel>
-struct LatticeOf {
-  MeshLattice g;
-  __device__ __forceinline__ explicit LatticeOf(const Volume& V) : g(mesh_lattice(V.res, kLevel)) {}
-  __device__ __forceinline__ int cr(int a) const { return g.cr[a]; }
-  __device__ __forceinline__ int ntx() const { return g.ntx; }
-  __device__ __forceinline__ int nty() const { return g.nty; }
-};
-template <>
-struct LatticeOf<0> {
-  const Volume& V;
-  __device__ __forceinline__ explicit LatticeOf(const Volume& v) : V(v) {}
-  __device__ __forceinline__ int cr(int a) const { return V.res[a]; }
-  __device__ __forceinline__ int ntx() const { return V.ntx; }
-  __device__ __forceinline__ int nty() const { return V.nty; }
-};
+namespace rr {
+
+constexpr int kScanThreads = 256, kScanPerThread = 4, kScanPerBlock = kScanThreads * kScanPerThread;
+
+// the lattice of a level, the corner stage, a lattice point's record and the per-tile emit bodies: mesh_dev.hpp (shared with k_mesh_slab.hip)
 template <int kLevel>
 __device__ __forceinline__ MeshTile mesh_tile(const LatticeOf<kLevel>& L) {
   MeshTile t;
@@ -69,73 +46,6 @@ __device__ __forceinline__ MeshTile mesh_tile(const LatticeOf<kLevel>& L) {
   t.tz = layer; t.ty = in_layer / L.ntx(); t.tx = in_layer - t.ty * L.ntx();
   return t;
 }
-__device__ __forceinline__ int corner_index(int lx, int ly, int lz) { return (lz * 9 + ly) * 9 + lx; }
-
-// one voxel, sanitised; (x, y, z) inside the grid
-template <bool kSparse>
-__device__ __forceinline__ float mesh_voxel(const Volume& V, int x, int y, int z) {
-  return mesh_value(kSparse ? tsdf_tap_sparse(V, x, y, z) : V.data[vol_index(V, x, y, z)], V.limit);
-}
-// the tile's 9 x 9 x 9 corner values -> LDS; a corner outside the lattice reads -limit (no edge and no cell reaches it: see mesh_point).  Lattice point
-// (x, y, z) is voxel (x, y, z) << level: a point sample (the last lattice point times the stride is below the resolution, cr = ceil(res / stride))
-template <bool kSparse, int kLevel>
-__device__ __forceinline__ void mesh_stage(const Volume& V, const LatticeOf<kLevel>& L, const MeshTile& t, float* s_f) {
-  for (int i = threadIdx.x; i < kMeshCorners; i += kMeshThreads) {
-    const int lx = i % 9, ly = (i / 9) % 9, lz = i / 81;
-    const int x = t.tx * 8 + lx, y = t.ty * 8 + ly, z = t.tz * 8 + lz;
-    float f = -V.limit;
-    if (x < L.cr(0) && y < L.cr(1) && z < L.cr(2)) f = mesh_voxel<kSparse>(V, x << kLevel, y << kLevel, z << kLevel);
-    s_f[i] = f;
-  }
-}
-// Descent of a crossed lattice edge P -> P + (d << level) to the voxel edge that carries its vertex: bisection, the end on the midpoint's side of the
-// surface moves to the midpoint (a midpoint is a voxel read, never the LDS stage: it is no lattice point).  In: (x, y, z) = P as a voxel, a = f(P),
-// b = f(other end).  Out: neighbouring voxels (x, y, z), (x, y, z) + d with their values, exactly one of them inside, as on entry.
-template <bool kSparse, int kLevel>
-__device__ __forceinline__ void mesh_descend(const Volume& V, int bx, int by, int bz, int& x, int& y, int& z, float& a, float& b) {
-  const bool inside = a > 0.0f;
-#pragma unroll
-  for (int h = (1 << kLevel) >> 1; h >= 1; h >>= 1) {
-    const int mx = x + h * bx, my = y + h * by, mz = z + h * bz;
-    const float m = mesh_voxel<kSparse>(V, mx, my, mz);
-    if ((m > 0.0f) == inside) { a = m; x = mx; y = my; z = mz; } else b = m;
-  }
-}
-
-// What lattice point `lane` of the tile owns: its edge mask (bit d - 1: the edge p -> p + d lies inside the lattice and exactly one
-// of its ends is inside the surface), whether p itself is inside, and the triangles of the cell whose origin it is.
-struct MeshPoint { uint32_t mask, inside, ntri; };
-__device__ __forceinline__ uint32_t tet_triangles(uint32_t corners, int k) {   // corners: bit b = corner b is inside
-  const uint32_t n = ((corners >> c_tet[k][0]) & 1u) + ((corners >> c_tet[k][1]) & 1u) + ((corners >> c_tet[k][2]) & 1u) + ((corners >> c_tet[k][3]) & 1u);
-  return n == 2u ? 2u : ((n == 1u || n == 3u) ? 1u : 0u);
-}
-__device__ __forceinline__ uint32_t cell_triangles(uint32_t corners) {
-  uint32_t n = 0;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) n += tet_triangles(corners, k);
-  return n;
-}
-template <int kLevel>
-__device__ __forceinline__ MeshPoint mesh_point(const LatticeOf<kLevel>& L, const MeshTile& t, const float* s_f, int lane) {
-  const int lx = lane & 7, ly = (lane >> 3) & 7, lz = lane >> 6;
-  const int x = t.tx * 8 + lx, y = t.ty * 8 + ly, z = t.tz * 8 + lz;
-  MeshPoint p{0u, 0u, 0u};
-  if (x >= L.cr(0) || y >= L.cr(1) || z >= L.cr(2)) return p;
-  p.inside = s_f[corner_index(lx, ly, lz)] > 0.0f ? 1u : 0u;          // the raymarch's hit test, tsdf_raymarch.fs:96: zero and -0 are outside
-  uint32_t corners = p.inside;
-#pragma unroll
-  for (int d = 1; d < 8; ++d) {
-    const int bx = d & 1, by = (d >> 1) & 1, bz = d >> 2;
-    if (x + bx < L.cr(0) && y + by < L.cr(1) && z + bz < L.cr(2)) {
-      const uint32_t in = s_f[corner_index(lx + bx, ly + by, lz + bz)] > 0.0f ? 1u : 0u;
-      corners |= in << d;
-      if (in != p.inside) p.mask |= 1u << (d - 1);
-    }
-  }
-  if (x + 1 < L.cr(0) && y + 1 < L.cr(1) && z + 1 < L.cr(2)) p.ntri = cell_triangles(corners);
-  return p;
-}
-
 // ---- 1. count
 template <bool kSparse, int kLevel>
 __global__ __launch_bounds__(kMeshThreads) void k_mesh_count(Volume V, uint2* __restrict__ tile_cnt, uint8_t* __restrict__ tile_skip) {
@@ -266,46 +176,11 @@ __global__ __launch_bounds__(kMeshThreads) void k_mesh_vertices(Volume V, Stream
       if (p.mask & (1u << (d - 1))) s_edge[k++] = (uint16_t)((threadIdx.x << 3) | d);
   }
   __syncthreads();
-  const float ex = G.bbox_max[0] - G.bbox_min[0], ey = G.bbox_max[1] - G.bbox_min[1], ez = G.bbox_max[2] - G.bbox_min[2];
-  const float limit = V.limit, sd = limit * 0.5f;
-  for (uint32_t v = threadIdx.x; v < nv; v += kMeshThreads) {
-    const int e = s_edge[v], lane = e >> 3, d = e & 7;
-    const int lx = lane & 7, ly = (lane >> 3) & 7, lz = lane >> 6;
-    const int bx = d & 1, by = (d >> 1) & 1, bz = d >> 2;
-    float a = s_f[corner_index(lx, ly, lz)], b = s_f[corner_index(lx + bx, ly + by, lz + bz)];
-    float w;
-    int x, y, z;
-    if constexpr (kLevel == 0) {
-      w = a / (a - b);
-      x = t.tx * 8 + lx; y = t.ty * 8 + ly; z = t.tz * 8 + lz;
-    } else {                                                           // the voxel edge of the vertex: every level's vertex is a level-0 vertex
-      x = (t.tx * 8 + lx) << kLevel; y = (t.ty * 8 + ly) << kLevel; z = (t.tz * 8 + lz) << kLevel;
-      mesh_descend<kSparse, kLevel>(V, bx, by, bz, x, y, z, a, b);
-      w = a / (a - b);
-    }
-    const float upx = ((float)x + 0.5f) / (float)V.res[0], uqx = ((float)(x + bx) + 0.5f) / (float)V.res[0];
-    const float upy = ((float)y + 0.5f) / (float)V.res[1], uqy = ((float)(y + by) + 0.5f) / (float)V.res[1];
-    const float upz = ((float)z + 0.5f) / (float)V.res[2], uqz = ((float)(z + bz) + 0.5f) / (float)V.res[2];
-    const float3 u = make_float3(upx + w * (uqx - upx), upy + w * (uqy - upy), upz + w * (uqz - upz));
-    const size_t o = (size_t)tile_vbase[t.id] + v;
-    out_pos[o * 3 + 0] = G.bbox_min[0] + u.x * ex;                     // vol_to_world, recon_integration.cpp:66-72
-    out_pos[o * 3 + 1] = G.bbox_min[1] + u.y * ey;
-    out_pos[o * 3 + 2] = G.bbox_min[2] + u.z * ez;
-    if (out_nrm) {
-      const float gx = tex3d_tsdf<kSparse>(V, u.x + sd, u.y, u.z) - tex3d_tsdf<kSparse>(V, u.x - sd, u.y, u.z);
-      const float gy = tex3d_tsdf<kSparse>(V, u.x, u.y + sd, u.z) - tex3d_tsdf<kSparse>(V, u.x, u.y - sd, u.z);
-      const float gz = tex3d_tsdf<kSparse>(V, u.x, u.y, u.z + sd) - tex3d_tsdf<kSparse>(V, u.x, u.y, u.z - sd);
-      const float3 gn = normalize3(make_float3(gx, gy, gz));          // get_gradient(), tsdf_raymarch.fs:140-149, as shade_hit does it
-      // inverseTranspose(vol_to_world) of the shader's -gn: the NormalMatrix of recon_integration.cpp:199 without the model-view
-      const float3 n = normalize3(make_float3(-gn.x / ex, -gn.y / ey, -gn.z / ez));
-      out_nrm[o * 3 + 0] = n.x; out_nrm[o * 3 + 1] = n.y; out_nrm[o * 3 + 2] = n.z;
-    }
-    if (out_col) out_col[o] = blend_colors(T, F, limit, u);           // all four components: alpha +1 valid, -1 fallback
-  }
+  mesh_tile_vertices<kSparse, kLevel>(V, T, F, G, t, nv, s_f, s_edge, (size_t)tile_vbase[t.id], out_pos, out_nrm, out_col);
 }
 
-// ... and the streamed form (tsdf_mesh_stream): k_mesh_vertices' text up to the vertex's unit-cube position u, word for word (the extraction keeps its
-// kernel untouched, so the two are written out twice), then the same vertices, quantised in registers and written with ONE 8- or 16-byte store each -- no fp32
+// ... and the streamed form (tsdf_mesh_stream): k_mesh_vertices' text (mesh_dev.hpp: mesh_tile_vertices) up to the vertex's unit-cube position u, word
+// for word (the extraction keeps its kernel untouched, so the two are written out twice), then the same vertices, quantised in registers and written with ONE 8- or 16-byte store each -- no fp32
 // position, normal or colour exists in memory.  H is the frame's header in device memory (k_mesh_stream_header): when a need exceeds its capacity
 // every workgroup of both emit kernels returns before it reads anything else, so nothing is ever written past a capacity.
 __device__ __forceinline__ bool mesh_stream_overflow(const MeshStreamHeader* __restrict__ H) {
@@ -391,10 +266,6 @@ __global__ __launch_bounds__(kMeshThreads, 4) void k_mesh_vertices_packed(Volume
 }
 
 // ---- 4. triangles, from the records alone
-__device__ __forceinline__ uint32_t edge_vertex(const uint32_t* s_first, const uint8_t* s_mask, int lx, int ly, int lz, int x, int y) {   // corners x < y of the cell at (lx, ly, lz)
-  const int i = corner_index(lx + (x & 1), ly + ((x >> 1) & 1), lz + (x >> 2)), d = y - x;
-  return s_first[i] + (uint32_t)__popc((uint32_t)s_mask[i] & ((1u << (d - 1)) - 1u));
-}
 template <int kLevel>
 __device__ __forceinline__ void mesh_tile_triangles(const Volume& V, const uint2* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_vbase,
                                                     const unsigned long long* __restrict__ tile_tbase, const uint32_t* __restrict__ tile_rec,
@@ -432,35 +303,7 @@ __device__ __forceinline__ void mesh_tile_triangles(const Volume& V, const uint2
   uint32_t total;
   const uint32_t off = block_exclusive_sum<kMeshWaves>(ntri, s_wave, &total);
   if (ntri == 0) return;
-  uint32_t* __restrict__ o = out_tri + (size_t)(tile_tbase[t.id] + off) * 3;
-  for (int k = 0; k < 6; ++k) {
-    const int v[4] = {c_tet[k][0], c_tet[k][1], c_tet[k][2], c_tet[k][3]};
-    uint32_t cs = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) cs |= ((corners >> v[j]) & 1u) << j;
-    if (cs == 0u || cs == 15u) continue;
-    const bool flip = (c_mesh_flip[k] >> cs) & 1u;
-    const int n_in = __popc(cs);
-    if (n_in != 2) {                                                   // one vertex apart from the other three: one triangle over its three edges, in vertex order
-      const uint32_t lone = n_in == 1 ? cs : (cs ^ 15u);
-      const int a = __ffs((int)lone) - 1;
-      uint32_t e[3]; int n = 0;
-      for (int j = 0; j < 4; ++j)
-        if (j != a) { e[n++] = edge_vertex(s_first, s_mask, lx, ly, lz, min(v[a], v[j]), max(v[a], v[j])); }
-      o[0] = e[0]; o[1] = flip ? e[2] : e[1]; o[2] = flip ? e[1] : e[2];
-      o += 3;
-    } else {                                                           // inside A before B, outside C before D: the quad AC, AD, BD, BC as (AC, AD, BD), (AC, BD, BC)
-      int in[2], out[2], ni = 0, no = 0;
-      for (int j = 0; j < 4; ++j) { if ((cs >> j) & 1u) in[ni++] = v[j]; else out[no++] = v[j]; }
-      const uint32_t ac = edge_vertex(s_first, s_mask, lx, ly, lz, min(in[0], out[0]), max(in[0], out[0]));
-      const uint32_t ad = edge_vertex(s_first, s_mask, lx, ly, lz, min(in[0], out[1]), max(in[0], out[1]));
-      const uint32_t bd = edge_vertex(s_first, s_mask, lx, ly, lz, min(in[1], out[1]), max(in[1], out[1]));
-      const uint32_t bc = edge_vertex(s_first, s_mask, lx, ly, lz, min(in[1], out[0]), max(in[1], out[0]));
-      o[0] = ac; o[1] = flip ? bd : ad; o[2] = flip ? ad : bd;
-      o[3] = ac; o[4] = flip ? bc : bd; o[5] = flip ? bd : bc;
-      o += 6;
-    }
-  }
+  mesh_cell_triangles(corners, s_first, s_mask, lx, ly, lz, out_tri + (size_t)(tile_tbase[t.id] + off) * 3);
 }
 template <int kLevel>
 __global__ __launch_bounds__(kMeshThreads) void k_mesh_triangles(Volume V, const uint2* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_vbase,
@@ -490,18 +333,6 @@ __global__ void k_mesh_stream_header(const MeshSums* __restrict__ totals, MeshSt
 
 // ---- launchers.  S.level picks the instantiation; the caller has checked it (0 .. kMeshMaxLevel) and sized S by mesh_lattice(res, level).
 int mesh_scan_blocks(int n_tiles) { return (n_tiles + kScanPerBlock - 1) / kScanPerBlock; }
-// f(sparse, level), both as compile-time constants: the one place that turns the volume's storage and the scratch's level into template arguments
-template <typename F>
-static void mesh_instantiation(const Volume& V, const MeshScratch& S, F&& f) {
-  auto at = [&](auto sparse) {
-    switch (S.level) {
-      case 0: f(sparse, std::integral_constant<int, 0>{}); break;
-      case 1: f(sparse, std::integral_constant<int, 1>{}); break;
-      default: f(sparse, std::integral_constant<int, 2>{}); break;
-    }
-  };
-  if (V.slot) at(std::true_type{}); else at(std::false_type{});
-}
 void launch_mesh_count(hipStream_t st, const Volume& V, const MeshScratch& S) {
   mesh_instantiation(V, S, [&](auto sparse, auto level) {
     hipLaunchKernelGGL((k_mesh_count<decltype(sparse)::value, decltype(level)::value>), dim3(S.n_tiles), dim3(kMeshThreads), 0, st, V, S.tile_cnt, S.tile_skip);

@@ -1,0 +1,210 @@
+// Device helpers of the mesh extraction shared by k_mesh.hip (a whole volume) and k_mesh_slab.hip (a Z-slab's part): the lattice of a
+// level, a tile's corner stage, what a lattice point owns, the descent of a coarse edge and the index of an edge's vertex.  All of them speak of a
+// tile through MeshTile: (tx, ty, tz) is the tile in the WHOLE volume's lattice, id its index in the caller's per-tile arrays -- the two kernels files
+// differ in how they get one from blockIdx.x, in nothing else.  (The text is k_mesh.hip's, moved: its kernels' registers, LDS and scratch are what they
+// were.)
+// The two tables are NOT here: a __constant__ array belongs to one code object, so the file that includes this header defines c_tet and c_mesh_flip
+// in namespace rr first and says so with RR_MESH_TABLES_DEFINED (an `extern` declaration here cannot stand in for that: k_mesh_slab.hip's copy has
+// internal linkage, and two external definitions of one name would collide in the library's host symbols).  k_mesh.hip holds the definition
+// (tests/test_mesh_reference.py compares its words with the generated ones), with external linkage as it always had -- a table private to the translation unit is folded into k_mesh_triangles' code and costs that kernel 7 VGPRs.
+#pragma once
+#ifndef RR_MESH_TABLES_DEFINED
+#error "define rr::c_tet[6][4] and rr::c_mesh_flip[6] (__constant__), then RR_MESH_TABLES_DEFINED, before including mesh_dev.hpp"
+#endif
+#include <cfloat>
+#include <type_traits>
+
+#include "blend_dev.hpp"
+
+namespace rr {
+
+constexpr int kMeshThreads = 512;            // one lane per lattice point of a tile
+constexpr int kMeshWaves = kMeshThreads / 64;
+constexpr int kMeshCorners = 9 * 9 * 9;      // a tile's lattice points and their +x/+y/+z neighbours
+
+// f(sparse, level), both as compile-time constants: the one place that turns the volume's storage and the scratch's level into template arguments
+template <typename F>
+static void mesh_instantiation(const Volume& V, const MeshScratch& S, F&& f) {
+  auto at = [&](auto sparse) {
+    switch (S.level) {
+      case 0: f(sparse, std::integral_constant<int, 0>{}); break;
+      case 1: f(sparse, std::integral_constant<int, 1>{}); break;
+      default: f(sparse, std::integral_constant<int, 2>{}); break;
+    }
+  };
+  if (V.slot) at(std::true_type{}); else at(std::false_type{});
+}
+
+// a voxel as the mesh reads it: NaN and +-inf read as -limit (NaN voxels exist, tsdf_integration.vs:52)
+__device__ __forceinline__ float mesh_value(float f, float limit) { return fabsf(f) <= FLT_MAX ? f : -limit; }
+
+struct MeshTile { int tx, ty, tz, id; };
+// The lattice inside a kernel.  A level holds the MeshLattice of the volume's resolution (tsdf_common.hpp: the one definition, the host sizes the launch
+// by it).  Level 0 is the voxel grid and its storage tiles and reads the volume's own fields where they are used: the kernels' text before there were
+// levels (a copy made at the kernel's head costs k_mesh_triangles a scalar register and another block layout).
+template <int kLevel>
+struct LatticeOf {
+  MeshLattice g;
+  __device__ __forceinline__ explicit LatticeOf(const Volume& V) : g(mesh_lattice(V.res, kLevel)) {}
+  __device__ __forceinline__ int cr(int a) const { return g.cr[a]; }
+  __device__ __forceinline__ int ntx() const { return g.ntx; }
+  __device__ __forceinline__ int nty() const { return g.nty; }
+};
+template <>
+struct LatticeOf<0> {
+  const Volume& V;
+  __device__ __forceinline__ explicit LatticeOf(const Volume& v) : V(v) {}
+  __device__ __forceinline__ int cr(int a) const { return V.res[a]; }
+  __device__ __forceinline__ int ntx() const { return V.ntx; }
+  __device__ __forceinline__ int nty() const { return V.nty; }
+};
+__device__ __forceinline__ int corner_index(int lx, int ly, int lz) { return (lz * 9 + ly) * 9 + lx; }
+
+// one voxel, sanitised; (x, y, z) inside the grid
+template <bool kSparse>
+__device__ __forceinline__ float mesh_voxel(const Volume& V, int x, int y, int z) {
+  return mesh_value(kSparse ? tsdf_tap_sparse(V, x, y, z) : V.data[vol_index(V, x, y, z)], V.limit);
+}
+// the tile's 9 x 9 x 9 corner values -> LDS; a corner outside the lattice reads -limit (no edge and no cell reaches it: see mesh_point).  Lattice point
+// (x, y, z) is voxel (x, y, z) << level: a point sample (the last lattice point times the stride is below the resolution, cr = ceil(res / stride))
+template <bool kSparse, int kLevel>
+__device__ __forceinline__ void mesh_stage(const Volume& V, const LatticeOf<kLevel>& L, const MeshTile& t, float* s_f) {
+  for (int i = threadIdx.x; i < kMeshCorners; i += kMeshThreads) {
+    const int lx = i % 9, ly = (i / 9) % 9, lz = i / 81;
+    const int x = t.tx * 8 + lx, y = t.ty * 8 + ly, z = t.tz * 8 + lz;
+    float f = -V.limit;
+    if (x < L.cr(0) && y < L.cr(1) && z < L.cr(2)) f = mesh_voxel<kSparse>(V, x << kLevel, y << kLevel, z << kLevel);
+    s_f[i] = f;
+  }
+}
+// Descent of a crossed lattice edge P -> P + (d << level) to the voxel edge that carries its vertex: bisection, the end on the midpoint's side of the
+// surface moves to the midpoint (a midpoint is a voxel read, never the LDS stage: it is no lattice point).  In: (x, y, z) = P as a voxel, a = f(P),
+// b = f(other end).  Out: neighbouring voxels (x, y, z), (x, y, z) + d with their values, exactly one of them inside, as on entry.
+template <bool kSparse, int kLevel>
+__device__ __forceinline__ void mesh_descend(const Volume& V, int bx, int by, int bz, int& x, int& y, int& z, float& a, float& b) {
+  const bool inside = a > 0.0f;
+#pragma unroll
+  for (int h = (1 << kLevel) >> 1; h >= 1; h >>= 1) {
+    const int mx = x + h * bx, my = y + h * by, mz = z + h * bz;
+    const float m = mesh_voxel<kSparse>(V, mx, my, mz);
+    if ((m > 0.0f) == inside) { a = m; x = mx; y = my; z = mz; } else b = m;
+  }
+}
+
+// What lattice point `lane` of the tile owns: its edge mask (bit d - 1: the edge p -> p + d lies inside the lattice and exactly one
+// of its ends is inside the surface), whether p itself is inside, and the triangles of the cell whose origin it is.
+struct MeshPoint { uint32_t mask, inside, ntri; };
+__device__ __forceinline__ uint32_t tet_triangles(uint32_t corners, int k) {   // corners: bit b = corner b is inside
+  const uint32_t n = ((corners >> c_tet[k][0]) & 1u) + ((corners >> c_tet[k][1]) & 1u) + ((corners >> c_tet[k][2]) & 1u) + ((corners >> c_tet[k][3]) & 1u);
+  return n == 2u ? 2u : ((n == 1u || n == 3u) ? 1u : 0u);
+}
+__device__ __forceinline__ uint32_t cell_triangles(uint32_t corners) {
+  uint32_t n = 0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) n += tet_triangles(corners, k);
+  return n;
+}
+template <int kLevel>
+__device__ __forceinline__ MeshPoint mesh_point(const LatticeOf<kLevel>& L, const MeshTile& t, const float* s_f, int lane) {
+  const int lx = lane & 7, ly = (lane >> 3) & 7, lz = lane >> 6;
+  const int x = t.tx * 8 + lx, y = t.ty * 8 + ly, z = t.tz * 8 + lz;
+  MeshPoint p{0u, 0u, 0u};
+  if (x >= L.cr(0) || y >= L.cr(1) || z >= L.cr(2)) return p;
+  p.inside = s_f[corner_index(lx, ly, lz)] > 0.0f ? 1u : 0u;          // the raymarch's hit test, tsdf_raymarch.fs:96: zero and -0 are outside
+  uint32_t corners = p.inside;
+#pragma unroll
+  for (int d = 1; d < 8; ++d) {
+    const int bx = d & 1, by = (d >> 1) & 1, bz = d >> 2;
+    if (x + bx < L.cr(0) && y + by < L.cr(1) && z + bz < L.cr(2)) {
+      const uint32_t in = s_f[corner_index(lx + bx, ly + by, lz + bz)] > 0.0f ? 1u : 0u;
+      corners |= in << d;
+      if (in != p.inside) p.mask |= 1u << (d - 1);
+    }
+  }
+  if (x + 1 < L.cr(0) && y + 1 < L.cr(1) && z + 1 < L.cr(2)) p.ntri = cell_triangles(corners);
+  return p;
+}
+
+// The tile's nv vertices, one lane per vertex, into the arrays from `first` on: s_f the tile's corner stage, s_edge per vertex of the tile its
+// lattice point << 3 | d (in the defined order).  out_nrm / out_col may be null.
+template <bool kSparse, int kLevel>
+__device__ __forceinline__ void mesh_tile_vertices(const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshTile& t, uint32_t nv,
+                                                   const float* s_f, const uint16_t* s_edge, size_t first, float* __restrict__ out_pos, float* __restrict__ out_nrm,
+                                                   float4* __restrict__ out_col) {
+  const float ex = G.bbox_max[0] - G.bbox_min[0], ey = G.bbox_max[1] - G.bbox_min[1], ez = G.bbox_max[2] - G.bbox_min[2];
+  const float limit = V.limit, sd = limit * 0.5f;
+  for (uint32_t v = threadIdx.x; v < nv; v += kMeshThreads) {
+    const int e = s_edge[v], lane = e >> 3, d = e & 7;
+    const int lx = lane & 7, ly = (lane >> 3) & 7, lz = lane >> 6;
+    const int bx = d & 1, by = (d >> 1) & 1, bz = d >> 2;
+    float a = s_f[corner_index(lx, ly, lz)], b = s_f[corner_index(lx + bx, ly + by, lz + bz)];
+    float w;
+    int x, y, z;
+    if constexpr (kLevel == 0) {
+      w = a / (a - b);
+      x = t.tx * 8 + lx; y = t.ty * 8 + ly; z = t.tz * 8 + lz;
+    } else {                                                           // the voxel edge of the vertex: every level's vertex is a level-0 vertex
+      x = (t.tx * 8 + lx) << kLevel; y = (t.ty * 8 + ly) << kLevel; z = (t.tz * 8 + lz) << kLevel;
+      mesh_descend<kSparse, kLevel>(V, bx, by, bz, x, y, z, a, b);
+      w = a / (a - b);
+    }
+    const float upx = ((float)x + 0.5f) / (float)V.res[0], uqx = ((float)(x + bx) + 0.5f) / (float)V.res[0];
+    const float upy = ((float)y + 0.5f) / (float)V.res[1], uqy = ((float)(y + by) + 0.5f) / (float)V.res[1];
+    const float upz = ((float)z + 0.5f) / (float)V.res[2], uqz = ((float)(z + bz) + 0.5f) / (float)V.res[2];
+    const float3 u = make_float3(upx + w * (uqx - upx), upy + w * (uqy - upy), upz + w * (uqz - upz));
+    const size_t o = first + v;
+    out_pos[o * 3 + 0] = G.bbox_min[0] + u.x * ex;                     // vol_to_world, recon_integration.cpp:66-72
+    out_pos[o * 3 + 1] = G.bbox_min[1] + u.y * ey;
+    out_pos[o * 3 + 2] = G.bbox_min[2] + u.z * ez;
+    if (out_nrm) {
+      const float gx = tex3d_tsdf<kSparse>(V, u.x + sd, u.y, u.z) - tex3d_tsdf<kSparse>(V, u.x - sd, u.y, u.z);
+      const float gy = tex3d_tsdf<kSparse>(V, u.x, u.y + sd, u.z) - tex3d_tsdf<kSparse>(V, u.x, u.y - sd, u.z);
+      const float gz = tex3d_tsdf<kSparse>(V, u.x, u.y, u.z + sd) - tex3d_tsdf<kSparse>(V, u.x, u.y, u.z - sd);
+      const float3 gn = normalize3(make_float3(gx, gy, gz));          // get_gradient(), tsdf_raymarch.fs:140-149, as shade_hit does it
+      // inverseTranspose(vol_to_world) of the shader's -gn: the NormalMatrix of recon_integration.cpp:199 without the model-view
+      const float3 n = normalize3(make_float3(-gn.x / ex, -gn.y / ey, -gn.z / ez));
+      out_nrm[o * 3 + 0] = n.x; out_nrm[o * 3 + 1] = n.y; out_nrm[o * 3 + 2] = n.z;
+    }
+    if (out_col) out_col[o] = blend_colors(T, F, limit, u);           // all four components: alpha +1 valid, -1 fallback
+  }
+}
+
+// the mesh index of the vertex on the edge between corners x < y of the cell at (lx, ly, lz): s_first / s_mask hold, per corner of the tile, the index
+// of the first vertex it owns and its record's low byte
+__device__ __forceinline__ uint32_t edge_vertex(const uint32_t* s_first, const uint8_t* s_mask, int lx, int ly, int lz, int x, int y) {
+  const int i = corner_index(lx + (x & 1), ly + ((x >> 1) & 1), lz + (x >> 2)), d = y - x;
+  return s_first[i] + (uint32_t)__popc((uint32_t)s_mask[i] & ((1u << (d - 1)) - 1u));
+}
+// the triangles of the cell at (lx, ly, lz) with the corner bits `corners`, written from o on in (tetrahedron, triangle) order
+__device__ __forceinline__ void mesh_cell_triangles(uint32_t corners, const uint32_t* s_first, const uint8_t* s_mask, int lx, int ly, int lz, uint32_t* __restrict__ o) {
+  for (int k = 0; k < 6; ++k) {
+    const int v[4] = {c_tet[k][0], c_tet[k][1], c_tet[k][2], c_tet[k][3]};
+    uint32_t cs = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) cs |= ((corners >> v[j]) & 1u) << j;
+    if (cs == 0u || cs == 15u) continue;
+    const bool flip = (c_mesh_flip[k] >> cs) & 1u;
+    const int n_in = __popc(cs);
+    if (n_in != 2) {                                                   // one vertex apart from the other three: one triangle over its three edges, in vertex order
+      const uint32_t lone = n_in == 1 ? cs : (cs ^ 15u);
+      const int a = __ffs((int)lone) - 1;
+      uint32_t e[3]; int n = 0;
+      for (int j = 0; j < 4; ++j)
+        if (j != a) { e[n++] = edge_vertex(s_first, s_mask, lx, ly, lz, min(v[a], v[j]), max(v[a], v[j])); }
+      o[0] = e[0]; o[1] = flip ? e[2] : e[1]; o[2] = flip ? e[1] : e[2];
+      o += 3;
+    } else {                                                           // inside A before B, outside C before D: the quad AC, AD, BD, BC as (AC, AD, BD), (AC, BD, BC)
+      int in[2], out[2], ni = 0, no = 0;
+      for (int j = 0; j < 4; ++j) { if ((cs >> j) & 1u) in[ni++] = v[j]; else out[no++] = v[j]; }
+      const uint32_t ac = edge_vertex(s_first, s_mask, lx, ly, lz, min(in[0], out[0]), max(in[0], out[0]));
+      const uint32_t ad = edge_vertex(s_first, s_mask, lx, ly, lz, min(in[0], out[1]), max(in[0], out[1]));
+      const uint32_t bd = edge_vertex(s_first, s_mask, lx, ly, lz, min(in[1], out[1]), max(in[1], out[1]));
+      const uint32_t bc = edge_vertex(s_first, s_mask, lx, ly, lz, min(in[1], out[0]), max(in[1], out[0]));
+      o[0] = ac; o[1] = flip ? bd : ad; o[2] = flip ? ad : bd;
+      o[3] = ac; o[4] = flip ? bc : bd; o[5] = flip ? bd : bc;
+      o += 6;
+    }
+  }
+}
+
+}  // namespace rr

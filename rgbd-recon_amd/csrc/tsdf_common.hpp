@@ -342,7 +342,7 @@ void launch_colorfill(hipStream_t st, const Atlas& A, int w, int h, float4* fb_c
 void launch_resolve_masked(hipStream_t st, const Atlas& A, int w, int h, float4* fb_color, float* fb_depth, int mask, int keep_color);
 // frame read-out (k_present.hip): the framebuffer colour as RGBA8 (format 0: w * h * 4 bytes) or DXT1 blocks (1: ceil(w/4) * ceil(h/4) * 8 bytes) into out
 void launch_present(hipStream_t st, const float4* fb_c, void* out, int w, int h, uint32_t format, int top_down);
-// mesh extraction (k_mesh.hip): per-tile scratch of one extract, sized by the launchers' caller.  Whole-volume contexts only: tile id = stored tile index.
+// mesh extraction (k_mesh.hip): per-tile scratch of one extract, sized by the launchers' caller.  These launchers: whole-volume contexts only, tile id = stored tile index.
 struct MeshGeometry { float bbox_min[3], bbox_max[3]; };
 // The lattice of a level of detail (tsdf_mesh_extract_lod): lattice point (i, j, k) of level L is voxel (i, j, k) << L, cr = ceil(res / (1 << L)) points
 // per axis, tiles of 8^3 lattice points.  Level 0 is the voxel grid and its storage tiles.  A lattice tile's id is (tz * nty + ty) * ntx + tx.
@@ -375,6 +375,17 @@ void launch_mesh_scan(hipStream_t st, const MeshScratch& S);   // three launches
 // records: 512 words per tile with surface; nrm / col may be null (attribute not wanted; T and F are read for colours only)
 void launch_mesh_emit(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S, uint32_t* records,
                       float* pos, float* nrm, float* col, uint32_t* tri);
+// a Z-slab's part of the mesh (k_mesh_slab.hip): the scratch then covers n_own + n_seam slab-local tiles -- the owned lattice tile layers from layer0 on,
+// then the ntx * nty tiles of the first layer above them (n_seam = 0 when the slab reaches the volume's top) -- and launch_mesh_scan runs over all of them
+struct MeshSlab { int layer0, n_own, n_seam; };
+void launch_mesh_slab_count(hipStream_t st, const Volume& V, const MeshScratch& S, const MeshSlab& B);
+// records: 512 words per tile with surface, seam tiles included; pos / nrm / col: the owned tiles' vertices (nrm / col may be null)
+void launch_mesh_slab_vertices(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S, const MeshSlab& B,
+                               uint32_t* records, float* pos, float* nrm, float* col);
+// the owned tiles' triangles with indices base + (slab-local index); a seam tile's vertices start at base + slab_vertices + above[tile] (above: n_seam
+// words in device memory, not read when n_seam == 0).  The caller has checked that every index fits 32 bits.
+void launch_mesh_slab_triangles(hipStream_t st, const Volume& V, const MeshScratch& S, const MeshSlab& B, const uint32_t* records, uint32_t base, uint32_t slab_vertices,
+                                const uint32_t* above, uint32_t* tri);
 // mesh streaming (tsdf_mesh_stream): a frame's header as k_mesh_stream_header leaves it in the slot's device buffer, and as the copy stream brings it to
 // the host -- 64 bytes in front of the payload.  The emit kernels read the needs and the capacities from it and return at once when one is exceeded.
 struct MeshStreamHeader {

@@ -115,7 +115,7 @@ class ReconIntegrationHip {
   void setUseBricks(bool active) { check(tsdf_set_use_bricks(m_ctx, active)); }
   void setSpaceSkip(bool active) { check(tsdf_set_space_skip(m_ctx, active)); }
   void setDrawBricks(bool active) { check(tsdf_set_draw_bricks(m_ctx, active)); }   // drawF() then ends with drawOccupiedBricks(), recon_integration.cpp:166-168
-  void setVoxelSize(float size) { check(tsdf_set_voxel_size(m_ctx, size)); }      // recon_integration.cpp:340-353
+  void setVoxelSize(float size) { check(tsdf_set_voxel_size(m_ctx, size)); m_slab_valid = false; }      // recon_integration.cpp:340-353 (a slab part went with the old grid)
   void setTsdfLimit(float limit) { check(tsdf_set_tsdf_limit(m_ctx, limit)); }
   void setBrickSize(float size) { const float s[3] = {size, size, size}; check(tsdf_set_brick_size(m_ctx, s)); m_brick_size = size; }
   unsigned numBricks() const { uint32_t n = 0; tsdf_num_bricks(m_ctx, &n); return n; }
@@ -194,6 +194,45 @@ class ReconIntegrationHip {
                              out.triangles.data()));
   }
   void writeMeshPly(const char* path) { check(tsdf_mesh_write_ply(m_ctx, path)); }
+  // ---- a Z-slab's part of that mesh (tsdf_mesh_slab_extract): the parts of contiguous slabs, concatenated in slab order, ARE the whole volume's mesh.
+  // Call order per slab, the halo being current as for a draw: extractMeshSlab (its counts) -> meshSlabSeam (the table the slab BELOW links with) ->
+  // meshSlabLink(vertices of all slabs below, the table of the slab directly above; nullptr at the volume's top) -> downloadMeshSlab.  seamTiles: the
+  // table's entries at the extract's level.  The part is a state of its own: extractMesh and everything built on it do not see it.
+  MeshCounts extractMeshSlab(bool normals = true, bool colours = true, unsigned level = 0) {
+    const std::uint32_t flags = (normals ? TSDF_MESH_NORMALS : 0u) | (colours ? TSDF_MESH_COLOURS : 0u);
+    MeshCounts n;
+    m_slab_valid = false;                                                // (a refused extract leaves no part in the library either)
+    check(tsdf_mesh_slab_extract(m_ctx, flags, level, &n.vertices, &n.triangles));
+    m_slab = n; m_slab_flags = flags; m_slab_level = level; m_slab_valid = true;
+    return m_slab;
+  }
+  std::size_t seamTiles() {
+    requireSlabPart();
+    uint32_t res[3];
+    check(tsdf_get_resolution(m_ctx, res, nullptr, nullptr));
+    const std::size_t t = (std::size_t)8 << m_slab_level;
+    return ((res[0] + t - 1) / t) * ((res[1] + t - 1) / t);
+  }
+  void meshSlabSeam(std::vector<std::uint32_t>& out) {
+    out.assign(seamTiles(), 0u);
+    check(tsdf_mesh_slab_seam(m_ctx, out.data()));
+  }
+  void meshSlabLink(std::uint64_t vertex_base, const std::uint32_t* above_seam) { check(tsdf_mesh_slab_link(m_ctx, vertex_base, above_seam)); }
+  void downloadMeshSlab(Mesh& out) {
+    requireSlabPart();
+    out.position.resize((std::size_t)m_slab.vertices * 3);
+    out.normal.resize((m_slab_flags & TSDF_MESH_NORMALS) ? (std::size_t)m_slab.vertices * 3 : 0);
+    out.colour.resize((m_slab_flags & TSDF_MESH_COLOURS) ? (std::size_t)m_slab.vertices * 4 : 0);
+    out.triangles.resize((std::size_t)m_slab.triangles * 3);
+    check(tsdf_mesh_slab_download(m_ctx, out.position.data(), out.normal.empty() ? nullptr : out.normal.data(), out.colour.empty() ? nullptr : out.colour.data(),
+                                  out.triangles.data()));
+  }
+  struct MeshSlabStats { std::uint64_t tiles = 0, tiles_skipped = 0, tiles_with_surface = 0, bytes = 0; };
+  MeshSlabStats meshSlabStats() {
+    std::uint64_t s[4];
+    check(tsdf_mesh_slab_stats(m_ctx, s));
+    return MeshSlabStats{s[0], s[1], s[2], s[3]};
+  }
   // ---- the mesh's islands (tsdf_mesh_components).  The reference has no counterpart.  meshComponents labels the connected components of the last
   // extractMesh (by index; numbered by smallest vertex) and returns their number; downloadMeshComponents copies the labels and the 16-byte table;
   // keepMeshComponents / filterMeshComponents / keepLargestMeshComponents replace the mesh with the kept part -- downloadMesh and writeMeshPly serve it
@@ -379,6 +418,9 @@ class ReconIntegrationHip {
   ReconInputs m_in;
   tsdf_ctx* m_ctx = nullptr;
   MeshCounts m_mesh; std::uint32_t m_mesh_flags = 0;   // of the last extractMesh
+  MeshCounts m_slab; std::uint32_t m_slab_flags = 0; unsigned m_slab_level = 0; bool m_slab_valid = false;   // of the last extractMeshSlab that succeeded
+  // the sizes of seam table and arrays come from these: without them nothing is handed to the library to fill
+  void requireSlabPart() const { if (!m_slab_valid) throw std::logic_error("ReconIntegrationHip: no slab mesh (extractMeshSlab)"); }
   float m_mv[16], m_proj[16];
   float m_brick_size;
 };

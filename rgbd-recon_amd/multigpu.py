@@ -44,6 +44,7 @@ from __future__ import annotations
 
 import contextlib
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -358,6 +359,50 @@ class SlabDriver:
         self.last = (f, cap)
         self.frame_no = f + 1
 
+    # ------------------------------------------------------------------ the fused surface as ONE mesh, extracted where the volume is
+    def extract_mesh(self, normals=True, colours=True, level=0):
+        """A COLLECTIVE: every rank extracts its slab's part of the whole volume's mesh (tsdf_mesh_slab_extract; the halo must be current, as after
+        frame()), the counts and the seam tables are all-gathered, every rank links its triangles with global indices, and the parts are gathered on
+        rank 0.  Returns dict(part=the rank's arrays, vertex_base=..., counts=[world][2]) and, on rank 0, mesh=the concatenation: the arrays
+        extract_mesh(level=...) of a whole-volume context gives.  A dedicated compositor contributes zero counts and an empty part."""
+        b = self.b
+        s = 8 << int(level)
+        shape = (-(-int(b.res[1]) // s), -(-int(b.res[0]) // s))        # [nty][ntx] lattice tiles
+        if self.is_worker:
+            nv, nt = b.extract_mesh_slab(normals, colours, level)
+            seam = np.asarray(b.mesh_slab_seam(), np.uint32).reshape(shape)
+        else:
+            nv, nt, seam = 0, 0, np.zeros(shape, np.uint32)
+        world = self.world
+        if world > 1:
+            mine = torch.cat([torch.tensor([nv, nt], dtype=torch.int64), torch.from_numpy(seam.astype(np.int64).reshape(-1))]).to(self.dev)
+            rows = torch.empty((world, mine.numel()), dtype=torch.int64, device=self.dev)
+            with self._on_stream():
+                self._all_gather(rows, mine)
+                rows = rows.cpu().numpy()
+        else:
+            rows = np.concatenate([[nv, nt], seam.reshape(-1)]).astype(np.int64)[None]
+        counts = rows[:, :2]
+        base = int(counts[:self.rank, 0].sum())
+        if self.is_worker:
+            above = rows[self.rank + 1, 2:].astype(np.uint32).reshape(shape) if self.rank < world - 1 else None   # the slab above follows directly
+            b.mesh_slab_link(base, above)
+            part = b.mesh_slab_download(normals, colours)
+        else:
+            part = dict(position=np.zeros((0, 3), np.float32), triangles=np.zeros((0, 3), np.uint32))
+            if normals:
+                part["normal"] = np.zeros((0, 3), np.float32)
+            if colours:
+                part["colour"] = np.zeros((0, 4), np.float32)
+        out = dict(part=part, vertex_base=base, counts=counts.copy())
+        parts = [part]
+        if world > 1:
+            parts = [None] * world if self.rank == 0 else None
+            dist.gather_object(part, parts, dst=0, group=self.group)
+        if self.rank == 0:
+            out["mesh"] = {k: np.concatenate([p[k] for p in parts]) for k in part}
+        return out
+
     def finish(self):
         """Completes the latest frame: call before reading its result (and at the end of a timed region).  A COLLECTIVE when
         the compact gather of that frame turned out too small -- every rank sees the same counts and re-gathers together."""
@@ -382,6 +427,23 @@ class SlabDriver:
             self.stream.synchronize()
         elif hasattr(self.b, "sync"):
             self.b.sync()
+
+
+def mesh_slabs_on_one_device(backends, normals=True, colours=True, level=0):
+    """SlabDriver.extract_mesh with ONE visible device: backends[k] owns slab k (contiguous, in z order), each with a current halo (as
+    frame_slabs_on_one_device leaves it).  Every slab extracts its part, the prefix of the counts gives each part's vertex base, each seam table goes
+    one slab downwards, every slab links.  Returns the concatenated arrays -- the mesh extract_mesh(level=...) of a whole-volume context gives -- plus
+    counts [(vertices, triangles)] and seams [table] per slab."""
+    counts = [b.extract_mesh_slab(normals, colours, level) for b in backends]
+    seams = [b.mesh_slab_seam() for b in backends]
+    parts, base = [], 0
+    for k, b in enumerate(backends):
+        b.mesh_slab_link(base, seams[k + 1] if k + 1 < len(backends) else None)
+        parts.append(b.mesh_slab_download(normals, colours))
+        base += counts[k][0]
+    out = {key: np.concatenate([p[key] for p in parts]) for key in parts[0]}
+    out["counts"], out["seams"] = counts, seams
+    return out
 
 
 def frame_slabs_on_one_device(backends, mv, proj, device, halo="exchange", composite="dense"):

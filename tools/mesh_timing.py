@@ -8,8 +8,13 @@ level sees the same machine; the record then has a "levels" entry with each leve
 and its mesh bytes.  The top-level entries stay those of the first level named.
 --components: after that, N times extract (every attribute, the first level named) + tsdf_mesh_components, and with --min-triangles M also
 tsdf_mesh_filter_components(M): the record gets a "components" entry with the timers "mesh_components" and "mesh_filter" (each the sum of its call's two
-samples: the host sizes an allocation between them) beside mesh_count / mesh_scan / mesh_emit of the same extracts, and the counts."""
+samples: the host sizes an allocation between them) beside mesh_count / mesh_scan / mesh_emit of the same extracts, and the counts.
+--slabs K: the same volume once more as K Z-slab contexts (recomputed halos) on this one device, each extracting its part of the first level named with
+every attribute (tsdf_mesh_slab_extract / _link): the record gets a "slabs" entry with every slab's "mesh_slab_count" / "_scan" / "_emit" / "_link"
+device time, its counts and its tiles with surface, whether the joined parts equal the whole-volume extract byte for byte, and the slowest slab's time
+and share of the surface tiles beside the whole-volume extract's device time of this run."""
 import sys, os, json, time
+from importlib import import_module
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch  # noqa: F401  (torch first: the library binds to the HIP runtime torch loaded)
 import rgbd_recon_amd as rr
@@ -20,12 +25,15 @@ ARGS = sys.argv[1:]
 LEVELS = [int(x) for x in ARGS[ARGS.index("--level") + 1].split(",")] if "--level" in ARGS else [0]
 COMPONENTS = "--components" in ARGS or "--min-triangles" in ARGS
 MIN_TRIANGLES = int(ARGS[ARGS.index("--min-triangles") + 1]) if "--min-triangles" in ARGS else None
-OUT = [a for i, a in enumerate(ARGS) if not a.startswith("--") and (i == 0 or ARGS[i - 1] not in ("--level", "--min-triangles"))]
+SLABS = int(ARGS[ARGS.index("--slabs") + 1]) if "--slabs" in ARGS else 0
+SLAB_STAGES = ("mesh_slab_count", "mesh_slab_scan", "mesh_slab_emit", "mesh_slab_link")
+OUT = [a for i, a in enumerate(ARGS) if not a.startswith("--") and (i == 0 or ARGS[i - 1] not in ("--level", "--min-triangles", "--slabs"))]
 
 scene = rr.scene.make_scene(n_streams=4, width=640, height=480, lut_res=128, inv_res=128)
 ext = scene["bbox_max"] - scene["bbox_min"]
 res = (512,) * 3
-hip = rr.ReconIntegrationHip(scene, res=res, brick_size=[float(ext[a]) / res[a] * 8 for a in range(3)], limit=0.01, view=VIEW)
+CTX = dict(res=res, brick_size=[float(ext[a]) / res[a] * 8 for a in range(3)], limit=0.01, view=VIEW)
+hip = rr.ReconIntegrationHip(scene, **CTX)
 mv, pr = rr.scene.default_view(*VIEW)
 hip.clearOccupiedBricks(); hip.markBricks(); hip.updateOccupiedBricks(); hip.integrate(); hip.drawF(mv, pr)
 hip.sync()
@@ -96,6 +104,47 @@ rec["volume_download_wall_ms"] = (time.perf_counter() - t0) / 3 * 1e3
 cnt, total = hip.timer_stats("volume_download")
 rec["volume_download_ms"] = total / cnt
 rec["volume_bytes"] = int(vol.nbytes)
+del vol
+if SLABS:
+    mgpu = import_module("rgbd-recon_amd.multigpu")
+    L0 = LEVELS[0]
+    whole = hip.extract_mesh(level=L0, normals=True, colours=True)
+    ctxs = [rr.ReconIntegrationHip(scene, slab=mgpu.slab_range(res[2], k, SLABS), recompute_halo=True, **CTX) for k in range(SLABS)]
+    for c in ctxs:
+        c.clearOccupiedBricks(); c.markBricks(); c.updateOccupiedBricks(); c.integrate(); c.sync()
+        c.enable_timers(True)
+        c.set_timer_filter(list(SLAB_STAGES))
+    joined = mgpu.mesh_slabs_on_one_device(ctxs, normals=True, colours=True, level=L0)          # (also the warm-up)
+    identical = all(joined[k].tobytes() == whole[k].tobytes() for k in ("position", "normal", "colour", "triangles"))
+    for c in ctxs:
+        for s in SLAB_STAGES:
+            c.timer_stats(s)
+    ms = [{s: [] for s in SLAB_STAGES} for _ in ctxs]
+    for _ in range(N):
+        counts = [c.extract_mesh_slab(True, True, L0) for c in ctxs]
+        seams = [c.mesh_slab_seam() for c in ctxs]
+        base = 0
+        for k, c in enumerate(ctxs):
+            c.mesh_slab_link(base, seams[k + 1] if k + 1 < SLABS else None)
+            base += counts[k][0]
+            for s in SLAB_STAGES:
+                cnt, total = c.timer_stats(s)
+                ms[k][s].append(total / cnt if cnt else 0.0)
+    per = []
+    for k, c in enumerate(ctxs):
+        st = c.mesh_slab_stats()
+        r = {s + "_ms": float(np.mean(ms[k][s])) for s in SLAB_STAGES}
+        r["device_ms"] = sum(r.values())
+        r.update(planes=list(mgpu.slab_range(res[2], k, SLABS)), vertices=counts[k][0], triangles=counts[k][1], tiles=st["tiles"], tiles_skipped=st["tiles_skipped"],
+                 tiles_with_surface=st["tiles_with_surface"])
+        per.append(r)
+    slow = max(per, key=lambda r: r["device_ms"])
+    surface = sum(r["tiles_with_surface"] for r in per)
+    rec["slabs"] = dict(n=SLABS, level=L0, identical_to_whole_volume=bool(identical), per_slab=per, slowest_slab_ms=slow["device_ms"],
+                        slowest_slab_surface_share=slow["tiles_with_surface"] / max(surface, 1), sum_of_slabs_ms=sum(r["device_ms"] for r in per),
+                        whole_volume_device_ms=levels[L0]["all_attributes"]["device_ms"])
+    for c in ctxs:
+        c.close()
 print(json.dumps(rec), flush=True)
 if OUT:
     with open(OUT[0], "w") as f:
