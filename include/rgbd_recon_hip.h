@@ -939,6 +939,66 @@ int32_t tsdf_mesh_stream_config_filter(tsdf_ctx* ctx, uint32_t flags, uint32_t l
 int32_t tsdf_mesh_stream_min_triangles(tsdf_ctx* ctx, uint32_t* min_triangles);
 int32_t tsdf_mesh_stream_frame_filter(tsdf_ctx* ctx, uint64_t out[4]);
 
+/* ---- mesh streaming: compact triangles ---------------------------------------------------------------------
+ * The ring of "mesh streaming" with triangles of 6 bytes instead of 12: three 16-bit corner codes that name a vertex by its lattice tile and its place
+ * inside it, and a table with one 16-byte row per lattice tile of the frame.  The mesh, its order, its winding and its packed vertices are unchanged;
+ * decoding gives, byte for byte, the uint32 triangle array of the same frame -- at every level, and of the filtered frame with a filter.  No
+ * counterpart in the reference.  tests/mesh_compact_reference.py restates the format in numpy; device and numpy agree byte for byte.
+ *
+ * Why 15 bits name a corner.  The mesh is ordered by 8^3 lattice tile; a vertex is owned by the lower end of its edge; the corners of a cell lie in the
+ *   cell's tile or in one of its +x / +y / +z neighbours.  (a) offset < 3584: a tile has 512 lattice points, a point owns at most 7 edges, so a tile
+ *   owns at most 512 * 7 = 3584 vertices and an offset inside it fits 12 bits.  (b) A tile with triangles has a row: every one of Kuhn's tetrahedra
+ *   contains the cell's origin c0, so a tetrahedron with mixed signs has a crossed edge at c0; that edge is owned by c0, and c0 lies in the cell's own
+ *   tile -- the tile of every triangle owns a vertex.  Hence the rows are exactly the needed_tiles tiles max_surface_tiles bounds: there is no fourth
+ *   capacity and no fourth overflow bit.  The neighbour code 7 never occurs (corner 7 of a cell owns no edge of that cell).
+ * Payload.  In this order: the packed vertices, n_vertices * vertex_stride bytes, unchanged; zero padding up to a multiple of 16 (eight bytes
+ *   or none); the tile table, n_tile_rows rows of 16 bytes; the triangles, n_triangles rows of 6 bytes.  Little endian.  The
+ *   payload copied to the host is exactly these bytes, never the capacity; a frame without a vertex has no payload.
+ * Tile-table row.  {uint32 tile, first_vertex, first_triangle, n_triangles}: one row per lattice tile that owns at least one vertex of the frame,
+ *   ascending by tile; tile is the linear id, x fastest, in the level's lattice-tile grid tiles[a] = ceil(ceil(res[a] / s) / 8), s = 1 << level.  The
+ *   tile's vertices are [first_vertex, the next row's first_vertex) -- the last row's end at n_vertices --, its triangles (those of its cells)
+ *   [first_triangle, first_triangle + n_triangles), both in the frame's order.
+ * Triangle row.  Three uint16 corner codes in the corner order of the uint32 array.  Bits 0..11: index - first_vertex of the owner tile's row.  Bits
+ *   12..14: dx + 2 dy + 4 dz, the owner tile's position relative to the tile of the triangle's cell, each component 0 or 1.  Bit 15: 0.
+ * Decoding, for corner code `code` of a triangle in row r (rows[] the table, n its length):
+ *     owner = rows[r].tile + ((code >> 12) & 1) + ((code >> 13) & 1) * tiles[0] + ((code >> 14) & 1) * tiles[0] * tiles[1];
+ *     lo = r; hi = n;                       // the owner's row: rows ascend by tile, and owner >= rows[r].tile
+ *     while (hi - lo > 1) { mid = (lo + hi) / 2; if (rows[mid].tile <= owner) lo = mid; else hi = mid; }
+ *     index = rows[lo].first_vertex + (code & 0xfff);
+ * tsdf_mesh_stream_config_compact is tsdf_mesh_stream_config_filter with index_format.  TSDF_MESH_INDEX_U32 (0): it IS that call (which is this one
+ *   with 0, as the two older config entries are): the launches, events and copies of before.  TSDF_MESH_INDEX_TILE16 (1): the format above.  Any other
+ *   value: TSDF_ERR_INVALID_ARGUMENT.  Every other check and error code is tsdf_mesh_stream_config_filter's.  With format 1 a slot is the 64-byte header
+ *   + align16(max_vertices * vertex_stride) + max_surface_tiles * 16 + max_triangles * 6 bytes, and the 4 GiB bound applies to that size.
+ *   tsdf_mesh_stream_index_format reports the configured format (TSDF_ERR_STATE before any config, TSDF_ERR_INVALID_ARGUMENT for a NULL pointer).
+ * tsdf_mesh_frame keeps its 112 bytes.  In a frame of format 1 `triangles` is NULL; n_vertices, n_triangles, the needs, overflow and the rest mean
+ *   what they mean in format 0, and the three capacities overflow as they do there (zero counts, zero rows, no payload copy).
+ * tsdf_mesh_stream_frame_compact fills *out for the frame currently HELD: the table, the codes, the number of rows, the level's tile grid and the
+ *   level.  The pointers go into the slot's pinned buffer and are valid until tsdf_mesh_stream_release.  An overflowed frame and a frame whose every
+ *   component was dropped have zero rows.  TSDF_ERR_STATE when no frame is held or the ring has format 0; TSDF_ERR_INVALID_ARGUMENT for a NULL out.
+ * tsdf_mesh_stream_stats counts the payload bytes that were copied: the compact sizes.
+ * With a filter (min_triangles >= 1) the device's raw buffer keeps the unfiltered uint32 frame and its tile table; the kept triangles are coded against
+ *   the filtered table: a row stays iff it keeps a vertex, first_vertex counts the kept vertices before it, first_triangle and n_triangles are
+ *   recounted over the kept triangles (a kept triangle keeps its three vertices, so its row stays).  The filtered row count travels in the 64-byte
+ *   record in front of the header.  tsdf_mesh_stream_frame_filter answers as before.
+ * Protocol: that of the ring.  The table is one launch more in the emit (a lane per lattice tile writes its row at the tile's surface ordinal), and with
+ *   a filter one single-workgroup launch more in the filter (the rows that stay); no host wait and no allocation after the first call is added.
+ * Out of scope: a compact form for tsdf_mesh_download and the PLY; slab parts (a Z-slab context refuses the ring as before); texture taps in the ring;
+ *   any change to the vertex packing; entropy coding. */
+#define TSDF_MESH_INDEX_U32    0u
+#define TSDF_MESH_INDEX_TILE16 1u
+typedef struct tsdf_mesh_tile_row { uint32_t tile, first_vertex, first_triangle, n_triangles; } tsdf_mesh_tile_row;
+typedef struct tsdf_mesh_compact {
+  const tsdf_mesh_tile_row* table;   /* n_tile_rows rows, ascending by tile */
+  const uint16_t* triangles;         /* n_triangles (of the tsdf_mesh_frame) rows of three corner codes */
+  uint64_t n_tile_rows;
+  uint32_t tiles[3];                 /* the level's lattice-tile grid */
+  uint32_t level;
+} tsdf_mesh_compact;
+int32_t tsdf_mesh_stream_config_compact(tsdf_ctx* ctx, uint32_t flags, uint32_t level, uint32_t min_triangles, uint32_t index_format, uint32_t max_vertices,
+                                        uint32_t max_triangles, uint32_t max_surface_tiles, uint32_t slots);
+int32_t tsdf_mesh_stream_index_format(tsdf_ctx* ctx, uint32_t* index_format);
+int32_t tsdf_mesh_stream_frame_compact(tsdf_ctx* ctx, tsdf_mesh_compact* out);
+
 /* ---- frame read-out: the swap ------------------------------------------------------------------------
  * The client ends a frame with glfwSwapBuffers (source/kinect_client.cpp:533): an RGBA8 window goes to a display (GLFW's default framebuffer has 8
  * bits per channel and the client sets no window hint that changes it, :942-951).  This device has no display; tsdf_present is the swap for a host

@@ -191,6 +191,28 @@ class MeshFrame(C.Structure):
                 ("bbox_min", C.c_float * 3), ("bbox_max", C.c_float * 3)]
 
 
+MESH_INDEX_U32, MESH_INDEX_TILE16 = 0, 1   # tsdf_mesh_stream_config_compact: index_format
+MESH_TILE_ROW_DTYPE = np.dtype([("tile", "<u4"), ("first_vertex", "<u4"), ("first_triangle", "<u4"), ("n_triangles", "<u4")])   # tsdf_mesh_tile_row
+
+
+class MeshCompact(C.Structure):
+    """tsdf_mesh_compact of rgbd_recon_hip.h"""
+    _fields_ = [("table", C.c_void_p), ("triangles", C.POINTER(C.c_uint16)), ("n_tile_rows", C.c_uint64), ("tiles", C.c_uint32 * 3), ("level", C.c_uint32)]
+
+
+def unpack_mesh_triangles(table, codes, tiles):
+    """the header's decoding rule of the tile-local format: table (MESH_TILE_ROW_DTYPE [R]), codes (uint16 [T][3]), tiles (the level's lattice-tile
+    grid) -> uint32 [T][3], byte for byte the uint32 triangle array of the same frame"""
+    codes = np.asarray(codes, np.uint16).reshape(-1, 3).astype(np.int64)
+    if not len(codes):
+        return np.zeros((0, 3), np.uint32)
+    row = np.repeat(np.arange(len(table)), table["n_triangles"].astype(np.int64))          # the row of every triangle: rows own consecutive ranges
+    owner = (table["tile"].astype(np.int64)[row][:, None] + ((codes >> 12) & 1) + ((codes >> 13) & 1) * int(tiles[0])
+             + ((codes >> 14) & 1) * int(tiles[0]) * int(tiles[1]))
+    owner_row = np.searchsorted(table["tile"], owner.ravel(), side="right").reshape(owner.shape) - 1   # the last row whose tile is <= owner
+    return (table["first_vertex"].astype(np.int64)[owner_row] + (codes & 0xfff)).astype(np.uint32)
+
+
 def unpack_mesh_vertices(vertices):
     """a streamed frame's vertex array -> dict(position uint16 [V][3], and for the 16-byte stride normal int16 [V][2], colour uint8 [V][4])"""
     if vertices.dtype == np.uint16:
@@ -874,20 +896,41 @@ class ReconIntegrationHip:
 
     # ------------------------------------------------------------------ mesh streaming (no counterpart in the reference)
     def mesh_stream_config(self, normals=False, colours=False, max_vertices=1 << 20, max_triangles=1 << 21, max_surface_tiles=1 << 14, slots=3, level=0,
-                           min_triangles=0):
+                           min_triangles=0, index_format=0):
         """flags, the three capacities and the slot count of the mesh ring (tsdf_mesh_stream_config); the first mesh_stream after it allocates.
         level 1 / 2 (tsdf_mesh_stream_config_lod): every frame is that level's mesh, max_surface_tiles counts its 8^3 lattice tiles.
         min_triangles >= 1 (tsdf_mesh_stream_config_filter): every frame leaves the device without its components of fewer triangles; n_* in a frame's
-        info are the filtered counts, needed_* and the capacities those of the unfiltered mesh."""
+        info are the filtered counts, needed_* and the capacities those of the unfiltered mesh.
+        index_format MESH_INDEX_TILE16 (tsdf_mesh_stream_config_compact): 6-byte tile-local triangles and a tile table instead of uint32 indices."""
         flags = (MESH_NORMALS if normals else 0) | (MESH_COLOURS if colours else 0)
         caps = (C.c_uint32(int(max_vertices)), C.c_uint32(int(max_triangles)), C.c_uint32(int(max_surface_tiles)), C.c_uint32(int(slots)))
-        if min_triangles:
+        if index_format:
+            self._ck(self._L.tsdf_mesh_stream_config_compact(self._c, C.c_uint32(flags), C.c_uint32(int(level)), C.c_uint32(int(min_triangles)),
+                                                             C.c_uint32(int(index_format)), *caps))
+        elif min_triangles:
             self._ck(self._L.tsdf_mesh_stream_config_filter(self._c, C.c_uint32(flags), C.c_uint32(int(level)), C.c_uint32(int(min_triangles)), *caps))
         elif level:
             self._ck(self._L.tsdf_mesh_stream_config_lod(self._c, C.c_uint32(flags), C.c_uint32(int(level)), *caps))
         else:
             self._ck(self._L.tsdf_mesh_stream_config(self._c, C.c_uint32(flags), *caps))
         self._mesh_stream_filtered = bool(min_triangles)                 # (behind the checks: a refused config leaves the ring as it was)
+
+    def mesh_stream_index_format(self):
+        """the index format of the last mesh_stream_config (tsdf_mesh_stream_index_format)"""
+        fmt = C.c_uint32()
+        self._ck(self._L.tsdf_mesh_stream_index_format(self._c, C.byref(fmt)))
+        return int(fmt.value)
+
+    def mesh_stream_frame_compact(self, n_triangles):
+        """(table, codes, tiles, level) of the frame held now (tsdf_mesh_stream_frame_compact): VIEWS of the slot's pinned buffer, MESH_TILE_ROW_DTYPE [R]
+        and uint16 [n_triangles][3]; TsdfError, code -4, when no frame is held or the ring streams uint32 indices"""
+        m = MeshCompact()
+        self._ck(self._L.tsdf_mesh_stream_frame_compact(self._c, C.byref(m)))
+        rows = int(m.n_tile_rows)
+        table = (np.ctypeslib.as_array(C.cast(m.table, C.POINTER(C.c_uint32)), shape=(rows, 4)).view(MESH_TILE_ROW_DTYPE).reshape(rows)
+                 if rows else np.zeros(0, MESH_TILE_ROW_DTYPE))
+        codes = np.ctypeslib.as_array(m.triangles, shape=(n_triangles, 3)) if n_triangles else np.zeros((0, 3), np.uint16)
+        return table, codes, tuple(int(x) for x in m.tiles), int(m.level)
 
     def mesh_stream_level(self):
         """the level of the last mesh_stream_config (tsdf_mesh_stream_level)"""
@@ -915,7 +958,9 @@ class ReconIntegrationHip:
     def mesh_stream_acquire(self, wait=True):
         """the oldest streamed frame not yet released as (vertices, triangles, info), still held until mesh_stream_release(); None while it is not
         complete on the host (wait=False).  vertices: a VIEW of the slot's pinned buffer, uint16 [V][4] (qx, qy, qz, 0) with stride 8, uint8 [V][16] with
-        stride 16 (unpack_mesh_vertices splits it); triangles: a view, uint32 [T][3]; info: dict of the tsdf_mesh_frame fields."""
+        stride 16 (unpack_mesh_vertices splits it); triangles: a view, uint32 [T][3]; info: dict of the tsdf_mesh_frame fields.
+        On a ring of MESH_INDEX_TILE16 triangles is the uint16 [T][3] corner codes and info["compact"] = dict(table, tiles, level): unpack_mesh_triangles(
+        table, triangles, tiles) gives the uint32 array."""
         f, ready = MeshFrame(), C.c_int32()
         self._ck(self._L.tsdf_mesh_stream_acquire(self._c, C.c_int32(1 if wait else 0), C.byref(f), C.byref(ready)))
         if not ready.value:
@@ -923,10 +968,15 @@ class ReconIntegrationHip:
         nv, nt, stride = int(f.n_vertices), int(f.n_triangles), int(f.vertex_stride)
         raw = np.ctypeslib.as_array(C.cast(f.vertices, C.POINTER(C.c_uint8)), shape=(nv * stride,)) if nv else np.zeros(0, np.uint8)
         vertices = raw.view(np.uint16).reshape(nv, 4) if stride == 8 else raw.reshape(nv, 16)
-        triangles = np.ctypeslib.as_array(f.triangles, shape=(nt, 3)) if nt else np.zeros((0, 3), np.uint32)
+        compact = self.mesh_stream_index_format() == MESH_INDEX_TILE16
+        if not compact:
+            triangles = np.ctypeslib.as_array(f.triangles, shape=(nt, 3)) if nt else np.zeros((0, 3), np.uint32)
         info = dict(n_vertices=nv, n_triangles=nt, needed_vertices=int(f.needed_vertices), needed_triangles=int(f.needed_triangles),
                     needed_tiles=int(f.needed_tiles), tag=int(f.tag), flags=int(f.flags), vertex_stride=stride, overflow=int(f.overflow),
                     res=tuple(int(x) for x in f.res), bbox_min=np.array(f.bbox_min[:], np.float32), bbox_max=np.array(f.bbox_max[:], np.float32))
+        if compact:
+            table, triangles, tiles, level = self.mesh_stream_frame_compact(nt)
+            info["compact"] = dict(table=table, tiles=tiles, level=level, triangles_null=not f.triangles)   # (the C frame's uint32 pointer: NULL here)
         return vertices, triangles, info
 
     def mesh_stream_release(self):
@@ -939,6 +989,8 @@ class ReconIntegrationHip:
         if got is None:
             return None
         out = (got[0].copy(), got[1].copy(), got[2])
+        if "compact" in out[2]:
+            out[2]["compact"]["table"] = out[2]["compact"]["table"].copy()
         if getattr(self, "_mesh_stream_filtered", False):
             out[2]["filter"] = self.mesh_stream_frame_filter()
         self.mesh_stream_release()

@@ -679,8 +679,8 @@ void release_mesh_stream(tsdf_ctx* c) {
   }
   mesh_scratch_free(R.scratch, R.records);
   MeshStreamFilter& F = R.filter;
-  hipFree(F.raw); hipFree(F.parent); hipFree(F.label); hipFree(F.count); hipFree(F.keep); hipFree(F.vertex_sums); hipFree(F.triangle_sums); hipFree(F.words);
-  F = MeshStreamFilter{};
+  hipFree(F.raw); hipFree(F.parent); hipFree(F.label); hipFree(F.count); hipFree(F.keep); hipFree(F.vertex_sums); hipFree(F.triangle_sums); hipFree(F.words); hipFree(F.tri_local);
+  F = MeshStreamFilter{};                                                // (raw_table lies inside raw's allocation)
   R.allocated = false; R.ring.reset(); R.device_bytes = 0;
 }
 // a slab's part of the mesh and what its link needs (nothing queued reads them: extract, link and download synchronise)
@@ -2855,7 +2855,7 @@ int32_t tsdf_mesh_component_stats(tsdf_ctx* c, uint64_t out[4]) {
 }
 
 // ---- mesh streaming (the definition is in the header): the same mesh every frame, packed, without a host wait or an allocation after the first call
-static size_t mesh_stream_payload_capacity(const tsdf_ctx::MeshStream& R) { return (size_t)R.max_vertices * (R.flags ? 16 : 8) + (size_t)R.max_triangles * 12; }
+static size_t mesh_stream_payload_capacity(const tsdf_ctx::MeshStream& R) { return (size_t)R.layout().payload_capacity(R.max_vertices, R.max_triangles, R.max_tiles); }
 int32_t tsdf_mesh_stream_config(tsdf_ctx* c, uint32_t flags, uint32_t max_vertices, uint32_t max_triangles, uint32_t max_surface_tiles, uint32_t slots) {
   return tsdf_mesh_stream_config_lod(c, flags, 0u, max_vertices, max_triangles, max_surface_tiles, slots);
 }
@@ -2864,20 +2864,25 @@ int32_t tsdf_mesh_stream_config_lod(tsdf_ctx* c, uint32_t flags, uint32_t level,
 }
 int32_t tsdf_mesh_stream_config_filter(tsdf_ctx* c, uint32_t flags, uint32_t level, uint32_t min_triangles, uint32_t max_vertices, uint32_t max_triangles,
                                        uint32_t max_surface_tiles, uint32_t slots) {
+  return tsdf_mesh_stream_config_compact(c, flags, level, min_triangles, TSDF_MESH_INDEX_U32, max_vertices, max_triangles, max_surface_tiles, slots);
+}
+int32_t tsdf_mesh_stream_config_compact(tsdf_ctx* c, uint32_t flags, uint32_t level, uint32_t min_triangles, uint32_t index_format, uint32_t max_vertices,
+                                        uint32_t max_triangles, uint32_t max_surface_tiles, uint32_t slots) {
   CHECK_CTX(c);
   tsdf_ctx::MeshStream& R = c->mstream;
+  if (index_format > TSDF_MESH_INDEX_TILE16) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "mesh index format %u (0: uint32 indices, 1: tile-local 16-bit codes)", index_format);
   if (level > (uint32_t)kMeshMaxLevel) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "mesh level %u (0 .. %d: every voxel, every 2nd, every 4th)", level, kMeshMaxLevel);
   if ((flags & ~(TSDF_MESH_NORMALS | TSDF_MESH_COLOURS)) || !max_vertices || !max_triangles || !max_surface_tiles || slots < 2 || slots > kMaxResultSlots)
     FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "mesh stream flags %u / capacities %u vertices, %u triangles, %u tiles / slots %u (flags 1 normals, 2 colours; capacities > 0; 2..%u slots)",
          flags, max_vertices, max_triangles, max_surface_tiles, slots, kMaxResultSlots);
-  if ((uint64_t)max_vertices * (flags ? 16 : 8) + (uint64_t)max_triangles * 12 > (4ull << 30)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "a mesh stream slot of more than 4 GiB");
+  if (!MeshFrameLayout{index_format, flags ? 16u : 8u}.fits(max_vertices, max_triangles, max_surface_tiles)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "a mesh stream slot of more than 4 GiB");
   if (!R.ring.idle()) FAIL(c, TSDF_ERR_STATE, "%u streamed mesh frame(s) are queued or held: acquire and release them first", R.ring.count);
   HIP_TRY(c, hipSetDevice(c->device));
   // The ring is idle for the copies only (each was waited for before its frame was released): a frame that overflowed or had no payload was handed out
   // behind its header copy alone, and its emit launches, which read the slot's device header and the scratch, may still be queued on the context's stream.
   if (R.allocated) HIP_TRY(c, hipStreamSynchronize(c->stream));
   release_mesh_stream(c);
-  R.flags = flags; R.level = level; R.max_vertices = max_vertices; R.max_triangles = max_triangles; R.max_tiles = max_surface_tiles; R.min_triangles = min_triangles; R.ring.configure(slots); R.configured = true;
+  R.flags = flags; R.level = level; R.max_vertices = max_vertices; R.max_triangles = max_triangles; R.max_tiles = max_surface_tiles; R.min_triangles = min_triangles; R.index_format = index_format; R.ring.configure(slots); R.configured = true;
   R.frames = R.overflowed = R.bytes_copied = 0;
   return TSDF_OK;
 }
@@ -2895,16 +2900,35 @@ int32_t tsdf_mesh_stream_min_triangles(tsdf_ctx* c, uint32_t* min_triangles) {
   *min_triangles = c->mstream.min_triangles;
   return TSDF_OK;
 }
+int32_t tsdf_mesh_stream_index_format(tsdf_ctx* c, uint32_t* index_format) {
+  CHECK_CTX(c);
+  if (!index_format) return TSDF_ERR_INVALID_ARGUMENT;
+  if (!c->mstream.configured) FAIL(c, TSDF_ERR_STATE, "tsdf_mesh_stream_index_format before tsdf_mesh_stream_config");
+  *index_format = c->mstream.index_format;
+  return TSDF_OK;
+}
 // the filter's raw buffer and scratch (min_triangles >= 1): sized by the capacities, like everything the filter launches
-static bool mesh_stream_filter_allocate(tsdf_ctx::MeshStream& R, uint64_t* bytes) {
+static bool mesh_stream_filter_allocate(tsdf_ctx::MeshStream& R, const int c_res[3], uint64_t* bytes) {
   MeshStreamFilter& F = R.filter;
   F.max_vertices = R.max_vertices; F.max_triangles = R.max_triangles; F.min_triangles = R.min_triangles; F.stride = R.flags ? 16u : 8u;
   const size_t nv = R.max_vertices;
+  // the raw frame is the uint32 one in either format; the tile-local format keeps the raw tile table behind it, at a multiple of 16 bytes
+  const bool compact = R.index_format == kMeshIndexTile16;
+  const size_t raw_payload = (size_t)MeshFrameLayout{kMeshIndexU32, F.stride}.payload_capacity(R.max_vertices, R.max_triangles, R.max_tiles);
+  const size_t raw_frame = sizeof(MeshStreamHeader) + (compact ? (size_t)MeshFrameLayout::align16(raw_payload) : raw_payload);
+  if (compact) {
+    const MeshLattice L = mesh_lattice(c_res, (int)R.level);
+    F.ntx = L.ntx; F.nty = L.nty;
+    const size_t local_bytes = ((size_t)R.max_triangles + 3) / 4 * sizeof(uint16_t);
+    if (hipMalloc((void**)&F.tri_local, local_bytes) != hipSuccess) return false;
+    *bytes += local_bytes;
+  }
   const struct { void** p; size_t bytes; } arrays[8] = {
-    {(void**)&F.raw, sizeof(MeshStreamHeader) + mesh_stream_payload_capacity(R)}, {(void**)&F.parent, nv * sizeof(uint32_t)}, {(void**)&F.label, nv * sizeof(uint32_t)},
+    {(void**)&F.raw, raw_frame + (compact ? (size_t)R.max_tiles * sizeof(MeshTileRow) : 0)}, {(void**)&F.parent, nv * sizeof(uint32_t)}, {(void**)&F.label, nv * sizeof(uint32_t)},
     {(void**)&F.count, nv * sizeof(uint32_t)}, {(void**)&F.keep, (nv + 3) / 4 * 4}, {(void**)&F.vertex_sums, mesh_stream_filter_scan_words(R.max_vertices) * sizeof(uint64_t)},
-    {(void**)&F.triangle_sums, mesh_stream_filter_scan_words(R.max_triangles) * sizeof(uint64_t)}, {(void**)&F.words, 2 * sizeof(uint32_t)}};
+    {(void**)&F.triangle_sums, mesh_stream_filter_scan_words(R.max_triangles) * sizeof(uint64_t)}, {(void**)&F.words, 3 * sizeof(uint32_t)}};
   for (const auto& A : arrays) { if (hipMalloc(A.p, A.bytes) != hipSuccess) return false; *bytes += A.bytes; }
+  if (compact) F.raw_table = (MeshTileRow*)((uint8_t*)F.raw + raw_frame);
   return true;
 }
 // slots and scratch, once per configuration and grid
@@ -2915,7 +2939,7 @@ static int32_t mesh_stream_allocate(tsdf_ctx* c) {
                slot_bytes = lead + sizeof(MeshStreamHeader) + mesh_stream_payload_capacity(R), record_bytes = (size_t)R.max_tiles * 512 * sizeof(uint32_t);
   uint64_t bytes = (uint64_t)R.ring.slots * slot_bytes + record_bytes;
   bool ok = mesh_scratch_allocate(R.scratch, (int)n_tiles, (int)R.level, &bytes) == hipSuccess && hipMalloc((void**)&R.records, record_bytes) == hipSuccess;
-  if (ok && R.min_triangles) ok = mesh_stream_filter_allocate(R, &bytes);
+  if (ok && R.min_triangles) ok = mesh_stream_filter_allocate(R, c->vol.res, &bytes);
   for (uint32_t k = 0; ok && k < R.ring.slots; ++k) {
     tsdf_ctx::MeshStreamSlot& S = R.slot[k];
     ok = hipMalloc((void**)&S.dev, slot_bytes) == hipSuccess;
@@ -2941,7 +2965,10 @@ static int32_t mesh_stream_pump(tsdf_ctx* c) {
     if (int32_t rc = event_reached(c, S.header_ready, false, &arrived)) return rc;
     if (!arrived) break;                                                 // (behind a header still travelling nothing has arrived either)
     const MeshStreamHeader* H = (const MeshStreamHeader*)S.host;
-    S.payload_bytes = (size_t)H->n_vertices * (R.flags ? 16 : 8) + (size_t)H->n_triangles * 12;
+    S.table_rows = 0;
+    if (R.index_format == kMeshIndexTile16 && H->n_vertices)               // (an overflowed or emptied frame has no row)
+      S.table_rows = R.min_triangles ? ((const MeshStreamFilterRecord*)(S.host - S.lead))->table_rows : H->needed_tiles;
+    S.payload_bytes = (size_t)R.layout().payload_bytes(H->n_vertices, H->n_triangles, S.table_rows);
     if (S.payload_bytes) {
       HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, S.emitted, 0));
       HIP_TRY(c, hipMemcpyAsync(S.host + sizeof(MeshStreamHeader), S.dev + sizeof(MeshStreamHeader), S.payload_bytes, hipMemcpyDeviceToHost, c->copy_stream));
@@ -2959,7 +2986,8 @@ static int32_t mesh_stream_filtered_tail(tsdf_ctx* c, tsdf_ctx::MeshStreamSlot& 
   tsdf_ctx::MeshStream& R = c->mstream;
   const MeshStreamFilter& F = R.filter;
   timer_begin(c, "mesh_stream_emit");
-  launch_mesh_stream_emit(c->stream, c->vol, c->luts, c->frame, mesh_geometry(c), R.scratch, R.flags, F.raw, R.records, F.raw + 1);
+  if (F.raw_table) launch_mesh_stream_emit_compact(c->stream, c->vol, c->luts, c->frame, mesh_geometry(c), R.scratch, R.flags, F.raw, R.records, F.raw + 1, F.raw_table);
+  else launch_mesh_stream_emit(c->stream, c->vol, c->luts, c->frame, mesh_geometry(c), R.scratch, R.flags, F.raw, R.records, F.raw + 1);
   timer_end(c, "mesh_stream_emit");
   HIP_TRY(c, hipGetLastError());
   if (int32_t rc = overlay_rerecord_draw(c)) return rc;
@@ -2988,7 +3016,7 @@ int32_t tsdf_mesh_stream(tsdf_ctx* c, uint64_t tag) {
   if (!R.allocated && (rc = mesh_stream_allocate(c))) return rc;
   if ((rc = mesh_stream_pump(c))) return rc;
   tsdf_ctx::MeshStreamSlot& S = R.slot[R.ring.push()];                   // (queued before its calls are: result_paths.hpp's transitions precede what acts on them)
-  S.tag = tag; S.payload_issued = false; S.payload_bytes = 0;
+  S.tag = tag; S.payload_issued = false; S.payload_bytes = 0; S.table_rows = 0;
   for (int a = 0; a < 3; ++a) S.res[a] = c->res[a];
   const bool filtered = R.min_triangles != 0;
   MeshStreamHeader* H = filtered ? R.filter.raw : (MeshStreamHeader*)S.dev;   // with a filter: count, scan, header and emit write the raw buffer, not the slot
@@ -3014,7 +3042,8 @@ int32_t tsdf_mesh_stream(tsdf_ctx* c, uint64_t tag) {
   HIP_TRY(c, hipEventRecord(S.header_ready, c->copy_stream));
   if (cells) {
     timer_begin(c, "mesh_stream_emit");
-    launch_mesh_stream_emit(c->stream, V, c->luts, c->frame, mesh_geometry(c), R.scratch, R.flags, H, R.records, S.dev + sizeof(MeshStreamHeader));
+    if (R.index_format == kMeshIndexTile16) launch_mesh_stream_emit_compact(c->stream, V, c->luts, c->frame, mesh_geometry(c), R.scratch, R.flags, H, R.records, S.dev + sizeof(MeshStreamHeader), nullptr);
+    else launch_mesh_stream_emit(c->stream, V, c->luts, c->frame, mesh_geometry(c), R.scratch, R.flags, H, R.records, S.dev + sizeof(MeshStreamHeader));
     timer_end(c, "mesh_stream_emit");
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(S.emitted, c->stream));
@@ -3047,7 +3076,8 @@ int32_t tsdf_mesh_stream_acquire(tsdf_ctx* c, int32_t wait, tsdf_mesh_frame* out
   const uint32_t stride = R.flags ? 16u : 8u;
   *out = tsdf_mesh_frame{};
   out->vertices = S.host + sizeof(MeshStreamHeader);
-  out->triangles = (const uint32_t*)(S.host + sizeof(MeshStreamHeader) + (size_t)H->n_vertices * stride);
+  // (tile-local format: the triangles are 16-bit codes, tsdf_mesh_stream_frame_compact hands them out)
+  out->triangles = R.index_format == kMeshIndexTile16 ? nullptr : (const uint32_t*)(S.host + sizeof(MeshStreamHeader) + (size_t)H->n_vertices * stride);
   out->n_vertices = H->n_vertices; out->n_triangles = H->n_triangles;
   out->needed_vertices = H->needed_vertices; out->needed_triangles = H->needed_triangles; out->needed_tiles = H->needed_tiles;
   out->tag = S.tag; out->flags = R.flags; out->vertex_stride = stride; out->overflow = H->overflow;
@@ -3072,6 +3102,24 @@ int32_t tsdf_mesh_stream_frame_filter(tsdf_ctx* c, uint64_t out[4]) {
   const tsdf_ctx::MeshStreamSlot& S = R.slot[R.ring.oldest()];
   const MeshStreamFilterRecord* r = (const MeshStreamFilterRecord*)(S.host - S.lead);
   out[0] = r->components; out[1] = r->kept; out[2] = r->vertices_removed; out[3] = r->triangles_removed;
+  return TSDF_OK;
+}
+int32_t tsdf_mesh_stream_frame_compact(tsdf_ctx* c, tsdf_mesh_compact* out) {
+  CHECK_CTX(c);
+  if (!out) return TSDF_ERR_INVALID_ARGUMENT;
+  const tsdf_ctx::MeshStream& R = c->mstream;
+  if (!R.configured || R.index_format != kMeshIndexTile16) FAIL(c, TSDF_ERR_STATE, "the mesh ring is configured with uint32 indices (tsdf_mesh_stream_config_compact, TSDF_MESH_INDEX_TILE16)");
+  if (!R.ring.held) FAIL(c, TSDF_ERR_STATE, "no streamed mesh frame is held (tsdf_mesh_stream_acquire)");
+  const tsdf_ctx::MeshStreamSlot& S = R.slot[R.ring.oldest()];
+  const MeshStreamHeader* H = (const MeshStreamHeader*)S.host;
+  const MeshFrameLayout layout = R.layout();
+  const uint8_t* payload = S.host + sizeof(MeshStreamHeader);
+  const MeshLattice L = mesh_lattice(S.res, (int)R.level);
+  *out = tsdf_mesh_compact{};
+  out->table = (const tsdf_mesh_tile_row*)(payload + layout.table_offset(H->n_vertices));
+  out->triangles = (const uint16_t*)(payload + layout.triangle_offset(H->n_vertices, S.table_rows));
+  out->n_tile_rows = S.table_rows;
+  out->tiles[0] = (uint32_t)L.ntx; out->tiles[1] = (uint32_t)L.nty; out->tiles[2] = (uint32_t)L.ntz; out->level = R.level;
   return TSDF_OK;
 }
 int32_t tsdf_mesh_stream_stats(tsdf_ctx* c, uint64_t out[4]) {

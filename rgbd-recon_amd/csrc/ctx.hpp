@@ -153,14 +153,18 @@ struct tsdf_ctx {
   // With a filter (min_triangles >= 1, tsdf_mesh_stream_config_filter) the emit writes into filter.raw, header_written is recorded behind the filter's
   // final header and emitted behind its scatter; a slot's buffers then begin `lead` = 64 bytes in front of dev / host with the frame's
   // MeshStreamFilterRecord, so that record and header travel as one copy and the payload stays 64 bytes behind the header.
+  // index_format 1 (tsdf_mesh_stream_config_compact): the payload is vertices, padding, tile table, 6-byte triangles (result_paths.hpp: MeshFrameLayout);
+  // table_rows is what the pump read for the slot's frame: the header's needed_tiles, with a filter the record's table_rows.
   struct MeshStreamSlot { uint8_t* dev = nullptr; uint8_t* host = nullptr; hipEvent_t header_written = nullptr, emitted = nullptr, header_ready = nullptr, ready = nullptr;
-                          uint64_t tag = 0; size_t payload_bytes = 0; bool payload_issued = false; int res[3] = {0, 0, 0}; size_t lead = 0; };
+                          uint64_t tag = 0; size_t payload_bytes = 0; bool payload_issued = false; int res[3] = {0, 0, 0}; size_t lead = 0; uint64_t table_rows = 0; };
   struct MeshStream {
     MeshStreamSlot slot[kMaxResultSlots];
     ResultRing ring{};
     MeshScratch scratch{}; uint32_t* records = nullptr;
     uint32_t flags = 0, level = 0, max_vertices = 0, max_triangles = 0, max_tiles = 0;   // level: tsdf_mesh_stream_config_lod (the scratch is sized by its lattice tiles)
     uint32_t min_triangles = 0;     // 0: no filter, the frame is emitted into its slot
+    uint32_t index_format = 0;      // 0: uint32 triangles, 1: tile-local 6-byte triangles and a tile table
+    MeshFrameLayout layout() const { return MeshFrameLayout{index_format, flags ? 16u : 8u}; }
     MeshStreamFilter filter{};      // the raw buffer and the filter's scratch (null without a filter)
     bool configured = false, allocated = false;
     uint64_t frames = 0, overflowed = 0, bytes_copied = 0, device_bytes = 0;

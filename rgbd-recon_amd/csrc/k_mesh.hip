@@ -265,11 +265,16 @@ __global__ __launch_bounds__(kMeshThreads, 4) void k_mesh_vertices_packed(Volume
   }
 }
 
-// ---- 4. triangles, from the records alone
-template <int kLevel>
+#ifndef RR_MESH_COMPACT_LDS
+#define RR_MESH_COMPACT_LDS 0                                          // 1: the measured alternative of the 6-byte rows' stores (below; DESIGN.md has both)
+#endif
+// ---- 4. triangles, from the records alone.  Out = uint16_t: the streamed tile-local corner codes (bits 0..11 the vertex's offset inside its owner
+// tile, bits 12..14 where that tile lies from this one: a corner whose local coordinate is 8 belongs to the +x / +y / +z neighbour) instead of mesh indices
+template <int kLevel, typename Out = uint32_t>
 __device__ __forceinline__ void mesh_tile_triangles(const Volume& V, const uint2* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_vbase,
                                                     const unsigned long long* __restrict__ tile_tbase, const uint32_t* __restrict__ tile_rec,
-                                                    const uint32_t* __restrict__ records, uint32_t* __restrict__ out_tri) {
+                                                    const uint32_t* __restrict__ records, Out* __restrict__ out_tri) {
+  constexpr bool kLocal = std::is_same<Out, uint16_t>::value;
   __shared__ uint32_t s_first[kMeshCorners];                           // per corner: the mesh index of the first vertex it owns
   __shared__ uint8_t s_mask[kMeshCorners];                             // ... and its record's low byte (edge mask, inside bit)
   __shared__ uint32_t s_wave[kMeshWaves];
@@ -285,7 +290,9 @@ __device__ __forceinline__ void mesh_tile_triangles(const Volume& V, const uint2
       const uint32_t slot = tile_rec[tile];
       if (slot != kNoSlot) {                                           // (a tile without surface owns no crossed edge: nothing is looked up in it)
         const uint32_t r = records[(size_t)slot * kMeshThreads + (((z & 7) << 6) | ((y & 7) << 3) | (x & 7))];
-        first = tile_vbase[tile] + (r >> 8); mask = r & 0xffu;
+        if constexpr (kLocal) first = (r >> 8) | ((uint32_t)((lx >> 3) | ((ly >> 3) << 1) | ((lz >> 3) << 2)) << 12);
+        else first = tile_vbase[tile] + (r >> 8);
+        mask = r & 0xffu;
       }
     }
     s_first[i] = first; s_mask[i] = (uint8_t)mask;
@@ -302,8 +309,22 @@ __device__ __forceinline__ void mesh_tile_triangles(const Volume& V, const uint2
   }
   uint32_t total;
   const uint32_t off = block_exclusive_sum<kMeshWaves>(ntri, s_wave, &total);
-  if (ntri == 0) return;
-  mesh_cell_triangles(corners, s_first, s_mask, lx, ly, lz, out_tri + (size_t)(tile_tbase[t.id] + off) * 3);
+  if constexpr (kLocal && RR_MESH_COMPACT_LDS) {
+    // The alternative: a tile's rows are contiguous, so they are staged in LDS at the destination's offset inside its 16-byte line and leave as
+    // aligned 16-byte stores, the ragged head and tail as shorts.
+    __shared__ __attribute__((aligned(16))) uint16_t s_rows[kMeshThreads * 12 * 3 + 8];
+    Out* __restrict__ g = out_tri + (size_t)tile_tbase[t.id] * 3;
+    const uint32_t shift = (uint32_t)(((size_t)g & 15u) >> 1), n16 = total * 3u;
+    if (ntri) mesh_cell_triangles(corners, s_first, s_mask, lx, ly, lz, s_rows + shift + off * 3u);
+    __syncthreads();
+    const uint32_t head = min(n16, (8u - shift) & 7u), body = (n16 - head) >> 3, tail = head + (body << 3);
+    for (uint32_t i = threadIdx.x; i < head; i += kMeshThreads) g[i] = s_rows[shift + i];
+    for (uint32_t i = threadIdx.x; i < body; i += kMeshThreads) ((uint4*)(g + head))[i] = ((const uint4*)(s_rows + shift + head))[i];
+    for (uint32_t i = tail + threadIdx.x; i < n16; i += kMeshThreads) g[i] = s_rows[shift + i];
+  } else {
+    if (ntri == 0) return;
+    mesh_cell_triangles(corners, s_first, s_mask, lx, ly, lz, out_tri + (size_t)(tile_tbase[t.id] + off) * 3);
+  }
 }
 template <int kLevel>
 __global__ __launch_bounds__(kMeshThreads) void k_mesh_triangles(Volume V, const uint2* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_vbase,
@@ -319,6 +340,34 @@ __global__ __launch_bounds__(kMeshThreads) void k_mesh_triangles_stream(Volume V
                                                                         uint8_t* __restrict__ payload, uint32_t stride) {
   if (mesh_stream_overflow(H)) return;
   mesh_tile_triangles<kLevel>(V, tile_cnt, tile_vbase, tile_tbase, tile_rec, records, (uint32_t*)(payload + (size_t)H->needed_vertices * stride));
+}
+// The tile-local format (launch_mesh_stream_emit_compact): the tile table, one lane per lattice tile.  A tile with a vertex writes its row at its surface
+// ordinal (tile_rec: the rows are the surface tiles in tile order) as one 16-byte store; the row area begins at a multiple of 16 bytes -- in the payload
+// behind the vertices and their zero padding, or at raw_table (the filter's raw frame, whose payload is the uint32 one).  In a launch of its own: folded
+// into the triangle launch (lane 0 of a tile's workgroup) it measured slower at level 0.
+__device__ __forceinline__ MeshTileRow* mesh_stream_table(const MeshStreamHeader* __restrict__ H, uint8_t* __restrict__ payload, uint32_t stride) {
+  return (MeshTileRow*)(payload + (((size_t)H->needed_vertices * stride + 15u) & ~(size_t)15u));
+}
+__global__ __launch_bounds__(kScanThreads) void k_mesh_stream_table(const MeshStreamHeader* __restrict__ H, const uint2* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_vbase,
+                                                                    const unsigned long long* __restrict__ tile_tbase, const uint32_t* __restrict__ tile_rec, int n,
+                                                                    uint8_t* __restrict__ payload, uint32_t stride, MeshTileRow* __restrict__ raw_table) {
+  const int t = (int)(blockIdx.x * kScanThreads + threadIdx.x);
+  if (mesh_stream_overflow(H) || t >= n) return;
+  const size_t vertex_bytes = (size_t)H->needed_vertices * stride;
+  if (!raw_table && t == 0 && (vertex_bytes & 8u)) *(uint2*)(payload + vertex_bytes) = make_uint2(0u, 0u);   // the padding
+  const uint2 cnt = tile_cnt[t];
+  if (cnt.x)                                                             // (tile_rec < needed_tiles <= max_tiles)
+    *(uint4*)((raw_table ? raw_table : mesh_stream_table(H, payload, stride)) + tile_rec[t]) = make_uint4((uint32_t)t, tile_vbase[t], (uint32_t)tile_tbase[t], cnt.y);
+}
+// ... and the 6-byte triangles, behind the vertices, the padding and the needed_tiles table rows -- all inside the slot, as none of the three needs exceeds
+// its capacity
+template <int kLevel>
+__global__ __launch_bounds__(kMeshThreads) void k_mesh_triangles_stream_compact(Volume V, const MeshStreamHeader* __restrict__ H, const uint2* __restrict__ tile_cnt,
+                                                                                const uint32_t* __restrict__ tile_vbase, const unsigned long long* __restrict__ tile_tbase,
+                                                                                const uint32_t* __restrict__ tile_rec, const uint32_t* __restrict__ records,
+                                                                                uint8_t* __restrict__ payload, uint32_t stride) {
+  if (mesh_stream_overflow(H)) return;
+  mesh_tile_triangles<kLevel, uint16_t>(V, tile_cnt, tile_vbase, tile_tbase, tile_rec, records, (uint16_t*)(mesh_stream_table(H, payload, stride) + H->needed_tiles));
 }
 // one lane: the frame's header from the scan's totals (sums[nb]) and the ring's capacities
 __global__ void k_mesh_stream_header(const MeshSums* __restrict__ totals, MeshStreamHeader* __restrict__ H, uint32_t max_vertices, uint32_t max_triangles, uint32_t max_tiles) {
@@ -360,20 +409,35 @@ void launch_mesh_emit(hipStream_t st, const Volume& V, const StreamTable& T, con
 void launch_mesh_stream_header(hipStream_t st, const MeshScratch& S, MeshStreamHeader* H, uint32_t max_vertices, uint32_t max_triangles, uint32_t max_tiles) {
   hipLaunchKernelGGL(k_mesh_stream_header, dim3(1), dim3(1), 0, st, (const MeshSums*)S.sums + mesh_scan_blocks(S.n_tiles), H, max_vertices, max_triangles, max_tiles);
 }
-void launch_mesh_stream_emit(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S, uint32_t flags,
-                             const MeshStreamHeader* H, uint32_t* records, void* payload) {
+// compact: the tile-local format -- the same packed vertices (the same kernel), the table, then the 6-byte triangles, or, with raw_table (the filter's raw
+// frame), the uint32 triangles of the plain ring
+static void mesh_stream_emit(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S, uint32_t flags,
+                             const MeshStreamHeader* H, uint32_t* records, void* payload, bool compact, MeshTileRow* raw_table) {
   mesh_instantiation(V, S, [&](auto sparse, auto level) {
     constexpr bool kSparse = decltype(sparse)::value;
     constexpr int kLevel = decltype(level)::value;
     const dim3 g(S.n_tiles), b(kMeshThreads);
+    const uint32_t stride = flags ? 16u : 8u;
     switch (flags & 3u) {
       case 0u: hipLaunchKernelGGL((k_mesh_vertices_packed<kSparse, 0u, kLevel>), g, b, 0, st, V, T, F, G, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
       case 1u: hipLaunchKernelGGL((k_mesh_vertices_packed<kSparse, 1u, kLevel>), g, b, 0, st, V, T, F, G, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
       case 2u: hipLaunchKernelGGL((k_mesh_vertices_packed<kSparse, 2u, kLevel>), g, b, 0, st, V, T, F, G, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
       default: hipLaunchKernelGGL((k_mesh_vertices_packed<kSparse, 3u, kLevel>), g, b, 0, st, V, T, F, G, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
     }
-    hipLaunchKernelGGL(k_mesh_triangles_stream<kLevel>, g, b, 0, st, V, H, S.tile_cnt, S.tile_vbase, S.tile_tbase, S.tile_rec, records, (uint8_t*)payload, flags ? 16u : 8u);
+    if (compact)
+      hipLaunchKernelGGL(k_mesh_stream_table, dim3((S.n_tiles + kScanThreads - 1) / kScanThreads), dim3(kScanThreads), 0, st, H, S.tile_cnt, S.tile_vbase, S.tile_tbase, S.tile_rec,
+                         S.n_tiles, (uint8_t*)payload, stride, raw_table);
+    if (compact && !raw_table) hipLaunchKernelGGL(k_mesh_triangles_stream_compact<kLevel>, g, b, 0, st, V, H, S.tile_cnt, S.tile_vbase, S.tile_tbase, S.tile_rec, records, (uint8_t*)payload, stride);
+    else hipLaunchKernelGGL(k_mesh_triangles_stream<kLevel>, g, b, 0, st, V, H, S.tile_cnt, S.tile_vbase, S.tile_tbase, S.tile_rec, records, (uint8_t*)payload, stride);
   });
+}
+void launch_mesh_stream_emit(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S, uint32_t flags,
+                             const MeshStreamHeader* H, uint32_t* records, void* payload) {
+  mesh_stream_emit(st, V, T, F, G, S, flags, H, records, payload, false, nullptr);
+}
+void launch_mesh_stream_emit_compact(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S, uint32_t flags,
+                                     const MeshStreamHeader* H, uint32_t* records, void* payload, MeshTileRow* raw_table) {
+  mesh_stream_emit(st, V, T, F, G, S, flags, H, records, payload, true, raw_table);
 }
 
 }  // namespace rr

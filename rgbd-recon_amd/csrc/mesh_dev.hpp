@@ -175,8 +175,11 @@ __device__ __forceinline__ uint32_t edge_vertex(const uint32_t* s_first, const u
   const int i = corner_index(lx + (x & 1), ly + ((x >> 1) & 1), lz + (x >> 2)), d = y - x;
   return s_first[i] + (uint32_t)__popc((uint32_t)s_mask[i] & ((1u << (d - 1)) - 1u));
 }
-// the triangles of the cell at (lx, ly, lz) with the corner bits `corners`, written from o on in (tetrahedron, triangle) order
-__device__ __forceinline__ void mesh_cell_triangles(uint32_t corners, const uint32_t* s_first, const uint8_t* s_mask, int lx, int ly, int lz, uint32_t* __restrict__ o) {
+// the triangles of the cell at (lx, ly, lz) with the corner bits `corners`, written from o on in (tetrahedron, triangle) order.  Out: uint32_t, or
+// uint16_t for the streamed tile-local codes (s_first then holds, per corner, the offset inside the owner tile with the neighbour code from bit 12 up:
+// offset + rank stays below 3584, so the sum never reaches the code)
+template <typename Out>
+__device__ __forceinline__ void mesh_cell_triangles(uint32_t corners, const uint32_t* s_first, const uint8_t* s_mask, int lx, int ly, int lz, Out* __restrict__ o) {
   for (int k = 0; k < 6; ++k) {
     const int v[4] = {c_tet[k][0], c_tet[k][1], c_tet[k][2], c_tet[k][3]};
     uint32_t cs = 0;
@@ -191,7 +194,7 @@ __device__ __forceinline__ void mesh_cell_triangles(uint32_t corners, const uint
       uint32_t e[3]; int n = 0;
       for (int j = 0; j < 4; ++j)
         if (j != a) { e[n++] = edge_vertex(s_first, s_mask, lx, ly, lz, min(v[a], v[j]), max(v[a], v[j])); }
-      o[0] = e[0]; o[1] = flip ? e[2] : e[1]; o[2] = flip ? e[1] : e[2];
+      o[0] = (Out)e[0]; o[1] = (Out)(flip ? e[2] : e[1]); o[2] = (Out)(flip ? e[1] : e[2]);
       o += 3;
     } else {                                                           // inside A before B, outside C before D: the quad AC, AD, BD, BC as (AC, AD, BD), (AC, BD, BC)
       int in[2], out[2], ni = 0, no = 0;
@@ -200,8 +203,8 @@ __device__ __forceinline__ void mesh_cell_triangles(uint32_t corners, const uint
       const uint32_t ad = edge_vertex(s_first, s_mask, lx, ly, lz, min(in[0], out[1]), max(in[0], out[1]));
       const uint32_t bd = edge_vertex(s_first, s_mask, lx, ly, lz, min(in[1], out[1]), max(in[1], out[1]));
       const uint32_t bc = edge_vertex(s_first, s_mask, lx, ly, lz, min(in[1], out[0]), max(in[1], out[0]));
-      o[0] = ac; o[1] = flip ? bd : ad; o[2] = flip ? ad : bd;
-      o[3] = ac; o[4] = flip ? bc : bd; o[5] = flip ? bd : bc;
+      o[0] = (Out)ac; o[1] = (Out)(flip ? bd : ad); o[2] = (Out)(flip ? ad : bd);
+      o[3] = (Out)ac; o[4] = (Out)(flip ? bc : bd); o[5] = (Out)(flip ? bd : bc);
       o += 6;
     }
   }

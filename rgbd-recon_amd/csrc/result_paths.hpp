@@ -30,6 +30,30 @@ struct ResultRing {
   }
 };
 
+// The mesh ring's slot and payload arithmetic (include/rgbd_recon_hip.h: "mesh streaming" and "mesh streaming: compact triangles").  A slot is a 64-byte
+// header and a payload; the payload holds the packed vertices (stride 8 or 16) and then, in the uint32 format, the triangles (12 bytes each), in the
+// tile-local format zero padding to a multiple of 16, the tile table (16 bytes a row) and the triangles (6 bytes each).  The device computes the same
+// offsets from its header's counts (k_mesh.hip, k_mesh_stream_filter.hip); tests/test_mesh_compact_layout.py walks these functions on a CPU.
+constexpr uint32_t kMeshIndexU32 = 0, kMeshIndexTile16 = 1;             // TSDF_MESH_INDEX_U32 / _TILE16
+constexpr uint64_t kMeshHeaderBytes = 64, kMeshTileRowBytes = 16, kMeshSlotLimit = 4ull << 30;
+struct MeshFrameLayout {
+  uint32_t format, stride;
+  static uint64_t align16(uint64_t n) { return (n + 15u) & ~(uint64_t)15u; }
+  uint64_t triangle_bytes() const { return format == kMeshIndexTile16 ? 6u : 12u; }
+  // where the tile table and the triangles begin in a payload of nv vertices and `rows` table rows (the uint32 format has no table: rows is not read)
+  uint64_t table_offset(uint64_t nv) const { return format == kMeshIndexTile16 ? align16(nv * stride) : nv * stride; }
+  uint64_t triangle_offset(uint64_t nv, uint64_t rows) const { return table_offset(nv) + (format == kMeshIndexTile16 ? rows * kMeshTileRowBytes : 0u); }
+  // the bytes of a frame that are copied: exactly its counts', never a capacity's.  A frame without a vertex has no triangle and no row: nothing.
+  uint64_t payload_bytes(uint64_t nv, uint64_t nt, uint64_t rows) const { return nv ? triangle_offset(nv, rows) + nt * triangle_bytes() : 0u; }
+  uint64_t payload_capacity(uint64_t max_vertices, uint64_t max_triangles, uint64_t max_tiles) const { return triangle_offset(max_vertices, max_tiles) + max_triangles * triangle_bytes(); }
+  uint64_t slot_bytes(uint64_t max_vertices, uint64_t max_triangles, uint64_t max_tiles) const { return kMeshHeaderBytes + payload_capacity(max_vertices, max_triangles, max_tiles); }
+  // the 4 GiB bound of a configuration: on the payload in the uint32 format (as it always was), on the whole slot, header included, in the tile-local one
+  // (every capacity is below 2^32 and every factor at most 16: no sum here comes near 2^64)
+  bool fits(uint64_t max_vertices, uint64_t max_triangles, uint64_t max_tiles) const {
+    return (format == kMeshIndexTile16 ? slot_bytes(max_vertices, max_triangles, max_tiles) : payload_capacity(max_vertices, max_triangles, max_tiles)) <= kMeshSlotLimit;
+  }
+};
+
 // Staging of a call's synchronous form (host arrays in and out): one capacity, in elements of the call (rays, points), for the input and result buffers,
 // one for the buffer only some calls ask for (a cast's surface records, a tap call's sensor records: allocated by the first call that does); grown to the
 // next power of two at or above the need (at least 1024 elements), never shrunk.

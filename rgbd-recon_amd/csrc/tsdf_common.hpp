@@ -397,6 +397,14 @@ void launch_mesh_stream_header(hipStream_t st, const MeshScratch& S, MeshStreamH
 // flags: TSDF_MESH_NORMALS | TSDF_MESH_COLOURS; payload: packed vertices (8 bytes each, 16 with a flag), then the triangles
 void launch_mesh_stream_emit(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S, uint32_t flags,
                              const MeshStreamHeader* H, uint32_t* records, void* payload);
+// The tile-local triangle format (TSDF_MESH_INDEX_TILE16; the header's "mesh streaming: compact triangles"): a table row per lattice tile with a vertex,
+// three 16-bit corner codes per triangle; three launches (packed vertices, table, triangles).  raw_table == nullptr: the payload is vertices, padding to
+// 16, needed_tiles rows, the 6-byte triangles.
+// raw_table != nullptr (the filter's raw frame): the payload is the uint32 frame launch_mesh_stream_emit writes, and the rows go to raw_table.
+struct MeshTileRow { uint32_t tile, first_vertex, first_triangle, n_triangles; };
+static_assert(sizeof(MeshTileRow) == 16, "tsdf_mesh_tile_row");
+void launch_mesh_stream_emit_compact(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S, uint32_t flags,
+                                     const MeshStreamHeader* H, uint32_t* records, void* payload, MeshTileRow* raw_table);
 // the streamed filter (k_mesh_stream_filter.hip; tsdf_mesh_stream_config_filter with min_triangles >= 1): the emit writes the unfiltered frame into `raw`
 // (a header, the capacity-sized payload behind it: device only, one per configuration), the filter's launches move what stays into a slot's payload and
 // write the slot's header and record.  Every launch is sized by the capacities and reads the frame's counts from the raw header.
@@ -408,11 +416,17 @@ struct MeshStreamFilter {
   uint8_t* keep;                    // max_vertices bytes rounded up to 4
   unsigned long long* vertex_sums;  // mesh_stream_filter_scan_words(max_vertices): block prefixes of the kept vertices, then their total
   unsigned long long* triangle_sums;   // ... (max_triangles)
-  uint32_t* words;                  // {components, components kept}
+  uint32_t* words;                  // {components, components kept, table rows kept (tile-local format)}
   uint32_t max_vertices, max_triangles, min_triangles, stride;
+  // the tile-local format only (null / 0 otherwise): the raw frame's tile table (max_tiles rows, device only), per four triangles the kept triangles
+  // before them inside their scan block, and the level's lattice tiles per axis
+  MeshTileRow* raw_table;
+  uint16_t* tri_local;              // (max_triangles + 3) / 4 words
+  int ntx, nty;
 };
 // what travels to the host in front of a filtered slot's header: out[4] of tsdf_mesh_stream_frame_filter
-struct MeshStreamFilterRecord { unsigned long long components, kept, vertices_removed, triangles_removed, reserved[4]; };
+// (table_rows: the filtered frame's tile-table rows in the tile-local format, 0 otherwise)
+struct MeshStreamFilterRecord { unsigned long long components, kept, vertices_removed, triangles_removed, table_rows, reserved[3]; };
 static_assert(sizeof(MeshStreamFilterRecord) == 64, "record and header travel as one 128-byte copy; the payload stays 64 bytes behind the header");
 size_t mesh_stream_filter_scan_words(uint32_t capacity);
 void launch_mesh_stream_filter(hipStream_t st, const MeshStreamFilter& F, void* payload);   // everything up to the scatter

@@ -17,6 +17,9 @@
 // must equal those of extractMesh on the same volume (zero for this scene).
 // Option --mesh-level N (0, 1, 2), applied to --mesh and --mesh-stream: the mesh at that level of detail (the lattice of every 2^N-th voxel) through the
 // adapter's overloads with a level; the streamed frames' counts must equal those of the extract at the same level, and the ring must report the level.
+// Option --mesh-stream-compact (implies --mesh-stream): the ring streams 6-byte tile-local triangles (TSDF_MESH_INDEX_TILE16); every frame's uint32
+// pointer must be null, its codes decoded on the host (decodeMeshTriangles) must equal downloadMesh's triangles of the same extract, and the payload
+// bytes must be the compact sizes.
 //   g++ -std=c++17 frame_harness.cpp -o frame_harness -L.. -lrgbd_recon_hip -Wl,-rpath,'$ORIGIN/..'
 #include <cmath>
 #include <cstdio>
@@ -35,6 +38,7 @@ int main(int argc, char** argv) {
   bool mesh_stream = false;
   int mesh_level = -1;                                                    // -1: not given (the entries without a level)
   long mesh_stream_min_triangles = -1;                                    // -1: not given (the ring without a filter)
+  bool mesh_stream_compact = false;
   for (int a = 1; a < argc; ++a) {
     if (std::strcmp(argv[a], "--draw-bricks") == 0) draw_bricks = true;
     else if (std::strcmp(argv[a], "--sensor-view") == 0 && a + 2 < argc) { view_type = std::atoi(argv[a + 1]); view_width = (float)std::atof(argv[a + 2]); a += 2; }
@@ -47,9 +51,10 @@ int main(int argc, char** argv) {
     else if (std::strcmp(argv[a], "--mesh-stream-min-triangles") == 0 && a + 1 < argc && argv[a + 1][0] >= '0' && argv[a + 1][0] <= '9') {
       mesh_stream_min_triangles = std::atol(argv[a + 1]); mesh_stream = true; a += 1;
     }
+    else if (std::strcmp(argv[a], "--mesh-stream-compact") == 0) { mesh_stream_compact = true; mesh_stream = true; }
     else {
       std::fprintf(stderr, "usage: frame_harness [--draw-bricks] [--sensor-view TYPE WIDTH] [--present rgba8|dxt1] [--mesh FILE.ply] [--mesh-stream] [--mesh-level 0|1|2]"
-                           " [--mesh-stream-min-triangles N]\n");
+                           " [--mesh-stream-min-triangles N] [--mesh-stream-compact]\n");
       return 1;
     }
   }
@@ -162,11 +167,17 @@ int main(int argc, char** argv) {
         components = recon.meshComponents();
         n = recon.filterMeshComponents((std::uint32_t)mesh_stream_min_triangles);
       }
-      if (filtered) recon.configureMeshStream(true, true, (unsigned)(mesh_level < 0 ? 0 : mesh_level), (unsigned)mesh_stream_min_triangles, 4096, 8192, 64, 3);
+      kinect::ReconIntegrationHip::Mesh want;                                  // the triangles the decoded codes have to equal
+      if (mesh_stream_compact) recon.downloadMesh(want);
+      std::uint64_t want_bytes = 0;
+      if (mesh_stream_compact) recon.configureMeshStream(true, true, (unsigned)(mesh_level < 0 ? 0 : mesh_level), (unsigned)(filtered ? mesh_stream_min_triangles : 0),
+                                                         TSDF_MESH_INDEX_TILE16, 4096, 8192, 64, 3);
+      else if (filtered) recon.configureMeshStream(true, true, (unsigned)(mesh_level < 0 ? 0 : mesh_level), (unsigned)mesh_stream_min_triangles, 4096, 8192, 64, 3);
       else if (mesh_level < 0) recon.configureMeshStream(true, true, 4096, 8192, 64, 3);
       else recon.configureMeshStream(true, true, (unsigned)mesh_level, 4096, 8192, 64, 3);
       if (recon.meshStreamLevel() != (unsigned)(mesh_level < 0 ? 0 : mesh_level)) return 1;
       if (recon.meshStreamMinTriangles() != (unsigned)(filtered ? mesh_stream_min_triangles : 0)) return 1;
+      if (recon.meshStreamIndexFormat() != (mesh_stream_compact ? TSDF_MESH_INDEX_TILE16 : TSDF_MESH_INDEX_U32)) return 1;
       const int frames = 5, lag = 2;
       int got = 0, wrong = 0;
       auto take = [&](std::uint64_t want_tag) {
@@ -178,6 +189,11 @@ int main(int argc, char** argv) {
           const kinect::ReconIntegrationHip::MeshFrameFilter ff = recon.meshStreamFrameFilter();
           ok = ok && ff.components == components && ff.vertices_removed == whole.vertices - n.vertices && ff.triangles_removed == whole.triangles - n.triangles;
         }
+        if (mesh_stream_compact) {
+          const tsdf_mesh_compact c = recon.meshFrameCompact();
+          ok = ok && fr.triangles == nullptr && kinect::ReconIntegrationHip::decodeMeshTriangles(c, fr.n_triangles) == want.triangles;
+          want_bytes += fr.n_vertices ? (fr.n_vertices * 16 + 15) / 16 * 16 + c.n_tile_rows * 16 + fr.n_triangles * 6 : 0;
+        } else want_bytes += fr.n_vertices * 16 + fr.n_triangles * 12;
         recon.releaseMeshFrame();                                              // (before it is counted: a held frame would fail every later acquire too)
         ++(ok ? got : wrong);
       };
@@ -189,7 +205,7 @@ int main(int argc, char** argv) {
       for (int f = frames - lag; f < frames; ++f) take((std::uint64_t)(200 + f));
       const kinect::ReconIntegrationHip::MeshStreamStats st = recon.meshStreamStats();
       std::printf("%d mesh frames streamed, %d picked up in order, %d mismatches, %llu payload bytes\n", frames, got, wrong, (unsigned long long)st.payload_bytes);
-      if (got != frames || wrong != 0 || st.frames != (std::uint64_t)frames || st.payload_bytes != (std::uint64_t)frames * (n.vertices * 16 + n.triangles * 12)) return 1;
+      if (got != frames || wrong != 0 || st.frames != (std::uint64_t)frames || st.payload_bytes != want_bytes) return 1;
     }
     return band > 0 ? 0 : 1;
   } catch (std::exception const& e) {

@@ -317,6 +317,40 @@ class ReconIntegrationHip {
     check(tsdf_mesh_stream_frame_filter(m_ctx, s));
     return MeshFrameFilter{s[0], s[1], s[2], s[3]};
   }
+  // ... with 6-byte tile-local triangles (tsdf_mesh_stream_config_compact; index_format follows min_triangles as in the C entry, every argument given):
+  // TSDF_MESH_INDEX_TILE16 streams three 16-bit corner codes per triangle and a table row per lattice tile instead of uint32 indices; a frame's
+  // `triangles` is then null and meshFrameCompact() hands out the table and the codes of the frame HELD now (throws on a uint32 ring or without a
+  // frame).  decodeMeshTriangles is the header's decoding rule: it gives the uint32 array of the same frame, byte for byte.
+  auto configureMeshStream(bool normals, bool colours, unsigned level, unsigned min_triangles, unsigned index_format, unsigned max_vertices, unsigned max_triangles,
+                           unsigned max_surface_tiles, unsigned slots) -> void {
+    check(tsdf_mesh_stream_config_compact(m_ctx, (normals ? TSDF_MESH_NORMALS : 0u) | (colours ? TSDF_MESH_COLOURS : 0u), level, min_triangles, index_format, max_vertices,
+                                          max_triangles, max_surface_tiles, slots));
+  }
+  unsigned meshStreamIndexFormat() {
+    std::uint32_t format = 0;
+    check(tsdf_mesh_stream_index_format(m_ctx, &format));
+    return format;
+  }
+  tsdf_mesh_compact meshFrameCompact() {
+    tsdf_mesh_compact out{};
+    check(tsdf_mesh_stream_frame_compact(m_ctx, &out));
+    return out;
+  }
+  static std::vector<std::uint32_t> decodeMeshTriangles(const tsdf_mesh_compact& c, std::uint64_t n_triangles) {
+    std::vector<std::uint32_t> out(n_triangles * 3);
+    for (std::uint64_t r = 0; r < c.n_tile_rows; ++r) {
+      const tsdf_mesh_tile_row& row = c.table[r];
+      for (std::uint64_t t = row.first_triangle, end = t + row.n_triangles; t < end; ++t)
+        for (int k = 0; k < 3; ++k) {
+          const std::uint32_t code = c.triangles[t * 3 + k];
+          const std::uint32_t owner = row.tile + ((code >> 12) & 1u) + ((code >> 13) & 1u) * c.tiles[0] + ((code >> 14) & 1u) * c.tiles[0] * c.tiles[1];
+          std::uint64_t lo = r, hi = c.n_tile_rows;                      // the owner's row: rows ascend by tile, and owner >= row.tile
+          while (hi - lo > 1) { const std::uint64_t mid = (lo + hi) / 2; if (c.table[mid].tile <= owner) lo = mid; else hi = mid; }
+          out[t * 3 + k] = c.table[lo].first_vertex + (code & 0xfffu);
+        }
+    }
+    return out;
+  }
   // after drawF(): never blocks; false = every slot is queued or held (or there is no volume yet), nothing was queued
   bool streamMesh(std::uint64_t tag) {
     const int32_t rc = tsdf_mesh_stream(m_ctx, tag);

@@ -13,7 +13,11 @@ rates carry the level in their names.  The top-level entries stay those of the f
 --min-triangles N (default 0: no filter): the ring drops the components of fewer than N triangles on the device (tsdf_mesh_stream_config_filter).  The
 streamed stages then include "mesh_stream_filter" (everything between the emit and the final header), every variant reports the filtered counts, the
 four filter words and the payload bytes of the filtered and of the unfiltered frame, and the streamed loops are the filtered ring's.
---variants NAME[,NAME..] (positions, normals, colours, all_attributes; default all four): the attribute variants part 1 times."""
+--variants NAME[,NAME..] (positions, normals, colours, all_attributes; default all four): the attribute variants part 1 times.
+--compact: instead of parts 1 and 2, the uint32 ring against the ring of 6-byte tile-local triangles (tsdf_mesh_stream_config_compact) in this one
+process, per level and for positions / all attributes, the two formats alternating call by call: the stage timers, the payload bytes per frame (measured
+from tsdf_mesh_stream_stats, and what the format's arithmetic gives), the host time from tsdf_mesh_stream on an idle device to the frame complete on the
+host ("latency_ms"), the copy's share of it (latency - device stages) and the bandwidth that gives, and the frames per second of the streamed loop."""
 import sys, os, json, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch  # noqa: F401  (torch first: the library binds to the HIP runtime torch loaded)
@@ -53,6 +57,98 @@ for L in LEVELS:
     levels[L] = dict(vertices=nv, triangles=nt, tiles=st["tiles"], tiles_skipped=st["tiles_skipped"], tiles_with_surface=ns,
                      capacities=dict(max_vertices=nv + nv // 4, max_triangles=nt + nt // 4, max_surface_tiles=ns + ns // 4))
 rec = dict(shape="c2", res=list(hip.res), streams=4, level=LEVELS[0], min_triangles=MIN_TRIANGLES, **{k: v for k, v in levels[LEVELS[0]].items()})
+
+
+def compact_record():
+    """--compact: format 0 against format 1"""
+    out = dict(rec, tool="tools/mesh_stream_timing.py --compact", unit="ms (stages, latency), bytes, GB/s, frames/s", levels={})
+    for L in LEVELS:
+        out["levels"][str(L)] = dict(vertices=levels[L]["vertices"], triangles=levels[L]["triangles"], tiles_with_surface=levels[L]["tiles_with_surface"])
+        for label, kw in [v for v in VARIANTS if v[0] in ("positions", "all_attributes")]:
+            stride = 16 if (kw["normals"] or kw["colours"]) else 8
+            samples = {fmt: dict(latency=[], bytes=[], **{s: [] for s in STREAM_STAGES}) for fmt in (0, 1)}
+            info = {}
+            hip.enable_timers(True)
+            hip.set_timer_filter(list(STREAM_STAGES))
+            for k in range(2 + N):                                       # two warm calls, then N; the formats alternate: both see the same machine
+                for fmt in (0, 1):
+                    hip.mesh_stream_config(slots=3, level=L, min_triangles=MIN_TRIANGLES, index_format=fmt, **kw, **levels[L]["capacities"])
+                    hip.mesh_stream(0); hip.mesh_stream_take()           # (the configuration's first call allocates)
+                    for s in STREAM_STAGES:
+                        hip.timer_stats(s)
+                    hip.sync()
+                    before = hip.mesh_stream_stats()["payload_bytes"]
+                    t0 = time.perf_counter()
+                    hip.mesh_stream(1)
+                    got = hip.mesh_stream_acquire(wait=True)
+                    t1 = time.perf_counter()
+                    info[fmt] = dict(n_vertices=got[2]["n_vertices"], n_triangles=got[2]["n_triangles"], rows=len(got[2]["compact"]["table"]) if fmt else 0)
+                    assert got[2]["overflow"] == 0
+                    hip.mesh_stream_release()
+                    if k >= 2:
+                        samples[fmt]["latency"].append((t1 - t0) * 1e3)
+                        samples[fmt]["bytes"].append(hip.mesh_stream_stats()["payload_bytes"] - before)
+                        for s in STREAM_STAGES:
+                            cnt, total = hip.timer_stats(s)
+                            samples[fmt][s].append(total / cnt)
+            hip.enable_timers(False)
+            r = {}
+            for fmt in (0, 1):
+                S, I = samples[fmt], info[fmt]
+                t = {s + "_ms": float(np.mean(S[s])) for s in STREAM_STAGES}
+                device = sum(t.values())
+                nv, nt, rows = I["n_vertices"], I["n_triangles"], I["rows"]
+                expected = ((nv * stride + 15) // 16 * 16 + rows * 16 + nt * 6 if nv else 0) if fmt else nv * stride + nt * 12
+                assert set(S["bytes"]) == {expected}, (S["bytes"], expected)
+                lat = float(np.median(S["latency"]))
+                t.update(device_ms=device, latency_ms=lat, latency_ms_min=float(np.min(S["latency"])), latency_ms_max=float(np.max(S["latency"])),
+                         payload_bytes=expected, table_rows=rows, n_vertices=nv, n_triangles=nt,
+                         copy_ms=lat - device, copy_GB_per_s=expected / max(lat - device, 1e-6) / 1e6)
+                r["format%d" % fmt] = t
+            a, b = r["format0"], r["format1"]
+            saved = a["payload_bytes"] - b["payload_bytes"]
+            r["bytes_saved"] = saved
+            r["bytes_saved_fraction"] = saved / max(a["payload_bytes"], 1)
+            r["emit_and_filter_extra_ms"] = (b["mesh_stream_emit_ms"] + b.get("mesh_stream_filter_ms", 0.0)) - (a["mesh_stream_emit_ms"] + a.get("mesh_stream_filter_ms", 0.0))
+            r["saved_bytes_copy_ms_at_format0_bandwidth"] = saved / max(a["copy_GB_per_s"], 1e-9) / 1e6
+            r["latency_saved_ms"] = a["latency_ms"] - b["latency_ms"]
+            out["levels"][str(L)][label] = r
+    def streamed(f):
+        hip.mesh_stream(f)
+        if hip.mesh_stream_stats()["frames"] - streamed.taken > 2:
+            hip.mesh_stream_take(); streamed.taken += 1
+    def drain():
+        while hip.mesh_stream_stats()["frames"] > streamed.taken:
+            hip.mesh_stream_take(); streamed.taken += 1
+    def loop(n):
+        for f in range(10):
+            hip.frame_dev(mv, pr, ptrs); streamed(f)
+        drain(); hip.sync()
+        t0 = time.perf_counter()
+        for f in range(n):
+            hip.frame_dev(mv, pr, ptrs); streamed(f)
+        drain(); hip.sync()
+        return n / (time.perf_counter() - t0)
+    fps = {}
+    for rep in range(0 if STAGES_ONLY else 3):
+        for L in LEVELS:
+            for label, kw in [v for v in VARIANTS if v[0] in ("positions", "all_attributes")]:
+                for fmt in (0, 1):
+                    hip.mesh_stream_config(slots=3, level=L, min_triangles=MIN_TRIANGLES, index_format=fmt, **kw, **levels[L]["capacities"])
+                    streamed.taken = 0
+                    fps.setdefault("level%d_%s_format%d" % (L, label, fmt), []).append(loop(FRAMES))
+    out["frames_per_s"] = {k: dict(runs=[round(x, 1) for x in v], median=round(float(np.median(v)), 1)) for k, v in fps.items()}
+    return out
+
+
+if "--compact" in ARGS:
+    rec = compact_record()
+    print(json.dumps(rec), flush=True)
+    if OUT:
+        with open(OUT[0], "w") as f:
+            json.dump(rec, f, indent=1)
+    hip.close()
+    sys.exit(0)
 
 # 1. device time per stage
 hip.enable_timers(True)
