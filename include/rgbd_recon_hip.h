@@ -999,6 +999,54 @@ int32_t tsdf_mesh_stream_config_compact(tsdf_ctx* ctx, uint32_t flags, uint32_t 
 int32_t tsdf_mesh_stream_index_format(tsdf_ctx* ctx, uint32_t* index_format);
 int32_t tsdf_mesh_stream_frame_compact(tsdf_ctx* ctx, tsdf_mesh_compact* out);
 
+/* ---- mesh streaming: slab parts ----------------------------------------------------------------------------
+ * Where the volume exists only as Z-slabs, every slab context streams ITS PART of the compact frame above, every frame, through a ring of its own; the
+ * receiver joins the parts by concatenation and two running sums.  A part is complete without a number from another slab: no exchange, no link step, no
+ * host wait.  Why that is possible: a TSDF_MESH_INDEX_TILE16 corner code is not global -- it is the offset inside the owner tile | (dx, dy, dz) << 12.  For
+ * a corner in the slab above (dz = 1, lattice plane 0 of the seam layer) the slab computes that offset itself from its halo, exactly as
+ * tsdf_mesh_slab_extract computes its seam records ("mesh extraction on Z-slab contexts": plane 0 comes first in a tile, so its offsets depend on lattice
+ * planes 0 and 1 alone); the owner tile's first_vertex lives in the owner's table row, which the slab above writes.  No counterpart in the reference.
+ * tests/mesh_part_reference.py restates parts and join in numpy on top of the slab, packing and compact references; device and numpy agree byte for byte.
+ *
+ * tsdf_mesh_stream_config_part selects a ring whose frames are this context's part.  The index format is always TSDF_MESH_INDEX_TILE16; there is no filter
+ *   (components cross slabs).  The checks and error codes are tsdf_mesh_stream_config_lod's, plus the alignment rule of tsdf_mesh_slab_extract, applied
+ *   at config time: slab_z0 must be a multiple of 8 << level, slab_z1 too unless it is the volume's top; TSDF_ERR_INVALID_ARGUMENT otherwise.  A
+ *   whole-volume context is the one-slab case: every frame of its part ring equals the frame of its compact ring byte for byte.
+ *   tsdf_mesh_stream / _acquire / _release / _stats / _frame_compact / _level / _index_format serve the part ring unchanged; tsdf_mesh_frame keeps its
+ *   112 bytes.  A Z-slab context configured through any of the four other config entries keeps answering TSDF_ERR_STATE from tsdf_mesh_stream, and a
+ *   context that never calls this entry runs, launch for launch, what it ran before.
+ * The part of a context that owns lattice tile layers [L0, L1) (as "mesh extraction on Z-slab contexts" defines them):
+ *   vertices:   those owned by lattice points of these layers, in the order of the whole mesh, packed by the rule of "mesh streaming" (8 or 16 bytes).
+ *               Normals and colours as on a slab extract.  Halo: the precondition and the argument of "mesh extraction on Z-slab contexts" hold as they
+ *               stand there -- the halo is current, exchanged or recomputed, exactly as for a raymarch on the slab, and it covers every voxel a part reads.
+ *               A slab that stores no layer above a face below the volume's top is refused by tsdf_mesh_stream with TSDF_ERR_STATE.
+ *   table rows: one per OWNED lattice tile that owns a vertex, ascending.  `tile` is the linear id in the WHOLE level's lattice-tile grid
+ *               (tsdf_mesh_compact.tiles); first_vertex and first_triangle are PART-LOCAL.
+ *   triangles:  those of the cells whose origin lies in the owned layers: three corner codes each, exactly the codes of the whole-volume compact frame.
+ *   Payload layout as in "compact triangles": vertices, zero padding to 16, rows, codes.
+ * Capacities and overflow are per part, with the three bits of "mesh streaming".  needed_tiles and the rows count OWNED surface tiles only.  The seam
+ *   layer's records need slots too: the ring allocates max_surface_tiles + ntx * nty record slots (the seam layer is one tile layer; none at the top), so
+ *   a seam tile never causes an overflow and there is no fourth capacity.  needed_vertices, needed_tiles and the counts exclude the seam tiles; the
+ *   subtraction happens on the device.
+ * Join rule.  For parts k = 0 .. K-1 of contiguous slabs in slab order, all with overflow == 0:
+ *     vertices:  concatenate the packed vertices;
+ *     rows:      concatenate the rows with first_vertex += sum of n_vertices_j over j < k and first_triangle += sum of n_triangles_j over j < k;
+ *     codes:     concatenate the codes unchanged.
+ *   The result is, byte for byte, the frame a whole-volume context streams with tsdf_mesh_stream_config_compact(..., TSDF_MESH_INDEX_TILE16, ...).
+ *   Only the top part decodes alone: below the top, codes with dz = 1 name rows of the next part, so the unit of decoding is the joined frame.  If any
+ *   part overflowed, the frame is dropped whole.
+ * tsdf_mesh_stream_frame_part fills *out for the frame currently HELD: layers = {L0, L1}, the level, top = 1 when the slab reaches the volume's top, and
+ *   seam_tiles = the seam tiles with surface in this frame (it travels in a 64-byte record in front of the header, in the header's copy, as the filter's
+ *   record does).  TSDF_ERR_STATE when no frame is held or the ring is not a part ring; TSDF_ERR_INVALID_ARGUMENT for a NULL out.
+ * Protocol: that of the ring -- the same stream dependencies, events, pump and payload size rule; after the first call nothing is allocated and no call
+ *   waits for the GPU.  Timers as "mesh streaming".
+ * Out of scope: the filter, components and texture taps on parts; a uint32 part format; carrying parts over the native RCCL exchange; gaps between slabs;
+ *   any change to the vertex packing or to the existing entries' behaviour. */
+typedef struct tsdf_mesh_part { uint32_t layers[2]; uint32_t level; uint32_t top; uint32_t seam_tiles; uint32_t reserved[3]; } tsdf_mesh_part; /* 32 bytes */
+int32_t tsdf_mesh_stream_config_part(tsdf_ctx* ctx, uint32_t flags, uint32_t level, uint32_t max_vertices, uint32_t max_triangles, uint32_t max_surface_tiles,
+                                     uint32_t slots);
+int32_t tsdf_mesh_stream_frame_part(tsdf_ctx* ctx, tsdf_mesh_part* out);   /* of the frame currently HELD */
+
 /* ---- frame read-out: the swap ------------------------------------------------------------------------
  * The client ends a frame with glfwSwapBuffers (source/kinect_client.cpp:533): an RGBA8 window goes to a display (GLFW's default framebuffer has 8
  * bits per channel and the client sets no window hint that changes it, :942-951).  This device has no display; tsdf_present is the swap for a host

@@ -213,6 +213,40 @@ def unpack_mesh_triangles(table, codes, tiles):
     return (table["first_vertex"].astype(np.int64)[owner_row] + (codes & 0xfff)).astype(np.uint32)
 
 
+class MeshPart(C.Structure):
+    """tsdf_mesh_part of rgbd_recon_hip.h"""
+    _fields_ = [("layers", C.c_uint32 * 2), ("level", C.c_uint32), ("top", C.c_uint32), ("seam_tiles", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+def join_mesh_parts(parts):
+    """the header's join rule ("mesh streaming: slab parts"): parts = the (vertices, codes, info) frames of part rings (mesh_stream_config(part=True)) of
+    contiguous slabs, in slab order -> (vertices, codes, info) of the whole-volume compact frame: the vertices and codes concatenated, the rows
+    concatenated with the vertices and triangles of the parts below added to first_vertex and first_triangle.  ValueError when a part overflowed (the
+    frame is dropped whole), when the parts are not contiguous or differ in level or vertex stride."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("no part")
+    first = parts[0][2]
+    rows, nv, nt = [], 0, 0
+    for k, (vertices, codes, info) in enumerate(parts):
+        if info["overflow"]:
+            raise ValueError(f"part {k} overflowed (bits {info['overflow']}): the frame is dropped whole")
+        if info["vertex_stride"] != first["vertex_stride"] or info["compact"]["level"] != first["compact"]["level"] or info["compact"]["tiles"] != first["compact"]["tiles"]:
+            raise ValueError(f"part {k} has another vertex stride, level or tile grid")
+        if k and info["part"]["layers"][0] != parts[k - 1][2]["part"]["layers"][1]:
+            raise ValueError(f"part {k} does not follow part {k - 1}: layers {parts[k - 1][2]['part']['layers']} then {info['part']['layers']}")
+        t = np.array(info["compact"]["table"], MESH_TILE_ROW_DTYPE)
+        t["first_vertex"] += np.uint32(nv)
+        t["first_triangle"] += np.uint32(nt)
+        rows.append(t)
+        nv += len(vertices)
+        nt += len(codes)
+    info = dict(first, n_vertices=nv, n_triangles=nt, needed_vertices=nv, needed_triangles=nt, needed_tiles=sum(len(r) for r in rows), overflow=0,
+                compact=dict(first["compact"], table=np.concatenate(rows)),
+                part=dict(layers=(first["part"]["layers"][0], parts[-1][2]["part"]["layers"][1]), level=first["part"]["level"], top=parts[-1][2]["part"]["top"], seam_tiles=parts[-1][2]["part"]["seam_tiles"]))
+    return np.concatenate([p[0] for p in parts]), np.concatenate([np.asarray(p[1], np.uint16).reshape(-1, 3) for p in parts]), info
+
+
 def unpack_mesh_vertices(vertices):
     """a streamed frame's vertex array -> dict(position uint16 [V][3], and for the 16-byte stride normal int16 [V][2], colour uint8 [V][4])"""
     if vertices.dtype == np.uint16:
@@ -896,15 +930,21 @@ class ReconIntegrationHip:
 
     # ------------------------------------------------------------------ mesh streaming (no counterpart in the reference)
     def mesh_stream_config(self, normals=False, colours=False, max_vertices=1 << 20, max_triangles=1 << 21, max_surface_tiles=1 << 14, slots=3, level=0,
-                           min_triangles=0, index_format=0):
+                           min_triangles=0, index_format=0, part=False):
         """flags, the three capacities and the slot count of the mesh ring (tsdf_mesh_stream_config); the first mesh_stream after it allocates.
         level 1 / 2 (tsdf_mesh_stream_config_lod): every frame is that level's mesh, max_surface_tiles counts its 8^3 lattice tiles.
         min_triangles >= 1 (tsdf_mesh_stream_config_filter): every frame leaves the device without its components of fewer triangles; n_* in a frame's
         info are the filtered counts, needed_* and the capacities those of the unfiltered mesh.
-        index_format MESH_INDEX_TILE16 (tsdf_mesh_stream_config_compact): 6-byte tile-local triangles and a tile table instead of uint32 indices."""
+        index_format MESH_INDEX_TILE16 (tsdf_mesh_stream_config_compact): 6-byte tile-local triangles and a tile table instead of uint32 indices.
+        part=True (tsdf_mesh_stream_config_part): every frame is this context's PART of the tile-local frame -- the one ring a Z-slab context streams
+        through; the capacities are per part, join_mesh_parts joins the slabs' frames.  It has no filter and no uint32 form (ValueError)."""
         flags = (MESH_NORMALS if normals else 0) | (MESH_COLOURS if colours else 0)
         caps = (C.c_uint32(int(max_vertices)), C.c_uint32(int(max_triangles)), C.c_uint32(int(max_surface_tiles)), C.c_uint32(int(slots)))
-        if index_format:
+        if part:
+            if min_triangles or index_format not in (0, MESH_INDEX_TILE16):
+                raise ValueError("a part ring has no filter and streams tile-local triangles only")
+            self._ck(self._L.tsdf_mesh_stream_config_part(self._c, C.c_uint32(flags), C.c_uint32(int(level)), *caps))
+        elif index_format:
             self._ck(self._L.tsdf_mesh_stream_config_compact(self._c, C.c_uint32(flags), C.c_uint32(int(level)), C.c_uint32(int(min_triangles)),
                                                              C.c_uint32(int(index_format)), *caps))
         elif min_triangles:
@@ -914,6 +954,14 @@ class ReconIntegrationHip:
         else:
             self._ck(self._L.tsdf_mesh_stream_config(self._c, C.c_uint32(flags), *caps))
         self._mesh_stream_filtered = bool(min_triangles)                 # (behind the checks: a refused config leaves the ring as it was)
+        self._mesh_stream_part = bool(part)
+
+    def mesh_stream_frame_part(self):
+        """dict: layers (L0, L1), level, top, seam_tiles of the frame held now (tsdf_mesh_stream_frame_part); TsdfError, code -4, when no frame is held
+        or the ring does not stream parts"""
+        p = MeshPart()
+        self._ck(self._L.tsdf_mesh_stream_frame_part(self._c, C.byref(p)))
+        return dict(layers=(int(p.layers[0]), int(p.layers[1])), level=int(p.level), top=bool(p.top), seam_tiles=int(p.seam_tiles))
 
     def mesh_stream_index_format(self):
         """the index format of the last mesh_stream_config (tsdf_mesh_stream_index_format)"""
@@ -984,7 +1032,7 @@ class ReconIntegrationHip:
 
     def mesh_stream_take(self, wait=True):
         """acquire, COPY, release: (vertices, triangles, info) as numpy arrays of the caller's own, or None (wait=False, frame not complete).
-        With a filter configured info["filter"] is the frame's mesh_stream_frame_filter()."""
+        With a filter configured info["filter"] is the frame's mesh_stream_frame_filter(), on a part ring info["part"] its mesh_stream_frame_part()."""
         got = self.mesh_stream_acquire(wait)
         if got is None:
             return None
@@ -993,6 +1041,8 @@ class ReconIntegrationHip:
             out[2]["compact"]["table"] = out[2]["compact"]["table"].copy()
         if getattr(self, "_mesh_stream_filtered", False):
             out[2]["filter"] = self.mesh_stream_frame_filter()
+        if getattr(self, "_mesh_stream_part", False):
+            out[2]["part"] = self.mesh_stream_frame_part()
         self.mesh_stream_release()
         return out
 

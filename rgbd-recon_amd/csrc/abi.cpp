@@ -2866,9 +2866,9 @@ int32_t tsdf_mesh_stream_config_filter(tsdf_ctx* c, uint32_t flags, uint32_t lev
                                        uint32_t max_surface_tiles, uint32_t slots) {
   return tsdf_mesh_stream_config_compact(c, flags, level, min_triangles, TSDF_MESH_INDEX_U32, max_vertices, max_triangles, max_surface_tiles, slots);
 }
-int32_t tsdf_mesh_stream_config_compact(tsdf_ctx* c, uint32_t flags, uint32_t level, uint32_t min_triangles, uint32_t index_format, uint32_t max_vertices,
-                                        uint32_t max_triangles, uint32_t max_surface_tiles, uint32_t slots) {
-  CHECK_CTX(c);
+// every config entry ends here.  part: tsdf_mesh_stream_config_part (the frames are this context's part of the tile-local frame)
+static int32_t mesh_stream_configure(tsdf_ctx* c, uint32_t flags, uint32_t level, uint32_t min_triangles, uint32_t index_format, uint32_t max_vertices,
+                                     uint32_t max_triangles, uint32_t max_surface_tiles, uint32_t slots, bool part) {
   tsdf_ctx::MeshStream& R = c->mstream;
   if (index_format > TSDF_MESH_INDEX_TILE16) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "mesh index format %u (0: uint32 indices, 1: tile-local 16-bit codes)", index_format);
   if (level > (uint32_t)kMeshMaxLevel) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "mesh level %u (0 .. %d: every voxel, every 2nd, every 4th)", level, kMeshMaxLevel);
@@ -2876,15 +2876,29 @@ int32_t tsdf_mesh_stream_config_compact(tsdf_ctx* c, uint32_t flags, uint32_t le
     FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "mesh stream flags %u / capacities %u vertices, %u triangles, %u tiles / slots %u (flags 1 normals, 2 colours; capacities > 0; 2..%u slots)",
          flags, max_vertices, max_triangles, max_surface_tiles, slots, kMaxResultSlots);
   if (!MeshFrameLayout{index_format, flags ? 16u : 8u}.fits(max_vertices, max_triangles, max_surface_tiles)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "a mesh stream slot of more than 4 GiB");
+  if (part) {                                                            // the alignment rule of tsdf_mesh_slab_extract, here at config time
+    const Volume& V = c->vol;
+    if (!MeshPartLayers::of(V.own_tz0, V.own_tz1, (c->res[2] + 7) / 8, (int)level, mesh_lattice(V.res, (int)level).ntz).aligned)
+      FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "slab planes [%d, %d) do not lie on level %u's lattice tiles (%d planes each)", V.own_tz0 * 8, V.own_tz1 * 8, level, 8 << level);
+  }
   if (!R.ring.idle()) FAIL(c, TSDF_ERR_STATE, "%u streamed mesh frame(s) are queued or held: acquire and release them first", R.ring.count);
   HIP_TRY(c, hipSetDevice(c->device));
   // The ring is idle for the copies only (each was waited for before its frame was released): a frame that overflowed or had no payload was handed out
   // behind its header copy alone, and its emit launches, which read the slot's device header and the scratch, may still be queued on the context's stream.
   if (R.allocated) HIP_TRY(c, hipStreamSynchronize(c->stream));
   release_mesh_stream(c);
-  R.flags = flags; R.level = level; R.max_vertices = max_vertices; R.max_triangles = max_triangles; R.max_tiles = max_surface_tiles; R.min_triangles = min_triangles; R.index_format = index_format; R.ring.configure(slots); R.configured = true;
+  R.flags = flags; R.level = level; R.max_vertices = max_vertices; R.max_triangles = max_triangles; R.max_tiles = max_surface_tiles; R.min_triangles = min_triangles; R.index_format = index_format; R.part = part; R.ring.configure(slots); R.configured = true;
   R.frames = R.overflowed = R.bytes_copied = 0;
   return TSDF_OK;
+}
+int32_t tsdf_mesh_stream_config_compact(tsdf_ctx* c, uint32_t flags, uint32_t level, uint32_t min_triangles, uint32_t index_format, uint32_t max_vertices,
+                                        uint32_t max_triangles, uint32_t max_surface_tiles, uint32_t slots) {
+  CHECK_CTX(c);
+  return mesh_stream_configure(c, flags, level, min_triangles, index_format, max_vertices, max_triangles, max_surface_tiles, slots, false);
+}
+int32_t tsdf_mesh_stream_config_part(tsdf_ctx* c, uint32_t flags, uint32_t level, uint32_t max_vertices, uint32_t max_triangles, uint32_t max_surface_tiles, uint32_t slots) {
+  CHECK_CTX(c);
+  return mesh_stream_configure(c, flags, level, 0u, TSDF_MESH_INDEX_TILE16, max_vertices, max_triangles, max_surface_tiles, slots, true);
 }
 int32_t tsdf_mesh_stream_level(tsdf_ctx* c, uint32_t* level) {
   CHECK_CTX(c);
@@ -2935,8 +2949,18 @@ static bool mesh_stream_filter_allocate(tsdf_ctx::MeshStream& R, const int c_res
 static int32_t mesh_stream_allocate(tsdf_ctx* c) {
   tsdf_ctx::MeshStream& R = c->mstream;
   const MeshLattice L = mesh_lattice(c->vol.res, (int)R.level);
-  const size_t n_tiles = (size_t)L.ntx * L.nty * L.ntz, lead = R.min_triangles ? sizeof(MeshStreamFilterRecord) : 0,
-               slot_bytes = lead + sizeof(MeshStreamHeader) + mesh_stream_payload_capacity(R), record_bytes = (size_t)R.max_tiles * 512 * sizeof(uint32_t);
+  size_t n_tiles = (size_t)L.ntx * L.nty * L.ntz, record_slots = R.max_tiles;
+  if (R.part) {                                                          // the scratch over owned + seam tiles, records for the seam tiles beyond the capacity
+    const Volume& V = c->vol;
+    const MeshPartLayers P = MeshPartLayers::of(V.own_tz0, V.own_tz1, (c->res[2] + 7) / 8, (int)R.level, L.ntz);
+    const size_t per_layer = (size_t)L.ntx * L.nty;
+    if (!P.aligned) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "slab planes [%d, %d) do not lie on level %u's lattice tiles (%d planes each)", V.own_tz0 * 8, V.own_tz1 * 8, R.level, 8 << R.level);
+    R.slab = MeshSlab{P.layer0, (int)((size_t)(P.layer1 - P.layer0) * per_layer), (int)P.seam_tiles(per_layer)};
+    n_tiles = (size_t)R.slab.n_own + (size_t)R.slab.n_seam;
+    record_slots = (size_t)P.record_slots(R.max_tiles, per_layer);
+  }
+  const size_t lead = R.min_triangles ? sizeof(MeshStreamFilterRecord) : R.part ? sizeof(MeshStreamPartRecord) : 0,
+               slot_bytes = lead + sizeof(MeshStreamHeader) + mesh_stream_payload_capacity(R), record_bytes = record_slots * 512 * sizeof(uint32_t);
   uint64_t bytes = (uint64_t)R.ring.slots * slot_bytes + record_bytes;
   bool ok = mesh_scratch_allocate(R.scratch, (int)n_tiles, (int)R.level, &bytes) == hipSuccess && hipMalloc((void**)&R.records, record_bytes) == hipSuccess;
   if (ok && R.min_triangles) ok = mesh_stream_filter_allocate(R, c->vol.res, &bytes);
@@ -3010,7 +3034,13 @@ int32_t tsdf_mesh_stream(tsdf_ctx* c, uint64_t tag) {
   tsdf_ctx::MeshStream& R = c->mstream;
   if (!R.configured) FAIL(c, TSDF_ERR_STATE, "tsdf_mesh_stream before tsdf_mesh_stream_config");
   int32_t rc;
-  if ((rc = readable_volume_check(c, "tsdf_mesh_stream on a Z-slab context: slab parts (tsdf_mesh_slab_extract) are not streamed", (R.flags & TSDF_MESH_COLOURS) != 0))) return rc;
+  if (!R.part) {
+    if ((rc = readable_volume_check(c, "tsdf_mesh_stream on a Z-slab context: slab parts (tsdf_mesh_slab_extract) are not streamed", (R.flags & TSDF_MESH_COLOURS) != 0))) return rc;
+  } else {                                                               // a part ring: any context; the halo is the caller's to keep current, that it exists is checked
+    if (!c->have_volume) FAIL(c, TSDF_ERR_STATE, "no volume yet (tsdf_integrate or tsdf_upload_volume)");
+    if ((R.flags & TSDF_MESH_COLOURS) && (rc = require_inputs(c, false, true))) return rc;
+    if (c->vol.own_tz1 != (c->res[2] + 7) / 8 && c->vol.tz1 - c->vol.own_tz1 < 1) FAIL(c, TSDF_ERR_STATE, "the slab stores no halo layer above its planes");
+  }
   if (R.ring.full()) FAIL(c, TSDF_ERR_STATE, "all %u mesh stream slots are queued or held (tsdf_mesh_stream_acquire / tsdf_mesh_stream_release)", R.ring.slots);
   HIP_TRY(c, hipSetDevice(c->device));
   if (!R.allocated && (rc = mesh_stream_allocate(c))) return rc;
@@ -3027,11 +3057,12 @@ int32_t tsdf_mesh_stream(tsdf_ctx* c, uint64_t tag) {
     HIP_TRY(c, join_integ(c));                                           // the volume tsdf_download_volume would return now
     if (R.flags & TSDF_MESH_COLOURS) HIP_TRY(c, join_pre(c));            // ... and the current frame slot's images
     timer_begin(c, "mesh_stream_count");
-    launch_mesh_count(c->stream, V, R.scratch);
+    if (R.part) launch_mesh_slab_count(c->stream, V, R.scratch, R.slab); else launch_mesh_count(c->stream, V, R.scratch);
     timer_end(c, "mesh_stream_count");
     timer_begin(c, "mesh_stream_scan");
     launch_mesh_scan(c->stream, R.scratch);
-    launch_mesh_stream_header(c->stream, R.scratch, H, R.max_vertices, R.max_triangles, R.max_tiles);
+    if (R.part) launch_mesh_part_header(c->stream, R.scratch, R.slab, (MeshStreamPartRecord*)(S.dev - S.lead), H, R.max_vertices, R.max_triangles, R.max_tiles);
+    else launch_mesh_stream_header(c->stream, R.scratch, H, R.max_vertices, R.max_triangles, R.max_tiles);
     timer_end(c, "mesh_stream_scan");
   } else HIP_TRY(c, hipMemsetAsync(S.dev - S.lead, 0, S.lead + sizeof(MeshStreamHeader), c->stream));
   HIP_TRY(c, hipGetLastError());
@@ -3042,7 +3073,8 @@ int32_t tsdf_mesh_stream(tsdf_ctx* c, uint64_t tag) {
   HIP_TRY(c, hipEventRecord(S.header_ready, c->copy_stream));
   if (cells) {
     timer_begin(c, "mesh_stream_emit");
-    if (R.index_format == kMeshIndexTile16) launch_mesh_stream_emit_compact(c->stream, V, c->luts, c->frame, mesh_geometry(c), R.scratch, R.flags, H, R.records, S.dev + sizeof(MeshStreamHeader), nullptr);
+    if (R.part) launch_mesh_part_emit(c->stream, V, c->luts, c->frame, mesh_geometry(c), R.scratch, R.slab, R.flags, H, R.records, S.dev + sizeof(MeshStreamHeader));
+    else if (R.index_format == kMeshIndexTile16) launch_mesh_stream_emit_compact(c->stream, V, c->luts, c->frame, mesh_geometry(c), R.scratch, R.flags, H, R.records, S.dev + sizeof(MeshStreamHeader), nullptr);
     else launch_mesh_stream_emit(c->stream, V, c->luts, c->frame, mesh_geometry(c), R.scratch, R.flags, H, R.records, S.dev + sizeof(MeshStreamHeader));
     timer_end(c, "mesh_stream_emit");
     HIP_TRY(c, hipGetLastError());
@@ -3120,6 +3152,19 @@ int32_t tsdf_mesh_stream_frame_compact(tsdf_ctx* c, tsdf_mesh_compact* out) {
   out->triangles = (const uint16_t*)(payload + layout.triangle_offset(H->n_vertices, S.table_rows));
   out->n_tile_rows = S.table_rows;
   out->tiles[0] = (uint32_t)L.ntx; out->tiles[1] = (uint32_t)L.nty; out->tiles[2] = (uint32_t)L.ntz; out->level = R.level;
+  return TSDF_OK;
+}
+int32_t tsdf_mesh_stream_frame_part(tsdf_ctx* c, tsdf_mesh_part* out) {
+  CHECK_CTX(c);
+  if (!out) return TSDF_ERR_INVALID_ARGUMENT;
+  const tsdf_ctx::MeshStream& R = c->mstream;
+  if (!R.configured || !R.part) FAIL(c, TSDF_ERR_STATE, "the mesh ring does not stream parts (tsdf_mesh_stream_config_part)");
+  if (!R.ring.held) FAIL(c, TSDF_ERR_STATE, "no streamed mesh frame is held (tsdf_mesh_stream_acquire)");
+  const tsdf_ctx::MeshStreamSlot& S = R.slot[R.ring.oldest()];
+  const MeshPartLayers P = MeshPartLayers::of(c->vol.own_tz0, c->vol.own_tz1, (S.res[2] + 7) / 8, (int)R.level, mesh_lattice(S.res, (int)R.level).ntz);
+  *out = tsdf_mesh_part{};
+  out->layers[0] = (uint32_t)P.layer0; out->layers[1] = (uint32_t)P.layer1; out->level = R.level; out->top = P.top ? 1u : 0u;
+  out->seam_tiles = (uint32_t)((const MeshStreamPartRecord*)(S.host - S.lead))->seam_tiles;
   return TSDF_OK;
 }
 int32_t tsdf_mesh_stream_stats(tsdf_ctx* c, uint64_t out[4]) {

@@ -165,6 +165,10 @@ struct tsdf_ctx {
     uint32_t min_triangles = 0;     // 0: no filter, the frame is emitted into its slot
     uint32_t index_format = 0;      // 0: uint32 triangles, 1: tile-local 6-byte triangles and a tile table
     MeshFrameLayout layout() const { return MeshFrameLayout{index_format, flags ? 16u : 8u}; }
+    // part (tsdf_mesh_stream_config_part): every frame is this context's PART of the tile-local frame -- the owned lattice tile layers `slab` names (set with
+    // the allocation), count and emit by k_mesh_slab.hip, the scratch over owned + seam tiles, max_tiles + slab.n_seam record slots, and a slot's buffers
+    // begin `lead` = 64 bytes in front with the frame's MeshStreamPartRecord.  The one mode a Z-slab context streams in.
+    bool part = false; MeshSlab slab{};
     MeshStreamFilter filter{};      // the raw buffer and the filter's scratch (null without a filter)
     bool configured = false, allocated = false;
     uint64_t frames = 0, overflowed = 0, bytes_copied = 0, device_bytes = 0;

@@ -78,7 +78,6 @@ __global__ __launch_bounds__(kMeshThreads) void k_mesh_count(Volume V, uint2* __
 
 // ---- 2. scan of the per-tile counts: block sums, scan of the block sums, add.  Four quantities: vertices, triangles, tiles with
 // surface, tiles skipped by class.  A block covers kScanPerBlock tiles, so its own sums fit 32 bits; everything across blocks is 64-bit.
-struct MeshSums { unsigned long long nv, nt, surface, skipped; };
 __device__ __forceinline__ void scan_load(const uint2* __restrict__ tile_cnt, const uint8_t* __restrict__ tile_skip, int n, uint2 c[kScanPerThread], uint32_t sk[kScanPerThread]) {
   const int first = ((int)blockIdx.x * kScanThreads + (int)threadIdx.x) * kScanPerThread;
 #pragma unroll
@@ -179,28 +178,10 @@ __global__ __launch_bounds__(kMeshThreads) void k_mesh_vertices(Volume V, Stream
   mesh_tile_vertices<kSparse, kLevel>(V, T, F, G, t, nv, s_f, s_edge, (size_t)tile_vbase[t.id], out_pos, out_nrm, out_col);
 }
 
-// ... and the streamed form (tsdf_mesh_stream): k_mesh_vertices' text (mesh_dev.hpp: mesh_tile_vertices) up to the vertex's unit-cube position u, word
-// for word (the extraction keeps its kernel untouched, so the two are written out twice), then the same vertices, quantised in registers and written with ONE 8- or 16-byte store each -- no fp32
-// position, normal or colour exists in memory.  H is the frame's header in device memory (k_mesh_stream_header): when a need exceeds its capacity
-// every workgroup of both emit kernels returns before it reads anything else, so nothing is ever written past a capacity.
-__device__ __forceinline__ bool mesh_stream_overflow(const MeshStreamHeader* __restrict__ H) {
-  return H->needed_vertices > H->max_vertices || H->needed_triangles > H->max_triangles || H->needed_tiles > H->max_tiles;
-}
-__device__ __forceinline__ uint32_t unorm16(float u) { return (uint32_t)__float2int_rn(fminf(fmaxf(u, 0.0f), 1.0f) * 65535.0f); }
-__device__ __forceinline__ uint32_t snorm16(float p) { return (uint32_t)__float2int_rn(fminf(fmaxf(p, -1.0f), 1.0f) * 32767.0f) & 0xffffu; }
-// tsdf_present's RGBA8 rule (k_present.hip: unorm8): the clamp maps NaN to 0
-__device__ __forceinline__ uint32_t mesh_unorm8(float v) { return (uint32_t)__float2int_rn(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f); }
-// octahedral code of a unit normal, two int16; a NaN component: (-32768, -32768)
-__device__ __forceinline__ uint32_t mesh_oct_normal(float3 n) {
-  if (n.x != n.x || n.y != n.y || n.z != n.z) return 0x80008000u;
-  const float s = (fabsf(n.x) + fabsf(n.y)) + fabsf(n.z);
-  float px = n.x / s, py = n.y / s;
-  if (n.z < 0.0f) {
-    const float fx = (1.0f - fabsf(py)) * (px >= 0.0f ? 1.0f : -1.0f), fy = (1.0f - fabsf(px)) * (py >= 0.0f ? 1.0f : -1.0f);
-    px = fx; py = fy;
-  }
-  return snorm16(px) | (snorm16(py) << 16);
-}
+// ... and the streamed form (tsdf_mesh_stream): the same records, then the tile's vertices quantised in registers and written with ONE 8- or 16-byte
+// store each (mesh_dev.hpp: mesh_tile_vertices_packed, shared with the slab parts' emit).  H is the frame's header in device memory
+// (k_mesh_stream_header): when a need exceeds its capacity every workgroup of both emit kernels returns before it reads anything else, so nothing is ever
+// written past a capacity.
 template <bool kSparse, uint32_t kFlags, int kLevel>
 __global__ __launch_bounds__(kMeshThreads, 4) void k_mesh_vertices_packed(Volume V, StreamTable T, FrameImages F, MeshGeometry G, const MeshStreamHeader* __restrict__ H,
                                                                           const uint2* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_vbase,
@@ -225,44 +206,7 @@ __global__ __launch_bounds__(kMeshThreads, 4) void k_mesh_vertices_packed(Volume
       if (p.mask & (1u << (d - 1))) s_edge[k++] = (uint16_t)((threadIdx.x << 3) | d);
   }
   __syncthreads();
-  const float ex = G.bbox_max[0] - G.bbox_min[0], ey = G.bbox_max[1] - G.bbox_min[1], ez = G.bbox_max[2] - G.bbox_min[2];
-  const float limit = V.limit, sd = limit * 0.5f;
-  for (uint32_t v = threadIdx.x; v < nv; v += kMeshThreads) {
-    const int e = s_edge[v], lane = e >> 3, d = e & 7;
-    const int lx = lane & 7, ly = (lane >> 3) & 7, lz = lane >> 6;
-    const int bx = d & 1, by = (d >> 1) & 1, bz = d >> 2;
-    float a = s_f[corner_index(lx, ly, lz)], b = s_f[corner_index(lx + bx, ly + by, lz + bz)];
-    float w;
-    int x, y, z;
-    if constexpr (kLevel == 0) {
-      w = a / (a - b);
-      x = t.tx * 8 + lx; y = t.ty * 8 + ly; z = t.tz * 8 + lz;
-    } else {                                                           // the voxel edge of the vertex: every level's vertex is a level-0 vertex
-      x = (t.tx * 8 + lx) << kLevel; y = (t.ty * 8 + ly) << kLevel; z = (t.tz * 8 + lz) << kLevel;
-      mesh_descend<kSparse, kLevel>(V, bx, by, bz, x, y, z, a, b);
-      w = a / (a - b);
-    }
-    const float upx = ((float)x + 0.5f) / (float)V.res[0], uqx = ((float)(x + bx) + 0.5f) / (float)V.res[0];
-    const float upy = ((float)y + 0.5f) / (float)V.res[1], uqy = ((float)(y + by) + 0.5f) / (float)V.res[1];
-    const float upz = ((float)z + 0.5f) / (float)V.res[2], uqz = ((float)(z + bz) + 0.5f) / (float)V.res[2];
-    const float3 u = make_float3(upx + w * (uqx - upx), upy + w * (uqy - upy), upz + w * (uqz - upz));
-    const size_t o = (size_t)tile_vbase[t.id] + v;                     // (< needed_vertices <= max_vertices)
-    const uint2 pos = make_uint2(unorm16(u.x) | (unorm16(u.y) << 16), unorm16(u.z));
-    if (kFlags == 0u) { ((uint2*)out)[o] = pos; continue; }
-    uint32_t nrm = 0u, col = 0u;
-    if (kFlags & 1u) {
-      const float gx = tex3d_tsdf<kSparse>(V, u.x + sd, u.y, u.z) - tex3d_tsdf<kSparse>(V, u.x - sd, u.y, u.z);
-      const float gy = tex3d_tsdf<kSparse>(V, u.x, u.y + sd, u.z) - tex3d_tsdf<kSparse>(V, u.x, u.y - sd, u.z);
-      const float gz = tex3d_tsdf<kSparse>(V, u.x, u.y, u.z + sd) - tex3d_tsdf<kSparse>(V, u.x, u.y, u.z - sd);
-      const float3 gn = normalize3(make_float3(gx, gy, gz));
-      nrm = mesh_oct_normal(normalize3(make_float3(-gn.x / ex, -gn.y / ey, -gn.z / ez)));
-    }
-    if (kFlags & 2u) {
-      const float4 c = blend_colors(T, F, limit, u);
-      col = mesh_unorm8(c.x) | (mesh_unorm8(c.y) << 8) | (mesh_unorm8(c.z) << 16) | (mesh_unorm8(c.w) << 24);
-    }
-    ((uint4*)out)[o] = make_uint4(pos.x, pos.y, nrm, col);
-  }
+  mesh_tile_vertices_packed<kSparse, kFlags, kLevel>(V, T, F, G, t, nv, s_f, s_edge, (size_t)tile_vbase[t.id], out);   // (< needed_vertices <= max_vertices)
 }
 
 #ifndef RR_MESH_COMPACT_LDS
@@ -345,9 +289,6 @@ __global__ __launch_bounds__(kMeshThreads) void k_mesh_triangles_stream(Volume V
 // ordinal (tile_rec: the rows are the surface tiles in tile order) as one 16-byte store; the row area begins at a multiple of 16 bytes -- in the payload
 // behind the vertices and their zero padding, or at raw_table (the filter's raw frame, whose payload is the uint32 one).  In a launch of its own: folded
 // into the triangle launch (lane 0 of a tile's workgroup) it measured slower at level 0.
-__device__ __forceinline__ MeshTileRow* mesh_stream_table(const MeshStreamHeader* __restrict__ H, uint8_t* __restrict__ payload, uint32_t stride) {
-  return (MeshTileRow*)(payload + (((size_t)H->needed_vertices * stride + 15u) & ~(size_t)15u));
-}
 __global__ __launch_bounds__(kScanThreads) void k_mesh_stream_table(const MeshStreamHeader* __restrict__ H, const uint2* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_vbase,
                                                                     const unsigned long long* __restrict__ tile_tbase, const uint32_t* __restrict__ tile_rec, int n,
                                                                     uint8_t* __restrict__ payload, uint32_t stride, MeshTileRow* __restrict__ raw_table) {

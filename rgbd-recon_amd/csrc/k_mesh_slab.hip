@@ -12,6 +12,9 @@
 // Link.  k_mesh_slab_triangles reads the records alone.  The first vertex of an owned tile is base + tile_vbase[tile], of a seam tile
 // base + (the slab's vertices) + above[tile]: the slab above follows directly in the concatenation and `above` is its tsdf_mesh_slab_seam table.
 // As in k_mesh.hip no atomic decides a position and no workgroup waits for another.
+// Streamed parts (tsdf_mesh_stream on a ring of tsdf_mesh_stream_config_part; "mesh streaming: slab parts" in the header): the same count and scan, then
+// k_mesh_part_header, k_mesh_part_vertices_packed, k_mesh_part_table and k_mesh_part_triangles below -- the slab's part of the tile-local frame, whose
+// corner codes name no vertex of another slab by index, so that nothing of the link is needed.
 #include "tsdf_common.hpp"
 
 namespace rr {
@@ -116,12 +119,15 @@ __global__ __launch_bounds__(kMeshThreads) void k_mesh_slab_vertices(Volume V, S
   mesh_tile_vertices<kSparse, kLevel>(V, T, F, G, t, nv, s_f, s_edge, (size_t)tile_vbase[t.id], out_pos, out_nrm, out_col);
 }
 
-// ---- triangles of the owned tiles, with global indices: k_mesh_triangles' text, the tile of a corner taken relative to the slab's first layer
-template <int kLevel>
-__global__ __launch_bounds__(kMeshThreads) void k_mesh_slab_triangles(Volume V, MeshSlab B, const uint2* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_vbase,
-                                                                      const unsigned long long* __restrict__ tile_tbase, const uint32_t* __restrict__ tile_rec,
-                                                                      const uint32_t* __restrict__ records, uint32_t base, uint32_t slab_vertices,
-                                                                      const uint32_t* __restrict__ above, uint32_t* __restrict__ out_tri) {
+// ---- triangles of the owned tiles: k_mesh_triangles' text, the tile of a corner taken relative to the slab's first layer.  Out = uint32_t: global
+// indices (the link); Out = uint16_t: the streamed tile-local corner codes (the part ring), which name a corner by its offset inside its owner tile and
+// where that tile lies from this one -- nothing of base, slab_vertices and above is read then, a seam tile's records serve as an owned tile's do
+template <int kLevel, typename Out>
+__device__ __forceinline__ void mesh_slab_tile_triangles(const Volume& V, const MeshSlab& B, const uint2* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_vbase,
+                                                         const unsigned long long* __restrict__ tile_tbase, const uint32_t* __restrict__ tile_rec,
+                                                         const uint32_t* __restrict__ records, uint32_t base, uint32_t slab_vertices,
+                                                         const uint32_t* __restrict__ above, Out* __restrict__ out_tri) {
+  constexpr bool kLocal = std::is_same<Out, uint16_t>::value;
   __shared__ uint32_t s_first[kMeshCorners];                           // per corner: the mesh index of the first vertex it owns
   __shared__ uint8_t s_mask[kMeshCorners];                             // ... and its record's low byte (edge mask, inside bit)
   __shared__ uint32_t s_wave[kMeshWaves];
@@ -137,7 +143,8 @@ __global__ __launch_bounds__(kMeshThreads) void k_mesh_slab_triangles(Volume V, 
       const uint32_t slot = tile_rec[tile];
       if (slot != kNoSlot) {                                           // (a tile without surface owns no crossed edge: nothing is looked up in it)
         const uint32_t r = records[(size_t)slot * kMeshThreads + (((z & 7) << 6) | ((y & 7) << 3) | (x & 7))];
-        first = base + (tile < B.n_own ? tile_vbase[tile] : slab_vertices + above[tile - B.n_own]) + (r >> 8);
+        if constexpr (kLocal) first = (r >> 8) | ((uint32_t)((lx >> 3) | ((ly >> 3) << 1) | ((lz >> 3) << 2)) << 12);
+        else first = base + (tile < B.n_own ? tile_vbase[tile] : slab_vertices + above[tile - B.n_own]) + (r >> 8);
         mask = r & 0xffu;
       }
     }
@@ -158,6 +165,95 @@ __global__ __launch_bounds__(kMeshThreads) void k_mesh_slab_triangles(Volume V, 
   if (ntri == 0) return;
   mesh_cell_triangles(corners, s_first, s_mask, lx, ly, lz, out_tri + (size_t)(tile_tbase[t.id] + off) * 3);
 }
+template <int kLevel>
+__global__ __launch_bounds__(kMeshThreads) void k_mesh_slab_triangles(Volume V, MeshSlab B, const uint2* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_vbase,
+                                                                      const unsigned long long* __restrict__ tile_tbase, const uint32_t* __restrict__ tile_rec,
+                                                                      const uint32_t* __restrict__ records, uint32_t base, uint32_t slab_vertices,
+                                                                      const uint32_t* __restrict__ above, uint32_t* __restrict__ out_tri) {
+  mesh_slab_tile_triangles<kLevel>(V, B, tile_cnt, tile_vbase, tile_tbase, tile_rec, records, base, slab_vertices, above, out_tri);
+}
+
+// ---- the streamed part (tsdf_mesh_stream on a ring of tsdf_mesh_stream_config_part): the slab's part of the tile-local frame, complete without a number
+// from another slab.  Count and scan are the extract's, over owned + seam tiles.  Seam tiles sit last in the slab-local scan: the owned tiles' record
+// slots are [0, owned tiles with surface) -- the row ordinals --, their vertex and triangle bases part-local, and a seam tile's slot lies behind them, in
+// the n_seam slots the ring allocates beyond max_tiles.
+// The header: the scan's totals without the seam tiles' vertices and surface count, subtracted HERE (the extract does it on the host; the ring waits for
+// nothing).  One workgroup, a reduction over the n_seam counts, lane 0 writes; the record in front of the header carries what was subtracted.
+constexpr int kPartHeaderThreads = 256;
+__global__ __launch_bounds__(kPartHeaderThreads) void k_mesh_part_header(const MeshSums* __restrict__ totals, const uint2* __restrict__ tile_cnt, MeshSlab B,
+                                                                         MeshStreamPartRecord* __restrict__ record, MeshStreamHeader* __restrict__ H, uint32_t max_vertices,
+                                                                         uint32_t max_triangles, uint32_t max_tiles) {
+  __shared__ uint32_t s_wave[kPartHeaderThreads / 64];
+  uint32_t nv = 0, ns = 0;                                             // (a seam tile counts at most 64 * 7 vertices: the sums fit 32 bits at any resolution)
+  for (int k = threadIdx.x; k < B.n_seam; k += kPartHeaderThreads) { const uint32_t n = tile_cnt[B.n_own + k].x; nv += n; ns += n ? 1u : 0u; }
+  uint32_t seam_vertices, seam_tiles;
+  block_exclusive_sum<kPartHeaderThreads / 64>(nv, s_wave, &seam_vertices);
+  block_exclusive_sum<kPartHeaderThreads / 64>(ns, s_wave, &seam_tiles);
+  if (threadIdx.x != 0) return;
+  const MeshSums s = *totals;
+  const unsigned long long own_vertices = s.nv - seam_vertices, own_tiles = s.surface - seam_tiles;
+  MeshStreamHeader h{};
+  h.needed_vertices = own_vertices; h.needed_triangles = s.nt; h.needed_tiles = own_tiles; h.tiles_skipped = s.skipped;   // (a seam tile counts no triangle and no skip)
+  h.max_vertices = max_vertices; h.max_triangles = max_triangles; h.max_tiles = max_tiles;
+  h.overflow = (own_vertices > max_vertices ? 1u : 0u) | (s.nt > max_triangles ? 2u : 0u) | (own_tiles > max_tiles ? 4u : 0u);
+  h.n_vertices = h.overflow ? 0ull : own_vertices; h.n_triangles = h.overflow ? 0ull : s.nt;
+  *H = h;
+  MeshStreamPartRecord r{};
+  r.seam_tiles = seam_tiles; r.seam_vertices = seam_vertices;
+  *record = r;
+}
+// records of every tile with surface, packed vertices of the owned ones: k_mesh_vertices_packed per slab-local tile, the seam tile as in k_mesh_slab_vertices
+template <bool kSparse, uint32_t kFlags, int kLevel>
+__global__ __launch_bounds__(kMeshThreads, 4) void k_mesh_part_vertices_packed(Volume V, StreamTable T, FrameImages F, MeshGeometry G, MeshSlab B,
+                                                                               const MeshStreamHeader* __restrict__ H, const uint2* __restrict__ tile_cnt,
+                                                                               const uint32_t* __restrict__ tile_vbase, const uint32_t* __restrict__ tile_rec,
+                                                                               uint32_t* __restrict__ records, void* __restrict__ out) {
+  __shared__ float s_f[kMeshCorners];
+  __shared__ uint32_t s_wave[kMeshWaves];
+  __shared__ uint16_t s_edge[kMeshThreads * 7];                        // per vertex of the tile: lattice point << 3 | d
+  const LatticeOf<kLevel> L(V);
+  const MeshTile t = mesh_slab_tile(L, B);
+  const bool seam = t.id >= B.n_own;
+  const uint32_t nv = tile_cnt[t.id].x;
+  if (mesh_stream_overflow(H) || nv == 0) return;
+  if (seam) mesh_stage_seam<kSparse, kLevel>(V, L, t, s_f); else mesh_stage<kSparse, kLevel>(V, L, t, s_f);
+  __syncthreads();
+  const MeshPoint p = mesh_slab_point(L, t, s_f, seam);
+  uint32_t total;
+  const uint32_t off = block_exclusive_sum<kMeshWaves>((uint32_t)__popc(p.mask), s_wave, &total);
+  records[(size_t)tile_rec[t.id] * kMeshThreads + threadIdx.x] = p.mask | (p.inside << 7) | (off << 8);   // (tile_rec < needed_tiles + seam tiles <= max_tiles + n_seam)
+  if (seam) return;                                                    // (its vertices are the part above's)
+  {
+    uint32_t k = off;
+#pragma unroll
+    for (int d = 1; d < 8; ++d)
+      if (p.mask & (1u << (d - 1))) s_edge[k++] = (uint16_t)((threadIdx.x << 3) | d);
+  }
+  __syncthreads();
+  mesh_tile_vertices_packed<kSparse, kFlags, kLevel>(V, T, F, G, t, nv, s_f, s_edge, (size_t)tile_vbase[t.id], out);   // (owned tiles come first: < needed_vertices <= max_vertices)
+}
+// the table: one lane per OWNED tile, one 16-byte store at the tile's surface ordinal; `tile` is the id in the WHOLE level's grid, the two bases part-local
+__global__ __launch_bounds__(kPartHeaderThreads) void k_mesh_part_table(const MeshStreamHeader* __restrict__ H, const uint2* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_vbase,
+                                                                        const unsigned long long* __restrict__ tile_tbase, const uint32_t* __restrict__ tile_rec, int n_own,
+                                                                        uint32_t first_tile, uint8_t* __restrict__ payload, uint32_t stride) {
+  const int t = (int)(blockIdx.x * kPartHeaderThreads + threadIdx.x);
+  if (mesh_stream_overflow(H) || t >= n_own) return;
+  const size_t vertex_bytes = (size_t)H->needed_vertices * stride;
+  if (t == 0 && (vertex_bytes & 8u)) *(uint2*)(payload + vertex_bytes) = make_uint2(0u, 0u);   // the padding
+  const uint2 cnt = tile_cnt[t];
+  if (cnt.x)                                                           // (tile_rec < needed_tiles <= max_tiles)
+    *(uint4*)(mesh_stream_table(H, payload, stride) + tile_rec[t]) = make_uint4(first_tile + (uint32_t)t, tile_vbase[t], (uint32_t)tile_tbase[t], cnt.y);
+}
+// ... and the 6-byte triangles behind the rows: exactly the codes of the whole volume's compact frame (a code names no part)
+template <int kLevel>
+__global__ __launch_bounds__(kMeshThreads) void k_mesh_part_triangles(Volume V, MeshSlab B, const MeshStreamHeader* __restrict__ H, const uint2* __restrict__ tile_cnt,
+                                                                      const uint32_t* __restrict__ tile_vbase, const unsigned long long* __restrict__ tile_tbase,
+                                                                      const uint32_t* __restrict__ tile_rec, const uint32_t* __restrict__ records,
+                                                                      uint8_t* __restrict__ payload, uint32_t stride) {
+  if (mesh_stream_overflow(H)) return;
+  mesh_slab_tile_triangles<kLevel, uint16_t>(V, B, tile_cnt, tile_vbase, tile_tbase, tile_rec, records, 0u, 0u, nullptr,
+                                             (uint16_t*)(mesh_stream_table(H, payload, stride) + H->needed_tiles));
+}
 
 // ---- launchers.  S: the scratch over B.n_own + B.n_seam tiles, S.level the instantiation (the caller has checked it)
 void launch_mesh_slab_count(hipStream_t st, const Volume& V, const MeshScratch& S, const MeshSlab& B) {
@@ -177,6 +273,32 @@ void launch_mesh_slab_triangles(hipStream_t st, const Volume& V, const MeshScrat
   mesh_instantiation(V, S, [&](auto, auto level) {
     hipLaunchKernelGGL(k_mesh_slab_triangles<decltype(level)::value>, dim3(B.n_own), dim3(kMeshThreads), 0, st, V, B, S.tile_cnt, S.tile_vbase, S.tile_tbase, S.tile_rec,
                        records, base, slab_vertices, above, tri);
+  });
+}
+// the streamed part: header (behind launch_mesh_slab_count and launch_mesh_scan), then the emit.  record: 64 bytes in front of H; records: 512 words for
+// each of max_tiles + B.n_seam tiles; payload: the tile-local format's capacity (result_paths.hpp: MeshFrameLayout)
+void launch_mesh_part_header(hipStream_t st, const MeshScratch& S, const MeshSlab& B, MeshStreamPartRecord* record, MeshStreamHeader* H, uint32_t max_vertices,
+                             uint32_t max_triangles, uint32_t max_tiles) {
+  hipLaunchKernelGGL(k_mesh_part_header, dim3(1), dim3(kPartHeaderThreads), 0, st, (const MeshSums*)S.sums + mesh_scan_blocks(S.n_tiles), S.tile_cnt, B, record, H, max_vertices,
+                     max_triangles, max_tiles);
+}
+void launch_mesh_part_emit(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S, const MeshSlab& B,
+                           uint32_t flags, const MeshStreamHeader* H, uint32_t* records, void* payload) {
+  mesh_instantiation(V, S, [&](auto sparse, auto level) {
+    constexpr bool kSparse = decltype(sparse)::value;
+    constexpr int kLevel = decltype(level)::value;
+    const dim3 g(S.n_tiles), own(B.n_own), b(kMeshThreads);
+    const uint32_t stride = flags ? 16u : 8u;
+    switch (flags & 3u) {
+      case 0u: hipLaunchKernelGGL((k_mesh_part_vertices_packed<kSparse, 0u, kLevel>), g, b, 0, st, V, T, F, G, B, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
+      case 1u: hipLaunchKernelGGL((k_mesh_part_vertices_packed<kSparse, 1u, kLevel>), g, b, 0, st, V, T, F, G, B, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
+      case 2u: hipLaunchKernelGGL((k_mesh_part_vertices_packed<kSparse, 2u, kLevel>), g, b, 0, st, V, T, F, G, B, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
+      default: hipLaunchKernelGGL((k_mesh_part_vertices_packed<kSparse, 3u, kLevel>), g, b, 0, st, V, T, F, G, B, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
+    }
+    const MeshLattice lat = mesh_lattice(V.res, kLevel);
+    hipLaunchKernelGGL(k_mesh_part_table, dim3((B.n_own + kPartHeaderThreads - 1) / kPartHeaderThreads), dim3(kPartHeaderThreads), 0, st, H, S.tile_cnt, S.tile_vbase, S.tile_tbase,
+                       S.tile_rec, B.n_own, (uint32_t)(B.layer0 * lat.ntx * lat.nty), (uint8_t*)payload, stride);
+    hipLaunchKernelGGL(k_mesh_part_triangles<kLevel>, own, b, 0, st, V, B, H, S.tile_cnt, S.tile_vbase, S.tile_tbase, S.tile_rec, records, (uint8_t*)payload, stride);
   });
 }
 

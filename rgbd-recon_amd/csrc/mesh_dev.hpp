@@ -169,6 +169,78 @@ __device__ __forceinline__ void mesh_tile_vertices(const Volume& V, const Stream
   }
 }
 
+// ---- the streamed form (tsdf_mesh_stream): what the emit kernels of a whole volume (k_mesh.hip) and of a slab's part (k_mesh_slab.hip) share.
+// H is the frame's header in device memory: when a need exceeds its capacity every workgroup of the emit kernels returns before it reads anything else,
+// so nothing is ever written past a capacity.
+struct MeshSums { unsigned long long nv, nt, surface, skipped; };      // the scan's four quantities (k_mesh.hip: launch_mesh_scan); S.sums[blocks] the totals
+__device__ __forceinline__ bool mesh_stream_overflow(const MeshStreamHeader* __restrict__ H) {
+  return H->needed_vertices > H->max_vertices || H->needed_triangles > H->max_triangles || H->needed_tiles > H->max_tiles;
+}
+// the tile-local format's row area: behind the vertices and their zero padding, at a multiple of 16 bytes
+__device__ __forceinline__ MeshTileRow* mesh_stream_table(const MeshStreamHeader* __restrict__ H, uint8_t* __restrict__ payload, uint32_t stride) {
+  return (MeshTileRow*)(payload + (((size_t)H->needed_vertices * stride + 15u) & ~(size_t)15u));
+}
+__device__ __forceinline__ uint32_t unorm16(float u) { return (uint32_t)__float2int_rn(fminf(fmaxf(u, 0.0f), 1.0f) * 65535.0f); }
+__device__ __forceinline__ uint32_t snorm16(float p) { return (uint32_t)__float2int_rn(fminf(fmaxf(p, -1.0f), 1.0f) * 32767.0f) & 0xffffu; }
+// tsdf_present's RGBA8 rule (k_present.hip: unorm8): the clamp maps NaN to 0
+__device__ __forceinline__ uint32_t mesh_unorm8(float v) { return (uint32_t)__float2int_rn(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f); }
+// octahedral code of a unit normal, two int16; a NaN component: (-32768, -32768)
+__device__ __forceinline__ uint32_t mesh_oct_normal(float3 n) {
+  if (n.x != n.x || n.y != n.y || n.z != n.z) return 0x80008000u;
+  const float s = (fabsf(n.x) + fabsf(n.y)) + fabsf(n.z);
+  float px = n.x / s, py = n.y / s;
+  if (n.z < 0.0f) {
+    const float fx = (1.0f - fabsf(py)) * (px >= 0.0f ? 1.0f : -1.0f), fy = (1.0f - fabsf(px)) * (py >= 0.0f ? 1.0f : -1.0f);
+    px = fx; py = fy;
+  }
+  return snorm16(px) | (snorm16(py) << 16);
+}
+// The tile's nv vertices, packed: mesh_tile_vertices' text up to the vertex's unit-cube position u, word for word (the extraction keeps its body untouched,
+// so the two are written out twice), then the same vertex quantised in registers and written with ONE 8- or 16-byte store -- no fp32 position, normal or
+// colour exists in memory.  `first`: the tile's first vertex in `out` (first + nv <= needed_vertices <= max_vertices: the caller has read the header).
+template <bool kSparse, uint32_t kFlags, int kLevel>
+__device__ __forceinline__ void mesh_tile_vertices_packed(const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshTile& t, uint32_t nv,
+                                                          const float* s_f, const uint16_t* s_edge, size_t first, void* __restrict__ out) {
+  const float ex = G.bbox_max[0] - G.bbox_min[0], ey = G.bbox_max[1] - G.bbox_min[1], ez = G.bbox_max[2] - G.bbox_min[2];
+  const float limit = V.limit, sd = limit * 0.5f;
+  for (uint32_t v = threadIdx.x; v < nv; v += kMeshThreads) {
+    const int e = s_edge[v], lane = e >> 3, d = e & 7;
+    const int lx = lane & 7, ly = (lane >> 3) & 7, lz = lane >> 6;
+    const int bx = d & 1, by = (d >> 1) & 1, bz = d >> 2;
+    float a = s_f[corner_index(lx, ly, lz)], b = s_f[corner_index(lx + bx, ly + by, lz + bz)];
+    float w;
+    int x, y, z;
+    if constexpr (kLevel == 0) {
+      w = a / (a - b);
+      x = t.tx * 8 + lx; y = t.ty * 8 + ly; z = t.tz * 8 + lz;
+    } else {                                                           // the voxel edge of the vertex: every level's vertex is a level-0 vertex
+      x = (t.tx * 8 + lx) << kLevel; y = (t.ty * 8 + ly) << kLevel; z = (t.tz * 8 + lz) << kLevel;
+      mesh_descend<kSparse, kLevel>(V, bx, by, bz, x, y, z, a, b);
+      w = a / (a - b);
+    }
+    const float upx = ((float)x + 0.5f) / (float)V.res[0], uqx = ((float)(x + bx) + 0.5f) / (float)V.res[0];
+    const float upy = ((float)y + 0.5f) / (float)V.res[1], uqy = ((float)(y + by) + 0.5f) / (float)V.res[1];
+    const float upz = ((float)z + 0.5f) / (float)V.res[2], uqz = ((float)(z + bz) + 0.5f) / (float)V.res[2];
+    const float3 u = make_float3(upx + w * (uqx - upx), upy + w * (uqy - upy), upz + w * (uqz - upz));
+    const size_t o = first + v;
+    const uint2 pos = make_uint2(unorm16(u.x) | (unorm16(u.y) << 16), unorm16(u.z));
+    if (kFlags == 0u) { ((uint2*)out)[o] = pos; continue; }
+    uint32_t nrm = 0u, col = 0u;
+    if (kFlags & 1u) {
+      const float gx = tex3d_tsdf<kSparse>(V, u.x + sd, u.y, u.z) - tex3d_tsdf<kSparse>(V, u.x - sd, u.y, u.z);
+      const float gy = tex3d_tsdf<kSparse>(V, u.x, u.y + sd, u.z) - tex3d_tsdf<kSparse>(V, u.x, u.y - sd, u.z);
+      const float gz = tex3d_tsdf<kSparse>(V, u.x, u.y, u.z + sd) - tex3d_tsdf<kSparse>(V, u.x, u.y, u.z - sd);
+      const float3 gn = normalize3(make_float3(gx, gy, gz));
+      nrm = mesh_oct_normal(normalize3(make_float3(-gn.x / ex, -gn.y / ey, -gn.z / ez)));
+    }
+    if (kFlags & 2u) {
+      const float4 c = blend_colors(T, F, limit, u);
+      col = mesh_unorm8(c.x) | (mesh_unorm8(c.y) << 8) | (mesh_unorm8(c.z) << 16) | (mesh_unorm8(c.w) << 24);
+    }
+    ((uint4*)out)[o] = make_uint4(pos.x, pos.y, nrm, col);
+  }
+}
+
 // the mesh index of the vertex on the edge between corners x < y of the cell at (lx, ly, lz): s_first / s_mask hold, per corner of the tile, the index
 // of the first vertex it owns and its record's low byte
 __device__ __forceinline__ uint32_t edge_vertex(const uint32_t* s_first, const uint8_t* s_mask, int lx, int ly, int lz, int x, int y) {

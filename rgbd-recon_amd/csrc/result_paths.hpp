@@ -54,6 +54,24 @@ struct MeshFrameLayout {
   }
 };
 
+// A Z-slab's part of the tile-local frame ("mesh streaming: slab parts"): which lattice tile layers of a level a context owns, and what the part ring holds
+// beyond a whole-volume ring.  own_tz0 / own_tz1: the owned storage tile layers (8 voxel planes each), storage_ntz those of the whole volume, lattice_ntz
+// the level's lattice tile layers.  A slab reaching the volume's top owns the lattice's last layer whatever its height; below the top both faces must lie on
+// the level's lattice tiles (1 << level storage layers each).
+struct MeshPartLayers {
+  int layer0, layer1; bool top, aligned;
+  static MeshPartLayers of(int own_tz0, int own_tz1, int storage_ntz, int level, int lattice_ntz) {
+    const int stride = 1 << level;
+    const bool top = own_tz1 == storage_ntz;
+    return MeshPartLayers{own_tz0 >> level, top ? lattice_ntz : (own_tz1 >> level), top, own_tz0 % stride == 0 && (top || own_tz1 % stride == 0)};
+  }
+  // the seam layer: the tiles of the first layer above the owned ones, whose plane-0 records the part's top cells read (none at the top)
+  uint64_t seam_tiles(uint64_t tiles_per_layer) const { return top ? 0u : tiles_per_layer; }
+  // record slots: the owned surface tiles the capacity bounds, and every seam tile -- a seam tile never causes an overflow, there is no fourth capacity
+  uint64_t record_slots(uint64_t max_tiles, uint64_t tiles_per_layer) const { return max_tiles + seam_tiles(tiles_per_layer); }
+};
+constexpr uint64_t kMeshPartRecordBytes = 64;                           // MeshStreamPartRecord, in front of a part frame's header
+
 // Staging of a call's synchronous form (host arrays in and out): one capacity, in elements of the call (rays, points), for the input and result buffers,
 // one for the buffer only some calls ask for (a cast's surface records, a tap call's sensor records: allocated by the first call that does); grown to the
 // next power of two at or above the need (at least 1024 elements), never shrunk.

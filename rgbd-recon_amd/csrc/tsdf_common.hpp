@@ -405,6 +405,15 @@ struct MeshTileRow { uint32_t tile, first_vertex, first_triangle, n_triangles; }
 static_assert(sizeof(MeshTileRow) == 16, "tsdf_mesh_tile_row");
 void launch_mesh_stream_emit_compact(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S, uint32_t flags,
                                      const MeshStreamHeader* H, uint32_t* records, void* payload, MeshTileRow* raw_table);
+// A Z-slab's part of the tile-local frame (k_mesh_slab.hip; the header's "mesh streaming: slab parts"): behind launch_mesh_slab_count and launch_mesh_scan
+// over B.n_own + B.n_seam tiles.  The header counts the OWNED tiles' vertices and surface tiles; what the seam tiles added to the scan's totals goes into the
+// 64-byte record in front of it (one copy takes both, as with the filter's record).  records: 512 words for each of max_tiles + B.n_seam tiles.
+struct MeshStreamPartRecord { unsigned long long seam_tiles, seam_vertices, reserved[6]; };
+static_assert(sizeof(MeshStreamPartRecord) == 64, "the header stays 64 bytes in front of the payload");
+void launch_mesh_part_header(hipStream_t st, const MeshScratch& S, const MeshSlab& B, MeshStreamPartRecord* record, MeshStreamHeader* H, uint32_t max_vertices,
+                             uint32_t max_triangles, uint32_t max_tiles);
+void launch_mesh_part_emit(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S, const MeshSlab& B,
+                           uint32_t flags, const MeshStreamHeader* H, uint32_t* records, void* payload);
 // the streamed filter (k_mesh_stream_filter.hip; tsdf_mesh_stream_config_filter with min_triangles >= 1): the emit writes the unfiltered frame into `raw`
 // (a header, the capacity-sized payload behind it: device only, one per configuration), the filter's launches move what stays into a slot's payload and
 // write the slot's header and record.  Every launch is sized by the capacities and reads the frame's counts from the raw header.

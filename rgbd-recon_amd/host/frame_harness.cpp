@@ -20,6 +20,9 @@
 // Option --mesh-stream-compact (implies --mesh-stream): the ring streams 6-byte tile-local triangles (TSDF_MESH_INDEX_TILE16); every frame's uint32
 // pointer must be null, its codes decoded on the host (decodeMeshTriangles) must equal downloadMesh's triangles of the same extract, and the payload
 // bytes must be the compact sizes.
+// Option --mesh-stream-part (implies --mesh-stream-compact; no filter): the ring is configured with configureMeshStreamPart, so every frame is the
+// context's part of the tile-local frame -- on this whole-volume context the one-slab case: the part must reach the top, own every lattice tile layer
+// and have no seam tile, and the join of that one part (joinMeshParts) must decode to downloadMesh's triangles.
 //   g++ -std=c++17 frame_harness.cpp -o frame_harness -L.. -lrgbd_recon_hip -Wl,-rpath,'$ORIGIN/..'
 #include <cmath>
 #include <cstdio>
@@ -38,7 +41,7 @@ int main(int argc, char** argv) {
   bool mesh_stream = false;
   int mesh_level = -1;                                                    // -1: not given (the entries without a level)
   long mesh_stream_min_triangles = -1;                                    // -1: not given (the ring without a filter)
-  bool mesh_stream_compact = false;
+  bool mesh_stream_compact = false, mesh_stream_part = false;
   for (int a = 1; a < argc; ++a) {
     if (std::strcmp(argv[a], "--draw-bricks") == 0) draw_bricks = true;
     else if (std::strcmp(argv[a], "--sensor-view") == 0 && a + 2 < argc) { view_type = std::atoi(argv[a + 1]); view_width = (float)std::atof(argv[a + 2]); a += 2; }
@@ -52,12 +55,14 @@ int main(int argc, char** argv) {
       mesh_stream_min_triangles = std::atol(argv[a + 1]); mesh_stream = true; a += 1;
     }
     else if (std::strcmp(argv[a], "--mesh-stream-compact") == 0) { mesh_stream_compact = true; mesh_stream = true; }
+    else if (std::strcmp(argv[a], "--mesh-stream-part") == 0) { mesh_stream_part = true; mesh_stream_compact = true; mesh_stream = true; }
     else {
       std::fprintf(stderr, "usage: frame_harness [--draw-bricks] [--sensor-view TYPE WIDTH] [--present rgba8|dxt1] [--mesh FILE.ply] [--mesh-stream] [--mesh-level 0|1|2]"
-                           " [--mesh-stream-min-triangles N] [--mesh-stream-compact]\n");
+                           " [--mesh-stream-min-triangles N] [--mesh-stream-compact] [--mesh-stream-part]\n");
       return 1;
     }
   }
+  if (mesh_stream_part && mesh_stream_min_triangles >= 0) { std::fprintf(stderr, "--mesh-stream-part has no filter\n"); return 1; }
   kinect::ReconInputs in;
   in.num_kinects = 1;
   in.depth_width = in.color_width = 8;
@@ -170,7 +175,8 @@ int main(int argc, char** argv) {
       kinect::ReconIntegrationHip::Mesh want;                                  // the triangles the decoded codes have to equal
       if (mesh_stream_compact) recon.downloadMesh(want);
       std::uint64_t want_bytes = 0;
-      if (mesh_stream_compact) recon.configureMeshStream(true, true, (unsigned)(mesh_level < 0 ? 0 : mesh_level), (unsigned)(filtered ? mesh_stream_min_triangles : 0),
+      if (mesh_stream_part) recon.configureMeshStreamPart(true, true, (unsigned)(mesh_level < 0 ? 0 : mesh_level), 4096, 8192, 64, 3);
+      else if (mesh_stream_compact) recon.configureMeshStream(true, true, (unsigned)(mesh_level < 0 ? 0 : mesh_level), (unsigned)(filtered ? mesh_stream_min_triangles : 0),
                                                          TSDF_MESH_INDEX_TILE16, 4096, 8192, 64, 3);
       else if (filtered) recon.configureMeshStream(true, true, (unsigned)(mesh_level < 0 ? 0 : mesh_level), (unsigned)mesh_stream_min_triangles, 4096, 8192, 64, 3);
       else if (mesh_level < 0) recon.configureMeshStream(true, true, 4096, 8192, 64, 3);
@@ -193,6 +199,13 @@ int main(int argc, char** argv) {
           const tsdf_mesh_compact c = recon.meshFrameCompact();
           ok = ok && fr.triangles == nullptr && kinect::ReconIntegrationHip::decodeMeshTriangles(c, fr.n_triangles) == want.triangles;
           want_bytes += fr.n_vertices ? (fr.n_vertices * 16 + 15) / 16 * 16 + c.n_tile_rows * 16 + fr.n_triangles * 6 : 0;
+          if (mesh_stream_part) {
+            const tsdf_mesh_part part = recon.meshFramePart();
+            ok = ok && part.top == 1 && part.layers[0] == 0 && part.layers[1] == c.tiles[2] && part.seam_tiles == 0 && part.level == c.level;
+            kinect::ReconIntegrationHip::MeshPartFrame joined;
+            ok = ok && kinect::ReconIntegrationHip::joinMeshParts({recon.takeMeshPart(fr)}, joined) && joined.nVertices() == fr.n_vertices &&
+                 kinect::ReconIntegrationHip::decodeMeshTriangles(joined.compact(), joined.nTriangles()) == want.triangles;
+          }
         } else want_bytes += fr.n_vertices * 16 + fr.n_triangles * 12;
         recon.releaseMeshFrame();                                              // (before it is counted: a held frame would fail every later acquire too)
         ++(ok ? got : wrong);

@@ -351,6 +351,64 @@ class ReconIntegrationHip {
     }
     return out;
   }
+  // ... as this context's PART of the tile-local frame (tsdf_mesh_stream_config_part): the one ring a Z-slab context streams through; a whole-volume
+  // context is the one-slab case.  Capacities are per part; there is no filter.  meshFramePart(): the layers, level, top flag and seam tiles of the frame
+  // HELD now (throws on another ring or without a frame); takeMeshPart copies the held frame into a MeshPartFrame of the caller's own.  joinMeshParts
+  // is the header's join rule over the parts of contiguous slabs in slab order: false (and `out` empty) when a part overflowed -- the frame is dropped
+  // whole -- or the parts do not follow each other; the joined frame is the whole-volume compact frame, byte for byte.
+  struct MeshPartFrame {
+    std::vector<std::uint8_t> vertices; std::vector<tsdf_mesh_tile_row> table; std::vector<std::uint16_t> codes;
+    std::uint32_t vertex_stride = 0, overflow = 0, tiles[3] = {0, 0, 0};
+    tsdf_mesh_part part{};
+    std::uint64_t nVertices() const { return vertex_stride ? vertices.size() / vertex_stride : 0; }
+    std::uint64_t nTriangles() const { return codes.size() / 3; }
+    tsdf_mesh_compact compact() const { return tsdf_mesh_compact{table.data(), codes.data(), table.size(), {tiles[0], tiles[1], tiles[2]}, part.level}; }
+  };
+  void configureMeshStreamPart(bool normals, bool colours, unsigned level, unsigned max_vertices, unsigned max_triangles, unsigned max_surface_tiles, unsigned slots = 3) {
+    check(tsdf_mesh_stream_config_part(m_ctx, (normals ? TSDF_MESH_NORMALS : 0u) | (colours ? TSDF_MESH_COLOURS : 0u), level, max_vertices, max_triangles,
+                                       max_surface_tiles, slots));
+  }
+  tsdf_mesh_part meshFramePart() {
+    tsdf_mesh_part out{};
+    check(tsdf_mesh_stream_frame_part(m_ctx, &out));
+    return out;
+  }
+  MeshPartFrame takeMeshPart(const tsdf_mesh_frame& held) {
+    const tsdf_mesh_compact c = meshFrameCompact();
+    MeshPartFrame p;
+    p.part = meshFramePart();
+    p.vertex_stride = held.vertex_stride; p.overflow = held.overflow;
+    for (int a = 0; a < 3; ++a) p.tiles[a] = c.tiles[a];
+    const std::uint8_t* v = (const std::uint8_t*)held.vertices;
+    p.vertices.assign(v, v + held.n_vertices * held.vertex_stride);
+    p.table.assign(c.table, c.table + c.n_tile_rows);
+    p.codes.assign(c.triangles, c.triangles + held.n_triangles * 3);
+    return p;
+  }
+  static bool joinMeshParts(const std::vector<MeshPartFrame>& parts, MeshPartFrame& out) {
+    out = MeshPartFrame{};
+    if (parts.empty()) return false;
+    for (std::size_t k = 0; k < parts.size(); ++k) {
+      const MeshPartFrame& p = parts[k];
+      if (p.overflow || p.vertex_stride != parts[0].vertex_stride || p.part.level != parts[0].part.level) return false;
+      if (k && p.part.layers[0] != parts[k - 1].part.layers[1]) return false;
+    }
+    out.vertex_stride = parts[0].vertex_stride;
+    for (int a = 0; a < 3; ++a) out.tiles[a] = parts[0].tiles[a];
+    out.part = parts.back().part;
+    out.part.layers[0] = parts[0].part.layers[0];
+    std::uint64_t nv = 0, nt = 0;
+    for (const MeshPartFrame& p : parts) {
+      out.vertices.insert(out.vertices.end(), p.vertices.begin(), p.vertices.end());
+      for (tsdf_mesh_tile_row row : p.table) {
+        row.first_vertex += (std::uint32_t)nv; row.first_triangle += (std::uint32_t)nt;
+        out.table.push_back(row);
+      }
+      out.codes.insert(out.codes.end(), p.codes.begin(), p.codes.end());
+      nv += p.nVertices(); nt += p.nTriangles();
+    }
+    return true;
+  }
   // after drawF(): never blocks; false = every slot is queued or held (or there is no volume yet), nothing was queued
   bool streamMesh(std::uint64_t tag) {
     const int32_t rc = tsdf_mesh_stream(m_ctx, tag);

@@ -48,6 +48,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .binding import join_mesh_parts
+
 
 def worker_slab_range(res_z: int, rank: int, world: int):
     """Slab of rank `rank` when rank 0 is a dedicated compositor: ranks 1 .. world-1 split the volume; rank 0 gets the first worker's
@@ -403,6 +405,29 @@ class SlabDriver:
             out["mesh"] = {k: np.concatenate([p[k] for p in parts]) for k in part}
         return out
 
+    # ------------------------------------------------------------------ ... and streamed every frame: tile-local parts that join unaided
+    def stream_mesh(self, tag=0, take=True, wait=True):
+        """Queue this rank's PART of the frame's mesh on its part ring (mesh_stream_config(part=True) on the backend first; the halo must be current,
+        as after frame()): no exchange, no link step, no host wait -- a part is complete by itself.  take=False: that is all, the caller picks the
+        frame up from the backend when it likes (mesh_stream_take).  take=True: a COLLECTIVE -- every rank takes its oldest part (waiting for it), the
+        parts are gathered on rank 0 and joined by the header's rule; returns dict(part=the rank's (vertices, codes, info) or None) and, on rank 0,
+        frame=(vertices, codes, info): the whole-volume compact frame, or None when a part overflowed (the frame is dropped whole).  A dedicated
+        compositor contributes no part."""
+        if self.is_worker:
+            self.b.mesh_stream(tag)
+        if not take:
+            return None
+        part = self.b.mesh_stream_take(wait=wait) if self.is_worker else None
+        parts = [part]
+        if self.world > 1:
+            parts = [None] * self.world if self.rank == 0 else None
+            dist.gather_object(part, parts, dst=0, group=self.group)
+        out = dict(part=part)
+        if self.rank == 0:
+            parts = [p for p in parts if p is not None]
+            out["frame"] = None if any(p[2]["overflow"] for p in parts) else join_mesh_parts(parts)
+        return out
+
     def finish(self):
         """Completes the latest frame: call before reading its result (and at the end of a timed region).  A COLLECTIVE when
         the compact gather of that frame turned out too small -- every rank sees the same counts and re-gathers together."""
@@ -444,6 +469,16 @@ def mesh_slabs_on_one_device(backends, normals=True, colours=True, level=0):
     out = {key: np.concatenate([p[key] for p in parts]) for key in parts[0]}
     out["counts"], out["seams"] = counts, seams
     return out
+
+
+def mesh_parts_on_one_device(backends, tag=0):
+    """SlabDriver.stream_mesh with ONE visible device: backends[k] owns slab k (contiguous, in z order), each with a part ring configured
+    (mesh_stream_config(part=True)) and a current halo.  Every slab queues its part, then every part is taken; nothing travels between the slabs.
+    Returns (parts, frame): parts[k] = (vertices, codes, info) of slab k, frame = join_mesh_parts(parts), or None when a part overflowed."""
+    for b in backends:
+        b.mesh_stream(tag)
+    parts = [b.mesh_stream_take(wait=True) for b in backends]
+    return parts, (None if any(p[2]["overflow"] for p in parts) else join_mesh_parts(parts))
 
 
 def frame_slabs_on_one_device(backends, mv, proj, device, halo="exchange", composite="dense"):

@@ -17,8 +17,13 @@ four filter words and the payload bytes of the filtered and of the unfiltered fr
 --compact: instead of parts 1 and 2, the uint32 ring against the ring of 6-byte tile-local triangles (tsdf_mesh_stream_config_compact) in this one
 process, per level and for positions / all attributes, the two formats alternating call by call: the stage timers, the payload bytes per frame (measured
 from tsdf_mesh_stream_stats, and what the format's arithmetic gives), the host time from tsdf_mesh_stream on an idle device to the frame complete on the
-host ("latency_ms"), the copy's share of it (latency - device stages) and the bandwidth that gives, and the frames per second of the streamed loop."""
+host ("latency_ms"), the copy's share of it (latency - device stages) and the bandwidth that gives, and the frames per second of the streamed loop.
+--slabs K: instead of parts 1 and 2, K Z-slab contexts of the same volume on this one device (recomputed halos), each with a part ring
+(tsdf_mesh_stream_config_part), beside the whole-volume context's compact ring, at the first level named, for positions and all attributes: the stage
+timers of every slab's part (count + scan + emit; the slowest slab is what a frame waits for when every slab has a device of its own) and of the
+whole-volume ring, in WINDOWS windows of N calls with the two alternating call by call; and whether the joined parts equal the whole-volume frame."""
 import sys, os, json, time
+from importlib import import_module
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch  # noqa: F401  (torch first: the library binds to the HIP runtime torch loaded)
 import rgbd_recon_amd as rr
@@ -30,7 +35,9 @@ STAGES_ONLY = "--stages-only" in sys.argv
 ARGS = sys.argv[1:]
 LEVELS = [int(x) for x in ARGS[ARGS.index("--level") + 1].split(",")] if "--level" in ARGS else [0]
 MIN_TRIANGLES = int(ARGS[ARGS.index("--min-triangles") + 1]) if "--min-triangles" in ARGS else 0
-OUT = [a for i, a in enumerate(ARGS) if not a.startswith("--") and (i == 0 or ARGS[i - 1] not in ("--level", "--min-triangles", "--variants"))]
+SLABS = int(ARGS[ARGS.index("--slabs") + 1]) if "--slabs" in ARGS else 0
+WINDOWS = 5
+OUT = [a for i, a in enumerate(ARGS) if not a.startswith("--") and (i == 0 or ARGS[i - 1] not in ("--level", "--min-triangles", "--variants", "--slabs"))]
 VARIANTS = (("positions", dict(normals=False, colours=False)), ("normals", dict(normals=True, colours=False)), ("colours", dict(normals=False, colours=True)),
             ("all_attributes", dict(normals=True, colours=True)))
 if "--variants" in ARGS:
@@ -41,7 +48,8 @@ EXTRACT_STAGES = ("mesh_count", "mesh_scan", "mesh_emit")
 scene = rr.scene.make_scene(n_streams=4, width=640, height=480, lut_res=128, inv_res=128)
 ext = scene["bbox_max"] - scene["bbox_min"]
 res = (512,) * 3
-hip = rr.ReconIntegrationHip(scene, res=res, brick_size=[float(ext[a]) / res[a] * 8 for a in range(3)], limit=0.01, view=VIEW)
+CTX = dict(res=res, brick_size=[float(ext[a]) / res[a] * 8 for a in range(3)], limit=0.01, view=VIEW)
+hip = rr.ReconIntegrationHip(scene, **CTX)
 mv, pr = rr.scene.default_view(*VIEW)
 dev = [torch.from_numpy(np.ascontiguousarray(scene[k])).cuda() for k in ("depth", "quality", "silhouette", "color")]
 torch.cuda.synchronize()
@@ -141,8 +149,61 @@ def compact_record():
     return out
 
 
-if "--compact" in ARGS:
-    rec = compact_record()
+def slabs_record():
+    """--slabs K: the part rings of K slab contexts beside the whole-volume compact ring"""
+    mgpu = import_module("rgbd-recon_amd.multigpu")
+    L = LEVELS[0]
+    out = dict(rec, tool="tools/mesh_stream_timing.py --slabs %d" % SLABS, unit="ms", slabs=SLABS, windows=WINDOWS, calls_per_window=N)
+    ctxs = [rr.ReconIntegrationHip(scene, slab=mgpu.slab_range(res[2], k, SLABS), recompute_halo=True, **CTX) for k in range(SLABS)]
+    for c in ctxs:
+        c.clearOccupiedBricks(); c.markBricks(); c.updateOccupiedBricks(); c.integrate(); c.sync()
+    everyone = [hip] + ctxs
+    for label, kw in [v for v in VARIANTS if v[0] in ("positions", "all_attributes")]:
+        stride = 16 if (kw["normals"] or kw["colours"]) else 8
+        hip.mesh_stream_config(slots=3, level=L, index_format=rr.MESH_INDEX_TILE16, **kw, **levels[L]["capacities"])
+        for c in ctxs:
+            c.mesh_stream_config(slots=3, level=L, part=True, **kw, **levels[L]["capacities"])
+        hip.mesh_stream(0); want = hip.mesh_stream_take()                # (the configuration's first call allocates)
+        parts, joined = mgpu.mesh_parts_on_one_device(ctxs)
+        assert want[2]["overflow"] == 0 and joined is not None
+        identical = (joined[0].tobytes() == want[0].tobytes() and joined[1].tobytes() == want[1].tobytes() and
+                     joined[2]["compact"]["table"].tobytes() == want[2]["compact"]["table"].tobytes())
+        for c in everyone:
+            c.enable_timers(True); c.set_timer_filter(list(STREAM_STAGES))
+        windows = []
+        for w in range(WINDOWS):
+            ms = [{s: [] for s in STREAM_STAGES} for _ in everyone]
+            for k in range(2 + N):                                       # two warm calls, then N; whole and slabs alternate: all see the same machine
+                for i, c in enumerate(everyone):
+                    c.mesh_stream(k); c.mesh_stream_take()
+                    for s in STREAM_STAGES:
+                        cnt, total = c.timer_stats(s)
+                        if k >= 2:
+                            ms[i][s].append(total / cnt)
+            mean = [{s + "_ms": float(np.mean(m[s])) for s in STREAM_STAGES} for m in ms]
+            for m in mean:
+                m["device_ms"] = sum(m.values())
+            slow = max(range(SLABS), key=lambda k: mean[1 + k]["device_ms"])
+            windows.append(dict(whole_volume=mean[0], per_slab_device_ms=[m["device_ms"] for m in mean[1:]], slowest_slab=slow, slowest=mean[1 + slow],
+                                sum_of_slabs_ms=sum(m["device_ms"] for m in mean[1:])))
+        for c in everyone:
+            c.enable_timers(False)
+        per = [dict(planes=list(mgpu.slab_range(res[2], k, SLABS)), vertices=p[2]["n_vertices"], triangles=p[2]["n_triangles"], surface_tiles=p[2]["needed_tiles"],
+                    seam_tiles=p[2]["part"]["seam_tiles"], payload_bytes=(p[2]["n_vertices"] * stride + 15) // 16 * 16 + p[2]["needed_tiles"] * 16 + p[2]["n_triangles"] * 6
+                    if p[2]["n_vertices"] else 0) for k, p in enumerate(parts)]
+        whole_ms, slow_ms = [w["whole_volume"]["device_ms"] for w in windows], [w["slowest"]["device_ms"] for w in windows]
+        out[label] = dict(identical_to_whole_volume=bool(identical), per_slab=per, windows=windows,
+                          whole_volume_device_ms=dict(median=float(np.median(whole_ms)), min=min(whole_ms), max=max(whole_ms)),
+                          slowest_slab_device_ms=dict(median=float(np.median(slow_ms)), min=min(slow_ms), max=max(slow_ms)),
+                          whole_volume_payload_bytes=(want[2]["n_vertices"] * stride + 15) // 16 * 16 + want[2]["needed_tiles"] * 16 + want[2]["n_triangles"] * 6,
+                          sum_of_parts_payload_bytes=sum(r["payload_bytes"] for r in per))
+    for c in ctxs:
+        c.close()
+    return out
+
+
+if SLABS or "--compact" in ARGS:
+    rec = slabs_record() if SLABS else compact_record()
     print(json.dumps(rec), flush=True)
     if OUT:
         with open(OUT[0], "w") as f:
