@@ -646,8 +646,36 @@ void release_mesh_components(tsdf_ctx* c) {
   hipFree(K.vertex); hipFree(K.triangle); hipFree(K.table);
   K.vertex = nullptr; K.triangle = nullptr; K.table = nullptr; K.n = 0; K.largest = 0; K.valid = false;
 }
+// The four arrays of a mesh (tsdf_ctx::MeshStore), for the whole mesh, a slab's part and a filtered mesh in the making.  Allocate: the arrays that `flags`
+// names for nv vertices and nt triangles, each at least one element long (a part may own triangles and no vertex); false: out of memory, what was
+// allocated stays in A for the caller's free.  The counts and flags are the caller's to set.
+static bool mesh_store_allocate(MeshArrays& A, uint64_t nv, uint64_t nt, uint32_t flags) {
+  const size_t v = std::max<size_t>((size_t)nv, 1), t = std::max<size_t>((size_t)nt, 1);
+  bool ok = hipMalloc((void**)&A.pos, v * 3 * sizeof(float)) == hipSuccess && hipMalloc((void**)&A.tri, t * 3 * sizeof(uint32_t)) == hipSuccess;
+  if (ok && (flags & TSDF_MESH_NORMALS)) ok = hipMalloc((void**)&A.nrm, v * 3 * sizeof(float)) == hipSuccess;
+  if (ok && (flags & TSDF_MESH_COLOURS)) ok = hipMalloc((void**)&A.col, v * 4 * sizeof(float)) == hipSuccess;
+  return ok;
+}
+static void mesh_store_free(MeshArrays& A) {
+  hipFree(A.pos); hipFree(A.nrm); hipFree(A.col); hipFree(A.tri);
+  A = MeshArrays{nullptr, nullptr, nullptr, nullptr};
+}
+static uint64_t mesh_store_bytes(const tsdf_ctx::MeshStore& M) {
+  return M.nv * (3 + ((M.flags & TSDF_MESH_NORMALS) ? 3 : 0) + ((M.flags & TSDF_MESH_COLOURS) ? 4 : 0)) * sizeof(float) + M.nt * 3 * sizeof(uint32_t);
+}
+// into the caller's arrays, each of which may be null
+static hipError_t mesh_store_download(const tsdf_ctx::MeshStore& M, float* position_xyz, float* normal_xyz, float* colour_rgba, uint32_t* triangles) {
+  hipError_t e = hipSuccess;
+  if (M.nv) {
+    if (position_xyz) e = hipMemcpy(position_xyz, M.pos, (size_t)M.nv * 3 * sizeof(float), hipMemcpyDeviceToHost);
+    if (!e && normal_xyz) e = hipMemcpy(normal_xyz, M.nrm, (size_t)M.nv * 3 * sizeof(float), hipMemcpyDeviceToHost);
+    if (!e && colour_rgba) e = hipMemcpy(colour_rgba, M.col, (size_t)M.nv * 4 * sizeof(float), hipMemcpyDeviceToHost);
+  }
+  if (!e && M.nt && triangles) e = hipMemcpy(triangles, M.tri, (size_t)M.nt * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost);
+  return e;
+}
 void release_mesh(tsdf_ctx* c) {
-  hipFree(c->mesh.pos); hipFree(c->mesh.nrm); hipFree(c->mesh.col); hipFree(c->mesh.tri);
+  mesh_store_free(c->mesh);
   c->mesh = tsdf_ctx::Mesh{};
   release_mesh_texture_taps(c);
   release_mesh_components(c);
@@ -686,7 +714,7 @@ void release_mesh_stream(tsdf_ctx* c) {
 // a slab's part of the mesh and what its link needs (nothing queued reads them: extract, link and download synchronise)
 void release_mesh_slab(tsdf_ctx* c) {
   tsdf_ctx::MeshSlabPart& P = c->mslab;
-  hipFree(P.pos); hipFree(P.nrm); hipFree(P.col); hipFree(P.tri); hipFree(P.above);
+  mesh_store_free(P); hipFree(P.above);
   mesh_scratch_free(P.scratch, P.records);
   P = tsdf_ctx::MeshSlabPart{};
 }
@@ -2471,8 +2499,19 @@ static MeshGeometry mesh_geometry(const tsdf_ctx* c) {
   const float* lo = c->cfg.bbox_min; const float* hi = c->cfg.bbox_max;
   return MeshGeometry{{lo[0], lo[1], lo[2]}, {hi[0], hi[1], hi[2]}};
 }
-static uint64_t mesh_storage_bytes(const tsdf_ctx::Mesh& M) {
-  return M.nv * (3 + ((M.flags & TSDF_MESH_NORMALS) ? 3 : 0) + ((M.flags & TSDF_MESH_COLOURS) ? 4 : 0)) * sizeof(float) + M.nt * 3 * sizeof(uint32_t);
+// the attribute flags and the level of an extract or a ring.  report_flags false: the caller reports unknown flags itself, behind the level (the ring's
+// configuration names them with its capacities)
+static int32_t mesh_flags_level_check(tsdf_ctx* c, uint32_t flags, uint32_t level, bool report_flags = true) {
+  if (report_flags && (flags & ~(TSDF_MESH_NORMALS | TSDF_MESH_COLOURS))) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "unknown mesh flag");
+  if (level > (uint32_t)kMeshMaxLevel) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "mesh level %u (0 .. %d: every voxel, every 2nd, every 4th)", level, kMeshMaxLevel);
+  return TSDF_OK;
+}
+// the lattice tile layers of this context's slab at a level (result_paths.hpp), or the refusal of a slab whose planes do not lie on the level's tiles
+static int32_t mesh_part_layers(tsdf_ctx* c, uint32_t level, MeshPartLayers* layers) {
+  const Volume& V = c->vol;
+  *layers = MeshPartLayers::of(V.own_tz0, V.own_tz1, (c->res[2] + 7) / 8, (int)level, mesh_lattice(V.res, (int)level).ntz);
+  if (!layers->aligned) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "slab planes [%d, %d) do not lie on level %u's lattice tiles (%d planes each)", V.own_tz0 * 8, V.own_tz1 * 8, level, 8 << level);
+  return TSDF_OK;
 }
 // May a call read the fused volume (the extract, the mesh stream, a cast)?  The whole volume on this context, written at least once; with colours also
 // calibration and a frame.  on_a_slab: what the call says on a Z-slab context
@@ -2486,8 +2525,7 @@ int32_t tsdf_mesh_extract(tsdf_ctx* c, uint32_t flags, uint64_t* n_vertices, uin
 // per tile -- scratch, scan, records, stats -- is per LATTICE tile of that level.
 int32_t tsdf_mesh_extract_lod(tsdf_ctx* c, uint32_t flags, uint32_t level, uint64_t* n_vertices, uint64_t* n_triangles) {
   CHECK_CTX(c);
-  if (flags & ~(TSDF_MESH_NORMALS | TSDF_MESH_COLOURS)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "unknown mesh flag");
-  if (level > (uint32_t)kMeshMaxLevel) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "mesh level %u (0 .. %d: every voxel, every 2nd, every 4th)", level, kMeshMaxLevel);
+  if (int32_t rc = mesh_flags_level_check(c, flags, level)) return rc;
   if (int32_t rc = readable_volume_check(c, "tsdf_mesh_extract on a Z-slab context: a slab extracts its part with tsdf_mesh_slab_extract", (flags & TSDF_MESH_COLOURS) != 0)) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   release_mesh(c);                                                       // (nothing queued reads it: extract and download synchronise)
@@ -2515,10 +2553,7 @@ int32_t tsdf_mesh_extract_lod(tsdf_ctx* c, uint32_t flags, uint32_t level, uint6
     if (totals[0] > 0xffffffffull) FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "%llu vertices do not fit 32-bit indices", (unsigned long long)totals[0]);
     if (totals[0]) {
       const size_t nv = (size_t)totals[0], nt = (size_t)totals[1];
-      bool ok = hipMalloc((void**)&M.pos, nv * 3 * sizeof(float)) == hipSuccess && hipMalloc((void**)&M.tri, std::max<size_t>(nt, 1) * 3 * sizeof(uint32_t)) == hipSuccess &&
-                hipMalloc((void**)&tmp.records, (size_t)totals[2] * 512 * sizeof(uint32_t)) == hipSuccess;
-      if (ok && (flags & TSDF_MESH_NORMALS)) ok = hipMalloc((void**)&M.nrm, nv * 3 * sizeof(float)) == hipSuccess;
-      if (ok && (flags & TSDF_MESH_COLOURS)) ok = hipMalloc((void**)&M.col, nv * 4 * sizeof(float)) == hipSuccess;
+      const bool ok = mesh_store_allocate(M, nv, nt, flags) && hipMalloc((void**)&tmp.records, (size_t)totals[2] * 512 * sizeof(uint32_t)) == hipSuccess;
       if (!ok) { (void)hipGetLastError(); release_mesh(c); FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "no device memory for a mesh of %zu vertices and %zu triangles", nv, nt); }
       timer_begin(c, "mesh_emit");
       launch_mesh_emit(c->stream, V, c->luts, c->frame, mesh_geometry(c), S, tmp.records, M.pos, M.nrm, M.col, M.tri);
@@ -2529,7 +2564,7 @@ int32_t tsdf_mesh_extract_lod(tsdf_ctx* c, uint32_t flags, uint32_t level, uint6
   }
   M.nv = totals[0]; M.nt = totals[1]; M.valid = true;
   M.stats[1] = totals[3]; M.stats[2] = totals[2];
-  M.stats[3] = mesh_storage_bytes(M);
+  M.stats[3] = mesh_store_bytes(M);
   if (n_vertices) *n_vertices = M.nv;
   if (n_triangles) *n_triangles = M.nt;
   return TSDF_OK;
@@ -2545,13 +2580,7 @@ int32_t tsdf_mesh_download(tsdf_ctx* c, float* position_xyz, float* normal_xyz, 
   int32_t rc = mesh_attribute_check(c, normal_xyz != nullptr, colour_rgba != nullptr);
   if (rc) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
-  const tsdf_ctx::Mesh& M = c->mesh;
-  if (M.nv) {
-    if (position_xyz) HIP_TRY(c, hipMemcpy(position_xyz, M.pos, (size_t)M.nv * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (normal_xyz) HIP_TRY(c, hipMemcpy(normal_xyz, M.nrm, (size_t)M.nv * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (colour_rgba) HIP_TRY(c, hipMemcpy(colour_rgba, M.col, (size_t)M.nv * 4 * sizeof(float), hipMemcpyDeviceToHost));
-  }
-  if (M.nt && triangles) HIP_TRY(c, hipMemcpy(triangles, M.tri, (size_t)M.nt * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(c, mesh_store_download(c->mesh, position_xyz, normal_xyz, colour_rgba, triangles));
   return TSDF_OK;
 }
 int32_t tsdf_mesh_write_ply(tsdf_ctx* c, const char* path) {
@@ -2580,31 +2609,25 @@ int32_t tsdf_mesh_stats(tsdf_ctx* c, uint64_t out[4]) {
 
 // ---- a Z-slab's part of the mesh (k_mesh_slab.hip; the definition is in the header).  Extract: count, scan and vertices of the owned lattice tile layers
 // and the records of the seam layer's plane 0; link: the triangles, once the caller knows where the part starts and what the slab above begins with.
-static uint64_t mesh_slab_bytes(const tsdf_ctx::MeshSlabPart& P) {
-  return P.nv * (3 + ((P.flags & TSDF_MESH_NORMALS) ? 3 : 0) + ((P.flags & TSDF_MESH_COLOURS) ? 4 : 0)) * sizeof(float) + P.nt * 3 * sizeof(uint32_t);
-}
 int32_t tsdf_mesh_slab_extract(tsdf_ctx* c, uint32_t flags, uint32_t level, uint64_t* n_vertices, uint64_t* n_triangles) {
   CHECK_CTX(c);
   // The part of an earlier extract goes FIRST, before any argument is looked at: whatever this call answers, seam / link / download / stats never
   // serve a part whose sizes the caller no longer holds (nothing queued reads it: extract, link and download synchronise).
   HIP_TRY(c, hipSetDevice(c->device));
   release_mesh_slab(c);
-  if (flags & ~(TSDF_MESH_NORMALS | TSDF_MESH_COLOURS)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "unknown mesh flag");
-  if (level > (uint32_t)kMeshMaxLevel) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "mesh level %u (0 .. %d: every voxel, every 2nd, every 4th)", level, kMeshMaxLevel);
+  if (int32_t rc = mesh_flags_level_check(c, flags, level)) return rc;
   if (!c->have_volume) FAIL(c, TSDF_ERR_STATE, "no volume yet (tsdf_integrate or tsdf_upload_volume)");
   if (flags & TSDF_MESH_COLOURS) if (int32_t rc = require_inputs(c, false, true)) return rc;
   const Volume& V = c->vol;
   const MeshLattice L = mesh_lattice(V.res, (int)level);
-  const int stride = 1 << level;
-  const bool top = V.own_tz1 == (c->res[2] + 7) / 8;
-  if (V.own_tz0 % stride != 0 || (!top && V.own_tz1 % stride != 0))
-    FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "slab planes [%d, %d) do not lie on level %u's lattice tiles (%d planes each)", V.own_tz0 * 8, V.own_tz1 * 8, level, 8 * stride);
+  MeshPartLayers layers;
+  if (int32_t rc = mesh_part_layers(c, level, &layers)) return rc;
+  const bool top = layers.top;
   // The halo holds every plane a vertex of this slab reads (the header says why): voxel plane z1 + stride for the seam records, and the gradient taps'
   // footprint x + 1 planes past either face, x = limit / 2 * res_z, against 8 * halo_layers >= 2 x + 2.  Checked all the same, never clamped silently.
   if (!top && V.tz1 - V.own_tz1 < 1) FAIL(c, TSDF_ERR_STATE, "the slab stores no halo layer above its planes");
   tsdf_ctx::MeshSlabPart& P = c->mslab;
-  const int layer0 = V.own_tz0 >> level, layer1 = top ? L.ntz : (V.own_tz1 >> level);
-  P.slab = MeshSlab{layer0, (layer1 - layer0) * L.ntx * L.nty, top ? 0 : L.ntx * L.nty};
+  P.slab = MeshSlab{layers.layer0, (layers.layer1 - layers.layer0) * L.ntx * L.nty, top ? 0 : L.ntx * L.nty};
   P.ntx = L.ntx; P.nty = L.nty; P.flags = flags;
   P.seam_cnt.assign((size_t)P.slab.n_seam, 0u);
   P.stats[0] = (uint64_t)P.slab.n_own;
@@ -2633,11 +2656,7 @@ int32_t tsdf_mesh_slab_extract(tsdf_ctx* c, uint32_t flags, uint32_t level, uint
     for (size_t k = 0; k < seam.size(); ++k) { P.seam_cnt[k] = seam[k].x; seam_vertices += seam[k].x; seam_surface += seam[k].x ? 1u : 0u; }
     if (totals[2]) {                                                     // tiles with surface, seam tiles included: records for all of them
       const size_t nv = (size_t)(totals[0] - seam_vertices), nt = (size_t)totals[1];
-      bool ok = hipMalloc((void**)&P.pos, std::max<size_t>(nv, 1) * 3 * sizeof(float)) == hipSuccess &&
-                hipMalloc((void**)&P.tri, std::max<size_t>(nt, 1) * 3 * sizeof(uint32_t)) == hipSuccess &&
-                hipMalloc((void**)&P.records, (size_t)totals[2] * 512 * sizeof(uint32_t)) == hipSuccess;
-      if (ok && (flags & TSDF_MESH_NORMALS)) ok = hipMalloc((void**)&P.nrm, std::max<size_t>(nv, 1) * 3 * sizeof(float)) == hipSuccess;
-      if (ok && (flags & TSDF_MESH_COLOURS)) ok = hipMalloc((void**)&P.col, std::max<size_t>(nv, 1) * 4 * sizeof(float)) == hipSuccess;
+      const bool ok = mesh_store_allocate(P, nv, nt, flags) && hipMalloc((void**)&P.records, (size_t)totals[2] * 512 * sizeof(uint32_t)) == hipSuccess;
       if (!ok) { (void)hipGetLastError(); release_mesh_slab(c); FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "no device memory for a slab mesh of %zu vertices and %zu triangles", nv, nt); }
       timer_begin(c, "mesh_slab_emit");
       launch_mesh_slab_vertices(c->stream, V, c->luts, c->frame, mesh_geometry(c), S, P.slab, P.records, P.pos, P.nrm, P.col);
@@ -2648,7 +2667,7 @@ int32_t tsdf_mesh_slab_extract(tsdf_ctx* c, uint32_t flags, uint32_t level, uint
   }
   P.nv = totals[0] - seam_vertices; P.nt = totals[1]; P.valid = true; P.linked = false;
   P.stats[1] = totals[3]; P.stats[2] = totals[2] - seam_surface;
-  P.stats[3] = mesh_slab_bytes(P);
+  P.stats[3] = mesh_store_bytes(P);
   if (n_vertices) *n_vertices = P.nv;
   if (n_triangles) *n_triangles = P.nt;
   return TSDF_OK;
@@ -2699,12 +2718,7 @@ int32_t tsdf_mesh_slab_download(tsdf_ctx* c, float* position_xyz, float* normal_
   if (colour_rgba && !(P.flags & TSDF_MESH_COLOURS)) FAIL(c, TSDF_ERR_STATE, "the last tsdf_mesh_slab_extract produced no colours");
   if (triangles && !P.linked) FAIL(c, TSDF_ERR_STATE, "the slab's triangles have no indices yet (tsdf_mesh_slab_link)");
   HIP_TRY(c, hipSetDevice(c->device));
-  if (P.nv) {
-    if (position_xyz) HIP_TRY(c, hipMemcpy(position_xyz, P.pos, (size_t)P.nv * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (normal_xyz) HIP_TRY(c, hipMemcpy(normal_xyz, P.nrm, (size_t)P.nv * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (colour_rgba) HIP_TRY(c, hipMemcpy(colour_rgba, P.col, (size_t)P.nv * 4 * sizeof(float), hipMemcpyDeviceToHost));
-  }
-  if (P.nt && triangles) HIP_TRY(c, hipMemcpy(triangles, P.tri, (size_t)P.nt * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(c, mesh_store_download(P, position_xyz, normal_xyz, colour_rgba, triangles));
   return TSDF_OK;
 }
 int32_t tsdf_mesh_slab_stats(tsdf_ctx* c, uint64_t out[4]) {
@@ -2719,11 +2733,11 @@ int32_t tsdf_mesh_slab_stats(tsdf_ctx* c, uint64_t out[4]) {
 namespace {
 struct ComponentTemp {                                                    // what one call allocates besides what it leaves in the context: freed when it returns
   uint32_t* words = nullptr; unsigned long long* vsums = nullptr; unsigned long long* tsums = nullptr; uint32_t* largest = nullptr; uint8_t* keep = nullptr;
-  tsdf_ctx::MeshComponents made{}; tsdf_ctx::Mesh mesh{};                 // arrays not handed to the context yet
+  tsdf_ctx::MeshComponents made{}; MeshArrays mesh{};                     // arrays not handed to the context yet
   ~ComponentTemp() {
     hipFree(words); hipFree(vsums); hipFree(tsums); hipFree(largest); hipFree(keep);
     hipFree(made.vertex); hipFree(made.triangle); hipFree(made.table);
-    hipFree(mesh.pos); hipFree(mesh.nrm); hipFree(mesh.col); hipFree(mesh.tri);
+    mesh_store_free(mesh);
   }
 };
 bool device_alloc(void** p, size_t bytes) { return hipMalloc(p, std::max<size_t>(bytes, 4)) == hipSuccess; }
@@ -2809,27 +2823,21 @@ static int32_t mesh_keep(tsdf_ctx* c, const uint8_t* keep_host, uint32_t min_tri
   HIP_TRY(c, hipMemcpyAsync(&kept_t, tmp.tsums + nbt, 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, sync_ctx(c));                                               // (the new arrays are sized exactly; keep_host has been read)
   if (kept_v != M.nv) {                                                  // (every vertex has a component: all vertices kept = every component kept = the mesh as it is)
-    tsdf_ctx::Mesh& N = tmp.mesh;                                        // everything new is allocated before anything is replaced
-    ok = true;
-    if (kept_v) {
-      ok = device_alloc((void**)&N.pos, (size_t)kept_v * 12) && device_alloc((void**)&N.tri, (size_t)kept_t * 12);
-      if (ok && M.nrm) ok = device_alloc((void**)&N.nrm, (size_t)kept_v * 12);
-      if (ok && M.col) ok = device_alloc((void**)&N.col, (size_t)kept_v * 16);
-    }
+    MeshArrays& N = tmp.mesh;                                            // everything new is allocated before anything is replaced
+    ok = !kept_v || mesh_store_allocate(N, kept_v, kept_t, M.flags);
     if (!ok) { (void)hipGetLastError(); FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "no device memory for a filtered mesh of %llu vertices and %llu triangles", kept_v, kept_t); }
     if (kept_v) {
       timer_begin(c, "mesh_filter");
-      launch_mesh_cc_keep_scatter(c->stream, tmp.keep, K.vertex, K.triangle, nv, nt, tmp.vsums, tmp.tsums, MeshArrays{M.pos, M.nrm, M.col, M.tri},
-                                  MeshArrays{N.pos, N.nrm, N.col, N.tri}, tmp.words);
+      launch_mesh_cc_keep_scatter(c->stream, tmp.keep, K.vertex, K.triangle, nv, nt, tmp.vsums, tmp.tsums, M, N, tmp.words);
       timer_end(c, "mesh_filter");
       HIP_TRY(c, hipGetLastError());
       HIP_TRY(c, sync_ctx(c));
     }
-    std::swap(M.pos, N.pos); std::swap(M.nrm, N.nrm); std::swap(M.col, N.col); std::swap(M.tri, N.tri);   // (tmp frees the old arrays)
+    std::swap<MeshArrays>(M, N);                                         // (tmp frees the old arrays)
   }
   K.removed_vertices = M.nv - kept_v; K.removed_triangles = M.nt - kept_t;
   M.nv = kept_v; M.nt = kept_t;
-  M.stats[3] = mesh_storage_bytes(M);
+  M.stats[3] = mesh_store_bytes(M);
   release_mesh_components(c);                                            // (they labelled the mesh that was)
   release_mesh_texture_taps(c);
   if (n_vertices) *n_vertices = M.nv;
@@ -2871,16 +2879,13 @@ static int32_t mesh_stream_configure(tsdf_ctx* c, uint32_t flags, uint32_t level
                                      uint32_t max_triangles, uint32_t max_surface_tiles, uint32_t slots, bool part) {
   tsdf_ctx::MeshStream& R = c->mstream;
   if (index_format > TSDF_MESH_INDEX_TILE16) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "mesh index format %u (0: uint32 indices, 1: tile-local 16-bit codes)", index_format);
-  if (level > (uint32_t)kMeshMaxLevel) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "mesh level %u (0 .. %d: every voxel, every 2nd, every 4th)", level, kMeshMaxLevel);
+  if (int32_t rc = mesh_flags_level_check(c, flags, level, false)) return rc;
   if ((flags & ~(TSDF_MESH_NORMALS | TSDF_MESH_COLOURS)) || !max_vertices || !max_triangles || !max_surface_tiles || slots < 2 || slots > kMaxResultSlots)
     FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "mesh stream flags %u / capacities %u vertices, %u triangles, %u tiles / slots %u (flags 1 normals, 2 colours; capacities > 0; 2..%u slots)",
          flags, max_vertices, max_triangles, max_surface_tiles, slots, kMaxResultSlots);
   if (!MeshFrameLayout{index_format, flags ? 16u : 8u}.fits(max_vertices, max_triangles, max_surface_tiles)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "a mesh stream slot of more than 4 GiB");
-  if (part) {                                                            // the alignment rule of tsdf_mesh_slab_extract, here at config time
-    const Volume& V = c->vol;
-    if (!MeshPartLayers::of(V.own_tz0, V.own_tz1, (c->res[2] + 7) / 8, (int)level, mesh_lattice(V.res, (int)level).ntz).aligned)
-      FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "slab planes [%d, %d) do not lie on level %u's lattice tiles (%d planes each)", V.own_tz0 * 8, V.own_tz1 * 8, level, 8 << level);
-  }
+  MeshPartLayers layers;
+  if (part) if (int32_t rc = mesh_part_layers(c, level, &layers)) return rc;   // the alignment rule of tsdf_mesh_slab_extract, here at config time
   if (!R.ring.idle()) FAIL(c, TSDF_ERR_STATE, "%u streamed mesh frame(s) are queued or held: acquire and release them first", R.ring.count);
   HIP_TRY(c, hipSetDevice(c->device));
   // The ring is idle for the copies only (each was waited for before its frame was released): a frame that overflowed or had no payload was handed out
@@ -2951,10 +2956,9 @@ static int32_t mesh_stream_allocate(tsdf_ctx* c) {
   const MeshLattice L = mesh_lattice(c->vol.res, (int)R.level);
   size_t n_tiles = (size_t)L.ntx * L.nty * L.ntz, record_slots = R.max_tiles;
   if (R.part) {                                                          // the scratch over owned + seam tiles, records for the seam tiles beyond the capacity
-    const Volume& V = c->vol;
-    const MeshPartLayers P = MeshPartLayers::of(V.own_tz0, V.own_tz1, (c->res[2] + 7) / 8, (int)R.level, L.ntz);
+    MeshPartLayers P;
+    if (int32_t rc = mesh_part_layers(c, R.level, &P)) return rc;
     const size_t per_layer = (size_t)L.ntx * L.nty;
-    if (!P.aligned) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "slab planes [%d, %d) do not lie on level %u's lattice tiles (%d planes each)", V.own_tz0 * 8, V.own_tz1 * 8, R.level, 8 << R.level);
     R.slab = MeshSlab{P.layer0, (int)((size_t)(P.layer1 - P.layer0) * per_layer), (int)P.seam_tiles(per_layer)};
     n_tiles = (size_t)R.slab.n_own + (size_t)R.slab.n_seam;
     record_slots = (size_t)P.record_slots(R.max_tiles, per_layer);

@@ -130,15 +130,17 @@ struct tsdf_ctx {
   // mesh extraction (tsdf_mesh_extract): the arrays of the last extract, sized exactly from its counts, kept until the next extract, tsdf_set_voxel_size or
   // destroy; flags = the attributes it produced; stats = {tiles, tiles skipped by class, tiles with surface, bytes of mesh storage}.  Everything else an
   // extract allocates (per-tile counts, the lattice-point records) is gone when it returns.
-  struct Mesh { float* pos = nullptr; float* nrm = nullptr; float* col = nullptr; uint32_t* tri = nullptr; uint64_t nv = 0, nt = 0; uint32_t flags = 0; bool valid = false;
-                uint64_t stats[4] = {0, 0, 0, 0}; } mesh;
+  // MeshStore: the four arrays in device memory with the counts and flags that size them; abi.cpp's mesh_store_* allocate, free, size and download them
+  // for the whole mesh and for a slab's part alike.
+  struct MeshStore : MeshArrays { uint64_t nv = 0, nt = 0; uint32_t flags = 0; MeshStore() : MeshArrays{nullptr, nullptr, nullptr, nullptr} {} };
+  struct Mesh : MeshStore { bool valid = false; uint64_t stats[4] = {0, 0, 0, 0}; } mesh;
   // a Z-slab's part of the mesh (tsdf_mesh_slab_extract): a state of its own, so that everything built on `mesh` keeps refusing on a slab context.  The
   // vertex arrays and the triangle array (sized from the counts; the triangles are written by tsdf_mesh_slab_link, `linked` says whether they have been),
   // and what a link needs again: the scratch over owned + seam tiles, the records, the device copy of the table it was handed.  seam_cnt: the seam
   // tiles' plane-0 vertex counts on the host (the link's index check).  All of it lives until the next slab extract, tsdf_set_voxel_size or destroy.
-  struct MeshSlabPart { float* pos = nullptr; float* nrm = nullptr; float* col = nullptr; uint32_t* tri = nullptr; uint32_t* records = nullptr; uint32_t* above = nullptr;
-                        MeshScratch scratch{}; MeshSlab slab{}; int ntx = 0, nty = 0; std::vector<uint32_t> seam_cnt;
-                        uint64_t nv = 0, nt = 0; uint32_t flags = 0; bool valid = false, linked = false; uint64_t stats[4] = {0, 0, 0, 0}; } mslab;
+  struct MeshSlabPart : MeshStore { uint32_t* records = nullptr; uint32_t* above = nullptr;
+                                    MeshScratch scratch{}; MeshSlab slab{}; int ntx = 0, nty = 0; std::vector<uint32_t> seam_cnt;
+                                    bool valid = false, linked = false; uint64_t stats[4] = {0, 0, 0, 0}; } mslab;
   // mesh components (tsdf_mesh_components): the labels and the table of the current mesh, beside it in device memory; released with the mesh and by a
   // keep / filter (the mesh they labelled is gone then).  n / largest: components and the largest one's triangles of that labelling; removed_*: what the
   // last keep / filter of this extract took away.  Everything else a call allocates is gone when it returns.

@@ -37,43 +37,11 @@ namespace rr {
 
 constexpr int kScanThreads = 256, kScanPerThread = 4, kScanPerBlock = kScanThreads * kScanPerThread;
 
-// the lattice of a level, the corner stage, a lattice point's record and the per-tile emit bodies: mesh_dev.hpp (shared with k_mesh_slab.hip)
-template <int kLevel>
-__device__ __forceinline__ MeshTile mesh_tile(const LatticeOf<kLevel>& L) {
-  MeshTile t;
-  t.id = (int)blockIdx.x;
-  const int per_layer = L.ntx() * L.nty(), layer = t.id / per_layer, in_layer = t.id - layer * per_layer;
-  t.tz = layer; t.ty = in_layer / L.ntx(); t.tx = in_layer - t.ty * L.ntx();
-  return t;
-}
+// every stage's body is mesh_dev.hpp's; the kernels here name the whole volume's tiles (WholeTiles)
 // ---- 1. count
 template <bool kSparse, int kLevel>
 __global__ __launch_bounds__(kMeshThreads) void k_mesh_count(Volume V, uint2* __restrict__ tile_cnt, uint8_t* __restrict__ tile_skip) {
-  __shared__ float s_f[kMeshCorners];
-  __shared__ uint32_t s_wave[kMeshWaves];
-  const LatticeOf<kLevel> L(V);
-  const MeshTile t = mesh_tile(L);
-  // the tile and its seven +x/+y/+z neighbours hold the clear value only (-limit: outside): no edge of this tile can cross the surface.  At a level the
-  // lattice tile's corners and the midpoints of its edges lie in storage tiles [t << level, (t << level) + (1 << level)] per axis: 27 / 125 lanes
-  constexpr uint32_t kN = (1u << kLevel) + 1u;
-  int mixed = 0;
-  if (threadIdx.x < kN * kN * kN) {
-    const int nx = (t.tx << kLevel) + (int)(threadIdx.x % kN), ny = (t.ty << kLevel) + (int)((threadIdx.x / kN) % kN), nz = (t.tz << kLevel) + (int)(threadIdx.x / (kN * kN));
-    if (nx < V.ntx && ny < V.nty && nz < V.tz1) {
-      const uint32_t id = (uint32_t)((nz * V.nty + ny) * V.ntx + nx);
-      mixed = kSparse ? V.slot[id] != kNoSlot : V.cls[id] != kTileMinus;
-    }
-  }
-  if (!__syncthreads_or(mixed)) {
-    if (threadIdx.x == 0) { tile_cnt[t.id] = make_uint2(0u, 0u); tile_skip[t.id] = 1; }
-    return;
-  }
-  mesh_stage<kSparse, kLevel>(V, L, t, s_f);
-  __syncthreads();
-  const MeshPoint p = mesh_point(L, t, s_f, threadIdx.x);
-  uint32_t total;
-  block_exclusive_sum<kMeshWaves>((uint32_t)__popc(p.mask) | (p.ntri << 16), s_wave, &total);   // both counts in one word: at most 3584 and 6144 per tile
-  if (threadIdx.x == 0) { tile_cnt[t.id] = make_uint2(total & 0xffffu, total >> 16); tile_skip[t.id] = 0; }
+  mesh_tile_count<kSparse, kLevel>(V, WholeTiles{}, tile_cnt, tile_skip);
 }
 
 // ---- 2. scan of the per-tile counts: block sums, scan of the block sums, add.  Four quantities: vertices, triangles, tiles with
@@ -150,131 +118,39 @@ __global__ __launch_bounds__(kScanThreads) void k_mesh_scan_apply(const uint2* _
 }
 
 // ---- 3. records and vertices
-// record of a lattice point: bits 0..6 edge mask, bit 7 inside, bits 8.. the offset of its first vertex inside the tile
 template <bool kSparse, int kLevel>
 __global__ __launch_bounds__(kMeshThreads) void k_mesh_vertices(Volume V, StreamTable T, FrameImages F, MeshGeometry G, const uint2* __restrict__ tile_cnt,
                                                                 const uint32_t* __restrict__ tile_vbase, const uint32_t* __restrict__ tile_rec, uint32_t* __restrict__ records,
                                                                 float* __restrict__ out_pos, float* __restrict__ out_nrm, float4* __restrict__ out_col) {
-  __shared__ float s_f[kMeshCorners];
-  __shared__ uint32_t s_wave[kMeshWaves];
-  __shared__ uint16_t s_edge[kMeshThreads * 7];                        // per vertex of the tile: lattice point << 3 | d
+  __shared__ MeshVertexStage s;
   const LatticeOf<kLevel> L(V);
-  const MeshTile t = mesh_tile(L);
+  const MeshTile t = mesh_tile(L, WholeTiles{});
   const uint32_t nv = tile_cnt[t.id].x;
-  if (nv == 0) return;
-  mesh_stage<kSparse, kLevel>(V, L, t, s_f);
-  __syncthreads();
-  const MeshPoint p = mesh_point(L, t, s_f, threadIdx.x);
-  uint32_t total;
-  const uint32_t off = block_exclusive_sum<kMeshWaves>((uint32_t)__popc(p.mask), s_wave, &total);
-  records[(size_t)tile_rec[t.id] * kMeshThreads + threadIdx.x] = p.mask | (p.inside << 7) | (off << 8);
-  {
-    uint32_t k = off;
-#pragma unroll
-    for (int d = 1; d < 8; ++d)
-      if (p.mask & (1u << (d - 1))) s_edge[k++] = (uint16_t)((threadIdx.x << 3) | d);
-  }
-  __syncthreads();
-  mesh_tile_vertices<kSparse, kLevel>(V, T, F, G, t, nv, s_f, s_edge, (size_t)tile_vbase[t.id], out_pos, out_nrm, out_col);
+  if (nv == 0 || !mesh_tile_records<kSparse, kLevel>(V, L, WholeTiles{}, t, tile_rec, records, s)) return;
+  mesh_tile_vertices<kSparse, kLevel>(V, T, F, G, t, nv, s.f, s.edge, (size_t)tile_vbase[t.id], out_pos, out_nrm, out_col);
 }
 
 // ... and the streamed form (tsdf_mesh_stream): the same records, then the tile's vertices quantised in registers and written with ONE 8- or 16-byte
-// store each (mesh_dev.hpp: mesh_tile_vertices_packed, shared with the slab parts' emit).  H is the frame's header in device memory
-// (k_mesh_stream_header): when a need exceeds its capacity every workgroup of both emit kernels returns before it reads anything else, so nothing is ever
-// written past a capacity.
+// store each (mesh_tile_vertices_packed).  H is the frame's header in device memory (k_mesh_stream_header): when a need exceeds its capacity every
+// workgroup of both emit kernels returns before it reads anything else, so nothing is ever written past a capacity.
 template <bool kSparse, uint32_t kFlags, int kLevel>
 __global__ __launch_bounds__(kMeshThreads, 4) void k_mesh_vertices_packed(Volume V, StreamTable T, FrameImages F, MeshGeometry G, const MeshStreamHeader* __restrict__ H,
                                                                           const uint2* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_vbase,
                                                                           const uint32_t* __restrict__ tile_rec, uint32_t* __restrict__ records, void* __restrict__ out) {
-  __shared__ float s_f[kMeshCorners];
-  __shared__ uint32_t s_wave[kMeshWaves];
-  __shared__ uint16_t s_edge[kMeshThreads * 7];                        // per vertex of the tile: lattice point << 3 | d
+  __shared__ MeshVertexStage s;
   const LatticeOf<kLevel> L(V);
-  const MeshTile t = mesh_tile(L);
+  const MeshTile t = mesh_tile(L, WholeTiles{});
   const uint32_t nv = tile_cnt[t.id].x;                                // (read beside the header, not behind it: one wait for both; tile_cnt is valid on overflow too)
-  if (mesh_stream_overflow(H) || nv == 0) return;
-  mesh_stage<kSparse, kLevel>(V, L, t, s_f);
-  __syncthreads();
-  const MeshPoint p = mesh_point(L, t, s_f, threadIdx.x);
-  uint32_t total;
-  const uint32_t off = block_exclusive_sum<kMeshWaves>((uint32_t)__popc(p.mask), s_wave, &total);
-  records[(size_t)tile_rec[t.id] * kMeshThreads + threadIdx.x] = p.mask | (p.inside << 7) | (off << 8);   // (tile_rec < needed_tiles <= max_tiles)
-  {
-    uint32_t k = off;
-#pragma unroll
-    for (int d = 1; d < 8; ++d)
-      if (p.mask & (1u << (d - 1))) s_edge[k++] = (uint16_t)((threadIdx.x << 3) | d);
-  }
-  __syncthreads();
-  mesh_tile_vertices_packed<kSparse, kFlags, kLevel>(V, T, F, G, t, nv, s_f, s_edge, (size_t)tile_vbase[t.id], out);   // (< needed_vertices <= max_vertices)
+  if (mesh_stream_overflow(H) || nv == 0 || !mesh_tile_records<kSparse, kLevel>(V, L, WholeTiles{}, t, tile_rec, records, s)) return;
+  mesh_tile_vertices_packed<kSparse, kFlags, kLevel>(V, T, F, G, t, nv, s.f, s.edge, (size_t)tile_vbase[t.id], out);   // (< needed_vertices <= max_vertices)
 }
 
-#ifndef RR_MESH_COMPACT_LDS
-#define RR_MESH_COMPACT_LDS 0                                          // 1: the measured alternative of the 6-byte rows' stores (below; DESIGN.md has both)
-#endif
-// ---- 4. triangles, from the records alone.  Out = uint16_t: the streamed tile-local corner codes (bits 0..11 the vertex's offset inside its owner
-// tile, bits 12..14 where that tile lies from this one: a corner whose local coordinate is 8 belongs to the +x / +y / +z neighbour) instead of mesh indices
-template <int kLevel, typename Out = uint32_t>
-__device__ __forceinline__ void mesh_tile_triangles(const Volume& V, const uint2* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_vbase,
-                                                    const unsigned long long* __restrict__ tile_tbase, const uint32_t* __restrict__ tile_rec,
-                                                    const uint32_t* __restrict__ records, Out* __restrict__ out_tri) {
-  constexpr bool kLocal = std::is_same<Out, uint16_t>::value;
-  __shared__ uint32_t s_first[kMeshCorners];                           // per corner: the mesh index of the first vertex it owns
-  __shared__ uint8_t s_mask[kMeshCorners];                             // ... and its record's low byte (edge mask, inside bit)
-  __shared__ uint32_t s_wave[kMeshWaves];
-  const LatticeOf<kLevel> L(V);
-  const MeshTile t = mesh_tile(L);
-  if (tile_cnt[t.id].y == 0) return;
-  for (int i = threadIdx.x; i < kMeshCorners; i += kMeshThreads) {
-    const int lx = i % 9, ly = (i / 9) % 9, lz = i / 81;
-    const int x = t.tx * 8 + lx, y = t.ty * 8 + ly, z = t.tz * 8 + lz;
-    uint32_t first = 0, mask = 0;
-    if (x < L.cr(0) && y < L.cr(1) && z < L.cr(2)) {
-      const int tile = ((z >> 3) * L.nty() + (y >> 3)) * L.ntx() + (x >> 3);
-      const uint32_t slot = tile_rec[tile];
-      if (slot != kNoSlot) {                                           // (a tile without surface owns no crossed edge: nothing is looked up in it)
-        const uint32_t r = records[(size_t)slot * kMeshThreads + (((z & 7) << 6) | ((y & 7) << 3) | (x & 7))];
-        if constexpr (kLocal) first = (r >> 8) | ((uint32_t)((lx >> 3) | ((ly >> 3) << 1) | ((lz >> 3) << 2)) << 12);
-        else first = tile_vbase[tile] + (r >> 8);
-        mask = r & 0xffu;
-      }
-    }
-    s_first[i] = first; s_mask[i] = (uint8_t)mask;
-  }
-  __syncthreads();
-  const int lx = threadIdx.x & 7, ly = (threadIdx.x >> 3) & 7, lz = threadIdx.x >> 6;
-  const int x = t.tx * 8 + lx, y = t.ty * 8 + ly, z = t.tz * 8 + lz;
-  // the cell's corner bits from its origin's record: corner b is inside iff the origin is, unless the edge origin -> b is crossed
-  uint32_t corners = 0, ntri = 0;
-  if (x + 1 < L.cr(0) && y + 1 < L.cr(1) && z + 1 < L.cr(2)) {
-    const uint32_t m = s_mask[corner_index(lx, ly, lz)];
-    corners = ((m & 0x7fu) << 1) ^ ((m & 0x80u) ? 0xffu : 0u);
-    ntri = cell_triangles(corners);
-  }
-  uint32_t total;
-  const uint32_t off = block_exclusive_sum<kMeshWaves>(ntri, s_wave, &total);
-  if constexpr (kLocal && RR_MESH_COMPACT_LDS) {
-    // The alternative: a tile's rows are contiguous, so they are staged in LDS at the destination's offset inside its 16-byte line and leave as
-    // aligned 16-byte stores, the ragged head and tail as shorts.
-    __shared__ __attribute__((aligned(16))) uint16_t s_rows[kMeshThreads * 12 * 3 + 8];
-    Out* __restrict__ g = out_tri + (size_t)tile_tbase[t.id] * 3;
-    const uint32_t shift = (uint32_t)(((size_t)g & 15u) >> 1), n16 = total * 3u;
-    if (ntri) mesh_cell_triangles(corners, s_first, s_mask, lx, ly, lz, s_rows + shift + off * 3u);
-    __syncthreads();
-    const uint32_t head = min(n16, (8u - shift) & 7u), body = (n16 - head) >> 3, tail = head + (body << 3);
-    for (uint32_t i = threadIdx.x; i < head; i += kMeshThreads) g[i] = s_rows[shift + i];
-    for (uint32_t i = threadIdx.x; i < body; i += kMeshThreads) ((uint4*)(g + head))[i] = ((const uint4*)(s_rows + shift + head))[i];
-    for (uint32_t i = tail + threadIdx.x; i < n16; i += kMeshThreads) g[i] = s_rows[shift + i];
-  } else {
-    if (ntri == 0) return;
-    mesh_cell_triangles(corners, s_first, s_mask, lx, ly, lz, out_tri + (size_t)(tile_tbase[t.id] + off) * 3);
-  }
-}
+// ---- 4. triangles, from the records alone
 template <int kLevel>
 __global__ __launch_bounds__(kMeshThreads) void k_mesh_triangles(Volume V, const uint2* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_vbase,
                                                                  const unsigned long long* __restrict__ tile_tbase, const uint32_t* __restrict__ tile_rec,
                                                                  const uint32_t* __restrict__ records, uint32_t* __restrict__ out_tri) {
-  mesh_tile_triangles<kLevel>(V, tile_cnt, tile_vbase, tile_tbase, tile_rec, records, out_tri);
+  mesh_tile_triangles<kLevel>(V, WholeTiles{}, tile_cnt, tile_vbase, tile_tbase, tile_rec, records, MeshSlabLink{}, out_tri);
 }
 // the streamed form: the triangle array follows the frame's vertices directly (payload + needed_vertices * stride: one copy takes both)
 template <int kLevel>
@@ -283,22 +159,23 @@ __global__ __launch_bounds__(kMeshThreads) void k_mesh_triangles_stream(Volume V
                                                                         const uint32_t* __restrict__ tile_rec, const uint32_t* __restrict__ records,
                                                                         uint8_t* __restrict__ payload, uint32_t stride) {
   if (mesh_stream_overflow(H)) return;
-  mesh_tile_triangles<kLevel>(V, tile_cnt, tile_vbase, tile_tbase, tile_rec, records, (uint32_t*)(payload + (size_t)H->needed_vertices * stride));
+  mesh_tile_triangles<kLevel>(V, WholeTiles{}, tile_cnt, tile_vbase, tile_tbase, tile_rec, records, MeshSlabLink{}, (uint32_t*)(payload + (size_t)H->needed_vertices * stride));
 }
-// The tile-local format (launch_mesh_stream_emit_compact): the tile table, one lane per lattice tile.  A tile with a vertex writes its row at its surface
-// ordinal (tile_rec: the rows are the surface tiles in tile order) as one 16-byte store; the row area begins at a multiple of 16 bytes -- in the payload
-// behind the vertices and their zero padding, or at raw_table (the filter's raw frame, whose payload is the uint32 one).  In a launch of its own: folded
-// into the triangle launch (lane 0 of a tile's workgroup) it measured slower at level 0.
+// The tile-local format (launch_mesh_stream_emit_compact, and a slab's part of it: launch_mesh_part_emit): the tile table, one lane per tile of the frame
+// -- the whole volume's n lattice tiles, or a part's n owned ones, the first of which is first_tile in the WHOLE level's grid (the two bases stay
+// part-local).  A tile with a vertex writes its row at its surface ordinal (tile_rec: the rows are the surface tiles in tile order) as one 16-byte store;
+// the row area begins at a multiple of 16 bytes -- in the payload behind the vertices and their zero padding, or at raw_table (the filter's raw frame, whose
+// payload is the uint32 one).  In a launch of its own: folded into the triangle launch (lane 0 of a tile's workgroup) it measured slower at level 0.
 __global__ __launch_bounds__(kScanThreads) void k_mesh_stream_table(const MeshStreamHeader* __restrict__ H, const uint2* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_vbase,
                                                                     const unsigned long long* __restrict__ tile_tbase, const uint32_t* __restrict__ tile_rec, int n,
-                                                                    uint8_t* __restrict__ payload, uint32_t stride, MeshTileRow* __restrict__ raw_table) {
+                                                                    uint32_t first_tile, uint8_t* __restrict__ payload, uint32_t stride, MeshTileRow* __restrict__ raw_table) {
   const int t = (int)(blockIdx.x * kScanThreads + threadIdx.x);
   if (mesh_stream_overflow(H) || t >= n) return;
   const size_t vertex_bytes = (size_t)H->needed_vertices * stride;
   if (!raw_table && t == 0 && (vertex_bytes & 8u)) *(uint2*)(payload + vertex_bytes) = make_uint2(0u, 0u);   // the padding
   const uint2 cnt = tile_cnt[t];
   if (cnt.x)                                                             // (tile_rec < needed_tiles <= max_tiles)
-    *(uint4*)((raw_table ? raw_table : mesh_stream_table(H, payload, stride)) + tile_rec[t]) = make_uint4((uint32_t)t, tile_vbase[t], (uint32_t)tile_tbase[t], cnt.y);
+    *(uint4*)((raw_table ? raw_table : mesh_stream_table(H, payload, stride)) + tile_rec[t]) = make_uint4(first_tile + (uint32_t)t, tile_vbase[t], (uint32_t)tile_tbase[t], cnt.y);
 }
 // ... and the 6-byte triangles, behind the vertices, the padding and the needed_tiles table rows -- all inside the slot, as none of the three needs exceeds
 // its capacity
@@ -308,17 +185,12 @@ __global__ __launch_bounds__(kMeshThreads) void k_mesh_triangles_stream_compact(
                                                                                 const uint32_t* __restrict__ tile_rec, const uint32_t* __restrict__ records,
                                                                                 uint8_t* __restrict__ payload, uint32_t stride) {
   if (mesh_stream_overflow(H)) return;
-  mesh_tile_triangles<kLevel, uint16_t>(V, tile_cnt, tile_vbase, tile_tbase, tile_rec, records, (uint16_t*)(mesh_stream_table(H, payload, stride) + H->needed_tiles));
+  mesh_tile_triangles<kLevel>(V, WholeTiles{}, tile_cnt, tile_vbase, tile_tbase, tile_rec, records, MeshSlabLink{}, (uint16_t*)(mesh_stream_table(H, payload, stride) + H->needed_tiles));
 }
 // one lane: the frame's header from the scan's totals (sums[nb]) and the ring's capacities
 __global__ void k_mesh_stream_header(const MeshSums* __restrict__ totals, MeshStreamHeader* __restrict__ H, uint32_t max_vertices, uint32_t max_triangles, uint32_t max_tiles) {
   const MeshSums s = *totals;
-  MeshStreamHeader h{};
-  h.needed_vertices = s.nv; h.needed_triangles = s.nt; h.needed_tiles = s.surface; h.tiles_skipped = s.skipped;
-  h.max_vertices = max_vertices; h.max_triangles = max_triangles; h.max_tiles = max_tiles;
-  h.overflow = (s.nv > max_vertices ? 1u : 0u) | (s.nt > max_triangles ? 2u : 0u) | (s.surface > max_tiles ? 4u : 0u);
-  h.n_vertices = h.overflow ? 0ull : s.nv; h.n_triangles = h.overflow ? 0ull : s.nt;
-  *H = h;
+  *H = mesh_stream_header(s.nv, s.nt, s.surface, s.skipped, max_vertices, max_triangles, max_tiles);
 }
 
 // ---- launchers.  S.level picks the instantiation; the caller has checked it (0 .. kMeshMaxLevel) and sized S by mesh_lattice(res, level).
@@ -350,24 +222,21 @@ void launch_mesh_emit(hipStream_t st, const Volume& V, const StreamTable& T, con
 void launch_mesh_stream_header(hipStream_t st, const MeshScratch& S, MeshStreamHeader* H, uint32_t max_vertices, uint32_t max_triangles, uint32_t max_tiles) {
   hipLaunchKernelGGL(k_mesh_stream_header, dim3(1), dim3(1), 0, st, (const MeshSums*)S.sums + mesh_scan_blocks(S.n_tiles), H, max_vertices, max_triangles, max_tiles);
 }
+void launch_mesh_stream_table(hipStream_t st, const MeshScratch& S, const MeshStreamHeader* H, int n, uint32_t first_tile, void* payload, uint32_t stride, MeshTileRow* raw_table) {
+  hipLaunchKernelGGL(k_mesh_stream_table, dim3((n + kScanThreads - 1) / kScanThreads), dim3(kScanThreads), 0, st, H, S.tile_cnt, S.tile_vbase, S.tile_tbase, S.tile_rec, n, first_tile,
+                     (uint8_t*)payload, stride, raw_table);
+}
 // compact: the tile-local format -- the same packed vertices (the same kernel), the table, then the 6-byte triangles, or, with raw_table (the filter's raw
 // frame), the uint32 triangles of the plain ring
 static void mesh_stream_emit(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S, uint32_t flags,
                              const MeshStreamHeader* H, uint32_t* records, void* payload, bool compact, MeshTileRow* raw_table) {
-  mesh_instantiation(V, S, [&](auto sparse, auto level) {
-    constexpr bool kSparse = decltype(sparse)::value;
+  mesh_packed_instantiation(V, S, flags, [&](auto sparse, auto level, auto vertex_flags) {
     constexpr int kLevel = decltype(level)::value;
     const dim3 g(S.n_tiles), b(kMeshThreads);
     const uint32_t stride = flags ? 16u : 8u;
-    switch (flags & 3u) {
-      case 0u: hipLaunchKernelGGL((k_mesh_vertices_packed<kSparse, 0u, kLevel>), g, b, 0, st, V, T, F, G, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
-      case 1u: hipLaunchKernelGGL((k_mesh_vertices_packed<kSparse, 1u, kLevel>), g, b, 0, st, V, T, F, G, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
-      case 2u: hipLaunchKernelGGL((k_mesh_vertices_packed<kSparse, 2u, kLevel>), g, b, 0, st, V, T, F, G, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
-      default: hipLaunchKernelGGL((k_mesh_vertices_packed<kSparse, 3u, kLevel>), g, b, 0, st, V, T, F, G, H, S.tile_cnt, S.tile_vbase, S.tile_rec, records, payload); break;
-    }
-    if (compact)
-      hipLaunchKernelGGL(k_mesh_stream_table, dim3((S.n_tiles + kScanThreads - 1) / kScanThreads), dim3(kScanThreads), 0, st, H, S.tile_cnt, S.tile_vbase, S.tile_tbase, S.tile_rec,
-                         S.n_tiles, (uint8_t*)payload, stride, raw_table);
+    hipLaunchKernelGGL((k_mesh_vertices_packed<decltype(sparse)::value, decltype(vertex_flags)::value, kLevel>), g, b, 0, st, V, T, F, G, H, S.tile_cnt, S.tile_vbase, S.tile_rec,
+                       records, payload);
+    if (compact) launch_mesh_stream_table(st, S, H, S.n_tiles, 0u, payload, stride, raw_table);
     if (compact && !raw_table) hipLaunchKernelGGL(k_mesh_triangles_stream_compact<kLevel>, g, b, 0, st, V, H, S.tile_cnt, S.tile_vbase, S.tile_tbase, S.tile_rec, records, (uint8_t*)payload, stride);
     else hipLaunchKernelGGL(k_mesh_triangles_stream<kLevel>, g, b, 0, st, V, H, S.tile_cnt, S.tile_vbase, S.tile_tbase, S.tile_rec, records, (uint8_t*)payload, stride);
   });

@@ -405,6 +405,8 @@ struct MeshTileRow { uint32_t tile, first_vertex, first_triangle, n_triangles; }
 static_assert(sizeof(MeshTileRow) == 16, "tsdf_mesh_tile_row");
 void launch_mesh_stream_emit_compact(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const MeshGeometry& G, const MeshScratch& S, uint32_t flags,
                                      const MeshStreamHeader* H, uint32_t* records, void* payload, MeshTileRow* raw_table);
+// ... its table launch alone: the rows of S's first n tiles, the first of them first_tile in the level's grid (k_mesh.hip; launch_mesh_part_emit uses it too)
+void launch_mesh_stream_table(hipStream_t st, const MeshScratch& S, const MeshStreamHeader* H, int n, uint32_t first_tile, void* payload, uint32_t stride, MeshTileRow* raw_table);
 // A Z-slab's part of the tile-local frame (k_mesh_slab.hip; the header's "mesh streaming: slab parts"): behind launch_mesh_slab_count and launch_mesh_scan
 // over B.n_own + B.n_seam tiles.  The header counts the OWNED tiles' vertices and surface tiles; what the seam tiles added to the scan's totals goes into the
 // 64-byte record in front of it (one copy takes both, as with the filter's record).  records: 512 words for each of max_tiles + B.n_seam tiles.

@@ -103,7 +103,51 @@ def test_kernel_file_is_built_and_its_tables_are_the_generated_ones():
     assert m and tuple(tuple(int(x) for x in g.split(",")) for g in re.findall(r"\{([\d, ]+)\}", m.group(1))) == M.TETS
     for name in ("k_mesh_slab_count", "k_mesh_slab_vertices", "k_mesh_slab_triangles"):
         assert name in src, name
-    assert "atomic" not in re.sub(r"//.*", "", src)                                          # no atomic decides a position
+    for name in MESH_SOURCES:                                                                # no atomic decides a position: the bodies are mesh_dev.hpp's
+        assert "atomic" not in mesh_code(name), name
+
+
+MESH_SOURCES = ("mesh_dev.hpp", "k_mesh.hip", "k_mesh_slab.hip")
+
+
+def mesh_code(name):
+    """a mesh source file without its comments"""
+    return re.sub(r"//.*", "", open(os.path.join(CSRC, name)).read())
+
+
+def test_every_mesh_stage_has_one_body_and_the_kernels_are_wrappers():
+    """The whole-volume and the slab-part kernels are instantiations of one body per stage (mesh_dev.hpp, on a tile policy).  A stage's identifying
+    line stands once in the three files, and a __global__ kernel of the two .hip files is a wrapper of at most six lines -- but for the kernels
+    that exist once for both forms and have no body to share: the table, the two headers and the scan's three."""
+    text = "".join(mesh_code(name) for name in MESH_SOURCES)
+    for line in ("in_layer - t.ty * L.ntx()",                          # the tile of a workgroup
+                 "mesh_voxel<kSparse>(V, x << kLevel, y << kLevel, z << kLevel)",   # the corner stage
+                 "__syncthreads_or(mixed)",                            # count
+                 "p.mask | (p.inside << 7) | (off << 8)",              # the record store
+                 "edge[k++] =",                                        # the tile's vertex list
+                 "upx + w * (uqx - upx)",                              # a vertex's unit-cube position
+                 "corners = ((m & 0x7fu) << 1)",                       # triangles
+                 "h.overflow =",                                       # the streamed header
+                 "make_uint4(first_tile + (uint32_t)t"):               # the tile table
+        assert text.count(line) == 1, (line, text.count(line))
+    whole = ("k_mesh_block_sums", "k_mesh_scan_sums", "k_mesh_scan_apply", "k_mesh_stream_table", "k_mesh_stream_header", "k_mesh_part_header")
+    seen = []
+    for name in ("k_mesh.hip", "k_mesh_slab.hip"):
+        src = mesh_code(name)
+        for m in re.finditer(r"__global__[^;{]*?\bvoid\s+(k_\w+)\s*\(", src):
+            depth, i = 1, m.end()
+            while depth:                                               # the end of the argument list ...
+                depth += {"(": 1, ")": -1}.get(src[i], 0); i += 1
+            start = src.index("{", i)
+            depth, i = 1, start + 1
+            while depth:                                               # ... and of the body
+                depth += {"{": 1, "}": -1}.get(src[i], 0); i += 1
+            body = [ln for ln in src[start + 1:i - 1].splitlines() if ln.strip()]
+            seen.append(m.group(1))
+            assert m.group(1) in whole or len(body) <= 6, (m.group(1), len(body))
+    for name in ("k_mesh_count", "k_mesh_vertices", "k_mesh_vertices_packed", "k_mesh_triangles", "k_mesh_triangles_stream", "k_mesh_triangles_stream_compact",
+                 "k_mesh_slab_count", "k_mesh_slab_vertices", "k_mesh_slab_triangles", "k_mesh_part_vertices_packed", "k_mesh_part_triangles") + whole:
+        assert seen.count(name) == 1, name
 
 
 def test_timing_tool_has_the_slab_option():
