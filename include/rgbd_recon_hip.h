@@ -1047,6 +1047,62 @@ int32_t tsdf_mesh_stream_config_part(tsdf_ctx* ctx, uint32_t flags, uint32_t lev
                                      uint32_t slots);
 int32_t tsdf_mesh_stream_frame_part(tsdf_ctx* ctx, tsdf_mesh_part* out);   /* of the frame currently HELD */
 
+/* ---- mesh streaming: texture taps in the frame -------------------------------------------------------------
+ * A streamed frame carries one blendColors colour per vertex: voxel resolution.  With TSDF_MESH_STREAM_TAPS every frame of the ring also carries, per
+ * vertex and stream, the texture tap of "texture taps" above, packed to 8 bytes, so that a receiver that has the colour images textures the streamed
+ * mesh at camera resolution by plain projective texturing -- without a second, unpacked mesh and without the calibration volumes.  One pass serves
+ * every form of the ring (uint32 indices, level of detail, filtered, tile-local compact, slab parts).  No counterpart in the reference.
+ * tests/mesh_tap_pack_reference.py restates packing and pass in numpy on top of tests/texture_tap_reference.py and tests/mesh_pack_reference.py; device
+ * and numpy agree byte for byte.
+ *
+ * The point.  A streamed vertex carries its position as three uint16 codes q (bytes 0-5 of the packed vertex, at either stride).  The taps of a streamed
+ *   vertex are taken at the position the RECEIVER reconstructs from those codes, not at the emit kernel's fp32 u: per axis u_q = (float) q / 65535.0f,
+ *   one fp32 division, used as a unit-cube coordinate.  The pass therefore reads the frame's final packed rows (after the filter's scatter where there
+ *   is one), needs nothing from the emit, and the receiver can check it.  u_q is at most half a code step, 0.5 / 65535 of the extent per axis, from the
+ *   vertex's u.  At a depth discontinuity that is enough to flip dist < limit, or the nearest depth pixel, for a stream.  Measured with the numpy
+ *   reference on the "3-streams" scene of tests/test_gpu_texture_taps.py at 37 x 43 x 35, 5 108 vertices: the receiver's rule on taps at u_q against
+ *   taps at the exact u differs by 0.027 / 255 in the mean colour and by 22.7 / 255 at the worst single vertex; the branch (alpha) is the same at every
+ *   vertex.  So no per-vertex closeness to the vertex colour is claimed: the caveat tsdf_mesh_texture_taps states already.
+ * The values.  Per stream i, in stream order, exactly the four values of tsdf_texture_tap at the unit-cube point u_q by the definition of "texture
+ *   taps": pc, pcol, the NEAREST depth, dist, quality gated by dist < limit; the frame slot is the one current at the tsdf_mesh_stream call.  u_q lies in
+ *   [0, 1], so every pair is evaluated: the not-evaluated record cannot occur.
+ * The packed tap, tsdf_packed_tap, 8 bytes, little endian: the fp32 tap at 16 bits a field.
+ *   bytes 0-1, 2-3  u, v as uint16: (uint16) rint(min(max(x, 0), 1) * 65535.0f) -- the position's rule: the product in fp32, half-way cases to even; a
+ *                   NaN coordinate packs as 0.  Clamping the coordinate to [0, 1] does not change a LINEAR, CLAMP_TO_EDGE fetch: outside [0, 1] both
+ *                   texels of an axis are the edge texel, as they are at 0 and at 1 (for every coordinate whose product with the image size is finite).
+ *   bytes 4-5, 6-7  quality, dist as IEEE binary16: converted from fp32 with round to nearest even, overflow to +-inf, binary16 subnormals kept, every
+ *                   NaN 0x7E00.  (numpy's astype(float16) is this rule for every value that is not a NaN.)
+ * Layout.  [n_vertices][N], vertex-major, N = num_streams, 8 * N bytes per vertex, in the order of the frame's vertices: of a filtered frame the
+ *   FILTERED vertices, of a part the part's vertices.  Parts therefore join by concatenation, like the vertices.
+ * The receiver's rule is unchanged: unpack with u = code / 65535.0f for the coordinates and the halfs widened to fp32 for the weights, then the rule of
+ *   "texture taps" (blend_from_taps in the binding serves as it is).
+ * Where the block lives.  At a fixed place in the slot, behind the payload's CAPACITY: align16(payload capacity of max_vertices, max_triangles,
+ *   max_surface_tiles) bytes behind the payload's first byte, max_vertices * N * 8 bytes long.  It travels in a copy of its own, of exactly
+ *   n_vertices * N * 8 bytes, queued with the payload copy.  The payload's layout, its single exact-size copy and tsdf_mesh_frame do not change.  The
+ *   4 GiB bound of a configuration applies to the slot including this block (header, payload capacity, padding, block).
+ *
+ * tsdf_mesh_stream_config_taps amends the current configuration, after any of the five config entries: TSDF_MESH_STREAM_TAPS turns the block on, 0 turns
+ *   it off.  Every tsdf_mesh_stream_config* call resets it to off, so the five entries mean exactly what they meant.  A change of the flag drops slots
+ *   already allocated, as a re-config does; the next tsdf_mesh_stream allocates again.  tsdf_mesh_stream_tap_flags reports the flag.
+ * tsdf_mesh_stream with the flag on needs calibration (cv_xyz_inv, cv_uv) of every stream and a frame, whatever the vertex flags, and takes the lane
+ *   ahead as a stream dependency, as a coloured frame does; it never waits for the host and allocates nothing after the first call.  One more launch per
+ *   frame, sized by max_vertices, which reads n_vertices from the slot's header on the device: behind the emit, on a filtered ring behind the final
+ *   header (whose copy does not wait for it).  A frame that overflowed or is empty has no tap bytes.  It works on a Z-slab context through a part ring: a
+ *   slab holds whole LUTs and frames.  A ring without the flag queues exactly the launches and copies it queued before.
+ * tsdf_mesh_stream_frame_taps fills *out for the frame currently HELD: taps points into the slot's pinned buffer and is valid until the release;
+ *   n_streams = N, tap_bytes = 8.  taps is non-NULL and n_vertices 0 for a held frame without vertices.
+ * tsdf_mesh_stream_stats: out[2] counts the tap bytes copied too, out[3] the larger slots.  Timer "mesh_stream_taps".
+ * Errors.  tsdf_mesh_stream_config_taps: TSDF_ERR_STATE before any config and while frames are queued or held (the rule of the config entries);
+ *   TSDF_ERR_INVALID_ARGUMENT for any other bit, and when the slot with the block exceeds 4 GiB (the flag stays as it was).  tsdf_mesh_stream:
+ *   TSDF_ERR_STATE without calibration or a frame, nothing queued.  tsdf_mesh_stream_frame_taps: TSDF_ERR_STATE when no frame is held or the ring has
+ *   no taps; TSDF_ERR_INVALID_ARGUMENT for a NULL out.  tsdf_set_voxel_size and tsdf_destroy: the ring's rules. */
+#define TSDF_MESH_STREAM_TAPS 1u
+typedef struct tsdf_packed_tap { uint16_t u, v, quality_h, dist_h; } tsdf_packed_tap;   /* 8 bytes */
+typedef struct tsdf_mesh_taps { const tsdf_packed_tap* taps; uint64_t n_vertices; uint32_t n_streams, tap_bytes; } tsdf_mesh_taps;   /* 24 bytes */
+int32_t tsdf_mesh_stream_config_taps(tsdf_ctx* ctx, uint32_t tap_flags);
+int32_t tsdf_mesh_stream_tap_flags(tsdf_ctx* ctx, uint32_t* tap_flags);
+int32_t tsdf_mesh_stream_frame_taps(tsdf_ctx* ctx, tsdf_mesh_taps* out);   /* of the frame currently HELD */
+
 /* ---- frame read-out: the swap ------------------------------------------------------------------------
  * The client ends a frame with glfwSwapBuffers (source/kinect_client.cpp:533): an RGBA8 window goes to a display (GLFW's default framebuffer has 8
  * bits per channel and the client sets no window hint that changes it, :942-951).  This device has no display; tsdf_present is the swap for a host

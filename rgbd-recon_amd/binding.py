@@ -244,6 +244,9 @@ def join_mesh_parts(parts):
     info = dict(first, n_vertices=nv, n_triangles=nt, needed_vertices=nv, needed_triangles=nt, needed_tiles=sum(len(r) for r in rows), overflow=0,
                 compact=dict(first["compact"], table=np.concatenate(rows)),
                 part=dict(layers=(first["part"]["layers"][0], parts[-1][2]["part"]["layers"][1]), level=first["part"]["level"], top=parts[-1][2]["part"]["top"], seam_tiles=parts[-1][2]["part"]["seam_tiles"]))
+    info.pop("taps", None)
+    if all("taps" in p[2] for p in parts):                               # ("texture taps in the frame": the parts' blocks join by concatenation, like the vertices)
+        info["taps"] = np.concatenate([np.ascontiguousarray(p[2]["taps"], PACKED_TAP_DTYPE).view(np.uint64) for p in parts]).view(PACKED_TAP_DTYPE)   # ([V_k][N] each, joined as 8-byte words; a part without a vertex adds nothing)
     return np.concatenate([p[0] for p in parts]), np.concatenate([np.asarray(p[1], np.uint16).reshape(-1, 3) for p in parts]), info
 
 
@@ -313,6 +316,35 @@ class SensorTap(C.Structure):
 # the same two records as numpy dtypes: what texture_taps / mesh_texture_taps return, [points][streams]
 TEXTURE_TAP_DTYPE = np.dtype([("u", np.float32), ("v", np.float32), ("quality", np.float32), ("dist", np.float32)])
 SENSOR_TAP_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("z", np.float32), ("depth", np.float32)])
+
+
+MESH_STREAM_TAPS = 1   # tsdf_mesh_stream_config_taps: tap_flags
+
+
+class PackedTap(C.Structure):
+    """tsdf_packed_tap of rgbd_recon_hip.h"""
+    _fields_ = [("u", C.c_uint16), ("v", C.c_uint16), ("quality_h", C.c_uint16), ("dist_h", C.c_uint16)]
+
+
+class MeshTaps(C.Structure):
+    """tsdf_mesh_taps of rgbd_recon_hip.h"""
+    _fields_ = [("taps", C.c_void_p), ("n_vertices", C.c_uint64), ("n_streams", C.c_uint32), ("tap_bytes", C.c_uint32)]
+
+
+PACKED_TAP_DTYPE = np.dtype([("u", "<u2"), ("v", "<u2"), ("quality_h", "<u2"), ("dist_h", "<u2")])   # a streamed frame's tap block, [vertices][streams]
+
+
+def unpack_mesh_taps(packed):
+    """the receiver's unpacking of a streamed frame's tap block (the header's "mesh streaming: texture taps in the frame"): PACKED_TAP_DTYPE [V][N] ->
+    TEXTURE_TAP_DTYPE [V][N] in float32, u = code / 65535.0f and the binary16 weights widened; blend_from_taps takes the result as it is"""
+    packed = np.asarray(packed)
+    assert packed.dtype == PACKED_TAP_DTYPE
+    out = np.zeros(packed.shape, TEXTURE_TAP_DTYPE)
+    out["u"] = packed["u"].astype(np.float32) / np.float32(65535.0)
+    out["v"] = packed["v"].astype(np.float32) / np.float32(65535.0)
+    out["quality"] = np.ascontiguousarray(packed["quality_h"]).view(np.float16).astype(np.float32)
+    out["dist"] = np.ascontiguousarray(packed["dist_h"]).view(np.float16).astype(np.float32)
+    return out
 
 
 def _axis_linear(u, n):
@@ -930,14 +962,15 @@ class ReconIntegrationHip:
 
     # ------------------------------------------------------------------ mesh streaming (no counterpart in the reference)
     def mesh_stream_config(self, normals=False, colours=False, max_vertices=1 << 20, max_triangles=1 << 21, max_surface_tiles=1 << 14, slots=3, level=0,
-                           min_triangles=0, index_format=0, part=False):
+                           min_triangles=0, index_format=0, part=False, taps=False):
         """flags, the three capacities and the slot count of the mesh ring (tsdf_mesh_stream_config); the first mesh_stream after it allocates.
         level 1 / 2 (tsdf_mesh_stream_config_lod): every frame is that level's mesh, max_surface_tiles counts its 8^3 lattice tiles.
         min_triangles >= 1 (tsdf_mesh_stream_config_filter): every frame leaves the device without its components of fewer triangles; n_* in a frame's
         info are the filtered counts, needed_* and the capacities those of the unfiltered mesh.
         index_format MESH_INDEX_TILE16 (tsdf_mesh_stream_config_compact): 6-byte tile-local triangles and a tile table instead of uint32 indices.
         part=True (tsdf_mesh_stream_config_part): every frame is this context's PART of the tile-local frame -- the one ring a Z-slab context streams
-        through; the capacities are per part, join_mesh_parts joins the slabs' frames.  It has no filter and no uint32 form (ValueError)."""
+        through; the capacities are per part, join_mesh_parts joins the slabs' frames.  It has no filter and no uint32 form (ValueError).
+        taps=True (tsdf_mesh_stream_config_taps, called after the config): every frame carries its packed texture taps, PACKED_TAP_DTYPE [V][N]."""
         flags = (MESH_NORMALS if normals else 0) | (MESH_COLOURS if colours else 0)
         caps = (C.c_uint32(int(max_vertices)), C.c_uint32(int(max_triangles)), C.c_uint32(int(max_surface_tiles)), C.c_uint32(int(slots)))
         if part:
@@ -955,6 +988,31 @@ class ReconIntegrationHip:
             self._ck(self._L.tsdf_mesh_stream_config(self._c, C.c_uint32(flags), *caps))
         self._mesh_stream_filtered = bool(min_triangles)                 # (behind the checks: a refused config leaves the ring as it was)
         self._mesh_stream_part = bool(part)
+        self._mesh_stream_taps = False                                   # (every config entry turns the taps off)
+        if taps:
+            self.mesh_stream_config_taps(True)
+
+    def mesh_stream_config_taps(self, taps=True):
+        """turn the tap block of the current mesh ring configuration on or off (tsdf_mesh_stream_config_taps; `taps` may be the raw flag word)"""
+        self._ck(self._L.tsdf_mesh_stream_config_taps(self._c, C.c_uint32(MESH_STREAM_TAPS if taps is True else int(taps))))
+        self._mesh_stream_taps = bool(taps)
+
+    def mesh_stream_tap_flags(self):
+        """the tap flags of the mesh ring (tsdf_mesh_stream_tap_flags): MESH_STREAM_TAPS or 0"""
+        flags = C.c_uint32()
+        self._ck(self._L.tsdf_mesh_stream_tap_flags(self._c, C.byref(flags)))
+        return int(flags.value)
+
+    def mesh_stream_frame_taps(self):
+        """the packed texture taps of the frame held now (tsdf_mesh_stream_frame_taps): a VIEW of the slot's pinned buffer, PACKED_TAP_DTYPE [V][N];
+        TsdfError, code -4, when no frame is held or the ring carries no taps"""
+        m = MeshTaps()
+        self._ck(self._L.tsdf_mesh_stream_frame_taps(self._c, C.byref(m)))
+        nv, n = int(m.n_vertices), int(m.n_streams)
+        assert m.taps and int(m.tap_bytes) == PACKED_TAP_DTYPE.itemsize
+        if not nv:
+            return np.zeros((0, n), PACKED_TAP_DTYPE)
+        return np.ctypeslib.as_array(C.cast(m.taps, C.POINTER(C.c_uint16)), shape=(nv * n, 4)).view(PACKED_TAP_DTYPE).reshape(nv, n)
 
     def mesh_stream_frame_part(self):
         """dict: layers (L0, L1), level, top, seam_tiles of the frame held now (tsdf_mesh_stream_frame_part); TsdfError, code -4, when no frame is held
@@ -1032,7 +1090,8 @@ class ReconIntegrationHip:
 
     def mesh_stream_take(self, wait=True):
         """acquire, COPY, release: (vertices, triangles, info) as numpy arrays of the caller's own, or None (wait=False, frame not complete).
-        With a filter configured info["filter"] is the frame's mesh_stream_frame_filter(), on a part ring info["part"] its mesh_stream_frame_part()."""
+        With a filter configured info["filter"] is the frame's mesh_stream_frame_filter(), on a part ring info["part"] its mesh_stream_frame_part(),
+        with taps configured info["taps"] a copy of its mesh_stream_frame_taps()."""
         got = self.mesh_stream_acquire(wait)
         if got is None:
             return None
@@ -1043,11 +1102,15 @@ class ReconIntegrationHip:
             out[2]["filter"] = self.mesh_stream_frame_filter()
         if getattr(self, "_mesh_stream_part", False):
             out[2]["part"] = self.mesh_stream_frame_part()
+        if getattr(self, "_mesh_stream_taps", False):
+            # (copied as 8-byte words: numpy copies a structured array record by record, 20 times slower than the words -- 35 ms for c2's 6.7 M taps)
+            out[2]["taps"] = self.mesh_stream_frame_taps().view(np.uint64).copy().view(PACKED_TAP_DTYPE)
         self.mesh_stream_release()
         return out
 
     def mesh_stream_stats(self):
-        """dict: frames (queued since the config), overflowed, payload_bytes (copied to the host, headers not counted), device_bytes (held)"""
+        """dict: frames (queued since the config), overflowed, payload_bytes (copied to the host, tap blocks included, headers not counted),
+        device_bytes (held)"""
         out = (C.c_uint64 * 4)()
         self._ck(self._L.tsdf_mesh_stream_stats(self._c, out))
         return dict(frames=int(out[0]), overflowed=int(out[1]), payload_bytes=int(out[2]), device_bytes=int(out[3]))

@@ -702,7 +702,7 @@ void release_mesh_stream(tsdf_ctx* c) {
   for (auto& S : R.slot) {
     if (S.dev) hipFree(S.dev - S.lead);
     if (S.host) hipHostFree(S.host - S.lead);
-    for (hipEvent_t e : {S.header_written, S.emitted, S.header_ready, S.ready}) if (e) hipEventDestroy(e);
+    for (hipEvent_t e : {S.header_written, S.emitted, S.header_ready, S.ready, S.taps_written}) if (e) hipEventDestroy(e);
     S = tsdf_ctx::MeshStreamSlot{};
   }
   mesh_scratch_free(R.scratch, R.records);
@@ -2864,6 +2864,7 @@ int32_t tsdf_mesh_component_stats(tsdf_ctx* c, uint64_t out[4]) {
 
 // ---- mesh streaming (the definition is in the header): the same mesh every frame, packed, without a host wait or an allocation after the first call
 static size_t mesh_stream_payload_capacity(const tsdf_ctx::MeshStream& R) { return (size_t)R.layout().payload_capacity(R.max_vertices, R.max_triangles, R.max_tiles); }
+static size_t mesh_stream_tap_offset(const tsdf_ctx::MeshStream& R) { return (size_t)R.layout().tap_offset(R.max_vertices, R.max_triangles, R.max_tiles); }
 int32_t tsdf_mesh_stream_config(tsdf_ctx* c, uint32_t flags, uint32_t max_vertices, uint32_t max_triangles, uint32_t max_surface_tiles, uint32_t slots) {
   return tsdf_mesh_stream_config_lod(c, flags, 0u, max_vertices, max_triangles, max_surface_tiles, slots);
 }
@@ -2893,6 +2894,7 @@ static int32_t mesh_stream_configure(tsdf_ctx* c, uint32_t flags, uint32_t level
   if (R.allocated) HIP_TRY(c, hipStreamSynchronize(c->stream));
   release_mesh_stream(c);
   R.flags = flags; R.level = level; R.max_vertices = max_vertices; R.max_triangles = max_triangles; R.max_tiles = max_surface_tiles; R.min_triangles = min_triangles; R.index_format = index_format; R.part = part; R.ring.configure(slots); R.configured = true;
+  R.tap_flags = 0;                                                       // (every config entry means what it meant: tsdf_mesh_stream_config_taps amends it)
   R.frames = R.overflowed = R.bytes_copied = 0;
   return TSDF_OK;
 }
@@ -2924,6 +2926,29 @@ int32_t tsdf_mesh_stream_index_format(tsdf_ctx* c, uint32_t* index_format) {
   if (!index_format) return TSDF_ERR_INVALID_ARGUMENT;
   if (!c->mstream.configured) FAIL(c, TSDF_ERR_STATE, "tsdf_mesh_stream_index_format before tsdf_mesh_stream_config");
   *index_format = c->mstream.index_format;
+  return TSDF_OK;
+}
+// "mesh streaming: texture taps in the frame": amends the current configuration; a change drops the slots as a config does (they are sized with the block)
+int32_t tsdf_mesh_stream_config_taps(tsdf_ctx* c, uint32_t tap_flags) {
+  CHECK_CTX(c);
+  tsdf_ctx::MeshStream& R = c->mstream;
+  if (!R.configured) FAIL(c, TSDF_ERR_STATE, "tsdf_mesh_stream_config_taps before tsdf_mesh_stream_config");
+  if (tap_flags & ~kMeshStreamTaps) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "mesh stream tap flags %u (1: packed texture taps behind every frame)", tap_flags);
+  if (!R.ring.idle()) FAIL(c, TSDF_ERR_STATE, "%u streamed mesh frame(s) are queued or held: acquire and release them first", R.ring.count);
+  if (tap_flags && !R.layout().fits_taps(R.max_vertices, R.max_triangles, R.max_tiles, c->cfg.num_streams))
+    FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "a mesh stream slot of more than 4 GiB with the taps of %u vertices and %u streams", R.max_vertices, c->cfg.num_streams);
+  if (tap_flags == R.tap_flags) return TSDF_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (R.allocated) HIP_TRY(c, hipStreamSynchronize(c->stream));         // (as a config: launches of frames without payload may still be queued)
+  release_mesh_stream(c);
+  R.tap_flags = tap_flags;
+  return TSDF_OK;
+}
+int32_t tsdf_mesh_stream_tap_flags(tsdf_ctx* c, uint32_t* tap_flags) {
+  CHECK_CTX(c);
+  if (!tap_flags) return TSDF_ERR_INVALID_ARGUMENT;
+  if (!c->mstream.configured) FAIL(c, TSDF_ERR_STATE, "tsdf_mesh_stream_tap_flags before tsdf_mesh_stream_config");
+  *tap_flags = c->mstream.tap_flags;
   return TSDF_OK;
 }
 // the filter's raw buffer and scratch (min_triangles >= 1): sized by the capacities, like everything the filter launches
@@ -2964,7 +2989,10 @@ static int32_t mesh_stream_allocate(tsdf_ctx* c) {
     record_slots = (size_t)P.record_slots(R.max_tiles, per_layer);
   }
   const size_t lead = R.min_triangles ? sizeof(MeshStreamFilterRecord) : R.part ? sizeof(MeshStreamPartRecord) : 0,
-               slot_bytes = lead + sizeof(MeshStreamHeader) + mesh_stream_payload_capacity(R), record_bytes = record_slots * 512 * sizeof(uint32_t);
+               // with taps a slot ends with their block (the filter's raw buffer needs none: taps are taken from the slot, after the scatter)
+               slot_bytes = lead + (R.tap_flags ? (size_t)R.layout().slot_bytes_taps(R.max_vertices, R.max_triangles, R.max_tiles, c->cfg.num_streams)
+                                                : sizeof(MeshStreamHeader) + mesh_stream_payload_capacity(R)),
+               record_bytes = record_slots * 512 * sizeof(uint32_t);
   uint64_t bytes = (uint64_t)R.ring.slots * slot_bytes + record_bytes;
   bool ok = mesh_scratch_allocate(R.scratch, (int)n_tiles, (int)R.level, &bytes) == hipSuccess && hipMalloc((void**)&R.records, record_bytes) == hipSuccess;
   if (ok && R.min_triangles) ok = mesh_stream_filter_allocate(R, c->vol.res, &bytes);
@@ -2975,6 +3003,7 @@ static int32_t mesh_stream_allocate(tsdf_ctx* c) {
     ok = ok && hipHostMalloc((void**)&S.host, slot_bytes, hipHostMallocDefault) == hipSuccess;
     if (ok) S.host += lead;
     for (hipEvent_t* e : {&S.header_written, &S.emitted, &S.header_ready, &S.ready}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+    if (R.tap_flags) ok = ok && hipEventCreateWithFlags(&S.taps_written, hipEventDisableTiming) == hipSuccess;
   }
   if (ok) ok = ensure_copy_stream(c) == TSDF_OK;
   if (!ok) { (void)hipGetLastError(); release_mesh_stream(c); FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "no memory for %u mesh stream slots of %zu bytes and the scratch of %zu tiles", R.ring.slots, slot_bytes, n_tiles); }
@@ -2997,16 +3026,36 @@ static int32_t mesh_stream_pump(tsdf_ctx* c) {
     if (R.index_format == kMeshIndexTile16 && H->n_vertices)               // (an overflowed or emptied frame has no row)
       S.table_rows = R.min_triangles ? ((const MeshStreamFilterRecord*)(S.host - S.lead))->table_rows : H->needed_tiles;
     S.payload_bytes = (size_t)R.layout().payload_bytes(H->n_vertices, H->n_triangles, S.table_rows);
+    S.tap_bytes = R.tap_flags ? (size_t)MeshFrameLayout::tap_bytes(H->n_vertices, c->cfg.num_streams) : 0;   // (no vertex: no payload and no tap)
     if (S.payload_bytes) {
       HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, S.emitted, 0));
       HIP_TRY(c, hipMemcpyAsync(S.host + sizeof(MeshStreamHeader), S.dev + sizeof(MeshStreamHeader), S.payload_bytes, hipMemcpyDeviceToHost, c->copy_stream));
+      if (S.tap_bytes) {                                                 // the tap block: a copy of its own, of exactly the frame's bytes, from its fixed place
+        const size_t at = sizeof(MeshStreamHeader) + mesh_stream_tap_offset(R);
+        HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, S.taps_written, 0));
+        HIP_TRY(c, hipMemcpyAsync(S.host + at, S.dev + at, S.tap_bytes, hipMemcpyDeviceToHost, c->copy_stream));
+      }
       HIP_TRY(c, hipEventRecord(S.ready, c->copy_stream));
     }
     S.payload_issued = true;                                             // (the counters move with it: a call that failed above repeats the slot without counting it twice)
     if (H->overflow) ++R.overflowed;
-    R.bytes_copied += S.payload_bytes;
+    R.bytes_copied += S.payload_bytes + S.tap_bytes;
   }
   return TSDF_OK;
+}
+// The packed taps of the frame in slot S ("mesh streaming: texture taps in the frame"): one launch behind the last launch that writes the slot's packed
+// vertices and behind the header that holds the final n_vertices, which the kernel reads on the device.  It reads LUTs and the current frame slot's
+// images (join_pre was taken with the frame's first launch), no volume.  The upload that overwrites that frame slot two frames later waits for the lane
+// ahead's gate, which the context's stream records behind this launch; draw_done[set] is recorded again behind it, as tsdf_texture_taps_dev does.
+static int32_t mesh_stream_queue_taps(tsdf_ctx* c, tsdf_ctx::MeshStreamSlot& S) {
+  const tsdf_ctx::MeshStream& R = c->mstream;
+  timer_begin(c, "mesh_stream_taps");
+  launch_mesh_stream_taps(c->stream, c->luts, c->frame, c->vol.limit, (const MeshStreamHeader*)S.dev, S.dev + sizeof(MeshStreamHeader), R.flags ? 16u : 8u, R.max_vertices,
+                          S.dev + sizeof(MeshStreamHeader) + mesh_stream_tap_offset(R));
+  timer_end(c, "mesh_stream_taps");
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipEventRecord(S.taps_written, c->stream));
+  return overlay_rerecord_draw(c);
 }
 // A filtered frame behind its raw header: emit into the raw buffer, the filter into the slot, the slot's final header, and only then the header's copy.
 // draw_done is recorded again right behind the emit: the filter reads no volume, a later integrate() does not wait for it.
@@ -3030,6 +3079,7 @@ static int32_t mesh_stream_filtered_tail(tsdf_ctx* c, tsdf_ctx::MeshStreamSlot& 
   HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, S.header_written, 0));
   HIP_TRY(c, hipMemcpyAsync(S.host - S.lead, S.dev - S.lead, S.lead + sizeof(MeshStreamHeader), hipMemcpyDeviceToHost, c->copy_stream));
   HIP_TRY(c, hipEventRecord(S.header_ready, c->copy_stream));
+  if (R.tap_flags) if (int32_t rc = mesh_stream_queue_taps(c, S)) return rc;   // behind the final header; the header's copy does not wait for it
   ++R.frames;
   return TSDF_OK;
 }
@@ -3045,12 +3095,13 @@ int32_t tsdf_mesh_stream(tsdf_ctx* c, uint64_t tag) {
     if ((R.flags & TSDF_MESH_COLOURS) && (rc = require_inputs(c, false, true))) return rc;
     if (c->vol.own_tz1 != (c->res[2] + 7) / 8 && c->vol.tz1 - c->vol.own_tz1 < 1) FAIL(c, TSDF_ERR_STATE, "the slab stores no halo layer above its planes");
   }
+  if (R.tap_flags && (rc = require_inputs(c, false, true))) return rc;   // taps: calibration (cv_xyz_inv, cv_uv) and a frame, whatever the vertex flags
   if (R.ring.full()) FAIL(c, TSDF_ERR_STATE, "all %u mesh stream slots are queued or held (tsdf_mesh_stream_acquire / tsdf_mesh_stream_release)", R.ring.slots);
   HIP_TRY(c, hipSetDevice(c->device));
   if (!R.allocated && (rc = mesh_stream_allocate(c))) return rc;
   if ((rc = mesh_stream_pump(c))) return rc;
   tsdf_ctx::MeshStreamSlot& S = R.slot[R.ring.push()];                   // (queued before its calls are: result_paths.hpp's transitions precede what acts on them)
-  S.tag = tag; S.payload_issued = false; S.payload_bytes = 0; S.table_rows = 0;
+  S.tag = tag; S.payload_issued = false; S.payload_bytes = 0; S.table_rows = 0; S.tap_bytes = 0;
   for (int a = 0; a < 3; ++a) S.res[a] = c->res[a];
   const bool filtered = R.min_triangles != 0;
   MeshStreamHeader* H = filtered ? R.filter.raw : (MeshStreamHeader*)S.dev;   // with a filter: count, scan, header and emit write the raw buffer, not the slot
@@ -3059,7 +3110,7 @@ int32_t tsdf_mesh_stream(tsdf_ctx* c, uint64_t tag) {
   const bool cells = L.cr[0] >= 2 && L.cr[1] >= 2 && L.cr[2] >= 2;       // (a lattice one point thick has no cell)
   if (cells) {
     HIP_TRY(c, join_integ(c));                                           // the volume tsdf_download_volume would return now
-    if (R.flags & TSDF_MESH_COLOURS) HIP_TRY(c, join_pre(c));            // ... and the current frame slot's images
+    if ((R.flags & TSDF_MESH_COLOURS) || R.tap_flags) HIP_TRY(c, join_pre(c));   // ... and the current frame slot's images
     timer_begin(c, "mesh_stream_count");
     if (R.part) launch_mesh_slab_count(c->stream, V, R.scratch, R.slab); else launch_mesh_count(c->stream, V, R.scratch);
     timer_end(c, "mesh_stream_count");
@@ -3086,6 +3137,7 @@ int32_t tsdf_mesh_stream(tsdf_ctx* c, uint64_t tag) {
     // With the volume sets alternating, the integrate() two frames later overwrites the set these launches read, and it waits for draw_done[set] only:
     // record that event again behind them (as an overlay does).
     if ((rc = overlay_rerecord_draw(c))) return rc;
+    if (R.tap_flags && (rc = mesh_stream_queue_taps(c, S))) return rc;   // behind the emit (the header was written and its copy queued before it)
   }
   ++R.frames;
   return TSDF_OK;
@@ -3169,6 +3221,18 @@ int32_t tsdf_mesh_stream_frame_part(tsdf_ctx* c, tsdf_mesh_part* out) {
   *out = tsdf_mesh_part{};
   out->layers[0] = (uint32_t)P.layer0; out->layers[1] = (uint32_t)P.layer1; out->level = R.level; out->top = P.top ? 1u : 0u;
   out->seam_tiles = (uint32_t)((const MeshStreamPartRecord*)(S.host - S.lead))->seam_tiles;
+  return TSDF_OK;
+}
+int32_t tsdf_mesh_stream_frame_taps(tsdf_ctx* c, tsdf_mesh_taps* out) {
+  CHECK_CTX(c);
+  if (!out) return TSDF_ERR_INVALID_ARGUMENT;
+  const tsdf_ctx::MeshStream& R = c->mstream;
+  if (!R.configured || !R.tap_flags) FAIL(c, TSDF_ERR_STATE, "the mesh ring carries no texture taps (tsdf_mesh_stream_config_taps, TSDF_MESH_STREAM_TAPS)");
+  if (!R.ring.held) FAIL(c, TSDF_ERR_STATE, "no streamed mesh frame is held (tsdf_mesh_stream_acquire)");
+  const tsdf_ctx::MeshStreamSlot& S = R.slot[R.ring.oldest()];
+  *out = tsdf_mesh_taps{};
+  out->taps = (const tsdf_packed_tap*)(S.host + sizeof(MeshStreamHeader) + mesh_stream_tap_offset(R));
+  out->n_vertices = ((const MeshStreamHeader*)S.host)->n_vertices; out->n_streams = c->cfg.num_streams; out->tap_bytes = (uint32_t)kMeshTapBytes;
   return TSDF_OK;
 }
 int32_t tsdf_mesh_stream_stats(tsdf_ctx* c, uint64_t out[4]) {

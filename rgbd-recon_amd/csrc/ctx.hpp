@@ -157,7 +157,10 @@ struct tsdf_ctx {
   // MeshStreamFilterRecord, so that record and header travel as one copy and the payload stays 64 bytes behind the header.
   // index_format 1 (tsdf_mesh_stream_config_compact): the payload is vertices, padding, tile table, 6-byte triangles (result_paths.hpp: MeshFrameLayout);
   // table_rows is what the pump read for the slot's frame: the header's needed_tiles, with a filter the record's table_rows.
+  // tap_flags (tsdf_mesh_stream_config_taps): a slot ends with the block of packed texture taps, at MeshFrameLayout::tap_offset behind the payload's first
+  // byte; taps_written (context's stream, behind the tap launch: the block's copy waits for it), tap_bytes what the pump queued beside the payload.
   struct MeshStreamSlot { uint8_t* dev = nullptr; uint8_t* host = nullptr; hipEvent_t header_written = nullptr, emitted = nullptr, header_ready = nullptr, ready = nullptr;
+                          hipEvent_t taps_written = nullptr; size_t tap_bytes = 0;
                           uint64_t tag = 0; size_t payload_bytes = 0; bool payload_issued = false; int res[3] = {0, 0, 0}; size_t lead = 0; uint64_t table_rows = 0; };
   struct MeshStream {
     MeshStreamSlot slot[kMaxResultSlots];
@@ -166,6 +169,7 @@ struct tsdf_ctx {
     uint32_t flags = 0, level = 0, max_vertices = 0, max_triangles = 0, max_tiles = 0;   // level: tsdf_mesh_stream_config_lod (the scratch is sized by its lattice tiles)
     uint32_t min_triangles = 0;     // 0: no filter, the frame is emitted into its slot
     uint32_t index_format = 0;      // 0: uint32 triangles, 1: tile-local 6-byte triangles and a tile table
+    uint32_t tap_flags = 0;         // TSDF_MESH_STREAM_TAPS: packed texture taps behind every frame (off after every config entry)
     MeshFrameLayout layout() const { return MeshFrameLayout{index_format, flags ? 16u : 8u}; }
     // part (tsdf_mesh_stream_config_part): every frame is this context's PART of the tile-local frame -- the owned lattice tile layers `slab` names (set with
     // the allocation), count and emit by k_mesh_slab.hip, the scratch over owned + seam tiles, max_tiles + slab.n_seam record slots, and a slot's buffers

@@ -14,7 +14,7 @@
 // tsdf_texture_tap_stats' two counts are taken per wave with a ballot and one vector atomic per wave and count, as k_rays_march does -- but into one of
 // kTapStatSlots pairs of counters chosen by the wave's number: these waves are short, and a hundred thousand of them adding to one address took five
 // times as long as everything else the launch does (texture_taps.hpp, DESIGN.md "Texture taps").
-#include "sampling.hpp"
+#include "texture_taps_dev.hpp"
 #include "texture_taps.hpp"
 
 namespace rr {
@@ -35,15 +35,10 @@ __global__ __launch_bounds__(kTapsThreads) void k_texture_taps(StreamTable T, Fr
     evaluated = fabsf(u.x) < 1.0e6f && fabsf(u.y) < 1.0e6f && fabsf(u.z) < 1.0e6f;
     float4 tap = make_float4(0.0f, 0.0f, 0.0f, -1.0f), sen = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (evaluated) {                                                     // blend_colors()' per-stream values, by its own device functions
-      const StreamLut& L = T.s[stream];
-      const float3 pc = tex3d_rgba_xyz(L.inv, L.inv_res, u.x, u.y, u.z);
-      const float2 pcol = tex3d_rg(L.uv, L.uv_res, pc.x, pc.y, pc.z);
-      const Dqs q = dqs_fetch(F, (int)stream, pc.x, pc.y);               // (every tap index is clamped into its array, whatever pc holds)
-      const float depth = dqs_depth(q);
-      const float dist = fabsf(depth - pc.z);
-      if (dist < limit) quality = dqs_quality(q);
-      tap = make_float4(pcol.x, pcol.y, quality, dist);
-      sen = make_float4(pc.x, pc.y, pc.z, depth);
+      const TapValues t = texture_tap_values(T.s[stream], F, (int)stream, limit, u);   // (texture_taps_dev.hpp: shared with the mesh ring's packed taps)
+      quality = t.quality;
+      tap = make_float4(t.pcol.x, t.pcol.y, t.quality, t.dist);
+      sen = make_float4(t.pc.x, t.pc.y, t.pc.z, t.depth);
     }
     taps[g] = tap;                                                       // (point < n_points, stream < N: inside the launch's [points][N] records)
     if (sensor) sensor[g] = sen;

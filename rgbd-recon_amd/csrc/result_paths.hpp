@@ -36,6 +36,8 @@ struct ResultRing {
 // offsets from its header's counts (k_mesh.hip, k_mesh_stream_filter.hip); tests/test_mesh_compact_layout.py walks these functions on a CPU.
 constexpr uint32_t kMeshIndexU32 = 0, kMeshIndexTile16 = 1;             // TSDF_MESH_INDEX_U32 / _TILE16
 constexpr uint64_t kMeshHeaderBytes = 64, kMeshTileRowBytes = 16, kMeshSlotLimit = 4ull << 30;
+constexpr uint64_t kMeshTapBytes = 8;                                   // sizeof(tsdf_packed_tap)
+constexpr uint32_t kMeshStreamTaps = 1u;                                // TSDF_MESH_STREAM_TAPS
 struct MeshFrameLayout {
   uint32_t format, stride;
   static uint64_t align16(uint64_t n) { return (n + 15u) & ~(uint64_t)15u; }
@@ -51,6 +53,19 @@ struct MeshFrameLayout {
   // (every capacity is below 2^32 and every factor at most 16: no sum here comes near 2^64)
   bool fits(uint64_t max_vertices, uint64_t max_triangles, uint64_t max_tiles) const {
     return (format == kMeshIndexTile16 ? slot_bytes(max_vertices, max_triangles, max_tiles) : payload_capacity(max_vertices, max_triangles, max_tiles)) <= kMeshSlotLimit;
+  }
+  // "mesh streaming: texture taps in the frame": a block of packed taps (kMeshTapBytes per vertex and stream, [vertex][stream]) at a fixed place behind
+  // the payload's CAPACITY, so that the payload keeps its layout and its one exact-size copy; the block travels in a copy of its own, of a frame's bytes.
+  // tap_offset counts from the payload's first byte, as table_offset and triangle_offset do.  (streams <= 16: no product here comes near 2^64)
+  uint64_t tap_offset(uint64_t max_vertices, uint64_t max_triangles, uint64_t max_tiles) const { return align16(payload_capacity(max_vertices, max_triangles, max_tiles)); }
+  static uint64_t tap_capacity(uint64_t max_vertices, uint64_t streams) { return max_vertices * streams * kMeshTapBytes; }
+  static uint64_t tap_bytes(uint64_t nv, uint64_t streams) { return nv * streams * kMeshTapBytes; }
+  uint64_t slot_bytes_taps(uint64_t max_vertices, uint64_t max_triangles, uint64_t max_tiles, uint64_t streams) const {
+    return kMeshHeaderBytes + tap_offset(max_vertices, max_triangles, max_tiles) + tap_capacity(max_vertices, streams);
+  }
+  // the 4 GiB bound with the block: what fits() asks, and the whole slot -- header, payload capacity, padding, block -- in either format
+  bool fits_taps(uint64_t max_vertices, uint64_t max_triangles, uint64_t max_tiles, uint64_t streams) const {
+    return fits(max_vertices, max_triangles, max_tiles) && slot_bytes_taps(max_vertices, max_triangles, max_tiles, streams) <= kMeshSlotLimit;
   }
 };
 

@@ -486,6 +486,9 @@ struct TapsLaunch {
 // of device words {pairs with quality > 0, pairs not evaluated} (texture_taps.hpp), added to
 void launch_texture_taps(hipStream_t st, const StreamTable& T, const FrameImages& F, float limit, const TapsLaunch& Q, const float* xyz, tsdf_texture_tap* taps,
                          tsdf_sensor_tap* sensor, unsigned long long* stats);
+// the packed taps of a streamed frame (k_mesh_stream_taps.hip): sized by max_vertices, n_vertices read from the slot's device header H
+void launch_mesh_stream_taps(hipStream_t st, const StreamTable& T, const FrameImages& F, float limit, const MeshStreamHeader* H, const uint8_t* vertices,
+                             uint32_t stride, uint32_t max_vertices, void* taps);
 void launch_clear_image(hipStream_t st, float4* color, float* depth, size_t n, float4 c, float d);
 void launch_export_partial(hipStream_t st, const RayTarget& R, int w, int h, void* dst);
 void launch_composite(hipStream_t st, const void* gathered, int n, const RayTarget& R, int w, int h);

@@ -23,6 +23,9 @@
 // Option --mesh-stream-part (implies --mesh-stream-compact; no filter): the ring is configured with configureMeshStreamPart, so every frame is the
 // context's part of the tile-local frame -- on this whole-volume context the one-slab case: the part must reach the top, own every lattice tile layer
 // and have no seam tile, and the join of that one part (joinMeshParts) must decode to downloadMesh's triangles.
+// Option --mesh-stream-taps (implies --mesh-stream; with any of the switches above): meshStreamConfigTaps after the configuration, so every frame
+// carries its packed texture taps; the ring must report the flag, every held frame's block must be non-null with the frame's vertex count, one stream
+// and 8-byte records, decodeMeshTaps must give a record per pair, and the payload bytes must count the blocks.
 //   g++ -std=c++17 frame_harness.cpp -o frame_harness -L.. -lrgbd_recon_hip -Wl,-rpath,'$ORIGIN/..'
 #include <cmath>
 #include <cstdio>
@@ -41,7 +44,7 @@ int main(int argc, char** argv) {
   bool mesh_stream = false;
   int mesh_level = -1;                                                    // -1: not given (the entries without a level)
   long mesh_stream_min_triangles = -1;                                    // -1: not given (the ring without a filter)
-  bool mesh_stream_compact = false, mesh_stream_part = false;
+  bool mesh_stream_compact = false, mesh_stream_part = false, mesh_stream_taps = false;
   for (int a = 1; a < argc; ++a) {
     if (std::strcmp(argv[a], "--draw-bricks") == 0) draw_bricks = true;
     else if (std::strcmp(argv[a], "--sensor-view") == 0 && a + 2 < argc) { view_type = std::atoi(argv[a + 1]); view_width = (float)std::atof(argv[a + 2]); a += 2; }
@@ -56,9 +59,10 @@ int main(int argc, char** argv) {
     }
     else if (std::strcmp(argv[a], "--mesh-stream-compact") == 0) { mesh_stream_compact = true; mesh_stream = true; }
     else if (std::strcmp(argv[a], "--mesh-stream-part") == 0) { mesh_stream_part = true; mesh_stream_compact = true; mesh_stream = true; }
+    else if (std::strcmp(argv[a], "--mesh-stream-taps") == 0) { mesh_stream_taps = true; mesh_stream = true; }
     else {
       std::fprintf(stderr, "usage: frame_harness [--draw-bricks] [--sensor-view TYPE WIDTH] [--present rgba8|dxt1] [--mesh FILE.ply] [--mesh-stream] [--mesh-level 0|1|2]"
-                           " [--mesh-stream-min-triangles N] [--mesh-stream-compact] [--mesh-stream-part]\n");
+                           " [--mesh-stream-min-triangles N] [--mesh-stream-compact] [--mesh-stream-part] [--mesh-stream-taps]\n");
       return 1;
     }
   }
@@ -184,6 +188,9 @@ int main(int argc, char** argv) {
       if (recon.meshStreamLevel() != (unsigned)(mesh_level < 0 ? 0 : mesh_level)) return 1;
       if (recon.meshStreamMinTriangles() != (unsigned)(filtered ? mesh_stream_min_triangles : 0)) return 1;
       if (recon.meshStreamIndexFormat() != (mesh_stream_compact ? TSDF_MESH_INDEX_TILE16 : TSDF_MESH_INDEX_U32)) return 1;
+      if (recon.meshStreamHasTaps()) return 1;                                 // (every config entry leaves the taps off)
+      if (mesh_stream_taps) recon.meshStreamConfigTaps();
+      if (recon.meshStreamHasTaps() != mesh_stream_taps) return 1;
       const int frames = 5, lag = 2;
       int got = 0, wrong = 0;
       auto take = [&](std::uint64_t want_tag) {
@@ -207,6 +214,12 @@ int main(int argc, char** argv) {
                  kinect::ReconIntegrationHip::decodeMeshTriangles(joined.compact(), joined.nTriangles()) == want.triangles;
           }
         } else want_bytes += fr.n_vertices * 16 + fr.n_triangles * 12;
+        if (mesh_stream_taps) {
+          const tsdf_mesh_taps t = recon.meshStreamFrameTaps();
+          ok = ok && t.taps != nullptr && t.n_vertices == fr.n_vertices && t.n_streams == 1 && t.tap_bytes == sizeof(tsdf_packed_tap) &&
+               kinect::ReconIntegrationHip::decodeMeshTaps(t).size() == t.n_vertices * t.n_streams;
+          want_bytes += t.n_vertices * t.n_streams * sizeof(tsdf_packed_tap);
+        }
         recon.releaseMeshFrame();                                              // (before it is counted: a held frame would fail every later acquire too)
         ++(ok ? got : wrong);
       };

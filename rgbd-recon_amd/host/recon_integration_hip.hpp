@@ -351,6 +351,44 @@ class ReconIntegrationHip {
     }
     return out;
   }
+  // ... with the packed texture taps of every frame beside its vertices (tsdf_mesh_stream_config_taps, after any configureMeshStream*: each of those
+  // turns the taps off again): 8 bytes per vertex and stream, taken at the position the receiver reconstructs from the vertex's codes.  The reference
+  // has no counterpart.  meshStreamFrameTaps(): the block of the frame HELD now, [n_vertices][n_streams], valid until releaseMeshFrame() (throws on a
+  // ring without taps or without a frame).  decodeMeshTaps is the header's unpacking: u = code / 65535.0f, the binary16 weights widened to fp32 -- the
+  // records the receiver's rule of the texture taps takes as they are.
+  void meshStreamConfigTaps(bool taps = true) { check(tsdf_mesh_stream_config_taps(m_ctx, taps ? TSDF_MESH_STREAM_TAPS : 0u)); }
+  bool meshStreamHasTaps() {
+    std::uint32_t flags = 0;
+    check(tsdf_mesh_stream_tap_flags(m_ctx, &flags));
+    return (flags & TSDF_MESH_STREAM_TAPS) != 0;
+  }
+  tsdf_mesh_taps meshStreamFrameTaps() {
+    tsdf_mesh_taps out{};
+    check(tsdf_mesh_stream_frame_taps(m_ctx, &out));
+    return out;
+  }
+  static float halfToFloat(std::uint16_t h) {
+    const std::uint32_t sign = (std::uint32_t)(h & 0x8000u) << 16, exp = (h >> 10) & 0x1fu, man = h & 0x3ffu;
+    std::uint32_t bits;
+    if (exp == 0x1fu) bits = sign | 0x7f800000u | (man << 13);            // infinity, NaN
+    else if (exp) bits = sign | ((exp + 112u) << 23) | (man << 13);       // normal: the exponent re-biased, 127 - 15
+    else if (!man) bits = sign;                                           // +-0
+    else {                                                                // subnormal: man * 2^-24, exactly
+      float f = (float)man * 5.9604644775390625e-08f;
+      return sign ? -f : f;
+    }
+    float f;
+    std::memcpy(&f, &bits, sizeof f);
+    return f;
+  }
+  static std::vector<tsdf_texture_tap> decodeMeshTaps(const tsdf_mesh_taps& t) {
+    std::vector<tsdf_texture_tap> out(t.n_vertices * t.n_streams);
+    for (std::size_t k = 0; k < out.size(); ++k) {
+      const tsdf_packed_tap& p = t.taps[k];
+      out[k] = tsdf_texture_tap{(float)p.u / 65535.0f, (float)p.v / 65535.0f, halfToFloat(p.quality_h), halfToFloat(p.dist_h)};
+    }
+    return out;
+  }
   // ... as this context's PART of the tile-local frame (tsdf_mesh_stream_config_part): the one ring a Z-slab context streams through; a whole-volume
   // context is the one-slab case.  Capacities are per part; there is no filter.  meshFramePart(): the layers, level, top flag and seam tiles of the frame
   // HELD now (throws on another ring or without a frame); takeMeshPart copies the held frame into a MeshPartFrame of the caller's own.  joinMeshParts
@@ -358,6 +396,7 @@ class ReconIntegrationHip {
   // whole -- or the parts do not follow each other; the joined frame is the whole-volume compact frame, byte for byte.
   struct MeshPartFrame {
     std::vector<std::uint8_t> vertices; std::vector<tsdf_mesh_tile_row> table; std::vector<std::uint16_t> codes;
+    std::vector<tsdf_packed_tap> taps;                                  // [nVertices()][n_streams] on a ring with taps: parts join by concatenation
     std::uint32_t vertex_stride = 0, overflow = 0, tiles[3] = {0, 0, 0};
     tsdf_mesh_part part{};
     std::uint64_t nVertices() const { return vertex_stride ? vertices.size() / vertex_stride : 0; }
@@ -383,6 +422,10 @@ class ReconIntegrationHip {
     p.vertices.assign(v, v + held.n_vertices * held.vertex_stride);
     p.table.assign(c.table, c.table + c.n_tile_rows);
     p.codes.assign(c.triangles, c.triangles + held.n_triangles * 3);
+    if (meshStreamHasTaps()) {
+      const tsdf_mesh_taps t = meshStreamFrameTaps();
+      p.taps.assign(t.taps, t.taps + t.n_vertices * t.n_streams);
+    }
     return p;
   }
   static bool joinMeshParts(const std::vector<MeshPartFrame>& parts, MeshPartFrame& out) {
@@ -405,6 +448,7 @@ class ReconIntegrationHip {
         out.table.push_back(row);
       }
       out.codes.insert(out.codes.end(), p.codes.begin(), p.codes.end());
+      out.taps.insert(out.taps.end(), p.taps.begin(), p.taps.end());
       nv += p.nVertices(); nt += p.nTriangles();
     }
     return true;

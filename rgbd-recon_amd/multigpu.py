@@ -412,7 +412,8 @@ class SlabDriver:
         frame up from the backend when it likes (mesh_stream_take).  take=True: a COLLECTIVE -- every rank takes its oldest part (waiting for it), the
         parts are gathered on rank 0 and joined by the header's rule; returns dict(part=the rank's (vertices, codes, info) or None) and, on rank 0,
         frame=(vertices, codes, info): the whole-volume compact frame, or None when a part overflowed (the frame is dropped whole).  A dedicated
-        compositor contributes no part."""
+        compositor contributes no part.  Part rings configured with taps=True carry each part's packed texture taps in info["taps"]; they travel with
+        the part and the joined frame's info["taps"] is their concatenation, the whole-volume ring's block byte for byte."""
         if self.is_worker:
             self.b.mesh_stream(tag)
         if not take:
@@ -474,7 +475,8 @@ def mesh_slabs_on_one_device(backends, normals=True, colours=True, level=0):
 def mesh_parts_on_one_device(backends, tag=0):
     """SlabDriver.stream_mesh with ONE visible device: backends[k] owns slab k (contiguous, in z order), each with a part ring configured
     (mesh_stream_config(part=True)) and a current halo.  Every slab queues its part, then every part is taken; nothing travels between the slabs.
-    Returns (parts, frame): parts[k] = (vertices, codes, info) of slab k, frame = join_mesh_parts(parts), or None when a part overflowed."""
+    Returns (parts, frame): parts[k] = (vertices, codes, info) of slab k, frame = join_mesh_parts(parts), or None when a part overflowed.  With
+    taps=True on every part ring the parts' info["taps"] are joined into the frame's info["taps"] by concatenation."""
     for b in backends:
         b.mesh_stream(tag)
     parts = [b.mesh_stream_take(wait=True) for b in backends]

@@ -21,7 +21,11 @@ host ("latency_ms"), the copy's share of it (latency - device stages) and the ba
 --slabs K: instead of parts 1 and 2, K Z-slab contexts of the same volume on this one device (recomputed halos), each with a part ring
 (tsdf_mesh_stream_config_part), beside the whole-volume context's compact ring, at the first level named, for positions and all attributes: the stage
 timers of every slab's part (count + scan + emit; the slowest slab is what a frame waits for when every slab has a device of its own) and of the
-whole-volume ring, in WINDOWS windows of N calls with the two alternating call by call; and whether the joined parts equal the whole-volume frame."""
+whole-volume ring, in WINDOWS windows of N calls with the two alternating call by call; and whether the joined parts equal the whole-volume frame.
+--taps: instead of parts 1 and 2, the ring with packed texture taps in the frame (tsdf_mesh_stream_config_taps) against the same ring without, per level
+(and with --min-triangles the filtered ring), alternating call by call: the stage timers and "mesh_stream_taps", the bytes per frame with and without
+the block; beside them the two yardsticks on the same mesh -- "texture_taps" of tsdf_mesh_texture_taps (the fp32 form) and what TSDF_MESH_COLOURS
+adds to "mesh_stream_emit" -- and the frames per second of the streamed loop with the tap ring on and off."""
 import sys, os, json, time
 from importlib import import_module
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -202,8 +206,80 @@ def slabs_record():
     return out
 
 
-if SLABS or "--compact" in ARGS:
-    rec = slabs_record() if SLABS else compact_record()
+def taps_record():
+    """--taps: the ring with the tap block against the ring without"""
+    stages = STREAM_STAGES + ("mesh_stream_taps",)
+    out = dict(rec, tool="tools/mesh_stream_timing.py --taps", unit="ms (stages), bytes, frames/s", calls=N, levels={})
+    hip.enable_timers(True)
+    hip.set_timer_filter(list(stages) + ["texture_taps"])
+    for L in LEVELS:
+        r = dict(vertices=levels[L]["vertices"], triangles=levels[L]["triangles"])
+        rings = dict(plain=dict(normals=False, colours=False, taps=False), taps=dict(normals=False, colours=False, taps=True),
+                     colours=dict(normals=False, colours=True, taps=False), colours_taps=dict(normals=False, colours=True, taps=True))
+        samples = {k: dict(bytes=[], **{s: [] for s in stages}) for k in rings}
+        fp32 = []
+        for k in range(2 + N):                                           # two warm calls, then N; the rings alternate: all see the same machine
+            for name, kw in rings.items():
+                hip.mesh_stream_config(slots=3, level=L, min_triangles=MIN_TRIANGLES, **kw, **levels[L]["capacities"])
+                hip.mesh_stream(0); hip.mesh_stream_take()               # (the configuration's first call allocates)
+                for s in stages:
+                    hip.timer_stats(s)
+                before = hip.mesh_stream_stats()["payload_bytes"]
+                hip.mesh_stream(1)
+                got = hip.mesh_stream_take()
+                assert got[2]["overflow"] == 0 and (("taps" in got[2]) == kw["taps"])
+                r.setdefault("n_vertices", got[2]["n_vertices"])
+                if k >= 2:
+                    samples[name]["bytes"].append(hip.mesh_stream_stats()["payload_bytes"] - before)
+                    for s in stages:
+                        cnt, total = hip.timer_stats(s)
+                        samples[name][s].append(total / cnt if cnt else 0.0)
+            hip.extract_mesh(normals=False, colours=False, level=L)      # the yardstick: the fp32 taps of the one-shot extract at the same level
+            hip.timer_stats("texture_taps")
+            hip.mesh_texture_taps(download=False)
+            cnt, total = hip.timer_stats("texture_taps")
+            if k >= 2:
+                fp32.append(total)                                       # (summed over the call's launches)
+        for name in rings:
+            S = samples[name]
+            assert len(set(S["bytes"])) == 1
+            r[name] = dict(payload_and_tap_bytes=S["bytes"][0], **{s + "_ms": float(np.mean(S[s])) for s in stages},
+                           mesh_stream_taps_ms_min=float(np.min(S["mesh_stream_taps"])), mesh_stream_taps_ms_max=float(np.max(S["mesh_stream_taps"])))
+        r["tap_bytes_per_frame"] = r["taps"]["payload_and_tap_bytes"] - r["plain"]["payload_and_tap_bytes"]
+        r["fp32_texture_taps_ms"] = float(np.mean(fp32))
+        r["colours_add_to_emit_ms"] = r["colours"]["mesh_stream_emit_ms"] - r["plain"]["mesh_stream_emit_ms"]
+        out["levels"][str(L)] = r
+    hip.enable_timers(False)
+    def streamed(f):
+        hip.mesh_stream(f)
+        if hip.mesh_stream_stats()["frames"] - streamed.taken > 2:
+            hip.mesh_stream_take(); streamed.taken += 1
+    def loop(n):
+        for f in range(10):
+            hip.frame_dev(mv, pr, ptrs); streamed(f)
+        while hip.mesh_stream_stats()["frames"] > streamed.taken:
+            hip.mesh_stream_take(); streamed.taken += 1
+        hip.sync()
+        t0 = time.perf_counter()
+        for f in range(n):
+            hip.frame_dev(mv, pr, ptrs); streamed(f)
+        while hip.mesh_stream_stats()["frames"] > streamed.taken:
+            hip.mesh_stream_take(); streamed.taken += 1
+        hip.sync()
+        return n / (time.perf_counter() - t0)
+    fps = {}
+    for rep_ in range(0 if STAGES_ONLY else 3):
+        for L in LEVELS:
+            for taps in (False, True):
+                hip.mesh_stream_config(slots=3, level=L, min_triangles=MIN_TRIANGLES, taps=taps, **levels[L]["capacities"])
+                streamed.taken = 0
+                fps.setdefault("level%d_positions_%s" % (L, "taps" if taps else "plain"), []).append(loop(FRAMES))
+    out["frames_per_s"] = {k: dict(runs=[round(x, 1) for x in v], median=round(float(np.median(v)), 1)) for k, v in fps.items()}
+    return out
+
+
+if SLABS or "--compact" in ARGS or "--taps" in ARGS:
+    rec = slabs_record() if SLABS else taps_record() if "--taps" in ARGS else compact_record()
     print(json.dumps(rec), flush=True)
     if OUT:
         with open(OUT[0], "w") as f:
