@@ -1408,14 +1408,28 @@ void orc_draw_points(orc_ctx* c, const float* mv16, const float* proj16) {
 //     columns >= H of a W x H image are never drawn and the rows past the image collapse to zero-area triangles;
 //   * trigrid_accum.fs:69: gl_FragCoord.xy + 0.5 (one pixel diagonal offset of the reprojected surface position).
 // Definitions GL leaves to the implementation (shared with the kernels): P*MV formed in double; gl_NormalMatrix unused here;
-// a triangle with a vertex at w <= 0 is dropped; pixel-centre sampling, edge functions in fp32 with a top-left style
+// a triangle with a vertex at w <= 0 is cut at the near plane first (tri_clip_near), as GL clips before the window transform;
+// pixel-centre sampling, edge functions in fp32 with a top-left style
 // tie-break on exact zeros; window z linear in screen space, fragments outside 0 <= z <= 1 dropped; smooth varyings
 // perspective-correct as sum(l_i a_i / w_i) / sum(l_i / w_i); depth and quality images sampled NEAREST (the positions are
 // texel centres or clamp to them); additive blending in draw order (fp32).
 }  // extern "C" (helpers with templates follow)
 namespace {
-struct TriVert { vec3 pos_cs, pos_es; float tcx, tcy, depth, quality, xw, yw, zw, iw; bool front; };
-struct TriSetup { TriVert v[3]; vec3 normal; float area; bool ok; };
+struct TriVert { vec3 pos_cs, pos_es; float tcx, tcy, depth, quality, xw, yw, zw, iw, nd; bool front; };   // nd = clip.z + clip.w: >= 0 in front of the near plane
+struct TriSetup { TriVert v[3]; vec3 normal; float area; bool ok, cut; };
+
+// eye, clip and window position of a vertex at pos_cs (trigrid_accum.vs:28,33)
+void tri_project(const orc_ctx* c, const view_mats& V, const mat4& PMV, TriVert& t) {
+  const vec4 pe = mul(V.mv, {t.pos_cs.x, t.pos_cs.y, t.pos_cs.z, 1.0f});
+  t.pos_es = {pe.x, pe.y, pe.z};
+  const vec4 clip = mul(PMV, {t.pos_cs.x, t.pos_cs.y, t.pos_cs.z, 1.0f});
+  t.front = clip.w > 0.0f;
+  t.nd = clip.z + clip.w;
+  t.iw = 1.0f / clip.w;
+  t.xw = (clip.x / clip.w * 0.5f + 0.5f) * (float)c->vw;
+  t.yw = (clip.y / clip.w * 0.5f + 0.5f) * (float)c->vh;
+  t.zw = clip.z / clip.w * 0.5f + 0.5f;
+}
 
 TriVert tri_vertex(const orc_ctx* c, const view_mats& V, const mat4& PMV, int l, int gx, int gy) {
   const int W = (int)c->cfg.depth_w, H = (int)c->cfg.depth_h;
@@ -1428,29 +1442,57 @@ TriVert tri_vertex(const orc_ctx* c, const view_mats& V, const mat4& PMV, int l,
   tex3d(c->xyz[l], 3, c->xyz_res[l], u, v, t.depth, pc);
   tex3d(c->uv[l], 2, c->uv_res[l], u, v, t.depth, tc);
   t.pos_cs = {pc[0], pc[1], pc[2]}; t.tcx = tc[0]; t.tcy = tc[1];
-  const vec4 pe = mul(V.mv, {pc[0], pc[1], pc[2], 1.0f});
-  t.pos_es = {pe.x, pe.y, pe.z};
-  const vec4 clip = mul(PMV, {pc[0], pc[1], pc[2], 1.0f});
-  t.front = clip.w > 0.0f;
-  t.iw = 1.0f / clip.w;
-  t.xw = (clip.x / clip.w * 0.5f + 0.5f) * (float)c->vw;
-  t.yw = (clip.y / clip.w * 0.5f + 0.5f) * (float)c->vh;
-  t.zw = clip.z / clip.w * 0.5f + 0.5f;
+  tri_project(c, V, PMV, t);
   return t;
 }
 TriSetup tri_setup(const orc_ctx* c, TriVert a, TriVert b, TriVert d) {                 // trigrid_accum.gs
-  TriSetup T; T.v[0] = a; T.v[1] = b; T.v[2] = d; T.ok = false;
+  TriSetup T; T.v[0] = a; T.v[1] = b; T.v[2] = d; T.ok = T.cut = false;
   if (a.depth < 0.0f || b.depth < 0.0f || d.depth < 0.0f) return T;                    // validSurface, :31-42
   const float avg = (a.depth + b.depth + d.depth) / 3.0f;
   const float l = c->min_length * avg * 4.0f;
   if (!(length(b.pos_cs - a.pos_cs) < l && length(d.pos_cs - a.pos_cs) < l && length(d.pos_cs - b.pos_cs) < l)) return T;
-  if (!(a.front && b.front && d.front)) return T;
+  if (!(a.front || b.front || d.front)) return T;
   const vec3 ea = b.pos_es - a.pos_es, eb = d.pos_es - a.pos_es;
   T.normal = normalize(vec3{ea.y * eb.z - eb.y * ea.z, ea.z * eb.x - eb.z * ea.x, ea.x * eb.y - eb.x * ea.y});   // normalize(cross(a, b)), :59
+  if (!(a.front && b.front && d.front)) { T.ok = T.cut = true; return T; }               // reaches behind the eye: tri_clip_near() before it is drawn
   T.area = (b.xw - a.xw) * (d.yw - a.yw) - (d.xw - a.xw) * (b.yw - a.yw);
   if (!(T.area != 0.0f)) return T;
   T.ok = true;
   return T;
+}
+// GL clips a primitive before the window transform.  With every w > 0 the division by w is defined and the per-fragment 0 <= z <= 1 test IS the
+// near / far clip: such a triangle is drawn as it stands.  One that reaches behind the eye is cut at the near plane (z = -w; there w > 0 under a
+// perspective projection) into one or two triangles with the flat normal of the whole.  A vertex on the plane is i + t (o - i) in pos_cs and in every
+// varying, t = nd_i / (nd_i - nd_o) from the inside vertex i to the outside vertex o whichever way the edge runs, so the two triangles of an edge get
+// the same point; its eye, clip and window positions follow from pos_cs as a vertex's do.  Returns the number of triangles written to out[].
+int tri_clip_near(const orc_ctx* c, const view_mats& V, const mat4& PMV, const TriSetup& T, TriSetup out[2]) {
+  TriVert p[4];
+  int n = 0;
+  for (int k = 0; k < 3; ++k) {
+    const TriVert &a = T.v[k], &b = T.v[(k + 1) % 3];
+    const bool ia = a.front && a.nd >= 0.0f, ib = b.front && b.nd >= 0.0f;
+    if (ia) p[n++] = a;
+    if (ia != ib) {
+      const TriVert &i = ia ? a : b, &o = ia ? b : a;
+      const float t = i.nd / (i.nd - o.nd);
+      TriVert m;
+      m.pos_cs = {i.pos_cs.x + t * (o.pos_cs.x - i.pos_cs.x), i.pos_cs.y + t * (o.pos_cs.y - i.pos_cs.y), i.pos_cs.z + t * (o.pos_cs.z - i.pos_cs.z)};
+      m.tcx = i.tcx + t * (o.tcx - i.tcx); m.tcy = i.tcy + t * (o.tcy - i.tcy);
+      m.depth = i.depth + t * (o.depth - i.depth); m.quality = i.quality + t * (o.quality - i.quality);
+      tri_project(c, V, PMV, m);
+      p[n++] = m;
+    }
+  }
+  int count = 0;
+  for (int k = 2; k < n; ++k) {
+    TriSetup& S = out[count];
+    S = T; S.cut = false;
+    S.v[0] = p[0]; S.v[1] = p[k - 1]; S.v[2] = p[k];
+    S.area = (S.v[1].xw - S.v[0].xw) * (S.v[2].yw - S.v[0].yw) - (S.v[2].xw - S.v[0].xw) * (S.v[1].yw - S.v[0].yw);
+    S.ok = S.v[0].front && S.v[1].front && S.v[2].front && S.area != 0.0f;
+    count += S.ok;
+  }
+  return count;
 }
 struct Fragment { float z, tcx, tcy, quality; vec3 pos_es, pos_cs; };
 // coverage + interpolation at pixel centre (px + .5, py + .5); false: not covered
@@ -1495,9 +1537,15 @@ void for_each_triangle(orc_ctx* c, const view_mats& V, const mat4& PMV, F&& body
       for (int x = 0; x < H; ++x) {                                                       // sic: :54
         const TriVert v00 = tri_vertex(c, V, PMV, l, x, y), v10 = tri_vertex(c, V, PMV, l, x + 1, y), v01 = tri_vertex(c, V, PMV, l, x, y + 1),
                       v11 = tri_vertex(c, V, PMV, l, x + 1, y + 1);
-        const TriSetup tris[2] = {tri_setup(c, v00, v10, v01), tri_setup(c, v10, v11, v01)};   // :55-61
-        for (const TriSetup& T : tris) {
-          if (!T.ok) continue;
+        TriSetup tris[4];                                                                  // :55-61; a triangle cut at the near plane may become two
+        int nt = 0;
+        for (const TriSetup& W : {tri_setup(c, v00, v10, v01), tri_setup(c, v10, v11, v01)}) {
+          if (!W.ok) continue;
+          if (W.cut) nt += tri_clip_near(c, V, PMV, W, tris + nt);
+          else tris[nt++] = W;
+        }
+        for (int k = 0; k < nt; ++k) {
+          const TriSetup& T = tris[k];
           const float minx = fminf(fminf(T.v[0].xw, T.v[1].xw), T.v[2].xw), maxx = fmaxf(fmaxf(T.v[0].xw, T.v[1].xw), T.v[2].xw);
           const float miny = fminf(fminf(T.v[0].yw, T.v[1].yw), T.v[2].yw), maxy = fmaxf(fmaxf(T.v[0].yw, T.v[1].yw), T.v[2].yw);
           if (!(maxx >= 0.0f && maxy >= 0.0f && minx <= (float)vw && miny <= (float)vh)) continue;

@@ -7,6 +7,8 @@ nothing is promoted to float64 except where the reference host code itself compu
 * draw_mvt(...): the z pre-pass, the ONE/ONE blend and the normalise pass, restating the oracle's Trigrid rasteriser
   (oracle/tsdf_oracle.cpp, orc_draw_trigrid and its helpers) with MVT's validSurface (mvt_accum.gs:29-41) and fragment quality
   (mvt_accum.fs:53).  LUT and colour lookups go through the oracle's sampling primitives (oracle.tex3d / tex2d_linear).
+  A triangle that reaches behind the eye is dropped whole here; the oracle and the kernels cut it at the near plane (tri_clip_near).
+  The check that shares nothing with the oracle is tests/backend_reference.draw_mvt_raster, through tests/test_gpu_backends.py.
 """
 import numpy as np
 
