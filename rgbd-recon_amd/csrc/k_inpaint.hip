@@ -5,7 +5,9 @@
 // passes at 1280x720) and tsdf_inpaint.fs reads that copy with a 2/3 x-scale.  Here there is ONE atlas
 // and no copy: inpaint composes the squeeze mapping analytically (squeezed column s holds atlas column
 // floor(1.5 (s + .5))), and reproduces what the freshly cleared copy would contain for texels that were
-// not written yet.  Results are identical to the two-atlas sequence.
+// not written yet.  Results are identical to the two-atlas sequence evaluated in fp32 in the shaders'
+// operation order -- which is what a float64 restatement of the literal sequence holds them to wherever GL itself fixes the
+// answer (tests/fill_reference.py; DESIGN.md section 2, "A second judge for hole filling", lists what GL leaves open).
 #include "sampling.hpp"
 
 namespace rr {

@@ -86,3 +86,19 @@ def test_far_surface_wins_in_the_pyramid():
     assert (lvl1[..., 0] == 1).all() and (lvl1[..., 2] == 0).all()
     d1 = ad[off[1][1] + 2: off[1][1] + res[1][1] - 2, off[1][0] + 2: off[1][0] + res[1][0] - 2]
     assert np.abs(d1 - f32(0.9)).max() < 1e-6                          # sum of k far depths / k, fp32 rounding only
+
+
+def test_colorfill_reads_the_left_neighbour_where_fp32_truncates_below_the_pixel():
+    """Found by the float64 judge (tests/fill_reference.py): tsdf_colorfill.fs:32-38 computes ivec2(res * (x / res)).  At 61 x 45 the fp32
+    product falls below x for x = 1, 2, 4, 8, 16, 32 and truncates to x - 1: the framebuffer shows the left neighbour there.  GL leaves
+    the rounding of the division open, so this is one of two legitimate answers, not a defect -- but it is what oracle and kernel do."""
+    w, h = 61, 45
+    o = recon(w, h)
+    rng = np.random.default_rng(4)
+    rgba = np.concatenate([rng.random((h, w, 3), dtype=f32), np.ones((h, w, 1), f32)], -1)
+    o.set_view_images(rgba, np.full((h, w), 0.5, f32))
+    o.fillColors()
+    fc, _ = o.framebuffer()
+    src = np.array([int(f32(w) * (f32(x) / f32(w))) for x in range(w)])
+    assert np.flatnonzero(src != np.arange(w)).tolist() == [1, 2, 4, 8, 16, 32]
+    np.testing.assert_array_equal(fc, rgba[:, src])
