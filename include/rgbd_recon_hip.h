@@ -804,6 +804,48 @@ int32_t tsdf_cast_rays_dev(tsdf_ctx* ctx, const tsdf_ray* rays_dev, uint64_t n, 
 int32_t tsdf_view_rays(tsdf_ctx* ctx, const float mv[16], const float proj[16], int32_t x0, int32_t y0, int32_t w, int32_t h, tsdf_ray* rays);
 int32_t tsdf_ray_stats(tsdf_ctx* ctx, uint64_t out[4]);
 
+/* ---- ray queries: slab parts -------------------------------------------------------------------------------
+ * Where the volume exists only as Z-slabs (tsdf_config::slab_z0 / slab_z1) no context can answer a ray alone: a ray crosses slabs.  Every slab casts
+ * the SAME rays and answers for the samples it owns (tsdf_cast_rays_part); the parts merge per ray (tsdf_merge_ray_parts_dev, or the rule below on the
+ * host), and the merged arrays are byte for byte what tsdf_cast_rays gives on a whole-volume context.  It is the draw's slab march (owned samples,
+ * the smallest sample count wins) for caller-given rays.  tests/ray_part_reference.py restates this section in numpy.
+ *
+ * Ownership of a sample.  The ray, its mapping, validity, intersectBox, the caller's interval, pos, max_n, step and the chained additions are the ray
+ *   section's, unchanged.  Sample k (0-based) is at pos_k.  Its owner plane is fminf(fmaxf(floorf(pos_k.z * (float)rz), 0.0f), (float)(rz - 1)) with
+ *   rz the volume's z resolution -- the draw's rule; a NaN z gives plane 0, +-inf clamp.  A context owns the sample iff plane >> 3 lies in its owned tile
+ *   layers [own_tz0, own_tz1) = [slab_z0 / 8, (slab_z1 + 7) / 8).  Contiguous slabs that cover the volume own every sample exactly once.
+ * A part.  The context examines its owned samples only.  Its hit is its first owned sample with dens > 0.  prev is the density of sample k - 1: for
+ *   k = 0 it is -limit; if sample k - 1 is owned it is that sample's own value (it was no hit); otherwise it is fetched at pos_{k-1} from the halo.  The
+ *   refinement, t, pos (unit cube or vol_to_world) and the surface (the normal and blendColors at the refined point) are the ray section's arithmetic.
+ *   A record that can win the merge has prev <= 0 < dens, so its refined point lies within one step behind the owned sample and the halo covers its
+ *   surface taps.  Where sample k - 1 was itself a hit (a neighbour's: such a part record never wins) the refined point can lie anywhere on the ray; its
+ *   surface taps are clamped into the context's stored planes, as every z tap of a slab context is.
+ *   The part record is a tsdf_ray_hit: on a hit status = TSDF_RAY_HIT and n_samples = k + 1; without one status = 0, n_samples = max_n, t = -1,
+ *   pos = 0.  TSDF_RAY_OUTSIDE and TSDF_RAY_INVALID are as in the whole cast, and identical on every slab.  Surface records are zero without a hit.
+ * Merge rule.  Parts k = 0 .. K - 1 of contiguous slabs in slab order: per ray the answer is the part record with TSDF_RAY_HIT and the smallest
+ *   n_samples; no two parts can tie, a sample has one owner.  If no part hit, the answer is part 0's record.  The surface record travels with the winner.
+ *   Why this is the whole cast: the whole march stops at the smallest k with dens_k > 0; each slab finds the smallest such k among its own samples, so
+ *   the minimum over the slabs is that k, and its record is built from the same pos_k, dens_k and dens_{k-1} by the same arithmetic.  z is monotonic
+ *   along a chain of additions of one step (x + s >= x for s >= 0 in fp32, and the owner plane is monotonic in z), so a slab's samples are one contiguous
+ *   run and the kernel may stop behind it.  The merged arrays are byte for byte what tsdf_cast_rays gives on a whole-volume context, provided the halo
+ *   is current exactly as for a draw on the slab: exchanged (tsdf_halo_pack_dev / _unpack_dev) or recomputed (slab_recompute_halo).
+ * The one-slab case.  A whole-volume context is the one-slab case: it owns every sample, and its part cast equals its tsdf_cast_rays byte for byte.
+ *
+ * tsdf_cast_rays_part / tsdf_cast_rays_part_dev: the flags, argument checks, error codes, staging, chunking, stream ordering (they wait, on the GPU,
+ *   for an integrate() in flight; the integrate() that later overwrites the set they read waits for them) and n == 0 are tsdf_cast_rays' and
+ *   tsdf_cast_rays_dev's.  Timers "rays_part_march", "rays_part_surface".  They work on any context: slab or whole, dense or sparse pool.
+ *   TSDF_ERR_STATE: before the first tsdf_integrate / tsdf_upload_volume; TSDF_RAY_COLOURS without calibration and a frame.  The _dev form never waits
+ *   for the host and allocates nothing after the context's first cast.  Empty space is skipped by the tile classes as in the whole cast, for runs
+ *   whose first and last sample are both owned.  After a part cast tsdf_ray_stats gives {rays, hits found in THIS part, owned samples accounted for
+ *   (fetched or skipped), samples fetched}.
+ * tsdf_merge_ray_parts_dev: device arrays, queued on the context's stream; runs on any context and needs no volume.  Part k's records start at
+ *   hit_parts_dev + k * stride_records, the surface parts are laid out the same way.  TSDF_ERR_INVALID_ARGUMENT: parts == 0; with n > 0 a NULL array,
+ *   exactly one of the two surface arrays, stride_records < n.  n == 0: TSDF_OK, nothing is launched.  -1 for a NULL context. */
+int32_t tsdf_cast_rays_part(tsdf_ctx* ctx, const tsdf_ray* rays, uint64_t n, uint32_t flags, tsdf_ray_hit* hits, tsdf_ray_surface* surface);
+int32_t tsdf_cast_rays_part_dev(tsdf_ctx* ctx, const tsdf_ray* rays_dev, uint64_t n, uint32_t flags, tsdf_ray_hit* hits_dev, tsdf_ray_surface* surface_dev);
+int32_t tsdf_merge_ray_parts_dev(tsdf_ctx* ctx, const tsdf_ray_hit* hit_parts_dev, const tsdf_ray_surface* surface_parts_dev /* or NULL */, uint32_t parts, uint64_t n,
+                                 uint64_t stride_records, tsdf_ray_hit* hits_dev, tsdf_ray_surface* surface_dev /* or NULL */);
+
 /* ---- texture taps: per-stream colour coordinates and blend weights at caller-given points -----------------
  * A mesh carries one blendColors colour per vertex: voxel resolution, where the colour cameras deliver far more.  A receiver that already has the
  * colour images (the wire's DXT frames, a recording) needs, per vertex and stream, only WHERE that stream's colour image is read and the two numbers

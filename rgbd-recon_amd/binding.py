@@ -291,6 +291,25 @@ def as_rays(rays):
     return np.ascontiguousarray(rays)
 
 
+def merge_ray_parts(parts):
+    """The merge rule of the header's "ray queries: slab parts" in numpy, for a receiver without a GPU.  parts: per contiguous slab, in slab order, what
+    cast_rays_part returned -- hits, or (hits, surface).  Per ray the part with RAY_HIT and the smallest n_samples wins (no two tie: a sample has one
+    owner), part 0 when none hit; the surface record travels with the winner.  -> hits, or (hits, surface): what cast_rays gives on the whole volume."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("no part to merge")
+    with_surface = isinstance(parts[0], tuple)
+    hits = np.stack([np.ascontiguousarray(p[0] if with_surface else p, RAY_HIT_DTYPE) for p in parts])
+    key = np.where((hits["status"] & RAY_HIT) != 0, hits["n_samples"].astype(np.int64), np.int64(1) << 40)
+    win = np.argmin(key, axis=0)                                         # (the first minimum: part 0 where no part hit)
+    at = np.arange(hits.shape[1])
+    merged = hits[win, at]
+    if not with_surface:
+        return merged
+    surface = np.stack([np.ascontiguousarray(p[1], RAY_SURFACE_DTYPE) for p in parts])
+    return merged, surface[win, at]
+
+
 def make_rays(origin, direction, t_min=0.0, t_max=np.inf):
     """RAY_DTYPE records from origins [n][3] and directions [n][3] (t_min / t_max scalars or [n])"""
     origin = np.asarray(origin, np.float32).reshape(-1, 3)
@@ -1135,6 +1154,34 @@ class ReconIntegrationHip:
         self._ck(self._L.tsdf_cast_rays_dev(self._c, C.c_void_p(int(rays_ptr)), C.c_uint64(int(n)), C.c_uint32(flags), C.c_void_p(int(hits_ptr)),
                                             C.c_void_p(int(surface_ptr)) if surface_ptr else None))
 
+    # ... on Z-slab contexts: every slab casts the same rays and answers for the samples it owns; the parts merge per ray (header: "ray queries: slab parts")
+    def cast_rays_part(self, rays, normals=False, colours=False, unit_cube=False):
+        """This context's part of a cast (tsdf_cast_rays_part): arguments and results as cast_rays.  Works on any context; on a slab the halo must be
+        current, as for a draw.  merge_ray_parts / merge_ray_parts_dev join the parts of contiguous slabs into the whole-volume answer."""
+        rays = as_rays(rays)
+        n = len(rays)
+        flags = (RAYS_UNIT_CUBE if unit_cube else 0) | (RAY_NORMALS if normals else 0) | (RAY_COLOURS if colours else 0)
+        hits = np.zeros(n, RAY_HIT_DTYPE)
+        surface = np.zeros(n, RAY_SURFACE_DTYPE) if (normals or colours) else None
+        self._ck(self._L.tsdf_cast_rays_part(self._c, rays.ctypes.data_as(C.c_void_p), C.c_uint64(n), C.c_uint32(flags), hits.ctypes.data_as(C.c_void_p),
+                                             surface.ctypes.data_as(C.c_void_p) if surface is not None else None))
+        return hits if surface is None else (hits, surface)
+
+    def cast_rays_part_dev(self, rays_ptr, n, hits_ptr, surface_ptr=0, normals=False, colours=False, unit_cube=False):
+        """tsdf_cast_rays_part_dev: raw device pointers to n 32-byte records each; queued on the context's stream, no host wait.  The arrays must stay
+        alive until a later sync()."""
+        flags = (RAYS_UNIT_CUBE if unit_cube else 0) | (RAY_NORMALS if normals else 0) | (RAY_COLOURS if colours else 0)
+        self._ck(self._L.tsdf_cast_rays_part_dev(self._c, C.c_void_p(int(rays_ptr)), C.c_uint64(int(n)), C.c_uint32(flags), C.c_void_p(int(hits_ptr)),
+                                                 C.c_void_p(int(surface_ptr)) if surface_ptr else None))
+
+    def merge_ray_parts_dev(self, hit_parts_ptr, surface_parts_ptr, parts, n, stride_records, hits_ptr, surface_ptr=0):
+        """tsdf_merge_ray_parts_dev: part k's n records start stride_records records behind part k - 1's (the surface parts alike, or 0 for none);
+        queued on the context's stream, no host wait.  Needs no volume: any context merges."""
+        self._ck(self._L.tsdf_merge_ray_parts_dev(self._c, C.c_void_p(int(hit_parts_ptr)) if hit_parts_ptr else None,
+                                                  C.c_void_p(int(surface_parts_ptr)) if surface_parts_ptr else None, C.c_uint32(int(parts)), C.c_uint64(int(n)),
+                                                  C.c_uint64(int(stride_records)), C.c_void_p(int(hits_ptr)) if hits_ptr else None,
+                                                  C.c_void_p(int(surface_ptr)) if surface_ptr else None))
+
     def view_rays(self, mv, proj, rect=None):
         """The draw's own rays (tsdf_view_rays) of the pixel rectangle rect = (x0, y0, w, h), default the whole view: RAY_DTYPE [h * w], row-major,
         unit-cube coordinates -- cast them with unit_cube=True."""
@@ -1149,7 +1196,10 @@ class ReconIntegrationHip:
         hit's unit-cube position `unit`), t, n_samples, status, normal (world), rgba (zeros with colours=False)); hit=False: n_samples and status only."""
         ray = self.view_rays(mv, proj, (int(x), int(y), 1, 1))
         hits, surface = self.cast_rays(ray, normals=True, colours=colours, unit_cube=True)
-        h, s = hits[0], surface[0]
+        return self.pick_result(hits[0], surface[0])
+
+    def pick_result(self, h, s):
+        """pick()'s dict from one unit-cube hit record and its surface record (SlabDriver.pick builds it from the merged parts)"""
         if not (int(h["status"]) & RAY_HIT):
             return dict(hit=False, n_samples=int(h["n_samples"]), status=int(h["status"]))
         lo, hi = self._bbox

@@ -3244,7 +3244,8 @@ int32_t tsdf_mesh_stream_stats(tsdf_ctx* c, uint64_t out[4]) {
 }
 
 // ---- ray queries (k_rays.hip; the definition is in the header, the host bookkeeping in ray_staging.hpp).  The reference has no counterpart.
-static int32_t ray_cast_checks(tsdf_ctx* c, const void* rays, uint64_t n, uint32_t flags, const void* hits, const void* surface) {
+// part: the part cast (tsdf_cast_rays_part / _dev), which any context answers -- a slab its owned samples, a whole-volume context the one-slab case
+static int32_t ray_cast_checks(tsdf_ctx* c, const void* rays, uint64_t n, uint32_t flags, const void* hits, const void* surface, bool part = false) {
   switch (ray_cast_arguments(n, flags, rays != nullptr, hits != nullptr, surface != nullptr)) {
     case 0: break;
     case 1: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "unknown ray flag (1 unit cube, 2 normals, 4 colours)");
@@ -3252,10 +3253,14 @@ static int32_t ray_cast_checks(tsdf_ctx* c, const void* rays, uint64_t n, uint32
     case 3: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "the surface array goes with TSDF_RAY_NORMALS / TSDF_RAY_COLOURS: given exactly when one is set");
     default: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "%llu rays in one cast (at most 2^40)", (unsigned long long)n);
   }
-  return readable_volume_check(c, "ray queries on a Z-slab context: a ray crosses slabs, compositing per-ray partial results is not provided", (flags & TSDF_RAY_COLOURS) != 0);
+  if (part) {
+    if (!c->have_volume) FAIL(c, TSDF_ERR_STATE, "no volume yet (tsdf_integrate or tsdf_upload_volume)");
+    return (flags & TSDF_RAY_COLOURS) ? require_inputs(c, false, true) : TSDF_OK;
+  }
+  return readable_volume_check(c, "ray queries on a Z-slab context: a ray crosses slabs; a slab casts its part with tsdf_cast_rays_part and tsdf_merge_ray_parts_dev merges the parts", (flags & TSDF_RAY_COLOURS) != 0);
 }
 // the launches of one cast on the context's stream, device arrays in and out; no host wait
-static int32_t ray_cast_queue(tsdf_ctx* c, const tsdf_ray* rays, uint64_t n, uint32_t flags, tsdf_ray_hit* hits, tsdf_ray_surface* surface) {
+static int32_t ray_cast_queue(tsdf_ctx* c, const tsdf_ray* rays, uint64_t n, uint32_t flags, tsdf_ray_hit* hits, tsdf_ray_surface* surface, bool part = false) {
   tsdf_ctx::Rays& R = c->rays;
   if (!R.d_list) {                                                       // the context's first cast
     HIP_TRY(c, hipMalloc((void**)&R.d_list, (size_t)kRayChunk * sizeof(RayHitRec)));
@@ -3273,13 +3278,13 @@ static int32_t ray_cast_queue(tsdf_ctx* c, const tsdf_ray* rays, uint64_t n, uin
     const uint64_t first = K.first(k);
     Q.n = K.count(k);
     if (k && surface) HIP_TRY(c, hipMemsetAsync(count, 0, sizeof(uint32_t), c->stream));
-    timer_begin(c, "rays_march");
-    launch_rays_march(c->stream, c->vol, Q, rays + first, hits + first, surface ? surface + first : nullptr, R.d_list, count, R.d_words);
-    timer_end(c, "rays_march");
-    if (surface) {
-      timer_begin(c, "rays_surface");
+    timer_begin(c, part ? "rays_part_march" : "rays_march");
+    (part ? launch_rays_march_part : launch_rays_march)(c->stream, c->vol, Q, rays + first, hits + first, surface ? surface + first : nullptr, R.d_list, count, R.d_words);
+    timer_end(c, part ? "rays_part_march" : "rays_march");
+    if (surface) {                                                       // (serves a part unchanged: the halo covers the taps, a slab holds whole LUTs and frames)
+      timer_begin(c, part ? "rays_part_surface" : "rays_surface");
       launch_rays_surface(c->stream, c->vol, c->luts, c->frame, Q, R.d_list, count, surface + first);
-      timer_end(c, "rays_surface");
+      timer_end(c, part ? "rays_part_surface" : "rays_surface");
     }
   }
   HIP_TRY(c, hipGetLastError());
@@ -3315,6 +3320,54 @@ int32_t tsdf_cast_rays_dev(tsdf_ctx* c, const tsdf_ray* rays_dev, uint64_t n, ui
   HIP_TRY(c, hipSetDevice(c->device));
   return ray_cast_queue(c, rays_dev, n, flags, hits_dev, surface_dev);
 }
+// A slab's part of a cast: the same calls with the part form of the march (the checks, staging, chunking, stream order and the re-recorded draw event
+// are tsdf_cast_rays' and tsdf_cast_rays_dev's)
+int32_t tsdf_cast_rays_part(tsdf_ctx* c, const tsdf_ray* rays, uint64_t n, uint32_t flags, tsdf_ray_hit* hits, tsdf_ray_surface* surface) {
+  CHECK_CTX(c);
+  int32_t rc = ray_cast_checks(c, rays, n, flags, hits, surface, true);
+  if (rc) return rc;
+  if (n == 0) { c->rays.last_n = 0; c->rays.cast = true; return TSDF_OK; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  if ((rc = ray_staging_reserve(c, n, surface != nullptr))) return rc;
+  tsdf_ctx::Rays& R = c->rays;
+  HIP_TRY(c, hipMemcpyAsync(R.d_rays, rays, (size_t)(n * kRayBytes), hipMemcpyHostToDevice, c->stream));
+  if ((rc = ray_cast_queue(c, R.d_rays, n, flags, R.d_hits, surface ? R.d_surf : nullptr, true))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(hits, R.d_hits, (size_t)(n * kRayBytes), hipMemcpyDeviceToHost, c->stream));
+  if (surface) HIP_TRY(c, hipMemcpyAsync(surface, R.d_surf, (size_t)(n * kRayBytes), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, sync_ctx(c));
+  return TSDF_OK;
+}
+int32_t tsdf_cast_rays_part_dev(tsdf_ctx* c, const tsdf_ray* rays_dev, uint64_t n, uint32_t flags, tsdf_ray_hit* hits_dev, tsdf_ray_surface* surface_dev) {
+  CHECK_CTX(c);
+  int32_t rc = ray_cast_checks(c, rays_dev, n, flags, hits_dev, surface_dev, true);
+  if (rc) return rc;
+  if (n == 0) { c->rays.last_n = 0; c->rays.cast = true; return TSDF_OK; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  return ray_cast_queue(c, rays_dev, n, flags, hits_dev, surface_dev, true);
+}
+// the merge of `parts` parts on the context's stream: needs no volume, allocates nothing
+int32_t tsdf_merge_ray_parts_dev(tsdf_ctx* c, const tsdf_ray_hit* hit_parts_dev, const tsdf_ray_surface* surface_parts_dev, uint32_t parts, uint64_t n, uint64_t stride_records,
+                                 tsdf_ray_hit* hits_dev, tsdf_ray_surface* surface_dev) {
+  CHECK_CTX(c);
+  switch (ray_merge_arguments(parts, n, stride_records, hit_parts_dev != nullptr, hits_dev != nullptr, surface_parts_dev != nullptr, surface_dev != nullptr)) {
+    case 0: break;
+    case 1: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "no part to merge (parts == 0)");
+    case 2: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "null hit part / hit array");
+    case 3: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "the surface parts and the merged surface array go together: both or neither");
+    case 4: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "parts lie %llu records apart and hold %llu each", (unsigned long long)stride_records, (unsigned long long)n);
+    default: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "%llu rays x %u parts in one merge (at most 2^40 rays, their parts within 2^48 records)", (unsigned long long)n, parts);
+  }
+  if (n == 0) return TSDF_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const CallChunks K{n, kRayChunk};
+  for (uint64_t k = 0; k < K.launches(); ++k) {
+    const uint64_t first = K.first(k);
+    launch_rays_merge(c->stream, hit_parts_dev + first, surface_parts_dev ? surface_parts_dev + first : nullptr, parts, K.count(k), stride_records, hits_dev + first,
+                      surface_dev ? surface_dev + first : nullptr);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return TSDF_OK;
+}
 int32_t tsdf_view_rays(tsdf_ctx* c, const float* mv, const float* pr, int32_t x0, int32_t y0, int32_t w, int32_t h, tsdf_ray* rays) {
   CHECK_CTX(c);
   if (!mv || !pr || !rays) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "null matrix / ray array");
@@ -3335,7 +3388,7 @@ int32_t tsdf_ray_stats(tsdf_ctx* c, uint64_t out[4]) {
   CHECK_CTX(c);
   if (!out) return TSDF_ERR_INVALID_ARGUMENT;
   const tsdf_ctx::Rays& R = c->rays;
-  if (!R.cast) FAIL(c, TSDF_ERR_STATE, "no cast yet (tsdf_cast_rays / tsdf_cast_rays_dev)");
+  if (!R.cast) FAIL(c, TSDF_ERR_STATE, "no cast yet (tsdf_cast_rays / tsdf_cast_rays_dev / tsdf_cast_rays_part)");
   out[0] = R.last_n; out[1] = out[2] = out[3] = 0;
   if (!R.last_n) return TSDF_OK;
   HIP_TRY(c, hipSetDevice(c->device));

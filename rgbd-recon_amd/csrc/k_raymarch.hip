@@ -167,12 +167,7 @@ __device__ float3 blend_cameras(const StreamTable& T, const FrameImages& F, floa
   if (tw <= 0.0f) tc = make_float3(1.0f, 1.0f, 1.0f);
   return tc;
 }
-// Which slab owns a sample (multi-GPU): the voxel plane floor(pos.z * rz), clamped.
-__device__ __forceinline__ bool sample_owned(const Volume& V, float pz) {
-  const float f = fminf(fmaxf(floorf(pz * (float)V.res[2]), 0.0f), (float)(V.res[2] - 1));
-  const int tz = ((int)f) >> 3;
-  return tz >= V.own_tz0 && tz < V.own_tz1;
-}
+// Which slab owns a sample (multi-GPU): sample_owned, ray_dev.hpp (the ray queries' part form owns samples by the same text)
 
 // K2 runs as two launches.  k_march (one thread per pixel, 8x8 pixel tile per wave) finds the first zero crossing and
 // appends it to a compact hit list; k_shade (one thread per hit, dense waves) does submitFragment().  Rays that hit

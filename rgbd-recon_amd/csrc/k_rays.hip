@@ -16,6 +16,7 @@
 //   k_rays_surface  one lane per HIT, over the list k_rays_march compacted (one atomic per wave, as k_march -> k_shade): the 128-register blend_colors
 //                   runs in dense waves and for hits only.  Results are indexed by ray number, so the list's order shows nowhere.
 //   k_view_rays     the draw's own rays of a pixel rectangle, through pixel_dir_vol (ray_dev.hpp: the function k_march calls).
+//   k_rays_march<., true> / k_rays_merge   a Z-slab context's part of a cast and the merge of the parts (tsdf_cast_rays_part, tsdf_merge_ray_parts_dev).
 #include <cfloat>
 
 #include "blend_dev.hpp"
@@ -35,7 +36,9 @@ __device__ __forceinline__ bool ray_finite(float v) { return fabsf(v) <= FLT_MAX
 // leap: such a position takes the fetching path, which restates the filter whatever it gives)
 __device__ __forceinline__ bool ray_tame(float3 p) { return fabsf(p.x) < 1.0e6f && fabsf(p.y) < 1.0e6f && fabsf(p.z) < 1.0e6f; }
 // every voxel a tap of the positions a .. b (the run's first and last sample; the chain between them is monotonic per axis) can read is -limit
-template <bool kSparse>
+// kPart (a slab's part cast): the caller has found a and b owned, so their taps lie at most one plane outside the owned layers, inside the halo; the
+// test below restates it on the tile layers themselves, so that no lookup can index outside the stored [tz0, tz1) whatever the positions are.
+template <bool kSparse, bool kPart = false>
 __device__ __forceinline__ bool ray_run_clear(const Volume& V, float3 a, float3 b) {
   if (!(ray_tame(a) && ray_tame(b))) return false;
   const Axis ax = axis_linear(a.x, V.res[0]), ay = axis_linear(a.y, V.res[1]), az = axis_linear(a.z, V.res[2]);
@@ -43,6 +46,7 @@ __device__ __forceinline__ bool ray_run_clear(const Volume& V, float3 a, float3 
   const int lx = min(ax.i0, bx.i0) >> 3, ly = min(ay.i0, by.i0) >> 3, lz = min(az.i0, bz.i0) >> 3;
   const int hx = max(ax.i1, bx.i1) >> 3, hy = max(ay.i1, by.i1) >> 3, hz = max(az.i1, bz.i1) >> 3;
   if (hx - lx > 1 || hy - ly > 1 || hz - lz > 1) return false;       // more than two tiles on an axis: not looked up
+  if (kPart && (lz < V.tz0 || hz >= V.tz1)) return false;            // a tile layer this context does not store: not looked up
   bool clear = true;
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
@@ -53,7 +57,23 @@ __device__ __forceinline__ bool ray_run_clear(const Volume& V, float3 a, float3 
   return clear;
 }
 
-template <bool kSparse>
+// kPart: the part cast of a Z-slab context (tsdf_cast_rays_part; the header's "ray queries: slab parts"), as k_march has kPartial.  The lane examines
+// the samples its context owns (sample_owned, ray_dev.hpp: the draw's rule) and nothing else:
+//   - z is monotonic along a chain of additions of one step and the owner plane is monotonic in z, so the owned samples are ONE contiguous run.  The
+//     samples in front of it cost only the reference's `pos += step`; behind it the lane stops (a miss reports max_n, which every slab computes alike).
+//   - inside the run batches are fetched unconditionally with the clamped filter (tex3d_tsdf<kSparse>, not the kWhole form): an owned sample's taps lie
+//     in the stored planes, and whatever else a batch touches is clamped into them and never examined.
+//   - the hit's prev is sample k - 1's density: the lane's own when it examined that sample, else (the run's first sample, with samples in front of it)
+//     fetched at pos_{k-1} from the halo, which is sized for a sample one step behind an owned one (abi.cpp, above halo_layers_for).
+//   - tile-class skipping stays.  A run is tested only when its first and last sample are both owned (then all between are), and ray_run_clear<., true>
+//     refuses any tile layer outside the stored [tz0, tz1).  What cls and slot hold on halo layers (abi.cpp): the class array covers every STORED tile and
+//     is created kTileMixed; TileState::cls points at the first INTEGRATED layer.  Under an exchanged halo integrate() computes the owned layers only,
+//     tsdf_halo_unpack_dev copies voxels and no classes, so halo layers stay kTileMixed for good -- a run that touches one is fetched.  Under a
+//     recomputed halo (the only form a sparse slab takes) the halo layers are integrated like owned ones: their class / slot is what integrate() left,
+//     exact for the voxels the context itself stores and reads.  tsdf_upload_volume marks every integrated tile mixed.  So "clear" is only ever said of
+//     voxels this context wrote as -limit: a wrong "clear" would change bits, a mixed class only costs a fetch.
+// The kPart = false instantiations are the text they were: every addition is behind `if (kPart)`.
+template <bool kSparse, bool kPart>
 __global__ __launch_bounds__(kRayThreads) void k_rays_march(Volume V, RayCast Q, const float4* __restrict__ rays, float4* __restrict__ hits, float4* __restrict__ surf,
                                                             RayHitRec* __restrict__ list, uint32_t* __restrict__ list_count, unsigned long long* __restrict__ stats) {
   const uint32_t i = blockIdx.x * kRayThreads + threadIdx.x;
@@ -105,14 +125,26 @@ __global__ __launch_bounds__(kRayThreads) void k_rays_march(Volume V, RayCast Q,
   float3 hit_pos = pos;
   float hit_d = 0.0f;
   const float ml = -limit;
+  uint32_t owned = 0;                                                   // kPart: owned samples accounted for (n counts the definition's, a neighbour's included)
+  bool prev_mine = true;                                                // kPart: prev is sample n - 1's density (or -limit at n = 0); false: that sample is a neighbour's
+  float3 pos_prev = pos;
+  if (kPart) {
+    while (n < max_n && !sample_owned(V, pos.z)) {                      // in front of the run: the additions alone
+      pos_prev = pos;
+      pos = make_float3(pos.x + step.x, pos.y + step.y, pos.z + step.z);
+      n += 1; prev_mine = false;
+    }
+  }
   while (n < max_n && !hit) {
+    if (kPart && !sample_owned(V, pos.z)) break;                        // behind the run: nothing further is ours
     if (try_skip) {
       const uint32_t m = min((uint32_t)Q.run, max_n - n);
       float3 e = pos;
       for (uint32_t k = 1; k < m; ++k) e = make_float3(e.x + step.x, e.y + step.y, e.z + step.z);
-      if (ray_run_clear<kSparse>(V, pos, e)) {
+      if ((!kPart || sample_owned(V, e.z)) && ray_run_clear<kSparse, kPart>(V, pos, e)) {
         pos = make_float3(e.x + step.x, e.y + step.y, e.z + step.z);
         n += m; prev = ml;
+        if (kPart) { owned += m; prev_mine = true; }
         continue;
       }
       try_skip = false;
@@ -123,19 +155,27 @@ __global__ __launch_bounds__(kRayThreads) void k_rays_march(Volume V, RayCast Q,
 #pragma unroll
     for (int k = 1; k < kRayBatch; ++k) p[k] = make_float3(p[k - 1].x + step.x, p[k - 1].y + step.y, p[k - 1].z + step.z);
 #pragma unroll
-    for (int k = 0; k < kRayBatch; ++k) dv[k] = tex3d_tsdf<kSparse, true>(V, p[k].x, p[k].y, p[k].z);   // unconditional: taps are clamped into the allocation
+    for (int k = 0; k < kRayBatch; ++k) dv[k] = tex3d_tsdf<kSparse, !kPart>(V, p[k].x, p[k].y, p[k].z);   // unconditional: taps are clamped into the allocation
     bool all_clear = true;
+    bool mine = true;                                                   // kPart: p[0] is owned; the first sample that is not ends the run
 #pragma unroll
     for (int k = 0; k < kRayBatch; ++k) {
-      if (!hit && n < max_n) {
+      if (kPart) mine = mine && sample_owned(V, p[k].z);
+      if (!hit && n < max_n && mine) {
         n += 1; fetched += 1;
         all_clear &= dv[k] == ml;
         if (dv[k] > 0.0f) { hit = true; hit_pos = p[k]; hit_d = dv[k]; }   // (a NaN density compares as no hit, as in the draw)
-        else prev = dv[k];
+        else { prev = dv[k]; if (kPart) prev_mine = true; }
+        if (kPart) owned += 1;
       }
     }
+    if (kPart && !mine) break;                                          // the batch left the slab
     if (!hit) pos = make_float3(p[kRayBatch - 1].x + step.x, p[kRayBatch - 1].y + step.y, p[kRayBatch - 1].z + step.z);
     try_skip = all_clear;                                               // back in empty space: look at the classes again
+  }
+  if (kPart) {
+    if (!hit) n = max_n;                                                // a part's miss: max_n, identical on every slab
+    else if (!prev_mine) prev = tex3d_tsdf<kSparse>(V, pos_prev.x, pos_prev.y, pos_prev.z);   // sample n - 1 is a neighbour's: read it from the halo
   }
   float3 pu = make_float3(0, 0, 0), pw = make_float3(0, 0, 0);
   float t = -1.0f;
@@ -167,7 +207,7 @@ __global__ __launch_bounds__(kRayThreads) void k_rays_march(Volume V, RayCast Q,
     }
   }
   // tsdf_ray_stats: hits, samples accounted for, samples fetched
-  uint32_t sa = n, sf = fetched;
+  uint32_t sa = kPart ? owned : n, sf = fetched;                        // (a part accounts for the samples it owns)
   for (int s = 32; s; s >>= 1) { sa += (uint32_t)__shfl_xor((int)sa, s); sf += (uint32_t)__shfl_xor((int)sf, s); }   // (a wave's sums: 64 x max_n, far below 2^32 at n_cap)
   if (ln == 0) {
     if (hm) atomicAdd(&stats[0], (unsigned long long)__popcll(hm));
@@ -208,11 +248,43 @@ __global__ __launch_bounds__(kRayThreads) void k_view_rays(ViewParams P, int x0,
   rays[2 * i + 1] = make_float4(d.x, d.y, d.z, __int_as_float(0x7f800000));
 }
 
+// The merge of K slabs' parts (tsdf_merge_ray_parts_dev): one lane per ray.  The decision reads the K second halves of the hit records ({n_samples,
+// status, pad}: one 16-byte load each) -- the part with TSDF_RAY_HIT and the smallest n_samples, part 0 when none hit; no two parts tie, a sample has one
+// owner --, then the winner's first half and its two surface halves move as 16-byte loads and stores.  No atomics, no LDS; parts are stride records apart.
+__global__ __launch_bounds__(kRayThreads) void k_rays_merge(const float4* __restrict__ hit_parts, const float4* __restrict__ surf_parts, uint32_t parts, uint32_t n,
+                                                            unsigned long long stride, float4* __restrict__ hits, float4* __restrict__ surf) {
+  const uint32_t i = blockIdx.x * kRayThreads + threadIdx.x;
+  if (i >= n) return;
+  const size_t at = 2 * (size_t)i, pitch = 2 * (size_t)stride;          // in 16-byte halves
+  uint32_t win = 0, best = 0xffffffffu;
+  float4 tail = hit_parts[at + 1];
+  for (uint32_t k = 0; k < parts; ++k) {
+    const float4 t = hit_parts[(size_t)k * pitch + at + 1];
+    const uint32_t ns = __float_as_uint(t.x), status = __float_as_uint(t.y);
+    if ((status & TSDF_RAY_HIT) && ns < best) { best = ns; win = k; tail = t; }
+  }
+  const size_t from = (size_t)win * pitch + at;
+  hits[at] = hit_parts[from];
+  hits[at + 1] = tail;
+  if (surf) { surf[at] = surf_parts[from]; surf[at + 1] = surf_parts[from + 1]; }
+}
+
 void launch_rays_march(hipStream_t st, const Volume& V, const RayCast& Q, const tsdf_ray* rays, tsdf_ray_hit* hits, tsdf_ray_surface* surf, RayHitRec* list,
                        uint32_t* list_count, unsigned long long* stats) {
   const dim3 g((Q.n + kRayThreads - 1) / kRayThreads), b(kRayThreads);
-  if (V.slot) hipLaunchKernelGGL(k_rays_march<true>, g, b, 0, st, V, Q, (const float4*)rays, (float4*)hits, (float4*)surf, list, list_count, stats);
-  else hipLaunchKernelGGL(k_rays_march<false>, g, b, 0, st, V, Q, (const float4*)rays, (float4*)hits, (float4*)surf, list, list_count, stats);
+  if (V.slot) hipLaunchKernelGGL((k_rays_march<true, false>), g, b, 0, st, V, Q, (const float4*)rays, (float4*)hits, (float4*)surf, list, list_count, stats);
+  else hipLaunchKernelGGL((k_rays_march<false, false>), g, b, 0, st, V, Q, (const float4*)rays, (float4*)hits, (float4*)surf, list, list_count, stats);
+}
+void launch_rays_march_part(hipStream_t st, const Volume& V, const RayCast& Q, const tsdf_ray* rays, tsdf_ray_hit* hits, tsdf_ray_surface* surf, RayHitRec* list,
+                            uint32_t* list_count, unsigned long long* stats) {
+  const dim3 g((Q.n + kRayThreads - 1) / kRayThreads), b(kRayThreads);
+  if (V.slot) hipLaunchKernelGGL((k_rays_march<true, true>), g, b, 0, st, V, Q, (const float4*)rays, (float4*)hits, (float4*)surf, list, list_count, stats);
+  else hipLaunchKernelGGL((k_rays_march<false, true>), g, b, 0, st, V, Q, (const float4*)rays, (float4*)hits, (float4*)surf, list, list_count, stats);
+}
+void launch_rays_merge(hipStream_t st, const tsdf_ray_hit* hit_parts, const tsdf_ray_surface* surf_parts, uint32_t parts, uint32_t n, uint64_t stride_records,
+                       tsdf_ray_hit* hits, tsdf_ray_surface* surf) {
+  hipLaunchKernelGGL(k_rays_merge, dim3((n + kRayThreads - 1) / kRayThreads), dim3(kRayThreads), 0, st, (const float4*)hit_parts, (const float4*)surf_parts, parts, n,
+                     (unsigned long long)stride_records, (float4*)hits, (float4*)surf);
 }
 void launch_rays_surface(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const RayCast& Q, const RayHitRec* list,
                          const uint32_t* list_count, tsdf_ray_surface* surf) {

@@ -22,6 +22,17 @@ inline int ray_cast_arguments(uint64_t n, uint32_t flags, bool have_rays, bool h
   if (n > kRayMaxCount) return 4;
   return 0;
 }
+// The merge of slab parts (tsdf_merge_ray_parts_dev).  0: acceptable; 1: no part; 2: a NULL hit array with n > 0; 3: exactly one of the two surface
+// arrays; 4: parts closer together than their n records; 5: more than the entries index (n as a cast's, and parts * stride below 2^48 records)
+inline int ray_merge_arguments(uint32_t parts, uint64_t n, uint64_t stride_records, bool have_hit_parts, bool have_hits, bool have_surface_parts, bool have_surface) {
+  if (parts == 0) return 1;
+  if (n == 0) return 0;
+  if (!have_hit_parts || !have_hits) return 2;
+  if (have_surface_parts != have_surface) return 3;
+  if (stride_records < n) return 4;
+  if (n > kRayMaxCount || stride_records > (1ull << 48) / parts) return 5;
+  return 0;
+}
 // 0, or what is wrong with the pixel rectangle of tsdf_view_rays in a view of vw x vh: 1 empty or negative, 2 outside the view
 inline int ray_view_rect(int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t vw, int32_t vh) {
   if (w <= 0 || h <= 0 || x0 < 0 || y0 < 0) return 1;

@@ -475,6 +475,11 @@ void launch_rays_march(hipStream_t st, const Volume& V, const RayCast& Q, const 
                        uint32_t* list_count, unsigned long long* stats);
 void launch_rays_surface(hipStream_t st, const Volume& V, const StreamTable& T, const FrameImages& F, const RayCast& Q, const RayHitRec* list,
                          const uint32_t* list_count, tsdf_ray_surface* surf);
+// the part cast of a Z-slab context (the samples it owns; stats[1] counts those) and the merge of `parts` parts that lie stride_records apart
+void launch_rays_march_part(hipStream_t st, const Volume& V, const RayCast& Q, const tsdf_ray* rays, tsdf_ray_hit* hits, tsdf_ray_surface* surf, RayHitRec* list,
+                            uint32_t* list_count, unsigned long long* stats);
+void launch_rays_merge(hipStream_t st, const tsdf_ray_hit* hit_parts, const tsdf_ray_surface* surf_parts, uint32_t parts, uint32_t n, uint64_t stride_records,
+                       tsdf_ray_hit* hits, tsdf_ray_surface* surf);
 void launch_view_rays(hipStream_t st, const ViewParams& P, int x0, int y0, int w, int h, tsdf_ray* rays);
 // texture taps (k_texture_taps.hip): one launch serves at most kTapsChunk points (texture_taps.hpp), one lane per (point, stream) pair, blockIdx.y = stream
 struct TapsLaunch {

@@ -511,6 +511,35 @@ class ReconIntegrationHip {
     check(tsdf_ray_stats(m_ctx, s));
     return RayStats{s[0], s[1], s[2], s[3]};
   }
+  // ... where the volume is split into Z-slabs (tsdf_cast_rays_part): every slab's operator casts the SAME rays and answers for the samples it owns;
+  // mergeRayParts joins the parts of contiguous slabs, in slab order, into what castRays gives on the whole volume -- per ray the part that hit with the
+  // fewest samples, part 0 when none hit, the surface record with it.  Plain C++: the receiver of the parts needs no GPU.
+  void castRaysPart(const std::vector<tsdf_ray>& rays, RayResults& out, bool normals = false, bool colours = false, bool unit_cube = false) {
+    const std::uint32_t flags = (unit_cube ? TSDF_RAYS_UNIT_CUBE : 0u) | (normals ? TSDF_RAY_NORMALS : 0u) | (colours ? TSDF_RAY_COLOURS : 0u);
+    out.hits.assign(rays.size(), tsdf_ray_hit{});
+    out.surface.assign((normals || colours) ? rays.size() : 0, tsdf_ray_surface{});
+    check(tsdf_cast_rays_part(m_ctx, rays.data(), rays.size(), flags, out.hits.data(), out.surface.empty() ? nullptr : out.surface.data()));
+  }
+  static void mergeRayParts(const std::vector<RayResults>& parts, RayResults& out) {
+    out.hits.clear(); out.surface.clear();
+    if (parts.empty()) return;
+    const std::size_t n = parts[0].hits.size();
+    const bool surface = !parts[0].surface.empty();
+    for (const RayResults& p : parts)
+      if (p.hits.size() != n || p.surface.size() != (surface ? n : 0)) throw std::invalid_argument("mergeRayParts: the parts answer different casts");
+    out.hits.resize(n);
+    out.surface.resize(surface ? n : 0);
+    for (std::size_t i = 0; i < n; ++i) {
+      std::size_t win = 0;
+      std::uint32_t best = 0xffffffffu;
+      for (std::size_t k = 0; k < parts.size(); ++k) {
+        const tsdf_ray_hit& h = parts[k].hits[i];
+        if ((h.status & TSDF_RAY_HIT) && h.n_samples < best) { best = h.n_samples; win = k; }
+      }
+      out.hits[i] = parts[win].hits[i];
+      if (surface) out.surface[i] = parts[win].surface[i];
+    }
+  }
   // ---- texture taps (tsdf_texture_taps): camera-resolution colour for a receiver of the mesh.  The reference has no counterpart: its client runs
   // blendColors per pixel against the colour images and the LUT volumes.  textureTaps gives, per point (world coordinates, or the volume's unit cube) and
   // stream, where that stream's colour image is read and the two numbers blendColors weights the read with; meshTextureTaps the same at the vertices of the

@@ -48,7 +48,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .binding import join_mesh_parts
+from .binding import RAY_HIT_DTYPE, RAY_SURFACE_DTYPE, as_rays, join_mesh_parts, merge_ray_parts
 
 
 def worker_slab_range(res_z: int, rank: int, world: int):
@@ -429,6 +429,57 @@ class SlabDriver:
             out["frame"] = None if any(p[2]["overflow"] for p in parts) else join_mesh_parts(parts)
         return out
 
+    # ------------------------------------------------------------------ ray queries: every slab casts its part, rank 0 merges
+    def cast_rays(self, rays, normals=False, colours=False, unit_cube=False):
+        """A COLLECTIVE: every rank casts the SAME rays on its slab (tsdf_cast_rays_part_dev; the halo must be current, as after frame()), the parts go
+        to rank 0 through the driver's gather, and rank 0 merges them on the device (tsdf_merge_ray_parts_dev).  Rank 0 returns what cast_rays of a
+        whole-volume context gives -- hits, or (hits, surface) with normals or colours --, the other ranks None.  A dedicated compositor casts nothing
+        and merges the workers' parts.  With host buffers (the tests' stand-in backend) the parts are cast and merged on the host by the same rule."""
+        rays = as_rays(rays)
+        n, want = len(rays), bool(normals or colours)
+        rows, cuda = (2 if want else 1), self.dev.type == "cuda"
+        with self._on_stream():
+            mine = torch.zeros((rows, n, 32), dtype=torch.uint8, device=self.dev)      # [hit records][surface records]
+            if self.is_worker and cuda:
+                d_rays = torch.from_numpy(rays.view(np.uint8).reshape(n, 32).copy()).to(self.dev)
+                if self.stream is None:
+                    torch.cuda.synchronize(self.dev)                     # the context runs on its own stream: the buffers must exist before it writes them
+                self.b.cast_rays_part_dev(d_rays.data_ptr(), n, mine[0].data_ptr(), mine[1].data_ptr() if want else 0, normals, colours, unit_cube)
+                if self.stream is None:
+                    self.b.sync()
+            elif self.is_worker:
+                part = self.b.cast_rays_part(rays, normals=normals, colours=colours, unit_cube=unit_cube)
+                for row, a in enumerate(part if want else (part,)):
+                    mine[row] = torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(n, 32).copy())
+            parts = mine[None]
+            if self.world > 1:
+                parts = torch.zeros((self.world, rows, n, 32), dtype=torch.uint8, device=self.dev) if self.rank == 0 else None
+                self._gather0([parts[r].view(-1) for r in range(self.world)] if self.rank == 0 else None, mine.view(-1))
+            if self.rank != 0:
+                return None
+            parts = parts[self.first_worker:]                            # (a compositor without a slab has no part)
+            if cuda:                                                     # part k: its hit records, then its surface records -- rows * n records apart
+                out = torch.zeros((rows, n, 32), dtype=torch.uint8, device=self.dev)
+                if self.stream is None:
+                    torch.cuda.synchronize(self.dev)
+                self.b.merge_ray_parts_dev(parts[0, 0].data_ptr(), parts[0, 1].data_ptr() if want else 0, parts.shape[0], n, rows * n, out[0].data_ptr(),
+                                           out[1].data_ptr() if want else 0)
+                if self.stream is None:
+                    self.b.sync()
+                got = out.cpu().numpy()                                  # (on self.stream: behind the merge)
+                hits = got[0].reshape(-1).view(RAY_HIT_DTYPE)
+                return (hits, got[1].reshape(-1).view(RAY_SURFACE_DTYPE)) if want else hits
+            got = parts.numpy()
+            each = [(p[0].reshape(-1).view(RAY_HIT_DTYPE), p[1].reshape(-1).view(RAY_SURFACE_DTYPE)) if want else p[0].reshape(-1).view(RAY_HIT_DTYPE) for p in got]
+            return merge_ray_parts(each)
+
+    def pick(self, mv, proj, x, y, colours=True):
+        """A COLLECTIVE: what is under pixel (x, y) of the view, as ReconIntegrationHip.pick -- the pixel's own ray (tsdf_view_rays needs no volume: every
+        rank forms the same ray), then cast_rays.  Rank 0 returns pick()'s dict, the other ranks None."""
+        ray = self.b.view_rays(mv, proj, (int(x), int(y), 1, 1))
+        got = self.cast_rays(ray, normals=True, colours=colours, unit_cube=True)
+        return None if got is None else self.b.pick_result(got[0][0], got[1][0])
+
     def finish(self):
         """Completes the latest frame: call before reading its result (and at the end of a timed region).  A COLLECTIVE when
         the compact gather of that frame turned out too small -- every rank sees the same counts and re-gathers together."""
@@ -470,6 +521,31 @@ def mesh_slabs_on_one_device(backends, normals=True, colours=True, level=0):
     out = {key: np.concatenate([p[key] for p in parts]) for key in parts[0]}
     out["counts"], out["seams"] = counts, seams
     return out
+
+
+def rays_slabs_on_one_device(backends, rays, normals=False, colours=False, unit_cube=False, device="cuda:0"):
+    """SlabDriver.cast_rays with ONE visible device: backends[k] owns slab k (contiguous, in z order), each with a current halo (as
+    frame_slabs_on_one_device leaves it; nothing here touches a halo).  Every slab casts the same rays into its row of one gather buffer
+    (tsdf_cast_rays_part_dev), backends[0] merges the rows on the device (tsdf_merge_ray_parts_dev).  Returns dict(hits, surface (None without an
+    attribute), parts=[(hits, surface)] per slab, stats=[ray_stats()] per slab): hits and surface are what cast_rays of a whole-volume context gives."""
+    rays = as_rays(rays)
+    n, world, want_surface = len(rays), len(backends), bool(normals or colours)
+    u8 = dict(dtype=torch.uint8, device=device)
+    d_rays = torch.from_numpy(rays.view(np.uint8).reshape(n, 32).copy()).to(device)
+    hit_parts, hits = torch.zeros((world, n, 32), **u8), torch.zeros((n, 32), **u8)
+    surf_parts, surf = (torch.zeros((world, n, 32), **u8), torch.zeros((n, 32), **u8)) if want_surface else (None, None)
+    torch.cuda.synchronize()                      # the contexts run on their own streams: the buffers must exist before they write them
+    stats = []
+    for k, b in enumerate(backends):
+        b.cast_rays_part_dev(d_rays.data_ptr(), n, hit_parts[k].data_ptr(), surf_parts[k].data_ptr() if want_surface else 0, normals, colours, unit_cube)
+        stats.append(b.ray_stats())               # (waits for the cast: the merge below runs on another context's stream)
+    backends[0].merge_ray_parts_dev(hit_parts.data_ptr(), surf_parts.data_ptr() if want_surface else 0, world, n, n, hits.data_ptr(),
+                                    surf.data_ptr() if want_surface else 0)
+    backends[0].sync()
+    as_hits = lambda t: t.cpu().numpy().reshape(-1).view(RAY_HIT_DTYPE)
+    as_surf = lambda t: t.cpu().numpy().reshape(-1).view(RAY_SURFACE_DTYPE)
+    return dict(hits=as_hits(hits), surface=as_surf(surf) if want_surface else None, stats=stats,
+                parts=[(as_hits(hit_parts[k]), as_surf(surf_parts[k]) if want_surface else None) for k in range(world)])
 
 
 def mesh_parts_on_one_device(backends, tag=0):
