@@ -22,9 +22,6 @@
 using namespace rrhost;
 
 namespace {
-constexpr int kLag = 2;                       // frames between a hit count and its use as a gather size: its pinned copy has long arrived
-constexpr int kRing = kLag + 1;
-
 struct Rccl {
   void* lib = nullptr;
   ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
@@ -73,83 +70,52 @@ const char* rccl_why() { return rccl_state().why.c_str(); }            // why rc
 #define NCCL_TRY_IN_GROUP(c, expr) do { ncclResult_t _r = (expr); if (_r != ncclSuccess) { rccl()->GroupEnd(); FAIL(c, TSDF_ERR_HIP, "%s failed: %s (%s:%d)", #expr, rccl()->GetErrorString(_r), __FILE__, __LINE__); } } while (0)
 #define NEED_COMM(c) do { CHECK_CTX(c); if (!(c)->comm.comm) FAIL(c, TSDF_ERR_STATE, "no communicator (tsdf_comm_init)"); } while (0)
 
-bool is_worker(const tsdf_ctx* c) { return !(c->comm.dedicated && c->comm.rank == 0); }
-int first_worker(const tsdf_ctx* c) { return c->comm.dedicated ? 1 : 0; }
-
 void release_comm_buffers(tsdf_ctx* c) {
   tsdf_ctx::Comm& M = c->comm;
   hipFree(M.d_halo_send); hipFree(M.d_halo_gath); hipFree(M.d_hitbuf); hipFree(M.d_hitparts); hipFree(M.d_counts); hipFree(M.d_frame_stage);
-  for (int k = 0; k < kRing; ++k) { if (M.h_counts[k]) hipHostFree(M.h_counts[k]); if (M.counts_evt[k]) hipEventDestroy(M.counts_evt[k]); }
-  tsdf_ctx::Comm fresh;                                                 // the communicator, the roles and the statistics stay
-  fresh.comm = M.comm; fresh.rank = M.rank; fresh.world = M.world; fresh.dedicated = M.dedicated;
-  fresh.regathers = M.regathers; fresh.overflowed_frames = M.overflowed_frames; fresh.min_capacity = M.min_capacity; fresh.max_capacity = M.max_capacity;
+  for (int k = 0; k < GatherBook::kRing; ++k) { if (M.h_counts[k]) hipHostFree(M.h_counts[k]); if (M.counts_evt[k]) hipEventDestroy(M.counts_evt[k]); }
+  tsdf_ctx::Comm fresh;                                                 // the communicator and the roles stay; of the book, what released() keeps
+  fresh.comm = M.comm; fresh.roles = M.roles; fresh.book = M.book;
+  fresh.book.released();
   M = fresh;
 }
 
-// the all-gathered [written, hit] counts of frame f on the host (waits for their pinned copy: for f <= now - kLag it arrived long ago)
-const int32_t* counts_of(tsdf_ctx* c, uint64_t f) {
+// the largest per-rank hit count among the all-gathered [written, hit] counts in ring slot `slot` (waits for their pinned copy: for a frame
+// GatherBook::kLag frames back it arrived long ago)
+uint32_t max_hits(tsdf_ctx* c, int slot) {
   tsdf_ctx::Comm& M = c->comm;
-  const int slot = (int)(f % kRing);
-  if (M.counts_rec[slot]) hipEventSynchronize(M.counts_evt[slot]);
-  return M.h_counts[slot];
-}
-uint32_t max_hits(tsdf_ctx* c, uint64_t f) {
-  const int32_t* h = counts_of(c, f);
+  if (M.book.recorded(slot)) hipEventSynchronize(M.counts_evt[slot]);
+  const int32_t* h = M.h_counts[slot];
   int32_t m = 0;
-  for (int r = 0; r < c->comm.world; ++r) m = std::max(m, h[2 * r + 1]);
+  for (int r = 0; r < M.roles.world; ++r) m = std::max(m, h[2 * r + 1]);
   return (uint32_t)m;
 }
-void set_verdict(tsdf_ctx* c, uint64_t f, bool truncated) {
-  tsdf_ctx::Comm& M = c->comm;
-  const int k = (int)(f % tsdf_ctx::Comm::kVerdicts);
-  M.verdict_frame[k] = f; M.verdict[k] = truncated ? 1 : 0; M.verdict_set[k] = true;
-}
-// records gathered per rank for frame f: 1.5 x the largest per-rank hit count of frame f - kLag (every rank computes the same number).
-// The frame whose counts are read here was gathered with caps[...]: if it hit more rays than that and was not the latest frame when
-// tsdf_composite_finish ran, it was composited from truncated lists -- counted, so that a caller can tell.
-uint32_t capacity_for(tsdf_ctx* c, uint64_t f) {
-  tsdf_ctx::Comm& M = c->comm;
-  const uint32_t npx = M.max_capacity ? std::min(M.max_capacity, (uint32_t)(c->vw * c->vh)) : (uint32_t)(c->vw * c->vh);
-  if (f < (uint64_t)kLag) return npx;                                   // no history yet: a slab cannot hit more rays than there are pixels
-  const uint32_t m = max_hits(c, f - kLag);
-  const bool truncated = m > M.caps[(f - kLag) % kRing];               // (tsdf_composite_finish raises the capacity of a frame it repairs)
-  if (truncated) ++M.overflowed_frames;
-  set_verdict(c, f - kLag, truncated);
-  const uint32_t cap = std::max(M.min_capacity, ((m * 3u) / 2u + 1024u + 1023u) / 1024u * 1024u);
-  return std::min(cap, npx);
-}
 
-// Rank 0's own records never travel: it exports them -- ALL of them, whatever the capacity of the gather -- straight into its row of the
-// gather buffer, once per frame.  (They must not be exported again for a repeated gather: the first composite has overwritten the march
-// target they are read from.)
-int32_t exchange_hits(tsdf_ctx* c, uint32_t cap, bool first, uint64_t f) {
+// One exchange of `cap` records per rank, then rank 0 composites.  first: the frame's first exchange, which also all-gathers the hit counts into the
+// ring slot the book names; a repeated one (tsdf_composite_finish) does not.  Who exports what, sends and receives: SlabRoles
+int32_t exchange_hits(tsdf_ctx* c, uint32_t cap, bool first) {
   tsdf_ctx::Comm& M = c->comm;
+  const SlabRoles& P = M.roles;
   Rccl* R = rccl();
-  float* const own = M.rank == 0 ? M.d_hitparts : M.d_hitbuf;
-  if (is_worker(c) && (first || M.rank != 0)) {                         // (a compositor's header stays {0 records, 0 hits})
-    if (int32_t rc = tsdf_export_hits_dev(c, own, M.rank == 0 ? (uint32_t)(c->vw * c->vh) : cap)) return rc;
+  float* const own = P.own_in_parts() ? M.d_hitparts : M.d_hitbuf;
+  if (P.exports(first)) {
+    if (int32_t rc = tsdf_export_hits_dev(c, own, P.export_records((uint32_t)(c->vw * c->vh), cap))) return rc;
   }
-  const bool record_counts = first;
-  if (record_counts) {
+  if (first) {
     NCCL_TRY(c, R->AllGather(own, M.d_counts, 2, ncclInt32, (ncclComm_t)M.comm, c->stream));
-    const int slot = (int)(f % kRing);
-    HIP_TRY(c, hipMemcpyAsync(M.h_counts[slot], M.d_counts, (size_t)M.world * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    const int slot = M.book.open_slot();
+    HIP_TRY(c, hipMemcpyAsync(M.h_counts[slot], M.d_counts, (size_t)P.world * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipEventRecord(M.counts_evt[slot], c->stream));
-    M.counts_rec[slot] = true;
-    M.caps[slot] = cap;
   }
-  const size_t n = 8 + (size_t)cap * 8;                                 // floats: header + records
-  if (M.world > 1) {
+  const size_t n = SlabRoles::exchange_floats(cap);
+  if (P.grouped()) {
     NCCL_TRY(c, R->GroupStart());
-    if (M.rank == 0) {
-      for (int r = 1; r < M.world; ++r) NCCL_TRY_IN_GROUP(c, R->Recv(M.d_hitparts + (size_t)r * M.hit_floats, n, ncclFloat, r, (ncclComm_t)M.comm, c->stream));
-    } else {
-      NCCL_TRY_IN_GROUP(c, R->Send(M.d_hitbuf, n, ncclFloat, 0, (ncclComm_t)M.comm, c->stream));
-    }
+    for (int r = P.recv_begin(); r < P.world; ++r) NCCL_TRY_IN_GROUP(c, R->Recv(M.d_hitparts + SlabRoles::row_offset(r, M.hit_floats), n, ncclFloat, r, (ncclComm_t)M.comm, c->stream));
+    if (P.send_to() != SlabRoles::kNone) NCCL_TRY_IN_GROUP(c, R->Send(M.d_hitbuf, n, ncclFloat, P.send_to(), (ncclComm_t)M.comm, c->stream));
     NCCL_TRY(c, R->GroupEnd());
   }
-  if (M.rank == 0) {
-    if (int32_t rc = tsdf_composite_hits_dev(c, M.d_hitparts, (uint32_t)M.world, (uint64_t)M.hit_floats * sizeof(float))) return rc;
+  if (P.gathers()) {
+    if (int32_t rc = tsdf_composite_hits_dev(c, M.d_hitparts, (uint32_t)P.world, (uint64_t)M.hit_floats * sizeof(float))) return rc;
     if (c->fill_holes) { if (int32_t rc = tsdf_fill_colors(c)) return rc; }
   }
   return TSDF_OK;
@@ -185,7 +151,7 @@ int32_t tsdf_comm_init(tsdf_ctx* c, const uint8_t id[TSDF_COMM_ID_BYTES], uint32
   NCCL_TRY(c, R->CommInitRank(&comm, (int)world, u, (int)rank));        // (collective: every rank of the world calls it, each on its own device)
   tsdf_ctx::Comm& M = c->comm;
   M = tsdf_ctx::Comm{};
-  M.comm = comm; M.rank = (int)rank; M.world = (int)world; M.dedicated = dedicated;
+  M.comm = comm; M.roles = SlabRoles{(int)rank, (int)world, dedicated};
   return TSDF_OK;
 }
 
@@ -205,7 +171,7 @@ int32_t tsdf_comm_destroy(tsdf_ctx* c) {
 int32_t tsdf_comm_set_capacity_limits(tsdf_ctx* c, uint32_t min_records, uint32_t max_records) {
   NEED_COMM(c);
   if (min_records < 1 || (max_records && max_records < min_records)) return TSDF_ERR_INVALID_ARGUMENT;
-  c->comm.min_capacity = min_records; c->comm.max_capacity = max_records;
+  c->comm.book.set_limits(min_records, max_records);
   return TSDF_OK;
 }
 // Was frame `frame` (0 = the first tsdf_composite_gather of this communicator's buffers) composited from TRUNCATED record lists and left that way?
@@ -216,22 +182,23 @@ int32_t tsdf_comm_set_capacity_limits(tsdf_ctx* c, uint32_t min_records, uint32_
 int32_t tsdf_comm_frame_status(tsdf_ctx* c, uint64_t frame, int32_t* truncated) {
   NEED_COMM(c);
   if (!truncated) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "null argument");
-  tsdf_ctx::Comm& M = c->comm;
-  if (frame >= M.frame_no) FAIL(c, TSDF_ERR_STATE, "frame %llu has not been gathered yet (%llu frames so far)", (unsigned long long)frame, (unsigned long long)M.frame_no);
-  const int k = (int)(frame % tsdf_ctx::Comm::kVerdicts);
-  if (M.verdict_set[k] && M.verdict_frame[k] == frame) { *truncated = M.verdict[k]; return TSDF_OK; }
-  if (frame + kRing >= M.frame_no) {                                     // its counts are still in the ring of pinned copies
-    HIP_TRY(c, hipSetDevice(c->device));
-    const bool t = max_hits(c, frame) > M.caps[frame % kRing];
-    *truncated = t ? 1 : 0;                                              // (not stored: the latest frame may still be repaired by tsdf_composite_finish)
-    return TSDF_OK;
+  const GatherBook::Status S = c->comm.book.status(frame);
+  switch (S.kind) {
+    case GatherBook::Status::kNotGathered:
+      FAIL(c, TSDF_ERR_STATE, "frame %llu has not been gathered yet (%llu frames so far)", (unsigned long long)frame, (unsigned long long)c->comm.book.frame_no);
+    case GatherBook::Status::kVerdict: *truncated = S.truncated; return TSDF_OK;
+    case GatherBook::Status::kCompare:                                    // its counts are still in the ring of pinned copies
+      HIP_TRY(c, hipSetDevice(c->device));
+      *truncated = max_hits(c, S.slot) > S.cap ? 1 : 0;
+      return TSDF_OK;
+    default: break;
   }
-  FAIL(c, TSDF_ERR_STATE, "the verdict of frame %llu is no longer kept (the last %d frames are)", (unsigned long long)frame, tsdf_ctx::Comm::kVerdicts);
+  FAIL(c, TSDF_ERR_STATE, "the verdict of frame %llu is no longer kept (the last %d frames are)", (unsigned long long)frame, GatherBook::kVerdicts);
 }
 int32_t tsdf_comm_stats(tsdf_ctx* c, uint32_t* regathers, uint32_t* overflowed_frames) {
   NEED_COMM(c);
-  if (regathers) *regathers = c->comm.regathers;
-  if (overflowed_frames) *overflowed_frames = c->comm.overflowed_frames;
+  if (regathers) *regathers = c->comm.book.regathers;
+  if (overflowed_frames) *overflowed_frames = c->comm.book.overflowed_frames;
   return TSDF_OK;
 }
 
@@ -240,14 +207,15 @@ int32_t tsdf_comm_stats(tsdf_ctx* c, uint32_t* regathers, uint32_t* overflowed_f
 int32_t tsdf_broadcast_frame(tsdf_ctx* c, uint32_t root, const float* depth_rg, const float* quality, const float* silhouette, const uint8_t* colour) {
   NEED_COMM(c);
   tsdf_ctx::Comm& M = c->comm;
-  if ((int)root >= M.world) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "root out of range");
+  const SlabRoles& P = M.roles;
+  if ((int)root >= P.world) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "root out of range");
   HIP_TRY(c, hipSetDevice(c->device));
   const FrameImages& F = c->frame;
   const size_t np = (size_t)c->cfg.num_streams * F.w * F.h, nc = (size_t)c->cfg.num_streams * F.cw * F.ch;
   const size_t bytes = np * 16 + ((nc * 3 + 15) & ~(size_t)15);         // [depth_rg 8 B][quality 4 B][silhouette 4 B] per pixel, then RGB8
   if (!M.d_frame_stage) { HIP_TRY(c, hipMalloc((void**)&M.d_frame_stage, bytes)); M.frame_stage_bytes = bytes; }
   uint8_t* st = (uint8_t*)M.d_frame_stage;
-  if ((int)root == M.rank) {
+  if ((int)root == P.rank) {
     if (!depth_rg || !quality || !silhouette || !colour) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "the root passes all four arrays");
     // (hipMemcpyDefault: the root's arrays may lie in host memory -- pinned, for a copy that really is asynchronous -- or in device memory)
     HIP_TRY(c, hipMemcpyAsync(st, depth_rg, np * 8, hipMemcpyDefault, c->stream));
@@ -255,14 +223,15 @@ int32_t tsdf_broadcast_frame(tsdf_ctx* c, uint32_t root, const float* depth_rg, 
     HIP_TRY(c, hipMemcpyAsync(st + np * 12, silhouette, np * 4, hipMemcpyDefault, c->stream));
     HIP_TRY(c, hipMemcpyAsync(st + np * 16, colour, nc * 3, hipMemcpyDefault, c->stream));
   }
-  if (M.world > 1) NCCL_TRY(c, rccl()->Broadcast(st, st, bytes, ncclUint8, (int)root, (ncclComm_t)M.comm, c->stream));
-  if (!is_worker(c)) return TSDF_OK;                                    // a compositor without a slab reads no frame
+  if (P.grouped()) NCCL_TRY(c, rccl()->Broadcast(st, st, bytes, ncclUint8, (int)root, (ncclComm_t)M.comm, c->stream));
+  if (!P.worker()) return TSDF_OK;                                      // a compositor without a slab reads no frame
   return tsdf_upload_frame_dev(c, (const float*)st, (const float*)(st + np * 8), (const float*)(st + np * 12), st + np * 16, 0);   // (behind the broadcast on the context's stream)
 }
 
 int32_t tsdf_halo_exchange(tsdf_ctx* c) {
   NEED_COMM(c);
   tsdf_ctx::Comm& M = c->comm;
+  const SlabRoles& P = M.roles;
   HIP_TRY(c, hipSetDevice(c->device));
   uint32_t layers = 0; uint64_t face_bytes = 0;
   tsdf_halo_info(c, &layers, &face_bytes);
@@ -271,15 +240,16 @@ int32_t tsdf_halo_exchange(tsdf_ctx* c) {
     HIP_TRY(c, sync_ctx(c));
     hipFree(M.d_halo_send); hipFree(M.d_halo_gath); M.d_halo_send = M.d_halo_gath = nullptr;
     HIP_TRY(c, hipMalloc((void**)&M.d_halo_send, 2 * n * sizeof(float)));
-    HIP_TRY(c, hipMalloc((void**)&M.d_halo_gath, (size_t)M.world * 2 * n * sizeof(float)));
+    HIP_TRY(c, hipMalloc((void**)&M.d_halo_gath, (size_t)P.world * 2 * n * sizeof(float)));
     HIP_TRY(c, hipMemsetAsync(M.d_halo_send, 0, 2 * n * sizeof(float), c->stream));       // (a compositor sends these zeros: nobody reads them)
     M.halo_floats = n;
   }
-  if (is_worker(c)) { if (int32_t rc = tsdf_halo_pack_dev(c, M.d_halo_send, M.d_halo_send + n)) return rc; }
+  if (P.worker()) { if (int32_t rc = tsdf_halo_pack_dev(c, M.d_halo_send, M.d_halo_send + n)) return rc; }
   NCCL_TRY(c, rccl()->AllGather(M.d_halo_send, M.d_halo_gath, 2 * n, ncclFloat, (ncclComm_t)M.comm, c->stream));
-  if (!is_worker(c)) return TSDF_OK;                                    // (took part in the collective; has no slab faces of its own)
-  const float* below = M.rank > first_worker(c) ? M.d_halo_gath + ((size_t)(M.rank - 1) * 2 + 1) * n : nullptr;   // the lower neighbour's HIGH face
-  const float* above = M.rank < M.world - 1 ? M.d_halo_gath + ((size_t)(M.rank + 1) * 2 + 0) * n : nullptr;       // the upper neighbour's LOW face
+  if (!P.worker()) return TSDF_OK;                                      // (took part in the collective; has no slab faces of its own)
+  const SlabRoles::Face lo = P.below(), hi = P.above();                 // the lower neighbour's HIGH face, the upper neighbour's LOW face
+  const float* below = lo.row != SlabRoles::kNone ? M.d_halo_gath + SlabRoles::face_offset(lo, n) : nullptr;
+  const float* above = hi.row != SlabRoles::kNone ? M.d_halo_gath + SlabRoles::face_offset(hi, n) : nullptr;
   return tsdf_halo_unpack_dev(c, below, above);
 }
 
@@ -287,29 +257,30 @@ int32_t tsdf_composite_gather(tsdf_ctx* c) {
   NEED_COMM(c);
   tsdf_ctx::Comm& M = c->comm;
   HIP_TRY(c, hipSetDevice(c->device));
-  const size_t npx = (size_t)c->vw * c->vh, hf = 8 + npx * 8;
+  const SlabRoles& P = M.roles;
+  const size_t hf = SlabRoles::row_floats((size_t)c->vw * c->vh);
   if (!(M.d_hitbuf || M.d_hitparts) || M.hit_floats != hf) {
     HIP_TRY(c, sync_ctx(c));
-    release_comm_buffers(c);
-    if (M.rank != 0) {
+    release_comm_buffers(c);                                            // (the book counts frames from 0 again)
+    if (!P.gathers()) {
       HIP_TRY(c, hipMalloc((void**)&M.d_hitbuf, hf * sizeof(float)));
       HIP_TRY(c, hipMemsetAsync(M.d_hitbuf, 0, hf * sizeof(float), c->stream));
+    } else {
+      HIP_TRY(c, hipMalloc((void**)&M.d_hitparts, (size_t)P.world * hf * sizeof(float)));
+      HIP_TRY(c, hipMemsetAsync(M.d_hitparts, 0, (size_t)P.world * hf * sizeof(float), c->stream));
     }
-    if (M.rank == 0) { HIP_TRY(c, hipMalloc((void**)&M.d_hitparts, (size_t)M.world * hf * sizeof(float))); HIP_TRY(c, hipMemsetAsync(M.d_hitparts, 0, (size_t)M.world * hf * sizeof(float), c->stream)); }
-    HIP_TRY(c, hipMalloc((void**)&M.d_counts, (size_t)M.world * 2 * sizeof(int32_t)));
-    for (int k = 0; k < kRing; ++k) {
-      HIP_TRY(c, hipHostMalloc((void**)&M.h_counts[k], (size_t)M.world * 2 * sizeof(int32_t), hipHostMallocDefault));
-      memset(M.h_counts[k], 0, (size_t)M.world * 2 * sizeof(int32_t));
+    HIP_TRY(c, hipMalloc((void**)&M.d_counts, (size_t)P.world * 2 * sizeof(int32_t)));
+    for (int k = 0; k < GatherBook::kRing; ++k) {
+      HIP_TRY(c, hipHostMalloc((void**)&M.h_counts[k], (size_t)P.world * 2 * sizeof(int32_t), hipHostMallocDefault));
+      memset(M.h_counts[k], 0, (size_t)P.world * 2 * sizeof(int32_t));
       HIP_TRY(c, hipEventCreateWithFlags(&M.counts_evt[k], hipEventDisableTiming));
     }
-    M.hit_floats = hf; M.frame_no = 0; M.have_last = false;
-    for (bool& b : M.verdict_set) b = false;
+    M.hit_floats = hf;
   }
-  const uint64_t f = M.frame_no;
-  const uint32_t cap = capacity_for(c, f);
-  if (int32_t rc = exchange_hits(c, cap, true, f)) return rc;
-  M.have_last = true; M.last_frame = f; M.last_cap = cap;
-  M.frame_no = f + 1;
+  const int lagged = M.book.lagged_slot();                              // (none for the first kLag frames: no history yet)
+  const uint32_t cap = M.book.open((uint32_t)(c->vw * c->vh), lagged >= 0 ? max_hits(c, lagged) : 0);
+  if (int32_t rc = exchange_hits(c, cap, true)) return rc;
+  M.book.queued(cap);
   return TSDF_OK;
 }
 
@@ -320,17 +291,13 @@ int32_t tsdf_composite_finish(tsdf_ctx* c, uint32_t* regathered) {
   tsdf_ctx::Comm& M = c->comm;
   HIP_TRY(c, hipSetDevice(c->device));
   if (regathered) *regathered = 0;
-  if (M.have_last) {
-    M.have_last = false;
-    const uint32_t m = max_hits(c, M.last_frame);
-    if (m > M.last_cap) {
-      ++M.regathers;
+  const int pending = M.book.pending_slot();
+  if (pending >= 0) {
+    const GatherBook::Repair fix = M.book.finish((uint32_t)(c->vw * c->vh), max_hits(c, pending));
+    if (fix.regather) {
       if (regathered) *regathered = 1;
-      const uint32_t cap = std::min((uint32_t)(c->vw * c->vh), m);
-      if (int32_t rc = exchange_hits(c, cap, false, M.last_frame)) return rc;
-      M.caps[M.last_frame % kRing] = cap;
+      if (int32_t rc = exchange_hits(c, fix.cap, false)) return rc;
     }
-    set_verdict(c, M.last_frame, false);                                 // complete: gathered in full, or repaired just now
   }
   HIP_TRY(c, sync_ctx(c));
   return TSDF_OK;

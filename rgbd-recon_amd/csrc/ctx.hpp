@@ -12,6 +12,7 @@
 #include "frame_intake.hpp"
 #include "result_paths.hpp"
 #include "volume_sets.hpp"
+#include "slab_exchange.hpp"
 #include "ray_staging.hpp"
 #include "texture_taps.hpp"
 
@@ -223,21 +224,18 @@ struct tsdf_ctx {
   LaneAhead ahead{};
   hipStream_t pre_stream = nullptr; hipEvent_t pre_done = nullptr, pre_gate[2] = {nullptr, nullptr}, src_ready = nullptr;
   uint8_t* d_flags[2]{}; uint32_t* d_occupied[2]{};                             // the two occupancy sets (Bricks::flags / occupied point at the latest update's)
-  // native multi-GPU exchange (comm.cpp): one RCCL communicator per context, every collective on the context's stream
+  // The native multi-GPU exchange (comm.cpp: one RCCL communicator per context, every collective on the context's stream): the state and its protocol
+  // are slab_exchange.hpp's -- who owns a slab, exports, sends and receives, which rows of the gathered halo are a rank's neighbours, and of the compact
+  // composite which ring slot a frame's hit counts land in, the capacity it is gathered with, when tsdf_composite_finish gathers it again, which frames
+  // were left truncated.  Here: the communicator and the buffers and events it indexes
   struct Comm {
     void* comm = nullptr;                     // ncclComm_t
-    int rank = 0, world = 1;
-    bool dedicated = false;                   // rank 0 holds no slab: it only receives, composites and fills holes
+    SlabRoles roles{};
+    GatherBook book{};
     float* d_halo_send = nullptr; float* d_halo_gath = nullptr; size_t halo_floats = 0;   // 2 faces / world x 2 faces
     float* d_hitbuf = nullptr; float* d_hitparts = nullptr; size_t hit_floats = 0;        // 32-byte header + one 32-byte record per view pixel; rank 0: x world
     int32_t* d_counts = nullptr;              // [world][2]: records written, rays hit
-    int32_t* h_counts[3] = {nullptr, nullptr, nullptr}; hipEvent_t counts_evt[3] = {nullptr, nullptr, nullptr}; bool counts_rec[3] = {false, false, false};
-    uint32_t caps[3] = {0, 0, 0};             // capacity each of the ring's frames was gathered with
-    uint64_t frame_no = 0; bool have_last = false; uint64_t last_frame = 0; uint32_t last_cap = 0;
-    uint32_t regathers = 0, overflowed_frames = 0, min_capacity = 4096, max_capacity = 0;   // max_capacity: 0 = one record per pixel
-    // per-frame verdict of the compact composite (tsdf_comm_frame_status): 1 = the frame was composited from truncated record lists and not repaired
-    static constexpr int kVerdicts = 64;
-    uint64_t verdict_frame[kVerdicts] = {}; uint8_t verdict[kVerdicts] = {}; bool verdict_set[kVerdicts] = {};
+    int32_t* h_counts[GatherBook::kRing] = {}; hipEvent_t counts_evt[GatherBook::kRing] = {};   // the ring of pinned copies of d_counts, an event behind each copy
     float* d_frame_stage = nullptr; size_t frame_stage_bytes = 0;                          // tsdf_broadcast_frame: the four arrays as delivered
   } comm;
   bool timers_on = false;

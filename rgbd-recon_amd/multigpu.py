@@ -48,6 +48,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .slab_exchange import NONE, GatherBook, SlabRoles
 from .binding import RAY_HIT_DTYPE, RAY_SURFACE_DTYPE, as_rays, join_mesh_parts, merge_ray_parts
 
 
@@ -111,7 +112,7 @@ class SlabDriver:
                backend only needs the view (worker_slab_range() gives the workers' slabs) -- and never integrates or marches.
     """
 
-    LAG = 2            # frames between a hit count and its use as the gather size: its pinned copy has long arrived, the host never waits
+    LAG = GatherBook.LAG   # frames between a hit count and its use as the gather size: its pinned copy has long arrived, the host never waits
 
     def __init__(self, backend, rank, world, buf_device, group=None, view=(1280, 720), halo="exchange", composite="dense", preprocess=False,
                  exchange_when_alone=False, stream=None, min_capacity=4096, compositor="shared", native=False, max_capacity=0):
@@ -123,8 +124,8 @@ class SlabDriver:
         assert not self.native or composite == "compact", "the native exchange gathers hit records (compact composite)"
         assert compositor == "shared" or world >= 2, "a dedicated compositor needs at least one worker rank"
         self.dedicated = compositor == "dedicated"
-        self.is_worker = not (self.dedicated and rank == 0)          # owns a slab: marks bricks, integrates, marches, exports
-        self.first_worker = 1 if self.dedicated else 0
+        self.roles = SlabRoles(rank, world, self.dedicated)          # who owns a slab, exports, which halo rows are its neighbours (slab_exchange.py)
+        self.is_worker, self.first_worker = self.roles.worker, self.roles.first_worker
         self.b, self.rank, self.world, self.dev, self.group = backend, rank, world, torch.device(buf_device), group
         self.view, self.halo, self.composite = view, halo, composite
         self.preprocess = preprocess          # frames start from the raw sensor images: processTextures() instead of markBricks()
@@ -137,20 +138,17 @@ class SlabDriver:
             self.stream = stream if stream is not None else torch.cuda.Stream(self.dev)
             assert self.stream.cuda_stream != 0, "the NULL stream cannot be handed to tsdf_set_stream"
             backend.set_stream(self.stream.cuda_stream)
-        self.frame_no = 0
-        self.caps = {}                        # frame -> capacity it was gathered with, until its counts have been looked at
-        self.last = None                      # (frame number, gathered capacity) of the latest compact frame, until finish() has checked it
-        self.regathers = 0                    # frames whose first gather was too small (finish() repaired them)
-        self.min_capacity = int(min_capacity)
-        self.overflowed_frames = 0            # frames that were composited from truncated record lists and were no longer the latest when finish() ran
-        self.verdicts = {}                    # frame -> was it left truncated (frame_status)
+        # The compact composite's frame bookkeeping -- capacities, ring slots, repairs, verdicts, the two statistics -- is the book's (slab_exchange.py,
+        # the twin of the library's).  No maximum here: max_capacity bounds the NATIVE exchange's guess only (recorded behaviour)
+        self.book = GatherBook(min_capacity)
+        self.last = None                      # a compact frame is pending until finish() has checked it
         if self.exchanging and self.native:
             ids = [backend.comm_unique_id() if rank == 0 else None]
             if world > 1:
                 dist.broadcast_object_list(ids, src=0, group=group)
             with self._on_stream():
                 backend.comm_init(ids[0], rank, world, dedicated_compositor=self.dedicated)
-                backend.comm_set_capacity_limits(self.min_capacity, max_capacity)
+                backend.comm_set_capacity_limits(int(min_capacity), max_capacity)
             self.stage_cpu = False
         elif self.exchanging:
             npx = view[0] * view[1]
@@ -169,11 +167,15 @@ class SlabDriver:
                     self.hitbuf = torch.zeros(8 + npx * 8, dtype=torch.float32, device=self.dev)     # 32 B header + 32 B records; a slab cannot hit more rays than there are pixels
                     self.hitparts = torch.zeros((world, 8 + npx * 8), dtype=torch.float32, device=self.dev) if rank == 0 else None
                     self.counts = torch.zeros((world, 2), dtype=torch.int32, device=self.dev)        # per rank: [records written, rays hit]
-                    ring = self.LAG + 1
-                    self.counts_host = [torch.zeros((world, 2), dtype=torch.int32, pin_memory=(self.dev.type == "cuda")) for _ in range(ring)]
-                    self.counts_evt = [None] * ring
+                    self.counts_host = [torch.zeros((world, 2), dtype=torch.int32, pin_memory=(self.dev.type == "cuda")) for _ in range(GatherBook.RING)]
+                    self.counts_evt = [None] * GatherBook.RING
             if self.stream is not None:
                 self.stream.synchronize()
+
+    # frames gathered by the torch path; frames finish() repaired / frames left truncated (native: refreshed from the library's by finish())
+    frame_no = property(lambda self: self.book.frame_no)
+    regathers = property(lambda self: self.book.regathers)
+    overflowed_frames = property(lambda self: self.book.overflowed_frames)
 
     # ------------------------------------------------------------------ plumbing
     def _on_stream(self):
@@ -205,34 +207,22 @@ class SlabDriver:
         self._all_gather(self.gath, self.send)
         if not self.is_worker:
             return                                                   # (took part in the collective; has no slab faces of its own)
-        below = self.gath[self.rank - 1, 1].data_ptr() if self.rank > self.first_worker else 0
-        above = self.gath[self.rank + 1, 0].data_ptr() if self.rank < self.world - 1 else 0
-        b.halo_unpack_dev(below, above)
+        lo, hi = self.roles.below(), self.roles.above()              # the lower neighbour's HIGH face, the upper neighbour's LOW face
+        b.halo_unpack_dev(self.gath[lo].data_ptr() if lo[0] != NONE else 0, self.gath[hi].data_ptr() if hi[0] != NONE else 0)
 
     # ------------------------------------------------------------------ compact composite: sizes without a host sync
-    def _counts_of(self, f):
-        """the all-gathered [written, hit] counts of frame f on the host (waits for their pinned copy: for f <= now - LAG it arrived long ago)"""
-        slot = f % (self.LAG + 1)
+    def _max_hits(self, slot):
+        """the largest per-rank hit count among the all-gathered [written, hit] counts in ring slot `slot` (waits for their pinned copy: for a frame
+        LAG frames back it arrived long ago)"""
         if self.counts_evt[slot] is not None:
             self.counts_evt[slot].synchronize()
-        return self.counts_host[slot]
+        return int(self.counts_host[slot][:, 1].max())
 
     def _capacity(self, f):
-        """records gathered per rank for frame f: 1.5 x the largest per-rank hit count of frame f - LAG (the same number on every rank)"""
-        if f < self.LAG:
-            return self.npx                                # no history yet: a slab cannot hit more rays than there are pixels
-        m = int(self._counts_of(f - self.LAG)[:, 1].max())
-        truncated = m > self.caps.get(f - self.LAG, self.npx)   # that frame hit more rays than were gathered (finish() repairs the LATEST frame only)
-        if truncated:
-            self.overflowed_frames += 1
-        self._set_verdict(f - self.LAG, truncated)
-        self.caps.pop(f - self.LAG, None)
-        cap = max(self.min_capacity, ((m * 3) // 2 + 1024 + 1023) // 1024 * 1024)
-        return min(cap, self.npx)
-
-    def _set_verdict(self, f, truncated):
-        self.verdicts[f] = bool(truncated)
-        self.verdicts.pop(f - 64, None)                    # the last 64 frames are kept (comm.cpp keeps the same ring)
+        """records gathered per rank for frame f, the one about to be gathered: 1.5 x the largest per-rank hit count of frame f - LAG (the same
+        number on every rank)"""
+        slot = self.book.lagged_slot()
+        return self.book.open(self.npx, self._max_hits(slot) if slot != NONE else 0)
 
     def frame_status(self, f):
         """True: frame f (counted from 0) of the compact composite was built from truncated record lists and not repaired -- a caller that kept
@@ -240,32 +230,31 @@ class SlabDriver:
         KeyError: not gathered yet / too old.  (tsdf_comm_frame_status is the same rule inside the library.)"""
         if self.exchanging and self.native:
             return self.b.comm_frame_status(f)
-        if f in self.verdicts:
-            return self.verdicts[f]
-        if f < self.frame_no and f + self.LAG + 1 >= self.frame_no:
-            cap = self.caps.get(f, self.last[1] if self.last is not None and self.last[0] == f else self.npx)
-            return int(self._counts_of(f)[:, 1].max()) > cap
+        kind, truncated, slot, cap = self.book.status(f)
+        if kind == GatherBook.VERDICT:
+            return bool(truncated)
+        if kind == GatherBook.COMPARE:
+            return self._max_hits(slot) > cap
         raise KeyError(f"no verdict for frame {f} ({self.frame_no} frames gathered)")
 
-    def _exchange_hits(self, cap, record_counts_of=None):
-        """record_counts_of: the frame number on the frame's first exchange, None on a repeated one (finish()).  Rank 0's own records never
+    def _exchange_hits(self, cap, first):
+        """first: the frame's first exchange, which also all-gathers the hit counts; False on a repeated one (finish()).  Rank 0's own records never
         travel: it exports them -- ALL of them, whatever the capacity of the gather -- straight into its row of the gather buffer, once
         per frame (a repeated gather must not export them again: the first composite has overwritten the march target they are read from)."""
-        b = self.b
-        first = record_counts_of is not None
-        own = self.hitparts[0] if self.rank == 0 else self.hitbuf
-        if self.is_worker and (first or self.rank != 0):
-            b.export_hits_dev(own.data_ptr(), self.npx if self.rank == 0 else cap)     # (a compositor's header stays {0 records, 0 hits})
-        if record_counts_of is not None:
+        b, roles = self.b, self.roles
+        own = self.hitparts[0] if roles.own_in_parts else self.hitbuf
+        if roles.exports(first):
+            b.export_hits_dev(own.data_ptr(), roles.export_records(self.npx, cap))     # (a compositor's header stays {0 records, 0 hits})
+        if first:
             self._all_gather(self.counts, own[:2].view(torch.int32))
-            slot = record_counts_of % (self.LAG + 1)
+            slot = self.book.open_slot()
             self.counts_host[slot].copy_(self.counts, non_blocking=True)
             if self.stream is not None:
                 ev = self.counts_evt[slot] or torch.cuda.Event()
                 ev.record(self.stream)
                 self.counts_evt[slot] = ev
-        n = 8 + cap * 8
-        if self.world > 1:      # (rank 0's contribution to the collective is a header-sized dummy: its row is in place already)
+        n = roles.exchange_floats(cap)
+        if roles.grouped:       # (rank 0's contribution to the collective is a header-sized dummy: its row is in place already)
             if self.rank == 0 and getattr(self, "selfrow", None) is None:
                 self.selfrow = torch.zeros_like(self.hitbuf)
             self._gather0([self.selfrow[:n]] + [self.hitparts[r, :n] for r in range(1, self.world)] if self.rank == 0 else None, self.hitbuf[:n])
@@ -354,12 +343,10 @@ class SlabDriver:
                 b.composite_dev(self.parts.data_ptr(), self.world)
                 b.fillColors()
             return
-        f = self.frame_no
-        cap = self._capacity(f)
-        self._exchange_hits(cap, record_counts_of=f)
-        self.caps[f] = cap
-        self.last = (f, cap)
-        self.frame_no = f + 1
+        cap = self._capacity(self.frame_no)
+        self._exchange_hits(cap, first=True)
+        self.book.queued(cap)
+        self.last = True
 
     # ------------------------------------------------------------------ the fused surface as ONE mesh, extracted where the volume is
     def extract_mesh(self, normals=True, colours=True, level=0):
@@ -489,17 +476,13 @@ class SlabDriver:
                 with self._on_stream():
                     self.b.composite_finish()
                 st = self.b.comm_stats()
-                self.regathers, self.overflowed_frames = st["regathers"], st["overflowed_frames"]
+                self.book.regathers, self.book.overflowed_frames = st["regathers"], st["overflowed_frames"]
         elif self.exchanging and self.composite == "compact" and self.last is not None:
-            f, cap = self.last
             self.last = None
-            m = int(self._counts_of(f)[:, 1].max())
-            if m > cap:
-                self.regathers += 1
-                self.caps[f] = min(self.npx, m)
+            regather, cap = self.book.finish(self.npx, self._max_hits(self.book.pending_slot()))
+            if regather:
                 with self._on_stream():
-                    self._exchange_hits(min(self.npx, m))
-            self._set_verdict(f, False)                      # complete: gathered in full, or repaired just now
+                    self._exchange_hits(cap, first=False)
         if self.stream is not None:
             self.stream.synchronize()
         elif hasattr(self.b, "sync"):

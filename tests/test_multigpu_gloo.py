@@ -251,25 +251,33 @@ def test_compact_composite_sizes_its_gather_without_a_host_sync_and_repairs_over
 
 def test_capacity_rule():
     """1.5 x the largest per-rank hit count of LAG frames ago + 1024, rounded up to 1024, at least min_capacity, at most every pixel"""
-    mgpu = import_module("rgbd-recon_amd.multigpu")
+    Book = import_module("rgbd-recon_amd.slab_exchange").GatherBook
+    npx = 921600
+    counts = {0: [[10, 10], [7000, 9000]], 1: [[0, 0], [0, 0]], 5: [[1, 900000], [1, 5]]}     # frame -> per rank [written, hit]; the other frames hit nothing
+    hits = lambda f: max(h for _, h in counts.get(f, [[0, 0]]))
 
-    class D(mgpu.SlabDriver):
-        def __init__(self, counts, npx, min_capacity):
-            self.npx, self.min_capacity, self._c = npx, min_capacity, counts
-            self.caps, self.overflowed_frames, self.verdicts = {}, 0, {}
+    def gathered(frames, finish_after=()):
+        """the capacities a book hands frames 0 .. frames - 1, fed the counts above the way SlabDriver feeds them; finish() behind the frames named"""
+        book, caps = Book(4096), []
+        for f in range(frames):
+            assert book.frame_no == f and book.lagged_slot() == (-1 if f < 2 else (f - 2) % 3)
+            caps.append(book.open(npx, hits(f - 2) if f >= 2 else 0))
+            book.queued(caps[-1])
+            if f in finish_after:
+                book.finish(npx, hits(f))
+        return book, caps
 
-        def _counts_of(self, f):
-            return torch.tensor(self._c[f], dtype=torch.int32)
-
-    d = D({0: [[10, 10], [7000, 9000]], 1: [[0, 0], [0, 0]], 5: [[1, 900000], [1, 5]]}, 921600, 4096)
-    assert d._capacity(0) == 921600 and d._capacity(1) == 921600              # no history
-    assert d._capacity(2) == 15360                                            # 1.5 * 9000 + 1024 = 14524 -> the next multiple of 1024
-    assert d._capacity(3) == 4096                                             # nothing hit two frames ago: the floor
-    assert d._capacity(7) == 921600                                           # capped at one record per pixel
-    assert d.overflowed_frames == 0
+    # frame 5 was the latest when finish() ran: repaired (gathered again with its 900000 records), not counted
+    d, caps = gathered(8, finish_after=(5,))
+    assert caps[0] == 921600 and caps[1] == 921600                            # no history
+    assert caps[2] == 15360                                                   # 1.5 * 9000 + 1024 = 14524 -> the next multiple of 1024
+    assert caps[3] == 4096                                                    # nothing hit two frames ago: the floor
+    assert caps[7] == 921600                                                  # capped at one record per pixel
+    assert d.overflowed_frames == 0 and d.regathers == 1
     # ADVICE r02: a frame that hit more rays than were gathered for it, and was no longer the latest when finish() ran, is counted
-    d.caps[5] = 4096                                                          # frame 5 was gathered with 4096 records; rank 0 hit 900000 rays
-    d._capacity(7)
+    d, caps = gathered(7)
+    assert caps[5] == 4096 and d.overflowed_frames == 0                       # frame 5 was gathered with 4096 records; rank 0 hit 900000 rays
+    assert d.open(npx, hits(5)) == 921600
     assert d.overflowed_frames == 1
 
 
