@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "tsdf_common.hpp"
+#include "grid_plan.hpp"
 
 using namespace rr;
 
@@ -27,17 +28,7 @@ thread_local std::string g_create_error;
 
 namespace rrhost {       // host-side helpers (shared with comm.cpp through ctx.hpp where declared there)
 
-// n / d == (n * m) >> k for every n < 2^27: with l = ceil(log2 d), k = 27 + l and m = floor(2^k / d) + 1 = (2^k + e) / d, 0 < e <= d <= 2^l,
-// the product is n / d + n e / (d 2^k) with n e < 2^27 2^l = 2^k, i.e. less than 1 / d above the true quotient: the floor is the same.
-// (tile ids stay below 2^27: resolutions are capped at 4096 = 512 tiles per axis)
-FastDiv make_fast_div(uint32_t d) {
-  uint32_t l = 0;
-  while ((1ull << l) < d) ++l;
-  FastDiv f;
-  f.k = 27 + l;
-  f.m = (uint32_t)(((1ull << f.k) / d) + 1);
-  return f;
-}
+static_assert(kAtlasMaxLods == TSDF_MAX_LODS, "grid_plan.hpp mirrors TSDF_MAX_LODS");
 
 // ---- small double-precision matrix kit (column-major), results rounded once to float
 void mat_mul_d(const double* a, const double* b, double* o) {
@@ -126,31 +117,18 @@ int32_t staging_reserve(tsdf_ctx* c, CallStaging& G, uint64_t n, bool want_extra
 void release_bricks(tsdf_ctx* c) {
   for (int k = 0; k < 2; ++k) { hipFree(c->d_counters[k]); hipFree(c->d_flags[k]); hipFree(c->d_occupied[k]); c->d_counters[k] = nullptr; c->d_flags[k] = nullptr; c->d_occupied[k] = nullptr; }
   c->br.counters = nullptr; c->br.flags = nullptr; c->br.num_occupied = nullptr; c->br.occupied = nullptr;
-  for (int a = 0; a < 3; ++a) {
-    hipFree(c->d_vox_first[a]); hipFree(c->d_vox_count[a]); hipFree(c->d_tile_b0[a]); hipFree(c->d_tile_b1[a]); hipFree(c->d_tile_full[a]); c->d_tile_full[a] = nullptr;
-    hipFree(c->d_brick_t0[a]); hipFree(c->d_brick_t1[a]);
-    c->d_vox_first[a] = nullptr; c->d_vox_count[a] = nullptr; c->d_tile_b0[a] = nullptr; c->d_tile_b1[a] = nullptr;
-    c->d_brick_t0[a] = nullptr; c->d_brick_t1[a] = nullptr;
-  }
+  hipFree(c->d_brick_tables); c->d_brick_tables = nullptr;
 }
 
-// ViewLod::setResolution, view_lod.cpp:24-50; resize(), recon_integration.cpp:482-500
+// resize(), recon_integration.cpp:482-500; the atlas: AtlasPlan (grid_plan.hpp)
 int32_t setup_view(tsdf_ctx* c, uint32_t w, uint32_t h) {
-  if (w < 2 || h < 2 || w > 16384 || h > 16384) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "view size %ux%u out of range", w, h);
+  const AtlasPlan P = AtlasPlan::of(w, h);
+  if (!P.ok) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "view size %ux%u out of range", w, h);
   release_view(c);
   c->vw = (int)w; c->vh = (int)h;
   Atlas& A = c->atlas;
-  A.num_lods = 1 + (int)floorf(log2f((float)std::min(w, h)));
-  if (A.num_lods > TSDF_MAX_LODS) A.num_lods = TSDF_MAX_LODS;
-  A.aw = (int)((float)w * 1.5f);
-  A.h = (int)h;
-  int ox = (int)w, oy = (int)h;
-  for (int i = 0; i < TSDF_MAX_LODS; ++i) { A.off[i][0] = A.off[i][1] = A.res[i][0] = A.res[i][1] = 0; }
-  for (int i = 0; i < A.num_lods; ++i) {
-    A.res[i][0] = (int)floorf((float)w / powf(2.0f, (float)i));
-    A.res[i][1] = (int)floorf((float)h / powf(2.0f, (float)i));
-    if (i > 0) { oy -= A.res[i][1]; A.off[i][0] = ox; A.off[i][1] = oy; }
-  }
+  A.num_lods = P.num_lods; A.aw = P.aw; A.h = P.h;
+  memcpy(A.off, P.off, sizeof(A.off)); memcpy(A.res, P.res, sizeof(A.res));
   const size_t na = (size_t)A.aw * A.h, nv = (size_t)w * h;
   HIP_TRY(c, hipMalloc(&A.color, na * sizeof(float4)));
   HIP_TRY(c, hipMalloc(&A.depth, na * sizeof(float)));
@@ -183,98 +161,36 @@ int32_t setup_view(tsdf_ctx* c, uint32_t w, uint32_t h) {
   return TSDF_OK;
 }
 
-// setBrickSize + divideBox, recon_integration.cpp:462-472, :360-406, with the per-brick voxel lists of
-// VolumeSampler::containedVoxels (volume_sampler.cpp:50-62) kept as per-axis ranges.
-int32_t setup_bricks(tsdf_ctx* c, const float req[3]) {
-  for (int a = 0; a < 3; ++a) if (!(req[a] > 0.0f)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "brick size must be > 0");
+// The brick grid: BrickPlan (grid_plan.hpp).  A refused plan's message, with nothing touched
+int32_t refuse_bricks(tsdf_ctx* c, const BrickPlan& P, const float req[3]) {
+  switch (P.error) {
+    case BrickPlan::kNotPositive: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "brick size must be > 0");
+    case BrickPlan::kRoundsToZero: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "brick size %g rounds to zero voxels", req[P.error_axis]);
+    case BrickPlan::kTooManyBricks: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "more than 65535 bricks along one axis");
+    case BrickPlan::kDegenerateOverlap: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "degenerate brick/voxel overlap on axis %d", P.error_axis);
+    default: return TSDF_OK;
+  }
+}
+// ... and an accepted one's: release, allocate and upload (the 21 tables as one blob), bind
+int32_t build_bricks(tsdf_ctx* c, const BrickPlan& P, const float req[3]) {
   release_bricks(c);
   memcpy(c->brick_req, req, sizeof(float) * 3);
   Bricks& B = c->br;
-  const float bmin[3] = {c->cfg.bbox_min[0], c->cfg.bbox_min[1], c->cfg.bbox_min[2]};
-  float ext[3];
+  for (int a = 0; a < 3; ++a) { B.size[a] = P.size[a]; B.res[a] = P.res[a]; B.bbox_min[a] = c->cfg.bbox_min[a]; }
+  B.n = P.n;
+  const std::vector<uint8_t> blob = P.blob();
+  HIP_TRY(c, hipMalloc(&c->d_brick_tables, blob.size()));
+  HIP_TRY(c, hipMemcpy(c->d_brick_tables, blob.data(), blob.size(), hipMemcpyHostToDevice));
   for (int a = 0; a < 3; ++a) {
-    ext[a] = c->cfg.bbox_max[a] - c->cfg.bbox_min[a];
-    B.size[a] = c->vox[a] * roundf(req[a] / c->vox[a]);                 // :463
-    if (!(B.size[a] > 0.0f)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "brick size %g rounds to zero voxels", req[a]);
-    B.bbox_min[a] = bmin[a];
-  }
-  // the three nested while loops of divideBox() are separable: per axis, the sequence of brick starts
-  std::vector<float> starts[3];
-  for (int a = 0; a < 3; ++a) {
-    float s = bmin[a];
-    while (ext[a] - s + bmin[a] > 0.0f) {                               // :366-368
-      starts[a].push_back(s);
-      s += B.size[a];                                                   // :373,:379,:385
-      if (starts[a].size() > 65535) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "more than 65535 bricks along one axis");
-    }
-    B.res[a] = (int)starts[a].size();
-  }
-  B.n = B.res[0] * B.res[1] * B.res[2];
-  // containedVoxels(): for (v = pos/step; v < (pos+size)/step; ++v), all in float
-  std::vector<uint16_t> first[3];
-  std::vector<uint8_t> count[3];
-  for (int a = 0; a < 3; ++a) {
-    const float step = 1.0f / (float)c->res[a];
-    first[a].assign(c->res[a], 0); count[a].assign(c->res[a], 0);
-    for (size_t b = 0; b < starts[a].size(); ++b) {
-      const float bs = std::min(B.size[a], ext[a] - starts[a][b] + bmin[a]);   // :369 glm::min(brick, size - start + min)
-      const float pos = (starts[a][b] - bmin[a]) / ext[a], sz = bs / ext[a];   // :371
-      unsigned v = (unsigned)(pos / step);
-      for (; (float)v < (pos + sz) / step; ++v) {
-        if (v >= (unsigned)c->res[a]) break;
-        if (count[a][v] == 0) first[a][v] = (uint16_t)b;
-        if (count[a][v] == 255 || (unsigned)first[a][v] + count[a][v] != b) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "degenerate brick/voxel overlap on axis %d", a);
-        count[a][v]++;
-      }
-    }
-    HIP_TRY(c, hipMalloc(&c->d_vox_first[a], c->res[a] * sizeof(uint16_t)));
-    HIP_TRY(c, hipMalloc(&c->d_vox_count[a], c->res[a] * sizeof(uint8_t)));
-    HIP_TRY(c, hipMemcpy(c->d_vox_first[a], first[a].data(), c->res[a] * sizeof(uint16_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->d_vox_count[a], count[a].data(), c->res[a] * sizeof(uint8_t), hipMemcpyHostToDevice));
-    B.vox_first[a] = c->d_vox_first[a];
-    B.vox_count[a] = c->d_vox_count[a];
-    const int nt = (c->res[a] + 7) / 8;
-    std::vector<uint16_t> t0(nt, 1), t1(nt, 0);
-    for (int t = 0; t < nt; ++t) {
-      int lo = 0x7fffffff, hi = -1;
-      for (int v = t * 8; v < std::min(t * 8 + 8, c->res[a]); ++v)
-        if (count[a][v]) { lo = std::min(lo, (int)first[a][v]); hi = std::max(hi, (int)first[a][v] + count[a][v] - 1); }
-      if (hi >= 0) { t0[t] = (uint16_t)lo; t1[t] = (uint16_t)hi; }
-    }
-    HIP_TRY(c, hipMalloc(&c->d_tile_b0[a], nt * sizeof(uint16_t)));
-    HIP_TRY(c, hipMalloc(&c->d_tile_b1[a], nt * sizeof(uint16_t)));
-    HIP_TRY(c, hipMemcpy(c->d_tile_b0[a], t0.data(), nt * sizeof(uint16_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->d_tile_b1[a], t1.data(), nt * sizeof(uint16_t), hipMemcpyHostToDevice));
-    B.tile_b0[a] = c->d_tile_b0[a];
-    B.tile_b1[a] = c->d_tile_b1[a];
-    std::vector<uint8_t> full(nt, 1);
-    for (int t = 0; t < nt; ++t)
-      for (int v = t * 8; v < std::min(t * 8 + 8, c->res[a]); ++v) if (!count[a][v]) full[t] = 0;
-    HIP_TRY(c, hipMalloc(&c->d_tile_full[a], nt));
-    HIP_TRY(c, hipMemcpy(c->d_tile_full[a], full.data(), nt, hipMemcpyHostToDevice));
-    B.tile_full[a] = c->d_tile_full[a];
-    // and the inverse: the storage tiles a brick's voxel list reaches into
-    const int nb = (int)starts[a].size();
-    std::vector<uint16_t> bt0(nb, 1), bt1(nb, 0);
-    std::vector<int> blo(nb, 0x7fffffff), bhi(nb, -1);
-    for (int v = 0; v < c->res[a]; ++v)
-      for (int k = 0; k < count[a][v]; ++k) { const int b = first[a][v] + k; blo[b] = std::min(blo[b], v >> 3); bhi[b] = std::max(bhi[b], v >> 3); }
-    for (int b = 0; b < nb; ++b) if (bhi[b] >= 0) { bt0[b] = (uint16_t)blo[b]; bt1[b] = (uint16_t)bhi[b]; }
-    HIP_TRY(c, hipMalloc(&c->d_brick_t0[a], nb * sizeof(uint16_t)));
-    HIP_TRY(c, hipMalloc(&c->d_brick_t1[a], nb * sizeof(uint16_t)));
-    HIP_TRY(c, hipMemcpy(c->d_brick_t0[a], bt0.data(), nb * sizeof(uint16_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->d_brick_t1[a], bt1.data(), nb * sizeof(uint16_t), hipMemcpyHostToDevice));
-    B.brick_t0[a] = c->d_brick_t0[a];
-    B.brick_t1[a] = c->d_brick_t1[a];
+    auto u16 = [&](int t) { return (const uint16_t*)(c->d_brick_tables + P.offset(t, a)); };
+    auto u8 = [&](int t) { return (const uint8_t*)(c->d_brick_tables + P.offset(t, a)); };
+    B.vox_first[a] = u16(BrickPlan::kVoxFirst); B.vox_count[a] = u8(BrickPlan::kVoxCount);
+    B.tile_b0[a] = u16(BrickPlan::kTileB0); B.tile_b1[a] = u16(BrickPlan::kTileB1); B.tile_full[a] = u8(BrickPlan::kTileFull);
+    B.brick_t0[a] = u16(BrickPlan::kBrickT0); B.brick_t1[a] = u16(BrickPlan::kBrickT1);
   }
   for (tsdf_ctx::VolSet& s : c->vset) s.history.invalidate();            // a new brick grid: walk every tile once
-  // tiles == bricks structurally?  (every voxel in exactly one brick per axis, and a tile never straddles two)
-  bool uniform = true;
-  for (int a = 0; a < 3 && uniform; ++a)
-    for (int v = 0; v < c->res[a] && uniform; ++v)
-      uniform = count[a][v] == 1 && first[a][v] == first[a][v & ~7];
-  c->tiles.uniform = uniform ? 1 : 0;
-  c->counter_words = (((size_t)B.n + 3 + 63) / 64) * 64;      // padded: one aligned fill kernel; k_update_occupied reads whole quads
+  c->tiles.uniform = P.uniform ? 1 : 0;
+  c->counter_words = P.counter_words;
   for (int k = 0; k < 2; ++k) {
     HIP_TRY(c, hipMalloc(&c->d_counters[k], c->counter_words * sizeof(uint32_t)));
     HIP_TRY(c, hipMemset(c->d_counters[k], 0, c->counter_words * sizeof(uint32_t)));
@@ -294,6 +210,11 @@ int32_t setup_bricks(tsdf_ctx* c, const float req[3]) {
   // before any of them touches the new tables
   HIP_TRY(c, hipDeviceSynchronize());
   return TSDF_OK;
+}
+int32_t setup_bricks(tsdf_ctx* c, const float req[3]) {
+  const BrickPlan P = BrickPlan::of(c->cfg.bbox_min, c->cfg.bbox_max, c->res, c->vox, req);
+  if (int32_t rc = refuse_bricks(c, P, req)) return rc;
+  return build_bricks(c, P, req);
 }
 
 void timer_begin(tsdf_ctx* c, const char* name) {
@@ -616,8 +537,6 @@ void use_frame_slot(tsdf_ctx* c, int k) {
   c->frame.ranges = c->use_ranges ? c->slots[k].ranges : nullptr; c->frame.rcw = ((int)c->cfg.depth_w + 7) / 8; c->frame.rch = ((int)c->cfg.depth_h + 7) / 8;
 }
 
-int halo_layers_for(float limit, int res_z) { return (int)ceilf((limit * (float)res_z + 2.0f) / 8.0f); }
-
 // draw() without hole filling writes the default framebuffer through glColorMask (recon_integration.cpp:212-216): with a mask, or
 // with a colour buffer the client did not clear, the march renders into the (otherwise unused) atlas and a merge pass follows
 bool masked_direct(const tsdf_ctx* c) { return !c->fill_holes && (c->color_mask_mode != 0 || c->keep_color); }
@@ -732,37 +651,24 @@ void release_volume(tsdf_ctx* c) {
   c->vol.data = nullptr; c->vol.slot = nullptr; c->tiles.stamp = nullptr; c->d_linear = nullptr; c->d_tile_bounds = nullptr;
   c->tile_bounds_valid = false;
 }
-int32_t setup_volume(tsdf_ctx* c) {
-  Volume& V = c->vol;
-  for (int a = 0; a < 3; ++a) V.res[a] = c->res[a];
-  V.ntx = (c->res[0] + 7) / 8; V.nty = (c->res[1] + 7) / 8;
-  V.div_layer = make_fast_div((uint32_t)(V.ntx * V.nty)); V.div_row = make_fast_div((uint32_t)V.ntx);
-  const int ntz = (c->res[2] + 7) / 8;
-  if (!(V.limit > 0.0f)) V.limit = c->cfg.limit;                       // (re-created by setVoxelSize: keeps the current setTsdfLimit value)
-  uint32_t z0 = c->cfg.slab_z0, z1 = c->cfg.slab_z1;
-  if (z0 == 0 && z1 == 0) z1 = (uint32_t)c->res[2];
-  if (z1 > (uint32_t)c->res[2] || z0 >= z1 || (z0 % 8) != 0 || (z1 % 8 != 0 && z1 != (uint32_t)c->res[2])) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "slab range must be tile (8) aligned and inside the volume");
-  V.own_tz0 = (int)z0 / 8; V.own_tz1 = ((int)z1 + 7) / 8;
-  // How far past a slab face an owned sample can make this context read (x = limit/2 * res_z voxels = one sampleDistance):
-  // the refined hit position lies up to one step behind the owned sample (tsdf_raymarch.fs:99-101), its gradient taps another
-  // sampleDistance further (:140-149), and the trilinear footprint of that tap half a voxel + one plane beyond:
-  // ceil(2x + 0.5) planes below the face, floor(2x + 0.5) + 1 above.  (limit * res_z + 2) planes cover both.
-  c->halo_layers = halo_layers_for(V.limit, c->res[2]);
-  const bool whole = (V.own_tz0 == 0 && V.own_tz1 == ntz);
-  V.tz0 = whole ? 0 : std::max(0, V.own_tz0 - c->halo_layers);
-  V.tz1 = whole ? ntz : std::min(ntz, V.own_tz1 + c->halo_layers);
-  V.zlo = V.tz0 * 8; V.zhi = std::min(V.tz1 * 8, c->res[2]) - 1;
-  const bool recompute = !whole && c->cfg.slab_recompute_halo != 0;
-  V.int_tz0 = recompute ? V.tz0 : V.own_tz0;
-  V.int_tz1 = recompute ? V.tz1 : V.own_tz1;
-  if (!whole && V.own_tz1 - V.own_tz0 < c->halo_layers) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "slab thinner than its halo");
-  const bool sparse = c->cfg.sparse_pool_tiles > 0;
-  V.n_stored_tiles = (V.tz1 - V.tz0) * V.nty * V.ntx;
-  if ((uint64_t)(V.tz1 - V.tz0) * V.nty * V.ntx >= (1ull << 31)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "more than 2^31 storage tiles");
-  if (sparse && !whole && !recompute) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "a sparse slab context needs slab_recompute_halo (exchanged halo layers have no pool slots)");
-  if (sparse && c->cfg.sparse_pool_tiles >= (1u << 23)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "sparse_pool_tiles must be below 2^23 (16 GiB of tiles)");
-  const size_t nvox = sparse ? (size_t)c->cfg.sparse_pool_tiles * TILE_VOX : (size_t)(V.tz1 - V.tz0) * V.nty * V.ntx * TILE_VOX;
-  if (nvox >= (1ull << 32)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "a context stores at most 2^32 voxels (32-bit tap offsets); split the volume into Z-slabs or use a sparse pool");
+// The tile layers of the context's slab in a volume of res voxels: SlabPlan (grid_plan.hpp); a refused plan's message, with nothing touched
+SlabPlan plan_volume(const tsdf_ctx* c, const int res[3]) {
+  const float limit = c->vol.limit > 0.0f ? c->vol.limit : c->cfg.limit;   // (re-created by setVoxelSize: keeps the current setTsdfLimit value)
+  return SlabPlan::of(res, c->cfg.slab_z0, c->cfg.slab_z1, limit, c->cfg.slab_recompute_halo != 0, c->cfg.sparse_pool_tiles);
+}
+int32_t refuse_volume(tsdf_ctx* c, const SlabPlan& P) {
+  switch (P.error) {
+    case SlabPlan::kRange: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "slab range must be tile (8) aligned and inside the volume");
+    case SlabPlan::kThinnerThanHalo: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "slab thinner than its halo");
+    case SlabPlan::kStorageTiles: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "more than 2^31 storage tiles");
+    case SlabPlan::kSparseNeedsRecompute: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "a sparse slab context needs slab_recompute_halo (exchanged halo layers have no pool slots)");
+    case SlabPlan::kSparsePool: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "sparse_pool_tiles must be below 2^23 (16 GiB of tiles)");
+    case SlabPlan::kVoxels: FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "a context stores at most 2^32 voxels (32-bit tap offsets); split the volume into Z-slabs or use a sparse pool");
+    default: return TSDF_OK;
+  }
+}
+// ... and an accepted one's, for the voxel grid G it was made from: release, allocate, bind
+int32_t build_volume(tsdf_ctx* c, const VoxelGrid& G, const SlabPlan& P) {
   int32_t rc;
   auto tryhip = [&](hipError_t e, const char* what) -> int32_t {
     if (e == hipSuccess) return TSDF_OK;
@@ -770,33 +676,37 @@ int32_t setup_volume(tsdf_ctx* c) {
     return e == hipErrorOutOfMemory ? TSDF_ERR_OUT_OF_MEMORY : TSDF_ERR_HIP;
   };
   release_volume(c);
+  Volume& V = c->vol;
+  for (int a = 0; a < 3; ++a) { c->res[a] = V.res[a] = G.res[a]; c->vox[a] = G.vox[a]; }
+  V.ntx = P.ntx; V.nty = P.nty;
+  V.div_layer = FastDiv{P.div_layer.m, P.div_layer.k}; V.div_row = FastDiv{P.div_row.m, P.div_row.k};
+  if (!(V.limit > 0.0f)) V.limit = c->cfg.limit;
+  V.own_tz0 = P.own_tz0; V.own_tz1 = P.own_tz1; V.tz0 = P.tz0; V.tz1 = P.tz1; V.int_tz0 = P.int_tz0; V.int_tz1 = P.int_tz1;
+  V.zlo = P.zlo; V.zhi = P.zhi; V.n_stored_tiles = P.n_stored_tiles;
+  c->halo_layers = P.halo_layers;
   V.slot = nullptr; V.pool_tiles = 0;
-  if (sparse) {
+  if (P.pool_tiles) {
     if ((rc = tryhip(hipMalloc(&V.slot, (size_t)V.n_stored_tiles * sizeof(uint32_t)), "hipMalloc(slot table)"))) return rc;
     if ((rc = tryhip(hipMemsetAsync(V.slot, 0xff, (size_t)V.n_stored_tiles * sizeof(uint32_t), c->stream), "hipMemset(slot table)"))) return rc;
-    V.pool_tiles = c->cfg.sparse_pool_tiles;
+    V.pool_tiles = P.pool_tiles;
   }
-  c->tiles.n = (V.int_tz1 - V.int_tz0) * V.nty * V.ntx;
+  c->tiles.n = P.tiles_n;
   // the set in use -- either index: a released context keeps the one it was on --; the other one is the first integrate()'s on the lane (ensure_other_set)
   tsdf_ctx::VolSet& s = set_in_use(c);
   if ((rc = tryhip(alloc_volume_set(c, s, c->stream), "hipMalloc(volume set)"))) return rc;
   bind_volume_set(s, V, c->tiles);
   return TSDF_OK;
 }
-// the largest LUT texel box any 8^3 tile of the current volume touches, with the kernel's own fp32 index arithmetic, against the LDS
-// budget of the integrate kernels: which form stream i can use (depends on the LUT and on the volume resolution)
+int32_t setup_volume(tsdf_ctx* c, const VoxelGrid& G) {
+  const SlabPlan P = plan_volume(c, G.res);
+  if (int32_t rc = refuse_volume(c, P)) return rc;
+  return build_volume(c, G, P);
+}
+// which form of the integrate kernels stream i can use (depends on the LUT and on the volume resolution): LutFit (grid_plan.hpp)
 void fit_lut_to_volume(tsdf_ctx* c, uint32_t i) {
-  const StreamLut& L = c->luts.s[i];
-  int worst[3] = {1, 1, 1};
-  for (int a = 0; a < 3; ++a) {
-    const float step = 1.0f / (float)c->res[a];
-    const int n = L.inv_res[a];
-    auto idx0 = [&](int v) { float f = ((float)v + 0.5f) * step * (float)n - 0.5f; int k = (int)fminf(fmaxf(floorf(f), -1.0f), (float)n); return std::min(std::max(k, 0), n - 1); };
-    auto idx1 = [&](int v) { float f = ((float)v + 0.5f) * step * (float)n - 0.5f; int k = (int)fminf(fmaxf(floorf(f), -1.0f), (float)n); return std::min(std::max(k + 1, 0), n - 1); };
-    for (int t = 0; t * 8 < c->res[a]; ++t) worst[a] = std::max(worst[a], idx1(std::min(t * 8 + 7, c->res[a] - 1)) - idx0(t * 8) + 1);
-  }
-  c->lut_dz[i] = worst[2];
-  c->lds_ok[i] = worst[0] * worst[1] * worst[2] > integrate_box_cap() ? 0 : ((worst[1] * worst[2] * 8 <= integrate_row_cap() && worst[2] * 64 <= integrate_box_cap()) ? 2 : 1);
+  const LutFit F = LutFit::of(c->res, c->luts.s[i].inv_res, integrate_box_cap(), integrate_row_cap());
+  c->lut_dz[i] = F.dz;
+  c->lds_ok[i] = F.cls;
 }
 
 }  // namespace rrhost
@@ -894,21 +804,11 @@ int32_t tsdf_create(const tsdf_config* cfg, tsdf_ctx** out) {
   }
   if (const char* e = getenv("RR_K1_CULLED_RANGES")) c->culled_ranges = atoi(e) != 0;
   if (const char* e = getenv("RR_K1_REC")) c->use_recs = atoi(e) != 0;    // A/B hook: 0 = the LDS form's own tile head
-  // setVoxelSize(), :340-347
-  for (int a = 0; a < 3; ++a) {
-    const float ext = cfg->bbox_max[a] - cfg->bbox_min[a];
-    if (cfg->res[0] == 0) {
-      if (!(cfg->voxel_size > 0.0f)) { c->err = "voxel_size must be > 0 when res is not given"; return fail(TSDF_ERR_INVALID_ARGUMENT); }
-      c->res[a] = (int)ceilf(ext / cfg->voxel_size);
-      c->vox[a] = cfg->voxel_size;
-    } else {
-      c->res[a] = (int)cfg->res[a];
-      c->vox[a] = ext / (float)cfg->res[a];
-    }
-    if (c->res[a] < 1 || c->res[a] > 4096) { c->err = "volume resolution out of range [1, 4096]"; return fail(TSDF_ERR_INVALID_ARGUMENT); }
-  }
+  const VoxelGrid G = VoxelGrid::of(cfg->bbox_min, cfg->bbox_max, cfg->voxel_size, cfg->res);
+  if (G.error == VoxelGrid::kVoxelSize) { c->err = "voxel_size must be > 0 when res is not given"; return fail(TSDF_ERR_INVALID_ARGUMENT); }
+  if (G.error) { c->err = "volume resolution out of range [1, 4096]"; return fail(TSDF_ERR_INVALID_ARGUMENT); }
   int32_t rc;
-  if ((rc = setup_volume(c))) return fail(rc);
+  if ((rc = setup_volume(c, G))) return fail(rc);
   auto tryhip = [&](hipError_t e, const char* what) -> int32_t {
     if (e == hipSuccess) return TSDF_OK;
     c->err = std::string(what) + ": " + hipGetErrorString(e);
@@ -2143,7 +2043,7 @@ int32_t tsdf_draw_textures(tsdf_ctx* c, uint32_t which) {
   if (which == 1 && !c->tiles_img.limits_complete()) FAIL(c, TSDF_ERR_STATE, "unit 16: no draw with space skipping has produced the depth-limit image since the context was created or resized (or an integrate() reset it for the coming draw)");
   HIP_TRY(c, hipSetDevice(c->device));
   BlitParams Q{};
-  const float rf_x = (float)(uint32_t)(1.5f * (float)c->vw), rf_y = (float)c->vh;   // ViewLod::resolution_full, view_lod.cpp:29
+  const float rf_x = (float)c->atlas.aw, rf_y = (float)c->vh;            // ViewLod::resolution_full, view_lod.cpp:29 (AtlasPlan, grid_plan.hpp)
   Q.vw = (int)(uint32_t)(rf_x / 2.0f); Q.vh = (int)(uint32_t)(rf_y / 2.0f);          // uvec2(fvec2(resolution_full) / 2), kinect_client.cpp:706
   Q.vw = std::min(Q.vw, c->vw); Q.vh = std::min(Q.vh, c->vh);            // (the viewport lies inside the framebuffer: 0.75 w x 0.5 h)
   Q.fw = c->vw;
@@ -2250,6 +2150,7 @@ int32_t tsdf_set_tsdf_limit(tsdf_ctx* c, float limit) {
   CHECK_CTX(c);
   if (!(limit > 0.0f)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "limit must be > 0");
   const bool whole = whole_volume(c);
+  // (halo_layers_for, grid_plan.hpp: how far past its faces a limit makes a slab read)
   if (!whole && halo_layers_for(limit, c->res[2]) > c->halo_layers) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "limit needs a wider slab halo than this context allocated");
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, sync_ctx(c));
@@ -2271,24 +2172,25 @@ int32_t tsdf_set_voxel_size(tsdf_ctx* c, float size) {
   CHECK_CTX(c);
   if (!(size > 0.0f)) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "voxel size must be > 0");
   if (c->cfg.slab_z0 != 0 || c->cfg.slab_z1 != 0) FAIL(c, TSDF_ERR_STATE, "setVoxelSize on a slab context: the slab range is in voxel planes of the old grid (re-create the contexts)");
-  int res[3];
-  for (int a = 0; a < 3; ++a) {
-    res[a] = (int)ceilf((c->cfg.bbox_max[a] - c->cfg.bbox_min[a]) / size);
-    if (res[a] < 1 || res[a] > 4096) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "volume resolution out of range [1, 4096]");
-  }
+  const uint32_t by_size[3] = {0, 0, 0};
+  const VoxelGrid G = VoxelGrid::of(c->cfg.bbox_min, c->cfg.bbox_max, size, by_size);
+  if (G.error) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "volume resolution out of range [1, 4096]");
   if (!c->mstream.ring.idle()) FAIL(c, TSDF_ERR_STATE, "%u streamed mesh frame(s) are queued or held: acquire and release them before the grid changes", c->mstream.ring.count);
+  // both plans before anything is touched: a grid that the volume or the bricks refuse leaves the context as it was
+  const float brick[3] = {c->br.size[0], c->br.size[1], c->br.size[2]};
+  const SlabPlan S = plan_volume(c, G.res);
+  if (int32_t rc = refuse_volume(c, S)) return rc;
+  const BrickPlan B = BrickPlan::of(c->cfg.bbox_min, c->cfg.bbox_max, G.res, G.vox, brick);
+  if (int32_t rc = refuse_bricks(c, B, brick)) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, sync_ctx(c));
-  const int old_res[3] = {c->res[0], c->res[1], c->res[2]};
-  const float old_vox[3] = {c->vox[0], c->vox[1], c->vox[2]};
-  const float brick[3] = {c->br.size[0], c->br.size[1], c->br.size[2]};
-  for (int a = 0; a < 3; ++a) { c->res[a] = res[a]; c->vox[a] = size; }
-  int32_t rc = setup_volume(c);
-  if (rc == TSDF_OK) rc = setup_bricks(c, brick);
-  if (rc != TSDF_OK) {                                                   // leave a usable context behind: back to the old grid
+  VoxelGrid old{};
+  for (int a = 0; a < 3; ++a) { old.res[a] = c->res[a]; old.vox[a] = c->vox[a]; }
+  int32_t rc = build_volume(c, G, S);
+  if (rc == TSDF_OK) rc = build_bricks(c, B, brick);
+  if (rc != TSDF_OK) {                                                   // an allocation failed.  Leave a usable context behind: back to the old grid
     const std::string why = c->err;
-    for (int a = 0; a < 3; ++a) { c->res[a] = old_res[a]; c->vox[a] = old_vox[a]; }
-    if (setup_volume(c) == TSDF_OK) setup_bricks(c, brick);
+    if (setup_volume(c, old) == TSDF_OK) setup_bricks(c, brick);
     c->err = why;
     return rc;
   }

@@ -41,13 +41,7 @@ struct tsdf_ctx {
   float brick_req[3]{};          // requested size (setBrickSize argument)
   Bricks br{};
   std::vector<BrickRange> ranges;
-  uint16_t* d_vox_first[3]{};
-  uint8_t* d_vox_count[3]{};
-  uint16_t* d_tile_b0[3]{};
-  uint16_t* d_tile_b1[3]{};
-  uint8_t* d_tile_full[3]{};
-  uint16_t* d_brick_t0[3]{};
-  uint16_t* d_brick_t1[3]{};
+  uint8_t* d_brick_tables = nullptr;   // the 21 voxel <-> brick <-> tile tables as one blob (BrickPlan, grid_plan.hpp); Bricks's table members point into it
   uint32_t* d_occ_counts = nullptr;   // three occupied-brick count words: two used alternately (see Bricks::num_occupied), one spare (lane_ahead.hpp)
   uint32_t min_voxels = 10;      // recon_integration.cpp:59
   size_t counter_words = 0;

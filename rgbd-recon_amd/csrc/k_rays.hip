@@ -64,7 +64,7 @@ __device__ __forceinline__ bool ray_run_clear(const Volume& V, float3 a, float3 
 //   - inside the run batches are fetched unconditionally with the clamped filter (tex3d_tsdf<kSparse>, not the kWhole form): an owned sample's taps lie
 //     in the stored planes, and whatever else a batch touches is clamped into them and never examined.
 //   - the hit's prev is sample k - 1's density: the lane's own when it examined that sample, else (the run's first sample, with samples in front of it)
-//     fetched at pos_{k-1} from the halo, which is sized for a sample one step behind an owned one (abi.cpp, above halo_layers_for).
+//     fetched at pos_{k-1} from the halo, which is sized for a sample one step behind an owned one (grid_plan.hpp, above halo_layers_for).
 //   - tile-class skipping stays.  A run is tested only when its first and last sample are both owned (then all between are), and ray_run_clear<., true>
 //     refuses any tile layer outside the stored [tz0, tz1).  What cls and slot hold on halo layers (abi.cpp): the class array covers every STORED tile and
 //     is created kTileMixed; TileState::cls points at the first INTEGRATED layer.  Under an exchanged halo integrate() computes the owned layers only,

@@ -162,6 +162,33 @@ def test_set_brick_size_and_resize(rr, small_scene):
     assert compare(hip, orc) > 100
 
 
+def test_a_refused_brick_size_leaves_the_context_as_it_was(rr, small_scene):
+    """tsdf_set_brick_size with a size that rounds to zero voxels (0.01 under voxels of 2 / 64) is refused before anything is touched: the same grid, the
+    same tables, the same volume from the same frame.  The getters stand in front of the launches: a context left half set up fails there and starts
+    no kernel."""
+    import ctypes as C
+    hip = rr.ReconIntegrationHip(small_scene, **dict(KW, brick_size=[2.0 / 16, 2.2 / 16, 2.0 / 16]))
+
+    def layout():
+        r3, b3, s3 = (C.c_uint32 * 3)(), (C.c_uint32 * 3)(), (C.c_float * 3)()
+        hip._ck(hip._L.tsdf_get_resolution(hip._c, r3, b3, s3))
+        return tuple(r3), tuple(b3), tuple(s3), hip.numBricks()
+
+    def volume():
+        hip.upload_frame(small_scene)
+        hip.clearOccupiedBricks(); hip.markBricks(); ratio = hip.updateOccupiedBricks(); hip.integrate()
+        return ratio, hip.tsdf()
+    before, (ratio, vol) = layout(), volume()
+    assert before[:2] == ((64, 64, 64), (16, 16, 16)) and before[3] == 4096 and ratio > 0 and (vol != np.float32(-LIMIT)).sum() > 1000
+    with pytest.raises(rr.TsdfError) as e:
+        hip.setBrickSize(0.01)
+    assert e.value.code == -1 and str(e.value) == "tsdf error -1: brick size 0.01 rounds to zero voxels"     # TSDF_ERR_INVALID_ARGUMENT
+    assert layout() == before
+    again, vol2 = volume()
+    assert again == ratio
+    assert_same(vol2, vol, "the volume after a refused setBrickSize")
+
+
 def test_frame_sequence_resets_tiles_that_empty_out(rr):
     """Three different frames through ONE context vs a fresh oracle per frame: tiles occupied in frame k but not in k+1
     must read -limit again (the reference clears the whole volume every frame, recon_integration.cpp:249-250)."""
