@@ -277,8 +277,11 @@ int32_t tsdf_download_mvt_vertices(tsdf_ctx* ctx, float* out);
  *     the far plane (w - z >= 0): an end point e outside moves towards the other one o, to e + (o - e) * t with t = d_e / (d_e - d_o)
  *     (d: the plane distances above); a line wholly outside either plane is dropped, as is one with an end point at w <= 0 after clipping.  With the window coordinates of start a and end b: if
  *     |b.x - a.x| >= |b.y - a.y| (x-major) every pixel column i whose centre c = i + 0.5 lies in [a.x, b.x) along the direction of travel
- *     (a.x <= c < b.x, or b.x < c <= a.x) makes one fragment in row floor(a.y + (b.y - a.y) * t), t = (c - a.x) / (b.x - a.x), with depth
- *     a.z + (b.z - a.z) * t clamped to [0, 1]; y-major lines the same with rows.  Fragments outside the view are dropped.
+ *     (a.x <= c < b.x, or b.x < c <= a.x) makes one fragment in row r = floor(a.y + (b.y - a.y) * t), t = (c - a.x) / (b.x - a.x).  Its depth
+ *     is GL's (eq. 14.5, 14.6): that of the fragment's centre p = (c, r + 0.5) projected onto the segment, a.z + (b.z - a.z) * tz with
+ *     tz = ((p.x - a.x) * dx + (p.y - a.y) * dy) / (dx * dx + dy * dy), d = b - a, clamped to [0, 1] -- not the depth of the line where it
+ *     crosses the column, which is off by up to half a pixel's depth step.  y-major lines the same with rows.  Fragments outside the view
+ *     are dropped.
  *   Wide lines (GL 4.4 section 14.5.2.2, aliased; the bounding box's width 2).  After the near / far clip the width is rounded to w = 2 and
  *     the window segment moves by -(w - 1) / 2 = -0.5 in its minor direction (a.y and b.y of an x-major line, where |dx| >= |dy|; a.x and b.x
  *     of a y-major one; the major direction is that of the unmoved segment, which the shift does not change).  The moved segment is walked

@@ -90,9 +90,12 @@ __device__ __forceinline__ void overlay_line_fragment(float s0, float s1, float 
                                                       uint32_t id, const float* __restrict__ fb_d, unsigned long long* __restrict__ key) {
   const float c = (float)i + 0.5f;
   if (!(s1 > s0 ? (c >= s0 && c < s1) : (c <= s0 && c > s1))) return;
-  const float t = (c - s0) / (s1 - s0);
-  const float m = floorf(o0 + (o1 - o0) * t);
-  float z = az + (bz - az) * t;
+  const float ds = s1 - s0, dm = o1 - o0;
+  const float t = (c - s0) / ds;
+  const float m = floorf(o0 + dm * t);
+  // the depth is that of the fragment's centre projected onto the segment (GL 4.4 eq. 14.5, 14.6), not that of the line where it crosses column c
+  const float tz = ((c - s0) * ds + ((m + 0.5f) - o0) * dm) / (ds * ds + dm * dm);
+  float z = az + (bz - az) * tz;
   if (z != z) return;
   z = z > 0.0f ? (z < 1.0f ? z : 1.0f) : 0.0f;                            // the depth range [0, 1]
   const int n_minor = xmajor ? h : w;

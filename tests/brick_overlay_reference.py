@@ -125,9 +125,12 @@ def brick_fragments(ids, res_bricks, brick_size, bbox_min, mv, pr, view):
     with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
         c = i.astype(np.float32) + F(0.5)
         on = np.where(S1 > S0, (c >= S0) & (c < S1), (c <= S0) & (c > S1))
-        t = ((c - S0) / (S1 - S0)).astype(np.float32)
-        m = np.floor((O0 + ((O1 - O0) * t).astype(np.float32)).astype(np.float32))
-        z = (AZ + ((BZ - AZ) * t).astype(np.float32)).astype(np.float32)
+        DS, DM = (S1 - S0).astype(np.float32), (O1 - O0).astype(np.float32)
+        t = ((c - S0) / DS).astype(np.float32)
+        m = np.floor((O0 + (DM * t).astype(np.float32)).astype(np.float32))
+        tz = ((((c - S0) * DS).astype(np.float32) + (((m + F(0.5)) - O0).astype(np.float32) * DM).astype(np.float32)).astype(np.float32)
+              / ((DS * DS).astype(np.float32) + (DM * DM).astype(np.float32)).astype(np.float32)).astype(np.float32)   # eq. 14.5, as overlay_reference
+        z = (AZ + ((BZ - AZ) * tz).astype(np.float32)).astype(np.float32)
         on &= (m >= 0) & (m < n_minor[seg]) & ~np.isnan(z)
         z = np.where(z > 0, z, F(0)).astype(np.float32)
         z = np.where(z < 1, z, F(1)).astype(np.float32)

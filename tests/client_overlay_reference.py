@@ -61,9 +61,11 @@ def wide_window_line_fragments(a, b, view, width=2):
         c = F(i) + F(0.5)
         if not ((c >= s0 and c < s1) if s1 > s0 else (c <= s0 and c > s1)):
             continue
-        t = F(c - s0) / F(s1 - s0)
-        m = np.floor(F(o0 + F(o1 - o0) * t))
-        z = F(az + F(bz - az) * t)
+        ds, dm = F(s1 - s0), F(o1 - o0)
+        t = F(c - s0) / ds
+        m = np.floor(F(o0 + F(dm * t)))
+        tz = F(F(F(c - s0) * ds) + F(F(F(m + F(0.5)) - o0) * dm)) / F(F(ds * ds) + F(dm * dm))   # eq. 14.5: the fragment's centre projected onto the segment
+        z = F(az + F(F(bz - az) * tz))
         if z != z:
             continue
         z = z if z > 0 else F(0)
