@@ -102,11 +102,7 @@ __global__ __launch_bounds__(256) void k_classify_clear_tiles(Volume V, Bricks B
   }
   const unsigned long long am = __ballot(active);
   if (am) {
-    const int leader = __ffsll((long long)am) - 1;
-    uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(S.count, (uint32_t)__popcll(am));
-    base = __shfl(base, leader);
-    const uint32_t pos = base + (uint32_t)__popcll(am & ((1ull << lane) - 1ull));
+    const uint32_t pos = wave_append(S.count, am, lane) + wave_rank(am, lane);
     if (active) S.list[pos] = (uint32_t)tile;
     if (active && V.slot) V.slot[stored_tile_index(V, tile)] = pos < V.pool_tiles ? pos : kNoSlot;   // slot = position in this frame's list
   }

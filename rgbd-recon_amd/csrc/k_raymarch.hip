@@ -173,6 +173,19 @@ __device__ float3 blend_cameras(const StreamTable& T, const FrameImages& F, floa
 // appends it to a compact hit list; k_shade (one thread per hit, dense waves) does submitFragment().  Rays that hit
 // nothing cost no shading registers or divergence, and the hit list length never goes through the host.
 struct Hit { float x, y, z; uint32_t pix; };   // refined sample position (volume space) + pixel index
+// a pixel without a fragment (discard, :112, or no cube under it): the target holds its clear value
+__device__ __forceinline__ void store_clear(const RayTarget& R, int px, int py) {
+  const size_t oi = (size_t)py * R.stride + px;
+  R.color[oi] = make_float4(R.clear[0], R.clear[1], R.clear[2], R.clear[3]);
+  R.depth[oi] = 1.0f;
+}
+// writeNumSamples(), :395-398: imageStore at ivec2(gl_FragCoord.xy) -- the viewport's origin + the pixel; outside the image nothing is stored.
+// covered: the pixel lies under the cube (else it has no fragment, and the image holds its cleared 0)
+__device__ __forceinline__ void write_num_samples(const ViewParams& P, const RayTarget& R, int px, int py, uint32_t n, bool covered = true) {
+  const float ns = (float)n * 0.0027f;
+  const int sx = px + P.vp_org[0], sy = py + P.vp_org[1];
+  if (sx >= 0 && sy >= 0 && sx < P.w && sy < P.h) R.nsamples[(size_t)sy * P.w + sx] = covered ? ns : 0.0f;
+}
 
 #ifndef RR_MARCH_BATCH
 #define RR_MARCH_BATCH 8
@@ -226,11 +239,7 @@ __global__ __launch_bounds__(256, RR_MARCH_BOUNDS) void k_march(ViewParams P, Vo
     }
     if (!cur) {
       if (inside) {
-        if (before_target || R.rewrite_target) {                         // what the draw that last wrote THIS target left here
-          const size_t oi = (size_t)py * R.stride + px;
-          R.color[oi] = make_float4(R.clear[0], R.clear[1], R.clear[2], R.clear[3]);
-          R.depth[oi] = 1.0f;
-        }
+        if (before_target || R.rewrite_target) store_clear(R, px, py);   // what the draw that last wrote THIS target left here
         if (before || R.rewrite_all) R.nsamples[(size_t)py * P.w + px] = 0.0f;   // (one sample-count image: the previous draw's)
       }
       return;
@@ -240,25 +249,17 @@ __global__ __launch_bounds__(256, RR_MARCH_BOUNDS) void k_march(ViewParams P, Vo
   const unsigned long long t_start = wall_clock64();
   uint32_t st_pre = 0, st_batches = 0;
 #endif
-  const float fx = (float)px + 0.5f, fy = (float)py + 0.5f;
-  const float3 dn = normalize3(pixel_dir_vol(P, fx, fy));
-  const float3 step = make_float3(dn.x * sd, dn.y * sd, dn.z * sd);     // :64
+  const float3 step = pixel_step(P, px, py, sd);
   uint32_t max_n = 0;
   float3 pos = make_float3(0, 0, 0);
   bool covered = inside;
   if (inside) {
     // The fragments are those of the unit cube's faces (UnitCube::draw, culling off, recon_integration.cpp:223-225): a pixel whose ray misses
     // the cube has none, with or without skipSpace -- bricks of the last row / column reach past the bounding box, so depth limits alone
-    // would let rays march beside the volume.  The ray-cube test is intersectBox(), :363-374.
+    // would let rays march beside the volume.
     const float3 o = make_float3(P.cam_vol[0], P.cam_vol[1], P.cam_vol[2]);
-    const float3 inv = make_float3(1.0f / step.x, 1.0f / step.y, 1.0f / step.z);
-    const float3 tbot = make_float3(inv.x * (0.0f - o.x), inv.y * (0.0f - o.y), inv.z * (0.0f - o.z));
-    const float3 ttop = make_float3(inv.x * (1.0f - o.x), inv.y * (1.0f - o.y), inv.z * (1.0f - o.z));
-    const float3 tmn = make_float3(fminf(ttop.x, tbot.x), fminf(ttop.y, tbot.y), fminf(ttop.z, tbot.z));
-    const float3 tmx = make_float3(fmaxf(ttop.x, tbot.x), fmaxf(ttop.y, tbot.y), fmaxf(ttop.z, tbot.z));
-    const float t0 = fmaxf(fmaxf(tmn.x, tmn.y), fmaxf(tmn.x, tmn.z));
-    const float t1 = fminf(fminf(tmx.x, tmx.y), fminf(tmx.x, tmx.z));
-    if (!(t0 <= t1) || t1 < 0.0f) covered = false;                      // no fragment: pixel not under the cube
+    const CubeSpan span = unit_cube_span(o, step);
+    if (!span.hit) covered = false;                                     // no fragment: pixel not under the cube
     else if (P.skip) {                                                  // getStartPos(ivec2(gl_FragCoord.xy - viewport_offset)), :70, :384-393
       // gl_FragCoord = viewport origin + pixel + 0.5 (window coordinates); the shader subtracts its viewport_offset uniform again.
       // origin == offset (what the client sets, kinect_client.cpp:650-662) gives back the pixel centre exactly; anything else
@@ -276,10 +277,10 @@ __global__ __launch_bounds__(256, RR_MARCH_BOUNDS) void k_march(ViewParams P, Vo
       pos = pf;
       const float3 dd = make_float3(pf.x - pb.x, pf.y - pb.y, pf.z - pb.z);
       max_n = (uint32_t)ceilf(sqrtf(dd.x * dd.x + dd.y * dd.y + dd.z * dd.z) / sd);   // :73
-    } else {                                                            // :75-86
-      const float t_near = t0 < 0.0f ? 0.0f : t0;
-      pos = make_float3(o.x + step.x * t_near, o.y + step.y * t_near, o.z + step.z * t_near);
-      max_n = (uint32_t)ceilf(fabsf(t1 - t_near));
+    } else {
+      const float t_near = span_near(span.t0);
+      pos = ray_at(o, step, t_near);
+      max_n = (uint32_t)span_samples(t_near, span.t1);
     }
   }
   // The march, :89-110.  Sample positions never depend on the densities, so (a) while the ray is in space known to hold
@@ -300,7 +301,7 @@ __global__ __launch_bounds__(256, RR_MARCH_BOUNDS) void k_march(ViewParams P, Vo
     // every rank computes identically).
     while (n < max_n && !sample_owned(V, pos.z)) {
       pos_prev = pos;
-      pos = make_float3(pos.x + step.x, pos.y + step.y, pos.z + step.z);
+      pos = ray_advance(pos, step);
       n += 1;
       prev_valid = false;
 #ifdef RR_MARCH_STATS
@@ -317,7 +318,7 @@ __global__ __launch_bounds__(256, RR_MARCH_BOUNDS) void k_march(ViewParams P, Vo
     bool own[kBatch];
     p[0] = pos;
 #pragma unroll
-    for (int k = 1; k < kBatch; ++k) p[k] = make_float3(p[k - 1].x + step.x, p[k - 1].y + step.y, p[k - 1].z + step.z);
+    for (int k = 1; k < kBatch; ++k) p[k] = ray_advance(p[k - 1], step);
 #pragma unroll
     for (int k = 0; k < kBatch; ++k) {
       own[k] = (n + k < max_n) && (!partial || sample_owned(V, p[k].z));
@@ -344,7 +345,7 @@ __global__ __launch_bounds__(256, RR_MARCH_BOUNDS) void k_march(ViewParams P, Vo
         }
       }
     }
-    if (!hit) pos = make_float3(p[kBatch - 1].x + step.x, p[kBatch - 1].y + step.y, p[kBatch - 1].z + step.z);
+    if (!hit) pos = ray_advance(p[kBatch - 1], step);
     if (partial && !hit && !prev_valid) { n = max_n; break; }          // the batch ended outside the slab: nothing further is ours
     if (!partial && !hit && n >= cap && n < max_n) { deferred = true; break; }   // a long ray: k_march_long finishes it, one wave per ray
   }
@@ -352,42 +353,32 @@ __global__ __launch_bounds__(256, RR_MARCH_BOUNDS) void k_march(ViewParams P, Vo
   // launch as long as its slowest wave: hand them to a second kernel that puts 64 lanes on one ray.
   const unsigned long long dm = __ballot(deferred);
   if (dm) {
-    const int leader = __ffsll((long long)dm) - 1;
-    uint32_t base = 0;
-    if (ln == leader) base = atomicAdd(long_count, (uint32_t)__popcll(dm));
-    base = __shfl(base, leader);
+    const uint32_t base = wave_append(long_count, dm, ln);
     if (deferred) {
       LongRay r;
       r.pix = (uint32_t)(py * P.w + px); r.n = n; r.max_n = max_n; r.prev = prev;
       r.x = pos.x; r.y = pos.y; r.z = pos.z; r.pad = 0.0f;
-      longs[base + (uint32_t)__popcll(dm & ((1ull << ln) - 1ull))] = r;
+      longs[base + wave_rank(dm, ln)] = r;
     }
   }
-  if (hit) {                                                            // approximate ray-cell intersection, :99-101
+  if (hit) {
     if (partial && !prev_valid) prev = tex3d_tsdf<kSparse>(V, pos_prev.x, pos_prev.y, pos_prev.z);   // sample n-1 is a neighbour's: read it from the halo
-    const float kk = prev / (hit_d - prev);
-    pos = make_float3((hit_pos.x - step.x) - step.x * kk, (hit_pos.y - step.y) - step.y * kk, (hit_pos.z - step.z) - step.z * kk);
+    pos = refine_hit(hit_pos, step, prev, hit_d);
   }
   // compact the hits of this wave into the list (one atomic per wave)
   const unsigned long long hm = __ballot(hit);
   if (hm) {
-    const int leader = __ffsll((long long)hm) - 1;
-    uint32_t base = 0;
-    if (ln == leader) base = atomicAdd(hit_count, (uint32_t)__popcll(hm));
-    base = __shfl(base, leader);
+    const uint32_t base = wave_append(hit_count, hm, ln);
     if (hit) {
       Hit h;
       h.x = pos.x; h.y = pos.y; h.z = pos.z; h.pix = (uint32_t)(py * P.w + px);
-      hits[base + (uint32_t)__popcll(hm & ((1ull << ln) - 1ull))] = h;
+      hits[base + wave_rank(hm, ln)] = h;
     }
   }
   if (inside && !deferred) {
-    if (!hit) {                                                         // discard: the target keeps its clear value
-      const size_t oi = (size_t)py * R.stride + px;
-      R.color[oi] = make_float4(R.clear[0], R.clear[1], R.clear[2], R.clear[3]);
-      R.depth[oi] = 1.0f;
-    }
-    const float ns = (float)n * 0.0027f;                                // writeNumSamples(), :395-398: imageStore at ivec2(gl_FragCoord.xy)
+    if (!hit) store_clear(R, px, py);
+    // write_num_samples' text with a slab's sign (a miss stores -count).  Kept here: behind a call the slab instantiations change
+    const float ns = (float)n * 0.0027f;
     const int sx = px + P.vp_org[0], sy = py + P.vp_org[1];
     if (sx >= 0 && sy >= 0 && sx < P.w && sy < P.h) R.nsamples[(size_t)sy * P.w + sx] = covered ? ((partial && !hit) ? -ns : ns) : 0.0f;
   }
@@ -483,26 +474,18 @@ __global__ __launch_bounds__(kDB ? 128 : 256, kDB ? 2 : RR_BOX_BOUNDS) void k_ma
   const int px = blockIdx.x * 16 + (wv & 1) * 8 + (ln & 7);
   const int py = kDB ? blockIdx.y * 8 + (ln >> 3) : blockIdx.y * 16 + (wv >> 1) * 8 + (ln >> 3);
   const bool inside = px < P.w && py < P.h;
-  const float fx = (float)px + 0.5f, fy = (float)py + 0.5f;
-  const float3 dn = normalize3(pixel_dir_vol(P, fx, fy));
-  const float3 step = make_float3(dn.x * sd, dn.y * sd, dn.z * sd);     // :64
+  const float3 step = pixel_step(P, px, py, sd);
   uint32_t max_n = 0;
   float3 pos = make_float3(0, 0, 0);
   bool covered = inside;
-  if (inside) {                                                         // intersectBox(), :363-374
+  if (inside) {
     const float3 o = make_float3(P.cam_vol[0], P.cam_vol[1], P.cam_vol[2]);
-    const float3 inv = make_float3(1.0f / step.x, 1.0f / step.y, 1.0f / step.z);
-    const float3 tbot = make_float3(inv.x * (0.0f - o.x), inv.y * (0.0f - o.y), inv.z * (0.0f - o.z));
-    const float3 ttop = make_float3(inv.x * (1.0f - o.x), inv.y * (1.0f - o.y), inv.z * (1.0f - o.z));
-    const float3 tmn = make_float3(fminf(ttop.x, tbot.x), fminf(ttop.y, tbot.y), fminf(ttop.z, tbot.z));
-    const float3 tmx = make_float3(fmaxf(ttop.x, tbot.x), fmaxf(ttop.y, tbot.y), fmaxf(ttop.z, tbot.z));
-    const float t0 = fmaxf(fmaxf(tmn.x, tmn.y), fmaxf(tmn.x, tmn.z));
-    const float t1 = fminf(fminf(tmx.x, tmx.y), fminf(tmx.x, tmx.z));
-    if (!(t0 <= t1) || t1 < 0.0f) covered = false;                      // no fragment: pixel not under the cube
+    const CubeSpan span = unit_cube_span(o, step);
+    if (!span.hit) covered = false;                                     // no fragment: pixel not under the cube
     else {
-      const float t_near = t0 < 0.0f ? 0.0f : t0;
-      pos = make_float3(o.x + step.x * t_near, o.y + step.y * t_near, o.z + step.z * t_near);
-      max_n = (uint32_t)ceilf(fabsf(t1 - t_near));
+      const float t_near = span_near(span.t0);
+      pos = ray_at(o, step, t_near);
+      max_n = (uint32_t)span_samples(t_near, span.t1);
     }
   }
   const float nx = (float)V.res[0], ny = (float)V.res[1], nz = (float)V.res[2];
@@ -557,7 +540,7 @@ __global__ __launch_bounds__(kDB ? 128 : 256, kDB ? 2 : RR_BOX_BOUNDS) void k_ma
       }
       if (leap) {
         float3 e = pos;
-        for (int k = 0; k < kLeap; ++k) e = make_float3(e.x + step.x, e.y + step.y, e.z + step.z);   // the reference's chain of additions
+        for (int k = 0; k < kLeap; ++k) e = ray_advance(e, step);   // the reference's chain of additions
         if (live) { n += min((uint32_t)kLeap, max_n - n); prev = ml; }
         pos = e;
         RR_STAT(7, kLeap);
@@ -672,7 +655,7 @@ __global__ __launch_bounds__(kDB ? 128 : 256, kDB ? 2 : RR_BOX_BOUNDS) void k_ma
     if (empty && !odd) {
       // every sample of the batch is -limit: no hit, prev_density = -limit, the counter advances by the samples this ray still had;
       // the positions still go through the reference's chain of additions
-      for (int k = 0; k < s_run; ++k) p = make_float3(p.x + step.x, p.y + step.y, p.z + step.z);
+      for (int k = 0; k < s_run; ++k) p = ray_advance(p, step);
       if (live) { n += min((uint32_t)s_run, max_n - n); prev = ml; }
       pos = p;
       RR_STAT(7, s_run);
@@ -711,7 +694,7 @@ __global__ __launch_bounds__(kDB ? 128 : 256, kDB ? 2 : RR_BOX_BOUNDS) void k_ma
       float dv[kSub];
       q[0] = p;
 #pragma unroll
-      for (int j = 1; j < kSub; ++j) q[j] = make_float3(q[j - 1].x + step.x, q[j - 1].y + step.y, q[j - 1].z + step.z);
+      for (int j = 1; j < kSub; ++j) q[j] = ray_advance(q[j - 1], step);
       float wx[kSub], wy[kSub], wz[kSub];
       int cell[kSub];
       bool want[kSub];
@@ -759,7 +742,7 @@ __global__ __launch_bounds__(kDB ? 128 : 256, kDB ? 2 : RR_BOX_BOUNDS) void k_ma
           else prev = dv[j];
         }
       }
-      p = make_float3(q[kSub - 1].x + step.x, q[kSub - 1].y + step.y, q[kSub - 1].z + step.z);
+      p = ray_advance(q[kSub - 1], step);
 #pragma unroll
       for (int j = kSub - 1; j >= 1; --j) if (s_run - k0 == j) p = q[j];     // a last, shorter sub-batch: the chain stops after j additions
     }
@@ -771,31 +754,19 @@ __global__ __launch_bounds__(kDB ? 128 : 256, kDB ? 2 : RR_BOX_BOUNDS) void k_ma
   }
   if (kDB && have_pref) __builtin_amdgcn_s_waitcnt(0x0f70);             // a box still on its way must have landed before the wave (and its LDS) goes
   float3 out_pos = pos;
-  if (hit) {                                                            // approximate ray-cell intersection, :99-101
-    const float kk = prev / (hit_d - prev);
-    out_pos = make_float3((hit_pos.x - step.x) - step.x * kk, (hit_pos.y - step.y) - step.y * kk, (hit_pos.z - step.z) - step.z * kk);
-  }
+  if (hit) out_pos = refine_hit(hit_pos, step, prev, hit_d);
   const unsigned long long hm = __ballot(hit);
   if (hm) {
-    const int leader = __ffsll((long long)hm) - 1;
-    uint32_t base = 0;
-    if (ln == leader) base = atomicAdd(hit_count, (uint32_t)__popcll(hm));
-    base = __shfl(base, leader);
+    const uint32_t base = wave_append(hit_count, hm, ln);
     if (hit) {
       Hit h;
       h.x = out_pos.x; h.y = out_pos.y; h.z = out_pos.z; h.pix = (uint32_t)(py * P.w + px);
-      hits[base + (uint32_t)__popcll(hm & ((1ull << ln) - 1ull))] = h;
+      hits[base + wave_rank(hm, ln)] = h;
     }
   }
   if (inside) {
-    if (!hit) {                                                         // discard: the target keeps its clear value
-      const size_t oi = (size_t)py * R.stride + px;
-      R.color[oi] = make_float4(R.clear[0], R.clear[1], R.clear[2], R.clear[3]);
-      R.depth[oi] = 1.0f;
-    }
-    const float ns = (float)n * 0.0027f;                                // writeNumSamples(), :395-398
-    const int sx = px + P.vp_org[0], sy = py + P.vp_org[1];
-    if (sx >= 0 && sy >= 0 && sx < P.w && sy < P.h) R.nsamples[(size_t)sy * P.w + sx] = covered ? ns : 0.0f;
+    if (!hit) store_clear(R, px, py);
+    write_num_samples(P, R, px, py, n, covered);
   }
 }
 
@@ -820,8 +791,7 @@ __device__ __forceinline__ void march_long(const ViewParams& P, const Volume& V,
     const bool live = r < count;
     LongRay L = longs[live ? r : r0];
     const int px = (int)(L.pix % (uint32_t)P.w), py = (int)(L.pix / (uint32_t)P.w);
-    const float3 dn = normalize3(pixel_dir_vol(P, (float)px + 0.5f, (float)py + 0.5f));
-    const float3 step = make_float3(dn.x * sd, dn.y * sd, dn.z * sd);
+    const float3 step = pixel_step(P, px, py, sd);
     float3 pos = make_float3(L.x, L.y, L.z);
     float prev = L.prev;
     uint32_t n = L.n;
@@ -834,10 +804,10 @@ __device__ __forceinline__ void march_long(const ViewParams& P, const Volume& V,
       p[0] = pos;
       for (int t = 0; t < j; ++t) {
 #pragma unroll
-        for (int k = 0; k < kLongBatch; ++k) p[0] = make_float3(p[0].x + step.x, p[0].y + step.y, p[0].z + step.z);
+        for (int k = 0; k < kLongBatch; ++k) p[0] = ray_advance(p[0], step);
       }
 #pragma unroll
-      for (int k = 1; k < kLongBatch; ++k) p[k] = make_float3(p[k - 1].x + step.x, p[k - 1].y + step.y, p[k - 1].z + step.z);
+      for (int k = 1; k < kLongBatch; ++k) p[k] = ray_advance(p[k - 1], step);
 #pragma unroll
       for (int k = 0; k < kLongBatch; ++k) d[k] = tex3d_tsdf<kSparse, true>(V, p[k].x, p[k].y, p[k].z);   // (the long pass only exists for whole-volume contexts)     // unconditional: taps are clamped into the allocation
       // examine this lane's eight samples in order
@@ -874,25 +844,19 @@ __device__ __forceinline__ void march_long(const ViewParams& P, const Volume& V,
           n = L.max_n; done = true;
         } else {
           prev = d7_last;
-          pos = make_float3(p7_last.x + step.x, p7_last.y + step.y, p7_last.z + step.z);
+          pos = ray_advance(p7_last, step);
           n += (uint32_t)(kLanes * kLongBatch);
         }
       }
     }
     if (live && j == 0) {
-      if (hit) {                                                        // approximate ray-cell intersection, :99-101
-        const float kk = prev / (hit_d - prev);
+      if (hit) {
+        const float3 hp = refine_hit(hit_pos, step, prev, hit_d);
         Hit h;
-        h.x = (hit_pos.x - step.x) - step.x * kk; h.y = (hit_pos.y - step.y) - step.y * kk; h.z = (hit_pos.z - step.z) - step.z * kk;
-        h.pix = L.pix;
+        h.x = hp.x; h.y = hp.y; h.z = hp.z; h.pix = L.pix;
         shade_hit<kSparse>(P, *T, *F, V, R, h);                         // no list: the hit is shaded where it was found
-      } else {
-        const size_t oi = (size_t)py * R.stride + px;
-        R.color[oi] = make_float4(R.clear[0], R.clear[1], R.clear[2], R.clear[3]);
-        R.depth[oi] = 1.0f;
-      }
-      const int sx = px + P.vp_org[0], sy = py + P.vp_org[1];           // writeNumSamples(), :395-398
-      if (sx >= 0 && sy >= 0 && sx < P.w && sy < P.h) R.nsamples[(size_t)sy * P.w + sx] = (float)n * 0.0027f;
+      } else store_clear(R, px, py);
+      write_num_samples(P, R, px, py, n);
     }
   }
 }
@@ -903,10 +867,7 @@ __device__ __forceinline__ void shade_hit(const ViewParams& P, const StreamTable
   const float limit = V.limit, sd = limit * 0.5f;
   const float3 pos = make_float3(h.x, h.y, h.z);
   const int px = (int)(h.pix % (uint32_t)P.w), py = (int)(h.pix / (uint32_t)P.w);
-  const float gx = tex3d_tsdf<kSparse>(V, pos.x + sd, pos.y, pos.z) - tex3d_tsdf<kSparse>(V, pos.x - sd, pos.y, pos.z);
-  const float gy = tex3d_tsdf<kSparse>(V, pos.x, pos.y + sd, pos.z) - tex3d_tsdf<kSparse>(V, pos.x, pos.y - sd, pos.z);
-  const float gz = tex3d_tsdf<kSparse>(V, pos.x, pos.y, pos.z + sd) - tex3d_tsdf<kSparse>(V, pos.x, pos.y, pos.z - sd);
-  const float3 gn = normalize3(make_float3(gx, gy, gz));              // get_gradient(), :140-149
+  const float3 gn = tsdf_gradient<kSparse>(V, pos, sd);
   const float4 vn4 = mat_mul(P.normal, -gn.x, -gn.y, -gn.z, 0.0f);
   const float3 vn = normalize3(make_float3(vn4.x, vn4.y, vn4.z));
   const float4 vp4 = mat_mul(P.mv_v2w, pos.x, pos.y, pos.z, 1.0f);
@@ -1079,8 +1040,7 @@ __global__ __launch_bounds__(256) void k_comp_init(RayTarget R, int w, int h, un
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= w * h) return;
   const int x = i % w, y = i / w;
-  R.color[(size_t)y * R.stride + x] = make_float4(R.clear[0], R.clear[1], R.clear[2], R.clear[3]);
-  R.depth[(size_t)y * R.stride + x] = 1.0f;
+  store_clear(R, x, y);
   R.nsamples[i] = own_counts ? fabsf(R.nsamples[i]) : 0.0f;   // misses carry -count in slab mode (a context that did not march has none); a hit pixel is overwritten in (3)
   key[i] = ~0ull;
 }

@@ -92,29 +92,22 @@ __global__ __launch_bounds__(kRayThreads) void k_rays_march(Volume V, RayCast Q,
   const float len = sqrtf(len2);
   const bool valid = in && ray_finite(o.x) && ray_finite(o.y) && ray_finite(o.z) && ray_finite(d.x) && ray_finite(d.y) && ray_finite(d.z) &&
                      len > 0.0f && ray_finite(len) && !(t_min != t_min);
-  const float3 dn = normalize3(d);
-  const float3 step = make_float3(dn.x * sd, dn.y * sd, dn.z * sd);     // :64
+  const float3 step = ray_step(d, sd);
   uint32_t max_n = 0, status = valid ? 0u : TSDF_RAY_INVALID;
   float3 pos = make_float3(0, 0, 0);
-  if (valid) {                                                          // intersectBox(), :363-374, as k_march has it
-    const float3 inv = make_float3(1.0f / step.x, 1.0f / step.y, 1.0f / step.z);
-    const float3 tbot = make_float3(inv.x * (0.0f - o.x), inv.y * (0.0f - o.y), inv.z * (0.0f - o.z));
-    const float3 ttop = make_float3(inv.x * (1.0f - o.x), inv.y * (1.0f - o.y), inv.z * (1.0f - o.z));
-    const float3 tmn = make_float3(fminf(ttop.x, tbot.x), fminf(ttop.y, tbot.y), fminf(ttop.z, tbot.z));
-    const float3 tmx = make_float3(fmaxf(ttop.x, tbot.x), fmaxf(ttop.y, tbot.y), fmaxf(ttop.z, tbot.z));
-    const float t0 = fmaxf(fmaxf(tmn.x, tmn.y), fmaxf(tmn.x, tmn.z));
-    float t1 = fminf(fminf(tmx.x, tmx.y), fminf(tmx.x, tmx.z));
-    if (!(t0 <= t1) || t1 < 0.0f) status = TSDF_RAY_OUTSIDE;
+  if (valid) {
+    const CubeSpan span = unit_cube_span(o, step);
+    if (!span.hit) status = TSDF_RAY_OUTSIDE;
     else {
-      float t_near = t0 < 0.0f ? 0.0f : t0;                             // :75-86
+      float t_near = span_near(span.t0), t1 = span.t1;
       // the caller's interval, from units of `dir` to steps: one step is sd / len of them
       const float per = len / sd, s_min = t_min * per, s_max = t_max * per;
       if (s_min > t_near) t_near = s_min;
       if (s_max < t1) t1 = s_max;
       if (!(t_near <= t1)) status = TSDF_RAY_OUTSIDE;
       else {
-        pos = make_float3(o.x + step.x * t_near, o.y + step.y * t_near, o.z + step.z * t_near);
-        max_n = (uint32_t)fminf(ceilf(fabsf(t1 - t_near)), Q.n_cap);
+        pos = ray_at(o, step, t_near);
+        max_n = (uint32_t)fminf(span_samples(t_near, t1), Q.n_cap);
       }
     }
   }
@@ -131,7 +124,7 @@ __global__ __launch_bounds__(kRayThreads) void k_rays_march(Volume V, RayCast Q,
   if (kPart) {
     while (n < max_n && !sample_owned(V, pos.z)) {                      // in front of the run: the additions alone
       pos_prev = pos;
-      pos = make_float3(pos.x + step.x, pos.y + step.y, pos.z + step.z);
+      pos = ray_advance(pos, step);
       n += 1; prev_mine = false;
     }
   }
@@ -140,9 +133,9 @@ __global__ __launch_bounds__(kRayThreads) void k_rays_march(Volume V, RayCast Q,
     if (try_skip) {
       const uint32_t m = min((uint32_t)Q.run, max_n - n);
       float3 e = pos;
-      for (uint32_t k = 1; k < m; ++k) e = make_float3(e.x + step.x, e.y + step.y, e.z + step.z);
+      for (uint32_t k = 1; k < m; ++k) e = ray_advance(e, step);
       if ((!kPart || sample_owned(V, e.z)) && ray_run_clear<kSparse, kPart>(V, pos, e)) {
-        pos = make_float3(e.x + step.x, e.y + step.y, e.z + step.z);
+        pos = ray_advance(e, step);
         n += m; prev = ml;
         if (kPart) { owned += m; prev_mine = true; }
         continue;
@@ -153,7 +146,7 @@ __global__ __launch_bounds__(kRayThreads) void k_rays_march(Volume V, RayCast Q,
     float dv[kRayBatch];
     p[0] = pos;
 #pragma unroll
-    for (int k = 1; k < kRayBatch; ++k) p[k] = make_float3(p[k - 1].x + step.x, p[k - 1].y + step.y, p[k - 1].z + step.z);
+    for (int k = 1; k < kRayBatch; ++k) p[k] = ray_advance(p[k - 1], step);
 #pragma unroll
     for (int k = 0; k < kRayBatch; ++k) dv[k] = tex3d_tsdf<kSparse, !kPart>(V, p[k].x, p[k].y, p[k].z);   // unconditional: taps are clamped into the allocation
     bool all_clear = true;
@@ -170,7 +163,7 @@ __global__ __launch_bounds__(kRayThreads) void k_rays_march(Volume V, RayCast Q,
       }
     }
     if (kPart && !mine) break;                                          // the batch left the slab
-    if (!hit) pos = make_float3(p[kRayBatch - 1].x + step.x, p[kRayBatch - 1].y + step.y, p[kRayBatch - 1].z + step.z);
+    if (!hit) pos = ray_advance(p[kRayBatch - 1], step);
     try_skip = all_clear;                                               // back in empty space: look at the classes again
   }
   if (kPart) {
@@ -179,13 +172,11 @@ __global__ __launch_bounds__(kRayThreads) void k_rays_march(Volume V, RayCast Q,
   }
   float3 pu = make_float3(0, 0, 0), pw = make_float3(0, 0, 0);
   float t = -1.0f;
-  if (hit) {                                                            // approximate ray-cell intersection, :99-101
-    const float kk = prev / (hit_d - prev);
-    pu = make_float3((hit_pos.x - step.x) - step.x * kk, (hit_pos.y - step.y) - step.y * kk, (hit_pos.z - step.z) - step.z * kk);
+  if (hit) {
+    pu = refine_hit(hit_pos, step, prev, hit_d);
     t = ((pu.x - o.x) * d.x + (pu.y - o.y) * d.y + (pu.z - o.z) * d.z) / len2;
     pw = pu;
-    if (!(Q.flags & TSDF_RAYS_UNIT_CUBE))                               // vol_to_world, in the mesh section's order
-      pw = make_float3(Q.bbox_min[0] + pu.x * Q.ext[0], Q.bbox_min[1] + pu.y * Q.ext[1], Q.bbox_min[2] + pu.z * Q.ext[2]);
+    if (!(Q.flags & TSDF_RAYS_UNIT_CUBE)) pw = vol_to_world(Q.bbox_min, pu, Q.ext[0], Q.ext[1], Q.ext[2]);
     status |= TSDF_RAY_HIT;
   }
   if (in) {
@@ -196,14 +187,11 @@ __global__ __launch_bounds__(kRayThreads) void k_rays_march(Volume V, RayCast Q,
   // compact the hits of this wave into the list (one atomic per wave): what k_rays_surface runs over
   const unsigned long long hm = __ballot(hit);
   if (surf && hm) {
-    const int leader = __ffsll((long long)hm) - 1;
-    uint32_t base = 0;
-    if (ln == leader) base = atomicAdd(list_count, (uint32_t)__popcll(hm));
-    base = __shfl(base, leader);
+    const uint32_t base = wave_append(list_count, hm, ln);
     if (hit) {
       RayHitRec h;
       h.x = pu.x; h.y = pu.y; h.z = pu.z; h.ray = i;
-      list[base + (uint32_t)__popcll(hm & ((1ull << ln) - 1ull))] = h;   // (base + rank < hits of the launch <= Q.n <= the list's capacity)
+      list[base + wave_rank(hm, ln)] = h;   // (base + rank < hits of the launch <= Q.n <= the list's capacity)
     }
   }
   // tsdf_ray_stats: hits, samples accounted for, samples fetched
@@ -215,7 +203,7 @@ __global__ __launch_bounds__(kRayThreads) void k_rays_march(Volume V, RayCast Q,
   }
 }
 
-// the surface at the hits: exactly the mesh section's normal and colour (k_mesh_vertices' text) at the hit's unit-cube position
+// the surface at the hits: the mesh section's normal (tsdf_gradient, world_normal: sampling.hpp) and colour at the hit's unit-cube position
 template <bool kSparse>
 __global__ __launch_bounds__(kRayThreads) void k_rays_surface(Volume V, StreamTable T, FrameImages F, RayCast Q, const RayHitRec* __restrict__ list,
                                                               const uint32_t* __restrict__ list_count, float4* __restrict__ surf) {
@@ -226,11 +214,7 @@ __global__ __launch_bounds__(kRayThreads) void k_rays_surface(Volume V, StreamTa
   const float limit = V.limit, sd = limit * 0.5f;
   float4 nrm = make_float4(0, 0, 0, 0), col = make_float4(0, 0, 0, 0);
   if (Q.flags & TSDF_RAY_NORMALS) {
-    const float gx = tex3d_tsdf<kSparse>(V, u.x + sd, u.y, u.z) - tex3d_tsdf<kSparse>(V, u.x - sd, u.y, u.z);
-    const float gy = tex3d_tsdf<kSparse>(V, u.x, u.y + sd, u.z) - tex3d_tsdf<kSparse>(V, u.x, u.y - sd, u.z);
-    const float gz = tex3d_tsdf<kSparse>(V, u.x, u.y, u.z + sd) - tex3d_tsdf<kSparse>(V, u.x, u.y, u.z - sd);
-    const float3 gn = normalize3(make_float3(gx, gy, gz));            // get_gradient(), tsdf_raymarch.fs:140-149
-    const float3 nn = normalize3(make_float3(-gn.x / Q.ext[0], -gn.y / Q.ext[1], -gn.z / Q.ext[2]));
+    const float3 nn = world_normal(tsdf_gradient<kSparse>(V, u, sd), Q.ext[0], Q.ext[1], Q.ext[2]);
     nrm = make_float4(nn.x, nn.y, nn.z, 0.0f);
   }
   if (Q.flags & TSDF_RAY_COLOURS) col = blend_colors(T, F, limit, u);
@@ -269,18 +253,16 @@ __global__ __launch_bounds__(kRayThreads) void k_rays_merge(const float4* __rest
   if (surf) { surf[at] = surf_parts[from]; surf[at + 1] = surf_parts[from + 1]; }
 }
 
+// the one launcher of k_rays_march: part = a Z-slab context's part cast.  (The two names below are what the binding selects between; they only set the flag.)
+static void launch_rays_march_as(bool part, hipStream_t st, const Volume& V, const RayCast& Q, const tsdf_ray* rays, tsdf_ray_hit* hits, tsdf_ray_surface* surf,
+                                 RayHitRec* list, uint32_t* list_count, unsigned long long* stats) {
+  const auto k = !part ? (V.slot ? k_rays_march<true, false> : k_rays_march<false, false>) : (V.slot ? k_rays_march<true, true> : k_rays_march<false, true>);
+  hipLaunchKernelGGL(k, dim3((Q.n + kRayThreads - 1) / kRayThreads), dim3(kRayThreads), 0, st, V, Q, (const float4*)rays, (float4*)hits, (float4*)surf, list, list_count, stats);
+}
 void launch_rays_march(hipStream_t st, const Volume& V, const RayCast& Q, const tsdf_ray* rays, tsdf_ray_hit* hits, tsdf_ray_surface* surf, RayHitRec* list,
-                       uint32_t* list_count, unsigned long long* stats) {
-  const dim3 g((Q.n + kRayThreads - 1) / kRayThreads), b(kRayThreads);
-  if (V.slot) hipLaunchKernelGGL((k_rays_march<true, false>), g, b, 0, st, V, Q, (const float4*)rays, (float4*)hits, (float4*)surf, list, list_count, stats);
-  else hipLaunchKernelGGL((k_rays_march<false, false>), g, b, 0, st, V, Q, (const float4*)rays, (float4*)hits, (float4*)surf, list, list_count, stats);
-}
+                       uint32_t* list_count, unsigned long long* stats) { launch_rays_march_as(false, st, V, Q, rays, hits, surf, list, list_count, stats); }
 void launch_rays_march_part(hipStream_t st, const Volume& V, const RayCast& Q, const tsdf_ray* rays, tsdf_ray_hit* hits, tsdf_ray_surface* surf, RayHitRec* list,
-                            uint32_t* list_count, unsigned long long* stats) {
-  const dim3 g((Q.n + kRayThreads - 1) / kRayThreads), b(kRayThreads);
-  if (V.slot) hipLaunchKernelGGL((k_rays_march<true, true>), g, b, 0, st, V, Q, (const float4*)rays, (float4*)hits, (float4*)surf, list, list_count, stats);
-  else hipLaunchKernelGGL((k_rays_march<false, true>), g, b, 0, st, V, Q, (const float4*)rays, (float4*)hits, (float4*)surf, list, list_count, stats);
-}
+                            uint32_t* list_count, unsigned long long* stats) { launch_rays_march_as(true, st, V, Q, rays, hits, surf, list, list_count, stats); }
 void launch_rays_merge(hipStream_t st, const tsdf_ray_hit* hit_parts, const tsdf_ray_surface* surf_parts, uint32_t parts, uint32_t n, uint64_t stride_records,
                        tsdf_ray_hit* hits, tsdf_ray_surface* surf) {
   hipLaunchKernelGGL(k_rays_merge, dim3((n + kRayThreads - 1) / kRayThreads), dim3(kRayThreads), 0, st, (const float4*)hit_parts, (const float4*)surf_parts, parts, n,

@@ -273,16 +273,10 @@ __device__ __forceinline__ void mesh_tile_vertices(const Volume& V, const Stream
   for (uint32_t v = threadIdx.x; v < nv; v += kMeshThreads) {
     const float3 u = mesh_vertex_position<kSparse, kLevel>(V, t, s_f, s_edge[v]);
     const size_t o = first + v;
-    out_pos[o * 3 + 0] = G.bbox_min[0] + u.x * ex;                     // vol_to_world, recon_integration.cpp:66-72
-    out_pos[o * 3 + 1] = G.bbox_min[1] + u.y * ey;
-    out_pos[o * 3 + 2] = G.bbox_min[2] + u.z * ez;
+    const float3 w = vol_to_world(G.bbox_min, u, ex, ey, ez);
+    out_pos[o * 3 + 0] = w.x; out_pos[o * 3 + 1] = w.y; out_pos[o * 3 + 2] = w.z;
     if (out_nrm) {
-      const float gx = tex3d_tsdf<kSparse>(V, u.x + sd, u.y, u.z) - tex3d_tsdf<kSparse>(V, u.x - sd, u.y, u.z);
-      const float gy = tex3d_tsdf<kSparse>(V, u.x, u.y + sd, u.z) - tex3d_tsdf<kSparse>(V, u.x, u.y - sd, u.z);
-      const float gz = tex3d_tsdf<kSparse>(V, u.x, u.y, u.z + sd) - tex3d_tsdf<kSparse>(V, u.x, u.y, u.z - sd);
-      const float3 gn = normalize3(make_float3(gx, gy, gz));          // get_gradient(), tsdf_raymarch.fs:140-149, as shade_hit does it
-      // inverseTranspose(vol_to_world) of the shader's -gn: the NormalMatrix of recon_integration.cpp:199 without the model-view
-      const float3 n = normalize3(make_float3(-gn.x / ex, -gn.y / ey, -gn.z / ez));
+      const float3 n = world_normal(tsdf_gradient<kSparse>(V, u, sd), ex, ey, ez);
       out_nrm[o * 3 + 0] = n.x; out_nrm[o * 3 + 1] = n.y; out_nrm[o * 3 + 2] = n.z;
     }
     if (out_col) out_col[o] = blend_colors(T, F, limit, u);           // all four components: alpha +1 valid, -1 fallback
@@ -340,11 +334,7 @@ __device__ __forceinline__ void mesh_tile_vertices_packed(const Volume& V, const
     if (kFlags == 0u) { ((uint2*)out)[o] = pos; continue; }
     uint32_t nrm = 0u, col = 0u;
     if (kFlags & 1u) {
-      const float gx = tex3d_tsdf<kSparse>(V, u.x + sd, u.y, u.z) - tex3d_tsdf<kSparse>(V, u.x - sd, u.y, u.z);
-      const float gy = tex3d_tsdf<kSparse>(V, u.x, u.y + sd, u.z) - tex3d_tsdf<kSparse>(V, u.x, u.y - sd, u.z);
-      const float gz = tex3d_tsdf<kSparse>(V, u.x, u.y, u.z + sd) - tex3d_tsdf<kSparse>(V, u.x, u.y, u.z - sd);
-      const float3 gn = normalize3(make_float3(gx, gy, gz));
-      nrm = mesh_oct_normal(normalize3(make_float3(-gn.x / ex, -gn.y / ey, -gn.z / ez)));
+      nrm = mesh_oct_normal(world_normal(tsdf_gradient<kSparse>(V, u, sd), ex, ey, ez));
     }
     if (kFlags & 2u) {
       const float4 c = blend_colors(T, F, limit, u);

@@ -175,4 +175,32 @@ __device__ __forceinline__ float3 normalize3(float3 a) {
   return make_float3(a.x * s, a.y * s, a.z * s);
 }
 
+// get_gradient(), tsdf_raymarch.fs:140-149, at the unit-cube position u: central differences sd apart, normalised.  The one text of the draw's
+// shading (shade_hit), the ray queries' surface (k_rays_surface) and the mesh's vertex normals (mesh_dev.hpp).
+template <bool kSparse>
+__device__ __forceinline__ float3 tsdf_gradient(const Volume& V, float3 u, float sd) {
+  const float gx = tex3d_tsdf<kSparse>(V, u.x + sd, u.y, u.z) - tex3d_tsdf<kSparse>(V, u.x - sd, u.y, u.z);
+  const float gy = tex3d_tsdf<kSparse>(V, u.x, u.y + sd, u.z) - tex3d_tsdf<kSparse>(V, u.x, u.y - sd, u.z);
+  const float gz = tex3d_tsdf<kSparse>(V, u.x, u.y, u.z + sd) - tex3d_tsdf<kSparse>(V, u.x, u.y, u.z - sd);
+  return normalize3(make_float3(gx, gy, gz));
+}
+// the world normal of the gradient gn: inverseTranspose(vol_to_world) of the shader's -gn, the NormalMatrix of recon_integration.cpp:199 without the model-view
+__device__ __forceinline__ float3 world_normal(float3 gn, float ex, float ey, float ez) {
+  return normalize3(make_float3(-gn.x / ex, -gn.y / ey, -gn.z / ez));
+}
+// vol_to_world, recon_integration.cpp:66-72, of the unit-cube position u
+__device__ __forceinline__ float3 vol_to_world(const float* bbox_min, float3 u, float ex, float ey, float ez) {
+  return make_float3(bbox_min[0] + u.x * ex, bbox_min[1] + u.y * ey, bbox_min[2] + u.z * ez);
+}
+
+// Wave-compacted append to a list: the lanes of `mask` (a __ballot) take consecutive entries for ONE atomic of the wave.  The whole wave calls wave_append
+// inside `if (mask)` for the wave's base; a lane of the mask stores at base + wave_rank(mask, ln).  (Two functions: the rank belongs at the store -- DESIGN.md section 4.)
+__device__ __forceinline__ uint32_t wave_append(uint32_t* count, unsigned long long mask, int ln) {
+  const int leader = __ffsll((long long)mask) - 1;
+  uint32_t base = 0;
+  if (ln == leader) base = atomicAdd(count, (uint32_t)__popcll(mask));
+  return __shfl(base, leader);
+}
+__device__ __forceinline__ uint32_t wave_rank(unsigned long long mask, int ln) { return (uint32_t)__popcll(mask & ((1ull << ln) - 1ull)); }
+
 }  // namespace rr
