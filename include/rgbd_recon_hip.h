@@ -655,7 +655,8 @@ int32_t tsdf_mesh_extract_lod(tsdf_ctx* ctx, uint32_t flags, uint32_t level, uin
  * tsdf_mesh_slab_download: the shapes of tsdf_mesh_download; any pointer may be NULL.  TSDF_ERR_STATE before an extract, for an attribute the extract did
  *   not produce, and for the triangles before a link.
  * tsdf_mesh_slab_stats: out = {owned lattice tiles, of those skipped by class, of those with surface, bytes of the part's mesh storage}.
- * Out of scope.  Gaps between slabs.  Mesh streaming, components and texture taps on parts (run them where the concatenated mesh is).  The native RCCL
+ * Out of scope.  Gaps between slabs.  Mesh streaming, components and texture taps on parts are not these entries' business: each has entries of its
+ *   own further down (the part ring; "mesh components on Z-slab contexts", whose labels a new tsdf_mesh_slab_link releases).  The native RCCL
  *   exchange: the two numbers travel by whatever carries the caller's other collectives (rgbd-recon_amd/multigpu.py: SlabDriver.extract_mesh). */
 int32_t tsdf_mesh_slab_extract(tsdf_ctx* ctx, uint32_t flags, uint32_t level, uint64_t* n_vertices, uint64_t* n_triangles);
 int32_t tsdf_mesh_slab_seam(tsdf_ctx* ctx, uint32_t* out);
@@ -939,7 +940,8 @@ int32_t tsdf_texture_tap_stats(tsdf_ctx* ctx, uint64_t out[4]);
  * Errors.  TSDF_ERR_STATE without an extract (a Z-slab context extracts no mesh, so always there); for download, keep and filter without components of
  *   the current mesh.  TSDF_ERR_INVALID_ARGUMENT for a NULL keep or a NULL out.  -1 for a NULL context.
  * The streamed ring (tsdf_mesh_stream) filters by the same rule inside the frame: "mesh streaming: the filtered frame" below.
- * Out of scope.  Z-slab contexts (tsdf_mesh_slab_extract's parts join into one mesh on the host: label that one).  Welding by position.  Geometric measures per component (area, volume, bounding box): the caller has the arrays.
+ * Out of scope.  Z-slab contexts keep answering TSDF_ERR_STATE here: tsdf_mesh_slab_extract's parts are labelled where they are by "mesh components
+ *   on Z-slab contexts" below, and the joined labels are these.  Welding by position.  Geometric measures per component (area, volume, bounding box): the caller has the arrays.
  *   A context that never calls these entries runs exactly what it ran before they existed. */
 typedef struct tsdf_mesh_component { uint32_t first_vertex, n_vertices, n_triangles, reserved /* 0 */; } tsdf_mesh_component;
 int32_t tsdf_mesh_components(tsdf_ctx* ctx, uint64_t* n_components);
@@ -947,6 +949,74 @@ int32_t tsdf_mesh_download_components(tsdf_ctx* ctx, uint32_t* vertex_component,
 int32_t tsdf_mesh_keep_components(tsdf_ctx* ctx, const uint8_t* keep, uint64_t* n_vertices, uint64_t* n_triangles);
 int32_t tsdf_mesh_filter_components(tsdf_ctx* ctx, uint32_t min_triangles, uint64_t* n_vertices, uint64_t* n_triangles);
 int32_t tsdf_mesh_component_stats(tsdf_ctx* ctx, uint64_t out[4]);
+
+/* ---- mesh components on Z-slab contexts: part labels that join byte for byte -------------------------------
+ * At the multi-GPU configurations the concatenated mesh exists only in host memory; these entries label it where its parts are.  No counterpart in the
+ * reference.  tests/mesh_slab_component_reference.py restates the split, the lists, the merge and the link in numpy.
+ *
+ * Definition.  Take the whole volume's mesh at a level -- the concatenation of the linked parts of "mesh extraction on Z-slab contexts" -- and its
+ *   components, their numbering and their 16-byte table as "mesh components" defines them.  A part's results are
+ *   vertex_component [the part's n_vertices]:    GLOBAL component numbers;
+ *   triangle_component [the part's n_triangles]: GLOBAL numbers;
+ *   table: the rows of the components whose representative (smallest vertex index) the part owns, in order; n_vertices and n_triangles are the WHOLE
+ *          component's counts, whatever slabs it spans.
+ *   Concatenated in slab order the three arrays are byte for byte what tsdf_mesh_components + tsdf_mesh_download_components give on a whole-volume
+ *   context after tsdf_mesh_extract_lod at that level.  A whole-volume context is the one-slab case.
+ * Two facts.  Every triangle of a part has an own vertex: corner 0 of its cell is in every Kuhn tetrahedron, so every emitted triangle has a vertex on an
+ *   edge at corner 0, which the cell's origin owns; and indices into the slab above are all larger than own indices.  So the smallest index of every
+ *   component of a part taken alone -- a LOCAL component -- is an own vertex, its local root.  And: two local components of one slab can be joined through
+ *   another slab only (two columns that meet in the slab above), so merging neighbouring slabs pair by pair is not enough: the merge is transitive
+ *   over all seams.
+ * Protocol.  Three steps per slab and one host merge; no float anywhere, and arrival order decides nothing (flags and scans; the union-find's links only
+ *   point to a smaller index).
+ * 1. tsdf_mesh_slab_components labels the linked part on the context's stream, over the own vertices plus the span of indices into the slab above that
+ *   tsdf_mesh_slab_link's check knows, synchronises, and builds three lists on the device, every index in them GLOBAL:
+ *   down records (only when slab_z0 > 0): for every own vertex owned by a lattice point of plane 0 of the first owned lattice tile layer -- the vertices
+ *          the slab below can index -- {vertex, root}, ascending by vertex.  tsdf_mesh_seam_vertex, 8 bytes.
+ *   up records: for every vertex of the slab above that a triangle of the part uses, {vertex, root}, root its local root (an own vertex), ascending by
+ *          vertex.
+ *   root records: for every distinct root in the two lists {root, rank, n_vertices, n_triangles}: rank = the local roots with a smaller index, the
+ *          counts the local component's own vertices and the part's triangles in it; ascending by root.  tsdf_mesh_seam_root, 16 bytes.
+ *   out = {local components, down records, up records, root records}.  Timer "mesh_slab_components".
+ *   tsdf_mesh_slab_component_seam copies the three lists (sized by out[1 .. 3]); any pointer may be NULL.
+ * 2. tsdf_mesh_merge_component_seams is a pure host function: no context, no device.  Per slab, in slab order (tsdf_mesh_component_seams): vertex_base,
+ *   n_vertices, the local component count and the three lists.  A union-find over all root records, the smaller root on top, joins each up record
+ *   (g, r) of slab k with the down record (g, r') of slab k + 1; down records no up record matches are ignored.  Output per slab: component_base[k] =
+ *   the components whose representative lies in the slabs below, and one tsdf_mesh_component_link (32 bytes) per root record, in the same order, slab
+ *   after slab: {root, final_root, component, 0, n_vertices, n_triangles, 0, 0} -- the final component's global number and the WHOLE component's totals.
+ *   A surviving boundary root is numbered component_base + rank - (removed roots of that slab with a smaller index), removed = under a smaller final
+ *   root; this is what step 3's scan gives.  *n_components = the total.  TSDF_ERR_INVALID_ARGUMENT, nothing written: an up record without its down
+ *   record, a list that is not strictly ascending, a root outside its slab, slabs out of order.  rgbd-recon_amd/binding.py has its numpy twin.
+ * 3. tsdf_mesh_slab_link_components takes the slab's component_base and its links.  The host validates before any launch -- a bad index never reaches a
+ *   scatter --: n_links equals the exported root count; links[i].root is exported root i; final_root <= root; final_root == root, or final_root <
+ *   vertex_base, or it is another exported root of this slab.  TSDF_ERR_INVALID_ARGUMENT otherwise, the state untouched.  Then, on the device: the links
+ *   are scattered to their roots, the own final representatives flagged and scanned for the numbering, and vertex_component, triangle_component (any of
+ *   the three vertices: they agree) and the owned table rows written, boundary components with the links' totals.  *n_owned (may be NULL) = the rows.
+ *   It may be called again with other links.  Timer "mesh_slab_components_link".
+ *   tsdf_mesh_slab_download_components copies the three results; any pointer may be NULL.
+ * tsdf_mesh_slab_component_stats: out = {local components, components owned (0 before step 3), seam records down + up, local roots removed}.
+ * Lifetime.  The labels belong to the linked part: released by the next tsdf_mesh_slab_extract, by a new tsdf_mesh_slab_link (they hold global
+ *   indices), tsdf_set_voxel_size and tsdf_destroy.  An empty part (zero vertices) launches nothing and answers zeros.
+ * Errors.  TSDF_ERR_STATE before a link; for _seam and _link_components before step 1; for _download_components before step 3; for _stats without a
+ *   part.  -1 for a NULL context.  TSDF_ERR_INVALID_ARGUMENT for a NULL out, and for NULL links with n_links > 0.  TSDF_ERR_OUT_OF_MEMORY leaves the
+ *   state as it was.  tsdf_mesh_components keeps answering TSDF_ERR_STATE on a Z-slab context.
+ * Out of scope.  Filtering the parts themselves (a per-part compaction and a second link with a per-seam-vertex remap: the links carry the whole
+ *   component's totals so that every slab can decide a keep rule without another exchange; the joined mesh is filtered on the host, binding.py:
+ *   drop_mesh_components).  Filtered part rings.  The native RCCL exchange: the lists travel by whatever carries the caller's other collectives
+ *   (rgbd-recon_amd/multigpu.py: SlabDriver.mesh_components). */
+typedef struct tsdf_mesh_seam_vertex { uint32_t vertex, root; } tsdf_mesh_seam_vertex;
+typedef struct tsdf_mesh_seam_root { uint32_t root, rank, n_vertices, n_triangles; } tsdf_mesh_seam_root;
+typedef struct tsdf_mesh_component_link { uint32_t root, final_root, component, reserved0 /* 0 */, n_vertices, n_triangles, reserved1 /* 0 */, reserved2 /* 0 */; } tsdf_mesh_component_link;
+typedef struct tsdf_mesh_component_seams {
+  uint64_t vertex_base, n_vertices, n_local, n_down, n_up, n_roots;
+  const tsdf_mesh_seam_vertex* down; const tsdf_mesh_seam_vertex* up; const tsdf_mesh_seam_root* roots;
+} tsdf_mesh_component_seams;
+int32_t tsdf_mesh_slab_components(tsdf_ctx* ctx, uint64_t out[4]);
+int32_t tsdf_mesh_slab_component_seam(tsdf_ctx* ctx, tsdf_mesh_seam_vertex* down, tsdf_mesh_seam_vertex* up, tsdf_mesh_seam_root* roots);
+int32_t tsdf_mesh_merge_component_seams(const tsdf_mesh_component_seams* slabs, uint32_t n_slabs, uint64_t* component_base, tsdf_mesh_component_link* links, uint64_t* n_components);
+int32_t tsdf_mesh_slab_link_components(tsdf_ctx* ctx, uint64_t component_base, const tsdf_mesh_component_link* links, uint64_t n_links, uint64_t* n_owned);
+int32_t tsdf_mesh_slab_download_components(tsdf_ctx* ctx, uint32_t* vertex_component, uint32_t* triangle_component, tsdf_mesh_component* table);
+int32_t tsdf_mesh_slab_component_stats(tsdf_ctx* ctx, uint64_t out[4]);
 
 /* ---- mesh streaming: the filtered frame -------------------------------------------------------------------
  * The ring of "mesh streaming" above with the keep rule of "mesh components" inside it: a streamed frame is already the mesh without its small

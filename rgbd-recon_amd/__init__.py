@@ -16,5 +16,7 @@ from .binding import (LANES_NO_FILL_THREAD, LANES_NO_INTEGRATE_LANE, LANES_ONE_S
                       MeshFrame, unpack_mesh_vertices, MESH_INDEX_U32, MESH_INDEX_TILE16, MESH_TILE_ROW_DTYPE, MeshCompact, unpack_mesh_triangles, MeshPart, join_mesh_parts, MESH_COMPONENT_DTYPE, RAYS_UNIT_CUBE, RAY_NORMALS, RAY_COLOURS, RAY_HIT, RAY_OUTSIDE, RAY_INVALID, Ray, RayHit, RaySurface,
                       RAY_DTYPE, RAY_HIT_DTYPE, RAY_SURFACE_DTYPE, as_rays, make_rays, merge_ray_parts,
                       TAPS_UNIT_CUBE, TAPS_SENSOR, TextureTap, SensorTap, TEXTURE_TAP_DTYPE, SENSOR_TAP_DTYPE, blend_from_taps,
-                      MESH_STREAM_TAPS, PackedTap, MeshTaps, PACKED_TAP_DTYPE, unpack_mesh_taps)
+                      MESH_STREAM_TAPS, PackedTap, MeshTaps, PACKED_TAP_DTYPE, unpack_mesh_taps,
+                      MESH_SEAM_VERTEX_DTYPE, MESH_SEAM_ROOT_DTYPE, MESH_COMPONENT_LINK_DTYPE, MeshComponentSeams, component_seams_struct, merge_mesh_component_seams,
+                      drop_mesh_components)
 from . import scene  # noqa: F401

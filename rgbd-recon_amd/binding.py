@@ -258,6 +258,118 @@ def unpack_mesh_vertices(vertices):
     return dict(position=v[:, :8].view(np.uint16)[:, :3], normal=v[:, 8:12].view(np.int16), colour=v[:, 12:16])
 
 
+# ---------------------------------------------------------------------- mesh components on Z-slab contexts: the lists, the merge, the joined mesh
+MESH_SEAM_VERTEX_DTYPE = np.dtype([("vertex", "<u4"), ("root", "<u4")])                                                # tsdf_mesh_seam_vertex
+MESH_SEAM_ROOT_DTYPE = np.dtype([("root", "<u4"), ("rank", "<u4"), ("n_vertices", "<u4"), ("n_triangles", "<u4")])    # tsdf_mesh_seam_root
+MESH_COMPONENT_LINK_DTYPE = np.dtype([("root", "<u4"), ("final_root", "<u4"), ("component", "<u4"), ("reserved0", "<u4"),
+                                      ("n_vertices", "<u4"), ("n_triangles", "<u4"), ("reserved1", "<u4"), ("reserved2", "<u4")])   # tsdf_mesh_component_link
+
+
+class MeshComponentSeams(C.Structure):
+    """tsdf_mesh_component_seams of rgbd_recon_hip.h"""
+    _fields_ = [("vertex_base", C.c_uint64), ("n_vertices", C.c_uint64), ("n_local", C.c_uint64), ("n_down", C.c_uint64), ("n_up", C.c_uint64),
+                ("n_roots", C.c_uint64), ("down", C.c_void_p), ("up", C.c_void_p), ("roots", C.c_void_p)]
+
+
+def _component_seam_lists(slabs):
+    """the merge's input with every list as a contiguous array of its dtype"""
+    return [dict(vertex_base=int(s["vertex_base"]), n_vertices=int(s["n_vertices"]), n_local=int(s["n_local"]),
+                 down=np.ascontiguousarray(s["down"], MESH_SEAM_VERTEX_DTYPE).reshape(-1), up=np.ascontiguousarray(s["up"], MESH_SEAM_VERTEX_DTYPE).reshape(-1),
+                 roots=np.ascontiguousarray(s["roots"], MESH_SEAM_ROOT_DTYPE).reshape(-1)) for s in slabs]
+
+
+def component_seams_struct(slabs):
+    """(the tsdf_mesh_component_seams array of `slabs`, the arrays it points into -- keep them alive as long as the array)"""
+    lists = _component_seam_lists(slabs)
+    arr = (MeshComponentSeams * max(len(lists), 1))()
+    for a, s in zip(arr, lists):
+        a.vertex_base, a.n_vertices, a.n_local = s["vertex_base"], s["n_vertices"], s["n_local"]
+        a.n_down, a.n_up, a.n_roots = len(s["down"]), len(s["up"]), len(s["roots"])
+        a.down, a.up, a.roots = s["down"].ctypes.data, s["up"].ctypes.data, s["roots"].ctypes.data
+    return arr, lists
+
+
+def merge_mesh_component_seams(slabs, native=False):
+    """The host merge of the slabs' seam lists (tsdf_mesh_merge_component_seams; csrc/mesh_cc_seams.hpp): slabs = per slab, in slab order,
+    dict(vertex_base, n_vertices, n_local, down, up, roots) with the lists of mesh_slab_component_seam().  Returns dict(component_base=[per slab],
+    links=[MESH_COMPONENT_LINK_DTYPE array per slab, one record per root record], n_components).  native=False: the numpy twin, ValueError for lists
+    the library refuses; native=True: the library's function through ctypes (it needs no device), TsdfError with code -1.  Identical bytes."""
+    lists = _component_seam_lists(slabs)
+    n_roots = [len(s["roots"]) for s in lists]
+    first = np.concatenate([[0], np.cumsum(n_roots)]).astype(np.int64)
+    split = lambda links: [links[first[k]:first[k + 1]] for k in range(len(lists))]
+    if native:
+        arr, keep = component_seams_struct(lists)
+        base, links, n = np.zeros(max(len(lists), 1), np.uint64), np.zeros(int(first[-1]), MESH_COMPONENT_LINK_DTYPE), C.c_uint64()
+        rc = load_library().tsdf_mesh_merge_component_seams(arr, C.c_uint32(len(lists)), base.ctypes.data_as(C.c_void_p), links.ctypes.data_as(C.c_void_p), C.byref(n))
+        if rc:
+            raise TsdfError(rc, "tsdf_mesh_merge_component_seams refused the lists")
+        return dict(component_base=[int(b) for b in base[:len(lists)]], links=split(links), n_components=int(n.value))
+    for k, s in enumerate(lists):
+        v0, v1 = s["vertex_base"], s["vertex_base"] + s["n_vertices"]
+        if v1 > 1 << 32 or s["n_local"] > s["n_vertices"] or (k and v0 < lists[k - 1]["vertex_base"] + lists[k - 1]["n_vertices"]):
+            raise ValueError(f"slab {k}: out of order, or past the 32-bit indices")
+        r, d, u = s["roots"], s["down"], s["up"]
+        ascending = lambda a: len(a) < 2 or bool((np.diff(a.astype(np.int64)) > 0).all())
+        if not (ascending(r["root"]) and ascending(r["rank"]) and ascending(d["vertex"]) and ascending(u["vertex"])):
+            raise ValueError(f"slab {k}: a list is not strictly ascending")
+        if ((r["root"] < v0) | (r["root"] >= v1) | (r["rank"] >= s["n_local"])).any() or not (np.isin(d["root"], r["root"]).all() and np.isin(u["root"], r["root"]).all()):
+            raise ValueError(f"slab {k}: a root outside its slab")
+        if ((d["vertex"] < v0) | (d["vertex"] >= v1) | (d["root"] > d["vertex"])).any() or (u["vertex"] < v1).any():
+            raise ValueError(f"slab {k}: a seam record's vertex on the wrong side of the seam")
+        if len(u) and (k + 1 == len(lists) or not np.isin(u["vertex"], lists[k + 1]["down"]["vertex"]).all()):
+            raise ValueError(f"slab {k}: an up record without its down record")
+    # the union-find over all root records: node ids ascend with the roots, the smaller on top
+    parent = list(range(int(first[-1])))
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    for k in range(len(lists) - 1):
+        s, a = lists[k], lists[k + 1]
+        if not len(s["up"]):
+            continue
+        below = first[k] + np.searchsorted(s["roots"]["root"], s["up"]["root"])
+        above_root = a["down"]["root"][np.searchsorted(a["down"]["vertex"], s["up"]["vertex"])]
+        above = first[k + 1] + np.searchsorted(a["roots"]["root"], above_root)
+        for x, y in zip(below.tolist(), above.tolist()):
+            x, y = find(x), find(y)
+            if x != y:
+                parent[max(x, y)] = min(x, y)
+    top = np.array([find(x) for x in range(len(parent))], np.int64)
+    records = np.concatenate([s["roots"] for s in lists]) if lists else np.zeros(0, MESH_SEAM_ROOT_DTYPE)
+    nv, nt = np.zeros(len(parent), np.int64), np.zeros(len(parent), np.int64)
+    np.add.at(nv, top, records["n_vertices"].astype(np.int64))
+    np.add.at(nt, top, records["n_triangles"].astype(np.int64))
+    if len(parent) and (nv.max() > 0xffffffff or nt.max() > 0xffffffff):
+        raise ValueError("a component's totals leave 32 bits")
+    base, number = [0], np.zeros(len(parent), np.int64)
+    for k, s in enumerate(lists):
+        nodes = np.arange(first[k], first[k + 1])
+        removed = top[nodes] != nodes
+        number[nodes] = base[k] + s["roots"]["rank"].astype(np.int64) - np.cumsum(removed)   # (read at surviving roots only)
+        base.append(base[k] + s["n_local"] - int(removed.sum()))
+    links = np.zeros(len(parent), MESH_COMPONENT_LINK_DTYPE)
+    links["root"], links["final_root"], links["component"] = records["root"], records["root"][top], number[top]
+    links["n_vertices"], links["n_triangles"] = nv[top], nt[top]
+    return dict(component_base=base[:-1], links=split(links), n_components=base[-1])
+
+
+def drop_mesh_components(mesh, vertex_component, triangle_component, keep):
+    """The joined mesh without the components c with keep[c] == 0, by tsdf_mesh_keep_components' rule: kept vertices and triangles in their order, rows
+    moved bit for bit, a vertex's new index the number of kept vertices before it.  mesh: dict(position, triangles, and normal / colour where present);
+    vertex_component / triangle_component: the joined arrays of the slabs' mesh_slab_download_components()."""
+    flags = np.asarray(keep) != 0
+    kv, kt = flags[np.asarray(vertex_component, np.int64)], flags[np.asarray(triangle_component, np.int64)]
+    new_index = (np.cumsum(kv) - kv).astype(np.uint32)
+    out = {k: np.ascontiguousarray(v[kv]) for k, v in mesh.items() if k in ("position", "normal", "colour")}
+    out["triangles"] = np.ascontiguousarray(new_index[np.asarray(mesh["triangles"], np.uint32).reshape(-1, 3)[kt]].reshape(-1, 3))
+    return out
+
+
 RAYS_UNIT_CUBE, RAY_NORMALS, RAY_COLOURS = 1, 2, 4   # tsdf_cast_rays: flags
 RAY_HIT, RAY_OUTSIDE, RAY_INVALID = 1, 2, 4         # tsdf_ray_hit: status bits
 
@@ -888,7 +1000,7 @@ class ReconIntegrationHip:
         n_triangles).  The halo must be current, as for a draw.  The triangles exist after mesh_slab_link."""
         nv, nt = C.c_uint64(), C.c_uint64()
         flags = (MESH_NORMALS if normals else 0) | (MESH_COLOURS if colours else 0)
-        self._mesh_slab = None
+        self._mesh_slab = self._mesh_slab_cc = None
         self._ck(self._L.tsdf_mesh_slab_extract(self._c, C.c_uint32(flags), C.c_uint32(int(level)), C.byref(nv), C.byref(nt)))
         s = 8 << int(level)
         self._mesh_slab = (nv.value, nt.value, (-(-self.res[1] // s), -(-self.res[0] // s)))
@@ -907,6 +1019,7 @@ class ReconIntegrationHip:
         mesh_slab_seam() of the slab directly above (None at the volume's top)."""
         above = None if above_seam is None else np.ascontiguousarray(above_seam, np.uint32)
         self._ck(self._L.tsdf_mesh_slab_link(self._c, C.c_uint64(int(vertex_base)), above.ctypes.data_as(C.POINTER(C.c_uint32)) if above is not None else None))
+        self._mesh_slab_cc = None                                        # (the labels held the indices of the link that was: the library has released them)
 
     def mesh_slab_download(self, normals=True, colours=True, triangles=True):
         """dict of the part's arrays, shaped as download_mesh's (TsdfError, code -4, before an extract, and for the triangles before a link)"""
@@ -929,6 +1042,56 @@ class ReconIntegrationHip:
         out = (C.c_uint64 * 4)()
         self._ck(self._L.tsdf_mesh_slab_stats(self._c, out))
         return dict(tiles=int(out[0]), tiles_skipped=int(out[1]), tiles_with_surface=int(out[2]), bytes=int(out[3]))
+
+    # ------------------------------------------------------------------ the components of a Z-slab's part (no counterpart in the reference)
+    def mesh_slab_components(self):
+        """Step 1 (tsdf_mesh_slab_components): label the linked part alone and build its seam lists -> dict(local_components, down, up, roots): the
+        local component count and the three lists' lengths"""
+        out = (C.c_uint64 * 4)()
+        self._mesh_slab_cc = None
+        self._ck(self._L.tsdf_mesh_slab_components(self._c, out))
+        self._mesh_slab_cc = dict(local_components=int(out[0]), down=int(out[1]), up=int(out[2]), roots=int(out[3]), owned=None)
+        return {k: v for k, v in self._mesh_slab_cc.items() if k != "owned"}
+
+    def _mesh_slab_cc_sizes(self):
+        if getattr(self, "_mesh_slab", None) is None or getattr(self, "_mesh_slab_cc", None) is None:   # (no sizes: nothing may be copied into a buffer of this binding's)
+            raise TsdfError(-4, "no components of the slab's part (mesh_slab_components after mesh_slab_link)")
+        return self._mesh_slab_cc
+
+    def mesh_slab_component_seam(self):
+        """dict(down, up (MESH_SEAM_VERTEX_DTYPE), roots (MESH_SEAM_ROOT_DTYPE)): the three lists of the last mesh_slab_components, global indices"""
+        n = self._mesh_slab_cc_sizes()
+        out = dict(down=np.zeros(n["down"], MESH_SEAM_VERTEX_DTYPE), up=np.zeros(n["up"], MESH_SEAM_VERTEX_DTYPE), roots=np.zeros(n["roots"], MESH_SEAM_ROOT_DTYPE))
+        self._ck(self._L.tsdf_mesh_slab_component_seam(self._c, *[out[k].ctypes.data_as(C.c_void_p) for k in ("down", "up", "roots")]))
+        return out
+
+    def mesh_slab_link_components(self, component_base, links):
+        """Step 3 (tsdf_mesh_slab_link_components): component_base and links = this slab's entries of merge_mesh_component_seams -> the components
+        whose representative this part owns (the rows of its table)"""
+        n = self._mesh_slab_cc_sizes()
+        links = np.ascontiguousarray(links, MESH_COMPONENT_LINK_DTYPE).reshape(-1)
+        owned = C.c_uint64()
+        self._ck(self._L.tsdf_mesh_slab_link_components(self._c, C.c_uint64(int(component_base)), links.ctypes.data_as(C.c_void_p) if len(links) else None,
+                                                        C.c_uint64(len(links)), C.byref(owned)))
+        n["owned"] = int(owned.value)
+        return n["owned"]
+
+    def mesh_slab_download_components(self):
+        """dict(vertex_component [the part's V] uint32, triangle_component [T] uint32 -- GLOBAL numbers --, table [owned] (MESH_COMPONENT_DTYPE, the whole
+        components' counts)): concatenated in slab order, what mesh_download_components of a whole-volume context gives"""
+        n = self._mesh_slab_cc_sizes()
+        if n["owned"] is None:
+            raise TsdfError(-4, "the part's components have no global numbers yet (mesh_slab_link_components)")
+        nv, nt = self._mesh_slab[:2]
+        out = dict(vertex_component=np.zeros(nv, np.uint32), triangle_component=np.zeros(nt, np.uint32), table=np.zeros(n["owned"], MESH_COMPONENT_DTYPE))
+        self._ck(self._L.tsdf_mesh_slab_download_components(self._c, *[out[k].ctypes.data_as(C.c_void_p) for k in ("vertex_component", "triangle_component", "table")]))
+        return out
+
+    def mesh_slab_component_stats(self):
+        """dict: local_components, owned (0 before mesh_slab_link_components), seam_records (down + up), roots_removed (local roots under a smaller final root)"""
+        out = (C.c_uint64 * 4)()
+        self._ck(self._L.tsdf_mesh_slab_component_stats(self._c, out))
+        return dict(local_components=int(out[0]), owned=int(out[1]), seam_records=int(out[2]), roots_removed=int(out[3]))
 
     # ------------------------------------------------------------------ mesh components (no counterpart in the reference)
     def mesh_components(self):

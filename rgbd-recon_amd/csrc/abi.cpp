@@ -630,8 +630,15 @@ void release_mesh_stream(tsdf_ctx* c) {
   F = MeshStreamFilter{};                                                // (raw_table lies inside raw's allocation)
   R.allocated = false; R.ring.reset(); R.device_bytes = 0;
 }
+// the components of a slab's linked part (nothing queued reads them: every entry that launches synchronises)
+void release_mesh_slab_components(tsdf_ctx* c) {
+  tsdf_ctx::MeshSlabComponents& K = c->mslabc;
+  hipFree(K.label); hipFree(K.rank); hipFree(K.local); hipFree(K.down); hipFree(K.up); hipFree(K.roots); hipFree(K.vertex); hipFree(K.triangle); hipFree(K.table);
+  K = tsdf_ctx::MeshSlabComponents{};
+}
 // a slab's part of the mesh and what its link needs (nothing queued reads them: extract, link and download synchronise)
 void release_mesh_slab(tsdf_ctx* c) {
+  release_mesh_slab_components(c);
   tsdf_ctx::MeshSlabPart& P = c->mslab;
   mesh_store_free(P); hipFree(P.above);
   mesh_scratch_free(P.scratch, P.records);
@@ -2598,6 +2605,7 @@ int32_t tsdf_mesh_slab_link(tsdf_ctx* c, uint64_t vertex_base, const uint32_t* a
       if (P.seam_cnt[k]) end = std::max(end, vertex_base + P.nv + above_seam[k] + P.seam_cnt[k]);
   if (end > 0xffffffffull || vertex_base > 0xffffffffull) FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "indices up to %llu do not fit 32 bits", (unsigned long long)end);
   HIP_TRY(c, hipSetDevice(c->device));
+  release_mesh_slab_components(c);                                       // (they hold the indices of the link that was)
   if (P.nt) {
     if (P.slab.n_seam) {
       if (!P.above) HIP_TRY(c, hipMalloc((void**)&P.above, (size_t)P.slab.n_seam * sizeof(uint32_t)));
@@ -2609,7 +2617,7 @@ int32_t tsdf_mesh_slab_link(tsdf_ctx* c, uint64_t vertex_base, const uint32_t* a
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, sync_ctx(c));                                             // (above_seam is the caller's again)
   }
-  P.linked = true;
+  P.linked = true; P.vertex_base = vertex_base; P.index_end = end;
   return TSDF_OK;
 }
 int32_t tsdf_mesh_slab_download(tsdf_ctx* c, float* position_xyz, float* normal_xyz, float* colour_rgba, uint32_t* triangles) {
@@ -2628,6 +2636,147 @@ int32_t tsdf_mesh_slab_stats(tsdf_ctx* c, uint64_t out[4]) {
   if (!out) return TSDF_ERR_INVALID_ARGUMENT;
   if (!c->mslab.valid) FAIL(c, TSDF_ERR_STATE, "no slab mesh (tsdf_mesh_slab_extract)");
   for (int k = 0; k < 4; ++k) out[k] = c->mslab.stats[k];
+  return TSDF_OK;
+}
+
+// ---- the components of a slab's linked part (k_mesh_slab_components.hip, mesh_cc_seams.hpp; the definition is in the header).  Step 1 labels the part
+// alone and exports what crosses its seams, the merge is a host function of all slabs' lists, step 3 turns the merged links into global numbers.
+namespace {
+struct DeviceTemp {                                                       // device memory of one call: freed when it returns unless handed on
+  std::vector<void*> owned;
+  ~DeviceTemp() { for (void* p : owned) hipFree(p); }
+  bool get(void* out, size_t bytes) {                                    // out: the address of a pointer of any type (no template inside extern "C")
+    void* p = nullptr;
+    if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) { (void)hipGetLastError(); return false; }
+    owned.push_back(p); *(void**)out = p;
+    return true;
+  }
+  void hand_on(const void* p) { owned.erase(std::remove(owned.begin(), owned.end(), p), owned.end()); }
+};
+}  // namespace
+int32_t tsdf_mesh_slab_components(tsdf_ctx* c, uint64_t out[4]) {
+  CHECK_CTX(c);
+  if (!out) return TSDF_ERR_INVALID_ARGUMENT;
+  const tsdf_ctx::MeshSlabPart& P = c->mslab;
+  if (!P.valid || !P.linked) FAIL(c, TSDF_ERR_STATE, "no linked slab mesh (tsdf_mesh_slab_extract, then tsdf_mesh_slab_link)");
+  if (P.nt > 0xffffffffull) FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "%llu triangles do not fit a component's 32-bit count", (unsigned long long)P.nt);
+  HIP_TRY(c, hipSetDevice(c->device));
+  tsdf_ctx::MeshSlabComponents made;
+  made.labelled = true;
+  if (P.nv) {
+    const uint32_t nv = (uint32_t)P.nv, n = (uint32_t)(P.index_end - P.vertex_base);   // (the link has checked: index_end <= 2^32)
+    const int nb_own = mesh_sc_scan_blocks(nv), nb_up = mesh_sc_scan_blocks(n - nv);
+    DeviceTemp tmp;
+    MeshSlabLabelling W{P.tri, (size_t)P.nt, nv, n, (uint32_t)P.vertex_base, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    unsigned long long* sums = nullptr;
+    bool ok = tmp.get(&W.parent, (size_t)n * 4) && tmp.get(&W.label, (size_t)n * 4) && tmp.get(&W.rank, (size_t)nv * 4) && tmp.get(&W.down_mark, (size_t)nv * 2) &&
+              tmp.get(&sums, (size_t)(3 * (nb_own + 1) + nb_up + 1) * 8);
+    if (!ok) FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "no device memory for the components of a part of %u vertices", nv);
+    W.seam_root = W.down_mark + nv;
+    W.root_sums = sums; W.down_sums = sums + (nb_own + 1); W.seam_sums = sums + 2 * (nb_own + 1); W.up_sums = sums + 3 * (nb_own + 1);
+    HIP_TRY(c, hipMemsetAsync(W.down_mark, 0, (size_t)nv * 2, c->stream));
+    timer_begin(c, "mesh_slab_components");
+    launch_mesh_sc_label(c->stream, W, P.scratch, P.records, P.slab.layer0 > 0 ? P.ntx * P.nty : 0);
+    timer_end(c, "mesh_slab_components");
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long n_local = 0, n_down = 0, n_up = 0, n_roots = 0;
+    HIP_TRY(c, hipMemcpyAsync(&n_local, W.root_sums + nb_own, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&n_down, W.down_sums + nb_own, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&n_up, W.up_sums + nb_up, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, sync_ctx(c));                                             // (the lists are sized exactly: the host has to know the counts)
+    tsdf_mesh_component* local = nullptr; tsdf_mesh_seam_vertex* down = nullptr; tsdf_mesh_seam_vertex* up = nullptr; tsdf_mesh_seam_root* roots = nullptr;
+    ok = tmp.get(&local, (size_t)n_local * sizeof(*local)) && tmp.get(&down, (size_t)n_down * sizeof(*down)) && tmp.get(&up, (size_t)n_up * sizeof(*up)) &&
+         tmp.get(&roots, (size_t)(n_down + n_up) * sizeof(*roots));      // (at most one root per seam record)
+    if (!ok) FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "no device memory for %llu local components and %llu seam records", n_local, n_down + n_up);
+    timer_begin(c, "mesh_slab_components");                              // (a second sample of the same call: the host's allocation lies between the two)
+    launch_mesh_sc_lists(c->stream, W, local, down, up, roots);
+    timer_end(c, "mesh_slab_components");
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(&n_roots, W.seam_sums + nb_own, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, sync_ctx(c));
+    made.host_roots.resize((size_t)n_roots);
+    if (n_roots) HIP_TRY(c, hipMemcpy(made.host_roots.data(), roots, (size_t)n_roots * sizeof(*roots), hipMemcpyDeviceToHost));
+    made.label = W.label; made.rank = W.rank; made.local = local; made.down = down; made.up = up; made.roots = roots;
+    for (const void* p : {(const void*)W.label, (const void*)W.rank, (const void*)local, (const void*)down, (const void*)up, (const void*)roots}) tmp.hand_on(p);
+    made.n_index = n; made.n_local = n_local; made.n_down = n_down; made.n_up = n_up;
+  }
+  release_mesh_slab_components(c);                                       // (an earlier labelling of the same link: the same words)
+  c->mslabc = std::move(made);
+  const tsdf_ctx::MeshSlabComponents& K = c->mslabc;
+  out[0] = K.n_local; out[1] = K.n_down; out[2] = K.n_up; out[3] = K.host_roots.size();
+  return TSDF_OK;
+}
+int32_t tsdf_mesh_slab_component_seam(tsdf_ctx* c, tsdf_mesh_seam_vertex* down, tsdf_mesh_seam_vertex* up, tsdf_mesh_seam_root* roots) {
+  CHECK_CTX(c);
+  const tsdf_ctx::MeshSlabComponents& K = c->mslabc;
+  if (!K.labelled) FAIL(c, TSDF_ERR_STATE, "no components of the slab's part (tsdf_mesh_slab_components after the link)");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (down && K.n_down) HIP_TRY(c, hipMemcpy(down, K.down, (size_t)K.n_down * sizeof(*down), hipMemcpyDeviceToHost));
+  if (up && K.n_up) HIP_TRY(c, hipMemcpy(up, K.up, (size_t)K.n_up * sizeof(*up), hipMemcpyDeviceToHost));
+  if (roots && !K.host_roots.empty()) std::copy(K.host_roots.begin(), K.host_roots.end(), roots);
+  return TSDF_OK;
+}
+int32_t tsdf_mesh_merge_component_seams(const tsdf_mesh_component_seams* slabs, uint32_t n_slabs, uint64_t* component_base, tsdf_mesh_component_link* links,
+                                        uint64_t* n_components) {
+  return merge_component_seams(slabs, n_slabs, component_base, links, n_components) ? TSDF_ERR_INVALID_ARGUMENT : TSDF_OK;
+}
+int32_t tsdf_mesh_slab_link_components(tsdf_ctx* c, uint64_t component_base, const tsdf_mesh_component_link* links, uint64_t n_links, uint64_t* n_owned) {
+  CHECK_CTX(c);
+  tsdf_ctx::MeshSlabComponents& K = c->mslabc;
+  const tsdf_ctx::MeshSlabPart& P = c->mslab;
+  if (!K.labelled) FAIL(c, TSDF_ERR_STATE, "no components of the slab's part (tsdf_mesh_slab_components after the link)");
+  if (n_links && !links) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "null links");
+  // before any launch: a link names its root and final root by index, and only indices this slab exported itself may reach the scatter
+  if (const int why = component_links_check(K.host_roots.data(), K.host_roots.size(), P.vertex_base, links, n_links))
+    FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "the links are not those of this slab's %zu root records (mesh_cc_seams.hpp: component_links_check = %d)", K.host_roots.size(), why);
+  if (component_base + K.n_local > 0x100000000ull) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "component numbers from %llu on do not fit 32 bits", (unsigned long long)component_base);
+  HIP_TRY(c, hipSetDevice(c->device));
+  uint64_t removed = 0;
+  for (uint64_t i = 0; i < n_links; ++i) removed += links[i].final_root != links[i].root ? 1u : 0u;
+  unsigned long long owned = 0;
+  uint32_t* vertex = nullptr; uint32_t* triangle = nullptr; tsdf_mesh_component* table = nullptr;
+  DeviceTemp tmp;
+  if (P.nv) {
+    const uint32_t nv = (uint32_t)P.nv;
+    const int nb = mesh_sc_scan_blocks(nv);
+    tsdf_mesh_component_link* d_links = nullptr; uint32_t* link_of = nullptr; uint32_t* number = nullptr; unsigned long long* sums = nullptr;
+    const bool ok = tmp.get(&d_links, (size_t)n_links * sizeof(*links)) && tmp.get(&link_of, (size_t)nv * 4) && tmp.get(&number, (size_t)nv * 4) &&
+                    tmp.get(&sums, (size_t)(nb + 1) * 8) && tmp.get(&vertex, (size_t)nv * 4) && tmp.get(&triangle, (size_t)P.nt * 4) &&
+                    tmp.get(&table, (size_t)K.n_local * sizeof(*table));
+    if (!ok) FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "no device memory to number the components of a part of %u vertices", nv);
+    if (n_links) HIP_TRY(c, hipMemcpyAsync(d_links, links, (size_t)n_links * sizeof(*links), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(link_of, 0xff, (size_t)nv * 4, c->stream));
+    const MeshSlabLabelling W{P.tri, (size_t)P.nt, nv, (uint32_t)K.n_index, (uint32_t)P.vertex_base, nullptr, K.label, K.rank, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    timer_begin(c, "mesh_slab_components_link");
+    launch_mesh_sc_link(c->stream, W, K.local, d_links, (uint32_t)n_links, (uint32_t)component_base, link_of, number, sums, vertex, triangle, table);
+    timer_end(c, "mesh_slab_components_link");
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(&owned, sums + nb, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, sync_ctx(c));                                             // (links is the caller's again)
+  }
+  hipFree(K.vertex); hipFree(K.triangle); hipFree(K.table);              // (an earlier link of the same labelling)
+  K.vertex = vertex; K.triangle = triangle; K.table = table;
+  for (const void* p : {(const void*)vertex, (const void*)triangle, (const void*)table}) tmp.hand_on(p);
+  K.n_owned = owned; K.removed = removed; K.linked = true;
+  if (n_owned) *n_owned = owned;
+  return TSDF_OK;
+}
+int32_t tsdf_mesh_slab_download_components(tsdf_ctx* c, uint32_t* vertex_component, uint32_t* triangle_component, tsdf_mesh_component* table) {
+  CHECK_CTX(c);
+  const tsdf_ctx::MeshSlabComponents& K = c->mslabc;
+  if (!K.labelled || !K.linked) FAIL(c, TSDF_ERR_STATE, "the part's components have no global numbers yet (tsdf_mesh_slab_components, tsdf_mesh_slab_link_components)");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (vertex_component && c->mslab.nv) HIP_TRY(c, hipMemcpy(vertex_component, K.vertex, (size_t)c->mslab.nv * 4, hipMemcpyDeviceToHost));
+  if (triangle_component && c->mslab.nt) HIP_TRY(c, hipMemcpy(triangle_component, K.triangle, (size_t)c->mslab.nt * 4, hipMemcpyDeviceToHost));
+  if (table && K.n_owned) HIP_TRY(c, hipMemcpy(table, K.table, (size_t)K.n_owned * sizeof(*table), hipMemcpyDeviceToHost));
+  return TSDF_OK;
+}
+int32_t tsdf_mesh_slab_component_stats(tsdf_ctx* c, uint64_t out[4]) {
+  CHECK_CTX(c);
+  if (!out) return TSDF_ERR_INVALID_ARGUMENT;
+  if (!c->mslab.valid) FAIL(c, TSDF_ERR_STATE, "no slab mesh (tsdf_mesh_slab_extract)");
+  const tsdf_ctx::MeshSlabComponents& K = c->mslabc;
+  out[0] = K.n_local; out[1] = K.n_owned; out[2] = K.n_down + K.n_up; out[3] = K.removed;
   return TSDF_OK;
 }
 

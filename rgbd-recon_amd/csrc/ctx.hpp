@@ -15,6 +15,7 @@
 #include "slab_exchange.hpp"
 #include "ray_staging.hpp"
 #include "texture_taps.hpp"
+#include "mesh_cc_seams.hpp"
 
 using namespace rr;
 
@@ -135,7 +136,17 @@ struct tsdf_ctx {
   // tiles' plane-0 vertex counts on the host (the link's index check).  All of it lives until the next slab extract, tsdf_set_voxel_size or destroy.
   struct MeshSlabPart : MeshStore { uint32_t* records = nullptr; uint32_t* above = nullptr;
                                     MeshScratch scratch{}; MeshSlab slab{}; int ntx = 0, nty = 0; std::vector<uint32_t> seam_cnt;
-                                    bool valid = false, linked = false; uint64_t stats[4] = {0, 0, 0, 0}; } mslab;
+                                    bool valid = false, linked = false; uint64_t stats[4] = {0, 0, 0, 0};
+                                    uint64_t vertex_base = 0, index_end = 0; } mslab;   // of the last link: the part's indices lie in [vertex_base, index_end)
+  // the components of a slab's linked part (tsdf_mesh_slab_components / _link_components): they hold global indices, so they live until the next slab
+  // extract OR link, tsdf_set_voxel_size or destroy.  Step 1 leaves label (the local root of every index of the part's index space, as a local index),
+  // rank and the local table (a row per local component) and the three seam lists -- the root records on the host too: step 3 checks its links
+  // against them --, step 3 the three result arrays.  Everything else a call allocates is gone when it returns.
+  struct MeshSlabComponents { uint32_t* label = nullptr; uint32_t* rank = nullptr; tsdf_mesh_component* local = nullptr;
+                              tsdf_mesh_seam_vertex* down = nullptr; tsdf_mesh_seam_vertex* up = nullptr; tsdf_mesh_seam_root* roots = nullptr;
+                              std::vector<tsdf_mesh_seam_root> host_roots;
+                              uint32_t* vertex = nullptr; uint32_t* triangle = nullptr; tsdf_mesh_component* table = nullptr;
+                              uint64_t n_index = 0, n_local = 0, n_down = 0, n_up = 0, n_owned = 0, removed = 0; bool labelled = false, linked = false; } mslabc;
   // mesh components (tsdf_mesh_components): the labels and the table of the current mesh, beside it in device memory; released with the mesh and by a
   // keep / filter (the mesh they labelled is gone then).  n / largest: components and the largest one's triangles of that labelling; removed_*: what the
   // last keep / filter of this extract took away.  Everything else a call allocates is gone when it returns.

@@ -1,4 +1,5 @@
-// The union-find and the per-component counting the mesh components (k_mesh_components.hip) and the streamed filter (k_mesh_stream_filter.hip) share.
+// The union-find and the per-component counting the mesh components (k_mesh_components.hip), the streamed filter (k_mesh_stream_filter.hip) and the
+// components of a Z-slab's part (k_mesh_slab_components.hip) share.
 // k_mesh_components.hip's head explains why the labelling is defined although the arrival order is not; this is its text, as __device__ functions.
 #ifndef RR_MESH_CC_DEV_HPP
 #define RR_MESH_CC_DEV_HPP
@@ -58,7 +59,10 @@ __device__ __forceinline__ void cc_local_hook(uint32_t* s_parent, uint32_t a, ui
 }
 // Every lane of the workgroup calls it (it holds barriers); the triangles are [first, first + kCcChunk) of tri[nt].  s_parent: kCcWindow words of LDS,
 // s_min: one word per wave.  A workgroup that takes another chunk afterwards puts a __syncthreads() between the two calls.
-__device__ __forceinline__ void cc_hook_chunk(const uint32_t* __restrict__ tri, size_t nt, uint32_t* parent, uint32_t nv, size_t first, uint32_t* s_parent, uint32_t* s_min) {
+// index_base: what the triangles' indices count from (a slab part's are global: k_mesh_slab_components.hip); the forest's index space is
+// [0, nv) behind it, and an index below the base wraps past nv and is dropped with the triangle like any other the forest does not hold.
+__device__ __forceinline__ void cc_hook_chunk(const uint32_t* __restrict__ tri, size_t nt, uint32_t* parent, uint32_t nv, size_t first, uint32_t* s_parent, uint32_t* s_min,
+                                              uint32_t index_base = 0u) {
   uint32_t v[kCcChunkPerThread][3];
   uint32_t lowest = 0xffffffffu;
 #pragma unroll
@@ -66,7 +70,7 @@ __device__ __forceinline__ void cc_hook_chunk(const uint32_t* __restrict__ tri, 
     const size_t t = first + (size_t)k * kCcThreads + threadIdx.x;
     const bool in = t < nt;
 #pragma unroll
-    for (int j = 0; j < 3; ++j) v[k][j] = in ? tri[t * 3 + j] : 0xffffffffu;
+    for (int j = 0; j < 3; ++j) v[k][j] = in ? tri[t * 3 + j] - index_base : 0xffffffffu;
     if (v[k][0] >= nv || v[k][1] >= nv || v[k][2] >= nv) v[k][0] = v[k][1] = v[k][2] = 0xffffffffu;   // past the end, or an index no extract and no keep writes
     lowest = min(lowest, min(v[k][0], min(v[k][1], v[k][2])));
   }

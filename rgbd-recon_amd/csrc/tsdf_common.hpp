@@ -460,6 +460,26 @@ void launch_mesh_cc_keep_count(hipStream_t st, const uint8_t* keep, const uint32
 void launch_mesh_cc_keep_scatter(hipStream_t st, const uint8_t* keep, const uint32_t* vertex_component, const uint32_t* triangle_component, uint32_t nv, size_t nt,
                                  const unsigned long long* vertex_sums, const unsigned long long* triangle_sums, const MeshArrays& src, const MeshArrays& dst,
                                  uint32_t* new_index);
+// mesh components of a Z-slab's linked part (k_mesh_slab_components.hip).  tri: the part's nt triangles with global indices from `base` on; nv own
+// vertices, n >= nv the index space with the span into the slab above.  parent (scratch), label: n words; rank: nv words; down_mark, seam_root: nv bytes,
+// zero on entry; each of the four sums: mesh_sc_scan_blocks(of its elements) + 1 64-bit words, the last of them the total.  The caller launches with nv > 0.
+struct MeshSlabLabelling {
+  const uint32_t* tri; size_t nt; uint32_t nv, n, base;
+  uint32_t* parent; uint32_t* label; uint32_t* rank; uint8_t* down_mark; uint8_t* seam_root;
+  unsigned long long* root_sums; unsigned long long* up_sums; unsigned long long* down_sums; unsigned long long* seam_sums;
+};
+int mesh_sc_scan_blocks(size_t n);
+// step 1, up to what sizes the lists: root_sums' total = local components, up_sums' = up records, down_sums' = down records.  first_layer_tiles: the
+// lattice tiles of the part's first owned layer (S and records: the part's scratch), 0 for a slab at the volume's bottom (no down records)
+void launch_mesh_sc_label(hipStream_t st, const MeshSlabLabelling& W, const MeshScratch& S, const uint32_t* records, int first_layer_tiles);
+// ... and the rest: local (one row per local component), down, up sized by those totals, roots by down + up; seam_sums' total = root records
+void launch_mesh_sc_lists(hipStream_t st, const MeshSlabLabelling& W, tsdf_mesh_component* local, tsdf_mesh_seam_vertex* down, tsdf_mesh_seam_vertex* up,
+                          tsdf_mesh_seam_root* roots);
+// step 3.  links: n_links records in device memory, checked by the host (mesh_cc_seams.hpp: component_links_check); link_of: nv words of 0xffffffff on
+// entry; number: nv words of scratch; sums: blocks(nv) + 1 words, its total = the components the part owns; table: a row per local component at most
+void launch_mesh_sc_link(hipStream_t st, const MeshSlabLabelling& W, const tsdf_mesh_component* local, const tsdf_mesh_component_link* links, uint32_t n_links,
+                         uint32_t component_base, uint32_t* link_of, uint32_t* number, unsigned long long* sums, uint32_t* vertex_component,
+                         uint32_t* triangle_component, tsdf_mesh_component* table);
 // ray queries (k_rays.hip): one launch pair serves at most kRayChunk rays -- the capacity of the context's hit list
 constexpr uint32_t kRayChunk = 1u << 18;
 struct RayCast {

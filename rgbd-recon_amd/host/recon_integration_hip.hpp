@@ -115,7 +115,7 @@ class ReconIntegrationHip {
   void setUseBricks(bool active) { check(tsdf_set_use_bricks(m_ctx, active)); }
   void setSpaceSkip(bool active) { check(tsdf_set_space_skip(m_ctx, active)); }
   void setDrawBricks(bool active) { check(tsdf_set_draw_bricks(m_ctx, active)); }   // drawF() then ends with drawOccupiedBricks(), recon_integration.cpp:166-168
-  void setVoxelSize(float size) { check(tsdf_set_voxel_size(m_ctx, size)); m_slab_valid = false; }      // recon_integration.cpp:340-353 (a slab part went with the old grid)
+  void setVoxelSize(float size) { check(tsdf_set_voxel_size(m_ctx, size)); m_slab_valid = m_slab_components_valid = false; }      // recon_integration.cpp:340-353 (a slab part went with the old grid)
   void setTsdfLimit(float limit) { check(tsdf_set_tsdf_limit(m_ctx, limit)); }
   void setBrickSize(float size) { const float s[3] = {size, size, size}; check(tsdf_set_brick_size(m_ctx, s)); m_brick_size = size; }
   unsigned numBricks() const { uint32_t n = 0; tsdf_num_bricks(m_ctx, &n); return n; }
@@ -201,7 +201,7 @@ class ReconIntegrationHip {
   MeshCounts extractMeshSlab(bool normals = true, bool colours = true, unsigned level = 0) {
     const std::uint32_t flags = (normals ? TSDF_MESH_NORMALS : 0u) | (colours ? TSDF_MESH_COLOURS : 0u);
     MeshCounts n;
-    m_slab_valid = false;                                                // (a refused extract leaves no part in the library either)
+    m_slab_valid = m_slab_components_valid = false;                      // (a refused extract leaves no part in the library either)
     check(tsdf_mesh_slab_extract(m_ctx, flags, level, &n.vertices, &n.triangles));
     m_slab = n; m_slab_flags = flags; m_slab_level = level; m_slab_valid = true;
     return m_slab;
@@ -217,7 +217,10 @@ class ReconIntegrationHip {
     out.assign(seamTiles(), 0u);
     check(tsdf_mesh_slab_seam(m_ctx, out.data()));
   }
-  void meshSlabLink(std::uint64_t vertex_base, const std::uint32_t* above_seam) { check(tsdf_mesh_slab_link(m_ctx, vertex_base, above_seam)); }
+  void meshSlabLink(std::uint64_t vertex_base, const std::uint32_t* above_seam) {
+    check(tsdf_mesh_slab_link(m_ctx, vertex_base, above_seam));
+    m_slab_components_valid = false;                                     // (the part's component labels held the indices of the link that was)
+  }
   void downloadMeshSlab(Mesh& out) {
     requireSlabPart();
     out.position.resize((std::size_t)m_slab.vertices * 3);
@@ -277,6 +280,62 @@ class ReconIntegrationHip {
     std::uint64_t s[4] = {0, 0, 0, 0};
     check(tsdf_mesh_component_stats(m_ctx, s));
     return MeshComponentStats{s[0], s[1], s[2], s[3]};
+  }
+  // ---- ... of a Z-slab's part (tsdf_mesh_slab_components).  The reference has no counterpart.  Per slab, after meshSlabLink: meshSlabComponents (labels
+  // the part alone; the counts of its seam lists) -> meshSlabComponentSeam (the three lists, global indices) -> once, anywhere, mergeMeshComponentSeams
+  // over all slabs' lists in slab order (a host function: no context) -> linkMeshSlabComponents(this slab's base and links) ->
+  // downloadMeshSlabComponents: concatenated in slab order, what downloadMeshComponents gives on a whole-volume context.
+  struct MeshSlabComponentCounts { std::uint64_t local_components = 0, down = 0, up = 0, roots = 0; };
+  struct MeshComponentSeams { std::vector<tsdf_mesh_seam_vertex> down, up; std::vector<tsdf_mesh_seam_root> roots; };
+  struct MeshSlabSeams { std::uint64_t vertex_base = 0, n_vertices = 0, n_local = 0; MeshComponentSeams lists; };   // one slab's input of the merge
+  struct MergedMeshComponents { std::vector<std::uint64_t> component_base; std::vector<std::vector<tsdf_mesh_component_link>> links; std::uint64_t components = 0; };
+  MeshSlabComponentCounts meshSlabComponents() {
+    std::uint64_t n[4] = {0, 0, 0, 0};
+    m_slab_components_valid = false;
+    check(tsdf_mesh_slab_components(m_ctx, n));
+    m_slab_components = MeshSlabComponentCounts{n[0], n[1], n[2], n[3]};
+    m_slab_components_valid = true; m_slab_owned_valid = false;
+    return m_slab_components;
+  }
+  void meshSlabComponentSeam(MeshComponentSeams& out) {
+    requireSlabComponents();
+    out.down.resize((std::size_t)m_slab_components.down); out.up.resize((std::size_t)m_slab_components.up); out.roots.resize((std::size_t)m_slab_components.roots);
+    check(tsdf_mesh_slab_component_seam(m_ctx, out.down.data(), out.up.data(), out.roots.data()));
+  }
+  static MergedMeshComponents mergeMeshComponentSeams(const std::vector<MeshSlabSeams>& slabs) {
+    std::vector<tsdf_mesh_component_seams> in;
+    std::size_t n_links = 0;
+    for (const MeshSlabSeams& s : slabs) {
+      in.push_back(tsdf_mesh_component_seams{s.vertex_base, s.n_vertices, s.n_local, s.lists.down.size(), s.lists.up.size(), s.lists.roots.size(),
+                                             s.lists.down.data(), s.lists.up.data(), s.lists.roots.data()});
+      n_links += s.lists.roots.size();
+    }
+    MergedMeshComponents out;
+    out.component_base.assign(slabs.size(), 0);
+    std::vector<tsdf_mesh_component_link> links(n_links + 1);
+    if (tsdf_mesh_merge_component_seams(in.data(), (std::uint32_t)in.size(), out.component_base.data(), links.data(), &out.components) != TSDF_OK)
+      throw std::invalid_argument("ReconIntegrationHip: the slabs' seam lists do not belong together (tsdf_mesh_merge_component_seams)");
+    std::size_t first = 0;
+    for (const MeshSlabSeams& s : slabs) {
+      out.links.emplace_back(links.begin() + (std::ptrdiff_t)first, links.begin() + (std::ptrdiff_t)(first + s.lists.roots.size()));
+      first += s.lists.roots.size();
+    }
+    return out;
+  }
+  std::uint64_t linkMeshSlabComponents(std::uint64_t component_base, const std::vector<tsdf_mesh_component_link>& links) {
+    requireSlabComponents();
+    std::uint64_t owned = 0;
+    check(tsdf_mesh_slab_link_components(m_ctx, component_base, links.empty() ? nullptr : links.data(), links.size(), &owned));
+    m_slab_owned = owned; m_slab_owned_valid = true;
+    return owned;
+  }
+  void downloadMeshSlabComponents(MeshComponents& out) {
+    requireSlabComponents();
+    if (!m_slab_owned_valid) throw std::runtime_error("ReconIntegrationHip: the part's components have no global numbers yet (linkMeshSlabComponents)");
+    out.vertex_component.resize((std::size_t)m_slab.vertices);
+    out.triangle_component.resize((std::size_t)m_slab.triangles);
+    out.table.resize((std::size_t)m_slab_owned);
+    check(tsdf_mesh_slab_download_components(m_ctx, out.vertex_component.data(), out.triangle_component.data(), out.table.data()));
   }
   // ---- the same surface EVERY frame (tsdf_mesh_stream): packed vertices and uint32 triangles through a ring of pinned buffers, queued behind the frame
   // like present().  The reference has no counterpart.  configureMeshStream before the first frame: attributes, capacities (vertices, triangles, 8^3
@@ -586,6 +645,10 @@ class ReconIntegrationHip {
   MeshCounts m_slab; std::uint32_t m_slab_flags = 0; unsigned m_slab_level = 0; bool m_slab_valid = false;   // of the last extractMeshSlab that succeeded
   // the sizes of seam table and arrays come from these: without them nothing is handed to the library to fill
   void requireSlabPart() const { if (!m_slab_valid) throw std::logic_error("ReconIntegrationHip: no slab mesh (extractMeshSlab)"); }
+  MeshSlabComponentCounts m_slab_components; std::uint64_t m_slab_owned = 0; bool m_slab_components_valid = false, m_slab_owned_valid = false;   // of the last meshSlabComponents / linkMeshSlabComponents
+  void requireSlabComponents() const {
+    if (!m_slab_valid || !m_slab_components_valid) throw std::logic_error("ReconIntegrationHip: no components of the slab's part (meshSlabComponents after meshSlabLink)");
+  }
   float m_mv[16], m_proj[16];
   float m_brick_size;
 };

@@ -49,7 +49,8 @@ import torch
 import torch.distributed as dist
 
 from .slab_exchange import NONE, GatherBook, SlabRoles
-from .binding import RAY_HIT_DTYPE, RAY_SURFACE_DTYPE, as_rays, join_mesh_parts, merge_ray_parts
+from .binding import (MESH_COMPONENT_DTYPE, MESH_SEAM_ROOT_DTYPE, MESH_SEAM_VERTEX_DTYPE, RAY_HIT_DTYPE, RAY_SURFACE_DTYPE, as_rays, join_mesh_parts,
+                      merge_mesh_component_seams, merge_ray_parts)
 
 
 def worker_slab_range(res_z: int, rank: int, world: int):
@@ -384,12 +385,48 @@ class SlabDriver:
             if colours:
                 part["colour"] = np.zeros((0, 4), np.float32)
         out = dict(part=part, vertex_base=base, counts=counts.copy())
+        self._mesh_counts = counts.copy()                                # (mesh_components: every part's base and size)
         parts = [part]
         if world > 1:
             parts = [None] * world if self.rank == 0 else None
             dist.gather_object(part, parts, dst=0, group=self.group)
         if self.rank == 0:
             out["mesh"] = {k: np.concatenate([p[k] for p in parts]) for k in part}
+        return out
+
+    # ------------------------------------------------------------------ ... and its components, labelled where the parts are
+    def mesh_components(self):
+        """A COLLECTIVE, after extract_mesh: every rank labels its linked part alone (tsdf_mesh_slab_components), the three seam lists are all-gathered,
+        every rank runs the same host merge (tsdf_mesh_merge_component_seams) and links its part (tsdf_mesh_slab_link_components), and the arrays are
+        gathered on rank 0.  Returns dict(part=the rank's vertex_component / triangle_component / table, component_base, n_components) and, on rank 0,
+        components=the concatenation: what mesh_components() + mesh_download_components() of a whole-volume context give for extract_mesh's mesh.
+        A dedicated compositor contributes an empty part."""
+        counts = getattr(self, "_mesh_counts", None)
+        if counts is None:
+            raise RuntimeError("mesh_components labels the parts of an extract_mesh: call that first")
+        b = self.b
+        mine = dict(vertex_base=int(counts[:self.rank, 0].sum()), n_vertices=int(counts[self.rank, 0]), n_local=0,
+                    down=np.zeros(0, MESH_SEAM_VERTEX_DTYPE), up=np.zeros(0, MESH_SEAM_VERTEX_DTYPE), roots=np.zeros(0, MESH_SEAM_ROOT_DTYPE))
+        if self.is_worker:
+            mine["n_local"] = b.mesh_slab_components()["local_components"]
+            mine.update(b.mesh_slab_component_seam())
+        slabs = [mine]
+        if self.world > 1:
+            slabs = [None] * self.world
+            dist.all_gather_object(slabs, mine, group=self.group)
+        merged = merge_mesh_component_seams(slabs, native=True)
+        if self.is_worker:
+            b.mesh_slab_link_components(merged["component_base"][self.rank], merged["links"][self.rank])
+            part = b.mesh_slab_download_components()
+        else:
+            part = dict(vertex_component=np.zeros(0, np.uint32), triangle_component=np.zeros(0, np.uint32), table=np.zeros(0, MESH_COMPONENT_DTYPE))
+        out = dict(part=part, component_base=merged["component_base"][self.rank], n_components=merged["n_components"])
+        parts = [part]
+        if self.world > 1:
+            parts = [None] * self.world if self.rank == 0 else None
+            dist.gather_object(part, parts, dst=0, group=self.group)
+        if self.rank == 0:
+            out["components"] = {k: np.concatenate([p[k] for p in parts]) for k in part}
         return out
 
     # ------------------------------------------------------------------ ... and streamed every frame: tile-local parts that join unaided
@@ -503,6 +540,27 @@ def mesh_slabs_on_one_device(backends, normals=True, colours=True, level=0):
         base += counts[k][0]
     out = {key: np.concatenate([p[key] for p in parts]) for key in parts[0]}
     out["counts"], out["seams"] = counts, seams
+    return out
+
+
+def mesh_components_on_one_device(backends, native=True):
+    """SlabDriver.mesh_components with ONE visible device, after mesh_slabs_on_one_device on the same backends: every slab labels its linked part and
+    exports its lists, the host merge runs once (native: the library's function, else its numpy twin), every slab links.  Returns the concatenated
+    vertex_component, triangle_component and table -- what mesh_components() + mesh_download_components() of a whole-volume context give -- plus
+    n_components, lists (the merge's input, per slab), merged (its output) and counts (mesh_slab_components() per slab)."""
+    counts = [b.mesh_slab_components() for b in backends]
+    lists, base = [], 0
+    for b, n in zip(backends, counts):
+        nv = b.mesh_slab_download(False, False, triangles=False)["position"].shape[0]
+        lists.append(dict(vertex_base=base, n_vertices=nv, n_local=n["local_components"], **b.mesh_slab_component_seam()))
+        base += nv
+    merged = merge_mesh_component_seams(lists, native=native)
+    parts = []
+    for k, b in enumerate(backends):
+        b.mesh_slab_link_components(merged["component_base"][k], merged["links"][k])
+        parts.append(b.mesh_slab_download_components())
+    out = {key: np.concatenate([p[key] for p in parts]) for key in parts[0]}
+    out.update(n_components=merged["n_components"], lists=lists, merged=merged, counts=counts, parts=parts)
     return out
 
 

@@ -12,7 +12,11 @@ samples: the host sizes an allocation between them) beside mesh_count / mesh_sca
 --slabs K: the same volume once more as K Z-slab contexts (recomputed halos) on this one device, each extracting its part of the first level named with
 every attribute (tsdf_mesh_slab_extract / _link): the record gets a "slabs" entry with every slab's "mesh_slab_count" / "_scan" / "_emit" / "_link"
 device time, its counts and its tiles with surface, whether the joined parts equal the whole-volume extract byte for byte, and the slowest slab's time
-and share of the surface tiles beside the whole-volume extract's device time of this run."""
+and share of the surface tiles beside the whole-volume extract's device time of this run.
+--slabs K --components: the linked parts are labelled where they are (tsdf_mesh_slab_components, the host merge merge_mesh_component_seams through the
+library, tsdf_mesh_slab_link_components): "slabs" gets a "components" entry with every slab's "mesh_slab_components" / "mesh_slab_components_link" device
+time, its list sizes and their bytes, the host merge's wall time (and the numpy twin's, once), whether the joined labels equal the whole-volume
+context's byte for byte, and the slowest slab beside "mesh_components" of the whole volume in this run."""
 import sys, os, json, time
 from importlib import import_module
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -143,6 +147,52 @@ if SLABS:
     rec["slabs"] = dict(n=SLABS, level=L0, identical_to_whole_volume=bool(identical), per_slab=per, slowest_slab_ms=slow["device_ms"],
                         slowest_slab_surface_share=slow["tiles_with_surface"] / max(surface, 1), sum_of_slabs_ms=sum(r["device_ms"] for r in per),
                         whole_volume_device_ms=levels[L0]["all_attributes"]["device_ms"])
+    if COMPONENTS:                                                       # the parts are linked: label them where they are
+        CC = ("mesh_slab_components", "mesh_slab_components_link")
+        for c in ctxs:
+            c.set_timer_filter(list(SLAB_STAGES) + list(CC))
+        hip.extract_mesh(level=L0, normals=True, colours=True)
+        hip.mesh_components()
+        want = hip.mesh_download_components()
+        got = mgpu.mesh_components_on_one_device(ctxs)                   # (also the warm-up)
+        same = all(got[k].tobytes() == want[k].tobytes() for k in ("vertex_component", "triangle_component", "table"))
+        for c in ctxs:
+            for s in CC:
+                c.timer_stats(s)
+        cms = [{s: [] for s in CC} for _ in ctxs]
+        merge_ms = []
+        for _ in range(N):
+            lists, base = [], 0
+            for k, c in enumerate(ctxs):
+                n = c.mesh_slab_components()
+                lists.append(dict(vertex_base=base, n_vertices=counts[k][0], n_local=n["local_components"], **c.mesh_slab_component_seam()))
+                base += counts[k][0]
+            t0 = time.perf_counter()
+            merged = rr.merge_mesh_component_seams(lists, native=True)   # the library's host function
+            merge_ms.append((time.perf_counter() - t0) * 1e3)
+            for k, c in enumerate(ctxs):
+                c.mesh_slab_link_components(merged["component_base"][k], merged["links"][k])
+                for s in CC:
+                    cnt, total = c.timer_stats(s)                        # (step 1 is two samples: the host sizes the lists between them)
+                    cms[k][s].append(total)
+        t0 = time.perf_counter()
+        twin = rr.merge_mesh_component_seams(lists)
+        twin_ms = (time.perf_counter() - t0) * 1e3
+        cper = []
+        for k, c in enumerate(ctxs):
+            st = c.mesh_slab_component_stats()
+            r = {s + "_ms": float(np.mean(cms[k][s])) for s in CC}
+            r["device_ms"] = sum(r.values())
+            r.update(st, down_records=len(lists[k]["down"]), up_records=len(lists[k]["up"]), root_records=len(lists[k]["roots"]),
+                     seam_bytes=8 * (len(lists[k]["down"]) + len(lists[k]["up"])) + 16 * len(lists[k]["roots"]), link_bytes=32 * len(lists[k]["roots"]))
+            cper.append(r)
+        cslow = max(cper, key=lambda r: r["device_ms"])
+        rec["slabs"]["components"] = dict(
+            identical_to_whole_volume=bool(same), components=got["n_components"], per_slab=cper, slowest_slab_ms=cslow["device_ms"],
+            sum_of_slabs_ms=sum(r["device_ms"] for r in cper), host_merge_ms=float(np.mean(merge_ms)), host_merge_ms_min=float(np.min(merge_ms)),
+            host_merge_ms_max=float(np.max(merge_ms)), numpy_twin_merge_ms=twin_ms,
+            numpy_twin_identical=all(a.tobytes() == b.tobytes() for a, b in zip(twin["links"], merged["links"])),
+            whole_volume_mesh_components_ms=rec["components"]["mesh_components_ms"])
     for c in ctxs:
         c.close()
 print(json.dumps(rec), flush=True)
