@@ -941,7 +941,8 @@ int32_t tsdf_texture_tap_stats(tsdf_ctx* ctx, uint64_t out[4]);
  *   the current mesh.  TSDF_ERR_INVALID_ARGUMENT for a NULL keep or a NULL out.  -1 for a NULL context.
  * The streamed ring (tsdf_mesh_stream) filters by the same rule inside the frame: "mesh streaming: the filtered frame" below.
  * Out of scope.  Z-slab contexts keep answering TSDF_ERR_STATE here: tsdf_mesh_slab_extract's parts are labelled where they are by "mesh components
- *   on Z-slab contexts" below, and the joined labels are these.  Welding by position.  Geometric measures per component (area, volume, bounding box): the caller has the arrays.
+ *   on Z-slab contexts" below, and the joined labels are these.  Welding by position.  Geometric measures per component (area, volume, bounding box) are not
+ *   these entries' business: "mesh component measures" further down computes them beside the labels and filters by them.
  *   A context that never calls these entries runs exactly what it ran before they existed. */
 typedef struct tsdf_mesh_component { uint32_t first_vertex, n_vertices, n_triangles, reserved /* 0 */; } tsdf_mesh_component;
 int32_t tsdf_mesh_components(tsdf_ctx* ctx, uint64_t* n_components);
@@ -1217,6 +1218,66 @@ typedef struct tsdf_mesh_taps { const tsdf_packed_tap* taps; uint64_t n_vertices
 int32_t tsdf_mesh_stream_config_taps(tsdf_ctx* ctx, uint32_t tap_flags);
 int32_t tsdf_mesh_stream_tap_flags(tsdf_ctx* ctx, uint32_t* tap_flags);
 int32_t tsdf_mesh_stream_frame_taps(tsdf_ctx* ctx, tsdf_mesh_taps* out);   /* of the frame currently HELD */
+
+/* ---- mesh component measures: exact area, volume and bounds per island --------------------------------------
+ * "Mesh components" above knows an island by its counts alone, and a triangle count changes meaning with the resolution.  These entries give every
+ * component of the labelled mesh its surface area, its signed volume, its bounds and its vertex centroid, on the device, and filter by them: "drop
+ * everything smaller than 5 cm", "drop closed voids inside the subject".  Float sums by atomics would differ from run to run, so the measures are
+ * DEFINED on an integer grid and summed in integers: exact, independent of the order, two runs give identical bytes.  No counterpart in the reference.
+ * tests/mesh_measure_reference.py restates the definition in numpy and Python integers; device and numpy agree byte for byte.
+ *
+ * The measures belong to the labelled mesh of the last tsdf_mesh_components: any level, and also the mesh a keep / filter left once it has been
+ *   labelled again.
+ * Measure grid.  ext = bbox_max - bbox_min in fp32, as vol_to_world forms it; E = max(ext.x, ext.y, ext.z); scale = 1048576.0 / (double) E, one IEEE
+ *   double division done on the host; unit = 1.0 / scale.  The grid is isotropic: one unit is the same length on every axis (areas and volumes mean
+ *   nothing otherwise), 2^20 units along the longest edge of the box.
+ * Grid coordinate of a vertex, per axis a: d = (double) position[a] - (double) bbox_min[a]; q = rint(d * scale), half-way cases to even, clamped to
+ *   [0, 1048576]; NaN gives 0 (no extract produces one; the definition covers it).  Three double operations, each correctly rounded, none contracted
+ *   into an fma.  q needs 21 bits; the three coordinates pack into one uint64 as qx | qy << 21 | qz << 42.
+ * Per triangle (i0, i1, i2), in exact integer arithmetic: e1 = q1 - q0, e2 = q2 - q0; c = e1 x e2 (each component below 2^43); n2 = c . c (below 2^88);
+ *   a2 = floor(sqrt(n2)), the doubled area in unit^2, rounded down; v6 = det(q0, q1, q2), six times the signed volume of the tetrahedron from the grid
+ *   origin (bbox_min) in unit^3, |v6| < 2^63.  A triangle with an index that is not a vertex (no extract and no keep writes one) has a2 = v6 = 0.
+ * Per component one row, tsdf_mesh_component_measure, 80 bytes, little endian:
+ *   q_min[3], q_max[3]       uint32         bounds of the component's vertices' grid coordinates
+ *   area2                    uint64         sum of a2 over the component's triangles
+ *   volume6_lo, volume6_hi   uint64, int64  sum of v6 as one two's-complement 128-bit integer
+ *   sum_q[3]                 uint64         sum of q over the component's vertices: the vertex centroid is sum_q / n_vertices
+ *   reserved                 uint64         0
+ *   A component without triangles has area2 = 0 and volume6 = 0.
+ * Winding.  The normals point into empty space: a closed surface round solid matter has volume6 > 0, a closed void inside matter volume6 < 0.  For an
+ *   OPEN component volume6 depends on the origin: it is the volume of the cone from bbox_min over the surface, not a property of the surface alone.
+ * Conversion, tsdf_mesh_measure_grid {unit, origin = bbox_min, bits = 20}: area = area2 * unit^2 / 2; volume = volume6 * unit^3 / 6; world position
+ *   = origin + q * unit.
+ * Why 20 bits.  A unit is E / 2^20, about 2.1 um for the 2.2 m box: coarser than an fp32 ulp of the positions there, and 2 000 units per voxel at 512^3.
+ *   Rounding each triangle's doubled area down to a whole unit^2 costs below 1e-6 of its area there, and v6 still fits one signed 64-bit word.
+ *
+ * tsdf_mesh_component_measures computes the rows on the context's stream (a fill of the rows and three launches: vertices, triangles, finish; no host
+ *   wait between them), synchronises like tsdf_mesh_components and fills *grid (may be NULL).  Timer "mesh_component_measures": fill and launches.  The rows and a scratch of 8 bytes per
+ *   vertex (the packed coordinates) live beside the labels and die with them: next extract, keep / filter, a new tsdf_mesh_components,
+ *   tsdf_set_voxel_size, destroy.  It may be called again.  It allocates before it replaces anything: TSDF_ERR_OUT_OF_MEMORY leaves the state as it was.
+ *   Mesh, labels and table are untouched.
+ * tsdf_mesh_download_component_measures copies the C rows.
+ * tsdf_mesh_measure_grid_info fills *grid without a mesh: the grid is a property of the box.
+ * tsdf_mesh_filter_components_measured: a component stays iff every clause of the rule holds: n_triangles >= min_triangles; max over the axes of
+ *   (q_max[a] - q_min[a]) >= min_extent; area2 >= min_area2; |volume6| >= min_abs_volume6; with TSDF_MESH_RULE_POSITIVE_VOLUME, volume6 > 0.  The
+ *   thresholds are grid integers, so the decision is exact, and it is taken on the device.  The rebuilt mesh is what tsdf_mesh_keep_components gives for
+ *   those flags: the same scans and scatter, the same lifetime rules and stats, the timer "mesh_filter".  An all-zero rule keeps everything.
+ * Errors.  TSDF_ERR_STATE without labels of the current mesh (so always on a Z-slab context), and for download / filter without measures of them;
+ *   TSDF_ERR_INVALID_ARGUMENT for NULL rows, a NULL rule or a NULL grid of _grid_info, for rule.reserved != 0 and for an unknown flag.  -1 for a NULL context.
+ * Unchanged.  tsdf_mesh_component_stats keeps its four words.  A context that never calls these entries runs exactly what it ran before they existed.
+ * Out of scope.  Z-slab parts: a part's triangles index vertices of the slab above, whose positions it does not hold; the sums are additive, so a
+ *   later change can export per-slab partial rows and add them through the existing links.  A measure rule inside the streamed filter ring: it keeps
+ *   one triangle count per vertex, not a table.  Area-weighted centroids and inertia.  Welding. */
+#define TSDF_MESH_RULE_POSITIVE_VOLUME 1u
+typedef struct tsdf_mesh_component_measure {
+  uint32_t q_min[3], q_max[3]; uint64_t area2; uint64_t volume6_lo; int64_t volume6_hi; uint64_t sum_q[3]; uint64_t reserved /* 0 */;
+} tsdf_mesh_component_measure;                                              /* 80 bytes */
+typedef struct tsdf_mesh_measure_grid { double unit; float origin[3]; uint32_t bits /* 20 */; } tsdf_mesh_measure_grid;   /* 24 bytes */
+typedef struct tsdf_mesh_measure_rule { uint32_t min_triangles, min_extent; uint64_t min_area2, min_abs_volume6; uint32_t flags, reserved /* 0 */; } tsdf_mesh_measure_rule;   /* 32 bytes */
+int32_t tsdf_mesh_component_measures(tsdf_ctx* ctx, tsdf_mesh_measure_grid* grid /* may be NULL */);
+int32_t tsdf_mesh_download_component_measures(tsdf_ctx* ctx, tsdf_mesh_component_measure* rows /* [C] */);
+int32_t tsdf_mesh_measure_grid_info(tsdf_ctx* ctx, tsdf_mesh_measure_grid* grid);   /* needs no mesh */
+int32_t tsdf_mesh_filter_components_measured(tsdf_ctx* ctx, const tsdf_mesh_measure_rule* rule, uint64_t* n_vertices, uint64_t* n_triangles);
 
 /* ---- frame read-out: the swap ------------------------------------------------------------------------
  * The client ends a frame with glfwSwapBuffers (source/kinect_client.cpp:533): an RGBA8 window goes to a display (GLFW's default framebuffer has 8

@@ -13,7 +13,7 @@ from .binding import (LANES_NO_FILL_THREAD, LANES_NO_INTEGRATE_LANE, LANES_ONE_S
                       load_library, LIB_PATH, HEADER_PATH, read_calib_volume, write_calib_volume,
                       read_stream_record, stream_num_frames, frustum_from_volume, view_matrices, inverse_volume_resolution, invert_calibration, COLOR_RGB8, COLOR_DXT1, COLOR_DXT5, DEPTH_F32, DEPTH_U8,
                       PRESENT_RGBA8, PRESENT_DXT1, PRESENT_TOP_DOWN, MESH_NORMALS, MESH_COLOURS, MESH_OVERFLOW_VERTICES, MESH_OVERFLOW_TRIANGLES, MESH_OVERFLOW_TILES,
-                      MeshFrame, unpack_mesh_vertices, MESH_INDEX_U32, MESH_INDEX_TILE16, MESH_TILE_ROW_DTYPE, MeshCompact, unpack_mesh_triangles, MeshPart, join_mesh_parts, MESH_COMPONENT_DTYPE, RAYS_UNIT_CUBE, RAY_NORMALS, RAY_COLOURS, RAY_HIT, RAY_OUTSIDE, RAY_INVALID, Ray, RayHit, RaySurface,
+                      MeshFrame, unpack_mesh_vertices, MESH_INDEX_U32, MESH_INDEX_TILE16, MESH_TILE_ROW_DTYPE, MeshCompact, unpack_mesh_triangles, MeshPart, join_mesh_parts, MESH_COMPONENT_DTYPE, MESH_COMPONENT_MEASURE_DTYPE, MESH_MEASURE_GRID_DTYPE, MESH_MEASURE_RULE_DTYPE, MESH_RULE_POSITIVE_VOLUME, mesh_measures_si, mesh_measure_rule_for, mesh_volume6, RAYS_UNIT_CUBE, RAY_NORMALS, RAY_COLOURS, RAY_HIT, RAY_OUTSIDE, RAY_INVALID, Ray, RayHit, RaySurface,
                       RAY_DTYPE, RAY_HIT_DTYPE, RAY_SURFACE_DTYPE, as_rays, make_rays, merge_ray_parts,
                       TAPS_UNIT_CUBE, TAPS_SENSOR, TextureTap, SensorTap, TEXTURE_TAP_DTYPE, SENSOR_TAP_DTYPE, blend_from_taps,
                       MESH_STREAM_TAPS, PackedTap, MeshTaps, PACKED_TAP_DTYPE, unpack_mesh_taps,

@@ -8,6 +8,7 @@ There is NO CPU fallback: if the HIP library is missing or no device is visible 
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import re
 import subprocess
@@ -181,6 +182,48 @@ MESH_NORMALS, MESH_COLOURS = 1, 2     # tsdf_mesh_extract: flags
 MESH_OVERFLOW_VERTICES, MESH_OVERFLOW_TRIANGLES, MESH_OVERFLOW_TILES = 1, 2, 4   # tsdf_mesh_frame: overflow bits
 # tsdf_mesh_component as a numpy dtype: what mesh_download_components returns as its table
 MESH_COMPONENT_DTYPE = np.dtype([("first_vertex", "<u4"), ("n_vertices", "<u4"), ("n_triangles", "<u4"), ("reserved", "<u4")])
+# tsdf_mesh_component_measure (80 bytes), tsdf_mesh_measure_grid (24) and tsdf_mesh_measure_rule (32) as numpy dtypes
+MESH_COMPONENT_MEASURE_DTYPE = np.dtype([("q_min", "<u4", (3,)), ("q_max", "<u4", (3,)), ("area2", "<u8"), ("volume6_lo", "<u8"), ("volume6_hi", "<i8"),
+                                         ("sum_q", "<u8", (3,)), ("reserved", "<u8")])
+MESH_MEASURE_GRID_DTYPE = np.dtype([("unit", "<f8"), ("origin", "<f4", (3,)), ("bits", "<u4")])
+MESH_MEASURE_RULE_DTYPE = np.dtype([("min_triangles", "<u4"), ("min_extent", "<u4"), ("min_area2", "<u8"), ("min_abs_volume6", "<u8"), ("flags", "<u4"),
+                                    ("reserved", "<u4")])
+MESH_RULE_POSITIVE_VOLUME = 1
+
+
+def mesh_volume6(rows):
+    """the components' six-fold signed volumes in unit^3 as Python integers (volume6_hi * 2^64 + volume6_lo)"""
+    return [int(hi) * (1 << 64) + int(lo) for lo, hi in zip(rows["volume6_lo"].tolist(), rows["volume6_hi"].tolist())]
+
+
+def mesh_measure_rule_for(unit, min_triangles=0, min_extent_m=0.0, min_area_m2=0.0, min_volume_m3=0.0, positive_volume=False):
+    """A keep rule for tsdf_mesh_filter_components_measured (one MESH_MEASURE_RULE_DTYPE record) on a grid of `unit` metres: metres converted to grid
+    integers with a ceiling -- min_extent = ceil(m / unit), min_area2 = ceil(2 m2 / unit^2), min_abs_volume6 = ceil(6 m3 / unit^3) -- so a component
+    that passes is at least that large.  ValueError for a negative or NaN threshold and for one the rule's field cannot hold (with a unit of 2.1 um:
+    an extent above 9 km, a volume above 28 m^3)."""
+    u = float(unit)
+    rule = np.zeros((), MESH_MEASURE_RULE_DTYPE)
+    for field, name, value in (("min_triangles", "min_triangles", float(min_triangles)), ("min_extent", "min_extent_m", float(min_extent_m) / u),
+                               ("min_area2", "min_area_m2", 2.0 * float(min_area_m2) / (u * u)), ("min_abs_volume6", "min_volume_m3", 6.0 * float(min_volume_m3) / (u * u * u))):
+        top = int(np.iinfo(MESH_MEASURE_RULE_DTYPE[field]).max)
+        if not 0.0 <= value <= float(top):                                # (NaN too)
+            raise ValueError(f"{name} gives {value:g} grid units: outside 0 .. {top}, what the rule's {field} holds")
+        rule[field] = min(int(math.ceil(value)), top)
+    rule["flags"] = MESH_RULE_POSITIVE_VOLUME if positive_volume else 0
+    return rule
+
+
+def mesh_measures_si(rows, grid, table=None):
+    """The measure rows in world units, float64: dict(area [C] = area2 * unit^2 / 2, volume [C] = volume6 * unit^3 / 6 (signed: a closed void is
+    negative), bounds_min / bounds_max [C, 3] = origin + q * unit, centroid [C, 3] = origin + sum_q / n_vertices * unit -- the vertex centroid, with the
+    components' table (mesh_download_components()["table"]); without it the entry is absent).  grid: what mesh_component_measures() returned."""
+    u = float(grid["unit"])
+    origin = np.asarray(grid["origin"], np.float64)
+    out = dict(area=rows["area2"].astype(np.float64) * (u * u / 2.0), volume=np.array([v * (u ** 3 / 6.0) for v in mesh_volume6(rows)], np.float64),
+               bounds_min=origin + rows["q_min"].astype(np.float64) * u, bounds_max=origin + rows["q_max"].astype(np.float64) * u)
+    if table is not None:
+        out["centroid"] = origin + rows["sum_q"].astype(np.float64) / np.maximum(table["n_vertices"], 1)[:, None].astype(np.float64) * u
+    return out
 
 
 class MeshFrame(C.Structure):
@@ -1141,6 +1184,39 @@ class ReconIntegrationHip:
         out = (C.c_uint64 * 4)()
         self._ck(self._L.tsdf_mesh_component_stats(self._c, out))
         return dict(components=int(out[0]), largest_triangles=int(out[1]), vertices_removed=int(out[2]), triangles_removed=int(out[3]))
+
+    # ------------------------------------------------------------------ mesh component measures (no counterpart in the reference)
+    def _measure_grid(self, g):
+        return dict(unit=float(g["unit"][0]), origin=g["origin"][0].copy(), bits=int(g["bits"][0]))
+
+    def mesh_measure_grid(self):
+        """dict(unit, origin [3] float32, bits): the measure grid of this context's box (tsdf_mesh_measure_grid_info; needs no mesh)"""
+        g = np.zeros(1, MESH_MEASURE_GRID_DTYPE)
+        self._ck(self._L.tsdf_mesh_measure_grid_info(self._c, g.ctypes.data_as(C.c_void_p)))
+        return self._measure_grid(g)
+
+    def mesh_component_measures(self):
+        """Measure every component of the labelled mesh on the device (tsdf_mesh_component_measures: exact integer area, volume, bounds and vertex
+        sum on the measure grid) -> the grid, as mesh_measure_grid()"""
+        g = np.zeros(1, MESH_MEASURE_GRID_DTYPE)
+        self._ck(self._L.tsdf_mesh_component_measures(self._c, g.ctypes.data_as(C.c_void_p)))
+        return self._measure_grid(g)
+
+    def mesh_download_component_measures(self):
+        """[C] rows of MESH_COMPONENT_MEASURE_DTYPE of the last mesh_component_measures (mesh_measures_si converts them)"""
+        rows = np.zeros(max(self.mesh_component_stats()["components"], 1), MESH_COMPONENT_MEASURE_DTYPE)
+        self._ck(self._L.tsdf_mesh_download_component_measures(self._c, rows.ctypes.data_as(C.c_void_p)))
+        return rows[:self.mesh_component_stats()["components"]]
+
+    def mesh_measure_rule(self, min_triangles=0, min_extent_m=0.0, min_area_m2=0.0, min_volume_m3=0.0, positive_volume=False):
+        """A keep rule for mesh_filter_measured on this context's measure grid: mesh_measure_rule_for(unit, ...)"""
+        return mesh_measure_rule_for(self.mesh_measure_grid()["unit"], min_triangles, min_extent_m, min_area_m2, min_volume_m3, positive_volume)
+
+    def mesh_filter_measured(self, rule):
+        """mesh_keep of the components for which every clause of the rule holds, decided on the device from the measures
+        (tsdf_mesh_filter_components_measured; rule: mesh_measure_rule(...)) -> (vertices, triangles) left"""
+        r = np.ascontiguousarray(np.asarray(rule, MESH_MEASURE_RULE_DTYPE).reshape(1))
+        return self._mesh_kept(lambda nv, nt: self._L.tsdf_mesh_filter_components_measured(self._c, r.ctypes.data_as(C.c_void_p), nv, nt))
 
     # ------------------------------------------------------------------ mesh streaming (no counterpart in the reference)
     def mesh_stream_config(self, normals=False, colours=False, max_vertices=1 << 20, max_triangles=1 << 21, max_surface_tiles=1 << 14, slots=3, level=0,

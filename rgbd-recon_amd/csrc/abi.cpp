@@ -19,6 +19,7 @@
 
 #include "tsdf_common.hpp"
 #include "grid_plan.hpp"
+#include "mesh_measure.hpp"
 
 using namespace rr;
 
@@ -562,8 +563,9 @@ void release_mesh_texture_taps(tsdf_ctx* c) {
 // the labels and the table of a mesh (nothing queued reads them: tsdf_mesh_components, keep and filter synchronise); what a keep / filter removed stays on record
 void release_mesh_components(tsdf_ctx* c) {
   tsdf_ctx::MeshComponents& K = c->mcomp;
-  hipFree(K.vertex); hipFree(K.triangle); hipFree(K.table);
+  hipFree(K.vertex); hipFree(K.triangle); hipFree(K.table); hipFree(K.measure); hipFree(K.packed);
   K.vertex = nullptr; K.triangle = nullptr; K.table = nullptr; K.n = 0; K.largest = 0; K.valid = false;
+  K.measure = nullptr; K.packed = nullptr; K.measured = false;
 }
 // The four arrays of a mesh (tsdf_ctx::MeshStore), for the whole mesh, a slab's part and a filtered mesh in the making.  Allocate: the arrays that `flags`
 // names for nv vertices and nt triangles, each at least one element long (a part may own triangles and no vertex); false: out of memory, what was
@@ -2785,8 +2787,9 @@ namespace {
 struct ComponentTemp {                                                    // what one call allocates besides what it leaves in the context: freed when it returns
   uint32_t* words = nullptr; unsigned long long* vsums = nullptr; unsigned long long* tsums = nullptr; uint32_t* largest = nullptr; uint8_t* keep = nullptr;
   tsdf_ctx::MeshComponents made{}; MeshArrays mesh{};                     // arrays not handed to the context yet
+  tsdf_mesh_component_measure* rows = nullptr; unsigned long long* packed = nullptr;   // ... and measures not handed over yet
   ~ComponentTemp() {
-    hipFree(words); hipFree(vsums); hipFree(tsums); hipFree(largest); hipFree(keep);
+    hipFree(words); hipFree(vsums); hipFree(tsums); hipFree(largest); hipFree(keep); hipFree(rows); hipFree(packed);
     hipFree(made.vertex); hipFree(made.triangle); hipFree(made.table);
     mesh_store_free(mesh);
   }
@@ -2849,10 +2852,12 @@ int32_t tsdf_mesh_download_components(tsdf_ctx* c, uint32_t* vertex_component, u
   if (table && K.n) HIP_TRY(c, hipMemcpy(table, K.table, (size_t)K.n * sizeof(tsdf_mesh_component), hipMemcpyDeviceToHost));
   return TSDF_OK;
 }
-// keep_host: C bytes, or null = derive the flags from the table (n_triangles >= min_triangles) on the device
-static int32_t mesh_keep(tsdf_ctx* c, const uint8_t* keep_host, uint32_t min_triangles, uint64_t* n_vertices, uint64_t* n_triangles) {
+// keep_host: C bytes, or null = derive the flags on the device: from the table (n_triangles >= min_triangles), with a rule from the measures
+static int32_t mesh_keep(tsdf_ctx* c, const uint8_t* keep_host, uint32_t min_triangles, uint64_t* n_vertices, uint64_t* n_triangles,
+                         const tsdf_mesh_measure_rule* rule = nullptr) {
   int32_t rc = mesh_components_check(c);
   if (rc) return rc;
+  if (rule && !c->mcomp.measured) FAIL(c, TSDF_ERR_STATE, "no measures of the current mesh's components (tsdf_mesh_component_measures after tsdf_mesh_components)");
   HIP_TRY(c, hipSetDevice(c->device));
   tsdf_ctx::Mesh& M = c->mesh;
   tsdf_ctx::MeshComponents& K = c->mcomp;
@@ -2866,7 +2871,8 @@ static int32_t mesh_keep(tsdf_ctx* c, const uint8_t* keep_host, uint32_t min_tri
   unsigned long long kept_v = 0, kept_t = 0;
   if (keep_host && nc) HIP_TRY(c, hipMemcpyAsync(tmp.keep, keep_host, nc, hipMemcpyHostToDevice, c->stream));
   timer_begin(c, "mesh_filter");
-  if (!keep_host) launch_mesh_cc_keep_from_table(c->stream, K.table, nc, min_triangles, tmp.keep);
+  if (rule) launch_mesh_measure_keep(c->stream, K.measure, K.table, nc, *rule, tmp.keep);
+  else if (!keep_host) launch_mesh_cc_keep_from_table(c->stream, K.table, nc, min_triangles, tmp.keep);
   launch_mesh_cc_keep_count(c->stream, tmp.keep, K.vertex, K.triangle, nv, nt, tmp.vsums, tmp.tsums);
   timer_end(c, "mesh_filter");
   HIP_TRY(c, hipGetLastError());
@@ -2903,6 +2909,66 @@ int32_t tsdf_mesh_keep_components(tsdf_ctx* c, const uint8_t* keep, uint64_t* n_
 int32_t tsdf_mesh_filter_components(tsdf_ctx* c, uint32_t min_triangles, uint64_t* n_vertices, uint64_t* n_triangles) {
   CHECK_CTX(c);
   return mesh_keep(c, nullptr, min_triangles, n_vertices, n_triangles);
+}
+// ---- mesh component measures (k_mesh_component_measures.hip, mesh_measure.hpp; the definition is in the header)
+static int32_t mesh_measure_grid(tsdf_ctx* c, MeasureScale* S, tsdf_mesh_measure_grid* grid) {
+  if (!measure_scale(c->cfg.bbox_min, c->cfg.bbox_max, S)) FAIL(c, TSDF_ERR_STATE, "the box has no positive finite extent: no measure grid");
+  if (grid) *grid = tsdf_mesh_measure_grid{S->unit, {S->bbox_min[0], S->bbox_min[1], S->bbox_min[2]}, kMeasureBits};
+  return TSDF_OK;
+}
+int32_t tsdf_mesh_measure_grid_info(tsdf_ctx* c, tsdf_mesh_measure_grid* grid) {
+  CHECK_CTX(c);
+  if (!grid) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "null grid");
+  MeasureScale S;
+  return mesh_measure_grid(c, &S, grid);
+}
+int32_t tsdf_mesh_component_measures(tsdf_ctx* c, tsdf_mesh_measure_grid* grid) {
+  CHECK_CTX(c);
+  int32_t rc = mesh_components_check(c);
+  if (rc) return rc;
+  MeasureScale S;
+  if ((rc = mesh_measure_grid(c, &S, nullptr))) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const tsdf_ctx::Mesh& M = c->mesh;
+  tsdf_ctx::MeshComponents& K = c->mcomp;
+  const uint32_t nv = (uint32_t)M.nv, nc = (uint32_t)K.n;
+  ComponentTemp tmp;                                                       // everything new is allocated before anything is replaced
+  if (!device_alloc((void**)&tmp.rows, (size_t)nc * sizeof(tsdf_mesh_component_measure)) || !device_alloc((void**)&tmp.packed, (size_t)nv * 8)) {
+    (void)hipGetLastError();
+    FAIL(c, TSDF_ERR_OUT_OF_MEMORY, "no device memory for the measures of %u components and %u vertices", nc, nv);
+  }
+  if (nc) {                                                                // (the empty mesh has no component: nothing to launch)
+    timer_begin(c, "mesh_component_measures");                             // (the fill is part of the scheme: zero is every field's identity)
+    const hipError_t filled = hipMemsetAsync(tmp.rows, 0, (size_t)nc * sizeof(tsdf_mesh_component_measure), c->stream);
+    if (filled != hipSuccess) { timer_end(c, "mesh_component_measures"); HIP_TRY(c, filled); }
+    launch_mesh_measures(c->stream, MeshMeasureGeometry{{S.bbox_min[0], S.bbox_min[1], S.bbox_min[2]}, S.scale}, M.pos, M.tri, nv, (size_t)M.nt, K.vertex, K.triangle, nc,
+                         tmp.packed, tmp.rows);
+    timer_end(c, "mesh_component_measures");
+    HIP_TRY(c, hipGetLastError());
+  }
+  HIP_TRY(c, sync_ctx(c));
+  hipFree(K.measure); hipFree(K.packed);                                   // (an earlier call's: the same words)
+  K.measure = tmp.rows; K.packed = tmp.packed; K.measured = true;
+  tmp.rows = nullptr; tmp.packed = nullptr;
+  return mesh_measure_grid(c, &S, grid);
+}
+int32_t tsdf_mesh_download_component_measures(tsdf_ctx* c, tsdf_mesh_component_measure* rows) {
+  CHECK_CTX(c);
+  if (!rows) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "null rows");
+  int32_t rc = mesh_components_check(c);
+  if (rc) return rc;
+  const tsdf_ctx::MeshComponents& K = c->mcomp;
+  if (!K.measured) FAIL(c, TSDF_ERR_STATE, "no measures of the current mesh's components (tsdf_mesh_component_measures after tsdf_mesh_components)");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (K.n) HIP_TRY(c, hipMemcpy(rows, K.measure, (size_t)K.n * sizeof(tsdf_mesh_component_measure), hipMemcpyDeviceToHost));
+  return TSDF_OK;
+}
+int32_t tsdf_mesh_filter_components_measured(tsdf_ctx* c, const tsdf_mesh_measure_rule* rule, uint64_t* n_vertices, uint64_t* n_triangles) {
+  CHECK_CTX(c);
+  if (!rule) FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "null rule");
+  if (rule->reserved != 0u || (rule->flags & ~TSDF_MESH_RULE_POSITIVE_VOLUME))
+    FAIL(c, TSDF_ERR_INVALID_ARGUMENT, "rule.reserved = %u and flags = 0x%x: reserved has to be 0, the one flag is TSDF_MESH_RULE_POSITIVE_VOLUME", rule->reserved, rule->flags);
+  return mesh_keep(c, nullptr, 0u, n_vertices, n_triangles, rule);
 }
 int32_t tsdf_mesh_component_stats(tsdf_ctx* c, uint64_t out[4]) {
   CHECK_CTX(c);

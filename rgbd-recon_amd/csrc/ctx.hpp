@@ -150,8 +150,10 @@ struct tsdf_ctx {
   // mesh components (tsdf_mesh_components): the labels and the table of the current mesh, beside it in device memory; released with the mesh and by a
   // keep / filter (the mesh they labelled is gone then).  n / largest: components and the largest one's triangles of that labelling; removed_*: what the
   // last keep / filter of this extract took away.  Everything else a call allocates is gone when it returns.
+  // measure / packed (tsdf_mesh_component_measures): a row per component and the vertices' packed grid coordinates, beside the labels and released with them.
   struct MeshComponents { uint32_t* vertex = nullptr; uint32_t* triangle = nullptr; tsdf_mesh_component* table = nullptr; uint64_t n = 0, largest = 0;
-                          uint64_t removed_vertices = 0, removed_triangles = 0; bool valid = false; } mcomp;
+                          uint64_t removed_vertices = 0, removed_triangles = 0; bool valid = false;
+                          tsdf_mesh_component_measure* measure = nullptr; unsigned long long* packed = nullptr; bool measured = false; } mcomp;
   // mesh streaming (tsdf_mesh_stream): the mesh of every frame, packed, through a ring like the read-out's.  A slot's buffers start with the frame's 64-byte
   // MeshStreamHeader, the payload (packed vertices, then triangles) follows.  Events: header_written (context's stream, behind the header launch: the copy
   // stream's header copy waits for it), emitted (context's stream, behind the emit: the payload copy waits for it), header_ready / ready (copy stream, behind

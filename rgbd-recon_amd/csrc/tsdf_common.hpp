@@ -460,6 +460,14 @@ void launch_mesh_cc_keep_count(hipStream_t st, const uint8_t* keep, const uint32
 void launch_mesh_cc_keep_scatter(hipStream_t st, const uint8_t* keep, const uint32_t* vertex_component, const uint32_t* triangle_component, uint32_t nv, size_t nt,
                                  const unsigned long long* vertex_sums, const unsigned long long* triangle_sums, const MeshArrays& src, const MeshArrays& dst,
                                  uint32_t* new_index);
+// mesh component measures (k_mesh_component_measures.hip, mesh_measure.hpp): rows: n_components entries, ZERO on entry (the caller's memset on the same
+// stream), final on return; packed: nv 64-bit words, written whole.  The caller launches with n_components > 0 (so nv > 0).
+struct MeshMeasureGeometry { float bbox_min[3]; double scale; };
+void launch_mesh_measures(hipStream_t st, const MeshMeasureGeometry& G, const float* pos, const uint32_t* tri, uint32_t nv, size_t nt, const uint32_t* vertex_component,
+                          const uint32_t* triangle_component, uint32_t n_components, unsigned long long* packed, tsdf_mesh_component_measure* rows);
+// keep[c] = the rule holds for component c (rows final)
+void launch_mesh_measure_keep(hipStream_t st, const tsdf_mesh_component_measure* rows, const tsdf_mesh_component* table, uint32_t n_components,
+                              const tsdf_mesh_measure_rule& rule, uint8_t* keep);
 // mesh components of a Z-slab's linked part (k_mesh_slab_components.hip).  tri: the part's nt triangles with global indices from `base` on; nv own
 // vertices, n >= nv the index space with the span into the slab above.  parent (scratch), label: n words; rank: nv words; down_mark, seam_root: nv bytes,
 // zero on entry; each of the four sums: mesh_sc_scan_blocks(of its elements) + 1 64-bit words, the last of them the total.  The caller launches with nv > 0.

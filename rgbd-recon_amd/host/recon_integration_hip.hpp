@@ -281,6 +281,30 @@ class ReconIntegrationHip {
     check(tsdf_mesh_component_stats(m_ctx, s));
     return MeshComponentStats{s[0], s[1], s[2], s[3]};
   }
+  // ---- the islands' measures (tsdf_mesh_component_measures).  The reference has no counterpart.  After meshComponents: meshComponentMeasures computes,
+  // on the device and in exact integers on the measure grid, every component's doubled area, six-fold signed volume, bounds and vertex sum, and returns the
+  // grid (area = area2 * unit^2 / 2, volume = volume6 * unit^3 / 6, position = origin + q * unit); downloadMeshComponentMeasures copies the 80-byte rows;
+  // filterMeshComponentsMeasured keeps the components for which every clause of the rule holds (thresholds in grid integers) and replaces the mesh like
+  // filterMeshComponents.  Labels and measures are gone after a keep / filter.
+  tsdf_mesh_measure_grid meshMeasureGrid() {                               // needs no mesh
+    tsdf_mesh_measure_grid g{};
+    check(tsdf_mesh_measure_grid_info(m_ctx, &g));
+    return g;
+  }
+  tsdf_mesh_measure_grid meshComponentMeasures() {
+    tsdf_mesh_measure_grid g{};
+    check(tsdf_mesh_component_measures(m_ctx, &g));
+    return g;
+  }
+  void downloadMeshComponentMeasures(std::vector<tsdf_mesh_component_measure>& rows) {
+    rows.resize((std::size_t)meshComponentStats().components + 1);         // (never a null pointer)
+    check(tsdf_mesh_download_component_measures(m_ctx, rows.data()));
+    rows.pop_back();
+  }
+  MeshCounts filterMeshComponentsMeasured(const tsdf_mesh_measure_rule& rule) {
+    check(tsdf_mesh_filter_components_measured(m_ctx, &rule, &m_mesh.vertices, &m_mesh.triangles));
+    return m_mesh;
+  }
   // ---- ... of a Z-slab's part (tsdf_mesh_slab_components).  The reference has no counterpart.  Per slab, after meshSlabLink: meshSlabComponents (labels
   // the part alone; the counts of its seam lists) -> meshSlabComponentSeam (the three lists, global indices) -> once, anywhere, mergeMeshComponentSeams
   // over all slabs' lists in slab order (a host function: no context) -> linkMeshSlabComponents(this slab's base and links) ->

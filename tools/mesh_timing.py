@@ -9,6 +9,9 @@ and its mesh bytes.  The top-level entries stay those of the first level named.
 --components: after that, N times extract (every attribute, the first level named) + tsdf_mesh_components, and with --min-triangles M also
 tsdf_mesh_filter_components(M): the record gets a "components" entry with the timers "mesh_components" and "mesh_filter" (each the sum of its call's two
 samples: the host sizes an allocation between them) beside mesh_count / mesh_scan / mesh_emit of the same extracts, and the counts.
+--components --measures: also tsdf_mesh_component_measures after every labelling: "components" gets the timer "mesh_component_measures" (one sample:
+three launches) beside "mesh_components" of the same run, and the largest component's area and volume in SI units.  With --min-extent-m X the filter is
+tsdf_mesh_filter_components_measured(min_extent = ceil(X / unit)) instead of the triangle count's (not both).
 --slabs K: the same volume once more as K Z-slab contexts (recomputed halos) on this one device, each extracting its part of the first level named with
 every attribute (tsdf_mesh_slab_extract / _link): the record gets a "slabs" entry with every slab's "mesh_slab_count" / "_scan" / "_emit" / "_link"
 device time, its counts and its tiles with surface, whether the joined parts equal the whole-volume extract byte for byte, and the slowest slab's time
@@ -28,10 +31,14 @@ STAGES = ("mesh_count", "mesh_scan", "mesh_emit")
 ARGS = sys.argv[1:]
 LEVELS = [int(x) for x in ARGS[ARGS.index("--level") + 1].split(",")] if "--level" in ARGS else [0]
 COMPONENTS = "--components" in ARGS or "--min-triangles" in ARGS
+MEASURES = "--measures" in ARGS or "--min-extent-m" in ARGS
+MIN_EXTENT_M = float(ARGS[ARGS.index("--min-extent-m") + 1]) if "--min-extent-m" in ARGS else None
+assert not MEASURES or COMPONENTS, "--measures goes with --components"
+assert MIN_EXTENT_M is None or "--min-triangles" not in ARGS, "one filter per labelling: --min-triangles or --min-extent-m"
 MIN_TRIANGLES = int(ARGS[ARGS.index("--min-triangles") + 1]) if "--min-triangles" in ARGS else None
 SLABS = int(ARGS[ARGS.index("--slabs") + 1]) if "--slabs" in ARGS else 0
 SLAB_STAGES = ("mesh_slab_count", "mesh_slab_scan", "mesh_slab_emit", "mesh_slab_link")
-OUT = [a for i, a in enumerate(ARGS) if not a.startswith("--") and (i == 0 or ARGS[i - 1] not in ("--level", "--min-triangles", "--slabs"))]
+OUT = [a for i, a in enumerate(ARGS) if not a.startswith("--") and (i == 0 or ARGS[i - 1] not in ("--level", "--min-triangles", "--slabs", "--min-extent-m"))]
 
 scene = rr.scene.make_scene(n_streams=4, width=640, height=480, lut_res=128, inv_res=128)
 ext = scene["bbox_max"] - scene["bbox_min"]
@@ -42,7 +49,7 @@ mv, pr = rr.scene.default_view(*VIEW)
 hip.clearOccupiedBricks(); hip.markBricks(); hip.updateOccupiedBricks(); hip.integrate(); hip.drawF(mv, pr)
 hip.sync()
 hip.enable_timers(True)
-hip.set_timer_filter(list(STAGES) + ["volume_download", "mesh_components", "mesh_filter"])
+hip.set_timer_filter(list(STAGES) + ["volume_download", "mesh_components", "mesh_filter", "mesh_component_measures"])
 rec = dict(shape="c2", res=list(hip.res), streams=4)
 levels = {L: {} for L in LEVELS}
 for label, kw in (("positions", dict(normals=False, colours=False)), ("all_attributes", dict(normals=True, colours=True))):
@@ -80,13 +87,26 @@ rec.update(level=LEVELS[0], vertices=first["vertices"], triangles=first["triangl
 if "--level" in ARGS:
     rec["levels"] = {str(L): levels[L] for L in LEVELS}
 if COMPONENTS:
-    names = STAGES + ("mesh_components",) + (("mesh_filter",) if MIN_TRIANGLES is not None else ())
+    names = STAGES + ("mesh_components",) + (("mesh_component_measures",) if MEASURES else ()) + (("mesh_filter",) if MIN_TRIANGLES is not None or MIN_EXTENT_M is not None else ())
     ms = {s: [] for s in names}
     comp = dict(level=LEVELS[0])
     for it in range(N + 1):                                              # (the first turn is a warm-up)
         hip.extract_mesh(level=LEVELS[0], normals=True, colours=True)
         comp["components"] = hip.mesh_components()
         comp.update(largest_triangles=hip.mesh_component_stats()["largest_triangles"])
+        if MEASURES:
+            grid = hip.mesh_component_measures()
+            if not it:
+                rows, table = hip.mesh_download_component_measures(), hip.mesh_download_components()["table"]
+                big = int(np.argmax(table["n_triangles"]))
+                si = rr.mesh_measures_si(rows, grid, table)
+                comp.update(measure_unit_m=grid["unit"], largest_area_m2=float(si["area"][big]), largest_volume_m3=float(si["volume"][big]),
+                            total_area_m2=float(si["area"].sum()), negative_volume_components=int((si["volume"] < 0).sum()))
+        if MIN_EXTENT_M is not None:
+            rule = hip.mesh_measure_rule(min_extent_m=MIN_EXTENT_M)
+            comp["kept_vertices"], comp["kept_triangles"] = hip.mesh_filter_measured(rule)
+            st = hip.mesh_component_stats()
+            comp.update(min_extent_m=MIN_EXTENT_M, min_extent=int(rule["min_extent"]), vertices_removed=st["vertices_removed"], triangles_removed=st["triangles_removed"])
         if MIN_TRIANGLES is not None:
             comp["kept_vertices"], comp["kept_triangles"] = hip.mesh_filter(MIN_TRIANGLES)
             st = hip.mesh_component_stats()
